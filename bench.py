@@ -8,11 +8,13 @@ the SE(3) update -- exactly the reference's per-iteration loop body (icp_test_ru
 Default workload = BASELINE.json configs[3], the largest single-GPU configuration and the one the metric's roofline is
 quoted on: 1 M x 1 M-point synthetic corridor, runs of 50 ICP iterations, method Ours (Schur detection + PCG).  The steps
 are consecutive iterations of back-to-back 50-iteration runs from the same initial misalignment (a run's first iterations,
-0.87 m off at the corridor ends, cost several times an aligned one: they are part of the workload and of `value`).  The
-timed region of --steps K iterations is repeated (each repeat bracketed by barrier + synchronize, max over ranks) until the
-timed regions hold --min-seconds of work (default 10 s: a monitor sampling the device around the command then sees it busy);
-`value` = all timed steps / all timed time, `ms_per_step` = the same mean, with median / min / max alongside.  No HIP event is
+0.87 m off at the corridor ends, cost several times an aligned one: they are part of the workload and of `value`).  After
+--warmup W iterations, exactly --steps K iterations are timed, as one region bracketed by barrier + synchronize (max over
+ranks); --repeats R times that region R times and --min-seconds S repeats it until S seconds have been timed.  `value` = all
+timed steps / all timed time, `ms_per_step` = the same mean, with median / min / max over the repeats alongside.  No HIP event is
 recorded inside a timed region: `roofline.kernel_us_avg` comes from a separate, untimed pass over whole runs (kernel_pass).
+--dump-outputs DIR writes what the last timed step returned to its caller (step_outputs) as DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 The other BASELINE configs (C1 fixture, C2 100 k cylinder, C3 PK01-like 200 k, C5 = the 5000-trial Monte-Carlo experiment end
 to end) are measured briefly afterwards and reported under "configs", each with its own roofline block.
 
@@ -23,11 +25,12 @@ ICPContext per run, icp_test_runner.cpp:408-409), `configs.c3_pk01_8k_registrati
 dcreg_set_source + run to convergence, the reference's own metric, icp_test_runner.cpp:442-461) and the C5 experiment at 2 / 4 / all host
 threads.
 
---gpus N: one process per GPU (RCCL); when not already under torch.distributed.run the script re-executes itself under it.
+--gpus N: one process per GPU (RCCL); when not already under torch.distributed.run the script runs itself under it as a child process.
 Every rank runs its own scan pair (weak scaling, no data-path collective) = `value`; then the 5000-trial Monte-Carlo experiment
 (BASELINE configs[4]) is run ONCE across all ranks - trials k = rank mod N, the 64-double trial records gathered over RCCL inside the
 timed region, statistics on rank 0 (icp_test_runner.cpp:604-664) - and reported as `configs.c5_montecarlo_5000` (strong scaling).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line: the headline and a few numbers per side leg, at most LINE_BYTES (compact_line); --full-record PATH writes
+the whole record, the side legs' notes, lists and sub-records included, as JSON.
 """
 import argparse
 import json
@@ -48,7 +51,11 @@ MC_TRIALS, MC_SLOTS, MC_SEED = 5000, 256, 2024
 MC_KERNEL_TIMING_STRIDE = 13   # kernel pass of the Monte-Carlo experiment: a HIP-event pair around every 13th batched launch (an event pair costs
                                # ~10 us of host time and the experiment is thousands of launches).  The kernel pass is a SEPARATE, untimed pass:
                                # no launch of the region `value` is computed from carries events (kernel_pass below)
-MIN_SECONDS = 10.0             # the headline's timed regions are repeated until they hold at least this much device work
+LINE_BYTES = 4096              # compact_line: what the JSON line may take.  A reader of the command's output keeps only its last few KB
+                               # (a 30 KB line was left unparsed), so the line stays well below that, failed legs included
+LINE_STRING_CHARS = 32         # compact_line: the longest text of the roofline blocks the line carries (the prose goes to --full-record)
+LINE_ERROR_CHARS = 80          # compact_line: the first characters of a failed leg's error (the whole text goes to --full-record)
+LINE_LEG_KEYS = ("value", "ms_per_step", "ms_total", "iterations_per_s")   # what the line carries of a leg beside the headline
 
 # name: scene, points, radius, iterations per ICP run, weight-derivative Jacobian, BASELINE config
 WORKLOADS = {
@@ -92,11 +99,18 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps iterations is repeated this many times (0 = as often as "
-                                                             "--min-seconds asks)")
-    ap.add_argument("--min-seconds", type=float, default=MIN_SECONDS,
+    ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps iterations is repeated this many times (0 = once, or as "
+                                                             "often as --min-seconds asks)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="headline only: repeat the timed region until at least this many seconds of it have been timed, so that a sampling "
-                         "monitor around the command sees the device busy (each repeat is still exactly --steps steps between two fences)")
+                         "monitor around the command sees the device busy (each repeat is still exactly --steps steps between two fences); "
+                         "0 (default) = --steps steps are timed, no more")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller (pose, covariance, run state; the "
+                         "Monte-Carlo workload: the experiment's statistics) as DIR/<name>.npy in float64")
+    ap.add_argument("--full-record", metavar="PATH", default=None,
+                    help="also write the whole record as JSON to PATH: the JSON line carries the headline and only a few numbers per side "
+                         "leg")
     ap.add_argument("--workload", default="c4_corridor_1m", choices=list(WORKLOADS))
     ap.add_argument("--method", default="Ours")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -124,7 +138,8 @@ def parse_args(argv=None):
 
 
 def maybe_spawn(args):
-    """`python bench.py --gpus N` with N > 1 outside a launcher: re-execute under torch.distributed.run, one rank per GPU.
+    """`python bench.py --gpus N` with N > 1 outside a launcher: run the job under torch.distributed.run, one rank per GPU, as a child
+    process, and exit with its status.
     Refuses (non-zero exit) when fewer than N devices are visible instead of reporting a smaller job as N GPUs."""
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is not None:
@@ -135,8 +150,10 @@ def maybe_spawn(args):
         return
     shared = os.environ.get("DCREG_BENCH_BACKEND", "nccl") != "nccl"      # test hook: all ranks on one device over gloo
     if not shared and not os.environ.get("DCREG_BENCH_DRYRUN"):
-        import torch
-        have = torch.cuda.device_count()
+        # counted in a child of its own: this process starts the ranks and must not have brought up the HIP runtime itself
+        import subprocess
+        p = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True)
+        have = int(p.stdout.strip() or 0) if p.returncode == 0 else 0
         if have < args.gpus:
             sys.exit("bench.py: --gpus %d requested but only %d HIP device(s) visible; not running a smaller job under that name" % (args.gpus, have))
     s = socket.socket()
@@ -148,7 +165,9 @@ def maybe_spawn(args):
     # torch.distributed.run pins OMP_NUM_THREADS=1 unless told otherwise; the Monte-Carlo path solves its 6x6 systems with OpenMP
     from dcreg_amd import hostinfo
     os.environ.setdefault("OMP_NUM_THREADS", str(hostinfo.threads_per_rank(args.gpus)))
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.run(cmd).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 class Dist:
@@ -223,6 +242,8 @@ class Pair:
         self.tgt, src = make_pair(w["scene"], w["n"], seed)
         self.n_src_total = len(src)
         self.reducer, self.native = None, False
+        self.last = None      # the IcpResult of the latest dcreg_icp_run* call (step_outputs).  It is self.res or the sharded call's result, which
+                              # the next call overwrites: measure() copies it out right after the timed steps, before any other pass runs
         if self.by_points:                                        # points: the same pair everywhere, this rank's slice
             from dcreg_amd import pointshard
             lo, hi = pointshard.slice_of(len(src), D.rank, D.world)
@@ -287,6 +308,7 @@ class Pair:
                 it, st = out.iterations, out.status
                 self.R[:] = out.R[:]; self.t[:] = out.t[:]
                 self.res.R[:] = out.R[:]; self.res.t[:] = out.t[:]
+                self.last = out
             else:
                 rc = L.dcreg_icp_run(self.ctx._h, self.R.ctypes.data_as(self.dp), self.t.ctypes.data_as(self.dp), api.DETECTION[self.det],
                                      api.HANDLING[self.hand], C.byref(self.cfg), None, 0, C.byref(self.res))
@@ -294,6 +316,7 @@ class Pair:
                     raise RuntimeError("dcreg_icp_run failed: rc=%d %s" % (rc, L.dcreg_last_error(self.ctx._h)))
                 it, st = self.res.iterations, self.res.status
                 self.R[:] = self.res.R[:]; self.t[:] = self.res.t[:]
+                self.last = self.res
             if it != n or st != 0:
                 raise RuntimeError("%s: run stopped early: iterations=%d of %d status=%d" % (self.name, it, n, st))
             self.pos += n
@@ -360,7 +383,8 @@ def measure(P, D, steps, warmup, repeats, min_seconds=0.0, kernel_steps=None):
     """warm-up, then `repeats` timed regions of exactly `steps` steps, each bracketed by the fence; times are max-over-ranks.  min_seconds > 0:
     the region is repeated until the timed regions add up to that much (all ranks take the count from rank 0's calibration).  No HIP event is
     recorded inside a timed region; the kernel time comes from kernel_pass afterwards.
-    Returns dict(times=[s per block], kernel_us, iters_per_step, points_per_launch, poses_per_launch)."""
+    Returns dict(times=[s per block], outputs (step_outputs after the last timed step), kernel_us, iters_per_step, points_per_launch,
+    poses_per_launch)."""
     P.run_steps(warmup)
     P.ctx.set_option("time_kernels", 0)
     mc0 = P.mc_iters
@@ -384,11 +408,29 @@ def measure(P, D, steps, warmup, repeats, min_seconds=0.0, kernel_steps=None):
             one()
     finally:
         gc.enable()
+    outputs = step_outputs(P)             # (before kernel_pass: it restarts the pair and steps on)
     per_step = (P.mc_iters - mc0) / float(steps * len(times)) if P.mc else 1.0
     run_len = P.w["run_len"]
     kp = kernel_pass(P, kernel_steps if kernel_steps is not None else (1 if P.mc else 3 * run_len))
-    return {"times": times, "kernel_us": kp["kernel_us"], "kernel_source": kp["source"], "iters_per_step": per_step,
+    return {"times": times, "outputs": outputs, "kernel_us": kp["kernel_us"], "kernel_source": kp["source"], "iters_per_step": per_step,
             "points_per_launch": kp["points_per_launch"], "poses_per_launch": kp["poses_per_launch"]}
+
+
+def step_outputs(P):
+    """What the caller of the timed path received from its latest step, as float64 arrays: the pose, covariance and run state of the
+    IcpResult the last dcreg_icp_run* call returned, or for the Monte-Carlo workload the statistics of the last experiment.  Wall times
+    (IcpResult.time_ms, the statistics' *_time_ms) are measurements, not results, and are left out.  A few hundred bytes in all."""
+    if P.mc:
+        return {"montecarlo_" + k: np.float64(v) for k, v in (P.mc_stats or {}).items() if not k.endswith("time_ms")}
+    r = P.last
+    return {"R": np.array(r.R[:]).reshape(3, 3), "t": np.array(r.t[:]), "icp_cov": np.array(r.icp_cov[:]).reshape(6, 6),
+            "converged": np.float64(r.converged), "iterations": np.float64(r.iterations), "status": np.float64(r.status)}
+
+
+def write_outputs(out_dir, outputs):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def roofline_blocks(name, n_queries_per_launch, kern_us, kern_source=None):
@@ -784,6 +826,29 @@ def dry_run(args, D):
     D.close()
 
 
+def compact_line(result):
+    """The JSON line, at most LINE_BYTES: the headline in full except the prose of its roofline blocks; of every leg beside it the few
+    numbers of LINE_LEG_KEYS; a failed leg only under side_leg_errors, its error cut to LINE_ERROR_CHARS.  Regime blocks, sub-records,
+    notes and whole error texts are left to --full-record."""
+    legs = ("roofline_by_regime", "converged_run", "cold_run", "concurrent_pairs", "cpu_baseline", "configs")
+    line = {k: v for k, v in result.items() if k not in legs}
+    for k in ("roofline", "roofline_valu_issue"):
+        if k in line:
+            line[k] = {kk: v for kk, v in line[k].items() if not (isinstance(v, str) and len(v) > LINE_STRING_CHARS)}
+    if "side_leg_errors" in line:
+        line["side_leg_errors"] = {k: v[:LINE_ERROR_CHARS] for k, v in line["side_leg_errors"].items()}
+
+    def numbers(rec):
+        return {k: rec[k] for k in LINE_LEG_KEYS if k in rec}
+
+    for k in ("converged_run", "cold_run", "concurrent_pairs", "cpu_baseline"):
+        if k in result and "error" not in result[k]:
+            line[k] = numbers(result[k])
+    if "configs" in result:
+        line["configs"] = {name: numbers(rec) for name, rec in result["configs"].items() if "error" not in rec}
+    return line
+
+
 def main(argv=None):
     args = parse_args(argv)
     maybe_spawn(args)
@@ -801,6 +866,8 @@ def main(argv=None):
 
     P = Pair(args.workload, D, args, seed=100 + (0 if args.sharding == "points" else D.rank))   # pairs: every rank its own scan pair
     m = measure(P, D, args.steps, args.warmup, args.repeats, min_seconds=args.min_seconds)
+    if args.dump_outputs and D.rank == 0:
+        write_outputs(args.dump_outputs, m["outputs"])
     main_rec = summarize(args.workload, P, D, m, args.steps, n_gpus)
     if args.sub_record:                         # (montecarlo_child's job: the record is all the parent wants)
         main_rec["host_threads_per_rank"] = host_threads
@@ -890,6 +957,8 @@ def main(argv=None):
         D.close()
         if D.rank == 0 and not args.no_configs and args.sharding == "pairs" and not P.mc:
             sub["c5_montecarlo_5000"] = montecarlo_child(args, n_gpus)
+            if "error" in sub["c5_montecarlo_5000"]:
+                side_errors["c5_montecarlo_5000"] = sub["c5_montecarlo_5000"]["error"]
 
     if D.rank == 0:
         result = {
@@ -927,7 +996,10 @@ def main(argv=None):
         if side_errors:
             result["side_leg_errors"] = side_errors
         result["host_threads"] = host_threads
-        print(json.dumps(result), flush=True)
+        if args.full_record:
+            with open(args.full_record, "w") as f:
+                json.dump(result, f)
+        print(json.dumps(compact_line(result)), flush=True)
     if n_gpus == 1:
         P.close()
         D.close()
