@@ -137,6 +137,7 @@ EXPORTS = [
     "dcreg_pose_error", "dcreg_icp_run", "dcreg_icp_run_sharded", "dcreg_icp_run_many", "dcreg_icp_run_euler", "dcreg_icp_run_trials", "dcreg_icp_run_montecarlo", "dcreg_p2p_error", "dcreg_sizeof", "dcreg_version", "dcreg_trial_pose",
     "dcreg_set_host_threads", "dcreg_get_host_threads", "dcreg_comm_unique_id", "dcreg_comm_init", "dcreg_comm_destroy", "dcreg_comm_allgather_sum", "dcreg_icp_run_sharded_rccl",
     "dcreg_montecarlo_job", "dcreg_comm_allgather", "dcreg_comm_info", "dcreg_set_error_message",
+    "dcreg_register_frames", "dcreg_frames_load", "dcreg_frames_reserve_states", "dcreg_frames_reset_state", "dcreg_frames_batch_begin",
 ]
 
 _lib = None
@@ -221,6 +222,13 @@ def load():
     L.dcreg_icp_run_euler.argtypes = [vp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int,
                                       C.POINTER(IcpResult), dp]
     L.dcreg_icp_run_trials.argtypes = [vp, C.c_int, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(TrialResult)]
+    i64p = C.POINTER(C.c_int64)
+    L.dcreg_register_frames.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
+                                        C.POINTER(TrialResult)]
+    L.dcreg_frames_load.argtypes = [vp, C.c_int, fp, i64p, C.c_int64]
+    L.dcreg_frames_reserve_states.argtypes = [vp, C.c_int64]
+    L.dcreg_frames_reset_state.argtypes = [vp, C.c_int64]
+    L.dcreg_frames_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -713,6 +721,32 @@ class Context:
         res = (TrialResult * max(n, 1))()
         self._check(self._L.dcreg_icp_run_trials(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
                     "dcreg_icp_run_trials")
+        return [res[i] for i in range(n)]
+
+    def register_frames(self, frames, T0s, method, cfg, slots=0):
+        """dcreg_register_frames: many frames against this context's map in one call.  frames = a list of [n_i, 3] float32 arrays, or
+        (xyz [N, 3], offsets [n_frames + 1]) with frame f = xyz[offsets[f]:offsets[f + 1]]; T0s = one initial 4x4 pose per frame.  Returns one
+        record per frame, as icp_run_trials does; each is bitwise set_source(frame) + icp_run(T0) on this context."""
+        if isinstance(frames, tuple):
+            xyz, off = frames
+            xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        else:
+            parts = [np.asarray(f, dtype=np.float32).reshape(-1, 3) for f in frames]
+            off = np.zeros(len(parts) + 1, np.int64)
+            off[1:] = np.cumsum([len(f) for f in parts])
+            xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
+        n = len(off) - 1
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if n < 0 or T0s.shape[0] != n:
+            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), 3,
+                                                  _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
+                    "dcreg_register_frames")
         return [res[i] for i in range(n)]
 
     def p2p_error(self, T, error_threshold):

@@ -454,6 +454,16 @@ static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     return DCREG_OK;
 }
 
+// the curve frame of a source cloud (dcreg_set_source; the frames of dcreg_register_frames get exactly the same): key scale of its bounding
+// box, and levels of the curve resolved - log8(n) levels + 4 (a 4096-fold finer grid than one point per cell): 27 key bits for an 8 k-point
+// frame instead of 63, i.e. half the radix passes; points that share the prefix keep their input order (the sort is stable)
+static void curve_frame(int64_t n, const double mn[3], const double mx[3], double &inv_q, int &levels) {
+    const double ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-6});
+    inv_q = 2097151.0 / ext * 0.999999;
+    levels = 4;
+    while (levels < 21 && ((int64_t)1 << (3 * (levels - 4))) < n) ++levels;
+}
+
 static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device) {
     if (!c) return DCREG_E_INVALID;
     if (n <= 0) { c->fail("measure cloud is null or empty"); return DCREG_E_INVALID; }  // icp_test_runner.cpp:1635
@@ -471,8 +481,9 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     }
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("source cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     for (int a = 0; a < 3; ++a) { c->src_mn[a] = mn[a]; c->src_mx[a] = mx[a]; }
-    const double ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-6});
-    const double inv_q = 2097151.0 / ext * 0.999999;
+    double inv_q;
+    int levels;
+    curve_frame(n, mn, mx, inv_q, levels);
     {   // farthest corner of the bounding box: no point is farther from the body-frame origin
         double r2 = 0.0;
         for (int k = 0; k < 3; ++k) { const double m = std::max(std::fabs(mn[k]), std::fabs(mx[k])); r2 += m * m; }
@@ -485,11 +496,7 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (c->opt_keep_source_order) {      // experiments: the caller supplies the processing order
         HIP_TRY(c, hipMemcpyAsync(c->d_src, c->d_src_raw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     } else {
-        // the curve is resolved as far as the cloud can tell cells apart: log8(n) levels + 4 (a 4096-fold finer grid than one point
-        // per cell) - 27 key bits for an 8 k-point frame instead of 63, i.e. half the radix passes; points that share the prefix keep
-        // their input order (the sort is stable)
-        int levels = 4;
-        while (levels < 21 && ((int64_t)1 << (3 * (levels - 4))) < n) ++levels;
+        // the curve is resolved as far as the cloud can tell cells apart (curve_frame)
         // (round 6: ONE workgroup ordering a frame of <= 8192 points in LDS - keys, bitonic sort, gather, a single launch - was built and
         //  measured: 35 us of host time instead of 39, and 120 us of DEVICE time in front of the first linearisation instead of 15; removed)
         hipLaunchKernelGGL(k_curve_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw, n, mn[0], mn[1], mn[2], inv_q, c->opt_curve_x_scale, c->d_mkeys, c->d_vals);
@@ -515,6 +522,83 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     drop_warm(c);
     c->n_batch_states = 0;
     c->last_pose_valid = false;
+    return DCREG_OK;
+}
+
+// The frames of one dcreg_register_frames call (context.hpp FrameSet): checked (offsets, finite coordinates) before anything is queued,
+// uploaded in ONE copy, each frame in its own curve frame (curve_frame of its bounding box, computed on the host as dcreg_set_source does for
+// a frame from a host buffer) - one stable sort over (frame, key prefix) - and gathered so that every frame starts on a query-block boundary.
+// Waits for the stream: the caller's buffer is consumed when this returns.
+static int frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_t *off, int64_t stride) {
+    if (!c) return DCREG_E_INVALID;
+    dcreg_ctx::FrameSet &fs = c->frames;
+    if (n_frames < 0 || (n_frames > 0 && !off) || stride < 3) { c->fail("invalid frame arguments"); return DCREG_E_INVALID; }
+    if (n_frames > 0 && off[0] != 0) { c->fail("frame offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int f = 0; f < n_frames; ++f)
+        if (off[f + 1] < off[f]) { c->fail("frame offsets decrease at frame %d", f); return DCREG_E_INVALID; }
+    const int64_t n = n_frames > 0 ? off[n_frames] : 0;
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    std::vector<FrameBox> box((size_t)std::max(n_frames, 1));
+    std::vector<uint2> slice((size_t)n_frames);
+    std::vector<uint32_t> dst((size_t)std::max(n_frames, 1));
+    int64_t padded = 0, max_points = 0;
+    int max_bits = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t m = off[f + 1] - off[f];
+        if (m >= ((int64_t)1 << 31)) { c->fail("frame %d too large (%lld points)", f, (long long)m); return DCREG_E_INVALID; }
+        dst[(size_t)f] = (uint32_t)padded;
+        slice[(size_t)f] = make_uint2((uint32_t)padded, (uint32_t)m);
+        box[(size_t)f] = FrameBox{0.0, 0.0, 0.0, 1.0, 0ull};
+        if (m > 0) {
+            double mn[3], mx[3];
+            host_bounds(xyz + off[f] * stride, m, stride, mn, mx);
+            for (int a = 0; a < 3; ++a)
+                if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("frame %d has non-finite coordinates", f); return DCREG_E_INVALID; }
+            double inv_q;
+            int levels;
+            curve_frame(m, mn, mx, inv_q, levels);
+            box[(size_t)f] = FrameBox{mn[0], mn[1], mn[2], inv_q, 0ull};
+            if (!c->opt_keep_source_order) { box[(size_t)f].mask = (uint64_t)3 * levels; max_bits = std::max(max_bits, 3 * levels); }    // (bits; made a mask below)
+        }
+        padded += (m + kLinBlock - 1) / kLinBlock * kLinBlock;
+        max_points = std::max(max_points, m);
+        if (padded >= ((int64_t)1 << 31)) { c->fail("the frames of one call hold too many points (%lld)", (long long)padded); return DCREG_E_INVALID; }
+    }
+    int fbits = 0;
+    while (((int64_t)1 << fbits) < (int64_t)n_frames) ++fbits;
+    if (fbits + max_bits > 63) { c->fail("too many frames for one call at these frame sizes (%d key bits); split the call", fbits + max_bits); return DCREG_E_INVALID; }
+    for (int f = 0; f < n_frames; ++f) {        // the frame's prefix bits, below the frame id
+        const int bits = (int)box[(size_t)f].mask;
+        box[(size_t)f].mask = bits > 0 ? (((uint64_t)1 << bits) - 1) << (63 - fbits - bits) : 0ull;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    fs.slice.clear(); fs.max_points = 0; fs.n_states = 0; fs.state_valid.clear();
+    if (n > 0) {
+        if (ensure(c, fs.raw, fs.raw_cap, (size_t)n) || ensure(c, fs.src, fs.src_cap, (size_t)padded) || ensure(c, fs.d_off, fs.off_cap, (size_t)n_frames + 1) ||
+            ensure(c, fs.d_dst, fs.dst_cap, (size_t)n_frames) || ensure(c, fs.d_box, fs.box_cap, (size_t)n_frames) ||
+            ensure(c, c->d_stage, c->stage_cap, (size_t)(n * stride)) ||
+            ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
+            ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+            return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage, xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_off, off, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_dst, dst.data(), sizeof(uint32_t) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_box, box.data(), sizeof(FrameBox) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage, n, stride, fs.raw);
+        const uint32_t *order = nullptr;
+        if (fbits + max_bits > 0) {
+            hipLaunchKernelGGL(k_frame_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw, n, fs.d_off, n_frames, fs.d_box, fbits,
+                               c->opt_curve_x_scale, c->d_mkeys, c->d_vals);
+            const int rc = sort_pairs_u64(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, 63 - fbits - max_bits);
+            if (rc) return rc;
+            order = c->d_vals2;
+        }
+        hipLaunchKernelGGL(k_frame_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw, order, n, fs.d_off, n_frames, fs.d_dst, fs.src);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    fs.slice = std::move(slice);
+    fs.max_points = max_points;
     return DCREG_OK;
 }
 
@@ -668,8 +752,10 @@ static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double 
 
 // gated = true: a single-pose launch whose pose arrives later through the gate (R9, t3 ignored; dcreg_linearize_gate_open /
 // _gate_abort decide its fate)
+// frame_ids != null: pose i linearises frame frame_ids[i] of the frames loaded by dcreg_frames_load instead of the ctx's source, with the
+// frames' own neighbour states (state_ids name those); the ctx's source and states are not touched
 static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
-                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false) {
+                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false, const int32_t *frame_ids = nullptr) {
     if (!c) return DCREG_E_INVALID;
     // a timing probe, not a dump (dcreg_debug.h dcreg_lin_debug::stamps): certificates in use, only the stamps come back
     const bool stamps_only = dbg_host && dbg_host->stamps && !dbg_host->nn_idx && !dbg_host->nn_d2 && !dbg_host->flag && !dbg_host->normal &&
@@ -695,6 +781,16 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (!R9 || !t3 || n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
     if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
     if (c->n_tgt <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
+    dcreg_ctx::FrameSet &fs = c->frames;
+    int64_t n_frame_max = 0;             // frames: points of the largest frame of this launch
+    if (frame_ids) {
+        if (!state_ids || dbg_host || gated) { c->fail("frame launches are batched product launches"); return DCREG_E_INVALID; }
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t f = frame_ids[i];
+            if (f < 0 || (size_t)f >= fs.slice.size() || fs.slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
+            n_frame_max = std::max<int64_t>(n_frame_max, fs.slice[(size_t)f].y);
+        }
+    } else
     if (c->n_src <= 0) { c->fail("measure cloud is not set"); return DCREG_E_STATE; }
     if (c->need_set_device) { HIP_TRY(c, hipSetDevice(c->device)); }     // (before make_lin_args: the Euler branch allocates and copies)
     // which index the launch searches (context.hpp, the window of a large map): single-pose product launches the window around their pose, a
@@ -708,12 +804,13 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     LinArgs a;
     int rc = make_lin_args(c, p, a);
     if (rc) return rc;
+    if (frame_ids) a.count_scale = n_frame_max < ((int64_t)1 << 26) ? kCountScale : 0.0;     // (make_lin_args: of the ctx's own source)
     // the parameters the stored certificates, gate bits and planes depend on (context.hpp StateKey): a launch with other values
     // starts from empty states
     dcreg_ctx::StateKey key;
     key.radius_sq = a.radius_sq; key.max_thick_sq = a.max_thick_sq; key.min_norm = a.min_norm;
     key.radius_sq_f = a.radius_sq_f; key.cert_r_out = a.cert_r_out; key.cert_r_in = a.cert_r_in; key.fast_plane = c->opt_fast_plane ? 1 : 0;
-    const uint32_t nbx = blocks_for(c->n_src, kLinBlock);
+    const uint32_t nbx = blocks_for(frame_ids ? n_frame_max : c->n_src, kLinBlock);
     if (ensure(c, S.d_partials, S.partials_cap, (size_t)n_poses * nbx * kSlots)) return DCREG_E_NOMEM;
     // one pose: the kernels finish the reduction themselves (chunk rows -> pinned memory); many poses: k_finalize
     const uint32_t n_chunks = (nbx + kChunk - 1) / kChunk;
@@ -741,7 +838,8 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         HIP_TRY(c, hipHostGetDevicePointer((void **)&S.d_out, S.h_out, 0));
         S.out_cap = cap;
     }
-    const int64_t n = c->n_src;
+    const int64_t n = frame_ids ? n_frame_max : c->n_src;
+    const float4 *const d_src = frame_ids ? fs.src : c->d_src;
     a.state = nullptr; a.state_stride = 0;
     a.xcd_chunk = (uint32_t)std::max(c->opt_xcd_chunk, 0);
     if (n_poses == 1 && !state_ids && !gated) {
@@ -792,6 +890,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     PoseArg one{};
     one.state = kNoIdx; one.fresh = 1;
     const PoseArg *d_poses = nullptr;
+    const uint2 *d_slices = nullptr;     // frames: {first point, points} of every pose's frame (kernels.hpp k_lin SLICE)
     bool uses_state = false;
     if (n_poses == 1 && !state_ids && c->opt_warm && !(key == c->state_key)) { c->state_valid = false; c->state_key = key; }
     const bool state_was_valid = c->state_valid;
@@ -832,28 +931,33 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             d_poses = c->d_gate_pose;
         }
     } else {
-        // batched poses: each may own one of the reserved states (dcreg_reserve_warm_states); -1 = search cold, keep nothing
-        const bool use_states = state_ids && c->opt_warm && c->n_batch_states > 0;
-        if (use_states && !(key == c->batch_state_key)) {
-            std::fill(c->batch_state_valid.begin(), c->batch_state_valid.end(), (uint8_t)0);
-            c->batch_state_key = key;
+        // batched poses: each may own one of the reserved states (dcreg_reserve_warm_states; frames: dcreg_frames_reserve_states);
+        // -1 = search cold, keep nothing
+        const int64_t n_states = frame_ids ? fs.n_states : c->n_batch_states;
+        std::vector<uint8_t> &state_valid = frame_ids ? fs.state_valid : c->batch_state_valid;
+        dcreg_ctx::StateKey &states_key = frame_ids ? fs.key : c->batch_state_key;
+        const bool use_states = state_ids && c->opt_warm && n_states > 0;
+        if (use_states && !(key == states_key)) {
+            std::fill(state_valid.begin(), state_valid.end(), (uint8_t)0);
+            states_key = key;
         }
         if (state_ids && c->opt_warm) {
-            std::vector<uint8_t> seen((size_t)std::max<int64_t>(c->n_batch_states, 1), 0);
+            std::vector<uint8_t> seen((size_t)std::max<int64_t>(n_states, 1), 0);
             for (int i = 0; i < n_poses; ++i) {
                 const int32_t sid = state_ids[i];
                 if (sid < 0) continue;
-                if ((int64_t)sid >= c->n_batch_states) { c->fail("warm state %d was not reserved (dcreg_reserve_warm_states: %lld)", sid, (long long)c->n_batch_states); return DCREG_E_INVALID; }
+                if ((int64_t)sid >= n_states) { c->fail("warm state %d was not reserved (dcreg_reserve_warm_states: %lld)", sid, (long long)n_states); return DCREG_E_INVALID; }
                 if (seen[(size_t)sid]) { c->fail("warm state %d is used by two poses of one launch", sid); return DCREG_E_INVALID; }
                 seen[(size_t)sid] = 1;
             }
         }
-        const size_t bytes = (size_t)n_poses * sizeof(PoseArg);
+        // (frames: the poses' slices ride behind the poses in the same block - one copy)
+        const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (frame_ids ? (size_t)n_poses * sizeof(uint2) : 0);
         if (bytes > S.poses_cap) {      // the pinned block stays alive until end(): source of the asynchronous copy
             if (S.h_poses) (void)hipHostFree(S.h_poses);
             if (S.d_poses) (void)hipFree(S.d_poses);
             S.h_poses = nullptr; S.d_poses = nullptr; S.poses_cap = 0;
-            const size_t cap = std::max<size_t>(bytes, 256 * sizeof(PoseArg));
+            const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2)));
             HIP_TRY(c, hipHostMalloc((void **)&S.h_poses, cap, hipHostMallocDefault));
             if (hipMalloc((void **)&S.d_poses, cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
             S.poses_cap = cap;
@@ -863,15 +967,21 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             std::memcpy(hp[i].R, R9 + 9 * i, sizeof(one.R)); std::memcpy(hp[i].t, t3 + 3 * i, sizeof(one.t));
             const bool has = use_states && state_ids[i] >= 0;
             hp[i].state = has ? (uint32_t)state_ids[i] : kNoIdx;
-            hp[i].fresh = (has && c->batch_state_valid[(size_t)state_ids[i]] != 0) ? 0u : 1u;
-            if (has) c->batch_state_valid[(size_t)state_ids[i]] = 1;
+            hp[i].fresh = (has && state_valid[(size_t)state_ids[i]] != 0) ? 0u : 1u;
+            if (has) state_valid[(size_t)state_ids[i]] = 1;
+        }
+        if (frame_ids) {
+            uint2 *hs = (uint2 *)(S.h_poses + (size_t)n_poses * sizeof(PoseArg));
+            for (int i = 0; i < n_poses; ++i) hs[i] = fs.slice[(size_t)frame_ids[i]];
+            d_slices = (const uint2 *)(S.d_poses + (size_t)n_poses * sizeof(PoseArg));
         }
         // (measured and dropped, profiles/r05_ablation.md: the upload on a copy stream behind an event - the cross-stream dependency costs
         //  more than the 4.6 us copy it hides, C5 1.56 M against 1.64 M it/s - and no upload at all, the kernel reading the pinned block:
         //  +2.7 us per kernel, nothing gained - the experiment is bound by its kernels, two groups of trials alternating on the device)
         HIP_TRY(c, hipMemcpyAsync(S.d_poses, S.h_poses, bytes, hipMemcpyHostToDevice, c->stream));
         d_poses = (const PoseArg *)S.d_poses;
-        if (use_states) { a.state = c->d_state_batch; a.state_stride = (uint32_t)c->state_batch_stride; }
+        if (use_states && frame_ids) { a.state = fs.state; a.state_stride = (uint32_t)fs.state_stride; }
+        else if (use_states) { a.state = c->d_state_batch; a.state_stride = (uint32_t)c->state_batch_stride; }
     }
     a.use_cert = ((dbg_host && !stamps_only) || !c->opt_use_cert) ? 0 : 1;   // a debug dump searches every point (its statistics are those of the searches)
     a.search_count = c->opt_count_searches ? c->d_search_count : nullptr;
@@ -1017,29 +1127,43 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         const dim3 grid(nbx, (unsigned)n_poses);
 #define DCREG_LAUNCH_LIN(MODE, FUSED, FAST)                                                                                              \
     hipLaunchKernelGGL((k_lin<MODE, FUSED, FAST>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a,  \
-                       S.d_partials, nbx, fin, dd, abort_flag, gt)
+                       S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr)
+#define DCREG_LAUNCH_FRAMES(FUSED, FAST, ONE_)                                                                                           \
+    hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid,       \
+                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, \
+                       abort_flag, gt, d_slices)
+        if (frame_ids) {                   // the frames of dcreg_register_frames: every pose reads its own slice
+            if (one_wave) {
+                if (fast) DCREG_LAUNCH_FRAMES(true, true, true); else DCREG_LAUNCH_FRAMES(true, false, true);
+                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, d_slices);
+            }
+            else if (fused) { if (fast) DCREG_LAUNCH_FRAMES(true, true, false); else DCREG_LAUNCH_FRAMES(true, false, false); }
+            else { if (fast) DCREG_LAUNCH_FRAMES(false, true, false); else DCREG_LAUNCH_FRAMES(false, false, false); }
+        } else
         if (gate_inside && !team) {        // k_lin is the gated kernel (fused, MODE 0: a gated launch is never a dump)
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt);
-            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
         } else
         if (stamps_only) { if (fast) DCREG_LAUNCH_LIN(2, true, true); else DCREG_LAUNCH_LIN(2, true, false); }     // (the probe writes the shared state: same fit as the plain launches)
         else if (dbg_host) { if (fast) DCREG_LAUNCH_LIN(1, true, true); else DCREG_LAUNCH_LIN(1, true, false); }
         else if (one_wave) {               // one-wave blocks: a grid of tiles
             const dim3 tiles(nbx * (kLinBlock / kWave), (unsigned)n_poses);
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt);
-            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt);
-            hipLaunchKernelGGL(k_sum_tiles, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
+            hipLaunchKernelGGL(k_sum_tiles<false>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, nullptr);
         }
         else if (fused) { if (fast) DCREG_LAUNCH_LIN(0, true, true); else DCREG_LAUNCH_LIN(0, true, false); }
         else { if (fast) DCREG_LAUNCH_LIN(0, false, true); else DCREG_LAUNCH_LIN(0, false, false); }
 #undef DCREG_LAUNCH_LIN
+#undef DCREG_LAUNCH_FRAMES
     }
     {   // an invalid launch (bad grid, too many resources) must surface here, not as a spin timeout in end()
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) return bail("linearisation kernel launch", le);
     }
     if (!fused) {
-        hipLaunchKernelGGL(k_finalize, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq);
+        if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, d_slices);
+        else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, (const uint2 *)nullptr);
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) return bail("k_finalize launch", le);
     }
@@ -1333,7 +1457,8 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
                     c->d_mkeys, c->d_mkeys2, c->d_cell_start, c->d_scratch, c->sort_tmp,
                     c->d_nn_idx, c->d_nn_d2, c->d_p2p_part, c->d_aligned, c->d_aux, c->d_aux_cell_start, c->d_state, c->d_state_batch, c->d_search_count, c->d_gap, c->d_ymask, c->d_owner,
                     c->d_adv_counts, c->d_team_stamps, c->roi_store.raw, c->roi_store.sorted, c->roi_store.cell_start, c->roi_store.gap,
-                    c->roi_store.owner, c->roi_store.ymask};
+                    c->roi_store.owner, c->roi_store.ymask, c->frames.raw, c->frames.src, c->frames.d_off, c->frames.d_dst, c->frames.d_box,
+                    c->frames.state};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (LinSlot &S : c->slots) {
         for (void *b : {(void *)S.d_partials, (void *)S.d_poses, (void *)S.d_tickets}) if (b) (void)hipFree(b);
@@ -1471,6 +1596,37 @@ int dcreg_reset_warm_state(dcreg_ctx *c, int64_t state_id) {
     return DCREG_OK;
 }
 int dcreg_linearize_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return linearize_end(c, slot, outs); }
+int dcreg_frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats) {
+    if (c) for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    return frames_load(c, n_frames, xyz, frame_offsets, stride_floats);
+}
+int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) {
+    if (!c) return DCREG_E_INVALID;
+    if (n_states < 0) { c->fail("negative state count"); return DCREG_E_INVALID; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    dcreg_ctx::FrameSet &fs = c->frames;
+    fs.n_states = 0;
+    fs.state_valid.clear();
+    if (n_states == 0 || fs.max_points <= 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t stride = ((size_t)fs.max_points + 63) & ~(size_t)63;       // one stride: the largest frame's
+    if (ensure(c, fs.state, fs.state_cap, kStateRows * stride * (size_t)n_states)) return DCREG_E_NOMEM;
+    fs.state_stride = stride;
+    fs.n_states = n_states;
+    fs.state_valid.assign((size_t)n_states, 0);
+    return DCREG_OK;
+}
+int dcreg_frames_reset_state(dcreg_ctx *c, int64_t state_id) {
+    if (!c) return DCREG_E_INVALID;
+    if (state_id < 0 || state_id >= c->frames.n_states) { c->fail("frame state %lld was not reserved", (long long)state_id); return DCREG_E_INVALID; }
+    c->frames.state_valid[(size_t)state_id] = 0;
+    return DCREG_OK;
+}
+int dcreg_frames_batch_begin(dcreg_ctx *c, int slot, int n, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
+                             const dcreg_lin_params *p) {
+    if (c && (!frame_ids || !state_ids)) { c->fail("null argument"); return DCREG_E_INVALID; }
+    return linearize_begin(c, slot, n, R9, t3, state_ids, p, nullptr, false, frame_ids);
+}
 int dcreg_linearize_gated_begin(dcreg_ctx *c, int slot, const dcreg_lin_params *p) {
     return linearize_begin(c, slot, 1, nullptr, nullptr, nullptr, p, nullptr, true);
 }

@@ -123,6 +123,25 @@ struct dcreg_ctx {
     size_t state_batch_stride = 0;
     int64_t n_batch_states = 0;
     std::vector<uint8_t> batch_state_valid;
+    // The frames of dcreg_register_frames (engine.cpp): many source clouds beside the ctx's own, registered against the same map.  Every
+    // frame in the curve order dcreg_set_source would give it, starting on a query-block boundary; the launches of the call read each
+    // pose's frame through its slice (kernels.hpp k_lin SLICE) and keep their neighbour states here - the ctx's own source, its own state
+    // and its reserved batch states are not touched.
+    struct FrameSet {
+        float4 *raw = nullptr; size_t raw_cap = 0;             // upload order
+        float4 *src = nullptr; size_t src_cap = 0;             // curve order, frame f from point slice[f].x
+        int64_t *d_off = nullptr; size_t off_cap = 0;          // frame f = points [off[f], off[f + 1]) of the upload
+        uint32_t *d_dst = nullptr; size_t dst_cap = 0;         // ... and where it starts in src
+        dcreg::FrameBox *d_box = nullptr; size_t box_cap = 0;
+        std::vector<uint2> slice;                              // per frame: {first point in src, points}
+        int64_t max_points = 0;
+        uint32_t *state = nullptr; size_t state_cap = 0;       // [state][kStateRows][state_stride]
+        size_t state_stride = 0;
+        int64_t n_states = 0;
+        std::vector<uint8_t> state_valid;
+        StateKey key;
+    };
+    FrameSet frames;
     double *h_euler = nullptr, *d_euler = nullptr;     // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
     unsigned long long *d_search_count = nullptr;      // option "count_searches": points searched since the last reset
 

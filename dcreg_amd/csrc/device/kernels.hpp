@@ -232,13 +232,23 @@ __device__ __forceinline__ double block_sum_rows(const double *rows, uint32_t co
 // itself the sum would be the last arrival's, ONE wave with a kilobyte per lane to load: four dependent rounds of loads, 3 us each -
 // measured; here it is one round behind a kernel boundary.)
 // Grid: (chunks of a pose, poses) - batched launches of one-chunk poses (the Monte-Carlo batches) get their pose rows this way.
+// SLICE: every pose has a source slice of its own (k_lin's SLICE, dcreg_register_frames): its chunk holds the frame's OWN block count of rows
+// (n_blocks_x is the row stride: the blocks of the largest frame of the launch)
+template <bool SLICE>
 static __global__ __launch_bounds__(kLinBlock) void k_sum_tiles(const double *__restrict__ tile_rows, uint32_t n_blocks_x, double *__restrict__ out,
-                                                                unsigned long long seq, const uint32_t *__restrict__ abort_flag) {
+                                                                unsigned long long seq, const uint32_t *__restrict__ abort_flag,
+                                                                const uint2 *__restrict__ slices) {
     if (abort_flag && *abort_flag != 0u) return;       // the launch was called off: k_lin wrote no rows, nothing is published
     __shared__ double sm[kLinBlock / 32][kSlots];
     constexpr int G = kLinBlock / 32, T = kLinBlock / 64;
     const uint32_t chunk = blockIdx.x;
-    const uint32_t count = min((uint32_t)kChunk, n_blocks_x - chunk * kChunk);
+    uint32_t count;
+    if constexpr (SLICE) {
+        const uint32_t nb = (slices[blockIdx.y].y + kLinBlock - 1) / kLinBlock;
+        count = nb > chunk * kChunk ? min((uint32_t)kChunk, nb - chunk * kChunk) : 0u;
+    } else {
+        count = min((uint32_t)kChunk, n_blocks_x - chunk * kChunk);
+    }
     const double *rows = tile_rows + ((size_t)blockIdx.y * n_blocks_x + (size_t)chunk * kChunk) * T * kSlots;
     const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
     double x[kChunk / G][T];
@@ -473,13 +483,19 @@ static_assert(kAdvTile % kLinBlock == 0 && kAdvTile <= 65536, "a tile is a whole
 // more from the surface), and a loss where they are short (four times the blocks to dispatch: profiles/r06_ablation.md section 5).  Each
 // block leaves the row of its TILE; k_sum_tiles, queued behind, adds the tile rows in the order block_publish and block_sum_rows add the
 // waves' values and the block rows: the 31 sums are bitwise those of the four-wave launch.
-template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false>
+// SLICE: every pose of a batched launch linearises a source cloud of its own (dcreg_register_frames: many frames against one map) -
+// slices[pose] = {first point in src, points}, the first point on a query-block boundary.  n_blocks_x is then the block count of the
+// launch's largest frame; the blocks past the end of their pose's frame return before anything else, and the reduction (chunk sizes,
+// k_sum_tiles, k_finalize) runs over the frame's own blocks - the additions of the frame's single-pose launch, bit for bit.
+template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false, bool SLICE = false>
 static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
                                                           PoseArg pose1, const PoseArg *__restrict__ poses, LinArgs a,
                                                           double *__restrict__ partials, uint32_t n_blocks_x, FinArgs fin,
-                                                          DebugDev dbg, const uint32_t *__restrict__ abort_flag, GateArgs gt) {
+                                                          DebugDev dbg, const uint32_t *__restrict__ abort_flag, GateArgs gt,
+                                                          const uint2 *__restrict__ slices) {
     if (abort_flag && *abort_flag != 0u) return;       // a gated launch the host called off (uniform: every block returns)
     static_assert(!ONE || (MODE == 0 && FUSED && !GATE), "the one-wave instantiation is the fused product launch behind k_gate");
+    static_assert(!SLICE || (MODE == 0 && !GATE), "per-pose source slices are batched product launches");
     constexpr int kWavesHere = ONE ? 1 : kLinBlock / kWave;
     __shared__ double red[ONE ? 1 : kLinBlock / 32][kSlots];      // (ONE: the Gram matrix lives in the wave's RunList, behind the staging area)
     __shared__ double cnt[kWavesHere][2];
@@ -501,6 +517,13 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
             const uint32_t slot = (vb - lead) / a.group_blocks;
             vb = lead + (uint32_t)a.group_order[slot] * a.group_blocks + (vb - lead) % a.group_blocks;
         }
+    }
+    uint32_t nb_pose = n_blocks_x;                   // query blocks of this pose's cloud
+    if constexpr (SLICE) {                           // (uniform per block: before any state, ticket or row is touched)
+        const uint2 sl = slices[blockIdx.y];
+        nb_pose = (sl.y + kLinBlock - 1) / kLinBlock;
+        if (vb >= nb_pose) return;
+        src += sl.x; n_src = sl.y;
     }
     const uint32_t i = ONE ? vb * kLinBlock + tile * kWave + threadIdx.x : vb * kLinBlock + threadIdx.x;
     auto stamp = [&](int k, unsigned long long v) {       // MODE 2 only (timing probe): one store by lane 0, nothing kept in registers
@@ -707,7 +730,7 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
                      a.count_scale * (double)(w_refit + adv_r));
     if constexpr (MODE == 2) stamp(5, __builtin_readcyclecounter());
     __syncthreads();
-    block_publish<FUSED>(gm0, gm_stride, red, cnt, &s_role, partials + (size_t)pose_id * n_blocks_x * kSlots, vb, n_blocks_x, fin, pose_id);
+    block_publish<FUSED>(gm0, gm_stride, red, cnt, &s_role, partials + (size_t)pose_id * n_blocks_x * kSlots, vb, nb_pose, fin, pose_id);
     }
 }
 
@@ -1223,14 +1246,18 @@ static __global__ __launch_bounds__(kWave) void k_advance_team(const float4 *__r
 // single-pose path (chunk sums, then chunks in index order), so a batched pose is bitwise equal to the same pose
 // linearised alone.  Writes 31 sums + check word to the pinned, host-coherent result row the host spins on (no stream synchronise on
 // the hot path).  out row layout: [0..30] sums, [31] = check word (publish_row).
+// SLICE: the pose's own source slice (k_lin's SLICE): its rows are the frame's own blocks, n_blocks is the row stride
+template <bool SLICE>
 static __global__ __launch_bounds__(kLinBlock) void k_finalize(const double *__restrict__ partials, uint32_t n_blocks, double *__restrict__ out,
-                                                            unsigned long long seq) {
+                                                            unsigned long long seq, const uint2 *__restrict__ slices) {
     __shared__ double sm[kLinBlock / 32][kSlots];
     const uint32_t pose_id = blockIdx.x;
     const double *base = partials + (size_t)pose_id * n_blocks * kSlots;
+    uint32_t nb = n_blocks;
+    if constexpr (SLICE) nb = (slices[pose_id].y + kLinBlock - 1) / kLinBlock;
     double tot = 0.0;
-    for (uint32_t c0 = 0; c0 < n_blocks; c0 += kChunk)
-        tot += block_sum_rows(base + (size_t)c0 * kSlots, min((uint32_t)kChunk, n_blocks - c0), sm);
+    for (uint32_t c0 = 0; c0 < nb; c0 += kChunk)
+        tot += block_sum_rows(base + (size_t)c0 * kSlots, min((uint32_t)kChunk, nb - c0), sm);
     double *orow = out + (size_t)pose_id * kSlots;
     if (threadIdx.x < 32) publish_row(orow, tot, seq);
 }
@@ -1377,6 +1404,42 @@ static __global__ void k_gather4(const float4 *__restrict__ in, const uint32_t *
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = in[order[i]];
+}
+
+// ---- the frames of dcreg_register_frames: many source clouds back to back, each in the curve order dcreg_set_source gives it alone.
+// Frame f = points [off[f], off[f + 1]) of the upload; box[f] = its curve frame (dcreg_set_source's origin, scale and key prefix).  ONE
+// stable sort over (frame, the frame's key prefix) orders every frame as the sort over its prefix alone would, ties in input order.
+struct FrameBox { double ox, oy, oz, inv_q; uint64_t mask; };
+__device__ __forceinline__ uint32_t frame_of(const int64_t *__restrict__ off, int n_frames, int64_t i) {    // off[f] <= i < off[f + 1]
+    int lo = 0, hi = n_frames;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return (uint32_t)lo;
+}
+// key = frame id in the top fbits of the 63 sorted bits, then the frame's curve key with everything below its prefix cleared (mask)
+static __global__ void k_frame_keys(const float4 *__restrict__ p, int64_t n, const int64_t *__restrict__ off, int n_frames, const FrameBox *__restrict__ box,
+                                    int fbits, double x_scale, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = frame_of(off, n_frames, i);
+    const FrameBox b = box[f];
+    const uint64_t ck = curve_key(p[i], b.ox, b.oy, b.oz, b.inv_q, x_scale);
+    keys[i] = (fbits > 0 ? (uint64_t)f << (63 - fbits) : 0ull) | ((ck >> fbits) & b.mask);
+    vals[i] = (uint32_t)i;
+}
+// sorted position i (frame f, since frame ids lead the keys) -> dst[f] + (i - off[f]): every frame starts on a query-block boundary.  w = the
+// point's index within its frame (k_pack gives a cloud of its own that index)
+static __global__ void k_frame_gather(const float4 *__restrict__ in, const uint32_t *__restrict__ order, int64_t n, const int64_t *__restrict__ off,
+                                      int n_frames, const uint32_t *__restrict__ dst, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = frame_of(off, n_frames, i);
+    const uint32_t s = order ? order[i] : (uint32_t)i;
+    float4 v = in[s];
+    v.w = __uint_as_float((uint32_t)((int64_t)s - off[f]));
+    out[dst[f] + (uint32_t)(i - off[f])] = v;
 }
 
 // Heavy groups first.  The blocks of a launch are dispatched in index order and the launch ends when its slowest block does: where the

@@ -259,19 +259,25 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // group iteration is ONE batched launch over its live trials.  A trial that ends (converged, aborted, out of iterations) hands
 // its slot - and the slot's neighbour state, marked empty - to the next trial in line at once, so the batch stays full until the
 // queue runs dry instead of thinning out while its stragglers finish.  Each trial is bitwise the single run of its initial pose.
+// frame_points == null: every trial registers the ctx's own source.  Otherwise trial k registers frame k of the frames dcreg_frames_load
+// put on the device (frame_points[k] points; dcreg_register_frames), with the frames' own neighbour states: a slot that takes the next
+// frame takes its cloud with it, and an empty frame never takes a slot.
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
-                           const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted) {
+                           const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr) {
     const auto t_total = Clock::now();
     const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
     dcreg_index_info_get(ctx, &info);
+    const bool frames = frame_points != nullptr;
+    auto points_of = [&](int64_t k) { return frames ? frame_points[k] : info.n_source; };
     for (int64_t i = 0; i < n_trials; ++i) std::memset(&results[i], 0, sizeof(results[i]));
-    if (info.n_source <= 0 || info.n_target <= 0) {
+    if ((!frames && info.n_source <= 0) || info.n_target <= 0) {
         for (int64_t i = 0; i < n_trials; ++i) results[i].status = 3;
         return DCREG_OK;
     }
     if (cfg->max_iterations <= 0) {
         for (int64_t i = 0; i < n_trials; ++i) {
+            if (points_of(i) <= 0) { results[i].status = 3; continue; }
             dcreg::stateToMatrix(R0 + 9 * i, t0 + 3 * i, results[i].final_transform);
             dcreg::poseError(cfg->gt_matrix, results[i].final_transform, &results[i].trans_error_m, &results[i].rot_error_deg);
         }
@@ -281,18 +287,19 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     n_slots = std::min(n_slots, 2 * 65535);
     const int n_groups = n_slots >= 64 ? 2 : 1;
     // one neighbour state per slot; without the memory for them the trials still run, every launch searching from scratch
-    bool have_states = dcreg_reserve_warm_states(ctx, n_slots) == DCREG_OK;
+    bool have_states = (frames ? dcreg_frames_reserve_states(ctx, n_slots) : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
     struct Slot { int64_t trial = -1; int it = 0; double R[9], t[3]; };
     std::vector<Slot> slot((size_t)n_slots);
-    struct Group { std::vector<int> live; std::vector<int32_t> ids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
+    struct Group { std::vector<int> live; std::vector<int32_t> ids, fids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
     Group grp[2];
     int64_t next_trial = 0;
     auto load = [&](int si) -> bool {                      // next trial in line -> slot si
+        while (next_trial < n_trials && points_of(next_trial) <= 0) results[next_trial++].status = 3;     // an empty frame: nothing to run
         if (next_trial >= n_trials) { slot[(size_t)si].trial = -1; return false; }
         Slot &S = slot[(size_t)si];
         S.trial = next_trial++; S.it = 0;
         std::memcpy(S.R, R0 + 9 * S.trial, sizeof(S.R)); std::memcpy(S.t, t0 + 3 * S.trial, sizeof(S.t));
-        if (have_states) dcreg_reset_warm_state(ctx, si);
+        if (have_states) { if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si); }
         return true;
     };
     for (int si = 0; si < n_slots; ++si) load(si);
@@ -304,13 +311,15 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         for (int si = gi; si < n_slots; si += n_groups) if (slot[(size_t)si].trial >= 0) G.live.push_back(si);
         if (G.live.empty()) return DCREG_OK;
         const int nl = (int)G.live.size();
-        G.Rb.resize((size_t)nl * 9); G.tb.resize((size_t)nl * 3); G.outs.resize((size_t)nl); G.ids.resize((size_t)nl);
+        G.Rb.resize((size_t)nl * 9); G.tb.resize((size_t)nl * 3); G.outs.resize((size_t)nl); G.ids.resize((size_t)nl); G.fids.resize((size_t)nl);
         for (int j = 0; j < nl; ++j) {
             const Slot &S = slot[(size_t)G.live[(size_t)j]];
             G.ids[(size_t)j] = have_states ? (int32_t)G.live[(size_t)j] : -1;
+            G.fids[(size_t)j] = (int32_t)S.trial;
             std::memcpy(&G.Rb[(size_t)j * 9], S.R, sizeof(S.R)); std::memcpy(&G.tb[(size_t)j * 3], S.t, sizeof(S.t));
         }
-        const int rc = dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
+        const int rc = frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
+                              : dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
         G.in_flight = rc == DCREG_OK;
         return rc;
     };
@@ -342,7 +351,7 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
             if (st == 2) { tr.iterations = it; tr.status = 2; continue; }
             tr.iterations = it + 1;
             tr.final_rmse = std::sqrt(lo.sum_r2 / (double)lo.n_eff);
-            tr.final_fitness = (double)lo.n_pt / (double)info.n_source;
+            tr.final_fitness = (double)lo.n_pt / (double)points_of(S.trial);
             tr.corr_num = lo.n_eff;
             std::memcpy(tr.H_upper, lo.H_upper, sizeof(tr.H_upper));
             std::memcpy(tr.degenerate_mask, so.an.degenerate_mask, sizeof(tr.degenerate_mask));
@@ -393,6 +402,25 @@ int dcreg_icp_run_trials(dcreg_ctx *ctx, int n_trials, const double *R0, const d
     if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
     if (n_trials == 0) return DCREG_OK;
     return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0);
+}
+
+int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                          const double *R0, const double *t0, int detection, int handling, const dcreg_config *cfg, int slots,
+                          dcreg_trial_result *results) {
+    if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (n_frames == 0) return DCREG_OK;
+    if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
+    if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
+    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
+    if (rc != DCREG_OK) return rc;
+    std::vector<int64_t> points((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data());
 }
 
 int dcreg_icp_run_montecarlo(dcreg_ctx *ctx, const double base_xyzrpy[6], uint64_t seed, int64_t first_trial, int64_t trial_stride,

@@ -234,6 +234,26 @@ def scene_prior_map(n_map=50_000_000, n_frame=8_000, seed=11, extent=350.0, fram
     return tgt, body.astype(np.float32)
 
 
+def map_frames(tgt, poses, n_frame=8_000, seed=0, frame_range=30.0, noise=0.02):
+    """Frames cut out of an existing map at given sensor poses, with the recipe of the frame of scene_parkinglot / scene_prior_map: for pose
+    T (4x4, sensor -> map), up to n_frame map points within frame_range metres (in x-y) of T's position, expressed in the sensor frame by
+    T^-1 and perturbed by Gaussian range noise.  n_frame may be one number or one per pose.  -> list of [n_i, 3] float32 arrays."""
+    rng = np.random.default_rng(seed)
+    tgt = np.asarray(tgt, np.float32)
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    sizes = np.broadcast_to(np.asarray(n_frame, np.int64), (len(poses),))
+    out = []
+    for T, m in zip(poses, sizes):
+        R, t = T[:3, :3], T[:3, 3]
+        dx, dy = tgt[:, 0] - np.float32(t[0]), tgt[:, 1] - np.float32(t[1])
+        near = np.flatnonzero(dx * dx + dy * dy < np.float32(frame_range * frame_range))
+        sel = rng.choice(near, size=min(int(m), len(near)), replace=False)
+        body = (tgt[sel].astype(np.float64) - t) @ R          # R^T (p - t)
+        body += rng.normal(0, noise, body.shape)
+        out.append(body.astype(np.float32))
+    return out
+
+
 def write_pcd_xyzi(path, xyz):
     """Binary PCD v0.7, fields x y z intensity (float32), like pcl::io::savePCDFileBinary<PointXYZI>."""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)

@@ -339,6 +339,22 @@ typedef struct dcreg_trial_result {
 int dcreg_icp_run_trials(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection,
                          int handling, const dcreg_config *, dcreg_trial_result *results);
 
+/* Many frames registered against the context's map in one call (placing a recorded drive on a prior map from odometry guesses,
+ * multi-LiDAR rigs, loop-closure candidates, relocalisation): frame f = the points [frame_offsets[f], frame_offsets[f + 1]) of xyz
+ * (HOST memory, all frames back to back, stride_floats floats per point, x y z first; frame_offsets holds n_frames + 1 entries, in
+ * points, starting at 0), started from its own pose R0_9[9f..], t0_3[3f..].  The frames are uploaded in one copy and run as
+ * dcreg_icp_run_trials runs trials - `slots` registrations in flight (0 = 256), every iteration of a group of them ONE batched launch in
+ * which each pose reads its own frame - and results[f] is bitwise what dcreg_set_source(frame f) + dcreg_icp_run(R0, t0) give on this
+ * context: final_transform, iterations, converged, status, final_rmse, final_fitness (of the frame's own point count), corr_num, H_upper
+ * and degenerate_mask (time_ms: the call's time over the frames).  trans_error_m / rot_error_deg are taken against cfg->gt_matrix, as for
+ * trials.  Like the other batched launches the frames search the whole map's index (never the window index of dcreg_roi_info: it is
+ * invisible in the results).  An empty frame gets status 3 (as a trial with no source), the others run; n_frames == 0 does nothing.
+ * DCREG_E_INVALID, and nothing runs: offsets that do not start at 0 or decrease, non-finite coordinates in any frame; DCREG_E_STATE: no
+ * target.  The context's own source, its neighbour state and its reserved warm states are left as they were. */
+int dcreg_register_frames(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                          const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
+                          dcreg_trial_result *results);
+
 /* Initial pose of Monte-Carlo trial k (the reference has no RNG: its num_runs loop, icp_test_runner.cpp:339-349, repeats one
  * deterministic run; the seeded perturbation is this build's definition, shared by the runner and dcreg_amd/montecarlo.py):
  * k == 0 -> the base pose; k >= 1 -> base + U(-amp, amp) per degree of freedom from MT19937(low 32 bits of seed + k),

@@ -119,6 +119,17 @@ int dcreg_knn_timed(dcreg_ctx *, const float *q_xyz, int64_t n, int64_t stride_f
  * launches of at most 64 query blocks publish their block rows straight to pinned memory; batched launches of one-chunk poses finish inside
  * the kernel; a start bound counts as loose 1.5 cells beyond the nearest occupied cell; the windows of the two advance passes as above. */
 
+/* internal: the device seam of dcreg_register_frames (engine.cpp).  dcreg_frames_load checks, uploads and orders the frames of one call
+ * (arguments as there; waits for the stream); dcreg_frames_reserve_states / _reset_state are dcreg_reserve_warm_states / dcreg_reset_warm_state
+ * for the frames' own neighbour states (one per slot, sized for the largest frame); dcreg_frames_batch_begin is
+ * dcreg_linearize_batch_begin_warm with pose i linearising frame frame_ids[i] (dcreg_linearize_batch_end collects it).  None of them touches
+ * the context's own source or states. */
+int dcreg_frames_load(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats);
+int dcreg_frames_reserve_states(dcreg_ctx *, int64_t n_states);
+int dcreg_frames_reset_state(dcreg_ctx *, int64_t state_id);
+int dcreg_frames_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                             const int32_t *frame_ids, const dcreg_lin_params *);
+
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */
 void dcreg_set_error_message(dcreg_ctx *, const char *msg);
 
