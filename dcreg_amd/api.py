@@ -262,6 +262,14 @@ def _f64(a, n=None):
     return a
 
 
+def _points(a, what):
+    """a cloud as the C-ABI takes it: 2-D float32, x y z in the first three columns, any further columns skipped through stride_floats"""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype != np.float32 or a.shape[1] < 3:
+        raise ValueError("%s: a 2-D float32 array with at least 3 columns (x y z first) is expected, got %s %s" % (what, a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
 def default_config(**kw):
     cfg = Config()
     load().dcreg_default_config(C.byref(cfg))
@@ -537,10 +545,10 @@ class Context:
         return self._out_dict(out[0])
 
     def knn(self, q, k=5, max_radius=0.0):
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        q = _points(q, "knn")
         idx = np.empty((q.shape[0], k), np.int32)
         d2 = np.empty((q.shape[0], k), np.float32)
-        self._check(self._L.dcreg_knn(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], 3, k, float(max_radius),
+        self._check(self._L.dcreg_knn(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], q.shape[1], k, float(max_radius),
                                       idx.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(C.POINTER(C.c_float))), "dcreg_knn")
         return idx, d2
 
@@ -553,11 +561,11 @@ class Context:
 
     def knn_timed(self, q, k=5, max_radius=0.0, index="grid", repeats=10):
         """exact k-NN on the grid or on the kd-tree comparator -> (idx, d2, kernel ms per launch)"""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3)
+        q = _points(q, "knn_timed")
         idx = np.empty((q.shape[0], k), np.int32)
         d2 = np.empty((q.shape[0], k), np.float32)
         ms = C.c_double()
-        self._check(self._L.dcreg_knn_timed(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], 3, k, float(max_radius),
+        self._check(self._L.dcreg_knn_timed(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], q.shape[1], k, float(max_radius),
                                             {"grid": 0, "kdtree": 1, "grid_sweep": 2}[index], int(repeats), idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                             d2.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ms)), "dcreg_knn_timed")
         return idx, d2, ms.value
@@ -585,7 +593,9 @@ class Context:
         if n <= 0:
             return np.zeros((0, 8), np.uint64)
         st = np.zeros((n + 1, 8), np.uint64)          # the last row: outcome counts (served with slack, layers, wide, rows, list, OUT, no slack, refit)
-        self._L.dcreg_team_pass_stamps(self._h, st.ctypes.data_as(C.POINTER(C.c_uint64)), n + 1)
+        rc = self._L.dcreg_team_pass_stamps(self._h, st.ctypes.data_as(C.POINTER(C.c_uint64)), n + 1)
+        if rc < 0:
+            self._check(rc, "dcreg_team_pass_stamps")
         return st
 
     def roi_info(self):
@@ -724,15 +734,18 @@ class Context:
         return [res[i] for i in range(n)]
 
     def register_frames(self, frames, T0s, method, cfg, slots=0):
-        """dcreg_register_frames: many frames against this context's map in one call.  frames = a list of [n_i, 3] float32 arrays, or
-        (xyz [N, 3], offsets [n_frames + 1]) with frame f = xyz[offsets[f]:offsets[f + 1]]; T0s = one initial 4x4 pose per frame.  Returns one
-        record per frame, as icp_run_trials does; each is bitwise set_source(frame) + icp_run(T0) on this context."""
+        """dcreg_register_frames: many frames against this context's map in one call.  frames = a list of [n_i, c] float32 arrays, or
+        (xyz [N, c], offsets [n_frames + 1]) with frame f = xyz[offsets[f]:offsets[f + 1]] (c >= 3 columns, x y z first: an xyzi array is
+        passed as it is, the rows c floats apart); T0s = one initial 4x4 pose per frame.  Returns one record per frame, as icp_run_trials does;
+        each is bitwise set_source(frame) + icp_run(T0) on this context."""
         if isinstance(frames, tuple):
             xyz, off = frames
-            xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+            xyz = _points(xyz, "register_frames")
             off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
         else:
-            parts = [np.asarray(f, dtype=np.float32).reshape(-1, 3) for f in frames]
+            parts = [_points(f, "register_frames") for f in frames]
+            if len({f.shape[1] for f in parts}) > 1:
+                raise ValueError("register_frames: every frame needs the same number of columns, got %s" % sorted({f.shape[1] for f in parts}))
             off = np.zeros(len(parts) + 1, np.int64)
             off[1:] = np.cumsum([len(f) for f in parts])
             xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
@@ -744,7 +757,7 @@ class Context:
         t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
         det, hand = METHODS[method] if isinstance(method, str) else method
         res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), 3,
+        self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
                                                   _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
                     "dcreg_register_frames")
         return [res[i] for i in range(n)]

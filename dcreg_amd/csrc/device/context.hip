@@ -147,11 +147,14 @@ static double cap_cell_for_budget(double h, const double mn[3], const double mx[
     return h;
 }
 
-static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint32_t *occupied_out) {
+// (box = the cloud's bounds min xyz, max xyz when the caller has them already, else NULL)
+static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr) {
     const int64_t n = d.n;
     if (n <= 0) { c->fail("cloud is empty"); return DCREG_E_INVALID; }
     double mn[3], mx[3];
-    int rc = device_bounds(c, d.raw, n, mn, mx);
+    int rc = DCREG_OK;
+    if (box) for (int a = 0; a < 3; ++a) { mn[a] = box[a]; mx[a] = box[3 + a]; }
+    else rc = device_bounds(c, d.raw, n, mn, mx);
     if (rc) return rc;
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     const double ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-6});
@@ -393,6 +396,14 @@ int build_aux_index(dcreg_ctx *c) {
     return DCREG_OK;
 }
 
+// Entry points that queue work on the stream, wait for it, or free / replace buffers refuse while a linearisation is queued or in flight:
+// behind a gated launch they would wait for a gate nobody can open meanwhile, and a pending launch still reads the clouds and states.
+int refuse_in_flight(dcreg_ctx *c) {
+    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+
 // a frame from a host buffer small enough for the registration path (icp_test_runner.cpp:442-461): staged through pinned memory, bounds on the
 // host, no stream synchronise in dcreg_set_source
 static bool small_host_frame(int64_t n, int64_t stride) { return n <= 65536 && n * stride <= (int64_t)1 << 20; }
@@ -423,6 +434,13 @@ static int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t strid
         HIP_TRY(c, hipMemcpyAsync(c->d_stage, from, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
         if (from == c->h_stage) { HIP_TRY(c, hipEventRecord(c->h_stage_ev, c->stream)); c->h_stage_busy = true; }
         src = c->d_stage;
+    } else if (c->stream == c->own_stream) {
+        // The caller most likely wrote the cloud on the legacy default stream (torch's default stream is that stream: cuda_stream == 0), and
+        // the context's own stream is non-blocking, so nothing orders it after that stream: make it wait for the work queued there so far.
+        // A context given the caller's stream (dcreg_set_stream) is ordered on that stream instead.
+        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
     }
     hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw);
     HIP_TRY(c, hipGetLastError());
@@ -431,16 +449,23 @@ static int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t strid
 
 static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, double radius_hint, bool on_device) {
     if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
     if (n <= 0) { c->fail("target cloud is null or empty"); return DCREG_E_INVALID; }   // icp_test_runner.cpp:1643
     HIP_TRY(c, hipSetDevice(c->device));
+    // packed and checked beside the current map (in the k-NN query buffer): a refused cloud leaves the map as it was
+    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
+    if (rc) return rc;
+    double box[6];
+    rc = device_bounds(c, c->d_aligned, n, box, box + 3);
+    if (rc) return rc;
+    for (int a = 0; a < 6; ++a) if (!std::isfinite(box[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     (void)roi_deactivate(c);             // the new map goes into the whole map's buffers; a window of the old one means nothing
     c->roi_built = false; c->whole_capped = false;
-    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_tgt_raw, c->tgt_raw_cap);
-    if (rc) return rc;
+    std::swap(c->d_tgt_raw, c->d_aligned); std::swap(c->tgt_raw_cap, c->aligned_cap);
     c->n_tgt = n;
     c->radius_hint = radius_hint;
     // the cells are sized for the SEARCH radius (make_lin_args): one ring must cover it
-    rc = build_index(c, target_dst(c), radius_hint * (1.0 + c->opt_cert_margin), &c->occupied_cells);
+    rc = build_index(c, target_dst(c), radius_hint * (1.0 + c->opt_cert_margin), &c->occupied_cells, box);
     if (rc) { c->n_tgt = 0; return rc; }
     c->whole_capped = c->last_build_capped;
     rc = build_gap_field(c, radius_hint * (1.0 + c->opt_cert_margin));
@@ -466,9 +491,11 @@ static void curve_frame(int64_t n, const double mn[3], const double mx[3], doubl
 
 static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device) {
     if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
     if (n <= 0) { c->fail("measure cloud is null or empty"); return DCREG_E_INVALID; }  // icp_test_runner.cpp:1635
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_src_raw, c->src_raw_cap);
+    // packed and checked beside the current source (in the k-NN query buffer): a refused cloud leaves it as it was (dcreg_p2p_error reads it)
+    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
     if (rc) return rc;
     // Hilbert-curve order in the body frame (pose independent: a rigid motion keeps neighbours neighbours)
     double mn[3], mx[3];
@@ -476,10 +503,11 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (small_host) {
         host_bounds(xyz, n, stride, mn, mx);
     } else {
-        rc = device_bounds(c, c->d_src_raw, n, mn, mx);
+        rc = device_bounds(c, c->d_aligned, n, mn, mx);
         if (rc) return rc;
     }
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("source cloud has non-finite coordinates"); return DCREG_E_INVALID; }
+    std::swap(c->d_src_raw, c->d_aligned); std::swap(c->src_raw_cap, c->aligned_cap);
     for (int a = 0; a < 3; ++a) { c->src_mn[a] = mn[a]; c->src_mx[a] = mx[a]; }
     double inv_q;
     int levels;
@@ -1447,6 +1475,7 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
     if (c->h_euler) (void)hipHostFree(c->h_euler);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_stage_ev) (void)hipEventDestroy(c->h_stage_ev);
+    if (c->null_ev) (void)hipEventDestroy(c->null_ev);
     if (c->d_euler) (void)hipFree(c->d_euler);
     if (c->d_gate_pose) (void)hipFree(c->d_gate_pose);
     if (c->d_gate_abort) (void)hipFree(c->d_gate_abort);
@@ -1479,6 +1508,7 @@ void dcreg_set_error_message(dcreg_ctx *c, const char *msg) { if (c && msg) c->f
 
 int dcreg_set_stream(dcreg_ctx *c, void *s) {
     if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
     (void)hipStreamSynchronize(c->stream);
     c->stream = s ? (hipStream_t)s : c->own_stream;
     return DCREG_OK;
@@ -1664,6 +1694,7 @@ int dcreg_linearize_debug(dcreg_ctx *c, const double R[9], const double t[3], co
 
 int dcreg_knn(dcreg_ctx *c, const float *q, int64_t n, int64_t stride, int k, double max_radius, int32_t *idx, float *d2) {
     if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
     if (!q || !idx || !d2 || n < 0 || (k != 1 && k != 5)) { c->fail("invalid k-NN arguments (k must be 1 or 5)"); return DCREG_E_INVALID; }
     (void)roi_deactivate(c);
     if (c->n_tgt <= 0) { c->fail("target index is not set"); return DCREG_E_STATE; }
@@ -1703,6 +1734,7 @@ int dcreg_roi_info(const dcreg_ctx *c, double info[11]) {
 
 int dcreg_launch_stats_get(dcreg_ctx *c, dcreg_launch_stats *st, int reset) {
     if (!c || !st) return DCREG_E_INVALID;
+    if (c->opt_count_searches && c->d_search_count) if (int rc = refuse_in_flight(c)) return rc;    // (the counters are read behind every launch)
     st->launches = c->n_launches; st->poses = c->n_poses_launched; st->points = c->n_points_launched;
     st->points_searched = -1; st->points_team = -1;
     if (c->opt_count_searches && c->d_search_count) {      // synchronous: every launch so far has finished when this returns
@@ -1746,6 +1778,7 @@ int dcreg_team_pass_stamps(dcreg_ctx *c, uint64_t *out, int64_t cap_blocks) {
     if (!c->d_team_stamps || c->team_stamps_n == 0) return 0;
     const int64_t n = std::min<int64_t>(cap_blocks, (int64_t)c->team_stamps_n + 1);      // (+ 1: the outcome histogram behind the blocks)
     if (out && n > 0) {
+        if (int rc = refuse_in_flight(c)) return rc;
         HIP_TRY(c, hipMemcpyAsync(out, c->d_team_stamps, sizeof(unsigned long long) * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }

@@ -151,6 +151,7 @@ struct dcreg_ctx {
     // uploaded from there - the caller's buffer is consumed when dcreg_set_source returns whatever kind of memory it is, without a
     // stream synchronise; h_stage_ev = the upload behind the last use of the block
     float *h_stage = nullptr; size_t h_stage_cap = 0; hipEvent_t h_stage_ev = nullptr; bool h_stage_busy = false;
+    hipEvent_t null_ev = nullptr;          // a cloud in device memory: marks the work queued on the legacy default stream before it is read
     uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_vals = nullptr, *d_vals2 = nullptr;
     size_t keys_cap = 0, keys2_cap = 0, vals_cap = 0, vals2_cap = 0;
     uint64_t *d_mkeys = nullptr, *d_mkeys2 = nullptr; size_t mkeys_cap = 0, mkeys2_cap = 0;
@@ -262,6 +263,7 @@ int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
+int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
 int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, int k, double max_radius, const PoseArg *pose,
                int32_t *d_idx, float *d_d2, bool sweep = false);
 }  // namespace dcreg

@@ -52,6 +52,7 @@ static int reduce_p2p(dcreg_ctx *c, const float *d_d2, int64_t n, double thr, do
 extern "C" int dcreg_p2p_error(dcreg_ctx *c, const double T[16], double error_threshold, double *rmse, double *fitness,
                                double *chamfer, int64_t *valid) {
     if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
     if (!T || !rmse || !fitness || !chamfer || !valid) { c->fail("null argument"); return DCREG_E_INVALID; }
     (void)roi_deactivate(c);              // the metrics are taken on the whole map (context.hpp, the window index)
     if (c->n_tgt <= 0 || c->n_src <= 0) { c->fail("target / source clouds are not set"); return DCREG_E_STATE; }

@@ -107,7 +107,11 @@ typedef struct dcreg_index_info {
 int dcreg_backend_create(dcreg_ctx **out, int device);
 void dcreg_backend_destroy(dcreg_ctx *);
 const char *dcreg_last_error(const dcreg_ctx *);
-/* use an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = ctx-owned stream */
+/* use an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) - every later call is queued on it and so ordered after
+ * what the caller queued there before; NULL = the ctx-owned stream.  torch's DEFAULT stream is the legacy null stream (cuda_stream == 0),
+ * so dcreg_set_stream(ctx, torch.cuda.current_stream().cuda_stream) selects the ctx-owned stream there; that stream is non-blocking, and
+ * dcreg_set_*_device order themselves after the work queued on the null stream instead (below).  Like every call that queues work,
+ * refused (DCREG_E_STATE) while a linearisation is in flight (dcreg_linearize_gated_begin, dcreg_linearize_batch_begin). */
 int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
 /* options (every one of them changes speed only: results are identical whatever their values)
  *   "warm_start"    1 (default) = keep, per source point, the neighbours its last search found and a certificate of how far the
@@ -147,6 +151,11 @@ int dcreg_set_option(dcreg_ctx *, const char *key, double value);
 /* target cloud: copies + builds the device spatial index (stands for kd-tree build, utils.hpp:403).
  * search_radius_hint bounds the cell size (cell <= radius); pass Config::search_radius. */
 int dcreg_set_target(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, double search_radius_hint);
+/* _device: d_xyz is device memory of the ctx's device (x y z first, stride_floats floats per point, 4-byte aligned), read on the ctx's
+ * stream: on a stream given by dcreg_set_stream it is read after the work queued there before the call; on the ctx-owned stream after
+ * the work queued on the legacy null stream before the call (an asynchronous event wait: torch's default stream is that stream).  Work
+ * the caller queued on any other stream must be finished or waited for by the caller.  Consumed when the call returns, as a host buffer.
+ * A refused cloud (null, stride < 3, n <= 0, non-finite coordinates) leaves the ctx's clouds as they were. */
 int dcreg_set_target_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, double search_radius_hint);
 /* source ("measure") cloud: copies, orders along a space-filling curve.  The caller's buffer is consumed when the call returns - it
  * may be reused or freed at once, whatever kind of host memory it is.  A frame of at most 65536 points (and 2^20 floats) is copied
@@ -162,7 +171,11 @@ int dcreg_linearize(dcreg_ctx *, const double R[9], const double t[3], const dcr
 int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *,
                           dcreg_lin_out *outs);
 /* asynchronous pair of the above: _begin queues the copy + kernels on the ctx's stream and returns, _end waits for the
- * results of that slot (pinned-memory sequence numbers) and unpacks them.  Two slots (0, 1) with their own buffers: keep
+ * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
+ * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
+ * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
+ * dcreg_register_frames, the launches, and dcreg_debug.h's dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
+ * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
 int dcreg_linearize_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *);
 /* pipelined single-pose launches (what dcreg_icp_run does between two iterations): _gated_begin queues a linearisation on `slot`
