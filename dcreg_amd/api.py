@@ -138,6 +138,8 @@ EXPORTS = [
     "dcreg_set_host_threads", "dcreg_get_host_threads", "dcreg_comm_unique_id", "dcreg_comm_init", "dcreg_comm_destroy", "dcreg_comm_allgather_sum", "dcreg_icp_run_sharded_rccl",
     "dcreg_montecarlo_job", "dcreg_comm_allgather", "dcreg_comm_info", "dcreg_set_error_message",
     "dcreg_register_frames", "dcreg_frames_load", "dcreg_frames_reserve_states", "dcreg_frames_reset_state", "dcreg_frames_batch_begin",
+    "dcreg_register_pairs", "dcreg_pairs_plan", "dcreg_pairs_sources_load", "dcreg_pairs_build", "dcreg_pairs_reserve_states",
+    "dcreg_pairs_reset_state", "dcreg_pairs_batch_begin",
 ]
 
 _lib = None
@@ -226,6 +228,8 @@ def load():
     L.dcreg_register_frames.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
                                         C.POINTER(TrialResult)]
     L.dcreg_frames_load.argtypes = [vp, C.c_int, fp, i64p, C.c_int64]
+    L.dcreg_register_pairs.argtypes = [vp, C.c_int, fp, i64p, fp, i64p, C.c_int64, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
+                                       C.POINTER(TrialResult)]
     L.dcreg_frames_reserve_states.argtypes = [vp, C.c_int64]
     L.dcreg_frames_reset_state.argtypes = [vp, C.c_int64]
     L.dcreg_frames_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
@@ -760,6 +764,44 @@ class Context:
         self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
                                                   _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
                     "dcreg_register_frames")
+        return [res[i] for i in range(n)]
+
+    def register_pairs(self, sources, targets, T0s, method, cfg, slots=0):
+        """dcreg_register_pairs: many scan pairs in one call, pair p = sources[p] registered against targets[p] from T0s[p].  sources and
+        targets = lists of equal length of [n_i, c] float32 arrays (c >= 3 columns, x y z first, the same c for every cloud: the rows are
+        passed c floats apart); T0s = one initial 4x4 pose per pair.  The targets are indexed for cfg.search_radius.  Needs no map on this
+        context and leaves it as it was.  Returns one record per pair, as icp_run_trials does; each is bitwise set_target(target,
+        cfg.search_radius) + set_source(source) + icp_run(T0) on a context with the same options."""
+        if len(sources) != len(targets):
+            raise ValueError("register_pairs: one target per source: %d sources, %d targets" % (len(sources), len(targets)))
+        src = [_points(f, "register_pairs") for f in sources]
+        tgt = [_points(f, "register_pairs") for f in targets]
+        widths = {f.shape[1] for f in src + tgt}
+        if len(widths) > 1:
+            raise ValueError("register_pairs: every cloud needs the same number of columns, got %s" % sorted(widths))
+        width = widths.pop() if widths else 3
+        n = len(src)
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if T0s.shape[0] != n:
+            raise ValueError("one initial pose per pair: %d pairs, %d poses" % (n, T0s.shape[0]))
+
+        def pack(parts):
+            off = np.zeros(n + 1, np.int64)
+            off[1:] = np.cumsum([len(f) for f in parts])
+            xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, width), np.float32))
+            return xyz, off
+        sxyz, soff = pack(src)
+        txyz, toff = pack(tgt)
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        fp = C.POINTER(C.c_float)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_register_pairs(self._h, n, sxyz.ctypes.data_as(fp), soff.ctypes.data_as(i64p), txyz.ctypes.data_as(fp),
+                                                 toff.ctypes.data_as(i64p), width, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand],
+                                                 C.byref(cfg), int(slots), res),
+                    "dcreg_register_pairs")
         return [res[i] for i in range(n)]
 
     def p2p_error(self, T, error_threshold):

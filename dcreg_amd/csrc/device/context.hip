@@ -59,12 +59,12 @@ static int sort_pairs_u32(dcreg_ctx *c, uint32_t *keys_in, uint32_t *keys_out, u
     HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
     return DCREG_OK;
 }
-// sorts by the bits [lo_bit, 63) of the keys only (stable: equal prefixes keep their order)
-static int sort_pairs_u64(dcreg_ctx *c, uint64_t *keys_in, uint64_t *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int lo_bit = 0) {
+// sorts by the bits [lo_bit, hi_bit) of the keys only (stable: equal prefixes keep their order)
+static int sort_pairs_u64(dcreg_ctx *c, uint64_t *keys_in, uint64_t *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int lo_bit = 0, int hi_bit = 63) {
     size_t tmp = 0;
-    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, 63, c->stream));
+    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, hi_bit, c->stream));
     if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, 63, c->stream));
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, hi_bit, c->stream));
     return DCREG_OK;
 }
 
@@ -557,9 +557,9 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
 // uploaded in ONE copy, each frame in its own curve frame (curve_frame of its bounding box, computed on the host as dcreg_set_source does for
 // a frame from a host buffer) - one stable sort over (frame, key prefix) - and gathered so that every frame starts on a query-block boundary.
 // Waits for the stream: the caller's buffer is consumed when this returns.
-static int frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_t *off, int64_t stride) {
+// (fs: the ctx's frames, or the sources of dcreg_register_pairs)
+static int frames_load(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int n_frames, const float *xyz, const int64_t *off, int64_t stride) {
     if (!c) return DCREG_E_INVALID;
-    dcreg_ctx::FrameSet &fs = c->frames;
     if (n_frames < 0 || (n_frames > 0 && !off) || stride < 3) { c->fail("invalid frame arguments"); return DCREG_E_INVALID; }
     if (n_frames > 0 && off[0] != 0) { c->fail("frame offsets must start at 0"); return DCREG_E_INVALID; }
     for (int f = 0; f < n_frames; ++f)
@@ -630,16 +630,249 @@ static int frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64
     return DCREG_OK;
 }
 
+// the search bound of a launch: searches cover a little more than the gate radius (certificates of "5th neighbour beyond R" spend the
+// difference); candidates with d2 < this are kept
+static float search_bound_sq(const dcreg_ctx *c, double search_radius) {
+    const double rs = search_radius * (1.0 + c->opt_cert_margin), r2 = rs * rs;
+    float rf = (float)r2;
+    if ((double)rf < r2) rf = std::nextafterf(rf, INFINITY);
+    return std::nextafterf(rf, INFINITY);
+}
+// rings of cells of edge h that cover the search bound
+static int rings_for(double h, float radius_sq_f) {
+    int k = 1;
+    while (k < 100000) {
+        const double safe = (double)k * h * (1.0 - 1e-9);
+        if (safe * safe * (1.0 - 1e-6) >= (double)radius_sq_f) break;
+        ++k;
+    }
+    return k;
+}
+
+// ------------------------------------------------------------------------------------------ the targets of dcreg_register_pairs
+// Device bytes a build batch of pair targets may take ("pairs_max_bytes"; 0 = a quarter of the device's free memory), and what a target of
+// m points is counted at: the upload (stride floats a point), raw and sorted points, two key and two value arrays of the sort, and its cell
+// table at the table budget ("pair_max_table_entries": the table is not known before the bounds are)
+static double pairs_budget(dcreg_ctx *c) {
+    if (c->opt_pairs_max_bytes > 0.0) return c->opt_pairs_max_bytes;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 4.0e9; }
+    return 0.25 * (double)free_b;
+}
+static double pair_target_bytes(const dcreg_ctx *c, int64_t m, int64_t stride) {
+    return m > 0 ? (double)m * (4.0 * (double)stride + 16.0 + 16.0 + 16.0 + 8.0) + 4.0 * (double)c->opt_pair_max_table_entries + 16.0 * kPtsPad : 0.0;
+}
+
+// One pass over some targets of the batch (J: batch targets, cells[j]: the geometry of J[j] in this pass): cell keys of all their points
+// in one kernel, ONE sort over (pass target, cell).  occ != null: the occupied cells of every pass target (one readback).  Otherwise the
+// final index: points gathered target after target (kPtsPad zero entries behind each), every cell table and every target's row words.
+static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairCells> &cells, const std::vector<int64_t> &count,
+                      std::vector<uint32_t> *occ, std::vector<int64_t> *tab_first, std::vector<int64_t> *yw_first) {
+    dcreg_ctx::PairSet &ps = c->pairs;
+    const int n_j = (int)J.size();
+    std::vector<int64_t> offs((size_t)3 * (n_j + 1), 0);       // [pass points | table entries | row words] offsets
+    int64_t *po = offs.data(), *to = po + (n_j + 1), *yo = to + (n_j + 1);
+    int64_t max_entries = 1, pts = 0;
+    for (int j = 0; j < n_j; ++j) {
+        const PairCells &g = cells[(size_t)j];
+        const int64_t entries = (int64_t)g.nx * g.sx * g.ny * g.nz;
+        max_entries = std::max(max_entries, entries + 1);
+        po[j + 1] = po[j] + count[(size_t)J[(size_t)j]];
+        to[j + 1] = to[j] + entries + 1;
+        yo[j + 1] = yo[j] + (int64_t)g.nz * g.nxb * g.nyw;
+        cells[(size_t)j].pts_first = pts;
+        pts += count[(size_t)J[(size_t)j]] + kPtsPad;
+    }
+    const int64_t n = po[n_j];
+    int cbits = 1, jbits = 0;
+    while (((int64_t)1 << cbits) < max_entries) ++cbits;
+    while (((int64_t)1 << jbits) < (int64_t)n_j) ++jbits;
+    if (ensure(c, ps.d_off, ps.off_cap, offs.size()) || ensure(c, ps.d_cells, ps.cells_cap, (size_t)n_j) ||
+        ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
+        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+        return DCREG_E_NOMEM;
+    if (!occ && (ensure(c, ps.sorted, ps.sorted_cap, (size_t)pts) || ensure(c, ps.table, ps.table_cap, (size_t)to[n_j]) ||
+                 ensure(c, ps.ymask, ps.ymask_cap, (size_t)std::max<int64_t>(yo[n_j], 1))))
+        return DCREG_E_NOMEM;
+    int64_t *d_po = ps.d_off, *d_to = d_po + (n_j + 1), *d_yo = d_to + (n_j + 1);
+    HIP_TRY(c, hipMemcpyAsync(ps.d_off, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ps.d_cells, cells.data(), sizeof(PairCells) * (size_t)n_j, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw, n, d_po, n_j, ps.d_cells, cbits, c->d_mkeys, c->d_vals);
+    int rc = sort_pairs_u64(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, 0, cbits + jbits);
+    if (rc) return rc;
+    if (occ) {
+        HIP_TRY(c, hipMemsetAsync(ps.d_words, 0, sizeof(uint32_t) * (size_t)n_j, c->stream));
+        hipLaunchKernelGGL(k_pairs_occupancy, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_mkeys2, n, cbits, ps.d_words);
+        occ->assign((size_t)n_j, 0u);
+        HIP_TRY(c, hipMemcpyAsync(occ->data(), ps.d_words, sizeof(uint32_t) * (size_t)n_j, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw, c->d_vals2, n, d_po, n_j, ps.d_cells, ps.sorted);
+        hipLaunchKernelGGL(k_pairs_pad, dim3((unsigned)n_j), dim3(64), 0, c->stream, d_po, ps.d_cells, ps.sorted);
+        hipLaunchKernelGGL(k_pairs_table, dim3(blocks_for(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2, d_po, d_to, n_j, cbits, ps.table);
+        if (yo[n_j] > 0)
+            hipLaunchKernelGGL(k_pairs_ymask, dim3(blocks_for(yo[n_j], 256)), dim3(256), 0, c->stream, ps.table, d_to, d_yo, n_j, ps.d_cells, ps.ymask);
+        tab_first->assign(to, to + n_j);
+        yw_first->assign(yo, yo + n_j);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the host arrays above are the sources of the copies)
+    HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
+// The targets of one build batch (xyz: HOST memory, target t = points [off[t], off[t + 1]), off[0] = 0), each indexed as dcreg_set_target
+// with radius hint `search_radius` would index it alone - build_index's rules: the radius caps the cell edge, the table budget
+// ("pair_max_table_entries", per target) enlarges it, the density adaptation shrinks it, x sub-cells as far as the budget allows - all of
+// them at once: ONE upload, ONE segmented pack / finiteness / bounds pass and ONE readback, then passes over all targets (ONE sort each):
+// the occupancy at the first cell edge, at most two adaptation passes over the targets that ask for one, the final index.  No gap field and
+// no owners (GridDev::gap = owner = null).  The searches are exact in any cells, so the sums are those of the target's
+// own index.  The synchronises and launches do not grow with the number of targets.  DCREG_E_INVALID: a non-finite coordinate.
+static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *off, int64_t stride, double search_radius) {
+    dcreg_ctx::PairSet &ps = c->pairs;
+    if (n_t < 0 || !off || stride < 3 || off[0] != 0 || !(search_radius > 0.0)) { c->fail("invalid pair target arguments"); return DCREG_E_INVALID; }
+    ps.n = 0;
+    ps.built.assign((size_t)n_t, 0);
+    const int64_t n = n_t > 0 ? off[n_t] : 0;
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (n >= ((int64_t)1 << 31)) { c->fail("the pair targets of one build batch hold too many points (%lld)", (long long)n); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, ps.d_grids, ps.grids_cap, (size_t)std::max(n_t, 1)) || ensure(c, ps.d_words, ps.words_cap, (size_t)6 * std::max(n_t, 1)) ||
+        ensure(c, ps.d_off, ps.off_cap, (size_t)3 * (n_t + 1)))
+        return DCREG_E_NOMEM;
+    std::vector<PairGrid> grids((size_t)n_t);
+    std::memset(grids.data(), 0, sizeof(PairGrid) * (size_t)n_t);
+    std::vector<int64_t> count((size_t)n_t);
+    for (int t = 0; t < n_t; ++t) count[(size_t)t] = off[t + 1] - off[t];
+    std::vector<uint32_t> words((size_t)6 * n_t);
+    if (n > 0) {
+        if (ensure(c, ps.raw, ps.raw_cap, (size_t)n) || ensure(c, c->d_stage, c->stage_cap, (size_t)(n * stride))) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage, xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ps.d_off, off, sizeof(int64_t) * (size_t)(n_t + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(ps.d_words, 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+        HIP_TRY(c, hipMemsetAsync(ps.d_words + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage, n, stride, ps.d_off, n_t, ps.raw, ps.d_words);
+        HIP_TRY(c, hipMemcpyAsync(words.data(), ps.d_words, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+    }
+    // ---- every target's cell edge, as build_index chooses it
+    struct Plan { double mn[3], mx[3], h_cap, h1, m1, expo; bool adapt; int nx, ny, nz; };
+    std::vector<Plan> plan((size_t)n_t);
+    const double radius_hint = search_radius * (1.0 + c->opt_cert_margin);
+    const double max_cells = (double)c->opt_pair_max_table_entries;
+    auto geom = [](Plan &P, double h) {
+        const double inv_h = 1.0 / h;
+        P.nx = (int)std::floor((P.mx[0] - P.mn[0]) * inv_h) + 1;
+        P.ny = (int)std::floor((P.mx[1] - P.mn[1]) * inv_h) + 1;
+        P.nz = (int)std::floor((P.mx[2] - P.mn[2]) * inv_h) + 1;
+    };
+    auto cells_of = [&](int t, double h, int sx) {
+        Plan &P = plan[(size_t)t];
+        geom(P, h);
+        PairCells g{};
+        g.ox = P.mn[0]; g.oy = P.mn[1]; g.oz = P.mn[2]; g.inv_h = 1.0 / h;
+        g.nx = P.nx; g.ny = P.ny; g.nz = P.nz; g.sx = sx;
+        g.raw_first = off[t];
+        g.nxb = (g.nx + 15) >> 4; g.nyw = (g.ny + 31) >> 5;
+        return g;
+    };
+    std::vector<int> J;
+    std::vector<PairCells> cells;
+    for (int t = 0; t < n_t; ++t) {
+        const int64_t m = count[(size_t)t];
+        if (m <= 0) continue;
+        Plan &P = plan[(size_t)t];
+        for (int a = 0; a < 3; ++a) { P.mn[a] = ord2f(words[(size_t)3 * t + a]); P.mx[a] = ord2f(words[(size_t)3 * n_t + 3 * t + a]); }
+        for (int a = 0; a < 3; ++a) if (!std::isfinite(P.mn[a]) || !std::isfinite(P.mx[a])) { c->fail("pair target %d has non-finite coordinates", t); return DCREG_E_INVALID; }
+        const double ext = std::max({P.mx[0] - P.mn[0], P.mx[1] - P.mn[1], P.mx[2] - P.mn[2], 1e-6});
+        P.h_cap = radius_hint > 0.0 ? radius_hint * 1.00001 : ext / std::cbrt((double)m) * 4.0;
+        P.h1 = cap_cell_for_budget(c->opt_cell > 0.0 ? c->opt_cell : P.h_cap, P.mn, P.mx, max_cells);
+        P.expo = 2.0; P.adapt = c->opt_cell <= 0.0;
+        J.push_back(t);
+        cells.push_back(cells_of(t, P.h1, 1));
+    }
+    std::vector<uint32_t> occ;
+    int rc = DCREG_OK;
+    if (!J.empty() && c->opt_cell <= 0.0) {
+        // density-adaptive cells (build_index): the occupancy at the first edge, then up to two passes over the targets that ask for one
+        rc = pairs_pass(c, J, cells, count, &occ, nullptr, nullptr);
+        if (rc) return rc;
+        const double target_occ = 1.59 * c->opt_cell_factor * c->opt_cell_factor;
+        std::vector<double> h2s;
+        for (size_t j = 0; j < J.size(); ++j) { Plan &P = plan[(size_t)J[j]]; P.m1 = (double)count[(size_t)J[j]] / std::max<uint32_t>(occ[j], 1u); }
+        for (int pass = 0; pass < 2; ++pass) {
+            std::vector<int> K;
+            cells.clear(); h2s.clear();
+            for (int t : J) {
+                Plan &P = plan[(size_t)t];
+                if (!P.adapt || !(P.m1 > target_occ * 1.3)) { P.adapt = false; continue; }
+                double h2 = P.h1 * std::pow(target_occ / P.m1, 1.0 / P.expo);
+                h2 = std::max(h2, P.h_cap / 64.0);
+                h2 = cap_cell_for_budget(h2, P.mn, P.mx, max_cells);
+                if (h2 >= P.h1 * 0.95) { P.adapt = false; continue; }
+                K.push_back(t); h2s.push_back(h2);
+                cells.push_back(cells_of(t, h2, 1));
+            }
+            if (K.empty()) break;
+            rc = pairs_pass(c, K, cells, count, &occ, nullptr, nullptr);
+            if (rc) return rc;
+            for (size_t k = 0; k < K.size(); ++k) {
+                Plan &P = plan[(size_t)K[k]];
+                const double h2 = h2s[k], m2 = (double)count[(size_t)K[k]] / std::max<uint32_t>(occ[k], 1u);
+                if (m2 < P.m1 && h2 < P.h1) P.expo = std::min(3.0, std::max(1.0, std::log(P.m1 / m2) / std::log(P.h1 / h2)));
+                P.h1 = h2; P.m1 = m2;
+            }
+        }
+    }
+    // ---- the final index: the settled edge, x cut into sub-cells as far as the table budget allows
+    cells.clear();
+    for (int t : J) {
+        Plan &P = plan[(size_t)t];
+        geom(P, P.h1);
+        int sx = c->opt_x_subdiv;
+        while (sx > 1 && (double)P.nx * sx * P.ny * P.nz > max_cells) sx >>= 1;
+        cells.push_back(cells_of(t, P.h1, sx));
+    }
+    const float bound = search_bound_sq(c, search_radius);
+    if (!J.empty()) {
+        std::vector<int64_t> tab_first, yw_first;
+        rc = pairs_pass(c, J, cells, count, nullptr, &tab_first, &yw_first);
+        if (rc) return rc;
+        for (size_t j = 0; j < J.size(); ++j) {
+            const int t = J[j];
+            const PairCells &q = cells[j];
+            const double h = plan[(size_t)t].h1;
+            GridDev &g = grids[(size_t)t].g;
+            g.h = h; g.inv_h = q.inv_h;
+            g.ox = q.ox; g.oy = q.oy; g.oz = q.oz;
+            g.nx = q.nx; g.ny = q.ny; g.nz = q.nz; g.sx = q.sx;
+            g.n_pts = (uint32_t)count[(size_t)t];
+            g.cell_start = ps.table + tab_first[j];
+            g.pts = ps.sorted + q.pts_first;
+            g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
+            g.ymask = ps.ymask + yw_first[j]; g.nxb = q.nxb; g.nyw = q.nyw;
+            grids[(size_t)t].max_ring = rings_for(h, bound);
+            grids[(size_t)t].infl_max_d2 = (float)(4.0 * h * h);
+            ps.built[(size_t)t] = 1;
+        }
+    }
+    if (n_t > 0) {
+        HIP_TRY(c, hipMemcpyAsync(ps.d_grids, grids.data(), sizeof(PairGrid) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+    }
+    ps.n = n_t;
+    ps.radius_sq_f = bound;
+    return DCREG_OK;
+}
+
 // ------------------------------------------------------------------------------------------ linearise
-static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a) {
+// own_grid = false: the launch searches grids of its own (dcreg_register_pairs: LinArgs::max_ring and infl_max_d2 come with every pose's grid)
+static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bool own_grid = true) {
     if (!p || !(p->search_radius > 0.0)) { c->fail("invalid linearisation parameters"); return DCREG_E_INVALID; }
     if (p->k != 5 && p->k != 0) { c->fail("only k = 5 is supported (icp_test_runner.cpp:1722)"); return DCREG_E_INVALID; }
     a.radius_sq = p->search_radius * p->search_radius;
-    {   // searches cover a little more than the gate radius (certificates of "5th neighbour beyond R" spend the difference)
-        const double rs = p->search_radius * (1.0 + c->opt_cert_margin), r2 = rs * rs;
-        float rf = (float)r2;
-        if ((double)rf < r2) rf = std::nextafterf(rf, INFINITY);
-        a.radius_sq_f = std::nextafterf(rf, INFINITY);   // candidates with d2 < this are kept
+    {
+        a.radius_sq_f = search_bound_sq(c, p->search_radius);
         float ro = (float)(p->search_radius * (1.0 + 1e-5));
         if ((double)ro < p->search_radius * (1.0 + 1e-5)) ro = std::nextafterf(ro, INFINITY);
         a.cert_r_out = ro;
@@ -653,15 +886,9 @@ static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a) {
     a.team_max = std::min(std::max(c->opt_team_max, 0), kTeamMax);
     a.far_loose = (float)c->opt_far_loose;
     a.prune_infl = (float)((1.0 + c->opt_cert_inflate) * (1.0 + c->opt_cert_inflate));
-    a.infl_max_d2 = (float)(4.0 * c->grid.h * c->grid.h);
-    int k = 1;
-    while (k < 100000) {
-        const double safe = (double)k * c->grid.h * (1.0 - 1e-9);
-        if (safe * safe * (1.0 - 1e-6) >= (double)a.radius_sq_f) break;
-        ++k;
-    }
-    a.max_ring = k;
-    c->last_max_ring = k;
+    a.infl_max_d2 = own_grid ? (float)(4.0 * c->grid.h * c->grid.h) : 0.f;
+    a.max_ring = own_grid ? rings_for(c->grid.h, a.radius_sq_f) : 0;
+    if (own_grid) c->last_max_ring = a.max_ring;
     a.count_scale = c->n_src < ((int64_t)1 << 26) ? kCountScale : 0.0;      // (strictly below: a count of 2^26 would read as one more of the number riding above it)
     a.euler = p->parameterization != DCREG_PARAM_SO3 ? 1 : 0;
     if (p->parameterization != DCREG_PARAM_SO3 && p->parameterization != DCREG_PARAM_EULER && p->parameterization != DCREG_PARAM_EULER_EXACT) { c->fail("unknown parameterization"); return DCREG_E_INVALID; }
@@ -782,8 +1009,11 @@ static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double 
 // _gate_abort decide its fate)
 // frame_ids != null: pose i linearises frame frame_ids[i] of the frames loaded by dcreg_frames_load instead of the ctx's source, with the
 // frames' own neighbour states (state_ids name those); the ctx's source and states are not touched
+// grid_ids != null (with frame_ids): the scan pairs of dcreg_register_pairs - pose i linearises source frame_ids[i] of the pairs' sources
+// against target grid_ids[i] of the pairs' build batch (kernels.hpp k_lin GRIDS); the ctx's target and window index are not touched
 static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
-                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false, const int32_t *frame_ids = nullptr) {
+                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false, const int32_t *frame_ids = nullptr,
+                           const int32_t *grid_ids = nullptr) {
     if (!c) return DCREG_E_INVALID;
     // a timing probe, not a dump (dcreg_debug.h dcreg_lin_debug::stamps): certificates in use, only the stamps come back
     const bool stamps_only = dbg_host && dbg_host->stamps && !dbg_host->nn_idx && !dbg_host->nn_d2 && !dbg_host->flag && !dbg_host->normal &&
@@ -808,9 +1038,18 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (S.pending) { c->fail("slot %d still has a linearisation in flight", slot); return DCREG_E_STATE; }
     if (!R9 || !t3 || n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
     if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
-    if (c->n_tgt <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
-    dcreg_ctx::FrameSet &fs = c->frames;
+    if (!grid_ids && c->n_tgt <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
+    dcreg_ctx::FrameSet &fs = grid_ids ? c->pair_src : c->frames;
     int64_t n_frame_max = 0;             // frames: points of the largest frame of this launch
+    if (grid_ids) {
+        if (!frame_ids) { c->fail("pair launches name a source for every pose"); return DCREG_E_INVALID; }
+        const dcreg_ctx::PairSet &ps = c->pairs;
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t t = grid_ids[i];
+            if (t < 0 || t >= ps.n || !ps.built[(size_t)t]) { c->fail("pair target %d is not built", t); return DCREG_E_INVALID; }
+        }
+        if (!p || search_bound_sq(c, p->search_radius) != ps.radius_sq_f) { c->fail("the pair targets were built for another search radius"); return DCREG_E_INVALID; }
+    }
     if (frame_ids) {
         if (!state_ids || dbg_host || gated) { c->fail("frame launches are batched product launches"); return DCREG_E_INVALID; }
         for (int i = 0; i < n_poses; ++i) {
@@ -823,14 +1062,14 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (c->need_set_device) { HIP_TRY(c, hipSetDevice(c->device)); }     // (before make_lin_args: the Euler branch allocates and copies)
     // which index the launch searches (context.hpp, the window of a large map): single-pose product launches the window around their pose, a
     // gated launch whatever is active (its pose is checked when the gate opens), everything else the whole map
-    if (!gated && (c->roi_active || roi_wanted(c))) {
+    if (!gated && !grid_ids && (c->roi_active || roi_wanted(c))) {
         if (!p) { c->fail("null argument"); return DCREG_E_INVALID; }
         const bool product = n_poses == 1 && !state_ids && (!dbg_host || stamps_only);
         const int rr = product ? roi_ensure(c, R9, t3, p->search_radius) : roi_deactivate(c);
         if (rr) return rr;
     }
     LinArgs a;
-    int rc = make_lin_args(c, p, a);
+    int rc = make_lin_args(c, p, a, grid_ids == nullptr);
     if (rc) return rc;
     if (frame_ids) a.count_scale = n_frame_max < ((int64_t)1 << 26) ? kCountScale : 0.0;     // (make_lin_args: of the ctx's own source)
     // the parameters the stored certificates, gate bits and planes depend on (context.hpp StateKey): a launch with other values
@@ -919,6 +1158,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     one.state = kNoIdx; one.fresh = 1;
     const PoseArg *d_poses = nullptr;
     const uint2 *d_slices = nullptr;     // frames: {first point, points} of every pose's frame (kernels.hpp k_lin SLICE)
+    const uint32_t *d_grid_ids = nullptr;    // pairs: every pose's target grid (kernels.hpp k_lin GRIDS)
     bool uses_state = false;
     if (n_poses == 1 && !state_ids && c->opt_warm && !(key == c->state_key)) { c->state_valid = false; c->state_key = key; }
     const bool state_was_valid = c->state_valid;
@@ -979,13 +1219,14 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
                 seen[(size_t)sid] = 1;
             }
         }
-        // (frames: the poses' slices ride behind the poses in the same block - one copy)
-        const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (frame_ids ? (size_t)n_poses * sizeof(uint2) : 0);
+        // (frames: the poses' slices ride behind the poses in the same block - one copy; pairs: and their target ids behind those)
+        const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (frame_ids ? (size_t)n_poses * sizeof(uint2) : 0) +
+                             (grid_ids ? (size_t)n_poses * sizeof(uint32_t) : 0);
         if (bytes > S.poses_cap) {      // the pinned block stays alive until end(): source of the asynchronous copy
             if (S.h_poses) (void)hipHostFree(S.h_poses);
             if (S.d_poses) (void)hipFree(S.d_poses);
             S.h_poses = nullptr; S.d_poses = nullptr; S.poses_cap = 0;
-            const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2)));
+            const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2) + sizeof(uint32_t)));
             HIP_TRY(c, hipHostMalloc((void **)&S.h_poses, cap, hipHostMallocDefault));
             if (hipMalloc((void **)&S.d_poses, cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
             S.poses_cap = cap;
@@ -1002,6 +1243,11 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             uint2 *hs = (uint2 *)(S.h_poses + (size_t)n_poses * sizeof(PoseArg));
             for (int i = 0; i < n_poses; ++i) hs[i] = fs.slice[(size_t)frame_ids[i]];
             d_slices = (const uint2 *)(S.d_poses + (size_t)n_poses * sizeof(PoseArg));
+        }
+        if (grid_ids) {
+            const size_t at = (size_t)n_poses * (sizeof(PoseArg) + sizeof(uint2));
+            std::memcpy(S.h_poses + at, grid_ids, sizeof(uint32_t) * (size_t)n_poses);
+            d_grid_ids = (const uint32_t *)(S.d_poses + at);
         }
         // (measured and dropped, profiles/r05_ablation.md: the upload on a copy stream behind an event - the cross-stream dependency costs
         //  more than the 4.6 us copy it hides, C5 1.56 M against 1.64 M it/s - and no upload at all, the kernel reading the pinned block:
@@ -1155,11 +1401,23 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         const dim3 grid(nbx, (unsigned)n_poses);
 #define DCREG_LAUNCH_LIN(MODE, FUSED, FAST)                                                                                              \
     hipLaunchKernelGGL((k_lin<MODE, FUSED, FAST>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a,  \
-                       S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr)
+                       S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr)
 #define DCREG_LAUNCH_FRAMES(FUSED, FAST, ONE_)                                                                                           \
     hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid,       \
                        dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, \
-                       abort_flag, gt, d_slices)
+                       abort_flag, gt, d_slices, nullptr, nullptr)
+#define DCREG_LAUNCH_PAIRS(FUSED, FAST, ONE_)                                                                                            \
+    hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid, \
+                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, \
+                       abort_flag, gt, d_slices, c->pairs.d_grids, d_grid_ids)
+        if (grid_ids) {                    // the scan pairs of dcreg_register_pairs: every pose reads its own slice and its own target grid
+            if (one_wave) {
+                if (fast) DCREG_LAUNCH_PAIRS(true, true, true); else DCREG_LAUNCH_PAIRS(true, false, true);
+                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, d_slices);
+            }
+            else if (fused) { if (fast) DCREG_LAUNCH_PAIRS(true, true, false); else DCREG_LAUNCH_PAIRS(true, false, false); }
+            else { if (fast) DCREG_LAUNCH_PAIRS(false, true, false); else DCREG_LAUNCH_PAIRS(false, false, false); }
+        } else
         if (frame_ids) {                   // the frames of dcreg_register_frames: every pose reads its own slice
             if (one_wave) {
                 if (fast) DCREG_LAUNCH_FRAMES(true, true, true); else DCREG_LAUNCH_FRAMES(true, false, true);
@@ -1169,21 +1427,22 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             else { if (fast) DCREG_LAUNCH_FRAMES(false, true, false); else DCREG_LAUNCH_FRAMES(false, false, false); }
         } else
         if (gate_inside && !team) {        // k_lin is the gated kernel (fused, MODE 0: a gated launch is never a dump)
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
         } else
         if (stamps_only) { if (fast) DCREG_LAUNCH_LIN(2, true, true); else DCREG_LAUNCH_LIN(2, true, false); }     // (the probe writes the shared state: same fit as the plain launches)
         else if (dbg_host) { if (fast) DCREG_LAUNCH_LIN(1, true, true); else DCREG_LAUNCH_LIN(1, true, false); }
         else if (one_wave) {               // one-wave blocks: a grid of tiles
             const dim3 tiles(nbx * (kLinBlock / kWave), (unsigned)n_poses);
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
             hipLaunchKernelGGL(k_sum_tiles<false>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, nullptr);
         }
         else if (fused) { if (fast) DCREG_LAUNCH_LIN(0, true, true); else DCREG_LAUNCH_LIN(0, true, false); }
         else { if (fast) DCREG_LAUNCH_LIN(0, false, true); else DCREG_LAUNCH_LIN(0, false, false); }
 #undef DCREG_LAUNCH_LIN
 #undef DCREG_LAUNCH_FRAMES
+#undef DCREG_LAUNCH_PAIRS
     }
     {   // an invalid launch (bad grid, too many resources) must surface here, not as a spin timeout in end()
         const hipError_t le = hipGetLastError();
@@ -1487,7 +1746,8 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
                     c->d_nn_idx, c->d_nn_d2, c->d_p2p_part, c->d_aligned, c->d_aux, c->d_aux_cell_start, c->d_state, c->d_state_batch, c->d_search_count, c->d_gap, c->d_ymask, c->d_owner,
                     c->d_adv_counts, c->d_team_stamps, c->roi_store.raw, c->roi_store.sorted, c->roi_store.cell_start, c->roi_store.gap,
                     c->roi_store.owner, c->roi_store.ymask, c->frames.raw, c->frames.src, c->frames.d_off, c->frames.d_dst, c->frames.d_box,
-                    c->frames.state};
+                    c->frames.state, c->pair_src.raw, c->pair_src.src, c->pair_src.d_off, c->pair_src.d_dst, c->pair_src.d_box, c->pair_src.state,
+                    c->pairs.raw, c->pairs.sorted, c->pairs.table, c->pairs.ymask, c->pairs.d_off, c->pairs.d_cells, c->pairs.d_words, c->pairs.d_grids};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (LinSlot &S : c->slots) {
         for (void *b : {(void *)S.d_partials, (void *)S.d_poses, (void *)S.d_tickets}) if (b) (void)hipFree(b);
@@ -1544,6 +1804,8 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "curve_x_scale") c->opt_curve_x_scale = (v > 0.0 && v <= 1.0) ? v : 1.0;   // next dcreg_set_source: patches of the curve order 1 / v times as long in x
     else if (k == "roi_index") { c->opt_roi_index = (int)std::min(std::max(v, 0.0), 2.0); c->roi_built = false; }   // 0 never, 1 auto, 2 always (next single-pose launch)
     else if (k == "roi_margin") { c->opt_roi_margin = std::min(std::max(v, 0.0), 1.0e6); c->roi_built = false; }
+    else if (k == "pair_max_table_entries") c->opt_pair_max_table_entries = (int64_t)std::min(std::max(v, 4096.0), 2147483648.0);   // per target of dcreg_register_pairs
+    else if (k == "pairs_max_bytes") c->opt_pairs_max_bytes = std::max(v, 0.0);     // device bytes of one build batch of dcreg_register_pairs (0: a quarter of the free memory)
     else if (k == "max_table_entries") c->opt_max_table_entries = (int64_t)std::min(std::max(v, 1048576.0), 2147483648.0);   // next dcreg_set_target
     else if (k == "advance") c->opt_advance = (int)v;            // the advance pass in front of single-pose launches: 0 never, 1 (default) by the host's rule, 2 whenever possible
     else if (k == "one_wave") c->opt_one_wave = (int)v;                  // k_lin in one-wave blocks: 0 never, 1 by the rule (launches of many blocks in which most waves search), 2 wherever possible
@@ -1628,13 +1890,11 @@ int dcreg_reset_warm_state(dcreg_ctx *c, int64_t state_id) {
 int dcreg_linearize_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return linearize_end(c, slot, outs); }
 int dcreg_frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats) {
     if (c) for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
-    return frames_load(c, n_frames, xyz, frame_offsets, stride_floats);
+    return frames_load(c, c->frames, n_frames, xyz, frame_offsets, stride_floats);
 }
-int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) {
-    if (!c) return DCREG_E_INVALID;
+static int frames_reserve_states(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t n_states) {
     if (n_states < 0) { c->fail("negative state count"); return DCREG_E_INVALID; }
     for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
-    dcreg_ctx::FrameSet &fs = c->frames;
     fs.n_states = 0;
     fs.state_valid.clear();
     if (n_states == 0 || fs.max_points <= 0) return DCREG_OK;
@@ -1646,11 +1906,46 @@ int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) {
     fs.state_valid.assign((size_t)n_states, 0);
     return DCREG_OK;
 }
-int dcreg_frames_reset_state(dcreg_ctx *c, int64_t state_id) {
-    if (!c) return DCREG_E_INVALID;
-    if (state_id < 0 || state_id >= c->frames.n_states) { c->fail("frame state %lld was not reserved", (long long)state_id); return DCREG_E_INVALID; }
-    c->frames.state_valid[(size_t)state_id] = 0;
+static int frames_reset_state(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t state_id) {
+    if (state_id < 0 || state_id >= fs.n_states) { c->fail("frame state %lld was not reserved", (long long)state_id); return DCREG_E_INVALID; }
+    fs.state_valid[(size_t)state_id] = 0;
     return DCREG_OK;
+}
+int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) { return c ? frames_reserve_states(c, c->frames, n_states) : DCREG_E_INVALID; }
+int dcreg_frames_reset_state(dcreg_ctx *c, int64_t state_id) { return c ? frames_reset_state(c, c->frames, state_id) : DCREG_E_INVALID; }
+int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
+    if (!c || n_pairs < 0 || !tgt_offsets || !batch_end || !n_batches) return DCREG_E_INVALID;
+    // build batches of pair targets within the byte budget (pairs_budget): at least one pair each, fewer than 2^31 points each
+    const double budget = pairs_budget(c);
+    int nb = 0;
+    double bytes = 0.0;
+    int64_t pts = 0;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int64_t m = tgt_offsets[p + 1] - tgt_offsets[p];
+        const double b = pair_target_bytes(c, m, stride_floats);
+        if (p > 0 && (bytes + b > budget || pts + m >= ((int64_t)1 << 31) - 1)) { batch_end[nb++] = p; bytes = 0.0; pts = 0; }
+        bytes += b; pts += m;
+    }
+    if (n_pairs > 0) batch_end[nb++] = n_pairs;
+    *n_batches = nb;
+    return DCREG_OK;
+}
+int dcreg_pairs_sources_load(dcreg_ctx *c, int n_pairs, const float *xyz, const int64_t *src_offsets, int64_t stride_floats) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    return frames_load(c, c->pair_src, n_pairs, xyz, src_offsets, stride_floats);
+}
+int dcreg_pairs_build(dcreg_ctx *c, int n_targets, const float *xyz, const int64_t *tgt_offsets, int64_t stride_floats, double search_radius) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    return pairs_build(c, n_targets, xyz, tgt_offsets, stride_floats, search_radius);
+}
+int dcreg_pairs_reserve_states(dcreg_ctx *c, int64_t n_states) { return c ? frames_reserve_states(c, c->pair_src, n_states) : DCREG_E_INVALID; }
+int dcreg_pairs_reset_state(dcreg_ctx *c, int64_t state_id) { return c ? frames_reset_state(c, c->pair_src, state_id) : DCREG_E_INVALID; }
+int dcreg_pairs_batch_begin(dcreg_ctx *c, int slot, int n, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *source_ids,
+                            const int32_t *target_ids, const dcreg_lin_params *p) {
+    if (c && (!source_ids || !state_ids || !target_ids)) { c->fail("null argument"); return DCREG_E_INVALID; }
+    return linearize_begin(c, slot, n, R9, t3, state_ids, p, nullptr, false, source_ids, target_ids);
 }
 int dcreg_frames_batch_begin(dcreg_ctx *c, int slot, int n, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
                              const dcreg_lin_params *p) {

@@ -142,6 +142,27 @@ struct dcreg_ctx {
         StateKey key;
     };
     FrameSet frames;
+    // The scan pairs of dcreg_register_pairs (engine.cpp): pair p = source p (a frame of pair_src, loaded as dcreg_register_frames loads its
+    // frames) against target p (a build batch of PairSet: every target indexed on its own, all of them at once - context.hip pairs_build).
+    // The launches of the call read each pose's source slice and target grid (kernels.hpp k_lin SLICE + GRIDS); nothing of the ctx's own
+    // target, source, states, frames or window index is touched.
+    FrameSet pair_src;
+    struct PairSet {
+        float4 *raw = nullptr; size_t raw_cap = 0;             // the batch's targets in upload order (w = index within the own cloud)
+        float4 *sorted = nullptr; size_t sorted_cap = 0;       // cell-sorted, target after target, kPtsPad zero entries behind each
+        uint32_t *table = nullptr; size_t table_cap = 0;       // the cell tables, target after target
+        uint32_t *ymask = nullptr; size_t ymask_cap = 0;       // the row words, target after target
+        int64_t *d_off = nullptr; size_t off_cap = 0;          // [3][n + 1]: a pass's point, table and row-word offsets (kernels.hpp k_pairs_*)
+        dcreg::PairCells *d_cells = nullptr; size_t cells_cap = 0;
+        uint32_t *d_words = nullptr; size_t words_cap = 0;     // bounds of the batch's targets, then occupied cells of a pass
+        dcreg::PairGrid *d_grids = nullptr; size_t grids_cap = 0;   // per target of the batch: what k_lin<.., GRIDS> reads (empty target: n_pts 0)
+        std::vector<uint8_t> built;                            // per target of the batch: it has an index
+        int n = 0;                                             // targets of the batch
+        float radius_sq_f = 0.f;                               // the search bound the grids' rings were counted for (LinArgs::radius_sq_f)
+    };
+    PairSet pairs;
+    int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
+    double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     double *h_euler = nullptr, *d_euler = nullptr;     // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
     unsigned long long *d_search_count = nullptr;      // option "count_searches": points searched since the last reset
 

@@ -170,6 +170,14 @@ struct FinArgs {
                                    //    like single-pose ones - the chunk row IS the pose's result row - instead of a k_finalize launch
 };
 
+// the target index of one scan pair of dcreg_register_pairs (k_lin GRIDS): its grid, the rings that cover the launch's search bound in its
+// cells (LinArgs::max_ring) and the pruning cap sized for its cells (LinArgs::infl_max_d2)
+struct PairGrid {
+    GridDev g;
+    int max_ring;
+    float infl_max_d2;
+};
+
 // Cross-block traffic of the tree uses agent-scope (sc1, write-through / L2-coherent) relaxed atomics plus an explicit
 // s_waitcnt instead of __threadfence(): a release fence on gfx950 is a full L2 write-back (buffer_wbl2), measured at
 // +10 us per launch when every block executes one.
@@ -487,15 +495,24 @@ static_assert(kAdvTile % kLinBlock == 0 && kAdvTile <= 65536, "a tile is a whole
 // slices[pose] = {first point in src, points}, the first point on a query-block boundary.  n_blocks_x is then the block count of the
 // launch's largest frame; the blocks past the end of their pose's frame return before anything else, and the reduction (chunk sizes,
 // k_sum_tiles, k_finalize) runs over the frame's own blocks - the additions of the frame's single-pose launch, bit for bit.
-template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false, bool SLICE = false>
+// GRIDS: every pose also searches a target index of its own (dcreg_register_pairs: many scan pairs, each against its own target) -
+// grids[grid_ids[pose]] holds its grid, the rings that cover the search bound in that grid's cells and the pruning cap sized for them; the
+// block takes them before anything else and runs as a SLICE block against that grid.  Group dispatch order is never used (n_groups = 0).
+template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false, bool SLICE = false, bool GRIDS = false>
 static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
                                                           PoseArg pose1, const PoseArg *__restrict__ poses, LinArgs a,
                                                           double *__restrict__ partials, uint32_t n_blocks_x, FinArgs fin,
                                                           DebugDev dbg, const uint32_t *__restrict__ abort_flag, GateArgs gt,
-                                                          const uint2 *__restrict__ slices) {
+                                                          const uint2 *__restrict__ slices, const PairGrid *__restrict__ grids,
+                                                          const uint32_t *__restrict__ grid_ids) {
     if (abort_flag && *abort_flag != 0u) return;       // a gated launch the host called off (uniform: every block returns)
     static_assert(!ONE || (MODE == 0 && FUSED && !GATE), "the one-wave instantiation is the fused product launch behind k_gate");
     static_assert(!SLICE || (MODE == 0 && !GATE), "per-pose source slices are batched product launches");
+    static_assert(!GRIDS || SLICE, "per-pose target grids come with per-pose source slices");
+    if constexpr (GRIDS) {                           // (uniform per block)
+        const PairGrid &pg = grids[grid_ids[blockIdx.y]];
+        g = pg.g; a.max_ring = pg.max_ring; a.infl_max_d2 = pg.infl_max_d2;
+    }
     constexpr int kWavesHere = ONE ? 1 : kLinBlock / kWave;
     __shared__ double red[ONE ? 1 : kLinBlock / 32][kSlots];      // (ONE: the Gram matrix lives in the wave's RunList, behind the staging area)
     __shared__ double cnt[kWavesHere][2];
@@ -510,8 +527,8 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
     const uint32_t vbt = ONE ? xcd_remap(blockIdx.x, n_blocks_x * (kLinBlock / kWave), a.xcd_chunk * (kLinBlock / kWave)) : 0u;
     uint32_t vb = ONE ? vbt / (kLinBlock / kWave) : xcd_remap(blockIdx.x, n_blocks_x, a.xcd_chunk);
     const uint32_t tile = ONE ? vbt % (kLinBlock / kWave) : (uint32_t)wave;    // the wave's tile of its query block
-    if (a.n_groups) {       // heavy groups first (k_group_cost).  The groups cover the END of the block range: the blocks no group covers
-                            // are the first ones - dispatched first, whatever they cost
+    if (!GRIDS && a.n_groups) {   // heavy groups first (k_group_cost).  The groups cover the END of the block range: the blocks no group covers
+                                  // are the first ones - dispatched first, whatever they cost
         const uint32_t lead = n_blocks_x - a.n_groups * a.group_blocks;
         if (vb >= lead) {
             const uint32_t slot = (vb - lead) / a.group_blocks;
@@ -1581,9 +1598,7 @@ static __global__ void k_gap_dilate(uint8_t *gap, uint32_t *owner, int nx, int n
 }
 
 // row occupancy words of the row sweep (GridDev::ymask): one thread per word, 32 rows y of one (z, 16-cell x block)
-static __global__ void k_ymask(const uint32_t *__restrict__ cell_start, int nx, int ny, int nz, int sx, int nxb, int nyw, uint32_t *__restrict__ ymask) {
-    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= (int64_t)nz * nxb * nyw) return;
+__device__ __forceinline__ uint32_t ymask_word(const uint32_t *__restrict__ cell_start, int nx, int ny, int sx, int nxb, int nyw, int64_t w) {
     const int yw = (int)(w % nyw), xb = (int)((w / nyw) % nxb), z = (int)(w / ((int64_t)nyw * nxb));
     const int xa = xb * 16, xe = min(xa + 16, nx);
     const int64_t nxf = (int64_t)nx * sx;
@@ -1594,7 +1609,122 @@ static __global__ void k_ymask(const uint32_t *__restrict__ cell_start, int nx, 
         const int64_t row = ((int64_t)z * ny + y) * nxf;
         if (cell_start[row + (int64_t)xe * sx] > cell_start[row + (int64_t)xa * sx]) m |= 1u << b;
     }
-    ymask[w] = m;
+    return m;
+}
+static __global__ void k_ymask(const uint32_t *__restrict__ cell_start, int nx, int ny, int nz, int sx, int nxb, int nyw, uint32_t *__restrict__ ymask) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= (int64_t)nz * nxb * nyw) return;
+    ymask[w] = ymask_word(cell_start, nx, ny, sx, nxb, nyw, w);
+}
+
+// ---- the target indices of dcreg_register_pairs (context.hip pairs_build): the targets of a build batch back to back, each indexed as
+// dcreg_set_target indexes a target of its own, all of them at once.  A pass covers some of the batch's targets: pass target j = batch target
+// PairCells::t, its points [pass_off[j], pass_off[j + 1]) of the pass.  Keys are (j, cell) in 64 bits, ONE sort per pass.
+struct PairCells {
+    double ox, oy, oz, inv_h;
+    int nx, ny, nz, sx;
+    int64_t raw_first;              // first point of the target in the batch's upload
+    int64_t pts_first;              // ... in the cell-sorted points (every target is followed by kPtsPad zero entries)
+    int nxb, nyw;                   // row words (GridDev::nxb, nyw)
+};
+// pack the upload (w = the point's index within its OWN cloud, as k_pack gives a cloud of its own) and take every target's bounds:
+// bounds[3 t + a] = min (ordered-uint), bounds[3 n_t + 3 t + a] = max; a non-finite coordinate makes the target's x maximum infinite (k_bounds)
+static __global__ __launch_bounds__(256) void k_pairs_pack(const float *__restrict__ xyz, int64_t n, int64_t stride, const int64_t *__restrict__ off,
+                                                          int n_t, float4 *__restrict__ out, uint32_t *__restrict__ bounds) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    const uint32_t t = live ? frame_of(off, n_t, i) : 0u;
+    float v[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        v[0] = xyz[i * stride]; v[1] = xyz[i * stride + 1]; v[2] = xyz[i * stride + 2];
+        out[i] = make_float4(v[0], v[1], v[2], __uint_as_float((uint32_t)(i - off[t])));
+    }
+    const bool bad = live && (!(fabsf(v[0]) <= 3.4e38f) || !(fabsf(v[1]) <= 3.4e38f) || !(fabsf(v[2]) <= 3.4e38f));
+    const uint32_t t0 = __builtin_amdgcn_readfirstlane(t);
+    const unsigned long long lanes = __ballot(live), same = __ballot(live && t == t0);
+    if (lanes != 0ull && same == lanes) {           // the wave's points belong to one target (nearly always): 6 atomics per wave
+        float mn[3], mx[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = live ? v[a] : 3.4e38f; mx[a] = live ? v[a] : -3.4e38f;
+            for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o)); }
+        }
+        if (__ballot(bad) != 0ull) mx[0] = __builtin_inff();
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { atomicMin(&bounds[3 * t0 + a], f2ord(mn[a])); atomicMax(&bounds[3 * n_t + 3 * t0 + a], f2ord(mx[a])); }
+        }
+    } else if (live) {                              // a wave across a boundary: every lane for itself
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(&bounds[3 * t + a], f2ord(v[a]));
+            atomicMax(&bounds[3 * n_t + 3 * t + a], f2ord(a == 0 && bad ? __builtin_inff() : v[a]));
+        }
+    }
+}
+// key of pass point i = (pass target, cell as k_cell_keys takes it); vals = i
+static __global__ void k_pairs_keys(const float4 *__restrict__ raw, int64_t n, const int64_t *__restrict__ pass_off, int n_j,
+                                    const PairCells *__restrict__ cells, int cbits, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = frame_of(pass_off, n_j, i);
+    const PairCells g = cells[j];
+    const float4 c = raw[g.raw_first + (i - pass_off[j])];
+    const int nxf = g.nx * g.sx;
+    const int cx = clampi((int)floor(((double)c.x - g.ox) * g.inv_h * (double)g.sx), 0, nxf - 1);
+    const int cy = clampi((int)floor(((double)c.y - g.oy) * g.inv_h), 0, g.ny - 1);
+    const int cz = clampi((int)floor(((double)c.z - g.oz) * g.inv_h), 0, g.nz - 1);
+    keys[i] = ((uint64_t)j << cbits) | (uint64_t)(((int64_t)cz * g.ny + cy) * nxf + cx);
+    vals[i] = (uint32_t)i;
+}
+// occupied cells of every pass target: one count per distinct key of the sorted keys
+static __global__ void k_pairs_occupancy(const uint64_t *__restrict__ keys, int64_t n, int cbits, uint32_t *__restrict__ occ) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool first = i < n && (i == 0 || keys[i] != keys[i - 1]);
+    const uint32_t j = i < n ? (uint32_t)(keys[i] >> cbits) : 0u;
+    const uint32_t j0 = __builtin_amdgcn_readfirstlane(j);
+    const unsigned long long m = __ballot(first), same = __ballot(first && j == j0);
+    if (m == 0ull) return;
+    if (same == m) { if ((threadIdx.x & 63) == 0) atomicAdd(&occ[j0], (uint32_t)__popcll(m)); }
+    else if (first) atomicAdd(&occ[j], 1u);
+}
+// sorted position i of pass target j -> its place in the target's cell-sorted points
+static __global__ void k_pairs_gather(const float4 *__restrict__ raw, const uint32_t *__restrict__ order, int64_t n, const int64_t *__restrict__ pass_off,
+                                      int n_j, const PairCells *__restrict__ cells, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = frame_of(pass_off, n_j, i);
+    const int64_t first = pass_off[j];
+    out[cells[j].pts_first + (i - first)] = raw[cells[j].raw_first + ((int64_t)order[i] - first)];
+}
+// the kPtsPad zero entries behind every target's points (grid: one block per pass target)
+static __global__ void k_pairs_pad(const int64_t *__restrict__ pass_off, const PairCells *__restrict__ cells, float4 *__restrict__ out) {
+    const uint32_t j = blockIdx.x;
+    if (threadIdx.x < (uint32_t)kPtsPad) out[cells[j].pts_first + (pass_off[j + 1] - pass_off[j]) + threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// every target's cell table (k_cell_start, per target): entry e of the batch's tables = entry c of pass target j (tab_off[j] <= e <
+// tab_off[j + 1], nx sx ny nz + 1 entries each) = first position of j's sorted points whose cell is >= c
+static __global__ void k_pairs_table(const uint64_t *__restrict__ keys, const int64_t *__restrict__ pass_off, const int64_t *__restrict__ tab_off,
+                                     int n_j, int cbits, uint32_t *__restrict__ table) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= tab_off[n_j]) return;
+    const uint32_t j = frame_of(tab_off, n_j, e);
+    const uint64_t want = ((uint64_t)j << cbits) | (uint64_t)(e - tab_off[j]);
+    int64_t lo = pass_off[j], hi = pass_off[j + 1];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < want) lo = mid + 1; else hi = mid;
+    }
+    table[e] = (uint32_t)(lo - pass_off[j]);
+}
+// every target's row words (k_ymask, per target): word w of the batch = word w - yw_off[j] of pass target j
+static __global__ void k_pairs_ymask(const uint32_t *__restrict__ table, const int64_t *__restrict__ tab_off, const int64_t *__restrict__ yw_off, int n_j,
+                                     const PairCells *__restrict__ cells, uint32_t *__restrict__ ymask) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= yw_off[n_j]) return;
+    const uint32_t j = frame_of(yw_off, n_j, w);
+    const PairCells &g = cells[j];
+    ymask[w] = ymask_word(table + tab_off[j], g.nx, g.ny, g.sx, g.nxb, g.nyw, w - yw_off[j]);
 }
 
 // reductions for dcreg_p2p_error: sum sqrt(d2), sum d2 [dist<thr], count  (deterministic two-stage)

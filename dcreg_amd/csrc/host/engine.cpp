@@ -262,16 +262,20 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // frame_points == null: every trial registers the ctx's own source.  Otherwise trial k registers frame k of the frames dcreg_frames_load
 // put on the device (frame_points[k] points; dcreg_register_frames), with the frames' own neighbour states: a slot that takes the next
 // frame takes its cloud with it, and an empty frame never takes a slot.
+// first_pair >= 0 (with frame_points): trial k is scan pair first_pair + k of dcreg_register_pairs - its source of the pairs' sources,
+// target k of the build batch dcreg_pairs_build left on the device (frame_points[k] = 0: the source or the target is empty)
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
-                           const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr) {
+                           const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
+                           int64_t first_pair = -1) {
     const auto t_total = Clock::now();
     const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
     dcreg_index_info_get(ctx, &info);
     const bool frames = frame_points != nullptr;
+    const bool pairs = frames && first_pair >= 0;
     auto points_of = [&](int64_t k) { return frames ? frame_points[k] : info.n_source; };
     for (int64_t i = 0; i < n_trials; ++i) std::memset(&results[i], 0, sizeof(results[i]));
-    if ((!frames && info.n_source <= 0) || info.n_target <= 0) {
+    if ((!frames && info.n_source <= 0) || (!pairs && info.n_target <= 0)) {
         for (int64_t i = 0; i < n_trials; ++i) results[i].status = 3;
         return DCREG_OK;
     }
@@ -287,10 +291,11 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     n_slots = std::min(n_slots, 2 * 65535);
     const int n_groups = n_slots >= 64 ? 2 : 1;
     // one neighbour state per slot; without the memory for them the trials still run, every launch searching from scratch
-    bool have_states = (frames ? dcreg_frames_reserve_states(ctx, n_slots) : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
+    bool have_states = (pairs ? dcreg_pairs_reserve_states(ctx, n_slots) : frames ? dcreg_frames_reserve_states(ctx, n_slots)
+                                                                                  : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
     struct Slot { int64_t trial = -1; int it = 0; double R[9], t[3]; };
     std::vector<Slot> slot((size_t)n_slots);
-    struct Group { std::vector<int> live; std::vector<int32_t> ids, fids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
+    struct Group { std::vector<int> live; std::vector<int32_t> ids, fids, gids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
     Group grp[2];
     int64_t next_trial = 0;
     auto load = [&](int si) -> bool {                      // next trial in line -> slot si
@@ -299,7 +304,7 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         Slot &S = slot[(size_t)si];
         S.trial = next_trial++; S.it = 0;
         std::memcpy(S.R, R0 + 9 * S.trial, sizeof(S.R)); std::memcpy(S.t, t0 + 3 * S.trial, sizeof(S.t));
-        if (have_states) { if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si); }
+        if (have_states) { if (pairs) dcreg_pairs_reset_state(ctx, si); else if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si); }
         return true;
     };
     for (int si = 0; si < n_slots; ++si) load(si);
@@ -312,13 +317,16 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         if (G.live.empty()) return DCREG_OK;
         const int nl = (int)G.live.size();
         G.Rb.resize((size_t)nl * 9); G.tb.resize((size_t)nl * 3); G.outs.resize((size_t)nl); G.ids.resize((size_t)nl); G.fids.resize((size_t)nl);
+        G.gids.resize((size_t)nl);
         for (int j = 0; j < nl; ++j) {
             const Slot &S = slot[(size_t)G.live[(size_t)j]];
             G.ids[(size_t)j] = have_states ? (int32_t)G.live[(size_t)j] : -1;
-            G.fids[(size_t)j] = (int32_t)S.trial;
+            G.fids[(size_t)j] = (int32_t)(pairs ? first_pair + S.trial : S.trial);
+            G.gids[(size_t)j] = (int32_t)S.trial;
             std::memcpy(&G.Rb[(size_t)j * 9], S.R, sizeof(S.R)); std::memcpy(&G.tb[(size_t)j * 3], S.t, sizeof(S.t));
         }
-        const int rc = frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
+        const int rc = pairs ? dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm)
+                     : frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
                               : dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
         G.in_flight = rc == DCREG_OK;
         return rc;
@@ -421,6 +429,54 @@ int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const 
     std::vector<int64_t> points((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
     return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data());
+}
+
+// Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,
+// at once), the targets of the first build batch in its bounds pass and those of later batches here on the host - then every build batch
+// is indexed (dcreg_pairs_build) and its pairs run as frames do, each against its own target.
+int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                         const int64_t *tgt_offsets, int64_t stride_floats, const double *R0, const double *t0, int detection,
+                         int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    if (!ctx || !cfg || n_pairs < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (n_pairs == 0) return DCREG_OK;
+    if (!src_offsets || !tgt_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
+    for (const int64_t *off : {src_offsets, tgt_offsets}) {
+        if (off[0] != 0) { dcreg_set_error_message(ctx, "pair offsets must start at 0"); return DCREG_E_INVALID; }
+        for (int p = 0; p < n_pairs; ++p)
+            if (off[p + 1] < off[p]) { dcreg_set_error_message(ctx, "pair offsets decrease"); return DCREG_E_INVALID; }
+    }
+    if (tgt_offsets[n_pairs] > 0 && !tgt_xyz) { dcreg_set_error_message(ctx, "null target buffer"); return DCREG_E_INVALID; }
+    std::vector<int32_t> ends((size_t)n_pairs);
+    int n_batches = 0;
+    int rc = dcreg_pairs_plan(ctx, n_pairs, tgt_offsets, stride_floats, ends.data(), &n_batches);
+    if (rc != DCREG_OK) return rc;
+    if (n_batches > 1) {         // (the first batch's targets are checked by its bounds pass, before anything runs)
+        const int64_t first = tgt_offsets[ends[0]], n = tgt_offsets[n_pairs] - first;
+        int bad = 0;
+#pragma omp parallel for schedule(static) num_threads(host_team()) reduction(| : bad)
+        for (int64_t i = 0; i < n; ++i) {
+            const float *q = tgt_xyz + (first + i) * stride_floats;
+            if (!(std::fabs(q[0]) <= 3.4e38f) || !(std::fabs(q[1]) <= 3.4e38f) || !(std::fabs(q[2]) <= 3.4e38f)) bad = 1;
+        }
+        if (bad) { dcreg_set_error_message(ctx, "a pair target has non-finite coordinates"); return DCREG_E_INVALID; }
+    }
+    rc = dcreg_pairs_sources_load(ctx, n_pairs, src_xyz, src_offsets, stride_floats);      // (non-finite coordinates: refused here)
+    if (rc != DCREG_OK) return rc;
+    std::vector<int64_t> points((size_t)n_pairs), rel;
+    for (int p = 0; p < n_pairs; ++p) {
+        const bool empty = src_offsets[p + 1] == src_offsets[p] || tgt_offsets[p + 1] == tgt_offsets[p];
+        points[(size_t)p] = empty ? 0 : src_offsets[p + 1] - src_offsets[p];
+    }
+    for (int b = 0; b < n_batches; ++b) {
+        const int p0 = b > 0 ? ends[(size_t)b - 1] : 0, p1 = ends[(size_t)b];
+        rel.resize((size_t)(p1 - p0) + 1);
+        for (int p = p0; p <= p1; ++p) rel[(size_t)(p - p0)] = tgt_offsets[p] - tgt_offsets[p0];
+        rc = dcreg_pairs_build(ctx, p1 - p0, tgt_xyz ? tgt_xyz + tgt_offsets[p0] * stride_floats : nullptr, rel.data(), stride_floats, cfg->search_radius);
+        if (rc != DCREG_OK) return rc;
+        rc = run_trials_core(ctx, p1 - p0, R0 + 9 * (size_t)p0, t0 + 3 * (size_t)p0, detection, handling, cfg, results + p0, slots, points.data() + p0, p0);
+        if (rc != DCREG_OK) return rc;
+    }
+    return DCREG_OK;
 }
 
 int dcreg_icp_run_montecarlo(dcreg_ctx *ctx, const double base_xyzrpy[6], uint64_t seed, int64_t first_trial, int64_t trial_stride,

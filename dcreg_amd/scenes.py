@@ -254,6 +254,30 @@ def map_frames(tgt, poses, n_frame=8_000, seed=0, frame_range=30.0, noise=0.02):
     return out
 
 
+def scan_pairs(tgt, poses, n_frame=8_000, seed=0, mode="submap", n_submap=100_000, submap_radius=40.0, frame_range=30.0, noise=0.02):
+    """Scan pairs cut out of an existing map at sensor poses (4x4, sensor -> map), sources made by map_frames.  mode "submap": pair k = the
+    frame at poses[k] against a submap crop - up to n_submap map points within submap_radius metres (in x-y) of poses[k]'s position, in
+    the map frame (loop-closure verification against a submap).  mode "scan": pair k = the frame at poses[k + 1] against the frame at
+    poses[k] (scan-to-scan odometry of a recorded drive: len(poses) - 1 pairs).  -> (sources, targets, T_true) with T_true[k] the 4x4 pose
+    that maps source k into target k's frame."""
+    rng = np.random.default_rng(seed + 1)
+    tgt = np.asarray(tgt, np.float32)
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    frames = map_frames(tgt, poses, n_frame, seed=seed, frame_range=frame_range, noise=noise)
+    if mode == "scan":
+        return frames[1:], frames[:-1], [np.linalg.inv(poses[k]) @ poses[k + 1] for k in range(len(poses) - 1)]
+    if mode != "submap":
+        raise ValueError("scan_pairs: mode is 'submap' or 'scan', got %r" % (mode,))
+    targets = []
+    for T in poses:
+        dx, dy = tgt[:, 0] - np.float32(T[0, 3]), tgt[:, 1] - np.float32(T[1, 3])
+        near = np.flatnonzero(dx * dx + dy * dy < np.float32(submap_radius * submap_radius))
+        if len(near) > n_submap:
+            near = np.sort(rng.choice(near, size=n_submap, replace=False))
+        targets.append(np.ascontiguousarray(tgt[near]))
+    return frames, targets, [T.copy() for T in poses]
+
+
 def write_pcd_xyzi(path, xyz):
     """Binary PCD v0.7, fields x y z intensity (float32), like pcl::io::savePCDFileBinary<PointXYZI>."""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)

@@ -174,7 +174,7 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames, the launches, and dcreg_debug.h's dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
+ * dcreg_register_frames, dcreg_register_pairs, the launches, and dcreg_debug.h's dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
 int dcreg_linearize_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *);
@@ -367,6 +367,23 @@ int dcreg_icp_run_trials(dcreg_ctx *, int n_trials, const double *R0_9, const do
 int dcreg_register_frames(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                           const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
                           dcreg_trial_result *results);
+
+/* Many scan pairs registered in one call, each against a target of its own (loop-closure candidates against their submaps, scan-to-scan
+ * odometry of a recorded drive, multi-session alignment, accuracy evaluation over a dataset of pairs): pair p = source points
+ * [src_offsets[p], src_offsets[p + 1]) of src_xyz against target points [tgt_offsets[p], tgt_offsets[p + 1]) of tgt_xyz, started from
+ * R0_9[9p..], t0_3[3p..].  Both buffers in HOST memory, clouds back to back, stride_floats floats per point (x y z first); each offset
+ * array holds n_pairs + 1 entries, in points, starting at 0.  The targets are indexed in build batches (option "pairs_max_bytes"; their
+ * cell tables budgeted per target by "pair_max_table_entries"), every batch with one upload, one bounds pass and a fixed number of sorts
+ * and synchronises whatever its size, for the radius cfg->search_radius; the pairs of a batch then run as dcreg_register_frames runs
+ * frames, each pose reading its own source and its own target.  results[p] is bitwise what a context with the same options gives for
+ * dcreg_set_target(target p, cfg->search_radius) + dcreg_set_source(source p) + dcreg_icp_run(R0 p, t0 p) - the fields
+ * dcreg_register_frames promises, errors against cfg->gt_matrix.  An empty source or target: status 3, the other pairs run; n_pairs == 0
+ * does nothing.  DCREG_E_INVALID, and nothing runs: offsets that do not start at 0 or decrease, non-finite coordinates in any cloud;
+ * DCREG_E_STATE: a linearisation in flight.  Needs no target on the context, and leaves its target, source, neighbour states, reserved
+ * warm states, frames and window index as they were. */
+int dcreg_register_pairs(dcreg_ctx *, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                         const int64_t *tgt_offsets, int64_t stride_floats, const double *R0_9, const double *t0_3, int detection,
+                         int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
 
 /* Initial pose of Monte-Carlo trial k (the reference has no RNG: its num_runs loop, icp_test_runner.cpp:339-349, repeats one
  * deterministic run; the seeded perturbation is this build's definition, shared by the runner and dcreg_amd/montecarlo.py):

@@ -130,6 +130,20 @@ int dcreg_frames_reset_state(dcreg_ctx *, int64_t state_id);
 int dcreg_frames_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                              const int32_t *frame_ids, const dcreg_lin_params *);
 
+/* internal: the device seam of dcreg_register_pairs (engine.cpp).  dcreg_pairs_plan cuts the pairs into build batches of their targets
+ * (batch b = pairs [batch_end[b - 1], batch_end[b]); option "pairs_max_bytes"); dcreg_pairs_sources_load is dcreg_frames_load for the
+ * pairs' sources (kept apart from the context's frames); dcreg_pairs_build indexes the targets of one batch (host memory, offsets from 0,
+ * cells for the search radius; waits for the stream); dcreg_pairs_reserve_states / _reset_state are the sources' neighbour states;
+ * dcreg_pairs_batch_begin is dcreg_frames_batch_begin with pose i against target target_ids[i] of the batch.  None of them touches the
+ * context's own target, source, states, frames or window index. */
+int dcreg_pairs_plan(dcreg_ctx *, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches);
+int dcreg_pairs_sources_load(dcreg_ctx *, int n_pairs, const float *xyz, const int64_t *src_offsets, int64_t stride_floats);
+int dcreg_pairs_build(dcreg_ctx *, int n_targets, const float *xyz, const int64_t *tgt_offsets, int64_t stride_floats, double search_radius);
+int dcreg_pairs_reserve_states(dcreg_ctx *, int64_t n_states);
+int dcreg_pairs_reset_state(dcreg_ctx *, int64_t state_id);
+int dcreg_pairs_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                            const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
+
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */
 void dcreg_set_error_message(dcreg_ctx *, const char *msg);
 
