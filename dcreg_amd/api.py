@@ -129,6 +129,8 @@ REDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_void_p)      # dcreg
 EXPORTS = [
     "dcreg_backend_create", "dcreg_backend_destroy", "dcreg_last_error", "dcreg_set_stream", "dcreg_set_option",
     "dcreg_set_target", "dcreg_set_target_device", "dcreg_set_source", "dcreg_set_source_device",
+    "dcreg_target_insert", "dcreg_target_insert_device", "dcreg_target_insert_source", "dcreg_target_crop", "dcreg_target_get",
+    "dcreg_debug_index_check",
     "dcreg_default_lin_params", "dcreg_linearize", "dcreg_linearize_batch", "dcreg_linearize_batch_begin",
     "dcreg_linearize_batch_end", "dcreg_linearize_batch_begin_warm", "dcreg_reserve_warm_states", "dcreg_reset_warm_state", "dcreg_hint_misalignment", "dcreg_linearize_debug", "dcreg_launch_stats_get", "dcreg_knn", "dcreg_kdtree_build", "dcreg_kdtree_info", "dcreg_knn_timed",
     "dcreg_linearize_gated_begin", "dcreg_linearize_gate_open", "dcreg_linearize_gate_abort",
@@ -143,6 +145,23 @@ EXPORTS = [
 ]
 
 _lib = None
+
+
+class MapUpdate(C.Structure):
+    _fields_ = [("n_offered", C.c_int64), ("n_added", C.c_int64), ("n_removed", C.c_int64), ("n_target", C.c_int64), ("rebuilt", C.c_int),
+                ("reserved_", C.c_int)]
+
+
+def _pose_rt(T, what):
+    """(R row-major [9], t [3]) of a 4x4 pose"""
+    T = np.asarray(T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("%s: a 4x4 pose is expected, got shape %s" % (what, T.shape))
+    return np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+
+
+def _update_dict(u):
+    return {"n_offered": u.n_offered, "n_added": u.n_added, "n_removed": u.n_removed, "n_target": u.n_target, "rebuilt": u.rebuilt}
 
 
 class DcregError(RuntimeError):
@@ -233,6 +252,13 @@ def load():
     L.dcreg_frames_reserve_states.argtypes = [vp, C.c_int64]
     L.dcreg_frames_reset_state.argtypes = [vp, C.c_int64]
     L.dcreg_frames_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
+    if hasattr(L, "dcreg_target_insert"):      # (absent from an older build loaded through DCREG_LIB for an A/B)
+        L.dcreg_target_insert.argtypes = [vp, fp, C.c_int64, C.c_int64, dp, dp, C.c_double, C.POINTER(MapUpdate)]
+        L.dcreg_target_insert_device.argtypes = [vp, vp, C.c_int64, C.c_int64, dp, dp, C.c_double, C.POINTER(MapUpdate)]
+        L.dcreg_target_insert_source.argtypes = [vp, dp, dp, C.c_double, C.POINTER(MapUpdate)]
+        L.dcreg_target_crop.argtypes = [vp, dp, dp, C.POINTER(MapUpdate)]
+        L.dcreg_target_get.argtypes = [vp, fp, C.c_int64]
+        L.dcreg_debug_index_check.argtypes = [vp, C.POINTER(C.c_int64)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -803,6 +829,54 @@ class Context:
                                                  C.byref(cfg), int(slots), res),
                     "dcreg_register_pairs")
         return [res[i] for i in range(n)]
+
+    def insert(self, xyz, T, min_spacing=0.0):
+        """dcreg_target_insert: the points xyz (body frame) transformed by the 4x4 pose T appended to the map, except those with a map point
+        closer than min_spacing (> 0) -> dict n_offered / n_added / n_removed / n_target / rebuilt"""
+        a = _points(xyz, "insert")
+        R, t = _pose_rt(T, "insert")
+        u = MapUpdate()
+        self._check(self._L.dcreg_target_insert(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], a.shape[1], _dp(R), _dp(t),
+                                                float(min_spacing), C.byref(u)), "dcreg_target_insert")
+        return _update_dict(u)
+
+    def insert_device(self, dev_ptr, n, stride, T, min_spacing=0.0):
+        R, t = _pose_rt(T, "insert_device")
+        u = MapUpdate()
+        self._check(self._L.dcreg_target_insert_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), _dp(R), _dp(t), float(min_spacing),
+                                                       C.byref(u)), "dcreg_target_insert_device")
+        return _update_dict(u)
+
+    def insert_source(self, T, min_spacing=0.0):
+        """dcreg_target_insert_source: the source of the last set_source, transformed by T (typically the registration's result), into the map"""
+        R, t = _pose_rt(T, "insert_source")
+        u = MapUpdate()
+        self._check(self._L.dcreg_target_insert_source(self._h, _dp(R), _dp(t), float(min_spacing), C.byref(u)), "dcreg_target_insert_source")
+        return _update_dict(u)
+
+    def crop(self, lo, hi):
+        """dcreg_target_crop: keep the map points inside the box lo .. hi (inclusive, per axis)"""
+        lo = _f64(lo)
+        hi = _f64(hi)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("crop: lo and hi are 3 coordinates each, got shapes %s and %s" % (lo.shape, hi.shape))
+        u = MapUpdate()
+        self._check(self._L.dcreg_target_crop(self._h, _dp(lo), _dp(hi), C.byref(u)), "dcreg_target_crop")
+        return _update_dict(u)
+
+    def target_points(self):
+        """the map in index order, float32 [n, 3] (dcreg_target_get)"""
+        n = self.index_info().n_target
+        out = np.empty((max(n, 0), 3), np.float32)
+        self._check(self._L.dcreg_target_get(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n), "dcreg_target_get")
+        return out
+
+    def index_check(self):
+        """dcreg_debug_index_check: differing entries of sorted points, cell table, row words, gap field and owners against a full build
+        of the current grid (all zero = exact)"""
+        mm = (C.c_int64 * 5)()
+        self._check(self._L.dcreg_debug_index_check(self._h, mm), "dcreg_debug_index_check")
+        return dict(zip(("points", "table", "row_words", "gap", "owner"), [int(v) for v in mm]))
 
     def p2p_error(self, T, error_threshold):
         r, f, ch = C.c_double(), C.c_double(), C.c_double()

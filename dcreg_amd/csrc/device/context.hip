@@ -468,6 +468,8 @@ static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     rc = build_index(c, target_dst(c), radius_hint * (1.0 + c->opt_cert_margin), &c->occupied_cells, box);
     if (rc) { c->n_tgt = 0; return rc; }
     c->whole_capped = c->last_build_capped;
+    for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
+    c->build_per_cell = (double)n / (double)std::max<uint32_t>(c->occupied_cells, 1u);
     rc = build_gap_field(c, radius_hint * (1.0 + c->opt_cert_margin));
     if (rc) { c->n_tgt = 0; return rc; }
     rc = build_row_words(c);
@@ -476,6 +478,486 @@ static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     c->order_valid = false;  // ... and the cost estimate of the query groups to the old map
     c->last_pose_valid = false;
     c->n_batch_states = 0;
+    return DCREG_OK;
+}
+
+// ------------------------------------------------------------------------------------------ updates of the resident map (dcreg_target_insert*, _crop)
+// Points are appended to the map, or cut from it by a box, and the index follows in place: the grid is kept where it can serve (the merged
+// path), and re-derived from the device-resident raw points where it cannot (rebuilt).  Every search is exact in any grid, so either way
+// the map answers bitwise as dcreg_set_target of the updated cloud would.  A refused call changes nothing: everything is checked in scratch
+// buffers first, and the arrays that replace the map's are allocated before the first of them is written.
+
+// grows a buffer whose first `keep` elements must survive (geometric capacity; the old buffer is freed only once the copy is queued behind it)
+template <typename T>
+static int grow_keep(dcreg_ctx *c, T *&ptr, size_t &cap, size_t need, size_t keep) {
+    if (need <= cap && ptr) return DCREG_OK;
+    const size_t n = std::max(need, cap + cap / 2);
+    T *p = nullptr;
+    if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->fail("hipMalloc(%zu B) failed while growing the map", n * sizeof(T));
+        return DCREG_E_NOMEM;
+    }
+    if (ptr && keep) HIP_TRY(c, hipMemcpyAsync(p, ptr, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ptr) (void)hipFree(ptr);
+    ptr = p; cap = n;
+    return DCREG_OK;
+}
+
+static void update_info(dcreg_map_update *info, int64_t offered, int64_t added, int64_t removed, int64_t n_target, int rebuilt) {
+    if (!info) return;
+    info->n_offered = offered; info->n_added = added; info->n_removed = removed; info->n_target = n_target; info->rebuilt = rebuilt; info->reserved_ = 0;
+}
+
+// everything derived from the map as it was goes, as dcreg_set_target drops it
+static void map_changed(dcreg_ctx *c) {
+    c->roi_built = false;
+    drop_warm(c);
+    c->order_valid = false;
+    c->last_pose_valid = false;
+    c->n_batch_states = 0;
+    std::fill(c->frames.state_valid.begin(), c->frames.state_valid.end(), (uint8_t)0);
+    kdtree_free(c->kd); c->kd = nullptr;
+}
+
+static void words_init(uint32_t w[kMwWords]) {
+    for (int k = 0; k < kMwWords; ++k) w[k] = 0u;
+    for (int a = 0; a < 3; ++a) { w[kMwMin + a] = 0xFFFFFFFFu; w[kMwCellMin + a] = 0xFFFFFFFFu; }
+    w[kMwKeyMin] = 0xFFFFFFFFu;
+}
+
+static int64_t box_cells(const MapBox &b) { return (int64_t)(b.x1 - b.x0) * (b.y1 - b.y0) * (b.z1 - b.z0); }
+static MapBox box_grow(const MapBox &b, int r, const GridDev &g) {
+    return MapBox{std::max(b.x0 - r, 0), std::max(b.y0 - r, 0), std::max(b.z0 - r, 0), std::min(b.x1 + r, g.nx), std::min(b.y1 + r, g.ny), std::min(b.z1 + r, g.nz)};
+}
+// the cells of a change (words kMwCellMin .. : cell + 1) and one more in x (the dense seeds look at their x neighbours' points)
+static MapBox change_box(const uint32_t w[kMwWords], const GridDev &g) {
+    MapBox S{(int)w[kMwCellMin] - 1, (int)w[kMwCellMin + 1] - 1, (int)w[kMwCellMin + 2] - 1, (int)w[kMwCellMax], (int)w[kMwCellMax + 1], (int)w[kMwCellMax + 2]};
+    S.x0 = std::max(S.x0 - 1, 0); S.x1 = std::min(S.x1 + 1, g.nx);
+    return S;
+}
+// scratch the fields of a change need (before the first write of an update)
+static int fields_reserve(dcreg_ctx *c, const MapBox &S) {
+    const GridDev &g = c->grid;
+    if (!g.gap) return DCREG_OK;
+    const MapBox E = box_grow(S, 2 * g.gap_cap, g);
+    const size_t ne = (size_t)box_cells(E);
+    if (ensure(c, c->d_fgap, c->fgap_cap, 2 * ne) || ensure(c, c->d_fown, c->fown_cap, 2 * ne)) return DCREG_E_NOMEM;
+    return DCREG_OK;
+}
+// row words and fields of the cells a change can reach, recomputed from the updated table (k_ymask_box, k_gap_*_box)
+static void fields_local(dcreg_ctx *c, const MapBox &S) {
+    const GridDev &g = c->grid;
+    if (g.ymask) {
+        const int xb0 = S.x0 >> 4, xb1 = (S.x1 + 15) >> 4, yw0 = S.y0 >> 5, yw1 = (S.y1 + 31) >> 5;
+        const int64_t nw = (int64_t)(xb1 - xb0) * (yw1 - yw0) * (S.z1 - S.z0);
+        hipLaunchKernelGGL(k_ymask_box, dim3(blocks_for(nw, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, g.nxb, g.nyw,
+                           xb0, xb1 - xb0, yw0, yw1 - yw0, S.z0, S.z1 - S.z0, c->d_ymask);
+    }
+    if (!g.gap) return;
+    const int rings = g.gap_cap;
+    const MapBox B = box_grow(S, rings, g), E = box_grow(B, rings, g);
+    const int64_t ne = box_cells(E), nb = box_cells(B);
+    uint8_t *gap_p = c->d_fgap, *gap_d = c->d_fgap + ne;
+    uint32_t *own_p = c->d_fown, *own_d = c->d_fown + ne;
+    hipLaunchKernelGGL(k_gap_init_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 0, 0u, gap_p, own_p);
+    for (int r = 1; r <= rings; ++r)
+        hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.nx, g.ny, E, r);
+    if (g.owner) {
+        hipLaunchKernelGGL(k_gap_init_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 1, 6u, gap_d, own_d);
+        for (int r = 1; r <= rings; ++r)
+            hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_d, own_d, g.nx, g.ny, E, r);
+    }
+    hipLaunchKernelGGL(k_gap_store_box, dim3(blocks_for(nb, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.owner ? own_d : (const uint32_t *)nullptr,
+                       g.nx, g.ny, E, B, c->d_gap, c->d_owner);
+}
+
+static int count_occupied(dcreg_ctx *c, const GridDev &g, int64_t n_cells, uint32_t *out) {
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_count_occupied, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.cell_start, n_cells, g.sx, c->d_scratch);
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
+// a field buffer sized for a new grid, allocated beside the current one (which the current index keeps reading until the swap)
+template <typename T>
+static int reserve_beside(dcreg_ctx *c, T *cur, size_t cap, size_t need, T *&fresh) {
+    fresh = nullptr;
+    if (need <= cap && cur) return DCREG_OK;
+    if (hipMalloc((void **)&fresh, std::max<size_t>(need, 1) * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError(); fresh = nullptr;
+        c->fail("hipMalloc(%zu B) failed while re-deriving the map's grid", need * sizeof(T));
+        return DCREG_E_NOMEM;
+    }
+    return DCREG_OK;
+}
+
+// The map's raw points (c->n_tgt of them, index order) are final and bounded by c->tgt_box: derive the grid anew, over that box enlarged by
+// "map_grow_margin" on each side in x and y - not in z: a ground vehicle's map is flat, and z slack would multiply the dense table of a
+// wide, flat map (12 m of height grown by 20 m on each side is 4.3 x the entries) and push it past its budget into coarser cells.  A point
+// that leaves the box in z re-derives the grid again.  keep_edge: the current cell edge and x sub-cells where the table budget allows
+// them (one key sort); otherwise - or when it does not - build_index's rules.  Built beside the current index and swapped in at the end;
+// *swapped tells whether that happened (a failure before it leaves the current index standing).
+static int map_rebuild(dcreg_ctx *c, bool keep_edge, bool *swapped) {
+    *swapped = false;
+    const double m[3] = {c->opt_map_grow_margin, c->opt_map_grow_margin, 0.0};
+    double box[6];
+    for (int a = 0; a < 3; ++a) { box[a] = c->tgt_box[a] - m[a]; box[3 + a] = c->tgt_box[3 + a] + m[a]; }
+    GridDev g2{};
+    int64_t n_cells2 = 0;
+    uint32_t occ = 0;
+    GridDst d{c->d_tgt_raw, c->n_tgt, &c->d_tgt_alt, &c->tgt_alt_cap, &c->d_cell_alt, &c->cell_alt_cap, &g2, &n_cells2};
+    const GridDev &g = c->grid;
+    bool capped = c->whole_capped, built = false;
+    if (keep_edge) {
+        double dims[3], entries = (double)g.sx;
+        for (int a = 0; a < 3; ++a) { dims[a] = std::floor((box[3 + a] - box[a]) * g.inv_h) + 1.0; entries *= dims[a]; }
+        if (entries <= (double)c->opt_max_table_entries && dims[0] < 2e9 && dims[1] < 2e9 && dims[2] < 2e9) {
+            int rc = build_grid_at(c, d, g.h, box, box + 3, &occ, g.sx);
+            if (rc) return rc;
+            rc = count_occupied(c, g2, n_cells2, &occ);
+            if (rc) return rc;
+            built = true;
+        }
+    }
+    if (!built) {
+        int rc = build_index(c, d, c->radius_hint * (1.0 + c->opt_cert_margin), &occ, box);
+        if (rc) return rc;
+        capped = c->last_build_capped;
+    }
+    // the fields of the new grid: buffers beside the current ones where these are too small
+    const size_t n_words = (size_t)g2.nz * (size_t)((g2.nx + 15) >> 4) * (size_t)((g2.ny + 31) >> 5);
+    uint8_t *gap = nullptr; uint32_t *owner = nullptr, *ymask = nullptr;
+    int rc = reserve_beside(c, c->d_ymask, c->ymask_cap, n_words, ymask);
+    if (rc == DCREG_OK && c->opt_gap_field) rc = reserve_beside(c, c->d_gap, c->gap_cap, (size_t)n_cells2, gap);
+    if (rc == DCREG_OK && c->opt_gap_field) rc = reserve_beside(c, c->d_owner, c->owner_cap, (size_t)n_cells2, owner);
+    if (rc) {
+        for (void *p : {(void *)gap, (void *)owner, (void *)ymask}) if (p) (void)hipFree(p);
+        return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ymask) { if (c->d_ymask) (void)hipFree(c->d_ymask); c->d_ymask = ymask; c->ymask_cap = std::max<size_t>(n_words, 1); }
+    if (gap) { if (c->d_gap) (void)hipFree(c->d_gap); c->d_gap = gap; c->gap_cap = std::max<size_t>((size_t)n_cells2, 1); }
+    if (owner) { if (c->d_owner) (void)hipFree(c->d_owner); c->d_owner = owner; c->owner_cap = std::max<size_t>((size_t)n_cells2, 1); }
+    std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
+    std::swap(c->d_cell_start, c->d_cell_alt); std::swap(c->cell_cap, c->cell_alt_cap);
+    *swapped = true;
+    c->grid = g2; c->n_cells = n_cells2;
+    c->occupied_cells = occ;
+    c->whole_capped = capped;
+    c->build_per_cell = (double)c->n_tgt / (double)std::max<uint32_t>(occ, 1u);
+    rc = build_gap_field(c, c->radius_hint * (1.0 + c->opt_cert_margin));
+    if (rc == DCREG_OK) rc = build_row_words(c);
+    return rc;
+}
+
+// The appended points (c->d_map_new[0, n_add), w = their map indices; their keys and input ranks at keys / vals) go into the current grid.
+static int map_merge(dcreg_ctx *c, uint32_t n_add, uint32_t *keys, uint32_t *vals, uint32_t *keys2, uint32_t *vals2, uint32_t *b, const uint32_t w[kMwWords]) {
+    GridDev &g = c->grid;
+    const int64_t n_old = c->n_tgt, n_new = n_old + n_add;
+    const int64_t n_entries = (int64_t)g.nx * g.sx * g.ny * g.nz;
+    const MapBox S = change_box(w, g);
+    // ---- every allocation first
+    if (grow_keep(c, c->d_tgt_raw, c->tgt_raw_cap, (size_t)n_new, (size_t)n_old) || ensure(c, c->d_tgt_alt, c->tgt_alt_cap, (size_t)n_new + kPtsPad) ||
+        fields_reserve(c, S))
+        return DCREG_E_NOMEM;
+    int bits = 1;
+    while (((int64_t)1 << bits) < n_entries && bits < 32) ++bits;
+    int rc = sort_pairs_u32(c, keys, keys2, vals, vals2, (size_t)n_add, bits);
+    if (rc) return rc;
+    // ---- from here on the map is rewritten
+    HIP_TRY(c, hipMemcpyAsync(c->d_tgt_raw + n_old, c->d_map_new, sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch + kMwOccupied, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_map_bpos, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, keys2, n_add, g.cell_start, g.sx, b, c->d_scratch);
+    hipLaunchKernelGGL(k_map_merge_old, dim3(blocks_for(n_old, 256)), dim3(256), 0, c->stream, c->d_tgt, (uint32_t)n_old, b, n_add, c->d_tgt_alt);
+    hipLaunchKernelGGL(k_map_merge_new, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, c->d_map_new, vals2, b, n_add, c->d_tgt_alt);
+    HIP_TRY(c, hipMemsetAsync(c->d_tgt_alt + n_new, 0, kPtsPad * sizeof(float4), c->stream));
+    const int64_t first = (int64_t)w[kMwKeyMin] + 1;       // entries up to the smallest new key keep their value
+    if (first <= n_entries)
+        hipLaunchKernelGGL(k_map_table_insert, dim3(blocks_for(n_entries - first + 1, 256)), dim3(256), 0, c->stream, c->d_cell_start, first, n_entries, keys2, n_add);
+    std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
+    c->n_tgt = n_new;
+    g.pts = c->d_tgt; g.n_pts = (uint32_t)n_new;
+    fields_local(c, S);
+    uint32_t occ_new = 0;
+    HIP_TRY(c, hipMemcpyAsync(&occ_new, c->d_scratch + kMwOccupied, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->occupied_cells += occ_new;
+    return DCREG_OK;
+}
+
+// a view of the whole map's index, whichever index is active (a refused or empty update must not swap them: that drops the states)
+struct WholeMap { float4 *raw; float4 *sorted; int64_t n; GridDev g; };
+static WholeMap whole_map(const dcreg_ctx *c) {
+    if (c->roi_active) return WholeMap{c->roi_store.raw, c->roi_store.sorted, c->roi_store.n, c->roi_store.grid};
+    return WholeMap{c->d_tgt_raw, c->d_tgt, c->n_tgt, c->grid};
+}
+
+static bool finite_pose(const double *R, const double *t) {
+    for (int k = 0; k < 9; ++k) if (!std::isfinite(R[k])) return false;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(t[k])) return false;
+    return true;
+}
+
+static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, bool from_source, const double *R, const double *t,
+                      double min_spacing, dcreg_map_update *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!R || !t || (!from_source && (!xyz || n < 0 || stride < 3)) || !std::isfinite(min_spacing)) { c->fail("invalid insert arguments"); return DCREG_E_INVALID; }
+    if (!finite_pose(R, t)) { c->fail("the pose of an insert has non-finite entries"); return DCREG_E_INVALID; }
+    if (c->n_tgt <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (from_source && c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    const int64_t m = from_source ? c->n_src : n;
+    if (m >= ((int64_t)1 << 31)) { c->fail("too many points (%lld)", (long long)m); return DCREG_E_INVALID; }
+    const int64_t n_old = whole_map(c).n;
+    if (m == 0) { update_info(info, 0, 0, 0, n_old, 0); return DCREG_OK; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const float4 *in = c->d_src_raw;
+    if (!from_source) {
+        int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
+        if (rc) return rc;
+        in = c->d_aligned;
+    }
+    const size_t m1 = (size_t)m + 1;
+    if (ensure(c, c->d_map_q, c->map_q_cap, (size_t)m) || ensure(c, c->d_map_new, c->map_new_cap, (size_t)m) || ensure(c, c->d_upd, c->upd_cap, 6 * m1))
+        return DCREG_E_NOMEM;
+    uint32_t *flag = c->d_upd, *pos = flag + m1, *keys = pos + m1, *vals = keys + m1, *keys2 = vals + m1, *vals2 = keys2 + m1;
+    uint32_t w[kMwWords];
+    words_init(w);
+    HIP_TRY(c, hipMemcpyAsync(c->d_scratch, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    PoseArg P{};
+    for (int k = 0; k < 9; ++k) P.R[k] = R[k];
+    for (int k = 0; k < 3; ++k) P.t[k] = t[k];
+    hipLaunchKernelGGL(k_map_transform, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, in, m, P, c->d_map_q, c->d_scratch);
+    const WholeMap wm = whole_map(c);
+    const float *d2 = nullptr;
+    float spacing_sq = 0.f;
+    if (min_spacing > 0.0) {      // the map as it stood: dcreg_knn with k = 1 (the bound only has to reach the spacing)
+        if (ensure(c, c->d_nn_idx, c->nn_idx_cap, (size_t)m) || ensure(c, c->d_nn_d2, c->nn_d2_cap, (size_t)m)) return DCREG_E_NOMEM;
+        int rc = launch_knn(c, wm.g, c->d_map_q, m, 1, min_spacing, nullptr, c->d_nn_idx, c->d_nn_d2);
+        if (rc) return rc;
+        d2 = c->d_nn_d2;
+        spacing_sq = (float)(min_spacing * min_spacing);
+    }
+    hipLaunchKernelGGL(k_map_keep, dim3(blocks_for((int64_t)m1, 256)), dim3(256), 0, c->stream, m, d2, spacing_sq, flag);
+    {
+        size_t tmp = 0;
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
+        if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
+    }
+    hipLaunchKernelGGL(k_map_append, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, c->d_map_q, m, flag, pos, (uint32_t)n_old, wm.g, c->d_map_new,
+                       keys, vals, c->d_scratch);
+    uint32_t n_add = 0;
+    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&n_add, pos + m, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (w[kMwBad]) { c->fail("inserted points have non-finite coordinates"); return DCREG_E_INVALID; }
+    if (n_old + (int64_t)n_add > (int64_t)INT32_MAX) { c->fail("the map would hold more than 2^31 - 1 points"); return DCREG_E_INVALID; }
+    if (n_add == 0) { update_info(info, m, 0, 0, n_old, 0); return DCREG_OK; }     // everything thinned: nothing changes
+    // ---- the map changes
+    (void)roi_deactivate(c);
+    double box[6];
+    for (int a = 0; a < 3; ++a) {
+        box[a] = std::min(c->tgt_box[a], (double)ord2f(w[kMwMin + a]));
+        box[3 + a] = std::max(c->tgt_box[3 + a], (double)ord2f(w[kMwMax + a]));
+    }
+    int rebuilt = 0, rc = DCREG_OK;
+    bool swapped = false;
+    if (c->opt_map_update && !w[kMwOutside]) {
+        rc = map_merge(c, n_add, keys, vals, keys2, vals2, flag, w);
+        if (rc) return rc;
+        for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
+        map_changed(c);
+        // the density the cell edge was sized for has doubled: derive the grid again (build_index's rules)
+        if ((double)c->n_tgt / (double)std::max<uint32_t>(c->occupied_cells, 1u) > 2.0 * c->build_per_cell) {
+            rc = map_rebuild(c, false, &swapped);
+            rebuilt = swapped ? 1 : 0;
+            if (rc != DCREG_OK && !swapped) {
+                // nothing was swapped in: the merged map stands, complete and exact, in the grid it had.  Short of memory that is the
+                // result (the re-derivation only restores speed; the next update tries again); any other failure is reported
+                if (rc != DCREG_E_NOMEM) return rc;
+                (void)hipGetLastError();
+                rc = DCREG_OK;
+            }
+        }
+    } else {
+        if (grow_keep(c, c->d_tgt_raw, c->tgt_raw_cap, (size_t)(n_old + n_add), (size_t)n_old)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_tgt_raw + n_old, c->d_map_new, sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
+        const double old_box[6] = {c->tgt_box[0], c->tgt_box[1], c->tgt_box[2], c->tgt_box[3], c->tgt_box[4], c->tgt_box[5]};
+        c->n_tgt = n_old + n_add;               // (the points beyond n_old are not read by the index as it was)
+        for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
+        rebuilt = 1;
+        rc = map_rebuild(c, true, &swapped);
+        if (rc != DCREG_OK && !swapped) {                               // nothing was swapped in: the old map stands
+            c->n_tgt = n_old;
+            for (int a = 0; a < 6; ++a) c->tgt_box[a] = old_box[a];
+            return rc;
+        }
+        map_changed(c);
+    }
+    if (rc) { c->n_tgt = 0; return rc; }         // (a failure after a rebuild swapped its grid in: the map is gone, as after a failed dcreg_set_target)
+    update_info(info, m, n_add, 0, c->n_tgt, rebuilt);
+    return DCREG_OK;
+}
+
+static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_update *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!lo || !hi) { c->fail("invalid crop arguments"); return DCREG_E_INVALID; }
+    for (int a = 0; a < 3; ++a) if (std::isnan(lo[a]) || std::isnan(hi[a])) { c->fail("the crop box has NaN bounds"); return DCREG_E_INVALID; }
+    if (c->n_tgt <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const WholeMap wm = whole_map(c);
+    const int64_t n = wm.n;
+    const size_t n1 = (size_t)n + 1;
+    if (ensure(c, c->d_upd, c->upd_cap, 4 * n1)) return DCREG_E_NOMEM;
+    uint32_t *flag_r = c->d_upd, *pos_r = flag_r + n1, *flag_s = pos_r + n1, *pos_s = flag_s + n1;
+    CropBox bx;
+    for (int a = 0; a < 3; ++a) { bx.lo[a] = lo[a]; bx.hi[a] = hi[a]; }
+    uint32_t w[kMwWords];
+    words_init(w);
+    HIP_TRY(c, hipMemcpyAsync(c->d_scratch, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw, n, bx, flag_r);
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted, n, bx, flag_s);
+    {
+        size_t tmp = 0;
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
+        if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag_s, pos_s, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
+    }
+    hipLaunchKernelGGL(k_crop_scan_box, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.sorted, n, flag_s, wm.g, c->d_scratch);
+    uint32_t kept = 0;
+    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&kept, pos_r + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (kept == 0) { c->fail("the crop box keeps no point of the map"); return DCREG_E_INVALID; }
+    if ((int64_t)kept == n) { update_info(info, n, 0, 0, n, 0); return DCREG_OK; }      // nothing outside the box: nothing changes
+    // ---- the map changes
+    (void)roi_deactivate(c);
+    GridDev &g = c->grid;
+    double kbox[6];
+    for (int a = 0; a < 3; ++a) { kbox[a] = ord2f(w[kMwMin + a]); kbox[3 + a] = ord2f(w[kMwMax + a]); }
+    const int64_t n_entries = (int64_t)g.nx * g.sx * g.ny * g.nz;
+    double kept_entries = (double)g.sx;
+    for (int a = 0; a < 3; ++a) kept_entries *= std::floor((kbox[3 + a] - kbox[a] + (a < 2 ? 2.0 * c->opt_map_grow_margin : 0.0)) * g.inv_h) + 1.0;
+    const bool rederive = !c->opt_map_update || kept_entries < 0.25 * (double)n_entries;
+    const MapBox S = change_box(w, g);
+    if (ensure(c, c->d_tgt_raw_alt, c->tgt_raw_alt_cap, (size_t)kept) || (!rederive && (ensure(c, c->d_tgt_alt, c->tgt_alt_cap, (size_t)kept + kPtsPad) || fields_reserve(c, S))))
+        return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_crop_raw, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_tgt_raw, n, flag_r, pos_r, c->d_tgt_raw_alt);
+    int rebuilt = 0, rc = DCREG_OK;
+    bool swapped = false;
+    if (rederive) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
+        const double old_box[6] = {c->tgt_box[0], c->tgt_box[1], c->tgt_box[2], c->tgt_box[3], c->tgt_box[4], c->tgt_box[5]};
+        c->n_tgt = kept;
+        for (int a = 0; a < 6; ++a) c->tgt_box[a] = kbox[a];
+        rebuilt = 1;
+        rc = map_rebuild(c, true, &swapped);
+        if (rc != DCREG_OK && !swapped) {                               // nothing was swapped in: the old map stands
+            std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
+            c->n_tgt = n;
+            for (int a = 0; a < 6; ++a) c->tgt_box[a] = old_box[a];
+            return rc;
+        }
+    } else {
+        hipLaunchKernelGGL(k_crop_sorted, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_tgt, n, flag_s, pos_s, pos_r, c->d_tgt_alt);
+        HIP_TRY(c, hipMemsetAsync(c->d_tgt_alt + kept, 0, kPtsPad * sizeof(float4), c->stream));
+        hipLaunchKernelGGL(k_crop_table, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_cell_start, n_entries, pos_s);
+        std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
+        std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
+        c->n_tgt = kept;
+        g.pts = c->d_tgt; g.n_pts = kept;
+        for (int a = 0; a < 6; ++a) c->tgt_box[a] = kbox[a];
+        fields_local(c, S);
+        rc = count_occupied(c, g, c->n_cells, &c->occupied_cells);
+        if (rc == DCREG_OK) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { c->fail("crop: %s", hipGetErrorString(e)); rc = DCREG_E_DEVICE; } }
+    }
+    map_changed(c);
+    if (rc) { c->n_tgt = 0; return rc; }
+    update_info(info, n, 0, n - kept, c->n_tgt, rebuilt);
+    return DCREG_OK;
+}
+
+// dcreg_debug_index_check: the whole map's grid built from scratch (same origin, edge, dims, sub-cells) from its raw points, compared entry by entry
+static int index_check(dcreg_ctx *c, int64_t mm[5]) {
+    const WholeMap wm = whole_map(c);
+    const GridDev &g = wm.g;
+    const int64_t n = wm.n, n_cells = (int64_t)g.nx * g.ny * g.nz, n_entries = n_cells * g.sx;
+    const int64_t n_words = (int64_t)g.nz * g.nxb * g.nyw;
+    if (ensure(c, c->d_keys, c->keys_cap, (size_t)n) || ensure(c, c->d_keys2, c->keys2_cap, (size_t)n) ||
+        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+        return DCREG_E_NOMEM;
+    float4 *pts = nullptr; uint32_t *tab = nullptr, *ym = nullptr, *own = nullptr, *own2 = nullptr; uint8_t *gap = nullptr, *gap2 = nullptr;
+    unsigned long long *cnt = nullptr;
+    auto release = [&]() { for (void *p : {(void *)pts, (void *)tab, (void *)ym, (void *)own, (void *)own2, (void *)gap, (void *)gap2, (void *)cnt}) if (p) (void)hipFree(p); };
+    if (hipMalloc((void **)&pts, sizeof(float4) * (size_t)(n + kPtsPad)) != hipSuccess || hipMalloc((void **)&tab, sizeof(uint32_t) * (size_t)(n_entries + 1)) != hipSuccess ||
+        hipMalloc((void **)&ym, sizeof(uint32_t) * (size_t)std::max<int64_t>(n_words, 1)) != hipSuccess ||
+        hipMalloc((void **)&own, sizeof(uint32_t) * (size_t)n_cells) != hipSuccess || hipMalloc((void **)&own2, sizeof(uint32_t) * (size_t)n_cells) != hipSuccess ||
+        hipMalloc((void **)&gap, (size_t)n_cells) != hipSuccess || hipMalloc((void **)&gap2, (size_t)n_cells) != hipSuccess ||
+        hipMalloc((void **)&cnt, sizeof(unsigned long long) * 5) != hipSuccess) {
+        (void)hipGetLastError(); release(); c->fail("no memory for the index check"); return DCREG_E_NOMEM;
+    }
+    HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 5, c->stream));
+    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw, n, g, c->d_keys, c->d_vals);
+    int bits = 1;
+    while (((int64_t)1 << bits) < n_entries && bits < 32) ++bits;
+    int rc = sort_pairs_u32(c, c->d_keys, c->d_keys2, c->d_vals, c->d_vals2, (size_t)n, bits);
+    if (rc) { release(); return rc; }
+    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw, c->d_vals2, n, pts);
+    HIP_TRY(c, hipMemsetAsync(pts + n, 0, kPtsPad * sizeof(float4), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_keys2, n, n_entries, tab, c->d_scratch);
+    hipLaunchKernelGGL(k_count_diff<float4>, dim3(blocks_for(n + kPtsPad, 256)), dim3(256), 0, c->stream, (const float4 *)g.pts, (const float4 *)pts, n + kPtsPad, cnt);
+    hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, g.cell_start, (const uint32_t *)tab, n_entries + 1, cnt + 1);
+    if (g.ymask) {
+        hipLaunchKernelGGL(k_ymask, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, tab, g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw, ym);
+        hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, g.ymask, (const uint32_t *)ym, n_words, cnt + 2);
+    }
+    if (g.gap) {
+        hipLaunchKernelGGL(k_gap_init, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, tab, n_cells, g.sx, gap, own);
+        for (int r = 1; r <= g.gap_cap; ++r)
+            hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap, own, g.nx, g.ny, g.nz, r);
+        if (g.owner) {
+            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, tab, g.nx, n_cells, g.sx, 6u, gap2, own2);
+            for (int r = 1; r <= g.gap_cap; ++r)
+                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap2, own2, g.nx, g.ny, g.nz, r);
+            hipLaunchKernelGGL(k_owner_merge, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, own, own2, n_cells);
+            hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.owner, (const uint32_t *)own, n_cells, cnt + 4);
+        }
+        hipLaunchKernelGGL(k_count_diff<uint8_t>, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.gap, (const uint8_t *)gap, n_cells, cnt + 3);
+    }
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    const hipError_t e0 = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e1 = hipStreamSynchronize(c->stream);
+    release();
+    HIP_TRY(c, e0); HIP_TRY(c, e1);
+    HIP_TRY(c, hipGetLastError());
+    for (int k = 0; k < 5; ++k) mm[k] = (int64_t)h[k];
+    return DCREG_OK;
+}
+
+static int target_get(const dcreg_ctx *cc, float *out, int64_t capacity) {
+    dcreg_ctx *c = const_cast<dcreg_ctx *>(cc);
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    const WholeMap wm = whole_map(c);
+    if (wm.n <= 0) { c->fail("no target"); return DCREG_E_STATE; }
+    if (!out || capacity < wm.n) { c->fail("the output holds %lld points, the map %lld", (long long)capacity, (long long)wm.n); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (ensure(c, c->d_stage, c->stage_cap, (size_t)(3 * wm.n))) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_unpack3, dim3(blocks_for(wm.n, 256)), dim3(256), 0, c->stream, wm.raw, wm.n, c->d_stage);
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_stage, sizeof(float) * (size_t)(3 * wm.n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
 }
 
@@ -1747,7 +2229,8 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
                     c->d_adv_counts, c->d_team_stamps, c->roi_store.raw, c->roi_store.sorted, c->roi_store.cell_start, c->roi_store.gap,
                     c->roi_store.owner, c->roi_store.ymask, c->frames.raw, c->frames.src, c->frames.d_off, c->frames.d_dst, c->frames.d_box,
                     c->frames.state, c->pair_src.raw, c->pair_src.src, c->pair_src.d_off, c->pair_src.d_dst, c->pair_src.d_box, c->pair_src.state,
-                    c->pairs.raw, c->pairs.sorted, c->pairs.table, c->pairs.ymask, c->pairs.d_off, c->pairs.d_cells, c->pairs.d_words, c->pairs.d_grids};
+                    c->pairs.raw, c->pairs.sorted, c->pairs.table, c->pairs.ymask, c->pairs.d_off, c->pairs.d_cells, c->pairs.d_words, c->pairs.d_grids,
+                    c->d_tgt_alt, c->d_tgt_raw_alt, c->d_cell_alt, c->d_map_q, c->d_map_new, c->d_upd, c->d_fgap, c->d_fown};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (LinSlot &S : c->slots) {
         for (void *b : {(void *)S.d_partials, (void *)S.d_poses, (void *)S.d_tickets}) if (b) (void)hipFree(b);
@@ -1823,12 +2306,34 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "dispatch_order") { c->opt_dispatch_order = v != 0.0; c->order_valid = false; }   // heavy query groups first (kernels.hpp k_group_cost)
     else if (k == "keep_source_order") c->opt_keep_source_order = v != 0.0;   // next dcreg_set_source: no Hilbert sort
     else if (k == "gap_field") c->opt_gap_field = v != 0.0;      // takes effect at the next dcreg_set_target
+    else if (k == "map_update") c->opt_map_update = v != 0.0 ? 1 : 0;    // dcreg_target_insert / _crop: 1 merge into the current grid where possible, 0 always re-derive it
+    else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;
 }
 
 int dcreg_set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, double r) { return set_target(c, xyz, n, stride, r, false); }
 int dcreg_set_target_device(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, double r) { return set_target(c, xyz, n, stride, r, true); }
+int dcreg_target_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const double R[9], const double t[3], double min_spacing,
+                        dcreg_map_update *info) {
+    return map_insert(c, xyz, n, stride, false, false, R, t, min_spacing, info);
+}
+int dcreg_target_insert_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const double R[9], const double t[3], double min_spacing,
+                               dcreg_map_update *info) {
+    return map_insert(c, d_xyz, n, stride, true, false, R, t, min_spacing, info);
+}
+int dcreg_target_insert_source(dcreg_ctx *c, const double R[9], const double t[3], double min_spacing, dcreg_map_update *info) {
+    return map_insert(c, nullptr, 0, 3, false, true, R, t, min_spacing, info);
+}
+int dcreg_target_crop(dcreg_ctx *c, const double lo[3], const double hi[3], dcreg_map_update *info) { return map_crop(c, lo, hi, info); }
+int dcreg_target_get(const dcreg_ctx *c, float *xyz_out, int64_t capacity_points) { return target_get(c, xyz_out, capacity_points); }
+int dcreg_debug_index_check(dcreg_ctx *c, int64_t mismatches[5]) {
+    if (!c || !mismatches) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (whole_map(c).n <= 0) { c->fail("no target"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    return index_check(c, mismatches);
+}
 int dcreg_set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, false); }
 int dcreg_set_source_device(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, true); }
 

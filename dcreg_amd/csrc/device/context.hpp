@@ -56,6 +56,19 @@ struct dcreg_ctx {
     uint32_t occupied_cells = 0;
     double radius_hint = 0.0;
     int last_max_ring = 0;
+    // ---- updates of the map in place (context.hip map_insert / map_crop: dcreg_target_insert*, dcreg_target_crop).  The new sorted points,
+    // and the raw ones of a crop, are built beside the current arrays and swapped in at the end; tgt_box = bounds of the map's points
+    float4 *d_tgt_alt = nullptr; size_t tgt_alt_cap = 0;
+    float4 *d_tgt_raw_alt = nullptr; size_t tgt_raw_alt_cap = 0;
+    uint32_t *d_cell_alt = nullptr; size_t cell_alt_cap = 0;
+    float4 *d_map_q = nullptr, *d_map_new = nullptr; size_t map_q_cap = 0, map_new_cap = 0;   // the offered points in the map frame / the appended ones
+    uint32_t *d_upd = nullptr; size_t upd_cap = 0;        // flags, scans, keys of an update
+    uint8_t *d_fgap = nullptr; size_t fgap_cap = 0;       // the fields over the box of a change (k_gap_init_box): plain and dense
+    uint32_t *d_fown = nullptr; size_t fown_cap = 0;
+    double tgt_box[6] = {};
+    double build_per_cell = 0.0;   // points per occupied cell when the grid was last derived (a merge that doubles it re-derives)
+    int opt_map_update = 1;        // 1: merge into the current grid where possible, 0: always re-derive the grid
+    double opt_map_grow_margin = 20.0;   // metres added to each side of the box when an update re-derives the grid
 
     // ---- the WINDOW index of a large map (context.hip roi_ensure).  A prior map whose dense cell table would exceed "max_table_entries" gets
     // coarser cells the larger its extent - a local search then pays for the size of the map.  Single-pose linearisations of such a map

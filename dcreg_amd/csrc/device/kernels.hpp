@@ -1727,6 +1727,286 @@ static __global__ void k_pairs_ymask(const uint32_t *__restrict__ table, const i
     ymask[w] = ymask_word(table + tab_off[j], g.nx, g.ny, g.sx, g.nxb, g.nyw, w - yw_off[j]);
 }
 
+// ---- updates of the resident map (context.hip map_insert / map_crop): points appended to it or cut from it in the grid it has.  The
+// products are bitwise what a full build of that grid gives (dcreg_debug_index_check): the cell-sorted order is (cell, index), so points
+// appended with the next indices go to the end of their cells, and the fields are recomputed over the cells a change can reach.
+struct MapBox { int x0, y0, z0, x1, y1, z1; };   // cells [x0, x1) x [y0, y1) x [z0, z1)
+// the words of an update's single readback (context.hip): bounds of the new / kept points (ordered floats), flags, cell box of the change
+enum : int { kMwMin = 0, kMwMax = 3, kMwOutside = 6, kMwBad = 7, kMwCellMin = 8, kMwCellMax = 11, kMwKeyMin = 14, kMwOccupied = 15, kMwWords = 16 };
+
+__device__ __forceinline__ void wave_atomic_min(uint32_t *dst, uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    if ((threadIdx.x & 63) == 0 && v != 0xFFFFFFFFu) atomicMin(dst, v);
+}
+__device__ __forceinline__ void wave_atomic_max(uint32_t *dst, uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    if ((threadIdx.x & 63) == 0 && v != 0u) atomicMax(dst, v);
+}
+__device__ __forceinline__ void wave_bounds_update(uint32_t *w, bool on, float x, float y, float z) {
+    wave_atomic_min(w + kMwMin + 0, on ? f2ord(x) : 0xFFFFFFFFu);
+    wave_atomic_min(w + kMwMin + 1, on ? f2ord(y) : 0xFFFFFFFFu);
+    wave_atomic_min(w + kMwMin + 2, on ? f2ord(z) : 0xFFFFFFFFu);
+    wave_atomic_max(w + kMwMax + 0, on ? f2ord(x) : 0u);
+    wave_atomic_max(w + kMwMax + 1, on ? f2ord(y) : 0u);
+    wave_atomic_max(w + kMwMax + 2, on ? f2ord(z) : 0u);
+}
+// (the cell box words hold cell + 1, 0 = none: both reductions start from a neutral value)
+__device__ __forceinline__ void wave_cells_update(uint32_t *w, bool on, int cx, int cy, int cz) {
+    wave_atomic_min(w + kMwCellMin + 0, on ? (uint32_t)cx + 1u : 0xFFFFFFFFu);
+    wave_atomic_min(w + kMwCellMin + 1, on ? (uint32_t)cy + 1u : 0xFFFFFFFFu);
+    wave_atomic_min(w + kMwCellMin + 2, on ? (uint32_t)cz + 1u : 0xFFFFFFFFu);
+    wave_atomic_max(w + kMwCellMax + 0, on ? (uint32_t)cx + 1u : 0u);
+    wave_atomic_max(w + kMwCellMax + 1, on ? (uint32_t)cy + 1u : 0u);
+    wave_atomic_max(w + kMwCellMax + 2, on ? (uint32_t)cz + 1u : 0u);
+}
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return fabsf(x) <= 3.4e38f && fabsf(y) <= 3.4e38f && fabsf(z) <= 3.4e38f; }
+
+// q_i = the new point in the map frame (the transform of k_lin), w = i; a non-finite input or result sets words[kMwBad]
+static __global__ void k_map_transform(const float4 *__restrict__ p, int64_t n, PoseArg P, float4 *__restrict__ q, uint32_t *__restrict__ words) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 s = p[i];
+    float qx, qy, qz;
+    body_to_global(P, (double)s.x, (double)s.y, (double)s.z, qx, qy, qz);
+    q[i] = make_float4(qx, qy, qz, __uint_as_float((uint32_t)i));      // (w: where k_knn writes the point's neighbour)
+    if (!finite3(s.x, s.y, s.z) || !finite3(qx, qy, qz)) atomicOr(words + kMwBad, 1u);
+}
+// keep flag of every new point (n + 1 entries, the last 0: its exclusive scan ends in the count): appended unless the map had a point
+// closer than the spacing (d2 of the k = 1 search of dcreg_knn; null = no thinning)
+static __global__ void k_map_keep(int64_t n, const float *__restrict__ d2, float spacing_sq, uint32_t *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    flag[i] = i == n ? 0u : (d2 && d2[i] < spacing_sq) ? 0u : 1u;
+}
+// the kept points, compacted in input order, with their map indices n_old + rank in w; their cell keys in grid g (keys / vals, for the
+// merged path) and whether each lies inside g's box (unclamped cell coordinates of k_cell_keys in range; words[kMwOutside] otherwise);
+// their bounds, cell box and smallest key into words
+static __global__ __launch_bounds__(256) void k_map_append(const float4 *__restrict__ q, int64_t n, const uint32_t *__restrict__ flag,
+                                                          const uint32_t *__restrict__ pos, uint32_t n_old, GridDev g, float4 *__restrict__ out,
+                                                          uint32_t *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t *__restrict__ words) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = i < n && flag[i] != 0u;
+    bool inside = false;
+    int cx = 0, cy = 0, cz = 0;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t key = 0xFFFFFFFFu;
+    if (on) {
+        const uint32_t r = pos[i];
+        v = q[i];
+        v.w = __uint_as_float(n_old + r);
+        out[r] = v;
+        const int nxf = g.nx * g.sx;
+        const double fx = floor(((double)v.x - g.ox) * g.inv_h * (double)g.sx);
+        const double fy = floor(((double)v.y - g.oy) * g.inv_h);
+        const double fz = floor(((double)v.z - g.oz) * g.inv_h);
+        inside = fx >= 0.0 && fx <= (double)(nxf - 1) && fy >= 0.0 && fy <= (double)(g.ny - 1) && fz >= 0.0 && fz <= (double)(g.nz - 1);
+        if (inside) {
+            const int xs = (int)fx;
+            cx = xs / g.sx; cy = (int)fy; cz = (int)fz;
+            key = (uint32_t)(((int64_t)cz * g.ny + cy) * nxf + xs);
+        } else {
+            atomicOr(words + kMwOutside, 1u);
+        }
+        keys[r] = inside ? key : 0u;
+        vals[r] = r;
+    }
+    wave_bounds_update(words, on, v.x, v.y, v.z);
+    wave_cells_update(words, on && inside, cx, cy, cz);
+    wave_atomic_min(words + kMwKeyMin, on && inside ? key : 0xFFFFFFFFu);
+}
+// b[j] = first position behind the cell of the j-th new key in the map as it was; words[kMwOccupied] += cells the insert occupies
+static __global__ void k_map_bpos(const uint32_t *__restrict__ keys, uint32_t m, const uint32_t *__restrict__ cell_start, int sx,
+                                  uint32_t *__restrict__ b, uint32_t *__restrict__ words) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    bool first = false;
+    if (j < m) {
+        const uint32_t k = keys[j], cell = k / (uint32_t)sx;
+        b[j] = cell_start[(size_t)k + 1];
+        first = (j == 0 || keys[j - 1] / (uint32_t)sx != cell) &&
+                cell_start[(size_t)(cell + 1) * sx] == cell_start[(size_t)cell * sx];
+    }
+    const unsigned long long w = __ballot(first);
+    if ((threadIdx.x & 63) == 0 && w) atomicAdd(words + kMwOccupied, (uint32_t)__popcll(w));
+}
+// old point i moves behind the new points of the cells before its own: the b[j] <= i
+static __global__ void k_map_merge_old(const float4 *__restrict__ old, uint32_t n_old, const uint32_t *__restrict__ b, uint32_t m, float4 *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_old) return;
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (b[mid] <= i) lo = mid + 1; else hi = mid;
+    }
+    out[(size_t)i + lo] = old[i];
+}
+// new point j (key order, input order within a cell) goes behind its cell's old points and the j new points before it
+static __global__ void k_map_merge_new(const float4 *__restrict__ pts, const uint32_t *__restrict__ order, const uint32_t *__restrict__ b, uint32_t m,
+                                       float4 *__restrict__ out) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) out[(size_t)b[j] + j] = pts[order[j]];
+}
+// cell_start[c] += new keys below c, for the entries first .. last (in place: every entry reads only itself)
+static __global__ void k_map_table_insert(uint32_t *__restrict__ cell_start, int64_t first, int64_t last, const uint32_t *__restrict__ keys, uint32_t m) {
+    const int64_t c = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > last) return;
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((int64_t)keys[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    cell_start[c] += lo;
+}
+
+struct CropBox { double lo[3], hi[3]; };
+// keep flags of a crop (n + 1 entries, the last 0)
+static __global__ void k_crop_flags(const float4 *__restrict__ p, int64_t n, CropBox bx, uint32_t *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    bool keep = false;
+    if (i < n) {
+        const float4 v = p[i];
+        keep = bx.lo[0] <= (double)v.x && (double)v.x <= bx.hi[0] && bx.lo[1] <= (double)v.y && (double)v.y <= bx.hi[1] &&
+               bx.lo[2] <= (double)v.z && (double)v.z <= bx.hi[2];
+    }
+    flag[i] = keep ? 1u : 0u;
+}
+// bounds of the kept points; cell box (the cells k_cell_keys put them in) of the dropped ones
+static __global__ __launch_bounds__(256) void k_crop_scan_box(const float4 *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ flag, GridDev g,
+                                                             uint32_t *__restrict__ words) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = i < n;
+    const float4 v = in ? sorted[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool keep = in && flag[i] != 0u, drop = in && !keep;
+    int cx = 0, cy = 0, cz = 0;
+    if (drop) {
+        const int nxf = g.nx * g.sx;
+        cx = clampi((int)floor(((double)v.x - g.ox) * g.inv_h * (double)g.sx), 0, nxf - 1) / g.sx;
+        cy = clampi((int)floor(((double)v.y - g.oy) * g.inv_h), 0, g.ny - 1);
+        cz = clampi((int)floor(((double)v.z - g.oz) * g.inv_h), 0, g.nz - 1);
+    }
+    wave_bounds_update(words, keep, v.x, v.y, v.z);
+    wave_cells_update(words, drop, cx, cy, cz);
+}
+// stable compaction of the raw points (w = new index) and of the cell-sorted ones (w = the new index of their raw point)
+static __global__ void k_crop_raw(const float4 *__restrict__ raw, int64_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                  float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    float4 v = raw[i];
+    v.w = __uint_as_float(pos[i]);
+    out[pos[i]] = v;
+}
+static __global__ void k_crop_sorted(const float4 *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                     const uint32_t *__restrict__ raw_pos, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    float4 v = sorted[i];
+    v.w = __uint_as_float(raw_pos[__float_as_uint(v.w)]);
+    out[pos[i]] = v;
+}
+// cell_start[c] = kept points in front of it (in place)
+static __global__ void k_crop_table(uint32_t *__restrict__ cell_start, int64_t n_entries, const uint32_t *__restrict__ pos) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c <= n_entries) cell_start[c] = pos[cell_start[c]];
+}
+// occupied cells of a table (the count build_index reports)
+static __global__ void k_count_occupied(const uint32_t *__restrict__ cell_start, int64_t n_cells, int sx, uint32_t *__restrict__ count) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool occ = c < n_cells && cell_start[(c + 1) * sx] > cell_start[c * sx];
+    const unsigned long long m = __ballot(occ);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, (uint32_t)__popcll(m));
+}
+
+// row words of the words whose 16 x 32 cells meet the cells [x0, x1) x [y0, y1) x [z0, z1) of a change (k_ymask there)
+static __global__ void k_ymask_box(const uint32_t *__restrict__ cell_start, int nx, int ny, int sx, int nxb, int nyw, int xb0, int n_xb, int yw0,
+                                   int n_yw, int z0, int n_z, uint32_t *__restrict__ ymask) {
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= (int64_t)n_xb * n_yw * n_z) return;
+    const int yw = yw0 + (int)(l % n_yw), xb = xb0 + (int)((l / n_yw) % n_xb), z = z0 + (int)(l / ((int64_t)n_yw * n_xb));
+    const int64_t w = ((int64_t)z * nxb + xb) * nyw + yw;
+    ymask[w] = ymask_word(cell_start, nx, ny, sx, nxb, nyw, w);
+}
+// The gap field and owners over a box E of cells (scratch indexed inside E, owners as cells of the whole grid): k_gap_init /
+// k_gap_init_dense / k_gap_dilate restricted to E.  A cell's value after ring r depends only on the cells within r of it, so every cell
+// at least `rings` inside E - the box B that k_gap_store_box writes back - comes out as a full build gives it.
+__device__ __forceinline__ int64_t box_cell(const MapBox &E, int nx, int ny, int64_t l) {
+    const int ex = E.x1 - E.x0, ey = E.y1 - E.y0;
+    const int x = E.x0 + (int)(l % ex), y = E.y0 + (int)((l / ex) % ey), z = E.z0 + (int)(l / ((int64_t)ex * ey));
+    return ((int64_t)z * ny + y) * nx + x;
+}
+static __global__ void k_gap_init_box(const uint32_t *__restrict__ cell_start, int nx, int ny, int sx, MapBox E, int dense, uint32_t min_pts,
+                                      uint8_t *__restrict__ gap, uint32_t *__restrict__ owner) {
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= (int64_t)(E.x1 - E.x0) * (E.y1 - E.y0) * (E.z1 - E.z0)) return;
+    const int64_t c = box_cell(E, nx, ny, l);
+    const int x = (int)(c % nx);
+    const int64_t row = c - x;
+    bool seed = cell_start[(c + 1) * sx] > cell_start[c * sx];
+    if (dense) seed = seed && cell_start[(row + min(x + 2, nx)) * sx] - cell_start[(row + max(x - 1, 0)) * sx] >= min_pts;
+    gap[l] = seed ? 0 : 255;
+    owner[l] = seed ? (uint32_t)c : kNoIdx;
+}
+static __global__ void k_gap_dilate_box(uint8_t *gap, uint32_t *owner, int nx, int ny, MapBox E, int ring) {
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int ex = E.x1 - E.x0, ey = E.y1 - E.y0, ez = E.z1 - E.z0;
+    if (l >= (int64_t)ex * ey * ez || gap[l] != 255) return;
+    const int lx = (int)(l % ex), ly = (int)((l / ex) % ey), lz = (int)(l / ((int64_t)ex * ey));
+    const int x = E.x0 + lx, y = E.y0 + ly, z = E.z0 + lz;
+    const uint8_t want = (uint8_t)(ring - 1);
+    uint32_t own = kNoIdx;
+    int64_t best = INT64_MAX;
+    for (int dz = -1; dz <= 1; ++dz) {
+        const int zz = lz + dz;
+        if (zz < 0 || zz >= ez) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int yy = ly + dy;
+            if (yy < 0 || yy >= ey) continue;
+            const int64_t row = ((int64_t)zz * ey + yy) * ex;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int xx = lx + dx;
+                if (xx < 0 || xx >= ex || gap[row + xx] != want) continue;
+                const uint32_t o = owner[row + xx];
+                const int64_t ox = o % (uint32_t)nx, oy = (o / (uint32_t)nx) % (uint32_t)ny, oz = o / ((uint32_t)nx * (uint32_t)ny);
+                const int64_t d = (ox - x) * (ox - x) + (oy - y) * (oy - y) + (oz - z) * (oz - z);
+                if (d < best) { best = d; own = o; }
+            }
+        }
+    }
+    if (own != kNoIdx) { gap[l] = (uint8_t)ring; owner[l] = own; }
+}
+// B (inside E) back into the grid's field: the plain field's distance, the dense owner where there is one (k_owner_merge)
+static __global__ void k_gap_store_box(const uint8_t *__restrict__ gap_e, const uint32_t *__restrict__ own_e, const uint32_t *__restrict__ dense_e,
+                                       int nx, int ny, MapBox E, MapBox B, uint8_t *__restrict__ gap, uint32_t *__restrict__ owner) {
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int bx = B.x1 - B.x0, by = B.y1 - B.y0;
+    if (l >= (int64_t)bx * by * (B.z1 - B.z0)) return;
+    const int x = B.x0 + (int)(l % bx), y = B.y0 + (int)((l / bx) % by), z = B.z0 + (int)(l / ((int64_t)bx * by));
+    const int64_t e = ((int64_t)(z - E.z0) * (E.y1 - E.y0) + (y - E.y0)) * (E.x1 - E.x0) + (x - E.x0);
+    const int64_t c = ((int64_t)z * ny + y) * nx + x;
+    gap[c] = gap_e[e];
+    owner[c] = (dense_e && dense_e[e] != kNoIdx) ? dense_e[e] : own_e[e];
+}
+
+// dcreg_target_get: the map's points in index order, 3 floats each
+static __global__ void k_unpack3(const float4 *__restrict__ p, int64_t n, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 v = p[i];
+    out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
+}
+// dcreg_debug_index_check: entries of two arrays that differ (bitwise)
+template <class T>
+static __global__ void k_count_diff(const T *__restrict__ a, const T *__restrict__ b, int64_t n, unsigned long long *__restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool diff = false;
+    if (i < n) {
+        const unsigned char *x = (const unsigned char *)(a + i), *y = (const unsigned char *)(b + i);
+        for (int k = 0; k < (int)sizeof(T); ++k) diff |= x[k] != y[k];
+    }
+    const unsigned long long m = __ballot(diff);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, (unsigned long long)__popcll(m));
+}
+
 // reductions for dcreg_p2p_error: sum sqrt(d2), sum d2 [dist<thr], count  (deterministic two-stage)
 static __global__ __launch_bounds__(kBlock) void k_p2p_partial(const float *__restrict__ d2, int64_t n, double thr, double *__restrict__ part) {
     __shared__ double tile[kBlock / 64][4];

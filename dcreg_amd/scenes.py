@@ -254,6 +254,26 @@ def map_frames(tgt, poses, n_frame=8_000, seed=0, frame_range=30.0, noise=0.02):
     return out
 
 
+def drive(world, n_keyframes, step=1.5, n_frame=8_000, seed=0, start=None, heading=0.0, yaw_rate=0.01, frame_range=30.0, noise=0.02):
+    """A drive through `world` for a growing map: n_keyframes sensor poses (4x4, sensor -> map) `step` metres apart along a gently curving
+    path (heading in radians, yaw_rate radians per keyframe) from `start` (x, y; default: frame_range / 2 inside the world's x minimum, at
+    its y centre), the sensor 1.8 m above the world's median height - a path that leaves the box of its first frames - and the frames cut
+    from `world` there by map_frames.  -> (poses, frames)"""
+    world = np.asarray(world, np.float32)
+    lo, hi = world.min(0).astype(np.float64), world.max(0).astype(np.float64)
+    x, y = (lo[0] + 0.5 * frame_range, 0.5 * (lo[1] + hi[1])) if start is None else (float(start[0]), float(start[1]))
+    z = float(np.median(world[:, 2])) + 1.8
+    poses = []
+    yaw = heading
+    for _ in range(n_keyframes):
+        poses.append(pose6d_matrix(x, y, z, 0.0, 0.0, yaw))
+        x += step * np.cos(yaw)
+        y += step * np.sin(yaw)
+        yaw += yaw_rate
+    frames = map_frames(world, poses, n_frame, seed=seed, frame_range=frame_range, noise=noise)
+    return poses, frames
+
+
 def scan_pairs(tgt, poses, n_frame=8_000, seed=0, mode="submap", n_submap=100_000, submap_radius=40.0, frame_range=30.0, noise=0.02):
     """Scan pairs cut out of an existing map at sensor poses (4x4, sensor -> map), sources made by map_frames.  mode "submap": pair k = the
     frame at poses[k] against a submap crop - up to n_submap map points within submap_radius metres (in x-y) of poses[k]'s position, in

@@ -136,6 +136,10 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *   "max_table_entries" default 2^30 (at most 2^31): entries of the dense cell table - one uint32 per x sub-cell of the target's
  *                   bounding box; a map whose cells at the wanted edge would need more gets fewer x sub-cells first and a larger cell
  *                   edge after that (next dcreg_set_target);
+ *   "map_update"    1 (default) = dcreg_target_insert* / dcreg_target_crop update the index in the grid it has where they can (new
+ *                   points inside its box, density at most twice what the cell edge was sized for), 0 = every update re-derives the grid;
+ *   "map_grow_margin" default 20: metres added on each side of the map's box in x and y (not z) when an update re-derives the grid (a
+ *                   map that grows along a path re-derives it once per that many metres, not at every keyframe);
  *   "roi_index", "roi_margin": the WINDOW index of a large map.  A map whose table ran into that budget is searched through cells that
  *                   grow with its extent; dcreg_linearize / the engines' single-pose launches therefore search such a map through a
  *                   second index over the map's points inside a box around the transformed source cloud (its bounding box at the pose +
@@ -215,6 +219,45 @@ int dcreg_linearize_batch_begin_warm(dcreg_ctx *, int slot, int n_poses, const d
 int dcreg_knn(dcreg_ctx *, const float *q_xyz, int64_t n, int64_t stride_floats, int k, double max_radius,
               int32_t *idx, float *d2);
 int dcreg_index_info_get(const dcreg_ctx *, dcreg_index_info *);
+
+/* ---------------- updates of the resident map ----------------
+ * A mapping front-end grows its map at every keyframe and now and then drops what lies far behind.  These calls do it on the device,
+ * without a host copy of the map or a full index build.  For every call that returns DCREG_OK, every later call behaves bitwise as on a
+ * context with the same options given dcreg_set_target(M', search_radius_hint of the last dcreg_set_target), M' = the updated cloud in
+ * index order (dcreg_target_get) - linearisations, the engines, dcreg_register_frames, dcreg_knn, dcreg_p2p_error, the window index.
+ * An update that changes the map drops what dcreg_set_target drops: neighbour states (own, reserved, of loaded frames), the dispatch
+ * estimate, the window index and the kd-tree comparator.  info may be NULL.
+ * Refusals leave the map, its index and every state as they were: DCREG_E_INVALID (null or negative arguments, stride < 3, non-finite
+ * coordinates or pose, more than 2^31 - 1 points in all, a crop that would keep no point), DCREG_E_STATE (no target, no source for
+ * _insert_source, a linearisation in flight), DCREG_E_NOMEM (the new arrays are built beside the old ones and swapped in at the end;
+ * one exception: on a context whose window index was active, the switch back to the whole map's index has already dropped the neighbour
+ * states - results are unaffected).  An insert merged into the current grid whose follow-up re-derivation (density doubled) finds no
+ * memory returns DCREG_OK with rebuilt = 0: the merged map is complete and exact, and the next update tries again.
+ * Memory: after the first update the context keeps a second sorted array and, after a crop, a second raw array (16 B per map point
+ * each); after a re-derivation a second cell table; and field scratch of 10 B per cell of the last change's box grown by two field
+ * radii.  They are reused by later updates and freed with the context. */
+typedef struct dcreg_map_update {
+    int64_t n_offered;   /* points passed in (insert) / map points before the call (crop) */
+    int64_t n_added;     /* points appended to the map (insert, after min_spacing) */
+    int64_t n_removed;   /* points dropped (crop) */
+    int64_t n_target;    /* map points after the call */
+    int rebuilt;         /* 0 = merged into the current grid, 1 = grid re-derived */
+    int reserved_;
+} dcreg_map_update;
+/* Point i becomes q_i = R p_i + t (double arithmetic, float store: the transform of the linearisation) and is appended with index
+ * n_old + (its rank among the appended points, input order) unless min_spacing > 0 and the map as it stood before the call has a point
+ * with float d2 < (float)(min_spacing^2) to it (d2 as dcreg_knn with k = 1 computes it).  New points are not thinned against each
+ * other.  An insert that appends nothing changes nothing.  _device: d_xyz as dcreg_set_target_device reads it. */
+int dcreg_target_insert(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const double R[9], const double t[3], double min_spacing,
+                        dcreg_map_update *info);
+int dcreg_target_insert_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const double R[9], const double t[3],
+                               double min_spacing, dcreg_map_update *info);
+/* the source cloud of the last dcreg_set_source, in its input order (set_source + dcreg_icp_run + insert_source(result): no second upload) */
+int dcreg_target_insert_source(dcreg_ctx *, const double R[9], const double t[3], double min_spacing, dcreg_map_update *info);
+/* keeps the points with lo[a] <= p[a] <= hi[a] on every axis (float coordinate widened to double), renumbered 0.. in their old order */
+int dcreg_target_crop(dcreg_ctx *, const double lo[3], const double hi[3], dcreg_map_update *info);
+/* the map in index order, 3 floats per point; DCREG_E_INVALID when capacity_points is below the map's size */
+int dcreg_target_get(const dcreg_ctx *, float *xyz_out, int64_t capacity_points);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */

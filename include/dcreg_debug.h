@@ -144,6 +144,12 @@ int dcreg_pairs_reset_state(dcreg_ctx *, int64_t state_id);
 int dcreg_pairs_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                             const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
 
+/* Checks the whole map's index after updates (dcreg_target_insert*, dcreg_target_crop): rebuilds the current grid (same origin, cell
+ * edge, dims and x sub-cells) from scratch in scratch buffers from the raw points and counts the entries that differ, bitwise:
+ * mismatches[0] sorted points (kPtsPad tail included), [1] cell table, [2] row words, [3] gap field, [4] owners.  All zero = the index is
+ * exactly what a full build of that grid gives. */
+int dcreg_debug_index_check(dcreg_ctx *, int64_t mismatches[5]);
+
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */
 void dcreg_set_error_message(dcreg_ctx *, const char *msg);
 
