@@ -122,6 +122,7 @@ _STRUCTS = {"dcreg_lin_params": LinParams, "dcreg_lin_out": LinOut, "dcreg_lin_d
             "dcreg_index_info": IndexInfo, "dcreg_config": Config, "dcreg_analysis": Analysis,
             "dcreg_iter_log": IterLog, "dcreg_icp_result": IcpResult, "dcreg_trial_result": TrialResult,
             "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats}
+# (VoxelParams / VoxelInfo are defined below and join _STRUCTS there)
 
 # every symbol include/dcreg.h and include/dcreg_debug.h declare
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_void_p)      # dcreg_reduce_fn
@@ -142,6 +143,8 @@ EXPORTS = [
     "dcreg_register_frames", "dcreg_frames_load", "dcreg_frames_reserve_states", "dcreg_frames_reset_state", "dcreg_frames_batch_begin",
     "dcreg_register_pairs", "dcreg_pairs_plan", "dcreg_pairs_sources_load", "dcreg_pairs_build", "dcreg_pairs_reserve_states",
     "dcreg_pairs_reset_state", "dcreg_pairs_batch_begin",
+    "dcreg_voxel_downsample", "dcreg_voxel_downsample_device", "dcreg_set_source_voxel", "dcreg_set_source_voxel_device",
+    "dcreg_set_target_voxel", "dcreg_set_target_voxel_device",
 ]
 
 _lib = None
@@ -150,6 +153,60 @@ _lib = None
 class MapUpdate(C.Structure):
     _fields_ = [("n_offered", C.c_int64), ("n_added", C.c_int64), ("n_removed", C.c_int64), ("n_target", C.c_int64), ("rebuilt", C.c_int),
                 ("reserved_", C.c_int)]
+
+
+class VoxelParams(C.Structure):
+    _fields_ = [("leaf", C.c_double * 3), ("mode", C.c_int), ("min_points", C.c_int)]
+
+
+class VoxelInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_voxels", C.c_int64), ("n_out", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_voxel_params": VoxelParams, "dcreg_voxel_info": VoxelInfo})
+VOXEL_MODES = {"centroid": 0, "first": 1}      # DCREG_VOXEL_CENTROID / DCREG_VOXEL_FIRST
+
+
+def voxel_params(leaf, mode="centroid", min_points=1):
+    """dcreg_voxel_params of a leaf (one edge for a cubic voxel, or three), a mode name and PCL's minimum points per voxel"""
+    lf = np.asarray(leaf, dtype=np.float64).reshape(-1)
+    if lf.size == 1:
+        lf = np.repeat(lf, 3)
+    if lf.size != 3:
+        raise ValueError("voxel leaf: one edge or three are expected, got %d values" % lf.size)
+    if not np.all(np.isfinite(lf)) or not np.all(lf > 0.0):
+        raise ValueError("voxel leaf: finite edges > 0 are expected, got %s" % (lf.tolist(),))
+    if mode not in VOXEL_MODES:
+        raise ValueError("voxel mode: one of %s is expected, got %r" % (sorted(VOXEL_MODES), mode))
+    p = VoxelParams()
+    for a in range(3):
+        p.leaf[a] = float(lf[a])
+    p.mode = VOXEL_MODES[mode]
+    p.min_points = int(min_points)
+    return p
+
+
+def _voxel_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_voxels": i.n_voxels, "n_out": i.n_out}
+
+
+def _clouds(clouds, what):
+    """(xyz [N, c] float32, offsets [n + 1] int64, was_list) of a list of [n_i, c] float32 arrays or an (xyz, offsets) pair"""
+    if isinstance(clouds, tuple):
+        if len(clouds) != 2:
+            raise ValueError("%s: an (xyz, offsets) pair is expected" % what)
+        xyz = _points(clouds[0], what)
+        off = np.ascontiguousarray(clouds[1], dtype=np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0) or off[-1] != len(xyz):
+            raise ValueError("%s: offsets must start at 0, not decrease and end at the number of points (%d)" % (what, len(xyz)))
+        return xyz, off, False
+    parts = [_points(f, what) for f in clouds]
+    if len({f.shape[1] for f in parts}) > 1:
+        raise ValueError("%s: every cloud needs the same number of columns, got %s" % (what, sorted({f.shape[1] for f in parts})))
+    off = np.zeros(len(parts) + 1, np.int64)
+    off[1:] = np.cumsum([len(f) for f in parts])
+    xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
+    return xyz, off, True
 
 
 def _pose_rt(T, what):
@@ -259,6 +316,12 @@ def load():
         L.dcreg_target_crop.argtypes = [vp, dp, dp, C.POINTER(MapUpdate)]
         L.dcreg_target_get.argtypes = [vp, fp, C.c_int64]
         L.dcreg_debug_index_check.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.dcreg_voxel_downsample.argtypes = [vp, C.c_int, vp, i64p, C.c_int64, C.POINTER(VoxelParams), vp, C.c_int64, i64p, C.POINTER(VoxelInfo)]
+    L.dcreg_voxel_downsample_device.argtypes = L.dcreg_voxel_downsample.argtypes
+    for name in ("dcreg_set_source_voxel", "dcreg_set_source_voxel_device"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(VoxelParams), C.POINTER(VoxelInfo)]
+    for name in ("dcreg_set_target_voxel", "dcreg_set_target_voxel_device"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(VoxelParams), C.c_double, C.POINTER(VoxelInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -462,6 +525,72 @@ class Context:
 
     def set_source_device(self, dev_ptr, n, stride):
         self._check(self._L.dcreg_set_source_device(self._h, C.c_void_p(dev_ptr), n, stride), "dcreg_set_source_device")
+
+    def voxel_downsample(self, clouds, leaf, mode="centroid", min_points=1):
+        """dcreg_voxel_downsample: one point per occupied voxel of every cloud (include/dcreg.h has the rules).  clouds = a list of [n_i, c]
+        float32 arrays, or (xyz [N, c], offsets [n + 1]) as register_frames takes them (c >= 3 columns, x y z first); leaf = one edge (cubic
+        voxels) or three; mode "centroid" or "first"; min_points as PCL's setMinimumPointsNumberPerVoxel.  -> (the output in the shape of
+        the input: a list of [m_i, 3] float32 arrays, or (xyz [M, 3], offsets [n + 1]); dict n_in / n_finite / n_voxels / n_out)"""
+        p = voxel_params(leaf, mode, min_points)
+        xyz, off, was_list = _clouds(clouds, "voxel_downsample")
+        n = len(off) - 1
+        out = np.empty((max(int(off[-1]), 1), 3), np.float32)
+        out_off = np.zeros(n + 1, np.int64)
+        info = VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_voxel_downsample(self._h, n, xyz.ctypes.data, off.ctypes.data_as(i64p), xyz.shape[1], C.byref(p), out.ctypes.data,
+                                                   int(off[-1]), out_off.ctypes.data_as(i64p), C.byref(info)), "dcreg_voxel_downsample")
+        out = out[:int(out_off[-1])]
+        if was_list:
+            return [out[out_off[k]:out_off[k + 1]] for k in range(n)], _voxel_info_dict(info)
+        return (out, out_off), _voxel_info_dict(info)
+
+    def voxel_downsample_device(self, dev_ptr, offsets, stride, dev_out_ptr, capacity, leaf, mode="centroid", min_points=1):
+        """dcreg_voxel_downsample_device: clouds in device memory (dev_ptr, stride floats per point, offsets on the host), the output to
+        the device buffer dev_out_ptr (3 floats per point, capacity points).  -> (out_offsets [n + 1], info dict)"""
+        p = voxel_params(leaf, mode, min_points)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError("voxel_downsample_device: offsets must start at 0 and not decrease")
+        n = len(off) - 1
+        out_off = np.zeros(n + 1, np.int64)
+        info = VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_voxel_downsample_device(self._h, n, C.c_void_p(dev_ptr), off.ctypes.data_as(i64p), int(stride), C.byref(p),
+                                                          C.c_void_p(dev_out_ptr), int(capacity), out_off.ctypes.data_as(i64p), C.byref(info)),
+                    "dcreg_voxel_downsample_device")
+        return out_off, _voxel_info_dict(info)
+
+    def set_source_voxel(self, xyz, leaf, mode="centroid", min_points=1):
+        """dcreg_set_source_voxel: the cloud voxelised on the device and kept as the source (bitwise set_source(voxel_downsample(xyz)))"""
+        p = voxel_params(leaf, mode, min_points)
+        a = _points(xyz, "set_source_voxel")
+        info = VoxelInfo()
+        self._check(self._L.dcreg_set_source_voxel(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(p), C.byref(info)), "dcreg_set_source_voxel")
+        return _voxel_info_dict(info)
+
+    def set_source_voxel_device(self, dev_ptr, n, stride, leaf, mode="centroid", min_points=1):
+        p = voxel_params(leaf, mode, min_points)
+        info = VoxelInfo()
+        self._check(self._L.dcreg_set_source_voxel_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(p), C.byref(info)),
+                    "dcreg_set_source_voxel_device")
+        return _voxel_info_dict(info)
+
+    def set_target_voxel(self, xyz, search_radius, leaf, mode="centroid", min_points=1):
+        """dcreg_set_target_voxel: the cloud voxelised on the device and kept as the map (bitwise set_target(voxel_downsample(xyz)))"""
+        p = voxel_params(leaf, mode, min_points)
+        a = _points(xyz, "set_target_voxel")
+        info = VoxelInfo()
+        self._check(self._L.dcreg_set_target_voxel(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(p), float(search_radius), C.byref(info)),
+                    "dcreg_set_target_voxel")
+        return _voxel_info_dict(info)
+
+    def set_target_voxel_device(self, dev_ptr, n, stride, search_radius, leaf, mode="centroid", min_points=1):
+        p = voxel_params(leaf, mode, min_points)
+        info = VoxelInfo()
+        self._check(self._L.dcreg_set_target_voxel_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(p), float(search_radius),
+                                                          C.byref(info)), "dcreg_set_target_voxel_device")
+        return _voxel_info_dict(info)
 
     def index_info(self):
         info = IndexInfo()

@@ -20,6 +20,7 @@ SOURCES = [
     "device/metrics.hip",
     "device/kdtree.hip",
     "device/exchange.hip",
+    "device/voxel.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

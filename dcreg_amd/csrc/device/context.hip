@@ -21,31 +21,6 @@
 
 namespace dcreg {
 
-#define HIP_TRY(ctx, expr)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return DCREG_E_DEVICE;                                                               \
-        }                                                                                        \
-    } while (0)
-
-template <typename T>
-static int ensure(dcreg_ctx *c, T *&ptr, size_t &cap, size_t need) {
-    if (need <= cap && ptr) return DCREG_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr; cap = 0;
-    size_t n = std::max<size_t>(need, 1);
-    hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();      // (the failed allocation must not surface as the "launch error" of whatever is queued next)
-        c->fail("hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e));
-        return DCREG_E_NOMEM;
-    }
-    cap = n;
-    return DCREG_OK;
-}
-
 constexpr double kCountScale = 67108864.0;      // 2^26 (search.hpp LinArgs::count_scale)
 constexpr size_t kSearchCountBytes = 64 * kCounterStride * sizeof(uint32_t);     // 64 counters, one per 128-byte line
 static inline unsigned blocks_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
@@ -408,7 +383,7 @@ int refuse_in_flight(dcreg_ctx *c) {
 // host, no stream synchronise in dcreg_set_source
 static bool small_host_frame(int64_t n, int64_t stride) { return n <= 65536 && n * stride <= (int64_t)1 << 20; }
 
-static int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, float4 *&raw, size_t &raw_cap) {
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, float4 *&raw, size_t &raw_cap) {
     if (!xyz || n < 0 || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("cloud too large (%lld points)", (long long)n); return DCREG_E_INVALID; }
     if (ensure(c, raw, raw_cap, (size_t)n)) return DCREG_E_NOMEM;
@@ -447,6 +422,7 @@ static int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t strid
     return DCREG_OK;
 }
 
+static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double radius_hint);
 static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, double radius_hint, bool on_device) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
@@ -459,6 +435,12 @@ static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     rc = device_bounds(c, c->d_aligned, n, box, box + 3);
     if (rc) return rc;
     for (int a = 0; a < 6; ++a) if (!std::isfinite(box[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
+    return target_commit(c, n, box, radius_hint);
+}
+
+// the checked cloud of n points in c->d_aligned (packed as k_pack packs it), with bounds box = {min xyz, max xyz}, becomes the target
+static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double radius_hint) {
+    int rc;
     (void)roi_deactivate(c);             // the new map goes into the whole map's buffers; a window of the old one means nothing
     c->roi_built = false; c->whole_capped = false;
     std::swap(c->d_tgt_raw, c->d_aligned); std::swap(c->tgt_raw_cap, c->aligned_cap);
@@ -971,6 +953,7 @@ static void curve_frame(int64_t n, const double mn[3], const double mx[3], doubl
     while (levels < 21 && ((int64_t)1 << (3 * (levels - 4))) < n) ++levels;
 }
 
+static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const double mx[3], bool must_wait);
 static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
@@ -989,6 +972,12 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
         if (rc) return rc;
     }
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("source cloud has non-finite coordinates"); return DCREG_E_INVALID; }
+    return source_commit(c, n, mn, mx, !small_host);
+}
+
+// the checked cloud of n points in c->d_aligned (packed as k_pack packs it), with bounds mn .. mx, becomes the source
+static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const double mx[3], bool must_wait) {
+    int rc;
     std::swap(c->d_src_raw, c->d_aligned); std::swap(c->src_raw_cap, c->aligned_cap);
     for (int a = 0; a < 3; ++a) { c->src_mn[a] = mn[a]; c->src_mx[a] = mx[a]; }
     double inv_q;
@@ -1017,7 +1006,6 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     // A small frame from a host buffer went through the context's pinned block (upload_cloud): the caller's buffer is consumed, whatever
     // kind of memory it is, and nothing has to be waited for - the first linearisation queues behind the sort, and a device fault surfaces
     // at that linearisation (include/dcreg.h says so).  Everything else is waited for here.
-    const bool must_wait = !small_host;
     if (must_wait) HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     c->n_src = n;
@@ -2230,7 +2218,9 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
                     c->roi_store.owner, c->roi_store.ymask, c->frames.raw, c->frames.src, c->frames.d_off, c->frames.d_dst, c->frames.d_box,
                     c->frames.state, c->pair_src.raw, c->pair_src.src, c->pair_src.d_off, c->pair_src.d_dst, c->pair_src.d_box, c->pair_src.state,
                     c->pairs.raw, c->pairs.sorted, c->pairs.table, c->pairs.ymask, c->pairs.d_off, c->pairs.d_cells, c->pairs.d_words, c->pairs.d_grids,
-                    c->d_tgt_alt, c->d_tgt_raw_alt, c->d_cell_alt, c->d_map_q, c->d_map_new, c->d_upd, c->d_fgap, c->d_fown};
+                    c->d_tgt_alt, c->d_tgt_raw_alt, c->d_cell_alt, c->d_map_q, c->d_map_new, c->d_upd, c->d_fgap, c->d_fown,
+                    c->vox.pts, c->vox.seg, c->vox.rel, c->vox.head, c->vox.incl, c->vox.start, c->vox.keep, c->vox.pos, c->vox.vout, c->vox.out,
+                    c->vox.d_off, c->vox.cnt};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (LinSlot &S : c->slots) {
         for (void *b : {(void *)S.d_partials, (void *)S.d_poses, (void *)S.d_tickets}) if (b) (void)hipFree(b);
@@ -2336,6 +2326,43 @@ int dcreg_debug_index_check(dcreg_ctx *c, int64_t mismatches[5]) {
 }
 int dcreg_set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, false); }
 int dcreg_set_source_device(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, true); }
+
+// dcreg_set_source_voxel* / dcreg_set_target_voxel*: the voxel pass writes its output packed into c->d_aligned - where set_source / set_target
+// upload and check a cloud - with its bounds from the pass's one readback, and the commit of the plain calls takes it from there
+static void voxel_info(dcreg_voxel_info *info, const VoxelResult &r) {
+    if (info) { info->n_in = r.n_in; info->n_finite = r.n_finite; info->n_voxels = r.n_voxels; info->n_out = r.n_out; }
+}
+static int set_cloud_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_voxel_params *p, bool target,
+                           double radius_hint, dcreg_voxel_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (n <= 0) { c->fail("%s cloud is null or empty", target ? "target" : "measure"); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t off[2] = {0, n};
+    VoxelResult r;
+    int rc = voxel_pass(c, 1, xyz, off, stride, on_device, p, true, r);
+    if (rc) return rc;
+    voxel_info(info, r);
+    if (r.n_out <= 0) { c->fail("no point of the %s cloud is left after the voxel pass", target ? "target" : "measure"); return DCREG_E_INVALID; }
+    if (target) {
+        const double box[6] = {r.mn[0], r.mn[1], r.mn[2], r.mx[0], r.mx[1], r.mx[2]};
+        return target_commit(c, r.n_out, box, radius_hint);
+    }
+    return source_commit(c, r.n_out, r.mn, r.mx, true);
+}
+int dcreg_set_source_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, dcreg_voxel_info *info) {
+    return set_cloud_voxel(c, xyz, n, stride, false, p, false, 0.0, info);
+}
+int dcreg_set_source_voxel_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, dcreg_voxel_info *info) {
+    return set_cloud_voxel(c, d_xyz, n, stride, true, p, false, 0.0, info);
+}
+int dcreg_set_target_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, double r, dcreg_voxel_info *info) {
+    return set_cloud_voxel(c, xyz, n, stride, false, p, true, r, info);
+}
+int dcreg_set_target_voxel_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, double r,
+                                  dcreg_voxel_info *info) {
+    return set_cloud_voxel(c, d_xyz, n, stride, true, p, true, r, info);
+}
 
 int dcreg_default_lin_params(dcreg_lin_params *p, double radius) {
     if (!p) return DCREG_E_INVALID;

@@ -4,10 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <vector>
 
+#include "../../../include/dcreg.h"
 #include "kernels.hpp"
 
 struct dcreg_lin_params;
@@ -174,6 +176,21 @@ struct dcreg_ctx {
         float radius_sq_f = 0.f;                               // the search bound the grids' rings were counted for (LinArgs::radius_sq_f)
     };
     PairSet pairs;
+    // voxel-grid downsampling (voxel.hip voxel_pass: dcreg_voxel_downsample*, dcreg_set_*_voxel).  Per input point: the packed cloud, its
+    // cloud (segment) and voxel key relative to the cloud's minimum voxel; per sorted position: head flags and their inclusive scan; per voxel:
+    // its first sorted position, its point and keep flag (then their scan); per cloud: the counters of the call (voxel.hip VoxCounters)
+    struct VoxelBufs {
+        float4 *pts = nullptr; size_t pts_cap = 0;
+        uint32_t *seg = nullptr; size_t seg_cap = 0;
+        uint64_t *rel = nullptr; size_t rel_cap = 0;
+        uint32_t *head = nullptr, *incl = nullptr, *start = nullptr, *keep = nullptr, *pos = nullptr;
+        size_t head_cap = 0, incl_cap = 0, start_cap = 0, keep_cap = 0, pos_cap = 0;
+        float4 *vout = nullptr; size_t vout_cap = 0;
+        float *out = nullptr; size_t out_cap = 0;            // 3 floats per output point (dcreg_voxel_downsample*)
+        int64_t *d_off = nullptr; size_t off_cap = 0;
+        int64_t *cnt = nullptr; size_t cnt_cap = 0;
+    };
+    VoxelBufs vox;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     double *h_euler = nullptr, *d_euler = nullptr;     // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
@@ -293,11 +310,48 @@ struct dcreg_ctx {
 };
 
 namespace dcreg {
+#define HIP_TRY(ctx, expr)                                                                       \
+    do {                                                                                         \
+        hipError_t e__ = (expr);                                                                 \
+        if (e__ != hipSuccess) {                                                                 \
+            (ctx)->fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return DCREG_E_DEVICE;                                                               \
+        }                                                                                        \
+    } while (0)
+
+// (re)allocates a device buffer of at least `need` elements; the contents are not kept
+template <typename T>
+static int ensure(dcreg_ctx *c, T *&ptr, size_t &cap, size_t need) {
+    if (need <= cap && ptr) return DCREG_OK;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr; cap = 0;
+    size_t n = std::max<size_t>(need, 1);
+    hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();      // (the failed allocation must not surface as the "launch error" of whatever is queued next)
+        c->fail("hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e));
+        return DCREG_E_NOMEM;
+    }
+    cap = n;
+    return DCREG_OK;
+}
+
 int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *p,
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, float4 *&raw, size_t &raw_cap);   // context.hip
+// voxel.hip: the voxel-grid pass of n_clouds clouds (offsets off[n_clouds + 1], host memory) - checks everything before it writes; the output
+// points go to c->vox.out (3 floats each) or, packed, to c->d_aligned as k_pack packs a cloud (one cloud only).  Ends with ONE readback of
+// the per-cloud counts and the bounds of the output.
+struct VoxelResult {
+    std::vector<int64_t> voxels, kept;     // per cloud
+    int64_t n_in = 0, n_finite = 0, n_voxels = 0, n_out = 0;
+    double mn[3] = {}, mx[3] = {};         // bounds of the output points (as k_bounds takes them)
+};
+int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
+               bool packed, VoxelResult &r);
 int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, int k, double max_radius, const PoseArg *pose,
                int32_t *d_idx, float *d_d2, bool sweep = false);
 }  // namespace dcreg

@@ -1,0 +1,439 @@
+// Voxel-grid downsampling on the device (include/dcreg.h: dcreg_voxel_downsample*, dcreg_set_source_voxel*, dcreg_set_target_voxel*).
+// Raw LiDAR sweeps (NaN where a beam had no return) and dense maps go in; one point per occupied voxel comes out, with PCL VoxelGrid's order
+// and semantics (the exact rules are in the header).  One segmented path serves every entry point - a cloud is a segment, a single cloud one
+// segment:
+//   k_vox_coords   finite flag, voxel coordinates, per-cloud minimum / maximum voxel and finite count (integer atomics: deterministic)
+//   (readback)     spans and refusals on the host, the key widths
+//   k_vox_keys     key = (cloud, voxel relative to the cloud's minimum), z y x; non-finite points get cloud id n_clouds (sorted behind all)
+//   radix sort     stable: the points of a voxel stay in input order (one pass when cloud + voxel bits fit 64, else voxel key then cloud)
+//   k_vox_heads    first sorted position of every voxel; inclusive scan = voxel numbers; k_vox_starts: where each voxel starts
+//   k_vox_reduce   ONE lane per voxel: count, min_points, the sequential double sum (or the first point) - exact and reproducible
+//   scan + k_vox_write   compaction, per-cloud counts, bounds of the output
+//   (readback)     counts, bounds: the only one at the end of the call
+// A voxel's result depends on its own points only: where its cloud sits in the call and how the launches are cut never enter it.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "context.hpp"
+
+namespace dcreg {
+namespace {
+
+constexpr int kVoxBlock = 256;
+constexpr int kVoxPerThread = 8;                        // points per thread of k_vox_coords (a block covers one tile of 2048 points)
+constexpr int kSpanBits = 21;                           // a cloud spans fewer than 2^21 voxels per axis
+constexpr double kVoxLimit = 4611686018427387904.0;     // 2^62: voxel coordinates beyond it are refused
+// counters of one call, per cloud s: cnt[kCnt s + 0..2] minimum voxel x y z, + 3..5 maximum, + 6 finite points, + 7 voxels, + 8 kept voxels;
+// behind the clouds kTail int64 slots read as uint32: [0..2] minimum, [3..5] maximum of the output (ordered-uint, k_bounds), [6] overflow
+constexpr int kCnt = 9;
+constexpr int kTail = 4;
+
+inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
+// the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i)
+__device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
+    int lo = 0, hi = n_clouds;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return (uint32_t)lo;
+}
+
+__device__ __forceinline__ bool finite3(const float4 p) {
+    return fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
+}
+
+// floor((double)p / leaf) per axis, as the header defines it (an IEEE double division: the build has no fast-math)
+__device__ __forceinline__ void voxel_of(const float4 p, const double lx, const double ly, const double lz, double v[3]) {
+    v[0] = floor((double)p.x / lx);
+    v[1] = floor((double)p.y / ly);
+    v[2] = floor((double)p.z / lz);
+}
+
+static __global__ void k_vox_init(int64_t *__restrict__ cnt, int n_clouds) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nc = (int64_t)kCnt * n_clouds;
+    if (i < nc) {
+        const int f = (int)(i % kCnt);
+        cnt[i] = f < 3 ? INT64_MAX : f < 6 ? INT64_MIN : 0;
+    } else if (i < nc + 2 * kTail) {
+        const int j = (int)(i - nc);
+        reinterpret_cast<uint32_t *>(cnt + nc)[j] = j < 3 ? 0xFFFFFFFFu : 0u;
+    }
+}
+
+// Pass 1: the cloud of every point, and per cloud the minimum / maximum voxel and the finite points.  A block covers a tile of kVoxBlock x
+// kVoxPerThread points; a tile inside one cloud reduces in registers and LDS and adds 7 atomics, a tile across clouds adds per point.
+static __global__ void __launch_bounds__(kVoxBlock) k_vox_coords(const float4 *__restrict__ pts, int64_t n, const int64_t *__restrict__ off,
+                                                                 int n_clouds, double lx, double ly, double lz, uint32_t *__restrict__ seg,
+                                                                 int64_t *__restrict__ cnt) {
+    const int64_t base = (int64_t)blockIdx.x * (kVoxBlock * kVoxPerThread);
+    const int64_t last = std::min<int64_t>(n, base + kVoxBlock * kVoxPerThread) - 1;
+    const uint32_t s0 = seg_of(off, n_clouds, base);
+    const bool uniform = seg_of(off, n_clouds, last) == s0;
+    uint32_t *ovf = reinterpret_cast<uint32_t *>(cnt + (int64_t)kCnt * n_clouds) + 6;
+    long long mn[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, mx[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    long long fin = 0;
+    for (int k = 0; k < kVoxPerThread; ++k) {
+        const int64_t i = base + threadIdx.x + (int64_t)k * kVoxBlock;
+        if (i > last) break;
+        const uint32_t s = uniform ? s0 : seg_of(off, n_clouds, i);
+        seg[i] = s;
+        const float4 p = pts[i];
+        if (!finite3(p)) continue;
+        double v[3];
+        voxel_of(p, lx, ly, lz, v);
+        long long vi[3];
+        bool big = false;
+        for (int a = 0; a < 3; ++a) {
+            big |= !(fabs(v[a]) < kVoxLimit);
+            vi[a] = big ? 0 : (long long)v[a];
+        }
+        if (big) { atomicOr(ovf, 1u); continue; }
+        if (uniform) {
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], vi[a]); mx[a] = std::max(mx[a], vi[a]); }
+            ++fin;
+        } else {
+            long long *c = reinterpret_cast<long long *>(cnt + (int64_t)kCnt * s);
+            for (int a = 0; a < 3; ++a) { atomicMin(c + a, vi[a]); atomicMax(c + 3 + a, vi[a]); }
+            atomicAdd(reinterpret_cast<unsigned long long *>(c + 6), 1ull);
+        }
+    }
+    if (!uniform) return;          // (block-uniform)
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], (long long)__shfl_xor(mn[a], o)); mx[a] = std::max(mx[a], (long long)__shfl_xor(mx[a], o)); }
+        fin += __shfl_xor(fin, o);
+    }
+    __shared__ long long smn[kVoxBlock / 64][3], smx[kVoxBlock / 64][3], sfin[kVoxBlock / 64];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        for (int a = 0; a < 3; ++a) { smn[wave][a] = mn[a]; smx[wave][a] = mx[a]; }
+        sfin[wave] = fin;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kVoxBlock / 64; ++w) {
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], smn[w][a]); mx[a] = std::max(mx[a], smx[w][a]); }
+            fin += sfin[w];
+        }
+        if (fin > 0) {
+            long long *c = reinterpret_cast<long long *>(cnt + (int64_t)kCnt * s0);
+            for (int a = 0; a < 3; ++a) { atomicMin(c + a, mn[a]); atomicMax(c + 3 + a, mx[a]); }
+            atomicAdd(reinterpret_cast<unsigned long long *>(c + 6), (unsigned long long)fin);
+        }
+    }
+}
+
+// Pass 2: the sort key of every point - (cloud, voxel z y x relative to the cloud's minimum) when `with_seg`, else the voxel part alone -
+// and rel = the voxel part.  A non-finite point is given cloud n_clouds (seg[i] too): it sorts behind every voxel.
+static __global__ void k_vox_keys(const float4 *__restrict__ pts, int64_t n, uint32_t *__restrict__ seg, int n_clouds, double lx, double ly,
+                                  double lz, const int64_t *__restrict__ cnt, int bx, int by, int bz, bool with_seg, uint64_t *__restrict__ keys,
+                                  uint32_t *__restrict__ vals, uint64_t *__restrict__ rel) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    uint32_t s = seg[i];
+    uint64_t r = 0;
+    if (finite3(p)) {
+        double v[3];
+        voxel_of(p, lx, ly, lz, v);
+        const int64_t *c = cnt + (int64_t)kCnt * s;
+        const uint64_t rx = (uint64_t)((long long)v[0] - c[0]), ry = (uint64_t)((long long)v[1] - c[1]), rz = (uint64_t)((long long)v[2] - c[2]);
+        r = (rz << (bx + by)) | (ry << bx) | rx;
+    } else {
+        s = (uint32_t)n_clouds;
+        seg[i] = s;
+    }
+    rel[i] = r;
+    keys[i] = with_seg ? (((uint64_t)s << (bx + by + bz)) | r) : r;
+    vals[i] = (uint32_t)i;
+}
+
+// the cloud of every sorted position: the key of the second (stable) sort of the two-pass order
+static __global__ void k_vox_seg_keys(const uint32_t *__restrict__ ord, int64_t n, const uint32_t *__restrict__ seg, uint32_t *__restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keys[i] = seg[ord[i]];
+}
+
+// head[i] = sorted position i is the first point of a voxel
+static __global__ void k_vox_heads(const uint32_t *__restrict__ ord, int64_t n, const uint32_t *__restrict__ seg, const uint64_t *__restrict__ rel,
+                                   uint32_t n_clouds, uint32_t *__restrict__ head) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = ord[i], s = seg[o];
+    bool h = s < n_clouds;
+    if (h && i > 0) {
+        const uint32_t q = ord[i - 1];
+        h = seg[q] != s || rel[q] != rel[o];
+    }
+    head[i] = h ? 1u : 0u;
+}
+
+// start[v] = first sorted position of voxel v (v = incl - 1 at a head); start[V] = one past the last finite point
+static __global__ void k_vox_starts(const uint32_t *__restrict__ ord, int64_t n, const uint32_t *__restrict__ seg, uint32_t n_clouds,
+                                    const uint32_t *__restrict__ head, const uint32_t *__restrict__ incl, uint32_t *__restrict__ start) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (head[i]) start[incl[i] - 1] = (uint32_t)i;
+    if (seg[ord[i]] < n_clouds && (i == n - 1 || seg[ord[i + 1]] >= n_clouds)) start[incl[i]] = (uint32_t)(i + 1);
+}
+
+// One lane per voxel: its points are ord[start[v] .. start[v + 1]), in input order.  The centroid is the sequential double sum divided by
+// the count; "first" copies the lowest-index point.  Per cloud: voxels and kept voxels (one atomic pair per run of a cloud in a wave).
+static __global__ void __launch_bounds__(kVoxBlock) k_vox_reduce(const float4 *__restrict__ pts, const uint32_t *__restrict__ ord, int64_t n,
+                                                                 const uint32_t *__restrict__ seg, const uint32_t *__restrict__ start,
+                                                                 const uint32_t *__restrict__ incl, int mode, int min_points,
+                                                                 float4 *__restrict__ vout, uint32_t *__restrict__ keep, int64_t *__restrict__ cnt) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n_vox = incl[n - 1];
+    const bool act = v < n_vox;
+    uint32_t s = 0;
+    bool k = false;
+    if (act) {
+        const uint32_t b = start[v], e = start[v + 1];
+        const uint32_t o = ord[b];
+        s = seg[o];
+        k = (int64_t)(e - b) >= (int64_t)min_points;
+        float4 q;
+        if (mode == DCREG_VOXEL_FIRST) {
+            q = pts[o];
+        } else {
+            const float4 p0 = pts[o];
+            double sx = p0.x, sy = p0.y, sz = p0.z;
+            for (uint32_t j = b + 1; j < e; ++j) {
+                const float4 p = pts[ord[j]];
+                sx += (double)p.x; sy += (double)p.y; sz += (double)p.z;
+            }
+            const double m = (double)(e - b);
+            q = make_float4((float)(sx / m), (float)(sy / m), (float)(sz / m), 0.f);
+        }
+        vout[v] = make_float4(q.x, q.y, q.z, 0.f);
+        keep[v] = k ? 1u : 0u;
+    } else if (v < n) {
+        keep[v] = 0u;              // (the scan of keep runs over n entries)
+    }
+    // the active lanes are a prefix of the wave and their clouds ascend: a lane whose cloud differs from its left neighbour's starts a run
+    const int lane = (int)(threadIdx.x & 63);
+    const uint32_t left = __shfl_up(s, 1);
+    const bool leader = act && (lane == 0 || left != s);
+    const uint64_t L = __ballot(leader), A = __ballot(act), K = __ballot(act && k);
+    if (leader) {
+        const uint64_t above = lane == 63 ? 0ull : (L & ~((2ull << lane) - 1ull));
+        const int end = above ? __ffsll((unsigned long long)above) - 1 : 64 - __clzll((long long)A);     // next run / past the last active lane
+        const uint64_t run = (end >= 64 ? ~0ull : ((1ull << end) - 1ull)) & ~((1ull << lane) - 1ull);
+        unsigned long long *c = reinterpret_cast<unsigned long long *>(cnt + (int64_t)kCnt * s);
+        atomicAdd(c + 7, (unsigned long long)(end - lane));
+        atomicAdd(c + 8, (unsigned long long)__popcll(K & run));
+    }
+}
+
+// compaction of the kept voxels (pos = exclusive scan of keep): 3 floats per point, or packed as k_pack packs a cloud (w = the point's index)
+// with the bounds of the output (ordered-uint atomics, one set per block)
+static __global__ void __launch_bounds__(kVoxBlock) k_vox_write(const float4 *__restrict__ vout, const uint32_t *__restrict__ keep,
+                                                                const uint32_t *__restrict__ pos, const uint32_t *__restrict__ incl, int64_t n,
+                                                                float *__restrict__ out3, float4 *__restrict__ out4, uint32_t *__restrict__ bounds) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n_vox = incl[n - 1];
+    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
+    if (v < n_vox && keep[v]) {
+        const float4 q = vout[v];
+        const uint32_t j = pos[v];
+        if (out4) {
+            out4[j] = make_float4(q.x, q.y, q.z, __uint_as_float(j));
+            const float c[3] = {q.x, q.y, q.z};
+            for (int a = 0; a < 3; ++a) { lo[a] = f2ord(c[a]); hi[a] = f2ord(c[a]); }
+        } else {
+            out3[3 * (int64_t)j] = q.x; out3[3 * (int64_t)j + 1] = q.y; out3[3 * (int64_t)j + 2] = q.z;
+        }
+    }
+    if (!out4) return;             // (grid-uniform)
+    for (int o = 32; o > 0; o >>= 1)
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], (uint32_t)__shfl_xor(lo[a], o)); hi[a] = std::max(hi[a], (uint32_t)__shfl_xor(hi[a], o)); }
+    __shared__ uint32_t slo[kVoxBlock / 64][3], shi[kVoxBlock / 64][3];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 3; ++a) { slo[wave][a] = lo[a]; shi[wave][a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        uint32_t l = slo[0][a], h = shi[0][a];
+        for (int w = 1; w < kVoxBlock / 64; ++w) { l = std::min(l, slo[w][a]); h = std::max(h, shi[w][a]); }
+        if (l <= h) { atomicMin(&bounds[a], l); atomicMax(&bounds[3 + a], h); }
+    }
+}
+
+template <typename K>
+int sort_pairs(dcreg_ctx *c, K *keys_in, K *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int bits) {
+    size_t tmp = 0;
+    HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
+    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
+    return DCREG_OK;
+}
+
+int scan(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inclusive) {
+    size_t tmp = 0;
+    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
+    else HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
+    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp, tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
+    else HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
+    return DCREG_OK;
+}
+
+int bits_for(int64_t v) { int b = 0; while (b < 63 && ((int64_t)1 << b) <= v) ++b; return b; }
+
+}  // namespace
+
+int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
+               bool packed, VoxelResult &r) {
+    // ---- everything the host can check, before anything is queued
+    if (!p) { c->fail("null voxel parameters"); return DCREG_E_INVALID; }
+    for (int a = 0; a < 3; ++a)
+        if (!(std::isfinite(p->leaf[a]) && p->leaf[a] > 0.0)) { c->fail("voxel leaf %d is %g: finite and > 0 expected", a, p->leaf[a]); return DCREG_E_INVALID; }
+    if (p->mode != DCREG_VOXEL_CENTROID && p->mode != DCREG_VOXEL_FIRST) { c->fail("unknown voxel mode %d", p->mode); return DCREG_E_INVALID; }
+    if (n_clouds < 0 || (n_clouds > 0 && !off) || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
+    if (n_clouds > 0 && off[0] != 0) { c->fail("cloud offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int s = 0; s < n_clouds; ++s)
+        if (off[s + 1] < off[s]) { c->fail("cloud offsets decrease at cloud %d", s); return DCREG_E_INVALID; }
+    const int64_t n = n_clouds > 0 ? off[n_clouds] : 0;
+    if (n >= ((int64_t)1 << 31) - 1) { c->fail("too many points for one voxel pass (%lld)", (long long)n); return DCREG_E_INVALID; }
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (packed && n_clouds != 1) { c->fail("a packed voxel output holds one cloud"); return DCREG_E_INVALID; }
+    const int min_points = std::max(p->min_points, 1);
+    r = VoxelResult();
+    r.voxels.assign((size_t)n_clouds, 0);
+    r.kept.assign((size_t)n_clouds, 0);
+    r.n_in = n;
+    if (n == 0) return DCREG_OK;
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::VoxelBufs &B = c->vox;
+    const size_t nc = (size_t)kCnt * n_clouds + kTail;
+    if (ensure(c, B.seg, B.seg_cap, (size_t)n) || ensure(c, B.rel, B.rel_cap, (size_t)n) || ensure(c, B.head, B.head_cap, (size_t)n) ||
+        ensure(c, B.incl, B.incl_cap, (size_t)n) || ensure(c, B.start, B.start_cap, (size_t)n + 1) || ensure(c, B.keep, B.keep_cap, (size_t)n) ||
+        ensure(c, B.pos, B.pos_cap, (size_t)n) || ensure(c, B.vout, B.vout_cap, (size_t)n) || ensure(c, B.d_off, B.off_cap, (size_t)n_clouds + 1) ||
+        ensure(c, B.cnt, B.cnt_cap, nc) || ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
+        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+        return DCREG_E_NOMEM;
+    if (packed ? ensure(c, c->d_aligned, c->aligned_cap, (size_t)n) : ensure(c, B.out, B.out_cap, (size_t)(3 * n))) return DCREG_E_NOMEM;
+    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts, B.pts_cap);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(B.d_off, off, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt, n_clouds);
+    const double lx = p->leaf[0], ly = p->leaf[1], lz = p->leaf[2];
+    hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, B.pts, n, B.d_off, n_clouds,
+                       lx, ly, lz, B.seg, B.cnt);
+    std::vector<int64_t> h((size_t)nc);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+
+    // ---- spans: refusals, key widths
+    uint32_t tail[2 * kTail];
+    std::memcpy(tail, h.data() + (size_t)kCnt * n_clouds, sizeof(tail));
+    if (tail[6]) { c->fail("a voxel coordinate reaches 2^62 (leaf too small for the coordinates)"); return DCREG_E_INVALID; }
+    int64_t span[3] = {0, 0, 0};
+    for (int s = 0; s < n_clouds; ++s) {
+        const int64_t *q = h.data() + (size_t)kCnt * s;
+        if (q[6] == 0) continue;
+        r.n_finite += q[6];
+        for (int a = 0; a < 3; ++a) {
+            const int64_t d = q[3 + a] - q[a];
+            if (d >= ((int64_t)1 << kSpanBits)) {
+                c->fail("cloud %d spans %lld voxels on axis %d (at most 2^21 - 1)", s, (long long)d + 1, a);
+                return DCREG_E_INVALID;
+            }
+            span[a] = std::max(span[a], d);
+        }
+    }
+    if (r.n_finite == 0) return DCREG_OK;
+    const int bx = bits_for(span[0]), by = bits_for(span[1]), bz = bits_for(span[2]);
+    const int sbits = bits_for(n_clouds);        // cloud ids 0 .. n_clouds (n_clouds = the non-finite points)
+    const bool one_pass = sbits + bx + by + bz <= 64;
+
+    // ---- keys, stable sort, voxel heads and starts
+    hipLaunchKernelGGL(k_vox_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts, n, B.seg, n_clouds, lx, ly, lz, B.cnt,
+                       bx, by, bz, one_pass, c->d_mkeys, c->d_vals, B.rel);
+    const uint32_t *ord;
+    if (one_pass) {
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, sbits + bx + by + bz);
+        if (rc) return rc;
+        ord = c->d_vals2;
+    } else {            // voxel key first, then the cloud: both sorts stable, so each cloud's voxels and each voxel's points keep their order
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, bx + by + bz);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_vox_seg_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, c->d_vals2, n, B.seg, B.head);
+        rc = sort_pairs<uint32_t>(c, B.head, B.incl, c->d_vals2, c->d_vals, (size_t)n, sbits);
+        if (rc) return rc;
+        ord = c->d_vals;
+    }
+    hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg, B.rel, (uint32_t)n_clouds, B.head);
+    rc = scan(c, B.head, B.incl, (size_t)n, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg, (uint32_t)n_clouds, B.head, B.incl,
+                       B.start);
+    // ---- one lane per voxel (at most n of them: the grids are sized for n, the lanes beyond the voxel count idle), compaction
+    hipLaunchKernelGGL(k_vox_reduce, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts, ord, n, B.seg, B.start, B.incl, p->mode,
+                       min_points, B.vout, B.keep, B.cnt);
+    rc = scan(c, B.keep, B.pos, (size_t)n, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vox_write, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.vout, B.keep, B.pos, B.incl, n,
+                       packed ? nullptr : B.out, packed ? c->d_aligned : nullptr,
+                       reinterpret_cast<uint32_t *>(B.cnt + (size_t)kCnt * n_clouds));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    for (int s = 0; s < n_clouds; ++s) {
+        r.voxels[(size_t)s] = h[(size_t)kCnt * s + 7];
+        r.kept[(size_t)s] = h[(size_t)kCnt * s + 8];
+        r.n_voxels += r.voxels[(size_t)s];
+        r.n_out += r.kept[(size_t)s];
+    }
+    std::memcpy(tail, h.data() + (size_t)kCnt * n_clouds, sizeof(tail));
+    for (int a = 0; a < 3; ++a) { r.mn[a] = ord2f(tail[a]); r.mx[a] = ord2f(tail[3 + a]); }
+    return DCREG_OK;
+}
+
+}  // namespace dcreg
+
+using namespace dcreg;
+
+// dcreg_voxel_downsample*: the pass into the context's output buffer, then - when the caller's capacity holds it - one copy to the caller
+static int voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
+                            float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!out_off || capacity < 0) { c->fail("invalid output arguments"); return DCREG_E_INVALID; }
+    VoxelResult r;
+    int rc = voxel_pass(c, n_clouds, xyz, off, stride, on_device, p, false, r);
+    if (rc) return rc;
+    out_off[0] = 0;
+    for (int s = 0; s < n_clouds; ++s) out_off[s + 1] = out_off[s] + r.kept[(size_t)s];
+    if (info) { info->n_in = r.n_in; info->n_finite = r.n_finite; info->n_voxels = r.n_voxels; info->n_out = r.n_out; }
+    if (r.n_out > capacity) { c->fail("the output holds %lld points, the capacity is %lld", (long long)r.n_out, (long long)capacity); return DCREG_E_INVALID; }
+    if (r.n_out == 0) return DCREG_OK;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    const size_t bytes = sizeof(float) * 3 * (size_t)r.n_out;
+    HIP_TRY(c, hipMemcpyAsync(out, c->vox.out, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
+extern "C" {
+int dcreg_voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_voxel_params *p,
+                           float *out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
+    return voxel_downsample(c, n_clouds, xyz, offsets, stride_floats, false, p, out_xyz, capacity_points, out_offsets, info);
+}
+int dcreg_voxel_downsample_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                  const dcreg_voxel_params *p, float *d_out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
+    return voxel_downsample(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_out_xyz, capacity_points, out_offsets, info);
+}
+}

@@ -731,6 +731,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_trial_result")) return sizeof(dcreg_trial_result);
     if (!std::strcmp(name, "dcreg_launch_stats")) return sizeof(dcreg_launch_stats);
     if (!std::strcmp(name, "dcreg_method_stats")) return sizeof(dcreg_method_stats);
+    if (!std::strcmp(name, "dcreg_voxel_params")) return sizeof(dcreg_voxel_params);
+    if (!std::strcmp(name, "dcreg_voxel_info")) return sizeof(dcreg_voxel_info);
     return 0;
 }
 

@@ -309,3 +309,31 @@ def write_pcd_xyzi(path, xyz):
         f.write(("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\n"
                  "COUNT 1 1 1 1\nWIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA binary\n" % (n, n)).encode("ascii"))
         f.write(rec.tobytes())
+
+
+def lidar_sweep(world, pose, rings=128, cols=1024, fov_up=22.5, fov_down=-22.5, min_range=0.5, max_range=80.0, noise=0.01, seed=0):
+    """An ORGANISED sweep of a spinning LiDAR (rings x cols beams, e.g. 128 x 1024 = 131 k points) at the sensor pose `pose` (4x4, sensor ->
+    map) over the points of `world`: each beam returns the nearest world point that falls in its pixel (azimuth column, elevation ring),
+    placed on the beam's centre direction at that range plus Gaussian range noise; a beam with no point in range has no return and its row
+    is NaN, as in an organised cloud.  -> [rings * cols, 3] float32 in the sensor frame, ring after ring."""
+    rng = np.random.default_rng(seed)
+    T = np.asarray(pose, np.float64)
+    body = (np.asarray(world, np.float32).astype(np.float64) - T[:3, 3]) @ T[:3, :3]      # R^T (p - t)
+    r = np.linalg.norm(body, axis=1)
+    ok = (r > min_range) & (r < max_range)
+    body, r = body[ok], r[ok]
+    az = np.arctan2(body[:, 1], body[:, 0])
+    el = np.degrees(np.arcsin(body[:, 2] / r))
+    col = np.minimum((az + np.pi) / (2 * np.pi) * cols, cols - 1).astype(np.int64)
+    ring = np.floor((fov_up - el) / (fov_up - fov_down) * rings).astype(np.int64)
+    inside = (ring >= 0) & (ring < rings)
+    pix, r = ring[inside] * cols + col[inside], r[inside]
+    order = np.lexsort((r, pix))                       # nearest point of each pixel first
+    first = order[np.r_[True, pix[order][1:] != pix[order][:-1]]] if len(order) else order
+    rng_px = np.full(rings * cols, np.nan)
+    rng_px[pix[first]] = r[first] + rng.normal(0.0, noise, len(first))
+    jr, jc = np.divmod(np.arange(rings * cols), cols)
+    a = (jc + 0.5) / cols * 2 * np.pi - np.pi
+    e = np.radians(fov_up - (jr + 0.5) * (fov_up - fov_down) / rings)
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], 1)
+    return (d * rng_px[:, None]).astype(np.float32)

@@ -18,6 +18,10 @@
  *                                                                                 -> dcreg_icp_run_euler
  *       TestRunner::runMethod num_runs loop  icp_test_runner.cpp:331-390         -> dcreg_icp_run_trials
  *       calculatePointToPointError           utils.hpp:538-589                   -> dcreg_p2p_error
+ *   raw clouds (not in the reference, which reads clouds a pcl::VoxelGrid filtered beforehand)
+ *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
+ *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
+ *                                                                                   dcreg_set_target_voxel[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -258,6 +262,59 @@ int dcreg_target_insert_source(dcreg_ctx *, const double R[9], const double t[3]
 int dcreg_target_crop(dcreg_ctx *, const double lo[3], const double hi[3], dcreg_map_update *info);
 /* the map in index order, 3 floats per point; DCREG_E_INVALID when capacity_points is below the map's size */
 int dcreg_target_get(const dcreg_ctx *, float *xyz_out, int64_t capacity_points);
+
+/* ---------------- voxel-grid downsampling of raw clouds ----------------
+ * A raw LiDAR sweep (an organised cloud holds NaN where a beam had no return) or a dense map thinned on the device, with PCL VoxelGrid's
+ * semantics (INTEGRATION.md lists where it differs).  For each cloud:
+ *   - a point is used only when x, y and z are all finite (the others are dropped and counted);
+ *   - its voxel is v_a = floor((double)p_a / leaf[a]) per axis (an IEEE double division);
+ *   - voxels are output in ascending (v_z, v_y, v_x) order (x fastest), the points of a voxel taken in ascending input index;
+ *   - a voxel with fewer than max(min_points, 1) points is dropped;
+ *   - DCREG_VOXEL_CENTROID: the output point is (float)(S_a / count), S_a = the double sum of (double)p_a over the voxel's points, left to
+ *     right in input order (S_a = p_0 for one point); DCREG_VOXEL_FIRST: the voxel's lowest-index point, copied bitwise.
+ * A voxel's result depends on its own points only (not on other clouds of the call, nor on the launch configuration).  Each cloud is keyed
+ * relative to its own minimum voxel.  DCREG_E_INVALID, and nothing is written: a leaf that is not finite and > 0, an unknown mode, offsets
+ * that do not start at 0 or decrease, stride < 3, more than 2^31 - 1 points in all, a cloud that spans 2^21 or more voxels on an axis (at a
+ * 1 cm leaf 20 km) or has a voxel coordinate of magnitude 2^62 or more; DCREG_E_STATE: a linearisation in flight.  The pass sums every voxel
+ * sequentially in one lane: a cloud whose points crowd into a few voxels pays for the longest of them.
+ * Device memory: about 120 B per input point of scratch, kept by the context for the next call. */
+#define DCREG_VOXEL_CENTROID 0
+#define DCREG_VOXEL_FIRST 1
+typedef struct dcreg_voxel_params {
+    double leaf[3];      /* voxel edge per axis (m) */
+    int mode;            /* DCREG_VOXEL_CENTROID / DCREG_VOXEL_FIRST */
+    int min_points;      /* PCL setMinimumPointsNumberPerVoxel; <= 1 keeps every voxel */
+} dcreg_voxel_params;
+typedef struct dcreg_voxel_info {    /* summed over the clouds of the call */
+    int64_t n_in;        /* points passed in */
+    int64_t n_finite;    /* ... with three finite coordinates */
+    int64_t n_voxels;    /* occupied voxels */
+    int64_t n_out;       /* ... with at least min_points points: points written */
+} dcreg_voxel_info;
+/* Many clouds in one call: cloud c = points [offsets[c], offsets[c + 1]) of xyz (n_clouds + 1 offsets, in points, from 0; stride_floats
+ * floats per point, x y z first); the output points, 3 floats each, go to out_xyz cloud after cloud, cloud c from out_offsets[c]
+ * (n_clouds + 1 entries) - the pair (out_xyz, out_offsets) is what dcreg_register_frames takes with stride 3.  capacity_points = offsets[n_clouds]
+ * is always enough; a smaller capacity that the output does not fit returns DCREG_E_INVALID with out_offsets and info filled (the size
+ * needed) and nothing written to out_xyz.  offsets, out_offsets and info are host memory; info may be NULL.  Waits for the stream. */
+int dcreg_voxel_downsample(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats,
+                           const dcreg_voxel_params *, float *out_xyz, int64_t capacity_points, int64_t *out_offsets,
+                           dcreg_voxel_info *);
+/* _device: d_xyz is read as dcreg_set_source_device reads a cloud; d_out_xyz is device memory, written on the ctx's stream */
+int dcreg_voxel_downsample_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                  const dcreg_voxel_params *, float *d_out_xyz, int64_t capacity_points, int64_t *out_offsets,
+                                  dcreg_voxel_info *);
+/* One cloud voxelised and kept as the source / target: the context is left exactly as dcreg_set_source / dcreg_set_target of the output of
+ * dcreg_voxel_downsample leaves it (the output goes from the pass to the source / target build on the device, no host round trip).  A
+ * refused call - the refusals of dcreg_voxel_downsample, n <= 0, no point left after the pass - leaves the context's source / target
+ * as it was.  info may be NULL.  _device: d_xyz as dcreg_set_source_device / dcreg_set_target_device read it. */
+int dcreg_set_source_voxel(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *,
+                           dcreg_voxel_info *);
+int dcreg_set_source_voxel_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *,
+                                  dcreg_voxel_info *);
+int dcreg_set_target_voxel(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *,
+                           double search_radius_hint, dcreg_voxel_info *);
+int dcreg_set_target_voxel_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *,
+                                  double search_radius_hint, dcreg_voxel_info *);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
