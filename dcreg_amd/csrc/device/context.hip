@@ -30,16 +30,16 @@ static void drop_warm(dcreg_ctx *c);
 static int sort_pairs_u32(dcreg_ctx *c, uint32_t *keys_in, uint32_t *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int bits) {
     size_t tmp = 0;
     HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
-    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
+    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp.data(), tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
     return DCREG_OK;
 }
 // sorts by the bits [lo_bit, hi_bit) of the keys only (stable: equal prefixes keep their order)
 static int sort_pairs_u64(dcreg_ctx *c, uint64_t *keys_in, uint64_t *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int lo_bit = 0, int hi_bit = 63) {
     size_t tmp = 0;
     HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, hi_bit, c->stream));
-    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, hi_bit, c->stream));
+    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp.data(), tmp, keys_in, keys_out, vals_in, vals_out, n, lo_bit, hi_bit, c->stream));
     return DCREG_OK;
 }
 
@@ -59,27 +59,22 @@ static void host_bounds(const float *xyz, int64_t n, int64_t stride, double mn[3
 
 static int device_bounds(dcreg_ctx *c, const float4 *pts, int64_t n, double mn[3], double mx[3]) {
     uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
-    HIP_TRY(c, hipMemcpyAsync(c->d_scratch, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     const unsigned nb = std::min<unsigned>(blocks_for(n, 256), 256);      // grid-stride: one block per CU is plenty
-    hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(256), 0, c->stream, pts, n, c->d_scratch);
+    hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(256), 0, c->stream, pts, n, c->d_scratch.data());
     uint32_t out[6];
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch.data(), sizeof(out), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int a = 0; a < 3; ++a) { mn[a] = ord2f(out[a]); mx[a] = ord2f(out[3 + a]); }
     return DCREG_OK;
 }
 
-struct GridDst {   // where a grid build puts its products
-    const float4 *raw; int64_t n;
-    float4 **sorted; size_t *sorted_cap;
-    uint32_t **cell_start; size_t *cell_cap;
-    GridDev *grid; int64_t *n_cells;
-};
+using IndexSet = dcreg_ctx::IndexSet;
 
-// builds keys/sort/cell_start for the given cell edge; returns number of occupied cells
-// (sx = x sub-cells per cell, GridDev::sx; *occupied then counts sub-cells)
-static int build_grid_at(dcreg_ctx *c, const GridDst &d, double h, const double mn[3], const double mx[3], uint32_t *occupied, int sx = 1) {
-    const int64_t n = d.n;
+// builds keys/sort/cell_start of the n points at raw into d (sorted, cell_start, grid, n_cells) for the given cell edge; returns number
+// of occupied cells (sx = x sub-cells per cell, GridDev::sx; *occupied then counts sub-cells)
+static int build_grid_at(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d, double h, const double mn[3], const double mx[3], uint32_t *occupied,
+                         int sx = 1) {
     GridDev g{};
     g.h = h; g.inv_h = 1.0 / h;
     g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
@@ -89,26 +84,26 @@ static int build_grid_at(dcreg_ctx *c, const GridDst &d, double h, const double 
     g.sx = sx;
     const int64_t n_cells = (int64_t)g.nx * sx * g.ny * g.nz;       // table entries
     g.n_pts = (uint32_t)n;
-    if (ensure(c, c->d_keys, c->keys_cap, (size_t)n) || ensure(c, c->d_keys2, c->keys2_cap, (size_t)n) ||
-        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n) ||
-        ensure(c, *d.cell_start, *d.cell_cap, (size_t)n_cells + 1) || ensure(c, *d.sorted, *d.sorted_cap, (size_t)n + kPtsPad))
+    if (c->d_keys.ensure(c, (size_t)n) || c->d_keys2.ensure(c, (size_t)n) || c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) ||
+        d.cell_start.ensure(c, (size_t)n_cells + 1) || d.sorted.ensure(c, (size_t)n + kPtsPad))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, d.raw, n, g, c->d_keys, c->d_vals);
+    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, n, g, c->d_keys.data(), c->d_vals.data());
     int bits = 1;
     while (((int64_t)1 << bits) < n_cells && bits < 32) ++bits;
-    int rc = sort_pairs_u32(c, c->d_keys, c->d_keys2, c->d_vals, c->d_vals2, (size_t)n, bits);
+    int rc = sort_pairs_u32(c, c->d_keys.data(), c->d_keys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bits);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, d.raw, c->d_vals2, n, *d.sorted);
-    HIP_TRY(c, hipMemsetAsync(*d.sorted + n, 0, kPtsPad * sizeof(float4), c->stream));   // tail padding
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_cells + 1, 256)), dim3(256), 0, c->stream, c->d_keys2, n, n_cells, *d.cell_start, c->d_scratch);
-    HIP_TRY(c, hipMemcpyAsync(occupied, c->d_scratch, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d.sorted.data());
+    HIP_TRY(c, hipMemsetAsync(d.sorted.data() + n, 0, kPtsPad * sizeof(float4), c->stream));   // tail padding
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_cells + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_cells, d.cell_start.data(),
+                       c->d_scratch.data());
+    HIP_TRY(c, hipMemcpyAsync(occupied, c->d_scratch.data(), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    g.cell_start = *d.cell_start;
-    g.pts = *d.sorted;
-    *d.grid = g;
-    *d.n_cells = n_cells / sx;
+    g.cell_start = d.cell_start.data();
+    g.pts = d.sorted.data();
+    d.grid = g;
+    d.n_cells = n_cells / sx;
     return DCREG_OK;
 }
 
@@ -122,14 +117,14 @@ static double cap_cell_for_budget(double h, const double mn[3], const double mx[
     return h;
 }
 
-// (box = the cloud's bounds min xyz, max xyz when the caller has them already, else NULL)
-static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr) {
-    const int64_t n = d.n;
+// the index of the n points at raw, built into d (build_grid_at); box = the cloud's bounds min xyz, max xyz when the caller has them
+// already, else NULL
+static int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr) {
     if (n <= 0) { c->fail("cloud is empty"); return DCREG_E_INVALID; }
     double mn[3], mx[3];
     int rc = DCREG_OK;
     if (box) for (int a = 0; a < 3; ++a) { mn[a] = box[a]; mx[a] = box[3 + a]; }
-    else rc = device_bounds(c, d.raw, n, mn, mx);
+    else rc = device_bounds(c, raw, n, mn, mx);
     if (rc) return rc;
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     const double ext = std::max({mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2], 1e-6});
@@ -151,7 +146,7 @@ static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint3
         h = cap_cell_for_budget(h, mn, mx, max_cells);
         cap_ratio = h / h0;
     }
-    rc = build_grid_at(c, d, h, mn, mx, &occ);
+    rc = build_grid_at(c, raw, n, d, h, mn, mx, &occ);
     if (rc) return rc;
     if (c->opt_cell <= 0.0) {
         // density-adaptive cell: aim at `target_occ` points per occupied cell (surface data: occupancy ~ h^2)
@@ -167,7 +162,7 @@ static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint3
                 cap_ratio = h2 / h20;                              // (the last pass decides the cell edge)
             }
             if (h2 >= h1 * 0.95) break;
-            rc = build_grid_at(c, d, h2, mn, mx, &occ);
+            rc = build_grid_at(c, raw, n, d, h2, mn, mx, &occ);
             if (rc) return rc;
             const double m2 = (double)n / std::max<uint32_t>(occ, 1);
             if (m2 < m1 && h2 < h1) expo = std::min(3.0, std::max(1.0, std::log(m1 / m2) / std::log(h1 / h2)));
@@ -178,81 +173,70 @@ static int build_index(dcreg_ctx *c, const GridDst &d, double radius_hint, uint3
     // the cell edge is settled: cut x into sub-cells (same rows, same table loads, tighter candidate runs), as far as the
     // table budget allows
     int sx = c->opt_x_subdiv;
-    while (sx > 1 && (double)d.grid->nx * sx * d.grid->ny * d.grid->nz > max_cells) sx >>= 1;
+    while (sx > 1 && (double)d.grid.nx * sx * d.grid.ny * d.grid.nz > max_cells) sx >>= 1;
     // one step of the budget (x 1.26) with sub-cells left is what a 50 M-point, 700 m map gets: a window of its own has nothing to add there
     // (measured, window forced: 0.79 against 0.73 ms per registration); two steps, or no sub-cells at all, is where the window pays (100 M points: 0.93 -> 0.76 ms)
     c->last_build_capped = cap_ratio > 1.5 || (sx == 1 && c->opt_x_subdiv > 1 && cap_ratio > 1.0);
     if (sx > 1) {
         uint32_t occ_sub = 0;
-        rc = build_grid_at(c, d, d.grid->h, mn, mx, &occ_sub, sx);
+        rc = build_grid_at(c, raw, n, d, d.grid.h, mn, mx, &occ_sub, sx);
         if (rc) return rc;
     }
     return DCREG_OK;
 }
 
-// empty-space distance field of the target grid (queries far from any point skip the rings they know are empty)
-static int build_gap_field(dcreg_ctx *c, double radius_hint) {
-    GridDev &g = c->grid;
+// empty-space distance field of the grid of d (queries far from any point skip the rings they know are empty)
+static int build_gap_field(dcreg_ctx *c, IndexSet &d, double radius_hint) {
+    GridDev &g = d.grid;
     g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
     if (!c->opt_gap_field) return DCREG_OK;
-    const int64_t n_cells = c->n_cells;
+    const int64_t n_cells = d.n_cells;
     int rings = 1;                                            // rings that a search up to the radius can need
     while (rings < 12 && (double)rings * g.h < (radius_hint > 0.0 ? radius_hint : 4.0 * g.h)) ++rings;
     if (rings < 2) return DCREG_OK;                           // one ring covers the radius: nothing to skip
-    if (ensure(c, c->d_gap, c->gap_cap, (size_t)n_cells) || ensure(c, c->d_owner, c->owner_cap, (size_t)n_cells)) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_gap_init, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, c->d_cell_start, n_cells, g.sx, c->d_gap, c->d_owner);
+    if (d.gap.ensure(c, (size_t)n_cells) || d.owner.ensure(c, (size_t)n_cells)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_gap_init, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), n_cells, g.sx, d.gap.data(), d.owner.data());
     for (int r = 1; r <= rings; ++r)
-        hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, c->d_gap, c->d_owner, g.nx, g.ny, g.nz, r);
-    if (c->opt_far_bound) {      // the probe's owners: nearest DENSE cell (kernels.hpp k_gap_init_dense); scratch of this build only
-        uint8_t *gap2 = nullptr; uint32_t *own2 = nullptr;
-        if (hipMalloc((void **)&gap2, (size_t)n_cells) == hipSuccess && hipMalloc((void **)&own2, sizeof(uint32_t) * (size_t)n_cells) == hipSuccess) {
-            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, c->d_cell_start, g.nx, n_cells, g.sx, 6u, gap2, own2);
+        hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.gap.data(), d.owner.data(), g.nx, g.ny, g.nz, r);
+    if (c->opt_far_bound) {      // the probe's owners: nearest DENSE cell (kernels.hpp k_gap_init_dense); scratch of this block only
+        DevBuf<uint8_t> gap2;
+        DevBuf<uint32_t> own2;
+        if (gap2.alloc((size_t)n_cells) == hipSuccess && own2.alloc((size_t)n_cells) == hipSuccess) {
+            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, n_cells, g.sx, 6u,
+                               gap2.data(), own2.data());
             for (int r = 1; r <= rings; ++r)
-                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap2, own2, g.nx, g.ny, g.nz, r);
-            hipLaunchKernelGGL(k_owner_merge, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, c->d_owner, own2, n_cells);
+                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap2.data(), own2.data(), g.nx, g.ny, g.nz, r);
+            hipLaunchKernelGGL(k_owner_merge, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.owner.data(), own2.data(), n_cells);
         } else {
             (void)hipGetLastError();     // (no memory for the scratch: the plain owners serve)
         }
-        const hipError_t se = hipStreamSynchronize(c->stream);
-        if (gap2) (void)hipFree(gap2);
-        if (own2) (void)hipFree(own2);
-        HIP_TRY(c, se);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    g.gap = c->d_gap; g.gap_cap = rings;
-    g.owner = c->opt_far_bound ? c->d_owner : nullptr;
+    g.gap = d.gap.data(); g.gap_cap = rings;
+    g.owner = c->opt_far_bound ? d.owner.data() : nullptr;
     return DCREG_OK;
 }
 
-// row occupancy words of the target grid (GridDev::ymask): what the searches of the linearisation sweep instead of walking rings
-static int build_row_words(dcreg_ctx *c) {
-    GridDev &g = c->grid;
+// row occupancy words of the grid of d (GridDev::ymask): what the searches of the linearisation sweep instead of walking rings
+static int build_row_words(dcreg_ctx *c, IndexSet &d) {
+    GridDev &g = d.grid;
     g.ymask = nullptr;
     g.nxb = (g.nx + 15) >> 4; g.nyw = (g.ny + 31) >> 5;
     const int64_t n_words = (int64_t)g.nz * g.nxb * g.nyw;
-    if (ensure(c, c->d_ymask, c->ymask_cap, (size_t)n_words)) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_ymask, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, c->d_cell_start, g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw, c->d_ymask);
+    if (d.ymask.ensure(c, (size_t)n_words)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_ymask, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw,
+                       d.ymask.data());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    g.ymask = c->d_ymask;
+    g.ymask = d.ymask.data();
     return DCREG_OK;
-}
-
-static GridDst target_dst(dcreg_ctx *c) {
-    return GridDst{c->d_tgt_raw, c->n_tgt, &c->d_tgt, &c->tgt_cap, &c->d_cell_start, &c->cell_cap, &c->grid, &c->n_cells};
 }
 
 // ------------------------------------------------------------------------------------------ the window index of a large map (context.hpp)
 static void swap_index(dcreg_ctx *c) {
-    dcreg_ctx::IndexSet &s = c->roi_store;
-    std::swap(c->d_tgt_raw, s.raw); std::swap(c->tgt_raw_cap, s.raw_cap); std::swap(c->n_tgt, s.n);
-    std::swap(c->d_tgt, s.sorted); std::swap(c->tgt_cap, s.sorted_cap);
-    std::swap(c->d_cell_start, s.cell_start); std::swap(c->cell_cap, s.cell_cap);
-    std::swap(c->grid, s.grid); std::swap(c->n_cells, s.n_cells); std::swap(c->occupied_cells, s.occupied);
-    std::swap(c->d_gap, s.gap); std::swap(c->gap_cap, s.gap_cap);
-    std::swap(c->d_owner, s.owner); std::swap(c->owner_cap, s.owner_cap);
-    std::swap(c->d_ymask, s.ymask); std::swap(c->ymask_cap, s.ymask_cap);
+    std::swap(c->map, c->roi_store);
     c->roi_active = !c->roi_active;
     drop_warm(c);                 // the states' positions are positions in the other index's order
     c->order_valid = false;
@@ -286,8 +270,6 @@ static bool roi_covers(const dcreg_ctx *c, const double *R, const double *t, dou
 }
 static bool roi_wanted(const dcreg_ctx *c) { return c->opt_roi_index == 2 || (c->opt_roi_index == 1 && c->whole_capped); }
 
-static int build_gap_field(dcreg_ctx *c, double radius_hint);
-static int build_row_words(dcreg_ctx *c);
 // A single-pose linearisation at (R, t) with this search radius is about to be queued: make the index it should search the active one -
 // the window if the map wants one (building it around the pose when there is none that covers it), the whole map otherwise.
 static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius) {
@@ -299,7 +281,7 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
         return DCREG_OK;
     }
     // ---- a new window around this pose
-    (void)roi_deactivate(c);                                        // the members are the whole map's
+    (void)roi_deactivate(c);                                        // map is the whole map
     HIP_TRY(c, hipStreamSynchronize(c->stream));                    // (nothing in flight reads the buffers that are about to be replaced)
     double lo[3], hi[3];
     source_box_at(c, R, t, lo, hi);
@@ -312,8 +294,8 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
     // the map's points in the box: the x-runs of the whole map's (y,z) rows that cross it - contiguous ranges of its cell-sorted points (every cell
     // the box touches is taken whole: a few points more than the box holds, all of them the map's), read through the whole map's OWN index,
     // i.e. a pass over the window and not over the map
-    const int64_t n = c->n_tgt;
-    const GridDev &g = c->grid;
+    const int64_t n = c->map.n;
+    const GridDev &g = c->map.grid;
     int c0[3], c1[3];                                   // cell ranges [c0, c1) of the box in the whole map's grid
     const double org[3] = {g.ox, g.oy, g.oz};
     const int dims[3] = {g.nx, g.ny, g.nz};
@@ -327,22 +309,23 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
     c->roi_rebuilds += 1;
     if (c1[0] > c0[0] && n_rows64 > 0 && n_rows64 < ((int64_t)1 << 30)) {
         const int n_rows = (int)n_rows64, nxs = g.nx * g.sx, x0s = c0[0] * g.sx, x1s = c1[0] * g.sx;
-        if (ensure(c, c->d_vals, c->vals_cap, (size_t)n_rows) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n_rows)) return DCREG_E_NOMEM;
-        hipLaunchKernelGGL(k_roi_rows, dim3(blocks_for(n_rows, 256)), dim3(256), 0, c->stream, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], n_rows, c->d_vals);
+        if (c->d_vals.ensure(c, (size_t)n_rows) || c->d_vals2.ensure(c, (size_t)n_rows)) return DCREG_E_NOMEM;
+        uint32_t *vals = c->d_vals.data(), *vals2 = c->d_vals2.data();
+        hipLaunchKernelGGL(k_roi_rows, dim3(blocks_for(n_rows, 256)), dim3(256), 0, c->stream, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], n_rows, vals);
         size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, c->d_vals, c->d_vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
-        if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, c->d_vals, c->d_vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, vals, vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
+        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, vals, vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
         uint32_t last[2] = {0u, 0u};
-        HIP_TRY(c, hipMemcpyAsync(&last[0], c->d_vals + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(&last[1], c->d_vals2 + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&last[0], vals + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&last[1], vals2 + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
         count = last[0] + last[1];
         if (count != 0u && (int64_t)count < n) {
-            dcreg_ctx::IndexSet &s = c->roi_store;
-            if (ensure(c, s.raw, s.raw_cap, (size_t)count)) return DCREG_E_NOMEM;
-            hipLaunchKernelGGL(k_roi_copy, dim3((unsigned)n_rows), dim3(256), 0, c->stream, g.pts, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], c->d_vals2, s.raw);
+            if (c->roi_store.raw.ensure(c, (size_t)count)) return DCREG_E_NOMEM;
+            hipLaunchKernelGGL(k_roi_copy, dim3((unsigned)n_rows), dim3(256), 0, c->stream, g.pts, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], vals2,
+                               c->roi_store.raw.data());
             HIP_TRY(c, hipGetLastError());
         }
     }
@@ -350,12 +333,12 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
         c->roi_built = true; c->roi_empty = true;
         return DCREG_OK;
     }
-    dcreg_ctx::IndexSet &s = c->roi_store;
-    s.n = (int64_t)count;
-    swap_index(c);                                                  // the members are the window's now (its buffers of the last build are reused)
-    int rc = build_index(c, target_dst(c), c->radius_hint * (1.0 + c->opt_cert_margin), &c->occupied_cells);
-    if (rc == DCREG_OK) rc = build_gap_field(c, c->radius_hint * (1.0 + c->opt_cert_margin));
-    if (rc == DCREG_OK) rc = build_row_words(c);
+    c->roi_store.n = (int64_t)count;
+    swap_index(c);                                                  // map is the window's now (its buffers of the last build are reused)
+    IndexSet &m = c->map;
+    int rc = build_index(c, m.raw.data(), m.n, m, c->radius_hint * (1.0 + c->opt_cert_margin), &m.occupied);
+    if (rc == DCREG_OK) rc = build_gap_field(c, m, c->radius_hint * (1.0 + c->opt_cert_margin));
+    if (rc == DCREG_OK) rc = build_row_words(c, m);
     if (rc != DCREG_OK) { swap_index(c); return rc; }               // (the whole map stays usable)
     c->roi_built = true;
     return DCREG_OK;
@@ -364,8 +347,7 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
 // grid over the body-frame source cloud (backward pass of dcreg_p2p_error); built lazily, once per source
 int build_aux_index(dcreg_ctx *c) {
     if (c->aux_valid) return DCREG_OK;
-    GridDst d{c->d_src_raw, c->n_src, &c->d_aux, &c->aux_cap, &c->d_aux_cell_start, &c->aux_cell_cap, &c->aux_grid, &c->aux_n_cells};
-    int rc = build_index(c, d, c->radius_hint, nullptr);
+    int rc = build_index(c, c->d_src_raw.data(), c->n_src, c->aux, c->radius_hint, nullptr);
     if (rc) return rc;
     c->aux_valid = true;
     return DCREG_OK;
@@ -383,32 +365,31 @@ int refuse_in_flight(dcreg_ctx *c) {
 // host, no stream synchronise in dcreg_set_source
 static bool small_host_frame(int64_t n, int64_t stride) { return n <= 65536 && n * stride <= (int64_t)1 << 20; }
 
-int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, float4 *&raw, size_t &raw_cap) {
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw) {
     if (!xyz || n < 0 || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("cloud too large (%lld points)", (long long)n); return DCREG_E_INVALID; }
-    if (ensure(c, raw, raw_cap, (size_t)n)) return DCREG_E_NOMEM;
+    if (raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     if (n == 0) return DCREG_OK;
     const float *src = xyz;
     if (!on_device) {
-        if (ensure(c, c->d_stage, c->stage_cap, (size_t)(n * stride))) return DCREG_E_NOMEM;
+        if (c->d_stage.ensure(c, (size_t)(n * stride))) return DCREG_E_NOMEM;
         const float *from = xyz;
         const size_t words = (size_t)(n * stride);
         if (small_host_frame(n, stride)) {
             // through the context's own pinned block: safe for pageable, pinned and registered buffers alike, and the
             // copy engine reads pinned memory without the runtime's staging pass
-            if (words > c->h_stage_cap) {
-                if (c->h_stage) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_cap = 0; c->h_stage_busy = false; }
-                HIP_TRY(c, hipHostMalloc((void **)&c->h_stage, sizeof(float) * words, hipHostMallocDefault));
-                c->h_stage_cap = words;
+            if (words > c->h_stage.cap()) {
+                if (c->h_stage) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->h_stage.reset(); c->h_stage_busy = false; }
+                HIP_TRY(c, c->h_stage.alloc(words, hipHostMallocDefault));
             }
             if (!c->h_stage_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->h_stage_ev, hipEventDisableTiming));
             if (c->h_stage_busy) { HIP_TRY(c, hipEventSynchronize(c->h_stage_ev)); c->h_stage_busy = false; }   // (the previous frame's upload: long done)
-            std::memcpy(c->h_stage, xyz, sizeof(float) * words);
-            from = c->h_stage;
+            std::memcpy(c->h_stage.data(), xyz, sizeof(float) * words);
+            from = c->h_stage.data();
         }
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage, from, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-        if (from == c->h_stage) { HIP_TRY(c, hipEventRecord(c->h_stage_ev, c->stream)); c->h_stage_busy = true; }
-        src = c->d_stage;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), from, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+        if (from == c->h_stage.data()) { HIP_TRY(c, hipEventRecord(c->h_stage_ev, c->stream)); c->h_stage_busy = true; }
+        src = c->d_stage.data();
     } else if (c->stream == c->own_stream) {
         // The caller most likely wrote the cloud on the legacy default stream (torch's default stream is that stream: cuda_stream == 0), and
         // the context's own stream is non-blocking, so nothing orders it after that stream: make it wait for the work queued there so far.
@@ -417,7 +398,7 @@ int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool
         HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
     }
-    hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw);
+    hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw.data());
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
 }
@@ -429,33 +410,34 @@ static int set_target(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (n <= 0) { c->fail("target cloud is null or empty"); return DCREG_E_INVALID; }   // icp_test_runner.cpp:1643
     HIP_TRY(c, hipSetDevice(c->device));
     // packed and checked beside the current map (in the k-NN query buffer): a refused cloud leaves the map as it was
-    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
+    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned);
     if (rc) return rc;
     double box[6];
-    rc = device_bounds(c, c->d_aligned, n, box, box + 3);
+    rc = device_bounds(c, c->d_aligned.data(), n, box, box + 3);
     if (rc) return rc;
     for (int a = 0; a < 6; ++a) if (!std::isfinite(box[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     return target_commit(c, n, box, radius_hint);
 }
 
-// the checked cloud of n points in c->d_aligned (packed as k_pack packs it), with bounds box = {min xyz, max xyz}, becomes the target
+// the checked cloud of n points in c->d_aligned.data() (packed as k_pack packs it), with bounds box = {min xyz, max xyz}, becomes the target
 static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double radius_hint) {
     int rc;
     (void)roi_deactivate(c);             // the new map goes into the whole map's buffers; a window of the old one means nothing
     c->roi_built = false; c->whole_capped = false;
-    std::swap(c->d_tgt_raw, c->d_aligned); std::swap(c->tgt_raw_cap, c->aligned_cap);
-    c->n_tgt = n;
+    IndexSet &m = c->map;
+    m.raw.swap(c->d_aligned);
+    m.n = n;
     c->radius_hint = radius_hint;
     // the cells are sized for the SEARCH radius (make_lin_args): one ring must cover it
-    rc = build_index(c, target_dst(c), radius_hint * (1.0 + c->opt_cert_margin), &c->occupied_cells, box);
-    if (rc) { c->n_tgt = 0; return rc; }
+    rc = build_index(c, m.raw.data(), n, m, radius_hint * (1.0 + c->opt_cert_margin), &m.occupied, box);
+    if (rc) { m.n = 0; return rc; }
     c->whole_capped = c->last_build_capped;
     for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
-    c->build_per_cell = (double)n / (double)std::max<uint32_t>(c->occupied_cells, 1u);
-    rc = build_gap_field(c, radius_hint * (1.0 + c->opt_cert_margin));
-    if (rc) { c->n_tgt = 0; return rc; }
-    rc = build_row_words(c);
-    if (rc) { c->n_tgt = 0; return rc; }
+    c->build_per_cell = (double)n / (double)std::max<uint32_t>(m.occupied, 1u);
+    rc = build_gap_field(c, m, radius_hint * (1.0 + c->opt_cert_margin));
+    if (rc) { m.n = 0; return rc; }
+    rc = build_row_words(c, m);
+    if (rc) { m.n = 0; return rc; }
     drop_warm(c);            // positions and certificates refer to the old target
     c->order_valid = false;  // ... and the cost estimate of the query groups to the old map
     c->last_pose_valid = false;
@@ -468,24 +450,6 @@ static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double ra
 // path), and re-derived from the device-resident raw points where it cannot (rebuilt).  Every search is exact in any grid, so either way
 // the map answers bitwise as dcreg_set_target of the updated cloud would.  A refused call changes nothing: everything is checked in scratch
 // buffers first, and the arrays that replace the map's are allocated before the first of them is written.
-
-// grows a buffer whose first `keep` elements must survive (geometric capacity; the old buffer is freed only once the copy is queued behind it)
-template <typename T>
-static int grow_keep(dcreg_ctx *c, T *&ptr, size_t &cap, size_t need, size_t keep) {
-    if (need <= cap && ptr) return DCREG_OK;
-    const size_t n = std::max(need, cap + cap / 2);
-    T *p = nullptr;
-    if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->fail("hipMalloc(%zu B) failed while growing the map", n * sizeof(T));
-        return DCREG_E_NOMEM;
-    }
-    if (ptr && keep) HIP_TRY(c, hipMemcpyAsync(p, ptr, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (ptr) (void)hipFree(ptr);
-    ptr = p; cap = n;
-    return DCREG_OK;
-}
 
 static void update_info(dcreg_map_update *info, int64_t offered, int64_t added, int64_t removed, int64_t n_target, int rebuilt) {
     if (!info) return;
@@ -521,28 +485,28 @@ static MapBox change_box(const uint32_t w[kMwWords], const GridDev &g) {
 }
 // scratch the fields of a change need (before the first write of an update)
 static int fields_reserve(dcreg_ctx *c, const MapBox &S) {
-    const GridDev &g = c->grid;
+    const GridDev &g = c->map.grid;
     if (!g.gap) return DCREG_OK;
     const MapBox E = box_grow(S, 2 * g.gap_cap, g);
     const size_t ne = (size_t)box_cells(E);
-    if (ensure(c, c->d_fgap, c->fgap_cap, 2 * ne) || ensure(c, c->d_fown, c->fown_cap, 2 * ne)) return DCREG_E_NOMEM;
+    if (c->d_fgap.ensure(c, 2 * ne) || c->d_fown.ensure(c, 2 * ne)) return DCREG_E_NOMEM;
     return DCREG_OK;
 }
 // row words and fields of the cells a change can reach, recomputed from the updated table (k_ymask_box, k_gap_*_box)
 static void fields_local(dcreg_ctx *c, const MapBox &S) {
-    const GridDev &g = c->grid;
+    const GridDev &g = c->map.grid;
     if (g.ymask) {
         const int xb0 = S.x0 >> 4, xb1 = (S.x1 + 15) >> 4, yw0 = S.y0 >> 5, yw1 = (S.y1 + 31) >> 5;
         const int64_t nw = (int64_t)(xb1 - xb0) * (yw1 - yw0) * (S.z1 - S.z0);
         hipLaunchKernelGGL(k_ymask_box, dim3(blocks_for(nw, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, g.nxb, g.nyw,
-                           xb0, xb1 - xb0, yw0, yw1 - yw0, S.z0, S.z1 - S.z0, c->d_ymask);
+                           xb0, xb1 - xb0, yw0, yw1 - yw0, S.z0, S.z1 - S.z0, c->map.ymask.data());
     }
     if (!g.gap) return;
     const int rings = g.gap_cap;
     const MapBox B = box_grow(S, rings, g), E = box_grow(B, rings, g);
     const int64_t ne = box_cells(E), nb = box_cells(B);
-    uint8_t *gap_p = c->d_fgap, *gap_d = c->d_fgap + ne;
-    uint32_t *own_p = c->d_fown, *own_d = c->d_fown + ne;
+    uint8_t *gap_p = c->d_fgap.data(), *gap_d = gap_p + ne;
+    uint32_t *own_p = c->d_fown.data(), *own_d = own_p + ne;
     hipLaunchKernelGGL(k_gap_init_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 0, 0u, gap_p, own_p);
     for (int r = 1; r <= rings; ++r)
         hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.nx, g.ny, E, r);
@@ -552,131 +516,116 @@ static void fields_local(dcreg_ctx *c, const MapBox &S) {
             hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_d, own_d, g.nx, g.ny, E, r);
     }
     hipLaunchKernelGGL(k_gap_store_box, dim3(blocks_for(nb, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.owner ? own_d : (const uint32_t *)nullptr,
-                       g.nx, g.ny, E, B, c->d_gap, c->d_owner);
+                       g.nx, g.ny, E, B, c->map.gap.data(), c->map.owner.data());
 }
 
 static int count_occupied(dcreg_ctx *c, const GridDev &g, int64_t n_cells, uint32_t *out) {
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_count_occupied, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.cell_start, n_cells, g.sx, c->d_scratch);
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_count_occupied, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.cell_start, n_cells, g.sx, c->d_scratch.data());
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch.data(), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
 }
 
-// a field buffer sized for a new grid, allocated beside the current one (which the current index keeps reading until the swap)
-template <typename T>
-static int reserve_beside(dcreg_ctx *c, T *cur, size_t cap, size_t need, T *&fresh) {
-    fresh = nullptr;
-    if (need <= cap && cur) return DCREG_OK;
-    if (hipMalloc((void **)&fresh, std::max<size_t>(need, 1) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError(); fresh = nullptr;
-        c->fail("hipMalloc(%zu B) failed while re-deriving the map's grid", need * sizeof(T));
-        return DCREG_E_NOMEM;
-    }
-    return DCREG_OK;
-}
-
-// The map's raw points (c->n_tgt of them, index order) are final and bounded by c->tgt_box: derive the grid anew, over that box enlarged by
+// The map's raw points (c->map.n of them, index order) are final and bounded by c->tgt_box: derive the grid anew, over that box enlarged by
 // "map_grow_margin" on each side in x and y - not in z: a ground vehicle's map is flat, and z slack would multiply the dense table of a
 // wide, flat map (12 m of height grown by 20 m on each side is 4.3 x the entries) and push it past its budget into coarser cells.  A point
 // that leaves the box in z re-derives the grid again.  keep_edge: the current cell edge and x sub-cells where the table budget allows
-// them (one key sort); otherwise - or when it does not - build_index's rules.  Built beside the current index and swapped in at the end;
-// *swapped tells whether that happened (a failure before it leaves the current index standing).
+// them (one key sort); otherwise - or when it does not - build_index's rules.  Built beside the current index (c->map_alt, and fields
+// allocated beside the current ones where these are too small) and swapped in at the end; *swapped tells whether that happened (a
+// failure before it leaves the current index standing).
 static int map_rebuild(dcreg_ctx *c, bool keep_edge, bool *swapped) {
     *swapped = false;
     const double m[3] = {c->opt_map_grow_margin, c->opt_map_grow_margin, 0.0};
     double box[6];
     for (int a = 0; a < 3; ++a) { box[a] = c->tgt_box[a] - m[a]; box[3 + a] = c->tgt_box[3 + a] + m[a]; }
-    GridDev g2{};
-    int64_t n_cells2 = 0;
     uint32_t occ = 0;
-    GridDst d{c->d_tgt_raw, c->n_tgt, &c->d_tgt_alt, &c->tgt_alt_cap, &c->d_cell_alt, &c->cell_alt_cap, &g2, &n_cells2};
-    const GridDev &g = c->grid;
+    IndexSet &cur = c->map, &alt = c->map_alt;
+    const GridDev &g = cur.grid;
     bool capped = c->whole_capped, built = false;
     if (keep_edge) {
         double dims[3], entries = (double)g.sx;
         for (int a = 0; a < 3; ++a) { dims[a] = std::floor((box[3 + a] - box[a]) * g.inv_h) + 1.0; entries *= dims[a]; }
         if (entries <= (double)c->opt_max_table_entries && dims[0] < 2e9 && dims[1] < 2e9 && dims[2] < 2e9) {
-            int rc = build_grid_at(c, d, g.h, box, box + 3, &occ, g.sx);
+            int rc = build_grid_at(c, cur.raw.data(), cur.n, alt, g.h, box, box + 3, &occ, g.sx);
             if (rc) return rc;
-            rc = count_occupied(c, g2, n_cells2, &occ);
+            rc = count_occupied(c, alt.grid, alt.n_cells, &occ);
             if (rc) return rc;
             built = true;
         }
     }
     if (!built) {
-        int rc = build_index(c, d, c->radius_hint * (1.0 + c->opt_cert_margin), &occ, box);
+        int rc = build_index(c, cur.raw.data(), cur.n, alt, c->radius_hint * (1.0 + c->opt_cert_margin), &occ, box);
         if (rc) return rc;
         capped = c->last_build_capped;
     }
-    // the fields of the new grid: buffers beside the current ones where these are too small
-    const size_t n_words = (size_t)g2.nz * (size_t)((g2.nx + 15) >> 4) * (size_t)((g2.ny + 31) >> 5);
-    uint8_t *gap = nullptr; uint32_t *owner = nullptr, *ymask = nullptr;
-    int rc = reserve_beside(c, c->d_ymask, c->ymask_cap, n_words, ymask);
-    if (rc == DCREG_OK && c->opt_gap_field) rc = reserve_beside(c, c->d_gap, c->gap_cap, (size_t)n_cells2, gap);
-    if (rc == DCREG_OK && c->opt_gap_field) rc = reserve_beside(c, c->d_owner, c->owner_cap, (size_t)n_cells2, owner);
-    if (rc) {
-        for (void *p : {(void *)gap, (void *)owner, (void *)ymask}) if (p) (void)hipFree(p);
-        return rc;
-    }
+    // the fields of the new grid (the current index keeps reading the current ones until the swap)
+    const GridDev &g2 = alt.grid;
+    const size_t n_words = (size_t)g2.nz * (size_t)((g2.nx + 15) >> 4) * (size_t)((g2.ny + 31) >> 5), n_cells2 = (size_t)alt.n_cells;
+    const char *why = "while re-deriving the map's grid";
+    DevBuf<uint8_t> gap;
+    DevBuf<uint32_t> owner, ymask;
+    if ((!cur.ymask.holds(n_words) && ymask.ensure(c, n_words, why)) ||
+        (c->opt_gap_field && !cur.gap.holds(n_cells2) && gap.ensure(c, n_cells2, why)) ||
+        (c->opt_gap_field && !cur.owner.holds(n_cells2) && owner.ensure(c, n_cells2, why)))
+        return DCREG_E_NOMEM;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (ymask) { if (c->d_ymask) (void)hipFree(c->d_ymask); c->d_ymask = ymask; c->ymask_cap = std::max<size_t>(n_words, 1); }
-    if (gap) { if (c->d_gap) (void)hipFree(c->d_gap); c->d_gap = gap; c->gap_cap = std::max<size_t>((size_t)n_cells2, 1); }
-    if (owner) { if (c->d_owner) (void)hipFree(c->d_owner); c->d_owner = owner; c->owner_cap = std::max<size_t>((size_t)n_cells2, 1); }
-    std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
-    std::swap(c->d_cell_start, c->d_cell_alt); std::swap(c->cell_cap, c->cell_alt_cap);
+    if (ymask) cur.ymask = std::move(ymask);
+    if (gap) cur.gap = std::move(gap);
+    if (owner) cur.owner = std::move(owner);
+    cur.sorted.swap(alt.sorted);
+    cur.cell_start.swap(alt.cell_start);
     *swapped = true;
-    c->grid = g2; c->n_cells = n_cells2;
-    c->occupied_cells = occ;
+    cur.grid = alt.grid; cur.n_cells = alt.n_cells;
+    cur.occupied = occ;
     c->whole_capped = capped;
-    c->build_per_cell = (double)c->n_tgt / (double)std::max<uint32_t>(occ, 1u);
-    rc = build_gap_field(c, c->radius_hint * (1.0 + c->opt_cert_margin));
-    if (rc == DCREG_OK) rc = build_row_words(c);
+    c->build_per_cell = (double)cur.n / (double)std::max<uint32_t>(occ, 1u);
+    int rc = build_gap_field(c, cur, c->radius_hint * (1.0 + c->opt_cert_margin));
+    if (rc == DCREG_OK) rc = build_row_words(c, cur);
     return rc;
 }
 
 // The appended points (c->d_map_new[0, n_add), w = their map indices; their keys and input ranks at keys / vals) go into the current grid.
 static int map_merge(dcreg_ctx *c, uint32_t n_add, uint32_t *keys, uint32_t *vals, uint32_t *keys2, uint32_t *vals2, uint32_t *b, const uint32_t w[kMwWords]) {
-    GridDev &g = c->grid;
-    const int64_t n_old = c->n_tgt, n_new = n_old + n_add;
+    IndexSet &m = c->map;
+    DevBuf<float4> &alt = c->map_alt.sorted;
+    GridDev &g = m.grid;
+    const int64_t n_old = m.n, n_new = n_old + n_add;
     const int64_t n_entries = (int64_t)g.nx * g.sx * g.ny * g.nz;
     const MapBox S = change_box(w, g);
     // ---- every allocation first
-    if (grow_keep(c, c->d_tgt_raw, c->tgt_raw_cap, (size_t)n_new, (size_t)n_old) || ensure(c, c->d_tgt_alt, c->tgt_alt_cap, (size_t)n_new + kPtsPad) ||
-        fields_reserve(c, S))
+    if (m.raw.grow_keep(c, (size_t)n_new, (size_t)n_old) || alt.ensure(c, (size_t)n_new + kPtsPad) || fields_reserve(c, S))
         return DCREG_E_NOMEM;
     int bits = 1;
     while (((int64_t)1 << bits) < n_entries && bits < 32) ++bits;
     int rc = sort_pairs_u32(c, keys, keys2, vals, vals2, (size_t)n_add, bits);
     if (rc) return rc;
     // ---- from here on the map is rewritten
-    HIP_TRY(c, hipMemcpyAsync(c->d_tgt_raw + n_old, c->d_map_new, sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch + kMwOccupied, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_map_bpos, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, keys2, n_add, g.cell_start, g.sx, b, c->d_scratch);
-    hipLaunchKernelGGL(k_map_merge_old, dim3(blocks_for(n_old, 256)), dim3(256), 0, c->stream, c->d_tgt, (uint32_t)n_old, b, n_add, c->d_tgt_alt);
-    hipLaunchKernelGGL(k_map_merge_new, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, c->d_map_new, vals2, b, n_add, c->d_tgt_alt);
-    HIP_TRY(c, hipMemsetAsync(c->d_tgt_alt + n_new, 0, kPtsPad * sizeof(float4), c->stream));
+    uint32_t *scratch = c->d_scratch.data();
+    HIP_TRY(c, hipMemcpyAsync(m.raw.data() + n_old, c->d_map_new.data(), sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(scratch + kMwOccupied, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_map_bpos, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, keys2, n_add, g.cell_start, g.sx, b, scratch);
+    hipLaunchKernelGGL(k_map_merge_old, dim3(blocks_for(n_old, 256)), dim3(256), 0, c->stream, m.sorted.data(), (uint32_t)n_old, b, n_add, alt.data());
+    hipLaunchKernelGGL(k_map_merge_new, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, c->d_map_new.data(), vals2, b, n_add, alt.data());
+    HIP_TRY(c, hipMemsetAsync(alt.data() + n_new, 0, kPtsPad * sizeof(float4), c->stream));
     const int64_t first = (int64_t)w[kMwKeyMin] + 1;       // entries up to the smallest new key keep their value
     if (first <= n_entries)
-        hipLaunchKernelGGL(k_map_table_insert, dim3(blocks_for(n_entries - first + 1, 256)), dim3(256), 0, c->stream, c->d_cell_start, first, n_entries, keys2, n_add);
-    std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
-    c->n_tgt = n_new;
-    g.pts = c->d_tgt; g.n_pts = (uint32_t)n_new;
+        hipLaunchKernelGGL(k_map_table_insert, dim3(blocks_for(n_entries - first + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), first, n_entries,
+                           keys2, n_add);
+    m.sorted.swap(alt);
+    m.n = n_new;
+    g.pts = m.sorted.data(); g.n_pts = (uint32_t)n_new;
     fields_local(c, S);
     uint32_t occ_new = 0;
-    HIP_TRY(c, hipMemcpyAsync(&occ_new, c->d_scratch + kMwOccupied, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&occ_new, scratch + kMwOccupied, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->occupied_cells += occ_new;
+    m.occupied += occ_new;
     return DCREG_OK;
 }
 
-// a view of the whole map's index, whichever index is active (a refused or empty update must not swap them: that drops the states)
-struct WholeMap { float4 *raw; float4 *sorted; int64_t n; GridDev g; };
-static WholeMap whole_map(const dcreg_ctx *c) {
-    if (c->roi_active) return WholeMap{c->roi_store.raw, c->roi_store.sorted, c->roi_store.n, c->roi_store.grid};
-    return WholeMap{c->d_tgt_raw, c->d_tgt, c->n_tgt, c->grid};
-}
+// the whole map's index, whichever index is active (a refused or empty update must not swap them: that drops the states)
+static const IndexSet &whole_map(const dcreg_ctx *c) { return c->roi_active ? c->roi_store : c->map; }
 
 static bool finite_pose(const double *R, const double *t) {
     for (int k = 0; k < 9; ++k) if (!std::isfinite(R[k])) return false;
@@ -690,51 +639,50 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (int rc = refuse_in_flight(c)) return rc;
     if (!R || !t || (!from_source && (!xyz || n < 0 || stride < 3)) || !std::isfinite(min_spacing)) { c->fail("invalid insert arguments"); return DCREG_E_INVALID; }
     if (!finite_pose(R, t)) { c->fail("the pose of an insert has non-finite entries"); return DCREG_E_INVALID; }
-    if (c->n_tgt <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     if (from_source && c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
     const int64_t m = from_source ? c->n_src : n;
     if (m >= ((int64_t)1 << 31)) { c->fail("too many points (%lld)", (long long)m); return DCREG_E_INVALID; }
     const int64_t n_old = whole_map(c).n;
     if (m == 0) { update_info(info, 0, 0, 0, n_old, 0); return DCREG_OK; }
     HIP_TRY(c, hipSetDevice(c->device));
-    const float4 *in = c->d_src_raw;
+    const float4 *in = c->d_src_raw.data();
     if (!from_source) {
-        int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
+        int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned);
         if (rc) return rc;
-        in = c->d_aligned;
+        in = c->d_aligned.data();
     }
     const size_t m1 = (size_t)m + 1;
-    if (ensure(c, c->d_map_q, c->map_q_cap, (size_t)m) || ensure(c, c->d_map_new, c->map_new_cap, (size_t)m) || ensure(c, c->d_upd, c->upd_cap, 6 * m1))
-        return DCREG_E_NOMEM;
-    uint32_t *flag = c->d_upd, *pos = flag + m1, *keys = pos + m1, *vals = keys + m1, *keys2 = vals + m1, *vals2 = keys2 + m1;
+    if (c->d_map_q.ensure(c, (size_t)m) || c->d_map_new.ensure(c, (size_t)m) || c->d_upd.ensure(c, 6 * m1)) return DCREG_E_NOMEM;
+    uint32_t *flag = c->d_upd.data(), *pos = flag + m1, *keys = pos + m1, *vals = keys + m1, *keys2 = vals + m1, *vals2 = keys2 + m1;
     uint32_t w[kMwWords];
     words_init(w);
-    HIP_TRY(c, hipMemcpyAsync(c->d_scratch, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
     PoseArg P{};
     for (int k = 0; k < 9; ++k) P.R[k] = R[k];
     for (int k = 0; k < 3; ++k) P.t[k] = t[k];
-    hipLaunchKernelGGL(k_map_transform, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, in, m, P, c->d_map_q, c->d_scratch);
-    const WholeMap wm = whole_map(c);
+    hipLaunchKernelGGL(k_map_transform, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, in, m, P, c->d_map_q.data(), c->d_scratch.data());
+    const GridDev wg = whole_map(c).grid;
     const float *d2 = nullptr;
     float spacing_sq = 0.f;
     if (min_spacing > 0.0) {      // the map as it stood: dcreg_knn with k = 1 (the bound only has to reach the spacing)
-        if (ensure(c, c->d_nn_idx, c->nn_idx_cap, (size_t)m) || ensure(c, c->d_nn_d2, c->nn_d2_cap, (size_t)m)) return DCREG_E_NOMEM;
-        int rc = launch_knn(c, wm.g, c->d_map_q, m, 1, min_spacing, nullptr, c->d_nn_idx, c->d_nn_d2);
+        if (c->d_nn_idx.ensure(c, (size_t)m) || c->d_nn_d2.ensure(c, (size_t)m)) return DCREG_E_NOMEM;
+        int rc = launch_knn(c, wg, c->d_map_q.data(), m, 1, min_spacing, nullptr, c->d_nn_idx.data(), c->d_nn_d2.data());
         if (rc) return rc;
-        d2 = c->d_nn_d2;
+        d2 = c->d_nn_d2.data();
         spacing_sq = (float)(min_spacing * min_spacing);
     }
     hipLaunchKernelGGL(k_map_keep, dim3(blocks_for((int64_t)m1, 256)), dim3(256), 0, c->stream, m, d2, spacing_sq, flag);
     {
         size_t tmp = 0;
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
-        if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
+        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
     }
-    hipLaunchKernelGGL(k_map_append, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, c->d_map_q, m, flag, pos, (uint32_t)n_old, wm.g, c->d_map_new,
-                       keys, vals, c->d_scratch);
+    hipLaunchKernelGGL(k_map_append, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, c->d_map_q.data(), m, flag, pos, (uint32_t)n_old, wg, c->d_map_new.data(),
+                       keys, vals, c->d_scratch.data());
     uint32_t n_add = 0;
-    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch.data(), sizeof(w), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&n_add, pos + m, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -756,7 +704,7 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
         for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
         map_changed(c);
         // the density the cell edge was sized for has doubled: derive the grid again (build_index's rules)
-        if ((double)c->n_tgt / (double)std::max<uint32_t>(c->occupied_cells, 1u) > 2.0 * c->build_per_cell) {
+        if ((double)c->map.n / (double)std::max<uint32_t>(c->map.occupied, 1u) > 2.0 * c->build_per_cell) {
             rc = map_rebuild(c, false, &swapped);
             rebuilt = swapped ? 1 : 0;
             if (rc != DCREG_OK && !swapped) {
@@ -768,22 +716,22 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
             }
         }
     } else {
-        if (grow_keep(c, c->d_tgt_raw, c->tgt_raw_cap, (size_t)(n_old + n_add), (size_t)n_old)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_tgt_raw + n_old, c->d_map_new, sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
+        if (c->map.raw.grow_keep(c, (size_t)(n_old + n_add), (size_t)n_old)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->map.raw.data() + n_old, c->d_map_new.data(), sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
         const double old_box[6] = {c->tgt_box[0], c->tgt_box[1], c->tgt_box[2], c->tgt_box[3], c->tgt_box[4], c->tgt_box[5]};
-        c->n_tgt = n_old + n_add;               // (the points beyond n_old are not read by the index as it was)
+        c->map.n = n_old + n_add;               // (the points beyond n_old are not read by the index as it was)
         for (int a = 0; a < 6; ++a) c->tgt_box[a] = box[a];
         rebuilt = 1;
         rc = map_rebuild(c, true, &swapped);
         if (rc != DCREG_OK && !swapped) {                               // nothing was swapped in: the old map stands
-            c->n_tgt = n_old;
+            c->map.n = n_old;
             for (int a = 0; a < 6; ++a) c->tgt_box[a] = old_box[a];
             return rc;
         }
         map_changed(c);
     }
-    if (rc) { c->n_tgt = 0; return rc; }         // (a failure after a rebuild swapped its grid in: the map is gone, as after a failed dcreg_set_target)
-    update_info(info, m, n_add, 0, c->n_tgt, rebuilt);
+    if (rc) { c->map.n = 0; return rc; }         // (a failure after a rebuild swapped its grid in: the map is gone, as after a failed dcreg_set_target)
+    update_info(info, m, n_add, 0, c->map.n, rebuilt);
     return DCREG_OK;
 }
 
@@ -792,30 +740,30 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     if (int rc = refuse_in_flight(c)) return rc;
     if (!lo || !hi) { c->fail("invalid crop arguments"); return DCREG_E_INVALID; }
     for (int a = 0; a < 3; ++a) if (std::isnan(lo[a]) || std::isnan(hi[a])) { c->fail("the crop box has NaN bounds"); return DCREG_E_INVALID; }
-    if (c->n_tgt <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
-    const WholeMap wm = whole_map(c);
+    const IndexSet &wm = whole_map(c);
     const int64_t n = wm.n;
     const size_t n1 = (size_t)n + 1;
-    if (ensure(c, c->d_upd, c->upd_cap, 4 * n1)) return DCREG_E_NOMEM;
-    uint32_t *flag_r = c->d_upd, *pos_r = flag_r + n1, *flag_s = pos_r + n1, *pos_s = flag_s + n1;
+    if (c->d_upd.ensure(c, 4 * n1)) return DCREG_E_NOMEM;
+    uint32_t *flag_r = c->d_upd.data(), *pos_r = flag_r + n1, *flag_s = pos_r + n1, *pos_s = flag_s + n1;
     CropBox bx;
     for (int a = 0; a < 3; ++a) { bx.lo[a] = lo[a]; bx.hi[a] = hi[a]; }
     uint32_t w[kMwWords];
     words_init(w);
-    HIP_TRY(c, hipMemcpyAsync(c->d_scratch, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw, n, bx, flag_r);
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted, n, bx, flag_s);
+    HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, bx, flag_r);
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, bx, flag_s);
     {
         size_t tmp = 0;
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
-        if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, flag_s, pos_s, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
+        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag_s, pos_s, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
     }
-    hipLaunchKernelGGL(k_crop_scan_box, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.sorted, n, flag_s, wm.g, c->d_scratch);
+    hipLaunchKernelGGL(k_crop_scan_box, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, flag_s, wm.grid, c->d_scratch.data());
     uint32_t kept = 0;
-    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch.data(), sizeof(w), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&kept, pos_r + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -823,7 +771,8 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     if ((int64_t)kept == n) { update_info(info, n, 0, 0, n, 0); return DCREG_OK; }      // nothing outside the box: nothing changes
     // ---- the map changes
     (void)roi_deactivate(c);
-    GridDev &g = c->grid;
+    IndexSet &m = c->map, &alt = c->map_alt;
+    GridDev &g = m.grid;
     double kbox[6];
     for (int a = 0; a < 3; ++a) { kbox[a] = ord2f(w[kMwMin + a]); kbox[3 + a] = ord2f(w[kMwMax + a]); }
     const int64_t n_entries = (int64_t)g.nx * g.sx * g.ny * g.nz;
@@ -831,73 +780,77 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     for (int a = 0; a < 3; ++a) kept_entries *= std::floor((kbox[3 + a] - kbox[a] + (a < 2 ? 2.0 * c->opt_map_grow_margin : 0.0)) * g.inv_h) + 1.0;
     const bool rederive = !c->opt_map_update || kept_entries < 0.25 * (double)n_entries;
     const MapBox S = change_box(w, g);
-    if (ensure(c, c->d_tgt_raw_alt, c->tgt_raw_alt_cap, (size_t)kept) || (!rederive && (ensure(c, c->d_tgt_alt, c->tgt_alt_cap, (size_t)kept + kPtsPad) || fields_reserve(c, S))))
+    if (alt.raw.ensure(c, (size_t)kept) || (!rederive && (alt.sorted.ensure(c, (size_t)kept + kPtsPad) || fields_reserve(c, S))))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_crop_raw, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_tgt_raw, n, flag_r, pos_r, c->d_tgt_raw_alt);
+    hipLaunchKernelGGL(k_crop_raw, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, m.raw.data(), n, flag_r, pos_r, alt.raw.data());
     int rebuilt = 0, rc = DCREG_OK;
     bool swapped = false;
     if (rederive) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
+        m.raw.swap(alt.raw);
         const double old_box[6] = {c->tgt_box[0], c->tgt_box[1], c->tgt_box[2], c->tgt_box[3], c->tgt_box[4], c->tgt_box[5]};
-        c->n_tgt = kept;
+        m.n = kept;
         for (int a = 0; a < 6; ++a) c->tgt_box[a] = kbox[a];
         rebuilt = 1;
         rc = map_rebuild(c, true, &swapped);
         if (rc != DCREG_OK && !swapped) {                               // nothing was swapped in: the old map stands
-            std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
-            c->n_tgt = n;
+            m.raw.swap(alt.raw);
+            m.n = n;
             for (int a = 0; a < 6; ++a) c->tgt_box[a] = old_box[a];
             return rc;
         }
     } else {
-        hipLaunchKernelGGL(k_crop_sorted, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_tgt, n, flag_s, pos_s, pos_r, c->d_tgt_alt);
-        HIP_TRY(c, hipMemsetAsync(c->d_tgt_alt + kept, 0, kPtsPad * sizeof(float4), c->stream));
-        hipLaunchKernelGGL(k_crop_table, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_cell_start, n_entries, pos_s);
-        std::swap(c->d_tgt_raw, c->d_tgt_raw_alt); std::swap(c->tgt_raw_cap, c->tgt_raw_alt_cap);
-        std::swap(c->d_tgt, c->d_tgt_alt); std::swap(c->tgt_cap, c->tgt_alt_cap);
-        c->n_tgt = kept;
-        g.pts = c->d_tgt; g.n_pts = kept;
+        hipLaunchKernelGGL(k_crop_sorted, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, m.sorted.data(), n, flag_s, pos_s, pos_r, alt.sorted.data());
+        HIP_TRY(c, hipMemsetAsync(alt.sorted.data() + kept, 0, kPtsPad * sizeof(float4), c->stream));
+        hipLaunchKernelGGL(k_crop_table, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), n_entries, pos_s);
+        m.raw.swap(alt.raw);
+        m.sorted.swap(alt.sorted);
+        m.n = kept;
+        g.pts = m.sorted.data(); g.n_pts = kept;
         for (int a = 0; a < 6; ++a) c->tgt_box[a] = kbox[a];
         fields_local(c, S);
-        rc = count_occupied(c, g, c->n_cells, &c->occupied_cells);
+        rc = count_occupied(c, g, m.n_cells, &m.occupied);
         if (rc == DCREG_OK) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { c->fail("crop: %s", hipGetErrorString(e)); rc = DCREG_E_DEVICE; } }
     }
     map_changed(c);
-    if (rc) { c->n_tgt = 0; return rc; }
-    update_info(info, n, 0, n - kept, c->n_tgt, rebuilt);
+    if (rc) { m.n = 0; return rc; }
+    update_info(info, n, 0, n - kept, m.n, rebuilt);
     return DCREG_OK;
 }
 
 // dcreg_debug_index_check: the whole map's grid built from scratch (same origin, edge, dims, sub-cells) from its raw points, compared entry by entry
 static int index_check(dcreg_ctx *c, int64_t mm[5]) {
-    const WholeMap wm = whole_map(c);
-    const GridDev &g = wm.g;
+    const IndexSet &wm = whole_map(c);
+    const GridDev &g = wm.grid;
     const int64_t n = wm.n, n_cells = (int64_t)g.nx * g.ny * g.nz, n_entries = n_cells * g.sx;
     const int64_t n_words = (int64_t)g.nz * g.nxb * g.nyw;
-    if (ensure(c, c->d_keys, c->keys_cap, (size_t)n) || ensure(c, c->d_keys2, c->keys2_cap, (size_t)n) ||
-        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+    if (c->d_keys.ensure(c, (size_t)n) || c->d_keys2.ensure(c, (size_t)n) || c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
-    float4 *pts = nullptr; uint32_t *tab = nullptr, *ym = nullptr, *own = nullptr, *own2 = nullptr; uint8_t *gap = nullptr, *gap2 = nullptr;
-    unsigned long long *cnt = nullptr;
-    auto release = [&]() { for (void *p : {(void *)pts, (void *)tab, (void *)ym, (void *)own, (void *)own2, (void *)gap, (void *)gap2, (void *)cnt}) if (p) (void)hipFree(p); };
-    if (hipMalloc((void **)&pts, sizeof(float4) * (size_t)(n + kPtsPad)) != hipSuccess || hipMalloc((void **)&tab, sizeof(uint32_t) * (size_t)(n_entries + 1)) != hipSuccess ||
-        hipMalloc((void **)&ym, sizeof(uint32_t) * (size_t)std::max<int64_t>(n_words, 1)) != hipSuccess ||
-        hipMalloc((void **)&own, sizeof(uint32_t) * (size_t)n_cells) != hipSuccess || hipMalloc((void **)&own2, sizeof(uint32_t) * (size_t)n_cells) != hipSuccess ||
-        hipMalloc((void **)&gap, (size_t)n_cells) != hipSuccess || hipMalloc((void **)&gap2, (size_t)n_cells) != hipSuccess ||
-        hipMalloc((void **)&cnt, sizeof(unsigned long long) * 5) != hipSuccess) {
-        (void)hipGetLastError(); release(); c->fail("no memory for the index check"); return DCREG_E_NOMEM;
+    // scratch of this check only
+    DevBuf<float4> pts_b;
+    DevBuf<uint32_t> tab_b, ym_b, own_b, own2_b;
+    DevBuf<uint8_t> gap_b, gap2_b;
+    DevBuf<unsigned long long> cnt_b;
+    if (pts_b.alloc((size_t)(n + kPtsPad)) != hipSuccess || tab_b.alloc((size_t)(n_entries + 1)) != hipSuccess ||
+        ym_b.alloc((size_t)std::max<int64_t>(n_words, 1)) != hipSuccess || own_b.alloc((size_t)n_cells) != hipSuccess ||
+        own2_b.alloc((size_t)n_cells) != hipSuccess || gap_b.alloc((size_t)n_cells) != hipSuccess || gap2_b.alloc((size_t)n_cells) != hipSuccess ||
+        cnt_b.alloc(5) != hipSuccess) {
+        (void)hipGetLastError(); c->fail("no memory for the index check"); return DCREG_E_NOMEM;
     }
+    float4 *pts = pts_b.data();
+    uint32_t *tab = tab_b.data(), *ym = ym_b.data(), *own = own_b.data(), *own2 = own2_b.data();
+    uint8_t *gap = gap_b.data(), *gap2 = gap2_b.data();
+    unsigned long long *cnt = cnt_b.data();
     HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 5, c->stream));
-    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw, n, g, c->d_keys, c->d_vals);
+    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, g, c->d_keys.data(), c->d_vals.data());
     int bits = 1;
     while (((int64_t)1 << bits) < n_entries && bits < 32) ++bits;
-    int rc = sort_pairs_u32(c, c->d_keys, c->d_keys2, c->d_vals, c->d_vals2, (size_t)n, bits);
-    if (rc) { release(); return rc; }
-    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw, c->d_vals2, n, pts);
+    int rc = sort_pairs_u32(c, c->d_keys.data(), c->d_keys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bits);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), c->d_vals2.data(), n, pts);
     HIP_TRY(c, hipMemsetAsync(pts + n, 0, kPtsPad * sizeof(float4), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_keys2, n, n_entries, tab, c->d_scratch);
+    HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_entries, tab, c->d_scratch.data());
     hipLaunchKernelGGL(k_count_diff<float4>, dim3(blocks_for(n + kPtsPad, 256)), dim3(256), 0, c->stream, (const float4 *)g.pts, (const float4 *)pts, n + kPtsPad, cnt);
     hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, g.cell_start, (const uint32_t *)tab, n_entries + 1, cnt + 1);
     if (g.ymask) {
@@ -920,7 +873,6 @@ static int index_check(dcreg_ctx *c, int64_t mm[5]) {
     unsigned long long h[5] = {0, 0, 0, 0, 0};
     const hipError_t e0 = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     const hipError_t e1 = hipStreamSynchronize(c->stream);
-    release();
     HIP_TRY(c, e0); HIP_TRY(c, e1);
     HIP_TRY(c, hipGetLastError());
     for (int k = 0; k < 5; ++k) mm[k] = (int64_t)h[k];
@@ -931,13 +883,13 @@ static int target_get(const dcreg_ctx *cc, float *out, int64_t capacity) {
     dcreg_ctx *c = const_cast<dcreg_ctx *>(cc);
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
-    const WholeMap wm = whole_map(c);
+    const IndexSet &wm = whole_map(c);
     if (wm.n <= 0) { c->fail("no target"); return DCREG_E_STATE; }
     if (!out || capacity < wm.n) { c->fail("the output holds %lld points, the map %lld", (long long)capacity, (long long)wm.n); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, c->d_stage, c->stage_cap, (size_t)(3 * wm.n))) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_unpack3, dim3(blocks_for(wm.n, 256)), dim3(256), 0, c->stream, wm.raw, wm.n, c->d_stage);
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_stage, sizeof(float) * (size_t)(3 * wm.n), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_stage.ensure(c, (size_t)(3 * wm.n))) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_unpack3, dim3(blocks_for(wm.n, 256)), dim3(256), 0, c->stream, wm.raw.data(), wm.n, c->d_stage.data());
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_stage.data(), sizeof(float) * (size_t)(3 * wm.n), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
@@ -960,7 +912,7 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (n <= 0) { c->fail("measure cloud is null or empty"); return DCREG_E_INVALID; }  // icp_test_runner.cpp:1635
     HIP_TRY(c, hipSetDevice(c->device));
     // packed and checked beside the current source (in the k-NN query buffer): a refused cloud leaves it as it was (dcreg_p2p_error reads it)
-    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, c->aligned_cap);
+    int rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned);
     if (rc) return rc;
     // Hilbert-curve order in the body frame (pose independent: a rigid motion keeps neighbours neighbours)
     double mn[3], mx[3];
@@ -968,17 +920,17 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (small_host) {
         host_bounds(xyz, n, stride, mn, mx);
     } else {
-        rc = device_bounds(c, c->d_aligned, n, mn, mx);
+        rc = device_bounds(c, c->d_aligned.data(), n, mn, mx);
         if (rc) return rc;
     }
     for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("source cloud has non-finite coordinates"); return DCREG_E_INVALID; }
     return source_commit(c, n, mn, mx, !small_host);
 }
 
-// the checked cloud of n points in c->d_aligned (packed as k_pack packs it), with bounds mn .. mx, becomes the source
+// the checked cloud of n points in c->d_aligned.data() (packed as k_pack packs it), with bounds mn .. mx, becomes the source
 static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const double mx[3], bool must_wait) {
     int rc;
-    std::swap(c->d_src_raw, c->d_aligned); std::swap(c->src_raw_cap, c->aligned_cap);
+    c->d_src_raw.swap(c->d_aligned);
     for (int a = 0; a < 3; ++a) { c->src_mn[a] = mn[a]; c->src_mx[a] = mx[a]; }
     double inv_q;
     int levels;
@@ -988,20 +940,20 @@ static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const doub
         for (int k = 0; k < 3; ++k) { const double m = std::max(std::fabs(mn[k]), std::fabs(mx[k])); r2 += m * m; }
         c->src_radius = std::sqrt(r2);
     }
-    if (ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
-        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n) ||
-        ensure(c, c->d_src, c->src_cap, (size_t)n))
+    if (c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
+        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) ||
+        c->d_src.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
     if (c->opt_keep_source_order) {      // experiments: the caller supplies the processing order
-        HIP_TRY(c, hipMemcpyAsync(c->d_src, c->d_src_raw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_src.data(), c->d_src_raw.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     } else {
         // the curve is resolved as far as the cloud can tell cells apart (curve_frame)
         // (round 6: ONE workgroup ordering a frame of <= 8192 points in LDS - keys, bitonic sort, gather, a single launch - was built and
         //  measured: 35 us of host time instead of 39, and 120 us of DEVICE time in front of the first linearisation instead of 15; removed)
-        hipLaunchKernelGGL(k_curve_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw, n, mn[0], mn[1], mn[2], inv_q, c->opt_curve_x_scale, c->d_mkeys, c->d_vals);
-        rc = sort_pairs_u64(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, 63 - 3 * levels);
+        hipLaunchKernelGGL(k_curve_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), n, mn[0], mn[1], mn[2], inv_q, c->opt_curve_x_scale, c->d_mkeys.data(), c->d_vals.data());
+        rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 63 - 3 * levels);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw, c->d_vals2, n, c->d_src);
+        hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), c->d_vals2.data(), n, c->d_src.data());
     }
     // A small frame from a host buffer went through the context's pinned block (upload_cloud): the caller's buffer is consumed, whatever
     // kind of memory it is, and nothing has to be waited for - the first linearisation queues behind the sort, and a device fault surfaces
@@ -1072,26 +1024,26 @@ static int frames_load(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int n_frames, cons
     HIP_TRY(c, hipSetDevice(c->device));
     fs.slice.clear(); fs.max_points = 0; fs.n_states = 0; fs.state_valid.clear();
     if (n > 0) {
-        if (ensure(c, fs.raw, fs.raw_cap, (size_t)n) || ensure(c, fs.src, fs.src_cap, (size_t)padded) || ensure(c, fs.d_off, fs.off_cap, (size_t)n_frames + 1) ||
-            ensure(c, fs.d_dst, fs.dst_cap, (size_t)n_frames) || ensure(c, fs.d_box, fs.box_cap, (size_t)n_frames) ||
-            ensure(c, c->d_stage, c->stage_cap, (size_t)(n * stride)) ||
-            ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
-            ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+        if (fs.raw.ensure(c, (size_t)n) || fs.src.ensure(c, (size_t)padded) || fs.d_off.ensure(c, (size_t)n_frames + 1) ||
+            fs.d_dst.ensure(c, (size_t)n_frames) || fs.d_box.ensure(c, (size_t)n_frames) ||
+            c->d_stage.ensure(c, (size_t)(n * stride)) ||
+            c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
+            c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
             return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage, xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(fs.d_off, off, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(fs.d_dst, dst.data(), sizeof(uint32_t) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(fs.d_box, box.data(), sizeof(FrameBox) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage, n, stride, fs.raw);
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_off.data(), off, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_dst.data(), dst.data(), sizeof(uint32_t) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fs.d_box.data(), box.data(), sizeof(FrameBox) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, fs.raw.data());
         const uint32_t *order = nullptr;
         if (fbits + max_bits > 0) {
-            hipLaunchKernelGGL(k_frame_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw, n, fs.d_off, n_frames, fs.d_box, fbits,
-                               c->opt_curve_x_scale, c->d_mkeys, c->d_vals);
-            const int rc = sort_pairs_u64(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, 63 - fbits - max_bits);
+            hipLaunchKernelGGL(k_frame_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), n, fs.d_off.data(), n_frames, fs.d_box.data(), fbits,
+                               c->opt_curve_x_scale, c->d_mkeys.data(), c->d_vals.data());
+            const int rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 63 - fbits - max_bits);
             if (rc) return rc;
-            order = c->d_vals2;
+            order = c->d_vals2.data();
         }
-        hipLaunchKernelGGL(k_frame_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw, order, n, fs.d_off, n_frames, fs.d_dst, fs.src);
+        hipLaunchKernelGGL(k_frame_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), order, n, fs.d_off.data(), n_frames, fs.d_dst.data(), fs.src.data());
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -1157,30 +1109,30 @@ static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairC
     int cbits = 1, jbits = 0;
     while (((int64_t)1 << cbits) < max_entries) ++cbits;
     while (((int64_t)1 << jbits) < (int64_t)n_j) ++jbits;
-    if (ensure(c, ps.d_off, ps.off_cap, offs.size()) || ensure(c, ps.d_cells, ps.cells_cap, (size_t)n_j) ||
-        ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
-        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+    if (ps.d_off.ensure(c, offs.size()) || ps.d_cells.ensure(c, (size_t)n_j) ||
+        c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
+        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
-    if (!occ && (ensure(c, ps.sorted, ps.sorted_cap, (size_t)pts) || ensure(c, ps.table, ps.table_cap, (size_t)to[n_j]) ||
-                 ensure(c, ps.ymask, ps.ymask_cap, (size_t)std::max<int64_t>(yo[n_j], 1))))
+    if (!occ && (ps.sorted.ensure(c, (size_t)pts) || ps.table.ensure(c, (size_t)to[n_j]) ||
+                 ps.ymask.ensure(c, (size_t)std::max<int64_t>(yo[n_j], 1))))
         return DCREG_E_NOMEM;
-    int64_t *d_po = ps.d_off, *d_to = d_po + (n_j + 1), *d_yo = d_to + (n_j + 1);
-    HIP_TRY(c, hipMemcpyAsync(ps.d_off, offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ps.d_cells, cells.data(), sizeof(PairCells) * (size_t)n_j, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw, n, d_po, n_j, ps.d_cells, cbits, c->d_mkeys, c->d_vals);
-    int rc = sort_pairs_u64(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, 0, cbits + jbits);
+    int64_t *d_po = ps.d_off.data(), *d_to = d_po + (n_j + 1), *d_yo = d_to + (n_j + 1);
+    HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ps.d_cells.data(), cells.data(), sizeof(PairCells) * (size_t)n_j, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw.data(), n, d_po, n_j, ps.d_cells.data(), cbits, c->d_mkeys.data(), c->d_vals.data());
+    int rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 0, cbits + jbits);
     if (rc) return rc;
     if (occ) {
-        HIP_TRY(c, hipMemsetAsync(ps.d_words, 0, sizeof(uint32_t) * (size_t)n_j, c->stream));
-        hipLaunchKernelGGL(k_pairs_occupancy, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_mkeys2, n, cbits, ps.d_words);
+        HIP_TRY(c, hipMemsetAsync(ps.d_words.data(), 0, sizeof(uint32_t) * (size_t)n_j, c->stream));
+        hipLaunchKernelGGL(k_pairs_occupancy, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), n, cbits, ps.d_words.data());
         occ->assign((size_t)n_j, 0u);
-        HIP_TRY(c, hipMemcpyAsync(occ->data(), ps.d_words, sizeof(uint32_t) * (size_t)n_j, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(occ->data(), ps.d_words.data(), sizeof(uint32_t) * (size_t)n_j, hipMemcpyDeviceToHost, c->stream));
     } else {
-        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw, c->d_vals2, n, d_po, n_j, ps.d_cells, ps.sorted);
-        hipLaunchKernelGGL(k_pairs_pad, dim3((unsigned)n_j), dim3(64), 0, c->stream, d_po, ps.d_cells, ps.sorted);
-        hipLaunchKernelGGL(k_pairs_table, dim3(blocks_for(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2, d_po, d_to, n_j, cbits, ps.table);
+        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw.data(), c->d_vals2.data(), n, d_po, n_j, ps.d_cells.data(), ps.sorted.data());
+        hipLaunchKernelGGL(k_pairs_pad, dim3((unsigned)n_j), dim3(64), 0, c->stream, d_po, ps.d_cells.data(), ps.sorted.data());
+        hipLaunchKernelGGL(k_pairs_table, dim3(blocks_for(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), d_po, d_to, n_j, cbits, ps.table.data());
         if (yo[n_j] > 0)
-            hipLaunchKernelGGL(k_pairs_ymask, dim3(blocks_for(yo[n_j], 256)), dim3(256), 0, c->stream, ps.table, d_to, d_yo, n_j, ps.d_cells, ps.ymask);
+            hipLaunchKernelGGL(k_pairs_ymask, dim3(blocks_for(yo[n_j], 256)), dim3(256), 0, c->stream, ps.table.data(), d_to, d_yo, n_j, ps.d_cells.data(), ps.ymask.data());
         tab_first->assign(to, to + n_j);
         yw_first->assign(yo, yo + n_j);
     }
@@ -1205,8 +1157,8 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("the pair targets of one build batch hold too many points (%lld)", (long long)n); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (ensure(c, ps.d_grids, ps.grids_cap, (size_t)std::max(n_t, 1)) || ensure(c, ps.d_words, ps.words_cap, (size_t)6 * std::max(n_t, 1)) ||
-        ensure(c, ps.d_off, ps.off_cap, (size_t)3 * (n_t + 1)))
+    if (ps.d_grids.ensure(c, (size_t)std::max(n_t, 1)) || ps.d_words.ensure(c, (size_t)6 * std::max(n_t, 1)) ||
+        ps.d_off.ensure(c, (size_t)3 * (n_t + 1)))
         return DCREG_E_NOMEM;
     std::vector<PairGrid> grids((size_t)n_t);
     std::memset(grids.data(), 0, sizeof(PairGrid) * (size_t)n_t);
@@ -1214,13 +1166,13 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     for (int t = 0; t < n_t; ++t) count[(size_t)t] = off[t + 1] - off[t];
     std::vector<uint32_t> words((size_t)6 * n_t);
     if (n > 0) {
-        if (ensure(c, ps.raw, ps.raw_cap, (size_t)n) || ensure(c, c->d_stage, c->stage_cap, (size_t)(n * stride))) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage, xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(ps.d_off, off, sizeof(int64_t) * (size_t)(n_t + 1), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(ps.d_words, 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
-        HIP_TRY(c, hipMemsetAsync(ps.d_words + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
-        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage, n, stride, ps.d_off, n_t, ps.raw, ps.d_words);
-        HIP_TRY(c, hipMemcpyAsync(words.data(), ps.d_words, sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
+        if (ps.raw.ensure(c, (size_t)n) || c->d_stage.ensure(c, (size_t)(n * stride))) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), off, sizeof(int64_t) * (size_t)(n_t + 1), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(ps.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+        HIP_TRY(c, hipMemsetAsync(ps.d_words.data() + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, ps.d_off.data(), n_t, ps.raw.data(), ps.d_words.data());
+        HIP_TRY(c, hipMemcpyAsync(words.data(), ps.d_words.data(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
     }
@@ -1316,17 +1268,17 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
             g.ox = q.ox; g.oy = q.oy; g.oz = q.oz;
             g.nx = q.nx; g.ny = q.ny; g.nz = q.nz; g.sx = q.sx;
             g.n_pts = (uint32_t)count[(size_t)t];
-            g.cell_start = ps.table + tab_first[j];
-            g.pts = ps.sorted + q.pts_first;
+            g.cell_start = ps.table.data() + tab_first[j];
+            g.pts = ps.sorted.data() + q.pts_first;
             g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
-            g.ymask = ps.ymask + yw_first[j]; g.nxb = q.nxb; g.nyw = q.nyw;
+            g.ymask = ps.ymask.data() + yw_first[j]; g.nxb = q.nxb; g.nyw = q.nyw;
             grids[(size_t)t].max_ring = rings_for(h, bound);
             grids[(size_t)t].infl_max_d2 = (float)(4.0 * h * h);
             ps.built[(size_t)t] = 1;
         }
     }
     if (n_t > 0) {
-        HIP_TRY(c, hipMemcpyAsync(ps.d_grids, grids.data(), sizeof(PairGrid) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ps.d_grids.data(), grids.data(), sizeof(PairGrid) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
     }
@@ -1356,8 +1308,8 @@ static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bo
     a.team_max = std::min(std::max(c->opt_team_max, 0), kTeamMax);
     a.far_loose = (float)c->opt_far_loose;
     a.prune_infl = (float)((1.0 + c->opt_cert_inflate) * (1.0 + c->opt_cert_inflate));
-    a.infl_max_d2 = own_grid ? (float)(4.0 * c->grid.h * c->grid.h) : 0.f;
-    a.max_ring = own_grid ? rings_for(c->grid.h, a.radius_sq_f) : 0;
+    a.infl_max_d2 = own_grid ? (float)(4.0 * c->map.grid.h * c->map.grid.h) : 0.f;
+    a.max_ring = own_grid ? rings_for(c->map.grid.h, a.radius_sq_f) : 0;
     if (own_grid) c->last_max_ring = a.max_ring;
     a.count_scale = c->n_src < ((int64_t)1 << 26) ? kCountScale : 0.0;      // (strictly below: a count of 2^26 would read as one more of the number riding above it)
     a.euler = p->parameterization != DCREG_PARAM_SO3 ? 1 : 0;
@@ -1369,12 +1321,12 @@ static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bo
         // - the shape of icp_test_runner.cpp:2323-2335 with its axis relabelling (pointOri = (p.y, p.z, p.x), coeff = (c.y, c.z, c.x)) undone for c
         // and kept for p, so that every product and every sum is taken in the order of the source text.  The 27 coefficients come from here.
         if (!c->h_euler) {
-            HIP_TRY(c, hipHostMalloc((void **)&c->h_euler, 27 * sizeof(double), hipHostMallocDefault));
-            HIP_TRY(c, hipMalloc((void **)&c->d_euler, 27 * sizeof(double)));
+            HIP_TRY(c, c->h_euler.alloc(27, hipHostMallocDefault));
+            HIP_TRY(c, c->d_euler.alloc(27));
         }
         // (the staging block is reused: the launches of the Euler engine are blocking calls, one at a time)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        double *D = c->h_euler;
+        double *D = c->h_euler.data();
         if (p->parameterization == DCREG_PARAM_EULER) {
             // the reference's row, literally (:2299-2346): srx / crx of PITCH, sry / cry of YAW, srz / crz of ROLL; the brackets of arx times coeff.z,
             // coeff.x, coeff.y (LOAM: x, y, z), of ary times coeff.z, coeff.y, of arz times coeff.z, coeff.x, coeff.y; matA row = [arz, arx, ary, ...]
@@ -1410,8 +1362,8 @@ static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bo
             };
             mul3(Rz, Ry, dRx, D); mul3(Rz, dRy, Rx, D + 9); mul3(dRz, Ry, Rx, D + 18);
         }
-        HIP_TRY(c, hipMemcpyAsync(c->d_euler, c->h_euler, 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        a.dR = c->d_euler;
+        HIP_TRY(c, hipMemcpyAsync(c->d_euler.data(), c->h_euler.data(), 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        a.dR = c->d_euler.data();
     }
     return DCREG_OK;
 }
@@ -1420,10 +1372,7 @@ static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bo
 // the pinned result rows, unpack).  Two slots with their own pose / partial / result buffers let a caller keep one batch
 // on the device while the host works on the other (dcreg_linearize_batch_begin / _end); the blocking entry points use
 // slot 0.  Debug dumps are synchronous and only exist on slot 0.
-static void free_tmp(LinSlot &S) {
-    for (void *p2 : S.tmp_dev) (void)hipFree(p2);
-    S.tmp_dev.clear();
-}
+static void free_tmp(LinSlot &S) { S.tmp_dev.clear(); }
 
 // after a launch that may not have run: what the states hold is unknown
 static void drop_warm(dcreg_ctx *c) {
@@ -1436,7 +1385,7 @@ static void drop_warm(dcreg_ctx *c) {
 static void gate_publish(dcreg_ctx *c, unsigned long long seq_word, const double *R, const double *t) {
     unsigned long long w[kGateWords];
     w[0] = seq_word;
-    for (int k = 1; k < kGateWords - 1; ++k) w[k] = c->h_gate->w[k];
+    for (int k = 1; k < kGateWords - 1; ++k) w[k] = c->h_gate.data()->w[k];
     if (R) {
         std::memcpy(&w[1], R, 9 * sizeof(double));
         std::memcpy(&w[10], t, 3 * sizeof(double));
@@ -1444,24 +1393,24 @@ static void gate_publish(dcreg_ctx *c, unsigned long long seq_word, const double
     unsigned long long x = kGateSalt;
     for (int k = 0; k < kGateWords - 1; ++k) x ^= w[k];
     w[kGateWords - 1] = x;
-    volatile unsigned long long *dst = c->h_gate->w;
+    volatile unsigned long long *dst = c->h_gate.data()->w;
     for (int k = 1; k < kGateWords; ++k) dst[k] = w[k];
-    __atomic_store_n(&c->h_gate->w[0], w[0], __ATOMIC_RELEASE);
+    __atomic_store_n(&c->h_gate.data()->w[0], w[0], __ATOMIC_RELEASE);
 }
 static void gate_call_off(dcreg_ctx *c) { gate_publish(c, (c->gate_seq << 1) | 1ull, nullptr, nullptr); }
 
 // dispatch order of the query-block groups (kernels.hpp k_group_cost): estimated cost of every group at this pose, heaviest first
 static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double *t3, int max_ring) {
-    if (!c->d_group_est) { HIP_TRY(c, hipMalloc((void **)&c->d_group_est, sizeof(float) * kMaxGroups)); }
+    if (!c->d_group_est) HIP_TRY(c, c->d_group_est.alloc(kMaxGroups));
     PoseArg P{};
     for (int k = 0; k < 9; ++k) P.R[k] = R9[k];
     for (int k = 0; k < 3; ++k) P.t[k] = t3[k];
     const uint32_t ng = c->n_groups;
     const uint32_t lead = (blocks_for(c->n_src, kLinBlock) - ng * c->group_blocks) * (uint32_t)kLinBlock;      // points in front of the first group
-    hipLaunchKernelGGL(k_group_cost, dim3(ng), dim3(256), 0, c->stream, c->d_src + lead, (uint32_t)c->n_src - lead, c->grid, P, c->group_blocks * (uint32_t)kLinBlock,
-                       max_ring, c->d_group_est);
+    hipLaunchKernelGGL(k_group_cost, dim3(ng), dim3(256), 0, c->stream, c->d_src.data() + lead, (uint32_t)c->n_src - lead, c->map.grid, P, c->group_blocks * (uint32_t)kLinBlock,
+                       max_ring, c->d_group_est.data());
     float est[kMaxGroups];
-    HIP_TRY(c, hipMemcpyAsync(est, c->d_group_est, sizeof(float) * ng, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(est, c->d_group_est.data(), sizeof(float) * ng, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     uint32_t order[kMaxGroups];
     for (uint32_t k = 0; k < (uint32_t)kMaxGroups; ++k) order[k] = k;
@@ -1508,7 +1457,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (S.pending) { c->fail("slot %d still has a linearisation in flight", slot); return DCREG_E_STATE; }
     if (!R9 || !t3 || n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
     if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
-    if (!grid_ids && c->n_tgt <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
+    if (!grid_ids && c->map.n <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
     dcreg_ctx::FrameSet &fs = grid_ids ? c->pair_src : c->frames;
     int64_t n_frame_max = 0;             // frames: points of the largest frame of this launch
     if (grid_ids) {
@@ -1548,7 +1497,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     key.radius_sq = a.radius_sq; key.max_thick_sq = a.max_thick_sq; key.min_norm = a.min_norm;
     key.radius_sq_f = a.radius_sq_f; key.cert_r_out = a.cert_r_out; key.cert_r_in = a.cert_r_in; key.fast_plane = c->opt_fast_plane ? 1 : 0;
     const uint32_t nbx = blocks_for(frame_ids ? n_frame_max : c->n_src, kLinBlock);
-    if (ensure(c, S.d_partials, S.partials_cap, (size_t)n_poses * nbx * kSlots)) return DCREG_E_NOMEM;
+    if (S.d_partials.ensure(c, (size_t)n_poses * nbx * kSlots)) return DCREG_E_NOMEM;
     // one pose: the kernels finish the reduction themselves (chunk rows -> pinned memory); many poses: k_finalize
     const uint32_t n_chunks = (nbx + kChunk - 1) / kChunk;
     // ... and so do batches whose poses are one chunk each (the Monte-Carlo batches: 30 blocks per pose): the last block of a pose sums
@@ -1558,25 +1507,21 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     const bool direct = fused && n_poses == 1 && nbx <= (uint32_t)kChunk && c->opt_direct_rows && c->opt_one_wave < 2;     // (one_wave = 2: tile rows even there - tests)
     const size_t n_rows = direct ? (size_t)nbx : (fused ? (size_t)n_chunks * (size_t)n_poses : (size_t)n_poses);      // result rows the host waits for
     if (fused) {   // tickets: zero when (re)allocated, afterwards every completed launch leaves them zero
-        const size_t had = S.tickets_cap;
-        if (ensure(c, S.d_tickets, S.tickets_cap, (size_t)n_chunks * (size_t)n_poses * kCounterStride)) return DCREG_E_NOMEM;
-        if (S.tickets_cap != had || S.tickets_dirty) {
-            HIP_TRY(c, hipMemsetAsync(S.d_tickets, 0, sizeof(unsigned int) * S.tickets_cap, c->stream));
+        const size_t had = S.d_tickets.cap();
+        if (S.d_tickets.ensure(c, (size_t)n_chunks * (size_t)n_poses * kCounterStride)) return DCREG_E_NOMEM;
+        if (S.d_tickets.cap() != had || S.tickets_dirty) {
+            HIP_TRY(c, hipMemsetAsync(S.d_tickets.data(), 0, sizeof(unsigned int) * S.d_tickets.cap(), c->stream));
             S.tickets_dirty = false;
         }
     }
-    if (n_rows > S.out_cap) {
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        S.h_out = nullptr; S.out_cap = 0;
-        const size_t cap = std::max<size_t>(n_rows, 64);
-        HIP_TRY(c, hipHostMalloc((void **)&S.h_out, cap * kSlots * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(S.h_out, 0, cap * kSlots * sizeof(double));
+    if (n_rows * kSlots > S.h_out.cap()) {
+        const size_t cap = std::max<size_t>(n_rows, 64) * kSlots;
+        HIP_TRY(c, S.h_out.alloc(cap, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(S.h_out.data(), 0, cap * sizeof(double));
         std::fill(S.row_chk.begin(), S.row_chk.end(), 0ull);
-        HIP_TRY(c, hipHostGetDevicePointer((void **)&S.d_out, S.h_out, 0));
-        S.out_cap = cap;
     }
     const int64_t n = frame_ids ? n_frame_max : c->n_src;
-    const float4 *const d_src = frame_ids ? fs.src : c->d_src;
+    const float4 *const d_src = frame_ids ? fs.src.data() : c->d_src.data();
     a.state = nullptr; a.state_stride = 0;
     a.xcd_chunk = (uint32_t)std::max(c->opt_xcd_chunk, 0);
     if (n_poses == 1 && !state_ids && !gated) {
@@ -1588,11 +1533,11 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             for (int k = 0; k < 3; ++k) dt += (t3[k] - c->last_t[k]) * (t3[k] - c->last_t[k]);
             jump = std::sqrt(dr) * c->src_radius + std::sqrt(dt);
         }
-        if (c->hint_unknown && jump <= 0.5 * c->grid.h) c->hint_misalign = c->hint_last;      // the same trajectory, continued
+        if (c->hint_unknown && jump <= 0.5 * c->map.grid.h) c->hint_misalign = c->hint_last;      // the same trajectory, continued
         // ... and what the last completed launch searched says nothing about a launch half a cell or more away from it (the first
         // launch of a new run): expect a search of everything - for this launch and for the one that may be queued behind it before
         // its counts are known (scheduling only: which kernels carry the launch out)
-        if (jump > 0.5 * c->grid.h) { c->last_searched = n_poses * c->n_src; c->last_points = c->last_searched; }
+        if (jump > 0.5 * c->map.grid.h) { c->last_searched = n_poses * c->n_src; c->last_points = c->last_searched; }
         c->hint_unknown = false;
         std::memcpy(c->last_R, R9, sizeof(c->last_R)); std::memcpy(c->last_t, t3, sizeof(c->last_t));
         c->last_pose_valid = true;
@@ -1601,7 +1546,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         // know its pose yet: it uses the order there is)
         // (a launch whose blocks are all resident at once - 4 per CU - has no order to speak of)
         const bool wanted = c->opt_dispatch_order && n_poses == 1 && !state_ids && c->n_groups >= 2 && nbx > 4u * (uint32_t)c->n_cus &&
-                            c->hint_misalign > 0.5 * c->grid.h;
+                            c->hint_misalign > 0.5 * c->map.grid.h;
         if (wanted && !gated) {
             // the estimate holds for poses near the one it was made at (within a cell for every point)
             bool stale = !c->order_valid;
@@ -1613,7 +1558,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
                 double dr = 0.0, dt = 0.0;
                 for (int k = 0; k < 9; ++k) dr += (R9[k] - c->est_R[k]) * (R9[k] - c->est_R[k]);
                 for (int k = 0; k < 3; ++k) dt += (t3[k] - c->est_t[k]) * (t3[k] - c->est_t[k]);
-                stale = std::sqrt(dr) * c->src_radius + std::sqrt(dt) > c->grid.h;
+                stale = std::sqrt(dr) * c->src_radius + std::sqrt(dt) > c->map.grid.h;
             }
             if (stale) {
                 rc = estimate_dispatch_order(c, R9, t3, a.max_ring);
@@ -1637,36 +1582,33 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         if (c->opt_warm) {      // single pose: the ctx's own state
             const size_t stride = ((size_t)n + 63) & ~(size_t)63;
             if (!c->state_valid || c->state_stride != stride) {
-                if (ensure(c, c->d_state, c->state_cap, kStateRows * stride)) return DCREG_E_NOMEM;
+                if (c->d_state.ensure(c, kStateRows * stride)) return DCREG_E_NOMEM;
                 c->state_stride = stride; c->state_valid = false;
             }
             uses_state = true;
             one.state = 0; one.fresh = c->state_valid ? 0u : 1u;
-            a.state = c->d_state; a.state_stride = (uint32_t)c->state_stride;
+            a.state = c->d_state.data(); a.state_stride = (uint32_t)c->state_stride;
         }
         if (gated) {
             if (!c->h_gate) {     // all or nothing: a half-built gate would be taken for a whole one by the next call
-                GateHost *hg = nullptr; PoseArg *dp = nullptr; uint32_t *da = nullptr; GateDev *gd = nullptr;
-                bool ok = hipHostMalloc((void **)&hg, sizeof(GateHost), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-                ok = ok && hipMalloc((void **)&dp, sizeof(PoseArg)) == hipSuccess && hipMalloc((void **)&da, sizeof(uint32_t)) == hipSuccess;
+                PinnedBuf<GateHost> hg;
+                DevBuf<PoseArg> dp;
+                DevBuf<uint32_t> da;
+                DevBuf<GateDev> gd;
+                bool ok = hg.alloc(1, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+                ok = ok && dp.alloc(1) == hipSuccess && da.alloc(1) == hipSuccess;
                 // (the device copy of the record, for launches gated in their first kernel: cleared IN THE STREAM - the ctx stream does not
                 //  synchronise with the null stream)
-                ok = ok && hipMalloc((void **)&gd, sizeof(GateDev)) == hipSuccess && hipMemsetAsync(gd, 0, sizeof(GateDev), c->stream) == hipSuccess;
-                void *dgh = nullptr;
-                ok = ok && hipHostGetDevicePointer(&dgh, hg, 0) == hipSuccess;
+                ok = ok && gd.alloc(1) == hipSuccess && hipMemsetAsync(gd.data(), 0, sizeof(GateDev), c->stream) == hipSuccess;
                 if (!ok) {
-                    if (hg) (void)hipHostFree(hg);
-                    if (dp) (void)hipFree(dp);
-                    if (da) (void)hipFree(da);
-                    if (gd) (void)hipFree(gd);
                     c->state_valid = state_was_valid;
                     c->fail("allocating the launch gate failed");
                     return DCREG_E_NOMEM;
                 }
-                std::memset(hg, 0, sizeof(GateHost));
-                c->h_gate = hg; c->d_gate_host = (GateHost *)dgh; c->d_gate_pose = dp; c->d_gate_abort = da; c->d_gate_dev = gd;
+                std::memset(hg.data(), 0, sizeof(GateHost));
+                c->h_gate = std::move(hg); c->d_gate_pose = std::move(dp); c->d_gate_abort = std::move(da); c->d_gate_dev = std::move(gd);
             }
-            d_poses = c->d_gate_pose;
+            d_poses = c->d_gate_pose.data();
         }
     } else {
         // batched poses: each may own one of the reserved states (dcreg_reserve_warm_states; frames: dcreg_frames_reserve_states);
@@ -1692,16 +1634,13 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         // (frames: the poses' slices ride behind the poses in the same block - one copy; pairs: and their target ids behind those)
         const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (frame_ids ? (size_t)n_poses * sizeof(uint2) : 0) +
                              (grid_ids ? (size_t)n_poses * sizeof(uint32_t) : 0);
-        if (bytes > S.poses_cap) {      // the pinned block stays alive until end(): source of the asynchronous copy
-            if (S.h_poses) (void)hipHostFree(S.h_poses);
-            if (S.d_poses) (void)hipFree(S.d_poses);
-            S.h_poses = nullptr; S.d_poses = nullptr; S.poses_cap = 0;
+        if (bytes > S.d_poses.cap()) {      // the pinned block stays alive until end(): source of the asynchronous copy
+            S.h_poses.reset(); S.d_poses.reset();
             const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2) + sizeof(uint32_t)));
-            HIP_TRY(c, hipHostMalloc((void **)&S.h_poses, cap, hipHostMallocDefault));
-            if (hipMalloc((void **)&S.d_poses, cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
-            S.poses_cap = cap;
+            HIP_TRY(c, S.h_poses.alloc(cap, hipHostMallocDefault));
+            if (S.d_poses.alloc(cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
         }
-        PoseArg *hp = (PoseArg *)S.h_poses;
+        PoseArg *hp = (PoseArg *)S.h_poses.data();
         for (int i = 0; i < n_poses; ++i) {
             std::memcpy(hp[i].R, R9 + 9 * i, sizeof(one.R)); std::memcpy(hp[i].t, t3 + 3 * i, sizeof(one.t));
             const bool has = use_states && state_ids[i] >= 0;
@@ -1710,25 +1649,25 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             if (has) state_valid[(size_t)state_ids[i]] = 1;
         }
         if (frame_ids) {
-            uint2 *hs = (uint2 *)(S.h_poses + (size_t)n_poses * sizeof(PoseArg));
+            uint2 *hs = (uint2 *)(S.h_poses.data() + (size_t)n_poses * sizeof(PoseArg));
             for (int i = 0; i < n_poses; ++i) hs[i] = fs.slice[(size_t)frame_ids[i]];
-            d_slices = (const uint2 *)(S.d_poses + (size_t)n_poses * sizeof(PoseArg));
+            d_slices = (const uint2 *)(S.d_poses.data() + (size_t)n_poses * sizeof(PoseArg));
         }
         if (grid_ids) {
             const size_t at = (size_t)n_poses * (sizeof(PoseArg) + sizeof(uint2));
-            std::memcpy(S.h_poses + at, grid_ids, sizeof(uint32_t) * (size_t)n_poses);
-            d_grid_ids = (const uint32_t *)(S.d_poses + at);
+            std::memcpy(S.h_poses.data() + at, grid_ids, sizeof(uint32_t) * (size_t)n_poses);
+            d_grid_ids = (const uint32_t *)(S.d_poses.data() + at);
         }
         // (measured and dropped, profiles/r05_ablation.md: the upload on a copy stream behind an event - the cross-stream dependency costs
         //  more than the 4.6 us copy it hides, C5 1.56 M against 1.64 M it/s - and no upload at all, the kernel reading the pinned block:
         //  +2.7 us per kernel, nothing gained - the experiment is bound by its kernels, two groups of trials alternating on the device)
-        HIP_TRY(c, hipMemcpyAsync(S.d_poses, S.h_poses, bytes, hipMemcpyHostToDevice, c->stream));
-        d_poses = (const PoseArg *)S.d_poses;
-        if (use_states && frame_ids) { a.state = fs.state; a.state_stride = (uint32_t)fs.state_stride; }
-        else if (use_states) { a.state = c->d_state_batch; a.state_stride = (uint32_t)c->state_batch_stride; }
+        HIP_TRY(c, hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        d_poses = (const PoseArg *)S.d_poses.data();
+        if (use_states && frame_ids) { a.state = fs.state.data(); a.state_stride = (uint32_t)fs.state_stride; }
+        else if (use_states) { a.state = c->d_state_batch.data(); a.state_stride = (uint32_t)c->state_batch_stride; }
     }
     a.use_cert = ((dbg_host && !stamps_only) || !c->opt_use_cert) ? 0 : 1;   // a debug dump searches every point (its statistics are those of the searches)
-    a.search_count = c->opt_count_searches ? c->d_search_count : nullptr;
+    a.search_count = c->opt_count_searches ? c->d_search_count.data() : nullptr;
     // The advance pass (kernels.hpp k_advance) in front of this launch?  Only where it can pay: a single pose on the ctx's own state,
     // certificates in use, the state filled by an earlier launch; by default ("advance" = 1) a cloud whose query blocks exceed what the
     // device holds at once (below that a launch lasts as long as one search whether its searches are dense or not) in a launch expected
@@ -1747,7 +1686,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         // ... and only against a map whose occupied cells hold several points each: there a query with a loose bound (an OUT point, a
         // jump) has a hundred and more candidates in its 27-cell block and the lock-step search, two trips in flight, is at its slowest;
         // against a sparse map (the 7.5 k-point fixture: 1.6 points per occupied cell) it is as fast as the teams
-        const double per_cell = (double)c->n_tgt / (double)std::max<uint32_t>(c->occupied_cells, 1u);
+        const double per_cell = (double)c->map.n / (double)std::max<uint32_t>(c->map.occupied, 1u);
         team = c->opt_team_pass >= 2 || (c->opt_team_pass == 1 && n <= (int64_t)c->opt_team_pass_max_points && known && f >= c->opt_team_pass_min_frac &&
                                          per_cell >= c->opt_team_pass_min_cell_pts);
     }
@@ -1763,37 +1702,37 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         const bool known = c->last_searched >= 0 && c->last_points == n;
         const bool most = !uses_state || one.fresh != 0u || !a.use_cert || (known && (double)c->last_searched >= c->opt_one_wave_min_frac * (double)n);
         one_wave = c->opt_one_wave >= 2 || (c->opt_one_wave == 1 && nbx >= (uint32_t)c->opt_one_wave_min_blocks && !adv && most &&
-                                            c->hint_misalign > c->opt_one_wave_min_cells * c->grid.h);
+                                            c->hint_misalign > c->opt_one_wave_min_cells * c->map.grid.h);
     }
     // (a row per TILE then: grown here, before any kernel of this launch is queued)
-    if (one_wave && ensure(c, S.d_partials, S.partials_cap, (size_t)n_poses * nbx * kSlots * (kLinBlock / kWave))) return DCREG_E_NOMEM;
+    if (one_wave && S.d_partials.ensure(c, (size_t)n_poses * nbx * kSlots * (kLinBlock / kWave))) return DCREG_E_NOMEM;
     const uint32_t n_tiles = team ? blocks_for(n, kTeamTile) : blocks_for(n, kAdvTile);
     if (adv || team) {      // the passes' counts, per query block of k_lin: zero between launches (k_lin takes them and zeroes them again)
-        const size_t had = c->adv_counts_cap;
-        if (ensure(c, c->d_adv_counts, c->adv_counts_cap, (size_t)kCounterStride * nbx)) return DCREG_E_NOMEM;      // (a 128-byte line per query block)
-        if (c->adv_counts_cap != had || c->adv_counts_dirty) {
-            HIP_TRY(c, hipMemsetAsync(c->d_adv_counts, 0, sizeof(uint32_t) * c->adv_counts_cap, c->stream));
+        const size_t had = c->d_adv_counts.cap();
+        if (c->d_adv_counts.ensure(c, (size_t)kCounterStride * nbx)) return DCREG_E_NOMEM;      // (a 128-byte line per query block)
+        if (c->d_adv_counts.cap() != had || c->adv_counts_dirty) {
+            HIP_TRY(c, hipMemsetAsync(c->d_adv_counts.data(), 0, sizeof(uint32_t) * c->d_adv_counts.cap(), c->stream));
             c->adv_counts_dirty = false;
         }
-        a.adv_counts = c->d_adv_counts;
+        a.adv_counts = c->d_adv_counts.data();
     }
     unsigned long long *team_stamps = nullptr;
     if (team && c->opt_team_stamps) {          // timing probe (dcreg_debug.h dcreg_team_pass_stamps): eight clock words per block of the pass.  Grown HERE,
         // before any kernel of this launch is queued: a hipFree behind a gate kernel that waits for the host would wait for it
-        if (ensure(c, c->d_team_stamps, c->team_stamps_cap, (size_t)8 * (n_tiles + 1))) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemsetAsync(c->d_team_stamps, 0, sizeof(unsigned long long) * 8 * (n_tiles + 1), c->stream));
-        team_stamps = c->d_team_stamps; c->team_stamps_n = n_tiles;
+        if (c->d_team_stamps.ensure(c, (size_t)8 * (n_tiles + 1))) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemsetAsync(c->d_team_stamps.data(), 0, sizeof(unsigned long long) * 8 * (n_tiles + 1), c->stream));
+        team_stamps = c->d_team_stamps.data(); c->team_stamps_n = n_tiles;
     }
     DebugDev dd{};
     free_tmp(S);
     if (dbg_host) {
         bool oom = false;
         auto alloc = [&](size_t bytes, int fill) -> void * {
-            void *p2 = nullptr;
-            if (hipMalloc(&p2, bytes) != hipSuccess) { oom = true; return nullptr; }
-            (void)hipMemsetAsync(p2, fill, bytes, c->stream);
-            S.tmp_dev.push_back(p2);
-            return p2;
+            DevBuf<unsigned char> b;
+            if (b.alloc(bytes) != hipSuccess) { oom = true; return nullptr; }
+            (void)hipMemsetAsync(b.data(), fill, bytes, c->stream);
+            S.tmp_dev.push_back(std::move(b));
+            return S.tmp_dev.back().data();
         };
         if (dbg_host->nn_idx) dd.nn_idx = (int32_t *)alloc(sizeof(int32_t) * 5 * n, 0xFF);
         if (dbg_host->nn_d2) dd.nn_d2 = (float *)alloc(sizeof(float) * 5 * n, 0);
@@ -1806,7 +1745,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         if (oom) { free_tmp(S); drop_warm(c); c->fail("hipMalloc of the debug dump buffers failed"); return DCREG_E_NOMEM; }
     }
     const unsigned long long seq = ++c->seq;
-    FinArgs fin{S.d_tickets, S.d_out, seq, direct ? 1u : 0u, n_chunks};
+    FinArgs fin{S.d_tickets.data(), S.h_out.dev(), seq, direct ? 1u : 0u, n_chunks};
     if (fused) S.tickets_dirty = true;    // cleared again once this launch is known to have completed
     // kernel timing: HIP events around every opt_time_kernels-th linearisation (each timed launch costs ~10 us of host time)
     bool timed = c->opt_time_kernels > 0 && (c->launch_counter++ % (uint64_t)c->opt_time_kernels) == 0;
@@ -1834,12 +1773,12 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (gated) {
         const unsigned long long want = ++c->gate_seq;
         if (gate_inside) {
-            gt = GateArgs{c->d_gate_host, c->d_gate_dev, want, team ? c->d_gate_pose : nullptr, team ? c->d_gate_abort : nullptr, one.fresh};
-            if (team) abort_flag = c->d_gate_abort;        // (k_lin behind the teams reads what their polling wave left, as behind k_gate)
+            gt = GateArgs{c->h_gate.dev(), c->d_gate_dev.data(), want, team ? c->d_gate_pose.data() : nullptr, team ? c->d_gate_abort.data() : nullptr, one.fresh};
+            if (team) abort_flag = c->d_gate_abort.data();        // (k_lin behind the teams reads what their polling wave left, as behind k_gate)
             else lin_poses = nullptr;                      // (k_lin itself is the gated kernel: pose1 carries state / fresh)
         } else {
-            hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, c->d_gate_host, want, c->d_gate_pose, one.fresh, c->d_gate_abort);
-            abort_flag = c->d_gate_abort;
+            hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, c->h_gate.dev(), want, c->d_gate_pose.data(), one.fresh, c->d_gate_abort.data());
+            abort_flag = c->d_gate_abort.data();
         }
     }
     if (timed) {                           // after the gate: the events bracket the linearisation, not the wait for the pose
@@ -1848,8 +1787,8 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     }
     const bool fast = c->opt_fast_plane;
     if (adv) {
-        if (fast) hipLaunchKernelGGL((k_advance<true>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, d_poses, a, c->d_adv_counts, abort_flag);
-        else hipLaunchKernelGGL((k_advance<false>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, d_poses, a, c->d_adv_counts, abort_flag);
+        if (fast) hipLaunchKernelGGL((k_advance<true>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag);
+        else hipLaunchKernelGGL((k_advance<false>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag);
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) return bail("advance pass launch", le);
         c->n_advance_launches += 1;
@@ -1857,11 +1796,11 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (team) {
         unsigned long long *stamps = team_stamps;
         if (gate_inside) {      // the teams are the gated kernel
-            if (fast) hipLaunchKernelGGL((k_advance_team<true, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts, (const uint32_t *)nullptr, stamps, gt);
-            else hipLaunchKernelGGL((k_advance_team<false, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts, (const uint32_t *)nullptr, stamps, gt);
+            if (fast) hipLaunchKernelGGL((k_advance_team<true, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts.data(), (const uint32_t *)nullptr, stamps, gt);
+            else hipLaunchKernelGGL((k_advance_team<false, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts.data(), (const uint32_t *)nullptr, stamps, gt);
         } else {
-            if (fast) hipLaunchKernelGGL((k_advance_team<true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, d_poses, a, c->d_adv_counts, abort_flag, stamps, gt);
-            else hipLaunchKernelGGL((k_advance_team<false>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, d_poses, a, c->d_adv_counts, abort_flag, stamps, gt);
+            if (fast) hipLaunchKernelGGL((k_advance_team<true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag, stamps, gt);
+            else hipLaunchKernelGGL((k_advance_team<false>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag, stamps, gt);
         }
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) return bail("team advance pass launch", le);
@@ -1870,20 +1809,20 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     {
         const dim3 grid(nbx, (unsigned)n_poses);
 #define DCREG_LAUNCH_LIN(MODE, FUSED, FAST)                                                                                              \
-    hipLaunchKernelGGL((k_lin<MODE, FUSED, FAST>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a,  \
-                       S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr)
+    hipLaunchKernelGGL((k_lin<MODE, FUSED, FAST>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a,  \
+                       S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr)
 #define DCREG_LAUNCH_FRAMES(FUSED, FAST, ONE_)                                                                                           \
     hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid,       \
-                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, \
+                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, \
                        abort_flag, gt, d_slices, nullptr, nullptr)
 #define DCREG_LAUNCH_PAIRS(FUSED, FAST, ONE_)                                                                                            \
     hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid, \
-                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, \
-                       abort_flag, gt, d_slices, c->pairs.d_grids, d_grid_ids)
+                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, \
+                       abort_flag, gt, d_slices, c->pairs.d_grids.data(), d_grid_ids)
         if (grid_ids) {                    // the scan pairs of dcreg_register_pairs: every pose reads its own slice and its own target grid
             if (one_wave) {
                 if (fast) DCREG_LAUNCH_PAIRS(true, true, true); else DCREG_LAUNCH_PAIRS(true, false, true);
-                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, d_slices);
+                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, d_slices);
             }
             else if (fused) { if (fast) DCREG_LAUNCH_PAIRS(true, true, false); else DCREG_LAUNCH_PAIRS(true, false, false); }
             else { if (fast) DCREG_LAUNCH_PAIRS(false, true, false); else DCREG_LAUNCH_PAIRS(false, false, false); }
@@ -1891,22 +1830,22 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         if (frame_ids) {                   // the frames of dcreg_register_frames: every pose reads its own slice
             if (one_wave) {
                 if (fast) DCREG_LAUNCH_FRAMES(true, true, true); else DCREG_LAUNCH_FRAMES(true, false, true);
-                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, d_slices);
+                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, d_slices);
             }
             else if (fused) { if (fast) DCREG_LAUNCH_FRAMES(true, true, false); else DCREG_LAUNCH_FRAMES(true, false, false); }
             else { if (fast) DCREG_LAUNCH_FRAMES(false, true, false); else DCREG_LAUNCH_FRAMES(false, false, false); }
         } else
         if (gate_inside && !team) {        // k_lin is the gated kernel (fused, MODE 0: a gated launch is never a dump)
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
         } else
         if (stamps_only) { if (fast) DCREG_LAUNCH_LIN(2, true, true); else DCREG_LAUNCH_LIN(2, true, false); }     // (the probe writes the shared state: same fit as the plain launches)
         else if (dbg_host) { if (fast) DCREG_LAUNCH_LIN(1, true, true); else DCREG_LAUNCH_LIN(1, true, false); }
         else if (one_wave) {               // one-wave blocks: a grid of tiles
             const dim3 tiles(nbx * (kLinBlock / kWave), (unsigned)n_poses);
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src, (uint32_t)n, c->grid, one, lin_poses, a, S.d_partials, nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            hipLaunchKernelGGL(k_sum_tiles<false>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, abort_flag, nullptr);
+            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
+            hipLaunchKernelGGL(k_sum_tiles<false>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, nullptr);
         }
         else if (fused) { if (fast) DCREG_LAUNCH_LIN(0, true, true); else DCREG_LAUNCH_LIN(0, true, false); }
         else { if (fast) DCREG_LAUNCH_LIN(0, false, true); else DCREG_LAUNCH_LIN(0, false, false); }
@@ -1919,8 +1858,8 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
         if (le != hipSuccess) return bail("linearisation kernel launch", le);
     }
     if (!fused) {
-        if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, d_slices);
-        else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials, nbx, S.d_out, seq, (const uint2 *)nullptr);
+        if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, d_slices);
+        else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, (const uint2 *)nullptr);
         const hipError_t le = hipGetLastError();
         if (le != hipSuccess) return bail("k_finalize launch", le);
     }
@@ -1975,7 +1914,7 @@ static int wait_rows(dcreg_ctx *c, LinSlot &S) {
     auto arrived = [&](size_t i) {
         unsigned long long v[kSlots];
         asm volatile("" ::: "memory");
-        std::memcpy(v, (const void *)(S.h_out + i * kSlots), sizeof(v));
+        std::memcpy(v, (const void *)(S.h_out.data() + i * kSlots), sizeof(v));
         unsigned long long c0 = S.seq * mults.m[31], c1 = 0, c2 = 0, c3 = 0;
         for (int k = 0; k < 28; k += 4) { c0 += v[k] * mults.m[k]; c1 += v[k + 1] * mults.m[k + 1]; c2 += v[k + 2] * mults.m[k + 2]; c3 += v[k + 3] * mults.m[k + 3]; }
         c0 += v[28] * mults.m[28]; c1 += v[29] * mults.m[29]; c2 += v[30] * mults.m[30];
@@ -1987,7 +1926,7 @@ static int wait_rows(dcreg_ctx *c, LinSlot &S) {
     // (cheap look first: a row whose check word is still the one taken last time has not been written again - the word carries the
     // launch number)
     auto touched = [&](size_t i) {
-        return __atomic_load_n((const unsigned long long *)(S.h_out + i * kSlots) + 31, __ATOMIC_RELAXED) != S.row_chk[i];
+        return __atomic_load_n((const unsigned long long *)(S.h_out.data() + i * kSlots) + 31, __ATOMIC_RELAXED) != S.row_chk[i];
     };
     S.h_rows.resize(S.n_rows * kSlots);
     // rows are taken in the order they arrive (the last one to come is then the only one left to check), not in index order
@@ -2183,7 +2122,7 @@ int dcreg_backend_create(dcreg_ctx **out, int device) {
     }
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
-        hipMalloc((void **)&c->d_scratch, 256) != hipSuccess) {
+        c->d_scratch.alloc(256 / sizeof(uint32_t)) != hipSuccess) {
         delete c;
         return DCREG_E_DEVICE;
     }
@@ -2200,39 +2139,16 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)dcreg_linearize_gate_abort(c);
     (void)hipStreamSynchronize(c->stream);
-    if (c->h_gate) (void)hipHostFree(c->h_gate);
-    if (c->h_euler) (void)hipHostFree(c->h_euler);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_stage_ev) (void)hipEventDestroy(c->h_stage_ev);
     if (c->null_ev) (void)hipEventDestroy(c->null_ev);
-    if (c->d_euler) (void)hipFree(c->d_euler);
-    if (c->d_gate_pose) (void)hipFree(c->d_gate_pose);
-    if (c->d_gate_abort) (void)hipFree(c->d_gate_abort);
-    if (c->d_gate_dev) (void)hipFree(c->d_gate_dev);
-    if (c->d_group_est) (void)hipFree(c->d_group_est);
     kdtree_free(c->kd); c->kd = nullptr;
-    void *bufs[] = {c->d_tgt_raw, c->d_tgt, c->d_src_raw, c->d_src, c->d_stage, c->d_keys, c->d_keys2, c->d_vals, c->d_vals2,
-                    c->d_mkeys, c->d_mkeys2, c->d_cell_start, c->d_scratch, c->sort_tmp,
-                    c->d_nn_idx, c->d_nn_d2, c->d_p2p_part, c->d_aligned, c->d_aux, c->d_aux_cell_start, c->d_state, c->d_state_batch, c->d_search_count, c->d_gap, c->d_ymask, c->d_owner,
-                    c->d_adv_counts, c->d_team_stamps, c->roi_store.raw, c->roi_store.sorted, c->roi_store.cell_start, c->roi_store.gap,
-                    c->roi_store.owner, c->roi_store.ymask, c->frames.raw, c->frames.src, c->frames.d_off, c->frames.d_dst, c->frames.d_box,
-                    c->frames.state, c->pair_src.raw, c->pair_src.src, c->pair_src.d_off, c->pair_src.d_dst, c->pair_src.d_box, c->pair_src.state,
-                    c->pairs.raw, c->pairs.sorted, c->pairs.table, c->pairs.ymask, c->pairs.d_off, c->pairs.d_cells, c->pairs.d_words, c->pairs.d_grids,
-                    c->d_tgt_alt, c->d_tgt_raw_alt, c->d_cell_alt, c->d_map_q, c->d_map_new, c->d_upd, c->d_fgap, c->d_fown,
-                    c->vox.pts, c->vox.seg, c->vox.rel, c->vox.head, c->vox.incl, c->vox.start, c->vox.keep, c->vox.pos, c->vox.vout, c->vox.out,
-                    c->vox.d_off, c->vox.cnt};
-    for (void *b : bufs) if (b) (void)hipFree(b);
     for (LinSlot &S : c->slots) {
-        for (void *b : {(void *)S.d_partials, (void *)S.d_poses, (void *)S.d_tickets}) if (b) (void)hipFree(b);
-        for (void *b : S.tmp_dev) (void)hipFree(b);
         if (S.ev0) (void)hipEventDestroy(S.ev0);
         if (S.ev1) (void)hipEventDestroy(S.ev1);
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        if (S.h_poses) (void)hipHostFree(S.h_poses);
     }
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
     (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                         // (the buffers go with it)
 }
 
 const char *dcreg_last_error(const dcreg_ctx *c) { return c ? c->err : "null context"; }
@@ -2255,8 +2171,8 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "use_certificates") c->opt_use_cert = v != 0.0;
     else if (k == "count_searches") {
         if (v != 0.0 && !c->d_search_count) {
-            HIP_TRY(c, hipMalloc((void **)&c->d_search_count, kSearchCountBytes));
-            HIP_TRY(c, hipMemsetAsync(c->d_search_count, 0, kSearchCountBytes, c->stream));
+            HIP_TRY(c, c->d_search_count.alloc(kSearchCountBytes / sizeof(unsigned long long)));
+            HIP_TRY(c, hipMemsetAsync(c->d_search_count.data(), 0, kSearchCountBytes, c->stream));
         }
         c->opt_count_searches = v != 0.0;
     }
@@ -2327,7 +2243,7 @@ int dcreg_debug_index_check(dcreg_ctx *c, int64_t mismatches[5]) {
 int dcreg_set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, false); }
 int dcreg_set_source_device(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride) { return set_source(c, xyz, n, stride, true); }
 
-// dcreg_set_source_voxel* / dcreg_set_target_voxel*: the voxel pass writes its output packed into c->d_aligned - where set_source / set_target
+// dcreg_set_source_voxel* / dcreg_set_target_voxel*: the voxel pass writes its output packed into c->d_aligned.data() - where set_source / set_target
 // upload and check a cloud - with its bounds from the pass's one readback, and the commit of the plain calls takes it from there
 static void voxel_info(dcreg_voxel_info *info, const VoxelResult &r) {
     if (info) { info->n_in = r.n_in; info->n_finite = r.n_finite; info->n_voxels = r.n_voxels; info->n_out = r.n_out; }
@@ -2395,7 +2311,7 @@ int dcreg_reserve_warm_states(dcreg_ctx *c, int64_t n_states) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t stride = ((size_t)c->n_src + 63) & ~(size_t)63;
     // nothing is cleared: a state is "fresh" (host-side flag) until its first launch has filled it
-    if (ensure(c, c->d_state_batch, c->state_batch_cap, kStateRows * stride * (size_t)n_states)) return DCREG_E_NOMEM;
+    if (c->d_state_batch.ensure(c, kStateRows * stride * (size_t)n_states)) return DCREG_E_NOMEM;
     c->state_batch_stride = stride;
     c->n_batch_states = n_states;
     c->batch_state_valid.assign((size_t)n_states, 0);
@@ -2432,7 +2348,7 @@ static int frames_reserve_states(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t 
     if (n_states == 0 || fs.max_points <= 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t stride = ((size_t)fs.max_points + 63) & ~(size_t)63;       // one stride: the largest frame's
-    if (ensure(c, fs.state, fs.state_cap, kStateRows * stride * (size_t)n_states)) return DCREG_E_NOMEM;
+    if (fs.state.ensure(c, kStateRows * stride * (size_t)n_states)) return DCREG_E_NOMEM;
     fs.state_stride = stride;
     fs.n_states = n_states;
     fs.state_valid.assign((size_t)n_states, 0);
@@ -2524,27 +2440,28 @@ int dcreg_knn(dcreg_ctx *c, const float *q, int64_t n, int64_t stride, int k, do
     if (int rc = refuse_in_flight(c)) return rc;
     if (!q || !idx || !d2 || n < 0 || (k != 1 && k != 5)) { c->fail("invalid k-NN arguments (k must be 1 or 5)"); return DCREG_E_INVALID; }
     (void)roi_deactivate(c);
-    if (c->n_tgt <= 0) { c->fail("target index is not set"); return DCREG_E_STATE; }
+    if (c->map.n <= 0) { c->fail("target index is not set"); return DCREG_E_STATE; }
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = upload_cloud(c, q, n, stride, false, c->d_aligned, c->aligned_cap);
+    int rc = upload_cloud(c, q, n, stride, false, c->d_aligned);
     if (rc) return rc;
-    if (ensure(c, c->d_nn_idx, c->nn_idx_cap, (size_t)n * k) || ensure(c, c->d_nn_d2, c->nn_d2_cap, (size_t)n * k)) return DCREG_E_NOMEM;
-    rc = launch_knn(c, c->grid, c->d_aligned, n, k, max_radius, nullptr, c->d_nn_idx, c->d_nn_d2);
+    if (c->d_nn_idx.ensure(c, (size_t)n * k) || c->d_nn_d2.ensure(c, (size_t)n * k)) return DCREG_E_NOMEM;
+    rc = launch_knn(c, c->map.grid, c->d_aligned.data(), n, k, max_radius, nullptr, c->d_nn_idx.data(), c->d_nn_d2.data());
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(idx, c->d_nn_idx, sizeof(int32_t) * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d2, c->d_nn_d2, sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx, c->d_nn_idx.data(), sizeof(int32_t) * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d2, c->d_nn_d2.data(), sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
 }
 
 int dcreg_index_info_get(const dcreg_ctx *c, dcreg_index_info *info) {
     if (!c || !info) return DCREG_E_INVALID;
-    const dcreg::GridDev &g = c->roi_active ? c->roi_store.grid : c->grid;         // the whole map's index, whichever is active
+    const IndexSet &w = whole_map(c);
+    const dcreg::GridDev &g = w.grid;
     info->cell = g.h;
     info->origin[0] = g.ox; info->origin[1] = g.oy; info->origin[2] = g.oz;
     info->dims[0] = g.nx; info->dims[1] = g.ny; info->dims[2] = g.nz;
-    info->n_cells = c->roi_active ? c->roi_store.n_cells : c->n_cells; info->n_target = c->roi_active ? c->roi_store.n : c->n_tgt;
+    info->n_cells = w.n_cells; info->n_target = w.n;
     info->n_source = c->n_src; info->max_ring = c->last_max_ring;
     return DCREG_OK;
 }
@@ -2553,8 +2470,9 @@ int dcreg_roi_info(const dcreg_ctx *c, double info[11]) {
     if (!c || !info) return DCREG_E_INVALID;
     for (int a = 0; a < 3; ++a) { info[a] = c->roi_lo[a]; info[3 + a] = c->roi_hi[a]; }
     const bool have = c->roi_built && !c->roi_empty;
-    info[6] = have ? (double)(c->roi_active ? c->n_tgt : c->roi_store.n) : 0.0;
-    info[7] = have ? (c->roi_active ? c->grid.h : c->roi_store.grid.h) : 0.0;
+    const IndexSet &win = c->roi_active ? c->map : c->roi_store;       // the window's index, whichever is active
+    info[6] = have ? (double)win.n : 0.0;
+    info[7] = have ? win.grid.h : 0.0;
     info[8] = (double)c->roi_rebuilds; info[9] = c->roi_active ? 1.0 : 0.0; info[10] = c->whole_capped ? 1.0 : 0.0;
     return DCREG_OK;
 }
@@ -2566,13 +2484,13 @@ int dcreg_launch_stats_get(dcreg_ctx *c, dcreg_launch_stats *st, int reset) {
     st->points_searched = -1; st->points_team = -1;
     if (c->opt_count_searches && c->d_search_count) {      // synchronous: every launch so far has finished when this returns
         std::vector<unsigned long long> v(kSearchCountBytes / sizeof(unsigned long long));
-        HIP_TRY(c, hipMemcpyAsync(v.data(), c->d_search_count, kSearchCountBytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(v.data(), c->d_search_count.data(), kSearchCountBytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         unsigned long long tot = 0, team = 0;
         for (size_t k = 0; k < v.size(); k += kCounterStride / 2) { tot += v[k]; team += v[k + 1]; }
         st->points_searched = (int64_t)tot;
         st->points_team = (int64_t)team;
-        if (reset) HIP_TRY(c, hipMemsetAsync(c->d_search_count, 0, kSearchCountBytes, c->stream));
+        if (reset) HIP_TRY(c, hipMemsetAsync(c->d_search_count.data(), 0, kSearchCountBytes, c->stream));
     }
     if (reset) { c->n_launches = 0; c->n_poses_launched = 0; c->n_points_launched = 0; }
     return DCREG_OK;
@@ -2606,7 +2524,7 @@ int dcreg_team_pass_stamps(dcreg_ctx *c, uint64_t *out, int64_t cap_blocks) {
     const int64_t n = std::min<int64_t>(cap_blocks, (int64_t)c->team_stamps_n + 1);      // (+ 1: the outcome histogram behind the blocks)
     if (out && n > 0) {
         if (int rc = refuse_in_flight(c)) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out, c->d_team_stamps, sizeof(unsigned long long) * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out, c->d_team_stamps.data(), sizeof(unsigned long long) * 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     return (int)std::min<int64_t>((int64_t)c->team_stamps_n, 0x7FFFFFFF);

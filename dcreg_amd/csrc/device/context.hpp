@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../../include/dcreg.h"
@@ -16,18 +17,93 @@ struct dcreg_lin_params;
 struct dcreg_lin_out;
 struct dcreg_lin_debug;
 
+#define HIP_TRY(ctx, expr)                                                                       \
+    do {                                                                                         \
+        hipError_t e__ = (expr);                                                                 \
+        if (e__ != hipSuccess) {                                                                 \
+            (ctx)->fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return DCREG_E_DEVICE;                                                               \
+        }                                                                                        \
+    } while (0)
+
+// A device buffer (hipMalloc) that owns its memory: move-only, freed by its destructor.  No conversion to T*: a kernel argument is
+// written .data(), so a buffer object is never handed to a launch by value.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); swap(o); } return *this; }
+    ~DevBuf() { reset(); }
+    T *data() const { return p_; }
+    size_t cap() const { return cap_; }                 // elements
+    explicit operator bool() const { return p_ != nullptr; }
+    bool holds(size_t need) const { return p_ && need <= cap_; }
+    void swap(DevBuf &o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; cap_ = 0; }
+    // frees what it holds, then allocates exactly n elements (the caller reports a failure)
+    hipError_t alloc(size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        else cap_ = n;
+        return e;
+    }
+    // at least `need` elements, contents not kept: freed, then max(need, 1) allocated.  why != null: the failure's text names the caller
+    int ensure(dcreg_ctx *c, size_t need, const char *why = nullptr);
+    // at least `need` elements of which the first `keep` survive: allocated first (geometric capacity), the copy queued on c->stream and
+    // waited for, then the old buffer freed
+    int grow_keep(dcreg_ctx *c, size_t need, size_t keep);
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+// Pinned host memory (hipHostMalloc) that owns its block, as DevBuf; a block allocated hipHostMallocMapped also has its device address.
+template <typename T>
+class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    PinnedBuf(PinnedBuf &&o) noexcept { swap(o); }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { if (this != &o) { reset(); swap(o); } return *this; }
+    ~PinnedBuf() { reset(); }
+    T *data() const { return p_; }
+    T *dev() const { return d_; }                       // device address of a mapped block (null otherwise)
+    size_t cap() const { return cap_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void swap(PinnedBuf &o) noexcept { std::swap(p_, o.p_); std::swap(d_, o.d_); std::swap(cap_, o.cap_); }
+    void reset() { if (p_) (void)hipHostFree(p_); p_ = d_ = nullptr; cap_ = 0; }
+    // frees what it holds, then allocates n elements with these flags (capacity n once the block and its device address exist)
+    hipError_t alloc(size_t n, unsigned flags) {
+        reset();
+        hipError_t e = hipHostMalloc((void **)&p_, n * sizeof(T), flags);
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer((void **)&d_, p_, 0);
+        if (e == hipSuccess) cap_ = n;
+        return e;
+    }
+private:
+    T *p_ = nullptr, *d_ = nullptr;
+    size_t cap_ = 0;
+};
+
 // buffers and in-flight state of one linearisation slot
 
 struct LinSlot {
-    double *d_partials = nullptr; size_t partials_cap = 0;
+    DevBuf<double> d_partials;
     // batched poses: ONE pinned staging block [PoseArg x n | pose ids x n] and its device copy (one plain DMA per launch; a pageable
     // source is staged by the runtime, and beyond 16 KB that cost 14 us per launch)
-    unsigned char *h_poses = nullptr, *d_poses = nullptr; size_t poses_cap = 0;      // bytes
-    double *h_out = nullptr, *d_out = nullptr; size_t out_cap = 0;   // pinned, device-mapped result rows
+    PinnedBuf<unsigned char> h_poses;
+    DevBuf<unsigned char> d_poses;
+    PinnedBuf<double> h_out;       // pinned, device-mapped result rows
     std::vector<double> h_rows;    // ... and the checked snapshot of them the sums are taken from
-    unsigned int *d_tickets = nullptr; size_t tickets_cap = 0;
+    DevBuf<unsigned int> d_tickets;
     bool tickets_dirty = false;    // a launch may have died half-way: clear the tickets before the next one
-    std::vector<void *> tmp_dev;   // debug dump buffers of the launch in flight
+    std::vector<DevBuf<unsigned char>> tmp_dev;   // debug dump buffers of the launch in flight
     bool pending = false, fused = false, timed = false, sync = false;
     int n_poses = 0;
     uint32_t n_chunks = 0;
@@ -48,25 +124,28 @@ struct dcreg_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     char err[512] = {0};
 
-    // target
-    int64_t n_tgt = 0;
-    float4 *d_tgt_raw = nullptr; size_t tgt_raw_cap = 0;   // original order
-    float4 *d_tgt = nullptr; size_t tgt_cap = 0;           // cell-sorted
-    uint32_t *d_cell_start = nullptr; size_t cell_cap = 0;
-    dcreg::GridDev grid{};
-    int64_t n_cells = 0;
-    uint32_t occupied_cells = 0;
+    // a spatial index over a cloud (context.hip build_index): its points in original and in cell order, the cell table, the grid, and the
+    // empty-space field, its owners and the row words of the grid (build_gap_field, build_row_words)
+    struct IndexSet {
+        DevBuf<float4> raw; int64_t n = 0;
+        DevBuf<float4> sorted;
+        DevBuf<uint32_t> cell_start;
+        dcreg::GridDev grid{}; int64_t n_cells = 0; uint32_t occupied = 0;
+        DevBuf<uint8_t> gap;
+        DevBuf<uint32_t> owner, ymask;
+    };
+    // target: the ACTIVE index, the one every kernel launch uses (the whole map, or its window: see roi_store below)
+    IndexSet map;
     double radius_hint = 0.0;
     int last_max_ring = 0;
-    // ---- updates of the map in place (context.hip map_insert / map_crop: dcreg_target_insert*, dcreg_target_crop).  The new sorted points,
-    // and the raw ones of a crop, are built beside the current arrays and swapped in at the end; tgt_box = bounds of the map's points
-    float4 *d_tgt_alt = nullptr; size_t tgt_alt_cap = 0;
-    float4 *d_tgt_raw_alt = nullptr; size_t tgt_raw_alt_cap = 0;
-    uint32_t *d_cell_alt = nullptr; size_t cell_alt_cap = 0;
-    float4 *d_map_q = nullptr, *d_map_new = nullptr; size_t map_q_cap = 0, map_new_cap = 0;   // the offered points in the map frame / the appended ones
-    uint32_t *d_upd = nullptr; size_t upd_cap = 0;        // flags, scans, keys of an update
-    uint8_t *d_fgap = nullptr; size_t fgap_cap = 0;       // the fields over the box of a change (k_gap_init_box): plain and dense
-    uint32_t *d_fown = nullptr; size_t fown_cap = 0;
+    // ---- updates of the map in place (context.hip map_insert / map_crop: dcreg_target_insert*, dcreg_target_crop).  The new sorted points
+    // and cell table, and the raw points of a crop, are built beside the current arrays (map_alt: raw, sorted, cell_start, grid) and swapped
+    // in at the end; tgt_box = bounds of the map's points
+    IndexSet map_alt;
+    DevBuf<float4> d_map_q, d_map_new;                   // the offered points in the map frame / the appended ones
+    DevBuf<uint32_t> d_upd;                              // flags, scans, keys of an update
+    DevBuf<uint8_t> d_fgap;                              // the fields over the box of a change (k_gap_init_box): plain and dense
+    DevBuf<uint32_t> d_fown;
     double tgt_box[6] = {};
     double build_per_cell = 0.0;   // points per occupied cell when the grid was last derived (a merge that doubles it re-derives)
     int opt_map_update = 1;        // 1: merge into the current grid where possible, 0: always re-derive the grid
@@ -77,21 +156,12 @@ struct dcreg_ctx {
     // therefore search a second index built over the points of a BOX around the transformed source (its bounding box at the pose, the search
     // radius, "roi_margin" metres on top): the same points as the whole map holds there, in cells sized for their density alone.  Every
     // neighbour of every query lies inside the box, so the searches return what they would on the whole map (exact: the sums are bitwise the
-    // same, tests/test_gpu_round6.py); a pose that leaves the box rebuilds the window around itself.  One of the two indices is ACTIVE (the
-    // members above: what every kernel launch uses), the other is kept in roi_store; swapping them drops the neighbour states (their
-    // positions refer to one index's sorted order).  Everything but the single-pose product launches (k-NN, metrics, batches, dumps, the
-    // kd-tree comparator) runs on the whole map.
-    struct IndexSet {
-        float4 *raw = nullptr; size_t raw_cap = 0; int64_t n = 0;
-        float4 *sorted = nullptr; size_t sorted_cap = 0;
-        uint32_t *cell_start = nullptr; size_t cell_cap = 0;
-        dcreg::GridDev grid{}; int64_t n_cells = 0; uint32_t occupied = 0;
-        uint8_t *gap = nullptr; size_t gap_cap = 0;
-        uint32_t *owner = nullptr; size_t owner_cap = 0;
-        uint32_t *ymask = nullptr; size_t ymask_cap = 0;
-    };
+    // same, tests/test_gpu_round6.py); a pose that leaves the box rebuilds the window around itself.  One of the two indices is ACTIVE (map:
+    // what every kernel launch uses), the other is kept in roi_store; swapping them drops the neighbour states (their positions refer to
+    // one index's sorted order).  Everything but the single-pose product launches (k-NN, metrics, batches, dumps, the kd-tree comparator)
+    // runs on the whole map.
     IndexSet roi_store;            // the index that is NOT active
-    bool roi_active = false;       // the members above hold the window, roi_store the whole map
+    bool roi_active = false;       // map holds the window, roi_store the whole map
     bool roi_built = false;        // a window exists for the box roi_lo .. roi_hi
     bool roi_empty = false;        // ... but the map has no point in it: the whole map serves inside this box
     int opt_roi_index = 1;         // 0 never, 1 when the whole map's build ran into the table budget, 2 always
@@ -102,19 +172,16 @@ struct dcreg_ctx {
     double src_mn[3] = {}, src_mx[3] = {};      // bounding box of the source in the body frame (dcreg_set_source)
     int64_t roi_rebuilds = 0;
 
-    // auxiliary grid over the body-frame source (backward pass of dcreg_p2p_error)
-    float4 *d_aux = nullptr; size_t aux_cap = 0;
-    uint32_t *d_aux_cell_start = nullptr; size_t aux_cell_cap = 0;
-    dcreg::GridDev aux_grid{};
-    int64_t aux_n_cells = 0;
+    // auxiliary grid over the body-frame source (backward pass of dcreg_p2p_error): sorted, cell_start, grid, n_cells (the raw points are d_src_raw)
+    IndexSet aux;
     bool aux_valid = false;
 
     // source
     int64_t n_src = 0;
-    float4 *d_src_raw = nullptr; size_t src_raw_cap = 0;
-    float4 *d_src = nullptr; size_t src_cap = 0;           // Hilbert-sorted
+    DevBuf<float4> d_src_raw;
+    DevBuf<float4> d_src;                                  // Hilbert-sorted
     // neighbour state of the ctx's own single-pose launches (search.hpp kStateRows): [kStateRows][state_stride]
-    uint32_t *d_state = nullptr; size_t state_cap = 0;
+    DevBuf<uint32_t> d_state;
     size_t state_stride = 0;
     bool state_valid = false;      // the state holds the results of a search of the current clouds
     // What the states hold was measured against the parameters of the launch that wrote it: certificates against the search / gate
@@ -134,7 +201,7 @@ struct dcreg_ctx {
     double src_radius = 0.0;       // largest distance of a source point from the body-frame origin (bounds a pose change's effect)
     // batched launches: n_batch_states states of the same layout, [state][kStateRows][state_batch_stride] (dcreg_reserve_warm_states),
     // and whether each holds anything yet
-    uint32_t *d_state_batch = nullptr; size_t state_batch_cap = 0;
+    DevBuf<uint32_t> d_state_batch;
     size_t state_batch_stride = 0;
     int64_t n_batch_states = 0;
     std::vector<uint8_t> batch_state_valid;
@@ -143,14 +210,14 @@ struct dcreg_ctx {
     // pose's frame through its slice (kernels.hpp k_lin SLICE) and keep their neighbour states here - the ctx's own source, its own state
     // and its reserved batch states are not touched.
     struct FrameSet {
-        float4 *raw = nullptr; size_t raw_cap = 0;             // upload order
-        float4 *src = nullptr; size_t src_cap = 0;             // curve order, frame f from point slice[f].x
-        int64_t *d_off = nullptr; size_t off_cap = 0;          // frame f = points [off[f], off[f + 1]) of the upload
-        uint32_t *d_dst = nullptr; size_t dst_cap = 0;         // ... and where it starts in src
-        dcreg::FrameBox *d_box = nullptr; size_t box_cap = 0;
+        DevBuf<float4> raw;                                    // upload order
+        DevBuf<float4> src;                                    // curve order, frame f from point slice[f].x
+        DevBuf<int64_t> d_off;                                 // frame f = points [off[f], off[f + 1]) of the upload
+        DevBuf<uint32_t> d_dst;                                // ... and where it starts in src
+        DevBuf<dcreg::FrameBox> d_box;
         std::vector<uint2> slice;                              // per frame: {first point in src, points}
         int64_t max_points = 0;
-        uint32_t *state = nullptr; size_t state_cap = 0;       // [state][kStateRows][state_stride]
+        DevBuf<uint32_t> state;                                // [state][kStateRows][state_stride]
         size_t state_stride = 0;
         int64_t n_states = 0;
         std::vector<uint8_t> state_valid;
@@ -163,14 +230,14 @@ struct dcreg_ctx {
     // target, source, states, frames or window index is touched.
     FrameSet pair_src;
     struct PairSet {
-        float4 *raw = nullptr; size_t raw_cap = 0;             // the batch's targets in upload order (w = index within the own cloud)
-        float4 *sorted = nullptr; size_t sorted_cap = 0;       // cell-sorted, target after target, kPtsPad zero entries behind each
-        uint32_t *table = nullptr; size_t table_cap = 0;       // the cell tables, target after target
-        uint32_t *ymask = nullptr; size_t ymask_cap = 0;       // the row words, target after target
-        int64_t *d_off = nullptr; size_t off_cap = 0;          // [3][n + 1]: a pass's point, table and row-word offsets (kernels.hpp k_pairs_*)
-        dcreg::PairCells *d_cells = nullptr; size_t cells_cap = 0;
-        uint32_t *d_words = nullptr; size_t words_cap = 0;     // bounds of the batch's targets, then occupied cells of a pass
-        dcreg::PairGrid *d_grids = nullptr; size_t grids_cap = 0;   // per target of the batch: what k_lin<.., GRIDS> reads (empty target: n_pts 0)
+        DevBuf<float4> raw;                                    // the batch's targets in upload order (w = index within the own cloud)
+        DevBuf<float4> sorted;                                 // cell-sorted, target after target, kPtsPad zero entries behind each
+        DevBuf<uint32_t> table;                                // the cell tables, target after target
+        DevBuf<uint32_t> ymask;                                // the row words, target after target
+        DevBuf<int64_t> d_off;                                 // [3][n + 1]: a pass's point, table and row-word offsets (kernels.hpp k_pairs_*)
+        DevBuf<dcreg::PairCells> d_cells;
+        DevBuf<uint32_t> d_words;                              // bounds of the batch's targets, then occupied cells of a pass
+        DevBuf<dcreg::PairGrid> d_grids;                       // per target of the batch: what k_lin<.., GRIDS> reads (empty target: n_pts 0)
         std::vector<uint8_t> built;                            // per target of the batch: it has an index
         int n = 0;                                             // targets of the batch
         float radius_sq_f = 0.f;                               // the search bound the grids' rings were counted for (LinArgs::radius_sq_f)
@@ -180,41 +247,40 @@ struct dcreg_ctx {
     // cloud (segment) and voxel key relative to the cloud's minimum voxel; per sorted position: head flags and their inclusive scan; per voxel:
     // its first sorted position, its point and keep flag (then their scan); per cloud: the counters of the call (voxel.hip VoxCounters)
     struct VoxelBufs {
-        float4 *pts = nullptr; size_t pts_cap = 0;
-        uint32_t *seg = nullptr; size_t seg_cap = 0;
-        uint64_t *rel = nullptr; size_t rel_cap = 0;
-        uint32_t *head = nullptr, *incl = nullptr, *start = nullptr, *keep = nullptr, *pos = nullptr;
-        size_t head_cap = 0, incl_cap = 0, start_cap = 0, keep_cap = 0, pos_cap = 0;
-        float4 *vout = nullptr; size_t vout_cap = 0;
-        float *out = nullptr; size_t out_cap = 0;            // 3 floats per output point (dcreg_voxel_downsample*)
-        int64_t *d_off = nullptr; size_t off_cap = 0;
-        int64_t *cnt = nullptr; size_t cnt_cap = 0;
+        DevBuf<float4> pts;
+        DevBuf<uint32_t> seg;
+        DevBuf<uint64_t> rel;
+        DevBuf<uint32_t> head, incl, start, keep, pos;
+        DevBuf<float4> vout;
+        DevBuf<float> out;                                   // 3 floats per output point (dcreg_voxel_downsample*)
+        DevBuf<int64_t> d_off;
+        DevBuf<int64_t> cnt;
     };
     VoxelBufs vox;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
-    double *h_euler = nullptr, *d_euler = nullptr;     // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
-    unsigned long long *d_search_count = nullptr;      // option "count_searches": points searched since the last reset
+    PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
+    DevBuf<double> d_euler;
+    DevBuf<unsigned long long> d_search_count;         // option "count_searches": points searched since the last reset
 
     // build scratch
-    float *d_stage = nullptr; size_t stage_cap = 0;
+    DevBuf<float> d_stage;
     // small frames from host buffers (the registration path): the caller's floats are copied into this pinned block with a plain memcpy and
     // uploaded from there - the caller's buffer is consumed when dcreg_set_source returns whatever kind of memory it is, without a
     // stream synchronise; h_stage_ev = the upload behind the last use of the block
-    float *h_stage = nullptr; size_t h_stage_cap = 0; hipEvent_t h_stage_ev = nullptr; bool h_stage_busy = false;
+    PinnedBuf<float> h_stage; hipEvent_t h_stage_ev = nullptr; bool h_stage_busy = false;
     hipEvent_t null_ev = nullptr;          // a cloud in device memory: marks the work queued on the legacy default stream before it is read
-    uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_vals = nullptr, *d_vals2 = nullptr;
-    size_t keys_cap = 0, keys2_cap = 0, vals_cap = 0, vals2_cap = 0;
-    uint64_t *d_mkeys = nullptr, *d_mkeys2 = nullptr; size_t mkeys_cap = 0, mkeys2_cap = 0;
-    uint32_t *d_scratch = nullptr;
-    char *sort_tmp = nullptr; size_t sort_tmp_cap = 0;
+    DevBuf<uint32_t> d_keys, d_keys2, d_vals, d_vals2;
+    DevBuf<uint64_t> d_mkeys, d_mkeys2;
+    DevBuf<uint32_t> d_scratch;
+    DevBuf<char> sort_tmp;
 
     // linearisation: per-slot buffers (see linearize_begin / linearize_end)
     // gate of pipelined launches (kernels.hpp k_gate): pinned sequence number + pose, the device-resident pose it fills, abort word
-    dcreg::GateHost *h_gate = nullptr, *d_gate_host = nullptr;
-    dcreg::PoseArg *d_gate_pose = nullptr;
-    uint32_t *d_gate_abort = nullptr;
-    dcreg::GateDev *d_gate_dev = nullptr;  // device copy of the gate record: launches gated in their first kernel (kernels.hpp gate_wait)
+    PinnedBuf<dcreg::GateHost> h_gate;     // (mapped: h_gate.dev() is the record's device address)
+    DevBuf<dcreg::PoseArg> d_gate_pose;
+    DevBuf<uint32_t> d_gate_abort;
+    DevBuf<dcreg::GateDev> d_gate_dev;     // device copy of the gate record: launches gated in their first kernel (kernels.hpp gate_wait)
     bool opt_gate_in_kernel = true;
     int opt_one_wave = 1;                 // k_lin<.., ONE> (one-wave blocks): 0 never, 1 by the rule, 2 wherever possible
     bool opt_one_wave_batches = true;     // ... for batched launches of one-chunk poses with at least opt_one_wave_min_blocks blocks in all
@@ -229,15 +295,16 @@ struct dcreg_ctx {
     LinSlot slots[kLinSlots];
 
     // k-NN / p2p
-    float4 *d_aligned = nullptr; size_t aligned_cap = 0;
-    int32_t *d_nn_idx = nullptr; size_t nn_idx_cap = 0;
-    float *d_nn_d2 = nullptr; size_t nn_d2_cap = 0;
-    double *d_p2p_part = nullptr; size_t p2p_part_cap = 0;
+    DevBuf<float4> d_aligned;
+    DevBuf<int32_t> d_nn_idx;
+    DevBuf<float> d_nn_d2;
+    DevBuf<double> d_p2p_part;
 
     // native exchange of point-sharded runs (exchange.hip): an ncclComm_t on this ctx's device + staging rows
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;
-    double *d_xrow = nullptr, *d_xall = nullptr, *h_xrow = nullptr, *h_xall = nullptr;
+    DevBuf<double> d_xrow, d_xall;
+    PinnedBuf<double> h_xrow, h_xall;
 
     // options / timing
     double opt_cell = 0.0, opt_cell_factor = 2.0;
@@ -255,15 +322,12 @@ struct dcreg_ctx {
     int opt_xcd_chunk = 16;        // query-block -> XCD mapping (kernels.hpp xcd_remap): runs of 16 blocks round-robin (measured: C4 -13 %)
     bool opt_fast_plane = true;    // plane_fit_qr_fast (search.hpp) instead of the Eigen-shaped plane_fit_qr
     bool opt_gap_field = true;     // build the empty-space distance field of the target grid
-    uint8_t *d_gap = nullptr; size_t gap_cap = 0;
     bool opt_direct_rows = true;   // single-pose launches of at most kChunk blocks publish block rows; the host adds them
     bool opt_far_bound = true;     // far queries with a loose bound start from the points around the nearest occupied cell (search.hpp lin_search6)
-    uint32_t *d_owner = nullptr; size_t owner_cap = 0;
-    uint32_t *d_ymask = nullptr; size_t ymask_cap = 0;
     bool opt_keep_source_order = false;   // experiments only
     // heavy groups first (kernels.hpp k_group_cost): the dispatch order of the query-block groups, estimated once per cloud pair
     bool opt_dispatch_order = true;
-    uint8_t group_order[256] = {}; float *d_group_est = nullptr;
+    uint8_t group_order[256] = {}; DevBuf<float> d_group_est;
     uint32_t group_blocks = 0, n_groups = 0;
     int n_cus = 256;                // compute units of the device
     void *kd = nullptr;             // kd-tree comparator (kdtree.hip), built on request
@@ -291,8 +355,8 @@ struct dcreg_ctx {
     int opt_team_pass = 1;
     double opt_team_pass_max_points = 16384.0, opt_team_pass_min_frac = 0.5, opt_team_pass_min_cell_pts = 3.0;
     bool opt_team_stamps = false;
-    unsigned long long *d_team_stamps = nullptr; size_t team_stamps_cap = 0; uint32_t team_stamps_n = 0;
-    uint32_t *d_adv_counts = nullptr; size_t adv_counts_cap = 0; bool adv_counts_dirty = true;
+    DevBuf<unsigned long long> d_team_stamps; uint32_t team_stamps_n = 0;
+    DevBuf<uint32_t> d_adv_counts; bool adv_counts_dirty = true;
     int64_t n_advance_launches = 0;
     int opt_team_max = 7;          // search.hpp team_search6: waves with at most this many lanes to search serve them cooperatively
     bool opt_warm = true;          // bound each search by the previous neighbour set (same exact result, fewer cells)
@@ -309,39 +373,44 @@ struct dcreg_ctx {
     void fail(const char *fmt, ...);
 };
 
-namespace dcreg {
-#define HIP_TRY(ctx, expr)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return DCREG_E_DEVICE;                                                               \
-        }                                                                                        \
-    } while (0)
-
-// (re)allocates a device buffer of at least `need` elements; the contents are not kept
 template <typename T>
-static int ensure(dcreg_ctx *c, T *&ptr, size_t &cap, size_t need) {
-    if (need <= cap && ptr) return DCREG_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr; cap = 0;
-    size_t n = std::max<size_t>(need, 1);
-    hipError_t e = hipMalloc((void **)&ptr, n * sizeof(T));
+int DevBuf<T>::ensure(dcreg_ctx *c, size_t need, const char *why) {
+    if (holds(need)) return DCREG_OK;
+    const size_t n = std::max<size_t>(need, 1);
+    const hipError_t e = alloc(n);
     if (e != hipSuccess) {
         (void)hipGetLastError();      // (the failed allocation must not surface as the "launch error" of whatever is queued next)
-        c->fail("hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e));
+        if (why) c->fail("hipMalloc(%zu B) failed %s", n * sizeof(T), why);
+        else c->fail("hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e));
         return DCREG_E_NOMEM;
     }
-    cap = n;
     return DCREG_OK;
 }
+
+template <typename T>
+int DevBuf<T>::grow_keep(dcreg_ctx *c, size_t need, size_t keep) {
+    if (holds(need)) return DCREG_OK;
+    DevBuf fresh;
+    const size_t n = std::max(need, cap_ + cap_ / 2);
+    if (fresh.alloc(n) != hipSuccess) {
+        (void)hipGetLastError();
+        c->fail("hipMalloc(%zu B) failed while growing the map", n * sizeof(T));
+        return DCREG_E_NOMEM;
+    }
+    if (p_ && keep) HIP_TRY(c, hipMemcpyAsync(fresh.p_, p_, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    swap(fresh);                      // (the old buffer goes with `fresh`)
+    return DCREG_OK;
+}
+
+namespace dcreg {
 
 int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *p,
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
-int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, float4 *&raw, size_t &raw_cap);   // context.hip
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw);   // context.hip
 // voxel.hip: the voxel-grid pass of n_clouds clouds (offsets off[n_clouds + 1], host memory) - checks everything before it writes; the output
 // points go to c->vox.out (3 floats each) or, packed, to c->d_aligned as k_pack packs a cloud (one cloud only).  Ends with ONE readback of
 // the per-cloud counts and the bounds of the output.

@@ -94,10 +94,7 @@ int dcreg_comm_destroy(dcreg_ctx *c) {
         if (A.ok()) (void)A.CommDestroy((ncclComm_t)c->comm);
         c->comm = nullptr;
     }
-    if (c->d_xrow) { (void)hipFree(c->d_xrow); c->d_xrow = nullptr; }
-    if (c->d_xall) { (void)hipFree(c->d_xall); c->d_xall = nullptr; }
-    if (c->h_xrow) { (void)hipHostFree(c->h_xrow); c->h_xrow = nullptr; }
-    if (c->h_xall) { (void)hipHostFree(c->h_xall); c->h_xall = nullptr; }
+    c->d_xrow.reset(); c->d_xall.reset(); c->h_xrow.reset(); c->h_xall.reset();
     c->comm_world = 0; c->comm_rank = 0;
     return DCREG_OK;
 }
@@ -124,10 +121,8 @@ int dcreg_comm_init(dcreg_ctx *c, const void *id128, int rank, int world) {
     }
     if (r != ncclSuccess) { c->fail("ncclCommInitRank failed: %s", A.GetErrorString(r)); return DCREG_E_DEVICE; }
     c->comm = comm; c->comm_rank = rank; c->comm_world = world;
-    const size_t row = 32 * sizeof(double);
-    if (hipMalloc((void **)&c->d_xrow, row) != hipSuccess || hipMalloc((void **)&c->d_xall, row * (size_t)world) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_xrow, row, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_xall, row * (size_t)world, hipHostMallocDefault) != hipSuccess) {
+    if (c->d_xrow.alloc(32) != hipSuccess || c->d_xall.alloc(32 * (size_t)world) != hipSuccess || c->h_xrow.alloc(32, hipHostMallocDefault) != hipSuccess ||
+        c->h_xall.alloc(32 * (size_t)world, hipHostMallocDefault) != hipSuccess) {
         (void)dcreg_comm_destroy(c);
         c->fail("allocating the exchange buffers failed");
         return DCREG_E_NOMEM;
@@ -141,18 +136,18 @@ int dcreg_comm_allgather_sum(dcreg_ctx *c, double row[32]) {
     if (!c->comm) { c->fail("no communicator: call dcreg_comm_init first"); return DCREG_E_STATE; }
     RcclApi &A = rccl();
     const size_t bytes = 32 * sizeof(double);
-    std::memcpy(c->h_xrow, row, bytes);
-    hipError_t e = hipMemcpyAsync(c->d_xrow, c->h_xrow, bytes, hipMemcpyHostToDevice, c->stream);
+    std::memcpy(c->h_xrow.data(), row, bytes);
+    hipError_t e = hipMemcpyAsync(c->d_xrow.data(), c->h_xrow.data(), bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        const ncclResult_t r = A.AllGather(c->d_xrow, c->d_xall, 32, ncclDouble, (ncclComm_t)c->comm, c->stream);
+        const ncclResult_t r = A.AllGather(c->d_xrow.data(), c->d_xall.data(), 32, ncclDouble, (ncclComm_t)c->comm, c->stream);
         if (r != ncclSuccess) { c->fail("ncclAllGather failed: %s", A.GetErrorString(r)); return DCREG_E_DEVICE; }
-        e = hipMemcpyAsync(c->h_xall, c->d_xall, bytes * (size_t)c->comm_world, hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(c->h_xall.data(), c->d_xall.data(), bytes * (size_t)c->comm_world, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { c->fail("exchange failed: %s", hipGetErrorString(e)); return DCREG_E_DEVICE; }
     for (int k = 0; k < 32; ++k) row[k] = 0.0;
     for (int r = 0; r < c->comm_world; ++r)              // fixed association order
-        for (int k = 0; k < 32; ++k) row[k] += c->h_xall[(size_t)r * 32 + k];
+        for (int k = 0; k < 32; ++k) row[k] += c->h_xall.data()[(size_t)r * 32 + k];
     return DCREG_OK;
 }
 
@@ -165,23 +160,21 @@ int dcreg_comm_allgather(dcreg_ctx *c, const double *send, double *recv, int64_t
     RcclApi &A = rccl();
     if (hipSetDevice(c->device) != hipSuccess) { c->fail("hipSetDevice failed"); return DCREG_E_DEVICE; }
     const size_t bytes = sizeof(double) * (size_t)count, all = bytes * (size_t)c->comm_world;
-    double *d_send = nullptr, *d_recv = nullptr;
-    if (hipMalloc((void **)&d_send, bytes) != hipSuccess || hipMalloc((void **)&d_recv, all) != hipSuccess) {
-        if (d_send) (void)hipFree(d_send);
+    DevBuf<double> d_send, d_recv;          // (freed on return, after the stream is drained)
+    if (d_send.alloc((size_t)count) != hipSuccess || d_recv.alloc((size_t)count * c->comm_world) != hipSuccess) {
         c->fail("allocating %zu bytes for the gather failed", bytes + all);
         return DCREG_E_NOMEM;
     }
     int rc = DCREG_OK;
-    hipError_t e = hipMemcpyAsync(d_send, send, bytes, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(d_send.data(), send, bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        const ncclResult_t r = A.AllGather(d_send, d_recv, (size_t)count, ncclDouble, (ncclComm_t)c->comm, c->stream);
+        const ncclResult_t r = A.AllGather(d_send.data(), d_recv.data(), (size_t)count, ncclDouble, (ncclComm_t)c->comm, c->stream);
         if (r != ncclSuccess) { c->fail("ncclAllGather failed: %s", A.GetErrorString(r)); rc = DCREG_E_DEVICE; }
-        else e = hipMemcpyAsync(recv, d_recv, all, hipMemcpyDeviceToHost, c->stream);
+        else e = hipMemcpyAsync(recv, d_recv.data(), all, hipMemcpyDeviceToHost, c->stream);
     }
     if (rc == DCREG_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (rc == DCREG_OK && e != hipSuccess) { c->fail("gather failed: %s", hipGetErrorString(e)); rc = DCREG_E_DEVICE; }
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d_send); (void)hipFree(d_recv);
     return rc;
 }
 int dcreg_comm_info(const dcreg_ctx *c, int *rank, int *world) {

@@ -25,15 +25,6 @@
 
 using namespace dcreg;
 
-#define HIP_TRY3(ctx, expr)                                                                      \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return DCREG_E_DEVICE;                                                               \
-        }                                                                                        \
-    } while (0)
-
 namespace dcreg {
 
 static inline unsigned blocks_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
@@ -47,29 +38,21 @@ struct KdDev {
 };
 
 struct KdTree {
-    float *d_split = nullptr;
-    uint8_t *d_axis = nullptr;
-    uint32_t *d_leaf_start = nullptr;
-    float4 *d_pts = nullptr;
-    float4 *d_q = nullptr; size_t q_cap = 0;
-    int32_t *d_idx = nullptr; float *d_d2 = nullptr; size_t out_cap = 0;
+    DevBuf<float> d_split;
+    DevBuf<uint8_t> d_axis;
+    DevBuf<uint32_t> d_leaf_start;
+    DevBuf<float4> d_pts;
+    DevBuf<float4> d_q;
+    DevBuf<int32_t> d_idx;
+    DevBuf<float> d_d2;
     uint32_t n_internal = 0, n_leaves = 0;
     int depth = 0, leaf_size = 0;
     int64_t n = 0;
     double build_ms = 0.0;
-    KdDev dev() const { return KdDev{d_split, d_axis, d_leaf_start, d_pts, n_internal}; }
-    void release() {
-        for (void *p : {(void *)d_split, (void *)d_axis, (void *)d_leaf_start, (void *)d_pts, (void *)d_q, (void *)d_idx, (void *)d_d2}) if (p) (void)hipFree(p);
-        *this = KdTree{};
-    }
+    KdDev dev() const { return KdDev{d_split.data(), d_axis.data(), d_leaf_start.data(), d_pts.data(), n_internal}; }
 };
 
-void kdtree_free(void *p) {
-    if (!p) return;
-    KdTree *t = (KdTree *)p;
-    t->release();
-    delete t;
-}
+void kdtree_free(void *p) { delete (KdTree *)p; }
 
 constexpr int kKdStack = 40;      // depth <= 31 internal levels: one pending sibling per level
 
@@ -162,16 +145,16 @@ int dcreg_kdtree_build(dcreg_ctx *c, int leaf_size) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     (void)roi_deactivate(c);
-    if (c->n_tgt <= 0) { c->fail("target cloud is not set"); return DCREG_E_STATE; }
+    if (c->map.n <= 0) { c->fail("target cloud is not set"); return DCREG_E_STATE; }
     if (leaf_size < 1 || leaf_size > 256) { c->fail("kd-tree leaf size must be 1 .. 256"); return DCREG_E_INVALID; }
-    HIP_TRY3(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipSetDevice(c->device));
     if (!c->kd) c->kd = new KdTree();
     KdTree &T = *(KdTree *)c->kd;
-    T.release();
-    const int64_t n = c->n_tgt;
+    T = KdTree{};
+    const int64_t n = c->map.n;
     std::vector<float4> raw((size_t)n);
-    HIP_TRY3(c, hipMemcpyAsync(raw.data(), c->d_tgt_raw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY3(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(raw.data(), c->map.raw.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<float> split; std::vector<uint8_t> axis; std::vector<uint32_t> leaf_start, order;
     kd_build_host(raw, leaf_size, split, axis, leaf_start, order, T.depth);
@@ -179,16 +162,16 @@ int dcreg_kdtree_build(dcreg_ctx *c, int leaf_size) {
     for (int64_t k = 0; k < n; ++k) pts[(size_t)k] = raw[order[(size_t)k]];
     T.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     T.n = n; T.leaf_size = leaf_size; T.n_internal = (uint32_t)split.size(); T.n_leaves = T.n_internal + 1u;
-    HIP_TRY3(c, hipMalloc((void **)&T.d_split, sizeof(float) * std::max<size_t>(split.size(), 1)));
-    HIP_TRY3(c, hipMalloc((void **)&T.d_axis, std::max<size_t>(axis.size(), 1)));
-    HIP_TRY3(c, hipMalloc((void **)&T.d_leaf_start, sizeof(uint32_t) * leaf_start.size()));
-    HIP_TRY3(c, hipMalloc((void **)&T.d_pts, sizeof(float4) * pts.size()));
+    HIP_TRY(c, T.d_split.alloc(std::max<size_t>(split.size(), 1)));
+    HIP_TRY(c, T.d_axis.alloc(std::max<size_t>(axis.size(), 1)));
+    HIP_TRY(c, T.d_leaf_start.alloc(leaf_start.size()));
+    HIP_TRY(c, T.d_pts.alloc(pts.size()));
     if (!split.empty()) {
-        HIP_TRY3(c, hipMemcpy(T.d_split, split.data(), sizeof(float) * split.size(), hipMemcpyHostToDevice));
-        HIP_TRY3(c, hipMemcpy(T.d_axis, axis.data(), axis.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(T.d_split.data(), split.data(), sizeof(float) * split.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(T.d_axis.data(), axis.data(), axis.size(), hipMemcpyHostToDevice));
     }
-    HIP_TRY3(c, hipMemcpy(T.d_leaf_start, leaf_start.data(), sizeof(uint32_t) * leaf_start.size(), hipMemcpyHostToDevice));
-    HIP_TRY3(c, hipMemcpy(T.d_pts, pts.data(), sizeof(float4) * pts.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(T.d_leaf_start.data(), leaf_start.data(), sizeof(uint32_t) * leaf_start.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(T.d_pts.data(), pts.data(), sizeof(float4) * pts.size(), hipMemcpyHostToDevice));
     return DCREG_OK;
 }
 
@@ -198,27 +181,19 @@ int dcreg_knn_timed(dcreg_ctx *c, const float *q, int64_t n, int64_t stride, int
     if (int rc = refuse_in_flight(c)) return rc;
     if (!q || !idx || !d2 || n <= 0 || stride < 3 || (k != 1 && k != 5) || repeats < 1 || (index < 0 || index > 2)) { c->fail("invalid arguments"); return DCREG_E_INVALID; }
     (void)roi_deactivate(c);
-    if (c->n_tgt <= 0) { c->fail("target index is not set"); return DCREG_E_STATE; }
-    if (index == 1 && (!c->kd || ((KdTree *)c->kd)->n != c->n_tgt)) { c->fail("dcreg_kdtree_build first (after the last dcreg_set_target)"); return DCREG_E_STATE; }
-    HIP_TRY3(c, hipSetDevice(c->device));
+    if (c->map.n <= 0) { c->fail("target index is not set"); return DCREG_E_STATE; }
+    if (index == 1 && (!c->kd || ((KdTree *)c->kd)->n != c->map.n)) { c->fail("dcreg_kdtree_build first (after the last dcreg_set_target)"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
     if (!c->kd) c->kd = new KdTree();
     KdTree &T = *(KdTree *)c->kd;
-    if ((size_t)n > T.q_cap) { if (T.d_q) (void)hipFree(T.d_q); T.d_q = nullptr; T.q_cap = 0; HIP_TRY3(c, hipMalloc((void **)&T.d_q, sizeof(float4) * (size_t)n)); T.q_cap = (size_t)n; }
-    if ((size_t)n * k > T.out_cap) {
-        if (T.d_idx) (void)hipFree(T.d_idx);
-        if (T.d_d2) (void)hipFree(T.d_d2);
-        T.d_idx = nullptr; T.d_d2 = nullptr; T.out_cap = 0;
-        HIP_TRY3(c, hipMalloc((void **)&T.d_idx, sizeof(int32_t) * (size_t)n * k));
-        HIP_TRY3(c, hipMalloc((void **)&T.d_d2, sizeof(float) * (size_t)n * k));
-        T.out_cap = (size_t)n * k;
-    }
+    if (T.d_q.ensure(c, (size_t)n) || T.d_idx.ensure(c, (size_t)n * k) || T.d_d2.ensure(c, (size_t)n * k)) return DCREG_E_NOMEM;
     {
         std::vector<float4> hq((size_t)n);
         for (int64_t i = 0; i < n; ++i) {
             union { uint32_t u; float f; } w; w.u = (uint32_t)i;
             hq[(size_t)i] = float4{q[i * stride], q[i * stride + 1], q[i * stride + 2], w.f};
         }
-        HIP_TRY3(c, hipMemcpy(T.d_q, hq.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(T.d_q.data(), hq.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
     }
     float bound = 3.0e38f;
     if (max_radius > 0.0 && std::isfinite(max_radius)) {            // as launch_knn: candidates with d2 < bound are kept
@@ -227,23 +202,23 @@ int dcreg_knn_timed(dcreg_ctx *c, const float *q, int64_t n, int64_t stride, int
         bound = std::nextafterf(rf, INFINITY);
     }
     auto launch = [&]() -> int {
-        if (index != 1) return launch_knn(c, c->grid, T.d_q, n, k, max_radius, nullptr, T.d_idx, T.d_d2, index == 2);
-        if (k == 1) hipLaunchKernelGGL(k_kdtree_knn<1>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q, (uint32_t)n, T.dev(), bound, T.d_idx, T.d_d2);
-        else hipLaunchKernelGGL(k_kdtree_knn<5>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q, (uint32_t)n, T.dev(), bound, T.d_idx, T.d_d2);
-        HIP_TRY3(c, hipGetLastError());
+        if (index != 1) return launch_knn(c, c->map.grid, T.d_q.data(), n, k, max_radius, nullptr, T.d_idx.data(), T.d_d2.data(), index == 2);
+        if (k == 1) hipLaunchKernelGGL(k_kdtree_knn<1>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
+        else hipLaunchKernelGGL(k_kdtree_knn<5>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
+        HIP_TRY(c, hipGetLastError());
         return DCREG_OK;
     };
     int rc = launch();                                              // warm-up (and the result)
     if (rc) return rc;
-    HIP_TRY3(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     for (int r = 0; r < repeats; ++r) { rc = launch(); if (rc) return rc; }
-    HIP_TRY3(c, hipEventRecord(c->ev1, c->stream));
-    HIP_TRY3(c, hipEventSynchronize(c->ev1));
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
     float ms = 0.f;
-    HIP_TRY3(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (kernel_ms) *kernel_ms = (double)ms / repeats;
-    HIP_TRY3(c, hipMemcpy(idx, T.d_idx, sizeof(int32_t) * (size_t)n * k, hipMemcpyDeviceToHost));
-    HIP_TRY3(c, hipMemcpy(d2, T.d_d2, sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(idx, T.d_idx.data(), sizeof(int32_t) * (size_t)n * k, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(d2, T.d_d2.data(), sizeof(float) * (size_t)n * k, hipMemcpyDeviceToHost));
     return DCREG_OK;
 }
 

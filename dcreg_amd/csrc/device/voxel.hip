@@ -273,8 +273,8 @@ template <typename K>
 int sort_pairs(dcreg_ctx *c, K *keys_in, K *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int bits) {
     size_t tmp = 0;
     HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
-    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
+    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    HIP_TRY(c, rocprim::radix_sort_pairs(c->sort_tmp.data(), tmp, keys_in, keys_out, vals_in, vals_out, n, 0, bits, c->stream));
     return DCREG_OK;
 }
 
@@ -282,9 +282,9 @@ int scan(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inclusi
     size_t tmp = 0;
     if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
     else HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    if (ensure(c, c->sort_tmp, c->sort_tmp_cap, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp, tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
-    else HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
+    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.data(), tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
+    else HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
     return DCREG_OK;
 }
 
@@ -317,22 +317,22 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
     HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::VoxelBufs &B = c->vox;
     const size_t nc = (size_t)kCnt * n_clouds + kTail;
-    if (ensure(c, B.seg, B.seg_cap, (size_t)n) || ensure(c, B.rel, B.rel_cap, (size_t)n) || ensure(c, B.head, B.head_cap, (size_t)n) ||
-        ensure(c, B.incl, B.incl_cap, (size_t)n) || ensure(c, B.start, B.start_cap, (size_t)n + 1) || ensure(c, B.keep, B.keep_cap, (size_t)n) ||
-        ensure(c, B.pos, B.pos_cap, (size_t)n) || ensure(c, B.vout, B.vout_cap, (size_t)n) || ensure(c, B.d_off, B.off_cap, (size_t)n_clouds + 1) ||
-        ensure(c, B.cnt, B.cnt_cap, nc) || ensure(c, c->d_mkeys, c->mkeys_cap, (size_t)n) || ensure(c, c->d_mkeys2, c->mkeys2_cap, (size_t)n) ||
-        ensure(c, c->d_vals, c->vals_cap, (size_t)n) || ensure(c, c->d_vals2, c->vals2_cap, (size_t)n))
+    if (B.seg.ensure(c, (size_t)n) || B.rel.ensure(c, (size_t)n) || B.head.ensure(c, (size_t)n) ||
+        B.incl.ensure(c, (size_t)n) || B.start.ensure(c, (size_t)n + 1) || B.keep.ensure(c, (size_t)n) ||
+        B.pos.ensure(c, (size_t)n) || B.vout.ensure(c, (size_t)n) || B.d_off.ensure(c, (size_t)n_clouds + 1) ||
+        B.cnt.ensure(c, nc) || c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
+        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
-    if (packed ? ensure(c, c->d_aligned, c->aligned_cap, (size_t)n) : ensure(c, B.out, B.out_cap, (size_t)(3 * n))) return DCREG_E_NOMEM;
-    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts, B.pts_cap);
+    if (packed ? c->d_aligned.ensure(c, (size_t)n) : B.out.ensure(c, (size_t)(3 * n))) return DCREG_E_NOMEM;
+    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(B.d_off, off, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt, n_clouds);
+    HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), n_clouds);
     const double lx = p->leaf[0], ly = p->leaf[1], lz = p->leaf[2];
-    hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, B.pts, n, B.d_off, n_clouds,
-                       lx, ly, lz, B.seg, B.cnt);
+    hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), n, B.d_off.data(), n_clouds,
+                       lx, ly, lz, B.seg.data(), B.cnt.data());
     std::vector<int64_t> h((size_t)nc);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt.data(), sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
 
@@ -360,35 +360,35 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
     const bool one_pass = sbits + bx + by + bz <= 64;
 
     // ---- keys, stable sort, voxel heads and starts
-    hipLaunchKernelGGL(k_vox_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts, n, B.seg, n_clouds, lx, ly, lz, B.cnt,
-                       bx, by, bz, one_pass, c->d_mkeys, c->d_vals, B.rel);
+    hipLaunchKernelGGL(k_vox_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), n, B.seg.data(), n_clouds, lx, ly, lz, B.cnt.data(),
+                       bx, by, bz, one_pass, c->d_mkeys.data(), c->d_vals.data(), B.rel.data());
     const uint32_t *ord;
     if (one_pass) {
-        rc = sort_pairs<uint64_t>(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, sbits + bx + by + bz);
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, sbits + bx + by + bz);
         if (rc) return rc;
-        ord = c->d_vals2;
+        ord = c->d_vals2.data();
     } else {            // voxel key first, then the cloud: both sorts stable, so each cloud's voxels and each voxel's points keep their order
-        rc = sort_pairs<uint64_t>(c, c->d_mkeys, c->d_mkeys2, c->d_vals, c->d_vals2, (size_t)n, bx + by + bz);
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bx + by + bz);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_vox_seg_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, c->d_vals2, n, B.seg, B.head);
-        rc = sort_pairs<uint32_t>(c, B.head, B.incl, c->d_vals2, c->d_vals, (size_t)n, sbits);
+        hipLaunchKernelGGL(k_vox_seg_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, c->d_vals2.data(), n, B.seg.data(), B.head.data());
+        rc = sort_pairs<uint32_t>(c, B.head.data(), B.incl.data(), c->d_vals2.data(), c->d_vals.data(), (size_t)n, sbits);
         if (rc) return rc;
-        ord = c->d_vals;
+        ord = c->d_vals.data();
     }
-    hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg, B.rel, (uint32_t)n_clouds, B.head);
-    rc = scan(c, B.head, B.incl, (size_t)n, true);
+    hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), B.rel.data(), (uint32_t)n_clouds, B.head.data());
+    rc = scan(c, B.head.data(), B.incl.data(), (size_t)n, true);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg, (uint32_t)n_clouds, B.head, B.incl,
-                       B.start);
+    hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), (uint32_t)n_clouds, B.head.data(), B.incl.data(),
+                       B.start.data());
     // ---- one lane per voxel (at most n of them: the grids are sized for n, the lanes beyond the voxel count idle), compaction
-    hipLaunchKernelGGL(k_vox_reduce, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts, ord, n, B.seg, B.start, B.incl, p->mode,
-                       min_points, B.vout, B.keep, B.cnt);
-    rc = scan(c, B.keep, B.pos, (size_t)n, false);
+    hipLaunchKernelGGL(k_vox_reduce, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), ord, n, B.seg.data(), B.start.data(), B.incl.data(), p->mode,
+                       min_points, B.vout.data(), B.keep.data(), B.cnt.data());
+    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n, false);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_vox_write, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.vout, B.keep, B.pos, B.incl, n,
-                       packed ? nullptr : B.out, packed ? c->d_aligned : nullptr,
-                       reinterpret_cast<uint32_t *>(B.cnt + (size_t)kCnt * n_clouds));
-    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_vox_write, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.vout.data(), B.keep.data(), B.pos.data(), B.incl.data(), n,
+                       packed ? nullptr : B.out.data(), packed ? c->d_aligned.data() : nullptr,
+                       reinterpret_cast<uint32_t *>(B.cnt.data() + (size_t)kCnt * n_clouds));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt.data(), sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     for (int s = 0; s < n_clouds; ++s) {
@@ -422,7 +422,7 @@ static int voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const 
     if (r.n_out == 0) return DCREG_OK;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     const size_t bytes = sizeof(float) * 3 * (size_t)r.n_out;
-    HIP_TRY(c, hipMemcpyAsync(out, c->vox.out, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->vox.out.data(), bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
 }
