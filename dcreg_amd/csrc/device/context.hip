@@ -269,12 +269,22 @@ static bool roi_covers(const dcreg_ctx *c, const double *R, const double *t, dou
     return true;
 }
 static bool roi_wanted(const dcreg_ctx *c) { return c->opt_roi_index == 2 || (c->opt_roi_index == 1 && c->whole_capped); }
+// what a linearisation at this search radius needs of the window beyond its transformed source's box
+static double roi_pad_for(const dcreg_ctx *c, double search_radius) {
+    return std::max(search_radius, c->radius_hint) * (1.0 + c->opt_cert_margin) * 1.001 + 1e-3;
+}
+// R (9) and t (3) of n poses are all finite numbers
+static bool poses_finite(int n, const double *R9, const double *t3) {
+    for (int64_t k = 0; k < 9 * (int64_t)n; ++k) if (!std::isfinite(R9[k])) return false;
+    for (int64_t k = 0; k < 3 * (int64_t)n; ++k) if (!std::isfinite(t3[k])) return false;
+    return true;
+}
 
 // A single-pose linearisation at (R, t) with this search radius is about to be queued: make the index it should search the active one -
 // the window if the map wants one (building it around the pose when there is none that covers it), the whole map otherwise.
 static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius) {
     if (!roi_wanted(c)) return roi_deactivate(c);
-    const double pad = std::max(search_radius, c->radius_hint) * (1.0 + c->opt_cert_margin) * 1.001 + 1e-3;
+    const double pad = roi_pad_for(c, search_radius);
     if (c->roi_built && pad <= c->roi_pad && roi_covers(c, R, t, pad)) {
         if (c->roi_empty) return roi_deactivate(c);
         if (!c->roi_active) swap_index(c);
@@ -282,15 +292,18 @@ static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double sea
     }
     // ---- a new window around this pose
     (void)roi_deactivate(c);                                        // map is the whole map
+    c->roi_built = false;                                           // (from here on no box describes the window: a failed build leaves none)
     HIP_TRY(c, hipStreamSynchronize(c->stream));                    // (nothing in flight reads the buffers that are about to be replaced)
-    double lo[3], hi[3];
+    double lo[3], hi[3], blo[3], bhi[3];
     source_box_at(c, R, t, lo, hi);
     for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return DCREG_OK;          // a pose that is not a pose: the whole map, the kernels decide
-        c->roi_lo[a] = lo[a] - pad - c->opt_roi_margin; c->roi_hi[a] = hi[a] + pad + c->opt_roi_margin;
+        blo[a] = lo[a] - pad - c->opt_roi_margin; bhi[a] = hi[a] + pad + c->opt_roi_margin;
+        // a pose that is not a pose (linearize_begin refuses those; a NaN pose leaves the inverted +-1e300 box): the whole map, no window
+        if (!(std::isfinite(blo[a]) && std::isfinite(bhi[a]) && blo[a] <= bhi[a] && std::fabs(lo[a]) < 1e300 && std::fabs(hi[a]) < 1e300)) return DCREG_OK;
     }
+    for (int a = 0; a < 3; ++a) { c->roi_lo[a] = blo[a]; c->roi_hi[a] = bhi[a]; }
     c->roi_pad = pad;
-    c->roi_built = false; c->roi_empty = false;
+    c->roi_empty = false;
     // the map's points in the box: the x-runs of the whole map's (y,z) rows that cross it - contiguous ranges of its cell-sorted points (every cell
     // the box touches is taken whole: a few points more than the box holds, all of them the map's), read through the whole map's OWN index,
     // i.e. a pass over the window and not over the map
@@ -627,18 +640,12 @@ static int map_merge(dcreg_ctx *c, uint32_t n_add, uint32_t *keys, uint32_t *val
 // the whole map's index, whichever index is active (a refused or empty update must not swap them: that drops the states)
 static const IndexSet &whole_map(const dcreg_ctx *c) { return c->roi_active ? c->roi_store : c->map; }
 
-static bool finite_pose(const double *R, const double *t) {
-    for (int k = 0; k < 9; ++k) if (!std::isfinite(R[k])) return false;
-    for (int k = 0; k < 3; ++k) if (!std::isfinite(t[k])) return false;
-    return true;
-}
-
 static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, bool from_source, const double *R, const double *t,
                       double min_spacing, dcreg_map_update *info) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (!R || !t || (!from_source && (!xyz || n < 0 || stride < 3)) || !std::isfinite(min_spacing)) { c->fail("invalid insert arguments"); return DCREG_E_INVALID; }
-    if (!finite_pose(R, t)) { c->fail("the pose of an insert has non-finite entries"); return DCREG_E_INVALID; }
+    if (!poses_finite(1, R, t)) { c->fail("the pose of an insert has non-finite entries"); return DCREG_E_INVALID; }
     if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     if (from_source && c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
     const int64_t m = from_source ? c->n_src : n;
@@ -1457,6 +1464,8 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (S.pending) { c->fail("slot %d still has a linearisation in flight", slot); return DCREG_E_STATE; }
     if (!R9 || !t3 || n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
     if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    // a pose with a NaN or an infinity is refused before anything is queued or changed (the search's cell keys of such a point are undefined)
+    if (!poses_finite(n_poses, R9, t3)) { c->fail("a pose with non-finite entries"); return DCREG_E_INVALID; }
     if (!grid_ids && c->map.n <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
     dcreg_ctx::FrameSet &fs = grid_ids ? c->pair_src : c->frames;
     int64_t n_frame_max = 0;             // frames: points of the largest frame of this launch
@@ -1480,7 +1489,9 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (c->n_src <= 0) { c->fail("measure cloud is not set"); return DCREG_E_STATE; }
     if (c->need_set_device) { HIP_TRY(c, hipSetDevice(c->device)); }     // (before make_lin_args: the Euler branch allocates and copies)
     // which index the launch searches (context.hpp, the window of a large map): single-pose product launches the window around their pose, a
-    // gated launch whatever is active (its pose is checked when the gate opens), everything else the whole map
+    // gated launch whatever is active (its pose is checked when the gate opens, against the window's pad: a gated launch whose search radius
+    // needs a larger pad than the window was built with runs on the whole map), everything else the whole map
+    if (gated && c->roi_active && p && roi_pad_for(c, p->search_radius) > c->roi_pad) (void)roi_deactivate(c);
     if (!gated && !grid_ids && (c->roi_active || roi_wanted(c))) {
         if (!p) { c->fail("null argument"); return DCREG_E_INVALID; }
         const bool product = n_poses == 1 && !state_ids && (!dbg_host || stamps_only);
@@ -2406,6 +2417,7 @@ int dcreg_linearize_gated_begin(dcreg_ctx *c, int slot, const dcreg_lin_params *
 int dcreg_linearize_gate_open(dcreg_ctx *c, const double R[9], const double t[3]) {
     if (!c) return DCREG_E_INVALID;
     if (c->gate_slot < 0 || !R || !t) { c->fail("no gated linearisation waits for a pose"); return DCREG_E_STATE; }
+    if (!poses_finite(1, R, t)) { c->fail("a pose with non-finite entries: the gate still waits"); return DCREG_E_INVALID; }
     if (c->roi_active && !roi_covers(c, R, t, c->roi_pad)) {
         // the queued launch was built on a window this pose has left: it is called off; the caller starts the launch the plain way
         // (DCREG_E_STATE = "no launch waits", as after a timeout) and that builds the window around the new pose

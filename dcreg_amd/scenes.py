@@ -234,6 +234,41 @@ def scene_prior_map(n_map=50_000_000, n_frame=8_000, seed=11, extent=350.0, fram
     return tgt, body.astype(np.float32)
 
 
+def scene_sparse_map(extent=300.0, spacing=1.4, n_frame=4_000, frame_range=20.0, seed=23, offset=(0.0, 0.0, 0.0), noise=0.02):
+    """A SPARSE map for the edges of the window index: jittered grid points about `spacing` metres apart (at the defaults ~ 1.4 m, about 190
+    thousand points) on a gently undulating ground 2 * extent metres square, on 40 vertical walls (20 - 50 m long, 6 m high) and
+    on 30 poles, and a frame cut out of it by map_frames at the sensor pose (sensor 1.8 m above the ground at the square's centre + offset).
+    Every query's 5th neighbour lies a metre or more away, so a window whose box is off by a fraction of a metre at the frame's edge
+    changes the neighbours of the queries there.  -> (map [n, 3] float32, frame [m, 3] float32 in the sensor frame, sensor pose 4x4)."""
+    rng = np.random.default_rng(seed)
+    o = np.asarray(offset, np.float64)
+    g = np.arange(-extent, extent + 1e-9, spacing)
+    gx, gy = np.meshgrid(g, g, indexing="ij")
+    gx = gx.ravel() + rng.uniform(-0.3, 0.3, gx.size) * spacing
+    gy = gy.ravel() + rng.uniform(-0.3, 0.3, gy.size) * spacing
+
+    def height(x, y):
+        return 0.01 * x - 0.004 * y + 0.3 * np.sin(x * 0.07) * np.cos(y * 0.05)
+
+    parts = [np.stack([gx, gy, height(gx, gy) + rng.normal(0, 0.02, gx.size)], 1)]
+    for k in range(40):
+        c = rng.uniform(-0.9 * extent, 0.9 * extent, 2) if k >= 8 else rng.uniform(-0.8 * frame_range, 0.8 * frame_range, 2)
+        L, hd = rng.uniform(20.0, 50.0), rng.uniform(0.0, np.pi)
+        s_, z_ = np.meshgrid(np.arange(-L / 2, L / 2, spacing), np.arange(0.0, 6.0, spacing), indexing="ij")
+        s_, z_ = s_.ravel() + rng.uniform(-0.2, 0.2, s_.size), z_.ravel() + rng.uniform(-0.2, 0.2, z_.size)
+        wx, wy = c[0] + s_ * np.cos(hd), c[1] + s_ * np.sin(hd)
+        parts.append(np.stack([wx, wy, height(wx, wy) + z_], 1))
+    for k in range(30):
+        c = rng.uniform(-0.9 * extent, 0.9 * extent, 2) if k >= 10 else rng.uniform(-0.8 * frame_range, 0.8 * frame_range, 2)
+        z_ = np.arange(0.0, 5.0, 0.5 * spacing)
+        a = rng.uniform(0, 2 * np.pi, z_.size)
+        parts.append(np.stack([c[0] + 0.2 * np.cos(a), c[1] + 0.2 * np.sin(a), height(c[0], c[1]) + z_], 1))
+    tgt = (np.concatenate(parts, 0) + o).astype(np.float32)
+    T = pose6d_matrix(o[0], o[1], o[2] + height(0.0, 0.0) + 1.8, 0.0, 0.0, 0.0)
+    frame = map_frames(tgt, [T], n_frame, seed=seed + 1, frame_range=frame_range, noise=noise)[0]
+    return tgt, frame, T
+
+
 def map_frames(tgt, poses, n_frame=8_000, seed=0, frame_range=30.0, noise=0.02):
     """Frames cut out of an existing map at given sensor poses, with the recipe of the frame of scene_parkinglot / scene_prior_map: for pose
     T (4x4, sensor -> map), up to n_frame map points within frame_range metres (in x-y) of T's position, expressed in the sensor frame by

@@ -151,6 +151,7 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   the local density.  Built by the first linearisation (about 4 ms, whatever the map's size), kept until a
  *                   pose leaves the box, then rebuilt around that pose (a queued gated launch is called off: dcreg_linearize_gate_open
  *                   returns DCREG_E_STATE and the caller starts the launch with dcreg_linearize_batch_begin, as the engines do).
+ *                   A gated launch whose search radius needs more of the box than the window was built for runs on the whole map.
  *                   roi_index 1 (default) = for maps whose cell edge the budget enlarged by more than one step (x 1.26) or whose x sub-cells it took, 0 = never, 2 = always.  dcreg_knn,
  *                   dcreg_p2p_error, batched launches and debug dumps always run on the whole map; dcreg_index_info_get describes
  *                   the whole map's index (dcreg_debug.h dcreg_roi_info: the window).
@@ -173,7 +174,11 @@ int dcreg_set_target_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t 
 int dcreg_set_source(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats);
 int dcreg_set_source_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats);
 int dcreg_default_lin_params(dcreg_lin_params *, double search_radius);
-/* one ICP linearisation (steps 1-5): R row-major 3x3, t 3 */
+/* one ICP linearisation (steps 1-5): R row-major 3x3, t 3.
+ * Every launch at a caller's pose - dcreg_linearize, _batch, _batch_begin[_warm], dcreg_frames_batch_begin, dcreg_pairs_batch_begin,
+ * dcreg_linearize_debug, the engines' initial poses - refuses a pose with a NaN or an infinity anywhere in R or t (of any of its n_poses)
+ * with DCREG_E_INVALID before anything is queued: warm states, window index and gate stay as they were.  dcreg_linearize_gate_open
+ * refuses such a pose the same way and leaves the gate waiting (open it again with a finite pose, or abort it). */
 int dcreg_linearize(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
 /* the same for n_poses independent poses of the same cloud pair in ONE launch (Monte-Carlo trials) */
 int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *,
