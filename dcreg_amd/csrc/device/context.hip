@@ -1503,7 +1503,8 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     if (rc) return rc;
     if (frame_ids) a.count_scale = n_frame_max < ((int64_t)1 << 26) ? kCountScale : 0.0;     // (make_lin_args: of the ctx's own source)
     // the parameters the stored certificates, gate bits and planes depend on (context.hpp StateKey): a launch with other values
-    // starts from empty states
+    // starts from empty states.  (weight_slope, weight_min and use_weight_derivative are not among them: the weight gate and the row
+    // are evaluated on the stored plane in every launch - tests/test_gpu_gate_edges.py alternates them on one context.)
     dcreg_ctx::StateKey key;
     key.radius_sq = a.radius_sq; key.max_thick_sq = a.max_thick_sq; key.min_norm = a.min_norm;
     key.radius_sq_f = a.radius_sq_f; key.cert_r_out = a.cert_r_out; key.cert_r_in = a.cert_r_in; key.fast_plane = c->opt_fast_plane ? 1 : 0;

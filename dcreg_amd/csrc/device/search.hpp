@@ -965,6 +965,9 @@ DCREG_DEVFN void knn_exact(const GridDev &g, RunList &rl, float qx, float qy, fl
 // Restates Eigen 3.3.7 ColPivHouseholderQR::compute + solve (icp_test_runner.cpp:1747) for [q_j] x = -1,
 // including the nonzeroPivots() truncation that decides rank-deficient (coplanar-with-origin / constant-
 // zero column) neighbourhoods.  Columns are swapped with selects so everything stays in registers.
+// Operation for operation the oracle's orc_colpiv_qr_solve (the parity instantiation's gate flags are bitwise the oracle's): the
+// essential part of a reflector is DIVIDED by (c0 - beta), the reflector is applied in Eigen's applyHouseholderOnTheLeft order
+// (products first, the head row last), and nothing is contracted to FMA (the oracle is built with -ffp-contract=off).
 DCREG_DEVFN void swap_col(double (&a)[5], double (&b)[5], bool doit) {
 #pragma unroll
     for (int i = 0; i < 5; ++i) { const double ta = a[i], tb = b[i]; a[i] = doit ? tb : ta; b[i] = doit ? ta : tb; }
@@ -976,6 +979,7 @@ template <int KCOL>
 DCREG_DEVFN void householder_step(double (&c0)[5], double (&c1)[5], double (&c2)[5], double (&tau)[3],
                                                  double (&nu)[3], double (&nd)[3]) {
     // acts on column KCOL (rows KCOL..4) and updates the trailing columns; c0,c1,c2 are the CURRENT columns
+#pragma clang fp contract(off)
     double(&ck)[5] = (KCOL == 0) ? c0 : (KCOL == 1 ? c1 : c2);
     double tail = 0.0;
 #pragma unroll
@@ -989,9 +993,9 @@ DCREG_DEVFN void householder_step(double (&c0)[5], double (&c1)[5], double (&c2)
     } else {
         beta = sqrt(a0 * a0 + tail);
         if (a0 >= 0.0) beta = -beta;
-        const double inv_den = 1.0 / (a0 - beta);      // one reciprocal + multiplies (fp64 division is ~11 instructions)
+        const double den = a0 - beta;
 #pragma unroll
-        for (int i = KCOL + 1; i < 5; ++i) ck[i] = ck[i] * inv_den;
+        for (int i = KCOL + 1; i < 5; ++i) ck[i] = ck[i] / den;
         t = (beta - a0) / beta;
     }
     tau[KCOL] = t;
@@ -1000,9 +1004,10 @@ DCREG_DEVFN void householder_step(double (&c0)[5], double (&c1)[5], double (&c2)
     for (int j = KCOL + 1; j < 3; ++j) {
         double(&cj)[5] = (j == 1) ? c1 : c2;
         if (t != 0.0) {
-            double tmp = cj[KCOL];
+            double tmp = 0.0;
 #pragma unroll
             for (int i = KCOL + 1; i < 5; ++i) tmp += ck[i] * cj[i];
+            tmp += cj[KCOL];
             cj[KCOL] -= t * tmp;
 #pragma unroll
             for (int i = KCOL + 1; i < 5; ++i) cj[i] -= t * ck[i] * tmp;
@@ -1026,6 +1031,7 @@ DCREG_DEVFN void householder_step(double (&c0)[5], double (&c1)[5], double (&c2)
 
 // returns x (plane coefficients, unnormalised); Q row j = neighbour j
 DCREG_DEVFN void plane_fit_qr(const double (&qx)[5], const double (&qy)[5], const double (&qz)[5], double (&x)[3]) {
+#pragma clang fp contract(off)
     double c0[5], c1[5], c2[5], tau[3], nu[3], nd[3];
     int p0 = 0, p1 = 1, p2 = 2;
 #pragma unroll
@@ -1109,7 +1115,8 @@ DCREG_DEVFN void plane_fit_qr(const double (&qx)[5], const double (&qy)[5], cons
 //   * reciprocal and square root by v_rcp_f64 / v_rsq_f64 + Newton steps without the IEEE corner-case scaffolding (the
 //     operands are coordinates in metres: no denormals, no overflow).
 // Result: the plane of plane_fit_qr to a few ulp (tests: normals / residuals / weights of the fixture, incl. its 751
-// rank-2 neighbourhoods, and of the synthetic scenes against the oracle; gate flags bit-exact).
+// rank-2 neighbourhoods, and of the synthetic scenes against the oracle).  Its gate flags can differ from the oracle's for a point
+// within a small band of a threshold (dcreg.h fast_plane_fit gives the band; tests/test_gpu_gate_edges.py measures it).
 DCREG_DEVFN double fast_rcp(double x) {
 #if DCREG_ON_DEVICE
     double r = __builtin_amdgcn_rcp(x);
@@ -1652,6 +1659,36 @@ DCREG_DEVFN unsigned long long team_search6(const GridDev &g, TeamLds &T, const 
 #endif
 
 
+// The normalisation and the two neighbour-only gates of the parity instantiation, as orc_plane_fit / orc_point_row write them: n = x / ps,
+// d = 1 / ps, every product and sum rounded on its own (no FMA contraction), so that a plane within rounding of a gate's threshold
+// gets the oracle's flag.
+// plane_normal_exact: {n, d} of x and returns |x| (orc_plane_fit's n_out, d_out, ps_out where ps > 0)
+DCREG_DEVFN double plane_normal_exact(const double (&x)[3], double (&plane)[4]) {
+#pragma clang fp contract(off)
+    const double ps = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    plane[0] = x[0] / ps; plane[1] = x[1] / ps; plane[2] = x[2] / ps; plane[3] = 1.0 / ps;
+    return ps;
+}
+DCREG_DEVFN uint8_t plane_gates_exact(const LinArgs &a, const double (&x)[3], const double (&nqx)[5], const double (&nqy)[5],
+                                      const double (&nqz)[5], double (&plane)[4]) {
+#pragma clang fp contract(off)
+    double n[4];
+    const double ps = plane_normal_exact(x, n);
+    plane[0] = plane[1] = plane[2] = plane[3] = 0.0;
+    if (ps < a.min_norm) return 2;                                          // :1752
+    const double pa = n[0], pb = n[1], pc = n[2], pd = n[3];
+    double maxd = 0.0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {                                           // :1763-1770
+        double d = pa * nqx[j] + pb * nqy[j] + pc * nqz[j] + pd;
+        d *= d;
+        maxd = d > maxd ? d : maxd;
+    }
+    plane[0] = pa; plane[1] = pb; plane[2] = pc; plane[3] = pd;
+    if (!(maxd < a.max_thick_sq)) return 3;                                 // :1773
+    return 0;
+}
+
 // Steps 3-4a for one query with its ordered neighbour set (icp_test_runner.cpp:1727-1773): plane fit and the two gates that depend on
 // the neighbours alone.  plane = {a, b, c, d} of a x + b y + c z + d = 0 with |(a,b,c)| = 1.  Returns 0 (ok), 2 (|x| < min_normal_norm,
 // :1752) or 3 (plane thickness, :1773).  The plane is a function of the five points and their ORDER only - not of the query -, which
@@ -1662,12 +1699,17 @@ DCREG_DEVFN uint8_t plane_of_set(const LinArgs &a, const KnnResult<5> &nn, doubl
 #pragma unroll
     for (int j = 0; j < 5; ++j) { nqx[j] = nn.pt[j].x; nqy[j] = nn.pt[j].y; nqz[j] = nn.pt[j].z; }
     double x[3];
-    if (FASTMATH) plane_fit_qr_fast(nqx, nqy, nqz, x); else plane_fit_qr(nqx, nqy, nqz, x);
+    if constexpr (!FASTMATH) {
+        plane_fit_qr(nqx, nqy, nqz, x);
+        return plane_gates_exact(a, x, nqx, nqy, nqz, plane);
+    }
+    // the fast instantiation only from here
+    plane_fit_qr_fast(nqx, nqy, nqz, x);
     const double ps2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    const double ps = FASTMATH ? fast_sqrt(ps2) : sqrt(ps2);
+    const double ps = fast_sqrt(ps2);
     plane[0] = plane[1] = plane[2] = plane[3] = 0.0;
     if (ps < a.min_norm) return 2;                                          // :1752
-    const double pd = FASTMATH ? fast_rcp(ps) : 1.0 / ps;
+    const double pd = fast_rcp(ps);
     const double pa = x[0] * pd, pb = x[1] * pd, pc = x[2] * pd;
     double maxd = 0.0;
 #pragma unroll
@@ -1696,15 +1738,12 @@ DCREG_DEVFN double euler_entry(const double *D, double c0, double c1, double c2,
     return b0 * c0 + b1 * c1 + b2 * c2;
 }
 
-template <bool FASTMATH>
-DCREG_DEVFN uint8_t row_of_plane(const PoseArg &P, const LinArgs &a, const float4 &s4, float qxf, float qyf, float qzf, const double (&plane)[4],
-                                 double (&row)[8], double (&nrm)[3], double &r_out, double &s_out) {
-    float sxf = s4.x, syf = s4.y, szf = s4.z;
-#if DCREG_ON_DEVICE
-    asm volatile("" : "+v"(sxf), "+v"(syf), "+v"(szf));   // re-convert instead of keeping doubles alive across the search
-    asm volatile("" : "+v"(qxf), "+v"(qyf), "+v"(qzf));
-#endif
-    const double px = sxf, py = syf, pz = szf;
+// row_of_plane of the parity instantiation: orc_point_row's arithmetic as written - n = c / s recovered by division, every product and
+// sum rounded on its own (no FMA contraction) -, so that r, s, the weight gate and the float stores are bitwise the oracle's.  The
+// formulas are row_of_plane's (below): a change to one belongs in both.
+DCREG_DEVFN uint8_t row_of_plane_exact(const PoseArg &P, const LinArgs &a, double px, double py, double pz, float qxf, float qyf, float qzf,
+                                       const double (&plane)[4], double (&row)[8], double (&nrm)[3], double &r_out, double &s_out) {
+#pragma clang fp contract(off)
     const double pa = plane[0], pb = plane[1], pc = plane[2], pd = plane[3];
     const double r = pa * (double)qxf + pb * (double)qyf + pc * (double)qzf + pd;   // :1774
     double s = 1.0 - a.w_slope * fabs(r);                                   // :1776
@@ -1715,7 +1754,50 @@ DCREG_DEVFN uint8_t row_of_plane(const PoseArg &P, const LinArgs &a, const float
     if (!(s > a.w_min)) return 4;                                           // :1785
     const float cxf = (float)(s * pa), cyf = (float)(s * pb), czf = (float)(s * pc);   // :1787-1789
     const float cif = (float)(s * r);                                                    // :1790
-    const double inv_s = FASTMATH ? fast_rcp(s) : 1.0 / s;
+    const double nx = (double)cxf / s, ny = (double)cyf / s, nz = (double)czf / s;      // :1889
+    double A[6];
+    if (!a.euler) {
+        const double m0 = P.R[0] * nx + P.R[3] * ny + P.R[6] * nz;
+        const double m1 = P.R[1] * nx + P.R[4] * ny + P.R[7] * nz;
+        const double m2 = P.R[2] * nx + P.R[5] * ny + P.R[8] * nz;
+        const double w = s + r * ds;                                                     // :1898
+        A[0] = w * (py * m2 - pz * m1); A[1] = w * (pz * m0 - px * m2); A[2] = w * (px * m1 - py * m0);
+        A[3] = w * m0; A[4] = w * m1; A[5] = w * m2;
+    } else {
+        const double c0 = (double)cxf, c1 = (double)cyf, c2 = (double)czf;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) A[k] = euler_entry(a.dR + 9 * k, c0, c1, c2, px, py, pz);
+        A[3] = c0; A[4] = c1; A[5] = c2;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) row[j] = A[j];
+    row[6] = -(double)cif;                                                               // :1906
+    row[7] = r;
+    return 1;
+}
+
+template <bool FASTMATH>
+DCREG_DEVFN uint8_t row_of_plane(const PoseArg &P, const LinArgs &a, const float4 &s4, float qxf, float qyf, float qzf, const double (&plane)[4],
+                                 double (&row)[8], double (&nrm)[3], double &r_out, double &s_out) {
+    float sxf = s4.x, syf = s4.y, szf = s4.z;
+#if DCREG_ON_DEVICE
+    asm volatile("" : "+v"(sxf), "+v"(syf), "+v"(szf));   // re-convert instead of keeping doubles alive across the search
+    asm volatile("" : "+v"(qxf), "+v"(qyf), "+v"(qzf));
+#endif
+    const double px = sxf, py = syf, pz = szf;
+    if constexpr (!FASTMATH) return row_of_plane_exact(P, a, px, py, pz, qxf, qyf, qzf, plane, row, nrm, r_out, s_out);
+    // the fast instantiation only from here; row_of_plane_exact holds the same formulas - a change to one belongs in both
+    const double pa = plane[0], pb = plane[1], pc = plane[2], pd = plane[3];
+    const double r = pa * (double)qxf + pb * (double)qyf + pc * (double)qzf + pd;   // :1774
+    double s = 1.0 - a.w_slope * fabs(r);                                   // :1776
+    s = s < 0.0 ? 0.0 : s;
+    double ds = 0.0;
+    if (a.use_wd && s > 0.0 && s < 1.0) ds = -a.w_slope * (r > 0.0 ? 1.0 : -1.0);   // :1780-1783
+    nrm[0] = pa; nrm[1] = pb; nrm[2] = pc; r_out = r; s_out = s;
+    if (!(s > a.w_min)) return 4;                                           // :1785
+    const float cxf = (float)(s * pa), cyf = (float)(s * pb), czf = (float)(s * pc);   // :1787-1789
+    const float cif = (float)(s * r);                                                    // :1790
+    const double inv_s = fast_rcp(s);
     const double nx = (double)cxf * inv_s, ny = (double)cyf * inv_s, nz = (double)czf * inv_s;   // :1889
     double A[6];
     if (!a.euler) {

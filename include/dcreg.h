@@ -117,7 +117,7 @@ const char *dcreg_last_error(const dcreg_ctx *);
  * dcreg_set_*_device order themselves after the work queued on the null stream instead (below).  Like every call that queues work,
  * refused (DCREG_E_STATE) while a linearisation is in flight (dcreg_linearize_gated_begin, dcreg_linearize_batch_begin). */
 int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
-/* options (every one of them changes speed only: results are identical whatever their values)
+/* options (every one of them but fast_plane_fit changes speed only: results are identical whatever their values)
  *   "warm_start"    1 (default) = keep, per source point, the neighbours its last search found and a certificate of how far the
  *                   point may move before the nearest five can change; later linearisations skip the search of every point whose
  *                   certificate still holds and bound the searches that remain by the old neighbours.  0 = search every point
@@ -126,8 +126,13 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   be certified too (takes effect at the next dcreg_set_target: the grid cells follow the search radius);
  *   "cert_inflate"  default 0.005: searches among nearby points look 0.5 % further than they must, which yields the second kind of
  *                   certificate ("the five nearest are among these six"; search.hpp);
- *   "fast_plane_fit" 1 (default) = the reduced-instruction 5x3 plane fit; 0 = the Eigen-shaped factorisation step for step (planes
- *                   agree to a few ulp, gate flags are identical on every test scene);
+ *   "fast_plane_fit" 1 (default) = the reduced-instruction 5x3 plane fit; 0 = the Eigen-shaped factorisation operation for operation,
+ *                   as the oracle computes it: its planes, residuals, weights and gate flags are bitwise the oracle's.  The fast fit's
+ *                   planes agree with those to a few ulp, so its gate flags can differ from the oracle's for a point whose normal norm,
+ *                   plane thickness or weight lies within 1e-11 relative of its threshold (measured on an MI355X for points up to
+ *                   50 m out: flips at up to 5e-13 for the thickness gate, 5e-14 for the weight and 6e-17 for the normal norm, none
+ *                   at 5e-12 or beyond; tests/test_gpu_gate_edges.py); a flag that differs changes n_eff and everything after it.
+ *                   See DESIGN.md;
  *   "spin"          1 (default) = wait for results on the pinned result flags instead of hipStreamSynchronize;
  *   "wait_seconds"  default 30: how long a result is awaited before the stream is drained to look for a device fault;
  *   "dispatch_order" 1 (default) = launches with more query blocks than the device holds at once hand them out heaviest group

@@ -176,6 +176,14 @@ def default_lin_params(search_radius=1.0, use_weight_derivative=0, num_threads=0
     return p
 
 
+def plane_fit(Q):
+    """orc_plane_fit of five neighbours (rows of Q) -> (n[3], d, ps): the plane of [q_j] x = -1, n = x / |x|, d = 1 / |x|, ps = |x|."""
+    Q = np.ascontiguousarray(Q, np.float64).reshape(15)
+    n, d, ps = np.empty(3), np.empty(1), np.empty(1)
+    lib().orc_plane_fit(_dp(Q), _dp(n), _dp(d), _dp(ps))
+    return n, float(d[0]), float(ps[0])
+
+
 class KdTree:
     """Owns an oracle kd-tree over a float32 [n,3] target cloud."""
 

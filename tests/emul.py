@@ -47,6 +47,7 @@ def lib():
         L.emu_linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LinParams),
                                     C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_void_p, C.c_int64, C.c_void_p]
         L.emu_plane_fit.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.emu_plane_fit_nd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.emu_ball_query.restype = C.c_int64
         L.emu_ball_query.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.emu_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
@@ -70,6 +71,14 @@ def plane_fit(Q, fast):
     x = np.empty(3)
     lib().emu_plane_fit(_ptr(Q), int(fast), _ptr(x))
     return x
+
+
+def plane_fit_nd(Q):
+    """The parity instantiation's plane of five neighbours, as orc_plane_fit returns it -> (n[3], d, ps): n = x / |x|, d = 1 / |x|, ps = |x|."""
+    Q = np.ascontiguousarray(Q, np.float64).reshape(5, 3)
+    n, d, ps = np.empty(3), np.empty(1), np.empty(1)
+    lib().emu_plane_fit_nd(_ptr(Q), _ptr(n), _ptr(d), _ptr(ps))
+    return n, float(d[0]), float(ps[0])
 
 
 CERT_MARGIN = 0.05      # dcreg_ctx::opt_cert_margin
@@ -146,13 +155,13 @@ class Source:
 
 
 def linearize(index, source, R, t, radius=None, wd=0, fast=True, warm=True, debug=False, stats=False, trace_cap=0, cert_move=CERT_MOVE,
-              plan=None, cert_inflate=CERT_INFLATE):
+              plan=None, cert_inflate=CERT_INFLATE, max_thick_sq=0.2 * 0.2, min_norm=1e-6, w_slope=0.9, w_min=0.1):
     """One linearisation through the device functions on the host -> dict like Context.linearize (+ "stats" [n, 8] in
     processing order: candidates, outermost shell, table loads, rows, runs, trips, faces, face skips).
     plan: None = as context.hip decides ("full" on a fresh state / debug / a pose change that may move a point farther than cert_move
     cells, else "cert"), or force "full" / "cert" (a fresh state is always searched in full)."""
     radius = index.radius if radius is None else radius
-    prm = LinParams(radius, 0.2 * 0.2, 1e-6, 0.9, 0.1, int(wd), int(fast), index.cert_margin, cert_inflate)
+    prm = LinParams(radius, max_thick_sq, min_norm, w_slope, w_min, int(wd), int(fast), index.cert_margin, cert_inflate)
     n = source.n
     fresh = source.state is None or source.prev_index is not index      # a new target voids positions and certificates
     if warm and fresh:

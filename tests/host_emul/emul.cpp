@@ -539,4 +539,14 @@ void emu_plane_fit(const double *Q, int fast, double x[3]) {
     x[0] = y[0]; x[1] = y[1]; x[2] = y[2];
 }
 
+// the parity instantiation's plane as orc_plane_fit returns it: n = x / |x|, d = 1 / |x|, ps = |x|
+void emu_plane_fit_nd(const double *Q, double n[3], double *d, double *ps) {
+    double qx[5], qy[5], qz[5];
+    for (int j = 0; j < 5; ++j) { qx[j] = Q[3 * j]; qy[j] = Q[3 * j + 1]; qz[j] = Q[3 * j + 2]; }
+    double x[3], plane[4];
+    plane_fit_qr(qx, qy, qz, x);
+    *ps = plane_normal_exact(x, plane);
+    n[0] = plane[0]; n[1] = plane[1]; n[2] = plane[2]; *d = plane[3];
+}
+
 }  // extern "C"

@@ -29,25 +29,8 @@ def _frame_poses(gt, n, seed, step=6.0):
     return T, T0
 
 
-def _single(ctx, frame, T0, method, cfg):
-    """the record dcreg_register_frames promises for one frame: dcreg_set_source + dcreg_icp_run"""
-    ctx.set_source(frame)
-    res, logs = ctx.icp_run(T0, method, cfg)
-    T = np.eye(4)
-    T[:3, :3] = np.array(res.R[:]).reshape(3, 3)
-    T[:3, 3] = res.t[:]
-    last = logs[-1] if logs else None
-    return dict(T=T.reshape(16), iterations=res.iterations, converged=res.converged, status=res.status,
-                rmse=last.rmse if last else 0.0, fitness=last.fitness if last else 0.0, corr=last.effective_points if last else 0,
-                H=np.array(last.H_upper[:]) if last else np.zeros(21), mask=list(last.analysis.degenerate_mask[:]) if last else [0] * 6,
-                trans_err=last.trans_error_vs_gt if last else None)
-
-
-def _assert_record(tr, s, what):
-    assert (tr.iterations, tr.converged, tr.status) == (s["iterations"], s["converged"], s["status"]), what
-    assert np.array_equal(np.array(tr.final_transform[:]), s["T"]), what
-    assert tr.final_rmse == s["rmse"] and tr.final_fitness == s["fitness"] and tr.corr_num == s["corr"], what
-    assert np.array_equal(np.array(tr.H_upper[:]), s["H"]) and list(tr.degenerate_mask[:]) == s["mask"], what
+_single = h.single_registration          # (test_gpu_pairs imports these two from here)
+_assert_record = h.assert_record
 
 
 @pytest.fixture(scope="module")
