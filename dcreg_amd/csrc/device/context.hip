@@ -970,7 +970,7 @@ static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const doub
     c->n_src = n;
     {   // dispatch groups of the single-pose launches (kernels.hpp k_group_cost): multiples of 16 query blocks, at most kMaxGroups of them
         const uint32_t nb = blocks_for(n, kLinBlock);
-        const uint32_t gq = 16u;                  // one XCD's run of query blocks (opt_xcd_chunk)
+        const uint32_t gq = 16u;                  // one XCD's run of query blocks (kXcdChunk)
         c->group_blocks = gq * std::max<uint32_t>(1u, (nb + gq * kMaxGroups - 1) / (gq * kMaxGroups));
         c->n_groups = std::min<uint32_t>(nb / c->group_blocks, (uint32_t)kMaxGroups);
         c->order_valid = false;                   // estimated at the pose of the next single-pose linearisation
@@ -1295,83 +1295,86 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
 }
 
 // ------------------------------------------------------------------------------------------ linearise
+// settled rules, once options (dcreg_debug.h "Settled and no longer options")
+constexpr uint32_t kXcdChunk = 16;    // query-block -> XCD mapping (kernels.hpp xcd_remap): runs of 16 blocks round-robin (measured: C4 -13 %)
+constexpr double kFarLoose = 1.5;     // search.hpp lin_search6: when a start bound is loose enough to be worth a probe (cells)
+
+// the kernel arguments of checked parameters (lin_check) for a source of n points per pose (the Euler coefficients: stage_euler);
 // own_grid = false: the launch searches grids of its own (dcreg_register_pairs: LinArgs::max_ring and infl_max_d2 come with every pose's grid)
-static int make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a, bool own_grid = true) {
-    if (!p || !(p->search_radius > 0.0)) { c->fail("invalid linearisation parameters"); return DCREG_E_INVALID; }
-    if (p->k != 5 && p->k != 0) { c->fail("only k = 5 is supported (icp_test_runner.cpp:1722)"); return DCREG_E_INVALID; }
+static LinArgs make_lin_args(dcreg_ctx *c, const dcreg_lin_params *p, bool own_grid, int64_t n) {
+    LinArgs a{};
     a.radius_sq = p->search_radius * p->search_radius;
-    {
-        a.radius_sq_f = search_bound_sq(c, p->search_radius);
-        float ro = (float)(p->search_radius * (1.0 + 1e-5));
-        if ((double)ro < p->search_radius * (1.0 + 1e-5)) ro = std::nextafterf(ro, INFINITY);
-        a.cert_r_out = ro;
-        float ri = (float)(p->search_radius * (1.0 - 1e-5));
-        if ((double)ri > p->search_radius * (1.0 - 1e-5)) ri = std::nextafterf(ri, 0.0f);
-        a.cert_r_in = ri;
-    }
+    a.radius_sq_f = search_bound_sq(c, p->search_radius);
+    float ro = (float)(p->search_radius * (1.0 + 1e-5));
+    if ((double)ro < p->search_radius * (1.0 + 1e-5)) ro = std::nextafterf(ro, INFINITY);
+    a.cert_r_out = ro;
+    float ri = (float)(p->search_radius * (1.0 - 1e-5));
+    if ((double)ri > p->search_radius * (1.0 - 1e-5)) ri = std::nextafterf(ri, 0.0f);
+    a.cert_r_in = ri;
     a.max_thick_sq = p->max_plane_thickness_sq; a.min_norm = p->min_normal_norm;
     a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
     a.warm = c->opt_warm ? 1 : 0;
     a.team_max = std::min(std::max(c->opt_team_max, 0), kTeamMax);
-    a.far_loose = (float)c->opt_far_loose;
+    a.far_loose = (float)kFarLoose; a.xcd_chunk = kXcdChunk;
     a.prune_infl = (float)((1.0 + c->opt_cert_inflate) * (1.0 + c->opt_cert_inflate));
     a.infl_max_d2 = own_grid ? (float)(4.0 * c->map.grid.h * c->map.grid.h) : 0.f;
     a.max_ring = own_grid ? rings_for(c->map.grid.h, a.radius_sq_f) : 0;
     if (own_grid) c->last_max_ring = a.max_ring;
-    a.count_scale = c->n_src < ((int64_t)1 << 26) ? kCountScale : 0.0;      // (strictly below: a count of 2^26 would read as one more of the number riding above it)
-    a.euler = p->parameterization != DCREG_PARAM_SO3 ? 1 : 0;
-    if (p->parameterization != DCREG_PARAM_SO3 && p->parameterization != DCREG_PARAM_EULER && p->parameterization != DCREG_PARAM_EULER_EXACT) { c->fail("unknown parameterization"); return DCREG_E_INVALID; }
-    a.dR = nullptr;
-    if (a.euler) {
-        // The kernel's Euler branch (search.hpp row_of_plane) evaluates, for k = 0 (roll column) / 1 (pitch) / 2 (yaw),
-        //     A[k] = c.x (D[9k+0] p.y + D[9k+1] p.z + D[9k+2] p.x) + c.y (D[9k+3] p.y + ...) + c.z (D[9k+6] p.y + ...)
-        // - the shape of icp_test_runner.cpp:2323-2335 with its axis relabelling (pointOri = (p.y, p.z, p.x), coeff = (c.y, c.z, c.x)) undone for c
-        // and kept for p, so that every product and every sum is taken in the order of the source text.  The 27 coefficients come from here.
-        if (!c->h_euler) {
-            HIP_TRY(c, c->h_euler.alloc(27, hipHostMallocDefault));
-            HIP_TRY(c, c->d_euler.alloc(27));
-        }
-        // (the staging block is reused: the launches of the Euler engine are blocking calls, one at a time)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        double *D = c->h_euler.data();
-        if (p->parameterization == DCREG_PARAM_EULER) {
-            // the reference's row, literally (:2299-2346): srx / crx of PITCH, sry / cry of YAW, srz / crz of ROLL; the brackets of arx times coeff.z,
-            // coeff.x, coeff.y (LOAM: x, y, z), of ary times coeff.z, coeff.y, of arz times coeff.z, coeff.x, coeff.y; matA row = [arz, arx, ary, ...]
-            const double srx = std::sin(p->euler_rpy[1]), crx = std::cos(p->euler_rpy[1]);
-            const double sry = std::sin(p->euler_rpy[2]), cry = std::cos(p->euler_rpy[2]);
-            const double srz = std::sin(p->euler_rpy[0]), crz = std::cos(p->euler_rpy[0]);
-            const double crx_sry = crx * sry, crz_sry = crz * sry, srx_sry = srx * sry, srx_srz = srx * srz;   // :2319-2322
-            // arz (:2331-2335) -> column 0
-            D[0] = crz * srx_sry - cry * srz;   D[1] = -cry * crz - srx_sry * srz;   D[2] = 0.0;      // x coeff.z (= c.x)
-            D[3] = crx * crz;                   D[4] = -(crx * srz);                 D[5] = 0.0;      // x coeff.x (= c.y)
-            D[6] = sry * srz + cry * crz * srx; D[7] = crz_sry - cry * srx_srz;      D[8] = 0.0;      // x coeff.y (= c.z)
-            // arx (:2323-2326) -> column 1
-            D[9] = crx_sry * srz;               D[10] = crx * crz_sry;               D[11] = -srx_sry;        // x coeff.z
-            D[12] = -srx_srz;                   D[13] = -(crz * srx);                D[14] = -crx;            // x coeff.x
-            D[15] = crx * cry * srz;            D[16] = crx * cry * crz;             D[17] = -(cry * srx);    // x coeff.y
-            // ary (:2327-2330) -> column 2 (no coeff.x bracket)
-            D[18] = cry * srx_srz - crz_sry;    D[19] = sry * srz + cry * crz * srx; D[20] = crx * cry;       // x coeff.z
-            D[21] = 0.0;                        D[22] = 0.0;                         D[23] = 0.0;
-            D[24] = -cry * crz - srx_sry * srz; D[25] = cry * srz - crz * srx_sry;   D[26] = -crx_sry;        // x coeff.y
-        } else {
-            // exact derivatives of R = Rz(yaw) Ry(pitch) Rx(roll) (Pose6D2Matrix, utils.hpp:452-460), columns in the kernel's (p.y, p.z, p.x) order
-            const double cr = std::cos(p->euler_rpy[0]), sr = std::sin(p->euler_rpy[0]);
-            const double cp = std::cos(p->euler_rpy[1]), sp = std::sin(p->euler_rpy[1]);
-            const double cy = std::cos(p->euler_rpy[2]), sy = std::sin(p->euler_rpy[2]);
-            const double Rx[9] = {1, 0, 0, 0, cr, -sr, 0, sr, cr}, dRx[9] = {0, 0, 0, 0, -sr, -cr, 0, cr, -sr};
-            const double Ry[9] = {cp, 0, sp, 0, 1, 0, -sp, 0, cp}, dRy[9] = {-sp, 0, cp, 0, 0, 0, -cp, 0, -sp};
-            const double Rz[9] = {cy, -sy, 0, sy, cy, 0, 0, 0, 1}, dRz[9] = {-sy, -cy, 0, cy, -sy, 0, 0, 0, 0};
-            auto mul3 = [](const double *A, const double *B, const double *C3, double *out) {
-                double T[9], O[9];
-                for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i * 3 + k] * B[k * 3 + j]; T[i * 3 + j] = s; }
-                for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += T[i * 3 + k] * C3[k * 3 + j]; O[i * 3 + j] = s; }
-                for (int i = 0; i < 3; ++i) { out[i * 3 + 0] = O[i * 3 + 1]; out[i * 3 + 1] = O[i * 3 + 2]; out[i * 3 + 2] = O[i * 3 + 0]; }
-            };
-            mul3(Rz, Ry, dRx, D); mul3(Rz, dRy, Rx, D + 9); mul3(dRz, Ry, Rx, D + 18);
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->d_euler.data(), c->h_euler.data(), 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        a.dR = c->d_euler.data();
+    a.count_scale = n < ((int64_t)1 << 26) ? kCountScale : 0.0;      // (strictly below: a count of 2^26 would read as one more of the number riding above it)
+    a.euler = p->parameterization != DCREG_PARAM_SO3 ? 1 : 0;      // (dR, state, adv_counts: null until lin_reserve and the state selection)
+    return a;
+}
+
+static int stage_euler(dcreg_ctx *c, const dcreg_lin_params *p, LinArgs &a) {
+    if (!a.euler) return DCREG_OK;
+    // The kernel's Euler branch (search.hpp row_of_plane) evaluates, for k = 0 (roll column) / 1 (pitch) / 2 (yaw),
+    //     A[k] = c.x (D[9k+0] p.y + D[9k+1] p.z + D[9k+2] p.x) + c.y (D[9k+3] p.y + ...) + c.z (D[9k+6] p.y + ...)
+    // - the shape of icp_test_runner.cpp:2323-2335 with its axis relabelling (pointOri = (p.y, p.z, p.x), coeff = (c.y, c.z, c.x)) undone for c
+    // and kept for p, so that every product and every sum is taken in the order of the source text.  The 27 coefficients come from here.
+    if (!c->h_euler) {
+        HIP_TRY(c, c->h_euler.alloc(27, hipHostMallocDefault));
+        HIP_TRY(c, c->d_euler.alloc(27));
     }
+    // (the staging block is reused: the launches of the Euler engine are blocking calls, one at a time)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    double *D = c->h_euler.data();
+    if (p->parameterization == DCREG_PARAM_EULER) {
+        // the reference's row, literally (:2299-2346): srx / crx of PITCH, sry / cry of YAW, srz / crz of ROLL; the brackets of arx times coeff.z,
+        // coeff.x, coeff.y (LOAM: x, y, z), of ary times coeff.z, coeff.y, of arz times coeff.z, coeff.x, coeff.y; matA row = [arz, arx, ary, ...]
+        const double srx = std::sin(p->euler_rpy[1]), crx = std::cos(p->euler_rpy[1]);
+        const double sry = std::sin(p->euler_rpy[2]), cry = std::cos(p->euler_rpy[2]);
+        const double srz = std::sin(p->euler_rpy[0]), crz = std::cos(p->euler_rpy[0]);
+        const double crx_sry = crx * sry, crz_sry = crz * sry, srx_sry = srx * sry, srx_srz = srx * srz;   // :2319-2322
+        // arz (:2331-2335) -> column 0
+        D[0] = crz * srx_sry - cry * srz;   D[1] = -cry * crz - srx_sry * srz;   D[2] = 0.0;      // x coeff.z (= c.x)
+        D[3] = crx * crz;                   D[4] = -(crx * srz);                 D[5] = 0.0;      // x coeff.x (= c.y)
+        D[6] = sry * srz + cry * crz * srx; D[7] = crz_sry - cry * srx_srz;      D[8] = 0.0;      // x coeff.y (= c.z)
+        // arx (:2323-2326) -> column 1
+        D[9] = crx_sry * srz;               D[10] = crx * crz_sry;               D[11] = -srx_sry;        // x coeff.z
+        D[12] = -srx_srz;                   D[13] = -(crz * srx);                D[14] = -crx;            // x coeff.x
+        D[15] = crx * cry * srz;            D[16] = crx * cry * crz;             D[17] = -(cry * srx);    // x coeff.y
+        // ary (:2327-2330) -> column 2 (no coeff.x bracket)
+        D[18] = cry * srx_srz - crz_sry;    D[19] = sry * srz + cry * crz * srx; D[20] = crx * cry;       // x coeff.z
+        D[21] = 0.0;                        D[22] = 0.0;                         D[23] = 0.0;
+        D[24] = -cry * crz - srx_sry * srz; D[25] = cry * srz - crz * srx_sry;   D[26] = -crx_sry;        // x coeff.y
+    } else {
+        // exact derivatives of R = Rz(yaw) Ry(pitch) Rx(roll) (Pose6D2Matrix, utils.hpp:452-460), columns in the kernel's (p.y, p.z, p.x) order
+        const double cr = std::cos(p->euler_rpy[0]), sr = std::sin(p->euler_rpy[0]);
+        const double cp = std::cos(p->euler_rpy[1]), sp = std::sin(p->euler_rpy[1]);
+        const double cy = std::cos(p->euler_rpy[2]), sy = std::sin(p->euler_rpy[2]);
+        const double Rx[9] = {1, 0, 0, 0, cr, -sr, 0, sr, cr}, dRx[9] = {0, 0, 0, 0, -sr, -cr, 0, cr, -sr};
+        const double Ry[9] = {cp, 0, sp, 0, 1, 0, -sp, 0, cp}, dRy[9] = {-sp, 0, cp, 0, 0, 0, -cp, 0, -sp};
+        const double Rz[9] = {cy, -sy, 0, sy, cy, 0, 0, 0, 1}, dRz[9] = {-sy, -cy, 0, cy, -sy, 0, 0, 0, 0};
+        auto mul3 = [](const double *A, const double *B, const double *C3, double *out) {
+            double T[9], O[9];
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i * 3 + k] * B[k * 3 + j]; T[i * 3 + j] = s; }
+            for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += T[i * 3 + k] * C3[k * 3 + j]; O[i * 3 + j] = s; }
+            for (int i = 0; i < 3; ++i) { out[i * 3 + 0] = O[i * 3 + 1]; out[i * 3 + 1] = O[i * 3 + 2]; out[i * 3 + 2] = O[i * 3 + 0]; }
+        };
+        mul3(Rz, Ry, dRx, D); mul3(Rz, dRy, Rx, D + 9); mul3(dRz, Ry, Rx, D + 18);
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_euler.data(), c->h_euler.data(), 27 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    a.dR = c->d_euler.data();
     return DCREG_OK;
 }
 
@@ -1406,6 +1409,14 @@ static void gate_publish(dcreg_ctx *c, unsigned long long seq_word, const double
 }
 static void gate_call_off(dcreg_ctx *c) { gate_publish(c, (c->gate_seq << 1) | 1ull, nullptr, nullptr); }
 
+// how far a pose (R9, t3) may carry a point of the source from where the pose (R, t) had it
+static double pose_jump(const dcreg_ctx *c, const double *R9, const double *t3, const double *R, const double *t) {
+    double dr = 0.0, dt = 0.0;
+    for (int k = 0; k < 9; ++k) dr += (R9[k] - R[k]) * (R9[k] - R[k]);
+    for (int k = 0; k < 3; ++k) dt += (t3[k] - t[k]) * (t3[k] - t[k]);
+    return std::sqrt(dr) * c->src_radius + std::sqrt(dt);
+}
+
 // dispatch order of the query-block groups (kernels.hpp k_group_cost): estimated cost of every group at this pose, heaviest first
 static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double *t3, int max_ring) {
     if (!c->d_group_est) HIP_TRY(c, c->d_group_est.alloc(kMaxGroups));
@@ -1431,24 +1442,33 @@ static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double 
     return DCREG_OK;
 }
 
-// gated = true: a single-pose launch whose pose arrives later through the gate (R9, t3 ignored; dcreg_linearize_gate_open /
-// _gate_abort decide its fate)
-// frame_ids != null: pose i linearises frame frame_ids[i] of the frames loaded by dcreg_frames_load instead of the ctx's source, with the
-// frames' own neighbour states (state_ids name those); the ctx's source and states are not touched
-// grid_ids != null (with frame_ids): the scan pairs of dcreg_register_pairs - pose i linearises source frame_ids[i] of the pairs' sources
-// against target grid_ids[i] of the pairs' build batch (kernels.hpp k_lin GRIDS); the ctx's target and window index are not touched
-static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
-                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false, const int32_t *frame_ids = nullptr,
-                           const int32_t *grid_ids = nullptr) {
-    if (!c) return DCREG_E_INVALID;
+// A launch as it goes through linearize_begin: the call's arguments, what lin_check settles (kind, points per pose) and what the steps
+// after it fill in (kernel arguments, the pose of a single-pose launch, debug buffers, the staged poses of a batch)
+struct LinLaunch {
+    int slot, n_poses; const double *R9, *t3; const int32_t *state_ids, *frame_ids, *grid_ids; const dcreg_lin_params *p; dcreg_lin_debug *dbg;
+    LinKind kind; int64_t n;            // points per pose: the ctx's source, or the largest frame of the launch
+    dcreg_ctx::FrameSet *fs;            // frames / pairs: the sources of the poses
+    dcreg_ctx::StateKey key; LinArgs a; DebugDev dd;
+    PoseArg one;                        // the pose of a single-pose launch (k_lin pose1)
+    const PoseArg *d_poses;             // batches: the staged poses (gated launches: the device pose the gate fills)
+    const uint2 *d_slices;              // frames: {first point, points} of every pose's frame (kernels.hpp k_lin SLICE)
+    const uint32_t *d_grid_ids;         // pairs: every pose's target grid (kernels.hpp k_lin GRIDS)
+    bool state_was_valid;               // the ctx's own state held a search before this launch (restored if a gated launch is called off)
+    bool own() const { return kind >= LinKind::single; }
+    bool uses_state(const dcreg_ctx *c) const { return own() && c->opt_warm; }
+};
+
+// Check: every refusal of a launch, before anything is changed (no HIP call; nothing of the ctx but its error text is written)
+static int lin_check(dcreg_ctx *c, LinLaunch &L) {
+    const bool gated = L.kind == LinKind::gated;
     // a timing probe, not a dump (dcreg_debug.h dcreg_lin_debug::stamps): certificates in use, only the stamps come back
-    const bool stamps_only = dbg_host && dbg_host->stamps && !dbg_host->nn_idx && !dbg_host->nn_d2 && !dbg_host->flag && !dbg_host->normal &&
-                             !dbg_host->r && !dbg_host->s && !dbg_host->stats;
+    const dcreg_lin_debug *d = L.dbg;
+    const bool stamps_only = d && d->stamps && !d->nn_idx && !d->nn_d2 && !d->flag && !d->normal && !d->r && !d->s && !d->stats;
     // nothing may be queued behind a gate that still waits: it would wait with it
     if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
     if (gated) {
         static const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, zero[3] = {0, 0, 0};
-        R9 = eye; t3 = zero; n_poses = 1; state_ids = nullptr; dbg_host = nullptr;
+        L.R9 = eye; L.t3 = zero; L.n_poses = 1; L.state_ids = nullptr; L.dbg = nullptr;
         // results must arrive through the pinned flags: a stream synchronise would wait for the gate, i.e. for its own caller
         if (!c->opt_spin) { c->fail("gated launches need the \"spin\" option (results through pinned flags)"); return DCREG_E_STATE; }
         // A launch that is to be TIMED (option "time_kernels": HIP events around it) is not gated - the caller starts it the plain way
@@ -1459,318 +1479,111 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
             c->fail("the next launch is a timed one: not gated"); return DCREG_E_STATE;
         }
     }
-    if (slot < 0 || slot >= dcreg_ctx::kLinSlots) { c->fail("invalid slot"); return DCREG_E_INVALID; }
-    LinSlot &S = c->slots[slot];
-    if (S.pending) { c->fail("slot %d still has a linearisation in flight", slot); return DCREG_E_STATE; }
-    if (!R9 || !t3 || n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
-    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    if (L.slot < 0 || L.slot >= dcreg_ctx::kLinSlots) { c->fail("invalid slot"); return DCREG_E_INVALID; }
+    if (c->slots[L.slot].pending) { c->fail("slot %d still has a linearisation in flight", L.slot); return DCREG_E_STATE; }
+    if (!L.R9 || !L.t3 || L.n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
+    if (L.n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", L.n_poses); return DCREG_E_INVALID; }
     // a pose with a NaN or an infinity is refused before anything is queued or changed (the search's cell keys of such a point are undefined)
-    if (!poses_finite(n_poses, R9, t3)) { c->fail("a pose with non-finite entries"); return DCREG_E_INVALID; }
-    if (!grid_ids && c->map.n <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
-    dcreg_ctx::FrameSet &fs = grid_ids ? c->pair_src : c->frames;
-    int64_t n_frame_max = 0;             // frames: points of the largest frame of this launch
-    if (grid_ids) {
-        if (!frame_ids) { c->fail("pair launches name a source for every pose"); return DCREG_E_INVALID; }
+    if (!poses_finite(L.n_poses, L.R9, L.t3)) { c->fail("a pose with non-finite entries"); return DCREG_E_INVALID; }
+    if (!L.grid_ids && c->map.n <= 0) { c->fail("KdTree/target index is not set up in context"); return DCREG_E_STATE; }   // :1639
+    L.fs = L.grid_ids ? &c->pair_src : &c->frames;
+    if (L.grid_ids) {
+        if (!L.frame_ids) { c->fail("pair launches name a source for every pose"); return DCREG_E_INVALID; }
         const dcreg_ctx::PairSet &ps = c->pairs;
-        for (int i = 0; i < n_poses; ++i) {
-            const int32_t t = grid_ids[i];
+        for (int i = 0; i < L.n_poses; ++i) {
+            const int32_t t = L.grid_ids[i];
             if (t < 0 || t >= ps.n || !ps.built[(size_t)t]) { c->fail("pair target %d is not built", t); return DCREG_E_INVALID; }
         }
-        if (!p || search_bound_sq(c, p->search_radius) != ps.radius_sq_f) { c->fail("the pair targets were built for another search radius"); return DCREG_E_INVALID; }
+        if (!L.p || search_bound_sq(c, L.p->search_radius) != ps.radius_sq_f) { c->fail("the pair targets were built for another search radius"); return DCREG_E_INVALID; }
     }
-    if (frame_ids) {
-        if (!state_ids || dbg_host || gated) { c->fail("frame launches are batched product launches"); return DCREG_E_INVALID; }
-        for (int i = 0; i < n_poses; ++i) {
-            const int32_t f = frame_ids[i];
-            if (f < 0 || (size_t)f >= fs.slice.size() || fs.slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
-            n_frame_max = std::max<int64_t>(n_frame_max, fs.slice[(size_t)f].y);
+    L.n = c->n_src;
+    if (L.frame_ids) {
+        if (!L.state_ids || L.dbg || gated) { c->fail("frame launches are batched product launches"); return DCREG_E_INVALID; }
+        L.n = 0;
+        for (int i = 0; i < L.n_poses; ++i) {
+            const int32_t f = L.frame_ids[i];
+            if (f < 0 || (size_t)f >= L.fs->slice.size() || L.fs->slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
+            L.n = std::max<int64_t>(L.n, L.fs->slice[(size_t)f].y);
         }
     } else
     if (c->n_src <= 0) { c->fail("measure cloud is not set"); return DCREG_E_STATE; }
-    if (c->need_set_device) { HIP_TRY(c, hipSetDevice(c->device)); }     // (before make_lin_args: the Euler branch allocates and copies)
-    // which index the launch searches (context.hpp, the window of a large map): single-pose product launches the window around their pose, a
-    // gated launch whatever is active (its pose is checked when the gate opens, against the window's pad: a gated launch whose search radius
-    // needs a larger pad than the window was built with runs on the whole map), everything else the whole map
-    if (gated && c->roi_active && p && roi_pad_for(c, p->search_radius) > c->roi_pad) (void)roi_deactivate(c);
-    if (!gated && !grid_ids && (c->roi_active || roi_wanted(c))) {
-        if (!p) { c->fail("null argument"); return DCREG_E_INVALID; }
-        const bool product = n_poses == 1 && !state_ids && (!dbg_host || stamps_only);
-        const int rr = product ? roi_ensure(c, R9, t3, p->search_radius) : roi_deactivate(c);
-        if (rr) return rr;
+    L.kind = L.grid_ids ? LinKind::pairs : L.frame_ids ? LinKind::frames : gated ? LinKind::gated : (L.n_poses > 1 || L.state_ids) ? LinKind::batch :
+             !L.dbg ? LinKind::single : stamps_only ? LinKind::stamps : LinKind::dump;
+    // (the launches that choose their index, the window of a large map or the whole map, need their parameters for that)
+    if (!L.p && !gated && (c->roi_active || roi_wanted(c))) { c->fail("null argument"); return DCREG_E_INVALID; }
+    const dcreg_lin_params *p = L.p;
+    if (!p || !(p->search_radius > 0.0)) { c->fail("invalid linearisation parameters"); return DCREG_E_INVALID; }
+    if (p->k != 5 && p->k != 0) { c->fail("only k = 5 is supported (icp_test_runner.cpp:1722)"); return DCREG_E_INVALID; }
+    if (p->parameterization != DCREG_PARAM_SO3 && p->parameterization != DCREG_PARAM_EULER && p->parameterization != DCREG_PARAM_EULER_EXACT) { c->fail("unknown parameterization"); return DCREG_E_INVALID; }
+    if (L.state_ids && c->opt_warm) {   // batched poses: each may own one of the reserved states, -1 = search cold, keep nothing
+        const int64_t n_states = L.frame_ids ? L.fs->n_states : c->n_batch_states;
+        std::vector<uint8_t> seen((size_t)std::max<int64_t>(n_states, 1), 0);
+        for (int i = 0; i < L.n_poses; ++i) {
+            const int32_t sid = L.state_ids[i];
+            if (sid < 0) continue;
+            if ((int64_t)sid >= n_states) { c->fail("warm state %d was not reserved (dcreg_reserve_warm_states: %lld)", sid, (long long)n_states); return DCREG_E_INVALID; }
+            if (seen[(size_t)sid]) { c->fail("warm state %d is used by two poses of one launch", sid); return DCREG_E_INVALID; }
+            seen[(size_t)sid] = 1;
+        }
     }
-    LinArgs a;
-    int rc = make_lin_args(c, p, a, grid_ids == nullptr);
-    if (rc) return rc;
-    if (frame_ids) a.count_scale = n_frame_max < ((int64_t)1 << 26) ? kCountScale : 0.0;     // (make_lin_args: of the ctx's own source)
-    // the parameters the stored certificates, gate bits and planes depend on (context.hpp StateKey): a launch with other values
-    // starts from empty states.  (weight_slope, weight_min and use_weight_derivative are not among them: the weight gate and the row
-    // are evaluated on the stored plane in every launch - tests/test_gpu_gate_edges.py alternates them on one context.)
-    dcreg_ctx::StateKey key;
-    key.radius_sq = a.radius_sq; key.max_thick_sq = a.max_thick_sq; key.min_norm = a.min_norm;
-    key.radius_sq_f = a.radius_sq_f; key.cert_r_out = a.cert_r_out; key.cert_r_in = a.cert_r_in; key.fast_plane = c->opt_fast_plane ? 1 : 0;
-    const uint32_t nbx = blocks_for(frame_ids ? n_frame_max : c->n_src, kLinBlock);
-    if (S.d_partials.ensure(c, (size_t)n_poses * nbx * kSlots)) return DCREG_E_NOMEM;
+    return DCREG_OK;
+}
+
+// heavy groups first: single-pose launches of at least two groups, once the order has been estimated (a gated launch does not know its
+// pose yet: it uses the order there is).  (A launch whose blocks are all resident at once - 4 per CU - has no order to speak of.)
+static bool order_wanted(const dcreg_ctx *c, const LinLaunch &L) {
+    return c->opt_dispatch_order && L.own() && c->n_groups >= 2 && blocks_for(L.n, kLinBlock) > 4u * (uint32_t)c->n_cus &&
+           c->hint_misalign > 0.5 * c->map.grid.h;
+}
+
+// Plan: how a checked launch is carried out.  fresh: the ctx's own state holds nothing yet (single-pose kinds)
+static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
+    LinPlan P;
+    P.kind = L.kind; P.n_poses = L.n_poses; P.nbx = blocks_for(L.n, kLinBlock);
     // one pose: the kernels finish the reduction themselves (chunk rows -> pinned memory); many poses: k_finalize
-    const uint32_t n_chunks = (nbx + kChunk - 1) / kChunk;
+    P.n_chunks = (P.nbx + kChunk - 1) / kChunk;
     // ... and so do batches whose poses are one chunk each (the Monte-Carlo batches: 30 blocks per pose): the last block of a pose sums
     // the pose's rows - block_sum_rows, as k_finalize would - and publishes the pose's result row
-    const bool fused = (n_poses == 1) || (n_chunks == 1 && c->opt_fused_batches);
+    const bool fused = L.n_poses == 1 || P.n_chunks == 1;
     // a launch of one chunk's worth of blocks: the blocks publish their rows themselves and the host adds them (kernels.hpp FinArgs)
-    const bool direct = fused && n_poses == 1 && nbx <= (uint32_t)kChunk && c->opt_direct_rows && c->opt_one_wave < 2;     // (one_wave = 2: tile rows even there - tests)
-    const size_t n_rows = direct ? (size_t)nbx : (fused ? (size_t)n_chunks * (size_t)n_poses : (size_t)n_poses);      // result rows the host waits for
-    if (fused) {   // tickets: zero when (re)allocated, afterwards every completed launch leaves them zero
-        const size_t had = S.d_tickets.cap();
-        if (S.d_tickets.ensure(c, (size_t)n_chunks * (size_t)n_poses * kCounterStride)) return DCREG_E_NOMEM;
-        if (S.d_tickets.cap() != had || S.tickets_dirty) {
-            HIP_TRY(c, hipMemsetAsync(S.d_tickets.data(), 0, sizeof(unsigned int) * S.d_tickets.cap(), c->stream));
-            S.tickets_dirty = false;
-        }
-    }
-    if (n_rows * kSlots > S.h_out.cap()) {
-        const size_t cap = std::max<size_t>(n_rows, 64) * kSlots;
-        HIP_TRY(c, S.h_out.alloc(cap, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(S.h_out.data(), 0, cap * sizeof(double));
-        std::fill(S.row_chk.begin(), S.row_chk.end(), 0ull);
-    }
-    const int64_t n = frame_ids ? n_frame_max : c->n_src;
-    const float4 *const d_src = frame_ids ? fs.src.data() : c->d_src.data();
-    a.state = nullptr; a.state_stride = 0;
-    a.xcd_chunk = (uint32_t)std::max(c->opt_xcd_chunk, 0);
-    if (n_poses == 1 && !state_ids && !gated) {
-        // how far this pose may carry a point from where the last linearised pose had it
-        double jump = 1e300;
-        if (c->last_pose_valid) {
-            double dr = 0.0, dt = 0.0;
-            for (int k = 0; k < 9; ++k) dr += (R9[k] - c->last_R[k]) * (R9[k] - c->last_R[k]);
-            for (int k = 0; k < 3; ++k) dt += (t3[k] - c->last_t[k]) * (t3[k] - c->last_t[k]);
-            jump = std::sqrt(dr) * c->src_radius + std::sqrt(dt);
-        }
-        if (c->hint_unknown && jump <= 0.5 * c->map.grid.h) c->hint_misalign = c->hint_last;      // the same trajectory, continued
-        // ... and what the last completed launch searched says nothing about a launch half a cell or more away from it (the first
-        // launch of a new run): expect a search of everything - for this launch and for the one that may be queued behind it before
-        // its counts are known (scheduling only: which kernels carry the launch out)
-        if (jump > 0.5 * c->map.grid.h) { c->last_searched = n_poses * c->n_src; c->last_points = c->last_searched; }
-        c->hint_unknown = false;
-        std::memcpy(c->last_R, R9, sizeof(c->last_R)); std::memcpy(c->last_t, t3, sizeof(c->last_t));
-        c->last_pose_valid = true;
-    }
-    {   // heavy groups first: single-pose launches of at least two groups, once the order has been estimated (a gated launch does not
-        // know its pose yet: it uses the order there is)
-        // (a launch whose blocks are all resident at once - 4 per CU - has no order to speak of)
-        const bool wanted = c->opt_dispatch_order && n_poses == 1 && !state_ids && c->n_groups >= 2 && nbx > 4u * (uint32_t)c->n_cus &&
-                            c->hint_misalign > 0.5 * c->map.grid.h;
-        if (wanted && !gated) {
-            // the estimate holds for poses near the one it was made at (within a cell for every point)
-            bool stale = !c->order_valid;
-            // (counted in c->seq, the launch number that is never reset: round 6 found this test dead - it compared with n_launches, which
-            //  dcreg_launch_stats_get(reset) zeroes, so that after one reset of the statistics the order of the moment was kept for good; with
-            //  `bench.py --steps 20 --warmup 5` that was the order estimated at an ALIGNED pose, i.e. none: 355 / 314 / 260 us for the first
-            //  launches of every later run instead of 264 / 216 / 205)
-            if (!stale && (int64_t)c->seq - c->est_launch >= 16) {       // (a loop of ungated launches does not re-estimate at every step)
-                double dr = 0.0, dt = 0.0;
-                for (int k = 0; k < 9; ++k) dr += (R9[k] - c->est_R[k]) * (R9[k] - c->est_R[k]);
-                for (int k = 0; k < 3; ++k) dt += (t3[k] - c->est_t[k]) * (t3[k] - c->est_t[k]);
-                stale = std::sqrt(dr) * c->src_radius + std::sqrt(dt) > c->map.grid.h;
-            }
-            if (stale) {
-                rc = estimate_dispatch_order(c, R9, t3, a.max_ring);
-                if (rc) return rc;
-            }
-        }
-        const bool ordered = wanted && c->order_valid && c->order_uneven;
-        a.group_blocks = std::max<uint32_t>(c->group_blocks, 1u); a.n_groups = ordered ? c->n_groups : 0u;
-        std::memcpy(a.group_order, c->group_order, sizeof(a.group_order));
-    }
-    PoseArg one{};
-    one.state = kNoIdx; one.fresh = 1;
-    const PoseArg *d_poses = nullptr;
-    const uint2 *d_slices = nullptr;     // frames: {first point, points} of every pose's frame (kernels.hpp k_lin SLICE)
-    const uint32_t *d_grid_ids = nullptr;    // pairs: every pose's target grid (kernels.hpp k_lin GRIDS)
-    bool uses_state = false;
-    if (n_poses == 1 && !state_ids && c->opt_warm && !(key == c->state_key)) { c->state_valid = false; c->state_key = key; }
-    const bool state_was_valid = c->state_valid;
-    if (n_poses == 1 && !state_ids) {
-        std::memcpy(one.R, R9, sizeof(one.R)); std::memcpy(one.t, t3, sizeof(one.t));
-        if (c->opt_warm) {      // single pose: the ctx's own state
-            const size_t stride = ((size_t)n + 63) & ~(size_t)63;
-            if (!c->state_valid || c->state_stride != stride) {
-                if (c->d_state.ensure(c, kStateRows * stride)) return DCREG_E_NOMEM;
-                c->state_stride = stride; c->state_valid = false;
-            }
-            uses_state = true;
-            one.state = 0; one.fresh = c->state_valid ? 0u : 1u;
-            a.state = c->d_state.data(); a.state_stride = (uint32_t)c->state_stride;
-        }
-        if (gated) {
-            if (!c->h_gate) {     // all or nothing: a half-built gate would be taken for a whole one by the next call
-                PinnedBuf<GateHost> hg;
-                DevBuf<PoseArg> dp;
-                DevBuf<uint32_t> da;
-                DevBuf<GateDev> gd;
-                bool ok = hg.alloc(1, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-                ok = ok && dp.alloc(1) == hipSuccess && da.alloc(1) == hipSuccess;
-                // (the device copy of the record, for launches gated in their first kernel: cleared IN THE STREAM - the ctx stream does not
-                //  synchronise with the null stream)
-                ok = ok && gd.alloc(1) == hipSuccess && hipMemsetAsync(gd.data(), 0, sizeof(GateDev), c->stream) == hipSuccess;
-                if (!ok) {
-                    c->state_valid = state_was_valid;
-                    c->fail("allocating the launch gate failed");
-                    return DCREG_E_NOMEM;
-                }
-                std::memset(hg.data(), 0, sizeof(GateHost));
-                c->h_gate = std::move(hg); c->d_gate_pose = std::move(dp); c->d_gate_abort = std::move(da); c->d_gate_dev = std::move(gd);
-            }
-            d_poses = c->d_gate_pose.data();
-        }
-    } else {
-        // batched poses: each may own one of the reserved states (dcreg_reserve_warm_states; frames: dcreg_frames_reserve_states);
-        // -1 = search cold, keep nothing
-        const int64_t n_states = frame_ids ? fs.n_states : c->n_batch_states;
-        std::vector<uint8_t> &state_valid = frame_ids ? fs.state_valid : c->batch_state_valid;
-        dcreg_ctx::StateKey &states_key = frame_ids ? fs.key : c->batch_state_key;
-        const bool use_states = state_ids && c->opt_warm && n_states > 0;
-        if (use_states && !(key == states_key)) {
-            std::fill(state_valid.begin(), state_valid.end(), (uint8_t)0);
-            states_key = key;
-        }
-        if (state_ids && c->opt_warm) {
-            std::vector<uint8_t> seen((size_t)std::max<int64_t>(n_states, 1), 0);
-            for (int i = 0; i < n_poses; ++i) {
-                const int32_t sid = state_ids[i];
-                if (sid < 0) continue;
-                if ((int64_t)sid >= n_states) { c->fail("warm state %d was not reserved (dcreg_reserve_warm_states: %lld)", sid, (long long)n_states); return DCREG_E_INVALID; }
-                if (seen[(size_t)sid]) { c->fail("warm state %d is used by two poses of one launch", sid); return DCREG_E_INVALID; }
-                seen[(size_t)sid] = 1;
-            }
-        }
-        // (frames: the poses' slices ride behind the poses in the same block - one copy; pairs: and their target ids behind those)
-        const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (frame_ids ? (size_t)n_poses * sizeof(uint2) : 0) +
-                             (grid_ids ? (size_t)n_poses * sizeof(uint32_t) : 0);
-        if (bytes > S.d_poses.cap()) {      // the pinned block stays alive until end(): source of the asynchronous copy
-            S.h_poses.reset(); S.d_poses.reset();
-            const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2) + sizeof(uint32_t)));
-            HIP_TRY(c, S.h_poses.alloc(cap, hipHostMallocDefault));
-            if (S.d_poses.alloc(cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
-        }
-        PoseArg *hp = (PoseArg *)S.h_poses.data();
-        for (int i = 0; i < n_poses; ++i) {
-            std::memcpy(hp[i].R, R9 + 9 * i, sizeof(one.R)); std::memcpy(hp[i].t, t3 + 3 * i, sizeof(one.t));
-            const bool has = use_states && state_ids[i] >= 0;
-            hp[i].state = has ? (uint32_t)state_ids[i] : kNoIdx;
-            hp[i].fresh = (has && state_valid[(size_t)state_ids[i]] != 0) ? 0u : 1u;
-            if (has) state_valid[(size_t)state_ids[i]] = 1;
-        }
-        if (frame_ids) {
-            uint2 *hs = (uint2 *)(S.h_poses.data() + (size_t)n_poses * sizeof(PoseArg));
-            for (int i = 0; i < n_poses; ++i) hs[i] = fs.slice[(size_t)frame_ids[i]];
-            d_slices = (const uint2 *)(S.d_poses.data() + (size_t)n_poses * sizeof(PoseArg));
-        }
-        if (grid_ids) {
-            const size_t at = (size_t)n_poses * (sizeof(PoseArg) + sizeof(uint2));
-            std::memcpy(S.h_poses.data() + at, grid_ids, sizeof(uint32_t) * (size_t)n_poses);
-            d_grid_ids = (const uint32_t *)(S.d_poses.data() + at);
-        }
-        // (measured and dropped, profiles/r05_ablation.md: the upload on a copy stream behind an event - the cross-stream dependency costs
-        //  more than the 4.6 us copy it hides, C5 1.56 M against 1.64 M it/s - and no upload at all, the kernel reading the pinned block:
-        //  +2.7 us per kernel, nothing gained - the experiment is bound by its kernels, two groups of trials alternating on the device)
-        HIP_TRY(c, hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        d_poses = (const PoseArg *)S.d_poses.data();
-        if (use_states && frame_ids) { a.state = fs.state.data(); a.state_stride = (uint32_t)fs.state_stride; }
-        else if (use_states) { a.state = c->d_state_batch.data(); a.state_stride = (uint32_t)c->state_batch_stride; }
-    }
-    a.use_cert = ((dbg_host && !stamps_only) || !c->opt_use_cert) ? 0 : 1;   // a debug dump searches every point (its statistics are those of the searches)
-    a.search_count = c->opt_count_searches ? c->d_search_count.data() : nullptr;
+    P.direct = fused && L.n_poses == 1 && P.nbx <= (uint32_t)kChunk && c->opt_one_wave < 2;     // (one_wave = 2: tile rows even there - tests)
+    P.n_rows = P.direct ? (size_t)P.nbx : (fused ? (size_t)P.n_chunks * (size_t)P.n_poses : (size_t)P.n_poses);
+    const bool dbg = L.kind == LinKind::dump || L.kind == LinKind::stamps;
+    P.use_cert = L.kind != LinKind::dump && c->opt_use_cert;     // a debug dump searches every point (its statistics are those of the searches)
+    P.ordered = order_wanted(c, L) && c->order_valid && c->order_uneven;
+    // what the launch is expected to search: what the last completed launch reported (with the engines' pipeline: the launch two back)
+    const bool known = c->last_searched >= 0 && c->last_points == L.n;
+    const double f = known ? (double)c->last_searched / (double)L.n : -1.0;
     // The advance pass (kernels.hpp k_advance) in front of this launch?  Only where it can pay: a single pose on the ctx's own state,
     // certificates in use, the state filled by an earlier launch; by default ("advance" = 1) a cloud whose query blocks exceed what the
     // device holds at once (below that a launch lasts as long as one search whether its searches are dense or not) in a launch expected
-    // to search a few per cent of its points - expected = what the last completed launch reported (with the engines' pipeline that is
-    // the launch two back).  Scheduling only: the sums are the same with and without the pass.
-    bool adv = false, team = false;
-    a.adv_counts = nullptr;
-    if (n_poses == 1 && !state_ids && uses_state && one.fresh == 0u && a.use_cert && !dbg_host && a.count_scale != 0.0 && a.warm) {
-        // what the launch is expected to search: what the last completed launch reported (with the engines' pipeline: the launch two back)
-        const bool known = c->last_searched >= 0 && c->last_points == n;
-        const double f = known ? (double)c->last_searched / (double)n : -1.0;
-        adv = c->opt_advance >= 2 || (c->opt_advance == 1 && nbx >= (uint32_t)c->opt_advance_min_blocks && known && f >= c->opt_advance_lo && f <= c->opt_advance_hi);
+    // to search a few per cent of its points.  Scheduling only: the sums are the same with and without the pass.
+    if ((L.kind == LinKind::single || L.kind == LinKind::gated) && c->opt_warm && !fresh && P.use_cert && L.a.count_scale != 0.0) {
+        constexpr double kAdvanceLo = 0.01, kAdvanceHi = 0.45;
+        const bool adv = c->opt_advance >= 2 || (c->opt_advance == 1 && P.nbx >= (uint32_t)c->opt_advance_min_blocks && known && f >= kAdvanceLo && f <= kAdvanceHi);
         // ... its small-frame form (k_advance_team: sixteen lanes per query, one wave per kTeamTile points): a frame of a few thousand
         // points, whose query blocks leave most of the device idle, in a launch expected to search most of its points (the pass costs
         // ~12 us whatever it finds to do; k_lin alone gets cheaper as its searching waves thin out, so below half it wins again)
         // ... and only against a map whose occupied cells hold several points each: there a query with a loose bound (an OUT point, a
         // jump) has a hundred and more candidates in its 27-cell block and the lock-step search, two trips in flight, is at its slowest;
         // against a sparse map (the 7.5 k-point fixture: 1.6 points per occupied cell) it is as fast as the teams
+        constexpr double kTeamPassMaxPoints = 16384.0, kTeamPassMinFrac = 0.5, kTeamPassMinCellPts = 3.0;
         const double per_cell = (double)c->map.n / (double)std::max<uint32_t>(c->map.occupied, 1u);
-        team = c->opt_team_pass >= 2 || (c->opt_team_pass == 1 && n <= (int64_t)c->opt_team_pass_max_points && known && f >= c->opt_team_pass_min_frac &&
-                                         per_cell >= c->opt_team_pass_min_cell_pts);
+        const bool team = c->opt_team_pass >= 2 || (c->opt_team_pass == 1 && L.n <= (int64_t)kTeamPassMaxPoints && known && f >= kTeamPassMinFrac &&
+                                                    per_cell >= kTeamPassMinCellPts);
+        P.pass = team ? LinPass::team : adv ? LinPass::advance : LinPass::none;
     }
-    if (team) adv = false;
     // the one-wave instantiation of k_lin (kernels.hpp): fused single-pose launches of many blocks in which most waves search
     bool one_wave = false;
-    if (n_poses > 1) {      // batched launches of one-chunk poses (the Monte-Carlo batches): trials at every stage of their runs side by side
-        one_wave = fused && !dbg_host && (c->opt_one_wave >= 2 || (c->opt_one_wave_batches && (uint64_t)n_poses * nbx >= (uint64_t)c->opt_one_wave_min_blocks));
-    } else
-    if (n_poses == 1 && fused && !direct && !dbg_host && !stamps_only && !team) {
+    if (L.n_poses > 1)      // batched launches of one-chunk poses (the Monte-Carlo batches): trials at every stage of their runs side by side
+        one_wave = fused && !dbg && (c->opt_one_wave >= 2 || (c->opt_one_wave_batches && (uint64_t)L.n_poses * P.nbx >= (uint64_t)c->opt_one_wave_min_blocks));
+    else if (!P.direct && !dbg && P.pass != LinPass::team) {
         // by the rule: a launch of many blocks whose searches are long - the queries more than a cell and a half from the surface (the
-        // engines' hint, as for the dispatch order above; unknown at the start of a run = far) - and most of whose points search
-        const bool known = c->last_searched >= 0 && c->last_points == n;
-        const bool most = !uses_state || one.fresh != 0u || !a.use_cert || (known && (double)c->last_searched >= c->opt_one_wave_min_frac * (double)n);
-        one_wave = c->opt_one_wave >= 2 || (c->opt_one_wave == 1 && nbx >= (uint32_t)c->opt_one_wave_min_blocks && !adv && most &&
+        // engines' hint, as for the dispatch order; unknown at the start of a run = far) - and most of whose points search
+        const bool most = !L.uses_state(c) || fresh || !P.use_cert || (known && (double)c->last_searched >= c->opt_one_wave_min_frac * (double)L.n);
+        one_wave = c->opt_one_wave >= 2 || (c->opt_one_wave == 1 && P.nbx >= (uint32_t)c->opt_one_wave_min_blocks && P.pass != LinPass::advance && most &&
                                             c->hint_misalign > c->opt_one_wave_min_cells * c->map.grid.h);
     }
-    // (a row per TILE then: grown here, before any kernel of this launch is queued)
-    if (one_wave && S.d_partials.ensure(c, (size_t)n_poses * nbx * kSlots * (kLinBlock / kWave))) return DCREG_E_NOMEM;
-    const uint32_t n_tiles = team ? blocks_for(n, kTeamTile) : blocks_for(n, kAdvTile);
-    if (adv || team) {      // the passes' counts, per query block of k_lin: zero between launches (k_lin takes them and zeroes them again)
-        const size_t had = c->d_adv_counts.cap();
-        if (c->d_adv_counts.ensure(c, (size_t)kCounterStride * nbx)) return DCREG_E_NOMEM;      // (a 128-byte line per query block)
-        if (c->d_adv_counts.cap() != had || c->adv_counts_dirty) {
-            HIP_TRY(c, hipMemsetAsync(c->d_adv_counts.data(), 0, sizeof(uint32_t) * c->d_adv_counts.cap(), c->stream));
-            c->adv_counts_dirty = false;
-        }
-        a.adv_counts = c->d_adv_counts.data();
-    }
-    unsigned long long *team_stamps = nullptr;
-    if (team && c->opt_team_stamps) {          // timing probe (dcreg_debug.h dcreg_team_pass_stamps): eight clock words per block of the pass.  Grown HERE,
-        // before any kernel of this launch is queued: a hipFree behind a gate kernel that waits for the host would wait for it
-        if (c->d_team_stamps.ensure(c, (size_t)8 * (n_tiles + 1))) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemsetAsync(c->d_team_stamps.data(), 0, sizeof(unsigned long long) * 8 * (n_tiles + 1), c->stream));
-        team_stamps = c->d_team_stamps.data(); c->team_stamps_n = n_tiles;
-    }
-    DebugDev dd{};
-    free_tmp(S);
-    if (dbg_host) {
-        bool oom = false;
-        auto alloc = [&](size_t bytes, int fill) -> void * {
-            DevBuf<unsigned char> b;
-            if (b.alloc(bytes) != hipSuccess) { oom = true; return nullptr; }
-            (void)hipMemsetAsync(b.data(), fill, bytes, c->stream);
-            S.tmp_dev.push_back(std::move(b));
-            return S.tmp_dev.back().data();
-        };
-        if (dbg_host->nn_idx) dd.nn_idx = (int32_t *)alloc(sizeof(int32_t) * 5 * n, 0xFF);
-        if (dbg_host->nn_d2) dd.nn_d2 = (float *)alloc(sizeof(float) * 5 * n, 0);
-        if (dbg_host->flag) dd.flag = (uint8_t *)alloc(n, 0);
-        if (dbg_host->normal) dd.normal = (double *)alloc(sizeof(double) * 3 * n, 0);
-        if (dbg_host->r) dd.r = (double *)alloc(sizeof(double) * n, 0);
-        if (dbg_host->s) dd.s = (double *)alloc(sizeof(double) * n, 0);
-        if (dbg_host->stats) dd.stats = (uint32_t *)alloc(sizeof(uint32_t) * n, 0);
-        if (dbg_host->stamps) dd.stamps = (unsigned long long *)alloc(sizeof(unsigned long long) * 8 * (kLinBlock / 64) * (size_t)nbx, 0);
-        if (oom) { free_tmp(S); drop_warm(c); c->fail("hipMalloc of the debug dump buffers failed"); return DCREG_E_NOMEM; }
-    }
-    const unsigned long long seq = ++c->seq;
-    FinArgs fin{S.d_tickets.data(), S.h_out.dev(), seq, direct ? 1u : 0u, n_chunks};
-    if (fused) S.tickets_dirty = true;    // cleared again once this launch is known to have completed
-    // kernel timing: HIP events around every opt_time_kernels-th linearisation (each timed launch costs ~10 us of host time)
-    bool timed = c->opt_time_kernels > 0 && (c->launch_counter++ % (uint64_t)c->opt_time_kernels) == 0;
-    if (timed && !S.ev0) timed = false;               // (the slot's events are created with the context)
-    const uint32_t *abort_flag = nullptr;
-    // a launch that was queued and must not run after all (errors below): call the gate off, forget what the states were about to hold
-    auto bail = [&](const char *what, hipError_t e) {
-        free_tmp(S);
-        if (gated) gate_call_off(c);
-        drop_warm(c);
-        c->fail("%s failed: %s", what, hipGetErrorString(e));
-        return DCREG_E_DEVICE;
-    };
     // A gated launch the device holds at once (at most kChunk query blocks) waits for its pose in its FIRST kernel instead of behind a
     // gate kernel (kernels.hpp gate_wait: one kernel boundary less on a launch that lasts a few microseconds); larger launches keep
     // k_gate (every wave would pay for the wait: profiles/r04_gate_in_kernel.txt).  What this relies on and costs: every
@@ -1779,134 +1592,316 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     // rests on block 0 being dispatched before the device is full, which holds while blocks are dispatched in index order and the launch
     // fits the device (nbx <= kChunk: it does).  A context that shares its device with other busy contexts holds wave slots idle that way;
     // option "gate_in_kernel" = 0 puts the one-wave k_gate back in front.
+    P.gate_inside = L.kind == LinKind::gated && c->opt_gate_in_kernel && P.nbx <= (uint32_t)kChunk && P.pass != LinPass::advance;
+    // the k_lin instantiation: a gated k_lin runs in four-wave blocks whatever the one-wave rule says
+    P.body = (P.gate_inside && P.pass != LinPass::team) ? LinBody::gated : L.kind == LinKind::stamps ? LinBody::stamps : L.kind == LinKind::dump ? LinBody::dump :
+             one_wave ? LinBody::one_wave : fused ? LinBody::fused : LinBody::chunked;
+    return P;
+}
+
+// the poses of a batched launch, their states and (frames, pairs) slices and target ids in one pinned block, and its upload
+static int stage_poses(dcreg_ctx *c, LinSlot &S, LinLaunch &L) {
+    const int64_t n_states = L.frame_ids ? L.fs->n_states : c->n_batch_states;
+    std::vector<uint8_t> &state_valid = L.frame_ids ? L.fs->state_valid : c->batch_state_valid;
+    dcreg_ctx::StateKey &states_key = L.frame_ids ? L.fs->key : c->batch_state_key;
+    const bool use_states = L.state_ids && c->opt_warm && n_states > 0;
+    if (use_states && !(L.key == states_key)) {
+        std::fill(state_valid.begin(), state_valid.end(), (uint8_t)0);
+        states_key = L.key;
+    }
+    const int n_poses = L.n_poses;
+    // (frames: the poses' slices ride behind the poses in the same block - one copy; pairs: and their target ids behind those)
+    const size_t bytes = (size_t)n_poses * sizeof(PoseArg) + (L.frame_ids ? (size_t)n_poses * sizeof(uint2) : 0) +
+                         (L.grid_ids ? (size_t)n_poses * sizeof(uint32_t) : 0);
+    if (bytes > S.d_poses.cap()) {      // the pinned block stays alive until end(): source of the asynchronous copy
+        S.h_poses.reset(); S.d_poses.reset();
+        const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2) + sizeof(uint32_t)));
+        HIP_TRY(c, S.h_poses.alloc(cap, hipHostMallocDefault));
+        if (S.d_poses.alloc(cap) != hipSuccess) { c->fail("hipMalloc(%zu B) failed", cap); return DCREG_E_NOMEM; }
+    }
+    PoseArg *hp = (PoseArg *)S.h_poses.data();
+    for (int i = 0; i < n_poses; ++i) {
+        std::memcpy(hp[i].R, L.R9 + 9 * i, sizeof(hp[i].R)); std::memcpy(hp[i].t, L.t3 + 3 * i, sizeof(hp[i].t));
+        const bool has = use_states && L.state_ids[i] >= 0;
+        hp[i].state = has ? (uint32_t)L.state_ids[i] : kNoIdx;
+        hp[i].fresh = (has && state_valid[(size_t)L.state_ids[i]] != 0) ? 0u : 1u;
+        if (has) state_valid[(size_t)L.state_ids[i]] = 1;
+    }
+    if (L.frame_ids) {
+        uint2 *hs = (uint2 *)(S.h_poses.data() + (size_t)n_poses * sizeof(PoseArg));
+        for (int i = 0; i < n_poses; ++i) hs[i] = L.fs->slice[(size_t)L.frame_ids[i]];
+        L.d_slices = (const uint2 *)(S.d_poses.data() + (size_t)n_poses * sizeof(PoseArg));
+    }
+    if (L.grid_ids) {
+        const size_t at = (size_t)n_poses * (sizeof(PoseArg) + sizeof(uint2));
+        std::memcpy(S.h_poses.data() + at, L.grid_ids, sizeof(uint32_t) * (size_t)n_poses);
+        L.d_grid_ids = (const uint32_t *)(S.d_poses.data() + at);
+    }
+    // (measured and dropped, profiles/r05_ablation.md: the upload on a copy stream behind an event - the cross-stream dependency costs
+    //  more than the 4.6 us copy it hides, C5 1.56 M against 1.64 M it/s - and no upload at all, the kernel reading the pinned block:
+    //  +2.7 us per kernel, nothing gained - the experiment is bound by its kernels, two groups of trials alternating on the device)
+    HIP_TRY(c, hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    L.d_poses = (const PoseArg *)S.d_poses.data();
+    if (use_states && L.frame_ids) { L.a.state = L.fs->state.data(); L.a.state_stride = (uint32_t)L.fs->state_stride; }
+    else if (use_states) { L.a.state = c->d_state_batch.data(); L.a.state_stride = (uint32_t)c->state_batch_stride; }
+    return DCREG_OK;
+}
+
+// Reserve: every buffer the plan needs is grown and cleared here, before the first kernel of the launch is queued - a hipFree queued
+// behind a gate kernel that waits for the host would wait for it
+static int lin_reserve(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
+    if (int rc = stage_euler(c, L.p, L.a)) return rc;
+    // (one-wave blocks: a row per TILE)
+    if (S.d_partials.ensure(c, (size_t)P.n_poses * P.nbx * kSlots * (P.one_wave() ? kLinBlock / kWave : 1))) return DCREG_E_NOMEM;
+    if (P.fused()) {   // tickets: zero when (re)allocated, afterwards every completed launch leaves them zero
+        const size_t had = S.d_tickets.cap();
+        if (S.d_tickets.ensure(c, (size_t)P.n_chunks * (size_t)P.n_poses * kCounterStride)) return DCREG_E_NOMEM;
+        if (S.d_tickets.cap() != had || S.tickets_dirty) {
+            HIP_TRY(c, hipMemsetAsync(S.d_tickets.data(), 0, sizeof(unsigned int) * S.d_tickets.cap(), c->stream));
+            S.tickets_dirty = false;
+        }
+    }
+    if (P.n_rows * kSlots > S.h_out.cap()) {
+        const size_t cap = std::max<size_t>(P.n_rows, 64) * kSlots;
+        HIP_TRY(c, S.h_out.alloc(cap, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(S.h_out.data(), 0, cap * sizeof(double));
+        std::fill(S.row_chk.begin(), S.row_chk.end(), 0ull);
+    }
+    if (L.kind == LinKind::gated) {
+        if (!c->h_gate) {     // all or nothing: a half-built gate would be taken for a whole one by the next call
+            PinnedBuf<GateHost> hg; DevBuf<PoseArg> dp; DevBuf<uint32_t> da; DevBuf<GateDev> gd;
+            bool ok = hg.alloc(1, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
+            ok = ok && dp.alloc(1) == hipSuccess && da.alloc(1) == hipSuccess;
+            // (the device copy of the record, for launches gated in their first kernel: cleared IN THE STREAM - the ctx stream does not
+            //  synchronise with the null stream)
+            ok = ok && gd.alloc(1) == hipSuccess && hipMemsetAsync(gd.data(), 0, sizeof(GateDev), c->stream) == hipSuccess;
+            if (!ok) {
+                c->state_valid = L.state_was_valid;
+                c->fail("allocating the launch gate failed");
+                return DCREG_E_NOMEM;
+            }
+            std::memset(hg.data(), 0, sizeof(GateHost));
+            c->h_gate = std::move(hg); c->d_gate_pose = std::move(dp); c->d_gate_abort = std::move(da); c->d_gate_dev = std::move(gd);
+        }
+        L.d_poses = c->d_gate_pose.data();
+    }
+    if (int rc = L.own() ? DCREG_OK : stage_poses(c, S, L)) return rc;
+    if (P.pass != LinPass::none) {      // the passes' counts, per query block of k_lin: zero between launches (k_lin takes them and zeroes them again)
+        const size_t had = c->d_adv_counts.cap();
+        if (c->d_adv_counts.ensure(c, (size_t)kCounterStride * P.nbx)) return DCREG_E_NOMEM;      // (a 128-byte line per query block)
+        if (c->d_adv_counts.cap() != had || c->adv_counts_dirty) {
+            HIP_TRY(c, hipMemsetAsync(c->d_adv_counts.data(), 0, sizeof(uint32_t) * c->d_adv_counts.cap(), c->stream));
+            c->adv_counts_dirty = false;
+        }
+        L.a.adv_counts = c->d_adv_counts.data();
+    }
+    if (P.pass == LinPass::team && c->opt_team_stamps) {   // timing probe (dcreg_debug.h dcreg_team_pass_stamps): eight clock words per block of the pass
+        const uint32_t n_tiles = blocks_for(L.n, kTeamTile);
+        if (c->d_team_stamps.ensure(c, (size_t)8 * (n_tiles + 1))) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemsetAsync(c->d_team_stamps.data(), 0, sizeof(unsigned long long) * 8 * (n_tiles + 1), c->stream));
+        c->team_stamps_n = n_tiles;
+    }
+    free_tmp(S);
+    if (L.dbg) {
+        const dcreg_lin_debug *dbg = L.dbg; const size_t n = (size_t)L.n; DebugDev &dd = L.dd;
+        bool oom = false;
+        auto alloc = [&](size_t bytes, int fill) -> void * {
+            DevBuf<unsigned char> b;
+            if (b.alloc(bytes) != hipSuccess) { oom = true; return nullptr; }
+            (void)hipMemsetAsync(b.data(), fill, bytes, c->stream);
+            S.tmp_dev.push_back(std::move(b));
+            return S.tmp_dev.back().data();
+        };
+        if (dbg->nn_idx) dd.nn_idx = (int32_t *)alloc(sizeof(int32_t) * 5 * n, 0xFF);
+        if (dbg->nn_d2) dd.nn_d2 = (float *)alloc(sizeof(float) * 5 * n, 0);
+        if (dbg->flag) dd.flag = (uint8_t *)alloc(n, 0);
+        if (dbg->normal) dd.normal = (double *)alloc(sizeof(double) * 3 * n, 0);
+        if (dbg->r) dd.r = (double *)alloc(sizeof(double) * n, 0);
+        if (dbg->s) dd.s = (double *)alloc(sizeof(double) * n, 0);
+        if (dbg->stats) dd.stats = (uint32_t *)alloc(sizeof(uint32_t) * n, 0);
+        if (dbg->stamps) dd.stamps = (unsigned long long *)alloc(sizeof(unsigned long long) * 8 * (kLinBlock / 64) * (size_t)P.nbx, 0);
+        if (oom) { free_tmp(S); drop_warm(c); c->fail("hipMalloc of the debug dump buffers failed"); return DCREG_E_NOMEM; }
+    }
+    L.a.use_cert = P.use_cert ? 1 : 0;
+    L.a.search_count = c->opt_count_searches ? c->d_search_count.data() : nullptr;
+    L.a.group_blocks = std::max<uint32_t>(c->group_blocks, 1u); L.a.n_groups = P.ordered ? c->n_groups : 0u;
+    std::memcpy(L.a.group_order, c->group_order, sizeof(L.a.group_order));
+    return DCREG_OK;
+}
+
+// the k_lin instantiation of a plan (kernels.hpp k_lin<MODE, FUSED, FAST, GATE, ONE, SLICE, GRIDS>)
+using LinKernel = decltype(&k_lin<0, true, true>);
+template <bool FAST, bool SLICE = false, bool GRIDS = false>
+static LinKernel lin_kernel(const LinPlan &P) {
+    if constexpr (!SLICE) {
+        if (P.kind == LinKind::pairs) return lin_kernel<FAST, true, true>(P);     // every pose reads its own slice and its own target grid
+        if (P.kind == LinKind::frames) return lin_kernel<FAST, true>(P);         // every pose reads its own slice
+        if (P.body == LinBody::gated) return k_lin<0, true, FAST, true>;         // (MODE 0: a gated launch is never a dump)
+        if (P.body == LinBody::stamps) return k_lin<2, true, FAST>;      // (the probe writes the shared state: same fit as the plain launches)
+        if (P.body == LinBody::dump) return k_lin<1, true, FAST>;
+    }
+    if (P.one_wave()) return k_lin<0, true, FAST, false, true, SLICE, GRIDS>;
+    return P.fused() ? k_lin<0, true, FAST, false, false, SLICE, GRIDS> : k_lin<0, false, FAST, false, false, SLICE, GRIDS>;
+}
+
+// Queue: gate, start event, pass, k_lin (k_sum_tiles behind one-wave blocks), k_finalize, end event, dump readback
+template <bool FAST>
+static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
+    const bool gated = L.kind == LinKind::gated, team = P.pass == LinPass::team, slice = L.kind == LinKind::frames || L.kind == LinKind::pairs;
+    const uint32_t n = (uint32_t)L.n;
+    const unsigned long long seq = ++c->seq;
+    FinArgs fin{S.d_tickets.data(), S.h_out.dev(), seq, P.direct ? 1u : 0u, P.n_chunks};
+    if (P.fused()) S.tickets_dirty = true;    // cleared again once this launch is known to have completed
+    // kernel timing: HIP events around every opt_time_kernels-th linearisation (each timed launch costs ~10 us of host time)
+    bool timed = c->opt_time_kernels > 0 && (c->launch_counter++ % (uint64_t)c->opt_time_kernels) == 0;
+    if (timed && !S.ev0) timed = false;               // (the slot's events are created with the context)
+    const uint32_t *abort_flag = nullptr;
+    // a launch that was queued and must not run after all (errors below): call the gate off, forget what the states were about to hold
+    auto bail = [&](const char *what, hipError_t e) {
+        if (e == hipSuccess) return DCREG_OK;
+        free_tmp(S);
+        if (gated) gate_call_off(c);
+        drop_warm(c);
+        c->fail("%s failed: %s", what, hipGetErrorString(e));
+        return DCREG_E_DEVICE;
+    };
+    auto record = [&](hipEvent_t ev) { return bail("hipEventRecord", timed ? hipEventRecord(ev, c->stream) : hipSuccess); };
     GateArgs gt{nullptr, nullptr, 0ull, nullptr, nullptr, 0u};
-    const bool gate_inside = gated && c->opt_gate_in_kernel && nbx <= (uint32_t)kChunk && !adv && !dbg_host;
-    const PoseArg *lin_poses = d_poses;            // what k_lin reads its pose from (null: pose1)
+    const PoseArg *lin_poses = L.d_poses;          // what k_lin reads its pose from (null: pose1)
     if (gated) {
         const unsigned long long want = ++c->gate_seq;
-        if (gate_inside) {
-            gt = GateArgs{c->h_gate.dev(), c->d_gate_dev.data(), want, team ? c->d_gate_pose.data() : nullptr, team ? c->d_gate_abort.data() : nullptr, one.fresh};
+        if (P.gate_inside) {
+            gt = GateArgs{c->h_gate.dev(), c->d_gate_dev.data(), want, team ? c->d_gate_pose.data() : nullptr, team ? c->d_gate_abort.data() : nullptr, L.one.fresh};
             if (team) abort_flag = c->d_gate_abort.data();        // (k_lin behind the teams reads what their polling wave left, as behind k_gate)
             else lin_poses = nullptr;                      // (k_lin itself is the gated kernel: pose1 carries state / fresh)
         } else {
-            hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, c->h_gate.dev(), want, c->d_gate_pose.data(), one.fresh, c->d_gate_abort.data());
+            hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, c->h_gate.dev(), want, c->d_gate_pose.data(), L.one.fresh, c->d_gate_abort.data());
             abort_flag = c->d_gate_abort.data();
         }
     }
-    if (timed) {                           // after the gate: the events bracket the linearisation, not the wait for the pose
-        const hipError_t ee = hipEventRecord(S.ev0, c->stream);
-        if (ee != hipSuccess) return bail("hipEventRecord", ee);
+    if (int rc = record(S.ev0)) return rc;         // after the gate: the events bracket the linearisation, not the wait for the pose
+    if (P.pass == LinPass::advance)
+        hipLaunchKernelGGL(k_advance<FAST>, dim3(blocks_for(L.n, kAdvTile)), dim3(kLinBlock), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, L.d_poses, L.a,
+                           c->d_adv_counts.data(), abort_flag);
+    if (team) {      // with the gate inside, the teams are the gated kernel
+        const auto pass = P.gate_inside ? k_advance_team<FAST, true> : k_advance_team<FAST>;
+        hipLaunchKernelGGL(pass, dim3(blocks_for(L.n, kTeamTile)), dim3(kWave), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, P.gate_inside ? nullptr : L.d_poses,
+                           L.a, c->d_adv_counts.data(), P.gate_inside ? nullptr : abort_flag, c->opt_team_stamps ? c->d_team_stamps.data() : nullptr, gt);
     }
-    const bool fast = c->opt_fast_plane;
-    if (adv) {
-        if (fast) hipLaunchKernelGGL((k_advance<true>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag);
-        else hipLaunchKernelGGL((k_advance<false>), dim3(n_tiles), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag);
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return bail("advance pass launch", le);
+    if (P.pass != LinPass::none) {
+        if (int rc = bail(team ? "team advance pass launch" : "advance pass launch", hipGetLastError())) return rc;
         c->n_advance_launches += 1;
     }
-    if (team) {
-        unsigned long long *stamps = team_stamps;
-        if (gate_inside) {      // the teams are the gated kernel
-            if (fast) hipLaunchKernelGGL((k_advance_team<true, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts.data(), (const uint32_t *)nullptr, stamps, gt);
-            else hipLaunchKernelGGL((k_advance_team<false, true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, (const PoseArg *)nullptr, a, c->d_adv_counts.data(), (const uint32_t *)nullptr, stamps, gt);
-        } else {
-            if (fast) hipLaunchKernelGGL((k_advance_team<true>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag, stamps, gt);
-            else hipLaunchKernelGGL((k_advance_team<false>), dim3(n_tiles), dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, d_poses, a, c->d_adv_counts.data(), abort_flag, stamps, gt);
-        }
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return bail("team advance pass launch", le);
-        c->n_advance_launches += 1;
+    const bool one = P.one_wave(); const auto lin = lin_kernel<FAST>(P);      // (one-wave blocks: a grid of tiles)
+    hipLaunchKernelGGL(lin, dim3(one ? P.nbx * (kLinBlock / kWave) : P.nbx, (unsigned)P.n_poses), dim3(one ? kWave : kLinBlock), 0, c->stream,
+                       slice ? L.fs->src.data() : c->d_src.data(), n, c->map.grid, L.one, lin_poses, L.a, S.d_partials.data(), P.nbx, fin, L.dd, abort_flag, gt,
+                       L.d_slices, L.kind == LinKind::pairs ? c->pairs.d_grids.data() : nullptr, L.d_grid_ids);
+    if (one)
+        hipLaunchKernelGGL(slice ? k_sum_tiles<true> : k_sum_tiles<false>, dim3(P.n_chunks, (unsigned)P.n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(),
+                           P.nbx, S.h_out.dev(), seq, abort_flag, L.d_slices);
+    // an invalid launch (bad grid, too many resources) must surface here, not as a spin timeout in end()
+    if (int rc = bail("linearisation kernel launch", hipGetLastError())) return rc;
+    if (!P.fused()) {
+        hipLaunchKernelGGL(slice ? k_finalize<true> : k_finalize<false>, dim3((unsigned)P.n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), P.nbx,
+                           S.h_out.dev(), seq, L.d_slices);
+        if (int rc = bail("k_finalize launch", hipGetLastError())) return rc;
     }
-    {
-        const dim3 grid(nbx, (unsigned)n_poses);
-#define DCREG_LAUNCH_LIN(MODE, FUSED, FAST)                                                                                              \
-    hipLaunchKernelGGL((k_lin<MODE, FUSED, FAST>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a,  \
-                       S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr)
-#define DCREG_LAUNCH_FRAMES(FUSED, FAST, ONE_)                                                                                           \
-    hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid,       \
-                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, \
-                       abort_flag, gt, d_slices, nullptr, nullptr)
-#define DCREG_LAUNCH_PAIRS(FUSED, FAST, ONE_)                                                                                            \
-    hipLaunchKernelGGL((k_lin<0, FUSED, FAST, false, ONE_, true, true>), ONE_ ? dim3(nbx * (kLinBlock / kWave), (unsigned)n_poses) : grid, \
-                       dim3(ONE_ ? kWave : kLinBlock), 0, c->stream, d_src, (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, \
-                       abort_flag, gt, d_slices, c->pairs.d_grids.data(), d_grid_ids)
-        if (grid_ids) {                    // the scan pairs of dcreg_register_pairs: every pose reads its own slice and its own target grid
-            if (one_wave) {
-                if (fast) DCREG_LAUNCH_PAIRS(true, true, true); else DCREG_LAUNCH_PAIRS(true, false, true);
-                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, d_slices);
-            }
-            else if (fused) { if (fast) DCREG_LAUNCH_PAIRS(true, true, false); else DCREG_LAUNCH_PAIRS(true, false, false); }
-            else { if (fast) DCREG_LAUNCH_PAIRS(false, true, false); else DCREG_LAUNCH_PAIRS(false, false, false); }
-        } else
-        if (frame_ids) {                   // the frames of dcreg_register_frames: every pose reads its own slice
-            if (one_wave) {
-                if (fast) DCREG_LAUNCH_FRAMES(true, true, true); else DCREG_LAUNCH_FRAMES(true, false, true);
-                hipLaunchKernelGGL(k_sum_tiles<true>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, d_slices);
-            }
-            else if (fused) { if (fast) DCREG_LAUNCH_FRAMES(true, true, false); else DCREG_LAUNCH_FRAMES(true, false, false); }
-            else { if (fast) DCREG_LAUNCH_FRAMES(false, true, false); else DCREG_LAUNCH_FRAMES(false, false, false); }
-        } else
-        if (gate_inside && !team) {        // k_lin is the gated kernel (fused, MODE 0: a gated launch is never a dump)
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, true>), grid, dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-        } else
-        if (stamps_only) { if (fast) DCREG_LAUNCH_LIN(2, true, true); else DCREG_LAUNCH_LIN(2, true, false); }     // (the probe writes the shared state: same fit as the plain launches)
-        else if (dbg_host) { if (fast) DCREG_LAUNCH_LIN(1, true, true); else DCREG_LAUNCH_LIN(1, true, false); }
-        else if (one_wave) {               // one-wave blocks: a grid of tiles
-            const dim3 tiles(nbx * (kLinBlock / kWave), (unsigned)n_poses);
-            if (fast) hipLaunchKernelGGL((k_lin<0, true, true, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            else hipLaunchKernelGGL((k_lin<0, true, false, false, true>), tiles, dim3(kWave), 0, c->stream, c->d_src.data(), (uint32_t)n, c->map.grid, one, lin_poses, a, S.d_partials.data(), nbx, fin, dd, abort_flag, gt, nullptr, nullptr, nullptr);
-            hipLaunchKernelGGL(k_sum_tiles<false>, dim3(n_chunks, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, abort_flag, nullptr);
-        }
-        else if (fused) { if (fast) DCREG_LAUNCH_LIN(0, true, true); else DCREG_LAUNCH_LIN(0, true, false); }
-        else { if (fast) DCREG_LAUNCH_LIN(0, false, true); else DCREG_LAUNCH_LIN(0, false, false); }
-#undef DCREG_LAUNCH_LIN
-#undef DCREG_LAUNCH_FRAMES
-#undef DCREG_LAUNCH_PAIRS
-    }
-    {   // an invalid launch (bad grid, too many resources) must surface here, not as a spin timeout in end()
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return bail("linearisation kernel launch", le);
-    }
-    if (!fused) {
-        if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, d_slices);
-        else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.d_partials.data(), nbx, S.h_out.dev(), seq, (const uint2 *)nullptr);
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return bail("k_finalize launch", le);
-    }
-    if (timed) {                           // brackets the linearisation's kernels
-        const hipError_t ee = hipEventRecord(S.ev1, c->stream);
-        if (ee != hipSuccess) return bail("hipEventRecord", ee);
-    }
-    if (dbg_host) {
+    if (int rc = record(S.ev1)) return rc;         // brackets the linearisation's kernels
+    if (const dcreg_lin_debug *dbg = L.dbg) {
+        const DebugDev &dd = L.dd;
         hipError_t ce = hipSuccess;
         auto back = [&](void *dst, const void *srcp, size_t bytes) { if (ce == hipSuccess && srcp) ce = hipMemcpyAsync(dst, srcp, bytes, hipMemcpyDeviceToHost, c->stream); };
-        back(dbg_host->nn_idx, dd.nn_idx, sizeof(int32_t) * 5 * n);
-        back(dbg_host->nn_d2, dd.nn_d2, sizeof(float) * 5 * n);
-        back(dbg_host->flag, dd.flag, (size_t)n);
-        back(dbg_host->normal, dd.normal, sizeof(double) * 3 * n);
-        back(dbg_host->r, dd.r, sizeof(double) * n);
-        back(dbg_host->s, dd.s, sizeof(double) * n);
-        back(dbg_host->stats, dd.stats, sizeof(uint32_t) * n);
-        back(dbg_host->stamps, dd.stamps, sizeof(unsigned long long) * 8 * (kLinBlock / 64) * (size_t)nbx);
-        if (ce != hipSuccess) {
-            (void)hipStreamSynchronize(c->stream);
-            return bail("copying the debug dump back", ce);
-        }
+        back(dbg->nn_idx, dd.nn_idx, sizeof(int32_t) * 5 * n);
+        back(dbg->nn_d2, dd.nn_d2, sizeof(float) * 5 * n);
+        back(dbg->flag, dd.flag, (size_t)n);
+        back(dbg->normal, dd.normal, sizeof(double) * 3 * n);
+        back(dbg->r, dd.r, sizeof(double) * n);
+        back(dbg->s, dd.s, sizeof(double) * n);
+        back(dbg->stats, dd.stats, sizeof(uint32_t) * n);
+        back(dbg->stamps, dd.stamps, sizeof(unsigned long long) * 8 * (kLinBlock / 64) * (size_t)P.nbx);
+        if (ce != hipSuccess) { (void)hipStreamSynchronize(c->stream); return bail("copying the debug dump back", ce); }
     }
-    c->n_launches += 1; c->n_poses_launched += n_poses; c->n_points_launched += (int64_t)n_poses * n;
-    if (uses_state) c->state_valid = true;          // once this launch has run, the state holds a search of the current clouds
-    S.pending = true; S.n_poses = n_poses; S.n_chunks = n_chunks; S.n_rows = n_rows; S.fused = fused; S.direct = direct; S.timed = timed;
-    S.seq = seq; S.sync = dbg_host != nullptr;
-    S.stamps_only = stamps_only;
-    S.advanced = (adv ? 1 : (team ? 2 : 0)) | (one_wave ? 4 : 0);
-    S.coded = a.count_scale != 0.0;        // how THIS launch's count slots are to be read (the source may be replaced while it is pending)
+    c->n_launches += 1; c->n_poses_launched += P.n_poses; c->n_points_launched += (int64_t)P.n_poses * L.n;
+    if (L.uses_state(c)) c->state_valid = true;          // once this launch has run, the state holds a search of the current clouds
+    S.pending = true; S.plan = P; S.timed = timed; S.seq = seq; S.sync = L.dbg != nullptr;
+    S.coded = L.a.count_scale != 0.0;        // how THIS launch's count slots are to be read (the source may be replaced while it is pending)
     if (gated) {
-        c->gate_slot = slot;
-        c->gate_uses_state = uses_state; c->gate_state_was_valid = state_was_valid;
+        c->gate_slot = L.slot;
+        c->gate_uses_state = L.uses_state(c); c->gate_state_was_valid = L.state_was_valid;
     }
     return DCREG_OK;
+}
+
+// gated = true: a single-pose launch whose pose arrives later through the gate (R9, t3 ignored; dcreg_linearize_gate_open /
+// _gate_abort decide its fate)
+// frame_ids != null: pose i linearises frame frame_ids[i] of the frames loaded by dcreg_frames_load instead of the ctx's source, with the
+// frames' own neighbour states (state_ids name those); the ctx's source and states are not touched
+// grid_ids != null (with frame_ids): the scan pairs of dcreg_register_pairs - pose i linearises source frame_ids[i] of the pairs' sources
+// against target grid_ids[i] of the pairs' build batch (kernels.hpp k_lin GRIDS); the ctx's target and window index are not touched
+static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                           const dcreg_lin_params *p, dcreg_lin_debug *dbg_host, bool gated = false, const int32_t *frame_ids = nullptr,
+                           const int32_t *grid_ids = nullptr) {
+    if (!c) return DCREG_E_INVALID;
+    LinLaunch L{slot, n_poses, R9, t3, state_ids, frame_ids, grid_ids, p, dbg_host, gated ? LinKind::gated : LinKind::single};
+    if (int rc = lin_check(c, L)) return rc;
+    if (c->need_set_device) { HIP_TRY(c, hipSetDevice(c->device)); }
+    // which index the launch searches (context.hpp, the window of a large map): single-pose product launches the window around their pose, a
+    // gated launch whatever is active (its pose is checked when the gate opens, against the window's pad: a gated launch whose search radius
+    // needs a larger pad than the window was built with runs on the whole map), everything else the whole map
+    if (gated && c->roi_active && roi_pad_for(c, p->search_radius) > c->roi_pad) (void)roi_deactivate(c);
+    if (!gated && L.kind != LinKind::pairs && (c->roi_active || roi_wanted(c))) {
+        const bool product = L.kind == LinKind::single || L.kind == LinKind::stamps;
+        if (int rc = product ? roi_ensure(c, L.R9, L.t3, p->search_radius) : roi_deactivate(c)) return rc;
+    }
+    L.a = make_lin_args(c, p, L.kind != LinKind::pairs, L.n);
+    // the parameters the stored certificates, gate bits and planes depend on (context.hpp StateKey): a launch with other values
+    // starts from empty states.  (weight_slope, weight_min and use_weight_derivative are not among them: the weight gate and the row
+    // are evaluated on the stored plane in every launch - tests/test_gpu_gate_edges.py alternates them on one context.)
+    const LinArgs &a = L.a;
+    L.key.radius_sq = a.radius_sq; L.key.max_thick_sq = a.max_thick_sq; L.key.min_norm = a.min_norm;
+    L.key.radius_sq_f = a.radius_sq_f; L.key.cert_r_out = a.cert_r_out; L.key.cert_r_in = a.cert_r_in; L.key.fast_plane = c->opt_fast_plane ? 1 : 0;
+    if (L.own() && !gated) {
+        const double jump = c->last_pose_valid ? pose_jump(c, L.R9, L.t3, c->last_R, c->last_t) : 1e300;
+        if (c->hint_unknown && jump <= 0.5 * c->map.grid.h) c->hint_misalign = c->hint_last;      // the same trajectory, continued
+        // ... and what the last completed launch searched says nothing about a launch half a cell or more away from it (the first
+        // launch of a new run): expect a search of everything - for this launch and for the one that may be queued behind it before
+        // its counts are known (scheduling only: which kernels carry the launch out)
+        if (jump > 0.5 * c->map.grid.h) { c->last_searched = c->n_src; c->last_points = c->last_searched; }
+        c->hint_unknown = false;
+        std::memcpy(c->last_R, L.R9, sizeof(c->last_R)); std::memcpy(c->last_t, L.t3, sizeof(c->last_t));
+        c->last_pose_valid = true;
+    }
+    if (!gated && order_wanted(c, L)) {
+        // the estimate holds for poses near the one it was made at (within a cell for every point)
+        bool stale = !c->order_valid;
+        // (counted in c->seq, the launch number that is never reset: round 6 found this test dead - it compared with n_launches, which
+        //  dcreg_launch_stats_get(reset) zeroes, so that after one reset of the statistics the order of the moment was kept for good; with
+        //  `bench.py --steps 20 --warmup 5` that was the order estimated at an ALIGNED pose, i.e. none: 355 / 314 / 260 us for the first
+        //  launches of every later run instead of 264 / 216 / 205)
+        if (!stale && (int64_t)c->seq - c->est_launch >= 16)       // (a loop of ungated launches does not re-estimate at every step)
+            stale = pose_jump(c, L.R9, L.t3, c->est_R, c->est_t) > c->map.grid.h;
+        if (int rc = stale ? estimate_dispatch_order(c, L.R9, L.t3, a.max_ring) : DCREG_OK) return rc;
+    }
+    // the ctx's own state (single-pose kinds)
+    if (L.uses_state(c) && !(L.key == c->state_key)) { c->state_valid = false; c->state_key = L.key; }
+    L.state_was_valid = c->state_valid;
+    L.one.state = kNoIdx; L.one.fresh = 1;
+    if (L.own()) {
+        std::memcpy(L.one.R, L.R9, sizeof(L.one.R)); std::memcpy(L.one.t, L.t3, sizeof(L.one.t));
+        if (c->opt_warm) {
+            const size_t stride = ((size_t)L.n + 63) & ~(size_t)63;
+            if (!c->state_valid || c->state_stride != stride) {
+                if (c->d_state.ensure(c, kStateRows * stride)) return DCREG_E_NOMEM;
+                c->state_stride = stride; c->state_valid = false;
+            }
+            L.one.state = 0; L.one.fresh = c->state_valid ? 0u : 1u;
+            L.a.state = c->d_state.data(); L.a.state_stride = (uint32_t)c->state_stride;
+        }
+    }
+    const LinPlan P = lin_plan(c, L, L.one.fresh != 0u);
+    LinSlot &S = c->slots[slot];
+    if (int rc = lin_reserve(c, S, L, P)) return rc;
+    return c->opt_fast_plane ? lin_queue<true>(c, S, L, P) : lin_queue<false>(c, S, L, P);
 }
 
 // wait for the result rows of a launch.  Hot path: spin on the rows the kernels publish into pinned host memory (check word).  A
@@ -1940,14 +1935,14 @@ static int wait_rows(dcreg_ctx *c, LinSlot &S) {
     auto touched = [&](size_t i) {
         return __atomic_load_n((const unsigned long long *)(S.h_out.data() + i * kSlots) + 31, __ATOMIC_RELAXED) != S.row_chk[i];
     };
-    S.h_rows.resize(S.n_rows * kSlots);
+    S.h_rows.resize(S.plan.n_rows * kSlots);
     // rows are taken in the order they arrive (the last one to come is then the only one left to check), not in index order
-    S.row_done.assign(S.n_rows, 0);
-    if (S.row_chk.size() < S.n_rows) S.row_chk.resize(S.n_rows, 0ull);
-    size_t pending = S.n_rows;
+    S.row_done.assign(S.plan.n_rows, 0);
+    if (S.row_chk.size() < S.plan.n_rows) S.row_chk.resize(S.plan.n_rows, 0ull);
+    size_t pending = S.plan.n_rows;
     uint64_t spins = 0;
     while (pending) {
-        for (size_t i = 0; i < S.n_rows; ++i)
+        for (size_t i = 0; i < S.plan.n_rows; ++i)
             if (!S.row_done[i] && touched(i) && arrived(i)) { S.row_done[i] = 1; --pending; }
         if (!pending) break;
         __builtin_ia32_pause();
@@ -1957,7 +1952,7 @@ static int wait_rows(dcreg_ctx *c, LinSlot &S) {
         if (c->gate_slot >= 0) (void)dcreg_linearize_gate_abort(c);      // nothing may wait behind us while we drain the stream
         const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { c->fail("device fault while waiting for a linearisation: %s", hipGetErrorString(e)); return DCREG_E_DEVICE; }
-        for (size_t i = 0; i < S.n_rows; ++i)
+        for (size_t i = 0; i < S.plan.n_rows; ++i)
             if (!S.row_done[i]) {
                 if (!arrived(i)) { c->fail("linearisation result never arrived"); return DCREG_E_DEVICE; }
                 S.row_done[i] = 1; --pending;
@@ -1995,21 +1990,22 @@ static int linearize_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
         launch_ms = ms;
     }
     double total[kSlots];
-    if (S.direct) {  // the rows of the blocks of ONE chunk, added exactly as block_sum_rows adds them on the device (so a pose gives
+    const LinPlan &P = S.plan;
+    if (P.direct) {  // the rows of the blocks of ONE chunk, added exactly as block_sum_rows adds them on the device (so a pose gives
                      // bitwise the same sums alone and in a batch): lane group g takes rows g, g + G, ..., then the G sums in order
         constexpr int G = kLinBlock / 32;
         for (int k = 0; k < 31; ++k) {
             double tot = 0.0;
             for (int g = 0; g < G; ++g) {
                 double t = 0.0;
-                for (size_t r = (size_t)g; r < S.n_rows; r += G) t += S.h_rows[r * kSlots + k];
+                for (size_t r = (size_t)g; r < P.n_rows; r += G) t += S.h_rows[r * kSlots + k];
                 tot += t;
             }
             total[k] = 0.0 + tot;                            // (the chunk total enters a sum that starts at zero, as everywhere)
         }
-    } else if (S.fused && S.n_poses == 1) {   // add the chunk rows in index order (fixed order: deterministic)
+    } else if (P.n_poses == 1) {   // add the chunk rows in index order (fixed order: deterministic)
         for (int k = 0; k < 31; ++k) total[k] = 0.0;
-        for (uint32_t ch = 0; ch < S.n_chunks; ++ch) {
+        for (uint32_t ch = 0; ch < P.n_chunks; ++ch) {
             const double *row = S.h_rows.data() + (size_t)ch * kSlots;
             for (int k = 0; k < 31; ++k) total[k] += row[k];
         }
@@ -2017,8 +2013,8 @@ static int linearize_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     // the count slots carry two numbers each when the launch was asked to report what it did (LinArgs::count_scale): exact integers
     const bool coded = S.coded;
     int64_t searched = coded ? 0 : -1, refitted = coded ? 0 : -1;
-    for (int i = 0; i < S.n_poses; ++i) {
-        const double *o = (S.fused && S.n_poses == 1) ? total : S.h_rows.data() + (size_t)i * kSlots;      // (batches: one row per pose)
+    for (int i = 0; i < P.n_poses; ++i) {
+        const double *o = P.n_poses == 1 ? total : S.h_rows.data() + (size_t)i * kSlots;      // (batches: one row per pose)
         std::memcpy(outs[i].H_upper, o, 21 * sizeof(double));
         std::memcpy(outs[i].g, o + 21, 6 * sizeof(double));
         outs[i].sum_r2 = o[27]; outs[i].sum_b2 = o[28];
@@ -2030,14 +2026,14 @@ static int linearize_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
         }
         outs[i].n_eff = c29; outs[i].n_pt = c30;
     }
-    c->last_points = (int64_t)S.n_poses * c->n_src;
+    c->last_points = (int64_t)P.n_poses * c->n_src;
     // (a point whose new certificate has no slack at all - distance ties - is served by an advance pass and searched again by k_lin: it is
     // counted twice.  The scheduling rules and the launch log read fractions: never more than every point.  ADVICE round 5)
     if (searched > c->last_points) searched = c->last_points;
     if (refitted > c->last_points) refitted = c->last_points;
     c->last_searched = searched; c->last_refitted = refitted;
     if (c->opt_record_launches && c->launch_series.size() < ((size_t)1 << 20))
-        c->launch_series.push_back(dcreg_ctx::LaunchRec{(double)launch_ms, searched, refitted, c->last_points, S.advanced});
+        c->launch_series.push_back(dcreg_ctx::LaunchRec{(double)launch_ms, searched, refitted, c->last_points, P.passes()});
     return DCREG_OK;
 }
 

@@ -91,8 +91,23 @@ private:
     size_t cap_ = 0;
 };
 
-// buffers and in-flight state of one linearisation slot
+// What a linearisation launch is and how it is carried out (context.hip linearize_begin: lin_check settles the kind, lin_plan the rest)
+enum class LinKind : uint8_t { batch, frames, pairs, single, gated, dump, stamps };   // single .. stamps: one pose on the ctx's own source
+enum class LinPass : uint8_t { none, advance, team };     // in front of k_lin: nothing, k_advance, k_advance_team (dcreg_launch_series_passes)
+enum class LinBody : uint8_t { chunked, fused, one_wave, gated, dump, stamps };   // the k_lin instantiation (context.hip lin_kernel)
+struct LinPlan {
+    LinKind kind = LinKind::single; LinPass pass = LinPass::none; LinBody body = LinBody::fused;
+    int n_poses = 0; uint32_t nbx = 0, n_chunks = 0;    // query blocks per pose, chunks of kChunk of them
+    size_t n_rows = 0;                 // result rows the host waits for
+    bool direct = false;               // the rows are block rows of one chunk (kernels.hpp FinArgs::direct)
+    bool gate_inside = false;          // the gated launch waits for its pose in its first kernel (kernels.hpp gate_wait)
+    bool ordered = false, use_cert = true;   // heavy query-block groups first (LinArgs::n_groups); certificates in use (LinArgs::use_cert)
+    bool fused() const { return body != LinBody::chunked; }     // the kernels sum and publish per pose (no k_finalize)
+    bool one_wave() const { return body == LinBody::one_wave; }
+    int passes() const { return (int)pass | (one_wave() ? 4 : 0); }   // dcreg_launch_series_passes: + 4 = k_lin ran in one-wave blocks
+};
 
+// buffers and in-flight state of one linearisation slot
 struct LinSlot {
     DevBuf<double> d_partials;
     // batched poses: ONE pinned staging block [PoseArg x n | pose ids x n] and its device copy (one plain DMA per launch; a pageable
@@ -104,17 +119,12 @@ struct LinSlot {
     DevBuf<unsigned int> d_tickets;
     bool tickets_dirty = false;    // a launch may have died half-way: clear the tickets before the next one
     std::vector<DevBuf<unsigned char>> tmp_dev;   // debug dump buffers of the launch in flight
-    bool pending = false, fused = false, timed = false, sync = false;
-    int n_poses = 0;
-    uint32_t n_chunks = 0;
-    bool direct = false;           // the rows are block rows of one chunk (kernels.hpp FinArgs::direct)
+    bool pending = false, timed = false, sync = false;
+    LinPlan plan;                  // of the launch in flight
     std::vector<uint8_t> row_done; // wait_rows: rows taken so far
     std::vector<unsigned long long> row_chk;   // ... and the check word each row carried when it was last taken
-    size_t n_rows = 0;
     unsigned long long seq = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // "time_kernels": the events of this slot's launch (the two slots alternate in a pipelined run)
-    bool stamps_only = false;
-    int advanced = 0;              // an advance pass ran in front of the launch in flight: 1 = k_advance, 2 = k_advance_team (kernels.hpp); + 4: k_lin ran in one-wave blocks
     bool coded = false;            // the launch in flight reports searched / refitted counts above its count slots (LinArgs::count_scale)
 };
 
@@ -319,10 +329,8 @@ struct dcreg_ctx {
     bool opt_spin = true;          // wait for results by spinning on pinned memory instead of hipStreamSynchronize
     bool need_set_device = true;
     unsigned long long seq = 0;
-    int opt_xcd_chunk = 16;        // query-block -> XCD mapping (kernels.hpp xcd_remap): runs of 16 blocks round-robin (measured: C4 -13 %)
     bool opt_fast_plane = true;    // plane_fit_qr_fast (search.hpp) instead of the Eigen-shaped plane_fit_qr
     bool opt_gap_field = true;     // build the empty-space distance field of the target grid
-    bool opt_direct_rows = true;   // single-pose launches of at most kChunk blocks publish block rows; the host adds them
     bool opt_far_bound = true;     // far queries with a loose bound start from the points around the nearest occupied cell (search.hpp lin_search6)
     bool opt_keep_source_order = false;   // experiments only
     // heavy groups first (kernels.hpp k_group_cost): the dispatch order of the query-block groups, estimated once per cloud pair
@@ -342,18 +350,13 @@ struct dcreg_ctx {
     bool hint_unknown = false;
     double hint_last = 1e300, last_R[9] = {}, last_t[3] = {};
     bool last_pose_valid = false;
-    bool opt_fused_batches = true; // batched launches of one-chunk poses sum and publish per pose inside k_lin (kernels.hpp FinArgs::chunks_per_pose)
     double opt_curve_x_scale = 1.0;  // kernels.hpp k_curve_keys: < 1 stretches the patches of the source's curve order along x
     int64_t opt_max_table_entries = (int64_t)1 << 30;   // entries of the dense cell table (x sub-cells of the bounding box) before the cell edge grows
-    double opt_far_loose = 1.5;    // search.hpp lin_search6: when a start bound is loose enough to be worth a probe (cells)
-    // the advance pass (kernels.hpp k_advance): 0 never, 1 by the rule below, 2 whenever a launch can take it (tests)
+    // the advance pass (kernels.hpp k_advance) and its small-frame form (k_advance_team): 0 never, 1 by the rules of context.hip lin_plan,
+    // 2 whenever a launch can take it (tests)
     int opt_advance = 1;
-    double opt_advance_lo = 0.01, opt_advance_hi = 0.45;     // ... the last completed launch searched between these fractions of its points
-    int opt_advance_min_blocks = 2048;                        // ... and the cloud has at least this many query blocks (twice what the device holds)
-    // its small-frame form (k_advance_team): same switch values; rule: at most max_points source points, the last completed launch
-    // searched at least min_frac of them, the map has at least min_cell_pts points per occupied cell
+    int opt_advance_min_blocks = 2048;   // k_advance by the rule: the cloud has at least this many query blocks (twice what the device holds)
     int opt_team_pass = 1;
-    double opt_team_pass_max_points = 16384.0, opt_team_pass_min_frac = 0.5, opt_team_pass_min_cell_pts = 3.0;
     bool opt_team_stamps = false;
     DevBuf<unsigned long long> d_team_stamps; uint32_t team_stamps_n = 0;
     DevBuf<uint32_t> d_adv_counts; bool adv_counts_dirty = true;

@@ -252,6 +252,37 @@ def test_one_wave_blocks_by_the_rule_in_whole_runs():
     assert picked["rule"][0] == 1 and picked["rule"][24] == 0           # the first launch of the first run, its last one
 
 
+def test_gated_launches_in_four_wave_blocks_are_reported_so():
+    """Pipelined run on the 7.5 k fixture (30 query blocks) with one-wave blocks forced ("one_wave" = 2): a gated launch that waits for
+    its pose inside k_lin ("gate_in_kernel" = 1) runs the four-wave gated k_lin, and the launch series reports it without the one-wave
+    bit; behind the gate kernel ("gate_in_kernel" = 0) the same launches run in one-wave blocks and say so.  Iteration by iteration the
+    runs are bitwise those of a run without one-wave blocks."""
+    pts = h.cylinder_cloud()
+    T0 = h.pose6d_matrix(**h.PAPER_INIT)
+    cfg = api.default_config(search_radius=1.0, max_iterations=30, KAPPA_TARGET=10.0, STD_REG_GAMMA=100.0, use_weight_derivative=1,
+                             always_compute_schur=1)
+    logs, ser = {}, {}
+    for name, opts in (("inside", {"one_wave": 2, "gate_in_kernel": 1}), ("gate_kernel", {"one_wave": 2, "gate_in_kernel": 0}),
+                       ("off", {"one_wave": 0})):
+        c = api.Context(0)
+        for k, v in opts.items():
+            c.set_option(k, v)
+        c.set_option("record_launches", 1)
+        c.set_target(pts, 1.0); c.set_source(pts)
+        res, lg = c.icp_run(T0, "Ours", cfg)
+        logs[name] = [(np.array(L.H_upper[:]), np.array(L.gradient[:]), L.effective_points, L.corr_pt_count, np.array(L.transform_matrix[:]))
+                      for L in lg[:res.iterations]]
+        ser[name] = c.launch_series(reset=True)["one_wave"]
+        c.close()
+    assert len(ser["inside"]) >= 5 and len(logs["off"]) >= 5
+    assert ser["inside"][0] == 1 and not ser["inside"][1:].any()      # the first launch of a run is not gated
+    assert ser["gate_kernel"].all() and not ser["off"].any()
+    for name in ("inside", "gate_kernel"):
+        assert len(logs[name]) == len(logs["off"])
+        for it, (x, y) in enumerate(zip(logs[name], logs["off"])):
+            assert np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1]) and x[2] == y[2] and x[3] == y[3] and np.array_equal(x[4], y[4]), (name, it)
+
+
 def test_montecarlo_batches_in_one_wave_blocks_give_the_same_records():
     """The Monte-Carlo experiment (batched launches of 30-block poses, trials at every stage of their runs side by side) with the batches'
     linearisation kernel in one-wave blocks ("one_wave_batches" = 1, the default: a tile row per wave, k_sum_tiles with one block per pose

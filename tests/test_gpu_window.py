@@ -332,6 +332,65 @@ def test_non_finite_poses_are_refused():
         _close(whole, win)
 
 
+@pytest.mark.timeout(600)
+def test_refused_launches_change_nothing():
+    """A launch refused for its parameters or its warm-state ids (DCREG_E_INVALID) leaves the context as it was: window box, rebuild
+    count and active index, the neighbour states and their keys.  Refused at a pose 10 m off the window, the next launch at the old pose
+    searches from the state the earlier launches left and gives the whole map's sums; a batch at the old pose after a refused batch at
+    another radius finds its warm states as they were."""
+    tgt, src, T = _scene()
+    Rg, tg = T[:3, :3], T[:3, 3]
+    Rf, tf = Rg, tg + np.array([10.0, 0.0, 0.0])
+    whole, win = _pair(tgt, src)
+    try:
+        P = _prm(2.0)
+        for c in (whole, win):
+            c.set_option("record_launches", 1)
+            c.reserve_warm_states(2)
+        for _ in range(2):
+            win.linearize(Rg, tg, P)
+            kept = whole.linearize_batch_warm(np.stack([Rg, Rg]), np.stack([tg, tg]), [0, 1], P)
+        assert win.roi_info()["active"]
+        ref = whole.linearize(Rg, tg, P)
+
+        def prm(**kw):
+            q = _prm(2.0)
+            for k, v in kw.items():
+                setattr(q, k, v)
+            return q
+
+        two = (np.stack([Rf, Rf]), np.stack([tf, tf]))
+        refusals = {
+            "radius 0": lambda c: c.linearize(Rf, tf, prm(search_radius=0.0)),
+            "radius nan": lambda c: c.linearize(Rf, tf, prm(search_radius=np.nan)),
+            "k 3": lambda c: c.linearize(Rf, tf, prm(k=3)),
+            "parameterization 7": lambda c: c.linearize(Rf, tf, prm(parameterization=7)),
+            "unreserved state": lambda c: c.linearize_batch_warm(*two, [0, 2], P),
+            "duplicate state": lambda c: c.linearize_batch_warm(*two, [1, 1], P),
+        }
+        win.launch_series(reset=True)
+        for name, fn in refusals.items():
+            before = win.roi_info()
+            with pytest.raises(api.DcregError) as e:
+                fn(win)
+            assert "failed (-1)" in str(e.value), (name, str(e.value))
+            assert win.roi_info() == before, name
+            out = win.linearize(Rg, tg, P)
+            searched = win.launch_series(reset=True)["searched"]
+            assert len(searched) == 1 and searched[0] < len(src), (name, searched)
+            assert _same_sums(out, ref), name
+        # the batch states: a duplicate id at another search radius (another state key) is refused before the key is taken
+        whole.launch_series(reset=True)
+        with pytest.raises(api.DcregError):
+            whole.linearize_batch_warm(*two, [1, 1], _prm(3.0))
+        outs = whole.linearize_batch_warm(np.stack([Rg, Rg]), np.stack([tg, tg]), [0, 1], P)
+        searched = whole.launch_series(reset=True)["searched"]
+        assert len(searched) == 1 and searched[0] < 2 * len(src), searched
+        assert all(_same_sums(o, k) for o, k in zip(outs, kept))
+    finally:
+        _close(whole, win)
+
+
 # ---------------------------------------------------------------- G: kernel options on the window
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("opts", [{"team_pass": 0}, {"team_pass": 2}, {"advance": 2}, {"one_wave": 2}, {"use_certificates": 0},
