@@ -4,6 +4,7 @@ Python is plumbing here: tests, bench.py and multi-GPU launch use this thin bind
 shared library.  There is no CPU fallback: creating a Context without a usable HIP device raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -145,6 +146,7 @@ EXPORTS = [
     "dcreg_pairs_reset_state", "dcreg_pairs_batch_begin",
     "dcreg_voxel_downsample", "dcreg_voxel_downsample_device", "dcreg_set_source_voxel", "dcreg_set_source_voxel_device",
     "dcreg_set_target_voxel", "dcreg_set_target_voxel_device",
+    "dcreg_deskew", "dcreg_deskew_device", "dcreg_set_source_deskew", "dcreg_set_source_deskew_device",
 ]
 
 _lib = None
@@ -188,6 +190,146 @@ def voxel_params(leaf, mode="centroid", min_points=1):
 
 def _voxel_info_dict(i):
     return {"n_in": i.n_in, "n_finite": i.n_finite, "n_voxels": i.n_voxels, "n_out": i.n_out}
+
+
+class TimeField(C.Structure):
+    _fields_ = [("column", C.c_int), ("type", C.c_int), ("scale", C.c_double)]
+
+
+class SweepMotion(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("t_begin", C.c_double), ("t_end", C.c_double), ("ref", C.c_double),
+                ("span_from_data", C.c_int), ("reserved_", C.c_int)]
+
+
+class DeskewInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_outside", C.c_int64), ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
+_STRUCTS.update({"dcreg_time_field": TimeField, "dcreg_sweep_motion": SweepMotion, "dcreg_deskew_info": DeskewInfo})
+TIME_TYPES = {"f32": 0, "f64": 1, "u32": 2, "u64": 3}      # DCREG_TIME_F32 / _F64 / _U32 / _U64
+
+
+def se3_exp(xi):
+    """SE(3) exponential of xi = (w, v) as include/dcreg.h defines it (series through theta^4 below theta = 1e-3) -> 4x4"""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    w, v = xi[:3], xi[3:]
+    th2 = float(w @ w)
+    th = np.sqrt(th2)
+    if th < 1e-3:
+        A, B, Cc = 1 - th2 / 6 + th2 * th2 / 120, 0.5 - th2 / 24 + th2 * th2 / 720, 1 / 6 - th2 / 120 + th2 * th2 / 5040
+    else:
+        A, B, Cc = np.sin(th) / th, (1 - np.cos(th)) / th2, (th - np.sin(th)) / (th2 * th)
+    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    W2 = W @ W
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + A * W + B * W2
+    T[:3, 3] = (np.eye(3) + B * W + Cc * W2) @ v
+    return T
+
+
+def se3_log(T):
+    """inverse of se3_exp for rotations below pi (angle-axis of R, then v = V^-1 t) -> xi = (w, v)"""
+    T = np.asarray(T, np.float64)
+    R, t = T[:3, :3], T[:3, 3]
+    s = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sn = np.linalg.norm(s)
+    th = np.arctan2(sn, 0.5 * (np.trace(R) - 1.0))
+    th2 = th * th
+    w = s * (1 + th2 / 6 + 7 * th2 * th2 / 360 if th < 1e-3 else th / sn)
+    if th < 1e-3:
+        D = 1 / 12 + th2 / 720 + th2 * th2 / 30240
+    else:
+        A, B = np.sin(th) / th, (1 - np.cos(th)) / th2
+        D = (1 - A / (2 * B)) / th2
+    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    return np.r_[w, (np.eye(3) - 0.5 * W + D * (W @ W)) @ t]
+
+
+def constant_velocity_motion(T_prev, T_last, ratio=1.0):
+    """the motion of the next sweep predicted from the last two registered poses (4x4, sensor -> map): Exp(ratio Log(T_prev^-1 T_last))"""
+    d = np.linalg.inv(np.asarray(T_prev, np.float64).reshape(4, 4)) @ np.asarray(T_last, np.float64).reshape(4, 4)
+    return se3_exp(float(ratio) * se3_log(d))
+
+
+def _check_field(f, stride, what):
+    if not isinstance(f, TimeField):
+        raise ValueError("%s: a time_field is expected, got %r" % (what, type(f).__name__))
+    if f.type not in TIME_TYPES.values():
+        raise ValueError("%s: unknown time type %r" % (what, f.type))
+    wide = f.type in (TIME_TYPES["f64"], TIME_TYPES["u64"])
+    if f.column < 3 or (stride is not None and (f.column >= stride or (wide and f.column + 1 >= stride))):
+        raise ValueError("%s: time column %d outside [3, %s)%s" % (what, f.column, stride, " (a 64-bit stamp takes two slots)" if wide else ""))
+    if not (np.isfinite(f.scale) and f.scale > 0.0):
+        raise ValueError("%s: time scale %r: finite and > 0 expected" % (what, f.scale))
+
+
+def _check_motion(m, what):
+    """the library's refusals of one motion, in plain Python (a call checks one per cloud: numpy's per-call overhead would dominate)"""
+    if not isinstance(m, SweepMotion):
+        raise ValueError("%s: a sweep_motion is expected, got %r" % (what, type(m).__name__))
+    R, t = m.R[:], m.t[:]
+    if not all(math.isfinite(v) for v in R + t):
+        raise ValueError("%s: the motion is not finite" % what)
+    det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6])
+    if not det > 0.0 or any(not abs(R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j] - (i == j)) <= 1e-6 for i in range(3) for j in range(3)):
+        raise ValueError("%s: R is not a rotation (|R^T R - I| > 1e-6 or det <= 0)" % what)
+    sn = 0.5 * math.sqrt((R[7] - R[5]) ** 2 + (R[2] - R[6]) ** 2 + (R[3] - R[1]) ** 2)
+    if not math.atan2(sn, 0.5 * (R[0] + R[4] + R[8] - 1.0)) < math.pi / 2:
+        raise ValueError("%s: the motion rotates by pi/2 or more over the sweep" % what)
+    if not m.span_from_data and not (np.isfinite(m.t_begin) and np.isfinite(m.t_end) and m.t_end >= m.t_begin):
+        raise ValueError("%s: span [%r, %r] is not finite and ordered" % (what, m.t_begin, m.t_end))
+    if not (0.0 <= m.ref <= 1.0):
+        raise ValueError("%s: ref %r outside [0, 1]" % (what, m.ref))
+
+
+def time_field(column, type="f32", scale=1.0):
+    """dcreg_time_field: the stamp at float slot `column` (>= 3) of every record, of type "f32", "f64", "u32" or "u64" (the 64-bit types take
+    two slots, little-endian), scale seconds per unit"""
+    if type not in TIME_TYPES:
+        raise ValueError("time type: one of %s is expected, got %r" % (sorted(TIME_TYPES), type))
+    f = TimeField()
+    f.column, f.type, f.scale = int(column), TIME_TYPES[type], float(scale)
+    _check_field(f, None, "time_field")
+    return f
+
+
+def sweep_motion(R, t, span=None, ref=0.5):
+    """dcreg_sweep_motion: (R 3x3, t 3) = the sensor pose at the end of the span in the frame of the pose at its start; span = (t_begin, t_end)
+    in seconds, or None = the cloud's own minimum / maximum finite stamp; ref = the reference instant in [0, 1] of the span"""
+    R, t = np.asarray(R, np.float64), np.asarray(t, np.float64).reshape(-1)
+    if R.shape != (3, 3) or t.shape != (3,):
+        raise ValueError("sweep_motion: R 3x3 and t 3 are expected, got %s and %s" % (R.shape, t.shape))
+    m = SweepMotion()
+    m.R[:] = [float(v) for v in R.reshape(9)]
+    m.t[:] = [float(v) for v in t]
+    if span is None:
+        m.span_from_data, m.t_begin, m.t_end = 1, 0.0, 0.0
+    else:
+        sp = np.asarray(span, np.float64).reshape(-1)
+        if sp.shape != (2,):
+            raise ValueError("sweep_motion: span = (t_begin, t_end) or None, got %r" % (span,))
+        m.span_from_data, m.t_begin, m.t_end = 0, float(sp[0]), float(sp[1])
+    m.ref = float(ref)
+    _check_motion(m, "sweep_motion")
+    return m
+
+
+def _deskew_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_outside": i.n_outside, "t_min": i.t_min, "t_max": i.t_max}
+
+
+def _motions(motions, n, what):
+    ms = [motions] if isinstance(motions, SweepMotion) else list(motions)
+    if len(ms) == 1 and n != 1:
+        ms = ms * n
+    if len(ms) != n:
+        raise ValueError("%s: one motion per cloud is expected (%d clouds, %d motions)" % (what, n, len(ms)))
+    for m in ms:
+        _check_motion(m, what)
+    arr = (SweepMotion * max(n, 1))()
+    for k, m in enumerate(ms):
+        arr[k] = m
+    return arr
 
 
 def _clouds(clouds, what):
@@ -322,6 +464,13 @@ def load():
         getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(VoxelParams), C.POINTER(VoxelInfo)]
     for name in ("dcreg_set_target_voxel", "dcreg_set_target_voxel_device"):
         getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(VoxelParams), C.c_double, C.POINTER(VoxelInfo)]
+    if hasattr(L, "dcreg_deskew"):             # (absent from an older build loaded through DCREG_LIB for an A/B)
+        L.dcreg_deskew.argtypes = [vp, C.c_int, vp, i64p, C.c_int64, C.POINTER(TimeField), C.POINTER(SweepMotion), C.POINTER(VoxelParams), vp,
+                                   C.c_int64, i64p, C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
+        L.dcreg_deskew_device.argtypes = L.dcreg_deskew.argtypes
+        for name in ("dcreg_set_source_deskew", "dcreg_set_source_deskew_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(TimeField), C.POINTER(SweepMotion), C.POINTER(VoxelParams),
+                                         C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -591,6 +740,69 @@ class Context:
         self._check(self._L.dcreg_set_target_voxel_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(p), float(search_radius),
                                                           C.byref(info)), "dcreg_set_target_voxel_device")
         return _voxel_info_dict(info)
+
+    def deskew(self, clouds, field, motions, leaf=None, mode="centroid", min_points=1):
+        """dcreg_deskew: every cloud moved into the sensor frame at its reference instant from per-point stamps (include/dcreg.h has the
+        rules).  clouds as voxel_downsample takes them, records of at least field.column + 1 (+ 1 for 64-bit stamps) float32 columns; field =
+        time_field(...); motions = one sweep_motion per cloud (or one for all); leaf = None: every point out, in input order, or a voxel
+        leaf: the voxel pass of the deskewed clouds.  -> (output in the shape of the input, deskew info dict, voxel info dict or None)"""
+        xyz, off, was_list = _clouds(clouds, "deskew")
+        n = len(off) - 1
+        _check_field(field, xyz.shape[1], "deskew")
+        mots = _motions(motions, n, "deskew")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        out = np.empty((max(int(off[-1]), 1), 3), np.float32)
+        out_off = np.zeros(n + 1, np.int64)
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_deskew(self._h, n, xyz.ctypes.data, off.ctypes.data_as(i64p), xyz.shape[1], C.byref(field), mots,
+                                         C.byref(p) if p is not None else None, out.ctypes.data, int(off[-1]), out_off.ctypes.data_as(i64p),
+                                         C.byref(info), C.byref(vinfo)), "dcreg_deskew")
+        out = out[:int(out_off[-1])]
+        vd = _voxel_info_dict(vinfo) if p is not None else None
+        if was_list:
+            return [out[out_off[k]:out_off[k + 1]] for k in range(n)], _deskew_info_dict(info), vd
+        return (out, out_off), _deskew_info_dict(info), vd
+
+    def deskew_device(self, dev_ptr, offsets, stride, field, motions, dev_out_ptr, capacity, leaf=None, mode="centroid", min_points=1):
+        """dcreg_deskew_device: records in device memory (dev_ptr, stride floats each, offsets on the host), the output to the device buffer
+        dev_out_ptr (3 floats per point, capacity points).  -> (out_offsets [n + 1], deskew info dict, voxel info dict or None)"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError("deskew_device: offsets must start at 0 and not decrease")
+        n = len(off) - 1
+        _check_field(field, int(stride), "deskew_device")
+        mots = _motions(motions, n, "deskew_device")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        out_off = np.zeros(n + 1, np.int64)
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_deskew_device(self._h, n, C.c_void_p(dev_ptr), off.ctypes.data_as(i64p), int(stride), C.byref(field), mots,
+                                                C.byref(p) if p is not None else None, C.c_void_p(dev_out_ptr), int(capacity),
+                                                out_off.ctypes.data_as(i64p), C.byref(info), C.byref(vinfo)), "dcreg_deskew_device")
+        return out_off, _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    def set_source_deskew(self, records, field, motion, leaf=None, mode="centroid", min_points=1):
+        """dcreg_set_source_deskew: one sweep deskewed on the device and kept as the source (bitwise set_source / set_source_voxel of its
+        deskew output).  -> (deskew info dict, voxel info dict or None)"""
+        a = _points(records, "set_source_deskew")
+        _check_field(field, a.shape[1], "set_source_deskew")
+        m = _motions(motion, 1, "set_source_deskew")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        self._check(self._L.dcreg_set_source_deskew(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(field), m,
+                                                    C.byref(p) if p is not None else None, C.byref(info), C.byref(vinfo)), "dcreg_set_source_deskew")
+        return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    def set_source_deskew_device(self, dev_ptr, n, stride, field, motion, leaf=None, mode="centroid", min_points=1):
+        _check_field(field, int(stride), "set_source_deskew_device")
+        m = _motions(motion, 1, "set_source_deskew_device")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        self._check(self._L.dcreg_set_source_deskew_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(field), m,
+                                                           C.byref(p) if p is not None else None, C.byref(info), C.byref(vinfo)),
+                    "dcreg_set_source_deskew_device")
+        return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
 
     def index_info(self):
         info = IndexInfo()

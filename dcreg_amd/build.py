@@ -21,6 +21,7 @@ SOURCES = [
     "device/kdtree.hip",
     "device/exchange.hip",
     "device/voxel.hip",
+    "device/deskew.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

@@ -57,13 +57,15 @@ static void host_bounds(const float *xyz, int64_t n, int64_t stride, double mn[3
     for (int a = 0; a < 3; ++a) { mn[a] = lo[a]; mx[a] = hi[a]; }
 }
 
-static int device_bounds(dcreg_ctx *c, const float4 *pts, int64_t n, double mn[3], double mx[3]) {
+// (dsk: the counts of a deskew that packed the cloud come back with the bounds)
+static int device_bounds(dcreg_ctx *c, const float4 *pts, int64_t n, double mn[3], double mx[3], DeskewRun *dsk = nullptr) {
     uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), init, sizeof(init), hipMemcpyHostToDevice, c->stream));
     const unsigned nb = std::min<unsigned>(blocks_for(n, 256), 256);      // grid-stride: one block per CU is plenty
     hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(256), 0, c->stream, pts, n, c->d_scratch.data());
     uint32_t out[6];
     HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch.data(), sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    if (dsk) if (int rc = deskew_readback(c, *dsk)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int a = 0; a < 3; ++a) { mn[a] = ord2f(out[a]); mx[a] = ord2f(out[3 + a]); }
     return DCREG_OK;
@@ -378,10 +380,10 @@ int refuse_in_flight(dcreg_ctx *c) {
 // host, no stream synchronise in dcreg_set_source
 static bool small_host_frame(int64_t n, int64_t stride) { return n <= 65536 && n * stride <= (int64_t)1 << 20; }
 
-int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw) {
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw, DeskewRun *dsk) {
     if (!xyz || n < 0 || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("cloud too large (%lld points)", (long long)n); return DCREG_E_INVALID; }
-    if (raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    if (!(dsk && dsk->out3) && raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     if (n == 0) return DCREG_OK;
     const float *src = xyz;
     if (!on_device) {
@@ -411,6 +413,7 @@ int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool
         HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
     }
+    if (dsk) return deskew_queue(c, src, n, stride, *dsk, dsk->out3 ? nullptr : raw.data());     // (deskew.hip: k_pack_deskew packs)
     hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw.data());
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
@@ -2257,22 +2260,54 @@ static void voxel_info(dcreg_voxel_info *info, const VoxelResult &r) {
     if (info) { info->n_in = r.n_in; info->n_finite = r.n_finite; info->n_voxels = r.n_voxels; info->n_out = r.n_out; }
 }
 static int set_cloud_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_voxel_params *p, bool target,
-                           double radius_hint, dcreg_voxel_info *info) {
+                           double radius_hint, dcreg_voxel_info *info, DeskewRun *dsk = nullptr, dcreg_deskew_info *dinfo = nullptr) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (n <= 0) { c->fail("%s cloud is null or empty", target ? "target" : "measure"); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t off[2] = {0, n};
     VoxelResult r;
-    int rc = voxel_pass(c, 1, xyz, off, stride, on_device, p, true, r);
+    int rc = voxel_pass(c, 1, xyz, off, stride, on_device, p, true, r, dsk);
     if (rc) return rc;
     voxel_info(info, r);
+    if (dsk) deskew_info(*dsk, n, dinfo);
     if (r.n_out <= 0) { c->fail("no point of the %s cloud is left after the voxel pass", target ? "target" : "measure"); return DCREG_E_INVALID; }
     if (target) {
         const double box[6] = {r.mn[0], r.mn[1], r.mn[2], r.mx[0], r.mx[1], r.mx[2]};
         return target_commit(c, r.n_out, box, radius_hint);
     }
     return source_commit(c, r.n_out, r.mn, r.mx, true);
+}
+// dcreg_set_source_deskew*: the records are deskewed while they are packed into c->d_aligned.data() (upload_cloud), then everything goes on
+// as dcreg_set_source (bounds on the device - the deskewed points are not on the host -, a non-finite point refuses) or as
+// dcreg_set_source_voxel goes on
+static int set_source_deskew(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_time_field *f,
+                             const dcreg_sweep_motion *m, const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (n <= 0) { c->fail("measure cloud is null or empty"); return DCREG_E_INVALID; }
+    const int64_t off[2] = {0, n};
+    DeskewRun d;
+    int rc = deskew_prepare(c, 1, off, stride, f, m, d);
+    if (rc) return rc;
+    if (p) return set_cloud_voxel(c, xyz, n, stride, on_device, p, false, 0.0, vinfo, &d, info);
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned, &d);
+    if (rc) return rc;
+    double mn[3], mx[3];
+    rc = device_bounds(c, c->d_aligned.data(), n, mn, mx, &d);
+    if (rc) return rc;
+    deskew_info(d, n, info);
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(mn[a]) || !std::isfinite(mx[a])) { c->fail("source cloud has non-finite coordinates"); return DCREG_E_INVALID; }
+    return source_commit(c, n, mn, mx, true);
+}
+int dcreg_set_source_deskew(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
+                            const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    return set_source_deskew(c, xyz, n, stride, false, f, m, p, info, vinfo);
+}
+int dcreg_set_source_deskew_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
+                                   const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    return set_source_deskew(c, d_xyz, n, stride, true, f, m, p, info, vinfo);
 }
 int dcreg_set_source_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, dcreg_voxel_info *info) {
     return set_cloud_voxel(c, xyz, n, stride, false, p, false, 0.0, info);

@@ -91,6 +91,25 @@ private:
     size_t cap_ = 0;
 };
 
+namespace dcreg {
+// one cloud of a deskew call on the device (deskew.hip k_pack_deskew): twist xi = Log(motion) (w then v), span, reference instant
+struct DeskewCloud {
+    double xi[6];
+    double t_begin, t_end, ref;
+    int from_data;                 // the span is the cloud's own minimum / maximum finite stamp (keys of k_deskew_span)
+    int pad_;
+};
+// the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i) - the segments of voxel.hip and deskew.hip
+__device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
+    int lo = 0, hi = n_clouds;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return (uint32_t)lo;
+}
+}  // namespace dcreg
+
 // What a linearisation launch is and how it is carried out (context.hip linearize_begin: lin_check settles the kind, lin_plan the rest)
 enum class LinKind : uint8_t { batch, frames, pairs, single, gated, dump, stamps };   // single .. stamps: one pose on the ctx's own source
 enum class LinPass : uint8_t { none, advance, team };     // in front of k_lin: nothing, k_advance, k_advance_team (dcreg_launch_series_passes)
@@ -267,6 +286,15 @@ struct dcreg_ctx {
         DevBuf<int64_t> cnt;
     };
     VoxelBufs vox;
+    // motion compensation (deskew.hip: dcreg_deskew*, dcreg_set_source_deskew*): per cloud its twist, span and reference instant, the
+    // cloud offsets, and the call's keys - [0] finite points, [1] stamps outside their span, [2] minimum stamp key, [3] ~maximum key, then
+    // per cloud s [4 + 2s] minimum and [5 + 2s] ~maximum key of its finite stamps (span_from_data)
+    struct DeskewBufs {
+        DevBuf<dcreg::DeskewCloud> clouds;
+        DevBuf<int64_t> d_off;
+        DevBuf<unsigned long long> keys;
+    };
+    DeskewBufs dsk;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
@@ -413,17 +441,43 @@ int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
-int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw);   // context.hip
+// deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before
+// anything is queued).  upload_cloud given one packs the records with k_pack_deskew instead of k_pack (into its float4 buffer, or 3 floats
+// per point to out3 when set); deskew_readback queues the copy of the call's counts into `head` (the caller synchronises: it rides on the
+// readback the call has anyway), deskew_info decodes them.
+struct DeskewRun {
+    int n_clouds = 0;
+    const int64_t *off = nullptr;          // host, n_clouds + 1
+    int column = 0, type = 0;
+    double scale = 1.0;
+    std::vector<DeskewCloud> clouds;
+    bool any_from_data = false;
+    float *out3 = nullptr;
+    bool queued = false;                   // the pack was queued (not for an empty call)
+    bool read = false;                     // the counts were queued for readback
+    unsigned long long head[4] = {0, 0, ~0ull, ~0ull};
+};
+int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
+                   DeskewRun &d);
+int deskew_queue(dcreg_ctx *c, const float *src, int64_t n, int64_t stride, DeskewRun &d, float4 *out4);
+int deskew_readback(dcreg_ctx *c, DeskewRun &d);
+void deskew_info(const DeskewRun &d, int64_t n_in, dcreg_deskew_info *info);
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw,
+                 DeskewRun *dsk = nullptr);   // context.hip
 // voxel.hip: the voxel-grid pass of n_clouds clouds (offsets off[n_clouds + 1], host memory) - checks everything before it writes; the output
 // points go to c->vox.out (3 floats each) or, packed, to c->d_aligned as k_pack packs a cloud (one cloud only).  Ends with ONE readback of
-// the per-cloud counts and the bounds of the output.
+// the per-cloud counts and the bounds of the output.  dsk: the clouds are deskewed while they are packed (its counts come back with the
+// pass's first readback).
 struct VoxelResult {
     std::vector<int64_t> voxels, kept;     // per cloud
     int64_t n_in = 0, n_finite = 0, n_voxels = 0, n_out = 0;
     double mn[3] = {}, mx[3] = {};         // bounds of the output points (as k_bounds takes them)
 };
 int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
-               bool packed, VoxelResult &r);
+               bool packed, VoxelResult &r, DeskewRun *dsk = nullptr);
+// voxel.hip: dcreg_voxel_downsample* (and dcreg_deskew* with a voxel block): the pass, then the copy of the output to the caller
+int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
+                        float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info, DeskewRun *dsk = nullptr);
 int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, int k, double max_radius, const PoseArg *pose,
                int32_t *d_idx, float *d_d2, bool sweep = false);
 }  // namespace dcreg

@@ -36,16 +36,6 @@ constexpr int kTail = 4;
 
 inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
-// the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i)
-__device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
-    int lo = 0, hi = n_clouds;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return (uint32_t)lo;
-}
-
 __device__ __forceinline__ bool finite3(const float4 p) {
     return fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
 }
@@ -293,7 +283,7 @@ int bits_for(int64_t v) { int b = 0; while (b < 63 && ((int64_t)1 << b) <= v) ++
 }  // namespace
 
 int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
-               bool packed, VoxelResult &r) {
+               bool packed, VoxelResult &r, DeskewRun *dsk) {
     // ---- everything the host can check, before anything is queued
     if (!p) { c->fail("null voxel parameters"); return DCREG_E_INVALID; }
     for (int a = 0; a < 3; ++a)
@@ -324,7 +314,7 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
         c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
     if (packed ? c->d_aligned.ensure(c, (size_t)n) : B.out.ensure(c, (size_t)(3 * n))) return DCREG_E_NOMEM;
-    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts);
+    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts, dsk);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), n_clouds);
@@ -333,6 +323,7 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
                        lx, ly, lz, B.seg.data(), B.cnt.data());
     std::vector<int64_t> h((size_t)nc);
     HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt.data(), sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    if (dsk && (rc = deskew_readback(c, *dsk))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
 
@@ -402,18 +393,15 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
     return DCREG_OK;
 }
 
-}  // namespace dcreg
-
-using namespace dcreg;
-
-// dcreg_voxel_downsample*: the pass into the context's output buffer, then - when the caller's capacity holds it - one copy to the caller
-static int voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
-                            float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info) {
+// dcreg_voxel_downsample* (and dcreg_deskew* with a voxel block): the pass into the context's output buffer, then - when the caller's capacity
+// holds it - one copy to the caller
+int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
+                        float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info, DeskewRun *dsk) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (!out_off || capacity < 0) { c->fail("invalid output arguments"); return DCREG_E_INVALID; }
     VoxelResult r;
-    int rc = voxel_pass(c, n_clouds, xyz, off, stride, on_device, p, false, r);
+    int rc = voxel_pass(c, n_clouds, xyz, off, stride, on_device, p, false, r, dsk);
     if (rc) return rc;
     out_off[0] = 0;
     for (int s = 0; s < n_clouds; ++s) out_off[s + 1] = out_off[s] + r.kept[(size_t)s];
@@ -427,13 +415,17 @@ static int voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const 
     return DCREG_OK;
 }
 
+}  // namespace dcreg
+
+using namespace dcreg;
+
 extern "C" {
 int dcreg_voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_voxel_params *p,
                            float *out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
-    return voxel_downsample(c, n_clouds, xyz, offsets, stride_floats, false, p, out_xyz, capacity_points, out_offsets, info);
+    return voxel_downsample_to(c, n_clouds, xyz, offsets, stride_floats, false, p, out_xyz, capacity_points, out_offsets, info);
 }
 int dcreg_voxel_downsample_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
                                   const dcreg_voxel_params *p, float *d_out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
-    return voxel_downsample(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_out_xyz, capacity_points, out_offsets, info);
+    return voxel_downsample_to(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_out_xyz, capacity_points, out_offsets, info);
 }
 }

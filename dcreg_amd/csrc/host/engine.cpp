@@ -733,6 +733,9 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_method_stats")) return sizeof(dcreg_method_stats);
     if (!std::strcmp(name, "dcreg_voxel_params")) return sizeof(dcreg_voxel_params);
     if (!std::strcmp(name, "dcreg_voxel_info")) return sizeof(dcreg_voxel_info);
+    if (!std::strcmp(name, "dcreg_time_field")) return sizeof(dcreg_time_field);
+    if (!std::strcmp(name, "dcreg_sweep_motion")) return sizeof(dcreg_sweep_motion);
+    if (!std::strcmp(name, "dcreg_deskew_info")) return sizeof(dcreg_deskew_info);
     return 0;
 }
 

@@ -29,6 +29,64 @@ inline void so3Exp(const double w[3], double R[9]) {
     for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + s * K[i] + c1 * KK[i];
 }
 
+// se(3) -> SE(3) (include/dcreg.h, deskew): xi = (w, v), theta = |w|, R = I + A W + B W^2, t = (I + B W + C W^2) v with W = [w]x; below
+// theta = 1e-3 the coefficients are their series through theta^4.  deskew.hip evaluates the same expression on the device.
+inline void se3Coeffs(double th2, double th, double &A, double &B, double &Cc) {
+    if (th < 1e-3) {
+        A = 1.0 - th2 / 6.0 + th2 * th2 / 120.0;
+        B = 0.5 - th2 / 24.0 + th2 * th2 / 720.0;
+        Cc = 1.0 / 6.0 - th2 / 120.0 + th2 * th2 / 5040.0;
+    } else {
+        const double s = std::sin(th), c = std::cos(th);
+        A = s / th;
+        B = (1.0 - c) / th2;
+        Cc = (th - s) / (th2 * th);
+    }
+}
+inline void se3Exp(const double xi[6], double R[9], double t[3]) {
+    const double wx = xi[0], wy = xi[1], wz = xi[2];
+    const double th2 = wx * wx + wy * wy + wz * wz, th = std::sqrt(th2);
+    double A, B, Cc;
+    se3Coeffs(th2, th, A, B, Cc);
+    const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+    double W2[9], V[9];
+    mat3mul(W, W, W2);
+    for (int i = 0; i < 9; ++i) {
+        const double I = i % 4 == 0 ? 1.0 : 0.0;
+        R[i] = I + A * W[i] + B * W2[i];
+        V[i] = I + B * W[i] + Cc * W2[i];
+    }
+    for (int i = 0; i < 3; ++i) t[i] = V[i * 3] * xi[3] + V[i * 3 + 1] * xi[4] + V[i * 3 + 2] * xi[5];
+}
+
+// SE(3) -> se(3), the inverse of se3Exp for rotations below pi: w = angle-axis of R (theta = atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2)),
+// v = V^-1 t with V^-1 = I - W / 2 + D W^2, D = (1 - A / (2 B)) / theta^2 (series below theta = 1e-3).  Returns theta.
+inline double se3Log(const double R[9], const double t[3], double xi[6]) {
+    const double s[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+    const double sn = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    const double th = std::atan2(sn, 0.5 * (R[0] + R[4] + R[8] - 1.0));
+    const double th2 = th * th;
+    const double f = th < 1e-3 ? 1.0 + th2 / 6.0 + 7.0 * th2 * th2 / 360.0 : th / sn;
+    for (int a = 0; a < 3; ++a) xi[a] = f * s[a];
+    double D;
+    if (th < 1e-3) {
+        D = 1.0 / 12.0 + th2 / 720.0 + th2 * th2 / 30240.0;
+    } else {
+        double A, B, Cc;
+        se3Coeffs(th2, th, A, B, Cc);
+        D = (1.0 - A / (2.0 * B)) / th2;
+    }
+    const double W[9] = {0, -xi[2], xi[1], xi[2], 0, -xi[0], -xi[1], xi[0], 0};
+    double W2[9];
+    mat3mul(W, W, W2);
+    for (int i = 0; i < 3; ++i) {
+        double v = 0.0;
+        for (int j = 0; j < 3; ++j) v += ((i == j ? 1.0 : 0.0) - 0.5 * W[i * 3 + j] + D * W2[i * 3 + j]) * t[j];
+        xi[3 + i] = v;
+    }
+    return th;
+}
+
 // right perturbation: R <- R exp(w), t <- t + R v
 inline void boxplus(const double R[9], const double t[3], const double dx[6], double Ro[9], double to[3]) {
     double E[9], Rn[9], tn[3];

@@ -372,3 +372,80 @@ def lidar_sweep(world, pose, rings=128, cols=1024, fov_up=22.5, fov_down=-22.5, 
     e = np.radians(fov_up - (jr + 0.5) * (fov_up - fov_down) / rings)
     d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], 1)
     return (d * rng_px[:, None]).astype(np.float32)
+
+
+def _se3_exp_many(xi):
+    """SE(3) exponential of many twists [m, 6] = (w, v) (include/dcreg.h's formula) -> (R [m, 3, 3], t [m, 3])"""
+    w, v = xi[:, :3], xi[:, 3:]
+    th2 = np.einsum("ij,ij->i", w, w)
+    th = np.sqrt(th2)
+    small = th < 1e-3
+    ths = np.where(small, 1.0, th)
+    A = np.where(small, 1 - th2 / 6 + th2 * th2 / 120, np.sin(ths) / ths)
+    B = np.where(small, 0.5 - th2 / 24 + th2 * th2 / 720, (1 - np.cos(ths)) / ths ** 2)
+    Cc = np.where(small, 1 / 6 - th2 / 120 + th2 * th2 / 5040, (ths - np.sin(ths)) / ths ** 3)
+    W = np.zeros((len(xi), 3, 3))
+    W[:, 0, 1], W[:, 0, 2], W[:, 1, 0], W[:, 1, 2], W[:, 2, 0], W[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    W2 = W @ W
+    eye = np.eye(3)[None]
+    R = eye + A[:, None, None] * W + B[:, None, None] * W2
+    V = eye + B[:, None, None] * W + Cc[:, None, None] * W2
+    return R, np.einsum("mij,mj->mi", V, v)
+
+
+def lidar_sweep_moving(world, pose_begin, motion, period=0.1, ref=0.5, rings=128, cols=1024, fov_up=22.5, fov_down=-22.5, min_range=0.5,
+                       max_range=80.0, noise=0.01, seed=0):
+    """lidar_sweep of a MOVING sensor: column j is measured at s_j = (j + 0.5) / cols * period seconds from the sensor pose
+    T(s_j) = pose_begin Exp(s_j / period Log(motion)) (motion = the pose at the end of the sweep in the frame of the pose at its start: a
+    constant twist over the sweep).  Each world point is assigned to the column whose pose sees it in that column (a fixed point found per
+    point: a few vectorised passes over the world, not one per column); then, as lidar_sweep, each beam returns the nearest point of its pixel
+    on the beam's centre direction plus range noise, NaN where there is none.  -> (records [rings * cols, 4] float32 = x y z in the sensor
+    frame of the column's instant and the stamp s_j in seconds, ring after ring; the true sensor pose at the reference instant ref * period,
+    4x4)."""
+    from .api import se3_log, se3_exp
+    rng = np.random.default_rng(seed)
+    T0 = np.asarray(pose_begin, np.float64)
+    xi = se3_log(motion)
+    p = np.asarray(world, np.float32).astype(np.float64)
+    d0 = p - T0[:3, 3]
+    p = p[np.einsum("ij,ij->i", d0, d0) < (max_range + np.linalg.norm(xi[3:]) + 1.0) ** 2]
+    stamps = (np.arange(cols) + 0.5) / cols * period
+    Rc, tc = _se3_exp_many(np.outer(stamps / period, xi))
+    Rc, tc = T0[:3, :3][None] @ Rc, T0[:3, :3] @ tc.T + T0[:3, 3][:, None]       # column poses in the world
+    tc = tc.T
+
+    def column_of(j):
+        body = np.einsum("mji,mj->mi", Rc[j], p - tc[j])          # R_j^T (p - t_j)
+        az = np.arctan2(body[:, 1], body[:, 0])
+        return np.minimum((az + np.pi) / (2 * np.pi) * cols, cols - 1).astype(np.int64), body
+
+    Rm, tm = T0[:3, :3] @ se3_exp(0.5 * xi)[:3, :3], T0[:3, :3] @ se3_exp(0.5 * xi)[:3, 3] + T0[:3, 3]
+    body = (p - tm) @ Rm
+    j = np.minimum((np.arctan2(body[:, 1], body[:, 0]) + np.pi) / (2 * np.pi) * cols, cols - 1).astype(np.int64)
+    for _ in range(6):                                            # the column's own pose sees the point in that column
+        jn, body = column_of(j)
+        if np.array_equal(jn, j):
+            break
+        j = jn
+    jn, body = column_of(j)
+    keep = jn == j
+    body, col = body[keep], j[keep]
+    r = np.linalg.norm(body, axis=1)
+    ok = (r > min_range) & (r < max_range)
+    body, r, col = body[ok], r[ok], col[ok]
+    el = np.degrees(np.arcsin(body[:, 2] / r))
+    ring = np.floor((fov_up - el) / (fov_up - fov_down) * rings).astype(np.int64)
+    inside = (ring >= 0) & (ring < rings)
+    pix, r = ring[inside] * cols + col[inside], r[inside]
+    order = np.lexsort((r, pix))
+    first = order[np.r_[True, pix[order][1:] != pix[order][:-1]]] if len(order) else order
+    rng_px = np.full(rings * cols, np.nan)
+    rng_px[pix[first]] = r[first] + rng.normal(0.0, noise, len(first))
+    jr, jc = np.divmod(np.arange(rings * cols), cols)
+    a = (jc + 0.5) / cols * 2 * np.pi - np.pi
+    e = np.radians(fov_up - (jr + 0.5) * (fov_up - fov_down) / rings)
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], 1)
+    rec = np.empty((rings * cols, 4), np.float32)
+    rec[:, :3] = d * rng_px[:, None]
+    rec[:, 3] = stamps[jc]
+    return rec, T0 @ se3_exp(ref * xi)

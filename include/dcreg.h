@@ -22,6 +22,8 @@
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
  *                                                                                   dcreg_set_target_voxel[_device]
+ *       motion compensation (deskew) of sweeps from per-point stamps             -> dcreg_deskew[_device],
+ *                                                                                   dcreg_set_source_deskew[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -325,6 +327,72 @@ int dcreg_set_target_voxel(dcreg_ctx *, const float *xyz, int64_t n, int64_t str
                            double search_radius_hint, dcreg_voxel_info *);
 int dcreg_set_target_voxel_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *,
                                   double search_radius_hint, dcreg_voxel_info *);
+
+/* ---------------- motion compensation (deskew) of raw sweeps from per-point stamps ----------------
+ * A spinning LiDAR measures each column of a sweep from a different sensor pose.  These calls move every point into the sensor frame at one
+ * reference instant of the sweep, on the device, while the records are packed (no extra pass over memory).  For each point i of cloud c:
+ *   - its stamp is stored in its record at float slot `column` of the stride_floats floats, read as raw 32-bit words: DCREG_TIME_F32 a float,
+ *     DCREG_TIME_F64 a double over slots column, column + 1 (little-endian, any alignment), DCREG_TIME_U32 an unsigned tick count,
+ *     DCREG_TIME_U64 an unsigned tick count over two slots (little-endian); s_i = scale * (double)stamp_i, in seconds;
+ *   - the cloud's motion D = (R, t) is the sensor pose at t_end expressed in the frame of the pose at t_begin (R row-major); its twist
+ *     xi = Log(D) is computed once per cloud on the host in double (below);
+ *   - the span [t_begin, t_end] is the caller's, or with span_from_data the minimum and maximum s_i over the cloud's points whose x, y, z
+ *     and s_i are all finite (integer atomics on order-preserving keys: deterministic);
+ *   - tau_i = (s_i - t_begin) / (t_end - t_begin) (an IEEE double division), a_i = tau_i - ref; a_i = 0 for a zero-length span;
+ *     (R_i, t_i) = Exp(a_i xi), p'_i = (float)(R_i p_i + t_i) in double with p_i = (double) x y z.  This is T(ref)^-1 T(s_i) p_i: the output
+ *     is expressed in the sensor frame at the reference instant, and a registration of it estimates the sensor pose at that instant;
+ *   - Exp(w, v), theta = |w|: R = I + A [w]x + B [w]x^2, V = I + B [w]x + C [w]x^2, t = V v with A = sin(theta)/theta, B = (1 - cos(theta))/theta^2,
+ *     C = (theta - sin(theta))/theta^3, and for theta < 1e-3 their series through theta^4 (A = 1 - theta^2/6 + theta^4/120, B = 1/2 - theta^2/24
+ *     + theta^4/720, C = 1/6 - theta^2/120 + theta^4/5040); Log is its inverse (angle-axis of R, then v = V^-1 t);
+ *   - where every component of a_i xi is exactly zero (a zero-length span, an identity motion, a stamp at the reference instant) the point
+ *     is copied bit for bit (-0.0 stays -0.0);
+ *   - a point whose x, y, z or s_i is not finite comes out as three NaN (it is not counted in n_finite); a finite s_i outside the span is
+ *     extrapolated and counted in n_outside (a span taken from the data has no such point; a zero-length span copies them).
+ * A point's result depends on its own record and its cloud's motion only (not on other clouds of the call, nor on the launch configuration).
+ * DCREG_E_INVALID, and nothing is written: t_end < t_begin, a non-finite span or ref, ref outside [0, 1]; a non-finite R or t, an R that is
+ * not a rotation (an element of |R^T R - I| above 1e-6, or det(R) <= 0) or rotates by pi/2 or more; a column outside [3, stride_floats)
+ * (column + 1 < stride_floats too for the 64-bit types); an unknown type; a scale that is not finite and > 0; null field or motions; and the
+ * voxel pass's own refusals when a voxel block is given.  DCREG_E_STATE: a linearisation in flight. */
+#define DCREG_TIME_F32 0
+#define DCREG_TIME_F64 1
+#define DCREG_TIME_U32 2
+#define DCREG_TIME_U64 3
+typedef struct dcreg_time_field {
+    int column;          /* float slot of the stamp in each record (>= 3: x y z come first) */
+    int type;            /* DCREG_TIME_F32 / _F64 / _U32 / _U64 */
+    double scale;        /* seconds per stamp unit (1 for seconds, 1e-9 for nanosecond ticks) */
+} dcreg_time_field;
+typedef struct dcreg_sweep_motion {
+    double R[9], t[3];   /* sensor pose at t_end in the frame of the pose at t_begin */
+    double t_begin, t_end;   /* span in seconds (ignored with span_from_data) */
+    double ref;          /* reference instant in [0, 1] of the span: 0 start, 0.5 middle, 1 end */
+    int span_from_data;  /* 1: the span is the minimum / maximum finite stamp of the cloud */
+    int reserved_;
+} dcreg_sweep_motion;
+typedef struct dcreg_deskew_info {   /* over the clouds of the call */
+    int64_t n_in;        /* points passed in */
+    int64_t n_finite;    /* ... with finite x, y, z and stamp */
+    int64_t n_outside;   /* ... of those, stamps outside their cloud's span (extrapolated) */
+    double t_min, t_max; /* smallest / largest s_i of those (NaN when there is none) */
+} dcreg_deskew_info;
+/* Many clouds (offsets as dcreg_voxel_downsample), one motion per cloud.  voxel == NULL: every point comes out, in input order, 3 floats each,
+ * and out_offsets = offsets (an organised sweep stays organised; capacity_points must hold offsets[n_clouds]).  voxel != NULL: the output is
+ * bitwise dcreg_voxel_downsample of the deskewed clouds (what dcreg_register_frames takes with stride 3), capacity as there.  info and
+ * vinfo may be NULL.  Waits for the stream.  _device: d_xyz read as dcreg_voxel_downsample_device reads it, d_out_xyz device memory. */
+int dcreg_deskew(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *,
+                 const dcreg_sweep_motion *motions, const dcreg_voxel_params *voxel, float *out_xyz, int64_t capacity_points,
+                 int64_t *out_offsets, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
+int dcreg_deskew_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *,
+                        const dcreg_sweep_motion *motions, const dcreg_voxel_params *voxel, float *d_out_xyz, int64_t capacity_points,
+                        int64_t *out_offsets, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
+/* One sweep deskewed and kept as the source: the context is left bitwise as dcreg_set_source (voxel == NULL: a point that comes out
+ * non-finite refuses the call, as there) or dcreg_set_source_voxel (voxel != NULL) of the dcreg_deskew output leaves it.  A refused call
+ * leaves the source as it was.  _device: d_xyz as dcreg_set_source_device reads it. */
+int dcreg_set_source_deskew(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_time_field *,
+                            const dcreg_sweep_motion *, const dcreg_voxel_params *voxel, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
+int dcreg_set_source_deskew_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_time_field *,
+                                   const dcreg_sweep_motion *, const dcreg_voxel_params *voxel, dcreg_deskew_info *info,
+                                   dcreg_voxel_info *vinfo);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
