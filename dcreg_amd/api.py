@@ -147,6 +147,7 @@ EXPORTS = [
     "dcreg_voxel_downsample", "dcreg_voxel_downsample_device", "dcreg_set_source_voxel", "dcreg_set_source_voxel_device",
     "dcreg_set_target_voxel", "dcreg_set_target_voxel_device",
     "dcreg_deskew", "dcreg_deskew_device", "dcreg_set_source_deskew", "dcreg_set_source_deskew_device",
+    "dcreg_deskew_path", "dcreg_deskew_path_device", "dcreg_set_source_deskew_path", "dcreg_set_source_deskew_path_device",
 ]
 
 _lib = None
@@ -205,7 +206,15 @@ class DeskewInfo(C.Structure):
     _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_outside", C.c_int64), ("t_min", C.c_double), ("t_max", C.c_double)]
 
 
-_STRUCTS.update({"dcreg_time_field": TimeField, "dcreg_sweep_motion": SweepMotion, "dcreg_deskew_info": DeskewInfo})
+class SweepPath(C.Structure):
+    _fields_ = [("first_knot", C.c_int64), ("n_knots", C.c_int), ("reserved_", C.c_int), ("t_ref", C.c_double), ("ext_R", C.c_double * 9),
+                ("ext_t", C.c_double * 3)]
+
+
+_STRUCTS.update({"dcreg_time_field": TimeField, "dcreg_sweep_motion": SweepMotion, "dcreg_deskew_info": DeskewInfo,
+                 "dcreg_sweep_path": SweepPath})
+_SWEEP_PATH_DTYPE = np.dtype([("first_knot", np.int64), ("n_knots", np.int32), ("reserved_", np.int32), ("t_ref", np.float64),
+                              ("ext_R", np.float64, (3, 3)), ("ext_t", np.float64, 3)])
 TIME_TYPES = {"f32": 0, "f64": 1, "u32": 2, "u64": 3}      # DCREG_TIME_F32 / _F64 / _U32 / _U64
 
 
@@ -329,6 +338,93 @@ def _motions(motions, n, what):
     arr = (SweepMotion * max(n, 1))()
     for k, m in enumerate(ms):
         arr[k] = m
+    return arr
+
+
+def _rotations_ok(R):
+    """per matrix of R [m, 3, 3]: |R^T R - I| <= 1e-6 in every element and det > 0 (the library's is_rotation)"""
+    G = np.einsum("mki,mkj->mij", R, R) - np.eye(3)
+    with np.errstate(invalid="ignore"):
+        return np.all(np.abs(G) <= 1e-6, axis=(1, 2)) & (np.linalg.det(R) > 0.0)
+
+
+def _check_extrinsic(R, t, what):
+    if not (np.all(np.isfinite(R)) and np.all(np.isfinite(t))):
+        raise ValueError("%s: the extrinsic is not finite" % what)
+    if not np.all(_rotations_ok(R.reshape(-1, 3, 3))):
+        raise ValueError("%s: the extrinsic's R is not a rotation (|R^T R - I| > 1e-6 or det <= 0)" % what)
+
+
+def sweep_path(first_knot, n_knots, t_ref, extrinsic=None):
+    """dcreg_sweep_path: the cloud's window [first_knot, first_knot + n_knots) of the call's knot table (n_knots >= 2), the reference instant
+    t_ref in seconds (inside the window's stamps) and the pose of the sensor in the body frame (4x4, None = identity: the knots are the
+    sensor's own poses)"""
+    if int(n_knots) < 2 or int(first_knot) < 0:
+        raise ValueError("sweep_path: a window of at least 2 knots from a knot >= 0 is expected, got %r knots from %r" % (n_knots, first_knot))
+    if not np.isfinite(t_ref):
+        raise ValueError("sweep_path: t_ref %r is not finite" % (t_ref,))
+    E = np.eye(4) if extrinsic is None else np.asarray(extrinsic, np.float64)
+    if E.shape != (4, 4):
+        raise ValueError("sweep_path: a 4x4 extrinsic is expected, got %s" % (E.shape,))
+    _check_extrinsic(E[:3, :3], E[:3, 3], "sweep_path")
+    b = SweepPath()
+    b.first_knot, b.n_knots, b.t_ref = int(first_knot), int(n_knots), float(t_ref)
+    b.ext_R[:] = [float(v) for v in E[:3, :3].reshape(9)]
+    b.ext_t[:] = [float(v) for v in E[:3, 3]]
+    return b
+
+
+def _knot_table(knot_stamps, knot_poses, what):
+    """(stamps [K] float64, poses [K, 12] float64 = R row-major then t) of a knot table given as [K, 12] or [K, 4, 4] poses"""
+    st = np.ascontiguousarray(knot_stamps, dtype=np.float64).reshape(-1)
+    P = np.asarray(knot_poses, dtype=np.float64)
+    if P.ndim == 3 and P.shape[1:] == (4, 4):
+        P = np.concatenate([P[:, :3, :3].reshape(-1, 9), P[:, :3, 3]], axis=1)
+    if P.ndim != 2 or P.shape[1] != 12 or len(P) != len(st):
+        raise ValueError("%s: a knot table of K stamps and K poses ([K, 12] = R row-major then t, or [K, 4, 4]) is expected, got %s and %s"
+                         % (what, st.shape, np.shape(knot_poses)))
+    return st, np.ascontiguousarray(P)
+
+
+def _paths(paths, n, st, P, what):
+    """the library's refusals of a path call, over all blocks and all knots at once -> the array of blocks the call takes"""
+    ps = [paths] if isinstance(paths, SweepPath) else list(paths)
+    if len(ps) == 1 and n != 1:
+        ps = ps * n
+    if len(ps) != n:
+        raise ValueError("%s: one path block per cloud is expected (%d clouds, %d blocks)" % (what, n, len(ps)))
+    if any(not isinstance(b, SweepPath) for b in ps):
+        raise ValueError("%s: sweep_path blocks are expected" % what)
+    arr = (SweepPath * max(n, 1))(*ps)
+    if n == 0:
+        return arr
+    b = np.frombuffer(arr, dtype=_SWEEP_PATH_DTYPE, count=n)
+    K = len(st)
+    first, nk = b["first_knot"], b["n_knots"].astype(np.int64)
+    if np.any(nk < 2) or np.any(first < 0) or np.any(first + nk > K):
+        raise ValueError("%s: every window must hold at least 2 knots inside the table of %d knots" % (what, K))
+    _check_extrinsic(b["ext_R"], b["ext_t"], what)
+    cover = np.zeros(K + 1, np.int64)                  # knots and segments (knot j to j + 1) inside some window
+    np.add.at(cover, first, 1)
+    np.add.at(cover, first + nk, -1)
+    knots = np.cumsum(cover[:-1]) > 0
+    cover[:] = 0
+    np.add.at(cover, first, 1)
+    np.add.at(cover, first + nk - 1, -1)
+    segs = np.flatnonzero(np.cumsum(cover[:-1]) > 0)
+    if not np.all(np.isfinite(P[knots])):
+        raise ValueError("%s: a knot pose is not finite" % what)
+    if not np.all(_rotations_ok(P[knots, :9].reshape(-1, 3, 3))):
+        raise ValueError("%s: R of a knot is not a rotation (|R^T R - I| > 1e-6 or det <= 0)" % what)
+    if not np.all(np.isfinite(st[knots])) or not np.all(st[segs + 1] > st[segs]):
+        raise ValueError("%s: the stamps of a window's knots are not finite and strictly increasing" % what)
+    D = np.einsum("mki,mkj->mij", P[segs, :9].reshape(-1, 3, 3), P[segs + 1, :9].reshape(-1, 3, 3))        # R_k^T R_k+1
+    sn = 0.5 * np.sqrt((D[:, 2, 1] - D[:, 1, 2]) ** 2 + (D[:, 0, 2] - D[:, 2, 0]) ** 2 + (D[:, 1, 0] - D[:, 0, 1]) ** 2)
+    if not np.all(np.arctan2(sn, 0.5 * (np.trace(D, axis1=1, axis2=2) - 1.0)) < np.pi / 2):
+        raise ValueError("%s: a segment rotates by pi/2 or more" % what)
+    with np.errstate(invalid="ignore"):
+        if not np.all((b["t_ref"] >= st[first]) & (b["t_ref"] <= st[first + nk - 1])):
+            raise ValueError("%s: t_ref must be finite and inside the stamps of its window's knots" % what)
     return arr
 
 
@@ -471,6 +567,12 @@ def load():
         for name in ("dcreg_set_source_deskew", "dcreg_set_source_deskew_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.POINTER(TimeField), C.POINTER(SweepMotion), C.POINTER(VoxelParams),
                                          C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
+    if hasattr(L, "dcreg_deskew_path"):
+        tail = [C.POINTER(TimeField), C.c_int64, dp, dp, C.POINTER(SweepPath), C.POINTER(VoxelParams)]
+        L.dcreg_deskew_path.argtypes = [vp, C.c_int, vp, i64p, C.c_int64] + tail + [vp, C.c_int64, i64p, C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
+        L.dcreg_deskew_path_device.argtypes = L.dcreg_deskew_path.argtypes
+        for name in ("dcreg_set_source_deskew_path", "dcreg_set_source_deskew_path_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64] + tail + [C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -802,6 +904,76 @@ class Context:
         self._check(self._L.dcreg_set_source_deskew_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(field), m,
                                                            C.byref(p) if p is not None else None, C.byref(info), C.byref(vinfo)),
                     "dcreg_set_source_deskew_device")
+        return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    def deskew_path(self, clouds, field, knot_stamps, knot_poses, paths, leaf=None, mode="centroid", min_points=1):
+        """dcreg_deskew_path: deskew as above, the pose at a point's stamp read off a sampled trajectory through a sensor-to-body extrinsic
+        (include/dcreg.h has the rule).  knot_stamps [K] seconds and knot_poses [K, 12] (R row-major then t) or [K, 4, 4]: the BODY's poses
+        in any fixed frame; paths = one sweep_path per cloud (or one for all).  The output is each sweep in its sensor frame at its t_ref.
+        -> as deskew"""
+        xyz, off, was_list = _clouds(clouds, "deskew_path")
+        n = len(off) - 1
+        _check_field(field, xyz.shape[1], "deskew_path")
+        st, P = _knot_table(knot_stamps, knot_poses, "deskew_path")
+        blocks = _paths(paths, n, st, P, "deskew_path")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        out = np.empty((max(int(off[-1]), 1), 3), np.float32)
+        out_off = np.zeros(n + 1, np.int64)
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_deskew_path(self._h, n, xyz.ctypes.data, off.ctypes.data_as(i64p), xyz.shape[1], C.byref(field), len(st), _dp(st),
+                                              _dp(P), blocks, C.byref(p) if p is not None else None, out.ctypes.data, int(off[-1]),
+                                              out_off.ctypes.data_as(i64p), C.byref(info), C.byref(vinfo)), "dcreg_deskew_path")
+        out = out[:int(out_off[-1])]
+        vd = _voxel_info_dict(vinfo) if p is not None else None
+        if was_list:
+            return [out[out_off[k]:out_off[k + 1]] for k in range(n)], _deskew_info_dict(info), vd
+        return (out, out_off), _deskew_info_dict(info), vd
+
+    def deskew_path_device(self, dev_ptr, offsets, stride, field, knot_stamps, knot_poses, paths, dev_out_ptr, capacity, leaf=None,
+                           mode="centroid", min_points=1):
+        """dcreg_deskew_path_device: records and output in device memory as deskew_device takes them; the knot table and the blocks on the host.
+        -> (out_offsets [n + 1], deskew info dict, voxel info dict or None)"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise ValueError("deskew_path_device: offsets must start at 0 and not decrease")
+        n = len(off) - 1
+        _check_field(field, int(stride), "deskew_path_device")
+        st, P = _knot_table(knot_stamps, knot_poses, "deskew_path_device")
+        blocks = _paths(paths, n, st, P, "deskew_path_device")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        out_off = np.zeros(n + 1, np.int64)
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_deskew_path_device(self._h, n, C.c_void_p(dev_ptr), off.ctypes.data_as(i64p), int(stride), C.byref(field),
+                                                     len(st), _dp(st), _dp(P), blocks, C.byref(p) if p is not None else None,
+                                                     C.c_void_p(dev_out_ptr), int(capacity), out_off.ctypes.data_as(i64p), C.byref(info),
+                                                     C.byref(vinfo)), "dcreg_deskew_path_device")
+        return out_off, _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    def set_source_deskew_path(self, records, field, knot_stamps, knot_poses, path, leaf=None, mode="centroid", min_points=1):
+        """dcreg_set_source_deskew_path: one sweep deskewed along its path on the device and kept as the source (bitwise set_source /
+        set_source_voxel of its deskew_path output).  -> (deskew info dict, voxel info dict or None)"""
+        a = _points(records, "set_source_deskew_path")
+        _check_field(field, a.shape[1], "set_source_deskew_path")
+        st, P = _knot_table(knot_stamps, knot_poses, "set_source_deskew_path")
+        block = _paths(path, 1, st, P, "set_source_deskew_path")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        self._check(self._L.dcreg_set_source_deskew_path(self._h, a.ctypes.data, a.shape[0], a.shape[1], C.byref(field), len(st), _dp(st), _dp(P),
+                                                         block, C.byref(p) if p is not None else None, C.byref(info), C.byref(vinfo)),
+                    "dcreg_set_source_deskew_path")
+        return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    def set_source_deskew_path_device(self, dev_ptr, n, stride, field, knot_stamps, knot_poses, path, leaf=None, mode="centroid", min_points=1):
+        _check_field(field, int(stride), "set_source_deskew_path_device")
+        st, P = _knot_table(knot_stamps, knot_poses, "set_source_deskew_path_device")
+        block = _paths(path, 1, st, P, "set_source_deskew_path_device")
+        p = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        info, vinfo = DeskewInfo(), VoxelInfo()
+        self._check(self._L.dcreg_set_source_deskew_path_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(field), len(st), _dp(st),
+                                                                _dp(P), block, C.byref(p) if p is not None else None, C.byref(info),
+                                                                C.byref(vinfo)), "dcreg_set_source_deskew_path_device")
         return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
 
     def index_info(self):

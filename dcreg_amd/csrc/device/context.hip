@@ -385,6 +385,7 @@ int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool
     if (n >= ((int64_t)1 << 31)) { c->fail("cloud too large (%lld points)", (long long)n); return DCREG_E_INVALID; }
     if (!(dsk && dsk->out3) && raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     if (n == 0) return DCREG_OK;
+    if (dsk) if (int rc = deskew_reserve(c, *dsk)) return rc;
     const float *src = xyz;
     if (!on_device) {
         if (c->d_stage.ensure(c, (size_t)(n * stride))) return DCREG_E_NOMEM;
@@ -2281,14 +2282,16 @@ static int set_cloud_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t st
 // dcreg_set_source_deskew*: the records are deskewed while they are packed into c->d_aligned.data() (upload_cloud), then everything goes on
 // as dcreg_set_source (bounds on the device - the deskewed points are not on the host -, a non-finite point refuses) or as
 // dcreg_set_source_voxel goes on
+// (pt: the path form, dcreg_set_source_deskew_path*; m otherwise)
 static int set_source_deskew(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_time_field *f,
-                             const dcreg_sweep_motion *m, const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+                             const dcreg_sweep_motion *m, const PathTable *pt, const dcreg_voxel_params *p, dcreg_deskew_info *info,
+                             dcreg_voxel_info *vinfo) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (n <= 0) { c->fail("measure cloud is null or empty"); return DCREG_E_INVALID; }
     const int64_t off[2] = {0, n};
     DeskewRun d;
-    int rc = deskew_prepare(c, 1, off, stride, f, m, d);
+    int rc = pt ? deskew_path_prepare(c, 1, off, stride, f, *pt, d) : deskew_prepare(c, 1, off, stride, f, m, d);
     if (rc) return rc;
     if (p) return set_cloud_voxel(c, xyz, n, stride, on_device, p, false, 0.0, vinfo, &d, info);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2303,11 +2306,23 @@ static int set_source_deskew(dcreg_ctx *c, const float *xyz, int64_t n, int64_t 
 }
 int dcreg_set_source_deskew(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
                             const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
-    return set_source_deskew(c, xyz, n, stride, false, f, m, p, info, vinfo);
+    return set_source_deskew(c, xyz, n, stride, false, f, m, nullptr, p, info, vinfo);
 }
 int dcreg_set_source_deskew_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
                                    const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
-    return set_source_deskew(c, d_xyz, n, stride, true, f, m, p, info, vinfo);
+    return set_source_deskew(c, d_xyz, n, stride, true, f, m, nullptr, p, info, vinfo);
+}
+int dcreg_set_source_deskew_path(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_time_field *f, int64_t n_knots,
+                                 const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *path, const dcreg_voxel_params *p,
+                                 dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    const PathTable pt = {n_knots, knot_stamps, knot_poses, path};
+    return set_source_deskew(c, xyz, n, stride, false, f, nullptr, &pt, p, info, vinfo);
+}
+int dcreg_set_source_deskew_path_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_time_field *f, int64_t n_knots,
+                                        const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *path,
+                                        const dcreg_voxel_params *p, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    const PathTable pt = {n_knots, knot_stamps, knot_poses, path};
+    return set_source_deskew(c, d_xyz, n, stride, true, f, nullptr, &pt, p, info, vinfo);
 }
 int dcreg_set_source_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *p, dcreg_voxel_info *info) {
     return set_cloud_voxel(c, xyz, n, stride, false, p, false, 0.0, info);

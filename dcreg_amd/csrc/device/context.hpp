@@ -99,6 +99,21 @@ struct DeskewCloud {
     int from_data;                 // the span is the cloud's own minimum / maximum finite stamp (keys of k_deskew_span)
     int pad_;
 };
+// one cloud of a path deskew on the device (deskew.hip k_pack_deskew_path): its segment records segs[first_seg .. first_seg + n_seg), the
+// first and last stamp of its knot window, and the extrinsic E = (R row-major, t)
+struct PathCloud {
+    int64_t first_seg;
+    int n_seg;
+    int pad_;
+    double s_first, s_last;
+    double E[12];
+};
+// one (cloud, segment) record: the segment's twist xi_k (w then v), G_k = E^-1 B(t_ref)^-1 P_k (R row-major, t), its first stamp and length
+struct PathSeg {
+    double xi[6];
+    double G[12];
+    double s0, len;
+};
 // the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i) - the segments of voxel.hip and deskew.hip
 __device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
     int lo = 0, hi = n_clouds;
@@ -293,6 +308,8 @@ struct dcreg_ctx {
         DevBuf<dcreg::DeskewCloud> clouds;
         DevBuf<int64_t> d_off;
         DevBuf<unsigned long long> keys;
+        DevBuf<dcreg::PathCloud> pclouds;      // the path form (dcreg_deskew_path*): per cloud, and per (cloud, segment)
+        DevBuf<dcreg::PathSeg> segs;
     };
     DeskewBufs dsk;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
@@ -444,7 +461,8 @@ int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a lin
 // deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before
 // anything is queued).  upload_cloud given one packs the records with k_pack_deskew instead of k_pack (into its float4 buffer, or 3 floats
 // per point to out3 when set); deskew_readback queues the copy of the call's counts into `head` (the caller synchronises: it rides on the
-// readback the call has anyway), deskew_info decodes them.
+// readback the call has anyway), deskew_info decodes them.  deskew_path_prepare fills the path form (dcreg_deskew_path*) instead: the pack
+// is then k_pack_deskew_path, everything else goes the same way.
 struct DeskewRun {
     int n_clouds = 0;
     const int64_t *off = nullptr;          // host, n_clouds + 1
@@ -452,6 +470,9 @@ struct DeskewRun {
     double scale = 1.0;
     std::vector<DeskewCloud> clouds;
     bool any_from_data = false;
+    bool path = false;                     // the path form: pclouds and segs instead of clouds
+    std::vector<PathCloud> pclouds;
+    std::vector<PathSeg> segs;
     float *out3 = nullptr;
     bool queued = false;                   // the pack was queued (not for an empty call)
     bool read = false;                     // the counts were queued for readback
@@ -459,6 +480,14 @@ struct DeskewRun {
 };
 int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
                    DeskewRun &d);
+struct PathTable {                         // the knot table and path blocks of a dcreg_deskew_path* call (host memory, borrowed)
+    int64_t n_knots;
+    const double *stamps, *poses;
+    const dcreg_sweep_path *paths;
+};
+int deskew_path_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const PathTable &t,
+                        DeskewRun &d);
+int deskew_reserve(dcreg_ctx *c, const DeskewRun &d);       // the call's device buffers grow here, before upload_cloud queues anything
 int deskew_queue(dcreg_ctx *c, const float *src, int64_t n, int64_t stride, DeskewRun &d, float4 *out4);
 int deskew_readback(dcreg_ctx *c, DeskewRun &d);
 void deskew_info(const DeskewRun &d, int64_t n_in, dcreg_deskew_info *info);

@@ -5,6 +5,9 @@
 //                   64-bit keys: deterministic), read by the pack from the device (no readback)
 //   k_pack_deskew   replaces k_pack inside upload_cloud: reads a record's x y z and stamp words, finds its cloud (seg_of), evaluates
 //                   Exp(a xi) in fp64 and writes the packed float4 exactly as k_pack packs it (w = the point's index), or 3 floats
+//   k_pack_deskew_path   the same pack for dcreg_deskew_path*: the pose at a point's stamp is read off a sampled trajectory (a binary search
+//                   for its segment, Exp(u xi_k) along it) through a sensor-to-body extrinsic, from per-(cloud, segment) records the host
+//                   prepares (deskew_path_prepare)
 // Behind the pack everything runs as for a plain cloud - the voxel pass, the bounds, the source commit - so "bitwise the plain call of the
 // deskewed cloud" holds by construction.  The call's counts ride on the readback the call has anyway.
 #include <cmath>
@@ -128,6 +131,39 @@ static __global__ void __launch_bounds__(kDskBlock) k_deskew_span(const float *_
     }
 }
 
+// the tail both pack kernels share.  pack_store: point i as k_pack packs a record (w = the point's index), or 3 floats
+__device__ __forceinline__ void pack_store(float4 *__restrict__ out4, float *__restrict__ out3, int64_t i, float ox, float oy, float oz) {
+    if (out4) out4[i] = make_float4(ox, oy, oz, __uint_as_float((uint32_t)i));
+    else { out3[3 * i] = ox; out3[3 * i + 1] = oy; out3[3 * i + 2] = oz; }
+}
+// reduce_counts: a lane's counts (finite, outside its span, its stamp's key and ~key) reduce per wave, then per block, into keys[0..3].  Every
+// thread of the block calls it
+__device__ __forceinline__ void reduce_counts(unsigned long long fin, unsigned long long outside, unsigned long long kmin,
+                                              unsigned long long kmaxn, unsigned long long *__restrict__ keys) {
+    for (int o = 32; o > 0; o >>= 1) {
+        fin += __shfl_xor(fin, o);
+        outside += __shfl_xor(outside, o);
+        kmin = std::min(kmin, (unsigned long long)__shfl_xor(kmin, o));
+        kmaxn = std::min(kmaxn, (unsigned long long)__shfl_xor(kmaxn, o));
+    }
+    __shared__ unsigned long long sh[kDskBlock / 64][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sh[wave][0] = fin; sh[wave][1] = outside; sh[wave][2] = kmin; sh[wave][3] = kmaxn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kDskBlock / 64; ++w) {
+            fin += sh[w][0]; outside += sh[w][1];
+            kmin = std::min(kmin, sh[w][2]); kmaxn = std::min(kmaxn, sh[w][3]);
+        }
+        if (fin) {
+            atomicAdd(keys, fin);
+            if (outside) atomicAdd(keys + 1, outside);
+            atomicMin(keys + 2, kmin);
+            atomicMin(keys + 3, kmaxn);
+        }
+    }
+}
+
 // the pack of a deskewed cloud: out4[i] = (x', y', z', i) as k_pack packs a record, or out3[3i ..] = x', y', z'.  One point per lane; the call's
 // counts (finite points, stamps outside their span, minimum / maximum finite stamp) reduce per block into keys[0..3]
 static __global__ void __launch_bounds__(kDskBlock) k_pack_deskew(const float *__restrict__ xyz, int64_t n, int64_t stride, int column, int type,
@@ -165,31 +201,58 @@ static __global__ void __launch_bounds__(kDskBlock) k_pack_deskew(const float *_
             kmin = key_of(t);
             kmaxn = ~kmin;
         }
-        if (out4) out4[i] = make_float4(ox, oy, oz, __uint_as_float((uint32_t)i));
-        else { out3[3 * i] = ox; out3[3 * i + 1] = oy; out3[3 * i + 2] = oz; }
+        pack_store(out4, out3, i, ox, oy, oz);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        fin += __shfl_xor(fin, o);
-        outside += __shfl_xor(outside, o);
-        kmin = std::min(kmin, (unsigned long long)__shfl_xor(kmin, o));
-        kmaxn = std::min(kmaxn, (unsigned long long)__shfl_xor(kmaxn, o));
-    }
-    __shared__ unsigned long long sh[kDskBlock / 64][4];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[wave][0] = fin; sh[wave][1] = outside; sh[wave][2] = kmin; sh[wave][3] = kmaxn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kDskBlock / 64; ++w) {
-            fin += sh[w][0]; outside += sh[w][1];
-            kmin = std::min(kmin, sh[w][2]); kmaxn = std::min(kmaxn, sh[w][3]);
+    reduce_counts(fin, outside, kmin, kmaxn, keys);
+}
+
+// q = R p + t for a rigid transform stored as R[9] row-major then t[3]
+__device__ __forceinline__ void rigid_apply(const double *__restrict__ T, const double p[3], double q[3]) {
+    for (int a = 0; a < 3; ++a) q[a] = (T[3 * a] * p[0] + T[3 * a + 1] * p[1] + T[3 * a + 2] * p[2]) + T[9 + a];
+}
+
+// the pack of a cloud deskewed along its path (dcreg_deskew_path*): the point's cloud by seg_of, its segment by a binary search over the
+// starts of the cloud's segment records (the last one that starts at or before the stamp; the first for an earlier stamp), then q = E p,
+// q = Exp(u xi_k) q, p' = G_k q.  Lanes of a wave are neighbouring columns of a sweep: they read the same or neighbouring records.  Output
+// and counts as k_pack_deskew
+static __global__ void __launch_bounds__(kDskBlock) k_pack_deskew_path(const float *__restrict__ xyz, int64_t n, int64_t stride, int column, int type,
+                                                                       double scale, const int64_t *__restrict__ off, int n_clouds,
+                                                                       const PathCloud *__restrict__ cl, const PathSeg *__restrict__ sg,
+                                                                       unsigned long long *__restrict__ keys, float4 *__restrict__ out4,
+                                                                       float *__restrict__ out3) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long fin = 0, outside = 0, kmin = ~0ull, kmaxn = ~0ull;
+    if (i < n) {
+        const float *r = xyz + i * stride;
+        const float x = r[0], y = r[1], z = r[2];
+        const double t = stamp_of(r, column, type, scale);
+        float ox = __builtin_nanf(""), oy = ox, oz = ox;
+        if (finite3f(x, y, z) && isfinite(t)) {
+            const uint32_t s = n_clouds == 1 ? 0u : seg_of(off, n_clouds, i);
+            const PathCloud &q = cl[s];
+            const PathSeg *S = sg + q.first_seg;
+            int lo = 0, hi = q.n_seg - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (S[mid].s0 <= t) lo = mid; else hi = mid - 1;
+            }
+            const PathSeg &g = S[lo];
+            const double u = (t - g.s0) / g.len;
+            const double w[3] = {u * g.xi[0], u * g.xi[1], u * g.xi[2]}, v[3] = {u * g.xi[3], u * g.xi[4], u * g.xi[5]};
+            const double p[3] = {(double)x, (double)y, (double)z};
+            double a[3], b[3], o[3];
+            rigid_apply(q.E, p, a);
+            exp_apply(w, v, a, b);
+            rigid_apply(g.G, b, o);
+            ox = (float)o[0]; oy = (float)o[1]; oz = (float)o[2];
+            fin = 1;
+            outside = (t < q.s_first || t > q.s_last) ? 1 : 0;
+            kmin = key_of(t);
+            kmaxn = ~kmin;
         }
-        if (fin) {
-            atomicAdd(keys, fin);
-            if (outside) atomicAdd(keys + 1, outside);
-            atomicMin(keys + 2, kmin);
-            atomicMin(keys + 3, kmaxn);
-        }
+        pack_store(out4, out3, i, ox, oy, oz);
     }
+    reduce_counts(fin, outside, kmin, kmaxn, keys);
 }
 
 bool is_rotation(const double R[9]) {
@@ -204,10 +267,10 @@ bool is_rotation(const double R[9]) {
 
 }  // namespace
 
-int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
-                   DeskewRun &d) {
+// what both forms check of the clouds and the time field (blocks: the per-cloud motions or path blocks are there)
+static int check_clouds_and_field(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, bool blocks) {
     if (!f) { c->fail("null time field"); return DCREG_E_INVALID; }
-    if (n_clouds < 0 || (n_clouds > 0 && (!off || !m)) || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
+    if (n_clouds < 0 || (n_clouds > 0 && (!off || !blocks)) || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
     if (n_clouds > 0 && off[0] != 0) { c->fail("cloud offsets must start at 0"); return DCREG_E_INVALID; }
     for (int s = 0; s < n_clouds; ++s)
         if (off[s + 1] < off[s]) { c->fail("cloud offsets decrease at cloud %d", s); return DCREG_E_INVALID; }
@@ -218,6 +281,20 @@ int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t strid
         return DCREG_E_INVALID;
     }
     if (!(std::isfinite(f->scale) && f->scale > 0.0)) { c->fail("time scale %g: finite and > 0 expected", f->scale); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+static void run_of(DeskewRun &d, int n_clouds, const int64_t *off, const dcreg_time_field *f) {
+    d.n_clouds = n_clouds;
+    d.off = off;
+    d.column = f->column;
+    d.type = f->type;
+    d.scale = f->scale;
+}
+
+int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const dcreg_sweep_motion *m,
+                   DeskewRun &d) {
+    if (int rc = check_clouds_and_field(c, n_clouds, off, stride, f, m != nullptr)) return rc;
     d = DeskewRun();
     d.clouds.resize((size_t)n_clouds);
     for (int s = 0; s < n_clouds; ++s) {
@@ -242,27 +319,154 @@ int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t strid
         o.pad_ = 0;
         d.any_from_data |= o.from_data != 0;
     }
-    d.n_clouds = n_clouds;
-    d.off = off;
-    d.column = f->column;
-    d.type = f->type;
-    d.scale = f->scale;
+    run_of(d, n_clouds, off, f);
+    return DCREG_OK;
+}
+
+static bool finite_n(const double *v, int n) {
+    bool ok = true;
+    for (int k = 0; k < n; ++k) ok &= std::isfinite(v[k]);
+    return ok;
+}
+// C = A^T B of two rotations; o = A^T v
+static void mat3tmul(const double *A, const double *B, double *C) {
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
+}
+static void mat3tvec(const double *A, const double v[3], double o[3]) {
+    for (int i = 0; i < 3; ++i) o[i] = A[i] * v[0] + A[3 + i] * v[1] + A[6 + i] * v[2];
+}
+
+// the path form: every refusal of include/dcreg.h, then per (cloud, segment) the twist xi_k and G_k = E^-1 B(t_ref)^-1 P_k in double.  A knot
+// and a segment of the table are checked (and the segment's twist taken) once per call, however many windows hold them.
+int deskew_path_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t stride, const dcreg_time_field *f, const PathTable &t,
+                        DeskewRun &d) {
+    if (int rc = check_clouds_and_field(c, n_clouds, off, stride, f, t.paths != nullptr)) return rc;
+    if (n_clouds > 0 && (t.n_knots < 0 || !t.stamps || !t.poses)) { c->fail("null knot table"); return DCREG_E_INVALID; }
+    d = DeskewRun();
+    d.path = true;
+    d.pclouds.resize((size_t)n_clouds);
+    int64_t n_seg = 0;
+    for (int s = 0; s < n_clouds; ++s) {
+        const dcreg_sweep_path &q = t.paths[s];
+        if (q.n_knots < 2 || q.first_knot < 0 || q.first_knot > t.n_knots || (int64_t)q.n_knots > t.n_knots - q.first_knot) {
+            c->fail("cloud %d: the window of %d knots from %lld is outside the table of %lld knots or has fewer than 2 knots", s, q.n_knots,
+                    (long long)q.first_knot, (long long)t.n_knots);
+            return DCREG_E_INVALID;
+        }
+        n_seg += q.n_knots - 1;
+    }
+    d.segs.resize((size_t)n_seg);
+    int64_t k_lo = t.n_knots, k_hi = 0;              // the knots some window holds lie in [k_lo, k_hi)
+    for (int s = 0; s < n_clouds; ++s) {
+        k_lo = std::min(k_lo, t.paths[s].first_knot);
+        k_hi = std::max(k_hi, t.paths[s].first_knot + t.paths[s].n_knots);
+    }
+    std::vector<char> knot_ok((size_t)std::max<int64_t>(k_hi - k_lo, 0), 0), seg_ok(knot_ok.size(), 0);
+    std::vector<double> xis(6 * knot_ok.size());
+    n_seg = 0;
+    for (int s = 0; s < n_clouds; ++s) {
+        const dcreg_sweep_path &q = t.paths[s];
+        const int K = q.n_knots;
+        const double *st = t.stamps + q.first_knot, *P = t.poses + 12 * q.first_knot;
+        for (int k = 0; k < K; ++k) {
+            const int64_t j = q.first_knot + k, jj = j - k_lo;
+            if (!knot_ok[(size_t)jj]) {
+                if (!finite_n(P + 12 * k, 12)) { c->fail("cloud %d: the pose of knot %lld is not finite", s, (long long)j); return DCREG_E_INVALID; }
+                if (!is_rotation(P + 12 * k)) {
+                    c->fail("cloud %d: R of knot %lld is not a rotation (|R^T R - I| > 1e-6 or det <= 0)", s, (long long)j);
+                    return DCREG_E_INVALID;
+                }
+                knot_ok[(size_t)jj] = 1;
+            }
+            if (!std::isfinite(st[k]) || (k > 0 && !(st[k] > st[k - 1]))) {
+                c->fail("cloud %d: the stamps of its knots are not finite and strictly increasing at knot %lld", s, (long long)j);
+                return DCREG_E_INVALID;
+            }
+            if (k > 0 && !seg_ok[(size_t)jj - 1]) {
+                const double *A = P + 12 * (k - 1), *B = P + 12 * k;
+                const double dt[3] = {B[9] - A[9], B[10] - A[10], B[11] - A[11]};
+                double R[9], tt[3];
+                mat3tmul(A, B, R);
+                mat3tvec(A, dt, tt);
+                const double th = se3Log(R, tt, &xis[6 * ((size_t)jj - 1)]);
+                if (!(th < M_PI / 2)) {
+                    c->fail("cloud %d: the segment before knot %lld rotates by %g rad (below pi/2 expected)", s, (long long)j, th);
+                    return DCREG_E_INVALID;
+                }
+                seg_ok[(size_t)jj - 1] = 1;
+            }
+        }
+        if (!finite_n(q.ext_R, 9) || !finite_n(q.ext_t, 3)) { c->fail("cloud %d: the extrinsic is not finite", s); return DCREG_E_INVALID; }
+        if (!is_rotation(q.ext_R)) { c->fail("cloud %d: the extrinsic's R is not a rotation (|R^T R - I| > 1e-6 or det <= 0)", s); return DCREG_E_INVALID; }
+        if (!(std::isfinite(q.t_ref) && q.t_ref >= st[0] && q.t_ref <= st[K - 1])) {
+            c->fail("cloud %d: t_ref %.17g outside its knots' [%.17g, %.17g]", s, q.t_ref, st[0], st[K - 1]);
+            return DCREG_E_INVALID;
+        }
+        int kr = 0;                                    // B(t_ref) = P_kr Exp(ur xi_kr) = (Rb, P_kr.t + P_kr.R tb)
+        for (int j = 1; j <= K - 2; ++j) kr += st[j] <= q.t_ref ? 1 : 0;
+        const double ur = (q.t_ref - st[kr]) / (st[kr + 1] - st[kr]);
+        const double *xr = &xis[6 * (size_t)(q.first_knot - k_lo + kr)], *Pr = P + 12 * kr;
+        const double xu[6] = {ur * xr[0], ur * xr[1], ur * xr[2], ur * xr[3], ur * xr[4], ur * xr[5]};
+        double Re[9], te[3], Rb[9], tb[3];
+        se3Exp(xu, Re, te);
+        mat3mul(Pr, Re, Rb);
+        for (int a = 0; a < 3; ++a) tb[a] = Pr[3 * a] * te[0] + Pr[3 * a + 1] * te[1] + Pr[3 * a + 2] * te[2];
+        PathCloud &o = d.pclouds[(size_t)s];
+        o.first_seg = n_seg;
+        o.n_seg = K - 1;
+        o.pad_ = 0;
+        o.s_first = st[0];
+        o.s_last = st[K - 1];
+        std::memcpy(o.E, q.ext_R, sizeof(q.ext_R));
+        std::memcpy(o.E + 9, q.ext_t, sizeof(q.ext_t));
+        for (int k = 0; k < K - 1; ++k) {
+            PathSeg &g = d.segs[(size_t)(n_seg + k)];
+            std::memcpy(g.xi, &xis[6 * (size_t)(q.first_knot - k_lo + k)], sizeof(g.xi));
+            const double *Pk = P + 12 * k;
+            double M[9], dk[3], tm[3];                 // B(t_ref)^-1 P_k = (Rb^T R_k, Rb^T ((t_k - t_kr) - tb))
+            mat3tmul(Rb, Pk, M);
+            for (int a = 0; a < 3; ++a) dk[a] = (Pk[9 + a] - Pr[9 + a]) - tb[a];
+            mat3tvec(Rb, dk, tm);
+            for (int a = 0; a < 3; ++a) tm[a] -= q.ext_t[a];
+            mat3tmul(q.ext_R, M, g.G);                 // E^-1 (M, tm) = (E_R^T M, E_R^T (tm - E_t))
+            mat3tvec(q.ext_R, tm, g.G + 9);
+            g.s0 = st[k];
+            g.len = st[k + 1] - st[k];
+        }
+        n_seg += K - 1;
+    }
+    run_of(d, n_clouds, off, f);
+    return DCREG_OK;
+}
+
+int deskew_reserve(dcreg_ctx *c, const DeskewRun &d) {
+    dcreg_ctx::DeskewBufs &B = c->dsk;
+    if (B.d_off.ensure(c, (size_t)d.n_clouds + 1) || B.keys.ensure(c, (size_t)kHead + 2 * (size_t)d.n_clouds)) return DCREG_E_NOMEM;
+    if (d.path ? B.pclouds.ensure(c, d.pclouds.size()) || B.segs.ensure(c, d.segs.size()) : B.clouds.ensure(c, (size_t)d.n_clouds)) return DCREG_E_NOMEM;
     return DCREG_OK;
 }
 
 int deskew_queue(dcreg_ctx *c, const float *src, int64_t n, int64_t stride, DeskewRun &d, float4 *out4) {
     dcreg_ctx::DeskewBufs &B = c->dsk;
     const size_t nk = (size_t)kHead + 2 * (size_t)d.n_clouds;
-    if (B.clouds.ensure(c, (size_t)d.n_clouds) || B.d_off.ensure(c, (size_t)d.n_clouds + 1) || B.keys.ensure(c, nk)) return DCREG_E_NOMEM;
-    HIP_TRY(c, hipMemcpyAsync(B.clouds.data(), d.clouds.data(), sizeof(DeskewCloud) * d.clouds.size(), hipMemcpyHostToDevice, c->stream));
+    if (d.path) {
+        HIP_TRY(c, hipMemcpyAsync(B.pclouds.data(), d.pclouds.data(), sizeof(PathCloud) * d.pclouds.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(B.segs.data(), d.segs.data(), sizeof(PathSeg) * d.segs.size(), hipMemcpyHostToDevice, c->stream));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(B.clouds.data(), d.clouds.data(), sizeof(DeskewCloud) * d.clouds.size(), hipMemcpyHostToDevice, c->stream));
+    }
     HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), d.off, sizeof(int64_t) * ((size_t)d.n_clouds + 1), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(B.keys.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     HIP_TRY(c, hipMemsetAsync(B.keys.data() + 2, 0xFF, (nk - 2) * sizeof(unsigned long long), c->stream));
     if (d.any_from_data)
         hipLaunchKernelGGL(k_deskew_span, dim3(blocks(n, kDskBlock * kSpanPerThread)), dim3(kDskBlock), 0, c->stream, src, n, stride, d.column, d.type,
                            d.scale, B.d_off.data(), d.n_clouds, B.clouds.data(), B.keys.data());
-    hipLaunchKernelGGL(k_pack_deskew, dim3(blocks(n, kDskBlock)), dim3(kDskBlock), 0, c->stream, src, n, stride, d.column, d.type, d.scale,
-                       B.d_off.data(), d.n_clouds, B.clouds.data(), B.keys.data(), out4, d.out3);
+    if (d.path)
+        hipLaunchKernelGGL(k_pack_deskew_path, dim3(blocks(n, kDskBlock)), dim3(kDskBlock), 0, c->stream, src, n, stride, d.column, d.type, d.scale,
+                           B.d_off.data(), d.n_clouds, B.pclouds.data(), B.segs.data(), B.keys.data(), out4, d.out3);
+    else
+        hipLaunchKernelGGL(k_pack_deskew, dim3(blocks(n, kDskBlock)), dim3(kDskBlock), 0, c->stream, src, n, stride, d.column, d.type, d.scale,
+                           B.d_off.data(), d.n_clouds, B.clouds.data(), B.keys.data(), out4, d.out3);
     HIP_TRY(c, hipGetLastError());
     d.queued = true;
     return DCREG_OK;
@@ -291,13 +495,14 @@ using namespace dcreg;
 
 // dcreg_deskew*: with a voxel block the voxel pass of the deskewed clouds (voxel.hip); without one every point in input order, written by the
 // pack itself (to the caller's device buffer, or to the context's and copied to the host with the counts)
+// (pt: the path form, dcreg_deskew_path*; m otherwise)
 static int deskew(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_time_field *f,
-                  const dcreg_sweep_motion *m, const dcreg_voxel_params *voxel, float *out, int64_t capacity, int64_t *out_off,
-                  dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+                  const dcreg_sweep_motion *m, const PathTable *pt, const dcreg_voxel_params *voxel, float *out, int64_t capacity,
+                  int64_t *out_off, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     DeskewRun d;
-    int rc = deskew_prepare(c, n_clouds, off, stride, f, m, d);
+    int rc = pt ? deskew_path_prepare(c, n_clouds, off, stride, f, *pt, d) : deskew_prepare(c, n_clouds, off, stride, f, m, d);
     if (rc) return rc;
     const int64_t n = n_clouds > 0 ? off[n_clouds] : 0;
     if (voxel) {
@@ -328,11 +533,25 @@ extern "C" {
 int dcreg_deskew(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *f,
                  const dcreg_sweep_motion *motions, const dcreg_voxel_params *voxel, float *out_xyz, int64_t capacity_points, int64_t *out_offsets,
                  dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
-    return deskew(c, n_clouds, xyz, offsets, stride_floats, false, f, motions, voxel, out_xyz, capacity_points, out_offsets, info, vinfo);
+    return deskew(c, n_clouds, xyz, offsets, stride_floats, false, f, motions, nullptr, voxel, out_xyz, capacity_points, out_offsets, info, vinfo);
 }
 int dcreg_deskew_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *f,
                         const dcreg_sweep_motion *motions, const dcreg_voxel_params *voxel, float *d_out_xyz, int64_t capacity_points,
                         int64_t *out_offsets, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
-    return deskew(c, n_clouds, d_xyz, offsets, stride_floats, true, f, motions, voxel, d_out_xyz, capacity_points, out_offsets, info, vinfo);
+    return deskew(c, n_clouds, d_xyz, offsets, stride_floats, true, f, motions, nullptr, voxel, d_out_xyz, capacity_points, out_offsets, info, vinfo);
+}
+int dcreg_deskew_path(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *f,
+                      int64_t n_knots, const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *paths,
+                      const dcreg_voxel_params *voxel, float *out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_deskew_info *info,
+                      dcreg_voxel_info *vinfo) {
+    const PathTable pt = {n_knots, knot_stamps, knot_poses, paths};
+    return deskew(c, n_clouds, xyz, offsets, stride_floats, false, f, nullptr, &pt, voxel, out_xyz, capacity_points, out_offsets, info, vinfo);
+}
+int dcreg_deskew_path_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                             const dcreg_time_field *f, int64_t n_knots, const double *knot_stamps, const double *knot_poses,
+                             const dcreg_sweep_path *paths, const dcreg_voxel_params *voxel, float *d_out_xyz, int64_t capacity_points,
+                             int64_t *out_offsets, dcreg_deskew_info *info, dcreg_voxel_info *vinfo) {
+    const PathTable pt = {n_knots, knot_stamps, knot_poses, paths};
+    return deskew(c, n_clouds, d_xyz, offsets, stride_floats, true, f, nullptr, &pt, voxel, d_out_xyz, capacity_points, out_offsets, info, vinfo);
 }
 }

@@ -736,6 +736,7 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_time_field")) return sizeof(dcreg_time_field);
     if (!std::strcmp(name, "dcreg_sweep_motion")) return sizeof(dcreg_sweep_motion);
     if (!std::strcmp(name, "dcreg_deskew_info")) return sizeof(dcreg_deskew_info);
+    if (!std::strcmp(name, "dcreg_sweep_path")) return sizeof(dcreg_sweep_path);
     return 0;
 }
 

@@ -449,3 +449,87 @@ def lidar_sweep_moving(world, pose_begin, motion, period=0.1, ref=0.5, rings=128
     rec[:, :3] = d * rng_px[:, None]
     rec[:, 3] = stamps[jc]
     return rec, T0 @ se3_exp(ref * xi)
+
+
+def lidar_sweep_path(world, body_poses_at, extrinsic, period=0.1, t_ref=0.05, rings=128, cols=1024, fov_up=22.5, fov_down=-22.5, min_range=0.5,
+                     max_range=80.0, noise=0.01, seed=0):
+    """lidar_sweep_moving along a PATH: column j is measured at s_j = (j + 0.5) / cols * period seconds from the sensor pose B(s_j) E, with
+    B = body_poses_at(stamps [m]) -> (R [m, 3, 3], t [m, 3]) the poses of the body in the world (a vectorised callable, used as it answers:
+    no interpolation here) and E = extrinsic the pose of the sensor in the body frame (4x4).  Same fixed-point column assignment, beam model
+    and record layout as lidar_sweep_moving.  -> (records [rings * cols, 4] float32 = x y z in the sensor frame of the column's instant and
+    the stamp s_j, ring after ring; the true sensor pose B(t_ref) E, 4x4)."""
+    rng = np.random.default_rng(seed)
+    E = np.asarray(extrinsic, np.float64)
+
+    def sensor_poses(s):
+        Rb, tb = body_poses_at(np.asarray(s, np.float64))
+        return Rb @ E[:3, :3][None], Rb @ E[:3, 3] + tb
+
+    stamps = (np.arange(cols) + 0.5) / cols * period
+    Rc, tc = sensor_poses(stamps)                                 # column poses in the world
+    Rm, tm = sensor_poses(np.array([0.5 * period]))
+    Rm, tm = Rm[0], tm[0]
+    p = np.asarray(world, np.float32).astype(np.float64)
+    d0 = p - tm
+    p = p[np.einsum("ij,ij->i", d0, d0) < (max_range + np.linalg.norm(tc - tm, axis=1).max() + 1.0) ** 2]
+
+    def column_of(j):
+        body = np.einsum("mji,mj->mi", Rc[j], p - tc[j])          # R_j^T (p - t_j)
+        az = np.arctan2(body[:, 1], body[:, 0])
+        return np.minimum((az + np.pi) / (2 * np.pi) * cols, cols - 1).astype(np.int64), body
+
+    body = (p - tm) @ Rm
+    j = np.minimum((np.arctan2(body[:, 1], body[:, 0]) + np.pi) / (2 * np.pi) * cols, cols - 1).astype(np.int64)
+    for _ in range(6):                                            # the column's own pose sees the point in that column
+        jn, body = column_of(j)
+        if np.array_equal(jn, j):
+            break
+        j = jn
+    jn, body = column_of(j)
+    keep = jn == j
+    body, col = body[keep], j[keep]
+    r = np.linalg.norm(body, axis=1)
+    ok = (r > min_range) & (r < max_range)
+    body, r, col = body[ok], r[ok], col[ok]
+    el = np.degrees(np.arcsin(body[:, 2] / r))
+    ring = np.floor((fov_up - el) / (fov_up - fov_down) * rings).astype(np.int64)
+    inside = (ring >= 0) & (ring < rings)
+    pix, r = ring[inside] * cols + col[inside], r[inside]
+    order = np.lexsort((r, pix))
+    first = order[np.r_[True, pix[order][1:] != pix[order][:-1]]] if len(order) else order
+    rng_px = np.full(rings * cols, np.nan)
+    rng_px[pix[first]] = r[first] + rng.normal(0.0, noise, len(first))
+    jr, jc = np.divmod(np.arange(rings * cols), cols)
+    a = (jc + 0.5) / cols * 2 * np.pi - np.pi
+    e = np.radians(fov_up - (jr + 0.5) * (fov_up - fov_down) / rings)
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], 1)
+    rec = np.empty((rings * cols, 4), np.float32)
+    rec[:, :3] = d * rng_px[:, None]
+    rec[:, 3] = stamps[jc]
+    Rr, tr = sensor_poses(np.array([float(t_ref)]))
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = Rr[0], tr[0]
+    return rec, T
+
+
+def turn_in_path(pose_begin, alpha=30.0, v0=10.0, dec=8.0):
+    """A body path a constant twist cannot express, as lidar_sweep_path takes it: planar motion from pose_begin (4x4, body -> world at s = 0)
+    with constant angular acceleration in yaw (yaw = alpha s^2 / 2) and speed v0 - dec s along the heading; the position is the integral of
+    the velocity by 16-point Gauss-Legendre quadrature over [0, s] (exact to rounding for s of a sweep).
+    -> callable stamps [m] -> (R [m, 3, 3], t [m, 3])"""
+    T0 = np.asarray(pose_begin, np.float64)
+    x16, w16 = np.polynomial.legendre.leggauss(16)
+
+    def at(stamps):
+        s = np.asarray(stamps, np.float64).reshape(-1)
+        tau = 0.5 * s[:, None] * (x16 + 1.0)
+        wt = 0.5 * s[:, None] * w16
+        speed, yaw = v0 - dec * tau, 0.5 * alpha * tau ** 2
+        local = np.zeros((len(s), 3))
+        local[:, 0], local[:, 1] = np.sum(wt * speed * np.cos(yaw), 1), np.sum(wt * speed * np.sin(yaw), 1)
+        c, sn = np.cos(0.5 * alpha * s ** 2), np.sin(0.5 * alpha * s ** 2)
+        Rl = np.zeros((len(s), 3, 3))
+        Rl[:, 0, 0], Rl[:, 0, 1], Rl[:, 1, 0], Rl[:, 1, 1], Rl[:, 2, 2] = c, -sn, sn, c, 1.0
+        return T0[:3, :3][None] @ Rl, local @ T0[:3, :3].T + T0[:3, 3]
+
+    return at

@@ -24,6 +24,8 @@
  *                                                                                   dcreg_set_target_voxel[_device]
  *       motion compensation (deskew) of sweeps from per-point stamps             -> dcreg_deskew[_device],
  *                                                                                   dcreg_set_source_deskew[_device]
+ *       ... along a sampled trajectory, through a sensor-to-body extrinsic       -> dcreg_deskew_path[_device],
+ *                                                                                   dcreg_set_source_deskew_path[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -393,6 +395,59 @@ int dcreg_set_source_deskew(dcreg_ctx *, const float *xyz, int64_t n, int64_t st
 int dcreg_set_source_deskew_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_time_field *,
                                    const dcreg_sweep_motion *, const dcreg_voxel_params *voxel, dcreg_deskew_info *info,
                                    dcreg_voxel_info *vinfo);
+
+/* ---------------- deskew along a sampled trajectory, through a sensor-to-body extrinsic ----------------
+ * The same calls in the same place (inside the pack), for callers that have an odometry or IMU-propagated pose many times per sweep instead of
+ * one twist.  A call carries one knot table and one path block per cloud:
+ *   - knot table: n_knots instants knot_stamps[j] (seconds) and poses knot_poses[12 j ..] = R[9] row-major then t[3], the pose of the BODY
+ *     in any fixed frame at that instant;
+ *   - the path block of cloud c names its window [first_knot, first_knot + n_knots) of the table (K = n_knots >= 2 knots with stamps s[0..K-1]
+ *     and poses P[0..K-1]; windows of different clouds may overlap or coincide: one trajectory for a whole drive, or one table per cloud),
+ *     the reference instant t_ref (seconds, absolute) and the extrinsic E = (ext_R, ext_t), the pose of the SENSOR in the body frame
+ *     (identity: the knots are the sensor's own poses);
+ *   - the time field is decoded exactly as above: s_i = scale * (double)stamp_i;
+ *   - segment twists, on the host in double: xi_k = Log(P_k^-1 P_k+1), k = 0..K-2 (P_k^-1 P_k+1 = (R_k^T R_k+1, R_k^T (t_k+1 - t_k)));
+ *   - the segment of an instant s: k(s) = the number of j in [1, K-2] with s[j] <= s (an instant on a knot belongs to the segment that
+ *     starts there, the last knot to the last segment); u(s) = (s - s[k]) / (s[k+1] - s[k]) (an IEEE double division);
+ *     B(s) = P_k Exp(u xi_k), Exp as above;
+ *   - an instant before s[0] or after s[K-1] is extrapolated along the first / last segment (u < 0, u > 1) and counted in n_outside;
+ *   - p'_i = (float)(E^-1 B(t_ref)^-1 B(s_i) E p_i), evaluated in double as q = E p_i, q = Exp(u_i xi_k) q, p'_i = G_k q with
+ *     G_k = E^-1 B(t_ref)^-1 P_k computed once per (cloud, segment) on the host in double, translations taken relative to the knot that
+ *     starts t_ref's segment (knots kilometres from the origin cost no precision).  The output is the sweep in the SENSOR frame at t_ref:
+ *     a registration of it estimates the sensor pose B(t_ref) E at that instant (the body pose is that times E^-1);
+ *   - a point whose x, y, z or s_i is not finite comes out as three NaN (it is not counted in n_finite).  dcreg_deskew_info is the one
+ *     above; n_outside counts the finite stamps outside [s[0], s[K-1]] of their cloud's window;
+ *   - there is no bit-for-bit clause here: a path that stands still returns the points to within rounding (G_k of equal poses is the
+ *     identity up to rounding only), not their bits.
+ * A point's result depends on its own record, its cloud's path block and that block's knot window only.
+ * DCREG_E_INVALID, and nothing is written: a null table or null blocks with clouds present; a window outside the table or with fewer than 2
+ * knots; stamps of a window that are not finite and strictly increasing; a knot pose or extrinsic that is not finite or not a rotation (as
+ * above); a segment that rotates by pi/2 or more; a t_ref that is not finite or lies outside [s[0], s[K-1]]; the time field's refusals and,
+ * with a voxel block, the voxel pass's.  Only knots inside some cloud's window are checked.  DCREG_E_STATE: a linearisation in flight. */
+typedef struct dcreg_sweep_path {
+    int64_t first_knot;  /* the cloud's window of the knot table: [first_knot, first_knot + n_knots) */
+    int n_knots;         /* >= 2 */
+    int reserved_;
+    double t_ref;        /* reference instant in seconds, inside [s[0], s[n_knots - 1]] of the window */
+    double ext_R[9], ext_t[3];   /* pose of the sensor in the body frame (R row-major) */
+} dcreg_sweep_path;
+/* The four forms of the constant-twist deskew with (n_knots, knot_stamps, knot_poses, paths) in place of motions: the table and the blocks
+ * (one per cloud) are host memory in all four; voxel block, output layout, capacity, info / vinfo, stream and in-flight behaviour are those
+ * of dcreg_deskew* / dcreg_set_source_deskew*. */
+int dcreg_deskew_path(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_time_field *,
+                      int64_t n_knots, const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *paths,
+                      const dcreg_voxel_params *voxel, float *out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_deskew_info *info,
+                      dcreg_voxel_info *vinfo);
+int dcreg_deskew_path_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                             const dcreg_time_field *, int64_t n_knots, const double *knot_stamps, const double *knot_poses,
+                             const dcreg_sweep_path *paths, const dcreg_voxel_params *voxel, float *d_out_xyz, int64_t capacity_points,
+                             int64_t *out_offsets, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
+int dcreg_set_source_deskew_path(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_time_field *, int64_t n_knots,
+                                 const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *path,
+                                 const dcreg_voxel_params *voxel, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
+int dcreg_set_source_deskew_path_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_time_field *,
+                                        int64_t n_knots, const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *path,
+                                        const dcreg_voxel_params *voxel, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
