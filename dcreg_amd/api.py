@@ -148,6 +148,9 @@ EXPORTS = [
     "dcreg_set_target_voxel", "dcreg_set_target_voxel_device",
     "dcreg_deskew", "dcreg_deskew_device", "dcreg_set_source_deskew", "dcreg_set_source_deskew_device",
     "dcreg_deskew_path", "dcreg_deskew_path_device", "dcreg_set_source_deskew_path", "dcreg_set_source_deskew_path_device",
+    "dcreg_default_place_params", "dcreg_place_descriptors", "dcreg_place_descriptors_device", "dcreg_places_reset", "dcreg_places_count",
+    "dcreg_places_add", "dcreg_places_add_clouds", "dcreg_places_add_clouds_device", "dcreg_places_add_source", "dcreg_places_get",
+    "dcreg_places_query", "dcreg_places_query_clouds", "dcreg_places_query_clouds_device", "dcreg_places_query_source",
 ]
 
 _lib = None
@@ -428,6 +431,89 @@ def _paths(paths, n, st, P, what):
     return arr
 
 
+class PlaceParams(C.Structure):
+    _fields_ = [("n_rings", C.c_int), ("n_sectors", C.c_int), ("max_range", C.c_double), ("min_range", C.c_double), ("z_offset", C.c_double)]
+
+
+class PlaceInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_used", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_place_params": PlaceParams, "dcreg_place_info": PlaceInfo})
+PLACE_MAX_K = 64
+
+
+def _check_place_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_place_params block"""
+    if not isinstance(p, PlaceParams):
+        raise ValueError("%s: place_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not 1 <= p.n_rings <= 64:
+        raise ValueError("%s: n_rings in [1, 64] is expected, got %d" % (what, p.n_rings))
+    if not 1 <= p.n_sectors <= 128:
+        raise ValueError("%s: n_sectors in [1, 128] is expected, got %d" % (what, p.n_sectors))
+    if not (np.isfinite(p.max_range) and p.max_range > 0.0):
+        raise ValueError("%s: a finite max_range > 0 is expected, got %r" % (what, p.max_range))
+    if not (np.isfinite(p.min_range) and 0.0 <= p.min_range < p.max_range):
+        raise ValueError("%s: a finite min_range in [0, max_range) is expected, got %r" % (what, p.min_range))
+    if not np.isfinite(p.z_offset):
+        raise ValueError("%s: a finite z_offset is expected, got %r" % (what, p.z_offset))
+
+
+def place_params(n_rings=20, n_sectors=60, max_range=80.0, min_range=0.0, z_offset=2.0):
+    """dcreg_place_params: the Scan Context grid (rings x sectors out to max_range, nothing nearer than min_range) and the height offset"""
+    p = PlaceParams()
+    p.n_rings, p.n_sectors = int(n_rings), int(n_sectors)
+    p.max_range, p.min_range, p.z_offset = float(max_range), float(min_range), float(z_offset)
+    _check_place_params(p, "place_params")
+    return p
+
+
+def place_guess(shift, n_sectors):
+    """the 4x4 start pose for registering a query (source) against the entry (target) a search returned with this shift:
+    a rotation about z by 2 pi shift / n_sectors, no translation (include/dcreg.h)"""
+    n_sectors = int(n_sectors)
+    if not 1 <= n_sectors <= 128:
+        raise ValueError("place_guess: n_sectors in [1, 128] is expected, got %d" % n_sectors)
+    if not 0 <= int(shift) < n_sectors:
+        raise ValueError("place_guess: a shift in [0, %d) is expected, got %d" % (n_sectors, int(shift)))
+    a = 2.0 * np.pi * int(shift) / n_sectors
+    T = np.eye(4)
+    T[0, 0], T[0, 1], T[1, 0], T[1, 1] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
+    return T
+
+
+def _place_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_used": i.n_used}
+
+
+def _descriptors(desc, bins, what):
+    """[n, bins] float32 of finite values"""
+    d = np.ascontiguousarray(desc, dtype=np.float32)
+    if d.ndim == 3:
+        d = d.reshape(d.shape[0], -1)
+    if d.ndim == 1 and d.size == bins:
+        d = d.reshape(1, bins)
+    if d.ndim != 2 or d.shape[1] != bins:
+        raise ValueError("%s: descriptors of %d floats each are expected, got shape %s" % (what, bins, np.shape(desc)))
+    if not np.all(np.isfinite(d)):
+        raise ValueError("%s: a descriptor holds a value that is not finite" % what)
+    return d
+
+
+def _check_range(first, last, k, what):
+    if int(first) < 0 or int(first) > int(last):
+        raise ValueError("%s: a range 0 <= first <= last is expected, got [%d, %d)" % (what, int(first), int(last)))
+    if not 1 <= int(k) <= PLACE_MAX_K:
+        raise ValueError("%s: k in [1, %d] is expected, got %d" % (what, PLACE_MAX_K, int(k)))
+
+
+def _offsets(offsets, what):
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("%s: offsets must start at 0 and not decrease" % what)
+    return off
+
+
 def _clouds(clouds, what):
     """(xyz [N, c] float32, offsets [n + 1] int64, was_list) of a list of [n_i, c] float32 arrays or an (xyz, offsets) pair"""
     if isinstance(clouds, tuple):
@@ -573,6 +659,24 @@ def load():
         L.dcreg_deskew_path_device.argtypes = L.dcreg_deskew_path.argtypes
         for name in ("dcreg_set_source_deskew_path", "dcreg_set_source_deskew_path_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64] + tail + [C.POINTER(DeskewInfo), C.POINTER(VoxelInfo)]
+    if hasattr(L, "dcreg_places_reset"):       # (absent from an older build loaded through DCREG_LIB for an A/B)
+        pp, pi = C.POINTER(PlaceParams), C.POINTER(PlaceInfo)
+        res = [C.c_int64, C.c_int64, C.c_int, ip, ip, dp]           # first, last, k, idx, shift, dist
+        L.dcreg_default_place_params.argtypes = [pp]
+        for name in ("dcreg_place_descriptors", "dcreg_place_descriptors_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64, pp, vp, pi]
+        L.dcreg_places_reset.argtypes = [vp, pp]
+        L.dcreg_places_count.restype = C.c_int64
+        L.dcreg_places_count.argtypes = [vp]
+        L.dcreg_places_add.argtypes = [vp, C.c_int64, fp]
+        for name in ("dcreg_places_add_clouds", "dcreg_places_add_clouds_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64, pi]
+        L.dcreg_places_add_source.argtypes = [vp, pi]
+        L.dcreg_places_get.argtypes = [vp, C.c_int64, C.c_int64, fp]
+        L.dcreg_places_query.argtypes = [vp, C.c_int, fp] + res
+        for name in ("dcreg_places_query_clouds", "dcreg_places_query_clouds_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64] + res + [pi]
+        L.dcreg_places_query_source.argtypes = [vp] + res + [pi]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -975,6 +1079,159 @@ class Context:
                                                                 _dp(P), block, C.byref(p) if p is not None else None, C.byref(info),
                                                                 C.byref(vinfo)), "dcreg_set_source_deskew_path_device")
         return _deskew_info_dict(info), (_voxel_info_dict(vinfo) if p is not None else None)
+
+    # ---- place recognition (include/dcreg.h has the rules)
+    def place_descriptors(self, clouds, params=None):
+        """dcreg_place_descriptors: the Scan Context descriptor of every cloud (clouds as voxel_downsample takes them); the database is
+        not touched.  -> ([n, n_rings, n_sectors] float32, dict n_in / n_finite / n_used)"""
+        p = params if params is not None else place_params()
+        _check_place_params(p, "place_descriptors")
+        xyz, off, _ = _clouds(clouds, "place_descriptors")
+        n = len(off) - 1
+        out = np.zeros((n, p.n_rings, p.n_sectors), np.float32)
+        info = PlaceInfo()
+        self._check(self._L.dcreg_place_descriptors(self._h, n, xyz.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1], C.byref(p),
+                                                    out.ctypes.data, C.byref(info)), "dcreg_place_descriptors")
+        return out, _place_info_dict(info)
+
+    def place_descriptors_device(self, dev_ptr, offsets, stride, dev_out_ptr, params=None):
+        """dcreg_place_descriptors_device: clouds in device memory (dev_ptr, stride floats per point, offsets on the host), the descriptors
+        to the device buffer dev_out_ptr (n * n_rings * n_sectors floats) -> info dict"""
+        p = params if params is not None else place_params()
+        _check_place_params(p, "place_descriptors_device")
+        off = _offsets(offsets, "place_descriptors_device")
+        if int(stride) < 3:
+            raise ValueError("place_descriptors_device: a stride of at least 3 floats is expected, got %d" % int(stride))
+        info = PlaceInfo()
+        self._check(self._L.dcreg_place_descriptors_device(self._h, len(off) - 1, C.c_void_p(dev_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           int(stride), C.byref(p), C.c_void_p(dev_out_ptr), C.byref(info)),
+                    "dcreg_place_descriptors_device")
+        return _place_info_dict(info)
+
+    def places_reset(self, params=None):
+        """dcreg_places_reset: an empty place database with these parameters (place_params(...); the defaults when None)"""
+        p = params if params is not None else place_params()
+        _check_place_params(p, "places_reset")
+        self._check(self._L.dcreg_places_reset(self._h, C.byref(p)), "dcreg_places_reset")
+        self._place_shape = (p.n_rings, p.n_sectors)
+
+    def _places_shape(self, what):
+        shape = getattr(self, "_place_shape", None)
+        if shape is None:
+            raise ValueError("%s: no place database (places_reset first)" % what)
+        return shape
+
+    def places_count(self):
+        return int(self._L.dcreg_places_count(self._h))
+
+    def places_add(self, desc):
+        """dcreg_places_add: host descriptors ([n, n_rings, n_sectors] or [n, n_rings * n_sectors], finite) appended -> index of the first"""
+        R, S = self._places_shape("places_add")
+        d = _descriptors(desc, R * S, "places_add")
+        at = self.places_count()
+        self._check(self._L.dcreg_places_add(self._h, d.shape[0], d.ctypes.data_as(C.POINTER(C.c_float))), "dcreg_places_add")
+        return at
+
+    def places_add_clouds(self, clouds):
+        """dcreg_places_add_clouds: the descriptors of the clouds computed and appended on the device -> (index of the first, info dict)"""
+        self._places_shape("places_add_clouds")
+        xyz, off, _ = _clouds(clouds, "places_add_clouds")
+        info = PlaceInfo()
+        at = self.places_count()
+        self._check(self._L.dcreg_places_add_clouds(self._h, len(off) - 1, xyz.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
+                                                    C.byref(info)), "dcreg_places_add_clouds")
+        return at, _place_info_dict(info)
+
+    def places_add_clouds_device(self, dev_ptr, offsets, stride):
+        self._places_shape("places_add_clouds_device")
+        off = _offsets(offsets, "places_add_clouds_device")
+        if int(stride) < 3:
+            raise ValueError("places_add_clouds_device: a stride of at least 3 floats is expected, got %d" % int(stride))
+        info = PlaceInfo()
+        at = self.places_count()
+        self._check(self._L.dcreg_places_add_clouds_device(self._h, len(off) - 1, C.c_void_p(dev_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           int(stride), C.byref(info)), "dcreg_places_add_clouds_device")
+        return at, _place_info_dict(info)
+
+    def places_add_source(self):
+        """dcreg_places_add_source: the descriptor of the current source appended -> (its index, info dict)"""
+        self._places_shape("places_add_source")
+        info = PlaceInfo()
+        at = self.places_count()
+        self._check(self._L.dcreg_places_add_source(self._h, C.byref(info)), "dcreg_places_add_source")
+        return at, _place_info_dict(info)
+
+    def places_get(self, first=0, n=None):
+        """dcreg_places_get: entries [first, first + n) (to the end when n is None) -> [n, n_rings, n_sectors] float32"""
+        R, S = self._places_shape("places_get")
+        if int(first) < 0 or (n is not None and int(n) < 0):
+            raise ValueError("places_get: first >= 0 and n >= 0 are expected, got %d and %s" % (int(first), n))
+        if n is None:
+            n = max(self.places_count() - int(first), 0)
+        out = np.zeros((int(n), R, S), np.float32)
+        self._check(self._L.dcreg_places_get(self._h, int(first), int(n), out.ctypes.data_as(C.POINTER(C.c_float))), "dcreg_places_get")
+        return out
+
+    def _place_results(self, n, k):
+        return np.full((n, k), -1, np.int32), np.zeros((n, k), np.int32), np.full((n, k), np.inf, np.float64)
+
+    def _place_range(self, first, last, k, what):
+        if last is None:
+            last = self.places_count()
+        _check_range(first, last, k, what)
+        return int(first), int(last), int(k)
+
+    def places_query(self, desc, k=1, first=0, last=None):
+        """dcreg_places_query: for every host descriptor the k entries of [first, last) (to the end when last is None) with the smallest
+        distance, ordered by (distance, index) -> (idx [n, k] int32, shift [n, k] int32, dist [n, k] float64); unused slots -1, 0, inf"""
+        R, S = self._places_shape("places_query")
+        d = _descriptors(desc, R * S, "places_query")
+        first, last, k = self._place_range(first, last, k, "places_query")
+        idx, shift, dist = self._place_results(d.shape[0], k)
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.dcreg_places_query(self._h, d.shape[0], d.ctypes.data_as(C.POINTER(C.c_float)), first, last, k, idx.ctypes.data_as(ip),
+                                               shift.ctypes.data_as(ip), _dp(dist)), "dcreg_places_query")
+        return idx, shift, dist
+
+    def places_query_clouds(self, clouds, k=1, first=0, last=None):
+        """dcreg_places_query_clouds: one query per cloud, its descriptor computed on the device -> (idx, shift, dist, info dict)"""
+        self._places_shape("places_query_clouds")
+        xyz, off, _ = _clouds(clouds, "places_query_clouds")
+        first, last, k = self._place_range(first, last, k, "places_query_clouds")
+        n = len(off) - 1
+        idx, shift, dist = self._place_results(n, k)
+        info = PlaceInfo()
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.dcreg_places_query_clouds(self._h, n, xyz.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1], first, last,
+                                                      k, idx.ctypes.data_as(ip), shift.ctypes.data_as(ip), _dp(dist), C.byref(info)),
+                    "dcreg_places_query_clouds")
+        return idx, shift, dist, _place_info_dict(info)
+
+    def places_query_clouds_device(self, dev_ptr, offsets, stride, k=1, first=0, last=None):
+        self._places_shape("places_query_clouds_device")
+        off = _offsets(offsets, "places_query_clouds_device")
+        if int(stride) < 3:
+            raise ValueError("places_query_clouds_device: a stride of at least 3 floats is expected, got %d" % int(stride))
+        first, last, k = self._place_range(first, last, k, "places_query_clouds_device")
+        n = len(off) - 1
+        idx, shift, dist = self._place_results(n, k)
+        info = PlaceInfo()
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.dcreg_places_query_clouds_device(self._h, n, C.c_void_p(dev_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)), int(stride),
+                                                             first, last, k, idx.ctypes.data_as(ip), shift.ctypes.data_as(ip), _dp(dist),
+                                                             C.byref(info)), "dcreg_places_query_clouds_device")
+        return idx, shift, dist, _place_info_dict(info)
+
+    def places_query_source(self, k=1, first=0, last=None):
+        """dcreg_places_query_source: the current source as the one query -> (idx [k], shift [k], dist [k], info dict)"""
+        self._places_shape("places_query_source")
+        first, last, k = self._place_range(first, last, k, "places_query_source")
+        idx, shift, dist = self._place_results(1, k)
+        info = PlaceInfo()
+        ip = C.POINTER(C.c_int32)
+        self._check(self._L.dcreg_places_query_source(self._h, first, last, k, idx.ctypes.data_as(ip), shift.ctypes.data_as(ip), _dp(dist),
+                                                      C.byref(info)), "dcreg_places_query_source")
+        return idx[0], shift[0], dist[0], _place_info_dict(info)
 
     def index_info(self):
         info = IndexInfo()

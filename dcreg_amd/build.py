@@ -22,6 +22,7 @@ SOURCES = [
     "device/exchange.hip",
     "device/voxel.hip",
     "device/deskew.hip",
+    "device/places.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

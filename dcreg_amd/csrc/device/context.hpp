@@ -312,6 +312,29 @@ struct dcreg_ctx {
         DevBuf<dcreg::PathSeg> segs;
     };
     DeskewBufs dsk;
+    // place recognition (places.hip: dcreg_place_descriptors*, dcreg_places_*).  The database: `count` descriptors of p.n_rings x p.n_sectors
+    // floats (ring-major) and per column the inverse of its norm (0: a zero column); it lives until dcreg_places_reset or the context's end,
+    // whatever happens to the target and the source.  The rest is scratch of one call: per (cloud, bin) the key of its maximum, the cloud
+    // offsets, the call's counts; the query descriptors and their inverse norms; per (query, entry of the range) distance and shift; the
+    // candidate lists of the selection (two sides, used in turn) and the shifts of the result
+    struct PlaceBufs {
+        bool ready = false;                                  // dcreg_places_reset has fixed p
+        dcreg_place_params p{};
+        int64_t count = 0;
+        DevBuf<float> desc;
+        DevBuf<double> inv;
+        DevBuf<uint32_t> keys;
+        DevBuf<int64_t> d_off;
+        DevBuf<unsigned long long> cnt;
+        DevBuf<float> qdesc;
+        DevBuf<double> qinv;
+        DevBuf<double> dist;
+        DevBuf<int32_t> shift;
+        DevBuf<double> sel_d[2];
+        DevBuf<int32_t> sel_i[2];
+        DevBuf<int32_t> sel_shift;
+    };
+    PlaceBufs places;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)

@@ -737,6 +737,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_sweep_motion")) return sizeof(dcreg_sweep_motion);
     if (!std::strcmp(name, "dcreg_deskew_info")) return sizeof(dcreg_deskew_info);
     if (!std::strcmp(name, "dcreg_sweep_path")) return sizeof(dcreg_sweep_path);
+    if (!std::strcmp(name, "dcreg_place_params")) return sizeof(dcreg_place_params);
+    if (!std::strcmp(name, "dcreg_place_info")) return sizeof(dcreg_place_info);
     return 0;
 }
 

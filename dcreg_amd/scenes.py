@@ -309,6 +309,24 @@ def drive(world, n_keyframes, step=1.5, n_frame=8_000, seed=0, start=None, headi
     return poses, frames
 
 
+def revisits(world, poses, n_revisits, max_offset=1.5, n_frame=8_000, seed=0, frame_range=30.0, noise=0.02):
+    """Revisits of a drive for place recognition: n_revisits sweeps taken later near keyframes drawn without replacement from `poses`, each up
+    to max_offset metres off its keyframe's position (uniform over the disc) and at a random yaw, cut from `world` by map_frames.
+    -> (the keyframe each revisit is near [n] ascending, the revisits' sensor poses, their frames)"""
+    rng = np.random.default_rng(seed)
+    near = np.sort(rng.choice(len(poses), n_revisits, replace=False))
+    out = []
+    for kf in near:
+        r, a = max_offset * np.sqrt(rng.uniform()), rng.uniform(0.0, 2 * np.pi)
+        yaw = rng.uniform(0.0, 2 * np.pi)
+        T = np.array(poses[kf], np.float64)
+        T[:3, 3] += [r * np.cos(a), r * np.sin(a), 0.0]
+        Rz = np.eye(4)
+        Rz[:2, :2] = [[np.cos(yaw), -np.sin(yaw)], [np.sin(yaw), np.cos(yaw)]]
+        out.append(T @ Rz)
+    return near, out, map_frames(world, out, n_frame, seed=seed + 100, frame_range=frame_range, noise=noise)
+
+
 def scan_pairs(tgt, poses, n_frame=8_000, seed=0, mode="submap", n_submap=100_000, submap_radius=40.0, frame_range=30.0, noise=0.02):
     """Scan pairs cut out of an existing map at sensor poses (4x4, sensor -> map), sources made by map_frames.  mode "submap": pair k = the
     frame at poses[k] against a submap crop - up to n_submap map points within submap_radius metres (in x-y) of poses[k]'s position, in

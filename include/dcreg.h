@@ -449,6 +449,87 @@ int dcreg_set_source_deskew_path_device(dcreg_ctx *, const float *d_xyz, int64_t
                                         int64_t n_knots, const double *knot_stamps, const double *knot_poses, const dcreg_sweep_path *path,
                                         const dcreg_voxel_params *voxel, dcreg_deskew_info *info, dcreg_voxel_info *vinfo);
 
+/* ---------------- place recognition: Scan Context descriptors, a database of them, exhaustive search ----------------
+ * dcreg_register_frames and dcreg_register_pairs verify loop-closure and relocalisation candidates; these calls produce them.  A sweep gets a
+ * Scan Context descriptor (Kim & Kim, IROS 2018: the maximum height per polar bin) on the device, descriptors are kept in a database that
+ * lives in the context, and a query is compared with every entry of an index range at every column shift.
+ * Descriptor of one cloud: n_rings x n_sectors floats, ring-major (d[ring * n_sectors + sector]).
+ *   - a point is used when x, y and z are finite and min_range^2 <= rho2 < max_range^2 with rho2 = x^2 + y^2 in double (the squares are
+ *     exact: one rounding);
+ *   - ring coordinate a = sqrt(rho2) * n_rings / max_range, ring = min(floor(a), n_rings - 1);
+ *   - theta = atan2(y, x), plus 2 pi when negative; sector coordinate b = theta * n_sectors / (2 pi), sector = min(floor(b), n_sectors - 1);
+ *   - a bin's value is the maximum over its points of (float)((double)z + z_offset); an empty bin holds 0;
+ *   - a point whose a or b lies within 1e-9 of an integer may fall in either neighbouring bin (sqrt and atan2 differ between libraries in
+ *     their last bits); every other point falls in the bin the formulas give.
+ * The maximum is taken with integer atomics on order-preserving keys, so a descriptor does not depend on the order of the points, on the
+ * launch configuration, or on the other clouds of the call.
+ * Distance of a query descriptor q and an entry c at shift n in [0, n_sectors), everything in double: over the columns j for which both
+ * q's column j and c's column (j + n) mod n_sectors have a non-zero norm (m of them), D_n = (1/m) sum_j (1 - q_j . c_(j+n) / (|q_j| |c_(j+n)|));
+ * D_n = 1 when m = 0.  The distance of the pair is min_n D_n and its shift the smallest n that attains it.  The sums run in a fixed
+ * order: results are bitwise repeatable.
+ * Geometry: a query taken at the entry's position with its sensor frame yawed by +psi has its best shift at psi * n_sectors / (2 pi).  The
+ * start pose for registering the query (source) against the entry's cloud (target) is therefore R0 = Rz(2 pi * shift / n_sectors), t0 = 0,
+ * good to half a sector: what dcreg_register_pairs takes.
+ * Search: for each query the k entries (k in [1, 64]) of the index range [first, last) with the smallest distance, ordered by (distance,
+ * index): idx[q k + s] (int32), shift[q k + s] (int32), dist[q k + s] (double).  Slots beyond the range's size hold index -1, shift 0 and
+ * distance +inf.  The range is how a mapping loop leaves out its most recent keyframes.  The result for a (query, entry) pair depends on
+ * those two descriptors only: not on the number of queries, the range, k, or the database's size.  There is no ring-key or tree
+ * prefilter: every entry of the range is compared (DESIGN.md says why).
+ * The database is created by dcreg_places_reset, which fixes its parameters, and freed by dcreg_backend_destroy.  It needs no target, and
+ * it is not dropped by dcreg_set_target, dcreg_set_source, the map updates or the registration calls: a map and its places live side by
+ * side.  None of these calls changes the target, the source, neighbour states, loaded frames or the window index.
+ * DCREG_E_INVALID: n_rings outside [1, 64], n_sectors outside [1, 128], a max_range that is not finite and > 0, a min_range that is not
+ * finite, is below 0 or is not below max_range, a z_offset that is not finite; the cloud refusals of dcreg_voxel_downsample (offsets,
+ * stride, 2^31 - 1 points); first > last or a range outside [0, count]; k outside [1, 64]; a host descriptor with a value that is not
+ * finite; null buffers.  DCREG_E_STATE: a linearisation in flight; add, get or query before dcreg_places_reset; a _source form without a
+ * source.  A refused call and a failed allocation (DCREG_E_NOMEM) leave the database as it was.  All calls wait for the stream.
+ * Device memory: 4 B per bin and 8 B per column of every entry, and scratch of 12 B per (query, entry) pair of a query batch (at most 2^24
+ * pairs at once). */
+typedef struct dcreg_place_params {
+    int n_rings;         /* radial bins, 1 .. 64 */
+    int n_sectors;       /* azimuthal bins, 1 .. 128 */
+    double max_range;    /* points at this horizontal distance or beyond are not used (m) */
+    double min_range;    /* points nearer than this are not used (m) */
+    double z_offset;     /* added to z: heights must come out positive for an occupied bin to differ from an empty one (the sensor height) */
+} dcreg_place_params;
+typedef struct dcreg_place_info {    /* summed over the clouds of the call */
+    int64_t n_in;        /* points passed in */
+    int64_t n_finite;    /* ... with three finite coordinates */
+    int64_t n_used;      /* ... of those, inside the range gate */
+} dcreg_place_info;
+/* 20 rings, 60 sectors, max_range 80, min_range 0, z_offset 2 */
+int dcreg_default_place_params(dcreg_place_params *);
+/* The descriptors of many clouds (offsets as dcreg_voxel_downsample) to desc_out[n_clouds * n_rings * n_sectors], host memory; the database is
+ * not touched and need not exist.  info may be NULL.  _device: d_xyz as dcreg_voxel_downsample_device reads it, d_desc_out device memory. */
+int dcreg_place_descriptors(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_place_params *,
+                            float *desc_out, dcreg_place_info *info);
+int dcreg_place_descriptors_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                   const dcreg_place_params *, float *d_desc_out, dcreg_place_info *info);
+/* empties the database and fixes its parameters */
+int dcreg_places_reset(dcreg_ctx *, const dcreg_place_params *);
+/* entries in the database (0 before dcreg_places_reset) */
+int64_t dcreg_places_count(const dcreg_ctx *);
+/* appends n host descriptors (what dcreg_places_get or dcreg_place_descriptors returned); they receive the indices count, count + 1, .. */
+int dcreg_places_add(dcreg_ctx *, int64_t n, const float *desc);
+/* computes the descriptors of the call's clouds with the database's parameters and appends them on the device (no host round trip) */
+int dcreg_places_add_clouds(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, dcreg_place_info *info);
+int dcreg_places_add_clouds_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                   dcreg_place_info *info);
+/* ... of the context's current source, in its input order (the copy dcreg_target_insert_source reads) */
+int dcreg_places_add_source(dcreg_ctx *, dcreg_place_info *info);
+/* entries [first, first + n) to desc_out (host): persistence for a caller */
+int dcreg_places_get(dcreg_ctx *, int64_t first, int64_t n, float *desc_out);
+/* n_queries host descriptors against the entries [first, last): idx, shift and dist hold n_queries * k results each (host memory) */
+int dcreg_places_query(dcreg_ctx *, int n_queries, const float *desc, int64_t first, int64_t last, int k, int32_t *idx, int32_t *shift,
+                       double *dist);
+/* ... with the descriptors of the call's clouds (one query per cloud), computed with the database's parameters; info may be NULL */
+int dcreg_places_query_clouds(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, int64_t first,
+                              int64_t last, int k, int32_t *idx, int32_t *shift, double *dist, dcreg_place_info *info);
+int dcreg_places_query_clouds_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats, int64_t first,
+                                     int64_t last, int k, int32_t *idx, int32_t *shift, double *dist, dcreg_place_info *info);
+/* ... with the descriptor of the context's current source (one query) */
+int dcreg_places_query_source(dcreg_ctx *, int64_t first, int64_t last, int k, int32_t *idx, int32_t *shift, double *dist, dcreg_place_info *info);
+
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
 typedef struct dcreg_config {
