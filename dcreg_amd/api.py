@@ -136,7 +136,7 @@ EXPORTS = [
     "dcreg_default_lin_params", "dcreg_linearize", "dcreg_linearize_batch", "dcreg_linearize_batch_begin",
     "dcreg_linearize_batch_end", "dcreg_linearize_batch_begin_warm", "dcreg_reserve_warm_states", "dcreg_reset_warm_state", "dcreg_hint_misalignment", "dcreg_linearize_debug", "dcreg_launch_stats_get", "dcreg_knn", "dcreg_kdtree_build", "dcreg_kdtree_info", "dcreg_knn_timed",
     "dcreg_linearize_gated_begin", "dcreg_linearize_gate_open", "dcreg_linearize_gate_abort",
-    "dcreg_index_info_get", "dcreg_kernel_time", "dcreg_launch_series", "dcreg_launch_series_passes", "dcreg_team_pass_stamps", "dcreg_roi_info", "dcreg_default_config", "dcreg_analyze_degeneracy", "dcreg_analyze_degeneracy_two_part",
+    "dcreg_index_info_get", "dcreg_kernel_time", "dcreg_launch_series", "dcreg_launch_series_passes", "dcreg_launch_series_structure", "dcreg_team_pass_stamps", "dcreg_roi_info", "dcreg_default_config", "dcreg_analyze_degeneracy", "dcreg_analyze_degeneracy_two_part",
     "dcreg_solve_degenerate_system", "dcreg_unpack_hessian", "dcreg_boxplus", "dcreg_pose6d_to_matrix",
     "dcreg_pose_error", "dcreg_icp_run", "dcreg_icp_run_sharded", "dcreg_icp_run_many", "dcreg_icp_run_euler", "dcreg_icp_run_trials", "dcreg_icp_run_montecarlo", "dcreg_p2p_error", "dcreg_sizeof", "dcreg_version", "dcreg_trial_pose",
     "dcreg_set_host_threads", "dcreg_get_host_threads", "dcreg_comm_unique_id", "dcreg_comm_init", "dcreg_comm_destroy", "dcreg_comm_allgather_sum", "dcreg_icp_run_sharded_rccl",
@@ -595,6 +595,8 @@ def load():
     L.dcreg_launch_series.argtypes = [vp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_int]
     if hasattr(L, "dcreg_launch_series_passes"):        # (absent from an older build loaded through DCREG_LIB for an A/B: scripts/ab_multi.sh)
         L.dcreg_launch_series_passes.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64]
+    if hasattr(L, "dcreg_launch_series_structure"):
+        L.dcreg_launch_series_structure.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64]
     if hasattr(L, "dcreg_team_pass_stamps"):
         L.dcreg_team_pass_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64]
     L.dcreg_default_config.restype = None
@@ -1372,8 +1374,9 @@ class Context:
 
     def launch_series(self, reset=True, cap=1 << 20):
         """dcreg_launch_series (dcreg_debug.h; option "record_launches"): per completed launch its HIP-event time (ms, -1 = untimed),
-        points searched, points refitted and points linearised, which pass ran in front (dcreg_launch_series_passes: 0 / 1 / 2) and
-        whether the linearisation kernel ran in one-wave blocks -> dict of arrays"""
+        points searched, points refitted and points linearised, which pass ran in front (dcreg_launch_series_passes: 0 / 1 / 2),
+        whether the linearisation kernel ran in one-wave blocks and which kernels carried the launch out (dcreg_launch_series_structure:
+        0 the linearisation kernel alone, 1 a pass and the kernel behind it, 2 the advance pass alone) -> dict of arrays"""
         lp = C.POINTER(C.c_int64)
         n = self._L.dcreg_launch_series(self._h, None, None, None, None, 0, 0)
         if n < 0:
@@ -1384,8 +1387,11 @@ class Context:
         adv = np.zeros(n, np.uint8)
         if hasattr(self._L, "dcreg_launch_series_passes"):
             self._L.dcreg_launch_series_passes(self._h, adv.ctypes.data_as(C.POINTER(C.c_uint8)), n)
+        st = np.where((adv & 3) != 0, 1, 0).astype(np.uint8)      # (a build without the getter has the two-kernel form only)
+        if hasattr(self._L, "dcreg_launch_series_structure"):
+            self._L.dcreg_launch_series_structure(self._h, st.ctypes.data_as(C.POINTER(C.c_uint8)), n)
         self._L.dcreg_launch_series(self._h, _dp(ms), se.ctypes.data_as(lp), rf.ctypes.data_as(lp), pt.ctypes.data_as(lp), n, int(reset))
-        return {"ms": ms, "searched": se, "refitted": rf, "points": pt, "advanced": adv & 3, "one_wave": (adv >> 2) & 1}
+        return {"ms": ms, "searched": se, "refitted": rf, "points": pt, "advanced": adv & 3, "one_wave": (adv >> 2) & 1, "structure": st}
 
     def team_pass_stamps(self):
         """dcreg_team_pass_stamps (option "team_stamps"): [n_blocks, 8] shader-clock words of the last launch that ran the small-frame pass"""

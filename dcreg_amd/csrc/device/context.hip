@@ -1561,9 +1561,10 @@ static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
     // The advance pass (kernels.hpp k_advance) in front of this launch?  Only where it can pay: a single pose on the ctx's own state,
     // certificates in use, the state filled by an earlier launch; by default ("advance" = 1) a cloud whose query blocks exceed what the
     // device holds at once (below that a launch lasts as long as one search whether its searches are dense or not) in a launch expected
-    // to search a few per cent of its points.  Scheduling only: the sums are the same with and without the pass.
+    // to search between 0.5 % and 70 % of its points (profiles/fused_pass_ablation.md section 3: the window in which the pass that builds
+    // the rows itself beats k_lin alone by 6 us and more).  Scheduling only: the sums are the same with and without the pass.
     if ((L.kind == LinKind::single || L.kind == LinKind::gated) && c->opt_warm && !fresh && P.use_cert && L.a.count_scale != 0.0) {
-        constexpr double kAdvanceLo = 0.01, kAdvanceHi = 0.45;
+        constexpr double kAdvanceLo = 0.005, kAdvanceHi = 0.70;
         const bool adv = c->opt_advance >= 2 || (c->opt_advance == 1 && P.nbx >= (uint32_t)c->opt_advance_min_blocks && known && f >= kAdvanceLo && f <= kAdvanceHi);
         // ... its small-frame form (k_advance_team: sixteen lanes per query, one wave per kTeamTile points): a frame of a few thousand
         // points, whose query blocks leave most of the device idle, in a launch expected to search most of its points (the pass costs
@@ -1600,6 +1601,9 @@ static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
     // the k_lin instantiation: a gated k_lin runs in four-wave blocks whatever the one-wave rule says
     P.body = (P.gate_inside && P.pass != LinPass::team) ? LinBody::gated : L.kind == LinKind::stamps ? LinBody::stamps : L.kind == LinKind::dump ? LinBody::dump :
              one_wave ? LinBody::one_wave : fused ? LinBody::fused : LinBody::chunked;
+    // the pass carries the launch out alone (kernels.hpp k_advance ROWS: the rows of a tile by the block that worked its list off, no k_lin
+    // behind it) wherever k_lin would run as the plain fused kernel behind it; direct launches keep the two kernels (option "advance_fused")
+    P.pass_rows = P.pass == LinPass::advance && c->opt_advance_fused != 0 && !P.direct && P.body == LinBody::fused;
     return P;
 }
 
@@ -1690,7 +1694,7 @@ static int lin_reserve(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P)
         L.d_poses = c->d_gate_pose.data();
     }
     if (int rc = L.own() ? DCREG_OK : stage_poses(c, S, L)) return rc;
-    if (P.pass != LinPass::none) {      // the passes' counts, per query block of k_lin: zero between launches (k_lin takes them and zeroes them again)
+    if (P.pass != LinPass::none && !P.pass_rows) {      // the passes' counts, per query block of k_lin: zero between launches (k_lin takes them and zeroes them again)
         const size_t had = c->d_adv_counts.cap();
         if (c->d_adv_counts.ensure(c, (size_t)kCounterStride * P.nbx)) return DCREG_E_NOMEM;      // (a 128-byte line per query block)
         if (c->d_adv_counts.cap() != had || c->adv_counts_dirty) {
@@ -1748,7 +1752,8 @@ static LinKernel lin_kernel(const LinPlan &P) {
     return P.fused() ? k_lin<0, true, FAST, false, false, SLICE, GRIDS> : k_lin<0, false, FAST, false, false, SLICE, GRIDS>;
 }
 
-// Queue: gate, start event, pass, k_lin (k_sum_tiles behind one-wave blocks), k_finalize, end event, dump readback
+// Queue: gate, start event, pass, k_lin (k_sum_tiles behind one-wave blocks; none behind a pass that builds the rows itself), k_finalize,
+// end event, dump readback
 template <bool FAST>
 static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
     const bool gated = L.kind == LinKind::gated, team = P.pass == LinPass::team, slice = L.kind == LinKind::frames || L.kind == LinKind::pairs;
@@ -1784,9 +1789,11 @@ static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
         }
     }
     if (int rc = record(S.ev0)) return rc;         // after the gate: the events bracket the linearisation, not the wait for the pose
-    if (P.pass == LinPass::advance)
-        hipLaunchKernelGGL(k_advance<FAST>, dim3(blocks_for(L.n, kAdvTile)), dim3(kLinBlock), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, L.d_poses, L.a,
-                           c->d_adv_counts.data(), abort_flag);
+    if (P.pass == LinPass::advance) {          // (pass_rows: the launch's only linearisation kernel - rows, tickets and chunk rows are its own)
+        const auto pass = P.pass_rows ? k_advance<FAST, true> : k_advance<FAST, false>;
+        hipLaunchKernelGGL(pass, dim3(blocks_for(L.n, kAdvTile)), dim3(kLinBlock), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, L.d_poses, L.a,
+                           P.pass_rows ? nullptr : c->d_adv_counts.data(), abort_flag, S.d_partials.data(), P.nbx, fin);
+    }
     if (team) {      // with the gate inside, the teams are the gated kernel
         const auto pass = P.gate_inside ? k_advance_team<FAST, true> : k_advance_team<FAST>;
         hipLaunchKernelGGL(pass, dim3(blocks_for(L.n, kTeamTile)), dim3(kWave), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, P.gate_inside ? nullptr : L.d_poses,
@@ -1797,6 +1804,7 @@ static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
         c->n_advance_launches += 1;
     }
     const bool one = P.one_wave(); const auto lin = lin_kernel<FAST>(P);      // (one-wave blocks: a grid of tiles)
+    if (!P.pass_rows)
     hipLaunchKernelGGL(lin, dim3(one ? P.nbx * (kLinBlock / kWave) : P.nbx, (unsigned)P.n_poses), dim3(one ? kWave : kLinBlock), 0, c->stream,
                        slice ? L.fs->src.data() : c->d_src.data(), n, c->map.grid, L.one, lin_poses, L.a, S.d_partials.data(), P.nbx, fin, L.dd, abort_flag, gt,
                        L.d_slices, L.kind == LinKind::pairs ? c->pairs.d_grids.data() : nullptr, L.d_grid_ids);
@@ -2037,7 +2045,7 @@ static int linearize_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     if (refitted > c->last_points) refitted = c->last_points;
     c->last_searched = searched; c->last_refitted = refitted;
     if (c->opt_record_launches && c->launch_series.size() < ((size_t)1 << 20))
-        c->launch_series.push_back(dcreg_ctx::LaunchRec{(double)launch_ms, searched, refitted, c->last_points, P.passes()});
+        c->launch_series.push_back(dcreg_ctx::LaunchRec{(double)launch_ms, searched, refitted, c->last_points, P.passes(), P.structure()});
     return DCREG_OK;
 }
 
@@ -2209,6 +2217,7 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "pairs_max_bytes") c->opt_pairs_max_bytes = std::max(v, 0.0);     // device bytes of one build batch of dcreg_register_pairs (0: a quarter of the free memory)
     else if (k == "max_table_entries") c->opt_max_table_entries = (int64_t)std::min(std::max(v, 1048576.0), 2147483648.0);   // next dcreg_set_target
     else if (k == "advance") c->opt_advance = (int)v;            // the advance pass in front of single-pose launches: 0 never, 1 (default) by the host's rule, 2 whenever possible
+    else if (k == "advance_fused") c->opt_advance_fused = (int)v;   // ... carried out by one kernel (1, default: the pass builds the rows itself) or by k_advance + k_lin (0)
     else if (k == "one_wave") c->opt_one_wave = (int)v;                  // k_lin in one-wave blocks: 0 never, 1 by the rule (launches of many blocks in which most waves search), 2 wherever possible
     else if (k == "one_wave_batches") c->opt_one_wave_batches = v != 0.0;
     else if (k == "one_wave_min_frac") c->opt_one_wave_min_frac = v;
@@ -2574,6 +2583,13 @@ int dcreg_launch_series_passes(dcreg_ctx *c, uint8_t *advanced, int64_t cap) {
     if (!c || cap < 0) return -1;
     const int64_t n = std::min<int64_t>(cap, (int64_t)c->launch_series.size());
     for (int64_t i = 0; i < n; ++i) if (advanced) advanced[i] = (uint8_t)c->launch_series[(size_t)i].advanced;
+    return (int)std::min<int64_t>((int64_t)c->launch_series.size(), 0x7FFFFFFF);
+}
+
+int dcreg_launch_series_structure(dcreg_ctx *c, uint8_t *structure, int64_t cap) {
+    if (!c || cap < 0) return -1;
+    const int64_t n = std::min<int64_t>(cap, (int64_t)c->launch_series.size());
+    for (int64_t i = 0; i < n; ++i) if (structure) structure[i] = (uint8_t)c->launch_series[(size_t)i].structure;
     return (int)std::min<int64_t>((int64_t)c->launch_series.size(), 0x7FFFFFFF);
 }
 

@@ -135,10 +135,12 @@ struct LinPlan {
     size_t n_rows = 0;                 // result rows the host waits for
     bool direct = false;               // the rows are block rows of one chunk (kernels.hpp FinArgs::direct)
     bool gate_inside = false;          // the gated launch waits for its pose in its first kernel (kernels.hpp gate_wait)
+    bool pass_rows = false;            // the advance pass builds the rows and finishes the launch itself: no k_lin behind it (k_advance ROWS)
     bool ordered = false, use_cert = true;   // heavy query-block groups first (LinArgs::n_groups); certificates in use (LinArgs::use_cert)
     bool fused() const { return body != LinBody::chunked; }     // the kernels sum and publish per pose (no k_finalize)
     bool one_wave() const { return body == LinBody::one_wave; }
     int passes() const { return (int)pass | (one_wave() ? 4 : 0); }   // dcreg_launch_series_passes: + 4 = k_lin ran in one-wave blocks
+    int structure() const { return pass_rows ? 2 : pass != LinPass::none ? 1 : 0; }   // dcreg_launch_series_structure
 };
 
 // buffers and in-flight state of one linearisation slot
@@ -423,6 +425,7 @@ struct dcreg_ctx {
     // the advance pass (kernels.hpp k_advance) and its small-frame form (k_advance_team): 0 never, 1 by the rules of context.hip lin_plan,
     // 2 whenever a launch can take it (tests)
     int opt_advance = 1;
+    int opt_advance_fused = 1;           // the advance pass carries its launch out alone (kernels.hpp k_advance ROWS); 0: k_advance + k_lin
     int opt_advance_min_blocks = 2048;   // k_advance by the rule: the cloud has at least this many query blocks (twice what the device holds)
     int opt_team_pass = 1;
     bool opt_team_stamps = false;
@@ -437,7 +440,7 @@ struct dcreg_ctx {
     // what the last completed launch did (decoded from the count slots of its result rows, search.hpp LinArgs::count_scale): points
     // searched / refitted, -1 = not reported.  Scheduling input of the next launches; "record_launches": every launch is also logged
     int64_t last_searched = -1, last_refitted = -1, last_points = 0;
-    struct LaunchRec { double ms; int64_t searched, refitted, points; int advanced; };
+    struct LaunchRec { double ms; int64_t searched, refitted, points; int advanced, structure; };
     bool opt_record_launches = false;
     std::vector<LaunchRec> launch_series;
 

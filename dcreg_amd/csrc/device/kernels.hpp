@@ -764,16 +764,42 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
 // changes a result (history independence), so the sums are bitwise those of a launch without the pass.  The host decides per launch
 // (context.hip: the fraction of points the last completed launch searched; clouds whose query blocks exceed what the device holds).
 // A point whose new certificate has no slack at all (exact distance ties) is searched again by k_lin - correct, merely slower.
+//
+// ROWS (the product form, option "advance_fused"): the pass carries the whole launch out - no k_lin behind it.  Once a tile's list is worked off, every certificate of the tile
+// holds (the points the tests passed) or was set at this very pose (the points of the list), so what k_lin would do for the tile's
+// kAdvTile / kLinBlock query blocks is its stored-plane path and nothing else.  The block does just that, behind a block barrier (the
+// state one wave wrote is read by another wave of the same CU: workgroup scope, no agent-scope fence): thread t of step u takes point
+// base + u * kLinBlock + t - wave w then holds the 64 points wave w of k_lin's block base / kLinBlock + u holds, in the same lanes -,
+// builds the row from the stored plane (row_of_plane), the wave's Gram matrix by the same matrix-core sequence (wave_rows_to_lds) and
+// the block row ((0 + w0) + w1) + w2) + w3 as block_publish adds it: bitwise k_lin's rows.  (No barrier between the steps: a wave keeps
+// its Gram matrices of all the tile's query blocks in its RunList, and 32 threads per query block add them behind ONE barrier.)  What k_lin's second look at a served point
+// decides and the state does not say - a refit that failed the radius gate leaves the fit word 0, as a valid fit without slack does -
+// travels in a bit per point (nofit).  A point whose new certificate has no slack is NOT searched a second time: its state is this
+// pose's own search, which is what k_lin would find again (history independence).  One tail per tile instead of one per query block:
+// the rows go to the coherence point, one wait, one barrier, then the tile arrives at its chunk's ticket with the number of its query
+// blocks inside that chunk (a tile spans at most two chunks; both arrivals are issued together); the last arrival sums and publishes
+// the chunk as k_lin's last block does.  The tile's searched / refitted counts ride in the count slots of its first query block's row.
+// Not for direct launches (FinArgs::direct); `counts` is unused.
 constexpr int kAdvDepth = 4;                      // trips in flight in the pass's searches (search.hpp knn_search DEPTH); > 2: the kernel takes
                                                   // the registers of two waves per SIMD - its dense waves are few and each a chain of round trips
-template <bool FAST>
+constexpr int kAdvRowsBatch = 6;                  // ROWS: query blocks whose loads are in flight together (14 registers of operands each)
+static_assert((kAdvTile / kLinBlock) % kAdvRowsBatch == 0 && kAdvTile / kLinBlock <= kChunk, "whole batches; a tile spans at most two chunks");
+template <bool FAST, bool ROWS = false>
 static __global__ __launch_bounds__(kLinBlock, (kAdvDepth > 2 ? 2 : kLinOcc)) void k_advance(const float4 *__restrict__ src, uint32_t n_src, GridDev g, PoseArg pose1,
                                                                               const PoseArg *__restrict__ poses, LinArgs a,
-                                                                              uint32_t *__restrict__ counts, const uint32_t *__restrict__ abort_flag) {
+                                                                              uint32_t *__restrict__ counts, const uint32_t *__restrict__ abort_flag,
+                                                                              double *__restrict__ partials, uint32_t n_blocks_x, FinArgs fin) {
     if (abort_flag && *abort_flag != 0u) return;       // a gated launch the host called off
     __shared__ RunList runs[kLinBlock / kWave];
     __shared__ uint16_t list[kAdvTile];              // offsets into the tile: points to search from the front, refit-only points from the back
     __shared__ uint32_t n_list[2];
+    // ROWS: the scratch of the chunk sum; the waves' counts, per query block of the tile (their Gram matrices live in their RunLists,
+    // behind the staging area); the points of the list whose refit failed the radius gate; what the tile's ticket arrivals found
+    __shared__ double red[kLinBlock / 32][kSlots];
+    __shared__ double cnt[ROWS ? kAdvTile / kLinBlock : 1][kLinBlock / kWave][2];
+    static_assert(sizeof(RunList) >= sizeof(double) * (kWave * kRowStride + (kAdvTile / kLinBlock) * 64), "a wave's Gram matrices of a tile live in its RunList");
+    __shared__ uint32_t nofit[kAdvTile / 32];
+    __shared__ int s_role;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     PoseArg P;
     if (poses) P = poses[0]; else P = pose1;
@@ -785,6 +811,7 @@ static __global__ __launch_bounds__(kLinBlock, (kAdvDepth > 2 ? 2 : kLinOcc)) vo
     uint32_t *const SW3 = sbase + kStW3 * ss;
     uint2 *const SY = reinterpret_cast<uint2 *>(sbase + kStY * ss);
     if (threadIdx.x < 2) n_list[threadIdx.x] = 0u;
+    if constexpr (ROWS) { if (threadIdx.x < (uint32_t)(kAdvTile / 32)) nofit[threadIdx.x] = 0u; }
     __syncthreads();
     const uint32_t base = blockIdx.x * (uint32_t)kAdvTile;
     // ---- the tests: every thread takes kAdvTile / kLinBlock points, all their loads in flight together
@@ -827,7 +854,7 @@ static __global__ __launch_bounds__(kLinBlock, (kAdvDepth > 2 ? 2 : kLinOcc)) vo
     __syncthreads();
     const uint32_t n_s = n_list[0], n_r = n_list[1];
     // (reported by the first query block of the tile: LinArgs::adv_counts)
-    if (threadIdx.x == 0 && counts) { counts[(size_t)blockIdx.x * (kAdvTile / kLinBlock) * kCounterStride] = n_s; counts[(size_t)blockIdx.x * (kAdvTile / kLinBlock) * kCounterStride + 1] = n_r; }
+    if (!ROWS && threadIdx.x == 0 && counts) { counts[(size_t)blockIdx.x * (kAdvTile / kLinBlock) * kCounterStride] = n_s; counts[(size_t)blockIdx.x * (kAdvTile / kLinBlock) * kCounterStride + 1] = n_r; }
     if (threadIdx.x == 0 && a.search_count && n_s)            // (option "count_searches": the pass's searches count like k_lin's)
         atomicAdd(a.search_count + (size_t)(blockIdx.x & 63u) * (kCounterStride / 2), (unsigned long long)n_s);
     // ---- the list, 64 entries per wave at a time: the searches (waves in turn), then the refit-only points
@@ -872,7 +899,8 @@ static __global__ __launch_bounds__(kLinBlock, (kAdvDepth > 2 ? 2 : kLinOcc)) vo
             if (set) {
                 KnnResult<5> nn;
                 Fit fit;
-                (void)fit_from_set<FAST>(g, a, qx, qy, qz, pos6, six, nn, fit, searching);     // (searched just now: the six are in order)
+                const uint8_t in_r = fit_from_set<FAST>(g, a, qx, qy, qz, pos6, six, nn, fit, searching);     // (searched just now: the six are in order)
+                if constexpr (ROWS) { if (!in_r) atomicOr(&nofit[off >> 5], 1u << (off & 31u)); }
                 SV0[iw] = make_uint4(cert, fit.word, __float_as_uint(qx), __float_as_uint(qy));
                 SV1[iw] = dbl2{fit.plane[0], fit.plane[1]};
                 SV2[iw] = dbl2{fit.plane[2], fit.plane[3]};
@@ -893,6 +921,93 @@ static __global__ __launch_bounds__(kLinBlock, (kAdvDepth > 2 ? 2 : kLinOcc)) vo
          k += (uint32_t)(kLinBlock / kWave)) {
         const uint32_t e = k * 64u + (uint32_t)lane;
         chunk(std::false_type{}, e, e < n_r);
+    }
+    if constexpr (ROWS) {
+        __syncthreads();                            // the list is worked off: the tile's state is what this pose's linearisation reads
+        const uint32_t vb0 = blockIdx.x * (uint32_t)U;
+        const uint32_t nbt = min((uint32_t)U, n_blocks_x - vb0);      // the tile's query blocks
+#pragma unroll
+        for (int u0 = 0; u0 < U; u0 += kAdvRowsBatch) {
+            if ((uint32_t)u0 >= nbt) break;
+            // (loaded again: nothing of the tests is kept alive across the searches)
+            float4 s4[kAdvRowsBatch];
+            uint2 cf[kAdvRowsBatch];                // certificate, fit word
+            dbl2 p01[kAdvRowsBatch], p23[kAdvRowsBatch];
+#pragma unroll
+            for (int k = 0; k < kAdvRowsBatch; ++k) {
+                const uint32_t i = base + (uint32_t)((u0 + k) * kLinBlock) + threadIdx.x;
+                const bool have = i < n_src;
+                s4[k] = have ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+                cf[k] = have ? *reinterpret_cast<const uint2 *>(SV0 + i) : make_uint2(0x80000000u, kFitNone);      // (padding: OUT)
+                p01[k] = have ? SV1[i] : dbl2{0.0, 0.0};
+                p23[k] = have ? SV2[i] : dbl2{0.0, 0.0};
+            }
+#pragma unroll
+            for (int k = 0; k < kAdvRowsBatch; ++k) {
+                const int u = u0 + k;
+                if ((uint32_t)u >= nbt) break;
+                const uint32_t off = (uint32_t)(u * kLinBlock) + threadIdx.x;
+                float qx, qy, qz;
+                body_to_global(P, (double)s4[k].x, (double)s4[k].y, (double)s4[k].z, qx, qy, qz);
+                // 0: plane usable; 2 / 3: neighbour-only gate failed; 255: radius gate failed / OUT (k_lin's gate)
+                uint8_t gate = 255;
+                if (!cert_is_out(cf[k].x) && ((nofit[off >> 5] >> (off & 31u)) & 1u) == 0u) gate = (uint8_t)(cf[k].y & 3u);
+                double nrm[3] = {0.0, 0.0, 0.0}, r_pt = 0.0, s_pt = 0.0;
+                double row[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) row[e] = 0.0;
+                uint8_t flag = 0;
+                if (base + off < n_src) {
+                    const double plane[4] = {p01[k].x, p01[k].y, p23[k].x, p23[k].y};
+                    if (gate == 0) flag = row_of_plane<FAST>(P, a, s4[k], qx, qy, qz, plane, row, nrm, r_pt, s_pt);
+                    else flag = gate == 255 ? (uint8_t)0 : gate;
+                }
+                const bool first = u == 0 && wave == 0;         // (the tile's counts: with its first query block's first wave)
+                // (no barrier between the steps: every wave keeps its Gram matrix of every query block, the waves run on independently)
+                wave_rows_to_lds(row, flag, runs[wave].stage, runs[wave].stage + kWave * kRowStride + u * 64, cnt[u], first ? a.count_scale * (double)n_s : 0.0,
+                                 first ? a.count_scale * (double)n_r : 0.0);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < nbt * (uint32_t)kSlots) {             // the block rows, as block_publish adds them: 32 threads per query block
+            const uint32_t u = threadIdx.x / (uint32_t)kSlots, slot = threadIdx.x % (uint32_t)kSlots;
+            double t = 0.0;
+            if (slot < 29u) {
+                const int e = gram_entry_of_slot((int)slot);
+#pragma unroll
+                for (int w = 0; w < kLinBlock / 64; ++w) t += (runs[w].stage + kWave * kRowStride)[u * 64u + (uint32_t)e];
+            } else if (slot < 31u) {
+#pragma unroll
+                for (int w = 0; w < kLinBlock / 64; ++w) t += cnt[u][w][slot - 29u];
+            }
+            st_agent(partials + (size_t)(vb0 + u) * kSlots + slot, t);
+            wait_stores();                                      // the tile's rows are at the coherence point before the tickets are taken
+        }
+        __syncthreads();
+        const uint32_t c0 = vb0 / kChunk;
+        const uint32_t k0 = min(nbt, (c0 + 1u) * (uint32_t)kChunk - vb0), k1 = nbt - k0;      // the tile's query blocks in chunk c0 and in c0 + 1
+        const uint32_t cs0 = min((uint32_t)kChunk, n_blocks_x - c0 * kChunk);
+        const uint32_t cs1 = k1 ? min((uint32_t)kChunk, n_blocks_x - (c0 + 1u) * kChunk) : 0u;
+        if (threadIdx.x == 0) {
+            unsigned int *const t0 = fin.tickets + (size_t)c0 * kCounterStride, *const t1 = t0 + kCounterStride;
+            const unsigned int prev0 = __hip_atomic_fetch_add(t0, k0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned int prev1 = 0u;
+            if (k1) prev1 = __hip_atomic_fetch_add(t1, k1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool last0 = prev0 + k0 == cs0, last1 = k1 != 0u && prev1 + k1 == cs1;
+            if (last0) __hip_atomic_store(t0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (last1) __hip_atomic_store(t1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_role = (last0 ? 1 : 0) | (last1 ? 2 : 0);
+        }
+        __syncthreads();
+        const int role = s_role;
+        if (role & 1) {                             // last arrival of a chunk: sum its rows, publish to the host
+            const double t = block_sum_rows(partials + (size_t)c0 * kChunk * kSlots, cs0, red);
+            if (threadIdx.x < 32) publish_row(fin.out + (size_t)c0 * kSlots, t, fin.seq);
+        }
+        if (role & 2) {
+            const double t = block_sum_rows(partials + (size_t)(c0 + 1u) * kChunk * kSlots, cs1, red);
+            if (threadIdx.x < 32) publish_row(fin.out + (size_t)(c0 + 1u) * kSlots, t, fin.seq);
+        }
     }
 }
 

@@ -62,6 +62,10 @@ int dcreg_launch_series(dcreg_ctx *, double *ms, int64_t *searched, int64_t *ref
  * Bit 2 (+ 4): the linearisation kernel ran in one-wave blocks with k_sum_tiles behind it (option "one_wave"; its duration covers
  * both).  Returns the number of entries logged. */
 int dcreg_launch_series_passes(dcreg_ctx *, uint8_t *advanced, int64_t cap);
+/* ... and which kernels carried each launch of that log out: 0 = the linearisation kernel alone, 1 = a pass and the linearisation kernel
+ * behind it, 2 = the advance pass alone (kernels.hpp k_advance ROWS: it builds the rows of its tiles and finishes the launch itself;
+ * option "advance_fused").  Call it before the resetting dcreg_launch_series too.  Returns the number of entries logged. */
+int dcreg_launch_series_structure(dcreg_ctx *, uint8_t *structure, int64_t cap);
 
 /* Timing probe of the small-frame advance pass (option "team_stamps" = 1): of the LAST launch that ran the pass, per block (one wave,
  * kTeamTile points) eight shader-clock words - start, tests done, old neighbours gathered, rows listed, rows cut (table loads), candidates
@@ -99,8 +103,11 @@ int dcreg_knn_timed(dcreg_ctx *, const float *q_xyz, int64_t n, int64_t stride_f
  *   "use_certificates"   0 = search every point in every launch (the old neighbours still bound the searches), 1 = default;
  *   "keep_source_order"  1 = the next dcreg_set_source keeps the caller's point order instead of the Hilbert-curve sort;
  *   "advance"            the advance pass in front of single-pose launches: 0 = never, 1 (default) = when the last completed launch searched
- *                        between 1 % and 45 % of its points and the cloud has at least "advance_min_blocks" (2048) query blocks, 2 = whenever
+ *                        between 0.5 % and 70 % of its points and the cloud has at least "advance_min_blocks" (2048) query blocks, 2 = whenever
  *                        the launch can take it (warm state, certificates in use): tests;
+ *   "advance_fused"      1 (default) = a launch that takes the advance pass is ONE kernel: the pass builds the rows of its tiles and finishes
+ *                        the launch itself (launches of at most 64 query blocks excepted); 0 = the pass and the linearisation kernel behind
+ *                        it, two kernels (A/B and the bitwise comparisons of the tests);
  *   "team_pass"          the small-frame advance pass (sixteen lanes per query) in front of single-pose launches: 0 = never, 1 (default) =
  *                        for clouds of at most 16384 points when the last completed launch searched at least half of them and the map holds
  *                        at least 3 points per occupied cell, 2 = whenever the launch can take it; "team_stamps": see dcreg_team_pass_stamps;
