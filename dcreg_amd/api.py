@@ -151,6 +151,8 @@ EXPORTS = [
     "dcreg_default_place_params", "dcreg_place_descriptors", "dcreg_place_descriptors_device", "dcreg_places_reset", "dcreg_places_count",
     "dcreg_places_add", "dcreg_places_add_clouds", "dcreg_places_add_clouds_device", "dcreg_places_add_source", "dcreg_places_get",
     "dcreg_places_query", "dcreg_places_query_clouds", "dcreg_places_query_clouds_device", "dcreg_places_query_source",
+    "dcreg_default_outlier_params", "dcreg_outlier_filter", "dcreg_outlier_filter_device", "dcreg_set_source_outliers",
+    "dcreg_set_source_outliers_device", "dcreg_set_target_outliers", "dcreg_set_target_outliers_device", "dcreg_target_remove_outliers",
 ]
 
 _lib = None
@@ -507,6 +509,67 @@ def _check_range(first, last, k, what):
         raise ValueError("%s: k in [1, %d] is expected, got %d" % (what, PLACE_MAX_K, int(k)))
 
 
+class OutlierParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("k", C.c_int), ("std_mul", C.c_double), ("search_radius", C.c_double), ("radius", C.c_double),
+                ("min_neighbors", C.c_int), ("reserved_", C.c_int)]
+
+
+class OutlierInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_sparse", C.c_int64), ("n_out", C.c_int64), ("mean", C.c_double),
+                ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
+_STRUCTS.update({"dcreg_outlier_params": OutlierParams, "dcreg_outlier_info": OutlierInfo})
+OUTLIER_MODES = {"statistical": 0, "radius": 1}      # DCREG_OUTLIER_STATISTICAL / DCREG_OUTLIER_RADIUS
+OUTLIER_MAX_K = 32
+OUTLIER_MAX_POINTS = 2 ** 31 - 1
+
+
+def _check_outlier_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_outlier_params block"""
+    if not isinstance(p, OutlierParams):
+        raise ValueError("%s: outlier_params(...) is expected, got %s" % (what, type(p).__name__))
+    if p.mode == OUTLIER_MODES["statistical"]:
+        if not 1 <= p.k <= OUTLIER_MAX_K:
+            raise ValueError("%s: k in [1, %d] is expected, got %d" % (what, OUTLIER_MAX_K, p.k))
+        if not np.isfinite(p.std_mul):
+            raise ValueError("%s: a finite std_mul is expected, got %r" % (what, p.std_mul))
+        if not (np.isfinite(p.search_radius) and p.search_radius >= 0.0):
+            raise ValueError("%s: a finite search_radius >= 0 is expected, got %r" % (what, p.search_radius))
+    elif p.mode == OUTLIER_MODES["radius"]:
+        if not (np.isfinite(p.radius) and p.radius > 0.0):
+            raise ValueError("%s: a finite radius > 0 is expected, got %r" % (what, p.radius))
+        if p.min_neighbors < 1:
+            raise ValueError("%s: min_neighbors >= 1 is expected, got %d" % (what, p.min_neighbors))
+    else:
+        raise ValueError("%s: an outlier mode of %s is expected, got %d" % (what, sorted(OUTLIER_MODES.values()), p.mode))
+
+
+def outlier_params(mode="statistical", k=8, std_mul=2.0, search_radius=0.0, radius=0.5, min_neighbors=3):
+    """dcreg_outlier_params: "statistical" (PCL StatisticalOutlierRemoval: k = setMeanK, std_mul = setStddevMulThresh, search_radius > 0
+    bounds the search) or "radius" (PCL RadiusOutlierRemoval: radius, min_neighbors); include/dcreg.h has the rules"""
+    if mode not in OUTLIER_MODES:
+        raise ValueError("outlier_params: a mode of %s is expected, got %r" % (sorted(OUTLIER_MODES), mode))
+    p = OutlierParams()
+    p.mode = OUTLIER_MODES[mode]
+    p.k, p.min_neighbors = int(k), int(min_neighbors)
+    p.std_mul, p.search_radius, p.radius = float(std_mul), float(search_radius), float(radius)
+    _check_outlier_params(p, "outlier_params")
+    return p
+
+
+def _outlier_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_sparse": i.n_sparse, "n_out": i.n_out, "mean": i.mean, "stddev": i.stddev,
+            "threshold": i.threshold}
+
+
+def _check_device_cloud(n, stride, what):
+    if int(n) < 0 or int(n) > OUTLIER_MAX_POINTS:
+        raise ValueError("%s: 0 .. 2^31 - 1 points are expected, got %d" % (what, int(n)))
+    if int(stride) < 3:
+        raise ValueError("%s: a stride of at least 3 floats is expected, got %d" % (what, int(stride)))
+
+
 def _offsets(offsets, what):
     off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
     if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
@@ -679,6 +742,16 @@ def load():
         for name in ("dcreg_places_query_clouds", "dcreg_places_query_clouds_device"):
             getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64] + res + [pi]
         L.dcreg_places_query_source.argtypes = [vp] + res + [pi]
+    if hasattr(L, "dcreg_outlier_filter"):     # (absent from an older build loaded through DCREG_LIB for an A/B)
+        op, oi, vpp, vi = C.POINTER(OutlierParams), C.POINTER(OutlierInfo), C.POINTER(VoxelParams), C.POINTER(VoxelInfo)
+        L.dcreg_default_outlier_params.argtypes = [op]
+        for name in ("dcreg_outlier_filter", "dcreg_outlier_filter_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, op, vp, C.c_int64, i64p, vp, vp, oi]
+        for name in ("dcreg_set_source_outliers", "dcreg_set_source_outliers_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vpp, op, vi, oi]
+        for name in ("dcreg_set_target_outliers", "dcreg_set_target_outliers_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vpp, op, C.c_double, vi, oi]
+        L.dcreg_target_remove_outliers.argtypes = [vp, op, oi]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1234,6 +1307,80 @@ class Context:
         self._check(self._L.dcreg_places_query_source(self._h, first, last, k, idx.ctypes.data_as(ip), shift.ctypes.data_as(ip), _dp(dist),
                                                       C.byref(info)), "dcreg_places_query_source")
         return idx[0], shift[0], dist[0], _place_info_dict(info)
+
+    def outlier_filter(self, xyz, params=None, want_mask=True, want_scores=True):
+        """dcreg_outlier_filter: the points of one cloud ([n, c] float32, x y z first; non-finite points are dropped) that pass the
+        statistical or radius filter of params (outlier_params(...); None = the defaults), in input order (include/dcreg.h has the
+        rules).  -> (kept [m, 3] float32, keep mask [n] bool or None, scores [n] float32 or None, dict n_in / n_finite / n_sparse /
+        n_out / mean / stddev / threshold)"""
+        p = params if params is not None else outlier_params()
+        _check_outlier_params(p, "outlier_filter")
+        a = _points(xyz, "outlier_filter")
+        n = a.shape[0]
+        out = np.empty((max(n, 1), 3), np.float32)
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        scores = np.full(max(n, 1), np.nan, np.float32) if want_scores else None
+        n_out = C.c_int64(0)
+        info = OutlierInfo()
+        self._check(self._L.dcreg_outlier_filter(self._h, a.ctypes.data, n, a.shape[1], C.byref(p), out.ctypes.data, n, C.byref(n_out),
+                                                 mask.ctypes.data if want_mask else None, scores.ctypes.data if want_scores else None,
+                                                 C.byref(info)), "dcreg_outlier_filter")
+        return (out[:n_out.value], mask[:n].astype(bool) if want_mask else None, scores[:n] if want_scores else None,
+                _outlier_info_dict(info))
+
+    def outlier_filter_device(self, dev_ptr, n, stride, dev_out_ptr, capacity, params=None, dev_mask_ptr=0, dev_scores_ptr=0):
+        """dcreg_outlier_filter_device: the cloud in device memory, the kept points to dev_out_ptr (3 floats per point, capacity points),
+        optionally the uint8 mask and the float scores to device buffers of n entries.  -> (n_out, info dict)"""
+        p = params if params is not None else outlier_params()
+        _check_outlier_params(p, "outlier_filter_device")
+        _check_device_cloud(n, stride, "outlier_filter_device")
+        if int(capacity) < 0:
+            raise ValueError("outlier_filter_device: a capacity >= 0 is expected, got %d" % int(capacity))
+        n_out = C.c_int64(0)
+        info = OutlierInfo()
+        self._check(self._L.dcreg_outlier_filter_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(p), C.c_void_p(dev_out_ptr),
+                                                        int(capacity), C.byref(n_out), C.c_void_p(dev_mask_ptr or None),
+                                                        C.c_void_p(dev_scores_ptr or None), C.byref(info)), "dcreg_outlier_filter_device")
+        return n_out.value, _outlier_info_dict(info)
+
+    def _set_outliers(self, name, ptr, n, stride, params, leaf, mode, min_points, search_radius=None):
+        p = params if params is not None else outlier_params()
+        _check_outlier_params(p, name)
+        v = voxel_params(leaf, mode, min_points) if leaf is not None else None
+        _check_device_cloud(n, stride, name)
+        vinfo, info = VoxelInfo(), OutlierInfo()
+        args = [self._h, ptr, int(n), int(stride), C.byref(v) if v is not None else None, C.byref(p)]
+        if search_radius is not None:
+            args.append(float(search_radius))
+        self._check(getattr(self._L, "dcreg_" + name)(*(args + [C.byref(vinfo), C.byref(info)])), "dcreg_" + name)
+        return _outlier_info_dict(info), (_voxel_info_dict(vinfo) if v is not None else None)
+
+    def set_source_outliers(self, xyz, params=None, leaf=None, mode="centroid", min_points=1):
+        """dcreg_set_source_outliers: the cloud filtered on the device (leaf given: voxelised first) and kept as the source - bitwise
+        set_source(outlier_filter(xyz)).  -> (outlier info dict, voxel info dict or None)"""
+        a = _points(xyz, "set_source_outliers")
+        return self._set_outliers("set_source_outliers", a.ctypes.data, a.shape[0], a.shape[1], params, leaf, mode, min_points)
+
+    def set_source_outliers_device(self, dev_ptr, n, stride, params=None, leaf=None, mode="centroid", min_points=1):
+        return self._set_outliers("set_source_outliers_device", C.c_void_p(dev_ptr), n, stride, params, leaf, mode, min_points)
+
+    def set_target_outliers(self, xyz, search_radius, params=None, leaf=None, mode="centroid", min_points=1):
+        """dcreg_set_target_outliers: the cloud filtered on the device (leaf given: voxelised first) and kept as the map - bitwise
+        set_target(outlier_filter(xyz), search_radius).  -> (outlier info dict, voxel info dict or None)"""
+        a = _points(xyz, "set_target_outliers")
+        return self._set_outliers("set_target_outliers", a.ctypes.data, a.shape[0], a.shape[1], params, leaf, mode, min_points, search_radius)
+
+    def set_target_outliers_device(self, dev_ptr, n, stride, search_radius, params=None, leaf=None, mode="centroid", min_points=1):
+        return self._set_outliers("set_target_outliers_device", C.c_void_p(dev_ptr), n, stride, params, leaf, mode, min_points, search_radius)
+
+    def remove_outliers(self, params=None):
+        """dcreg_target_remove_outliers: the resident map cleaned in place (later calls are bitwise set_target of the cleaned cloud).
+        -> dict n_in / n_finite / n_sparse / n_out / mean / stddev / threshold"""
+        p = params if params is not None else outlier_params()
+        _check_outlier_params(p, "remove_outliers")
+        info = OutlierInfo()
+        self._check(self._L.dcreg_target_remove_outliers(self._h, C.byref(p), C.byref(info)), "dcreg_target_remove_outliers")
+        return _outlier_info_dict(info)
 
     def index_info(self):
         info = IndexInfo()

@@ -23,6 +23,7 @@ SOURCES = [
     "device/voxel.hip",
     "device/deskew.hip",
     "device/places.hip",
+    "device/outliers.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

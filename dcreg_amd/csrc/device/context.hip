@@ -121,7 +121,7 @@ static double cap_cell_for_budget(double h, const double mn[3], const double mx[
 
 // the index of the n points at raw, built into d (build_grid_at); box = the cloud's bounds min xyz, max xyz when the caller has them
 // already, else NULL
-static int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr) {
+int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d, double radius_hint, uint32_t *occupied_out, const double *box) {
     if (n <= 0) { c->fail("cloud is empty"); return DCREG_E_INVALID; }
     double mn[3], mx[3];
     int rc = DCREG_OK;
@@ -188,7 +188,7 @@ static int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d, 
 }
 
 // empty-space distance field of the grid of d (queries far from any point skip the rings they know are empty)
-static int build_gap_field(dcreg_ctx *c, IndexSet &d, double radius_hint) {
+int build_gap_field(dcreg_ctx *c, IndexSet &d, double radius_hint) {
     GridDev &g = d.grid;
     g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
     if (!c->opt_gap_field) return DCREG_OK;
@@ -746,6 +746,7 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     return DCREG_OK;
 }
 
+static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_update *info);
 static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_update *info) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
@@ -757,14 +758,25 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     const int64_t n = wm.n;
     const size_t n1 = (size_t)n + 1;
     if (c->d_upd.ensure(c, 4 * n1)) return DCREG_E_NOMEM;
-    uint32_t *flag_r = c->d_upd.data(), *pos_r = flag_r + n1, *flag_s = pos_r + n1, *pos_s = flag_s + n1;
+    uint32_t *flag_r = c->d_upd.data(), *flag_s = flag_r + 2 * n1;
     CropBox bx;
     for (int a = 0; a < 3; ++a) { bx.lo[a] = lo[a]; bx.hi[a] = hi[a]; }
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, bx, flag_r);
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, bx, flag_s);
+    return map_keep_flagged(c, "the crop box keeps no point of the map", info);
+}
+
+// The keep flags of the whole map's points are in c->d_upd (n + 1 entries each, the last 0): [0] in index order, [2 (n + 1)] in sorted
+// order.  The kept points, renumbered in their old order, become the map (dcreg_target_crop, dcreg_target_remove_outliers); none_kept: the
+// refusal's text when no flag is set
+static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_update *info) {
+    const IndexSet &wm = whole_map(c);
+    const int64_t n = wm.n;
+    const size_t n1 = (size_t)n + 1;
+    uint32_t *flag_r = c->d_upd.data(), *pos_r = flag_r + n1, *flag_s = pos_r + n1, *pos_s = flag_s + n1;
     uint32_t w[kMwWords];
     words_init(w);
     HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, bx, flag_r);
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, bx, flag_s);
     {
         size_t tmp = 0;
         HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
@@ -778,7 +790,7 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     HIP_TRY(c, hipMemcpyAsync(&kept, pos_r + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (kept == 0) { c->fail("the crop box keeps no point of the map"); return DCREG_E_INVALID; }
+    if (kept == 0) { c->fail("%s", none_kept); return DCREG_E_INVALID; }
     if ((int64_t)kept == n) { update_info(info, n, 0, 0, n, 0); return DCREG_OK; }      // nothing outside the box: nothing changes
     // ---- the map changes
     (void)roi_deactivate(c);
@@ -827,6 +839,31 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     if (rc) { m.n = 0; return rc; }
     update_info(info, n, 0, n - kept, m.n, rebuilt);
     return DCREG_OK;
+}
+
+// dcreg_target_remove_outliers: the filter over the whole map's points through the map's own index (outliers.hip), the survivors through the
+// update path of the crop.  Nothing of the context changes before the flags are known and some point goes.
+static int map_remove_outliers(dcreg_ctx *c, const dcreg_outlier_params *p, dcreg_outlier_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = outlier_check(c, p)) return rc;
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const IndexSet &wm = whole_map(c);
+    const int64_t n = wm.n;
+    const size_t n1 = (size_t)n + 1;
+    OutlierResult r;
+    int rc = outlier_pass(c, wm.raw.data(), n, p, &wm, r);
+    if (rc) return rc;
+    if (r.n_out == 0) { c->fail("the filter would remove every point of the map"); return DCREG_E_INVALID; }
+    outlier_info(info, r);
+    if (r.n_out == n) return DCREG_OK;               // nothing to remove: nothing changes
+    if (c->d_upd.ensure(c, 4 * n1)) return DCREG_E_NOMEM;
+    uint32_t *flag_r = c->d_upd.data(), *flag_s = flag_r + 2 * n1;
+    HIP_TRY(c, hipMemcpyAsync(flag_r, c->outl.keep.data(), sizeof(uint32_t) * n1, hipMemcpyDeviceToDevice, c->stream));
+    rc = outlier_sorted_flags(c, wm.sorted.data(), n, flag_r, flag_s);
+    if (rc) return rc;
+    return map_keep_flagged(c, "the filter would remove every point of the map", nullptr);
 }
 
 // dcreg_debug_index_check: the whole map's grid built from scratch (same origin, edge, dims, sub-cells) from its raw points, compared entry by entry
@@ -2346,6 +2383,61 @@ int dcreg_set_target_voxel_device(dcreg_ctx *c, const float *d_xyz, int64_t n, i
                                   dcreg_voxel_info *info) {
     return set_cloud_voxel(c, d_xyz, n, stride, true, p, true, r, info);
 }
+
+// dcreg_set_source_outliers* / dcreg_set_target_outliers*: the cloud - packed by upload_cloud, or the packed output of the voxel pass - is
+// filtered where it lies in c->d_aligned.data(), the kept points are packed beside it and swapped in, and the commit of the plain calls takes them
+static int set_cloud_outliers(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_voxel_params *vp,
+                              const dcreg_outlier_params *p, bool target, double radius_hint, dcreg_voxel_info *vinfo, dcreg_outlier_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = outlier_check(c, p)) return rc;
+    if (n <= 0) { c->fail("%s cloud is null or empty", target ? "target" : "measure"); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t m = n;
+    int rc;
+    if (vp) {
+        const int64_t off[2] = {0, n};
+        VoxelResult v;
+        rc = voxel_pass(c, 1, xyz, off, stride, on_device, vp, true, v);
+        if (rc) return rc;
+        voxel_info(vinfo, v);
+        if (v.n_out <= 0) { c->fail("no point of the %s cloud is left after the voxel pass", target ? "target" : "measure"); return DCREG_E_INVALID; }
+        m = v.n_out;
+    } else {
+        rc = upload_cloud(c, xyz, n, stride, on_device, c->d_aligned);
+        if (rc) return rc;
+    }
+    OutlierResult r;
+    rc = outlier_pass(c, c->d_aligned.data(), m, p, nullptr, r);
+    if (rc) return rc;
+    outlier_info(info, r);
+    if (r.n_out <= 0) { c->fail("no point of the %s cloud is left after the outlier filter", target ? "target" : "measure"); return DCREG_E_INVALID; }
+    rc = outlier_write_packed(c, c->d_aligned.data(), m, r.n_out);
+    if (rc) return rc;
+    c->d_aligned.swap(c->outl.out4);
+    double box[6];
+    rc = device_bounds(c, c->d_aligned.data(), r.n_out, box, box + 3);
+    if (rc) return rc;
+    if (target) return target_commit(c, r.n_out, box, radius_hint);
+    return source_commit(c, r.n_out, box, box + 3, true);
+}
+int dcreg_set_source_outliers(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *voxel, const dcreg_outlier_params *p,
+                              dcreg_voxel_info *vinfo, dcreg_outlier_info *info) {
+    return set_cloud_outliers(c, xyz, n, stride, false, voxel, p, false, 0.0, vinfo, info);
+}
+int dcreg_set_source_outliers_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_voxel_params *voxel,
+                                     const dcreg_outlier_params *p, dcreg_voxel_info *vinfo, dcreg_outlier_info *info) {
+    return set_cloud_outliers(c, d_xyz, n, stride, true, voxel, p, false, 0.0, vinfo, info);
+}
+int dcreg_set_target_outliers(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const dcreg_voxel_params *voxel, const dcreg_outlier_params *p,
+                              double r, dcreg_voxel_info *vinfo, dcreg_outlier_info *info) {
+    return set_cloud_outliers(c, xyz, n, stride, false, voxel, p, true, r, vinfo, info);
+}
+int dcreg_set_target_outliers_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride, const dcreg_voxel_params *voxel,
+                                     const dcreg_outlier_params *p, double r, dcreg_voxel_info *vinfo, dcreg_outlier_info *info) {
+    return set_cloud_outliers(c, d_xyz, n, stride, true, voxel, p, true, r, vinfo, info);
+}
+int dcreg_target_remove_outliers(dcreg_ctx *c, const dcreg_outlier_params *p, dcreg_outlier_info *info) { return map_remove_outliers(c, p, info); }
 
 int dcreg_default_lin_params(dcreg_lin_params *p, double radius) {
     if (!p) return DCREG_E_INVALID;

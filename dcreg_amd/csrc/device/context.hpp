@@ -337,6 +337,21 @@ struct dcreg_ctx {
         DevBuf<int32_t> sel_shift;
     };
     PlaceBufs places;
+    // outlier removal (outliers.hip: dcreg_outlier_filter*, dcreg_set_*_outliers*, dcreg_target_remove_outliers).  Scratch of one call: the
+    // packed cloud, the used flags and their scan, the used points compacted (w = input index) and their index; per input point the score,
+    // the keep flag and its scan (n + 1 entries each, the last flag 0); the partial sums of the tree reductions (two sides, used in turn);
+    // the call's counts ([0] points in the statistics, [1] sparse points); the outputs (3 floats per point, or packed as k_pack packs a
+    // cloud) and the byte mask
+    struct OutlierBufs {
+        DevBuf<float4> pts, cpts, out4;
+        DevBuf<uint32_t> used, upos, keep, pos;
+        DevBuf<float> score, out;
+        DevBuf<uint8_t> mask;
+        DevBuf<double> part[2];
+        DevBuf<unsigned long long> cnt;
+        IndexSet idx;
+    };
+    OutlierBufs outl;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
@@ -535,4 +550,21 @@ int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int6
                         float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info, DeskewRun *dsk = nullptr);
 int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, int k, double max_radius, const PoseArg *pose,
                int32_t *d_idx, float *d_d2, bool sweep = false);
+// context.hip: the index of the n points at raw built into d, and the empty-space field of its grid
+int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, dcreg_ctx::IndexSet &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr);
+int build_gap_field(dcreg_ctx *c, dcreg_ctx::IndexSet &d, double radius_hint);
+// outliers.hip: one call's filter over the n packed points at `in` (input order, w = the index).  map == null: the used points are compacted
+// and indexed (c->outl.idx); otherwise the points ARE the map behind that index (all finite) and its grid is searched.  Leaves the scores in
+// c->outl.score, the keep flags and their exclusive scan in c->outl.keep / pos (n + 1 entries) and the counts in r; waits for the stream.
+struct OutlierResult {
+    int64_t n_in = 0, n_finite = 0, n_sparse = 0, n_out = 0;
+    double mean = 0.0, stddev = 0.0, threshold = 0.0;
+};
+int outlier_check(dcreg_ctx *c, const dcreg_outlier_params *p);      // the parameter refusals of include/dcreg.h
+int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_params *p, const dcreg_ctx::IndexSet *map, OutlierResult &r);
+void outlier_info(dcreg_outlier_info *info, const OutlierResult &r);
+// the kept points of the pass packed into c->outl.out4 as k_pack packs a cloud (w = the new index)
+int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_out);
+// flag_s[p] = the keep flag of the map point at sorted position p (n + 1 entries, the last 0)
+int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s);
 }  // namespace dcreg

@@ -739,6 +739,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_sweep_path")) return sizeof(dcreg_sweep_path);
     if (!std::strcmp(name, "dcreg_place_params")) return sizeof(dcreg_place_params);
     if (!std::strcmp(name, "dcreg_place_info")) return sizeof(dcreg_place_info);
+    if (!std::strcmp(name, "dcreg_outlier_params")) return sizeof(dcreg_outlier_params);
+    if (!std::strcmp(name, "dcreg_outlier_info")) return sizeof(dcreg_outlier_info);
     return 0;
 }
 

@@ -22,6 +22,10 @@
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
  *                                                                                   dcreg_set_target_voxel[_device]
+ *       statistical / radius outlier removal of one cloud                        -> dcreg_outlier_filter[_device],
+ *       ... kept as the source / target, ... of the resident map in place           dcreg_set_source_outliers[_device],
+ *                                                                                   dcreg_set_target_outliers[_device],
+ *                                                                                   dcreg_target_remove_outliers
  *       motion compensation (deskew) of sweeps from per-point stamps             -> dcreg_deskew[_device],
  *                                                                                   dcreg_set_source_deskew[_device]
  *       ... along a sampled trajectory, through a sensor-to-body extrinsic       -> dcreg_deskew_path[_device],
@@ -529,6 +533,95 @@ int dcreg_places_query_clouds_device(dcreg_ctx *, int n_clouds, const float *d_x
                                      int64_t last, int k, int32_t *idx, int32_t *shift, double *dist, dcreg_place_info *info);
 /* ... with the descriptor of the context's current source (one query) */
 int dcreg_places_query_source(dcreg_ctx *, int64_t first, int64_t last, int k, int32_t *idx, int32_t *shift, double *dist, dcreg_place_info *info);
+
+/* ---------------- outlier removal: statistical and radius filters ----------------
+ * PCL's StatisticalOutlierRemoval and RadiusOutlierRemoval on the device, with rules fixed tightly enough that the output is bitwise the
+ * numpy reference of tests/outliers_ref.py (INTEGRATION.md lists where the statistical filter differs from PCL's).  For one cloud of n
+ * points and the parameters mode, k, std_mul, radius, min_neighbors, search_radius:
+ *   - used points: a point is used when x, y and z are all finite; the others are dropped and counted.  "Index" is the input index;
+ *   - distances between used points are the float d2 that dcreg_knn computes; neighbours are ranked by the total order (d2, index);
+ *   - a point is never its own neighbour, by index and not by distance: exact duplicates are neighbours at distance 0.  (With more than k
+ *     duplicates of a point that point is not among its own k + 1 nearest, so "search k + 1 and drop the first" is wrong: the entry with
+ *     the point's own index is dropped if it is there, otherwise the last.  The k distances that remain are the k smallest d2 to OTHER
+ *     points either way, which is what the device keeps.)
+ *   DCREG_OUTLIER_STATISTICAL (k in [1, 32], std_mul finite, search_radius finite and >= 0):
+ *   - score m_i = (float)((sum_{j=1..k} (double)sqrtf(d2_ij)) / k), summed left to right over the k nearest others in ascending rank, with
+ *     an IEEE float square root and an IEEE double division;
+ *   - search_radius > 0: only neighbours with d2 < (float)(search_radius^2) count; a used point with fewer than k of them is SPARSE: it
+ *     is dropped, counted in n_sparse, and takes no part in the statistics;
+ *   - search_radius = 0: the search is unbounded.  A cloud with at most k used points has no statistics: all its used points are kept,
+ *     every score is NaN, and mean, stddev and threshold are NaN;
+ *   - tree sum T(a) of a length-n array: pad with +0.0 to the next power of two, replace the array by a[2j] + a[2j+1] until one value is
+ *     left (numpy: while len(b) > 1: b = b[0::2] + b[1::2]).  Any reduction whose blocks are power-of-two sized and aligned reproduces
+ *     this tree: the result does not depend on the launch configuration;
+ *   - statistics over the n_stat points that are used and not sparse, every other position of the n contributing +0.0:
+ *     mean = T((double)m_i) / n_stat; var = T(((double)m_i - mean)^2) / (n_stat - 1), or 0 for n_stat = 1; stddev = sqrt(var);
+ *     threshold = mean + std_mul * stddev as one rounded multiply and one rounded add (no fused multiply-add).  n_stat = 0: all three NaN;
+ *   - point i is kept iff (double)m_i <= threshold.
+ *   DCREG_OUTLIER_RADIUS (radius finite and > 0, min_neighbors >= 1):
+ *   - a used point is kept iff at least min_neighbors other used points have d2 < (float)(radius^2) - the comparison min_spacing uses in
+ *     dcreg_target_insert.  No statistics (mean, stddev, threshold: NaN; n_sparse: 0), no order dependence; the count stops at min_neighbors.
+ *   Output: the kept points in input order, each copied bit for bit, 3 floats per point; optionally (NULL: not wanted) a keep mask
+ *   uint8[n] and the scores float[n] - statistical mode m_i, radius mode the neighbour count capped at min_neighbors as a float, NaN for
+ *   unused and sparse points.
+ * A call's result depends on the cloud and the parameters only - not on what else the context holds - and repeated calls are bitwise equal.
+ * None of the filter calls changes the target, the source, neighbour states, loaded frames, the places database or the window index;
+ * dcreg_set_source_outliers / dcreg_set_target_outliers change what dcreg_set_source / dcreg_set_target change, and
+ * dcreg_target_remove_outliers what dcreg_target_crop changes.
+ * An unbounded search of an isolated point walks the rings of the grid out to its k-th neighbour: a hundred points tens of metres from a
+ * 1 M-point cloud take the call from 4 ms to a second; search_radius is the practical answer for clouds with far outliers.
+ * DCREG_E_INVALID, and nothing is written: null parameters, an unknown mode, k outside [1, 32], a std_mul that is not finite, a
+ * search_radius that is not finite or is negative, a radius that is not finite and > 0, min_neighbors < 1, stride < 3, n < 0, more than
+ * 2^31 - 1 points, null buffers; DCREG_E_STATE: a linearisation in flight.  A failed allocation (DCREG_E_NOMEM) leaves the context as it
+ * was.  Device memory: about 60 B per input point of scratch plus the index of the cloud, kept by the context for the next call. */
+#define DCREG_OUTLIER_STATISTICAL 0
+#define DCREG_OUTLIER_RADIUS 1
+typedef struct dcreg_outlier_params {
+    int mode;            /* DCREG_OUTLIER_STATISTICAL / DCREG_OUTLIER_RADIUS */
+    int k;               /* statistical: neighbours per point (PCL setMeanK), 1 .. 32 */
+    double std_mul;      /* statistical: PCL setStddevMulThresh */
+    double search_radius;/* statistical: 0 = unbounded, > 0 = neighbours beyond it do not count (m) */
+    double radius;       /* radius mode: PCL setRadiusSearch (m) */
+    int min_neighbors;   /* radius mode: PCL setMinNeighborsInRadius, >= 1 */
+    int reserved_;
+} dcreg_outlier_params;
+typedef struct dcreg_outlier_info {
+    int64_t n_in;        /* points passed in (after the voxel block, where one runs first) */
+    int64_t n_finite;    /* ... with three finite coordinates (used) */
+    int64_t n_sparse;    /* ... of those, with fewer than k neighbours inside search_radius */
+    int64_t n_out;       /* points kept */
+    double mean, stddev, threshold;   /* statistical mode (NaN otherwise) */
+} dcreg_outlier_info;
+/* statistical, k = 8, std_mul = 2, search_radius = 0; radius = 0.5, min_neighbors = 3 */
+int dcreg_default_outlier_params(dcreg_outlier_params *);
+/* One cloud in (stride_floats floats per point, x y z first), the kept points out.  *n_out receives the number of kept points;
+ * capacity_points = n is always enough; a smaller capacity that the output does not fit returns DCREG_E_INVALID with *n_out and info filled
+ * (the size needed) and nothing written to out_xyz, keep_mask or scores.  info may be NULL.  Waits for the stream.
+ * _device: d_xyz is read as dcreg_set_source_device reads a cloud; d_out_xyz, d_keep_mask and d_scores are device memory. */
+int dcreg_outlier_filter(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_outlier_params *, float *out_xyz,
+                         int64_t capacity_points, int64_t *n_out, uint8_t *keep_mask, float *scores, dcreg_outlier_info *info);
+int dcreg_outlier_filter_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_outlier_params *,
+                                float *d_out_xyz, int64_t capacity_points, int64_t *n_out, uint8_t *d_keep_mask, float *d_scores,
+                                dcreg_outlier_info *info);
+/* One cloud filtered and kept as the source / target; voxel != NULL runs the voxel pass first (voxel -> filter -> build), as the deskew
+ * forms take a voxel block.  The context is left bitwise as dcreg_set_source / dcreg_set_target of the filtered cloud leaves it (the points
+ * go from pass to build on the device).  A refused call - the filter's refusals, the voxel pass's, n <= 0, no point left - leaves the
+ * context's source / target as it was.  vinfo and info may be NULL. */
+int dcreg_set_source_outliers(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *voxel,
+                              const dcreg_outlier_params *, dcreg_voxel_info *vinfo, dcreg_outlier_info *info);
+int dcreg_set_source_outliers_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *voxel,
+                                     const dcreg_outlier_params *, dcreg_voxel_info *vinfo, dcreg_outlier_info *info);
+int dcreg_set_target_outliers(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *voxel,
+                              const dcreg_outlier_params *, double search_radius_hint, dcreg_voxel_info *vinfo, dcreg_outlier_info *info);
+int dcreg_set_target_outliers_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_voxel_params *voxel,
+                                     const dcreg_outlier_params *, double search_radius_hint, dcreg_voxel_info *vinfo,
+                                     dcreg_outlier_info *info);
+/* Cleans the resident map in place: the filter over the map's points in index order, searched through the map's own index (on a map with
+ * a window index the whole map's, as dcreg_knn), the survivors through the update path of dcreg_target_crop.  It carries the contract of
+ * the map-update section above: later calls are bitwise dcreg_set_target of the cleaned cloud in index order; a call that changes the map
+ * drops what dcreg_set_target drops; a call that removes nothing changes nothing (the neighbour states stay warm); a call that would
+ * remove every point is refused (DCREG_E_INVALID); refusals leave everything as it was.  DCREG_E_STATE: no target. */
+int dcreg_target_remove_outliers(dcreg_ctx *, const dcreg_outlier_params *, dcreg_outlier_info *info);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
