@@ -153,6 +153,8 @@ EXPORTS = [
     "dcreg_places_query", "dcreg_places_query_clouds", "dcreg_places_query_clouds_device", "dcreg_places_query_source",
     "dcreg_default_outlier_params", "dcreg_outlier_filter", "dcreg_outlier_filter_device", "dcreg_set_source_outliers",
     "dcreg_set_source_outliers_device", "dcreg_set_target_outliers", "dcreg_set_target_outliers_device", "dcreg_target_remove_outliers",
+    "dcreg_keyframes_reset", "dcreg_keyframes_count", "dcreg_keyframes_sizes", "dcreg_keyframes_add_clouds", "dcreg_keyframes_add_clouds_device",
+    "dcreg_keyframes_add_source", "dcreg_keyframes_get", "dcreg_keyframes_submaps", "dcreg_keyframes_submaps_device", "dcreg_set_target_keyframes",
 ]
 
 _lib = None
@@ -570,6 +572,61 @@ def _check_device_cloud(n, stride, what):
         raise ValueError("%s: a stride of at least 3 floats is expected, got %d" % (what, int(stride)))
 
 
+KEYFRAME_MAX_POINTS = 2 ** 31 - 1      # member points of one gather (include/dcreg.h)
+
+
+def _voxel_block(leaf, mode, min_points, what):
+    """None (no voxel pass), a voxel_params(...) block, or the block of a leaf / mode / min_points"""
+    if leaf is None:
+        return None
+    if isinstance(leaf, VoxelParams):
+        p = leaf
+        if not all(np.isfinite(p.leaf[a]) and p.leaf[a] > 0.0 for a in range(3)):
+            raise ValueError("%s: voxel leaf: finite edges > 0 are expected, got %s" % (what, list(p.leaf)))
+        if p.mode not in VOXEL_MODES.values():
+            raise ValueError("%s: a voxel mode of %s is expected, got %d" % (what, sorted(VOXEL_MODES.values()), p.mode))
+        return p
+    if isinstance(leaf, (str, bytes, dict)) or isinstance(leaf, C.Structure):
+        raise ValueError("%s: leaf: None, one edge, three edges or voxel_params(...) is expected, got %s" % (what, type(leaf).__name__))
+    try:
+        return voxel_params(leaf, mode, min_points)
+    except (TypeError, ValueError) as e:
+        raise ValueError("%s: %s" % (what, e)) from None
+
+
+def _keyframe_id(i, what):
+    if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)):
+        raise ValueError("%s: keyframe ids are integers, got %r" % (what, i))
+    if int(i) < 0:
+        raise ValueError("%s: keyframe ids are >= 0, got %d" % (what, int(i)))
+    return int(i)
+
+
+def _members(members, what):
+    """(member_offsets [n + 1], ids [M], poses [M, 12]) of a list (one per submap) of lists of (keyframe id, T 4x4)"""
+    if isinstance(members, (str, bytes)) or not hasattr(members, "__len__"):
+        raise ValueError("%s: members: a list (one per submap) of lists of (id, T 4x4) is expected" % what)
+    off, ids, poses = [0], [], []
+    for g, sub in enumerate(members):
+        if isinstance(sub, (str, bytes)) or not hasattr(sub, "__len__"):
+            raise ValueError("%s: members[%d]: a list of (id, T 4x4) is expected" % (what, g))
+        for m, item in enumerate(sub):
+            if not isinstance(item, (tuple, list)) or len(item) != 2:
+                raise ValueError("%s: members[%d][%d]: an (id, T 4x4) pair is expected" % (what, g, m))
+            where = "%s: members[%d][%d]" % (what, g, m)
+            ids.append(_keyframe_id(item[0], where))
+            try:
+                R, t = _pose_rt(item[1], where)
+            except (TypeError, ValueError) as e:
+                raise ValueError(str(e) if str(e).startswith(where) else "%s: a 4x4 pose is expected (%s)" % (where, e)) from None
+            if not (np.all(np.isfinite(R)) and np.all(np.isfinite(t))):
+                raise ValueError("%s: a finite pose is expected" % where)
+            poses.append(np.concatenate([R, t]))
+        off.append(len(ids))
+    return (np.asarray(off, np.int64), np.asarray(ids, np.int64).reshape(-1),
+            np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)))
+
+
 def _offsets(offsets, what):
     off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
     if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
@@ -610,6 +667,13 @@ def _update_dict(u):
 
 class DcregError(RuntimeError):
     pass
+
+
+class CapacityError(DcregError):
+    """a device output buffer is too small: nothing was written; out_offsets / info carry the sizes needed (the capacity protocol)"""
+    def __init__(self, msg, out_offsets, info):
+        super().__init__(msg)
+        self.out_offsets, self.info = out_offsets, info
 
 
 def load():
@@ -752,6 +816,19 @@ def load():
         for name in ("dcreg_set_target_outliers", "dcreg_set_target_outliers_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vpp, op, C.c_double, vi, oi]
         L.dcreg_target_remove_outliers.argtypes = [vp, op, oi]
+    if hasattr(L, "dcreg_keyframes_reset"):    # (absent from an older build loaded through DCREG_LIB for an A/B)
+        vpp, vi = C.POINTER(VoxelParams), C.POINTER(VoxelInfo)
+        L.dcreg_keyframes_reset.argtypes = [vp]
+        L.dcreg_keyframes_count.argtypes = [vp]
+        L.dcreg_keyframes_count.restype = C.c_int64
+        L.dcreg_keyframes_sizes.argtypes = [vp, C.c_int64, C.c_int64, i64p]
+        for name in ("dcreg_keyframes_add_clouds", "dcreg_keyframes_add_clouds_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64, i64p]
+        L.dcreg_keyframes_add_source.argtypes = [vp, i64p]
+        L.dcreg_keyframes_get.argtypes = [vp, C.c_int64, vp, C.c_int64]
+        for name in ("dcreg_keyframes_submaps", "dcreg_keyframes_submaps_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, i64p, i64p, dp, vpp, vp, C.c_int64, i64p, vi]
+        L.dcreg_set_target_keyframes.argtypes = [vp, C.c_int64, i64p, dp, vpp, C.c_double, vi]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1381,6 +1458,124 @@ class Context:
         info = OutlierInfo()
         self._check(self._L.dcreg_target_remove_outliers(self._h, C.byref(p), C.byref(info)), "dcreg_target_remove_outliers")
         return _outlier_info_dict(info)
+
+    # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
+    def keyframes_reset(self):
+        """dcreg_keyframes_reset: creates the store, or empties it"""
+        self._check(self._L.dcreg_keyframes_reset(self._h), "dcreg_keyframes_reset")
+
+    def keyframes_count(self):
+        return int(self._L.dcreg_keyframes_count(self._h))
+
+    def keyframes_sizes(self, first=0, n=None):
+        """dcreg_keyframes_sizes: the points of the keyframes [first, first + n) (n = None: to the end) -> [n] int64"""
+        first = _keyframe_id(first, "keyframes_sizes: first")
+        if n is None:
+            n = max(self.keyframes_count() - first, 0)
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or int(n) < 0:
+            raise ValueError("keyframes_sizes: n: an integer >= 0 is expected, got %r" % (n,))
+        out = np.zeros(max(int(n), 1), np.int64)
+        self._check(self._L.dcreg_keyframes_sizes(self._h, first, int(n), out.ctypes.data_as(C.POINTER(C.c_int64))), "dcreg_keyframes_sizes")
+        return out[:int(n)]
+
+    def keyframes_add(self, clouds):
+        """dcreg_keyframes_add_clouds: clouds = a list of [n_i, c] float32 arrays, or (xyz [N, c], offsets [n + 1]); every cloud becomes one
+        keyframe, stored bit for bit in input order (non-finite coordinates are refused).  -> the first new id (the others follow)"""
+        xyz, off, _ = _clouds(clouds, "keyframes_add")
+        first = C.c_int64(-1)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self._L.dcreg_keyframes_add_clouds(self._h, len(off) - 1, xyz.ctypes.data, off.ctypes.data_as(i64p), xyz.shape[1], C.byref(first)),
+                    "dcreg_keyframes_add_clouds")
+        return first.value
+
+    def keyframes_add_device(self, dev_ptr, offsets, stride):
+        """dcreg_keyframes_add_clouds_device: the clouds in device memory (stride floats per point, offsets on the host) -> the first new id"""
+        off = _offsets(offsets, "keyframes_add_device")
+        if int(stride) < 3:
+            raise ValueError("keyframes_add_device: a stride of at least 3 floats is expected, got %d" % int(stride))
+        first = C.c_int64(-1)
+        self._check(self._L.dcreg_keyframes_add_clouds_device(self._h, len(off) - 1, C.c_void_p(dev_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                              int(stride), C.byref(first)), "dcreg_keyframes_add_clouds_device")
+        return first.value
+
+    def keyframes_add_source(self):
+        """dcreg_keyframes_add_source: the current source, in its input order, becomes a keyframe (no second upload) -> its id"""
+        i = C.c_int64(-1)
+        self._check(self._L.dcreg_keyframes_add_source(self._h, C.byref(i)), "dcreg_keyframes_add_source")
+        return i.value
+
+    def keyframes_get(self, i):
+        """dcreg_keyframes_get: the stored points of keyframe i -> [n, 3] float32"""
+        i = _keyframe_id(i, "keyframes_get")
+        n = int(self.keyframes_sizes(i, 1)[0])
+        out = np.empty((max(n, 1), 3), np.float32)
+        self._check(self._L.dcreg_keyframes_get(self._h, i, out.ctypes.data, n), "dcreg_keyframes_get")
+        return out[:n]
+
+    def _member_points(self, off, ids, what):
+        """points per submap of checked member lists (the ids against the store's count)"""
+        sizes = self.keyframes_sizes()
+        if len(ids) and int(ids.max()) >= len(sizes):
+            raise ValueError("%s: keyframe id %d is not inside the store's [0, %d)" % (what, int(ids.max()), len(sizes)))
+        per = np.concatenate([[0], np.cumsum(sizes[ids])]).astype(np.int64)
+        if int(per[-1]) >= KEYFRAME_MAX_POINTS:
+            raise ValueError("%s: fewer than 2^31 - 1 member points are expected in one call, got %d" % (what, int(per[-1])))
+        return per[off]
+
+    def keyframe_submaps(self, members, leaf=None, mode="centroid", min_points=1):
+        """dcreg_keyframes_submaps: members = a list (one per submap) of lists of (keyframe id, T 4x4); every member's stored points moved by
+        its pose on the device, a submap = its members one after the other; leaf given (an edge, three, or voxel_params(...)): each submap
+        through the voxel pass (include/dcreg.h has the rules).  -> (a list of [m, 3] float32 arrays, dict n_in / n_finite / n_voxels / n_out)"""
+        v = _voxel_block(leaf, mode, min_points, "keyframe_submaps")
+        off, ids, poses = _members(members, "keyframe_submaps")
+        cap = int(self._member_points(off, ids, "keyframe_submaps")[-1])
+        n = len(off) - 1
+        out = np.empty((max(cap, 1), 3), np.float32)
+        out_off = np.zeros(n + 1, np.int64)
+        info = VoxelInfo()
+        i64p, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        self._check(self._L.dcreg_keyframes_submaps(self._h, n, off.ctypes.data_as(i64p), ids.ctypes.data_as(i64p), poses.ctypes.data_as(dp),
+                                                    C.byref(v) if v is not None else None, out.ctypes.data, cap, out_off.ctypes.data_as(i64p),
+                                                    C.byref(info)), "dcreg_keyframes_submaps")
+        return [out[out_off[k]:out_off[k + 1]] for k in range(n)], _voxel_info_dict(info)
+
+    def keyframe_submaps_device(self, members, dev_out_ptr, capacity, leaf=None, mode="centroid", min_points=1):
+        """dcreg_keyframes_submaps_device: the output to the device buffer dev_out_ptr (3 floats per point, capacity points), written on the
+        context's stream.  A capacity the output does not fit raises CapacityError with nothing written; its out_offsets / info carry the
+        sizes needed (the member points in all, from keyframes_sizes, are always enough).  -> (out_offsets [n + 1], info dict)"""
+        v = _voxel_block(leaf, mode, min_points, "keyframe_submaps_device")
+        off, ids, poses = _members(members, "keyframe_submaps_device")
+        if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or int(capacity) < 0:
+            raise ValueError("keyframe_submaps_device: a capacity >= 0 is expected, got %r" % (capacity,))
+        n = len(off) - 1
+        out_off = np.zeros(n + 1, np.int64)
+        info = VoxelInfo()
+        i64p, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        rc = self._L.dcreg_keyframes_submaps_device(self._h, n, off.ctypes.data_as(i64p), ids.ctypes.data_as(i64p), poses.ctypes.data_as(dp),
+                                                    C.byref(v) if v is not None else None, C.c_void_p(dev_out_ptr or None), int(capacity),
+                                                    out_off.ctypes.data_as(i64p), C.byref(info))
+        if rc != OK and int(out_off[-1]) > int(capacity):
+            raise CapacityError("dcreg_keyframes_submaps_device: the output holds %d points, the capacity is %d" % (int(out_off[-1]), int(capacity)),
+                                out_off, _voxel_info_dict(info))
+        self._check(rc, "dcreg_keyframes_submaps_device")
+        return out_off, _voxel_info_dict(info)
+
+    def set_target_keyframes(self, members, search_radius, leaf=None, mode="centroid", min_points=1):
+        """dcreg_set_target_keyframes: members = a list of (keyframe id, T 4x4); the map becomes bitwise set_target (leaf given:
+        set_target_voxel) of keyframe_submaps([members], ...) - after a pose-graph update, or as a local map of the nearest keyframes; the
+        points never leave the device.  -> dict n_in / n_finite / n_voxels / n_out"""
+        v = _voxel_block(leaf, mode, min_points, "set_target_keyframes")
+        off, ids, poses = _members([members], "set_target_keyframes")
+        if len(ids) == 0:
+            raise ValueError("set_target_keyframes: members: at least one (id, T 4x4) is expected")
+        if not np.isfinite(float(search_radius)):
+            raise ValueError("set_target_keyframes: a finite search_radius is expected, got %r" % (search_radius,))
+        info = VoxelInfo()
+        i64p, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+        self._check(self._L.dcreg_set_target_keyframes(self._h, len(ids), ids.ctypes.data_as(i64p), poses.ctypes.data_as(dp),
+                                                       C.byref(v) if v is not None else None, float(search_radius), C.byref(info)),
+                    "dcreg_set_target_keyframes")
+        return _voxel_info_dict(info)
 
     def index_info(self):
         info = IndexInfo()

@@ -24,6 +24,7 @@ SOURCES = [
     "device/deskew.hip",
     "device/places.hip",
     "device/outliers.hip",
+    "device/keyframes.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

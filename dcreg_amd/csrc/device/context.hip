@@ -380,7 +380,13 @@ int refuse_in_flight(dcreg_ctx *c) {
 // host, no stream synchronise in dcreg_set_source
 static bool small_host_frame(int64_t n, int64_t stride) { return n <= 65536 && n * stride <= (int64_t)1 << 20; }
 
-int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw, DeskewRun *dsk) {
+int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw, DeskewRun *dsk,
+                 const GatherRun *gat) {
+    if (gat) {                 // the records are gathered from the keyframe store (keyframes.hip: k_kf_gather packs)
+        if (n != gat->n || n < 0 || n >= ((int64_t)1 << 31)) { c->fail("invalid gather arguments"); return DCREG_E_INVALID; }
+        if (raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+        return n == 0 ? DCREG_OK : gather_queue(c, *gat, raw.data(), nullptr);
+    }
     if (!xyz || n < 0 || stride < 3) { c->fail("invalid cloud arguments"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("cloud too large (%lld points)", (long long)n); return DCREG_E_INVALID; }
     if (!(dsk && dsk->out3) && raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
@@ -2307,14 +2313,15 @@ static void voxel_info(dcreg_voxel_info *info, const VoxelResult &r) {
     if (info) { info->n_in = r.n_in; info->n_finite = r.n_finite; info->n_voxels = r.n_voxels; info->n_out = r.n_out; }
 }
 static int set_cloud_voxel(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_voxel_params *p, bool target,
-                           double radius_hint, dcreg_voxel_info *info, DeskewRun *dsk = nullptr, dcreg_deskew_info *dinfo = nullptr) {
+                           double radius_hint, dcreg_voxel_info *info, DeskewRun *dsk = nullptr, dcreg_deskew_info *dinfo = nullptr,
+                           const GatherRun *gat = nullptr) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (n <= 0) { c->fail("%s cloud is null or empty", target ? "target" : "measure"); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t off[2] = {0, n};
     VoxelResult r;
-    int rc = voxel_pass(c, 1, xyz, off, stride, on_device, p, true, r, dsk);
+    int rc = voxel_pass(c, 1, xyz, off, stride, on_device, p, true, r, dsk, gat);
     if (rc) return rc;
     voxel_info(info, r);
     if (dsk) deskew_info(*dsk, n, dinfo);
@@ -2706,3 +2713,18 @@ int dcreg_kernel_time(dcreg_ctx *c, double *ms_total, int64_t *launches, int res
 }
 
 }  // extern "C"
+
+// dcreg_set_target_keyframes (keyframes.hip has checked the members): the gather stands where the upload of set_target / set_cloud_voxel stands
+int dcreg::set_target_gathered(dcreg_ctx *c, const GatherRun &g, const dcreg_voxel_params *p, double radius_hint, dcreg_voxel_info *info) {
+    if (p) return set_cloud_voxel(c, nullptr, g.n, 3, true, p, true, radius_hint, info, nullptr, nullptr, &g);
+    if (g.n <= 0) { c->fail("target cloud is null or empty"); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = upload_cloud(c, nullptr, g.n, 3, true, c->d_aligned, nullptr, &g);
+    if (rc) return rc;
+    double box[6];
+    rc = device_bounds(c, c->d_aligned.data(), g.n, box, box + 3);
+    if (rc) return rc;
+    for (int a = 0; a < 6; ++a) if (!std::isfinite(box[a])) { c->fail("target cloud has non-finite coordinates"); return DCREG_E_INVALID; }
+    if (info) { info->n_in = info->n_finite = info->n_out = g.n; info->n_voxels = 0; }
+    return target_commit(c, g.n, box, radius_hint);
+}

@@ -114,6 +114,12 @@ struct PathSeg {
     double G[12];
     double s0, len;
 };
+// one non-empty member of a keyframe gather on the device (keyframes.hip k_kf_gather): its first output point, its first point in the
+// store, and its pose (R row-major, t) - 104 B
+struct KfMember {
+    uint32_t start, src;
+    double pose[12];
+};
 // the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i) - the segments of voxel.hip and deskew.hip
 __device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
     int lo = 0, hi = n_clouds;
@@ -352,6 +358,19 @@ struct dcreg_ctx {
         IndexSet idx;
     };
     OutlierBufs outl;
+    // keyframe store (keyframes.hip: dcreg_keyframes_*, dcreg_set_target_keyframes).  The store: the points of all keyframes back to back,
+    // 3 floats each, in one growing array (capacity doubles), and on the host where each keyframe starts (count + 1 entries once `ready`); it
+    // lives until dcreg_keyframes_reset or the context's end, whatever happens to the target and the source.  The rest is scratch of one
+    // call: the member records of a gather, the raw output of a submap call to host memory, the non-finite flag of an add
+    struct KeyframeBufs {
+        bool ready = false;                                  // dcreg_keyframes_reset was called
+        DevBuf<float> xyz;
+        std::vector<int64_t> off;
+        DevBuf<dcreg::KfMember> members;
+        DevBuf<float> out;
+        DevBuf<uint32_t> flag;
+    };
+    KeyframeBufs kf;
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
@@ -532,8 +551,16 @@ int deskew_reserve(dcreg_ctx *c, const DeskewRun &d);       // the call's device
 int deskew_queue(dcreg_ctx *c, const float *src, int64_t n, int64_t stride, DeskewRun &d, float4 *out4);
 int deskew_readback(dcreg_ctx *c, DeskewRun &d);
 void deskew_info(const DeskewRun &d, int64_t n_in, dcreg_deskew_info *info);
+// keyframes.hip: one call's gather of keyframe members (checked on the host by the caller: ids, poses, sizes).  upload_cloud given one has
+// the n packed records written by k_kf_gather from the store instead of k_pack from a cloud (xyz is not read); gather_queue with out3 set
+// writes 3 floats per point there instead.  Empty members are left out of `members`.
+struct GatherRun {
+    std::vector<KfMember> members;
+    int64_t n = 0;                         // points of the call
+};
+int gather_queue(dcreg_ctx *c, const GatherRun &g, float4 *out4, float *out3);
 int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw,
-                 DeskewRun *dsk = nullptr);   // context.hip
+                 DeskewRun *dsk = nullptr, const GatherRun *gat = nullptr);   // context.hip
 // voxel.hip: the voxel-grid pass of n_clouds clouds (offsets off[n_clouds + 1], host memory) - checks everything before it writes; the output
 // points go to c->vox.out (3 floats each) or, packed, to c->d_aligned as k_pack packs a cloud (one cloud only).  Ends with ONE readback of
 // the per-cloud counts and the bounds of the output.  dsk: the clouds are deskewed while they are packed (its counts come back with the
@@ -544,7 +571,7 @@ struct VoxelResult {
     double mn[3] = {}, mx[3] = {};         // bounds of the output points (as k_bounds takes them)
 };
 int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
-               bool packed, VoxelResult &r, DeskewRun *dsk = nullptr);
+               bool packed, VoxelResult &r, DeskewRun *dsk = nullptr, const GatherRun *gat = nullptr);
 // voxel.hip: dcreg_voxel_downsample* (and dcreg_deskew* with a voxel block): the pass, then the copy of the output to the caller
 int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
                         float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info, DeskewRun *dsk = nullptr);
@@ -567,4 +594,7 @@ void outlier_info(dcreg_outlier_info *info, const OutlierResult &r);
 int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_out);
 // flag_s[p] = the keep flag of the map point at sorted position p (n + 1 entries, the last 0)
 int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s);
+// context.hip: the gathered points become the target as dcreg_set_target (p == null: a non-finite point refuses) or dcreg_set_target_voxel
+// takes a cloud - packed into c->d_aligned by the gather or by the voxel pass behind it, then the commit of the plain calls
+int set_target_gathered(dcreg_ctx *c, const GatherRun &g, const dcreg_voxel_params *p, double radius_hint, dcreg_voxel_info *info);
 }  // namespace dcreg

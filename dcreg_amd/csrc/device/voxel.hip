@@ -10,6 +10,7 @@
 //   k_vox_reduce   ONE lane per voxel: count, min_points, the sequential double sum (or the first point) - exact and reproducible
 //   scan + k_vox_write   compaction, per-cloud counts, bounds of the output
 //   (readback)     counts, bounds: the only one at the end of the call
+// The packed points come from upload_cloud: k_pack, the deskew packs (DeskewRun) or the keyframe gather (GatherRun, keyframes.hip).
 // A voxel's result depends on its own points only: where its cloud sits in the call and how the launches are cut never enter it.
 #include <algorithm>
 #include <cmath>
@@ -283,7 +284,7 @@ int bits_for(int64_t v) { int b = 0; while (b < 63 && ((int64_t)1 << b) <= v) ++
 }  // namespace
 
 int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
-               bool packed, VoxelResult &r, DeskewRun *dsk) {
+               bool packed, VoxelResult &r, DeskewRun *dsk, const GatherRun *gat) {
     // ---- everything the host can check, before anything is queued
     if (!p) { c->fail("null voxel parameters"); return DCREG_E_INVALID; }
     for (int a = 0; a < 3; ++a)
@@ -295,7 +296,7 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
         if (off[s + 1] < off[s]) { c->fail("cloud offsets decrease at cloud %d", s); return DCREG_E_INVALID; }
     const int64_t n = n_clouds > 0 ? off[n_clouds] : 0;
     if (n >= ((int64_t)1 << 31) - 1) { c->fail("too many points for one voxel pass (%lld)", (long long)n); return DCREG_E_INVALID; }
-    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (n > 0 && !xyz && !gat) { c->fail("null point buffer"); return DCREG_E_INVALID; }      // (gat: the points come from the keyframe store)
     if (packed && n_clouds != 1) { c->fail("a packed voxel output holds one cloud"); return DCREG_E_INVALID; }
     const int min_points = std::max(p->min_points, 1);
     r = VoxelResult();
@@ -314,7 +315,7 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
         c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
     if (packed ? c->d_aligned.ensure(c, (size_t)n) : B.out.ensure(c, (size_t)(3 * n))) return DCREG_E_NOMEM;
-    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts, dsk);
+    int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts, dsk, gat);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), n_clouds);

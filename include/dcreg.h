@@ -30,6 +30,11 @@
  *                                                                                   dcreg_set_source_deskew[_device]
  *       ... along a sampled trajectory, through a sensor-to-body extrinsic       -> dcreg_deskew_path[_device],
  *                                                                                   dcreg_set_source_deskew_path[_device]
+ *   keyframes (not in the reference: the clouds a mapper has registered, kept on the device by index)
+ *       the store                                                                -> dcreg_keyframes_reset / _count / _sizes / _get,
+ *                                                                                   dcreg_keyframes_add_clouds[_device], _add_source
+ *       submaps assembled from (keyframe id, pose) members                       -> dcreg_keyframes_submaps[_device]
+ *       ... as the map: a rebuild after a pose-graph update, a local map         -> dcreg_set_target_keyframes
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -622,6 +627,80 @@ int dcreg_set_target_outliers_device(dcreg_ctx *, const float *d_xyz, int64_t n,
  * drops what dcreg_set_target drops; a call that removes nothing changes nothing (the neighbour states stay warm); a call that would
  * remove every point is refused (DCREG_E_INVALID); refusals leave everything as it was.  DCREG_E_STATE: no target. */
 int dcreg_target_remove_outliers(dcreg_ctx *, const dcreg_outlier_params *, dcreg_outlier_info *info);
+
+/* ---------------- keyframe store: submaps and map rebuilds from poses ----------------
+ * The clouds a mapper registers are kept on the device by index, beside the map and the place database (which holds their descriptors: a
+ * caller that adds keyframe and place in lockstep - dcreg_places_add_source, dcreg_keyframes_add_source - has one index for both).  A
+ * SUBMAP is an ordered list of (keyframe id, pose) members: each member's points are moved by its pose on the device, the submap's points
+ * are the concatenation of its members, optionally through the voxel pass.  Poses are arguments of every assembling call and are never
+ * stored - the caller owns the pose graph, and its poses change.  Every output is bitwise the numpy reference of tests/keyframes_ref.py.
+ *
+ * Store.  A keyframe is a cloud of n >= 0 points, 3 floats each, stored bit for bit in input order.  Ids are 0, 1, 2, ... in the order
+ * added; the clouds of one dcreg_keyframes_add_clouds call get consecutive ids from *first_id.  The store needs no target; it is not
+ * dropped or changed by dcreg_set_target*, dcreg_set_source*, the map updates, the registration calls, the places calls or the filter
+ * calls.  It is emptied only by dcreg_keyframes_reset and freed with the context; single keyframes cannot be removed (as for places).
+ *
+ * Add.  dcreg_keyframes_add_clouds takes clouds as dcreg_voxel_downsample takes them and has its cloud refusals (offsets, stride, null
+ * buffers), plus dcreg_set_source's refusal of non-finite coordinates in ANY cloud of the call: raw sweeps go through the voxel or deskew
+ * calls first, whose output is what this call takes with stride 3.  Empty clouds are accepted and become empty keyframes.  A refused call
+ * or a failed allocation (DCREG_E_NOMEM) leaves the store as it was, bit for bit.  dcreg_keyframes_add_source adds the current source in
+ * its INPUT order - the copy dcreg_target_insert_source reads - without a second upload.
+ *
+ * Member transform.  member_poses[12 m ..] = R[9] row-major, then t[3].  A stored point p becomes
+ *     q_a = (float)(R[a][0] * (double)p_x + R[a][1] * (double)p_y + R[a][2] * (double)p_z + t[a]),
+ * the sum evaluated left to right, every product and sum rounded to double, no contraction - the transform of dcreg_target_insert (an
+ * identity pose therefore returns the stored values, a stored -0.0 as +0.0).  Poses must be finite; they are not checked for being
+ * rotations, as in dcreg_target_insert.  A submap in a local frame (a candidate keyframe's own frame, or a frame near a vehicle far from
+ * the origin) is the caller's pre-composed relative poses: the library composes nothing on the host, so the 12 numbers given fix the result.
+ *
+ * Submap.  Submap g has the members [member_offsets[g], member_offsets[g + 1]) (n_submaps + 1 offsets, from 0).  Its point sequence is
+ * member after member in list order, each member's points in stored order.  An id may repeat within and across submaps; a submap may have
+ * no members, and a member may be an empty keyframe.
+ *
+ * Output.  voxel == NULL: that sequence, 3 floats per point, submap after submap, submap g from out_offsets[g] (n_submaps + 1 entries);
+ * vinfo: n_in = n_finite = n_out = the points written, n_voxels = 0.  voxel != NULL: bitwise dcreg_voxel_downsample of the n_submaps
+ * sequences taken as n_clouds clouds - each submap keyed on its own, centroid sums in sequence order - so (out_xyz, out_offsets) is what
+ * dcreg_register_pairs takes as targets with stride 3.  The capacity protocol is dcreg_voxel_downsample's: the member points in all are
+ * always enough; a capacity the output does not fit returns DCREG_E_INVALID with out_offsets and vinfo filled and nothing written.  A
+ * transformed coordinate that overflows float is non-finite, and what consumes it treats it as a non-finite input point: the voxel pass
+ * drops it (counted in n_in - n_finite), the raw form writes it, the raw form of dcreg_set_target_keyframes refuses the call.
+ *
+ * dcreg_set_target_keyframes leaves the context bitwise as dcreg_set_target of the one-submap output of dcreg_keyframes_submaps with the
+ * same arguments leaves it (with a voxel block: dcreg_set_target_voxel); the points go from the gather to the build on the device.  It
+ * drops what dcreg_set_target drops; the store is untouched.  A refused call - the refusals below, no member, no point left, a non-finite
+ * point in the raw form - leaves map and index as they were.
+ *
+ * Refusals.  DCREG_E_INVALID, nothing written: null arrays, negative counts, offsets that do not start at 0 or decrease, an id outside
+ * [0, count), a non-finite pose, 2^31 - 1 or more member points in one call, the voxel pass's own refusals, an add that would take the
+ * store to 2^32 points or more.  DCREG_E_STATE: a linearisation in flight (every call but _count); any call but _reset / _count before
+ * the first _reset; _add_source without a source.  Every call that queues work waits for the stream before it returns.  A result depends on
+ * the stored bits, the member lists, the poses and the voxel block only - not on the launch configuration, on what else the store or the
+ * context holds, or on how many submaps share the call.
+ *
+ * Device memory: 12 B per stored point in one growing array whose capacity doubles - the new block is filled by a device-to-device copy
+ * before the old one is released, so a growth peaks at old + new block, at most three times the bytes stored - and a host vector of int64
+ * offsets.  Per call 104 B per non-empty member of scratch (output start, store offset, pose), uploaded in one copy; the raw form to host
+ * memory stages its 12 B per point; the voxel form has the voxel pass's scratch. */
+int dcreg_keyframes_reset(dcreg_ctx *);                       /* creates the store, or empties it and frees its points */
+int64_t dcreg_keyframes_count(const dcreg_ctx *);             /* 0 before the first reset */
+/* n_points[k] = the points of keyframe first + k, k < n; [first, first + n) must lie inside [0, count] */
+int dcreg_keyframes_sizes(const dcreg_ctx *, int64_t first, int64_t n, int64_t *n_points);
+/* first_id may be NULL.  _device: d_xyz is read as dcreg_voxel_downsample_device reads it */
+int dcreg_keyframes_add_clouds(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, int64_t *first_id);
+int dcreg_keyframes_add_clouds_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                      int64_t *first_id);
+int dcreg_keyframes_add_source(dcreg_ctx *, int64_t *id);    /* id may be NULL */
+/* the stored points of one keyframe to host memory; DCREG_E_INVALID when capacity_points is below its size */
+int dcreg_keyframes_get(dcreg_ctx *, int64_t id, float *xyz_out, int64_t capacity_points);
+int dcreg_keyframes_submaps(dcreg_ctx *, int n_submaps, const int64_t *member_offsets, const int64_t *member_ids, const double *member_poses,
+                            const dcreg_voxel_params *voxel, float *out_xyz, int64_t capacity_points, int64_t *out_offsets,
+                            dcreg_voxel_info *vinfo);
+/* d_out_xyz is device memory, written on the ctx's stream (the raw form writes it straight from the gather) */
+int dcreg_keyframes_submaps_device(dcreg_ctx *, int n_submaps, const int64_t *member_offsets, const int64_t *member_ids,
+                                   const double *member_poses, const dcreg_voxel_params *voxel, float *d_out_xyz, int64_t capacity_points,
+                                   int64_t *out_offsets, dcreg_voxel_info *vinfo);
+int dcreg_set_target_keyframes(dcreg_ctx *, int64_t n_members, const int64_t *member_ids, const double *member_poses,
+                               const dcreg_voxel_params *voxel, double search_radius_hint, dcreg_voxel_info *vinfo);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
