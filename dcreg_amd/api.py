@@ -155,6 +155,8 @@ EXPORTS = [
     "dcreg_set_source_outliers_device", "dcreg_set_target_outliers", "dcreg_set_target_outliers_device", "dcreg_target_remove_outliers",
     "dcreg_keyframes_reset", "dcreg_keyframes_count", "dcreg_keyframes_sizes", "dcreg_keyframes_add_clouds", "dcreg_keyframes_add_clouds_device",
     "dcreg_keyframes_add_source", "dcreg_keyframes_get", "dcreg_keyframes_submaps", "dcreg_keyframes_submaps_device", "dcreg_set_target_keyframes",
+    "dcreg_default_visibility_params", "dcreg_keyframes_range_images", "dcreg_keyframes_range_images_device", "dcreg_visibility_filter",
+    "dcreg_visibility_filter_device", "dcreg_target_remove_dynamic",
 ]
 
 _lib = None
@@ -627,6 +629,109 @@ def _members(members, what):
             np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 12)))
 
 
+class VisibilityParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("elev_min", C.c_double), ("elev_max", C.c_double), ("min_range", C.c_double),
+                ("max_range", C.c_double), ("margin_abs", C.c_double), ("margin_rel", C.c_double), ("window", C.c_int), ("min_votes", C.c_int),
+                ("min_ratio", C.c_double)]
+
+
+class VisibilityInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_observed", C.c_int64), ("n_flagged", C.c_int64), ("n_out", C.c_int64),
+                ("n_members", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_visibility_params": VisibilityParams, "dcreg_visibility_info": VisibilityInfo})
+VISIBILITY_MAX_ROWS, VISIBILITY_MAX_COLS, VISIBILITY_MAX_WINDOW = 256, 4096, 3
+
+
+def _check_visibility_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_visibility_params block"""
+    if not isinstance(p, VisibilityParams):
+        raise ValueError("%s: visibility_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not (1 <= p.rows <= VISIBILITY_MAX_ROWS and 1 <= p.cols <= VISIBILITY_MAX_COLS):
+        raise ValueError("%s: rows in [1, %d] and cols in [1, %d] are expected, got %d x %d"
+                         % (what, VISIBILITY_MAX_ROWS, VISIBILITY_MAX_COLS, p.rows, p.cols))
+    if not (np.isfinite(p.elev_min) and np.isfinite(p.elev_max) and -0.5 * np.pi <= p.elev_min < p.elev_max <= 0.5 * np.pi):
+        raise ValueError("%s: elev_min < elev_max inside [-pi/2, pi/2] is expected, got %r, %r" % (what, p.elev_min, p.elev_max))
+    if not (np.isfinite(p.min_range) and np.isfinite(p.max_range) and 0.0 <= p.min_range < p.max_range):
+        raise ValueError("%s: a finite 0 <= min_range < max_range is expected, got %r, %r" % (what, p.min_range, p.max_range))
+    if not (np.isfinite(p.margin_abs) and p.margin_abs >= 0.0):
+        raise ValueError("%s: a finite margin_abs >= 0 is expected, got %r" % (what, p.margin_abs))
+    if not (np.isfinite(p.margin_rel) and p.margin_rel >= 0.0):
+        raise ValueError("%s: a finite margin_rel >= 0 is expected, got %r" % (what, p.margin_rel))
+    if not 0 <= p.window <= VISIBILITY_MAX_WINDOW:
+        raise ValueError("%s: a window in [0, %d] is expected, got %d" % (what, VISIBILITY_MAX_WINDOW, p.window))
+    if p.min_votes < 1:
+        raise ValueError("%s: min_votes >= 1 is expected, got %d" % (what, p.min_votes))
+    if not 0.0 <= p.min_ratio <= 1.0:
+        raise ValueError("%s: a min_ratio in [0, 1] is expected, got %r" % (what, p.min_ratio))
+
+
+def visibility_params(rows=64, cols=1024, elev_min=-0.125 * np.pi, elev_max=0.125 * np.pi, min_range=0.5, max_range=80.0, margin_abs=0.2,
+                      margin_rel=0.01, window=1, min_votes=2, min_ratio=0.0):
+    """dcreg_visibility_params: the range image (rows x cols over the elevations [elev_min, elev_max] radians and the ranges
+    [min_range, max_range) metres), the margins of the see-through test (range > r + margin_abs + margin_rel r), the pixel window whose
+    minimum is compared, and the decision (through >= min_votes and through >= min_ratio x observed); include/dcreg.h has the rule"""
+    for name, v in (("rows", rows), ("cols", cols), ("window", window), ("min_votes", min_votes)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("visibility_params: %s: an integer is expected, got %r" % (name, v))
+    p = VisibilityParams()
+    p.rows, p.cols, p.window, p.min_votes = int(rows), int(cols), int(window), int(min_votes)
+    p.elev_min, p.elev_max, p.min_range, p.max_range = float(elev_min), float(elev_max), float(min_range), float(max_range)
+    p.margin_abs, p.margin_rel, p.min_ratio = float(margin_abs), float(margin_rel), float(min_ratio)
+    _check_visibility_params(p, "visibility_params")
+    return p
+
+
+def _visibility_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_observed": i.n_observed, "n_flagged": i.n_flagged, "n_out": i.n_out,
+            "n_members": i.n_members}
+
+
+def _keyframe_ids(ids, what):
+    """[n] int64 of a sequence of keyframe ids, checked as a whole (no loop over the ids)"""
+    a = np.asarray(ids)
+    if a.dtype == object or a.ndim != 1 and a.size:
+        raise ValueError("%s: keyframe ids: a 1-D sequence of integers is expected" % what)
+    a = a.reshape(-1)
+    if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("%s: keyframe ids are integers, got %s" % (what, a.dtype))
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if a.size and int(a.min()) < 0:
+        raise ValueError("%s: keyframe ids are >= 0, got %d" % (what, int(a.min())))
+    return a
+
+
+def _vote_members(members, what):
+    """(ids [M] int64, poses [M, 12] float64 = R row-major then t) of the members of a visibility call: an (ids [M], T [M, 4, 4]) pair of
+    arrays, or a list of (keyframe id, T 4x4) as set_target_keyframes takes it.  Checked with numpy over all members at once."""
+    if isinstance(members, (str, bytes)) or not hasattr(members, "__len__"):
+        raise ValueError("%s: members: a list of (id, T 4x4) or an (ids [M], T [M, 4, 4]) pair is expected" % what)
+    if isinstance(members, tuple) and len(members) == 2 and np.ndim(members[0]) == 1:
+        ids, Ts = members
+    elif len(members) == 0:
+        ids, Ts = np.zeros(0, np.int64), np.zeros((0, 4, 4))
+    else:
+        try:
+            ok = all(len(m) == 2 for m in members)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError("%s: members: a list of (id, T 4x4) or an (ids [M], T [M, 4, 4]) pair is expected" % what)
+        ids, Ts = zip(*members)
+    ids = _keyframe_ids(ids, "%s: members" % what)
+    try:
+        Ts = np.asarray(Ts, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: members: 4x4 poses are expected" % what) from None
+    if Ts.shape != (len(ids), 4, 4):
+        raise ValueError("%s: members: %d poses of shape 4x4 are expected, got shape %s" % (what, len(ids), Ts.shape))
+    poses = np.ascontiguousarray(np.concatenate([Ts[:, :3, :3].reshape(-1, 9), Ts[:, :3, 3]], 1))
+    if not np.all(np.isfinite(poses)):
+        raise ValueError("%s: members: finite poses are expected (member %d)" % (what, int(np.argmin(np.isfinite(poses).all(1)))))
+    return ids, poses
+
+
 def _offsets(offsets, what):
     off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
     if len(off) < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
@@ -829,6 +934,14 @@ def load():
         for name in ("dcreg_keyframes_submaps", "dcreg_keyframes_submaps_device"):
             getattr(L, name).argtypes = [vp, C.c_int, i64p, i64p, dp, vpp, vp, C.c_int64, i64p, vi]
         L.dcreg_set_target_keyframes.argtypes = [vp, C.c_int64, i64p, dp, vpp, C.c_double, vi]
+    if hasattr(L, "dcreg_visibility_filter"):  # (absent from an older build loaded through DCREG_LIB for an A/B)
+        sp, si = C.POINTER(VisibilityParams), C.POINTER(VisibilityInfo)
+        L.dcreg_default_visibility_params.argtypes = [sp]
+        for name in ("dcreg_keyframes_range_images", "dcreg_keyframes_range_images_device"):
+            getattr(L, name).argtypes = [vp, C.c_int64, i64p, sp, vp]
+        for name in ("dcreg_visibility_filter", "dcreg_visibility_filter_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, i64p, dp, sp, vp, C.c_int64, i64p, vp, vp, vp, si]
+        L.dcreg_target_remove_dynamic.argtypes = [vp, C.c_int64, i64p, dp, sp, si]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1576,6 +1689,94 @@ class Context:
                                                        C.byref(v) if v is not None else None, float(search_radius), C.byref(info)),
                     "dcreg_set_target_keyframes")
         return _voxel_info_dict(info)
+
+    # ---- moving objects (include/dcreg.h: visibility votes from keyframes): range images of stored keyframes, votes of (id, pose) members
+    def _ids_in_store(self, ids, what):
+        count = self.keyframes_count()
+        if len(ids) and int(ids.max()) >= count:
+            raise ValueError("%s: keyframe id %d is not inside the store's [0, %d)" % (what, int(ids.max()), count))
+
+    def keyframe_range_images(self, ids, params=None):
+        """dcreg_keyframes_range_images: the range images of the stored keyframes ids under params (visibility_params(...); None = the
+        defaults) -> [n, rows, cols] float32, +inf where a pixel holds no point"""
+        p = params if params is not None else visibility_params()
+        _check_visibility_params(p, "keyframe_range_images")
+        ids = _keyframe_ids(ids, "keyframe_range_images")
+        self._ids_in_store(ids, "keyframe_range_images")
+        out = np.empty((len(ids), p.rows, p.cols), np.float32)
+        self._check(self._L.dcreg_keyframes_range_images(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p),
+                                                         out.ctypes.data if len(ids) else None), "dcreg_keyframes_range_images")
+        return out
+
+    def keyframe_range_images_device(self, ids, dev_out_ptr, params=None):
+        """dcreg_keyframes_range_images_device: the images to the device buffer dev_out_ptr (len(ids) x rows x cols floats)"""
+        p = params if params is not None else visibility_params()
+        _check_visibility_params(p, "keyframe_range_images_device")
+        ids = _keyframe_ids(ids, "keyframe_range_images_device")
+        self._ids_in_store(ids, "keyframe_range_images_device")
+        self._check(self._L.dcreg_keyframes_range_images_device(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(p),
+                                                                C.c_void_p(dev_out_ptr or None)), "dcreg_keyframes_range_images_device")
+
+    def visibility_filter(self, xyz, members, params=None, want_mask=True, want_counts=True):
+        """dcreg_visibility_filter: the points of one cloud in the map frame ([n, c] float32, x y z first; non-finite points are dropped)
+        that the members - a list of (keyframe id, T 4x4 sensor -> map), or an (ids [M], T [M, 4, 4]) pair - do not look through
+        (include/dcreg.h has the rule), in input order.  -> (kept [m, 3] float32, keep mask [n] bool or None, through [n] int32 or None,
+        observed [n] int32 or None, dict n_in / n_finite / n_observed / n_flagged / n_out / n_members)"""
+        p = params if params is not None else visibility_params()
+        _check_visibility_params(p, "visibility_filter")
+        a = _points(xyz, "visibility_filter")
+        ids, poses = _vote_members(members, "visibility_filter")
+        self._ids_in_store(ids, "visibility_filter")
+        n = a.shape[0]
+        out = np.empty((max(n, 1), 3), np.float32)
+        mask = np.zeros(max(n, 1), np.uint8) if want_mask else None
+        through = np.zeros(max(n, 1), np.int32) if want_counts else None
+        observed = np.zeros(max(n, 1), np.int32) if want_counts else None
+        n_out = C.c_int64(0)
+        info = VisibilityInfo()
+        self._check(self._L.dcreg_visibility_filter(self._h, a.ctypes.data, n, a.shape[1], len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    _dp(poses), C.byref(p), out.ctypes.data, n, C.byref(n_out),
+                                                    mask.ctypes.data if want_mask else None, through.ctypes.data if want_counts else None,
+                                                    observed.ctypes.data if want_counts else None, C.byref(info)), "dcreg_visibility_filter")
+        return (out[:n_out.value], mask[:n].astype(bool) if want_mask else None, through[:n] if want_counts else None,
+                observed[:n] if want_counts else None, _visibility_info_dict(info))
+
+    def visibility_filter_device(self, dev_ptr, n, stride, members, dev_out_ptr, capacity, params=None, dev_mask_ptr=0, dev_through_ptr=0,
+                                 dev_observed_ptr=0):
+        """dcreg_visibility_filter_device: the cloud in device memory, the kept points to dev_out_ptr (3 floats per point, capacity points),
+        optionally the uint8 mask and the int32 counts to device buffers of n entries.  A capacity the output does not fit raises
+        CapacityError with nothing written; its info carries the size needed.  -> (n_out, info dict)"""
+        p = params if params is not None else visibility_params()
+        _check_visibility_params(p, "visibility_filter_device")
+        _check_device_cloud(n, stride, "visibility_filter_device")
+        if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or int(capacity) < 0:
+            raise ValueError("visibility_filter_device: a capacity >= 0 is expected, got %r" % (capacity,))
+        ids, poses = _vote_members(members, "visibility_filter_device")
+        self._ids_in_store(ids, "visibility_filter_device")
+        n_out = C.c_int64(-1)
+        info = VisibilityInfo()
+        rc = self._L.dcreg_visibility_filter_device(self._h, C.c_void_p(dev_ptr or None), int(n), int(stride), len(ids),
+                                                    ids.ctypes.data_as(C.POINTER(C.c_int64)), _dp(poses), C.byref(p), C.c_void_p(dev_out_ptr or None),
+                                                    int(capacity), C.byref(n_out), C.c_void_p(dev_mask_ptr or None),
+                                                    C.c_void_p(dev_through_ptr or None), C.c_void_p(dev_observed_ptr or None), C.byref(info))
+        if rc != OK and n_out.value > int(capacity):
+            raise CapacityError("dcreg_visibility_filter_device: the output holds %d points, the capacity is %d" % (n_out.value, int(capacity)),
+                                None, _visibility_info_dict(info))
+        self._check(rc, "dcreg_visibility_filter_device")
+        return n_out.value, _visibility_info_dict(info)
+
+    def remove_dynamic(self, members, params=None):
+        """dcreg_target_remove_dynamic: the points of the resident map that the members look through are removed in place (later calls are
+        bitwise set_target of the survivors) - after a pose-graph update and set_target_keyframes, or every few keyframes on a local map.
+        -> dict n_in / n_finite / n_observed / n_flagged / n_out / n_members"""
+        p = params if params is not None else visibility_params()
+        _check_visibility_params(p, "remove_dynamic")
+        ids, poses = _vote_members(members, "remove_dynamic")
+        self._ids_in_store(ids, "remove_dynamic")
+        info = VisibilityInfo()
+        self._check(self._L.dcreg_target_remove_dynamic(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int64)), _dp(poses), C.byref(p),
+                                                        C.byref(info)), "dcreg_target_remove_dynamic")
+        return _visibility_info_dict(info)
 
     def index_info(self):
         info = IndexInfo()

@@ -25,6 +25,7 @@ SOURCES = [
     "device/places.hip",
     "device/outliers.hip",
     "device/keyframes.hip",
+    "device/visibility.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

@@ -872,6 +872,36 @@ static int map_remove_outliers(dcreg_ctx *c, const dcreg_outlier_params *p, dcre
     return map_keep_flagged(c, "the filter would remove every point of the map", nullptr);
 }
 
+// dcreg_target_remove_dynamic: the visibility votes of the members over the whole map's points (visibility.hip), the survivors through the
+// update path of the crop.  Nothing of the context changes before the flags are known and some point goes.
+static int map_remove_dynamic(dcreg_ctx *c, int64_t n_members, const int64_t *ids, const double *poses, const dcreg_visibility_params *p,
+                              dcreg_visibility_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    VisRun v;
+    if (int rc = visibility_prepare(c, n_members, ids, poses, p, v)) return rc;
+    if (!poses && n_members > 0) { c->fail("null member poses"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const IndexSet &wm = whole_map(c);
+    const int64_t n = wm.n;
+    const size_t n1 = (size_t)n + 1;
+    if (c->d_upd.ensure(c, 4 * n1)) return DCREG_E_NOMEM;
+    uint32_t *flag_r = c->d_upd.data(), *flag_s = flag_r + 2 * n1;
+    const bool cell_order = c->opt_visibility_order != 0;
+    int rc = visibility_votes(c, cell_order ? wm.sorted.data() : wm.raw.data(), n, cell_order, v);
+    if (rc) return rc;
+    VisResult r;
+    rc = visibility_flags(c, wm.raw.data(), n, v, flag_r, r);
+    if (rc) return rc;
+    if (r.n_out == 0) { c->fail("the votes would remove every point of the map"); return DCREG_E_INVALID; }
+    visibility_info(info, r);
+    if (r.n_out == n) return DCREG_OK;               // nothing to remove: nothing changes
+    rc = outlier_sorted_flags(c, wm.sorted.data(), n, flag_r, flag_s);
+    if (rc) return rc;
+    return map_keep_flagged(c, "the votes would remove every point of the map", nullptr);
+}
+
 // dcreg_debug_index_check: the whole map's grid built from scratch (same origin, edge, dims, sub-cells) from its raw points, compared entry by entry
 static int index_check(dcreg_ctx *c, int64_t mm[5]) {
     const IndexSet &wm = whole_map(c);
@@ -2258,6 +2288,8 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "roi_margin") { c->opt_roi_margin = std::min(std::max(v, 0.0), 1.0e6); c->roi_built = false; }
     else if (k == "pair_max_table_entries") c->opt_pair_max_table_entries = (int64_t)std::min(std::max(v, 4096.0), 2147483648.0);   // per target of dcreg_register_pairs
     else if (k == "pairs_max_bytes") c->opt_pairs_max_bytes = std::max(v, 0.0);     // device bytes of one build batch of dcreg_register_pairs (0: a quarter of the free memory)
+    else if (k == "visibility_max_bytes") c->opt_visibility_max_bytes = std::max(v, 0.0);   // device bytes of the range images of one batch of members (visibility.hip)
+    else if (k == "visibility_order") c->opt_visibility_order = (int)v;   // dcreg_target_remove_dynamic votes over the map in index order (0) or in cell order (1, default)
     else if (k == "max_table_entries") c->opt_max_table_entries = (int64_t)std::min(std::max(v, 1048576.0), 2147483648.0);   // next dcreg_set_target
     else if (k == "advance") c->opt_advance = (int)v;            // the advance pass in front of single-pose launches: 0 never, 1 (default) by the host's rule, 2 whenever possible
     else if (k == "advance_fused") c->opt_advance_fused = (int)v;   // ... carried out by one kernel (1, default: the pass builds the rows itself) or by k_advance + k_lin (0)
@@ -2445,6 +2477,10 @@ int dcreg_set_target_outliers_device(dcreg_ctx *c, const float *d_xyz, int64_t n
     return set_cloud_outliers(c, d_xyz, n, stride, true, voxel, p, true, r, vinfo, info);
 }
 int dcreg_target_remove_outliers(dcreg_ctx *c, const dcreg_outlier_params *p, dcreg_outlier_info *info) { return map_remove_outliers(c, p, info); }
+int dcreg_target_remove_dynamic(dcreg_ctx *c, int64_t n_members, const int64_t *member_ids, const double *member_poses,
+                                const dcreg_visibility_params *p, dcreg_visibility_info *info) {
+    return map_remove_dynamic(c, n_members, member_ids, member_poses, p, info);
+}
 
 int dcreg_default_lin_params(dcreg_lin_params *p, double radius) {
     if (!p) return DCREG_E_INVALID;

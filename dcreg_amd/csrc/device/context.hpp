@@ -120,6 +120,12 @@ struct KfMember {
     uint32_t start, src;
     double pose[12];
 };
+// one non-empty member of a visibility batch on the device (visibility.hip k_vis_image, k_vis_vote): its first point among the batch's
+// stored points, its first point in the store, its range image within the batch, and its pose (R row-major, t) - 112 B
+struct VisMember {
+    uint32_t start, src, img, pad_;
+    double pose[12];
+};
 // the cloud of point i: the largest s with off[s] <= i (off[n_clouds] > i) - the segments of voxel.hip and deskew.hip
 __device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int n_clouds, int64_t i) {
     int lo = 0, hi = n_clouds;
@@ -371,6 +377,23 @@ struct dcreg_ctx {
         DevBuf<uint32_t> flag;
     };
     KeyframeBufs kf;
+    // visibility votes (visibility.hip: dcreg_keyframes_range_images*, dcreg_visibility_filter*, dcreg_target_remove_dynamic).  Scratch of one
+    // call: the range images of one batch of members and the batch's member records; per point the two counters; the packed cloud of the
+    // filter form, its keep flags and their scan (n + 1 entries, the last flag 0), its outputs; the call's counts ([0] finite, [1] observed,
+    // [2] flagged points)
+    struct VisibilityBufs {
+        DevBuf<float> images;
+        DevBuf<dcreg::VisMember> members;
+        DevBuf<int32_t> through, observed;
+        DevBuf<float4> pts;
+        DevBuf<uint32_t> keep, pos;
+        DevBuf<float> out;
+        DevBuf<uint8_t> mask;
+        DevBuf<unsigned long long> cnt;
+    };
+    VisibilityBufs vis;
+    double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members
+    int opt_visibility_order = 1;                              // the map form votes in index order (0) or in cell order (1)
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
     double opt_pairs_max_bytes = 0.0;                          // device bytes of one build batch of pair targets (0: a quarter of the free memory)
     PinnedBuf<double> h_euler;                         // Euler engine: the 27 derivative entries of a launch (LinArgs::dR)
@@ -594,6 +617,28 @@ void outlier_info(dcreg_outlier_info *info, const OutlierResult &r);
 int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_out);
 // flag_s[p] = the keep flag of the map point at sorted position p (n + 1 entries, the last 0)
 int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s);
+// the helpers the other passes share: the exclusive scan of n flags, and the compaction of the n packed points at `in` by keep flags and
+// their scan - 3 floats per kept point to out3, the byte mask where wanted
+int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n);
+int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask);
+// visibility.hip: one call's votes.  visibility_prepare checks parameters and members on the host (every refusal of include/dcreg.h before
+// anything is queued; poses == null: range images only) and cuts the members into batches; visibility_votes leaves through / observed of
+// the n packed points at `pts` in c->vis (by_w: point i counts at index w_i - a map in cell order); visibility_flags writes the keep flags
+// of the decision (n + 1 entries, the last 0) and reads the counts back: it waits for the stream
+struct VisRun {
+    dcreg_visibility_params p{};
+    std::vector<VisMember> members;        // the non-empty members, batch after batch
+    std::vector<int64_t> batch;            // batch b = members [batch[b], batch[b + 1]); its images: n_img[b], its stored points: n_pts[b]
+    std::vector<int64_t> n_img, n_pts;
+    int64_t n_members = 0;                 // members of the call, the empty ones among them
+};
+struct VisResult {
+    int64_t n_in = 0, n_finite = 0, n_observed = 0, n_flagged = 0, n_out = 0, n_members = 0;
+};
+int visibility_prepare(dcreg_ctx *c, int64_t n_members, const int64_t *ids, const double *poses, const dcreg_visibility_params *p, VisRun &v);
+int visibility_votes(dcreg_ctx *c, const float4 *pts, int64_t n, bool by_w, const VisRun &v);
+int visibility_flags(dcreg_ctx *c, const float4 *pts, int64_t n, const VisRun &v, uint32_t *keep, VisResult &r);
+void visibility_info(dcreg_visibility_info *info, const VisResult &r);
 // context.hip: the gathered points become the target as dcreg_set_target (p == null: a non-finite point refuses) or dcreg_set_target_voxel
 // takes a cloud - packed into c->d_aligned by the gather or by the voxel pass behind it, then the commit of the plain calls
 int set_target_gathered(dcreg_ctx *c, const GatherRun &g, const dcreg_voxel_params *p, double radius_hint, dcreg_voxel_info *info);

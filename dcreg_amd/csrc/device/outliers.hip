@@ -381,6 +381,15 @@ int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_ou
     return DCREG_OK;
 }
 
+int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n) { return scan_excl(c, flag, pos, n); }
+
+int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask) {
+    if (n <= 0) return DCREG_OK;
+    hipLaunchKernelGGL(k_out_write, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, keep, pos, out3, (float4 *)nullptr, mask);
+    HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
 int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s) {
     hipLaunchKernelGGL(k_out_sorted_flags, dim3(blocks(n + 1, 256)), dim3(256), 0, c->stream, sorted, n, flag_r, flag_s);
     HIP_TRY(c, hipGetLastError());

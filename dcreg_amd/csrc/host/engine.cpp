@@ -741,6 +741,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_place_info")) return sizeof(dcreg_place_info);
     if (!std::strcmp(name, "dcreg_outlier_params")) return sizeof(dcreg_outlier_params);
     if (!std::strcmp(name, "dcreg_outlier_info")) return sizeof(dcreg_outlier_info);
+    if (!std::strcmp(name, "dcreg_visibility_params")) return sizeof(dcreg_visibility_params);
+    if (!std::strcmp(name, "dcreg_visibility_info")) return sizeof(dcreg_visibility_info);
     return 0;
 }
 

@@ -162,6 +162,8 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   points inside its box, density at most twice what the cell edge was sized for), 0 = every update re-derives the grid;
  *   "map_grow_margin" default 20: metres added on each side of the map's box in x and y (not z) when an update re-derives the grid (a
  *                   map that grows along a path re-derives it once per that many metres, not at every keyframe);
+ *   "visibility_max_bytes" default 2^28 (256 MiB): device bytes the range images of one batch of members may take in the visibility
+ *                   calls (a batch always holds at least one image; the results do not depend on it);
  *   "roi_index", "roi_margin": the WINDOW index of a large map.  A map whose table ran into that budget is searched through cells that
  *                   grow with its extent; dcreg_linearize / the engines' single-pose launches therefore search such a map through a
  *                   second index over the map's points inside a box around the transformed source cloud (its bounding box at the pose +
@@ -701,6 +703,90 @@ int dcreg_keyframes_submaps_device(dcreg_ctx *, int n_submaps, const int64_t *me
                                    int64_t *out_offsets, dcreg_voxel_info *vinfo);
 int dcreg_set_target_keyframes(dcreg_ctx *, int64_t n_members, const int64_t *member_ids, const double *member_poses,
                                const dcreg_voxel_params *voxel, double search_radius_hint, dcreg_voxel_info *vinfo);
+
+/* ---------------- moving objects: visibility votes from keyframes ----------------
+ * A map assembled from keyframes holds every car and pedestrian that moved while it was recorded, as a dense trail that the outlier
+ * filters cannot remove.  The remedy is a range-image visibility check: a map point that other scans look THROUGH was not static.  The
+ * keyframe store holds the scans, the caller the poses; every output is bitwise the numpy reference of tests/visibility_ref.py.
+ *
+ * Parameters (dcreg_visibility_params; the defaults of dcreg_default_visibility_params behind each):
+ *   rows in [1, 256], cols in [1, 4096]                                          64, 1024
+ *   elev_min < elev_max, both finite and inside [-pi/2, pi/2] (radians)          -pi/8, +pi/8
+ *   0 <= min_range < max_range, finite (m)                                       0.5, 80
+ *   margin_abs >= 0 (m), margin_rel >= 0, finite                                 0.2, 0.01
+ *   window in [0, 3]                                                             1
+ *   min_votes >= 1                                                               2
+ *   min_ratio in [0, 1]                                                          0
+ * Everything below is evaluated in double, left to right, every product and sum rounded, no contraction.
+ *
+ * Pixel of a sensor-frame point s.  rho2 = sx^2 + sy^2, r2 = rho2 + sz^2, r = sqrt(r2).  The point is USED iff r2 > 0 and
+ * min_range^2 <= r2 < max_range^2 and, with
+ *     az = atan2(sy, sx), plus 2 pi (6.283185307179586) when negative;   b = az * cols / 2 pi;   col = min(floor(b), cols - 1);
+ *     el = atan2(sz, sqrt(rho2));   a = (elev_max - el) * rows / (elev_max - elev_min),
+ * 0 <= a < rows; then row = floor(a): row 0 is at the top.  A point whose a or b lies within 1e-9 of an integer may fall on either side
+ * (in or out at a = 0 and a = rows), as for the place descriptors: the device's atan2 is not the host's to the last bit.
+ *
+ * Range image of a keyframe.  Over its stored points, s = (double)p: image[row][col] = the minimum of (float)r over the used points of the
+ * pixel, +inf for an empty pixel (rows x cols floats, row-major).  The minimum is an integer atomic minimum on the floats' bits (positive
+ * values order as their bits do), so the image depends on neither the point order nor the launch shape.
+ *
+ * Vote of member (id, pose R, t; sensor -> map, 12 doubles as in the keyframe section) on a map-frame point q:
+ *     d_a = (double)q_a - t[a];   s_a = R[0][a] * d_0 + R[1][a] * d_1 + R[2][a] * d_2      (the pose is not checked for being a rotation)
+ * and the pixel of s as above; a point that is not used casts no vote.  m = the minimum of the member's image over the rows
+ * row - window .. row + window that lie inside [0, rows) and the columns col - window .. col + window taken modulo cols.  m = +inf: no
+ * vote.  Otherwise observed += 1, and through += 1 iff (double)m > r + (margin_abs + margin_rel * r).
+ *
+ * Decision.  Point i is REMOVED iff through_i >= min_votes and (double)through_i >= min_ratio * (double)observed_i.  The counts are
+ * integers summed over the members: a result does not depend on the member order, on how the members are batched ("visibility_max_bytes"
+ * of dcreg_set_option: the device bytes the range images of one batch may take, default 256 MiB, at least one image), or on what else
+ * the context holds; a repeated member votes twice; an empty keyframe casts no vote.
+ *
+ * dcreg_visibility_filter takes one cloud in the map frame and has the shape of dcreg_outlier_filter: non-finite points are dropped and
+ * counted (their counts are 0), the kept points are written in input order, bit for bit, and the optional outputs (NULL: not wanted) are
+ * the keep mask uint8[n] and the counts int32 through[n], observed[n].  The capacity protocol is dcreg_outlier_filter's.
+ * dcreg_target_remove_dynamic votes over the resident map's points (on a map with a window index the whole map's, as
+ * dcreg_target_remove_outliers) and sends the survivors through the update path of dcreg_target_crop.  It carries the contract of the
+ * map-update section: later calls are bitwise dcreg_set_target of the survivors in index order; a call that changes the map drops what
+ * dcreg_set_target drops; a call that removes nothing changes nothing (the neighbour states stay warm); a call that would remove every
+ * point is refused (DCREG_E_INVALID); refusals leave everything as it was.
+ *
+ * Refusals.  DCREG_E_INVALID, nothing written: null arrays, negative counts, an id outside [0, count), a non-finite pose, parameters
+ * outside the ranges above, stride < 3, more than 2^31 - 1 points.  DCREG_E_STATE: a linearisation in flight; no store
+ * (dcreg_keyframes_reset first); no target (the map form).  A failed allocation (DCREG_E_NOMEM) leaves the context as it was.  None of
+ * the calls touches source, places, store, neighbour states or window index, except the map form as dcreg_target_crop does.  Every call
+ * waits for the stream.  Device memory: the batch's images, 112 B per member, 8 B per point of counts and the filter's scratch. */
+typedef struct dcreg_visibility_params {
+    int rows, cols;                  /* the range image: elevation rows (row 0 at elev_max) x azimuth columns */
+    double elev_min, elev_max;       /* radians */
+    double min_range, max_range;     /* metres */
+    double margin_abs, margin_rel;   /* a pixel sees through a point when its range exceeds r + margin_abs + margin_rel * r */
+    int window, min_votes;
+    double min_ratio;
+} dcreg_visibility_params;
+typedef struct dcreg_visibility_info {
+    int64_t n_in;        /* points voted on */
+    int64_t n_finite;    /* ... with three finite coordinates */
+    int64_t n_observed;  /* ... with observed >= 1 */
+    int64_t n_flagged;   /* ... removed by the decision */
+    int64_t n_out;       /* points kept */
+    int64_t n_members;   /* members of the call */
+} dcreg_visibility_info;
+int dcreg_default_visibility_params(dcreg_visibility_params *);
+/* The range images of the keyframes ids[0 .. n), n x rows x cols floats to out (host memory; _device: device memory).  An id may repeat. */
+int dcreg_keyframes_range_images(dcreg_ctx *, int64_t n, const int64_t *ids, const dcreg_visibility_params *, float *out);
+int dcreg_keyframes_range_images_device(dcreg_ctx *, int64_t n, const int64_t *ids, const dcreg_visibility_params *, float *d_out);
+/* *n_out receives the number of kept points; capacity_points = n is always enough; a smaller capacity that the output does not fit returns
+ * DCREG_E_INVALID with *n_out and info filled and nothing written to out_xyz, keep_mask, through or observed.  info may be NULL.
+ * _device: d_xyz is read as dcreg_set_source_device reads a cloud; the outputs are device memory. */
+int dcreg_visibility_filter(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, int64_t n_members, const int64_t *member_ids,
+                            const double *member_poses, const dcreg_visibility_params *, float *out_xyz, int64_t capacity_points,
+                            int64_t *n_out, uint8_t *keep_mask, int32_t *through, int32_t *observed, dcreg_visibility_info *info);
+int dcreg_visibility_filter_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, int64_t n_members,
+                                   const int64_t *member_ids, const double *member_poses, const dcreg_visibility_params *, float *d_out_xyz,
+                                   int64_t capacity_points, int64_t *n_out, uint8_t *d_keep_mask, int32_t *d_through, int32_t *d_observed,
+                                   dcreg_visibility_info *info);
+int dcreg_target_remove_dynamic(dcreg_ctx *, int64_t n_members, const int64_t *member_ids, const double *member_poses,
+                                const dcreg_visibility_params *, dcreg_visibility_info *info);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
