@@ -5,8 +5,10 @@
 //   backward : every target point -> 1-NN in the aligned cloud.  A rigid motion preserves distances, so the
 //              nearest aligned point of q is the image of the nearest source point of T^-1 q; a second grid
 //              index is built over the (body-frame) source once and queried with T^-1-transformed targets.
-//              (The reference measures float distances between float-rounded aligned points; the difference
-//              is rounding of O(1e-7) relative and is covered by the test tolerance.)
+//              T^-1 is taken as (R^T, -R^T t): T must be a rigid motion, which the entry point checks on the host.
+//              (The reference measures float distances between float-rounded aligned points, this pass between the
+//              float-rounded T^-1 q and the source: the two means differ by rounding of 2^-24 of the largest
+//              coordinate in each frame - the bound is stated in include/dcreg.h and asserted in tests/test_gpu_p2p_error.py.)
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -20,6 +22,17 @@ using namespace dcreg;
 
 namespace dcreg {
 int build_aux_index(dcreg_ctx *c);   // context.hip
+}
+
+// the rule of the deskew calls (deskew.hip is_rotation) on the rotation block of a row-major 4x4
+static bool rigid_rotation(const double T[16]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = T[i] * T[j] + T[4 + i] * T[4 + j] + T[8 + i] * T[8 + j] - (i == j ? 1.0 : 0.0);   // (R^T R - I)_ij
+            if (!(std::fabs(g) <= 1e-6)) return false;
+        }
+    const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
+    return det > 0.0;
 }
 
 static int reduce_p2p(dcreg_ctx *c, const float *d_d2, int64_t n, double thr, double out[3]) {
@@ -40,7 +53,11 @@ extern "C" int dcreg_p2p_error(dcreg_ctx *c, const double T[16], double error_th
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (!T || !rmse || !fitness || !chamfer || !valid) { c->fail("null argument"); return DCREG_E_INVALID; }
-    (void)roi_deactivate(c);              // the metrics are taken on the whole map (context.hpp, the window index)
+    // the pose, on the host and before anything is queued or switched (the bottom row is ignored, as the reference's affine transform
+    // ignores it): a non-finite entry would reach the cell arithmetic of the search, and the backward pass inverts T as a rigid motion
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(T[i])) { c->fail("T has a non-finite entry"); return DCREG_E_INVALID; }
+    if (!rigid_rotation(T)) { c->fail("the rotation block of T is not a rotation (|R^T R - I| > 1e-6 or det <= 0)"); return DCREG_E_INVALID; }
+    (void)roi_deactivate(c);             // the metrics are taken on the whole map (context.hpp, the window index)
     if (c->map.n <= 0 || c->n_src <= 0) { c->fail("target / source clouds are not set"); return DCREG_E_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t ns = c->n_src, nt = c->map.n;

@@ -1006,7 +1006,25 @@ int dcreg_comm_info(const dcreg_ctx *, int *rank, int *world);
 int dcreg_set_host_threads(int n);
 int dcreg_get_host_threads(void);
 
-/* calculatePointToPointError (utils.hpp:538-589): aligned = T * source (float), both directions on the GPU */
+/* calculatePointToPointError (utils.hpp:538-589): aligned = T * source (float), both directions on the GPU.
+ *   T       row-major 4x4; the bottom row is ignored (the reference's affine transform ignores it).  T must be a RIGID motion: a non-finite
+ *           entry in its top three rows, or a rotation block that is not a rotation (an element of |R^T R - I| above 1e-6, or det(R) <= 0 -
+ *           the rule of the deskew calls), is refused with DCREG_E_INVALID before anything is queued.  No source or no target: DCREG_E_STATE.
+ *   forward (rmse, fitness, valid, and the forward half of chamfer): every T * p (double arithmetic, float store) against the map, as the
+ *           reference does it - valid and fitness are the reference's exactly, rmse and the forward mean are double sums of the same float
+ *           terms in another order.  A point counts as valid when (double)sqrtf(d2) < error_threshold, strictly: a threshold <= 0 counts
+ *           none (rmse = fitness = 0), +inf counts all.
+ *   backward (the other half of chamfer): the reference builds a second tree over the aligned cloud.  Here the map points are moved by
+ *           T^-1 = (R^T, -R^T t) into the body frame and searched in a grid over the source - the same nearest neighbours because a rigid
+ *           motion preserves distances; that is why T must be one.  The two differ only in where the float rounding happens (T^-1 q in
+ *           the body frame here, T p in the map frame there).  A nearest-neighbour distance is 1-Lipschitz in either point set, so against
+ *           the mean taken in exact arithmetic
+ *               |backward mean here - exact|      <= sqrt(3) * 2^-24 * B + 2^-21 * mean,
+ *               |backward mean reference - exact| <= sqrt(3) * 2^-24 * G + 2^-21 * mean,
+ *           with B (G) the largest absolute body-frame (map-frame) coordinate among the moved points and the cloud they are searched in;
+ *           the second term covers the float d2 arithmetic and sqrtf.  chamfer differs from the reference by at most half the sum of the
+ *           two.  (A rotation block at the edge of the 1e-6 rule adds up to 1e-6 * the distances involved.)
+ *   Results are deterministic: the same clouds and T give the same bits. */
 int dcreg_p2p_error(dcreg_ctx *, const double T[16], double error_threshold, double *rmse, double *fitness,
                     double *chamfer, int64_t *valid_correspondences);
 
