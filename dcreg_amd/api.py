@@ -157,6 +157,7 @@ EXPORTS = [
     "dcreg_keyframes_add_source", "dcreg_keyframes_get", "dcreg_keyframes_submaps", "dcreg_keyframes_submaps_device", "dcreg_set_target_keyframes",
     "dcreg_default_visibility_params", "dcreg_keyframes_range_images", "dcreg_keyframes_range_images_device", "dcreg_visibility_filter",
     "dcreg_visibility_filter_device", "dcreg_target_remove_dynamic",
+    "dcreg_default_normal_params", "dcreg_normals", "dcreg_normals_device", "dcreg_target_normals", "dcreg_target_normals_device",
 ]
 
 _lib = None
@@ -574,6 +575,57 @@ def _check_device_cloud(n, stride, what):
         raise ValueError("%s: a stride of at least 3 floats is expected, got %d" % (what, int(stride)))
 
 
+class NormalParams(C.Structure):
+    _fields_ = [("k", C.c_int), ("orient", C.c_int), ("search_radius", C.c_double), ("viewpoint", C.c_double * 3),
+                ("reserved_", C.c_double * 2)]
+
+
+class NormalInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_sparse", C.c_int64), ("n_out", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_normal_params": NormalParams, "dcreg_normal_info": NormalInfo})
+NORMAL_ORIENT = {"viewpoint": 0, "none": 1}      # DCREG_NORMAL_ORIENT_VIEWPOINT / DCREG_NORMAL_ORIENT_NONE
+NORMAL_MIN_K, NORMAL_MAX_K = 3, 32
+
+
+def _check_normal_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_normal_params block"""
+    if not isinstance(p, NormalParams):
+        raise ValueError("%s: normal_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not NORMAL_MIN_K <= p.k <= NORMAL_MAX_K:
+        raise ValueError("%s: k in [%d, %d] is expected, got %d" % (what, NORMAL_MIN_K, NORMAL_MAX_K, p.k))
+    if p.orient not in NORMAL_ORIENT.values():
+        raise ValueError("%s: an orientation of %s is expected, got %d" % (what, sorted(NORMAL_ORIENT.values()), p.orient))
+    if not (np.isfinite(p.search_radius) and p.search_radius >= 0.0):
+        raise ValueError("%s: a finite search_radius >= 0 is expected, got %r" % (what, p.search_radius))
+    if not all(np.isfinite(v) for v in p.viewpoint):
+        raise ValueError("%s: a finite viewpoint is expected, got %r" % (what, list(p.viewpoint)))
+
+
+def normal_params(k=5, search_radius=0.0, viewpoint=(0.0, 0.0, 0.0)):
+    """dcreg_normal_params: k neighbours per point, the point itself among them (PCL NormalEstimation setKSearch; the reference's
+    normal_nn), search_radius > 0 bounds the search, viewpoint = the side the normals point to (PCL setViewPoint), None = the solver's
+    sign (DCREG_NORMAL_ORIENT_NONE); include/dcreg.h has the rule"""
+    p = NormalParams()
+    p.k = int(k)
+    p.search_radius = float(search_radius)
+    if viewpoint is None:
+        p.orient = NORMAL_ORIENT["none"]
+    else:
+        v = np.asarray(viewpoint, np.float64).reshape(-1)
+        if v.shape != (3,):
+            raise ValueError("normal_params: a viewpoint of 3 values or None is expected, got %r" % (viewpoint,))
+        p.orient = NORMAL_ORIENT["viewpoint"]
+        p.viewpoint[0], p.viewpoint[1], p.viewpoint[2] = float(v[0]), float(v[1]), float(v[2])
+    _check_normal_params(p, "normal_params")
+    return p
+
+
+def _normal_info_dict(i):
+    return {"n_in": i.n_in, "n_finite": i.n_finite, "n_sparse": i.n_sparse, "n_out": i.n_out}
+
+
 KEYFRAME_MAX_POINTS = 2 ** 31 - 1      # member points of one gather (include/dcreg.h)
 
 
@@ -942,6 +994,13 @@ def load():
         for name in ("dcreg_visibility_filter", "dcreg_visibility_filter_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, i64p, dp, sp, vp, C.c_int64, i64p, vp, vp, vp, si]
         L.dcreg_target_remove_dynamic.argtypes = [vp, C.c_int64, i64p, dp, sp, si]
+    if hasattr(L, "dcreg_normals"):            # (absent from an older build loaded through DCREG_LIB for an A/B)
+        np_, ni = C.POINTER(NormalParams), C.POINTER(NormalInfo)
+        L.dcreg_default_normal_params.argtypes = [np_]
+        for name in ("dcreg_normals", "dcreg_normals_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, np_, vp, vp, vp, ni]
+        for name in ("dcreg_target_normals", "dcreg_target_normals_device"):
+            getattr(L, name).argtypes = [vp, np_, vp, vp, vp, C.c_int64, ni]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1571,6 +1630,63 @@ class Context:
         info = OutlierInfo()
         self._check(self._L.dcreg_target_remove_outliers(self._h, C.byref(p), C.byref(info)), "dcreg_target_remove_outliers")
         return _outlier_info_dict(info)
+
+    @staticmethod
+    def _normal_wants(want_normals, want_curvature, want_eigenvalues, what):
+        if not (want_normals or want_curvature or want_eigenvalues):
+            raise ValueError("%s: at least one of normals, curvature and eigenvalues is expected" % what)
+
+    def normals(self, xyz, params=None, want_normals=True, want_curvature=True, want_eigenvalues=False):
+        """dcreg_normals: per point of one cloud ([n, c] float32, x y z first) the normal of the plane through its k nearest points (itself
+        among them), the surface variation and optionally the three eigenvalues of the neighbourhood's covariance, ascending (PCL
+        NormalEstimation with setKSearch; include/dcreg.h has the rule).  Non-finite and sparse points get NaN.  params: normal_params(...),
+        None = the defaults.  -> (normals [n, 3] float32 or None, curvature [n] float32 or None, eigenvalues [n, 3] float32 or None,
+        dict n_in / n_finite / n_sparse / n_out)"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "normals")
+        self._normal_wants(want_normals, want_curvature, want_eigenvalues, "normals")
+        a = _points(xyz, "normals")
+        n = a.shape[0]
+        nrm = np.full((max(n, 1), 3), np.nan, np.float32) if want_normals else None
+        cur = np.full(max(n, 1), np.nan, np.float32) if want_curvature else None
+        eig = np.full((max(n, 1), 3), np.nan, np.float32) if want_eigenvalues else None
+        info = NormalInfo()
+        self._check(self._L.dcreg_normals(self._h, a.ctypes.data, n, a.shape[1], C.byref(p), nrm.ctypes.data if want_normals else None,
+                                          cur.ctypes.data if want_curvature else None, eig.ctypes.data if want_eigenvalues else None,
+                                          C.byref(info)), "dcreg_normals")
+        return (nrm[:n] if want_normals else None, cur[:n] if want_curvature else None, eig[:n] if want_eigenvalues else None,
+                _normal_info_dict(info))
+
+    def normals_device(self, dev_ptr, n, stride, params=None, dev_normals_ptr=0, dev_curvature_ptr=0, dev_eigenvalues_ptr=0):
+        """dcreg_normals_device: the cloud in device memory; the normals (3 n floats), curvature (n floats) and eigenvalues (3 n floats) to
+        the device buffers given (0: not wanted).  -> info dict"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "normals_device")
+        _check_device_cloud(n, stride, "normals_device")
+        self._normal_wants(dev_normals_ptr, dev_curvature_ptr, dev_eigenvalues_ptr, "normals_device")
+        info = NormalInfo()
+        self._check(self._L.dcreg_normals_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.byref(p), C.c_void_p(dev_normals_ptr or None),
+                                                 C.c_void_p(dev_curvature_ptr or None), C.c_void_p(dev_eigenvalues_ptr or None),
+                                                 C.byref(info)), "dcreg_normals_device")
+        return _normal_info_dict(info)
+
+    def target_normals(self, params=None, want_normals=True, want_curvature=True, want_eigenvalues=False):
+        """dcreg_target_normals: the same for the resident map's points in index order (target_points()), searched through the map's own
+        index - what ICPContext::setTargetCloud(target, normal_nn) keeps in targetNormals.  The map is untouched.
+        -> (normals, curvature, eigenvalues, info dict) as normals()"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "target_normals")
+        self._normal_wants(want_normals, want_curvature, want_eigenvalues, "target_normals")
+        n = max(int(self.index_info().n_target), 0)
+        nrm = np.full((max(n, 1), 3), np.nan, np.float32) if want_normals else None
+        cur = np.full(max(n, 1), np.nan, np.float32) if want_curvature else None
+        eig = np.full((max(n, 1), 3), np.nan, np.float32) if want_eigenvalues else None
+        info = NormalInfo()
+        self._check(self._L.dcreg_target_normals(self._h, C.byref(p), nrm.ctypes.data if want_normals else None,
+                                                 cur.ctypes.data if want_curvature else None, eig.ctypes.data if want_eigenvalues else None,
+                                                 n, C.byref(info)), "dcreg_target_normals")
+        return (nrm[:n] if want_normals else None, cur[:n] if want_curvature else None, eig[:n] if want_eigenvalues else None,
+                _normal_info_dict(info))
 
     # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
     def keyframes_reset(self):

@@ -26,6 +26,7 @@ SOURCES = [
     "device/outliers.hip",
     "device/keyframes.hip",
     "device/visibility.hip",
+    "device/normals.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]

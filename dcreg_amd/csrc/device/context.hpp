@@ -392,6 +392,14 @@ struct dcreg_ctx {
         DevBuf<unsigned long long> cnt;
     };
     VisibilityBufs vis;
+    // surface normals (normals.hip: dcreg_normals*, dcreg_target_normals*).  Scratch of one call: the outputs per input point (3 + 1 + 3
+    // floats, those that are wanted) and the call's counts ([0] points with a normal, [1] sparse points); the cloud form packs, compacts and
+    // indexes its cloud in the outlier scratch (outl.pts, cpts, used, upos, idx)
+    struct NormalBufs {
+        DevBuf<float> normal, curv, eig;
+        DevBuf<unsigned long long> cnt;
+    };
+    NormalBufs nrm;
     double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members
     int opt_visibility_order = 1;                              // the map form votes in index order (0) or in cell order (1)
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
@@ -621,6 +629,11 @@ int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const ui
 // their scan - 3 floats per kept point to out3, the byte mask where wanted
 int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n);
 int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask);
+// ... and for normals.hip: the first step of outlier_pass on its own - the used points of the n packed points at `in` compacted into
+// c->outl.cpts (w = the input index) and, when there are at least min_used of them, indexed in c->outl.idx (hint: the cell size follows
+// it, 0 = from the density); waits for the stream for *n_used.  outlier_rings: the rings a walk needs to cover a squared radius
+int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used);
+int outlier_rings(const GridDev &g, float bound);
 // visibility.hip: one call's votes.  visibility_prepare checks parameters and members on the host (every refusal of include/dcreg.h before
 // anything is queued; poses == null: range images only) and cuts the members into batches; visibility_votes leaves through / observed of
 // the n packed points at `pts` in c->vis (by_w: point i counts at index w_i - a map in cell order); visibility_flags writes the keep flags

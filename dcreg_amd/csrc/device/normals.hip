@@ -1,0 +1,298 @@
+// Surface normals and curvature on the device (include/dcreg.h: dcreg_normals*, dcreg_target_normals*): pcl::NormalEstimation with a k
+// search, with the rule of the header, bitwise the numpy reference of tests/normals_ref.py.
+//   (cloud form)  the used (finite) points compacted with their input index in w and indexed: the first step of the outlier pass
+//                 (outliers.hip outlier_index_used); the map form skips this - the map is its own index
+//   k_nrm<K>      one lane per used point, in the index's cell order: the ring walk of k_knn with a heap of (d2, index) keys and positions in
+//                 the last k of K slots; then the lane gathers its k neighbours in rank order (twice: the mean, the covariance - they are
+//                 hot in L2), solves the 3x3 problem with six Jacobi sweeps in registers, orients the normal and writes 12 + 4 (+ 12) bytes
+//                 at the point's input index
+// A point's result depends on the cloud only: the index decides how fast the neighbours are found, never which.
+#include <cmath>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "context.hpp"
+
+// every multiply and add below rounds once: the rule is stated operation by operation
+#pragma clang fp contract(off)
+
+namespace dcreg {
+namespace {
+
+constexpr int kMinK = 3, kMaxK = 32;
+
+inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
+// The k smallest (d2, index) keys of the candidates with d2 < bound, ascending, with their positions in the sorted array, in the last k of
+// K slots (the first K - k hold key 0, which nothing undercuts, and never move: one instantiation serves every k <= K, and the pruning
+// distance is the k-th best, not the K-th).  HeapExact's key (search.hpp); a slot that was never filled keeps position kNoIdx.  The
+// interface of search.hpp's heaps.
+template <int K_>
+struct HeapNrm {
+    static constexpr int K = K_;
+    static constexpr bool kDeferred = false;
+    uint64_t key[K];
+    uint32_t pos[K];
+    int k;
+    uint32_t n_eval, n_shell;
+    DCREG_DEVFN void init(float bound_f, float = 1.f, float = 0.f) {
+        const uint64_t bound = (uint64_t)__float_as_uint(bound_f) << 32;      // index 0: d2 == bound does not enter
+#pragma unroll
+        for (int i = 0; i < K; ++i) { key[i] = i < K - k ? 0ull : bound; pos[i] = kNoIdx; }
+        n_eval = 0; n_shell = 1;
+    }
+    DCREG_DEVFN void push(float d2, uint32_t idx, uint32_t p, bool valid = true) {
+        const uint64_t kk = ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)idx;
+        if (valid && kk < key[K - 1]) {
+            key[K - 1] = kk; pos[K - 1] = p;
+#pragma unroll
+            for (int j = K - 1; j > 0; --j) {
+                const bool sw = key[j] < key[j - 1];
+                const uint64_t ka = key[j - 1], kb = key[j];
+                const uint32_t pa = pos[j - 1], pb = pos[j];
+                key[j - 1] = sw ? kb : ka; key[j] = sw ? ka : kb;
+                pos[j - 1] = sw ? pb : pa; pos[j] = sw ? pa : pb;
+            }
+        }
+    }
+    DCREG_DEVFN float worst_d2() const { return __uint_as_float((uint32_t)(key[K - 1] >> 32)); }
+};
+
+struct NrmArgs {
+    double vx, vy, vz;
+    int orient;
+};
+
+// one Jacobi rotation of the pair (p, q), r the third index: the header's formulas, in its order
+DCREG_DEVFN void jacobi_rot(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q, double &v1p,
+                            double &v1q, double &v2p, double &v2q) {
+    double t = 0.0;
+    if (apq != 0.0) {
+        const double theta = (aqq - app) / (2.0 * apq);
+        t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    }
+    const double c = 1.0 / sqrt(t * t + 1.0);
+    const double s = t * c;
+    const double tp = t * apq;
+    app = app - tp;
+    aqq = aqq + tp;
+    apq = 0.0;
+    const double rp = arp, rq = arq;
+    arp = c * rp - s * rq;
+    arq = s * rp + c * rq;
+    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
+    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
+    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
+    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
+}
+
+static __global__ void k_nrm_fill(float *__restrict__ a, int64_t n, float v) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
+// One lane per used point, in the index's cell order (the lanes of a wave search neighbouring cells); the point's input index is in w, and
+// the outputs go there (a null output is not wanted).  cnt[0] += points with a normal, cnt[1] += sparse points (one atomic pair per wave)
+template <int K>
+static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict__ q, uint32_t n, GridDev g, float bound_f, int max_ring, int k,
+                                                       NrmArgs a, float *__restrict__ normal, float *__restrict__ curv, float *__restrict__ eig,
+                                                       unsigned long long *__restrict__ cnt) {
+    __shared__ RunList runs[kBlock / kWave];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 s4 = q[i];
+    const uint32_t self = __float_as_uint(s4.w);
+    HeapNrm<K> hp;
+    hp.k = k;
+    knn_search<HeapNrm<K>>(g, runs[threadIdx.x / kWave], s4.x, s4.y, s4.z, bound_f, max_ring, hp);
+    const bool sparse = hp.pos[K - 1] == kNoIdx;       // (sorted: the last slot is the last to fill)
+    if (!sparse) {
+        const double px = (double)s4.x, py = (double)s4.y, pz = (double)s4.z;
+        const double kd = (double)k;
+        // (-0.0 is the identity of the IEEE addition: -0.0 + x = x bit for bit, so the sums start with their first term)
+        double sx = -0.0, sy = -0.0, sz = -0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (j >= K - k) {
+                const float4 c = g.pts[hp.pos[j]];
+                sx = sx + ((double)c.x - px); sy = sy + ((double)c.y - py); sz = sz + ((double)c.z - pz);
+            }
+        const double mx = sx / kd, my = sy / kd, mz = sz / kd;
+        double cxx = -0.0, cxy = -0.0, cxz = -0.0, cyy = -0.0, cyz = -0.0, czz = -0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (j >= K - k) {
+                const float4 c = g.pts[hp.pos[j]];
+                const double dx = ((double)c.x - px) - mx, dy = ((double)c.y - py) - my, dz = ((double)c.z - pz) - mz;
+                cxx = cxx + dx * dx; cxy = cxy + dx * dy; cxz = cxz + dx * dz;
+                cyy = cyy + dy * dy; cyz = cyz + dy * dz; czz = czz + dz * dz;
+            }
+        double a00 = cxx / kd, a01 = cxy / kd, a02 = cxz / kd, a11 = cyy / kd, a12 = cyz / kd, a22 = czz / kd;
+        double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+        for (int sweep = 0; sweep < 6; ++sweep) {
+            jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);     // (0,1), r = 2
+            jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);     // (0,2), r = 1
+            jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);     // (1,2), r = 0
+        }
+        // the smallest eigenvalue, a tie to the lowest index
+        const bool b1 = a11 < a00;
+        const double l01 = b1 ? a11 : a00;
+        const bool b2 = a22 < l01;
+        const double lmin = b2 ? a22 : l01;
+        double nx = b2 ? v02 : (b1 ? v01 : v00), ny = b2 ? v12 : (b1 ? v11 : v10), nz = b2 ? v22 : (b1 ? v21 : v20);
+        const double trace = (a00 + a11) + a22;
+        const double cv = trace == 0.0 ? 0.0 : fabs(lmin) / trace;
+        if (a.orient == DCREG_NORMAL_ORIENT_VIEWPOINT) {
+            const double dot = ((a.vx - px) * nx + (a.vy - py) * ny) + (a.vz - pz) * nz;
+            if (dot < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
+        }
+        if (normal) { normal[3 * (size_t)self] = (float)nx; normal[3 * (size_t)self + 1] = (float)ny; normal[3 * (size_t)self + 2] = (float)nz; }
+        if (curv) curv[self] = (float)cv;
+        if (eig) {
+            double l0 = a00, l1 = a11, l2 = a22, t;
+            if (l1 < l0) { t = l0; l0 = l1; l1 = t; }
+            if (l2 < l1) { t = l1; l1 = l2; l2 = t; }
+            if (l1 < l0) { t = l0; l0 = l1; l1 = t; }
+            eig[3 * (size_t)self] = (float)l0; eig[3 * (size_t)self + 1] = (float)l1; eig[3 * (size_t)self + 2] = (float)l2;
+        }
+    }
+    const unsigned long long A = __ballot(true), S = __ballot(sparse);
+    if ((int)(threadIdx.x & 63) == __ffsll(A) - 1) {
+        const unsigned long long ns = (unsigned long long)__popcll(S);
+        atomicAdd(cnt, (unsigned long long)__popcll(A) - ns);
+        if (ns) atomicAdd(cnt + 1, ns);
+    }
+}
+
+template <int K>
+void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const NrmArgs &a, float *normal,
+                float *curv, float *eig) {
+    hipLaunchKernelGGL(k_nrm<K>, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, bound, max_ring, k, a, normal, curv, eig,
+                       c->nrm.cnt.data());
+}
+
+int normals_check(dcreg_ctx *c, const dcreg_normal_params *p) {
+    if (!p) { c->fail("null normal parameters"); return DCREG_E_INVALID; }
+    if (p->k < kMinK || p->k > kMaxK) { c->fail("normal k is %d: %d .. %d expected", p->k, kMinK, kMaxK); return DCREG_E_INVALID; }
+    if (p->orient != DCREG_NORMAL_ORIENT_VIEWPOINT && p->orient != DCREG_NORMAL_ORIENT_NONE) { c->fail("unknown normal orientation %d", p->orient); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->search_radius) && p->search_radius >= 0.0)) { c->fail("normal search_radius is %g: finite and >= 0 expected", p->search_radius); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->viewpoint[0]) && std::isfinite(p->viewpoint[1]) && std::isfinite(p->viewpoint[2]))) { c->fail("the normal viewpoint is not finite"); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+struct NormalOut {
+    float *normal, *curv, *eig;       // the caller's buffers (null: not wanted)
+    bool on_device;
+};
+
+// The outputs of n points start as NaN; the nq used points at q (cell order, w = the output index) behind the grid g get theirs; then the
+// copies to the caller and the counts.  nq = 0: no index was built (fewer than k of the n_used used points) - every used point is sparse
+int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int64_t n, int64_t n_used, const dcreg_normal_params *p, const NormalOut &o,
+                dcreg_normal_info *info) {
+    dcreg_ctx::NormalBufs &B = c->nrm;
+    if ((o.normal && B.normal.ensure(c, 3 * (size_t)n)) || (o.curv && B.curv.ensure(c, (size_t)n)) || (o.eig && B.eig.ensure(c, 3 * (size_t)n)) ||
+        B.cnt.ensure(c, 2))
+        return DCREG_E_NOMEM;
+    float *d_normal = o.normal ? B.normal.data() : nullptr, *d_curv = o.curv ? B.curv.data() : nullptr, *d_eig = o.eig ? B.eig.data() : nullptr;
+    const float nanf_ = __builtin_nanf("");
+    if (d_normal) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, d_normal, 3 * n, nanf_);
+    if (d_curv) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, d_curv, n, nanf_);
+    if (d_eig) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, d_eig, 3 * n, nanf_);
+    HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
+    unsigned long long cnt[2] = {0, (unsigned long long)n_used};
+    if (nq > 0) {
+        const int k = p->k;
+        float bound = 3.0e38f;
+        int max_ring = -1;
+        if (p->search_radius > 0.0) {
+            bound = (float)(p->search_radius * p->search_radius);
+            if (!(bound <= 3.0e38f)) bound = 3.0e38f;
+            max_ring = outlier_rings(g, bound);
+        }
+        NrmArgs a;
+        a.vx = p->viewpoint[0]; a.vy = p->viewpoint[1]; a.vz = p->viewpoint[2]; a.orient = p->orient;
+        if (k <= 8) launch_nrm<8>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
+        else if (k <= 16) launch_nrm<16>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
+        else launch_nrm<32>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(cnt, B.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    }
+    const hipMemcpyKind kind = o.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (o.normal) HIP_TRY(c, hipMemcpyAsync(o.normal, d_normal, sizeof(float) * 3 * (size_t)n, kind, c->stream));
+    if (o.curv) HIP_TRY(c, hipMemcpyAsync(o.curv, d_curv, sizeof(float) * (size_t)n, kind, c->stream));
+    if (o.eig) HIP_TRY(c, hipMemcpyAsync(o.eig, d_eig, sizeof(float) * 3 * (size_t)n, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (info) { info->n_in = n; info->n_finite = n_used; info->n_sparse = (int64_t)cnt[1]; info->n_out = (int64_t)cnt[0]; }
+    return DCREG_OK;
+}
+
+// dcreg_normals*: the cloud packed, its used points indexed, the kernel, the copies
+int normals_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, const dcreg_normal_params *p, float *normal, float *curv,
+                  float *eig, dcreg_normal_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = normals_check(c, p)) return rc;
+    if (n < 0 || stride < 3) { c->fail("invalid normal estimation arguments"); return DCREG_E_INVALID; }
+    if (n > (int64_t)INT32_MAX) { c->fail("too many points for one normal estimation (%lld)", (long long)n); return DCREG_E_INVALID; }
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (!normal && !curv && !eig) { c->fail("no output buffer: normals, curvature or eigenvalues expected"); return DCREG_E_INVALID; }
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (n == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::OutlierBufs &B = c->outl;
+    if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
+    int64_t n_used = 0;
+    if (int rc = outlier_index_used(c, B.pts.data(), n, p->search_radius, p->k, &n_used)) return rc;
+    const bool indexed = n_used >= p->k;
+    const NormalOut o{normal, curv, eig, on_device};
+    return normals_run(c, indexed ? B.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? B.idx.grid : GridDev{}, n, n_used, p, o, info);
+}
+
+// dcreg_target_normals*: the whole map's points through the map's own index
+int normals_map(dcreg_ctx *c, bool on_device, const dcreg_normal_params *p, float *normal, float *curv, float *eig, int64_t capacity,
+                dcreg_normal_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = normals_check(c, p)) return rc;
+    if (!normal && !curv && !eig) { c->fail("no output buffer: normals, curvature or eigenvalues expected"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;      // the whole map's index, whichever is active
+    const int64_t n = wm.n;
+    if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const NormalOut o{normal, curv, eig, on_device};
+    return normals_run(c, wm.sorted.data(), n, wm.grid, n, n, p, o, info);
+}
+
+}  // namespace
+}  // namespace dcreg
+
+using namespace dcreg;
+
+extern "C" {
+int dcreg_default_normal_params(dcreg_normal_params *p) {
+    if (!p) return DCREG_E_INVALID;
+    std::memset(p, 0, sizeof(*p));
+    p->k = 5; p->orient = DCREG_NORMAL_ORIENT_VIEWPOINT; p->search_radius = 0.0;
+    return DCREG_OK;
+}
+int dcreg_normals(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_normal_params *p, float *normals_out,
+                  float *curvature_out, float *eigenvalues_out, dcreg_normal_info *info) {
+    return normals_cloud(c, xyz, n, stride_floats, false, p, normals_out, curvature_out, eigenvalues_out, info);
+}
+int dcreg_normals_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_normal_params *p, float *d_normals_out,
+                         float *d_curvature_out, float *d_eigenvalues_out, dcreg_normal_info *info) {
+    return normals_cloud(c, d_xyz, n, stride_floats, true, p, d_normals_out, d_curvature_out, d_eigenvalues_out, info);
+}
+int dcreg_target_normals(dcreg_ctx *c, const dcreg_normal_params *p, float *normals_out, float *curvature_out, float *eigenvalues_out,
+                         int64_t capacity_points, dcreg_normal_info *info) {
+    return normals_map(c, false, p, normals_out, curvature_out, eigenvalues_out, capacity_points, info);
+}
+int dcreg_target_normals_device(dcreg_ctx *c, const dcreg_normal_params *p, float *d_normals_out, float *d_curvature_out,
+                                float *d_eigenvalues_out, int64_t capacity_points, dcreg_normal_info *info) {
+    return normals_map(c, true, p, d_normals_out, d_curvature_out, d_eigenvalues_out, capacity_points, info);
+}
+}

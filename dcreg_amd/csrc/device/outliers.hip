@@ -383,6 +383,29 @@ int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_ou
 
 int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n) { return scan_excl(c, flag, pos, n); }
 
+int outlier_rings(const GridDev &g, float bound) { return rings_for_bound(g, bound); }
+
+int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used_out) {
+    dcreg_ctx::OutlierBufs &B = c->outl;
+    const size_t n1 = (size_t)n + 1;
+    if (B.used.ensure(c, n1) || B.upos.ensure(c, n1) || B.cpts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_out_used, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, in, n, B.used.data());
+    if (int rc = scan_excl(c, B.used.data(), B.upos.data(), n1)) return rc;
+    uint32_t n_used = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_used, B.upos.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    *n_used_out = n_used;
+    if (n_used == 0 || (int64_t)n_used < min_used) return DCREG_OK;
+    hipLaunchKernelGGL(k_out_compact, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.used.data(), B.upos.data(), B.cpts.data());
+    // (the build reports whether the table budget capped its cells: that word belongs to the target's builds)
+    const bool capped = c->last_build_capped;
+    int rc = build_index(c, B.cpts.data(), n_used, B.idx, hint, nullptr);
+    if (rc == DCREG_OK) rc = build_gap_field(c, B.idx, hint);
+    c->last_build_capped = capped;
+    return rc;
+}
+
 int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask) {
     if (n <= 0) return DCREG_OK;
     hipLaunchKernelGGL(k_out_write, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, keep, pos, out3, (float4 *)nullptr, mask);

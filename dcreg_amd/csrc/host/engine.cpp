@@ -743,6 +743,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_outlier_info")) return sizeof(dcreg_outlier_info);
     if (!std::strcmp(name, "dcreg_visibility_params")) return sizeof(dcreg_visibility_params);
     if (!std::strcmp(name, "dcreg_visibility_info")) return sizeof(dcreg_visibility_info);
+    if (!std::strcmp(name, "dcreg_normal_params")) return sizeof(dcreg_normal_params);
+    if (!std::strcmp(name, "dcreg_normal_info")) return sizeof(dcreg_normal_info);
     return 0;
 }
 

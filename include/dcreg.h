@@ -18,6 +18,8 @@
  *                                                                                 -> dcreg_icp_run_euler
  *       TestRunner::runMethod num_runs loop  icp_test_runner.cpp:331-390         -> dcreg_icp_run_trials
  *       calculatePointToPointError           utils.hpp:538-589                   -> dcreg_p2p_error
+ *       ICPContext::setTargetCloud's pcl::NormalEstimation (targetNormals)  utils.hpp:393-424
+ *                                                                                 -> dcreg_target_normals[_device], dcreg_normals[_device]
  *   raw clouds (not in the reference, which reads clouds a pcl::VoxelGrid filtered beforehand)
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
@@ -787,6 +789,79 @@ int dcreg_visibility_filter_device(dcreg_ctx *, const float *d_xyz, int64_t n, i
                                    dcreg_visibility_info *info);
 int dcreg_target_remove_dynamic(dcreg_ctx *, int64_t n_members, const int64_t *member_ids, const double *member_poses,
                                 const dcreg_visibility_params *, dcreg_visibility_info *info);
+
+/* ---------------- surface normals and curvature ----------------
+ * pcl::NormalEstimation with setKSearch(k) on the device - what the reference's ICPContext::setTargetCloud(target, normal_nn) fills
+ * targetNormals with - for one cloud or for the resident map, with a rule fixed tightly enough that the output is bitwise the numpy
+ * reference of tests/normals_ref.py (INTEGRATION.md lists where it differs from PCL's arithmetic).  For one cloud of n points and the
+ * parameters k (3 .. 32), search_radius (>= 0, 0 = unbounded), orient and viewpoint[3]:
+ *   - used points: a point is used when x, y and z are all finite; the others get NaN in every output.  "Index" is the input index;
+ *   - distances are the float d2 that dcreg_knn computes, (dx*dx + dy*dy) + dz*dz with every operation rounded to float; candidates are
+ *     ranked by the total order (d2, index);
+ *   - the neighbours of point i are the first k used points of the cloud in that order with d2 < bound.  The point itself is a candidate
+ *     like any other, at d2 = 0 (PCL's NormalEstimation over its own input); among exact duplicates the index decides.
+ *     bound = min((float)(search_radius^2), 3.0e38f) for search_radius > 0, and 3.0e38f - the bound of every unbounded search of this
+ *     library - for search_radius = 0;
+ *   - a used point with fewer than k such neighbours is SPARSE: NaN outputs, counted in n_sparse.  (With search_radius = 0 a cloud with
+ *     fewer than k used points makes every used point sparse.)
+ *   - covariance, all in double without contraction (every multiply and add rounds once): with the neighbours q_1 .. q_k in rank order,
+ *     e_j = (double)q_j - (double)p_i per coordinate; s = e_1 + e_2 + ... summed left to right; m = s / k; d_j = e_j - m; the six unique
+ *     C_ab = (sum_j d_ja * d_jb) / k, summed left to right, for xx, xy, xz, yy, yz, zz;
+ *   - eigen-solve: cyclic Jacobi, exactly six sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r the third index, from V = I:
+ *       t = 0 if a_pq == 0, otherwise theta = (a_qq - a_pp) / (2 * a_pq) and t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta*theta + 1))
+ *       (an overflowing theta gives t = 0 by IEEE arithmetic); c = 1 / sqrt(t*t + 1), a division and a square root; s = t * c;
+ *       a_pp <- a_pp - t*a_pq; a_qq <- a_qq + t*a_pq; a_pq <- 0; a_rp <- c*a_rp - s*a_rq; a_rq <- s*a_rp(old) + c*a_rq;
+ *       v_ip <- c*v_ip - s*v_iq; v_iq <- s*v_ip(old) + c*v_iq for i = 0, 1, 2.
+ *     lambda is the diagonal.  The normal is the column of V at the smallest lambda (a tie: the lowest index), as computed - not
+ *     renormalised (its length differs from 1 by rounding only);
+ *   - trace = (lambda_0 + lambda_1) + lambda_2; curvature = |lambda_min| / trace, and 0 when trace == 0 (PCL's surface variation);
+ *   - DCREG_NORMAL_ORIENT_VIEWPOINT (default, viewpoint (0,0,0) as PCL): the normal is negated when
+ *     ((vx - (double)px)*nx + (vy - (double)py)*ny) + (vz - (double)pz)*nz < 0; a dot product of exactly 0 keeps the sign.
+ *     DCREG_NORMAL_ORIENT_NONE leaves the solver's sign;
+ *   - outputs per point, in input order: normal[3] = (float) of the doubles, curvature as a float, and optionally eigenvalues[3]: the
+ *     three lambda ascending - through the exchanges (0,1), (1,2), (0,1), each swapping when the second is smaller - as floats;
+ *   - info: n_in, n_finite, n_sparse and n_out = the points that received a normal (n_finite - n_sparse).
+ * A point's result depends on the cloud and the parameters only: the index decides how fast the neighbours are found, never which.
+ * Radius neighbourhoods (every point inside r, however many) are not offered: their sums would depend on the traversal order.
+ * dcreg_normals reads one cloud as dcreg_set_source[_device] reads it; dcreg_target_normals covers the resident map's points in index
+ * order (dcreg_target_get) and searches the map's own index - on a map with a window index the whole map's, as dcreg_knn.  Any of the
+ * three outputs may be NULL (not wanted), but not all three.  Neither call changes the target, the source, neighbour states, the window
+ * index, places or keyframes; both wait for the stream; repeated calls and calls on another context are bitwise equal.
+ * An unbounded search of an isolated point walks the rings of the grid out to its k-th neighbour, as the outlier filter's does:
+ * search_radius is the practical answer for clouds with far outliers.
+ * DCREG_E_INVALID, before anything is queued: null context or parameters, k outside 3 .. 32, an unknown orient, a search_radius that is
+ * not finite or is negative, a viewpoint that is not finite, stride < 3, n < 0, more than 2^31 - 1 points, a null cloud with n > 0, all
+ * three outputs NULL, a capacity below the map's size.  DCREG_E_STATE: a linearisation in flight; no target (the map form).  A failed
+ * allocation (DCREG_E_NOMEM) leaves the context as it was.  Device memory: the outlier filter's scratch for the cloud and its index
+ * (the cloud form), and up to 28 B per point of outputs. */
+#define DCREG_NORMAL_ORIENT_VIEWPOINT 0
+#define DCREG_NORMAL_ORIENT_NONE 1
+typedef struct dcreg_normal_params {
+    int k;                 /* neighbours per point, the point itself among them (PCL setKSearch; the reference's normal_nn), 3 .. 32 */
+    int orient;            /* DCREG_NORMAL_ORIENT_VIEWPOINT / DCREG_NORMAL_ORIENT_NONE */
+    double search_radius;  /* 0 = unbounded, > 0 = neighbours beyond it do not count (m) */
+    double viewpoint[3];   /* DCREG_NORMAL_ORIENT_VIEWPOINT: normals point to this side (PCL setViewPoint) */
+    double reserved_[2];
+} dcreg_normal_params;
+typedef struct dcreg_normal_info {
+    int64_t n_in;        /* points passed in / points of the map */
+    int64_t n_finite;    /* ... with three finite coordinates (used) */
+    int64_t n_sparse;    /* ... of those, with fewer than k neighbours inside the bound */
+    int64_t n_out;       /* points that received a normal */
+} dcreg_normal_info;
+/* k = 5, DCREG_NORMAL_ORIENT_VIEWPOINT, search_radius = 0, viewpoint (0, 0, 0) */
+int dcreg_default_normal_params(dcreg_normal_params *);
+/* One cloud in (stride_floats floats per point, x y z first); normals_out 3 n floats, curvature_out n floats, eigenvalues_out 3 n floats
+ * (host memory; _device: the cloud and the outputs are device memory).  info may be NULL. */
+int dcreg_normals(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const dcreg_normal_params *, float *normals_out,
+                  float *curvature_out, float *eigenvalues_out, dcreg_normal_info *info);
+int dcreg_normals_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_normal_params *, float *d_normals_out,
+                         float *d_curvature_out, float *d_eigenvalues_out, dcreg_normal_info *info);
+/* The resident map's points in index order; the outputs hold capacity_points points, at least the map's size. */
+int dcreg_target_normals(dcreg_ctx *, const dcreg_normal_params *, float *normals_out, float *curvature_out, float *eigenvalues_out,
+                         int64_t capacity_points, dcreg_normal_info *info);
+int dcreg_target_normals_device(dcreg_ctx *, const dcreg_normal_params *, float *d_normals_out, float *d_curvature_out,
+                                float *d_eigenvalues_out, int64_t capacity_points, dcreg_normal_info *info);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
