@@ -49,6 +49,12 @@ class LinDebug(C.Structure):
                 ("stamps", C.POINTER(C.c_uint64))]
 
 
+class NlinDebug(C.Structure):      # dcreg_nlin_debug: the per-point dump of dcreg_linearize_normals_debug
+    _fields_ = [("nn_idx", C.POINTER(C.c_int32)), ("nn_d2", C.POINTER(C.c_float)), ("flag", C.POINTER(C.c_uint8)),
+                ("normal", C.POINTER(C.c_double)), ("r", C.POINTER(C.c_double)), ("s", C.POINTER(C.c_double)),
+                ("row", C.POINTER(C.c_double))]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("poses", C.c_int64), ("points", C.c_int64), ("points_searched", C.c_int64),
                 ("points_team", C.c_int64)]
@@ -122,7 +128,7 @@ class TrialResult(C.Structure):
 _STRUCTS = {"dcreg_lin_params": LinParams, "dcreg_lin_out": LinOut, "dcreg_lin_debug": LinDebug,
             "dcreg_index_info": IndexInfo, "dcreg_config": Config, "dcreg_analysis": Analysis,
             "dcreg_iter_log": IterLog, "dcreg_icp_result": IcpResult, "dcreg_trial_result": TrialResult,
-            "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats}
+            "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats, "dcreg_nlin_debug": NlinDebug}
 # (VoxelParams / VoxelInfo are defined below and join _STRUCTS there)
 
 # every symbol include/dcreg.h and include/dcreg_debug.h declare
@@ -158,6 +164,8 @@ EXPORTS = [
     "dcreg_default_visibility_params", "dcreg_keyframes_range_images", "dcreg_keyframes_range_images_device", "dcreg_visibility_filter",
     "dcreg_visibility_filter_device", "dcreg_target_remove_dynamic",
     "dcreg_default_normal_params", "dcreg_normals", "dcreg_normals_device", "dcreg_target_normals", "dcreg_target_normals_device",
+    "dcreg_target_normals_keep", "dcreg_target_normals_set", "dcreg_target_normals_set_device", "dcreg_target_normals_kept",
+    "dcreg_target_normals_drop", "dcreg_linearize_normals", "dcreg_linearize_normals_debug", "dcreg_icp_run_normals",
 ]
 
 _lib = None
@@ -1001,6 +1009,15 @@ def load():
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, np_, vp, vp, vp, ni]
         for name in ("dcreg_target_normals", "dcreg_target_normals_device"):
             getattr(L, name).argtypes = [vp, np_, vp, vp, vp, C.c_int64, ni]
+    if hasattr(L, "dcreg_linearize_normals"):  # (likewise)
+        L.dcreg_target_normals_keep.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(NormalInfo)]
+        for name in ("dcreg_target_normals_set", "dcreg_target_normals_set_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64]
+        L.dcreg_target_normals_kept.argtypes = [vp]
+        L.dcreg_target_normals_drop.argtypes = [vp]
+        L.dcreg_linearize_normals.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
+        L.dcreg_linearize_normals_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(NlinDebug)]
+        L.dcreg_icp_run_normals.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1687,6 +1704,91 @@ class Context:
                                                  n, C.byref(info)), "dcreg_target_normals")
         return (nrm[:n] if want_normals else None, cur[:n] if want_curvature else None, eig[:n] if want_eigenvalues else None,
                 _normal_info_dict(info))
+
+    # ---- kept normals and the second engine (include/dcreg.h: dcreg_target_normals_keep .. dcreg_icp_run_normals)
+    def keep_target_normals(self, params=None):
+        """dcreg_target_normals_keep: the map's normals, as target_normals(params) returns them, stay on the device for linearize_normals and
+        icp_run_normals.  -> info dict"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "keep_target_normals")
+        info = NormalInfo()
+        self._check(self._L.dcreg_target_normals_keep(self._h, C.byref(p), C.byref(info)), "dcreg_target_normals_keep")
+        return _normal_info_dict(info)
+
+    def set_target_normals(self, normals=None, dev_ptr=0, n=None, stride=None):
+        """dcreg_target_normals_set[_device]: the caller's normals, one per map point in index order (target_points()), kept as given.
+        normals: [n, c >= 3] float32 on the host, or dev_ptr / n / stride for device memory.  A normal with a non-finite component
+        means that the point has none."""
+        if (normals is None) == (not dev_ptr):
+            raise ValueError("set_target_normals: either normals or dev_ptr is expected")
+        if normals is not None:
+            a = _points(normals, "set_target_normals")
+            self._check(self._L.dcreg_target_normals_set(self._h, a.ctypes.data, a.shape[0], a.shape[1]), "dcreg_target_normals_set")
+            return
+        if n is None or stride is None:
+            raise ValueError("set_target_normals: n and stride are expected with dev_ptr")
+        _check_device_cloud(n, stride, "set_target_normals")
+        self._check(self._L.dcreg_target_normals_set_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride)), "dcreg_target_normals_set_device")
+
+    def target_normals_kept(self):
+        return int(self._L.dcreg_target_normals_kept(self._h))
+
+    def drop_target_normals(self):
+        self._check(self._L.dcreg_target_normals_drop(self._h), "dcreg_target_normals_drop")
+
+    @staticmethod
+    def _nlin_params(params, what):
+        params = params if params is not None else default_lin_params()
+        if not isinstance(params, LinParams):
+            raise ValueError("%s: a default_lin_params(...) block is expected" % what)
+        if params.parameterization != 0:
+            raise ValueError("%s: parameterization must be SO3 (0), got %d" % (what, params.parameterization))
+        if not (np.isfinite(params.search_radius) and params.search_radius > 0.0):
+            raise ValueError("%s: search_radius must be finite and > 0, got %r" % (what, params.search_radius))
+        return params
+
+    def linearize_normals(self, T, params=None, debug=False):
+        """dcreg_linearize_normals at the pose T (4 x 4): the 1-NN point-to-plane rows against the kept normals (include/dcreg.h has the
+        rule) -> dict as linearize(); debug=True adds the per-point dump in source order: nn_idx, nn_d2, flag, normal [n, 3], r, s,
+        row [n, 8]."""
+        params = self._nlin_params(params, "linearize_normals")
+        T = _f64(T)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise ValueError("linearize_normals: a finite 4 x 4 pose is expected")
+        R, t = np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+        out = LinOut()
+        if not debug:
+            self._check(self._L.dcreg_linearize_normals(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), "dcreg_linearize_normals")
+            return self._out_dict(out)
+        n = self.index_info().n_source
+        keep = {"nn_idx": np.full(n, -1, np.int32), "nn_d2": np.full(n, np.inf, np.float32), "flag": np.zeros(n, np.uint8),
+                "normal": np.zeros((n, 3)), "r": np.zeros(n), "s": np.zeros(n), "row": np.zeros((n, 8))}
+        dbg = NlinDebug(keep["nn_idx"].ctypes.data_as(C.POINTER(C.c_int32)), keep["nn_d2"].ctypes.data_as(C.POINTER(C.c_float)),
+                        keep["flag"].ctypes.data_as(C.POINTER(C.c_uint8)), _dp(keep["normal"]), _dp(keep["r"]), _dp(keep["s"]), _dp(keep["row"]))
+        self._check(self._L.dcreg_linearize_normals_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)),
+                    "dcreg_linearize_normals_debug")
+        d = self._out_dict(out)
+        d.update(keep)
+        return d
+
+    def icp_run_normals(self, T0, method, cfg, log_capacity=None):
+        """dcreg_icp_run_normals: icp_run's loop against the kept normals -> (result, logs)"""
+        T0 = _f64(T0)
+        if T0.shape != (4, 4) or not np.isfinite(T0).all():
+            raise ValueError("icp_run_normals: a finite 4 x 4 pose is expected")
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("icp_run_normals: unknown method %r" % (method,))
+        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        cap = cfg.max_iterations if log_capacity is None else log_capacity
+        logs = (IterLog * max(cap, 1))()
+        res = IcpResult()
+        self._check(self._L.dcreg_icp_run_normals(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
+                                                  C.byref(res)), "dcreg_icp_run_normals")
+        n = min(res.iterations, cap)
+        if res.status == 1:
+            n = min(res.iterations - 1, cap)
+        return res, [logs[i] for i in range(max(n, 0))]
 
     # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
     def keyframes_reset(self):

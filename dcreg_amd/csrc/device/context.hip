@@ -284,7 +284,7 @@ static bool poses_finite(int n, const double *R9, const double *t3) {
 
 // A single-pose linearisation at (R, t) with this search radius is about to be queued: make the index it should search the active one -
 // the window if the map wants one (building it around the pose when there is none that covers it), the whole map otherwise.
-static int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius) {
+int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius) {
     if (!roi_wanted(c)) return roi_deactivate(c);
     const double pad = roi_pad_for(c, search_radius);
     if (c->roi_built && pad <= c->roi_pad && roi_covers(c, R, t, pad)) {
@@ -462,6 +462,7 @@ static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double ra
     rc = build_row_words(c, m);
     if (rc) { m.n = 0; return rc; }
     drop_warm(c);            // positions and certificates refer to the old target
+    c->nicp.kept = false;    // ... and the kept normals to the old map's points
     c->order_valid = false;  // ... and the cost estimate of the query groups to the old map
     c->last_pose_valid = false;
     c->n_batch_states = 0;
@@ -483,6 +484,7 @@ static void update_info(dcreg_map_update *info, int64_t offered, int64_t added, 
 static void map_changed(dcreg_ctx *c) {
     c->roi_built = false;
     drop_warm(c);
+    c->nicp.kept = false;
     c->order_valid = false;
     c->last_pose_valid = false;
     c->n_batch_states = 0;
@@ -1464,6 +1466,7 @@ static void free_tmp(LinSlot &S) { S.tmp_dev.clear(); }
 // after a launch that may not have run: what the states hold is unknown
 static void drop_warm(dcreg_ctx *c) {
     c->state_valid = false;
+    c->nicp.warm_valid = false;        // (normal_icp.hip: its positions are the active index's too)
     c->adv_counts_dirty = true;        // (a pass may have run without the k_lin that takes its counts)
     std::fill(c->batch_state_valid.begin(), c->batch_state_valid.end(), (uint8_t)0);
 }

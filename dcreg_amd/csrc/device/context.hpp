@@ -400,6 +400,19 @@ struct dcreg_ctx {
         DevBuf<unsigned long long> cnt;
     };
     NormalBufs nrm;
+    // kept normals and the second engine (normals.hip: dcreg_target_normals_keep / _set / _drop; normal_icp.hip: dcreg_linearize_normals).
+    // normals: float4 {nx, ny, nz, curvature} per map point in INDEX order (the kernel reaches it through the nearest point's original
+    // index: the whole map's index and the window serve alike); dropped with every change of the map's points (context.hip target_commit,
+    // map_changed).  warm: per source point (curve order) the sorted position of its last nearest neighbour - the start bound of its next
+    // search, nothing more; valid for one pair of source and ACTIVE index (context.hip drop_warm).  partials / d_out: the block rows of a
+    // launch and its result row; dbg: the dump buffers of the debug form
+    struct NormalIcpBufs {
+        DevBuf<float4> normals; bool kept = false;
+        DevBuf<uint32_t> warm; bool warm_valid = false;
+        DevBuf<double> partials, d_out;
+        DevBuf<unsigned char> dbg;
+    };
+    NormalIcpBufs nicp;
     double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members
     int opt_visibility_order = 1;                              // the map form votes in index order (0) or in cell order (1)
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
@@ -547,6 +560,7 @@ namespace dcreg {
 int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *p,
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
+int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius);   // context.hip: the index a single-pose linearisation at this pose searches becomes the active one
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
 // deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before

@@ -166,6 +166,14 @@ static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict_
     }
 }
 
+// the kept form: normal (3 floats, `stride` apart) and curvature (null: NaN) of point i -> float4 i
+static __global__ void k_nrm_pack(const float *__restrict__ normal, int64_t stride, const float *__restrict__ curv, int64_t n, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = normal + (size_t)i * (size_t)stride;
+    out[i] = float4{p[0], p[1], p[2], curv ? curv[i] : __builtin_nanf("")};
+}
+
 template <int K>
 void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const NrmArgs &a, float *normal,
                 float *curv, float *eig) {
@@ -185,6 +193,7 @@ int normals_check(dcreg_ctx *c, const dcreg_normal_params *p) {
 struct NormalOut {
     float *normal, *curv, *eig;       // the caller's buffers (null: not wanted)
     bool on_device;
+    bool keep = false;                // normal and curvature go to the context's kept normals instead (nothing is copied out)
 };
 
 // The outputs of n points start as NaN; the nq used points at q (cell order, w = the output index) behind the grid g get theirs; then the
@@ -192,10 +201,11 @@ struct NormalOut {
 int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int64_t n, int64_t n_used, const dcreg_normal_params *p, const NormalOut &o,
                 dcreg_normal_info *info) {
     dcreg_ctx::NormalBufs &B = c->nrm;
-    if ((o.normal && B.normal.ensure(c, 3 * (size_t)n)) || (o.curv && B.curv.ensure(c, (size_t)n)) || (o.eig && B.eig.ensure(c, 3 * (size_t)n)) ||
-        B.cnt.ensure(c, 2))
+    const bool want_n = o.normal || o.keep, want_c = o.curv || o.keep;
+    if ((want_n && B.normal.ensure(c, 3 * (size_t)n)) || (want_c && B.curv.ensure(c, (size_t)n)) || (o.eig && B.eig.ensure(c, 3 * (size_t)n)) ||
+        B.cnt.ensure(c, 2) || (o.keep && c->nicp.normals.ensure(c, (size_t)n)))
         return DCREG_E_NOMEM;
-    float *d_normal = o.normal ? B.normal.data() : nullptr, *d_curv = o.curv ? B.curv.data() : nullptr, *d_eig = o.eig ? B.eig.data() : nullptr;
+    float *d_normal = want_n ? B.normal.data() : nullptr, *d_curv = want_c ? B.curv.data() : nullptr, *d_eig = o.eig ? B.eig.data() : nullptr;
     const float nanf_ = __builtin_nanf("");
     if (d_normal) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, d_normal, 3 * n, nanf_);
     if (d_curv) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, d_curv, n, nanf_);
@@ -219,6 +229,7 @@ int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt, B.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     }
+    if (o.keep) hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, d_normal, (int64_t)3, d_curv, n, c->nicp.normals.data());
     const hipMemcpyKind kind = o.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (o.normal) HIP_TRY(c, hipMemcpyAsync(o.normal, d_normal, sizeof(float) * 3 * (size_t)n, kind, c->stream));
     if (o.curv) HIP_TRY(c, hipMemcpyAsync(o.curv, d_curv, sizeof(float) * (size_t)n, kind, c->stream));
@@ -252,19 +263,53 @@ int normals_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, boo
 }
 
 // dcreg_target_normals*: the whole map's points through the map's own index
+// keep: into the context's kept normals (dcreg_target_normals_keep: no outputs, no capacity)
 int normals_map(dcreg_ctx *c, bool on_device, const dcreg_normal_params *p, float *normal, float *curv, float *eig, int64_t capacity,
-                dcreg_normal_info *info) {
+                dcreg_normal_info *info, bool keep = false) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     if (int rc = normals_check(c, p)) return rc;
-    if (!normal && !curv && !eig) { c->fail("no output buffer: normals, curvature or eigenvalues expected"); return DCREG_E_INVALID; }
+    if (!keep && !normal && !curv && !eig) { c->fail("no output buffer: normals, curvature or eigenvalues expected"); return DCREG_E_INVALID; }
     if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;      // the whole map's index, whichever is active
     const int64_t n = wm.n;
-    if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (!keep && capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
-    const NormalOut o{normal, curv, eig, on_device};
-    return normals_run(c, wm.sorted.data(), n, wm.grid, n, n, p, o, info);
+    const NormalOut o{normal, curv, eig, on_device, keep};
+    if (!keep) return normals_run(c, wm.sorted.data(), n, wm.grid, n, n, p, o, info);
+    c->nicp.kept = false; c->nicp.warm_valid = false;          // (a failed call leaves none)
+    if (int rc = normals_run(c, wm.sorted.data(), n, wm.grid, n, n, p, o, info)) return rc;
+    c->nicp.kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_target_normals_set*: the caller's normals in index order become the kept normals, as given
+int normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, bool on_device) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    const int64_t n_map = c->roi_active ? c->roi_store.n : c->map.n;
+    if (n != n_map) { c->fail("the map holds %lld points, %lld normals were given", (long long)n_map, (long long)n); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->nicp.kept = false; c->nicp.warm_valid = false;
+    if (c->nicp.normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    const float *src = normals;
+    if (!on_device) {
+        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
+        if (c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+        src = c->d_stage.data();
+    } else if (c->stream == c->own_stream) {       // written on the legacy default stream, most likely: as upload_cloud orders a device cloud
+        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    }
+    hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, stride, (const float *)nullptr, n, c->nicp.normals.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->nicp.kept = true;
+    return DCREG_OK;
 }
 
 }  // namespace
@@ -294,5 +339,20 @@ int dcreg_target_normals(dcreg_ctx *c, const dcreg_normal_params *p, float *norm
 int dcreg_target_normals_device(dcreg_ctx *c, const dcreg_normal_params *p, float *d_normals_out, float *d_curvature_out,
                                 float *d_eigenvalues_out, int64_t capacity_points, dcreg_normal_info *info) {
     return normals_map(c, true, p, d_normals_out, d_curvature_out, d_eigenvalues_out, capacity_points, info);
+}
+int dcreg_target_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *info) {
+    return normals_map(c, true, p, nullptr, nullptr, nullptr, 0, info, true);
+}
+int dcreg_target_normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride_floats) { return normals_set(c, normals, n, stride_floats, false); }
+int dcreg_target_normals_set_device(dcreg_ctx *c, const float *d_normals, int64_t n, int64_t stride_floats) {
+    return normals_set(c, d_normals, n, stride_floats, true);
+}
+int dcreg_target_normals_kept(const dcreg_ctx *c) { return c && c->nicp.kept ? 1 : 0; }
+int dcreg_target_normals_drop(dcreg_ctx *c) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    c->nicp.kept = false; c->nicp.warm_valid = false;
+    c->nicp.normals.reset();
+    return DCREG_OK;
 }
 }

@@ -86,6 +86,23 @@ inline void host_step_finish(StepOut &so) {
     if (so.evd_owed) { dcreg::analyzeFinish(so.H, so.an, so.evd_owed); so.evd_owed = 0; }
 }
 
+// the log record of iteration `it`: its sums, the step taken and the pose after it
+inline void log_iteration(dcreg_iter_log &L, int it, const dcreg_lin_out &lo, const StepOut &so, const dcreg_config &cfg, double n_src_all,
+                          const double R[9], const double t[3], Clock::time_point t_iter) {
+    std::memset(&L, 0, sizeof(L));
+    L.iter_count = it;
+    L.effective_points = lo.n_eff; L.corr_pt_count = lo.n_pt;
+    L.fitness = (double)lo.n_pt / n_src_all;                      // :1856
+    L.rmse = std::sqrt(lo.sum_r2 / (double)lo.n_eff);             // :1858
+    L.objective_value = 0.5 * lo.sum_b2;                          // :1919
+    for (int i = 0; i < 6; ++i) { L.gradient[i] = -lo.g[i]; L.update_dx[i] = so.dx[i]; }   // :1918
+    dcreg::stateToMatrix(R, t, L.transform_matrix);               // :1954
+    dcreg::poseError(cfg.gt_matrix, L.transform_matrix, &L.trans_error_vs_gt, &L.rot_error_vs_gt);   // :1976
+    std::memcpy(L.H_upper, lo.H_upper, sizeof(L.H_upper));
+    L.analysis = so.an;
+    L.iter_time_ms = ms_since(t_iter);                            // :1973
+}
+
 // eigenvalue clamp of a symmetric 6x6 (:2020-2029): only when the smallest eigenvalue is <= 1e-12 (or `always`), to 1e-9
 inline void clamp_psd6(dcreg::Mat6 &M, bool always) {
     dcreg::Mat6 Ms;                                                             // SelfAdjointEigenSolver reads one triangle
@@ -199,21 +216,7 @@ int dcreg_icp_run_sharded(dcreg_ctx *ctx, const double R0[9], const double t0[3]
         }
         host_step_finish(so);                                                 // the part of the analysis only the log reads
         std::memcpy(Hlast, so.H, sizeof(Hlast));
-        if (log && it < log_capacity) {
-            dcreg_iter_log &L = log[it];
-            std::memset(&L, 0, sizeof(L));
-            L.iter_count = it;
-            L.effective_points = lo.n_eff; L.corr_pt_count = lo.n_pt;
-            L.fitness = (double)lo.n_pt / n_src_all;                      // :1856
-            L.rmse = std::sqrt(lo.sum_r2 / (double)lo.n_eff);             // :1858
-            L.objective_value = 0.5 * lo.sum_b2;                          // :1919
-            for (int i = 0; i < 6; ++i) { L.gradient[i] = -lo.g[i]; L.update_dx[i] = so.dx[i]; }   // :1918
-            dcreg::stateToMatrix(R, t, L.transform_matrix);               // :1954
-            dcreg::poseError(cfg->gt_matrix, L.transform_matrix, &L.trans_error_vs_gt, &L.rot_error_vs_gt);   // :1976
-            std::memcpy(L.H_upper, lo.H_upper, sizeof(L.H_upper));
-            L.analysis = so.an;
-            L.iter_time_ms = ms_since(t_iter);                            // :1973
-        }
+        if (log && it < log_capacity) log_iteration(log[it], it, lo, so, *cfg, n_src_all, R, t, t_iter);
         res->iterations = it + 1;
         if (st == 1) { res->converged = 1; break; }
     }
@@ -235,6 +238,48 @@ int dcreg_icp_run_sharded_rccl(dcreg_ctx *ctx, const double R0[9], const double 
 int dcreg_icp_run(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
                   const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
     return dcreg_icp_run_sharded(ctx, R0, t0, detection, handling, cfg, 0, nullptr, nullptr, log, log_capacity, res);
+}
+
+// The second engine (include/dcreg.h): the loop above with dcreg_linearize_normals as its linearisation - one launch per iteration, waited
+// for (the kept normals make an iteration a 1-NN search: nothing is queued ahead), then the same host step, log record and covariance.
+int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
+                          const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
+    if (!ctx || !R0 || !t0 || !cfg || !res) return DCREG_E_INVALID;
+    std::memset(res, 0, sizeof(*res));
+    const auto t_total = Clock::now();
+    double R[9], t[3], Hlast[36];
+    std::memcpy(R, R0, sizeof(R)); std::memcpy(t, t0, sizeof(t));
+    for (int i = 0; i < 36; ++i) Hlast[i] = (i % 7 == 0) ? 1.0 : 0.0;
+    const dcreg_lin_params prm = lin_params_of(*cfg);
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_source <= 0 || info.n_target <= 0) {   // :1635-1646
+        res->status = 3;
+        std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
+        covariance_of(false, Hlast, res->icp_cov);
+        return DCREG_OK;
+    }
+    for (int it = 0; it < cfg->max_iterations; ++it) {
+        const auto t_iter = Clock::now();
+        dcreg_lin_out lo;
+        std::memset(&lo, 0, sizeof(lo));
+        if (int rc = dcreg_linearize_normals(ctx, R, t, &prm, &lo)) return rc;
+        if (lo.n_eff < 10) {                            // :1847-1854
+            res->iterations = it + 1; res->converged = 0; res->status = 1;
+            break;
+        }
+        StepOut so;
+        const int st = host_step(lo, detection, handling, *cfg, R, t, so);
+        if (st == 2) { res->iterations = it; res->converged = 0; res->status = 2; break; }
+        std::memcpy(Hlast, so.H, sizeof(Hlast));
+        if (log && it < log_capacity) log_iteration(log[it], it, lo, so, *cfg, (double)info.n_source, R, t, t_iter);
+        res->iterations = it + 1;
+        if (st == 1) { res->converged = 1; break; }
+    }
+    std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
+    covariance_of(res->converged != 0, Hlast, res->icp_cov);
+    res->time_ms = ms_since(t_total);
+    return DCREG_OK;
 }
 
 int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const double *t0, int detection, int handling,
@@ -745,6 +790,7 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_visibility_info")) return sizeof(dcreg_visibility_info);
     if (!std::strcmp(name, "dcreg_normal_params")) return sizeof(dcreg_normal_params);
     if (!std::strcmp(name, "dcreg_normal_info")) return sizeof(dcreg_normal_info);
+    if (!std::strcmp(name, "dcreg_nlin_debug")) return sizeof(dcreg_nlin_debug);
     return 0;
 }
 

@@ -863,6 +863,52 @@ int dcreg_target_normals(dcreg_ctx *, const dcreg_normal_params *, float *normal
 int dcreg_target_normals_device(dcreg_ctx *, const dcreg_normal_params *, float *d_normals_out, float *d_curvature_out,
                                 float *d_eigenvalues_out, int64_t capacity_points, dcreg_normal_info *info);
 
+/* ---------------- kept normals and the 1-NN point-to-plane linearisation ----------------
+ * The map can KEEP one normal per point on the device - float4 {nx, ny, nz, curvature} in index order (the order of dcreg_target_get) -
+ * and a second linearisation registers against them: the correspondence stage of Open3D-style point-to-plane ICP, which is what the
+ * reference fills targetNormals for (ICPContext::setTargetCloud(target, normal_nn); icp_test_runner.cpp:2944-2963, :2974-2981).  A
+ * prior map fits its planes once; an iteration is then a 1-NN search, one 16-byte gather and a row.  The 6x6 system that comes out goes
+ * through the solver seam below unchanged.
+ *   dcreg_target_normals_keep   runs the map form of dcreg_target_normals into the member: bitwise what that call returns for the same
+ *                               parameters (normal and curvature; a sparse point keeps NaN).  Nothing is downloaded; info may be NULL.
+ *   dcreg_target_normals_set    takes the caller's normals, 3 floats first of stride_floats per point, in index order (curvature is
+ *                               stored as NaN); n must equal the map's size.  Stored as given, not renormalised.
+ *   A normal with any non-finite component means "this point has no normal".
+ *   dcreg_target_normals_kept   1 while the member holds normals, else 0 (also for a null context);  _drop frees it.
+ * Every call that changes the map's points or their index order drops the member: dcreg_set_target* in all its forms,
+ * dcreg_target_insert*, dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic, dcreg_set_target_keyframes.
+ * DCREG_E_INVALID, before anything is queued: null context, parameters or normals, the parameter refusals of dcreg_target_normals,
+ * stride_floats < 3, n different from the map's size.  DCREG_E_STATE: a linearisation in flight; no target.  A failed allocation
+ * (DCREG_E_NOMEM) leaves no kept normals.  16 B of device memory per map point.
+ *
+ * The rule of one linearisation (dcreg_linearize_normals; tests/normal_icp_ref.py states it in numpy).  Of the parameter block only
+ * search_radius (R), weight_slope, weight_min and use_weight_derivative are read; parameterization must be DCREG_PARAM_SO3
+ * (DCREG_E_INVALID otherwise).  Every operation rounds once (no contraction).  For each source point p (floats, widened to double):
+ *   - q = R p + t as dcreg_linearize transforms a point: per coordinate ((R_a0*px + R_a1*py) + R_a2*pz) + t_a in double, stored as float;
+ *   - candidates are ranked by the total order (d2, index) with the float d2 that dcreg_knn computes, (dx*dx + dy*dy) + dz*dz, every
+ *     operation rounded to float; j is the first map point in that order (dcreg_knn with k = 1).  Flag 0 (radius gate) unless
+ *     (double)d2 < R*R (icp_test_runner.cpp:2951); a d2 equal to R*R stays out.  A point that passes counts in n_pt;
+ *   - n = the kept normal of j, widened to double.  Flag 2 when j has no normal;
+ *   - e = (double)q - (double)t_j per coordinate; r = (nx*ex + ny*ey) + nz*ez;
+ *   - s = 1 - weight_slope*|r|, and 0 when that is negative; ds = -weight_slope*(r > 0 ? 1 : -1) when use_weight_derivative and
+ *     0 < s < 1, else 0.  Flag 4 unless s > weight_min (the weight and its gate are dcreg_linearize's);
+ *   - m = R^T n, component k = (R_0k*nx + R_1k*ny) + R_2k*nz; w = s + r*ds; A = w * [p x m, m] with
+ *     p x m = (py*m2 - pz*m1, pz*m0 - px*m2, px*m1 - py*m0): the right-perturbation row; b = -(s*r), in double (this engine has no
+ *     float store of the coefficients).  Flag 1: the point is effective and its row is [A0..A5, b, r];
+ *   - the sums, in dcreg_lin_out: H = sum A A^T, g = sum A b, sum_r2, sum_b2 = sum b^2 and n_eff over the effective points, n_pt.
+ * The sums are added in a fixed order (no floating-point atomics): a result depends on the clouds, the normals, the pose and the
+ * parameters only - not on earlier calls (each source point remembers where its last nearest neighbour sits and starts the next search
+ * bounded by that point's distance, inclusive: a speed device only), not on the context, and not on whether the map is searched through
+ * its window index.  Nothing of dcreg_linearize's neighbour states is read or written.
+ * DCREG_E_INVALID: null arguments, a non-finite pose, a search_radius that is not finite and > 0, a parameterization other than SO3.
+ * DCREG_E_STATE: no target, no source, no kept normals, a linearisation in flight.  Waits for the stream. */
+int dcreg_target_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *info);
+int dcreg_target_normals_set(dcreg_ctx *, const float *normals, int64_t n, int64_t stride_floats);
+int dcreg_target_normals_set_device(dcreg_ctx *, const float *d_normals, int64_t n, int64_t stride_floats);
+int dcreg_target_normals_kept(const dcreg_ctx *);
+int dcreg_target_normals_drop(dcreg_ctx *);
+int dcreg_linearize_normals(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
 typedef struct dcreg_config {
@@ -937,6 +983,12 @@ typedef struct dcreg_icp_result {
 
 int dcreg_icp_run(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                   const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
+
+/* The loop of dcreg_icp_run with dcreg_linearize_normals as its linearisation (the map's kept normals: dcreg_target_normals_keep / _set
+ * first, DCREG_E_STATE without them): the same aborts (n_eff < 10, a non-finite step), fitness n_pt / N_src, rmse, convergence test, log
+ * records, covariance and status codes, the same host step.  Single pose only: no batched, sharded or Euler form. */
+int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
+                          const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
 /* n independent scan pairs at once: one host thread per ctx (each ctx owns its clouds, index, stream), every thread runs
  * dcreg_icp_run.  One 100 k-point linearisation fills well under half of an MI355X and the device idles during each host

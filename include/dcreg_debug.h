@@ -32,6 +32,23 @@ typedef struct dcreg_lin_debug {
 int dcreg_linearize_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *,
                           dcreg_lin_out *, dcreg_lin_debug *);
 
+/* per-point dump of dcreg_linearize_normals (original source order; any pointer may be NULL).  flag: 1 effective, 0 radius gate,
+ * 2 the nearest point has no normal, 4 weight <= weight_min.  nn_idx / nn_d2: the nearest map point (original index) and its float d2
+ * for the points that pass the radius gate; -1 / +inf for flag 0.  normal: the kept normal of that point as stored (flag 2: with its
+ * non-finite components), r and s for flags 1 and 4, row = [A0..A5, b, r] for flag 1; everything else is 0. */
+typedef struct dcreg_nlin_debug {
+    int32_t *nn_idx; /* [n] */
+    float *nn_d2;    /* [n] */
+    uint8_t *flag;   /* [n] */
+    double *normal;  /* [3*n] */
+    double *r;       /* [n] */
+    double *s;       /* [n] */
+    double *row;     /* [8*n] */
+} dcreg_nlin_debug;
+/* dcreg_linearize_normals with the dump; searches every point cold and leaves the warm bounds of the plain calls as they were */
+int dcreg_linearize_normals_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *,
+                                  dcreg_nlin_debug *);
+
 /* total duration (ms, HIP events on the ctx stream around ALL kernels of a linearisation) of the timed linearisations since the
  * last reset, and their number; option "time_kernels" = N > 0 brackets every N-th linearisation of slot 0 (an event pair costs ~10 us
  * of host time), 0 = off */
