@@ -166,9 +166,29 @@ EXPORTS = [
     "dcreg_default_normal_params", "dcreg_normals", "dcreg_normals_device", "dcreg_target_normals", "dcreg_target_normals_device",
     "dcreg_target_normals_keep", "dcreg_target_normals_set", "dcreg_target_normals_set_device", "dcreg_target_normals_kept",
     "dcreg_target_normals_drop", "dcreg_linearize_normals", "dcreg_linearize_normals_debug", "dcreg_icp_run_normals",
+    "dcreg_register_frames_normals", "dcreg_icp_run_trials_normals", "dcreg_normals_reserve_slots", "dcreg_normals_reset_slot",
+    "dcreg_normals_batch_begin", "dcreg_normals_batch_end",
 ]
 
 _lib = None
+
+
+def _frames_arg(frames, what):
+    """frames as register_frames takes them -> (xyz [N, c] float32, offsets [n + 1] int64, n)"""
+    if isinstance(frames, tuple):
+        xyz, off = frames
+        xyz = _points(xyz, what)
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+    else:
+        parts = [_points(f, what) for f in frames]
+        if len({f.shape[1] for f in parts}) > 1:
+            raise ValueError("%s: every frame needs the same number of columns, got %s" % (what, sorted({f.shape[1] for f in parts})))
+        off = np.zeros(len(parts) + 1, np.int64)
+        off[1:] = np.cumsum([len(f) for f in parts])
+        xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
+    if len(off) < 1:
+        raise ValueError("%s: offsets need at least one entry" % what)
+    return xyz, off, len(off) - 1
 
 
 class MapUpdate(C.Structure):
@@ -1018,6 +1038,13 @@ def load():
         L.dcreg_linearize_normals.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
         L.dcreg_linearize_normals_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(NlinDebug)]
         L.dcreg_icp_run_normals.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
+    if hasattr(L, "dcreg_register_frames_normals"):  # (likewise)
+        L.dcreg_register_frames_normals.argtypes = L.dcreg_register_frames.argtypes
+        L.dcreg_icp_run_trials_normals.argtypes = L.dcreg_icp_run_trials.argtypes
+        L.dcreg_normals_reserve_slots.argtypes = [vp, C.c_int64, C.c_int]
+        L.dcreg_normals_reset_slot.argtypes = [vp, C.c_int64]
+        L.dcreg_normals_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
+        L.dcreg_normals_batch_end.argtypes = [vp, C.c_int, C.POINTER(LinOut)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2328,6 +2355,76 @@ class Context:
                                                   _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
                     "dcreg_register_frames")
         return [res[i] for i in range(n)]
+
+    def register_frames_normals(self, frames, T0s, method, cfg, slots=0):
+        """dcreg_register_frames_normals: register_frames with the second engine (the map's kept normals: keep_target_normals or
+        set_target_normals first).  Same arguments and records; each record is bitwise set_source(frame) + icp_run_normals(T0)."""
+        xyz, off, n = _frames_arg(frames, "register_frames_normals")
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if T0s.shape[0] != n:
+            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("register_frames_normals: unknown method %r" % (method,))
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        self._check(self._L.dcreg_register_frames_normals(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          xyz.shape[1], _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
+                    "dcreg_register_frames_normals")
+        return [res[i] for i in range(n)]
+
+    def icp_run_trials_normals(self, T0s, method, cfg):
+        """dcreg_icp_run_trials_normals: icp_run_trials with the second engine; each record is bitwise icp_run_normals from its pose"""
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("icp_run_trials_normals: unknown method %r" % (method,))
+        n = T0s.shape[0]
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        self._check(self._L.dcreg_icp_run_trials_normals(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
+                    "dcreg_icp_run_trials_normals")
+        return [res[i] for i in range(n)]
+
+    # ---- the device seam of the two calls above (include/dcreg_debug.h), for the tests
+    def frames_load(self, frames):
+        """dcreg_frames_load: the frames (as register_frames takes them) onto the device"""
+        xyz, off, n = _frames_arg(frames, "frames_load")
+        self._check(self._L.dcreg_frames_load(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1]),
+                    "dcreg_frames_load")
+
+    def normals_reserve_slots(self, n_slots, frames=True):
+        self._check(self._L.dcreg_normals_reserve_slots(self._h, int(n_slots), 1 if frames else 0), "dcreg_normals_reserve_slots")
+
+    def normals_reset_slot(self, slot_id):
+        self._check(self._L.dcreg_normals_reset_slot(self._h, int(slot_id)), "dcreg_normals_reset_slot")
+
+    def normals_batch_begin(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
+        """dcreg_normals_batch_begin: one launch over the poses Ts ([n, 4, 4]); pose i linearises frame frame_ids[i] of the loaded frames
+        (None: the own source) with warm slot state_ids[i] (-1, or None: cold).  -> the number of poses, for normals_batch_end"""
+        params = self._nlin_params(params, "normals_batch_begin")
+        Ts = _f64(Ts).reshape(-1, 4, 4)
+        n = Ts.shape[0]
+        Rs = np.ascontiguousarray(Ts[:, :3, :3]).reshape(n, 9)
+        ts = np.ascontiguousarray(Ts[:, :3, 3]).reshape(n, 3)
+        i32p = C.POINTER(C.c_int32)
+        ids = None if state_ids is None else np.ascontiguousarray(state_ids, dtype=np.int32).reshape(n)
+        fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
+        self._check(self._L.dcreg_normals_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
+                                                      None if fids is None else fids.ctypes.data_as(i32p), C.byref(params)),
+                    "dcreg_normals_batch_begin")
+        return n
+
+    def normals_batch_end(self, n_poses, slot=0):
+        """dcreg_normals_batch_end -> one dict per pose, as linearize_normals returns"""
+        outs = (LinOut * max(int(n_poses), 1))()
+        self._check(self._L.dcreg_normals_batch_end(self._h, int(slot), outs), "dcreg_normals_batch_end")
+        return [self._out_dict(outs[i]) for i in range(int(n_poses))]
+
+    def normals_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
+        return self.normals_batch_end(self.normals_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)
 
     def register_pairs(self, sources, targets, T0s, method, cfg, slots=0):
         """dcreg_register_pairs: many scan pairs in one call, pair p = sources[p] registered against targets[p] from T0s[p].  sources and

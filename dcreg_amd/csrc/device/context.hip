@@ -373,6 +373,7 @@ int build_aux_index(dcreg_ctx *c) {
 int refuse_in_flight(dcreg_ctx *c) {
     if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
     for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    if (c->nicp.batch_pending()) { c->fail("a batched normal linearisation is still in flight (dcreg_normals_batch_end first)"); return DCREG_E_STATE; }
     return DCREG_OK;
 }
 
@@ -1467,6 +1468,7 @@ static void free_tmp(LinSlot &S) { S.tmp_dev.clear(); }
 static void drop_warm(dcreg_ctx *c) {
     c->state_valid = false;
     c->nicp.warm_valid = false;        // (normal_icp.hip: its positions are the active index's too)
+    c->nicp.drop_slots();              // (... and the warm slots of its batched launches go with them)
     c->adv_counts_dirty = true;        // (a pass may have run without the k_lin that takes its counts)
     std::fill(c->batch_state_valid.begin(), c->batch_state_valid.end(), (uint8_t)0);
 }
@@ -1561,6 +1563,7 @@ static int lin_check(dcreg_ctx *c, LinLaunch &L) {
     }
     if (L.slot < 0 || L.slot >= dcreg_ctx::kLinSlots) { c->fail("invalid slot"); return DCREG_E_INVALID; }
     if (c->slots[L.slot].pending) { c->fail("slot %d still has a linearisation in flight", L.slot); return DCREG_E_STATE; }
+    if (c->nicp.batch_pending()) { c->fail("a batched normal linearisation is still in flight (dcreg_normals_batch_end first)"); return DCREG_E_STATE; }
     if (!L.R9 || !L.t3 || L.n_poses < 1) { c->fail("null argument"); return DCREG_E_INVALID; }
     if (L.n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", L.n_poses); return DCREG_E_INVALID; }
     // a pose with a NaN or an infinity is refused before anything is queued or changed (the search's cell keys of such a point are undefined)
@@ -2242,6 +2245,7 @@ void dcreg_backend_destroy(dcreg_ctx *c) {
         if (S.ev0) (void)hipEventDestroy(S.ev0);
         if (S.ev1) (void)hipEventDestroy(S.ev1);
     }
+    for (auto &B : c->nicp.batch) if (B.done) (void)hipEventDestroy(B.done);
     (void)hipEventDestroy(c->ev0); (void)hipEventDestroy(c->ev1);
     (void)hipStreamDestroy(c->own_stream);
     delete c;                         // (the buffers go with it)
@@ -2543,6 +2547,8 @@ int dcreg_reset_warm_state(dcreg_ctx *c, int64_t state_id) {
 int dcreg_linearize_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return linearize_end(c, slot, outs); }
 int dcreg_frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats) {
     if (c) for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    if (c && c->nicp.batch_pending()) { c->fail("a batched normal linearisation is still in flight (dcreg_normals_batch_end first)"); return DCREG_E_STATE; }
+    if (c) c->nicp.drop_slots();           // (normal_icp.hip: the warm slots of the batched form belong to the frames that were loaded)
     return frames_load(c, c->frames, n_frames, xyz, frame_offsets, stride_floats);
 }
 static int frames_reserve_states(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t n_states) {

@@ -406,11 +406,34 @@ struct dcreg_ctx {
     // map_changed).  warm: per source point (curve order) the sorted position of its last nearest neighbour - the start bound of its next
     // search, nothing more; valid for one pair of source and ACTIVE index (context.hip drop_warm).  partials / d_out: the block rows of a
     // launch and its result row; dbg: the dump buffers of the debug form
+    // The batched form (normal_icp.hip k_nlin_batch: dcreg_normals_batch_begin / _end, the engine of dcreg_register_frames_normals): two launch
+    // slots with their own block rows, pose block ([PoseArg x n | slices x n], pinned, and its device copy) and result rows (device, and
+    // the pinned copy `done` is recorded behind), so that one group's kernel runs while the host steps the other.  slots: n_slots warm
+    // arrays of slot_stride words, positions in the WHOLE map's sorted array (batched launches never search the window index), sized for
+    // the largest loaded frame (slots_frames) or for the own source; slot_valid: the array holds the positions of an earlier launch
     struct NormalIcpBufs {
         DevBuf<float4> normals; bool kept = false;
         DevBuf<uint32_t> warm; bool warm_valid = false;
         DevBuf<double> partials, d_out;
         DevBuf<unsigned char> dbg;
+        struct BatchSlot {
+            DevBuf<double> partials, d_out;
+            PinnedBuf<unsigned char> h_poses;
+            DevBuf<unsigned char> d_poses;
+            PinnedBuf<double> h_out;
+            hipEvent_t done = nullptr;
+            int n_poses = 0;
+            bool pending = false;
+            std::vector<int32_t> ids;          // the warm slots the launch in flight writes
+        };
+        BatchSlot batch[2];
+        DevBuf<uint32_t> slots;
+        size_t slot_stride = 0;
+        int64_t n_slots = 0;
+        bool slots_frames = false;
+        std::vector<uint8_t> slot_valid;
+        bool batch_pending() const { return batch[0].pending || batch[1].pending; }
+        void drop_slots() { std::fill(slot_valid.begin(), slot_valid.end(), (uint8_t)0); }
     };
     NormalIcpBufs nicp;
     double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members

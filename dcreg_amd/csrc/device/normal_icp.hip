@@ -4,6 +4,9 @@
 //                  with a one-slot heap on (d2, index) keys, started from the bound the point's last nearest neighbour gives when there is
 //                  one, one gather of the nearest point and one of its float4 normal, the row; then the wave's rows on the matrix cores
 //                  (kernels.hpp wave_gram_mfma) and the block row in LDS, added in wave order
+//   k_nlin_batch   the same for many poses in ONE launch (dcreg_normals_batch_begin: the engine of dcreg_register_frames_normals): block
+//                  (x, pose) runs nlin_point on block x of the pose's own source slice - a frame of the loaded frames, or the context's
+//                  source - with the pose read from a device array, and leaves its row at partials[pose][x]
 //   k_finalize     (kernels.hpp) the block rows in chunk order, the additions of the first engine's batched launches
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  A point's row depends on the clouds, the
 // normals and the pose only; the warm position decides how fast the neighbour is found, never which.
@@ -76,9 +79,71 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin(const float4
     }
 }
 
+// Many poses in one launch.  Block (x, pose): pose = poses[blockIdx.y]; its cloud is slices[pose] = {first point, points} of src (as k_lin's
+// SLICE mode reads one; a block past the end of a short frame's slice exits at once) or, slices == null, the n_src points at src.  The
+// pose's warm positions: warm + P.state * warm_stride (P.state == kNoIdx: search cold, keep nothing; P.fresh: the array holds nothing
+// yet) - a lane reads its word before it writes it, and no other lane's.  The block row goes to partials[pose * n_blocks_x + x], where
+// k_finalize<SLICE> finds it: the rows and additions of the pose's single launch.
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin_batch(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
+                                                                           const float4 *__restrict__ normals,
+                                                                           const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
+                                                                           NlinArgs a, uint32_t *warm, uint32_t warm_stride,
+                                                                           double *__restrict__ partials, uint32_t n_blocks_x) {
+    __shared__ RunList runs[kLinBlock / kWave];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const uint32_t pose_id = blockIdx.y;
+    if (slices) {                                    // (uniform per block: before anything is touched)
+        const uint2 sl = slices[pose_id];
+        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
+        src += sl.x; n_src = sl.y;
+    }
+    const PoseArg &P = poses[pose_id];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    double row[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) row[j] = 0.0;
+    uint8_t flag = 0;
+    if (i < n_src) {
+        uint32_t *w = P.state != kNoIdx ? warm + (size_t)P.state * warm_stride + i : nullptr;
+        const float4 s4 = src[i];
+        NlinPoint o;
+        flag = nlin_point(g, runs[wave], normals, P, a, s4, (w && P.fresh == 0u) ? *w : kNoIdx, row, o);
+        if (w) *w = o.pos;
+    }
+    wave_rows_to_lds(row, flag, runs[wave].stage, gm[wave], cnt);
+    __syncthreads();
+    if (threadIdx.x < kSlots) {
+        double t = 0.0;
+        if (threadIdx.x < 29) {
+            const int e = gram_entry_of_slot(threadIdx.x);
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
+        } else if (threadIdx.x < 31) {
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
+        }
+        partials[((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots + threadIdx.x] = t;
+    }
+}
+
 bool finite_n(const double *v, int n) {
     for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
     return true;
+}
+
+// the launch's arguments for a search on the grid g
+NlinArgs nlin_args(const GridDev &g, const dcreg_lin_params *p) {
+    NlinArgs a;
+    a.radius_sq = p->search_radius * p->search_radius;
+    float bound = (float)a.radius_sq;
+    if ((double)bound < a.radius_sq) bound = std::nextafterf(bound, __builtin_inff());     // the smallest float >= R^2
+    if (!(bound <= 3.0e38f)) bound = 3.0e38f;
+    a.bound_f = bound;
+    a.max_ring = outlier_rings(g, bound);
+    a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
+    return a;
 }
 
 int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_nlin_debug *dbg) {
@@ -99,14 +164,7 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     const uint32_t nb = (uint32_t)((n + kLinBlock - 1) / kLinBlock);
     if (!B.warm.holds((size_t)n)) B.warm_valid = false;          // (a new array holds nothing)
     if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || B.warm.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
-    NlinArgs a;
-    a.radius_sq = p->search_radius * p->search_radius;
-    float bound = (float)a.radius_sq;
-    if ((double)bound < a.radius_sq) bound = std::nextafterf(bound, __builtin_inff());     // the smallest float >= R^2
-    if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-    a.bound_f = bound;
-    a.max_ring = outlier_rings(c->map.grid, bound);
-    a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
+    const NlinArgs a = nlin_args(c->map.grid, p);
     PoseArg P;
     std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
     P.state = kNoIdx; P.fresh = 1;
@@ -154,6 +212,131 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     return DCREG_OK;
 }
 
+// ---- the batched form (context.hpp NormalIcpBufs::BatchSlot).  begin: every refusal before anything is queued or changed, then the pose
+// upload, k_nlin_batch, k_finalize and the copy of the result rows to pinned memory on the context's stream, and the slot's event behind
+// them; end waits for that event - never for what the other slot queued behind it.
+using BatchSlot = dcreg_ctx::NormalIcpBufs::BatchSlot;
+
+int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
+                 const dcreg_lin_params *p) {
+    if (!c) return DCREG_E_INVALID;
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
+    if (!R9 || !t3 || !p || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    BatchSlot &S = B.batch[slot];
+    if (S.pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the normal linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
+    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (!B.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    const std::vector<uint2> &slice = c->frames.slice;
+    int64_t n_max = c->n_src;                         // points of the launch's largest cloud
+    if (frame_ids) {
+        if (slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+        n_max = 0;
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t f = frame_ids[i];
+            if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
+            n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
+        }
+    } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    if (state_ids) {
+        std::vector<uint8_t> seen((size_t)std::max<int64_t>(B.n_slots, 1), 0);
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t sid = state_ids[i];
+            if (sid < 0) continue;
+            if ((int64_t)sid >= B.n_slots) { c->fail("warm slot %d was not reserved (dcreg_normals_reserve_slots: %lld)", sid, (long long)B.n_slots); return DCREG_E_INVALID; }
+            if (seen[(size_t)sid]) { c->fail("warm slot %d is used by two poses of one launch", sid); return DCREG_E_INVALID; }
+            if (B.slots_frames != (frame_ids != nullptr) || (int64_t)B.slot_stride < n_max) {
+                c->fail("the warm slots were reserved for other clouds (dcreg_normals_reserve_slots again)"); return DCREG_E_INVALID;
+            }
+            seen[(size_t)sid] = 1;
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the whole map's index, wherever it lives (context.hpp roi_store): the window index stays as it is, active or not
+    const dcreg_ctx::IndexSet &whole = c->roi_active ? c->roi_store : c->map;
+    const uint32_t nbx = (uint32_t)((n_max + kLinBlock - 1) / kLinBlock);
+    const size_t np = (size_t)n_poses, pose_bytes = np * sizeof(PoseArg), bytes = pose_bytes + (frame_ids ? np * sizeof(uint2) : 0);
+    // (sized for the call's largest cloud and for what the slot has held: the engine's launches stop growing them after the first)
+    const int64_t cloud_max = frame_ids ? c->frames.max_points : c->n_src;
+    const size_t rows_cap = std::max(np, S.d_out.cap() / kSlots) * (size_t)((cloud_max + kLinBlock - 1) / kLinBlock) * kSlots;
+    if (S.partials.ensure(c, std::max(rows_cap, np * nbx * kSlots)) || S.d_out.ensure(c, np * kSlots)) return DCREG_E_NOMEM;
+    if (S.h_out.cap() < np * kSlots) HIP_TRY(c, S.h_out.alloc(std::max<size_t>(np, 256) * kSlots, hipHostMallocDefault));
+    if (bytes > S.d_poses.cap()) {
+        const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2)));
+        HIP_TRY(c, S.h_poses.alloc(cap, hipHostMallocDefault));
+        if (S.d_poses.ensure(c, cap)) return DCREG_E_NOMEM;
+    }
+    if (!S.done) HIP_TRY(c, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    const bool use_slots = state_ids && c->opt_warm;
+    PoseArg *hp = (PoseArg *)S.h_poses.data();
+    S.ids.clear();
+    for (int i = 0; i < n_poses; ++i) {
+        std::memcpy(hp[i].R, R9 + 9 * i, sizeof(hp[i].R)); std::memcpy(hp[i].t, t3 + 3 * i, sizeof(hp[i].t));
+        const bool has = use_slots && state_ids[i] >= 0;
+        hp[i].state = has ? (uint32_t)state_ids[i] : kNoIdx;
+        hp[i].fresh = (has && B.slot_valid[(size_t)state_ids[i]] != 0) ? 0u : 1u;
+        if (has) { B.slot_valid[(size_t)state_ids[i]] = 1; S.ids.push_back(state_ids[i]); }
+    }
+    const uint2 *d_slices = nullptr;
+    if (frame_ids) {
+        uint2 *hs = (uint2 *)(S.h_poses.data() + pose_bytes);
+        for (int i = 0; i < n_poses; ++i) hs[i] = slice[(size_t)frame_ids[i]];
+        d_slices = (const uint2 *)(S.d_poses.data() + pose_bytes);
+    }
+    const NlinArgs a = nlin_args(whole.grid, p);
+    auto failed = [&](hipError_t e, const char *what) {          // something may be queued: what it leaves in the slots is unknown
+        for (int32_t sid : S.ids) B.slot_valid[(size_t)sid] = 0;
+        c->fail("%s failed: %s", what, hipGetErrorString(e));
+        return DCREG_E_DEVICE;
+    };
+    hipError_t e = hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return failed(e, "the pose upload");
+    hipLaunchKernelGGL(k_nlin_batch, dim3(nbx, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, frame_ids ? c->frames.src.data() : c->d_src.data(),
+                       (uint32_t)c->n_src, whole.grid, B.normals.data(), (const PoseArg *)S.d_poses.data(), d_slices, a,
+                       B.slots.data(), (uint32_t)B.slot_stride, S.partials.data(), nbx);
+    if ((e = hipGetLastError()) != hipSuccess) return failed(e, "the k_nlin_batch launch");
+    if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, d_slices);
+    else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, (const uint2 *)nullptr);
+    if ((e = hipGetLastError()) != hipSuccess) return failed(e, "the k_finalize launch");
+    if ((e = hipMemcpyAsync(S.h_out.data(), S.d_out.data(), np * kSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return failed(e, "the result copy");
+    if ((e = hipEventRecord(S.done, c->stream)) != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);                    // (no event to wait for: nothing of this launch stays in flight)
+        return failed(e, "hipEventRecord");
+    }
+    S.n_poses = n_poses;
+    S.pending = true;
+    return DCREG_OK;
+}
+
+int nbatch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
+    if (!c) return DCREG_E_INVALID;
+    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
+    BatchSlot &S = c->nicp.batch[slot];
+    if (!S.pending) { c->fail("slot %d has no batched normal linearisation in flight", slot); return DCREG_E_STATE; }
+    if (!outs) { c->fail("null argument"); return DCREG_E_INVALID; }
+    S.pending = false;
+    const hipError_t e = hipEventSynchronize(S.done);
+    if (e != hipSuccess) {
+        c->nicp.drop_slots();                                     // what the launch left in the slots is unknown
+        c->fail("device fault while waiting for a batched normal linearisation: %s", hipGetErrorString(e));
+        return DCREG_E_DEVICE;
+    }
+    for (int i = 0; i < S.n_poses; ++i) {
+        const double *h = S.h_out.data() + (size_t)i * kSlots;
+        std::memcpy(outs[i].H_upper, h, 21 * sizeof(double));
+        std::memcpy(outs[i].g, h + 21, 6 * sizeof(double));
+        outs[i].sum_r2 = h[27]; outs[i].sum_b2 = h[28];
+        outs[i].n_eff = (int64_t)std::llround(h[29]); outs[i].n_pt = (int64_t)std::llround(h[30]);
+    }
+    return DCREG_OK;
+}
+
 }  // namespace
 }  // namespace dcreg
 
@@ -168,4 +351,33 @@ int dcreg_linearize_normals_debug(dcreg_ctx *c, const double R[9], const double 
     if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }
     return nlin_run(c, R, t, p, out, dbg);
 }
+int dcreg_normals_reserve_slots(dcreg_ctx *c, int64_t n_slots, int frames) {
+    if (!c) return DCREG_E_INVALID;
+    if (n_slots < 0) { c->fail("negative slot count"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    B.n_slots = 0; B.slot_valid.clear(); B.slot_stride = 0;
+    B.slots_frames = frames != 0;
+    const int64_t points = frames ? c->frames.max_points : c->n_src;
+    if (n_slots == 0 || points <= 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t stride = ((size_t)points + 63) & ~(size_t)63;
+    // nothing is cleared: a slot is "fresh" (host-side flag) until its first launch has filled it
+    if (B.slots.ensure(c, stride * (size_t)n_slots)) return DCREG_E_NOMEM;
+    B.slot_stride = stride;
+    B.n_slots = n_slots;
+    B.slot_valid.assign((size_t)n_slots, 0);
+    return DCREG_OK;
+}
+int dcreg_normals_reset_slot(dcreg_ctx *c, int64_t slot_id) {
+    if (!c) return DCREG_E_INVALID;
+    if (slot_id < 0 || slot_id >= c->nicp.n_slots) { c->fail("warm slot %lld was not reserved", (long long)slot_id); return DCREG_E_INVALID; }
+    c->nicp.slot_valid[(size_t)slot_id] = 0;
+    return DCREG_OK;
+}
+int dcreg_normals_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                              const int32_t *frame_ids, const dcreg_lin_params *p) {
+    return nbatch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p);
+}
+int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return nbatch_end(c, slot, outs); }
 }

@@ -309,9 +309,11 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // frame takes its cloud with it, and an empty frame never takes a slot.
 // first_pair >= 0 (with frame_points): trial k is scan pair first_pair + k of dcreg_register_pairs - its source of the pairs' sources,
 // target k of the build batch dcreg_pairs_build left on the device (frame_points[k] = 0: the source or the target is empty)
+// normals: the second engine (dcreg_icp_run_trials_normals, dcreg_register_frames_normals; never pairs) - the launches are
+// dcreg_normals_batch_begin / _end with their warm slots instead of the first engine's and its neighbour states; everything else is shared
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
-                           int64_t first_pair = -1) {
+                           int64_t first_pair = -1, bool normals = false) {
     const auto t_total = Clock::now();
     const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
@@ -336,8 +338,9 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     n_slots = std::min(n_slots, 2 * 65535);
     const int n_groups = n_slots >= 64 ? 2 : 1;
     // one neighbour state per slot; without the memory for them the trials still run, every launch searching from scratch
-    bool have_states = (pairs ? dcreg_pairs_reserve_states(ctx, n_slots) : frames ? dcreg_frames_reserve_states(ctx, n_slots)
-                                                                                  : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
+    bool have_states = (normals ? dcreg_normals_reserve_slots(ctx, n_slots, frames ? 1 : 0)
+                        : pairs ? dcreg_pairs_reserve_states(ctx, n_slots)
+                        : frames ? dcreg_frames_reserve_states(ctx, n_slots) : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
     struct Slot { int64_t trial = -1; int it = 0; double R[9], t[3]; };
     std::vector<Slot> slot((size_t)n_slots);
     struct Group { std::vector<int> live; std::vector<int32_t> ids, fids, gids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
@@ -349,7 +352,10 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         Slot &S = slot[(size_t)si];
         S.trial = next_trial++; S.it = 0;
         std::memcpy(S.R, R0 + 9 * S.trial, sizeof(S.R)); std::memcpy(S.t, t0 + 3 * S.trial, sizeof(S.t));
-        if (have_states) { if (pairs) dcreg_pairs_reset_state(ctx, si); else if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si); }
+        if (have_states) {
+            if (normals) dcreg_normals_reset_slot(ctx, si);
+            else if (pairs) dcreg_pairs_reset_state(ctx, si); else if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si);
+        }
         return true;
     };
     for (int si = 0; si < n_slots; ++si) load(si);
@@ -370,17 +376,19 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
             G.gids[(size_t)j] = (int32_t)S.trial;
             std::memcpy(&G.Rb[(size_t)j * 9], S.R, sizeof(S.R)); std::memcpy(&G.tb[(size_t)j * 3], S.t, sizeof(S.t));
         }
-        const int rc = pairs ? dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm)
+        const int rc = normals ? dcreg_normals_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
+                     : pairs ? dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm)
                      : frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
                               : dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
         G.in_flight = rc == DCREG_OK;
         return rc;
     };
+    auto batch_end = [&](int gi, dcreg_lin_out *outs) { return normals ? dcreg_normals_batch_end(ctx, gi, outs) : dcreg_linearize_batch_end(ctx, gi, outs); };
     auto finish = [&](int gi) -> int {          // wait for the group's results, take the host steps, refill the slots that ended
         Group &G = grp[gi];
         if (!G.in_flight) return DCREG_OK;
         const auto t_a = Clock::now();
-        const int rc = dcreg_linearize_batch_end(ctx, gi, G.outs.data());
+        const int rc = batch_end(gi, G.outs.data());
         G.in_flight = false;
         if (rc != DCREG_OK) return rc;
         t_lin_ms += ms_since(t_a);
@@ -438,13 +446,13 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         if (n_groups == 2 && (rc = finish(1)) != DCREG_OK) break;                        // host steps of group 1 overlap group 0's kernel
     }
     if (rc != DCREG_OK) {                                            // drain whatever is still queued
-        for (int gi = 0; gi < 2; ++gi) if (grp[gi].in_flight) { grp[gi].outs.resize(grp[gi].live.size()); (void)dcreg_linearize_batch_end(ctx, gi, grp[gi].outs.data()); }
+        for (int gi = 0; gi < 2; ++gi) if (grp[gi].in_flight) { grp[gi].outs.resize(grp[gi].live.size()); (void)batch_end(gi, grp[gi].outs.data()); }
         return rc;
     }
     const double total_ms = ms_since(t_total);
     if (std::getenv("DCREG_TRIALS_TIMING"))
-        std::fprintf(stderr, "[dcreg_icp_run_trials] %lld trials in %d slots, %lld group steps: wait for results %.1f us/step, host %.1f us/step, wall %.1f us/step\n",
-                     (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
+        std::fprintf(stderr, "[dcreg_icp_run_trials%s] %lld trials in %d slots, %lld group steps: wait for results %.1f us/step, host %.1f us/step, wall %.1f us/step\n",
+                     normals ? "_normals" : "", (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
                      1e3 * t_host_ms / std::max<int64_t>(n_steps, 1), 1e3 * total_ms / std::max<int64_t>(n_steps, 1));
     for (int64_t i = 0; i < n_trials; ++i) results[i].time_ms = total_ms / (double)n_trials;   // amortised: trials advance together
     return DCREG_OK;
@@ -474,6 +482,38 @@ int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const 
     std::vector<int64_t> points((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
     return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data());
+}
+
+// The second engine's forms of the two calls above (include/dcreg.h): the same checks, the same core, the launches of normal_icp.hip
+int dcreg_icp_run_trials_normals(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
+                                 const dcreg_config *cfg, dcreg_trial_result *results) {
+    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (n_trials == 0) return DCREG_OK;
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
+    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, true);
+}
+
+int dcreg_register_frames_normals(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                                  const double *R0, const double *t0, int detection, int handling, const dcreg_config *cfg, int slots,
+                                  dcreg_trial_result *results) {
+    if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (n_frames == 0) return DCREG_OK;
+    if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
+    if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
+    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
+    if (rc != DCREG_OK) return rc;
+    std::vector<int64_t> points((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, true);
 }
 
 // Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,

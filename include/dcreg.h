@@ -209,7 +209,8 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames, dcreg_register_pairs, the launches, and dcreg_debug.h's dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
+ * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_linearize_normals, dcreg_target_normals_keep / _set / _drop,
+ * the launches, and dcreg_debug.h's dcreg_frames_load, dcreg_normals_reserve_slots (a pending launch slot of dcreg_normals_batch_begin counts as a slot in flight), dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
 int dcreg_linearize_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *);
@@ -986,7 +987,9 @@ int dcreg_icp_run(dcreg_ctx *, const double R0[9], const double t0[3], int detec
 
 /* The loop of dcreg_icp_run with dcreg_linearize_normals as its linearisation (the map's kept normals: dcreg_target_normals_keep / _set
  * first, DCREG_E_STATE without them): the same aborts (n_eff < 10, a non-finite step), fitness n_pt / N_src, rmse, convergence test, log
- * records, covariance and status codes, the same host step.  Single pose only: no batched, sharded or Euler form. */
+ * records, covariance and status codes, the same host step.  One pose per call; dcreg_register_frames_normals and
+ * dcreg_icp_run_trials_normals (below) run many registrations in one call.  There is no pairs form (a target per pair would need
+ * normals per pair), no sharded / RCCL form and no Euler form of this engine. */
 int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                           const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
@@ -1066,6 +1069,24 @@ int dcreg_icp_run_trials(dcreg_ctx *, int n_trials, const double *R0_9, const do
 int dcreg_register_frames(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                           const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
                           dcreg_trial_result *results);
+
+/* The same two calls for the second engine (dcreg_icp_run_normals: 1-NN rows against the map's kept normals).  Arguments, argument
+ * rules, slots, record fields and amortised time_ms are those of dcreg_register_frames / dcreg_icp_run_trials: offsets start at 0 and do
+ * not decrease, non-finite coordinates are refused (DCREG_E_INVALID, nothing runs), an empty frame gets status 3, n_frames == 0 /
+ * n_trials == 0 does nothing, errors are taken against cfg->gt_matrix.  Every iteration of a group of registrations is ONE batched
+ * launch (dcreg_debug.h: dcreg_normals_batch_begin) on the whole map's index, and results[f] is bitwise what dcreg_set_source(frame f) +
+ * dcreg_icp_run_normals(R0 f, t0 f) give on a context with the same map, normals and options - final_transform, iterations, converged,
+ * status (1: n_eff < 10, 2: a non-finite step), final_rmse, final_fitness (of the frame's own point count), corr_num, H_upper and
+ * degenerate_mask; for trials, dcreg_icp_run_normals of the context's own source from each pose.  DCREG_E_STATE: no target, or no kept
+ * normals (dcreg_target_normals_keep / _set first; every change of the map's points drops them) - results are then left untouched.  The
+ * context's own source, the warm positions of dcreg_linearize_normals, the first engine's own and reserved states, the window index and
+ * the kept normals are left as they were (dcreg_register_frames_normals replaces the frames a dcreg_register_frames call left on the
+ * device, and the other way round).  Not available for this engine: scan pairs, the sharded / RCCL forms, the Euler form. */
+int dcreg_register_frames_normals(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                                  const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
+                                  dcreg_trial_result *results);
+int dcreg_icp_run_trials_normals(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection, int handling,
+                                 const dcreg_config *, dcreg_trial_result *results);
 
 /* Many scan pairs registered in one call, each against a target of its own (loop-closure candidates against their submaps, scan-to-scan
  * odometry of a recorded drive, multi-session alignment, accuracy evaluation over a dataset of pairs): pair p = source points

@@ -156,6 +156,27 @@ int dcreg_frames_reset_state(dcreg_ctx *, int64_t state_id);
 int dcreg_frames_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                              const int32_t *frame_ids, const dcreg_lin_params *);
 
+/* internal: the device seam of dcreg_register_frames_normals and dcreg_icp_run_trials_normals (engine.cpp): dcreg_linearize_normals for
+ * n_poses poses in ONE launch.  Pose i linearises frame frame_ids[i] of the frames dcreg_frames_load left on the device or, frame_ids ==
+ * NULL, the context's own source, against the whole map's index and the kept normals; its 31 sums are bitwise what dcreg_set_source(that
+ * cloud) + dcreg_linearize_normals(pose i) return.  dcreg_normals_reserve_slots reserves n_slots warm slots - per point the sorted
+ * position of its last nearest neighbour, a bound of the next search and nothing more - sized for the largest loaded frame (frames != 0)
+ * or for the own source (frames == 0); state_ids[i] names the slot pose i reads and updates (-1, or state_ids == NULL: search cold, keep
+ * nothing), dcreg_normals_reset_slot marks one empty.  A map change, a new source, dcreg_frames_load and an index swap empty all of them;
+ * the context's own warm positions (dcreg_linearize_normals) are neither read nor written.  Two launch slots (0, 1) with their own
+ * buffers: _begin queues the pose upload and the kernels on the context's stream and returns, _end waits for that slot's results only.
+ * While a slot is pending every call that queues work returns DCREG_E_STATE (the list of dcreg_linearize_batch_begin in dcreg.h, and
+ * dcreg_linearize_normals, dcreg_target_normals_*, dcreg_frames_load); so does _begin while a launch of the first engine is pending or gated.
+ * Refusals as dcreg_linearize_normals (SO(3) only, search_radius finite and > 0, every pose finite: DCREG_E_INVALID; no target, no
+ * kept normals, no source / no frames: DCREG_E_STATE), and DCREG_E_INVALID for a frame_id outside the loaded frames or naming an empty
+ * frame, a state_id outside the reserved slots or used twice in one launch, slots reserved for the other kind of cloud, a bad slot;
+ * DCREG_E_STATE for a slot already pending.  Nothing is queued on a refusal. */
+int dcreg_normals_reserve_slots(dcreg_ctx *, int64_t n_slots, int frames);
+int dcreg_normals_reset_slot(dcreg_ctx *, int64_t slot_id);
+int dcreg_normals_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                              const int32_t *frame_ids, const dcreg_lin_params *);
+int dcreg_normals_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
+
 /* internal: the device seam of dcreg_register_pairs (engine.cpp).  dcreg_pairs_plan cuts the pairs into build batches of their targets
  * (batch b = pairs [batch_end[b - 1], batch_end[b]); option "pairs_max_bytes"); dcreg_pairs_sources_load is dcreg_frames_load for the
  * pairs' sources (kept apart from the context's frames); dcreg_pairs_build indexes the targets of one batch (host memory, offsets from 0,
