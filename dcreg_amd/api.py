@@ -168,6 +168,7 @@ EXPORTS = [
     "dcreg_target_normals_drop", "dcreg_linearize_normals", "dcreg_linearize_normals_debug", "dcreg_icp_run_normals",
     "dcreg_register_frames_normals", "dcreg_icp_run_trials_normals", "dcreg_normals_reserve_slots", "dcreg_normals_reset_slot",
     "dcreg_normals_batch_begin", "dcreg_normals_batch_end",
+    "dcreg_target_normals_get", "dcreg_target_normals_get_device", "dcreg_target_normals_follow_info",
 ]
 
 _lib = None
@@ -612,7 +613,11 @@ class NormalInfo(C.Structure):
     _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_sparse", C.c_int64), ("n_out", C.c_int64)]
 
 
-_STRUCTS.update({"dcreg_normal_params": NormalParams, "dcreg_normal_info": NormalInfo})
+class NormalsFollowInfo(C.Structure):
+    _fields_ = [("n_target", C.c_int64), ("n_refit", C.c_int64), ("n_carried", C.c_int64), ("followed", C.c_int), ("reserved_", C.c_int)]
+
+
+_STRUCTS.update({"dcreg_normal_params": NormalParams, "dcreg_normal_info": NormalInfo, "dcreg_normals_follow_info": NormalsFollowInfo})
 NORMAL_ORIENT = {"viewpoint": 0, "none": 1}      # DCREG_NORMAL_ORIENT_VIEWPOINT / DCREG_NORMAL_ORIENT_NONE
 NORMAL_MIN_K, NORMAL_MAX_K = 3, 32
 
@@ -1045,6 +1050,10 @@ def load():
         L.dcreg_normals_reset_slot.argtypes = [vp, C.c_int64]
         L.dcreg_normals_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
         L.dcreg_normals_batch_end.argtypes = [vp, C.c_int, C.POINTER(LinOut)]
+    if hasattr(L, "dcreg_target_normals_get"):  # (likewise)
+        for name in ("dcreg_target_normals_get", "dcreg_target_normals_get_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64]
+        L.dcreg_target_normals_follow_info.argtypes = [vp, C.POINTER(NormalsFollowInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1762,6 +1771,30 @@ class Context:
 
     def drop_target_normals(self):
         self._check(self._L.dcreg_target_normals_drop(self._h), "dcreg_target_normals_drop")
+
+    def kept_target_normals(self, dev_ptr=0, capacity=None):
+        """dcreg_target_normals_get[_device]: the kept normals as they stand, in index order (target_points()) - what a caller persists with
+        a map, and what set_option("normals_follow", 1) keeps up to date through inserts and removals.
+        -> (normals [n, 3] float32, curvature [n] float32); with dev_ptr: 4 floats per point (nx ny nz curvature) go to that device buffer
+        of `capacity` points instead, -> None"""
+        if dev_ptr:
+            if capacity is None or isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= int(capacity) <= OUTLIER_MAX_POINTS:
+                raise ValueError("kept_target_normals: with dev_ptr a capacity of 0 .. 2^31 - 1 points is expected, got %r" % (capacity,))
+            self._check(self._L.dcreg_target_normals_get_device(self._h, C.c_void_p(dev_ptr), int(capacity)), "dcreg_target_normals_get_device")
+            return None
+        if capacity is not None:
+            raise ValueError("kept_target_normals: a capacity is expected with dev_ptr only")
+        n = max(int(self.index_info().n_target), 0)
+        out = np.full((max(n, 1), 4), np.nan, np.float32)
+        self._check(self._L.dcreg_target_normals_get(self._h, out.ctypes.data, n), "dcreg_target_normals_get")
+        return np.ascontiguousarray(out[:n, :3]), np.ascontiguousarray(out[:n, 3])
+
+    def normals_follow_info(self):
+        """dcreg_target_normals_follow_info: what the last update that changed the map did to the kept normals -> dict n_target / n_refit /
+        n_carried / followed (0 dropped or no update yet, 1 refitted incrementally, 2 recomputed in full)"""
+        info = NormalsFollowInfo()
+        self._check(self._L.dcreg_target_normals_follow_info(self._h, C.byref(info)), "dcreg_target_normals_follow_info")
+        return {"n_target": int(info.n_target), "n_refit": int(info.n_refit), "n_carried": int(info.n_carried), "followed": int(info.followed)}
 
     @staticmethod
     def _nlin_params(params, what):

@@ -207,6 +207,8 @@ struct dcreg_ctx {
     double tgt_box[6] = {};
     double build_per_cell = 0.0;   // points per occupied cell when the grid was last derived (a merge that doubles it re-derives)
     int opt_map_update = 1;        // 1: merge into the current grid where possible, 0: always re-derive the grid
+    int opt_normals_follow = 0;    // "normals_follow": 1 = an update refits the kept normals of dcreg_target_normals_keep instead of dropping them
+    double opt_normals_follow_full_share = 0.25;   // "normals_follow_full_share": past this share of dirty points a followed update recomputes everything
     double opt_map_grow_margin = 20.0;   // metres added to each side of the box when an update re-derives the grid
 
     // ---- the WINDOW index of a large map (context.hip roi_ensure).  A prior map whose dense cell table would exceed "max_table_entries" gets
@@ -411,8 +413,20 @@ struct dcreg_ctx {
     // the pinned copy `done` is recorded behind), so that one group's kernel runs while the host steps the other.  slots: n_slots warm
     // arrays of slot_stride words, positions in the WHOLE map's sorted array (batched launches never search the window index), sized for
     // the largest loaded frame (slots_frames) or for the own source; slot_valid: the array holds the positions of an earlier launch
+    // Following the map ("normals_follow", normals.hip normals_follow_*): reach = one float per map point beside its normal, the squared
+    // distance within which a point that comes or goes can change it (the k-th neighbour's d2; the search bound for a sparse point);
+    // from_keep / keep_params: the normals came from dcreg_target_normals_keep with these parameters - the rule an update refits with.
+    // normals_alt / reach_alt: the survivors' entries of a removal, compacted beside the current arrays and swapped in once the update
+    // stands.  f_bits: one bit per cell of the updated map's grid, set where a point came or went; f_list: the dirty points, compacted
+    // in cell order (k_nrm's input).  follow: what the last update that changed the map did to the kept normals
     struct NormalIcpBufs {
         DevBuf<float4> normals; bool kept = false;
+        DevBuf<float> reach; bool from_keep = false;
+        dcreg_normal_params keep_params{};
+        DevBuf<float4> normals_alt, f_list;
+        DevBuf<float> reach_alt;
+        DevBuf<uint32_t> f_bits, f_flag;
+        dcreg_normals_follow_info follow{};
         DevBuf<uint32_t> warm; bool warm_valid = false;
         DevBuf<double> partials, d_out;
         DevBuf<unsigned char> dbg;
@@ -671,6 +685,21 @@ int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t
 // it, 0 = from the density); waits for the stream for *n_used.  outlier_rings: the rings a walk needs to cover a squared radius
 int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used);
 int outlier_rings(const GridDev &g, float bound);
+// normals.hip: the kept normals follow an update of the map ("normals_follow", include/dcreg.h).  normals_follow_wanted: asked BEFORE the
+// update drops them (option on, normals kept, and kept by dcreg_target_normals_keep).  normals_follow_carry (a removal, beside k_crop_raw,
+// before anything is swapped): the survivors' normals and reaches compacted by flag_r / pos_r into the alt arrays; false: out of memory,
+// the normals will not follow.  normals_follow_update (after the update stands and the whole map's index is the active one): the carried
+// entries are swapped in or the arrays grown, the cells of the points that came (added: n_added packed points) and went (old_raw: the n_old
+// points of the map as it was, flag_r their keep flags) are marked, the dirty points found, compacted and refitted - or, past the
+// threshold, everything recomputed.  On any failure the normals stay dropped.  carried: normals_follow_carry ran
+struct FollowChange {
+    const float4 *added = nullptr; int64_t n_added = 0;
+    const float4 *old_raw = nullptr; const uint32_t *flag_r = nullptr; int64_t n_old = 0;
+    bool carried = false;
+};
+bool normals_follow_wanted(const dcreg_ctx *c);
+bool normals_follow_carry(dcreg_ctx *c, int64_t n_old, const uint32_t *flag_r, const uint32_t *pos_r, int64_t kept);
+void normals_follow_update(dcreg_ctx *c, const FollowChange &ch);
 // visibility.hip: one call's votes.  visibility_prepare checks parameters and members on the host (every refusal of include/dcreg.h before
 // anything is queued; poses == null: range images only) and cuts the members into batches; visibility_votes leaves through / observed of
 // the n packed points at `pts` in c->vis (by_w: point i counts at index w_i - a map in cell order); visibility_flags writes the keep flags

@@ -6,6 +6,8 @@
 //                 the last k of K slots; then the lane gathers its k neighbours in rank order (twice: the mean, the covariance - they are
 //                 hot in L2), solves the 3x3 problem with six Jacobi sweeps in registers, orients the normal and writes 12 + 4 (+ 12) bytes
 //                 at the point's input index
+//   k_follow_*    the kept normals follow an update of the map ("normals_follow"): the cells of the points that came or went are marked,
+//                 the map points whose reach touches a marked cell are compacted and go through k_nrm again, the rest is carried
 // A point's result depends on the cloud only: the index decides how fast the neighbours are found, never which.
 #include <cmath>
 #include <cstring>
@@ -94,9 +96,12 @@ static __global__ void k_nrm_fill(float *__restrict__ a, int64_t n, float v) {
 
 // One lane per used point, in the index's cell order (the lanes of a wave search neighbouring cells); the point's input index is in w, and
 // the outputs go there (a null output is not wanted).  cnt[0] += points with a normal, cnt[1] += sparse points (one atomic pair per wave)
+// kept / reach (the map's kept normals, both or neither): {normal, curvature} - NaN for a sparse point - and the point's REACH, the squared
+// distance within which a point that comes or goes can change its result: the k-th neighbour's d2, or the search bound when sparse
 template <int K>
 static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict__ q, uint32_t n, GridDev g, float bound_f, int max_ring, int k,
                                                        NrmArgs a, float *__restrict__ normal, float *__restrict__ curv, float *__restrict__ eig,
+                                                       float4 *__restrict__ kept, float *__restrict__ reach,
                                                        unsigned long long *__restrict__ cnt) {
     __shared__ RunList runs[kBlock / kWave];
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -150,6 +155,7 @@ static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict_
         }
         if (normal) { normal[3 * (size_t)self] = (float)nx; normal[3 * (size_t)self + 1] = (float)ny; normal[3 * (size_t)self + 2] = (float)nz; }
         if (curv) curv[self] = (float)cv;
+        if (kept) { kept[self] = float4{(float)nx, (float)ny, (float)nz, (float)cv}; reach[self] = hp.worst_d2(); }
         if (eig) {
             double l0 = a00, l1 = a11, l2 = a22, t;
             if (l1 < l0) { t = l0; l0 = l1; l1 = t; }
@@ -157,6 +163,10 @@ static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict_
             if (l1 < l0) { t = l0; l0 = l1; l1 = t; }
             eig[3 * (size_t)self] = (float)l0; eig[3 * (size_t)self + 1] = (float)l1; eig[3 * (size_t)self + 2] = (float)l2;
         }
+    } else if (kept) {
+        const float nan_ = __builtin_nanf("");
+        kept[self] = float4{nan_, nan_, nan_, nan_};
+        reach[self] = bound_f;
     }
     const unsigned long long A = __ballot(true), S = __ballot(sparse);
     if ((int)(threadIdx.x & 63) == __ffsll(A) - 1) {
@@ -176,9 +186,29 @@ static __global__ void k_nrm_pack(const float *__restrict__ normal, int64_t stri
 
 template <int K>
 void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const NrmArgs &a, float *normal,
-                float *curv, float *eig) {
+                float *curv, float *eig, float4 *kept = nullptr, float *reach = nullptr) {
     hipLaunchKernelGGL(k_nrm<K>, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, bound, max_ring, k, a, normal, curv, eig,
-                       c->nrm.cnt.data());
+                       kept, reach, c->nrm.cnt.data());
+}
+// the search of a parameter set in a grid, and the launch of the instantiation its k takes
+struct NrmSearch { float bound; int max_ring; NrmArgs a; };
+NrmSearch nrm_search(const GridDev &g, const dcreg_normal_params *p) {
+    NrmSearch s{3.0e38f, -1, {}};
+    if (p->search_radius > 0.0) {
+        s.bound = (float)(p->search_radius * p->search_radius);
+        if (!(s.bound <= 3.0e38f)) s.bound = 3.0e38f;
+        s.max_ring = outlier_rings(g, s.bound);
+    }
+    s.a.vx = p->viewpoint[0]; s.a.vy = p->viewpoint[1]; s.a.vz = p->viewpoint[2]; s.a.orient = p->orient;
+    return s;
+}
+void launch_nrm_k(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, const dcreg_normal_params *p, float *normal, float *curv, float *eig,
+                  float4 *kept, float *reach) {
+    const NrmSearch s = nrm_search(g, p);
+    const int k = p->k;
+    if (k <= 8) launch_nrm<8>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
+    else if (k <= 16) launch_nrm<16>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
+    else launch_nrm<32>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
 }
 
 int normals_check(dcreg_ctx *c, const dcreg_normal_params *p) {
@@ -201,9 +231,11 @@ struct NormalOut {
 int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int64_t n, int64_t n_used, const dcreg_normal_params *p, const NormalOut &o,
                 dcreg_normal_info *info) {
     dcreg_ctx::NormalBufs &B = c->nrm;
-    const bool want_n = o.normal || o.keep, want_c = o.curv || o.keep;
+    // (keep: the kernel writes the kept normals and their reaches itself, at every point of the map - nq == n there)
+    const bool want_n = o.normal != nullptr, want_c = o.curv != nullptr;
+    if (o.keep && nq != n) { c->fail("kept normals need the map's own index"); return DCREG_E_STATE; }
     if ((want_n && B.normal.ensure(c, 3 * (size_t)n)) || (want_c && B.curv.ensure(c, (size_t)n)) || (o.eig && B.eig.ensure(c, 3 * (size_t)n)) ||
-        B.cnt.ensure(c, 2) || (o.keep && c->nicp.normals.ensure(c, (size_t)n)))
+        B.cnt.ensure(c, 2) || (o.keep && (c->nicp.normals.ensure(c, (size_t)n) || c->nicp.reach.ensure(c, (size_t)n))))
         return DCREG_E_NOMEM;
     float *d_normal = want_n ? B.normal.data() : nullptr, *d_curv = want_c ? B.curv.data() : nullptr, *d_eig = o.eig ? B.eig.data() : nullptr;
     const float nanf_ = __builtin_nanf("");
@@ -213,23 +245,10 @@ int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int
     HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[2] = {0, (unsigned long long)n_used};
     if (nq > 0) {
-        const int k = p->k;
-        float bound = 3.0e38f;
-        int max_ring = -1;
-        if (p->search_radius > 0.0) {
-            bound = (float)(p->search_radius * p->search_radius);
-            if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-            max_ring = outlier_rings(g, bound);
-        }
-        NrmArgs a;
-        a.vx = p->viewpoint[0]; a.vy = p->viewpoint[1]; a.vz = p->viewpoint[2]; a.orient = p->orient;
-        if (k <= 8) launch_nrm<8>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
-        else if (k <= 16) launch_nrm<16>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
-        else launch_nrm<32>(c, q, nq, g, bound, max_ring, k, a, d_normal, d_curv, d_eig);
+        launch_nrm_k(c, q, nq, g, p, d_normal, d_curv, d_eig, o.keep ? c->nicp.normals.data() : nullptr, o.keep ? c->nicp.reach.data() : nullptr);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt, B.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     }
-    if (o.keep) hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, d_normal, (int64_t)3, d_curv, n, c->nicp.normals.data());
     const hipMemcpyKind kind = o.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (o.normal) HIP_TRY(c, hipMemcpyAsync(o.normal, d_normal, sizeof(float) * 3 * (size_t)n, kind, c->stream));
     if (o.curv) HIP_TRY(c, hipMemcpyAsync(o.curv, d_curv, sizeof(float) * (size_t)n, kind, c->stream));
@@ -280,6 +299,7 @@ int normals_map(dcreg_ctx *c, bool on_device, const dcreg_normal_params *p, floa
     c->nicp.kept = false; c->nicp.warm_valid = false;          // (a failed call leaves none)
     if (int rc = normals_run(c, wm.sorted.data(), n, wm.grid, n, n, p, o, info)) return rc;
     c->nicp.kept = true;
+    c->nicp.from_keep = true; c->nicp.keep_params = *p;        // (the rule a followed update refits with: "normals_follow")
     return DCREG_OK;
 }
 
@@ -293,6 +313,7 @@ int normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, b
     if (n != n_map) { c->fail("the map holds %lld points, %lld normals were given", (long long)n_map, (long long)n); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     c->nicp.kept = false; c->nicp.warm_valid = false;
+    c->nicp.from_keep = false;                                 // (given normals have no rule to refit with: updates drop them)
     if (c->nicp.normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     const float *src = normals;
     if (!on_device) {
@@ -312,7 +333,198 @@ int normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, b
     return DCREG_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------ kept normals that follow the map ("normals_follow")
+// Candidates are ranked by (d2, index).  An insert appends, so an old point's neighbour set changes only if a new point has a float d2
+// BELOW its k-th d2 (an equal one loses on the index); a removal renumbers the survivors in their old order, so a survivor's set changes
+// only if a removed point had d2 AT OR BELOW its k-th d2.  With the k-th d2 kept per point (its reach; the search bound for a sparse point)
+// the points whose result can have changed are those with a point that came or went within their reach, and everything else is carried
+// bit for bit.  The test below is conservative - it may refit a clean point, never miss a changed one - and works on cells:
+//   k_follow_mark   one bit per cell of the UPDATED map's grid (x sub-cells ignored) for every point that came or went, its cell taken as
+//                   floor((x - o) / h) per axis in doubles and clamped to the grid: a removed point outside the new box lands in the
+//                   nearest cell, and clamping into a convex box that holds the query never increases a distance
+//   k_follow_dirty  one lane per point of the updated map in cell order: the cells whose distance to the point is within its reach are
+//                   walked and their bits tested.  A cell's distance is the exact one between the point and the cell's slab per axis, in
+//                   cells and doubles, against sqrt(reach) / h enlarged by 1e-5 relative and 1e-6 cells: dist2_nofma's float chain can
+//                   come out below the exact value by a few ulp (4e-7 relative at most), the doubles of the cell coordinates by 1e-10
+//                   cells - so the bound never exceeds a float d2 the search would compute for a point of that cell.  A reach of more
+//                   than kFollowRings cells (isolated points of an unbounded search, sparse points of a wide radius) is not walked:
+//                   the point is dirty.  Appended points (index >= n_old) are dirty.
+constexpr int kFollowRings = 3;
+constexpr double kFollowRel = 1.0e-5, kFollowAbs = 1.0e-6;
+
+DCREG_DEVFN int follow_cell(double f, int n) { return (int)fmin(fmax(floor(f), 0.0), (double)(n - 1)); }
+
+// keep != null: the points whose flag is set stay - only the others are marked
+static __global__ void k_follow_mark(const float4 *__restrict__ pts, int64_t n, const uint32_t *__restrict__ keep, GridDev g, uint32_t *__restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || (keep && keep[i] != 0u)) return;
+    const float4 v = pts[i];
+    const int cx = follow_cell(((double)v.x - g.ox) * g.inv_h, g.nx), cy = follow_cell(((double)v.y - g.oy) * g.inv_h, g.ny),
+              cz = follow_cell(((double)v.z - g.oz) * g.inv_h, g.nz);
+    const int64_t cell = ((int64_t)cz * g.ny + cy) * g.nx + cx;
+    atomicOr(bits + (cell >> 5), 1u << (uint32_t)(cell & 31));
+}
+
+// squared distance, in cells, from coordinate f to the slab [c, c + 1)
+DCREG_DEVFN double follow_gap2(double f, int c) {
+    const double lo = (double)c - f, hi = f - (double)(c + 1);
+    const double gp = fmax(fmax(lo, hi), 0.0);
+    return gp * gp;
+}
+
+// flag[i] = 1: the point at sorted position i must be refitted (n + 1 entries, the last 0)
+static __global__ __launch_bounds__(kBlock) void k_follow_dirty(const float4 *__restrict__ sorted, uint32_t n, uint32_t n_old, const float *__restrict__ reach,
+                                                               GridDev g, const uint32_t *__restrict__ bits, uint32_t *__restrict__ flag) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { flag[i] = 0u; return; }
+    const float4 s4 = sorted[i];
+    const uint32_t self = __float_as_uint(s4.w);
+    bool dirty = self >= n_old;
+    if (!dirty) {
+        const double rc = sqrt((double)reach[self]) * g.inv_h * (1.0 + kFollowRel) + kFollowAbs;      // the reach in cells
+        if (!(rc <= (double)kFollowRings)) dirty = true;                                              // (a NaN reach too)
+        else {
+            const double fx = ((double)s4.x - g.ox) * g.inv_h, fy = ((double)s4.y - g.oy) * g.inv_h, fz = ((double)s4.z - g.oz) * g.inv_h;
+            const double r2 = rc * rc;
+            const int x0 = follow_cell(fx - rc, g.nx), x1 = follow_cell(fx + rc, g.nx), y0 = follow_cell(fy - rc, g.ny), y1 = follow_cell(fy + rc, g.ny),
+                      z0 = follow_cell(fz - rc, g.nz), z1 = follow_cell(fz + rc, g.nz);
+            for (int z = z0; z <= z1 && !dirty; ++z) {
+                const double gz = follow_gap2(fz, z);
+                for (int y = y0; y <= y1 && !dirty; ++y) {
+                    const double gyz = gz + follow_gap2(fy, y);
+                    if (gyz > r2) continue;
+                    const int64_t row = ((int64_t)z * g.ny + y) * g.nx;
+                    for (int x = x0; x <= x1; ++x) {
+                        const int64_t cell = row + x;
+                        const bool hit = (bits[cell >> 5] >> (uint32_t)(cell & 31)) & 1u;
+                        if (hit && gyz + follow_gap2(fx, x) <= r2) { dirty = true; break; }
+                    }
+                }
+            }
+        }
+    }
+    flag[i] = dirty ? 1u : 0u;
+}
+
+// the dirty points, compacted in cell order: k_nrm's input
+static __global__ void k_follow_gather(const float4 *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                       float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    out[pos[i]] = sorted[i];
+}
+
+// the survivors' kept normals and reaches, renumbered as k_crop_raw renumbers the points
+static __global__ void k_follow_crop(const float4 *__restrict__ normals, const float *__restrict__ reach, int64_t n, const uint32_t *__restrict__ flag,
+                                     const uint32_t *__restrict__ pos, float4 *__restrict__ normals_out, float *__restrict__ reach_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const uint32_t r = pos[i];
+    normals_out[r] = normals[i];
+    reach_out[r] = reach[i];
+}
+
+// An incremental refit searches from a compacted list: its waves' lanes are neighbours only where dirty points are, and each pays the
+// dirty test of the whole map first.  Past a share of dirty points ("normals_follow_full_share") the update recomputes everything
+// (followed = 2).  DESIGN.md, "Kept normals that follow the map", has the numbers behind the default; no result depends on it.
+
+// dirty test, compaction and refit behind the marks; the arrays already hold the carried entries of the n points of c->map
+int follow_refit(dcreg_ctx *c, int64_t n, int64_t n_old) {
+    dcreg_ctx::NormalIcpBufs &N = c->nicp;
+    const dcreg_ctx::IndexSet &m = c->map;
+    const size_t n1 = (size_t)n + 1;
+    if (N.f_flag.ensure(c, 2 * n1) || c->nrm.cnt.ensure(c, 2)) return DCREG_E_NOMEM;
+    uint32_t *flag = N.f_flag.data(), *pos = flag + n1;
+    hipLaunchKernelGGL(k_follow_dirty, dim3(blocks((int64_t)n1, kBlock)), dim3(kBlock), 0, c->stream, m.sorted.data(), (uint32_t)n, (uint32_t)n_old,
+                       N.reach.data(), m.grid, N.f_bits.data(), flag);
+    if (int rc = outlier_scan_flags(c, flag, pos, n1)) return rc;
+    uint32_t n_dirty = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_dirty, pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if ((double)n_dirty > c->opt_normals_follow_full_share * (double)n) {
+        NormalOut o{nullptr, nullptr, nullptr, true, true};
+        if (int rc = normals_run(c, m.sorted.data(), n, m.grid, n, n, &N.keep_params, o, nullptr)) return rc;
+        N.follow.n_refit = n; N.follow.n_carried = 0; N.follow.followed = 2;
+        return DCREG_OK;
+    }
+    if (n_dirty > 0u) {
+        if (N.f_list.ensure(c, (size_t)n_dirty)) return DCREG_E_NOMEM;
+        hipLaunchKernelGGL(k_follow_gather, dim3(blocks(n, 256)), dim3(256), 0, c->stream, m.sorted.data(), n, flag, pos, N.f_list.data());
+        HIP_TRY(c, hipMemsetAsync(c->nrm.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
+        launch_nrm_k(c, N.f_list.data(), (int64_t)n_dirty, m.grid, &N.keep_params, nullptr, nullptr, nullptr, N.normals.data(), N.reach.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+    }
+    N.follow.n_refit = (int64_t)n_dirty; N.follow.n_carried = n - (int64_t)n_dirty; N.follow.followed = 1;
+    return DCREG_OK;
+}
+
+int follow_update(dcreg_ctx *c, const FollowChange &ch) {
+    dcreg_ctx::NormalIcpBufs &N = c->nicp;
+    const dcreg_ctx::IndexSet &m = c->map;
+    const GridDev &g = m.grid;
+    const int64_t n = m.n;
+    if (n <= 0 || c->roi_active) { c->fail("the kept normals cannot follow: the whole map's index is not the active one"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int64_t n_old = n;                                    // indices below it are points the map had before
+    if (ch.carried) {
+        N.normals.swap(N.normals_alt);
+        N.reach.swap(N.reach_alt);
+    } else {
+        n_old = n - ch.n_added;
+        if (n_old < 0 || N.normals.grow_keep(c, (size_t)n, (size_t)n_old) || N.reach.grow_keep(c, (size_t)n, (size_t)n_old)) return DCREG_E_NOMEM;
+    }
+    const size_t n_words = (size_t)(((int64_t)g.nx * g.ny * g.nz + 31) >> 5);
+    if (N.f_bits.ensure(c, n_words)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(N.f_bits.data(), 0, n_words * sizeof(uint32_t), c->stream));
+    if (ch.n_added > 0)
+        hipLaunchKernelGGL(k_follow_mark, dim3(blocks(ch.n_added, 256)), dim3(256), 0, c->stream, ch.added, ch.n_added, (const uint32_t *)nullptr, g,
+                           N.f_bits.data());
+    if (ch.n_old > 0)
+        hipLaunchKernelGGL(k_follow_mark, dim3(blocks(ch.n_old, 256)), dim3(256), 0, c->stream, ch.old_raw, ch.n_old, ch.flag_r, g, N.f_bits.data());
+    HIP_TRY(c, hipGetLastError());
+    return follow_refit(c, n, n_old);
+}
+
+// dcreg_target_normals_get*: the kept normals as they stand, 4 floats per point
+int normals_get(dcreg_ctx *c, float *out, int64_t capacity, bool on_device) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    const int64_t n = c->roi_active ? c->roi_store.n : c->map.n;
+    if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->nicp.normals.data(), sizeof(float4) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
 }  // namespace
+
+bool normals_follow_wanted(const dcreg_ctx *c) { return c->opt_normals_follow && c->nicp.kept && c->nicp.from_keep; }
+
+bool normals_follow_carry(dcreg_ctx *c, int64_t n_old, const uint32_t *flag_r, const uint32_t *pos_r, int64_t kept) {
+    dcreg_ctx::NormalIcpBufs &N = c->nicp;
+    if (N.normals_alt.ensure(c, (size_t)kept) || N.reach_alt.ensure(c, (size_t)kept)) return false;
+    hipLaunchKernelGGL(k_follow_crop, dim3(blocks(n_old, 256)), dim3(256), 0, c->stream, N.normals.data(), N.reach.data(), n_old, flag_r, pos_r,
+                       N.normals_alt.data(), N.reach_alt.data());
+    return true;
+}
+
+// (the update stands whatever happens here: a failure leaves the normals dropped, as map_changed left them, and says so in the info)
+void normals_follow_update(dcreg_ctx *c, const FollowChange &ch) {
+    c->nicp.follow.n_target = c->map.n;
+    if (follow_update(c, ch) == DCREG_OK) { c->nicp.kept = true; return; }
+    (void)hipGetLastError();
+    c->nicp.kept = false;
+    c->nicp.follow.n_refit = 0; c->nicp.follow.n_carried = 0; c->nicp.follow.followed = 0;
+}
+
 }  // namespace dcreg
 
 using namespace dcreg;
@@ -352,7 +564,15 @@ int dcreg_target_normals_drop(dcreg_ctx *c) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
     c->nicp.kept = false; c->nicp.warm_valid = false;
-    c->nicp.normals.reset();
+    c->nicp.normals.reset(); c->nicp.reach.reset();
+    c->nicp.normals_alt.reset(); c->nicp.reach_alt.reset(); c->nicp.f_list.reset(); c->nicp.f_bits.reset(); c->nicp.f_flag.reset();
+    return DCREG_OK;
+}
+int dcreg_target_normals_get(dcreg_ctx *c, float *out, int64_t capacity_points) { return normals_get(c, out, capacity_points, false); }
+int dcreg_target_normals_get_device(dcreg_ctx *c, float *d_out, int64_t capacity_points) { return normals_get(c, d_out, capacity_points, true); }
+int dcreg_target_normals_follow_info(const dcreg_ctx *c, dcreg_normals_follow_info *info) {
+    if (!c || !info) return DCREG_E_INVALID;
+    *info = c->nicp.follow;
     return DCREG_OK;
 }
 }

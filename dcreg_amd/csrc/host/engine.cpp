@@ -830,6 +830,7 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_visibility_info")) return sizeof(dcreg_visibility_info);
     if (!std::strcmp(name, "dcreg_normal_params")) return sizeof(dcreg_normal_params);
     if (!std::strcmp(name, "dcreg_normal_info")) return sizeof(dcreg_normal_info);
+    if (!std::strcmp(name, "dcreg_normals_follow_info")) return sizeof(dcreg_normals_follow_info);
     if (!std::strcmp(name, "dcreg_nlin_debug")) return sizeof(dcreg_nlin_debug);
     return 0;
 }

@@ -164,6 +164,12 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   points inside its box, density at most twice what the cell edge was sized for), 0 = every update re-derives the grid;
  *   "map_grow_margin" default 20: metres added on each side of the map's box in x and y (not z) when an update re-derives the grid (a
  *                   map that grows along a path re-derives it once per that many metres, not at every keyframe);
+ *   "normals_follow" 0 (default) = every update of the map drops the kept normals; 1 = dcreg_target_insert*, dcreg_target_crop,
+ *                   dcreg_target_remove_outliers and dcreg_target_remove_dynamic refit the kept normals of dcreg_target_normals_keep
+ *                   where the update can have changed them and carry the rest ("kept normals that follow the map" below); read
+ *                   at the time of the update;
+ *   "normals_follow_full_share" default 0.25 (0 .. 1): the share of the map's points a followed update may have to refit before it
+ *                   recomputes all of them instead (the results do not depend on it);
  *   "visibility_max_bytes" default 2^28 (256 MiB): device bytes the range images of one batch of members may take in the visibility
  *                   calls (a batch always holds at least one image; the results do not depend on it);
  *   "roi_index", "roi_margin": the WINDOW index of a large map.  A map whose table ran into that budget is searched through cells that
@@ -877,7 +883,8 @@ int dcreg_target_normals_device(dcreg_ctx *, const dcreg_normal_params *, float 
  *   A normal with any non-finite component means "this point has no normal".
  *   dcreg_target_normals_kept   1 while the member holds normals, else 0 (also for a null context);  _drop frees it.
  * Every call that changes the map's points or their index order drops the member: dcreg_set_target* in all its forms,
- * dcreg_target_insert*, dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic, dcreg_set_target_keyframes.
+ * dcreg_target_insert*, dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic, dcreg_set_target_keyframes
+ * (the updates refit it instead under the option "normals_follow": see "kept normals that follow the map" below).
  * DCREG_E_INVALID, before anything is queued: null context, parameters or normals, the parameter refusals of dcreg_target_normals,
  * stride_floats < 3, n different from the map's size.  DCREG_E_STATE: a linearisation in flight; no target.  A failed allocation
  * (DCREG_E_NOMEM) leaves no kept normals.  16 B of device memory per map point.
@@ -909,6 +916,46 @@ int dcreg_target_normals_set_device(dcreg_ctx *, const float *d_normals, int64_t
 int dcreg_target_normals_kept(const dcreg_ctx *);
 int dcreg_target_normals_drop(dcreg_ctx *);
 int dcreg_linearize_normals(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
+/* ---------------- kept normals that follow the map ----------------
+ * dcreg_set_option("normals_follow", 1) makes the map updates - dcreg_target_insert, _insert_device, _insert_source, dcreg_target_crop,
+ * dcreg_target_remove_outliers, dcreg_target_remove_dynamic - UPDATE the kept normals instead of dropping them, so that a keyframe loop
+ * (dcreg_set_source + dcreg_icp_run_normals + dcreg_target_insert_source, a crop every few keyframes) never pays for the whole map's
+ * normals again.  Default 0: every update drops them, as stated above.  The option is read at the time of the update.  It applies only
+ * while normals are kept AND they came from dcreg_target_normals_keep: the context remembers that call's parameter block and refits
+ * with it.  Normals given by dcreg_target_normals_set have no rule to refit with and are dropped as before; dcreg_set_target* in all
+ * its forms and dcreg_set_target_keyframes always drop (the map is a new one).
+ *   Contract.  After a followed update dcreg_target_normals_get returns, bit for bit, what a fresh context with the same options returns
+ *   after dcreg_set_target(M') + dcreg_target_normals_keep(params), M' = dcreg_target_get of the updated map; a sparse point keeps NaN.
+ *   Everything built on the kept normals is therefore bitwise the fresh context's too: dcreg_linearize_normals, dcreg_icp_run_normals,
+ *   dcreg_register_frames_normals, dcreg_icp_run_trials_normals.  The result does not depend on the sequence of updates, on
+ *   "map_update", on whether an update merged into the grid or re-derived it (dcreg_map_update::rebuilt), or on whether the window
+ *   index was active.  Only the points whose neighbourhood can have changed are computed: a point is refitted when an added or removed
+ *   point may lie within the distance of its k-th neighbour (within the search bound for a sparse point) - a conservative test on the
+ *   cells of the grid, never an approximation; past a share of the map everything is recomputed, with the same bits.
+ *   An update that changes nothing (an insert whose points were all thinned away, a crop that keeps everything) leaves normals and info
+ *   as they were; a refused update leaves the normals bitwise as they were.  If following runs out of memory after the map has changed,
+ *   the update stands and its return code is unchanged: the normals are dropped (dcreg_target_normals_kept 0, followed 0).  The start
+ *   positions of the next searches and the warm slots of the batched form are invalidated by every update exactly as without the option
+ *   (positions in the sorted array move).  Memory: 4 B more per map point beside the 16 B of a kept normal - 20 B in all - from
+ *   dcreg_target_normals_keep on, with the option or without; a removal holds a second copy of both arrays until the next one reuses it.
+ *   dcreg_target_normals_get[_device]   the kept normals in index order, 4 floats per point: nx ny nz curvature (NaN where the point has
+ *                                       none).  What a caller persists with a map.  DCREG_E_STATE: no kept normals, a linearisation in
+ *                                       flight.  DCREG_E_INVALID: null context or buffer, capacity_points below the map's size.  Waits
+ *                                       for the stream.
+ *   dcreg_target_normals_follow_info    what the last update that changed the map did: n_target = the map's size after it, n_refit =
+ *                                       points whose normal it computed (added points included), n_carried = points whose stored normal
+ *                                       was moved over unchanged, followed = 0 not followed (the normals were dropped, or no update
+ *                                       yet), 1 incremental, 2 followed by a full recompute.  n_refit + n_carried == n_target when
+ *                                       followed.  DCREG_E_INVALID: null context or info. */
+typedef struct dcreg_normals_follow_info {
+    int64_t n_target, n_refit, n_carried;
+    int followed;
+    int reserved_;
+} dcreg_normals_follow_info;
+int dcreg_target_normals_get(dcreg_ctx *, float *out, int64_t capacity_points);
+int dcreg_target_normals_get_device(dcreg_ctx *, float *d_out, int64_t capacity_points);
+int dcreg_target_normals_follow_info(const dcreg_ctx *, dcreg_normals_follow_info *info);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
