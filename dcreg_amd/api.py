@@ -55,6 +55,12 @@ class NlinDebug(C.Structure):      # dcreg_nlin_debug: the per-point dump of dcr
                 ("row", C.POINTER(C.c_double))]
 
 
+class GlinDebug(C.Structure):      # dcreg_glin_debug: the per-point dump of dcreg_linearize_gicp_debug
+    _fields_ = [("nn_idx", C.POINTER(C.c_int32)), ("nn_d2", C.POINTER(C.c_float)), ("flag", C.POINTER(C.c_uint8)),
+                ("normal_map", C.POINTER(C.c_double)), ("normal_src", C.POINTER(C.c_double)), ("w", C.POINTER(C.c_double)),
+                ("r", C.POINTER(C.c_double)), ("row", C.POINTER(C.c_double))]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("poses", C.c_int64), ("points", C.c_int64), ("points_searched", C.c_int64),
                 ("points_team", C.c_int64)]
@@ -128,7 +134,8 @@ class TrialResult(C.Structure):
 _STRUCTS = {"dcreg_lin_params": LinParams, "dcreg_lin_out": LinOut, "dcreg_lin_debug": LinDebug,
             "dcreg_index_info": IndexInfo, "dcreg_config": Config, "dcreg_analysis": Analysis,
             "dcreg_iter_log": IterLog, "dcreg_icp_result": IcpResult, "dcreg_trial_result": TrialResult,
-            "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats, "dcreg_nlin_debug": NlinDebug}
+            "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats, "dcreg_nlin_debug": NlinDebug,
+            "dcreg_glin_debug": GlinDebug}
 # (VoxelParams / VoxelInfo are defined below and join _STRUCTS there)
 
 # every symbol include/dcreg.h and include/dcreg_debug.h declare
@@ -169,6 +176,9 @@ EXPORTS = [
     "dcreg_register_frames_normals", "dcreg_icp_run_trials_normals", "dcreg_normals_reserve_slots", "dcreg_normals_reset_slot",
     "dcreg_normals_batch_begin", "dcreg_normals_batch_end",
     "dcreg_target_normals_get", "dcreg_target_normals_get_device", "dcreg_target_normals_follow_info",
+    "dcreg_source_normals_keep", "dcreg_source_normals_set", "dcreg_source_normals_set_device", "dcreg_source_normals_get",
+    "dcreg_source_normals_get_device", "dcreg_source_normals_kept", "dcreg_source_normals_drop", "dcreg_linearize_gicp",
+    "dcreg_linearize_gicp_debug", "dcreg_icp_run_gicp",
 ]
 
 _lib = None
@@ -1054,6 +1064,17 @@ def load():
         for name in ("dcreg_target_normals_get", "dcreg_target_normals_get_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64]
         L.dcreg_target_normals_follow_info.argtypes = [vp, C.POINTER(NormalsFollowInfo)]
+    if hasattr(L, "dcreg_linearize_gicp"):  # (likewise)
+        L.dcreg_source_normals_keep.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(NormalInfo)]
+        for name in ("dcreg_source_normals_set", "dcreg_source_normals_set_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64]
+        for name in ("dcreg_source_normals_get", "dcreg_source_normals_get_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64]
+        L.dcreg_source_normals_kept.argtypes = [vp]
+        L.dcreg_source_normals_drop.argtypes = [vp]
+        L.dcreg_linearize_gicp.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
+        L.dcreg_linearize_gicp_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(GlinDebug)]
+        L.dcreg_icp_run_gicp.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1845,6 +1866,100 @@ class Context:
         res = IcpResult()
         self._check(self._L.dcreg_icp_run_normals(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
                                                   C.byref(res)), "dcreg_icp_run_normals")
+        n = min(res.iterations, cap)
+        if res.status == 1:
+            n = min(res.iterations - 1, cap)
+        return res, [logs[i] for i in range(max(n, 0))]
+
+    # ---- kept source normals and the third engine (include/dcreg.h: dcreg_source_normals_keep .. dcreg_icp_run_gicp)
+    def keep_source_normals(self, params=None):
+        """dcreg_source_normals_keep: the source's own normals, as normals(source, params) returns them, stay on the device beside its
+        points for linearize_gicp and icp_run_gicp.  -> info dict"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "keep_source_normals")
+        info = NormalInfo()
+        self._check(self._L.dcreg_source_normals_keep(self._h, C.byref(p), C.byref(info)), "dcreg_source_normals_keep")
+        return _normal_info_dict(info)
+
+    def set_source_normals(self, normals=None, dev_ptr=0, n=None, stride=None):
+        """dcreg_source_normals_set[_device]: the caller's normals, one per source point in the order the source was given, kept as given.
+        normals: [n, c >= 3] float32 on the host, or dev_ptr / n / stride for device memory.  A normal with a non-finite component
+        means that the point has none."""
+        if (normals is None) == (not dev_ptr):
+            raise ValueError("set_source_normals: either normals or dev_ptr is expected")
+        if normals is not None:
+            a = _points(normals, "set_source_normals")
+            self._check(self._L.dcreg_source_normals_set(self._h, a.ctypes.data, a.shape[0], a.shape[1]), "dcreg_source_normals_set")
+            return
+        if n is None or stride is None:
+            raise ValueError("set_source_normals: n and stride are expected with dev_ptr")
+        _check_device_cloud(n, stride, "set_source_normals")
+        self._check(self._L.dcreg_source_normals_set_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride)), "dcreg_source_normals_set_device")
+
+    def source_normals_kept(self):
+        return int(self._L.dcreg_source_normals_kept(self._h))
+
+    def drop_source_normals(self):
+        self._check(self._L.dcreg_source_normals_drop(self._h), "dcreg_source_normals_drop")
+
+    def kept_source_normals(self, dev_ptr=0, capacity=None):
+        """dcreg_source_normals_get[_device]: the kept source normals in the order the source was given
+        -> (normals [n, 3] float32, curvature [n] float32); with dev_ptr: 4 floats per point (nx ny nz curvature) go to that device buffer
+        of `capacity` points instead, -> None"""
+        if dev_ptr:
+            if capacity is None or isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= int(capacity) <= OUTLIER_MAX_POINTS:
+                raise ValueError("kept_source_normals: with dev_ptr a capacity of 0 .. 2^31 - 1 points is expected, got %r" % (capacity,))
+            self._check(self._L.dcreg_source_normals_get_device(self._h, C.c_void_p(dev_ptr), int(capacity)), "dcreg_source_normals_get_device")
+            return None
+        if capacity is not None:
+            raise ValueError("kept_source_normals: a capacity is expected with dev_ptr only")
+        n = max(int(self.index_info().n_source), 0)
+        out = np.full((max(n, 1), 4), np.nan, np.float32)
+        self._check(self._L.dcreg_source_normals_get(self._h, out.ctypes.data, n), "dcreg_source_normals_get")
+        return np.ascontiguousarray(out[:n, :3]), np.ascontiguousarray(out[:n, 3])
+
+    def linearize_gicp(self, T, params=None, debug=False):
+        """dcreg_linearize_gicp at the pose T (4 x 4): three whitened point-to-plane rows per correspondence from the kept map normals and
+        the kept source normals (include/dcreg.h has the rule; of params only search_radius is read) -> dict as linearize(); debug=True
+        adds the per-point dump in source order: nn_idx, nn_d2, flag, normal_map [n, 3], normal_src [n, 3], w [n, 3, 3], r [n, 3],
+        row [n, 3, 8]."""
+        params = self._nlin_params(params, "linearize_gicp")
+        T = _f64(T)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise ValueError("linearize_gicp: a finite 4 x 4 pose is expected")
+        R, t = np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+        out = LinOut()
+        if not debug:
+            self._check(self._L.dcreg_linearize_gicp(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), "dcreg_linearize_gicp")
+            return self._out_dict(out)
+        n = self.index_info().n_source
+        keep = {"nn_idx": np.full(n, -1, np.int32), "nn_d2": np.full(n, np.inf, np.float32), "flag": np.zeros(n, np.uint8),
+                "normal_map": np.zeros((n, 3)), "normal_src": np.zeros((n, 3)), "w": np.zeros((n, 3, 3)), "r": np.zeros((n, 3)),
+                "row": np.zeros((n, 3, 8))}
+        dbg = GlinDebug(keep["nn_idx"].ctypes.data_as(C.POINTER(C.c_int32)), keep["nn_d2"].ctypes.data_as(C.POINTER(C.c_float)),
+                        keep["flag"].ctypes.data_as(C.POINTER(C.c_uint8)), _dp(keep["normal_map"]), _dp(keep["normal_src"]), _dp(keep["w"]),
+                        _dp(keep["r"]), _dp(keep["row"]))
+        self._check(self._L.dcreg_linearize_gicp_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)),
+                    "dcreg_linearize_gicp_debug")
+        d = self._out_dict(out)
+        d.update(keep)
+        return d
+
+    def icp_run_gicp(self, T0, method, cfg, log_capacity=None):
+        """dcreg_icp_run_gicp: icp_run_normals's loop around linearize_gicp -> (result, logs); a log's rmse is the RMS Mahalanobis distance
+        per effective point"""
+        T0 = _f64(T0)
+        if T0.shape != (4, 4) or not np.isfinite(T0).all():
+            raise ValueError("icp_run_gicp: a finite 4 x 4 pose is expected")
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("icp_run_gicp: unknown method %r" % (method,))
+        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        cap = cfg.max_iterations if log_capacity is None else log_capacity
+        logs = (IterLog * max(cap, 1))()
+        res = IcpResult()
+        self._check(self._L.dcreg_icp_run_gicp(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
+                                               C.byref(res)), "dcreg_icp_run_gicp")
         n = min(res.iterations, cap)
         if res.status == 1:
             n = min(res.iterations - 1, cap)

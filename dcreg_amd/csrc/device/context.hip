@@ -1032,6 +1032,7 @@ static int set_source(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
 // the checked cloud of n points in c->d_aligned.data() (packed as k_pack packs it), with bounds mn .. mx, becomes the source
 static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const double mx[3], bool must_wait) {
     int rc;
+    c->gicp.src_kept = false;          // (the kept source normals belong to the points that go)
     c->d_src_raw.swap(c->d_aligned);
     for (int a = 0; a < 3; ++a) { c->src_mn[a] = mn[a]; c->src_mx[a] = mx[a]; }
     double inv_q;
@@ -2333,6 +2334,10 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "map_update") c->opt_map_update = v != 0.0 ? 1 : 0;    // dcreg_target_insert / _crop: 1 merge into the current grid where possible, 0 always re-derive it
     else if (k == "normals_follow") c->opt_normals_follow = v != 0.0 ? 1 : 0;   // map updates refit the kept normals of dcreg_target_normals_keep instead of dropping them
     else if (k == "normals_follow_full_share") c->opt_normals_follow_full_share = std::min(std::max(v, 0.0), 1.0);   // dirty share past which a followed update recomputes everything (no result depends on it)
+    else if (k == "gicp_epsilon") {                              // dcreg_linearize_gicp: the small eigenvalue of both plane covariances, read at every call
+        if (!(v >= 1.0e-6 && v <= 1.0)) { c->fail("gicp_epsilon is %g: 1e-6 .. 1 expected", v); return DCREG_E_INVALID; }
+        c->opt_gicp_epsilon = v;
+    }
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;

@@ -450,6 +450,18 @@ struct dcreg_ctx {
         void drop_slots() { std::fill(slot_valid.begin(), slot_valid.end(), (uint8_t)0); }
     };
     NormalIcpBufs nicp;
+    // the third engine (gicp.hip: dcreg_linearize_gicp; normals.hip: dcreg_source_normals_keep / _set / _get / _drop).  src_normals: float4
+    // {nx, ny, nz, curvature} per SOURCE point in the context's curve order - lane i of k_glin reads it beside d_src[i]; dropped by every
+    // call that replaces the source's points (context.hip source_commit), left alone by the batched calls.  The warm words are nicp.warm:
+    // both 1-NN engines look for the same nearest point.  tmp: the original-order form of a get; partials / d_out / dbg as nicp's
+    struct GicpBufs {
+        DevBuf<float4> src_normals; bool src_kept = false;
+        DevBuf<float4> tmp;
+        DevBuf<double> partials, d_out;
+        DevBuf<unsigned char> dbg;
+    };
+    GicpBufs gicp;
+    double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
     double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members
     int opt_visibility_order = 1;                              // the map form votes in index order (0) or in cell order (1)
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target
@@ -598,6 +610,17 @@ int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius);   // context.hip: the index a single-pose linearisation at this pose searches becomes the active one
+// normal_icp.hip: what the single-pose 1-NN linearisations (dcreg_linearize_normals, dcreg_linearize_gicp) share.  one_nn_check: every refusal
+// of both, in the header's order, up to "no kept normals" (`what` names the linearisation in the messages).  one_nn_bound: the gate R^2, the
+// cold search bound (the smallest float >= R^2) and the rings that cover it.  The warm words (NormalIcpBufs::warm): _reserve sizes them for
+// the source (a new array holds nothing), _take returns what a plain launch starts from (null: cold) and marks them invalid until _done
+// says that the launch has run; a debug launch calls neither
+struct OneNnBound { double radius_sq; float bound_f; int max_ring; };
+int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what);
+OneNnBound one_nn_bound(const GridDev &g, double search_radius);
+int one_nn_warm_reserve(dcreg_ctx *c);
+const uint32_t *one_nn_warm_take(dcreg_ctx *c);
+void one_nn_warm_done(dcreg_ctx *c);
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
 // deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before

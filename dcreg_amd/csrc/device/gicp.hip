@@ -1,0 +1,211 @@
+// The third engine's linearisation on the device (include/dcreg.h: dcreg_linearize_gicp): plane-to-plane (Generalized-ICP) rows from the
+// map's kept normals and the source's own, with the rule of the header, bitwise the numpy reference of tests/gicp_ref.py.
+//   k_glin<DUMP>   one lane per source point, in the context's curve order: glin_point (gicp.hpp) - transform, k_nlin's 1-NN search from
+//                  the warm bound, one gather of the nearest point and one of its float4 normal, the coalesced float4 load of the point's
+//                  own normal, the covariance of the pair from the two normals, its Cholesky factor and W = L^-1; then THREE rows per
+//                  point, each built just before its pass over the matrix cores (wave_gram3_mfma below: row 0 of every point precedes
+//                  row 1 of any, one accumulator through the 24 steps), and the block row in LDS, added in wave order
+//   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_nlin
+// No floating-point atomics anywhere: the sums are a function of the rows and their order.  The search reads and writes the warm words of
+// k_nlin (context.hpp NormalIcpBufs::warm): both engines look for the same nearest point, and the word decides how fast, never which.
+#include <cmath>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../../include/dcreg_debug.h"
+#include "context.hpp"
+#include "gicp.hpp"
+
+namespace dcreg {
+namespace {
+
+struct GlinDump {
+    int32_t *nn_idx; float *nn_d2; uint8_t *flag; double *normal_map, *normal_src, *w, *r, *row;
+};
+
+// wave_gram_mfma (kernels.hpp) for three rows per lane: pass k stages row_of(k) of all 64 lanes and runs the 8 MFMA steps on the
+// accumulator the pass before left, then the two DPP adds - the Gram matrix of the wave's 192 rows, summed in the fixed order (pass,
+// step).  The rows of a pass are built just before it.  A pass's operand reads are other lanes' stores: within the wave the LDS
+// executes in program order, and the wavefront fences keep the compiler from moving a pass's stores above the reads of the pass before
+// (or its reads above its own stores).  Returns u0 / u1 as wave_gram_mfma does.
+template <class RowOf>
+__device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int lane, double &u0, double &u1) {
+    const int c16 = lane & 15, k = lane >> 4;
+    const double *op = stage + (2 * k + (c16 >> 3)) * kRowStride + (c16 & 7);
+    mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        double row[8];
+        row_of(pass, row);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // the reads of the pass before are over
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int c = 0; c < 8; ++c) stage[lane * kRowStride + c] = row[c];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // every lane's row is staged
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb) {
+            const double x = op[kb * 8 * kRowStride];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
+        }
+    }
+    const bool even = c16 < 8;
+    u0 = even ? acc[0] : acc[2];
+    u1 = even ? acc[1] : acc[3];
+    u0 = dpp_add<0x128, 0xF>(u0);      // row_ror:8 - the lane holding the other half's block entry
+    u1 = dpp_add<0x128, 0xF>(u1);
+}
+
+// warm_in / warm_out / partials: as k_nlin's.  src_normals: float4 per source point in the order of src.  Slot 29 counts the effective
+// POINTS (not rows), slot 30 the points inside the radius.
+template <bool DUMP>
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
+                                                                     const float4 *__restrict__ normals, const float4 *__restrict__ src_normals,
+                                                                     PoseArg P, GlinArgs a, const uint32_t *warm_in, uint32_t *warm_out,
+                                                                     double *__restrict__ partials, GlinDump d) {
+    __shared__ RunList runs[kLinBlock / kWave];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    uint8_t flag = 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    size_t oi = 0;
+    GlinPoint o;
+    if (i < n_src) {
+        const float4 s4 = src[i];
+        sx = s4.x; sy = s4.y; sz = s4.z;
+        flag = glin_point(g, runs[wave], normals, P, a, s4, src_normals + i, warm_in ? warm_in[i] : kNoIdx, o);
+        if (warm_out) warm_out[i] = o.pos;
+        if constexpr (DUMP) {
+            oi = __float_as_uint(s4.w);
+            if (d.nn_idx) d.nn_idx[oi] = o.idx == kNoIdx ? -1 : (int32_t)o.idx;
+            if (d.nn_d2) d.nn_d2[oi] = o.d2;
+            if (d.flag) d.flag[oi] = flag;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (d.normal_map) d.normal_map[3 * oi + k] = o.n[k];
+                if (d.normal_src) d.normal_src[3 * oi + k] = o.m[k];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) if (d.w) d.w[9 * oi + 3 * k + j] = o.w[k][j];
+            }
+        }
+    }
+    // (the wave's RunList is free now: it stages the rows; a lane past the cloud's end or with another flag than 1 carries zero rows)
+    auto row_of = [&](int k, double (&row)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) row[j] = 0.0;
+        if (flag == 1) glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+        if constexpr (DUMP) {
+            if (i < n_src) {
+                if (d.r) d.r[3 * oi + k] = row[7];
+                if (d.row) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) d.row[(3 * oi + k) * 8 + j] = row[j];
+                }
+            }
+        }
+    };
+    double u0, u1;
+    wave_gram3_mfma(row_of, runs[wave].stage, lane, u0, u1);
+    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
+    if ((lane & 15) < 8) {
+        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
+        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
+    }
+    const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
+    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
+    __syncthreads();
+    if (threadIdx.x < kSlots) {
+        double t = 0.0;
+        if (threadIdx.x < 29) {
+            const int e = gram_entry_of_slot(threadIdx.x);
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
+        } else if (threadIdx.x < 31) {
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
+        }
+        partials[(size_t)blockIdx.x * kSlots + threadIdx.x] = t;
+    }
+}
+
+int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_glin_debug *dbg) {
+    if (int rc = one_nn_check(c, R, t, p, out, "GICP")) return rc;
+    if (!c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize_normals (a swap drops the warm positions)
+    if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
+    dcreg_ctx::NormalIcpBufs &W = c->nicp;                // (the warm words are the second engine's)
+    dcreg_ctx::GicpBufs &B = c->gicp;
+    const int64_t n = c->n_src;
+    const uint32_t nb = (uint32_t)((n + kLinBlock - 1) / kLinBlock);
+    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
+    const GridDev &g = c->map.grid;
+    const OneNnBound sb = one_nn_bound(g, p->search_radius);
+    GlinArgs a;
+    a.radius_sq = sb.radius_sq; a.bound_f = sb.bound_f; a.max_ring = sb.max_ring;
+    a.c = 1.0 - c->opt_gicp_epsilon;
+    PoseArg P;
+    std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
+    P.state = kNoIdx; P.fresh = 1;
+    if (dbg) {
+        // one block of device memory for the dump, cut into its arrays (8-byte ones first)
+        const size_t N = (size_t)n;
+        const size_t off_nm = 0, off_ns = off_nm + 24 * N, off_w = off_ns + 24 * N, off_r = off_w + 72 * N, off_row = off_r + 24 * N,
+                     off_idx = off_row + 192 * N, off_d2 = off_idx + 4 * N, off_flag = off_d2 + 4 * N, total = off_flag + N;
+        if (B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
+        unsigned char *b = B.dbg.data();
+        GlinDump d;
+        d.normal_map = dbg->normal_map ? (double *)(b + off_nm) : nullptr; d.normal_src = dbg->normal_src ? (double *)(b + off_ns) : nullptr;
+        d.w = dbg->w ? (double *)(b + off_w) : nullptr; d.r = dbg->r ? (double *)(b + off_r) : nullptr;
+        d.row = dbg->row ? (double *)(b + off_row) : nullptr;
+        d.nn_idx = dbg->nn_idx ? (int32_t *)(b + off_idx) : nullptr; d.nn_d2 = dbg->nn_d2 ? (float *)(b + off_d2) : nullptr;
+        d.flag = dbg->flag ? b + off_flag : nullptr;
+        hipLaunchKernelGGL(k_glin<true>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, W.normals.data(),
+                           B.src_normals.data(), P, a, (const uint32_t *)nullptr, (uint32_t *)nullptr, B.partials.data(), d);
+        HIP_TRY(c, hipGetLastError());
+        if (d.normal_map) HIP_TRY(c, hipMemcpyAsync(dbg->normal_map, d.normal_map, 24 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.normal_src) HIP_TRY(c, hipMemcpyAsync(dbg->normal_src, d.normal_src, 24 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.w) HIP_TRY(c, hipMemcpyAsync(dbg->w, d.w, 72 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.r) HIP_TRY(c, hipMemcpyAsync(dbg->r, d.r, 24 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.row) HIP_TRY(c, hipMemcpyAsync(dbg->row, d.row, 192 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.nn_idx) HIP_TRY(c, hipMemcpyAsync(dbg->nn_idx, d.nn_idx, 4 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.nn_d2) HIP_TRY(c, hipMemcpyAsync(dbg->nn_d2, d.nn_d2, 4 * N, hipMemcpyDeviceToHost, c->stream));
+        if (d.flag) HIP_TRY(c, hipMemcpyAsync(dbg->flag, d.flag, N, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        const uint32_t *warm_in = one_nn_warm_take(c);
+        hipLaunchKernelGGL(k_glin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, W.normals.data(),
+                           B.src_normals.data(), P, a, warm_in, W.warm.data(), B.partials.data(), GlinDump{});
+        HIP_TRY(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    double h[kSlots];
+    HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (!dbg) one_nn_warm_done(c);
+    std::memcpy(out->H_upper, h, 21 * sizeof(double));
+    std::memcpy(out->g, h + 21, 6 * sizeof(double));
+    out->sum_r2 = h[27]; out->sum_b2 = h[28];
+    out->n_eff = (int64_t)std::llround(h[29]); out->n_pt = (int64_t)std::llround(h[30]);
+    return DCREG_OK;
+}
+
+}  // namespace
+}  // namespace dcreg
+
+using namespace dcreg;
+
+extern "C" {
+int dcreg_linearize_gicp(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out) {
+    return glin_run(c, R, t, p, out, nullptr);
+}
+int dcreg_linearize_gicp_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
+                               dcreg_glin_debug *dbg) {
+    if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }
+    return glin_run(c, R, t, p, out, dbg);
+}
+}

@@ -1,0 +1,119 @@
+// Per-thread device functions of the third engine (include/dcreg.h: dcreg_linearize_gicp): one source point against the map's kept
+// normals AND the source's own - transform, exact 1-NN on the cell grid, radius gate (all three nlin_point's), then the plane-to-plane
+// covariance of the pair formed from the two normals in registers, its Cholesky factor, the whitening matrix W = L^-1 and the three
+// point-to-plane rows whose pseudo-normals are W's rows.  The rule is the header's, operation by operation; tests/gicp_ref.py states
+// it in numpy.  Included by gicp.hip (the kernel and the reduction) and, like normal_icp.hpp, compiled for the host under
+// DCREG_HOST_EMUL by the test suite's replay (tests/host_emul/).
+#pragma once
+#include "normal_icp.hpp"
+
+namespace dcreg {
+
+struct GlinArgs {
+    double radius_sq;             // R^2 in double: the gate (double)d2 < R^2
+    float bound_f;                // the cold search bound: the smallest float >= R^2
+    int max_ring;                 // rings that cover it
+    double c;                     // 1 - epsilon ("gicp_epsilon"), formed once on the host
+};
+
+// what a point leaves for its rows and for the debug dump (flag 0: idx kNoIdx, d2 +inf; the normals as stored for every point that
+// passed the radius gate; w and e are zero unless the flag is 1)
+struct GlinPoint {
+    uint32_t idx, pos;            // original index of the nearest point and its position in the sorted array (kNoIdx: none inside the bound)
+    float d2;
+    double n[3], m[3];            // the kept normal of the nearest map point, the kept normal of the source point
+    double w[3][3];               // W = L^-1, lower triangular: row k is the pseudo-normal a_k
+    double e[3];                  // (double)q - (double)t_j
+    uint32_t n_eval;              // candidates the search evaluated (host replay)
+};
+
+// One point of dcreg_linearize_gicp up to its whitening matrix.  warm_pos: as nlin_point's - it bounds the search, never decides it.
+// normals: float4 per map point in index order; m4p: where the point's own kept normal lies (read after the two gathers, and only by a
+// point that passed the radius gate: nothing of it is live across the search).  Returns the flag (0 radius gate, 2 the nearest map
+// point has no normal, 3 the source point has none, 5 the covariance is not positive definite, 1 effective).
+DCREG_DEVFN uint8_t glin_point(const GridDev &g, RunList &rl, const float4 *normals, const PoseArg &P, const GlinArgs &a, const float4 &s4,
+                               const float4 *m4p, uint32_t warm_pos, GlinPoint &o) {
+#pragma clang fp contract(off)
+    const double px = (double)s4.x, py = (double)s4.y, pz = (double)s4.z;
+    float qx, qy, qz;
+    body_to_global(P, px, py, pz, qx, qy, qz);
+    HeapOne hp;
+    float bound_f = a.bound_f;
+    hp.start = (uint64_t)__float_as_uint(bound_f) << 32;                   // index 0: d2 == bound does not enter
+    if (warm_pos < g.n_pts) {
+        const float d2w = dist2_nofma(qx, qy, qz, g.pts[warm_pos]);
+        if (d2w < bound_f) {                                               // (finite and >= 0: its bit pattern + 1 is the next float up)
+            const uint32_t up = __float_as_uint(d2w) + 1u;
+            bound_f = __uint_as_float(up);
+            hp.start = (uint64_t)up << 32;                                 // every key (d2w, any index) enters
+        }
+    }
+    knn_search<HeapOne>(g, rl, qx, qy, qz, bound_f, a.max_ring, hp);
+    o.idx = kNoIdx; o.pos = kNoIdx; o.d2 = __builtin_inff(); o.n_eval = hp.n_eval;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o.n[k] = 0.0; o.m[k] = 0.0; o.e[k] = 0.0;
+        o.w[k][0] = o.w[k][1] = o.w[k][2] = 0.0;
+    }
+    if (hp.pos == kNoIdx) return 0;
+    const float d2 = __uint_as_float((uint32_t)(hp.key >> 32));
+    if (!((double)d2 < a.radius_sq)) return 0;
+    o.pos = hp.pos; o.idx = (uint32_t)hp.key; o.d2 = d2;
+    const float4 tj = g.pts[hp.pos];
+    const float4 n4 = normals[o.idx];
+    const float4 m4 = *m4p;
+    const double nx = (double)n4.x, ny = (double)n4.y, nz = (double)n4.z;
+    const double mx = (double)m4.x, my = (double)m4.y, mz = (double)m4.z;
+    o.n[0] = nx; o.n[1] = ny; o.n[2] = nz;
+    o.m[0] = mx; o.m[1] = my; o.m[2] = mz;
+    if (!(nlin_finite(n4.x) && nlin_finite(n4.y) && nlin_finite(n4.z))) return 2;
+    if (!(nlin_finite(m4.x) && nlin_finite(m4.y) && nlin_finite(m4.z))) return 3;
+    // u = R m, each component summed as body_to_global sums it
+    const double ux = (P.R[0] * mx + P.R[1] * my) + P.R[2] * mz;
+    const double uy = (P.R[3] * mx + P.R[4] * my) + P.R[5] * mz;
+    const double uz = (P.R[6] * mx + P.R[7] * my) + P.R[8] * mz;
+    // S = 2 I - c (n n^T + u u^T), lower triangle
+    const double s00 = 2.0 - a.c * (nx * nx + ux * ux);
+    const double s10 = 0.0 - a.c * (ny * nx + uy * ux);
+    const double s11 = 2.0 - a.c * (ny * ny + uy * uy);
+    const double s20 = 0.0 - a.c * (nz * nx + uz * ux);
+    const double s21 = 0.0 - a.c * (nz * ny + uz * uy);
+    const double s22 = 2.0 - a.c * (nz * nz + uz * uz);
+    // S = L L^T
+    const double l00 = sqrt(s00);
+    const double l10 = s10 / l00;
+    const double l20 = s20 / l00;
+    const double d11 = s11 - l10 * l10;
+    const double l11 = sqrt(d11);
+    const double l21 = (s21 - l20 * l10) / l11;
+    const double d22 = (s22 - l20 * l20) - l21 * l21;
+    const double l22 = sqrt(d22);
+    if (!(s00 > 0.0 && d11 > 0.0 && d22 > 0.0)) return 5;
+    // W = L^-1
+    const double w00 = 1.0 / l00, w11 = 1.0 / l11, w22 = 1.0 / l22;
+    const double w10 = -(l10 * w00) * w11;
+    const double w21 = -(l21 * w11) * w22;
+    const double w20 = -(l20 * w00 + l21 * w10) * w22;
+    o.w[0][0] = w00;
+    o.w[1][0] = w10; o.w[1][1] = w11;
+    o.w[2][0] = w20; o.w[2][1] = w21; o.w[2][2] = w22;
+    o.e[0] = (double)qx - (double)tj.x; o.e[1] = (double)qy - (double)tj.y; o.e[2] = (double)qz - (double)tj.z;
+    return 1;
+}
+
+// Row k of a flag-1 point: the second engine's row with weight 1 for the pseudo-normal a = (ax, ay, az), row k of W (its structural
+// zeros are multiplied and added like any other value).  p: the source point, e: q - t_j.
+DCREG_DEVFN void glin_row(const PoseArg &P, double px, double py, double pz, double ax, double ay, double az, double ex, double ey, double ez,
+                          double (&row)[8]) {
+#pragma clang fp contract(off)
+    const double r = (ax * ex + ay * ey) + az * ez;
+    const double m0 = (P.R[0] * ax + P.R[3] * ay) + P.R[6] * az;
+    const double m1 = (P.R[1] * ax + P.R[4] * ay) + P.R[7] * az;
+    const double m2 = (P.R[2] * ax + P.R[5] * ay) + P.R[8] * az;
+    row[0] = py * m2 - pz * m1; row[1] = pz * m0 - px * m2; row[2] = px * m1 - py * m0;
+    row[3] = m0; row[4] = m1; row[5] = m2;
+    row[6] = -r;
+    row[7] = r;
+}
+
+}  // namespace dcreg

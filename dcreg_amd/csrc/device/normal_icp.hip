@@ -135,35 +135,22 @@ bool finite_n(const double *v, int n) {
 
 // the launch's arguments for a search on the grid g
 NlinArgs nlin_args(const GridDev &g, const dcreg_lin_params *p) {
+    const OneNnBound b = one_nn_bound(g, p->search_radius);
     NlinArgs a;
-    a.radius_sq = p->search_radius * p->search_radius;
-    float bound = (float)a.radius_sq;
-    if ((double)bound < a.radius_sq) bound = std::nextafterf(bound, __builtin_inff());     // the smallest float >= R^2
-    if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-    a.bound_f = bound;
-    a.max_ring = outlier_rings(g, bound);
+    a.radius_sq = b.radius_sq; a.bound_f = b.bound_f; a.max_ring = b.max_ring;
     a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
     return a;
 }
 
 int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_nlin_debug *dbg) {
-    if (!c) return DCREG_E_INVALID;
-    if (!R || !t || !p || !out) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
-    if (int rc = refuse_in_flight(c)) return rc;
-    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the normal linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
-    if (!(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
-    if (!finite_n(R, 9) || !finite_n(t, 3)) { c->fail("the pose is not finite"); return DCREG_E_INVALID; }
-    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
-    if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
-    if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    if (int rc = one_nn_check(c, R, t, p, out, "normal")) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize (a swap drops the warm positions)
     if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
     dcreg_ctx::NormalIcpBufs &B = c->nicp;
     const int64_t n = c->n_src;
     const uint32_t nb = (uint32_t)((n + kLinBlock - 1) / kLinBlock);
-    if (!B.warm.holds((size_t)n)) B.warm_valid = false;          // (a new array holds nothing)
-    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || B.warm.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
     const NlinArgs a = nlin_args(c->map.grid, p);
     PoseArg P;
     std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
@@ -192,10 +179,9 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
         if (d.nn_d2) HIP_TRY(c, hipMemcpyAsync(dbg->nn_d2, d.nn_d2, 4 * N, hipMemcpyDeviceToHost, c->stream));
         if (d.flag) HIP_TRY(c, hipMemcpyAsync(dbg->flag, d.flag, N, hipMemcpyDeviceToHost, c->stream));
     } else {
-        const bool warm = c->opt_warm && B.warm_valid;
-        B.warm_valid = false;                 // (until the launch is known to have run)
+        const uint32_t *warm_in = one_nn_warm_take(c);
         hipLaunchKernelGGL(k_nlin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, B.normals.data(), P, a,
-                           warm ? B.warm.data() : (const uint32_t *)nullptr, B.warm.data(), B.partials.data(), NlinDump{});
+                           warm_in, B.warm.data(), B.partials.data(), NlinDump{});
         HIP_TRY(c, hipGetLastError());
     }
     hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
@@ -204,7 +190,7 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (!dbg) B.warm_valid = true;
+    if (!dbg) one_nn_warm_done(c);
     std::memcpy(out->H_upper, h, 21 * sizeof(double));
     std::memcpy(out->g, h + 21, 6 * sizeof(double));
     out->sum_r2 = h[27]; out->sum_b2 = h[28];
@@ -338,6 +324,43 @@ int nbatch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
 }
 
 }  // namespace
+
+// ---- shared with gicp.hip (context.hpp)
+int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what) {
+    if (!c) return DCREG_E_INVALID;
+    if (!R || !t || !p || !out) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the %s linearisation has the SO(3) row only (parameterization %d)", what, p->parameterization); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
+    if (!finite_n(R, 9) || !finite_n(t, 3)) { c->fail("the pose is not finite"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+OneNnBound one_nn_bound(const GridDev &g, double search_radius) {
+    OneNnBound b;
+    b.radius_sq = search_radius * search_radius;
+    float bound = (float)b.radius_sq;
+    if ((double)bound < b.radius_sq) bound = std::nextafterf(bound, __builtin_inff());     // the smallest float >= R^2
+    if (!(bound <= 3.0e38f)) bound = 3.0e38f;
+    b.bound_f = bound;
+    b.max_ring = outlier_rings(g, bound);
+    return b;
+}
+int one_nn_warm_reserve(dcreg_ctx *c) {
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    if (!B.warm.holds((size_t)c->n_src)) B.warm_valid = false;          // (a new array holds nothing)
+    return B.warm.ensure(c, (size_t)c->n_src) ? DCREG_E_NOMEM : DCREG_OK;
+}
+const uint32_t *one_nn_warm_take(dcreg_ctx *c) {
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    const bool warm = c->opt_warm && B.warm_valid;
+    B.warm_valid = false;                 // (until the launch is known to have run)
+    return warm ? B.warm.data() : nullptr;
+}
+void one_nn_warm_done(dcreg_ctx *c) { c->nicp.warm_valid = true; }
+
 }  // namespace dcreg
 
 using namespace dcreg;

@@ -184,6 +184,22 @@ static __global__ void k_nrm_pack(const float *__restrict__ normal, int64_t stri
     out[i] = float4{p[0], p[1], p[2], curv ? curv[i] : __builtin_nanf("")};
 }
 
+// the kept SOURCE normals: lane i takes the normal (3 floats, `stride` apart) and curvature (null: NaN) of the point that sits at
+// position i of the context's curve order (its original index rides in src[i].w) -> float4 i; and back: float4 i -> original order
+static __global__ void k_nrm_pack_src(const float4 *__restrict__ src, int64_t n, const float *__restrict__ normal, int64_t stride,
+                                      const float *__restrict__ curv, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t oi = __float_as_uint(src[i].w);
+    const float *p = normal + oi * (size_t)stride;
+    out[i] = float4{p[0], p[1], p[2], curv ? curv[oi] : __builtin_nanf("")};
+}
+static __global__ void k_nrm_unpack_src(const float4 *__restrict__ src, int64_t n, const float4 *__restrict__ kept, float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[__float_as_uint(src[i].w)] = kept[i];
+}
+
 template <int K>
 void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const NrmArgs &a, float *normal,
                 float *curv, float *eig, float4 *kept = nullptr, float *reach = nullptr) {
@@ -224,6 +240,7 @@ struct NormalOut {
     float *normal, *curv, *eig;       // the caller's buffers (null: not wanted)
     bool on_device;
     bool keep = false;                // normal and curvature go to the context's kept normals instead (nothing is copied out)
+    bool scratch = false;             // normal and curvature are computed into the call's scratch (c->nrm) and stay there for the caller
 };
 
 // The outputs of n points start as NaN; the nq used points at q (cell order, w = the output index) behind the grid g get theirs; then the
@@ -232,7 +249,7 @@ int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int
                 dcreg_normal_info *info) {
     dcreg_ctx::NormalBufs &B = c->nrm;
     // (keep: the kernel writes the kept normals and their reaches itself, at every point of the map - nq == n there)
-    const bool want_n = o.normal != nullptr, want_c = o.curv != nullptr;
+    const bool want_n = o.normal != nullptr || o.scratch, want_c = o.curv != nullptr || o.scratch;
     if (o.keep && nq != n) { c->fail("kept normals need the map's own index"); return DCREG_E_STATE; }
     if ((want_n && B.normal.ensure(c, 3 * (size_t)n)) || (want_c && B.curv.ensure(c, (size_t)n)) || (o.eig && B.eig.ensure(c, 3 * (size_t)n)) ||
         B.cnt.ensure(c, 2) || (o.keep && (c->nicp.normals.ensure(c, (size_t)n) || c->nicp.reach.ensure(c, (size_t)n))))
@@ -333,6 +350,79 @@ int normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, b
     return DCREG_OK;
 }
 
+
+// dcreg_source_normals_keep: the cloud form over the context's source in its original order (d_src_raw is what upload_cloud packs for
+// dcreg_normals: the same points, the same index build, the same kernel), then one pack into curve order
+int normals_source_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = normals_check(c, p)) return rc;
+    if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    if (info) std::memset(info, 0, sizeof(*info));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t n = c->n_src;
+    c->gicp.src_kept = false;                                   // (a failed call leaves none)
+    if (c->gicp.src_normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    int64_t n_used = 0;
+    if (int rc = outlier_index_used(c, c->d_src_raw.data(), n, p->search_radius, p->k, &n_used)) return rc;
+    const bool indexed = n_used >= p->k;
+    NormalOut o{nullptr, nullptr, nullptr, true};
+    o.scratch = true;
+    if (int rc = normals_run(c, indexed ? c->outl.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? c->outl.idx.grid : GridDev{}, n, n_used, p, o, info))
+        return rc;
+    hipLaunchKernelGGL(k_nrm_pack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, c->nrm.normal.data(), (int64_t)3,
+                       c->nrm.curv.data(), c->gicp.src_normals.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->gicp.src_kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_source_normals_set*: the caller's normals in the source's original order become the kept source normals, as given
+int normals_source_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, bool on_device) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    if (n != c->n_src) { c->fail("the source holds %lld points, %lld normals were given", (long long)c->n_src, (long long)n); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->gicp.src_kept = false;
+    if (c->gicp.src_normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    const float *src = normals;
+    if (!on_device) {
+        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
+        if (c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+        src = c->d_stage.data();
+    } else if (c->stream == c->own_stream) {       // written on the legacy default stream, most likely: as upload_cloud orders a device cloud
+        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    }
+    hipLaunchKernelGGL(k_nrm_pack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, src, stride, (const float *)nullptr,
+                       c->gicp.src_normals.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->gicp.src_kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_source_normals_get*: the kept source normals as they stand, 4 floats per point in the source's original order
+int normals_source_get(dcreg_ctx *c, float *out, int64_t capacity, bool on_device) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (!c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    const int64_t n = c->n_src;
+    if (capacity < n) { c->fail("the source holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->gicp.tmp.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_nrm_unpack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, c->gicp.src_normals.data(), c->gicp.tmp.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, c->gicp.tmp.data(), sizeof(float4) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
 
 // ------------------------------------------------------------------------------------------ kept normals that follow the map ("normals_follow")
 // Candidates are ranked by (d2, index).  An insert appends, so an old point's neighbour set changes only if a new point has a float d2
@@ -570,6 +660,21 @@ int dcreg_target_normals_drop(dcreg_ctx *c) {
 }
 int dcreg_target_normals_get(dcreg_ctx *c, float *out, int64_t capacity_points) { return normals_get(c, out, capacity_points, false); }
 int dcreg_target_normals_get_device(dcreg_ctx *c, float *d_out, int64_t capacity_points) { return normals_get(c, d_out, capacity_points, true); }
+int dcreg_source_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *info) { return normals_source_keep(c, p, info); }
+int dcreg_source_normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride_floats) { return normals_source_set(c, normals, n, stride_floats, false); }
+int dcreg_source_normals_set_device(dcreg_ctx *c, const float *d_normals, int64_t n, int64_t stride_floats) {
+    return normals_source_set(c, d_normals, n, stride_floats, true);
+}
+int dcreg_source_normals_get(dcreg_ctx *c, float *out, int64_t capacity_points) { return normals_source_get(c, out, capacity_points, false); }
+int dcreg_source_normals_get_device(dcreg_ctx *c, float *d_out, int64_t capacity_points) { return normals_source_get(c, d_out, capacity_points, true); }
+int dcreg_source_normals_kept(const dcreg_ctx *c) { return c && c->gicp.src_kept ? 1 : 0; }
+int dcreg_source_normals_drop(dcreg_ctx *c) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    c->gicp.src_kept = false;
+    c->gicp.src_normals.reset(); c->gicp.tmp.reset();
+    return DCREG_OK;
+}
 int dcreg_target_normals_follow_info(const dcreg_ctx *c, dcreg_normals_follow_info *info) {
     if (!c || !info) return DCREG_E_INVALID;
     *info = c->nicp.follow;

@@ -242,7 +242,9 @@ int dcreg_icp_run(dcreg_ctx *ctx, const double R0[9], const double t0[3], int de
 
 // The second engine (include/dcreg.h): the loop above with dcreg_linearize_normals as its linearisation - one launch per iteration, waited
 // for (the kept normals make an iteration a 1-NN search: nothing is queued ahead), then the same host step, log record and covariance.
-int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
+// (the third engine, dcreg_icp_run_gicp, is the same loop around dcreg_linearize_gicp: `linearize` is the only difference)
+typedef int (*lin_fn)(dcreg_ctx *, const double[9], const double[3], const dcreg_lin_params *, dcreg_lin_out *);
+static int icp_run_waited(lin_fn linearize, dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
                           const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
     if (!ctx || !R0 || !t0 || !cfg || !res) return DCREG_E_INVALID;
     std::memset(res, 0, sizeof(*res));
@@ -263,7 +265,7 @@ int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3]
         const auto t_iter = Clock::now();
         dcreg_lin_out lo;
         std::memset(&lo, 0, sizeof(lo));
-        if (int rc = dcreg_linearize_normals(ctx, R, t, &prm, &lo)) return rc;
+        if (int rc = linearize(ctx, R, t, &prm, &lo)) return rc;
         if (lo.n_eff < 10) {                            // :1847-1854
             res->iterations = it + 1; res->converged = 0; res->status = 1;
             break;
@@ -280,6 +282,14 @@ int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3]
     covariance_of(res->converged != 0, Hlast, res->icp_cov);
     res->time_ms = ms_since(t_total);
     return DCREG_OK;
+}
+int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
+                          const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
+    return icp_run_waited(dcreg_linearize_normals, ctx, R0, t0, detection, handling, cfg, log, log_capacity, res);
+}
+int dcreg_icp_run_gicp(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
+                       const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
+    return icp_run_waited(dcreg_linearize_gicp, ctx, R0, t0, detection, handling, cfg, log, log_capacity, res);
 }
 
 int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const double *t0, int detection, int handling,
@@ -832,6 +842,7 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_normal_info")) return sizeof(dcreg_normal_info);
     if (!std::strcmp(name, "dcreg_normals_follow_info")) return sizeof(dcreg_normals_follow_info);
     if (!std::strcmp(name, "dcreg_nlin_debug")) return sizeof(dcreg_nlin_debug);
+    if (!std::strcmp(name, "dcreg_glin_debug")) return sizeof(dcreg_glin_debug);
     return 0;
 }
 

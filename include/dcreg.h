@@ -20,6 +20,11 @@
  *       calculatePointToPointError           utils.hpp:538-589                   -> dcreg_p2p_error
  *       ICPContext::setTargetCloud's pcl::NormalEstimation (targetNormals)  utils.hpp:393-424
  *                                                                                 -> dcreg_target_normals[_device], dcreg_normals[_device]
+ *   plane-to-plane registration (Generalized-ICP; not in the reference)
+ *       normals kept beside the map and beside the source                        -> dcreg_target_normals_keep / _set,
+ *                                                                                   dcreg_source_normals_keep / _set[_device] / _get[_device] /
+ *                                                                                   _kept / _drop
+ *       one linearisation, the engine                                            -> dcreg_linearize_gicp, dcreg_icp_run_gicp
  *   raw clouds (not in the reference, which reads clouds a pcl::VoxelGrid filtered beforehand)
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
@@ -170,6 +175,8 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   at the time of the update;
  *   "normals_follow_full_share" default 0.25 (0 .. 1): the share of the map's points a followed update may have to refit before it
  *                   recomputes all of them instead (the results do not depend on it);
+ *   "gicp_epsilon"  default 1e-3 (1e-6 .. 1, DCREG_E_INVALID outside): the small eigenvalue of both plane covariances of
+ *                   dcreg_linearize_gicp; read at the time of every linearisation;
  *   "visibility_max_bytes" default 2^28 (256 MiB): device bytes the range images of one batch of members may take in the visibility
  *                   calls (a batch always holds at least one image; the results do not depend on it);
  *   "roi_index", "roi_margin": the WINDOW index of a large map.  A map whose table ran into that budget is searched through cells that
@@ -215,7 +222,7 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_linearize_normals, dcreg_target_normals_keep / _set / _drop,
+ * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
  * the launches, and dcreg_debug.h's dcreg_frames_load, dcreg_normals_reserve_slots (a pending launch slot of dcreg_normals_batch_begin counts as a slot in flight), dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
@@ -957,6 +964,63 @@ int dcreg_target_normals_get(dcreg_ctx *, float *out, int64_t capacity_points);
 int dcreg_target_normals_get_device(dcreg_ctx *, float *d_out, int64_t capacity_points);
 int dcreg_target_normals_follow_info(const dcreg_ctx *, dcreg_normals_follow_info *info);
 
+/* ---------------- kept source normals and the plane-to-plane (GICP) linearisation ----------------
+ * Generalized-ICP (Segal, Haehnel, Thrun 2009) weighs a correspondence by the covariances of both surfaces.  With the plane-regularised
+ * covariance of that paper (fast_gicp's PLANE mode) - eigenvalues (1, 1, eps) around the normal - a covariance is a function of its
+ * normal, C = I - (1 - eps) n n^T, so both sides' covariances and their sum at a pose are formed from the two normals in registers:
+ * the map keeps its normals (above), the SOURCE keeps its own beside its points, and nothing else is stored.  The whitened residual
+ * L^-1 e (Sigma = L L^T) turns one correspondence into three point-to-plane rows whose pseudo-normals are the rows of L^-1; the 6x6
+ * system goes through the solver seam below unchanged.
+ *   dcreg_source_normals_keep   runs dcreg_normals on the context's source points: bitwise what that call returns for the source's
+ *                               points in their original order (normal and curvature; a sparse point keeps NaN).  info may be NULL.
+ *   dcreg_source_normals_set    takes the caller's normals, 3 floats first of stride_floats per point, in the source's original order
+ *                               (curvature is stored as NaN); n must equal the source's size.  Stored as given, not renormalised.
+ *   A normal with any non-finite component means "this point has no normal".
+ *   dcreg_source_normals_get    4 floats per point (nx ny nz curvature) in the source's original order.
+ *   dcreg_source_normals_kept   1 while the member holds normals, else 0 (also for a null context);  _drop frees it.
+ * Every call that replaces the context's source points drops the member: dcreg_set_source* in all its forms (plain, _device, _voxel,
+ * _outliers, _deskew, _deskew_path).  The batched calls (dcreg_register_frames*, dcreg_icp_run_trials*, dcreg_register_pairs), which
+ * leave the context's own source as it was, leave the member as it was.  Nothing follows anything: the source normals are not updated.
+ * DCREG_E_INVALID, before anything is queued: null context, parameters, normals or output, the parameter refusals of dcreg_normals,
+ * stride_floats < 3, n different from the source's size, a capacity below it.  DCREG_E_STATE: a linearisation in flight; no source;
+ * _get without kept source normals.  A failed allocation (DCREG_E_NOMEM) leaves no kept source normals.  16 B of device memory per
+ * source point.
+ *
+ * The rule of one linearisation (dcreg_linearize_gicp; tests/gicp_ref.py states it in numpy).  eps = the option "gicp_epsilon" at the
+ * time of the call, c = 1 - eps.  Of the parameter block only search_radius (R) is read - the second engine's weight and its gate do
+ * not apply; parameterization must be DCREG_PARAM_SO3 (DCREG_E_INVALID otherwise).  Every operation rounds once in double (no
+ * contraction).  For each source point p (floats, widened to double):
+ *   - transform, nearest point j and radius gate exactly as dcreg_linearize_normals: q stored as float, j the first map point in
+ *     (float d2, index) order, flag 0 unless (double)d2 < R*R.  A point that passes counts in n_pt;
+ *   - n = the kept normal of j, flag 2 when it has none; m = the kept normal of p, flag 3 when it has none (in this order);
+ *   - u = R m, component a = (R_a0*mx + R_a1*my) + R_a2*mz;  S_ab = d_ab - c*(n_a*n_b + u_a*u_b) with d_ab = 2 on the diagonal and
+ *     0 off it, for the six entries of the lower triangle: the covariance C_map + R C_src R^T of the pair;
+ *   - the Cholesky factor, in this order: l00 = sqrt(S00); l10 = S10/l00; l20 = S20/l00; l11 = sqrt(S11 - l10*l10);
+ *     l21 = (S21 - l20*l10)/l11; l22 = sqrt((S22 - l20*l20) - l21*l21).  Flag 5 (not positive definite) unless each of the three
+ *     radicands is > 0 - possible only with caller-given normals that are not unit length;
+ *   - W = L^-1: w00 = 1/l00; w11 = 1/l11; w22 = 1/l22; w10 = -(l10*w00)*w11; w21 = -(l21*w11)*w22; w20 = -(l20*w00 + l21*w10)*w22.
+ *     The pseudo-normals are its rows: a_0 = (w00, 0, 0), a_1 = (w10, w11, 0), a_2 = (w20, w21, w22) - the zeros are multiplied and
+ *     added below like any other value;
+ *   - e = (double)q - (double)t_j per coordinate.  For k = 0, 1, 2: r_k = (a_kx*ex + a_ky*ey) + a_kz*ez; m_k = R^T a_k, component
+ *     i = (R_0i*a_kx + R_1i*a_ky) + R_2i*a_kz; row k = [p x m_k, m_k, -r_k, r_k] with p x m = (py*m2 - pz*m1, pz*m0 - px*m2,
+ *     px*m1 - py*m0): the second engine's row with weight 1, a right perturbation as dcreg_boxplus applies it.  Flag 1;
+ *   - the sums, in dcreg_lin_out, over the THREE rows of every flag-1 point: H = sum A A^T, g = sum A b; sum_r2 and sum_b2 are both
+ *     the sum of the squared Mahalanobis distances e^T S^-1 e.  n_eff counts the flag-1 POINTS (not rows), n_pt the points with flag != 0.
+ * The sums are added in a fixed order (no floating-point atomics): a result depends on the clouds, both sets of normals, the pose,
+ * R and eps only - not on earlier calls, not on the context, not on the window index.  The search starts from the warm bound that
+ * dcreg_linearize_normals keeps per source point and leaves its own there: both look for the same nearest point, so calls of the two
+ * may interleave on one context and neither moves a bit of the other.  Nothing of dcreg_linearize's neighbour states is read or written.
+ * DCREG_E_INVALID: null arguments, a non-finite pose, a search_radius that is not finite and > 0, a parameterization other than SO3.
+ * DCREG_E_STATE: no target, no source, no kept normals, no kept source normals, a linearisation in flight.  Waits for the stream. */
+int dcreg_source_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *info);
+int dcreg_source_normals_set(dcreg_ctx *, const float *normals, int64_t n, int64_t stride_floats);
+int dcreg_source_normals_set_device(dcreg_ctx *, const float *d_normals, int64_t n, int64_t stride_floats);
+int dcreg_source_normals_get(dcreg_ctx *, float *out, int64_t capacity_points);
+int dcreg_source_normals_get_device(dcreg_ctx *, float *d_out, int64_t capacity_points);
+int dcreg_source_normals_kept(const dcreg_ctx *);
+int dcreg_source_normals_drop(dcreg_ctx *);
+int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
 typedef struct dcreg_config {
@@ -1039,6 +1103,14 @@ int dcreg_icp_run(dcreg_ctx *, const double R0[9], const double t0[3], int detec
  * normals per pair), no sharded / RCCL form and no Euler form of this engine. */
 int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                           const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
+
+/* The same loop with dcreg_linearize_gicp as its linearisation (kept map normals AND kept source normals first, DCREG_E_STATE without
+ * either): one waited launch per iteration, the same aborts, fitness, convergence test, log records, covariance and status codes, the
+ * same host step.  rmse keeps its formula sqrt(sum_r2 / n_eff): here the RMS Mahalanobis distance per effective point (three whitened
+ * residuals each), not a distance in metres.  Of the configuration's linearisation parameters only search_radius is read.  One pose per
+ * call: no batched, pairs, sharded / RCCL or Euler form of this engine. */
+int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
+                       const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
 /* n independent scan pairs at once: one host thread per ctx (each ctx owns its clouds, index, stream), every thread runs
  * dcreg_icp_run.  One 100 k-point linearisation fills well under half of an MI355X and the device idles during each host

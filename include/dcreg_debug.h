@@ -49,6 +49,26 @@ typedef struct dcreg_nlin_debug {
 int dcreg_linearize_normals_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *,
                                   dcreg_nlin_debug *);
 
+/* per-point dump of dcreg_linearize_gicp (original source order; any pointer may be NULL).  flag: 1 effective, 0 radius gate, 2 the
+ * nearest map point has no normal, 3 the source point has none, 5 the pair's covariance is not positive definite.  nn_idx / nn_d2: the
+ * nearest map point (original index) and its float d2 for the points that pass the radius gate; -1 / +inf for flag 0.  normal_map /
+ * normal_src: the kept normal of that map point and the point's own kept normal as stored, for every point that passes the radius gate
+ * (with their non-finite components).  For flag 1: w = the whitening matrix W = L^-1 row-major (its upper triangle 0), r = the three
+ * whitened residuals, row = the three rows [A0..A5, -r_k, r_k]; everything else is 0. */
+typedef struct dcreg_glin_debug {
+    int32_t *nn_idx;     /* [n] */
+    float *nn_d2;        /* [n] */
+    uint8_t *flag;       /* [n] */
+    double *normal_map;  /* [3*n] */
+    double *normal_src;  /* [3*n] */
+    double *w;           /* [9*n] */
+    double *r;           /* [3*n] */
+    double *row;         /* [3*8*n] */
+} dcreg_glin_debug;
+/* dcreg_linearize_gicp with the dump; searches every point cold and leaves the warm bounds of the plain calls as they were */
+int dcreg_linearize_gicp_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *,
+                               dcreg_glin_debug *);
+
 /* total duration (ms, HIP events on the ctx stream around ALL kernels of a linearisation) of the timed linearisations since the
  * last reset, and their number; option "time_kernels" = N > 0 brackets every N-th linearisation of slot 0 (an event pair costs ~10 us
  * of host time), 0 = off */
