@@ -179,6 +179,8 @@ EXPORTS = [
     "dcreg_source_normals_keep", "dcreg_source_normals_set", "dcreg_source_normals_set_device", "dcreg_source_normals_get",
     "dcreg_source_normals_get_device", "dcreg_source_normals_kept", "dcreg_source_normals_drop", "dcreg_linearize_gicp",
     "dcreg_linearize_gicp_debug", "dcreg_icp_run_gicp",
+    "dcreg_normals_clouds", "dcreg_normals_clouds_device", "dcreg_frames_normals_keep", "dcreg_frames_normals_set", "dcreg_frames_normals_kept",
+    "dcreg_gicp_batch_begin", "dcreg_gicp_batch_end", "dcreg_normal_params_check", "dcreg_register_frames_gicp", "dcreg_icp_run_trials_gicp",
 ]
 
 _lib = None
@@ -1075,6 +1077,19 @@ def load():
         L.dcreg_linearize_gicp.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
         L.dcreg_linearize_gicp_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(GlinDebug)]
         L.dcreg_icp_run_gicp.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
+    if hasattr(L, "dcreg_register_frames_gicp"):  # (likewise)
+        np_, ni = C.POINTER(NormalParams), C.POINTER(NormalInfo)
+        for name in ("dcreg_normals_clouds", "dcreg_normals_clouds_device"):
+            getattr(L, name).argtypes = [vp, C.c_int, vp, i64p, C.c_int64, np_, vp, vp, ni]
+        L.dcreg_frames_normals_keep.argtypes = [vp, np_, ni]
+        L.dcreg_frames_normals_set.argtypes = [vp, vp, C.c_int64, C.c_int64]
+        L.dcreg_frames_normals_kept.argtypes = [vp]
+        L.dcreg_gicp_batch_begin.argtypes = L.dcreg_normals_batch_begin.argtypes
+        L.dcreg_gicp_batch_end.argtypes = L.dcreg_normals_batch_end.argtypes
+        L.dcreg_normal_params_check.argtypes = [vp, np_]
+        L.dcreg_register_frames_gicp.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, np_, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
+                                                 C.POINTER(TrialResult)]
+        L.dcreg_icp_run_trials_gicp.argtypes = L.dcreg_icp_run_trials.argtypes
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1237,6 +1252,7 @@ class Context:
     def __init__(self, device=0):
         self._L = load()
         self._h = C.c_void_p()
+        self._n_frames = 0            # frames the last successful load put on the device
         rc = self._L.dcreg_backend_create(C.byref(self._h), int(device))
         if rc != OK:
             self._h = None
@@ -1743,6 +1759,41 @@ class Context:
                                                  C.c_void_p(dev_curvature_ptr or None), C.c_void_p(dev_eigenvalues_ptr or None),
                                                  C.byref(info)), "dcreg_normals_device")
         return _normal_info_dict(info)
+
+    def normals_clouds(self, clouds, params=None, want_normals=True, want_curvature=True):
+        """dcreg_normals_clouds: normals() of many clouds in one call - a list of [n_i, c] float32 arrays or an (xyz, offsets) pair; every
+        cloud is indexed on its own, all of them in one build and one launch, and every value is bitwise what normals() returns for the
+        cloud alone.  -> (normals [N, 3] float32 or None, curvature [N] float32 or None, offsets [n + 1] int64, [info dict per cloud]);
+        cloud s is rows offsets[s]:offsets[s + 1]"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "normals_clouds")
+        self._normal_wants(want_normals, want_curvature, False, "normals_clouds")
+        xyz, off, _ = _clouds(clouds, "normals_clouds")
+        n_clouds, n = len(off) - 1, int(off[-1])
+        if n > OUTLIER_MAX_POINTS:
+            raise ValueError("normals_clouds: at most 2^31 - 1 points a call, got %d" % n)
+        nrm = np.full((max(n, 1), 3), np.nan, np.float32) if want_normals else None
+        cur = np.full(max(n, 1), np.nan, np.float32) if want_curvature else None
+        infos = (NormalInfo * max(n_clouds, 1))()
+        self._check(self._L.dcreg_normals_clouds(self._h, n_clouds, xyz.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1], C.byref(p),
+                                                 nrm.ctypes.data if want_normals else None, cur.ctypes.data if want_curvature else None, infos),
+                    "dcreg_normals_clouds")
+        return (nrm[:n] if want_normals else None, cur[:n] if want_curvature else None, off, [_normal_info_dict(infos[s]) for s in range(n_clouds)])
+
+    def normals_clouds_device(self, dev_ptr, offsets, stride, params=None, dev_normals_ptr=0, dev_curvature_ptr=0):
+        """dcreg_normals_clouds_device: the clouds back to back in device memory (offsets on the host); the normals (3 N floats) and the
+        curvature (N floats) to the device buffers given (0: not wanted).  -> [info dict per cloud]"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "normals_clouds_device")
+        off = _offsets(offsets, "normals_clouds_device")
+        _check_device_cloud(int(off[-1]), stride, "normals_clouds_device")
+        self._normal_wants(dev_normals_ptr, dev_curvature_ptr, False, "normals_clouds_device")
+        n_clouds = len(off) - 1
+        infos = (NormalInfo * max(n_clouds, 1))()
+        self._check(self._L.dcreg_normals_clouds_device(self._h, n_clouds, C.c_void_p(dev_ptr), off.ctypes.data_as(C.POINTER(C.c_int64)), int(stride),
+                                                        C.byref(p), C.c_void_p(dev_normals_ptr or None), C.c_void_p(dev_curvature_ptr or None), infos),
+                    "dcreg_normals_clouds_device")
+        return [_normal_info_dict(infos[s]) for s in range(n_clouds)]
 
     def target_normals(self, params=None, want_normals=True, want_curvature=True, want_eigenvalues=False):
         """dcreg_target_normals: the same for the resident map's points in index order (target_points()), searched through the map's own
@@ -2502,6 +2553,7 @@ class Context:
         self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
                                                   _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
                     "dcreg_register_frames")
+        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
         return [res[i] for i in range(n)]
 
     def register_frames_normals(self, frames, T0s, method, cfg, slots=0):
@@ -2520,6 +2572,7 @@ class Context:
         self._check(self._L.dcreg_register_frames_normals(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
                                                           xyz.shape[1], _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
                     "dcreg_register_frames_normals")
+        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
         return [res[i] for i in range(n)]
 
     def icp_run_trials_normals(self, T0s, method, cfg):
@@ -2542,6 +2595,7 @@ class Context:
         xyz, off, n = _frames_arg(frames, "frames_load")
         self._check(self._L.dcreg_frames_load(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1]),
                     "dcreg_frames_load")
+        self._n_frames = n            # (frames_normals_keep sizes its per-frame infos by the frames on the device)
 
     def normals_reserve_slots(self, n_slots, frames=True):
         self._check(self._L.dcreg_normals_reserve_slots(self._h, int(n_slots), 1 if frames else 0), "dcreg_normals_reserve_slots")
@@ -2573,6 +2627,95 @@ class Context:
 
     def normals_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
         return self.normals_batch_end(self.normals_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)
+
+    # ---- the third engine's many-frames form (include/dcreg.h: dcreg_register_frames_gicp, dcreg_icp_run_trials_gicp) and its device seam
+    # (include/dcreg_debug.h: dcreg_frames_normals_*, dcreg_gicp_batch_begin / _end)
+    def register_frames_gicp(self, frames, T0s, method, cfg, frame_normals=None, slots=0):
+        """dcreg_register_frames_gicp: register_frames with the third engine (the map's kept normals first; every frame's own normals are
+        estimated with frame_normals = normal_params(...), None = the defaults, all frames in one batched pass).  Same arguments and
+        records; each record is bitwise set_source(frame) + keep_source_normals(frame_normals) + icp_run_gicp(T0)."""
+        p = frame_normals if frame_normals is not None else normal_params()
+        _check_normal_params(p, "register_frames_gicp")
+        xyz, off, n = _frames_arg(frames, "register_frames_gicp")
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if T0s.shape[0] != n:
+            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("register_frames_gicp: unknown method %r" % (method,))
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        self._check(self._L.dcreg_register_frames_gicp(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       xyz.shape[1], C.byref(p), _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg),
+                                                       int(slots), res), "dcreg_register_frames_gicp")
+        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
+        return [res[i] for i in range(n)]
+
+    def icp_run_trials_gicp(self, T0s, method, cfg):
+        """dcreg_icp_run_trials_gicp: icp_run_trials with the third engine (kept map normals and kept source normals first); each record is
+        bitwise icp_run_gicp from its pose"""
+        T0s = _f64(T0s).reshape(-1, 4, 4)
+        if isinstance(method, str) and method not in METHODS:
+            raise ValueError("icp_run_trials_gicp: unknown method %r" % (method,))
+        n = T0s.shape[0]
+        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
+        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        det, hand = METHODS[method] if isinstance(method, str) else method
+        res = (TrialResult * max(n, 1))()
+        self._check(self._L.dcreg_icp_run_trials_gicp(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
+                    "dcreg_icp_run_trials_gicp")
+        return [res[i] for i in range(n)]
+
+    def frames_normals_keep(self, params=None):
+        """dcreg_frames_normals_keep: the loaded frames' own normals, all frames in one batched pass, kept beside their points
+        -> [info dict per frame]"""
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, "frames_normals_keep")
+        n = self._n_frames
+        infos = (NormalInfo * max(n, 1))()
+        self._check(self._L.dcreg_frames_normals_keep(self._h, C.byref(p), infos), "dcreg_frames_normals_keep")
+        return [_normal_info_dict(infos[s]) for s in range(n)]
+
+    def frames_normals_set(self, normals):
+        """dcreg_frames_normals_set: the caller's normals ([N, c >= 3] float32, or a list with one array per frame) for all points of the
+        load in its upload order, kept as given"""
+        if isinstance(normals, (list, tuple)):
+            parts = [_points(a, "frames_normals_set") for a in normals]
+            if len({a.shape[1] for a in parts}) > 1:
+                raise ValueError("frames_normals_set: every frame's normals need the same number of columns")
+            a = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
+        else:
+            a = _points(normals, "frames_normals_set")
+        self._check(self._L.dcreg_frames_normals_set(self._h, a.ctypes.data, a.shape[0], a.shape[1]), "dcreg_frames_normals_set")
+
+    def frames_normals_kept(self):
+        return int(self._L.dcreg_frames_normals_kept(self._h))
+
+    def gicp_batch_begin(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
+        """dcreg_gicp_batch_begin: normals_batch_begin for linearize_gicp - pose i linearises frame frame_ids[i] with its kept frame
+        normals (None: the own source with its kept source normals).  -> the number of poses, for gicp_batch_end"""
+        params = self._nlin_params(params, "gicp_batch_begin")
+        Ts = _f64(Ts).reshape(-1, 4, 4)
+        n = Ts.shape[0]
+        Rs = np.ascontiguousarray(Ts[:, :3, :3]).reshape(n, 9)
+        ts = np.ascontiguousarray(Ts[:, :3, 3]).reshape(n, 3)
+        i32p = C.POINTER(C.c_int32)
+        ids = None if state_ids is None else np.ascontiguousarray(state_ids, dtype=np.int32).reshape(n)
+        fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
+        self._check(self._L.dcreg_gicp_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
+                                                   None if fids is None else fids.ctypes.data_as(i32p), C.byref(params)),
+                    "dcreg_gicp_batch_begin")
+        return n
+
+    def gicp_batch_end(self, n_poses, slot=0):
+        """dcreg_gicp_batch_end -> one dict per pose, as linearize_gicp returns"""
+        outs = (LinOut * max(int(n_poses), 1))()
+        self._check(self._L.dcreg_gicp_batch_end(self._h, int(slot), outs), "dcreg_gicp_batch_end")
+        return [self._out_dict(outs[i]) for i in range(int(n_poses))]
+
+    def gicp_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
+        return self.gicp_batch_end(self.gicp_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)
 
     def register_pairs(self, sources, targets, T0s, method, cfg, slots=0):
         """dcreg_register_pairs: many scan pairs in one call, pair p = sources[p] registered against targets[p] from T0s[p].  sources and

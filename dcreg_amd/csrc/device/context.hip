@@ -1191,9 +1191,9 @@ static double pair_target_bytes(const dcreg_ctx *c, int64_t m, int64_t stride) {
 // One pass over some targets of the batch (J: batch targets, cells[j]: the geometry of J[j] in this pass): cell keys of all their points
 // in one kernel, ONE sort over (pass target, cell).  occ != null: the occupied cells of every pass target (one readback).  Otherwise the
 // final index: points gathered target after target (kPtsPad zero entries behind each), every cell table and every target's row words.
-static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairCells> &cells, const std::vector<int64_t> &count,
-                      std::vector<uint32_t> *occ, std::vector<int64_t> *tab_first, std::vector<int64_t> *yw_first) {
-    dcreg_ctx::PairSet &ps = c->pairs;
+// (ps / raw: the set whose buffers the pass fills and the packed points it indexes - the pair targets, or the clouds of dcreg_normals_clouds)
+static int pairs_pass(dcreg_ctx *c, dcreg_ctx::PairSet &ps, const float4 *raw, const std::vector<int> &J, std::vector<PairCells> &cells,
+                      const std::vector<int64_t> &count, std::vector<uint32_t> *occ, std::vector<int64_t> *tab_first, std::vector<int64_t> *yw_first) {
     const int n_j = (int)J.size();
     std::vector<int64_t> offs((size_t)3 * (n_j + 1), 0);       // [pass points | table entries | row words] offsets
     int64_t *po = offs.data(), *to = po + (n_j + 1), *yo = to + (n_j + 1);
@@ -1212,7 +1212,7 @@ static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairC
     int cbits = 1, jbits = 0;
     while (((int64_t)1 << cbits) < max_entries) ++cbits;
     while (((int64_t)1 << jbits) < (int64_t)n_j) ++jbits;
-    if (ps.d_off.ensure(c, offs.size()) || ps.d_cells.ensure(c, (size_t)n_j) ||
+    if (ps.d_off.ensure(c, offs.size()) || ps.d_cells.ensure(c, (size_t)n_j) || ps.d_words.ensure(c, (size_t)n_j) ||
         c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
         c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
         return DCREG_E_NOMEM;
@@ -1222,7 +1222,7 @@ static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairC
     int64_t *d_po = ps.d_off.data(), *d_to = d_po + (n_j + 1), *d_yo = d_to + (n_j + 1);
     HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(ps.d_cells.data(), cells.data(), sizeof(PairCells) * (size_t)n_j, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw.data(), n, d_po, n_j, ps.d_cells.data(), cbits, c->d_mkeys.data(), c->d_vals.data());
+    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, n, d_po, n_j, ps.d_cells.data(), cbits, c->d_mkeys.data(), c->d_vals.data());
     int rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 0, cbits + jbits);
     if (rc) return rc;
     if (occ) {
@@ -1231,7 +1231,7 @@ static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairC
         occ->assign((size_t)n_j, 0u);
         HIP_TRY(c, hipMemcpyAsync(occ->data(), ps.d_words.data(), sizeof(uint32_t) * (size_t)n_j, hipMemcpyDeviceToHost, c->stream));
     } else {
-        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, ps.raw.data(), c->d_vals2.data(), n, d_po, n_j, ps.d_cells.data(), ps.sorted.data());
+        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d_po, n_j, ps.d_cells.data(), ps.sorted.data());
         hipLaunchKernelGGL(k_pairs_pad, dim3((unsigned)n_j), dim3(64), 0, c->stream, d_po, ps.d_cells.data(), ps.sorted.data());
         hipLaunchKernelGGL(k_pairs_table, dim3(blocks_for(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), d_po, d_to, n_j, cbits, ps.table.data());
         if (yo[n_j] > 0)
@@ -1241,6 +1241,113 @@ static int pairs_pass(dcreg_ctx *c, const std::vector<int> &J, std::vector<PairC
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the host arrays above are the sources of the copies)
     HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
+// The indices of n_t clouds at once (pairs_build below; normals.hip: the clouds of dcreg_normals_clouds).  Cloud t = the count[t] packed
+// points from raw[first[t]] (count 0: no index), its bounds in `words` as k_pairs_pack leaves them (3 n_t minima, then 3 n_t maxima, ordered
+// floats; all finite).  radius_hint > 0 caps the cell edge as build_index does, 0 starts from the density; max_cells = the table budget per
+// cloud.  Fills grids[t] and built[t] for every indexed cloud; the arrays live in ps (sorted, table, ymask).  No gap field and no owners.
+int clouds_index_build(dcreg_ctx *c, dcreg_ctx::PairSet &ps, const float4 *raw, int n_t, const std::vector<int64_t> &count,
+                       const std::vector<int64_t> &first, const std::vector<uint32_t> &words, double radius_hint, double max_cells,
+                       std::vector<GridDev> &grids, std::vector<uint8_t> &built) {
+    grids.assign((size_t)n_t, GridDev{});
+    built.assign((size_t)n_t, 0);
+    // ---- every target's cell edge, as build_index chooses it
+    struct Plan { double mn[3], mx[3], h_cap, h1, m1, expo; bool adapt; int nx, ny, nz; };
+    std::vector<Plan> plan((size_t)n_t);
+    auto geom = [](Plan &P, double h) {
+        const double inv_h = 1.0 / h;
+        P.nx = (int)std::floor((P.mx[0] - P.mn[0]) * inv_h) + 1;
+        P.ny = (int)std::floor((P.mx[1] - P.mn[1]) * inv_h) + 1;
+        P.nz = (int)std::floor((P.mx[2] - P.mn[2]) * inv_h) + 1;
+    };
+    auto cells_of = [&](int t, double h, int sx) {
+        Plan &P = plan[(size_t)t];
+        geom(P, h);
+        PairCells g{};
+        g.ox = P.mn[0]; g.oy = P.mn[1]; g.oz = P.mn[2]; g.inv_h = 1.0 / h;
+        g.nx = P.nx; g.ny = P.ny; g.nz = P.nz; g.sx = sx;
+        g.raw_first = first[(size_t)t];
+        g.nxb = (g.nx + 15) >> 4; g.nyw = (g.ny + 31) >> 5;
+        return g;
+    };
+    std::vector<int> J;
+    std::vector<PairCells> cells;
+    for (int t = 0; t < n_t; ++t) {
+        const int64_t m = count[(size_t)t];
+        if (m <= 0) continue;
+        Plan &P = plan[(size_t)t];
+        for (int a = 0; a < 3; ++a) { P.mn[a] = ord2f(words[(size_t)3 * t + a]); P.mx[a] = ord2f(words[(size_t)3 * n_t + 3 * t + a]); }
+        const double ext = std::max({P.mx[0] - P.mn[0], P.mx[1] - P.mn[1], P.mx[2] - P.mn[2], 1e-6});
+        P.h_cap = radius_hint > 0.0 ? radius_hint * 1.00001 : ext / std::cbrt((double)m) * 4.0;
+        P.h1 = cap_cell_for_budget(c->opt_cell > 0.0 ? c->opt_cell : P.h_cap, P.mn, P.mx, max_cells);
+        P.expo = 2.0; P.adapt = c->opt_cell <= 0.0;
+        J.push_back(t);
+        cells.push_back(cells_of(t, P.h1, 1));
+    }
+    std::vector<uint32_t> occ;
+    int rc = DCREG_OK;
+    if (!J.empty() && c->opt_cell <= 0.0) {
+        // density-adaptive cells (build_index): the occupancy at the first edge, then up to two passes over the targets that ask for one
+        rc = pairs_pass(c, ps, raw, J, cells, count, &occ, nullptr, nullptr);
+        if (rc) return rc;
+        const double target_occ = 1.59 * c->opt_cell_factor * c->opt_cell_factor;
+        std::vector<double> h2s;
+        for (size_t j = 0; j < J.size(); ++j) { Plan &P = plan[(size_t)J[j]]; P.m1 = (double)count[(size_t)J[j]] / std::max<uint32_t>(occ[j], 1u); }
+        for (int pass = 0; pass < 2; ++pass) {
+            std::vector<int> K;
+            cells.clear(); h2s.clear();
+            for (int t : J) {
+                Plan &P = plan[(size_t)t];
+                if (!P.adapt || !(P.m1 > target_occ * 1.3)) { P.adapt = false; continue; }
+                double h2 = P.h1 * std::pow(target_occ / P.m1, 1.0 / P.expo);
+                h2 = std::max(h2, P.h_cap / 64.0);
+                h2 = cap_cell_for_budget(h2, P.mn, P.mx, max_cells);
+                if (h2 >= P.h1 * 0.95) { P.adapt = false; continue; }
+                K.push_back(t); h2s.push_back(h2);
+                cells.push_back(cells_of(t, h2, 1));
+            }
+            if (K.empty()) break;
+            rc = pairs_pass(c, ps, raw, K, cells, count, &occ, nullptr, nullptr);
+            if (rc) return rc;
+            for (size_t k = 0; k < K.size(); ++k) {
+                Plan &P = plan[(size_t)K[k]];
+                const double h2 = h2s[k], m2 = (double)count[(size_t)K[k]] / std::max<uint32_t>(occ[k], 1u);
+                if (m2 < P.m1 && h2 < P.h1) P.expo = std::min(3.0, std::max(1.0, std::log(P.m1 / m2) / std::log(P.h1 / h2)));
+                P.h1 = h2; P.m1 = m2;
+            }
+        }
+    }
+    // ---- the final index: the settled edge, x cut into sub-cells as far as the table budget allows
+    cells.clear();
+    for (int t : J) {
+        Plan &P = plan[(size_t)t];
+        geom(P, P.h1);
+        int sx = c->opt_x_subdiv;
+        while (sx > 1 && (double)P.nx * sx * P.ny * P.nz > max_cells) sx >>= 1;
+        cells.push_back(cells_of(t, P.h1, sx));
+    }
+    if (!J.empty()) {
+        std::vector<int64_t> tab_first, yw_first;
+        rc = pairs_pass(c, ps, raw, J, cells, count, nullptr, &tab_first, &yw_first);
+        if (rc) return rc;
+        for (size_t j = 0; j < J.size(); ++j) {
+            const int t = J[j];
+            const PairCells &q = cells[j];
+            const double h = plan[(size_t)t].h1;
+            GridDev &g = grids[(size_t)t];
+            g.h = h; g.inv_h = q.inv_h;
+            g.ox = q.ox; g.oy = q.oy; g.oz = q.oz;
+            g.nx = q.nx; g.ny = q.ny; g.nz = q.nz; g.sx = q.sx;
+            g.n_pts = (uint32_t)count[(size_t)t];
+            g.cell_start = ps.table.data() + tab_first[j];
+            g.pts = ps.sorted.data() + q.pts_first;
+            g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
+            g.ymask = ps.ymask.data() + yw_first[j]; g.nxb = q.nxb; g.nyw = q.nyw;
+            built[(size_t)t] = 1;
+        }
+    }
     return DCREG_OK;
 }
 
@@ -1279,106 +1386,23 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
     }
-    // ---- every target's cell edge, as build_index chooses it
-    struct Plan { double mn[3], mx[3], h_cap, h1, m1, expo; bool adapt; int nx, ny, nz; };
-    std::vector<Plan> plan((size_t)n_t);
-    const double radius_hint = search_radius * (1.0 + c->opt_cert_margin);
-    const double max_cells = (double)c->opt_pair_max_table_entries;
-    auto geom = [](Plan &P, double h) {
-        const double inv_h = 1.0 / h;
-        P.nx = (int)std::floor((P.mx[0] - P.mn[0]) * inv_h) + 1;
-        P.ny = (int)std::floor((P.mx[1] - P.mn[1]) * inv_h) + 1;
-        P.nz = (int)std::floor((P.mx[2] - P.mn[2]) * inv_h) + 1;
-    };
-    auto cells_of = [&](int t, double h, int sx) {
-        Plan &P = plan[(size_t)t];
-        geom(P, h);
-        PairCells g{};
-        g.ox = P.mn[0]; g.oy = P.mn[1]; g.oz = P.mn[2]; g.inv_h = 1.0 / h;
-        g.nx = P.nx; g.ny = P.ny; g.nz = P.nz; g.sx = sx;
-        g.raw_first = off[t];
-        g.nxb = (g.nx + 15) >> 4; g.nyw = (g.ny + 31) >> 5;
-        return g;
-    };
-    std::vector<int> J;
-    std::vector<PairCells> cells;
     for (int t = 0; t < n_t; ++t) {
-        const int64_t m = count[(size_t)t];
-        if (m <= 0) continue;
-        Plan &P = plan[(size_t)t];
-        for (int a = 0; a < 3; ++a) { P.mn[a] = ord2f(words[(size_t)3 * t + a]); P.mx[a] = ord2f(words[(size_t)3 * n_t + 3 * t + a]); }
-        for (int a = 0; a < 3; ++a) if (!std::isfinite(P.mn[a]) || !std::isfinite(P.mx[a])) { c->fail("pair target %d has non-finite coordinates", t); return DCREG_E_INVALID; }
-        const double ext = std::max({P.mx[0] - P.mn[0], P.mx[1] - P.mn[1], P.mx[2] - P.mn[2], 1e-6});
-        P.h_cap = radius_hint > 0.0 ? radius_hint * 1.00001 : ext / std::cbrt((double)m) * 4.0;
-        P.h1 = cap_cell_for_budget(c->opt_cell > 0.0 ? c->opt_cell : P.h_cap, P.mn, P.mx, max_cells);
-        P.expo = 2.0; P.adapt = c->opt_cell <= 0.0;
-        J.push_back(t);
-        cells.push_back(cells_of(t, P.h1, 1));
+        if (count[(size_t)t] <= 0) continue;
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(ord2f(words[(size_t)3 * t + a])) || !std::isfinite(ord2f(words[(size_t)3 * n_t + 3 * t + a]))) { c->fail("pair target %d has non-finite coordinates", t); return DCREG_E_INVALID; }
     }
-    std::vector<uint32_t> occ;
-    int rc = DCREG_OK;
-    if (!J.empty() && c->opt_cell <= 0.0) {
-        // density-adaptive cells (build_index): the occupancy at the first edge, then up to two passes over the targets that ask for one
-        rc = pairs_pass(c, J, cells, count, &occ, nullptr, nullptr);
-        if (rc) return rc;
-        const double target_occ = 1.59 * c->opt_cell_factor * c->opt_cell_factor;
-        std::vector<double> h2s;
-        for (size_t j = 0; j < J.size(); ++j) { Plan &P = plan[(size_t)J[j]]; P.m1 = (double)count[(size_t)J[j]] / std::max<uint32_t>(occ[j], 1u); }
-        for (int pass = 0; pass < 2; ++pass) {
-            std::vector<int> K;
-            cells.clear(); h2s.clear();
-            for (int t : J) {
-                Plan &P = plan[(size_t)t];
-                if (!P.adapt || !(P.m1 > target_occ * 1.3)) { P.adapt = false; continue; }
-                double h2 = P.h1 * std::pow(target_occ / P.m1, 1.0 / P.expo);
-                h2 = std::max(h2, P.h_cap / 64.0);
-                h2 = cap_cell_for_budget(h2, P.mn, P.mx, max_cells);
-                if (h2 >= P.h1 * 0.95) { P.adapt = false; continue; }
-                K.push_back(t); h2s.push_back(h2);
-                cells.push_back(cells_of(t, h2, 1));
-            }
-            if (K.empty()) break;
-            rc = pairs_pass(c, K, cells, count, &occ, nullptr, nullptr);
-            if (rc) return rc;
-            for (size_t k = 0; k < K.size(); ++k) {
-                Plan &P = plan[(size_t)K[k]];
-                const double h2 = h2s[k], m2 = (double)count[(size_t)K[k]] / std::max<uint32_t>(occ[k], 1u);
-                if (m2 < P.m1 && h2 < P.h1) P.expo = std::min(3.0, std::max(1.0, std::log(P.m1 / m2) / std::log(P.h1 / h2)));
-                P.h1 = h2; P.m1 = m2;
-            }
-        }
-    }
-    // ---- the final index: the settled edge, x cut into sub-cells as far as the table budget allows
-    cells.clear();
-    for (int t : J) {
-        Plan &P = plan[(size_t)t];
-        geom(P, P.h1);
-        int sx = c->opt_x_subdiv;
-        while (sx > 1 && (double)P.nx * sx * P.ny * P.nz > max_cells) sx >>= 1;
-        cells.push_back(cells_of(t, P.h1, sx));
-    }
+    // ---- every target's index, its cell edge chosen as build_index chooses it
+    std::vector<int64_t> first(off, off + n_t);
+    std::vector<GridDev> gs;
+    int rc = clouds_index_build(c, ps, ps.raw.data(), n_t, count, first, words, search_radius * (1.0 + c->opt_cert_margin),
+                                (double)c->opt_pair_max_table_entries, gs, ps.built);
+    if (rc) return rc;
     const float bound = search_bound_sq(c, search_radius);
-    if (!J.empty()) {
-        std::vector<int64_t> tab_first, yw_first;
-        rc = pairs_pass(c, J, cells, count, nullptr, &tab_first, &yw_first);
-        if (rc) return rc;
-        for (size_t j = 0; j < J.size(); ++j) {
-            const int t = J[j];
-            const PairCells &q = cells[j];
-            const double h = plan[(size_t)t].h1;
-            GridDev &g = grids[(size_t)t].g;
-            g.h = h; g.inv_h = q.inv_h;
-            g.ox = q.ox; g.oy = q.oy; g.oz = q.oz;
-            g.nx = q.nx; g.ny = q.ny; g.nz = q.nz; g.sx = q.sx;
-            g.n_pts = (uint32_t)count[(size_t)t];
-            g.cell_start = ps.table.data() + tab_first[j];
-            g.pts = ps.sorted.data() + q.pts_first;
-            g.gap = nullptr; g.gap_cap = 0; g.owner = nullptr;
-            g.ymask = ps.ymask.data() + yw_first[j]; g.nxb = q.nxb; g.nyw = q.nyw;
-            grids[(size_t)t].max_ring = rings_for(h, bound);
-            grids[(size_t)t].infl_max_d2 = (float)(4.0 * h * h);
-            ps.built[(size_t)t] = 1;
-        }
+    for (int t = 0; t < n_t; ++t) {
+        if (!ps.built[(size_t)t]) continue;
+        grids[(size_t)t].g = gs[(size_t)t];
+        grids[(size_t)t].max_ring = rings_for(gs[(size_t)t].h, bound);
+        grids[(size_t)t].infl_max_d2 = (float)(4.0 * gs[(size_t)t].h * gs[(size_t)t].h);
     }
     if (n_t > 0) {
         HIP_TRY(c, hipMemcpyAsync(ps.d_grids.data(), grids.data(), sizeof(PairGrid) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
@@ -2571,6 +2595,7 @@ int dcreg_frames_load(dcreg_ctx *c, int n_frames, const float *xyz, const int64_
     if (c) for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
     if (c && c->nicp.batch_pending()) { c->fail("a batched normal linearisation is still in flight (dcreg_normals_batch_end first)"); return DCREG_E_STATE; }
     if (c) c->nicp.drop_slots();           // (normal_icp.hip: the warm slots of the batched form belong to the frames that were loaded)
+    if (c) c->frames.normals_kept = false; // (normals.hip: ... and so do the frames' kept normals)
     return frames_load(c, c->frames, n_frames, xyz, frame_offsets, stride_floats);
 }
 static int frames_reserve_states(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t n_states) {

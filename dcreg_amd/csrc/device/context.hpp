@@ -282,6 +282,9 @@ struct dcreg_ctx {
         int64_t n_states = 0;
         std::vector<uint8_t> state_valid;
         StateKey key;
+        // the frames' own kept normals (normals.hip: dcreg_frames_normals_keep / _set; the third engine's many-frames form): float4 {nx,
+        // ny, nz, curvature} at the positions of src - lane i of k_glin_batch reads it beside src[i]; dropped by every load of the set
+        DevBuf<float4> normals; bool normals_kept = false;
     };
     FrameSet frames;
     // The scan pairs of dcreg_register_pairs (engine.cpp): pair p = source p (a frame of pair_src, loaded as dcreg_register_frames loads its
@@ -397,9 +400,17 @@ struct dcreg_ctx {
     // surface normals (normals.hip: dcreg_normals*, dcreg_target_normals*).  Scratch of one call: the outputs per input point (3 + 1 + 3
     // floats, those that are wanted) and the call's counts ([0] points with a normal, [1] sparse points); the cloud form packs, compacts and
     // indexes its cloud in the outlier scratch (outl.pts, cpts, used, upos, idx)
+    // The many-clouds form (dcreg_normals_clouds*, dcreg_frames_normals_keep): every cloud's used points indexed on its own, all at once
+    // (context.hip clouds_index_build into `clouds`: sorted points, tables, row words), cnt two words per cloud; d_off the cloud offsets,
+    // d_words the clouds' bounds (6 n ordered floats) and the first compacted point of each (n + 1), d_launch the launch's records
+    // [NrmCloud x indexed clouds | {cloud record, block within it} x blocks]
     struct NormalBufs {
         DevBuf<float> normal, curv, eig;
         DevBuf<unsigned long long> cnt;
+        PairSet clouds;
+        DevBuf<int64_t> d_off;
+        DevBuf<uint32_t> d_words;
+        DevBuf<unsigned char> d_launch;
     };
     NormalBufs nrm;
     // kept normals and the second engine (normals.hip: dcreg_target_normals_keep / _set / _drop; normal_icp.hip: dcreg_linearize_normals).
@@ -453,7 +464,9 @@ struct dcreg_ctx {
     // the third engine (gicp.hip: dcreg_linearize_gicp; normals.hip: dcreg_source_normals_keep / _set / _get / _drop).  src_normals: float4
     // {nx, ny, nz, curvature} per SOURCE point in the context's curve order - lane i of k_glin reads it beside d_src[i]; dropped by every
     // call that replaces the source's points (context.hip source_commit), left alone by the batched calls.  The warm words are nicp.warm:
-    // both 1-NN engines look for the same nearest point.  tmp: the original-order form of a get; partials / d_out / dbg as nicp's
+    // both 1-NN engines look for the same nearest point.  tmp: the original-order form of a get; partials / d_out / dbg as nicp's.
+    // The batched form (k_glin_batch: dcreg_gicp_batch_begin / _end) has no buffers of its own: it runs in nicp's launch slots and warm
+    // slots (normal_icp.hip one_nn_batch_begin) and reads a frame's normals from FrameSet::normals
     struct GicpBufs {
         DevBuf<float4> src_normals; bool src_kept = false;
         DevBuf<float4> tmp;
@@ -619,6 +632,24 @@ struct OneNnBound { double radius_sq; float bound_f; int max_ring; };
 int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what);
 OneNnBound one_nn_bound(const GridDev &g, double search_radius);
 int one_nn_warm_reserve(dcreg_ctx *c);
+// ... and what their batched forms share (dcreg_normals_batch_begin / _end, dcreg_gicp_batch_begin / _end): the two launch slots and the warm
+// slots of NormalIcpBufs.  one_nn_batch_begin makes every refusal of include/dcreg_debug.h before anything is queued (`extra`: the engine's
+// own state refusals, after "no kept normals"; frames = frame_ids were given), uploads the poses and slices, has `launch` queue the engine's
+// kernel for the filled record, then queues k_finalize, the result copy and the slot's event; one_nn_batch_end waits for that event
+struct OneNnBatch {
+    const float4 *src; uint32_t n_src;          // the frames' points (slices != null) or the own source
+    GridDev g;                                  // the whole map's index
+    const float4 *normals;                      // the map's kept normals
+    const PoseArg *poses; const uint2 *slices;  // device
+    OneNnBound bound;
+    uint32_t *warm; uint32_t warm_stride;
+    double *partials; uint32_t nbx; int n_poses;
+    const dcreg_lin_params *p;
+};
+int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
+                       const dcreg_lin_params *p, int (*extra)(dcreg_ctx *, bool frames), void (*launch)(dcreg_ctx *, const OneNnBatch &),
+                       const char *kernel_name);
+int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs);
 const uint32_t *one_nn_warm_take(dcreg_ctx *c);
 void one_nn_warm_done(dcreg_ctx *c);
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
@@ -685,6 +716,13 @@ int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, 
 // context.hip: the index of the n points at raw built into d, and the empty-space field of its grid
 int build_index(dcreg_ctx *c, const float4 *raw, int64_t n, dcreg_ctx::IndexSet &d, double radius_hint, uint32_t *occupied_out, const double *box = nullptr);
 int build_gap_field(dcreg_ctx *c, dcreg_ctx::IndexSet &d, double radius_hint);
+// context.hip: the indices of n_t clouds at once, as pairs_build builds its targets' (one sort per pass over all of them; synchronises and
+// launches do not grow with n_t).  Cloud t = the count[t] packed points from raw[first[t]] (count 0: none, no index), bounds in `words` (3 n_t
+// minima, then 3 n_t maxima, ordered floats, all finite); radius_hint 0: cells from the density alone; max_cells: table budget per cloud.
+// Fills grids[t] / built[t]; the arrays live in ps.  The grids carry no gap field and no owners: knn_search reads neither when they are null
+int clouds_index_build(dcreg_ctx *c, dcreg_ctx::PairSet &ps, const float4 *raw, int n_t, const std::vector<int64_t> &count,
+                       const std::vector<int64_t> &first, const std::vector<uint32_t> &words, double radius_hint, double max_cells,
+                       std::vector<GridDev> &grids, std::vector<uint8_t> &built);
 // outliers.hip: one call's filter over the n packed points at `in` (input order, w = the index).  map == null: the used points are compacted
 // and indexed (c->outl.idx); otherwise the points ARE the map behind that index (all finite) and its grid is searched.  Leaves the scores in
 // c->outl.score, the keep flags and their exclusive scan in c->outl.keep / pos (n + 1 entries) and the counts in r; waits for the stream.
@@ -708,6 +746,11 @@ int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t
 // it, 0 = from the density); waits for the stream for *n_used.  outlier_rings: the rings a walk needs to cover a squared radius
 int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used);
 int outlier_rings(const GridDev &g, float bound);
+// ... and its first two kernels alone, for many clouds at once: used flags and their scan (n + 1 entries in c->outl.used / upos) and ALL used
+// points compacted into c->outl.cpts (w = the input index); nothing is waited for
+int outlier_used_compact(dcreg_ctx *c, const float4 *in, int64_t n);
+// normals.hip: the parameter refusals of dcreg_normals (engine.cpp reaches it through dcreg_normal_params_check)
+int normals_check(dcreg_ctx *c, const dcreg_normal_params *p);
 // normals.hip: the kept normals follow an update of the map ("normals_follow", include/dcreg.h).  normals_follow_wanted: asked BEFORE the
 // update drops them (option on, normals kept, and kept by dcreg_target_normals_keep).  normals_follow_carry (a removal, beside k_crop_raw,
 // before anything is swapped): the survivors' normals and reaches compacted by flag_r / pos_r into the alt arrays; false: out of memory,

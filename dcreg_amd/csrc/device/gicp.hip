@@ -5,6 +5,8 @@
 //                  own normal, the covariance of the pair from the two normals, its Cholesky factor and W = L^-1; then THREE rows per
 //                  point, each built just before its pass over the matrix cores (wave_gram3_mfma below: row 0 of every point precedes
 //                  row 1 of any, one accumulator through the 24 steps), and the block row in LDS, added in wave order
+//   k_glin_batch   the same for many poses in ONE launch (dcreg_gicp_batch_begin: the engine of dcreg_register_frames_gicp): block (x, pose)
+//                  runs glin_point on block x of the pose's own source slice and its kept normals, and leaves its row at partials[pose][x]
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_nlin
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  The search reads and writes the warm words of
 // k_nlin (context.hpp NormalIcpBufs::warm): both engines look for the same nearest point, and the word decides how fast, never which.
@@ -57,6 +59,43 @@ __device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int
     u1 = dpp_add<0x128, 0xF>(u1);
 }
 
+// What a block does with its points once glin_point has run (k_glin and k_glin_batch): the three rows of every flag-1 point through
+// wave_gram3_mfma (the wave's RunList is free now: it stages the rows; a lane past the cloud's end or with another flag than 1 carries
+// zero rows), the wave's Gram matrix and counts in LDS, added in wave order, and the block row at `out`.  note(k, row): the dump's hook.
+template <class Note>
+__device__ __forceinline__ void glin_block_rows(const PoseArg &P, uint8_t flag, float sx, float sy, float sz, const GlinPoint &o, RunList &rl,
+                                                double (*gm)[64], double (*cnt)[2], double *__restrict__ out, Note note) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    auto row_of = [&](int k, double (&row)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) row[j] = 0.0;
+        if (flag == 1) glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+        note(k, row);
+    };
+    double u0, u1;
+    wave_gram3_mfma(row_of, rl.stage, lane, u0, u1);
+    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
+    if ((lane & 15) < 8) {
+        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
+        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
+    }
+    const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
+    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
+    __syncthreads();
+    if (threadIdx.x < kSlots) {
+        double t = 0.0;
+        if (threadIdx.x < 29) {
+            const int e = gram_entry_of_slot(threadIdx.x);
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
+        } else if (threadIdx.x < 31) {
+#pragma unroll
+            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
+        }
+        out[threadIdx.x] = t;
+    }
+}
+
 // warm_in / warm_out / partials: as k_nlin's.  src_normals: float4 per source point in the order of src.  Slot 29 counts the effective
 // POINTS (not rows), slot 30 the points inside the radius.
 template <bool DUMP>
@@ -67,7 +106,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
     __shared__ RunList runs[kLinBlock / kWave];
     __shared__ double gm[kLinBlock / kWave][64];
     __shared__ double cnt[kLinBlock / kWave][2];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
     const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
     uint8_t flag = 0;
     float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -92,11 +131,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
             }
         }
     }
-    // (the wave's RunList is free now: it stages the rows; a lane past the cloud's end or with another flag than 1 carries zero rows)
-    auto row_of = [&](int k, double (&row)[8]) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) row[j] = 0.0;
-        if (flag == 1) glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+    glin_block_rows(P, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
         if constexpr (DUMP) {
             if (i < n_src) {
                 if (d.r) d.r[3 * oi + k] = row[7];
@@ -106,29 +141,44 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
                 }
             }
         }
-    };
-    double u0, u1;
-    wave_gram3_mfma(row_of, runs[wave].stage, lane, u0, u1);
-    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
-    if ((lane & 15) < 8) {
-        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
-        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
+    });
+}
+
+// Many poses in one launch: k_glin as k_nlin_batch is k_nlin (normal_icp.hip).  Block (x, pose): pose = poses[blockIdx.y], read through a
+// block-uniform index; its cloud is slices[pose] = {first point, points} of src AND of src_normals (a frame of the loaded frames and that
+// frame's kept normals: the same positions; a block past the end of a short frame's slice exits before it touches anything) or, slices ==
+// null, the n_src points at src (the context's own source and its kept source normals).  The warm words are k_nlin_batch's slots.  The body
+// is glin_point and glin_block_rows, unchanged; the block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the
+// rows and additions of the pose's single launch.
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin_batch(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
+                                                                           const float4 *__restrict__ normals, const float4 *__restrict__ src_normals,
+                                                                           const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
+                                                                           GlinArgs a, uint32_t *warm, uint32_t warm_stride,
+                                                                           double *__restrict__ partials, uint32_t n_blocks_x) {
+    __shared__ RunList runs[kLinBlock / kWave];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const uint32_t pose_id = blockIdx.y;
+    if (slices) {                                    // (uniform per block: before anything is touched)
+        const uint2 sl = slices[pose_id];
+        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
+        src += sl.x; src_normals += sl.x; n_src = sl.y;
     }
-    const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
-    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-        double t = 0.0;
-        if (threadIdx.x < 29) {
-            const int e = gram_entry_of_slot(threadIdx.x);
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
-        } else if (threadIdx.x < 31) {
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
-        }
-        partials[(size_t)blockIdx.x * kSlots + threadIdx.x] = t;
+    const PoseArg &P = poses[pose_id];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    uint8_t flag = 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    GlinPoint o;
+    if (i < n_src) {
+        uint32_t *w = P.state != kNoIdx ? warm + (size_t)P.state * warm_stride + i : nullptr;
+        const float4 s4 = src[i];
+        sx = s4.x; sy = s4.y; sz = s4.z;
+        flag = glin_point(g, runs[wave], normals, P, a, s4, src_normals + i, (w && P.fresh == 0u) ? *w : kNoIdx, o);
+        if (w) *w = o.pos;
     }
+    glin_block_rows(P, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
+                    [](int, const double (&)[8]) {});
 }
 
 int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_glin_debug *dbg) {
@@ -194,6 +244,20 @@ int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     return DCREG_OK;
 }
 
+// ---- the batched form: the second engine's seam (normal_icp.hip one_nn_batch_begin) with this engine's state refusals and kernel
+int gicp_batch_refuse(dcreg_ctx *c, bool frames) {
+    if (frames && !c->frames.normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
+    if (!frames && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+void glin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
+    GlinArgs a;
+    a.radius_sq = L.bound.radius_sq; a.bound_f = L.bound.bound_f; a.max_ring = L.bound.max_ring;
+    a.c = 1.0 - c->opt_gicp_epsilon;
+    hipLaunchKernelGGL(k_glin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals,
+                       L.slices ? c->frames.normals.data() : c->gicp.src_normals.data(), L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx);
+}
+
 }  // namespace
 }  // namespace dcreg
 
@@ -203,6 +267,11 @@ extern "C" {
 int dcreg_linearize_gicp(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out) {
     return glin_run(c, R, t, p, out, nullptr);
 }
+int dcreg_gicp_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                           const int32_t *frame_ids, const dcreg_lin_params *p) {
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, gicp_batch_refuse, glin_batch_launch, "the k_glin_batch launch");
+}
+int dcreg_gicp_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 int dcreg_linearize_gicp_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
                                dcreg_glin_debug *dbg) {
     if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }

@@ -198,13 +198,24 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     return DCREG_OK;
 }
 
-// ---- the batched form (context.hpp NormalIcpBufs::BatchSlot).  begin: every refusal before anything is queued or changed, then the pose
-// upload, k_nlin_batch, k_finalize and the copy of the result rows to pinned memory on the context's stream, and the slot's event behind
-// them; end waits for that event - never for what the other slot queued behind it.
+// the second engine's kernel for a batched launch (one_nn_batch_begin below)
+void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
+    const NlinArgs a = nlin_args(L.g, L.p);
+    hipLaunchKernelGGL(k_nlin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals, L.poses, L.slices, a,
+                       L.warm, L.warm_stride, L.partials, L.nbx);
+}
+
+}  // namespace
+
+// ---- the batched form (context.hpp NormalIcpBufs::BatchSlot), shared with gicp.hip.  begin: every refusal before anything is queued or
+// changed, then the pose upload, the engine's batched kernel (`launch`: k_nlin_batch, k_glin_batch), k_finalize and the copy of the result
+// rows to pinned memory on the context's stream, and the slot's event behind them; end waits for that event - never for what the other
+// slot queued behind it.  The two launch slots serve both 1-NN engines: a pending slot of either refuses the other.
 using BatchSlot = dcreg_ctx::NormalIcpBufs::BatchSlot;
 
-int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
-                 const dcreg_lin_params *p) {
+int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
+                       const dcreg_lin_params *p, int (*extra)(dcreg_ctx *, bool frames), void (*launch)(dcreg_ctx *, const OneNnBatch &),
+                       const char *kernel_name) {
     if (!c) return DCREG_E_INVALID;
     dcreg_ctx::NormalIcpBufs &B = c->nicp;
     if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
@@ -230,6 +241,7 @@ int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const do
             n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
         }
     } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    if (extra) if (int rc = extra(c, frame_ids != nullptr)) return rc;
     if (state_ids) {
         std::vector<uint8_t> seen((size_t)std::max<int64_t>(B.n_slots, 1), 0);
         for (int i = 0; i < n_poses; ++i) {
@@ -275,7 +287,6 @@ int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const do
         for (int i = 0; i < n_poses; ++i) hs[i] = slice[(size_t)frame_ids[i]];
         d_slices = (const uint2 *)(S.d_poses.data() + pose_bytes);
     }
-    const NlinArgs a = nlin_args(whole.grid, p);
     auto failed = [&](hipError_t e, const char *what) {          // something may be queued: what it leaves in the slots is unknown
         for (int32_t sid : S.ids) B.slot_valid[(size_t)sid] = 0;
         c->fail("%s failed: %s", what, hipGetErrorString(e));
@@ -283,10 +294,15 @@ int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const do
     };
     hipError_t e = hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return failed(e, "the pose upload");
-    hipLaunchKernelGGL(k_nlin_batch, dim3(nbx, (unsigned)n_poses), dim3(kLinBlock), 0, c->stream, frame_ids ? c->frames.src.data() : c->d_src.data(),
-                       (uint32_t)c->n_src, whole.grid, B.normals.data(), (const PoseArg *)S.d_poses.data(), d_slices, a,
-                       B.slots.data(), (uint32_t)B.slot_stride, S.partials.data(), nbx);
-    if ((e = hipGetLastError()) != hipSuccess) return failed(e, "the k_nlin_batch launch");
+    OneNnBatch L;
+    L.src = frame_ids ? c->frames.src.data() : c->d_src.data(); L.n_src = (uint32_t)c->n_src;
+    L.g = whole.grid; L.normals = B.normals.data();
+    L.poses = (const PoseArg *)S.d_poses.data(); L.slices = d_slices;
+    L.bound = one_nn_bound(whole.grid, p->search_radius);
+    L.warm = B.slots.data(); L.warm_stride = (uint32_t)B.slot_stride;
+    L.partials = S.partials.data(); L.nbx = nbx; L.n_poses = n_poses; L.p = p;
+    launch(c, L);
+    if ((e = hipGetLastError()) != hipSuccess) return failed(e, kernel_name);
     if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, d_slices);
     else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, (const uint2 *)nullptr);
     if ((e = hipGetLastError()) != hipSuccess) return failed(e, "the k_finalize launch");
@@ -300,7 +316,7 @@ int nbatch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const do
     return DCREG_OK;
 }
 
-int nbatch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
+int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     if (!c) return DCREG_E_INVALID;
     if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
     BatchSlot &S = c->nicp.batch[slot];
@@ -322,8 +338,6 @@ int nbatch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     }
     return DCREG_OK;
 }
-
-}  // namespace
 
 // ---- shared with gicp.hip (context.hpp)
 int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what) {
@@ -400,7 +414,7 @@ int dcreg_normals_reset_slot(dcreg_ctx *c, int64_t slot_id) {
 }
 int dcreg_normals_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                               const int32_t *frame_ids, const dcreg_lin_params *p) {
-    return nbatch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p);
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, nullptr, nlin_batch_launch, "the k_nlin_batch launch");
 }
-int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return nbatch_end(c, slot, outs); }
+int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 }

@@ -6,6 +6,8 @@
 //                 the last k of K slots; then the lane gathers its k neighbours in rank order (twice: the mean, the covariance - they are
 //                 hot in L2), solves the 3x3 problem with six Jacobi sweeps in registers, orients the normal and writes 12 + 4 (+ 12) bytes
 //                 at the point's input index
+//   k_nrm_batch<K> the same body (nrm_point) for many clouds in ONE launch (dcreg_normals_clouds*, dcreg_frames_normals_keep): every cloud's
+//                 used points behind a grid of its own, all grids built at once (context.hip clouds_index_build); a block serves one cloud
 //   k_follow_*    the kept normals follow an update of the map ("normals_follow"): the cells of the points that came or went are marked,
 //                 the map points whose reach touches a marked cell are compacted and go through k_nrm again, the rest is carried
 // A point's result depends on the cloud only: the index decides how fast the neighbours are found, never which.
@@ -14,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../../include/dcreg_debug.h"
 #include "context.hpp"
 
 // every multiply and add below rounds once: the rule is stated operation by operation
@@ -98,19 +101,15 @@ static __global__ void k_nrm_fill(float *__restrict__ a, int64_t n, float v) {
 // the outputs go there (a null output is not wanted).  cnt[0] += points with a normal, cnt[1] += sparse points (one atomic pair per wave)
 // kept / reach (the map's kept normals, both or neither): {normal, curvature} - NaN for a sparse point - and the point's REACH, the squared
 // distance within which a point that comes or goes can change its result: the k-th neighbour's d2, or the search bound when sparse
+// (nrm_point: the body of one lane - k_nrm and k_nrm_batch below differ only in where the point, its grid and its counters come from)
 template <int K>
-static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict__ q, uint32_t n, GridDev g, float bound_f, int max_ring, int k,
-                                                       NrmArgs a, float *__restrict__ normal, float *__restrict__ curv, float *__restrict__ eig,
-                                                       float4 *__restrict__ kept, float *__restrict__ reach,
-                                                       unsigned long long *__restrict__ cnt) {
-    __shared__ RunList runs[kBlock / kWave];
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 s4 = q[i];
+DCREG_DEVFN void nrm_point(const float4 s4, const GridDev &g, RunList &rl, float bound_f, int max_ring, int k, const NrmArgs &a,
+                           float *__restrict__ normal, float *__restrict__ curv, float *__restrict__ eig, float4 *__restrict__ kept,
+                           float *__restrict__ reach, unsigned long long *__restrict__ cnt) {
     const uint32_t self = __float_as_uint(s4.w);
     HeapNrm<K> hp;
     hp.k = k;
-    knn_search<HeapNrm<K>>(g, runs[threadIdx.x / kWave], s4.x, s4.y, s4.z, bound_f, max_ring, hp);
+    knn_search<HeapNrm<K>>(g, rl, s4.x, s4.y, s4.z, bound_f, max_ring, hp);
     const bool sparse = hp.pos[K - 1] == kNoIdx;       // (sorted: the last slot is the last to fill)
     if (!sparse) {
         const double px = (double)s4.x, py = (double)s4.y, pz = (double)s4.z;
@@ -176,6 +175,97 @@ static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict_
     }
 }
 
+template <int K>
+static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict__ q, uint32_t n, GridDev g, float bound_f, int max_ring, int k,
+                                                       NrmArgs a, float *__restrict__ normal, float *__restrict__ curv, float *__restrict__ eig,
+                                                       float4 *__restrict__ kept, float *__restrict__ reach,
+                                                       unsigned long long *__restrict__ cnt) {
+    __shared__ RunList runs[kBlock / kWave];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    nrm_point<K>(q[i], g, runs[threadIdx.x / kWave], bound_f, max_ring, k, a, normal, curv, eig, kept, reach, cnt);
+}
+
+// ---- many clouds in one launch (dcreg_normals_clouds*, dcreg_frames_normals_keep).  Every indexed cloud has a record - its own grid (the
+// cloud's used points in its cell order are the grid's points: w = the point's index in the call's input), the rings that cover the search
+// bound in its cells (-1: unbounded) and its place in the call - and as many blocks as its points need: block b is block blk[b].y of record
+// blk[b].x, so a block never straddles two clouds and reads its grid through a block-uniform index.  Outputs at the point's input index;
+// the counts of record r's cloud at cnt[2 cloud], cnt[2 cloud + 1]
+struct NrmCloud {
+    GridDev g;
+    int max_ring;
+    uint32_t cloud;
+};
+template <int K>
+static __global__ __launch_bounds__(kBlock) void k_nrm_batch(const NrmCloud *__restrict__ clouds, const uint2 *__restrict__ blk, float bound_f, int k,
+                                                             NrmArgs a, float *__restrict__ normal, float *__restrict__ curv,
+                                                             unsigned long long *__restrict__ cnt) {
+    __shared__ RunList runs[kBlock / kWave];
+    const uint2 b = blk[blockIdx.x];
+    const NrmCloud &C = clouds[b.x];
+    const GridDev g = C.g;
+    const uint32_t i = b.y * kBlock + threadIdx.x;
+    if (i >= g.n_pts) return;
+    nrm_point<K>(g.pts[i], g, runs[threadIdx.x / kWave], bound_f, C.max_ring, k, a, normal, curv, nullptr, nullptr, nullptr, cnt + 2 * (size_t)C.cloud);
+}
+
+// the bounds of every cloud's used points (ordered floats: bounds[3 s + a] minima, bounds[3 n_clouds + 3 s + a] maxima, as k_pairs_pack
+// leaves a target's) - six atomics per wave where the wave's used points belong to one cloud, per lane across a boundary
+static __global__ __launch_bounds__(256) void k_ncl_bounds(const float4 *__restrict__ pts, int64_t n, const uint32_t *__restrict__ used,
+                                                          const int64_t *__restrict__ off, int n_clouds, uint32_t *__restrict__ bounds) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n && used[i] != 0u;
+    const uint32_t s = live ? seg_of(off, n_clouds, i) : 0u;
+    float v[3] = {0.f, 0.f, 0.f};
+    if (live) { const float4 p = pts[i]; v[0] = p.x; v[1] = p.y; v[2] = p.z; }
+    const unsigned long long lanes = __ballot(live);
+    if (lanes == 0ull) return;
+    const uint32_t s0 = (uint32_t)__shfl((int)s, __ffsll(lanes) - 1);
+    if (__ballot(live && s == s0) == lanes) {
+        float mn[3], mx[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = live ? v[a] : 3.4e38f; mx[a] = live ? v[a] : -3.4e38f;
+            for (int o = 32; o > 0; o >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o)); }
+        }
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { atomicMin(&bounds[3 * s0 + a], f2ord(mn[a])); atomicMax(&bounds[3 * n_clouds + 3 * s0 + a], f2ord(mx[a])); }
+        }
+    } else if (live) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { atomicMin(&bounds[3 * s + a], f2ord(v[a])); atomicMax(&bounds[3 * n_clouds + 3 * s + a], f2ord(v[a])); }
+    }
+}
+// starts[s] = the used points in front of cloud s (n_clouds + 1 entries: upos has n + 1)
+static __global__ void k_ncl_starts(const uint32_t *__restrict__ upos, const int64_t *__restrict__ off, int n_clouds, uint32_t *__restrict__ starts) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s <= n_clouds) starts[s] = upos[off[s]];
+}
+// the kept normals of loaded frames: position p of the frames' curve-ordered points (frame f from dst[f], every frame padded to a query
+// block; w = the point's index within its frame) takes the normal (3 floats, `stride` apart) and curvature (null: NaN) of upload point
+// off[f] + w -> float4 p; the padding gets NaN
+static __global__ void k_nrm_pack_frames(const float4 *__restrict__ src, int64_t n_padded, const uint32_t *__restrict__ dst, const int64_t *__restrict__ off,
+                                         int n_frames, const float *__restrict__ normal, int64_t stride, const float *__restrict__ curv,
+                                         float4 *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_padded) return;
+    int lo = 0, hi = n_frames - 1;                       // the last frame that starts at or before p (empty frames share a start)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)dst[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    const int64_t local = p - (int64_t)dst[lo];
+    const float nan_ = __builtin_nanf("");
+    float4 v = float4{nan_, nan_, nan_, nan_};
+    if (local < off[lo + 1] - off[lo]) {
+        const size_t oi = (size_t)(off[lo] + (int64_t)__float_as_uint(src[p].w));
+        const float *q = normal + oi * (size_t)stride;
+        v = float4{q[0], q[1], q[2], curv ? curv[oi] : nan_};
+    }
+    out[p] = v;
+}
+
 // the kept form: normal (3 floats, `stride` apart) and curvature (null: NaN) of point i -> float4 i
 static __global__ void k_nrm_pack(const float *__restrict__ normal, int64_t stride, const float *__restrict__ curv, int64_t n, float4 *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,14 +298,18 @@ void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, flo
 }
 // the search of a parameter set in a grid, and the launch of the instantiation its k takes
 struct NrmSearch { float bound; int max_ring; NrmArgs a; };
-NrmSearch nrm_search(const GridDev &g, const dcreg_normal_params *p) {
+NrmSearch nrm_search_bound(const dcreg_normal_params *p) {       // (the bound and the arguments: no grid yet, max_ring -1)
     NrmSearch s{3.0e38f, -1, {}};
     if (p->search_radius > 0.0) {
         s.bound = (float)(p->search_radius * p->search_radius);
         if (!(s.bound <= 3.0e38f)) s.bound = 3.0e38f;
-        s.max_ring = outlier_rings(g, s.bound);
     }
     s.a.vx = p->viewpoint[0]; s.a.vy = p->viewpoint[1]; s.a.vz = p->viewpoint[2]; s.a.orient = p->orient;
+    return s;
+}
+NrmSearch nrm_search(const GridDev &g, const dcreg_normal_params *p) {
+    NrmSearch s = nrm_search_bound(p);
+    if (p->search_radius > 0.0) s.max_ring = outlier_rings(g, s.bound);
     return s;
 }
 void launch_nrm_k(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, const dcreg_normal_params *p, float *normal, float *curv, float *eig,
@@ -227,6 +321,8 @@ void launch_nrm_k(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, c
     else launch_nrm<32>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
 }
 
+}  // namespace
+
 int normals_check(dcreg_ctx *c, const dcreg_normal_params *p) {
     if (!p) { c->fail("null normal parameters"); return DCREG_E_INVALID; }
     if (p->k < kMinK || p->k > kMaxK) { c->fail("normal k is %d: %d .. %d expected", p->k, kMinK, kMaxK); return DCREG_E_INVALID; }
@@ -235,6 +331,8 @@ int normals_check(dcreg_ctx *c, const dcreg_normal_params *p) {
     if (!(std::isfinite(p->viewpoint[0]) && std::isfinite(p->viewpoint[1]) && std::isfinite(p->viewpoint[2]))) { c->fail("the normal viewpoint is not finite"); return DCREG_E_INVALID; }
     return DCREG_OK;
 }
+
+namespace {
 
 struct NormalOut {
     float *normal, *curv, *eig;       // the caller's buffers (null: not wanted)
@@ -296,6 +394,192 @@ int normals_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, boo
     const bool indexed = n_used >= p->k;
     const NormalOut o{normal, curv, eig, on_device};
     return normals_run(c, indexed ? B.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? B.idx.grid : GridDev{}, n, n_used, p, o, info);
+}
+
+// ------------------------------------------------------------------------------------------ many clouds in one call
+// The n packed points at `in` (input order, w = the index; on the device) are n_clouds clouds, cloud s = [off[s], off[s + 1]) (host memory,
+// checked by the caller).  ONE used / scan / compaction pass and ONE bounds pass over all of them, ONE readback of every cloud's bounds
+// and used count; the clouds with at least k used points are indexed together (clouds_index_build: one sort per pass), the others get
+// no grid and come out all sparse; then ONE upload of the launch's records, ONE k_nrm_batch and ONE readback of the counts.  Leaves the
+// normals (3 n floats) and curvatures (n floats) in c->nrm.normal / curv - NaN where a point has none - with the work queued on the
+// stream and waited for; infos (may be null): one record per cloud, as dcreg_normals fills it.
+int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, const int64_t *off, const dcreg_normal_params *p,
+                       dcreg_normal_info *infos) {
+    dcreg_ctx::NormalBufs &B = c->nrm;
+    const size_t nc = (size_t)n_clouds;
+    if (B.normal.ensure(c, 3 * (size_t)n) || B.curv.ensure(c, (size_t)n) || B.cnt.ensure(c, 2 * nc) || B.d_off.ensure(c, nc + 1) ||
+        B.d_words.ensure(c, 7 * nc + 1))
+        return DCREG_E_NOMEM;
+    const float nanf_ = __builtin_nanf("");
+    hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, B.normal.data(), 3 * n, nanf_);
+    hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.curv.data(), n, nanf_);
+    HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * nc * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * (nc + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(B.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * nc, c->stream));
+    HIP_TRY(c, hipMemsetAsync(B.d_words.data() + 3 * nc, 0, sizeof(uint32_t) * 3 * nc, c->stream));
+    if (int rc = outlier_used_compact(c, in, n)) return rc;
+    hipLaunchKernelGGL(k_ncl_bounds, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, c->outl.used.data(), B.d_off.data(), n_clouds, B.d_words.data());
+    hipLaunchKernelGGL(k_ncl_starts, dim3(blocks((int64_t)nc + 1, 256)), dim3(256), 0, c->stream, c->outl.upos.data(), B.d_off.data(), n_clouds,
+                       B.d_words.data() + 6 * nc);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> words(7 * nc + 1);
+    HIP_TRY(c, hipMemcpyAsync(words.data(), B.d_words.data(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const uint32_t *starts = words.data() + 6 * nc;
+    std::vector<int64_t> used(nc), count(nc), first(nc);
+    bool any = false;
+    for (size_t s = 0; s < nc; ++s) {
+        used[s] = (int64_t)starts[s + 1] - (int64_t)starts[s];
+        count[s] = used[s] >= p->k ? used[s] : 0;             // (fewer than k used points: no index, all sparse - as the single call)
+        first[s] = (int64_t)starts[s];
+        any = any || count[s] > 0;
+    }
+    std::vector<unsigned long long> cnt(2 * nc, 0ull);
+    if (any) {
+        std::vector<GridDev> grids;
+        std::vector<uint8_t> built;
+        words.resize(6 * nc);
+        // (the table budget of a pair target, and at most 2^22 entries a cloud: the clouds of a call share the device)
+        const double max_cells = (double)std::min<int64_t>(c->opt_pair_max_table_entries, (int64_t)1 << 22);
+        if (int rc = clouds_index_build(c, B.clouds, c->outl.cpts.data(), n_clouds, count, first, words, p->search_radius, max_cells, grids, built)) return rc;
+        const NrmSearch sr = nrm_search_bound(p);                // (the rings are counted per grid below)
+        std::vector<NrmCloud> recs;
+        std::vector<uint2> blk;
+        for (size_t s = 0; s < nc; ++s) {
+            if (!built[s]) continue;
+            NrmCloud r;
+            r.g = grids[s];
+            r.max_ring = p->search_radius > 0.0 ? outlier_rings(grids[s], sr.bound) : -1;
+            r.cloud = (uint32_t)s;
+            const uint32_t nb = blocks(count[s], kBlock);
+            for (uint32_t b = 0; b < nb; ++b) blk.push_back(make_uint2((uint32_t)recs.size(), b));
+            recs.push_back(r);
+        }
+        const size_t rec_bytes = recs.size() * sizeof(NrmCloud), bytes = rec_bytes + blk.size() * sizeof(uint2);
+        std::vector<unsigned char> h(bytes);
+        std::memcpy(h.data(), recs.data(), rec_bytes);
+        std::memcpy(h.data() + rec_bytes, blk.data(), blk.size() * sizeof(uint2));
+        if (B.d_launch.ensure(c, bytes)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(B.d_launch.data(), h.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        const NrmCloud *d_recs = (const NrmCloud *)B.d_launch.data();
+        const uint2 *d_blk = (const uint2 *)(B.d_launch.data() + rec_bytes);
+        const dim3 grid((unsigned)blk.size()), block(kBlock);
+        const int k = p->k;
+        if (k <= 8) hipLaunchKernelGGL(k_nrm_batch<8>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+        else if (k <= 16) hipLaunchKernelGGL(k_nrm_batch<16>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+        else hipLaunchKernelGGL(k_nrm_batch<32>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(cnt.data(), B.cnt.data(), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));          // (h, recs and blk are the sources of the upload)
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (infos)
+        for (size_t s = 0; s < nc; ++s) {
+            infos[s].n_in = off[s + 1] - off[s]; infos[s].n_finite = used[s];
+            infos[s].n_sparse = count[s] > 0 ? (int64_t)cnt[2 * s + 1] : used[s];
+            infos[s].n_out = count[s] > 0 ? (int64_t)cnt[2 * s] : 0;
+        }
+    return DCREG_OK;
+}
+
+// the offset rules of dcreg_voxel_downsample, and the size of one call
+int clouds_check(dcreg_ctx *c, int n_clouds, const int64_t *off) {
+    if (n_clouds < 0) { c->fail("negative cloud count"); return DCREG_E_INVALID; }
+    if (n_clouds > 0 && !off) { c->fail("null cloud offsets"); return DCREG_E_INVALID; }
+    if (n_clouds > 0 && off[0] != 0) { c->fail("cloud offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int s = 0; s < n_clouds; ++s)
+        if (off[s + 1] < off[s]) { c->fail("cloud offsets decrease at cloud %d", s); return DCREG_E_INVALID; }
+    if (n_clouds > 0 && off[n_clouds] > (int64_t)INT32_MAX) { c->fail("too many points for one normal estimation (%lld)", (long long)off[n_clouds]); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+// dcreg_normals_clouds*: the clouds packed in one upload, the pass above, the copies to the caller
+int normals_clouds(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_normal_params *p,
+                   float *normal, float *curv, dcreg_normal_info *infos) {
+    if (!c) return DCREG_E_INVALID;
+    // (the arguments first, then the context's state: a call without clouds or without points queues nothing and asks for no state)
+    if (int rc = normals_check(c, p)) return rc;
+    if (stride < 3) { c->fail("invalid normal estimation arguments"); return DCREG_E_INVALID; }
+    if (int rc = clouds_check(c, n_clouds, off)) return rc;
+    if (!normal && !curv) { c->fail("no output buffer: normals or curvature expected"); return DCREG_E_INVALID; }
+    if (n_clouds == 0) return DCREG_OK;
+    const int64_t n = off[n_clouds];
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (n > 0) if (int rc = refuse_in_flight(c)) return rc;
+    if (infos) std::memset(infos, 0, sizeof(*infos) * (size_t)n_clouds);
+    if (n == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = upload_cloud(c, xyz, n, stride, on_device, c->outl.pts)) return rc;
+    if (int rc = normals_clouds_run(c, c->outl.pts.data(), n, n_clouds, off, p, infos)) return rc;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (normal) HIP_TRY(c, hipMemcpyAsync(normal, c->nrm.normal.data(), sizeof(float) * 3 * (size_t)n, kind, c->stream));
+    if (curv) HIP_TRY(c, hipMemcpyAsync(curv, c->nrm.curv.data(), sizeof(float) * (size_t)n, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
+// the loaded frames' host offsets (FrameSet keeps the slices) and the padded length of their curve-ordered points
+int64_t frames_offsets(const dcreg_ctx::FrameSet &fs, std::vector<int64_t> &off) {
+    off.assign(fs.slice.size() + 1, 0);
+    int64_t padded = 0;
+    for (size_t f = 0; f < fs.slice.size(); ++f) {
+        off[f + 1] = off[f] + (int64_t)fs.slice[f].y;
+        padded = (int64_t)fs.slice[f].x + ((int64_t)fs.slice[f].y + kLinBlock - 1) / kLinBlock * kLinBlock;
+    }
+    return padded;
+}
+
+// dcreg_frames_normals_keep: the pass above over the loaded frames in upload order (FrameSet::raw is what upload_cloud packs for
+// dcreg_normals_clouds: the same points, the same build, the same kernel), then one gather into every frame's curve order
+int frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = normals_check(c, p)) return rc;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (c->frames.slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+    dcreg_ctx::FrameSet &fs = c->frames;
+    std::vector<int64_t> off;
+    const int64_t padded = frames_offsets(fs, off), n = off.back();
+    const int n_frames = (int)fs.slice.size();
+    if (infos) std::memset(infos, 0, sizeof(*infos) * (size_t)n_frames);
+    HIP_TRY(c, hipSetDevice(c->device));
+    fs.normals_kept = false;                                    // (a failed call leaves none)
+    if (n > 0) {
+        if (fs.normals.ensure(c, (size_t)padded)) return DCREG_E_NOMEM;
+        if (int rc = normals_clouds_run(c, fs.raw.data(), n, n_frames, off.data(), p, infos)) return rc;
+        hipLaunchKernelGGL(k_nrm_pack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(), fs.d_off.data(),
+                           n_frames, c->nrm.normal.data(), (int64_t)3, c->nrm.curv.data(), fs.normals.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    fs.normals_kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_frames_normals_set: the caller's normals in the upload order of the load become the frames' kept normals, as given
+int frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_given, int64_t stride) {
+    if (!c) return DCREG_E_INVALID;
+    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (c->frames.slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+    dcreg_ctx::FrameSet &fs = c->frames;
+    std::vector<int64_t> off;
+    const int64_t padded = frames_offsets(fs, off), n = off.back();
+    if (n_given != n) { c->fail("the frames hold %lld points, %lld normals were given", (long long)n, (long long)n_given); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    fs.normals_kept = false;
+    if (n > 0) {
+        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
+        if (fs.normals.ensure(c, (size_t)padded) || c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_nrm_pack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(), fs.d_off.data(),
+                           (int)fs.slice.size(), c->d_stage.data(), stride, (const float *)nullptr, fs.normals.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    fs.normals_kept = true;
+    return DCREG_OK;
 }
 
 // dcreg_target_normals*: the whole map's points through the map's own index
@@ -634,6 +918,20 @@ int dcreg_normals_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t st
                          float *d_curvature_out, float *d_eigenvalues_out, dcreg_normal_info *info) {
     return normals_cloud(c, d_xyz, n, stride_floats, true, p, d_normals_out, d_curvature_out, d_eigenvalues_out, info);
 }
+int dcreg_normals_clouds(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_normal_params *p,
+                         float *normals_out, float *curvature_out, dcreg_normal_info *infos) {
+    return normals_clouds(c, n_clouds, xyz, offsets, stride_floats, false, p, normals_out, curvature_out, infos);
+}
+int dcreg_normals_clouds_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                const dcreg_normal_params *p, float *d_normals_out, float *d_curvature_out, dcreg_normal_info *infos) {
+    return normals_clouds(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_normals_out, d_curvature_out, infos);
+}
+int dcreg_frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) { return frames_normals_keep(c, p, infos); }
+int dcreg_frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_points, int64_t stride_floats) {
+    return frames_normals_set(c, normals, n_points, stride_floats);
+}
+int dcreg_frames_normals_kept(const dcreg_ctx *c) { return c && c->frames.normals_kept ? 1 : 0; }
+int dcreg_normal_params_check(dcreg_ctx *c, const dcreg_normal_params *p) { return c ? normals_check(c, p) : DCREG_E_INVALID; }
 int dcreg_target_normals(dcreg_ctx *c, const dcreg_normal_params *p, float *normals_out, float *curvature_out, float *eigenvalues_out,
                          int64_t capacity_points, dcreg_normal_info *info) {
     return normals_map(c, false, p, normals_out, curvature_out, eigenvalues_out, capacity_points, info);

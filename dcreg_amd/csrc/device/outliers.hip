@@ -385,19 +385,26 @@ int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t
 
 int outlier_rings(const GridDev &g, float bound) { return rings_for_bound(g, bound); }
 
-int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used_out) {
+int outlier_used_compact(dcreg_ctx *c, const float4 *in, int64_t n) {
     dcreg_ctx::OutlierBufs &B = c->outl;
     const size_t n1 = (size_t)n + 1;
     if (B.used.ensure(c, n1) || B.upos.ensure(c, n1) || B.cpts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_out_used, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, in, n, B.used.data());
     if (int rc = scan_excl(c, B.used.data(), B.upos.data(), n1)) return rc;
+    hipLaunchKernelGGL(k_out_compact, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.used.data(), B.upos.data(), B.cpts.data());
+    HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
+int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used_out) {
+    dcreg_ctx::OutlierBufs &B = c->outl;
+    if (int rc = outlier_used_compact(c, in, n)) return rc;
     uint32_t n_used = 0;
     HIP_TRY(c, hipMemcpyAsync(&n_used, B.upos.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     *n_used_out = n_used;
     if (n_used == 0 || (int64_t)n_used < min_used) return DCREG_OK;
-    hipLaunchKernelGGL(k_out_compact, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.used.data(), B.upos.data(), B.cpts.data());
     // (the build reports whether the table budget capped its cells: that word belongs to the target's builds)
     const bool capped = c->last_build_capped;
     int rc = build_index(c, B.cpts.data(), n_used, B.idx, hint, nullptr);

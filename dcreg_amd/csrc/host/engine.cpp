@@ -319,11 +319,15 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // frame takes its cloud with it, and an empty frame never takes a slot.
 // first_pair >= 0 (with frame_points): trial k is scan pair first_pair + k of dcreg_register_pairs - its source of the pairs' sources,
 // target k of the build batch dcreg_pairs_build left on the device (frame_points[k] = 0: the source or the target is empty)
-// normals: the second engine (dcreg_icp_run_trials_normals, dcreg_register_frames_normals; never pairs) - the launches are
-// dcreg_normals_batch_begin / _end with their warm slots instead of the first engine's and its neighbour states; everything else is shared
+// engine: Engine::normals, the second engine (dcreg_icp_run_trials_normals, dcreg_register_frames_normals; never pairs) - the launches are
+// dcreg_normals_batch_begin / _end with their warm slots instead of the first engine's and its neighbour states; Engine::gicp, the third
+// (dcreg_icp_run_trials_gicp, dcreg_register_frames_gicp) - dcreg_gicp_batch_begin / _end on the same launch and warm slots, the frames'
+// kept normals beside the frames; everything else is shared
+enum class Engine { planes, normals, gicp };
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
-                           int64_t first_pair = -1, bool normals = false) {
+                           int64_t first_pair = -1, Engine engine = Engine::planes) {
+    const bool normals = engine != Engine::planes;          // a 1-NN engine: the warm slots and launch slots of normal_icp.hip
     const auto t_total = Clock::now();
     const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
@@ -386,7 +390,8 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
             G.gids[(size_t)j] = (int32_t)S.trial;
             std::memcpy(&G.Rb[(size_t)j * 9], S.R, sizeof(S.R)); std::memcpy(&G.tb[(size_t)j * 3], S.t, sizeof(S.t));
         }
-        const int rc = normals ? dcreg_normals_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
+        const int rc = engine == Engine::gicp ? dcreg_gicp_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
+                     : normals ? dcreg_normals_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
                      : pairs ? dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm)
                      : frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
                               : dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
@@ -462,7 +467,7 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     const double total_ms = ms_since(t_total);
     if (std::getenv("DCREG_TRIALS_TIMING"))
         std::fprintf(stderr, "[dcreg_icp_run_trials%s] %lld trials in %d slots, %lld group steps: wait for results %.1f us/step, host %.1f us/step, wall %.1f us/step\n",
-                     normals ? "_normals" : "", (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
+                     engine == Engine::gicp ? "_gicp" : normals ? "_normals" : "", (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
                      1e3 * t_host_ms / std::max<int64_t>(n_steps, 1), 1e3 * total_ms / std::max<int64_t>(n_steps, 1));
     for (int64_t i = 0; i < n_trials; ++i) results[i].time_ms = total_ms / (double)n_trials;   // amortised: trials advance together
     return DCREG_OK;
@@ -503,7 +508,7 @@ int dcreg_icp_run_trials_normals(dcreg_ctx *ctx, int n_trials, const double *R0,
     dcreg_index_info_get(ctx, &info);
     if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
     if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
-    return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, true);
+    return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, Engine::normals);
 }
 
 int dcreg_register_frames_normals(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
@@ -523,7 +528,46 @@ int dcreg_register_frames_normals(dcreg_ctx *ctx, int n_frames, const float *xyz
     if (rc != DCREG_OK) return rc;
     std::vector<int64_t> points((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
-    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, true);
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, Engine::normals);
+}
+
+// The third engine's forms (include/dcreg.h): the same checks and the same core with the launches of gicp.hip; the frames' own normals are
+// estimated in one batched pass behind the load (dcreg_frames_normals_keep)
+int dcreg_icp_run_trials_gicp(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
+                              const dcreg_config *cfg, dcreg_trial_result *results) {
+    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (n_trials == 0) return DCREG_OK;
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
+    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    if (dcreg_source_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, Engine::gicp);
+}
+
+int dcreg_register_frames_gicp(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                               const dcreg_normal_params *frame_normals, const double *R0, const double *t0, int detection, int handling,
+                               const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (int rc = dcreg_normal_params_check(ctx, frame_normals)) return rc;
+    if (n_frames == 0) return DCREG_OK;
+    if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
+    if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
+    for (int f = 0; f < n_frames; ++f)
+        if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
+    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
+    if (rc != DCREG_OK) return rc;
+    if (frame_offsets[n_frames] > 0) {                                                // (all frames empty: nothing to estimate, nothing to run)
+        rc = dcreg_frames_normals_keep(ctx, frame_normals, nullptr);
+        if (rc != DCREG_OK) return rc;
+    }
+    std::vector<int64_t> points((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, Engine::gicp);
 }
 
 // Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,

@@ -871,6 +871,20 @@ int dcreg_normals(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_float
                   float *curvature_out, float *eigenvalues_out, dcreg_normal_info *info);
 int dcreg_normals_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const dcreg_normal_params *, float *d_normals_out,
                          float *d_curvature_out, float *d_eigenvalues_out, dcreg_normal_info *info);
+/* Many clouds in one call: cloud s = the points [offsets[s], offsets[s + 1]) of xyz (all clouds back to back, stride_floats floats per
+ * point; offsets holds n_clouds + 1 entries, in points, starting at 0 - host memory in both forms).  The outputs are packed back to back
+ * in input order, 3 floats per point of normals_out and 1 float per point of curvature_out (either may be NULL, not both; no eigenvalues
+ * in this form); infos (may be NULL) receives one record per cloud.  Every value and every record is BITWISE what dcreg_normals returns
+ * for that cloud alone with the same parameters - NaN for sparse and non-finite points included: a cloud's points never see another
+ * cloud's.  Every cloud's finite points are indexed on their own, in cells chosen from its own bounds and density, all clouds in one
+ * build (one upload, one sort per pass, one readback) and one kernel launch: the fixed cost of indexing a small cloud is paid once per
+ * call, and neither the synchronises nor the launches grow with n_clouds.  A cloud with fewer than k finite points gets no index and
+ * comes out all sparse, as in the single call.  n_clouds == 0 does nothing.  The refusals of dcreg_normals, and DCREG_E_INVALID for
+ * offsets that do not start at 0 or decrease and for a call of 2^31 points or more - all before anything is queued. */
+int dcreg_normals_clouds(dcreg_ctx *, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats,
+                         const dcreg_normal_params *, float *normals_out, float *curvature_out, dcreg_normal_info *infos);
+int dcreg_normals_clouds_device(dcreg_ctx *, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
+                                const dcreg_normal_params *, float *d_normals_out, float *d_curvature_out, dcreg_normal_info *infos);
 /* The resident map's points in index order; the outputs hold capacity_points points, at least the map's size. */
 int dcreg_target_normals(dcreg_ctx *, const dcreg_normal_params *, float *normals_out, float *curvature_out, float *eigenvalues_out,
                          int64_t capacity_points, dcreg_normal_info *info);
@@ -1108,7 +1122,8 @@ int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], i
  * either): one waited launch per iteration, the same aborts, fitness, convergence test, log records, covariance and status codes, the
  * same host step.  rmse keeps its formula sqrt(sum_r2 / n_eff): here the RMS Mahalanobis distance per effective point (three whitened
  * residuals each), not a distance in metres.  Of the configuration's linearisation parameters only search_radius is read.  One pose per
- * call: no batched, pairs, sharded / RCCL or Euler form of this engine. */
+ * call; dcreg_register_frames_gicp and dcreg_icp_run_trials_gicp (below) run many registrations in one call.  No pairs, sharded / RCCL
+ * or Euler form of this engine. */
 int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                        const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
@@ -1206,6 +1221,23 @@ int dcreg_register_frames_normals(dcreg_ctx *, int n_frames, const float *xyz, c
                                   dcreg_trial_result *results);
 int dcreg_icp_run_trials_normals(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection, int handling,
                                  const dcreg_config *, dcreg_trial_result *results);
+
+/* ... and for the third engine (dcreg_icp_run_gicp: plane-to-plane rows from the map's kept normals and each frame's own).  Arguments,
+ * argument rules, slots, record fields and amortised time_ms as above.  frame_normals: the rule every frame's own normals are estimated
+ * with - all frames in one batched pass (dcreg_normals_clouds' build and kernel over the loaded frames), kept beside the frames' points
+ * for the call; its refusals are those of dcreg_normals (DCREG_E_INVALID, before anything is queued).  Every iteration of a group of
+ * registrations is ONE batched launch (dcreg_debug.h: dcreg_gicp_batch_begin), and results[f] is bitwise what dcreg_set_source(frame f) +
+ * dcreg_source_normals_keep(frame_normals) + dcreg_icp_run_gicp(R0 f, t0 f) give on a context with the same map, kept map normals and
+ * options ("gicp_epsilon" among them); for trials, dcreg_icp_run_gicp of the context's own source and its kept source normals from each
+ * pose.  An empty frame gets status 3; a frame with fewer than k points runs and ends with status 1 (none of its points has a normal:
+ * n_eff = 0).  DCREG_E_STATE: no target, no kept map normals, or - the trials form - no kept source normals; results are then left
+ * untouched.  The context's own source and its kept normals, the warm positions of the single-pose 1-NN launches, the first engine's
+ * states, the window index and the map's kept normals are left as they were. */
+int dcreg_register_frames_gicp(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                               const dcreg_normal_params *frame_normals, const double *R0_9, const double *t0_3, int detection,
+                               int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
+int dcreg_icp_run_trials_gicp(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection, int handling,
+                              const dcreg_config *, dcreg_trial_result *results);
 
 /* Many scan pairs registered in one call, each against a target of its own (loop-closure candidates against their submaps, scan-to-scan
  * odometry of a recorded drive, multi-session alignment, accuracy evaluation over a dataset of pairs): pair p = source points

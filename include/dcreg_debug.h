@@ -197,6 +197,31 @@ int dcreg_normals_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *
                               const int32_t *frame_ids, const dcreg_lin_params *);
 int dcreg_normals_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
 
+/* internal: the device seam of dcreg_register_frames_gicp and dcreg_icp_run_trials_gicp (engine.cpp).
+ * Kept normals for the frames dcreg_frames_load left on the device, beside their points (float4 {nx, ny, nz, curvature} in every frame's
+ * curve order): dcreg_frames_normals_keep estimates them with the given rule for all frames in ONE batched pass (dcreg_normals_clouds'
+ * build and kernel over the frames in upload order, then one gather) - frame f's are bitwise what dcreg_source_normals_get returns after
+ * dcreg_set_source(frame f) + dcreg_source_normals_keep; infos (may be NULL): one record per frame.  dcreg_frames_normals_set stores the
+ * caller's normals as given (n_points = all points of the load, in its upload order, stride_floats >= 3 floats apart; curvature NaN).
+ * dcreg_frames_normals_kept: 1 while they are kept.  Every dcreg_frames_load drops them (the loads of dcreg_register_frames* included);
+ * the context's own kept source normals are never touched.  Refusals as the dcreg_source_normals_* calls (DCREG_E_INVALID: null
+ * parameters or a parameter out of range, null normals, stride < 3, a point count that is not the load's; DCREG_E_STATE: a linearisation
+ * in flight), and DCREG_E_STATE without loaded frames.
+ * dcreg_gicp_batch_begin / _end are dcreg_normals_batch_begin / _end for dcreg_linearize_gicp: arguments, refusals, the two launch
+ * slots - they ARE the second engine's: a pending slot of either engine refuses the other - and the warm slots of
+ * dcreg_normals_reserve_slots (both engines look for the same nearest point; the word bounds the search and decides nothing).  Pose i
+ * linearises frame frame_ids[i] with that frame's kept normals or, frame_ids == NULL, the context's own source with its kept source
+ * normals; its 31 sums are bitwise what dcreg_set_source(that cloud) + dcreg_source_normals_keep / _set + dcreg_linearize_gicp(pose i)
+ * return.  "gicp_epsilon" is read at _begin.  Two more DCREG_E_STATE refusals: no kept frame normals (frame_ids given), no kept source
+ * normals (frame_ids == NULL).  dcreg_normal_params_check: the parameter refusals of dcreg_normals on their own (DCREG_OK: none). */
+int dcreg_frames_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *infos);
+int dcreg_frames_normals_set(dcreg_ctx *, const float *normals, int64_t n_points, int64_t stride_floats);
+int dcreg_frames_normals_kept(const dcreg_ctx *);
+int dcreg_gicp_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                           const int32_t *frame_ids, const dcreg_lin_params *);
+int dcreg_gicp_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
+int dcreg_normal_params_check(dcreg_ctx *, const dcreg_normal_params *);
+
 /* internal: the device seam of dcreg_register_pairs (engine.cpp).  dcreg_pairs_plan cuts the pairs into build batches of their targets
  * (batch b = pairs [batch_end[b - 1], batch_end[b]); option "pairs_max_bytes"); dcreg_pairs_sources_load is dcreg_frames_load for the
  * pairs' sources (kept apart from the context's frames); dcreg_pairs_build indexes the targets of one batch (host memory, offsets from 0,
