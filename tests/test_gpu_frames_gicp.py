@@ -12,6 +12,7 @@ import gicp_ref as gref
 import gicp_scenes as gs
 import helpers as h
 import normal_icp_scenes as sc
+import sums_check as sums
 from dcreg_amd import api
 from test_gpu_normals import OPTS_WINDOW
 from test_normal_icp_reference import cfg_pk01
@@ -124,6 +125,7 @@ def test_a_batched_launch_is_bitwise_its_single_launches_at_block_edges():
         n, T = plan[2]
         want = gref.linearize(L["tgt"], L["nb"], sc.sized_source(n), gs.sized_source_normals(n), T, RADIUS, gs.EPS)
         sc.assert_sums_close(got[2], want, "reference")
+        sums.assert_sums_entrywise(got[2], want["row"], want["n_eff"], want["n_pt"], "reference")      # every slot against its own terms
         assert all((want["flag"] == f).any() for f in (1, 2, 3))
         d = context(sc.sized_source(n), gs.sized_source_normals(n))
         try:

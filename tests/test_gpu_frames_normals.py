@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 import helpers as h
+import normal_icp_ref as ref
 import normal_icp_scenes as sc
+import sums_check as sums
 from dcreg_amd import api
 from test_gpu_normals import OPTS_WINDOW
 from test_normal_icp_reference import cfg_pk01
@@ -108,6 +110,14 @@ def test_a_batched_launch_is_bitwise_its_single_launches_at_block_edges():
             for k, ((n, T), g) in enumerate(zip(plan, got)):
                 sc.assert_sums_bitwise(g, single(n, sc.sized_source(n), T), (k, n))
         assert any(g["n_eff"] >= 10 for g in got) and got[1]["n_pt"] <= 1
+        # one pose against the numpy reference, as the single launch is compared with it (tests/test_gpu_normal_icp.py): the counts exactly,
+        # the sums to the tolerances of the exactly rounded reference sums, and every slot against its own terms
+        n, T = plan[2]
+        L = sc.lot()
+        want = ref.linearize(L["tgt"], L["nb"], sc.sized_source(n), T, RADIUS, use_weight_derivative=1)
+        assert want["n_eff"] >= 10
+        sc.assert_sums_close(got[2], want, "reference")
+        sums.assert_sums_entrywise(got[2], want["row"], want["n_eff"], want["n_pt"], "reference")
         # naming the empty frame (or one that is not there): refused, nothing queued - the next begin on the same slot is accepted
         for bad in (EMPTY, len(frames), -1):
             with pytest.raises(api.DcregError) as e:

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import helpers as h
+import p2plane_rows
 from dcreg_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -180,3 +181,21 @@ def test_fused_pass_does_not_depend_on_the_states_history(scene):
         assert list(c.launch_series(reset=True)["structure"]) == ([2, 2] if adv else [0, 0])
         c.close()
     assert _same_sums(outs[0], outs[1]) and _same_sums(outs[0], outs[2])
+
+
+@pytest.mark.parametrize("scene", ["cylinder", "lattice_dups"])
+def test_the_sums_past_one_chunk_are_within_the_derived_bound_of_their_own_rows(scene):
+    """The last pose of the walk above at 16 897 points (67 query blocks: chunk sums, a second chunk of three block rows), in a plain
+    context of the parity instantiation: every one of the 31 sums against the exact sum over the rows rebuilt from the device's own dump
+    (tests/p2plane_rows.py, tests/sums_check.py)."""
+    tgt, src, radius = _scene(scene, 16897)
+    T = np.eye(4)
+    for sz in STEPS:
+        T = h.pose6d_matrix(sz * 0.6, -sz * 0.3, sz * 0.2, sz * 0.002, -sz * 0.001, sz * 0.004) @ T
+    c = _ctx(tgt, src, radius, 0, advance=0)
+    try:
+        got, worst = p2plane_rows.assert_dump_sums_entrywise(c, src, T, api.default_lin_params(radius, 1), scene)
+        print("%s: n_eff %d of %d, the largest error is %.3g of its bound" % (scene, got["n_eff"], len(src), worst))
+        assert got["n_eff"] > 0.9 * len(src)                          # nine points in ten effective: every chunk holds such rows
+    finally:
+        c.close()

@@ -1,6 +1,7 @@
 """The third engine on the device (dcreg_source_normals_keep / _set / _get, dcreg_linearize_gicp, dcreg_icp_run_gicp) against the numpy
 reference of tests/gicp_ref.py, which applies include/dcreg.h's rule literally: the per-point dump must be BITWISE the reference's, the
-sums agree with the exactly rounded sums of the reference rows to the tolerances of tests/test_gpu_parity.py, the counts exactly.
+sums agree with the exactly rounded sums of the reference rows to the tolerances of tests/test_gpu_parity.py, the counts exactly; every sum also lies within the derived bound of the
+exact sum over the reference's rows (tests/sums_check.py).
 History, interleaved calls of the second engine and the window index change no bit; the other engines' results do not move."""
 import ctypes as C
 
@@ -10,6 +11,7 @@ import pytest
 import gicp_ref as gref
 import gicp_scenes as gs
 import normal_icp_scenes as sc
+import sums_check as sums
 from dcreg_amd import api
 from test_gpu_device_seam import D2H, DevCloud, hip, strided
 from test_gpu_normals import OPTS_WINDOW
@@ -71,6 +73,7 @@ def check(c, want, T, what, radius=RADIUS):
     got = c.linearize_gicp(T, lin_params(radius), debug=True)
     gs.assert_dump_bitwise(got, want, what)
     sc.assert_sums_close(got, want, what)
+    sums.assert_sums_entrywise(got, want["row"], want["n_eff"], want["n_pt"], what)          # every slot against its own terms
     sc.assert_sums_bitwise(c.linearize_gicp(T, lin_params(radius)), got, what)          # the plain call: the same sums
     return got
 
@@ -156,7 +159,9 @@ def test_a_walk_is_bitwise_fresh_contexts_with_and_without_the_second_engine_in_
             for x in (n1, n3):
                 sc.assert_sums_bitwise(x, want_n, step)
             sc.assert_sums_bitwise(n2, only_n.linearize_normals(sc.walk()[(step + 2) % 5], lin_params()), step)
-            sc.assert_sums_close(a, gref.linearize(L["tgt"], L["nb"], L["src"], L["mb"], T, RADIUS, gs.EPS), step)
+            ref = gref.linearize(L["tgt"], L["nb"], L["src"], L["mb"], T, RADIUS, gs.EPS)
+            sc.assert_sums_close(a, ref, step)
+            sums.assert_sums_entrywise(a, ref["row"], ref["n_eff"], ref["n_pt"], step)
     finally:
         mixed.close()
         only_n.close()

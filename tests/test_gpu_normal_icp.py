@@ -1,6 +1,7 @@
 """The second engine on the device (dcreg_target_normals_keep / _set, dcreg_linearize_normals, dcreg_icp_run_normals) against the numpy
 reference of tests/normal_icp_ref.py, which applies include/dcreg.h's rule literally: the per-point dump must be BITWISE the reference's,
-the sums agree with the exactly rounded sums of the reference rows to the tolerances of tests/test_gpu_parity.py, the counts exactly.
+the sums agree with the exactly rounded sums of the reference rows to the tolerances of tests/test_gpu_parity.py, the counts exactly; every sum also lies within the derived bound of the
+exact sum over the reference's rows (tests/sums_check.py).
 History, context and window index change no bit; the first engine's results do not move."""
 import ctypes as C
 
@@ -9,6 +10,7 @@ import pytest
 
 import normal_icp_ref as ref
 import normal_icp_scenes as sc
+import sums_check as sums
 from dcreg_amd import api
 from test_gpu_device_seam import DevCloud, strided
 from test_gpu_normals import OPTS_WINDOW
@@ -77,6 +79,7 @@ def test_the_dump_is_bitwise_the_reference_across_wave_and_block_boundaries(n):
                         what = (n, name, pose, radius, wd)
                         sc.assert_dump_bitwise(got, want, what)
                         sc.assert_sums_close(got, want, what)
+                        sums.assert_sums_entrywise(got, want["row"], want["n_eff"], want["n_pt"], what)     # every slot against its own terms
                         sc.assert_sums_bitwise(c.linearize_normals(L[pose], lin_params(radius, wd)), got, what)     # the plain call: the same sums
         if n >= 255:
             assert (want["flag"] == 0).any() and (want["flag"] == 1).any() and (want["flag"] == 2).any()
@@ -95,6 +98,7 @@ def test_ties_duplicates_and_queries_outside_the_grid(name):
             got = c.linearize_normals(S["T"], lin_params(), debug=True)
             sc.assert_dump_bitwise(got, want, name)
             sc.assert_sums_close(got, want, name)
+            sums.assert_sums_entrywise(got, want["row"], want["n_eff"], want["n_pt"], name)
             plain = c.linearize_normals(S["T"], lin_params())
             sc.assert_sums_bitwise(plain, got, name)
     finally:
@@ -111,6 +115,7 @@ def test_the_planted_gates(slope):
         assert list(got["flag"]) == sc.GATE_FLAGS and got["nn_idx"][0] == -1        # d2 == R*R stays out
         sc.assert_dump_bitwise(got, want, slope)
         sc.assert_sums_close(got, want, slope)
+        sums.assert_sums_entrywise(got, want["row"], want["n_eff"], want["n_pt"], slope)
     finally:
         c.close()
 
@@ -184,7 +189,9 @@ def test_a_walk_is_bitwise_a_fresh_context_at_every_pose(lot_ctx):
             for x in (a, b, o, d):
                 sc.assert_sums_bitwise(x, want, step)
             sc.assert_dump_bitwise(d, want, step)
-            sc.assert_dump_bitwise(d, ref.linearize(L["tgt"], L["nb"], L["src"], T, RADIUS, use_weight_derivative=1), step)
+            want_ref = ref.linearize(L["tgt"], L["nb"], L["src"], T, RADIUS, use_weight_derivative=1)
+            sc.assert_dump_bitwise(d, want_ref, step)
+            sums.assert_sums_entrywise(d, want_ref["row"], want_ref["n_eff"], want_ref["n_pt"], step)
     finally:
         other.close()
 

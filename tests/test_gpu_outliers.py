@@ -479,3 +479,27 @@ def test_refusals_at_the_c_abi(park):        # noqa: F811
             e.close()
     finally:
         c.close()
+
+
+# ---- 7. the third level of the summation tree
+def mostly_nan(n, n_finite=3000):
+    """n rows, all NaN except about n_finite seeded finite points; rows 0, 262 143, 262 144 (where present) and the last are finite"""
+    rng = np.random.default_rng(3000 + n)
+    cloud = np.full((n, 3), np.nan, np.float32)
+    at = np.unique(np.concatenate([rng.choice(n, n_finite, replace=False), [0, 262143, min(262144, n - 1), n - 1]]))
+    cloud[at] = (rng.uniform(-2, 2, (len(at), 3)) * [1.0, 1.0, 0.3]).astype(np.float32)
+    return cloud, at
+
+
+@pytest.mark.parametrize("bounded", [False, True], ids=["unbounded", "bounded"])
+@pytest.mark.parametrize("n", [262144, 262145, 262657])
+def test_statistical_past_the_second_level_of_the_summation_tree(ctx, n, bounded):
+    """The tree sums run over the INPUT rows (a dropped row adds +0.0): a block reduces 512 values, a second level 512 blocks = 262 144
+    rows, and one row more needs a third level.  At exactly two levels, one value past them, and one block past them, the means, the
+    deviation and the threshold are bitwise the reference's T(a), and so is everything decided by them."""
+    cloud, at = mostly_nan(n)
+    p = api.outlier_params(k=8, std_mul=1.0, search_radius=0.3 if bounded else 0.0)
+    ref = ref_of(cloud, p)
+    assert ref["n_in"] == n and ref["n_finite"] == len(at) and 2900 < len(at) <= 3004
+    assert 0 < ref["n_out"] < ref["n_finite"] and (ref["n_sparse"] > 0) == bounded
+    assert_bitwise(ctx.outlier_filter(cloud, p), ref, (n, bounded))

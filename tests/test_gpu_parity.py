@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers as h
+import p2plane_rows
 from dcreg_amd import api
 from oracle import pyoracle as po
 
@@ -904,3 +905,42 @@ def test_montecarlo_cli_runs_and_is_seeded():
     assert a["Ours"]["total_runs"] == 48 and 0.0 <= a["ME-SR"]["success_rate"] <= 1.0
     for k in ("success_rate", "mean_trans_error", "mean_rot_error", "mean_iterations"):
         assert a["Ours"][k] == b["Ours"][k]
+
+
+def _entrywise_scene(name):
+    """-> (target, source, radius, pose, weight derivative)"""
+    if name in ("fixture_release", "fixture_paper"):
+        pts = h.cylinder_cloud()
+        return pts, pts, 1.0, h.pose6d_matrix(**(h.RELEASE_INIT if name == "fixture_release" else h.PAPER_INIT)), int(name == "fixture_paper")
+    if name == "sparse_3k":
+        tgt, radius = SCENES[name]()
+        rng = np.random.default_rng(11)
+        src = tgt[rng.permutation(len(tgt))[: max(len(tgt) // 2, 1000)]].copy()
+        src += rng.normal(0, 0.01, src.shape).astype(np.float32)
+        return tgt, src, radius, h.pose6d_matrix(0.05, -0.08, 0.03, h.deg2rad(0.2), h.deg2rad(-0.1), h.deg2rad(0.5)), 1
+    # the far_corridor scene of tests/test_host_emul.py: 3e4 m from the origin the translation block of H is 1e-10 of max |H|
+    tgt = (h.scene_corridor(8000, seed=6, length=20.0).astype(np.float64) + np.array([3.0e4, -2.0e4, 500.0])).astype(np.float32)
+    src = (tgt[::2] + np.random.default_rng(5).normal(0, 0.004, tgt[::2].shape)).astype(np.float32)
+    return tgt, src, 0.8, np.eye(4), 1
+
+
+@pytest.mark.parametrize("name", ["fixture_release", "fixture_paper", "sparse_3k", "far_corridor"])
+def test_every_sum_is_within_the_derived_bound_of_its_own_rows(name):
+    """The 31 sums entry by entry (tests/sums_check.py), not relative to max |H|: the rows are rebuilt in numpy (tests/p2plane_rows.py) from
+    the device's own dumped normal, r and s, in the parity instantiation ("fast_plane_fit" = 0)."""
+    tgt, src, radius, T, wd = _entrywise_scene(name)
+    c = api.Context(0)
+    try:
+        c.set_option("fast_plane_fit", 0)
+        c.set_target(tgt, radius)
+        c.set_source(src)
+        got, worst = p2plane_rows.assert_dump_sums_entrywise(c, src, T, api.default_lin_params(radius, wd), name)
+        print("%s: n_eff %d, the largest error is %.3g of its bound" % (name, got["n_eff"], worst))
+        assert got["n_eff"] > 10                                      # (sparse_3k has 15 effective points: most queries lack five neighbours)
+        if name == "far_corridor":
+            H = np.abs(got["H_upper"])
+            assert min(H[15], H[18], H[20]) < 1e-8 * H.max()          # the scene's point: a diagonal entry far below max |H|
+        if name == "fixture_release":
+            assert (got["n_eff"], got["n_pt"]) == (871, 1557)
+    finally:
+        c.close()
