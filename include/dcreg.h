@@ -964,7 +964,7 @@ int dcreg_linearize_normals(dcreg_ctx *, const double R[9], const double t[3], c
  *                                       none).  What a caller persists with a map.  DCREG_E_STATE: no kept normals, a linearisation in
  *                                       flight.  DCREG_E_INVALID: null context or buffer, capacity_points below the map's size.  Waits
  *                                       for the stream.
- *   dcreg_target_normals_follow_info    what the last update that changed the map did: n_target = the map's size after it, n_refit =
+ *   dcreg_target_normals_follow_info    what the last update that changed the map did (all zero after dcreg_set_target* in any of its forms: a new map has had no update yet): n_target = the map's size after it, n_refit =
  *                                       points whose normal it computed (added points included), n_carried = points whose stored normal
  *                                       was moved over unchanged, followed = 0 not followed (the normals were dropped, or no update
  *                                       yet), 1 incremental, 2 followed by a full recompute.  n_refit + n_carried == n_target when

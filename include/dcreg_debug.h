@@ -203,7 +203,7 @@ int dcreg_normals_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
  * build and kernel over the frames in upload order, then one gather) - frame f's are bitwise what dcreg_source_normals_get returns after
  * dcreg_set_source(frame f) + dcreg_source_normals_keep; infos (may be NULL): one record per frame.  dcreg_frames_normals_set stores the
  * caller's normals as given (n_points = all points of the load, in its upload order, stride_floats >= 3 floats apart; curvature NaN).
- * dcreg_frames_normals_kept: 1 while they are kept.  Every dcreg_frames_load drops them (the loads of dcreg_register_frames* included);
+ * dcreg_frames_normals_kept: 1 while they are kept.  Every dcreg_frames_load drops them (the loads of dcreg_register_frames* included, and a load refused for its frames with DCREG_E_INVALID too: the frames that were on the device stay, their normals do not; a load refused with DCREG_E_STATE for a linearisation in flight drops nothing);
  * the context's own kept source normals are never touched.  Refusals as the dcreg_source_normals_* calls (DCREG_E_INVALID: null
  * parameters or a parameter out of range, null normals, stride < 3, a point count that is not the load's; DCREG_E_STATE: a linearisation
  * in flight), and DCREG_E_STATE without loaded frames.
