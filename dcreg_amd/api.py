@@ -204,6 +204,45 @@ def _frames_arg(frames, what):
     return xyz, off, len(off) - 1
 
 
+def _pose_arg(T, what=None):
+    """a 4 x 4 pose -> (R [9], t [3]); what: the wrapper that refuses anything but a finite 4 x 4 itself (None: reshaped, the C side checks)"""
+    T = _f64(T)
+    if what is None:
+        T = T.reshape(4, 4)
+    elif T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("%s: a finite 4 x 4 pose is expected" % what)
+    return np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+
+
+def _poses_arg(Ts):
+    """[n, 4, 4] poses -> (R [n, 9], t [n, 3], n)"""
+    Ts = _f64(Ts).reshape(-1, 4, 4)
+    n = Ts.shape[0]
+    return np.ascontiguousarray(Ts[:, :3, :3]).reshape(n, 9), np.ascontiguousarray(Ts[:, :3, 3]).reshape(n, 3), n
+
+
+def _method(method, what=None):
+    """a name of METHODS or a (detection, handling) pair -> the two C enums; what: the wrapper that refuses an unknown name itself"""
+    if what is not None and isinstance(method, str) and method not in METHODS:
+        raise ValueError("%s: unknown method %r" % (what, method))
+    det, hand = METHODS[method] if isinstance(method, str) else method
+    return DETECTION[det], HANDLING[hand]
+
+
+# the per-point dumps of linearize_normals / linearize_gicp: (key, dtype, shape per point) of every array of the C struct
+_DUMP_FILL = {"nn_idx": -1, "nn_d2": np.inf}
+_NLIN_DUMP = [("nn_idx", np.int32, ()), ("nn_d2", np.float32, ()), ("flag", np.uint8, ()), ("normal", np.float64, (3,)), ("r", np.float64, ()),
+              ("s", np.float64, ()), ("row", np.float64, (8,))]
+_GLIN_DUMP = [("nn_idx", np.int32, ()), ("nn_d2", np.float32, ()), ("flag", np.uint8, ()), ("normal_map", np.float64, (3,)),
+              ("normal_src", np.float64, (3,)), ("w", np.float64, (3, 3)), ("r", np.float64, (3,)), ("row", np.float64, (3, 8))]
+
+
+def _dump_arg(n, entries, struct):
+    """-> ({key: array of n points}, the ctypes struct that points at them)"""
+    keep = {k: np.full((n,) + shape, _DUMP_FILL.get(k, 0), dtype) for k, dtype, shape in entries}
+    return keep, struct(**{k: keep[k].ctypes.data_as(t) for k, t in struct._fields_})
+
+
 class MapUpdate(C.Structure):
     _fields_ = [("n_offered", C.c_int64), ("n_added", C.c_int64), ("n_removed", C.c_int64), ("n_target", C.c_int64), ("rebuilt", C.c_int),
                 ("reserved_", C.c_int)]
@@ -1823,20 +1862,40 @@ class Context:
         self._check(self._L.dcreg_target_normals_keep(self._h, C.byref(p), C.byref(info)), "dcreg_target_normals_keep")
         return _normal_info_dict(info)
 
+    def _set_kept_normals(self, which, normals, dev_ptr, n, stride):
+        """set_target_normals / set_source_normals (which = "target" / "source")"""
+        what, symbol = "set_%s_normals" % which, "dcreg_%s_normals_set" % which
+        if (normals is None) == (not dev_ptr):
+            raise ValueError("%s: either normals or dev_ptr is expected" % what)
+        if normals is not None:
+            a = _points(normals, what)
+            self._check(getattr(self._L, symbol)(self._h, a.ctypes.data, a.shape[0], a.shape[1]), symbol)
+            return
+        if n is None or stride is None:
+            raise ValueError("%s: n and stride are expected with dev_ptr" % what)
+        _check_device_cloud(n, stride, what)
+        self._check(getattr(self._L, symbol + "_device")(self._h, C.c_void_p(dev_ptr), int(n), int(stride)), symbol + "_device")
+
+    def _kept_normals(self, which, dev_ptr, capacity):
+        """kept_target_normals / kept_source_normals (which = "target" / "source")"""
+        what, symbol = "kept_%s_normals" % which, "dcreg_%s_normals_get" % which
+        if dev_ptr:
+            if capacity is None or isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= int(capacity) <= OUTLIER_MAX_POINTS:
+                raise ValueError("%s: with dev_ptr a capacity of 0 .. 2^31 - 1 points is expected, got %r" % (what, capacity))
+            self._check(getattr(self._L, symbol + "_device")(self._h, C.c_void_p(dev_ptr), int(capacity)), symbol + "_device")
+            return None
+        if capacity is not None:
+            raise ValueError("%s: a capacity is expected with dev_ptr only" % what)
+        n = max(int(getattr(self.index_info(), "n_" + which)), 0)
+        out = np.full((max(n, 1), 4), np.nan, np.float32)
+        self._check(getattr(self._L, symbol)(self._h, out.ctypes.data, n), symbol)
+        return np.ascontiguousarray(out[:n, :3]), np.ascontiguousarray(out[:n, 3])
+
     def set_target_normals(self, normals=None, dev_ptr=0, n=None, stride=None):
         """dcreg_target_normals_set[_device]: the caller's normals, one per map point in index order (target_points()), kept as given.
         normals: [n, c >= 3] float32 on the host, or dev_ptr / n / stride for device memory.  A normal with a non-finite component
         means that the point has none."""
-        if (normals is None) == (not dev_ptr):
-            raise ValueError("set_target_normals: either normals or dev_ptr is expected")
-        if normals is not None:
-            a = _points(normals, "set_target_normals")
-            self._check(self._L.dcreg_target_normals_set(self._h, a.ctypes.data, a.shape[0], a.shape[1]), "dcreg_target_normals_set")
-            return
-        if n is None or stride is None:
-            raise ValueError("set_target_normals: n and stride are expected with dev_ptr")
-        _check_device_cloud(n, stride, "set_target_normals")
-        self._check(self._L.dcreg_target_normals_set_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride)), "dcreg_target_normals_set_device")
+        self._set_kept_normals("target", normals, dev_ptr, n, stride)
 
     def target_normals_kept(self):
         return int(self._L.dcreg_target_normals_kept(self._h))
@@ -1849,17 +1908,7 @@ class Context:
         a map, and what set_option("normals_follow", 1) keeps up to date through inserts and removals.
         -> (normals [n, 3] float32, curvature [n] float32); with dev_ptr: 4 floats per point (nx ny nz curvature) go to that device buffer
         of `capacity` points instead, -> None"""
-        if dev_ptr:
-            if capacity is None or isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= int(capacity) <= OUTLIER_MAX_POINTS:
-                raise ValueError("kept_target_normals: with dev_ptr a capacity of 0 .. 2^31 - 1 points is expected, got %r" % (capacity,))
-            self._check(self._L.dcreg_target_normals_get_device(self._h, C.c_void_p(dev_ptr), int(capacity)), "dcreg_target_normals_get_device")
-            return None
-        if capacity is not None:
-            raise ValueError("kept_target_normals: a capacity is expected with dev_ptr only")
-        n = max(int(self.index_info().n_target), 0)
-        out = np.full((max(n, 1), 4), np.nan, np.float32)
-        self._check(self._L.dcreg_target_normals_get(self._h, out.ctypes.data, n), "dcreg_target_normals_get")
-        return np.ascontiguousarray(out[:n, :3]), np.ascontiguousarray(out[:n, 3])
+        return self._kept_normals("target", dev_ptr, capacity)
 
     def normals_follow_info(self):
         """dcreg_target_normals_follow_info: what the last update that changed the map did to the kept normals -> dict n_target / n_refit /
@@ -1879,48 +1928,43 @@ class Context:
             raise ValueError("%s: search_radius must be finite and > 0, got %r" % (what, params.search_radius))
         return params
 
-    def linearize_normals(self, T, params=None, debug=False):
-        """dcreg_linearize_normals at the pose T (4 x 4): the 1-NN point-to-plane rows against the kept normals (include/dcreg.h has the
-        rule) -> dict as linearize(); debug=True adds the per-point dump in source order: nn_idx, nn_d2, flag, normal [n, 3], r, s,
-        row [n, 8]."""
-        params = self._nlin_params(params, "linearize_normals")
-        T = _f64(T)
-        if T.shape != (4, 4) or not np.isfinite(T).all():
-            raise ValueError("linearize_normals: a finite 4 x 4 pose is expected")
-        R, t = np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
+    def _linearize_kept(self, symbol, what, T, params, debug, entries, struct):
+        """linearize_normals / linearize_gicp: the plain call, or the debug form with every array of its dump"""
+        params = self._nlin_params(params, what)
+        R, t = _pose_arg(T, what)
         out = LinOut()
         if not debug:
-            self._check(self._L.dcreg_linearize_normals(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), "dcreg_linearize_normals")
+            self._check(getattr(self._L, symbol)(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), symbol)
             return self._out_dict(out)
-        n = self.index_info().n_source
-        keep = {"nn_idx": np.full(n, -1, np.int32), "nn_d2": np.full(n, np.inf, np.float32), "flag": np.zeros(n, np.uint8),
-                "normal": np.zeros((n, 3)), "r": np.zeros(n), "s": np.zeros(n), "row": np.zeros((n, 8))}
-        dbg = NlinDebug(keep["nn_idx"].ctypes.data_as(C.POINTER(C.c_int32)), keep["nn_d2"].ctypes.data_as(C.POINTER(C.c_float)),
-                        keep["flag"].ctypes.data_as(C.POINTER(C.c_uint8)), _dp(keep["normal"]), _dp(keep["r"]), _dp(keep["s"]), _dp(keep["row"]))
-        self._check(self._L.dcreg_linearize_normals_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)),
-                    "dcreg_linearize_normals_debug")
+        keep, dbg = _dump_arg(self.index_info().n_source, entries, struct)
+        self._check(getattr(self._L, symbol + "_debug")(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)), symbol + "_debug")
         d = self._out_dict(out)
         d.update(keep)
         return d
 
-    def icp_run_normals(self, T0, method, cfg, log_capacity=None):
-        """dcreg_icp_run_normals: icp_run's loop against the kept normals -> (result, logs)"""
-        T0 = _f64(T0)
-        if T0.shape != (4, 4) or not np.isfinite(T0).all():
-            raise ValueError("icp_run_normals: a finite 4 x 4 pose is expected")
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("icp_run_normals: unknown method %r" % (method,))
-        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
-        det, hand = METHODS[method] if isinstance(method, str) else method
+    def _run_logged(self, symbol, T0, method, cfg, log_capacity, what=None, extra=()):
+        """the single runs: `symbol` from the pose T0 -> (result, the log records the run wrote); what: the wrapper checks pose and method
+        itself (_pose_arg, _method); extra: the call's arguments between cfg and the log"""
+        R0, t0 = _pose_arg(T0, what)
+        det, hand = _method(method, what)
         cap = cfg.max_iterations if log_capacity is None else log_capacity
         logs = (IterLog * max(cap, 1))()
         res = IcpResult()
-        self._check(self._L.dcreg_icp_run_normals(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
-                                                  C.byref(res)), "dcreg_icp_run_normals")
+        self._check(getattr(self._L, symbol)(self._h, _dp(R0), _dp(t0), det, hand, C.byref(cfg), *extra, logs, cap, C.byref(res)), symbol)
         n = min(res.iterations, cap)
         if res.status == 1:
             n = min(res.iterations - 1, cap)
         return res, [logs[i] for i in range(max(n, 0))]
+
+    def linearize_normals(self, T, params=None, debug=False):
+        """dcreg_linearize_normals at the pose T (4 x 4): the 1-NN point-to-plane rows against the kept normals (include/dcreg.h has the
+        rule) -> dict as linearize(); debug=True adds the per-point dump in source order: nn_idx, nn_d2, flag, normal [n, 3], r, s,
+        row [n, 8]."""
+        return self._linearize_kept("dcreg_linearize_normals", "linearize_normals", T, params, debug, _NLIN_DUMP, NlinDebug)
+
+    def icp_run_normals(self, T0, method, cfg, log_capacity=None):
+        """dcreg_icp_run_normals: icp_run's loop against the kept normals -> (result, logs)"""
+        return self._run_logged("dcreg_icp_run_normals", T0, method, cfg, log_capacity, "icp_run_normals")
 
     # ---- kept source normals and the third engine (include/dcreg.h: dcreg_source_normals_keep .. dcreg_icp_run_gicp)
     def keep_source_normals(self, params=None):
@@ -1936,16 +1980,7 @@ class Context:
         """dcreg_source_normals_set[_device]: the caller's normals, one per source point in the order the source was given, kept as given.
         normals: [n, c >= 3] float32 on the host, or dev_ptr / n / stride for device memory.  A normal with a non-finite component
         means that the point has none."""
-        if (normals is None) == (not dev_ptr):
-            raise ValueError("set_source_normals: either normals or dev_ptr is expected")
-        if normals is not None:
-            a = _points(normals, "set_source_normals")
-            self._check(self._L.dcreg_source_normals_set(self._h, a.ctypes.data, a.shape[0], a.shape[1]), "dcreg_source_normals_set")
-            return
-        if n is None or stride is None:
-            raise ValueError("set_source_normals: n and stride are expected with dev_ptr")
-        _check_device_cloud(n, stride, "set_source_normals")
-        self._check(self._L.dcreg_source_normals_set_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride)), "dcreg_source_normals_set_device")
+        self._set_kept_normals("source", normals, dev_ptr, n, stride)
 
     def source_normals_kept(self):
         return int(self._L.dcreg_source_normals_kept(self._h))
@@ -1957,64 +1992,19 @@ class Context:
         """dcreg_source_normals_get[_device]: the kept source normals in the order the source was given
         -> (normals [n, 3] float32, curvature [n] float32); with dev_ptr: 4 floats per point (nx ny nz curvature) go to that device buffer
         of `capacity` points instead, -> None"""
-        if dev_ptr:
-            if capacity is None or isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= int(capacity) <= OUTLIER_MAX_POINTS:
-                raise ValueError("kept_source_normals: with dev_ptr a capacity of 0 .. 2^31 - 1 points is expected, got %r" % (capacity,))
-            self._check(self._L.dcreg_source_normals_get_device(self._h, C.c_void_p(dev_ptr), int(capacity)), "dcreg_source_normals_get_device")
-            return None
-        if capacity is not None:
-            raise ValueError("kept_source_normals: a capacity is expected with dev_ptr only")
-        n = max(int(self.index_info().n_source), 0)
-        out = np.full((max(n, 1), 4), np.nan, np.float32)
-        self._check(self._L.dcreg_source_normals_get(self._h, out.ctypes.data, n), "dcreg_source_normals_get")
-        return np.ascontiguousarray(out[:n, :3]), np.ascontiguousarray(out[:n, 3])
+        return self._kept_normals("source", dev_ptr, capacity)
 
     def linearize_gicp(self, T, params=None, debug=False):
         """dcreg_linearize_gicp at the pose T (4 x 4): three whitened point-to-plane rows per correspondence from the kept map normals and
         the kept source normals (include/dcreg.h has the rule; of params only search_radius is read) -> dict as linearize(); debug=True
         adds the per-point dump in source order: nn_idx, nn_d2, flag, normal_map [n, 3], normal_src [n, 3], w [n, 3, 3], r [n, 3],
         row [n, 3, 8]."""
-        params = self._nlin_params(params, "linearize_gicp")
-        T = _f64(T)
-        if T.shape != (4, 4) or not np.isfinite(T).all():
-            raise ValueError("linearize_gicp: a finite 4 x 4 pose is expected")
-        R, t = np.ascontiguousarray(T[:3, :3]).reshape(9), np.ascontiguousarray(T[:3, 3])
-        out = LinOut()
-        if not debug:
-            self._check(self._L.dcreg_linearize_gicp(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), "dcreg_linearize_gicp")
-            return self._out_dict(out)
-        n = self.index_info().n_source
-        keep = {"nn_idx": np.full(n, -1, np.int32), "nn_d2": np.full(n, np.inf, np.float32), "flag": np.zeros(n, np.uint8),
-                "normal_map": np.zeros((n, 3)), "normal_src": np.zeros((n, 3)), "w": np.zeros((n, 3, 3)), "r": np.zeros((n, 3)),
-                "row": np.zeros((n, 3, 8))}
-        dbg = GlinDebug(keep["nn_idx"].ctypes.data_as(C.POINTER(C.c_int32)), keep["nn_d2"].ctypes.data_as(C.POINTER(C.c_float)),
-                        keep["flag"].ctypes.data_as(C.POINTER(C.c_uint8)), _dp(keep["normal_map"]), _dp(keep["normal_src"]), _dp(keep["w"]),
-                        _dp(keep["r"]), _dp(keep["row"]))
-        self._check(self._L.dcreg_linearize_gicp_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)),
-                    "dcreg_linearize_gicp_debug")
-        d = self._out_dict(out)
-        d.update(keep)
-        return d
+        return self._linearize_kept("dcreg_linearize_gicp", "linearize_gicp", T, params, debug, _GLIN_DUMP, GlinDebug)
 
     def icp_run_gicp(self, T0, method, cfg, log_capacity=None):
         """dcreg_icp_run_gicp: icp_run_normals's loop around linearize_gicp -> (result, logs); a log's rmse is the RMS Mahalanobis distance
         per effective point"""
-        T0 = _f64(T0)
-        if T0.shape != (4, 4) or not np.isfinite(T0).all():
-            raise ValueError("icp_run_gicp: a finite 4 x 4 pose is expected")
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("icp_run_gicp: unknown method %r" % (method,))
-        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        cap = cfg.max_iterations if log_capacity is None else log_capacity
-        logs = (IterLog * max(cap, 1))()
-        res = IcpResult()
-        self._check(self._L.dcreg_icp_run_gicp(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
-                                               C.byref(res)), "dcreg_icp_run_gicp")
-        n = min(res.iterations, cap)
-        if res.status == 1:
-            n = min(res.iterations - 1, cap)
-        return res, [logs[i] for i in range(max(n, 0))]
+        return self._run_logged("dcreg_icp_run_gicp", T0, method, cfg, log_capacity, "icp_run_gicp")
 
     # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
     def keyframes_reset(self):
@@ -2405,18 +2395,7 @@ class Context:
         return ms.value, n.value
 
     def icp_run(self, T0, method, cfg, log_capacity=None):
-        T0 = _f64(T0).reshape(4, 4)
-        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        cap = cfg.max_iterations if log_capacity is None else log_capacity
-        logs = (IterLog * max(cap, 1))()
-        res = IcpResult()
-        self._check(self._L.dcreg_icp_run(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), logs, cap,
-                                          C.byref(res)), "dcreg_icp_run")
-        n = min(res.iterations, cap)
-        if res.status == 1:
-            n = min(res.iterations - 1, cap)
-        return res, [logs[i] for i in range(max(n, 0))]
+        return self._run_logged("dcreg_icp_run", T0, method, cfg, log_capacity)
 
     def icp_run_sharded(self, T0, method, cfg, n_source_total, reduce_rows, log_capacity=None):
         """dcreg_icp_run_sharded: reduce_rows(numpy float64[32] view) must overwrite the row IN PLACE with the sum over
@@ -2459,18 +2438,7 @@ class Context:
 
     def icp_run_sharded_rccl(self, T0, method, cfg, n_source_total, log_capacity=None):
         """dcreg_icp_run_sharded_rccl: point-sharded run, the per-iteration exchange is an RCCL all_gather inside the engine."""
-        T0 = _f64(T0).reshape(4, 4)
-        R0, t0 = np.ascontiguousarray(T0[:3, :3]).reshape(9), np.ascontiguousarray(T0[:3, 3])
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        cap = cfg.max_iterations if log_capacity is None else log_capacity
-        logs = (IterLog * max(cap, 1))()
-        res = IcpResult()
-        self._check(self._L.dcreg_icp_run_sharded_rccl(self._h, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg),
-                                                       int(n_source_total), logs, cap, C.byref(res)), "dcreg_icp_run_sharded_rccl")
-        n = min(res.iterations, cap)
-        if res.status == 1:
-            n = min(res.iterations - 1, cap)
-        return res, [logs[i] for i in range(max(n, 0))]
+        return self._run_logged("dcreg_icp_run_sharded_rccl", T0, method, cfg, log_capacity, extra=(int(n_source_total),))
 
     def icp_run_euler(self, pose6d, method, cfg, log_capacity=None):
         """Second engine (Pose6D state, LOAM Jacobian); pose6d = (roll, pitch, yaw, x, y, z).
@@ -2515,79 +2483,46 @@ class Context:
         self._check(self._L.dcreg_comm_allgather(self._h, _dp(row), _dp(out), len(row)), "dcreg_comm_allgather")
         return out
 
-    def icp_run_trials(self, T0s, method, cfg):
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        n = T0s.shape[0]
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
+    def _run_trials(self, symbol, T0s, method, cfg, what=None):
+        """icp_run_trials and the other engines' forms: one record per pose; what: the wrapper refuses an unknown method name itself"""
+        R0, t0, n = _poses_arg(T0s)
+        det, hand = _method(method, what)
         res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_icp_run_trials(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
-                    "dcreg_icp_run_trials")
+        self._check(getattr(self._L, symbol)(self._h, n, _dp(R0), _dp(t0), det, hand, C.byref(cfg), res), symbol)
         return [res[i] for i in range(n)]
+
+    def _register_frames(self, symbol, frames, T0s, method, cfg, slots, what, check_method=True, extra_args=()):
+        """register_frames and the other engines' forms: one record per frame; extra_args: the call's arguments between the frames and the
+        poses"""
+        xyz, off, n = _frames_arg(frames, what)
+        R0, t0, n_poses = _poses_arg(T0s)
+        if n_poses != n:
+            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, n_poses))
+        det, hand = _method(method, what if check_method else None)
+        res = (TrialResult * max(n, 1))()
+        self._check(getattr(self._L, symbol)(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
+                                             *extra_args, _dp(R0), _dp(t0), det, hand, C.byref(cfg), int(slots), res), symbol)
+        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
+        return [res[i] for i in range(n)]
+
+    def icp_run_trials(self, T0s, method, cfg):
+        return self._run_trials("dcreg_icp_run_trials", T0s, method, cfg)
 
     def register_frames(self, frames, T0s, method, cfg, slots=0):
         """dcreg_register_frames: many frames against this context's map in one call.  frames = a list of [n_i, c] float32 arrays, or
         (xyz [N, c], offsets [n_frames + 1]) with frame f = xyz[offsets[f]:offsets[f + 1]] (c >= 3 columns, x y z first: an xyzi array is
         passed as it is, the rows c floats apart); T0s = one initial 4x4 pose per frame.  Returns one record per frame, as icp_run_trials does;
         each is bitwise set_source(frame) + icp_run(T0) on this context."""
-        if isinstance(frames, tuple):
-            xyz, off = frames
-            xyz = _points(xyz, "register_frames")
-            off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
-        else:
-            parts = [_points(f, "register_frames") for f in frames]
-            if len({f.shape[1] for f in parts}) > 1:
-                raise ValueError("register_frames: every frame needs the same number of columns, got %s" % sorted({f.shape[1] for f in parts}))
-            off = np.zeros(len(parts) + 1, np.int64)
-            off[1:] = np.cumsum([len(f) for f in parts])
-            xyz = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
-        n = len(off) - 1
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        if n < 0 or T0s.shape[0] != n:
-            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_register_frames(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)), xyz.shape[1],
-                                                  _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
-                    "dcreg_register_frames")
-        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
-        return [res[i] for i in range(n)]
+        return self._register_frames("dcreg_register_frames", frames, T0s, method, cfg, slots, "register_frames", check_method=False)
 
     def register_frames_normals(self, frames, T0s, method, cfg, slots=0):
         """dcreg_register_frames_normals: register_frames with the second engine (the map's kept normals: keep_target_normals or
         set_target_normals first).  Same arguments and records; each record is bitwise set_source(frame) + icp_run_normals(T0)."""
-        xyz, off, n = _frames_arg(frames, "register_frames_normals")
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        if T0s.shape[0] != n:
-            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("register_frames_normals: unknown method %r" % (method,))
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_register_frames_normals(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                          xyz.shape[1], _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), int(slots), res),
-                    "dcreg_register_frames_normals")
-        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
-        return [res[i] for i in range(n)]
+        return self._register_frames("dcreg_register_frames_normals", frames, T0s, method, cfg, slots, "register_frames_normals")
 
     def icp_run_trials_normals(self, T0s, method, cfg):
         """dcreg_icp_run_trials_normals: icp_run_trials with the second engine; each record is bitwise icp_run_normals from its pose"""
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("icp_run_trials_normals: unknown method %r" % (method,))
-        n = T0s.shape[0]
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_icp_run_trials_normals(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
-                    "dcreg_icp_run_trials_normals")
-        return [res[i] for i in range(n)]
+        return self._run_trials("dcreg_icp_run_trials_normals", T0s, method, cfg, "icp_run_trials_normals")
 
     # ---- the device seam of the two calls above (include/dcreg_debug.h), for the tests
     def frames_load(self, frames):
@@ -2603,27 +2538,31 @@ class Context:
     def normals_reset_slot(self, slot_id):
         self._check(self._L.dcreg_normals_reset_slot(self._h, int(slot_id)), "dcreg_normals_reset_slot")
 
-    def normals_batch_begin(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
-        """dcreg_normals_batch_begin: one launch over the poses Ts ([n, 4, 4]); pose i linearises frame frame_ids[i] of the loaded frames
-        (None: the own source) with warm slot state_ids[i] (-1, or None: cold).  -> the number of poses, for normals_batch_end"""
-        params = self._nlin_params(params, "normals_batch_begin")
-        Ts = _f64(Ts).reshape(-1, 4, 4)
-        n = Ts.shape[0]
-        Rs = np.ascontiguousarray(Ts[:, :3, :3]).reshape(n, 9)
-        ts = np.ascontiguousarray(Ts[:, :3, 3]).reshape(n, 3)
+    def _batch_begin(self, symbol, what, Ts, state_ids, frame_ids, params, slot):
+        """normals_batch_begin / gicp_batch_begin -> the number of poses"""
+        params = self._nlin_params(params, what)
+        Rs, ts, n = _poses_arg(Ts)
         i32p = C.POINTER(C.c_int32)
         ids = None if state_ids is None else np.ascontiguousarray(state_ids, dtype=np.int32).reshape(n)
         fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
-        self._check(self._L.dcreg_normals_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
-                                                      None if fids is None else fids.ctypes.data_as(i32p), C.byref(params)),
-                    "dcreg_normals_batch_begin")
+        self._check(getattr(self._L, symbol)(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
+                                             None if fids is None else fids.ctypes.data_as(i32p), C.byref(params)), symbol)
         return n
+
+    def _batch_end(self, symbol, n_poses, slot):
+        """normals_batch_end / gicp_batch_end -> one dict per pose"""
+        outs = (LinOut * max(int(n_poses), 1))()
+        self._check(getattr(self._L, symbol)(self._h, int(slot), outs), symbol)
+        return [self._out_dict(outs[i]) for i in range(int(n_poses))]
+
+    def normals_batch_begin(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
+        """dcreg_normals_batch_begin: one launch over the poses Ts ([n, 4, 4]); pose i linearises frame frame_ids[i] of the loaded frames
+        (None: the own source) with warm slot state_ids[i] (-1, or None: cold).  -> the number of poses, for normals_batch_end"""
+        return self._batch_begin("dcreg_normals_batch_begin", "normals_batch_begin", Ts, state_ids, frame_ids, params, slot)
 
     def normals_batch_end(self, n_poses, slot=0):
         """dcreg_normals_batch_end -> one dict per pose, as linearize_normals returns"""
-        outs = (LinOut * max(int(n_poses), 1))()
-        self._check(self._L.dcreg_normals_batch_end(self._h, int(slot), outs), "dcreg_normals_batch_end")
-        return [self._out_dict(outs[i]) for i in range(int(n_poses))]
+        return self._batch_end("dcreg_normals_batch_end", n_poses, slot)
 
     def normals_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
         return self.normals_batch_end(self.normals_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)
@@ -2636,36 +2575,12 @@ class Context:
         records; each record is bitwise set_source(frame) + keep_source_normals(frame_normals) + icp_run_gicp(T0)."""
         p = frame_normals if frame_normals is not None else normal_params()
         _check_normal_params(p, "register_frames_gicp")
-        xyz, off, n = _frames_arg(frames, "register_frames_gicp")
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        if T0s.shape[0] != n:
-            raise ValueError("one initial pose per frame: %d frames, %d poses" % (n, T0s.shape[0]))
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("register_frames_gicp: unknown method %r" % (method,))
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_register_frames_gicp(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       xyz.shape[1], C.byref(p), _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg),
-                                                       int(slots), res), "dcreg_register_frames_gicp")
-        self._n_frames = n            # (the call loaded its frames: frames_normals_keep sizes its infos by it)
-        return [res[i] for i in range(n)]
+        return self._register_frames("dcreg_register_frames_gicp", frames, T0s, method, cfg, slots, "register_frames_gicp", extra_args=(C.byref(p),))
 
     def icp_run_trials_gicp(self, T0s, method, cfg):
         """dcreg_icp_run_trials_gicp: icp_run_trials with the third engine (kept map normals and kept source normals first); each record is
         bitwise icp_run_gicp from its pose"""
-        T0s = _f64(T0s).reshape(-1, 4, 4)
-        if isinstance(method, str) and method not in METHODS:
-            raise ValueError("icp_run_trials_gicp: unknown method %r" % (method,))
-        n = T0s.shape[0]
-        R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
-        t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
-        det, hand = METHODS[method] if isinstance(method, str) else method
-        res = (TrialResult * max(n, 1))()
-        self._check(self._L.dcreg_icp_run_trials_gicp(self._h, n, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand], C.byref(cfg), res),
-                    "dcreg_icp_run_trials_gicp")
-        return [res[i] for i in range(n)]
+        return self._run_trials("dcreg_icp_run_trials_gicp", T0s, method, cfg, "icp_run_trials_gicp")
 
     def frames_normals_keep(self, params=None):
         """dcreg_frames_normals_keep: the loaded frames' own normals, all frames in one batched pass, kept beside their points
@@ -2695,24 +2610,11 @@ class Context:
     def gicp_batch_begin(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
         """dcreg_gicp_batch_begin: normals_batch_begin for linearize_gicp - pose i linearises frame frame_ids[i] with its kept frame
         normals (None: the own source with its kept source normals).  -> the number of poses, for gicp_batch_end"""
-        params = self._nlin_params(params, "gicp_batch_begin")
-        Ts = _f64(Ts).reshape(-1, 4, 4)
-        n = Ts.shape[0]
-        Rs = np.ascontiguousarray(Ts[:, :3, :3]).reshape(n, 9)
-        ts = np.ascontiguousarray(Ts[:, :3, 3]).reshape(n, 3)
-        i32p = C.POINTER(C.c_int32)
-        ids = None if state_ids is None else np.ascontiguousarray(state_ids, dtype=np.int32).reshape(n)
-        fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
-        self._check(self._L.dcreg_gicp_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
-                                                   None if fids is None else fids.ctypes.data_as(i32p), C.byref(params)),
-                    "dcreg_gicp_batch_begin")
-        return n
+        return self._batch_begin("dcreg_gicp_batch_begin", "gicp_batch_begin", Ts, state_ids, frame_ids, params, slot)
 
     def gicp_batch_end(self, n_poses, slot=0):
         """dcreg_gicp_batch_end -> one dict per pose, as linearize_gicp returns"""
-        outs = (LinOut * max(int(n_poses), 1))()
-        self._check(self._L.dcreg_gicp_batch_end(self._h, int(slot), outs), "dcreg_gicp_batch_end")
-        return [self._out_dict(outs[i]) for i in range(int(n_poses))]
+        return self._batch_end("dcreg_gicp_batch_end", n_poses, slot)
 
     def gicp_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
         return self.gicp_batch_end(self.gicp_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)

@@ -2146,16 +2146,12 @@ static int linearize_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     int64_t searched = coded ? 0 : -1, refitted = coded ? 0 : -1;
     for (int i = 0; i < P.n_poses; ++i) {
         const double *o = P.n_poses == 1 ? total : S.h_rows.data() + (size_t)i * kSlots;      // (batches: one row per pose)
-        std::memcpy(outs[i].H_upper, o, 21 * sizeof(double));
-        std::memcpy(outs[i].g, o + 21, 6 * sizeof(double));
-        outs[i].sum_r2 = o[27]; outs[i].sum_b2 = o[28];
-        int64_t c29 = (int64_t)std::llround(o[29]), c30 = (int64_t)std::llround(o[30]);
+        lin_out_of_row(o, outs[i]);
         if (coded) {
             const int64_t S26 = (int64_t)1 << 26;
-            searched += c29 / S26; refitted += c30 / S26;
-            c29 %= S26; c30 %= S26;
+            searched += outs[i].n_eff / S26; refitted += outs[i].n_pt / S26;
+            outs[i].n_eff %= S26; outs[i].n_pt %= S26;
         }
-        outs[i].n_eff = c29; outs[i].n_pt = c30;
     }
     c->last_points = (int64_t)P.n_poses * c->n_src;
     // (a point whose new certificate has no slack at all - distance ties - is served by an advance pass and searched again by k_lin: it is

@@ -6,7 +6,10 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -464,14 +467,13 @@ struct dcreg_ctx {
     // the third engine (gicp.hip: dcreg_linearize_gicp; normals.hip: dcreg_source_normals_keep / _set / _get / _drop).  src_normals: float4
     // {nx, ny, nz, curvature} per SOURCE point in the context's curve order - lane i of k_glin reads it beside d_src[i]; dropped by every
     // call that replaces the source's points (context.hip source_commit), left alone by the batched calls.  The warm words are nicp.warm:
-    // both 1-NN engines look for the same nearest point.  tmp: the original-order form of a get; partials / d_out / dbg as nicp's.
+    // both 1-NN engines look for the same nearest point, and so are nicp's block rows, result row and dump block (normal_icp.hip one_nn_run: the
+    // two engines' launches never overlap).  tmp: the original-order form of a get.
     // The batched form (k_glin_batch: dcreg_gicp_batch_begin / _end) has no buffers of its own: it runs in nicp's launch slots and warm
     // slots (normal_icp.hip one_nn_batch_begin) and reads a frame's normals from FrameSet::normals
     struct GicpBufs {
         DevBuf<float4> src_normals; bool src_kept = false;
         DevBuf<float4> tmp;
-        DevBuf<double> partials, d_out;
-        DevBuf<unsigned char> dbg;
     };
     GicpBufs gicp;
     double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
@@ -632,6 +634,20 @@ struct OneNnBound { double radius_sq; float bound_f; int max_ring; };
 int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what);
 OneNnBound one_nn_bound(const GridDev &g, double search_radius);
 int one_nn_warm_reserve(dcreg_ctx *c);
+// one_nn_run: the single-pose call of either engine, plain or debug - one_nn_check, the engine's own refusal (`extra`, with frames == false),
+// roi_ensure, the buffers, then `launch` queues the engine's kernel for the filled record, the requested dump arrays come back, k_finalize,
+// the wait, the warm bookkeeping and the result.  fields: the debug form's arrays in the order they are cut from the dump block (8-byte ones
+// first): the caller's array (null: not asked for), its bytes per point, and the kernel argument's pointer that receives the device array
+struct OneNnLaunch {
+    PoseArg P; OneNnBound bound;                // the pose, the search bound on the active index
+    bool dump;                                  // the debug form: the kernel's dump instantiation, no warm words
+    const uint32_t *warm_in; uint32_t *warm_out;
+    double *partials; uint32_t nb;
+};
+struct OneNnDumpField { void *host; size_t bytes; void *dev; };
+int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
+               int (*extra)(dcreg_ctx *, bool frames), const std::function<void(const OneNnLaunch &)> &launch, bool dump, const OneNnDumpField *fields,
+               int n_fields);
 // ... and what their batched forms share (dcreg_normals_batch_begin / _end, dcreg_gicp_batch_begin / _end): the two launch slots and the warm
 // slots of NormalIcpBufs.  one_nn_batch_begin makes every refusal of include/dcreg_debug.h before anything is queued (`extra`: the engine's
 // own state refusals, after "no kept normals"; frames = frame_ids were given), uploads the poses and slices, has `launch` queue the engine's
@@ -652,6 +668,13 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
 int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs);
 const uint32_t *one_nn_warm_take(dcreg_ctx *c);
 void one_nn_warm_done(dcreg_ctx *c);
+// a result row of kSlots doubles (block_slot_sum's slots, summed) as the C-ABI's record
+inline void lin_out_of_row(const double *row, dcreg_lin_out &o) {
+    std::memcpy(o.H_upper, row, 21 * sizeof(double));
+    std::memcpy(o.g, row + 21, 6 * sizeof(double));
+    o.sum_r2 = row[27]; o.sum_b2 = row[28];
+    o.n_eff = (int64_t)std::llround(row[29]); o.n_pt = (int64_t)std::llround(row[30]);
+}
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
 // deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before

@@ -8,6 +8,9 @@
 //   k_glin_batch   the same for many poses in ONE launch (dcreg_gicp_batch_begin: the engine of dcreg_register_frames_gicp): block (x, pose)
 //                  runs glin_point on block x of the pose's own source slice and its kept normals, and leaves its row at partials[pose][x]
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_nlin
+// The host side is the second engine's (normal_icp.hip): one_nn_run for the single pose and one_nn_batch_begin / _end for many, with this
+// engine's refusal (gicp_refuse), its launch arguments (glin_args), its kernels and the fields of its dump; the block rows, the result
+// row and the dump block are nicp's.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  The search reads and writes the warm words of
 // k_nlin (context.hpp NormalIcpBufs::warm): both engines look for the same nearest point, and the word decides how fast, never which.
 #include <cmath>
@@ -82,18 +85,7 @@ __device__ __forceinline__ void glin_block_rows(const PoseArg &P, uint8_t flag, 
     const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
     if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
     __syncthreads();
-    if (threadIdx.x < kSlots) {
-        double t = 0.0;
-        if (threadIdx.x < 29) {
-            const int e = gram_entry_of_slot(threadIdx.x);
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
-        } else if (threadIdx.x < 31) {
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
-        }
-        out[threadIdx.x] = t;
-    }
+    if (threadIdx.x < kSlots) out[threadIdx.x] = block_slot_sum(&gm[0][0], 64, cnt);
 }
 
 // warm_in / warm_out / partials: as k_nlin's.  src_normals: float4 per source point in the order of src.  Slot 29 counts the effective
@@ -181,79 +173,36 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin_batch(const 
                     [](int, const double (&)[8]) {});
 }
 
-int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_glin_debug *dbg) {
-    if (int rc = one_nn_check(c, R, t, p, out, "GICP")) return rc;
-    if (!c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize_normals (a swap drops the warm positions)
-    if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
-    dcreg_ctx::NormalIcpBufs &W = c->nicp;                // (the warm words are the second engine's)
-    dcreg_ctx::GicpBufs &B = c->gicp;
-    const int64_t n = c->n_src;
-    const uint32_t nb = (uint32_t)((n + kLinBlock - 1) / kLinBlock);
-    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
-    const GridDev &g = c->map.grid;
-    const OneNnBound sb = one_nn_bound(g, p->search_radius);
+// the launch's arguments for a search within the bound b ("gicp_epsilon" is read at every call)
+GlinArgs glin_args(const dcreg_ctx *c, const OneNnBound &b) {
     GlinArgs a;
-    a.radius_sq = sb.radius_sq; a.bound_f = sb.bound_f; a.max_ring = sb.max_ring;
+    a.radius_sq = b.radius_sq; a.bound_f = b.bound_f; a.max_ring = b.max_ring;
     a.c = 1.0 - c->opt_gicp_epsilon;
-    PoseArg P;
-    std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
-    P.state = kNoIdx; P.fresh = 1;
-    if (dbg) {
-        // one block of device memory for the dump, cut into its arrays (8-byte ones first)
-        const size_t N = (size_t)n;
-        const size_t off_nm = 0, off_ns = off_nm + 24 * N, off_w = off_ns + 24 * N, off_r = off_w + 72 * N, off_row = off_r + 24 * N,
-                     off_idx = off_row + 192 * N, off_d2 = off_idx + 4 * N, off_flag = off_d2 + 4 * N, total = off_flag + N;
-        if (B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
-        unsigned char *b = B.dbg.data();
-        GlinDump d;
-        d.normal_map = dbg->normal_map ? (double *)(b + off_nm) : nullptr; d.normal_src = dbg->normal_src ? (double *)(b + off_ns) : nullptr;
-        d.w = dbg->w ? (double *)(b + off_w) : nullptr; d.r = dbg->r ? (double *)(b + off_r) : nullptr;
-        d.row = dbg->row ? (double *)(b + off_row) : nullptr;
-        d.nn_idx = dbg->nn_idx ? (int32_t *)(b + off_idx) : nullptr; d.nn_d2 = dbg->nn_d2 ? (float *)(b + off_d2) : nullptr;
-        d.flag = dbg->flag ? b + off_flag : nullptr;
-        hipLaunchKernelGGL(k_glin<true>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, W.normals.data(),
-                           B.src_normals.data(), P, a, (const uint32_t *)nullptr, (uint32_t *)nullptr, B.partials.data(), d);
-        HIP_TRY(c, hipGetLastError());
-        if (d.normal_map) HIP_TRY(c, hipMemcpyAsync(dbg->normal_map, d.normal_map, 24 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.normal_src) HIP_TRY(c, hipMemcpyAsync(dbg->normal_src, d.normal_src, 24 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.w) HIP_TRY(c, hipMemcpyAsync(dbg->w, d.w, 72 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.r) HIP_TRY(c, hipMemcpyAsync(dbg->r, d.r, 24 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.row) HIP_TRY(c, hipMemcpyAsync(dbg->row, d.row, 192 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.nn_idx) HIP_TRY(c, hipMemcpyAsync(dbg->nn_idx, d.nn_idx, 4 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.nn_d2) HIP_TRY(c, hipMemcpyAsync(dbg->nn_d2, d.nn_d2, 4 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.flag) HIP_TRY(c, hipMemcpyAsync(dbg->flag, d.flag, N, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        const uint32_t *warm_in = one_nn_warm_take(c);
-        hipLaunchKernelGGL(k_glin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, W.normals.data(),
-                           B.src_normals.data(), P, a, warm_in, W.warm.data(), B.partials.data(), GlinDump{});
-        HIP_TRY(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
-    HIP_TRY(c, hipGetLastError());
-    double h[kSlots];
-    HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (!dbg) one_nn_warm_done(c);
-    std::memcpy(out->H_upper, h, 21 * sizeof(double));
-    std::memcpy(out->g, h + 21, 6 * sizeof(double));
-    out->sum_r2 = h[27]; out->sum_b2 = h[28];
-    out->n_eff = (int64_t)std::llround(h[29]); out->n_pt = (int64_t)std::llround(h[30]);
-    return DCREG_OK;
+    return a;
 }
 
-// ---- the batched form: the second engine's seam (normal_icp.hip one_nn_batch_begin) with this engine's state refusals and kernel
-int gicp_batch_refuse(dcreg_ctx *c, bool frames) {
+// this engine's state refusals, after "no kept normals": the single-pose call (frames == false) and the batched form (the second engine's
+// seam, normal_icp.hip one_nn_batch_begin)
+int gicp_refuse(dcreg_ctx *c, bool frames) {
     if (frames && !c->frames.normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
     if (!frames && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
     return DCREG_OK;
 }
+
+int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_glin_debug *dbg) {
+    GlinDump d{};
+    const dcreg_glin_debug none{}, &h = dbg ? *dbg : none;
+    const OneNnDumpField fields[] = {{h.normal_map, 24, &d.normal_map}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
+                                     {h.row, 192, &d.row}, {h.nn_idx, 4, &d.nn_idx}, {h.nn_d2, 4, &d.nn_d2}, {h.flag, 1, &d.flag}};
+    return one_nn_run(c, R, t, p, out, "GICP", gicp_refuse, [&](const OneNnLaunch &L) {
+        hipLaunchKernelGGL(L.dump ? k_glin<true> : k_glin<false>, dim3(L.nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)c->n_src,
+                           c->map.grid, c->nicp.normals.data(), c->gicp.src_normals.data(), L.P, glin_args(c, L.bound), L.warm_in, L.warm_out,
+                           L.partials, d);
+    }, dbg != nullptr, fields, 8);
+}
+
 void glin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
-    GlinArgs a;
-    a.radius_sq = L.bound.radius_sq; a.bound_f = L.bound.bound_f; a.max_ring = L.bound.max_ring;
-    a.c = 1.0 - c->opt_gicp_epsilon;
+    const GlinArgs a = glin_args(c, L.bound);
     hipLaunchKernelGGL(k_glin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals,
                        L.slices ? c->frames.normals.data() : c->gicp.src_normals.data(), L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx);
 }
@@ -269,7 +218,7 @@ int dcreg_linearize_gicp(dcreg_ctx *c, const double R[9], const double t[3], con
 }
 int dcreg_gicp_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                            const int32_t *frame_ids, const dcreg_lin_params *p) {
-    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, gicp_batch_refuse, glin_batch_launch, "the k_glin_batch launch");
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, gicp_refuse, glin_batch_launch, "the k_glin_batch launch");
 }
 int dcreg_gicp_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 int dcreg_linearize_gicp_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,

@@ -435,7 +435,21 @@ __device__ __forceinline__ void wave_rows_to_lds(const double (&row)[8], uint8_t
     // (extra0 / extra1: the wave's searched / refitted lanes x LinArgs::count_scale, riding above the counts)
     if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff) + extra0; cnt[wave][1] = (double)__builtin_popcountll(inr) + extra1; }
 }
-// ... and, after a block barrier: the block partial (fixed order, no float atomics) and, for single-pose launches, the arrival at
+// ... then, after a block barrier, slot threadIdx.x (< kSlots) of the block row: the waves' Gram entries (slots 0..28, gram_entry_of_slot;
+// wave w's matrix at gm0 + w * gm_stride) or counts (29, 30), added in wave order; zero above.  Every 1-NN kernel's tail calls it too
+__device__ __forceinline__ double block_slot_sum(const double *gm0, int gm_stride, const double (*cnt)[2]) {
+    double t = 0.0;
+    if (threadIdx.x < 29) {
+        const int e = gram_entry_of_slot(threadIdx.x);
+#pragma unroll
+        for (int w = 0; w < kLinBlock / 64; ++w) t += gm0[w * gm_stride + e];
+    } else if (threadIdx.x < 31) {
+#pragma unroll
+        for (int w = 0; w < kLinBlock / 64; ++w) t += cnt[w][threadIdx.x - 29];
+    }
+    return t;
+}
+// ... and the block partial (fixed order, no float atomics) and, for single-pose launches, the arrival at
 // the chunk's ticket: the last of its blocks sums the chunk and publishes the row to the host.  All 256 threads call.
 // gm0 / gm_stride: the waves' Gram matrices (wave w at gm0 + w * gm_stride); red: kLinBlock / 32 x kSlots doubles of scratch for the chunk
 // sum (may overlap the Gram matrices: they are consumed before)
@@ -443,15 +457,7 @@ template <bool FUSED>
 __device__ __forceinline__ void block_publish(const double *gm0, int gm_stride, double (*red)[kSlots], double (*cnt)[2], int *s_role, double *my_rows, uint32_t vb,
                                               uint32_t n_blocks_x, const FinArgs &fin, uint32_t pose_id) {
     if (threadIdx.x < kSlots) {
-        double t = 0.0;
-        if (threadIdx.x < 29) {
-            const int e = gram_entry_of_slot(threadIdx.x);
-#pragma unroll
-            for (int w = 0; w < kLinBlock / 64; ++w) t += gm0[w * gm_stride + e];
-        } else if (threadIdx.x < 31) {
-#pragma unroll
-            for (int w = 0; w < kLinBlock / 64; ++w) t += cnt[w][threadIdx.x - 29];
-        }
+        const double t = block_slot_sum(gm0, gm_stride, cnt);
         if (FUSED && fin.direct) {
             publish_row(fin.out + (size_t)vb * kSlots, t, fin.seq);
         } else if (FUSED) {

@@ -8,6 +8,10 @@
 //                  (x, pose) runs nlin_point on block x of the pose's own source slice - a frame of the loaded frames, or the context's
 //                  source - with the pose read from a device array, and leaves its row at partials[pose][x]
 //   k_finalize     (kernels.hpp) the block rows in chunk order, the additions of the first engine's batched launches
+// Both kernels end in nlin_block_rows (the wave's rows to LDS, block_slot_sum of kernels.hpp, the block row).  On the host, one_nn_run is
+// the single-pose call of this engine AND of gicp.hip's (refusals, buffers, the dump block cut from a table of fields, launch, k_finalize,
+// warm bookkeeping): an engine brings its extra refusal, its kernel launch and its dump fields.  one_nn_batch_begin / _end are the same
+// seam for the batched form.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  A point's row depends on the clouds, the
 // normals and the pose only; the warm position decides how fast the neighbour is found, never which.
 #include <cmath>
@@ -25,6 +29,16 @@ namespace {
 struct NlinDump {
     int32_t *nn_idx; float *nn_d2; uint8_t *flag; double *normal, *r, *s, *row;
 };
+
+// What a block does with its points' rows once nlin_point has run (k_nlin and k_nlin_batch; the shape of gicp.hip's glin_block_rows): the
+// wave's rows through the matrix cores (the wave's RunList is free now: it stages the rows; the lanes past the cloud's end carry a zero
+// row and flag 0), the wave's Gram matrix and counts in LDS, added in wave order, and the block row at `out`
+__device__ __forceinline__ void nlin_block_rows(const double (&row)[8], uint8_t flag, RunList &rl, double (*gm)[64], double (*cnt)[2],
+                                                double *__restrict__ out) {
+    wave_rows_to_lds(row, flag, rl.stage, gm[threadIdx.x >> 6], cnt);
+    __syncthreads();
+    if (threadIdx.x < kSlots) out[threadIdx.x] = block_slot_sum(&gm[0][0], 64, cnt);
+}
 
 // warm_in: the positions of the last launch (null: search cold), warm_out: where this launch leaves its own (null: nowhere; the same
 // array as warm_in in a plain call: a lane reads its word before it writes it, and no other lane's).  Block b
@@ -62,21 +76,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin(const float4
             }
         }
     }
-    // (the wave's RunList is free now: it stages the rows; the lanes past the cloud's end carry a zero row and flag 0)
-    wave_rows_to_lds(row, flag, runs[wave].stage, gm[wave], cnt);
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-        double t = 0.0;
-        if (threadIdx.x < 29) {
-            const int e = gram_entry_of_slot(threadIdx.x);
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
-        } else if (threadIdx.x < 31) {
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
-        }
-        partials[(size_t)blockIdx.x * kSlots + threadIdx.x] = t;
-    }
+    nlin_block_rows(row, flag, runs[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots);
 }
 
 // Many poses in one launch.  Block (x, pose): pose = poses[blockIdx.y]; its cloud is slices[pose] = {first point, points} of src (as k_lin's
@@ -112,20 +112,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin_batch(const 
         flag = nlin_point(g, runs[wave], normals, P, a, s4, (w && P.fresh == 0u) ? *w : kNoIdx, row, o);
         if (w) *w = o.pos;
     }
-    wave_rows_to_lds(row, flag, runs[wave].stage, gm[wave], cnt);
-    __syncthreads();
-    if (threadIdx.x < kSlots) {
-        double t = 0.0;
-        if (threadIdx.x < 29) {
-            const int e = gram_entry_of_slot(threadIdx.x);
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += gm[w][e];
-        } else if (threadIdx.x < 31) {
-#pragma unroll
-            for (int w = 0; w < kLinBlock / kWave; ++w) t += cnt[w][threadIdx.x - 29];
-        }
-        partials[((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots + threadIdx.x] = t;
-    }
+    nlin_block_rows(row, flag, runs[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots);
 }
 
 bool finite_n(const double *v, int n) {
@@ -133,9 +120,8 @@ bool finite_n(const double *v, int n) {
     return true;
 }
 
-// the launch's arguments for a search on the grid g
-NlinArgs nlin_args(const GridDev &g, const dcreg_lin_params *p) {
-    const OneNnBound b = one_nn_bound(g, p->search_radius);
+// the launch's arguments for a search within the bound b
+NlinArgs nlin_args(const OneNnBound &b, const dcreg_lin_params *p) {
     NlinArgs a;
     a.radius_sq = b.radius_sq; a.bound_f = b.bound_f; a.max_ring = b.max_ring;
     a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
@@ -143,64 +129,20 @@ NlinArgs nlin_args(const GridDev &g, const dcreg_lin_params *p) {
 }
 
 int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_nlin_debug *dbg) {
-    if (int rc = one_nn_check(c, R, t, p, out, "normal")) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize (a swap drops the warm positions)
-    if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
-    dcreg_ctx::NormalIcpBufs &B = c->nicp;
-    const int64_t n = c->n_src;
-    const uint32_t nb = (uint32_t)((n + kLinBlock - 1) / kLinBlock);
-    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
-    const NlinArgs a = nlin_args(c->map.grid, p);
-    PoseArg P;
-    std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
-    P.state = kNoIdx; P.fresh = 1;
-    const GridDev &g = c->map.grid;
-    if (dbg) {
-        // one block of device memory for the dump, cut into its arrays (8-byte ones first)
-        const size_t N = (size_t)n;
-        const size_t off_normal = 0, off_r = off_normal + 24 * N, off_s = off_r + 8 * N, off_row = off_s + 8 * N, off_idx = off_row + 64 * N,
-                     off_d2 = off_idx + 4 * N, off_flag = off_d2 + 4 * N, total = off_flag + N;
-        if (B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
-        unsigned char *b = B.dbg.data();
-        NlinDump d;
-        d.normal = dbg->normal ? (double *)(b + off_normal) : nullptr; d.r = dbg->r ? (double *)(b + off_r) : nullptr;
-        d.s = dbg->s ? (double *)(b + off_s) : nullptr; d.row = dbg->row ? (double *)(b + off_row) : nullptr;
-        d.nn_idx = dbg->nn_idx ? (int32_t *)(b + off_idx) : nullptr; d.nn_d2 = dbg->nn_d2 ? (float *)(b + off_d2) : nullptr;
-        d.flag = dbg->flag ? b + off_flag : nullptr;
-        hipLaunchKernelGGL(k_nlin<true>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, B.normals.data(), P, a,
-                           (const uint32_t *)nullptr, (uint32_t *)nullptr, B.partials.data(), d);
-        HIP_TRY(c, hipGetLastError());
-        if (d.normal) HIP_TRY(c, hipMemcpyAsync(dbg->normal, d.normal, 24 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.r) HIP_TRY(c, hipMemcpyAsync(dbg->r, d.r, 8 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.s) HIP_TRY(c, hipMemcpyAsync(dbg->s, d.s, 8 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.row) HIP_TRY(c, hipMemcpyAsync(dbg->row, d.row, 64 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.nn_idx) HIP_TRY(c, hipMemcpyAsync(dbg->nn_idx, d.nn_idx, 4 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.nn_d2) HIP_TRY(c, hipMemcpyAsync(dbg->nn_d2, d.nn_d2, 4 * N, hipMemcpyDeviceToHost, c->stream));
-        if (d.flag) HIP_TRY(c, hipMemcpyAsync(dbg->flag, d.flag, N, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        const uint32_t *warm_in = one_nn_warm_take(c);
-        hipLaunchKernelGGL(k_nlin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)n, g, B.normals.data(), P, a,
-                           warm_in, B.warm.data(), B.partials.data(), NlinDump{});
-        HIP_TRY(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
-    HIP_TRY(c, hipGetLastError());
-    double h[kSlots];
-    HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (!dbg) one_nn_warm_done(c);
-    std::memcpy(out->H_upper, h, 21 * sizeof(double));
-    std::memcpy(out->g, h + 21, 6 * sizeof(double));
-    out->sum_r2 = h[27]; out->sum_b2 = h[28];
-    out->n_eff = (int64_t)std::llround(h[29]); out->n_pt = (int64_t)std::llround(h[30]);
-    return DCREG_OK;
+    NlinDump d{};
+    const dcreg_nlin_debug none{}, &h = dbg ? *dbg : none;
+    const OneNnDumpField fields[] = {{h.normal, 24, &d.normal}, {h.r, 8, &d.r}, {h.s, 8, &d.s}, {h.row, 64, &d.row},
+                                     {h.nn_idx, 4, &d.nn_idx}, {h.nn_d2, 4, &d.nn_d2}, {h.flag, 1, &d.flag}};
+    return one_nn_run(c, R, t, p, out, "normal", nullptr, [&](const OneNnLaunch &L) {
+        const GridDev &g = c->map.grid;
+        hipLaunchKernelGGL(L.dump ? k_nlin<true> : k_nlin<false>, dim3(L.nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)c->n_src, g,
+                           c->nicp.normals.data(), L.P, nlin_args(L.bound, p), L.warm_in, L.warm_out, L.partials, d);
+    }, dbg != nullptr, fields, 7);
 }
 
 // the second engine's kernel for a batched launch (one_nn_batch_begin below)
 void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
-    const NlinArgs a = nlin_args(L.g, L.p);
+    const NlinArgs a = nlin_args(L.bound, L.p);
     hipLaunchKernelGGL(k_nlin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals, L.poses, L.slices, a,
                        L.warm, L.warm_stride, L.partials, L.nbx);
 }
@@ -329,13 +271,7 @@ int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
         c->fail("device fault while waiting for a batched normal linearisation: %s", hipGetErrorString(e));
         return DCREG_E_DEVICE;
     }
-    for (int i = 0; i < S.n_poses; ++i) {
-        const double *h = S.h_out.data() + (size_t)i * kSlots;
-        std::memcpy(outs[i].H_upper, h, 21 * sizeof(double));
-        std::memcpy(outs[i].g, h + 21, 6 * sizeof(double));
-        outs[i].sum_r2 = h[27]; outs[i].sum_b2 = h[28];
-        outs[i].n_eff = (int64_t)std::llround(h[29]); outs[i].n_pt = (int64_t)std::llround(h[30]);
-    }
+    for (int i = 0; i < S.n_poses; ++i) lin_out_of_row(S.h_out.data() + (size_t)i * kSlots, outs[i]);
     return DCREG_OK;
 }
 
@@ -350,6 +286,50 @@ int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin
     if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
     if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+// The single-pose runner of both 1-NN engines (context.hpp).  The engine's kernel searches the index roi_ensure made the active one; a debug
+// launch searches cold and keeps no positions, a plain one starts from the warm words and leaves its own there.
+int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
+               int (*extra)(dcreg_ctx *, bool frames), const std::function<void(const OneNnLaunch &)> &launch, bool dump, const OneNnDumpField *fields, int n_fields) {
+    if (int rc = one_nn_check(c, R, t, p, out, what)) return rc;
+    if (extra) if (int rc = extra(c, false)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize (a swap drops the warm positions)
+    if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    const size_t N = (size_t)c->n_src;
+    OneNnLaunch L;
+    L.nb = (uint32_t)((N + kLinBlock - 1) / kLinBlock);
+    if (B.partials.ensure(c, (size_t)L.nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
+    L.bound = one_nn_bound(c->map.grid, p->search_radius);
+    std::memcpy(L.P.R, R, sizeof(L.P.R)); std::memcpy(L.P.t, t, sizeof(L.P.t));
+    L.P.state = kNoIdx; L.P.fresh = 1;
+    L.dump = dump;
+    if (!dump) n_fields = 0;
+    // one block of device memory for the dump, cut into its arrays in the table's order (8-byte ones first)
+    size_t total = 0;
+    for (int k = 0; k < n_fields; ++k) total += fields[k].bytes * N;
+    if (dump && B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
+    unsigned char *b = B.dbg.data();
+    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
+        if (fields[k].host) std::memcpy(fields[k].dev, &b, sizeof(b));
+    L.warm_in = dump ? nullptr : one_nn_warm_take(c);
+    L.warm_out = dump ? nullptr : B.warm.data();
+    L.partials = B.partials.data();
+    launch(L);
+    HIP_TRY(c, hipGetLastError());
+    b = B.dbg.data();
+    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
+        if (fields[k].host) HIP_TRY(c, hipMemcpyAsync(fields[k].host, b, fields[k].bytes * N, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), L.nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    double h[kSlots];
+    HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (!dump) one_nn_warm_done(c);
+    lin_out_of_row(h, *out);
     return DCREG_OK;
 }
 OneNnBound one_nn_bound(const GridDev &g, double search_radius) {

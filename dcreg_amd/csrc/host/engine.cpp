@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <thread>
 #include <vector>
@@ -131,6 +132,21 @@ inline void covariance_of(bool converged, const double Hlast[36], double cov[36]
     std::memcpy(cov, C.v, sizeof(C.v));
 }
 
+// What a single run starts from and leaves (dcreg_icp_run_sharded, icp_run_waited).  run_open: the pose, H = I for the covariance of a run
+// that takes no step, the clouds' sizes.  run_close: the final pose and its covariance; t_total given: the run's time (null: the status-3
+// result of a run without clouds, which has none)
+inline void run_open(dcreg_ctx *ctx, const double R0[9], const double t0[3], double R[9], double t[3], double Hlast[36], dcreg_index_info &info) {
+    std::memcpy(R, R0, 9 * sizeof(double)); std::memcpy(t, t0, 3 * sizeof(double));
+    for (int i = 0; i < 36; ++i) Hlast[i] = (i % 7 == 0) ? 1.0 : 0.0;
+    dcreg_index_info_get(ctx, &info);
+}
+inline int run_close(dcreg_icp_result *res, const double R[9], const double t[3], const double Hlast[36], const Clock::time_point *t_total, int rc) {
+    std::memcpy(res->R, R, sizeof(res->R)); std::memcpy(res->t, t, sizeof(res->t));
+    covariance_of(res->converged != 0, Hlast, res->icp_cov);
+    if (t_total) res->time_ms = ms_since(*t_total);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,11 +160,9 @@ int dcreg_icp_run_sharded(dcreg_ctx *ctx, const double R0[9], const double t0[3]
     if (reduce && n_source_total <= 0) return DCREG_E_INVALID;
     const auto t_total = Clock::now();
     double R[9], t[3], Hlast[36];
-    std::memcpy(R, R0, sizeof(R)); std::memcpy(t, t0, sizeof(t));
-    for (int i = 0; i < 36; ++i) Hlast[i] = (i % 7 == 0) ? 1.0 : 0.0;
-    const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
+    run_open(ctx, R0, t0, R, t, Hlast, info);
+    const dcreg_lin_params prm = lin_params_of(*cfg);
     const double n_src_all = reduce ? (double)n_source_total : (double)info.n_source;
     // Sharded runs: a rank whose slice is empty, or whose target is missing, still takes part in EVERY exchange (it
     // contributes a zero row, or a poisoned one) - leaving the loop alone would block the other ranks in the collective.
@@ -156,9 +170,7 @@ int dcreg_icp_run_sharded(dcreg_ctx *ctx, const double R0[9], const double t0[3]
     const bool local_bad = info.n_target <= 0;
     if (!reduce && (local_empty || local_bad)) {   // :1635-1646
         res->status = 3;
-        std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
-        covariance_of(false, Hlast, res->icp_cov);
-        return DCREG_OK;
+        return run_close(res, R, t, Hlast, nullptr, DCREG_OK);
     }
     int rc_all = DCREG_OK;
     // One pair, no exchange: the launches are pipelined - while linearisation `it` runs, linearisation `it + 1` is queued behind
@@ -221,10 +233,7 @@ int dcreg_icp_run_sharded(dcreg_ctx *ctx, const double R0[9], const double t0[3]
         if (st == 1) { res->converged = 1; break; }
     }
     if (queued) dcreg_linearize_gate_abort(ctx);     // left the loop early: the launch queued ahead is called off
-    std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
-    covariance_of(res->converged != 0, Hlast, res->icp_cov);
-    res->time_ms = ms_since(t_total);
-    return rc_all;
+    return run_close(res, R, t, Hlast, &t_total, rc_all);
 }
 
 static int rccl_reduce(double row[32], void *user) { return dcreg_comm_allgather_sum((dcreg_ctx *)user, row) == DCREG_OK ? 0 : 1; }
@@ -250,16 +259,12 @@ static int icp_run_waited(lin_fn linearize, dcreg_ctx *ctx, const double R0[9], 
     std::memset(res, 0, sizeof(*res));
     const auto t_total = Clock::now();
     double R[9], t[3], Hlast[36];
-    std::memcpy(R, R0, sizeof(R)); std::memcpy(t, t0, sizeof(t));
-    for (int i = 0; i < 36; ++i) Hlast[i] = (i % 7 == 0) ? 1.0 : 0.0;
-    const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
+    run_open(ctx, R0, t0, R, t, Hlast, info);
+    const dcreg_lin_params prm = lin_params_of(*cfg);
     if (info.n_source <= 0 || info.n_target <= 0) {   // :1635-1646
         res->status = 3;
-        std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
-        covariance_of(false, Hlast, res->icp_cov);
-        return DCREG_OK;
+        return run_close(res, R, t, Hlast, nullptr, DCREG_OK);
     }
     for (int it = 0; it < cfg->max_iterations; ++it) {
         const auto t_iter = Clock::now();
@@ -278,10 +283,7 @@ static int icp_run_waited(lin_fn linearize, dcreg_ctx *ctx, const double R0[9], 
         res->iterations = it + 1;
         if (st == 1) { res->converged = 1; break; }
     }
-    std::memcpy(res->R, R, sizeof(R)); std::memcpy(res->t, t, sizeof(t));
-    covariance_of(res->converged != 0, Hlast, res->icp_cov);
-    res->time_ms = ms_since(t_total);
-    return DCREG_OK;
+    return run_close(res, R, t, Hlast, &t_total, DCREG_OK);
 }
 int dcreg_icp_run_normals(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
                           const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
@@ -327,7 +329,6 @@ enum class Engine { planes, normals, gicp };
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
                            int64_t first_pair = -1, Engine engine = Engine::planes) {
-    const bool normals = engine != Engine::planes;          // a 1-NN engine: the warm slots and launch slots of normal_icp.hip
     const auto t_total = Clock::now();
     const dcreg_lin_params prm = lin_params_of(*cfg);
     dcreg_index_info info;
@@ -335,6 +336,44 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     const bool frames = frame_points != nullptr;
     const bool pairs = frames && first_pair >= 0;
     auto points_of = [&](int64_t k) { return frames ? frame_points[k] : info.n_source; };
+    struct Group { std::vector<int> live; std::vector<int32_t> ids, fids, gids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
+    // The engine's calls, chosen once: reserve n neighbour states (the 1-NN engines: warm slots), mark state si empty, queue group gi's launch
+    // over its nl live trials, wait for it; label: the suffix of the call's name in the timing line.  The first engine's three forms (own
+    // source, frames, pairs) differ in the same four calls.
+    struct EngineCalls {
+        std::function<int(int)> reserve;
+        std::function<void(int)> reset;
+        std::function<int(int, int, Group &)> begin;
+        int (*end)(dcreg_ctx *, int, dcreg_lin_out *);
+        const char *label;
+    };
+    typedef int (*one_nn_begin_fn)(dcreg_ctx *, int, int, const double *, const double *, const int32_t *, const int32_t *, const dcreg_lin_params *);
+    auto one_nn = [&](one_nn_begin_fn batch_begin, const char *label) {        // the launch and warm slots of normal_icp.hip, shared by both
+        return EngineCalls{[&](int n) { return dcreg_normals_reserve_slots(ctx, n, frames ? 1 : 0); },
+                           [&](int si) { dcreg_normals_reset_slot(ctx, si); },
+                           [&, batch_begin](int gi, int nl, Group &G) {
+                               return batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm);
+                           },
+                           dcreg_normals_batch_end, label};
+    };
+    const EngineCalls E =
+        engine == Engine::gicp ? one_nn(dcreg_gicp_batch_begin, "_gicp")
+        : engine == Engine::normals ? one_nn(dcreg_normals_batch_begin, "_normals")
+        : pairs ? EngineCalls{[&](int n) { return dcreg_pairs_reserve_states(ctx, n); }, [&](int si) { dcreg_pairs_reset_state(ctx, si); },
+                              [&](int gi, int nl, Group &G) {
+                                  return dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm);
+                              },
+                              dcreg_linearize_batch_end, ""}
+        : frames ? EngineCalls{[&](int n) { return dcreg_frames_reserve_states(ctx, n); }, [&](int si) { dcreg_frames_reset_state(ctx, si); },
+                               [&](int gi, int nl, Group &G) {
+                                   return dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm);
+                               },
+                               dcreg_linearize_batch_end, ""}
+                 : EngineCalls{[&](int n) { return dcreg_reserve_warm_states(ctx, n); }, [&](int si) { dcreg_reset_warm_state(ctx, si); },
+                               [&](int gi, int nl, Group &G) {
+                                   return dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
+                               },
+                               dcreg_linearize_batch_end, ""};
     for (int64_t i = 0; i < n_trials; ++i) std::memset(&results[i], 0, sizeof(results[i]));
     if ((!frames && info.n_source <= 0) || (!pairs && info.n_target <= 0)) {
         for (int64_t i = 0; i < n_trials; ++i) results[i].status = 3;
@@ -352,12 +391,9 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     n_slots = std::min(n_slots, 2 * 65535);
     const int n_groups = n_slots >= 64 ? 2 : 1;
     // one neighbour state per slot; without the memory for them the trials still run, every launch searching from scratch
-    bool have_states = (normals ? dcreg_normals_reserve_slots(ctx, n_slots, frames ? 1 : 0)
-                        : pairs ? dcreg_pairs_reserve_states(ctx, n_slots)
-                        : frames ? dcreg_frames_reserve_states(ctx, n_slots) : dcreg_reserve_warm_states(ctx, n_slots)) == DCREG_OK;
+    bool have_states = E.reserve(n_slots) == DCREG_OK;
     struct Slot { int64_t trial = -1; int it = 0; double R[9], t[3]; };
     std::vector<Slot> slot((size_t)n_slots);
-    struct Group { std::vector<int> live; std::vector<int32_t> ids, fids, gids; std::vector<double> Rb, tb; std::vector<dcreg_lin_out> outs; bool in_flight = false; };
     Group grp[2];
     int64_t next_trial = 0;
     auto load = [&](int si) -> bool {                      // next trial in line -> slot si
@@ -366,10 +402,7 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         Slot &S = slot[(size_t)si];
         S.trial = next_trial++; S.it = 0;
         std::memcpy(S.R, R0 + 9 * S.trial, sizeof(S.R)); std::memcpy(S.t, t0 + 3 * S.trial, sizeof(S.t));
-        if (have_states) {
-            if (normals) dcreg_normals_reset_slot(ctx, si);
-            else if (pairs) dcreg_pairs_reset_state(ctx, si); else if (frames) dcreg_frames_reset_state(ctx, si); else dcreg_reset_warm_state(ctx, si);
-        }
+        if (have_states) E.reset(si);
         return true;
     };
     for (int si = 0; si < n_slots; ++si) load(si);
@@ -390,20 +423,15 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
             G.gids[(size_t)j] = (int32_t)S.trial;
             std::memcpy(&G.Rb[(size_t)j * 9], S.R, sizeof(S.R)); std::memcpy(&G.tb[(size_t)j * 3], S.t, sizeof(S.t));
         }
-        const int rc = engine == Engine::gicp ? dcreg_gicp_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
-                     : normals ? dcreg_normals_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm)
-                     : pairs ? dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm)
-                     : frames ? dcreg_frames_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), &prm)
-                              : dcreg_linearize_batch_begin_warm(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), &prm);
+        const int rc = E.begin(gi, nl, G);
         G.in_flight = rc == DCREG_OK;
         return rc;
     };
-    auto batch_end = [&](int gi, dcreg_lin_out *outs) { return normals ? dcreg_normals_batch_end(ctx, gi, outs) : dcreg_linearize_batch_end(ctx, gi, outs); };
     auto finish = [&](int gi) -> int {          // wait for the group's results, take the host steps, refill the slots that ended
         Group &G = grp[gi];
         if (!G.in_flight) return DCREG_OK;
         const auto t_a = Clock::now();
-        const int rc = batch_end(gi, G.outs.data());
+        const int rc = E.end(ctx, gi, G.outs.data());
         G.in_flight = false;
         if (rc != DCREG_OK) return rc;
         t_lin_ms += ms_since(t_a);
@@ -461,13 +489,13 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         if (n_groups == 2 && (rc = finish(1)) != DCREG_OK) break;                        // host steps of group 1 overlap group 0's kernel
     }
     if (rc != DCREG_OK) {                                            // drain whatever is still queued
-        for (int gi = 0; gi < 2; ++gi) if (grp[gi].in_flight) { grp[gi].outs.resize(grp[gi].live.size()); (void)batch_end(gi, grp[gi].outs.data()); }
+        for (int gi = 0; gi < 2; ++gi) if (grp[gi].in_flight) { grp[gi].outs.resize(grp[gi].live.size()); (void)E.end(ctx, gi, grp[gi].outs.data()); }
         return rc;
     }
     const double total_ms = ms_since(t_total);
     if (std::getenv("DCREG_TRIALS_TIMING"))
         std::fprintf(stderr, "[dcreg_icp_run_trials%s] %lld trials in %d slots, %lld group steps: wait for results %.1f us/step, host %.1f us/step, wall %.1f us/step\n",
-                     engine == Engine::gicp ? "_gicp" : normals ? "_normals" : "", (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
+                     E.label, (long long)n_trials, n_slots, (long long)n_steps, 1e3 * t_lin_ms / std::max<int64_t>(n_steps, 1),
                      1e3 * t_host_ms / std::max<int64_t>(n_steps, 1), 1e3 * total_ms / std::max<int64_t>(n_steps, 1));
     for (int64_t i = 0; i < n_trials; ++i) results[i].time_ms = total_ms / (double)n_trials;   // amortised: trials advance together
     return DCREG_OK;
@@ -480,10 +508,16 @@ int dcreg_icp_run_trials(dcreg_ctx *ctx, int n_trials, const double *R0, const d
     return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0);
 }
 
-int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
-                          const double *R0, const double *t0, int detection, int handling, const dcreg_config *cfg, int slots,
-                          dcreg_trial_result *results) {
+// What the three dcreg_register_frames* refuse before they load anything, in the header's order: null and size arguments, (check_frame_normals:
+// the third engine's estimation parameters, before the empty call returns), offsets that start at 0 and do not decrease, a target, and for
+// the 1-NN engines (kept_normals) its kept normals.  DCREG_OK with n_frames == 0: the caller has nothing to do.
+static const char *const kNoTarget = "KdTree/target index is not set up in context";
+static const char *const kNoKeptNormals = "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first";
+static int frames_call_check(dcreg_ctx *ctx, int n_frames, const int64_t *frame_offsets, int64_t stride_floats, const double *R0, const double *t0,
+                             const dcreg_config *cfg, const dcreg_trial_result *results, bool kept_normals, bool check_frame_normals = false,
+                             const dcreg_normal_params *frame_normals = nullptr) {
     if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (check_frame_normals) if (int rc = dcreg_normal_params_check(ctx, frame_normals)) return rc;
     if (n_frames == 0) return DCREG_OK;
     if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
     if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
@@ -491,83 +525,73 @@ int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const 
         if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
     dcreg_index_info info;
     dcreg_index_info_get(ctx, &info);
-    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
-    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
-    if (rc != DCREG_OK) return rc;
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, kNoTarget); return DCREG_E_STATE; }
+    if (kept_normals && dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, kNoKeptNormals); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+// the frames' point counts
+static std::vector<int64_t> frame_points(int n_frames, const int64_t *frame_offsets) {
     std::vector<int64_t> points((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
-    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data());
+    return points;
+}
+// ... and what the 1-NN engines' dcreg_icp_run_trials_* refuse (source_normals: the third engine's kept source normals, last)
+static int one_nn_trials_check(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, const dcreg_config *cfg, const dcreg_trial_result *results,
+                               bool source_normals) {
+    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (n_trials == 0) return DCREG_OK;
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, kNoTarget); return DCREG_E_STATE; }
+    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, kNoKeptNormals); return DCREG_E_STATE; }
+    if (source_normals && dcreg_source_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+
+int dcreg_register_frames(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                          const double *R0, const double *t0, int detection, int handling, const dcreg_config *cfg, int slots,
+                          dcreg_trial_result *results) {
+    if (int rc = frames_call_check(ctx, n_frames, frame_offsets, stride_floats, R0, t0, cfg, results, false)) return rc;
+    if (n_frames == 0) return DCREG_OK;
+    if (int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats)) return rc;     // (non-finite coordinates: refused here, nothing queued)
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, frame_points(n_frames, frame_offsets).data());
 }
 
 // The second engine's forms of the two calls above (include/dcreg.h): the same checks, the same core, the launches of normal_icp.hip
 int dcreg_icp_run_trials_normals(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
                                  const dcreg_config *cfg, dcreg_trial_result *results) {
-    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (int rc = one_nn_trials_check(ctx, n_trials, R0, t0, cfg, results, false)) return rc;
     if (n_trials == 0) return DCREG_OK;
-    dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
-    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
-    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
     return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, Engine::normals);
 }
 
 int dcreg_register_frames_normals(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                                   const double *R0, const double *t0, int detection, int handling, const dcreg_config *cfg, int slots,
                                   dcreg_trial_result *results) {
-    if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (int rc = frames_call_check(ctx, n_frames, frame_offsets, stride_floats, R0, t0, cfg, results, true)) return rc;
     if (n_frames == 0) return DCREG_OK;
-    if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
-    if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
-    for (int f = 0; f < n_frames; ++f)
-        if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
-    dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
-    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
-    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
-    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
-    if (rc != DCREG_OK) return rc;
-    std::vector<int64_t> points((size_t)n_frames);
-    for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
-    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, Engine::normals);
+    if (int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats)) return rc;     // (non-finite coordinates: refused here, nothing queued)
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, frame_points(n_frames, frame_offsets).data(), -1, Engine::normals);
 }
 
 // The third engine's forms (include/dcreg.h): the same checks and the same core with the launches of gicp.hip; the frames' own normals are
 // estimated in one batched pass behind the load (dcreg_frames_normals_keep)
 int dcreg_icp_run_trials_gicp(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
                               const dcreg_config *cfg, dcreg_trial_result *results) {
-    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (int rc = one_nn_trials_check(ctx, n_trials, R0, t0, cfg, results, true)) return rc;
     if (n_trials == 0) return DCREG_OK;
-    dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
-    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
-    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
-    if (dcreg_source_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
     return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, Engine::gicp);
 }
 
 int dcreg_register_frames_gicp(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                                const dcreg_normal_params *frame_normals, const double *R0, const double *t0, int detection, int handling,
                                const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
-    if (!ctx || !cfg || n_frames < 0 || stride_floats < 3) return DCREG_E_INVALID;
-    if (int rc = dcreg_normal_params_check(ctx, frame_normals)) return rc;
+    if (int rc = frames_call_check(ctx, n_frames, frame_offsets, stride_floats, R0, t0, cfg, results, true, true, frame_normals)) return rc;
     if (n_frames == 0) return DCREG_OK;
-    if (!frame_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
-    if (frame_offsets[0] != 0) { dcreg_set_error_message(ctx, "frame offsets must start at 0"); return DCREG_E_INVALID; }
-    for (int f = 0; f < n_frames; ++f)
-        if (frame_offsets[f + 1] < frame_offsets[f]) { dcreg_set_error_message(ctx, "frame offsets decrease"); return DCREG_E_INVALID; }
-    dcreg_index_info info;
-    dcreg_index_info_get(ctx, &info);
-    if (info.n_target <= 0) { dcreg_set_error_message(ctx, "KdTree/target index is not set up in context"); return DCREG_E_STATE; }
-    if (dcreg_target_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
-    int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats);     // (non-finite coordinates: refused here, nothing queued)
-    if (rc != DCREG_OK) return rc;
-    if (frame_offsets[n_frames] > 0) {                                                // (all frames empty: nothing to estimate, nothing to run)
-        rc = dcreg_frames_normals_keep(ctx, frame_normals, nullptr);
-        if (rc != DCREG_OK) return rc;
-    }
-    std::vector<int64_t> points((size_t)n_frames);
-    for (int f = 0; f < n_frames; ++f) points[(size_t)f] = frame_offsets[f + 1] - frame_offsets[f];
-    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, points.data(), -1, Engine::gicp);
+    if (int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats)) return rc;     // (non-finite coordinates: refused here, nothing queued)
+    if (frame_offsets[n_frames] > 0)                                                  // (all frames empty: nothing to estimate, nothing to run)
+        if (int rc = dcreg_frames_normals_keep(ctx, frame_normals, nullptr)) return rc;
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, frame_points(n_frames, frame_offsets).data(), -1, Engine::gicp);
 }
 
 // Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,
