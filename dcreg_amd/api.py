@@ -181,6 +181,9 @@ EXPORTS = [
     "dcreg_linearize_gicp_debug", "dcreg_icp_run_gicp",
     "dcreg_normals_clouds", "dcreg_normals_clouds_device", "dcreg_frames_normals_keep", "dcreg_frames_normals_set", "dcreg_frames_normals_kept",
     "dcreg_gicp_batch_begin", "dcreg_gicp_batch_end", "dcreg_normal_params_check", "dcreg_register_frames_gicp", "dcreg_icp_run_trials_gicp",
+    "dcreg_register_pairs_normals", "dcreg_register_pairs_gicp", "dcreg_pairs_plan_normals", "dcreg_pairs_normals_keep", "dcreg_pairs_normals_set",
+    "dcreg_pairs_normals_get", "dcreg_pairs_normals_kept", "dcreg_pairs_sources_normals_keep", "dcreg_pairs_sources_normals_set",
+    "dcreg_pairs_sources_normals_get", "dcreg_pairs_normals_reserve_slots", "dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin",
 ]
 
 _lib = None
@@ -1129,6 +1132,22 @@ def load():
         L.dcreg_register_frames_gicp.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, np_, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
                                                  C.POINTER(TrialResult)]
         L.dcreg_icp_run_trials_gicp.argtypes = L.dcreg_icp_run_trials.argtypes
+    if hasattr(L, "dcreg_register_pairs_normals"):  # (likewise)
+        np_, ni, cfgp, trp = C.POINTER(NormalParams), C.POINTER(NormalInfo), C.POINTER(Config), C.POINTER(TrialResult)
+        L.dcreg_register_pairs_normals.argtypes = [vp, C.c_int, fp, i64p, fp, i64p, C.c_int64, np_, dp, dp, C.c_int, C.c_int, cfgp, C.c_int, trp]
+        L.dcreg_register_pairs_gicp.argtypes = [vp, C.c_int, fp, i64p, fp, i64p, C.c_int64, np_, np_, dp, dp, C.c_int, C.c_int, cfgp, C.c_int, trp]
+        L.dcreg_pairs_sources_load.argtypes = [vp, C.c_int, fp, i64p, C.c_int64]
+        L.dcreg_pairs_build.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, C.c_double]
+        for name in ("dcreg_pairs_normals_keep", "dcreg_pairs_sources_normals_keep"):
+            getattr(L, name).argtypes = [vp, np_, ni]
+        for name in ("dcreg_pairs_normals_set", "dcreg_pairs_sources_normals_set"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64]
+        for name in ("dcreg_pairs_normals_get", "dcreg_pairs_sources_normals_get"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64]
+        L.dcreg_pairs_normals_kept.argtypes = [vp]
+        L.dcreg_pairs_normals_reserve_slots.argtypes = [vp, C.c_int64]
+        for name in ("dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin"):
+            getattr(L, name).argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, ip, C.POINTER(LinParams)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2619,19 +2638,17 @@ class Context:
     def gicp_batch(self, Ts, state_ids=None, frame_ids=None, params=None, slot=0):
         return self.gicp_batch_end(self.gicp_batch_begin(Ts, state_ids, frame_ids, params, slot), slot)
 
-    def register_pairs(self, sources, targets, T0s, method, cfg, slots=0):
-        """dcreg_register_pairs: many scan pairs in one call, pair p = sources[p] registered against targets[p] from T0s[p].  sources and
-        targets = lists of equal length of [n_i, c] float32 arrays (c >= 3 columns, x y z first, the same c for every cloud: the rows are
-        passed c floats apart); T0s = one initial 4x4 pose per pair.  The targets are indexed for cfg.search_radius.  Needs no map on this
-        context and leaves it as it was.  Returns one record per pair, as icp_run_trials does; each is bitwise set_target(target,
-        cfg.search_radius) + set_source(source) + icp_run(T0) on a context with the same options."""
+    @staticmethod
+    def _pairs_args(sources, targets, T0s, what):
+        """the argument checks of register_pairs and the other engines' forms -> (source points, source offsets, target points, target
+        offsets, columns, R0 [n, 9], t0 [n, 3], n)"""
         if len(sources) != len(targets):
-            raise ValueError("register_pairs: one target per source: %d sources, %d targets" % (len(sources), len(targets)))
-        src = [_points(f, "register_pairs") for f in sources]
-        tgt = [_points(f, "register_pairs") for f in targets]
+            raise ValueError("%s: one target per source: %d sources, %d targets" % (what, len(sources), len(targets)))
+        src = [_points(f, what) for f in sources]
+        tgt = [_points(f, what) for f in targets]
         widths = {f.shape[1] for f in src + tgt}
         if len(widths) > 1:
-            raise ValueError("register_pairs: every cloud needs the same number of columns, got %s" % sorted(widths))
+            raise ValueError("%s: every cloud needs the same number of columns, got %s" % (what, sorted(widths)))
         width = widths.pop() if widths else 3
         n = len(src)
         T0s = _f64(T0s).reshape(-1, 4, 4)
@@ -2647,15 +2664,138 @@ class Context:
         txyz, toff = pack(tgt)
         R0 = np.ascontiguousarray(T0s[:, :3, :3]).reshape(n, 9)
         t0 = np.ascontiguousarray(T0s[:, :3, 3]).reshape(n, 3)
+        return sxyz, soff, txyz, toff, width, R0, t0, n
+
+    def _register_pairs(self, symbol, what, sources, targets, T0s, method, cfg, slots, extra_args=()):
+        """register_pairs and the other engines' forms: one record per pair; extra_args: the call's arguments between the clouds and the
+        poses"""
+        sxyz, soff, txyz, toff, width, R0, t0, n = self._pairs_args(sources, targets, T0s, what)
         det, hand = METHODS[method] if isinstance(method, str) else method
         res = (TrialResult * max(n, 1))()
         fp = C.POINTER(C.c_float)
         i64p = C.POINTER(C.c_int64)
-        self._check(self._L.dcreg_register_pairs(self._h, n, sxyz.ctypes.data_as(fp), soff.ctypes.data_as(i64p), txyz.ctypes.data_as(fp),
-                                                 toff.ctypes.data_as(i64p), width, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand],
-                                                 C.byref(cfg), int(slots), res),
-                    "dcreg_register_pairs")
+        self._check(getattr(self._L, symbol)(self._h, n, sxyz.ctypes.data_as(fp), soff.ctypes.data_as(i64p), txyz.ctypes.data_as(fp),
+                                             toff.ctypes.data_as(i64p), width, *extra_args, _dp(R0), _dp(t0), DETECTION[det], HANDLING[hand],
+                                             C.byref(cfg), int(slots), res), symbol)
         return [res[i] for i in range(n)]
+
+    def register_pairs(self, sources, targets, T0s, method, cfg, slots=0):
+        """dcreg_register_pairs: many scan pairs in one call, pair p = sources[p] registered against targets[p] from T0s[p].  sources and
+        targets = lists of equal length of [n_i, c] float32 arrays (c >= 3 columns, x y z first, the same c for every cloud: the rows are
+        passed c floats apart); T0s = one initial 4x4 pose per pair.  The targets are indexed for cfg.search_radius.  Needs no map on this
+        context and leaves it as it was.  Returns one record per pair, as icp_run_trials does; each is bitwise set_target(target,
+        cfg.search_radius) + set_source(source) + icp_run(T0) on a context with the same options."""
+        return self._register_pairs("dcreg_register_pairs", "register_pairs", sources, targets, T0s, method, cfg, slots)
+
+    def register_pairs_normals(self, sources, targets, T0s, method, cfg, target_normals=None, slots=0):
+        """dcreg_register_pairs_normals: register_pairs with the second engine.  Every target's normals are estimated with target_normals
+        = normal_params(...), None = the defaults, all targets of a build batch in one launch.  Same arguments and records; each record is
+        bitwise set_target(target, cfg.search_radius) + keep_target_normals(target_normals) + set_source(source) + icp_run_normals(T0)."""
+        tn = target_normals if target_normals is not None else normal_params()
+        _check_normal_params(tn, "register_pairs_normals")
+        return self._register_pairs("dcreg_register_pairs_normals", "register_pairs_normals", sources, targets, T0s, method, cfg, slots,
+                                    extra_args=(C.byref(tn),))
+
+    def register_pairs_gicp(self, sources, targets, T0s, method, cfg, target_normals=None, source_normals=None, slots=0):
+        """dcreg_register_pairs_gicp: register_pairs with the third engine.  target_normals as register_pairs_normals takes it;
+        source_normals: the rule of every source's own normals (None = the defaults), all sources in one batched pass.  Each record is
+        bitwise set_target(target, cfg.search_radius) + keep_target_normals(target_normals) + set_source(source) +
+        keep_source_normals(source_normals) + icp_run_gicp(T0)."""
+        tn = target_normals if target_normals is not None else normal_params()
+        sn = source_normals if source_normals is not None else normal_params()
+        _check_normal_params(tn, "register_pairs_gicp")
+        _check_normal_params(sn, "register_pairs_gicp")
+        return self._register_pairs("dcreg_register_pairs_gicp", "register_pairs_gicp", sources, targets, T0s, method, cfg, slots,
+                                    extra_args=(C.byref(tn), C.byref(sn)))
+
+    # ---- the device seam of the two calls above (include/dcreg_debug.h), for the tests
+    def pairs_sources_load(self, sources):
+        """dcreg_pairs_sources_load: the pairs' sources (a list of [n_i, c] arrays) onto the device"""
+        xyz, off, n = _frames_arg(sources, "pairs_sources_load")
+        self._check(self._L.dcreg_pairs_sources_load(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     xyz.shape[1]), "dcreg_pairs_sources_load")
+        self._n_pair_sources, self._n_pair_source_points = n, int(off[-1]) if n else 0
+
+    def pairs_build(self, targets, search_radius):
+        """dcreg_pairs_build: the targets of one build batch (a list of [n_i, c] arrays) indexed for search_radius"""
+        xyz, off, n = _frames_arg(targets, "pairs_build")
+        self._check(self._L.dcreg_pairs_build(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              xyz.shape[1], float(search_radius)), "dcreg_pairs_build")
+        self._n_pair_targets, self._n_pair_target_points = n, int(off[-1]) if n else 0
+
+    def _pairs_keep(self, symbol, params, n):
+        p = params if params is not None else normal_params()
+        _check_normal_params(p, symbol[len("dcreg_"):])
+        infos = (NormalInfo * max(n, 1))()
+        self._check(getattr(self._L, symbol)(self._h, C.byref(p), infos), symbol)
+        return [_normal_info_dict(infos[s]) for s in range(n)]
+
+    def _pairs_set(self, symbol, normals):
+        what = symbol[len("dcreg_"):]
+        if isinstance(normals, (list, tuple)):
+            parts = [_points(a, what) for a in normals]
+            if len({a.shape[1] for a in parts}) > 1:
+                raise ValueError("%s: every cloud's normals need the same number of columns" % what)
+            a = np.ascontiguousarray(np.concatenate(parts, 0) if parts else np.zeros((0, 3), np.float32))
+        else:
+            a = _points(normals, what)
+        self._check(getattr(self._L, symbol)(self._h, a.ctypes.data, a.shape[0], a.shape[1]), symbol)
+
+    def _pairs_get(self, symbol, n):
+        out = np.empty((max(n, 1), 4), np.float32)
+        self._check(getattr(self._L, symbol)(self._h, out.ctypes.data, n), symbol)
+        return out[:n]
+
+    def pairs_normals_keep(self, params=None):
+        """dcreg_pairs_normals_keep: the kept normals of the build batch's targets, one launch -> [info dict per target]"""
+        return self._pairs_keep("dcreg_pairs_normals_keep", params, getattr(self, "_n_pair_targets", 0))
+
+    def pairs_normals_set(self, normals):
+        """dcreg_pairs_normals_set: the caller's normals ([N, c >= 3], or one array per target) for all points of the batch, as given"""
+        self._pairs_set("dcreg_pairs_normals_set", normals)
+
+    def pairs_normals_get(self):
+        """dcreg_pairs_normals_get -> [N, 4] float32: normal and curvature of every point of the batch, target after target"""
+        return self._pairs_get("dcreg_pairs_normals_get", getattr(self, "_n_pair_target_points", 0))
+
+    def pairs_normals_kept(self):
+        return int(self._L.dcreg_pairs_normals_kept(self._h))
+
+    def pairs_sources_normals_keep(self, params=None):
+        """dcreg_pairs_sources_normals_keep: the loaded pair sources' own normals, one batched pass -> [info dict per source]"""
+        return self._pairs_keep("dcreg_pairs_sources_normals_keep", params, getattr(self, "_n_pair_sources", 0))
+
+    def pairs_sources_normals_set(self, normals):
+        self._pairs_set("dcreg_pairs_sources_normals_set", normals)
+
+    def pairs_sources_normals_get(self):
+        """dcreg_pairs_sources_normals_get -> [N, 4] float32 in the upload order of the load"""
+        return self._pairs_get("dcreg_pairs_sources_normals_get", getattr(self, "_n_pair_source_points", 0))
+
+    def pairs_normals_reserve_slots(self, n_slots):
+        self._check(self._L.dcreg_pairs_normals_reserve_slots(self._h, int(n_slots)), "dcreg_pairs_normals_reserve_slots")
+
+    def _pairs_batch_begin(self, symbol, Ts, source_ids, target_ids, state_ids, params, slot):
+        params = self._nlin_params(params, symbol[len("dcreg_"):])
+        Rs, ts, n = _poses_arg(Ts)
+        i32p = C.POINTER(C.c_int32)
+        ids = None if state_ids is None else np.ascontiguousarray(state_ids, dtype=np.int32).reshape(n)
+        sids = np.ascontiguousarray(source_ids, dtype=np.int32).reshape(n)
+        tids = np.ascontiguousarray(target_ids, dtype=np.int32).reshape(n)
+        self._check(getattr(self._L, symbol)(self._h, int(slot), n, _dp(Rs), _dp(ts), None if ids is None else ids.ctypes.data_as(i32p),
+                                             sids.ctypes.data_as(i32p), tids.ctypes.data_as(i32p), C.byref(params)), symbol)
+        return n
+
+    def pairs_normals_batch(self, Ts, source_ids, target_ids, state_ids=None, params=None, slot=0):
+        """dcreg_pairs_normals_batch_begin + dcreg_normals_batch_end: pose i linearises pair source source_ids[i] against target
+        target_ids[i] of the build batch and its kept normals -> one dict per pose, as linearize_normals returns"""
+        n = self._pairs_batch_begin("dcreg_pairs_normals_batch_begin", Ts, source_ids, target_ids, state_ids, params, slot)
+        return self.normals_batch_end(n, slot)
+
+    def pairs_gicp_batch(self, Ts, source_ids, target_ids, state_ids=None, params=None, slot=0):
+        """dcreg_pairs_gicp_batch_begin + dcreg_normals_batch_end: the same for linearize_gicp, with the sources' kept normals"""
+        n = self._pairs_batch_begin("dcreg_pairs_gicp_batch_begin", Ts, source_ids, target_ids, state_ids, params, slot)
+        return self.normals_batch_end(n, slot)
 
     def insert(self, xyz, T, min_spacing=0.0):
         """dcreg_target_insert: the points xyz (body frame) transformed by the 4x4 pose T appended to the map, except those with a map point

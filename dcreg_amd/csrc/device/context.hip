@@ -1184,8 +1184,9 @@ static double pairs_budget(dcreg_ctx *c) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 4.0e9; }
     return 0.25 * (double)free_b;
 }
-static double pair_target_bytes(const dcreg_ctx *c, int64_t m, int64_t stride) {
-    return m > 0 ? (double)m * (4.0 * (double)stride + 16.0 + 16.0 + 16.0 + 8.0) + 4.0 * (double)c->opt_pair_max_table_entries + 16.0 * kPtsPad : 0.0;
+// (extra: further bytes per point - the 1-NN engines keep a float4 normal per target point and estimate it through 3 + 1 floats of scratch)
+static double pair_target_bytes(const dcreg_ctx *c, int64_t m, int64_t stride, double extra = 0.0) {
+    return m > 0 ? (double)m * (4.0 * (double)stride + 16.0 + 16.0 + 16.0 + 8.0 + extra) + 4.0 * (double)c->opt_pair_max_table_entries + 16.0 * kPtsPad : 0.0;
 }
 
 // One pass over some targets of the batch (J: batch targets, cells[j]: the geometry of J[j] in this pass): cell keys of all their points
@@ -1363,6 +1364,8 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     if (n_t < 0 || !off || stride < 3 || off[0] != 0 || !(search_radius > 0.0)) { c->fail("invalid pair target arguments"); return DCREG_E_INVALID; }
     ps.n = 0;
     ps.built.assign((size_t)n_t, 0);
+    ps.normals_kept = false;                     // (the kept normals of the 1-NN engines belong to the batch that was built)
+    ps.grids.clear(); ps.off.clear();
     const int64_t n = n_t > 0 ? off[n_t] : 0;
     if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
     if (n >= ((int64_t)1 << 31)) { c->fail("the pair targets of one build batch hold too many points (%lld)", (long long)n); return DCREG_E_INVALID; }
@@ -1411,6 +1414,9 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     }
     ps.n = n_t;
     ps.radius_sq_f = bound;
+    ps.grids = std::move(gs);
+    ps.off.assign(off, off + n_t + 1);
+    ps.search_radius = search_radius;
     return DCREG_OK;
 }
 
@@ -2615,7 +2621,7 @@ static int frames_reset_state(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t sta
 }
 int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) { return c ? frames_reserve_states(c, c->frames, n_states) : DCREG_E_INVALID; }
 int dcreg_frames_reset_state(dcreg_ctx *c, int64_t state_id) { return c ? frames_reset_state(c, c->frames, state_id) : DCREG_E_INVALID; }
-int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
+static int pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, double extra, int32_t *batch_end, int *n_batches) {
     if (!c || n_pairs < 0 || !tgt_offsets || !batch_end || !n_batches) return DCREG_E_INVALID;
     // build batches of pair targets within the byte budget (pairs_budget): at least one pair each, fewer than 2^31 points each
     const double budget = pairs_budget(c);
@@ -2624,7 +2630,7 @@ int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int6
     int64_t pts = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const int64_t m = tgt_offsets[p + 1] - tgt_offsets[p];
-        const double b = pair_target_bytes(c, m, stride_floats);
+        const double b = pair_target_bytes(c, m, stride_floats, extra);
         if (p > 0 && (bytes + b > budget || pts + m >= ((int64_t)1 << 31) - 1)) { batch_end[nb++] = p; bytes = 0.0; pts = 0; }
         bytes += b; pts += m;
     }
@@ -2632,9 +2638,19 @@ int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int6
     *n_batches = nb;
     return DCREG_OK;
 }
+int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
+    return pairs_plan(c, n_pairs, tgt_offsets, stride_floats, 0.0, batch_end, n_batches);
+}
+// ... for the 1-NN engines: a batch also holds its targets' kept normals (16 B a point) and the scratch of their estimation (3 + 1 floats)
+int dcreg_pairs_plan_normals(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
+    return pairs_plan(c, n_pairs, tgt_offsets, stride_floats, 32.0, batch_end, n_batches);
+}
 int dcreg_pairs_sources_load(dcreg_ctx *c, int n_pairs, const float *xyz, const int64_t *src_offsets, int64_t stride_floats) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
+    // (normal_icp.hip: warm slots sized for the pairs' sources belong to the sources that were loaded, and so do their kept normals)
+    if (c->nicp.slots_for == dcreg_ctx::NormalIcpBufs::SlotsFor::pairs) c->nicp.drop_slots();
+    c->pair_src.normals_kept = false;
     return frames_load(c, c->pair_src, n_pairs, xyz, src_offsets, stride_floats);
 }
 int dcreg_pairs_build(dcreg_ctx *c, int n_targets, const float *xyz, const int64_t *tgt_offsets, int64_t stride_floats, double search_radius) {

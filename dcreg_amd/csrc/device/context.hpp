@@ -140,6 +140,16 @@ __device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int 
 }
 }  // namespace dcreg
 
+namespace dcreg {
+// the target of one scan pair as the batched 1-NN launches read it (normal_icp.hip k_nlin_batch<GRIDS>, gicp.hip k_glin_batch<GRIDS>): its
+// grid, the rings that cover the 1-NN search bound in its cells, and where its kept normals start among the build batch's
+struct OneNnGrid {
+    GridDev g;
+    int max_ring;
+    uint32_t normals_first;
+};
+}  // namespace dcreg
+
 // What a linearisation launch is and how it is carried out (context.hip linearize_begin: lin_check settles the kind, lin_plan the rest)
 enum class LinKind : uint8_t { batch, frames, pairs, single, gated, dump, stamps };   // single .. stamps: one pose on the ctx's own source
 enum class LinPass : uint8_t { none, advance, team };     // in front of k_lin: nothing, k_advance, k_advance_team (dcreg_launch_series_passes)
@@ -307,6 +317,14 @@ struct dcreg_ctx {
         std::vector<uint8_t> built;                            // per target of the batch: it has an index
         int n = 0;                                             // targets of the batch
         float radius_sq_f = 0.f;                               // the search bound the grids' rings were counted for (LinArgs::radius_sq_f)
+        // The 1-NN engines' pairs forms (dcreg_register_pairs_normals / _gicp; normals.hip pairs_normals_keep / _set): the kept normals of the
+        // batch's targets - float4 {nx, ny, nz, curvature}, target after target, each in its own index order, target t from off[t] - and the
+        // record k_nlin_batch<GRIDS> reads per target; both dropped by every build.  off / search_radius: what the batch was built with
+        DevBuf<float4> normals; bool normals_kept = false;
+        DevBuf<dcreg::OneNnGrid> d_nn_grids;
+        std::vector<dcreg::GridDev> grids;                     // host copies of the built targets' grids (the normals pass reads them)
+        std::vector<int64_t> off;
+        double search_radius = 0.0;
     };
     PairSet pairs;
     // voxel-grid downsampling (voxel.hip voxel_pass: dcreg_voxel_downsample*, dcreg_set_*_voxel).  Per input point: the packed cloud, its
@@ -426,7 +444,7 @@ struct dcreg_ctx {
     // slots with their own block rows, pose block ([PoseArg x n | slices x n], pinned, and its device copy) and result rows (device, and
     // the pinned copy `done` is recorded behind), so that one group's kernel runs while the host steps the other.  slots: n_slots warm
     // arrays of slot_stride words, positions in the WHOLE map's sorted array (batched launches never search the window index), sized for
-    // the largest loaded frame (slots_frames) or for the own source; slot_valid: the array holds the positions of an earlier launch
+    // the largest loaded frame, the largest pair source or the own source (slots_for); slot_valid: the array holds the positions of an earlier launch
     // Following the map ("normals_follow", normals.hip normals_follow_*): reach = one float per map point beside its normal, the squared
     // distance within which a point that comes or goes can change it (the k-th neighbour's d2; the search bound for a sparse point);
     // from_keep / keep_params: the normals came from dcreg_target_normals_keep with these parameters - the rule an update refits with.
@@ -458,7 +476,8 @@ struct dcreg_ctx {
         DevBuf<uint32_t> slots;
         size_t slot_stride = 0;
         int64_t n_slots = 0;
-        bool slots_frames = false;
+        enum class SlotsFor : uint8_t { source, frames, pairs };   // the clouds the warm slots were sized for: the own source, the loaded frames, the pairs' sources
+        SlotsFor slots_for = SlotsFor::source;
         std::vector<uint8_t> slot_valid;
         bool batch_pending() const { return batch[0].pending || batch[1].pending; }
         void drop_slots() { std::fill(slot_valid.begin(), slot_valid.end(), (uint8_t)0); }
@@ -634,7 +653,7 @@ struct OneNnBound { double radius_sq; float bound_f; int max_ring; };
 int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what);
 OneNnBound one_nn_bound(const GridDev &g, double search_radius);
 int one_nn_warm_reserve(dcreg_ctx *c);
-// one_nn_run: the single-pose call of either engine, plain or debug - one_nn_check, the engine's own refusal (`extra`, with frames == false),
+// one_nn_run: the single-pose call of either engine, plain or debug - one_nn_check, the engine's own refusal (`extra`, with fs == null),
 // roi_ensure, the buffers, then `launch` queues the engine's kernel for the filled record, the requested dump arrays come back, k_finalize,
 // the wait, the warm bookkeeping and the result.  fields: the debug form's arrays in the order they are cut from the dump block (8-byte ones
 // first): the caller's array (null: not asked for), its bytes per point, and the kernel argument's pointer that receives the device array
@@ -646,25 +665,33 @@ struct OneNnLaunch {
 };
 struct OneNnDumpField { void *host; size_t bytes; void *dev; };
 int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
-               int (*extra)(dcreg_ctx *, bool frames), const std::function<void(const OneNnLaunch &)> &launch, bool dump, const OneNnDumpField *fields,
-               int n_fields);
+               int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), const std::function<void(const OneNnLaunch &)> &launch, bool dump,
+               const OneNnDumpField *fields, int n_fields);
 // ... and what their batched forms share (dcreg_normals_batch_begin / _end, dcreg_gicp_batch_begin / _end): the two launch slots and the warm
 // slots of NormalIcpBufs.  one_nn_batch_begin makes every refusal of include/dcreg_debug.h before anything is queued (`extra`: the engine's
-// own state refusals, after "no kept normals"; frames = frame_ids were given), uploads the poses and slices, has `launch` queue the engine's
-// kernel for the filled record, then queues k_finalize, the result copy and the slot's event; one_nn_batch_end waits for that event
+// own state refusals, after "no kept normals"; fs = the set the frame_ids name, null without them), uploads the poses and slices, has
+// `launch` queue the engine's kernel for the filled record, then queues k_finalize, the result copy and the slot's event; one_nn_batch_end
+// waits for that event.  fs: the source set frame_ids index (c->frames, or c->pair_src; null with frame_ids == null: the own source).
+// target_ids (with fs == &c->pair_src only): pose i searches target target_ids[i] of the pairs' build batch and reads that target's kept
+// normals (OneNnGrid) instead of the map and its kept normals; the state refusals are then "no pair batch built" and "no kept pair normals"
 struct OneNnBatch {
-    const float4 *src; uint32_t n_src;          // the frames' points (slices != null) or the own source
-    GridDev g;                                  // the whole map's index
-    const float4 *normals;                      // the map's kept normals
+    const float4 *src; uint32_t n_src;          // the set's points (slices != null) or the own source
+    const float4 *src_normals;                  // ... and its kept normals at the same positions (the third engine)
+    GridDev g;                                  // the whole map's index (grids == null)
+    const float4 *normals;                      // the map's kept normals, or the pair batch's
+    const OneNnGrid *grids; const uint32_t *grid_ids;   // device; pairs: the batch's target records and every pose's target
     const PoseArg *poses; const uint2 *slices;  // device
     OneNnBound bound;
     uint32_t *warm; uint32_t warm_stride;
     double *partials; uint32_t nbx; int n_poses;
     const dcreg_lin_params *p;
 };
-int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
-                       const dcreg_lin_params *p, int (*extra)(dcreg_ctx *, bool frames), void (*launch)(dcreg_ctx *, const OneNnBatch &),
-                       const char *kernel_name);
+int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                       const int32_t *frame_ids, const int32_t *target_ids, const dcreg_lin_params *p,
+                       int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), void (*launch)(dcreg_ctx *, const OneNnBatch &), const char *kernel_name);
+// the warm slots of the batched form, sized for the own source, the loaded frames or the pairs' sources (dcreg_normals_reserve_slots,
+// dcreg_pairs_normals_reserve_slots)
+int one_nn_reserve_slots(dcreg_ctx *c, int64_t n_slots, dcreg_ctx::NormalIcpBufs::SlotsFor what);
 int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs);
 const uint32_t *one_nn_warm_take(dcreg_ctx *c);
 void one_nn_warm_done(dcreg_ctx *c);

@@ -142,15 +142,23 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
 // null, the n_src points at src (the context's own source and its kept source normals).  The warm words are k_nlin_batch's slots.  The body
 // is glin_point and glin_block_rows, unchanged; the block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the
 // rows and additions of the pose's single launch.
+// GRIDS (scan pairs: dcreg_pairs_gicp_batch_begin): as k_nlin_batch<GRIDS> - grids[grid_ids[pose]], read through a block-uniform index, holds
+// the pose's own target: its grid, its rings and where its kept normals start in `normals`; src and src_normals are the pairs' sources.
+template <bool GRIDS>
 static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin_batch(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
                                                                            const float4 *__restrict__ normals, const float4 *__restrict__ src_normals,
                                                                            const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
                                                                            GlinArgs a, uint32_t *warm, uint32_t warm_stride,
-                                                                           double *__restrict__ partials, uint32_t n_blocks_x) {
+                                                                           double *__restrict__ partials, uint32_t n_blocks_x,
+                                                                           const OneNnGrid *__restrict__ grids, const uint32_t *__restrict__ grid_ids) {
     __shared__ RunList runs[kLinBlock / kWave];
     __shared__ double gm[kLinBlock / kWave][64];
     __shared__ double cnt[kLinBlock / kWave][2];
     const uint32_t pose_id = blockIdx.y;
+    if constexpr (GRIDS) {                           // (uniform per block)
+        const OneNnGrid &og = grids[grid_ids[pose_id]];
+        g = og.g; a.max_ring = og.max_ring; normals += og.normals_first;
+    }
     if (slices) {                                    // (uniform per block: before anything is touched)
         const uint2 sl = slices[pose_id];
         if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
@@ -181,11 +189,12 @@ GlinArgs glin_args(const dcreg_ctx *c, const OneNnBound &b) {
     return a;
 }
 
-// this engine's state refusals, after "no kept normals": the single-pose call (frames == false) and the batched form (the second engine's
-// seam, normal_icp.hip one_nn_batch_begin)
-int gicp_refuse(dcreg_ctx *c, bool frames) {
-    if (frames && !c->frames.normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
-    if (!frames && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+// this engine's state refusals, after "no kept normals": the single-pose call (fs == null) and the batched form over the loaded frames or
+// the pairs' sources (the second engine's seam, normal_icp.hip one_nn_batch_begin)
+int gicp_refuse(dcreg_ctx *c, const dcreg_ctx::FrameSet *fs) {
+    if (fs == &c->pair_src && !fs->normals_kept) { c->fail("no kept pair source normals: dcreg_pairs_sources_normals_keep or dcreg_pairs_sources_normals_set first"); return DCREG_E_STATE; }
+    if (fs && !fs->normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
+    if (!fs && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
     return DCREG_OK;
 }
 
@@ -203,8 +212,8 @@ int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
 
 void glin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
     const GlinArgs a = glin_args(c, L.bound);
-    hipLaunchKernelGGL(k_glin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals,
-                       L.slices ? c->frames.normals.data() : c->gicp.src_normals.data(), L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx);
+    hipLaunchKernelGGL(L.grids ? k_glin_batch<true> : k_glin_batch<false>, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src,
+                       L.g, L.normals, L.src_normals, L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx, L.grids, L.grid_ids);
 }
 
 }  // namespace
@@ -218,7 +227,14 @@ int dcreg_linearize_gicp(dcreg_ctx *c, const double R[9], const double t[3], con
 }
 int dcreg_gicp_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                            const int32_t *frame_ids, const dcreg_lin_params *p) {
-    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, gicp_refuse, glin_batch_launch, "the k_glin_batch launch");
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->frames : nullptr, frame_ids, nullptr, p, gicp_refuse, glin_batch_launch,
+                              "the k_glin_batch launch");
+}
+int dcreg_pairs_gicp_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                                 const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *p) {
+    if (c && (!source_ids || !target_ids)) { c->fail("null argument"); return DCREG_E_INVALID; }
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->pair_src : nullptr, source_ids, target_ids, p, gicp_refuse, glin_batch_launch,
+                              "the k_glin_batch launch");
 }
 int dcreg_gicp_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 int dcreg_linearize_gicp_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,

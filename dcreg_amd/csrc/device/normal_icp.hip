@@ -6,7 +6,8 @@
 //                  (kernels.hpp wave_gram_mfma) and the block row in LDS, added in wave order
 //   k_nlin_batch   the same for many poses in ONE launch (dcreg_normals_batch_begin: the engine of dcreg_register_frames_normals): block
 //                  (x, pose) runs nlin_point on block x of the pose's own source slice - a frame of the loaded frames, or the context's
-//                  source - with the pose read from a device array, and leaves its row at partials[pose][x]
+//                  source - with the pose read from a device array, and leaves its row at partials[pose][x]; <GRIDS>: against the pose's
+//                  own target and that target's kept normals (dcreg_pairs_normals_batch_begin: dcreg_register_pairs_normals)
 //   k_finalize     (kernels.hpp) the block rows in chunk order, the additions of the first engine's batched launches
 // Both kernels end in nlin_block_rows (the wave's rows to LDS, block_slot_sum of kernels.hpp, the block row).  On the host, one_nn_run is
 // the single-pose call of this engine AND of gicp.hip's (refusals, buffers, the dump block cut from a table of fields, launch, k_finalize,
@@ -84,15 +85,25 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin(const float4
 // pose's warm positions: warm + P.state * warm_stride (P.state == kNoIdx: search cold, keep nothing; P.fresh: the array holds nothing
 // yet) - a lane reads its word before it writes it, and no other lane's.  The block row goes to partials[pose * n_blocks_x + x], where
 // k_finalize<SLICE> finds it: the rows and additions of the pose's single launch.
+// GRIDS (scan pairs: dcreg_pairs_normals_batch_begin): every pose also searches a target of its own - grids[grid_ids[pose]], read through a
+// block-uniform index, holds its grid, the rings that cover the search bound in its cells and where its kept normals start in `normals`; the
+// block takes them before anything else and runs as a slice block against that target (the warm words are then positions in that target's
+// sorted points).  The search bound and the gate depend on the radius alone and stay in `a`.
+template <bool GRIDS>
 static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin_batch(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
                                                                            const float4 *__restrict__ normals,
                                                                            const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
                                                                            NlinArgs a, uint32_t *warm, uint32_t warm_stride,
-                                                                           double *__restrict__ partials, uint32_t n_blocks_x) {
+                                                                           double *__restrict__ partials, uint32_t n_blocks_x,
+                                                                           const OneNnGrid *__restrict__ grids, const uint32_t *__restrict__ grid_ids) {
     __shared__ RunList runs[kLinBlock / kWave];
     __shared__ double gm[kLinBlock / kWave][64];
     __shared__ double cnt[kLinBlock / kWave][2];
     const uint32_t pose_id = blockIdx.y;
+    if constexpr (GRIDS) {                           // (uniform per block)
+        const OneNnGrid &og = grids[grid_ids[pose_id]];
+        g = og.g; a.max_ring = og.max_ring; normals += og.normals_first;
+    }
     if (slices) {                                    // (uniform per block: before anything is touched)
         const uint2 sl = slices[pose_id];
         if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
@@ -143,8 +154,8 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
 // the second engine's kernel for a batched launch (one_nn_batch_begin below)
 void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
     const NlinArgs a = nlin_args(L.bound, L.p);
-    hipLaunchKernelGGL(k_nlin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, L.g, L.normals, L.poses, L.slices, a,
-                       L.warm, L.warm_stride, L.partials, L.nbx);
+    hipLaunchKernelGGL(L.grids ? k_nlin_batch<true> : k_nlin_batch<false>, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src,
+                       L.g, L.normals, L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx, L.grids, L.grid_ids);
 }
 
 }  // namespace
@@ -155,11 +166,16 @@ void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
 // slot queued behind it.  The two launch slots serve both 1-NN engines: a pending slot of either refuses the other.
 using BatchSlot = dcreg_ctx::NormalIcpBufs::BatchSlot;
 
-int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, const int32_t *frame_ids,
-                       const dcreg_lin_params *p, int (*extra)(dcreg_ctx *, bool frames), void (*launch)(dcreg_ctx *, const OneNnBatch &),
-                       const char *kernel_name) {
+int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                       const int32_t *frame_ids, const int32_t *target_ids, const dcreg_lin_params *p,
+                       int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), void (*launch)(dcreg_ctx *, const OneNnBatch &), const char *kernel_name) {
     if (!c) return DCREG_E_INVALID;
     dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    using SlotsFor = dcreg_ctx::NormalIcpBufs::SlotsFor;
+    if (!frame_ids) fs = nullptr;
+    const bool pairs = fs == &c->pair_src;
+    if (pairs != (target_ids != nullptr)) { c->fail("pair launches name a source and a target for every pose"); return DCREG_E_INVALID; }
+    const SlotsFor slots_for = pairs ? SlotsFor::pairs : fs ? SlotsFor::frames : SlotsFor::source;
     if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
     if (!R9 || !t3 || !p || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
     if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
@@ -170,12 +186,24 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the normal linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
     if (!(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
     if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
-    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
-    if (!B.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
-    const std::vector<uint2> &slice = c->frames.slice;
+    const dcreg_ctx::PairSet &ps = c->pairs;
+    if (pairs) {
+        if (ps.n <= 0) { c->fail("no pair batch built: dcreg_pairs_build first"); return DCREG_E_STATE; }
+        if (!ps.normals_kept) { c->fail("no kept pair normals: dcreg_pairs_normals_keep or dcreg_pairs_normals_set first"); return DCREG_E_STATE; }
+        if (p->search_radius != ps.search_radius) { c->fail("the pair targets were built for another search radius"); return DCREG_E_INVALID; }
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t t = target_ids[i];
+            if (t < 0 || t >= ps.n || !ps.built[(size_t)t]) { c->fail("pair target %d is not built", t); return DCREG_E_INVALID; }
+        }
+    } else {
+        if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+        if (!B.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    }
+    static const std::vector<uint2> no_slices;
+    const std::vector<uint2> &slice = fs ? fs->slice : no_slices;
     int64_t n_max = c->n_src;                         // points of the launch's largest cloud
     if (frame_ids) {
-        if (slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+        if (slice.empty()) { c->fail(pairs ? "no pair sources: dcreg_pairs_sources_load first" : "no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
         n_max = 0;
         for (int i = 0; i < n_poses; ++i) {
             const int32_t f = frame_ids[i];
@@ -183,7 +211,7 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
             n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
         }
     } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
-    if (extra) if (int rc = extra(c, frame_ids != nullptr)) return rc;
+    if (extra) if (int rc = extra(c, fs)) return rc;
     if (state_ids) {
         std::vector<uint8_t> seen((size_t)std::max<int64_t>(B.n_slots, 1), 0);
         for (int i = 0; i < n_poses; ++i) {
@@ -191,7 +219,7 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
             if (sid < 0) continue;
             if ((int64_t)sid >= B.n_slots) { c->fail("warm slot %d was not reserved (dcreg_normals_reserve_slots: %lld)", sid, (long long)B.n_slots); return DCREG_E_INVALID; }
             if (seen[(size_t)sid]) { c->fail("warm slot %d is used by two poses of one launch", sid); return DCREG_E_INVALID; }
-            if (B.slots_frames != (frame_ids != nullptr) || (int64_t)B.slot_stride < n_max) {
+            if (B.slots_for != slots_for || (int64_t)B.slot_stride < n_max) {
                 c->fail("the warm slots were reserved for other clouds (dcreg_normals_reserve_slots again)"); return DCREG_E_INVALID;
             }
             seen[(size_t)sid] = 1;
@@ -201,14 +229,15 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     // the whole map's index, wherever it lives (context.hpp roi_store): the window index stays as it is, active or not
     const dcreg_ctx::IndexSet &whole = c->roi_active ? c->roi_store : c->map;
     const uint32_t nbx = (uint32_t)((n_max + kLinBlock - 1) / kLinBlock);
-    const size_t np = (size_t)n_poses, pose_bytes = np * sizeof(PoseArg), bytes = pose_bytes + (frame_ids ? np * sizeof(uint2) : 0);
+    const size_t np = (size_t)n_poses, pose_bytes = np * sizeof(PoseArg), slice_bytes = frame_ids ? np * sizeof(uint2) : 0,
+                 bytes = pose_bytes + slice_bytes + (pairs ? np * sizeof(uint32_t) : 0);
     // (sized for the call's largest cloud and for what the slot has held: the engine's launches stop growing them after the first)
-    const int64_t cloud_max = frame_ids ? c->frames.max_points : c->n_src;
+    const int64_t cloud_max = fs ? fs->max_points : c->n_src;
     const size_t rows_cap = std::max(np, S.d_out.cap() / kSlots) * (size_t)((cloud_max + kLinBlock - 1) / kLinBlock) * kSlots;
     if (S.partials.ensure(c, std::max(rows_cap, np * nbx * kSlots)) || S.d_out.ensure(c, np * kSlots)) return DCREG_E_NOMEM;
     if (S.h_out.cap() < np * kSlots) HIP_TRY(c, S.h_out.alloc(std::max<size_t>(np, 256) * kSlots, hipHostMallocDefault));
     if (bytes > S.d_poses.cap()) {
-        const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2)));
+        const size_t cap = std::max<size_t>(bytes, 256 * (sizeof(PoseArg) + sizeof(uint2) + sizeof(uint32_t)));
         HIP_TRY(c, S.h_poses.alloc(cap, hipHostMallocDefault));
         if (S.d_poses.ensure(c, cap)) return DCREG_E_NOMEM;
     }
@@ -229,6 +258,11 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
         for (int i = 0; i < n_poses; ++i) hs[i] = slice[(size_t)frame_ids[i]];
         d_slices = (const uint2 *)(S.d_poses.data() + pose_bytes);
     }
+    const uint32_t *d_grid_ids = nullptr;
+    if (pairs) {
+        std::memcpy(S.h_poses.data() + pose_bytes + slice_bytes, target_ids, np * sizeof(uint32_t));
+        d_grid_ids = (const uint32_t *)(S.d_poses.data() + pose_bytes + slice_bytes);
+    }
     auto failed = [&](hipError_t e, const char *what) {          // something may be queued: what it leaves in the slots is unknown
         for (int32_t sid : S.ids) B.slot_valid[(size_t)sid] = 0;
         c->fail("%s failed: %s", what, hipGetErrorString(e));
@@ -237,10 +271,14 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     hipError_t e = hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return failed(e, "the pose upload");
     OneNnBatch L;
-    L.src = frame_ids ? c->frames.src.data() : c->d_src.data(); L.n_src = (uint32_t)c->n_src;
-    L.g = whole.grid; L.normals = B.normals.data();
+    L.src = fs ? fs->src.data() : c->d_src.data(); L.n_src = (uint32_t)c->n_src;
+    L.src_normals = fs ? fs->normals.data() : c->gicp.src_normals.data();
+    L.g = pairs ? GridDev{} : whole.grid; L.normals = pairs ? ps.normals.data() : B.normals.data();
+    L.grids = pairs ? ps.d_nn_grids.data() : nullptr; L.grid_ids = d_grid_ids;
     L.poses = (const PoseArg *)S.d_poses.data(); L.slices = d_slices;
-    L.bound = one_nn_bound(whole.grid, p->search_radius);
+    GridDev bound_grid = whole.grid;
+    if (pairs) bound_grid.h = p->search_radius;                 // (the rings come with every pose's target: only the radius' part is used)
+    L.bound = one_nn_bound(bound_grid, p->search_radius);
     L.warm = B.slots.data(); L.warm_stride = (uint32_t)B.slot_stride;
     L.partials = S.partials.data(); L.nbx = nbx; L.n_poses = n_poses; L.p = p;
     launch(c, L);
@@ -291,9 +329,10 @@ int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin
 // The single-pose runner of both 1-NN engines (context.hpp).  The engine's kernel searches the index roi_ensure made the active one; a debug
 // launch searches cold and keeps no positions, a plain one starts from the warm words and leaves its own there.
 int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
-               int (*extra)(dcreg_ctx *, bool frames), const std::function<void(const OneNnLaunch &)> &launch, bool dump, const OneNnDumpField *fields, int n_fields) {
+               int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), const std::function<void(const OneNnLaunch &)> &launch, bool dump,
+               const OneNnDumpField *fields, int n_fields) {
     if (int rc = one_nn_check(c, R, t, p, out, what)) return rc;
-    if (extra) if (int rc = extra(c, false)) return rc;
+    if (extra) if (int rc = extra(c, nullptr)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize (a swap drops the warm positions)
     if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
@@ -354,6 +393,25 @@ const uint32_t *one_nn_warm_take(dcreg_ctx *c) {
     return warm ? B.warm.data() : nullptr;
 }
 void one_nn_warm_done(dcreg_ctx *c) { c->nicp.warm_valid = true; }
+// the warm slots of the batched form: n_slots arrays sized for the largest cloud of `what` (nothing is reserved without such a cloud)
+int one_nn_reserve_slots(dcreg_ctx *c, int64_t n_slots, dcreg_ctx::NormalIcpBufs::SlotsFor what) {
+    using SlotsFor = dcreg_ctx::NormalIcpBufs::SlotsFor;
+    if (n_slots < 0) { c->fail("negative slot count"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    B.n_slots = 0; B.slot_valid.clear(); B.slot_stride = 0;
+    B.slots_for = what;
+    const int64_t points = what == SlotsFor::pairs ? c->pair_src.max_points : what == SlotsFor::frames ? c->frames.max_points : c->n_src;
+    if (n_slots == 0 || points <= 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t stride = ((size_t)points + 63) & ~(size_t)63;
+    // nothing is cleared: a slot is "fresh" (host-side flag) until its first launch has filled it
+    if (B.slots.ensure(c, stride * (size_t)n_slots)) return DCREG_E_NOMEM;
+    B.slot_stride = stride;
+    B.n_slots = n_slots;
+    B.slot_valid.assign((size_t)n_slots, 0);
+    return DCREG_OK;
+}
 
 }  // namespace dcreg
 
@@ -369,22 +427,17 @@ int dcreg_linearize_normals_debug(dcreg_ctx *c, const double R[9], const double 
     return nlin_run(c, R, t, p, out, dbg);
 }
 int dcreg_normals_reserve_slots(dcreg_ctx *c, int64_t n_slots, int frames) {
-    if (!c) return DCREG_E_INVALID;
-    if (n_slots < 0) { c->fail("negative slot count"); return DCREG_E_INVALID; }
-    if (int rc = refuse_in_flight(c)) return rc;
-    dcreg_ctx::NormalIcpBufs &B = c->nicp;
-    B.n_slots = 0; B.slot_valid.clear(); B.slot_stride = 0;
-    B.slots_frames = frames != 0;
-    const int64_t points = frames ? c->frames.max_points : c->n_src;
-    if (n_slots == 0 || points <= 0) return DCREG_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t stride = ((size_t)points + 63) & ~(size_t)63;
-    // nothing is cleared: a slot is "fresh" (host-side flag) until its first launch has filled it
-    if (B.slots.ensure(c, stride * (size_t)n_slots)) return DCREG_E_NOMEM;
-    B.slot_stride = stride;
-    B.n_slots = n_slots;
-    B.slot_valid.assign((size_t)n_slots, 0);
-    return DCREG_OK;
+    using SlotsFor = dcreg_ctx::NormalIcpBufs::SlotsFor;
+    return c ? one_nn_reserve_slots(c, n_slots, frames ? SlotsFor::frames : SlotsFor::source) : DCREG_E_INVALID;
+}
+int dcreg_pairs_normals_reserve_slots(dcreg_ctx *c, int64_t n_slots) {
+    return c ? one_nn_reserve_slots(c, n_slots, dcreg_ctx::NormalIcpBufs::SlotsFor::pairs) : DCREG_E_INVALID;
+}
+int dcreg_pairs_normals_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                                    const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *p) {
+    if (c && (!source_ids || !target_ids)) { c->fail("null argument"); return DCREG_E_INVALID; }
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->pair_src : nullptr, source_ids, target_ids, p, nullptr, nlin_batch_launch,
+                              "the k_nlin_batch launch");
 }
 int dcreg_normals_reset_slot(dcreg_ctx *c, int64_t slot_id) {
     if (!c) return DCREG_E_INVALID;
@@ -394,7 +447,8 @@ int dcreg_normals_reset_slot(dcreg_ctx *c, int64_t slot_id) {
 }
 int dcreg_normals_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                               const int32_t *frame_ids, const dcreg_lin_params *p) {
-    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, frame_ids, p, nullptr, nlin_batch_launch, "the k_nlin_batch launch");
+    return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->frames : nullptr, frame_ids, nullptr, p, nullptr, nlin_batch_launch,
+                              "the k_nlin_batch launch");
 }
 int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 }

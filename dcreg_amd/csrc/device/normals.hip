@@ -7,7 +7,8 @@
 //                 hot in L2), solves the 3x3 problem with six Jacobi sweeps in registers, orients the normal and writes 12 + 4 (+ 12) bytes
 //                 at the point's input index
 //   k_nrm_batch<K> the same body (nrm_point) for many clouds in ONE launch (dcreg_normals_clouds*, dcreg_frames_normals_keep): every cloud's
-//                 used points behind a grid of its own, all grids built at once (context.hip clouds_index_build); a block serves one cloud
+//                 used points behind a grid of its own, all grids built at once (context.hip clouds_index_build); a block serves one cloud;
+//                 <K, true>: over the grids of a pairs' build batch, the outputs target after target (dcreg_pairs_normals_keep)
 //   k_follow_*    the kept normals follow an update of the map ("normals_follow"): the cells of the points that came or went are marked,
 //                 the map points whose reach touches a marked cell are compacted and go through k_nrm again, the rest is carried
 // A point's result depends on the cloud only: the index decides how fast the neighbours are found, never which.
@@ -190,13 +191,16 @@ static __global__ __launch_bounds__(kBlock) void k_nrm(const float4 *__restrict_
 // cloud's used points in its cell order are the grid's points: w = the point's index in the call's input), the rings that cover the search
 // bound in its cells (-1: unbounded) and its place in the call - and as many blocks as its points need: block b is block blk[b].y of record
 // blk[b].x, so a block never straddles two clouds and reads its grid through a block-uniform index.  Outputs at the point's input index;
-// the counts of record r's cloud at cnt[2 cloud], cnt[2 cloud + 1]
+// the counts of record r's cloud at cnt[2 cloud], cnt[2 cloud + 1].  base (read by the BASE instantiations only): added to the output index
+// of every point of the record - 0 where w is the index in the call's input; the pair targets' grids carry w = the index within the own
+// cloud (k_pairs_pack), and base is the target's first point in the batch (pairs_normals_keep)
 struct NrmCloud {
     GridDev g;
     int max_ring;
     uint32_t cloud;
+    uint32_t base;
 };
-template <int K>
+template <int K, bool BASE = false>
 static __global__ __launch_bounds__(kBlock) void k_nrm_batch(const NrmCloud *__restrict__ clouds, const uint2 *__restrict__ blk, float bound_f, int k,
                                                              NrmArgs a, float *__restrict__ normal, float *__restrict__ curv,
                                                              unsigned long long *__restrict__ cnt) {
@@ -206,7 +210,11 @@ static __global__ __launch_bounds__(kBlock) void k_nrm_batch(const NrmCloud *__r
     const GridDev g = C.g;
     const uint32_t i = b.y * kBlock + threadIdx.x;
     if (i >= g.n_pts) return;
-    nrm_point<K>(g.pts[i], g, runs[threadIdx.x / kWave], bound_f, C.max_ring, k, a, normal, curv, nullptr, nullptr, nullptr, cnt + 2 * (size_t)C.cloud);
+    float4 s4 = g.pts[i];
+    // (BASE: the record's base is added to the output index - nothing else reads w; without it the kernel is the one of the two callers
+    // whose records carry base 0, register for register)
+    if constexpr (BASE) s4.w = __uint_as_float(__float_as_uint(s4.w) + C.base);
+    nrm_point<K>(s4, g, runs[threadIdx.x / kWave], bound_f, C.max_ring, k, a, normal, curv, nullptr, nullptr, nullptr, cnt + 2 * (size_t)C.cloud);
 }
 
 // the bounds of every cloud's used points (ordered floats: bounds[3 s + a] minima, bounds[3 n_clouds + 3 s + a] maxima, as k_pairs_pack
@@ -283,6 +291,19 @@ static __global__ void k_nrm_pack_src(const float4 *__restrict__ src, int64_t n,
     const size_t oi = __float_as_uint(src[i].w);
     const float *p = normal + oi * (size_t)stride;
     out[i] = float4{p[0], p[1], p[2], curv ? curv[oi] : __builtin_nanf("")};
+}
+// ... and the kept normals of loaded frames back in upload order (the inverse of k_nrm_pack_frames; the padding is skipped)
+static __global__ void k_nrm_unpack_frames(const float4 *__restrict__ src, int64_t n_padded, const uint32_t *__restrict__ dst, const int64_t *__restrict__ off,
+                                           int n_frames, const float4 *__restrict__ kept, float4 *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_padded) return;
+    int lo = 0, hi = n_frames - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)dst[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    const int64_t local = p - (int64_t)dst[lo];
+    if (local < off[lo + 1] - off[lo]) out[(size_t)(off[lo] + (int64_t)__float_as_uint(src[p].w))] = kept[p];
 }
 static __global__ void k_nrm_unpack_src(const float4 *__restrict__ src, int64_t n, const float4 *__restrict__ kept, float4 *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -452,6 +473,7 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
             r.g = grids[s];
             r.max_ring = p->search_radius > 0.0 ? outlier_rings(grids[s], sr.bound) : -1;
             r.cloud = (uint32_t)s;
+            r.base = 0u;
             const uint32_t nb = blocks(count[s], kBlock);
             for (uint32_t b = 0; b < nb; ++b) blk.push_back(make_uint2((uint32_t)recs.size(), b));
             recs.push_back(r);
@@ -533,12 +555,14 @@ int64_t frames_offsets(const dcreg_ctx::FrameSet &fs, std::vector<int64_t> &off)
 
 // dcreg_frames_normals_keep: the pass above over the loaded frames in upload order (FrameSet::raw is what upload_cloud packs for
 // dcreg_normals_clouds: the same points, the same build, the same kernel), then one gather into every frame's curve order
-int frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) {
-    if (!c) return DCREG_E_INVALID;
+// (fs: the context's frames, or the sources of the pairs' calls - dcreg_pairs_sources_normals_keep)
+const char *no_frames_msg(const dcreg_ctx *c, const dcreg_ctx::FrameSet &fs) {
+    return &fs == &c->pair_src ? "no pair sources: dcreg_pairs_sources_load first" : "no frames: dcreg_frames_load first";
+}
+int frames_normals_keep(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, const dcreg_normal_params *p, dcreg_normal_info *infos) {
     if (int rc = normals_check(c, p)) return rc;
     if (int rc = refuse_in_flight(c)) return rc;
-    if (c->frames.slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
-    dcreg_ctx::FrameSet &fs = c->frames;
+    if (fs.slice.empty()) { c->fail("%s", no_frames_msg(c, fs)); return DCREG_E_STATE; }
     std::vector<int64_t> off;
     const int64_t padded = frames_offsets(fs, off), n = off.back();
     const int n_frames = (int)fs.slice.size();
@@ -558,12 +582,10 @@ int frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal
 }
 
 // dcreg_frames_normals_set: the caller's normals in the upload order of the load become the frames' kept normals, as given
-int frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_given, int64_t stride) {
-    if (!c) return DCREG_E_INVALID;
+int frames_normals_set(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, const float *normals, int64_t n_given, int64_t stride) {
     if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
     if (int rc = refuse_in_flight(c)) return rc;
-    if (c->frames.slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
-    dcreg_ctx::FrameSet &fs = c->frames;
+    if (fs.slice.empty()) { c->fail("%s", no_frames_msg(c, fs)); return DCREG_E_STATE; }
     std::vector<int64_t> off;
     const int64_t padded = frames_offsets(fs, off), n = off.back();
     if (n_given != n) { c->fail("the frames hold %lld points, %lld normals were given", (long long)n, (long long)n_given); return DCREG_E_INVALID; }
@@ -579,6 +601,163 @@ int frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_given, int6
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     fs.normals_kept = true;
+    return DCREG_OK;
+}
+
+// the kept normals of a frame set in the upload order of its load, 4 floats per point (the pairs' sources: dcreg_pairs_sources_normals_get)
+int frames_normals_get(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, float *out, int64_t capacity) {
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (fs.slice.empty() || !fs.normals_kept) { c->fail("no kept normals of these clouds"); return DCREG_E_STATE; }
+    std::vector<int64_t> off;
+    const int64_t padded = frames_offsets(fs, off), n = off.back();
+    if (capacity < n) { c->fail("the clouds hold %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (n == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->gicp.tmp.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_nrm_unpack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(), fs.d_off.data(),
+                       (int)fs.slice.size(), fs.normals.data(), c->gicp.tmp.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, c->gicp.tmp.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the targets of a pairs' build batch
+// The record the batched 1-NN launches read per target (context.hpp OneNnGrid): its grid, the rings of the 1-NN bound at the radius the
+// batch was built for, the start of its kept normals.  Uploaded behind every keep / set; waits for the stream.
+int pairs_nn_grids(dcreg_ctx *c) {
+    dcreg_ctx::PairSet &ps = c->pairs;
+    const size_t nt = (size_t)ps.n;
+    std::vector<OneNnGrid> recs(nt);
+    std::memset(recs.data(), 0, sizeof(OneNnGrid) * nt);
+    for (size_t t = 0; t < nt; ++t) {
+        if (!ps.built[t]) continue;
+        recs[t].g = ps.grids[t];
+        recs[t].max_ring = one_nn_bound(ps.grids[t], ps.search_radius).max_ring;
+        recs[t].normals_first = (uint32_t)ps.off[t];
+    }
+    if (ps.d_nn_grids.ensure(c, nt)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemcpyAsync(ps.d_nn_grids.data(), recs.data(), sizeof(OneNnGrid) * nt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+int pairs_batch_check(dcreg_ctx *c) {
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (c->pairs.n <= 0 || c->pairs.off.size() != (size_t)c->pairs.n + 1) { c->fail("no pair batch built: dcreg_pairs_build first"); return DCREG_E_STATE; }
+    return DCREG_OK;
+}
+
+// dcreg_pairs_normals_keep: the kept normals of every target of the build batch, in ONE launch of k_nrm_batch over the grids the batch
+// already has - no second index, no second sort.  A grid's points carry w = the index within their own target, so every record adds the
+// target's first point (NrmCloud::base): the outputs land target after target, each in its own index order.  A target with fewer than k
+// points gets no record and keeps the NaN the outputs start with, as a cloud of normals_clouds_run; the rings per grid, -1 unbounded.
+// The searches are exact in any cells: target t's values are bitwise dcreg_normals of that target alone.
+int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = normals_check(c, p)) return rc;
+    if (int rc = pairs_batch_check(c)) return rc;
+    dcreg_ctx::PairSet &ps = c->pairs;
+    dcreg_ctx::NormalBufs &B = c->nrm;
+    const size_t nt = (size_t)ps.n;
+    const int64_t n = ps.off.back();
+    if (infos) std::memset(infos, 0, sizeof(*infos) * nt);
+    HIP_TRY(c, hipSetDevice(c->device));
+    ps.normals_kept = false;                                    // (a failed call leaves none)
+    std::vector<unsigned long long> cnt(2 * nt, 0ull);
+    std::vector<uint8_t> has(nt, 0);
+    if (n > 0) {
+        if (B.normal.ensure(c, 3 * (size_t)n) || B.curv.ensure(c, (size_t)n) || B.cnt.ensure(c, 2 * nt) || ps.normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+        const float nanf_ = __builtin_nanf("");
+        hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, B.normal.data(), 3 * n, nanf_);
+        hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.curv.data(), n, nanf_);
+        HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * nt * sizeof(unsigned long long), c->stream));
+        const NrmSearch sr = nrm_search_bound(p);
+        std::vector<NrmCloud> recs;
+        std::vector<uint2> blk;
+        for (size_t t = 0; t < nt; ++t) {
+            const int64_t m = ps.off[t + 1] - ps.off[t];
+            if (!ps.built[t] || m < p->k) continue;
+            NrmCloud r;
+            r.g = ps.grids[t];
+            r.max_ring = p->search_radius > 0.0 ? outlier_rings(ps.grids[t], sr.bound) : -1;
+            r.cloud = (uint32_t)t;
+            r.base = (uint32_t)ps.off[t];
+            const uint32_t nb = blocks(m, kBlock);
+            for (uint32_t b = 0; b < nb; ++b) blk.push_back(make_uint2((uint32_t)recs.size(), b));
+            recs.push_back(r);
+            has[t] = 1;
+        }
+        const size_t rec_bytes = recs.size() * sizeof(NrmCloud), bytes = rec_bytes + blk.size() * sizeof(uint2);
+        std::vector<unsigned char> h(bytes);
+        if (!recs.empty()) {
+            std::memcpy(h.data(), recs.data(), rec_bytes);
+            std::memcpy(h.data() + rec_bytes, blk.data(), blk.size() * sizeof(uint2));
+            if (B.d_launch.ensure(c, bytes)) return DCREG_E_NOMEM;
+            HIP_TRY(c, hipMemcpyAsync(B.d_launch.data(), h.data(), bytes, hipMemcpyHostToDevice, c->stream));
+            const NrmCloud *d_recs = (const NrmCloud *)B.d_launch.data();
+            const uint2 *d_blk = (const uint2 *)(B.d_launch.data() + rec_bytes);
+            const dim3 grid((unsigned)blk.size()), block(kBlock);
+            const int k = p->k;
+            if (k <= 8) hipLaunchKernelGGL((k_nrm_batch<8, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+            else if (k <= 16) hipLaunchKernelGGL((k_nrm_batch<16, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+            else hipLaunchKernelGGL((k_nrm_batch<32, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(cnt.data(), B.cnt.data(), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.normal.data(), (int64_t)3, B.curv.data(), n, ps.normals.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));              // (h is the source of the upload)
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (infos)
+        for (size_t t = 0; t < nt; ++t) {
+            const int64_t m = ps.off[t + 1] - ps.off[t];
+            infos[t].n_in = m; infos[t].n_finite = m;
+            infos[t].n_sparse = has[t] ? (int64_t)cnt[2 * t + 1] : m;
+            infos[t].n_out = has[t] ? (int64_t)cnt[2 * t] : 0;
+        }
+    if (int rc = pairs_nn_grids(c)) return rc;
+    ps.normals_kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_pairs_normals_set: the caller's normals for all points of the batch in its upload order become the kept normals, as given
+int pairs_normals_set(dcreg_ctx *c, const float *normals, int64_t n_given, int64_t stride) {
+    if (!c) return DCREG_E_INVALID;
+    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = pairs_batch_check(c)) return rc;
+    dcreg_ctx::PairSet &ps = c->pairs;
+    const int64_t n = ps.off.back();
+    if (n_given != n) { c->fail("the pair targets hold %lld points, %lld normals were given", (long long)n, (long long)n_given); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    ps.normals_kept = false;
+    if (n > 0) {
+        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
+        if (ps.normals.ensure(c, (size_t)n) || c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), stride, (const float *)nullptr, n, ps.normals.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (int rc = pairs_nn_grids(c)) return rc;
+    ps.normals_kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_pairs_normals_get: the batch's kept normals as they stand, 4 floats per point
+int pairs_normals_get(dcreg_ctx *c, float *out, int64_t capacity) {
+    if (!c) return DCREG_E_INVALID;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (int rc = pairs_batch_check(c)) return rc;
+    dcreg_ctx::PairSet &ps = c->pairs;
+    if (!ps.normals_kept) { c->fail("no kept pair normals: dcreg_pairs_normals_keep or dcreg_pairs_normals_set first"); return DCREG_E_STATE; }
+    const int64_t n = ps.off.back();
+    if (capacity < n) { c->fail("the pair targets hold %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (n == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, ps.normals.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
 }
 
@@ -926,10 +1105,27 @@ int dcreg_normals_clouds_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, 
                                 const dcreg_normal_params *p, float *d_normals_out, float *d_curvature_out, dcreg_normal_info *infos) {
     return normals_clouds(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_normals_out, d_curvature_out, infos);
 }
-int dcreg_frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) { return frames_normals_keep(c, p, infos); }
-int dcreg_frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_points, int64_t stride_floats) {
-    return frames_normals_set(c, normals, n_points, stride_floats);
+int dcreg_frames_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) {
+    return c ? frames_normals_keep(c, c->frames, p, infos) : DCREG_E_INVALID;
 }
+int dcreg_frames_normals_set(dcreg_ctx *c, const float *normals, int64_t n_points, int64_t stride_floats) {
+    return c ? frames_normals_set(c, c->frames, normals, n_points, stride_floats) : DCREG_E_INVALID;
+}
+int dcreg_pairs_sources_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) {
+    return c ? frames_normals_keep(c, c->pair_src, p, infos) : DCREG_E_INVALID;
+}
+int dcreg_pairs_sources_normals_set(dcreg_ctx *c, const float *normals, int64_t n_points, int64_t stride_floats) {
+    return c ? frames_normals_set(c, c->pair_src, normals, n_points, stride_floats) : DCREG_E_INVALID;
+}
+int dcreg_pairs_sources_normals_get(dcreg_ctx *c, float *out, int64_t capacity_points) {
+    return c ? frames_normals_get(c, c->pair_src, out, capacity_points) : DCREG_E_INVALID;
+}
+int dcreg_pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_info *infos) { return pairs_normals_keep(c, p, infos); }
+int dcreg_pairs_normals_set(dcreg_ctx *c, const float *normals, int64_t n_points, int64_t stride_floats) {
+    return pairs_normals_set(c, normals, n_points, stride_floats);
+}
+int dcreg_pairs_normals_get(dcreg_ctx *c, float *out, int64_t capacity_points) { return pairs_normals_get(c, out, capacity_points); }
+int dcreg_pairs_normals_kept(const dcreg_ctx *c) { return c && c->pairs.normals_kept ? 1 : 0; }
 int dcreg_frames_normals_kept(const dcreg_ctx *c) { return c && c->frames.normals_kept ? 1 : 0; }
 int dcreg_normal_params_check(dcreg_ctx *c, const dcreg_normal_params *p) { return c ? normals_check(c, p) : DCREG_E_INVALID; }
 int dcreg_target_normals(dcreg_ctx *c, const dcreg_normal_params *p, float *normals_out, float *curvature_out, float *eigenvalues_out,

@@ -321,10 +321,12 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // frame takes its cloud with it, and an empty frame never takes a slot.
 // first_pair >= 0 (with frame_points): trial k is scan pair first_pair + k of dcreg_register_pairs - its source of the pairs' sources,
 // target k of the build batch dcreg_pairs_build left on the device (frame_points[k] = 0: the source or the target is empty)
-// engine: Engine::normals, the second engine (dcreg_icp_run_trials_normals, dcreg_register_frames_normals; never pairs) - the launches are
-// dcreg_normals_batch_begin / _end with their warm slots instead of the first engine's and its neighbour states; Engine::gicp, the third
-// (dcreg_icp_run_trials_gicp, dcreg_register_frames_gicp) - dcreg_gicp_batch_begin / _end on the same launch and warm slots, the frames'
-// kept normals beside the frames; everything else is shared
+// engine: Engine::normals, the second engine (dcreg_icp_run_trials_normals, dcreg_register_frames_normals, dcreg_register_pairs_normals) - the
+// launches are dcreg_normals_batch_begin / _end with their warm slots instead of the first engine's and its neighbour states; Engine::gicp,
+// the third (dcreg_icp_run_trials_gicp, dcreg_register_frames_gicp, dcreg_register_pairs_gicp) - dcreg_gicp_batch_begin / _end on the same
+// launch and warm slots, the frames' kept normals beside the frames; with pairs the begin calls are dcreg_pairs_normals_batch_begin /
+// dcreg_pairs_gicp_batch_begin (every pose against its own target and that target's kept normals) and the warm slots are sized for the
+// pairs' sources; everything else is shared
 enum class Engine { planes, normals, gicp };
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
@@ -348,17 +350,21 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
         const char *label;
     };
     typedef int (*one_nn_begin_fn)(dcreg_ctx *, int, int, const double *, const double *, const int32_t *, const int32_t *, const dcreg_lin_params *);
-    auto one_nn = [&](one_nn_begin_fn batch_begin, const char *label) {        // the launch and warm slots of normal_icp.hip, shared by both
-        return EngineCalls{[&](int n) { return dcreg_normals_reserve_slots(ctx, n, frames ? 1 : 0); },
+    typedef int (*one_nn_pairs_begin_fn)(dcreg_ctx *, int, int, const double *, const double *, const int32_t *, const int32_t *, const int32_t *,
+                                         const dcreg_lin_params *);
+    // the launch and warm slots of normal_icp.hip, shared by both 1-NN engines; pairs: the pairs' begin call, with every pose's target
+    auto one_nn = [&](one_nn_begin_fn batch_begin, one_nn_pairs_begin_fn pairs_begin, const char *label) {
+        return EngineCalls{[&](int n) { return pairs ? dcreg_pairs_normals_reserve_slots(ctx, n) : dcreg_normals_reserve_slots(ctx, n, frames ? 1 : 0); },
                            [&](int si) { dcreg_normals_reset_slot(ctx, si); },
-                           [&, batch_begin](int gi, int nl, Group &G) {
+                           [&, batch_begin, pairs_begin](int gi, int nl, Group &G) {
+                               if (pairs) return pairs_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm);
                                return batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), frames ? G.fids.data() : nullptr, &prm);
                            },
                            dcreg_normals_batch_end, label};
     };
     const EngineCalls E =
-        engine == Engine::gicp ? one_nn(dcreg_gicp_batch_begin, "_gicp")
-        : engine == Engine::normals ? one_nn(dcreg_normals_batch_begin, "_normals")
+        engine == Engine::gicp ? one_nn(dcreg_gicp_batch_begin, dcreg_pairs_gicp_batch_begin, "_gicp")
+        : engine == Engine::normals ? one_nn(dcreg_normals_batch_begin, dcreg_pairs_normals_batch_begin, "_normals")
         : pairs ? EngineCalls{[&](int n) { return dcreg_pairs_reserve_states(ctx, n); }, [&](int si) { dcreg_pairs_reset_state(ctx, si); },
                               [&](int gi, int nl, Group &G) {
                                   return dcreg_pairs_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.ids.data(), G.fids.data(), G.gids.data(), &prm);
@@ -597,10 +603,16 @@ int dcreg_register_frames_gicp(dcreg_ctx *ctx, int n_frames, const float *xyz, c
 // Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,
 // at once), the targets of the first build batch in its bounds pass and those of later batches here on the host - then every build batch
 // is indexed (dcreg_pairs_build) and its pairs run as frames do, each against its own target.
-int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
-                         const int64_t *tgt_offsets, int64_t stride_floats, const double *R0, const double *t0, int detection,
-                         int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+// (engine: the first engine, or one of the 1-NN engines - dcreg_register_pairs_normals / _gicp: their parameter blocks are checked before the
+// empty call returns, a build batch is planned with its kept normals, the sources' own normals are estimated once behind the load (the
+// third engine), and every batch's target normals behind its build)
+static int register_pairs_run(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                              const int64_t *tgt_offsets, int64_t stride_floats, const double *R0, const double *t0, int detection,
+                              int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results, Engine engine,
+                              const dcreg_normal_params *target_normals, const dcreg_normal_params *source_normals) {
     if (!ctx || !cfg || n_pairs < 0 || stride_floats < 3) return DCREG_E_INVALID;
+    if (engine != Engine::planes) if (int rc = dcreg_normal_params_check(ctx, target_normals)) return rc;
+    if (engine == Engine::gicp) if (int rc = dcreg_normal_params_check(ctx, source_normals)) return rc;
     if (n_pairs == 0) return DCREG_OK;
     if (!src_offsets || !tgt_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
     for (const int64_t *off : {src_offsets, tgt_offsets}) {
@@ -611,7 +623,7 @@ int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, cons
     if (tgt_offsets[n_pairs] > 0 && !tgt_xyz) { dcreg_set_error_message(ctx, "null target buffer"); return DCREG_E_INVALID; }
     std::vector<int32_t> ends((size_t)n_pairs);
     int n_batches = 0;
-    int rc = dcreg_pairs_plan(ctx, n_pairs, tgt_offsets, stride_floats, ends.data(), &n_batches);
+    int rc = (engine == Engine::planes ? dcreg_pairs_plan : dcreg_pairs_plan_normals)(ctx, n_pairs, tgt_offsets, stride_floats, ends.data(), &n_batches);
     if (rc != DCREG_OK) return rc;
     if (n_batches > 1) {         // (the first batch's targets are checked by its bounds pass, before anything runs)
         const int64_t first = tgt_offsets[ends[0]], n = tgt_offsets[n_pairs] - first;
@@ -625,6 +637,8 @@ int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, cons
     }
     rc = dcreg_pairs_sources_load(ctx, n_pairs, src_xyz, src_offsets, stride_floats);      // (non-finite coordinates: refused here)
     if (rc != DCREG_OK) return rc;
+    if (engine == Engine::gicp && src_offsets[n_pairs] > 0)                                 // (all sources empty: nothing to estimate, nothing to run)
+        if ((rc = dcreg_pairs_sources_normals_keep(ctx, source_normals, nullptr)) != DCREG_OK) return rc;
     std::vector<int64_t> points((size_t)n_pairs), rel;
     for (int p = 0; p < n_pairs; ++p) {
         const bool empty = src_offsets[p + 1] == src_offsets[p] || tgt_offsets[p + 1] == tgt_offsets[p];
@@ -636,10 +650,32 @@ int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, cons
         for (int p = p0; p <= p1; ++p) rel[(size_t)(p - p0)] = tgt_offsets[p] - tgt_offsets[p0];
         rc = dcreg_pairs_build(ctx, p1 - p0, tgt_xyz ? tgt_xyz + tgt_offsets[p0] * stride_floats : nullptr, rel.data(), stride_floats, cfg->search_radius);
         if (rc != DCREG_OK) return rc;
-        rc = run_trials_core(ctx, p1 - p0, R0 + 9 * (size_t)p0, t0 + 3 * (size_t)p0, detection, handling, cfg, results + p0, slots, points.data() + p0, p0);
+        if (engine != Engine::planes && (rc = dcreg_pairs_normals_keep(ctx, target_normals, nullptr)) != DCREG_OK) return rc;
+        rc = run_trials_core(ctx, p1 - p0, R0 + 9 * (size_t)p0, t0 + 3 * (size_t)p0, detection, handling, cfg, results + p0, slots, points.data() + p0, p0, engine);
         if (rc != DCREG_OK) return rc;
     }
     return DCREG_OK;
+}
+
+int dcreg_register_pairs(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                         const int64_t *tgt_offsets, int64_t stride_floats, const double *R0, const double *t0, int detection,
+                         int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    return register_pairs_run(ctx, n_pairs, src_xyz, src_offsets, tgt_xyz, tgt_offsets, stride_floats, R0, t0, detection, handling, cfg, slots, results,
+                              Engine::planes, nullptr, nullptr);
+}
+// The 1-NN engines' forms (include/dcreg.h): the same body; every batch's target normals are estimated behind its build, in one launch
+int dcreg_register_pairs_normals(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                                 const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_normal_params *target_normals, const double *R0,
+                                 const double *t0, int detection, int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    return register_pairs_run(ctx, n_pairs, src_xyz, src_offsets, tgt_xyz, tgt_offsets, stride_floats, R0, t0, detection, handling, cfg, slots, results,
+                              Engine::normals, target_normals, nullptr);
+}
+int dcreg_register_pairs_gicp(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                              const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_normal_params *target_normals,
+                              const dcreg_normal_params *source_normals, const double *R0, const double *t0, int detection, int handling,
+                              const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    return register_pairs_run(ctx, n_pairs, src_xyz, src_offsets, tgt_xyz, tgt_offsets, stride_floats, R0, t0, detection, handling, cfg, slots, results,
+                              Engine::gicp, target_normals, source_normals);
 }
 
 int dcreg_icp_run_montecarlo(dcreg_ctx *ctx, const double base_xyzrpy[6], uint64_t seed, int64_t first_trial, int64_t trial_stride,

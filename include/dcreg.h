@@ -222,7 +222,7 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
+ * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_register_pairs_normals, dcreg_register_pairs_gicp, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
  * the launches, and dcreg_debug.h's dcreg_frames_load, dcreg_normals_reserve_slots (a pending launch slot of dcreg_normals_batch_begin counts as a slot in flight), dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
@@ -1113,8 +1113,8 @@ int dcreg_icp_run(dcreg_ctx *, const double R0[9], const double t0[3], int detec
 /* The loop of dcreg_icp_run with dcreg_linearize_normals as its linearisation (the map's kept normals: dcreg_target_normals_keep / _set
  * first, DCREG_E_STATE without them): the same aborts (n_eff < 10, a non-finite step), fitness n_pt / N_src, rmse, convergence test, log
  * records, covariance and status codes, the same host step.  One pose per call; dcreg_register_frames_normals and
- * dcreg_icp_run_trials_normals (below) run many registrations in one call.  There is no pairs form (a target per pair would need
- * normals per pair), no sharded / RCCL form and no Euler form of this engine. */
+ * dcreg_icp_run_trials_normals (below) run many registrations in one call, dcreg_register_pairs_normals many pairs, each against a
+ * target of its own.  There is no sharded / RCCL form and no Euler form of this engine. */
 int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                           const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
@@ -1122,8 +1122,8 @@ int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], i
  * either): one waited launch per iteration, the same aborts, fitness, convergence test, log records, covariance and status codes, the
  * same host step.  rmse keeps its formula sqrt(sum_r2 / n_eff): here the RMS Mahalanobis distance per effective point (three whitened
  * residuals each), not a distance in metres.  Of the configuration's linearisation parameters only search_radius is read.  One pose per
- * call; dcreg_register_frames_gicp and dcreg_icp_run_trials_gicp (below) run many registrations in one call.  No pairs, sharded / RCCL
- * or Euler form of this engine. */
+ * call; dcreg_register_frames_gicp and dcreg_icp_run_trials_gicp (below) run many registrations in one call, dcreg_register_pairs_gicp
+ * many pairs, each against a target of its own.  No sharded / RCCL or Euler form of this engine. */
 int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                        const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
@@ -1215,7 +1215,7 @@ int dcreg_register_frames(dcreg_ctx *, int n_frames, const float *xyz, const int
  * normals (dcreg_target_normals_keep / _set first; every change of the map's points drops them) - results are then left untouched.  The
  * context's own source, the warm positions of dcreg_linearize_normals, the first engine's own and reserved states, the window index and
  * the kept normals are left as they were (dcreg_register_frames_normals replaces the frames a dcreg_register_frames call left on the
- * device, and the other way round).  Not available for this engine: scan pairs, the sharded / RCCL forms, the Euler form. */
+ * device, and the other way round).  Not available for this engine: the sharded / RCCL forms, the Euler form. */
 int dcreg_register_frames_normals(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                                   const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
                                   dcreg_trial_result *results);
@@ -1255,6 +1255,34 @@ int dcreg_icp_run_trials_gicp(dcreg_ctx *, int n_trials, const double *R0_9, con
 int dcreg_register_pairs(dcreg_ctx *, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
                          const int64_t *tgt_offsets, int64_t stride_floats, const double *R0_9, const double *t0_3, int detection,
                          int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
+
+/* dcreg_register_pairs for the second engine (dcreg_icp_run_normals: 1-NN rows against kept normals) and the third (dcreg_icp_run_gicp:
+ * plane-to-plane rows).  Arguments, offset rules, build batches ("pairs_max_bytes", "pair_max_table_entries"; a batch is counted with 32
+ * more bytes per target point: its kept normals and the scratch of their estimation), slots, record fields and amortised time_ms are
+ * those of dcreg_register_pairs.  target_normals: the rule every target's normals are estimated with, all targets of a build batch in ONE
+ * launch over the grids the batch already has, kept beside them for the batch; source_normals (the GICP form): the rule of the sources'
+ * own normals, estimated once per call for all sources in one batched pass.  Every iteration of a group of pairs is ONE batched launch
+ * (dcreg_debug.h: dcreg_pairs_normals_batch_begin / dcreg_pairs_gicp_batch_begin), each pose reading its own source, its own target and
+ * that target's normals.  results[p] is bitwise what a context with the same options ("gicp_epsilon" among them, read as the single call
+ * reads it) gives for dcreg_set_target(target p, cfg->search_radius) + dcreg_target_normals_keep(target_normals) + dcreg_set_source(source
+ * p) [+ dcreg_source_normals_keep(source_normals)] + dcreg_icp_run_normals / dcreg_icp_run_gicp(R0 p, t0 p): final_transform, iterations,
+ * converged, status, final_rmse, final_fitness, corr_num, H_upper and degenerate_mask; errors against cfg->gt_matrix.  An empty source or
+ * target: status 3, the other pairs run; n_pairs == 0 does nothing.  A target with fewer than k points has no normals (all NaN), and so
+ * has, in the GICP form, a source with fewer than k points: the pair runs - as the serial sequence does - and ends after one launch with
+ * status 1, iterations 1 and n_eff = 0.  DCREG_E_INVALID, before anything is queued: the refusals of dcreg_register_pairs, and those of
+ * dcreg_normals for either parameter block (checked before the n_pairs == 0 return); DCREG_E_STATE: a linearisation or a batched 1-NN
+ * launch in flight.  The calls need no target on the context and leave alone its target, kept map normals, source, kept source normals,
+ * the warm positions of the single-pose 1-NN launches, the first engine's states and reserved warm states, the loaded frames with their
+ * kept normals and the window index; they replace the pairs' sources a dcreg_register_pairs* call left on the device, and size the warm
+ * slots of the batched 1-NN launches (dcreg_debug.h: dcreg_normals_reserve_slots) for their own sources, as dcreg_register_frames_normals does for its frames. */
+int dcreg_register_pairs_normals(dcreg_ctx *, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                                 const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_normal_params *target_normals,
+                                 const double *R0_9, const double *t0_3, int detection, int handling, const dcreg_config *, int slots,
+                                 dcreg_trial_result *results);
+int dcreg_register_pairs_gicp(dcreg_ctx *, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                              const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_normal_params *target_normals,
+                              const dcreg_normal_params *source_normals, const double *R0_9, const double *t0_3, int detection,
+                              int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
 
 /* Initial pose of Monte-Carlo trial k (the reference has no RNG: its num_runs loop, icp_test_runner.cpp:339-349, repeats one
  * deterministic run; the seeded perturbation is this build's definition, shared by the runner and dcreg_amd/montecarlo.py):

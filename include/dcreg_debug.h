@@ -236,6 +236,42 @@ int dcreg_pairs_reset_state(dcreg_ctx *, int64_t state_id);
 int dcreg_pairs_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                             const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
 
+/* internal: the device seam of dcreg_register_pairs_normals and dcreg_register_pairs_gicp (engine.cpp), on top of the one above.
+ * dcreg_pairs_plan_normals is dcreg_pairs_plan with 32 more bytes per target point (a batch's kept normals, 16 B, and the scratch of their
+ * estimation).  Kept normals of the build batch dcreg_pairs_build left on the device - float4 {nx, ny, nz, curvature}, target after target,
+ * each in its own index order, target t from the batch's offset t: dcreg_pairs_normals_keep estimates them for all targets in ONE launch of
+ * the many-clouds normal kernel over the batch's own grids (no second index); target t's are bitwise dcreg_normals of that target alone,
+ * and so what dcreg_target_normals_get returns after dcreg_set_target(target t) + dcreg_target_normals_keep; a target with fewer than k
+ * points has none (NaN); infos (may be NULL): one record per target, as dcreg_normals fills it.  dcreg_pairs_normals_set stores the caller's
+ * normals as given (n_points = all points of the batch in its upload order, stride_floats >= 3 apart; curvature NaN); _get copies them
+ * out, 4 floats per point; _kept: 1 while they are kept.  Every dcreg_pairs_build drops them.  dcreg_pairs_sources_normals_keep / _set /
+ * _get are dcreg_frames_normals_keep / _set for the sources dcreg_pairs_sources_load left on the device (source p's are bitwise what
+ * dcreg_source_normals_get returns after dcreg_set_source(source p) + dcreg_source_normals_keep; _get: upload order, 4 floats per point);
+ * every dcreg_pairs_sources_load drops them.  Refusals as the dcreg_frames_normals_* calls; DCREG_E_STATE without a built batch / loaded
+ * sources.
+ * dcreg_pairs_normals_reserve_slots is dcreg_normals_reserve_slots sized for the largest pair source (slots reserved for the own source
+ * or the frames are replaced, and the other way round; dcreg_normals_reset_slot marks one empty).  dcreg_pairs_normals_batch_begin /
+ * dcreg_pairs_gicp_batch_begin are dcreg_normals_batch_begin / dcreg_gicp_batch_begin with pose i linearising source source_ids[i] against
+ * target target_ids[i] of the batch and that target's kept normals (the GICP form: and the source's kept normals); its 31 sums are bitwise
+ * what dcreg_linearize_normals / dcreg_linearize_gicp return on a context with that target, those normals and that source.  A warm slot
+ * holds positions in its pose's own target's sorted points: reset it (dcreg_normals_reset_slot) before it serves another pair - a stale
+ * word only bounds the search from a valid point or is ignored, it never decides the result.  The state refusals become: no pair batch
+ * built, no kept pair normals, no loaded pair sources and - GICP - no kept pair source normals; DCREG_E_INVALID also for a target that is
+ * not built (empty) and for a search radius other than the batch's.  Results through dcreg_normals_batch_end. */
+int dcreg_pairs_plan_normals(dcreg_ctx *, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches);
+int dcreg_pairs_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *infos);
+int dcreg_pairs_normals_set(dcreg_ctx *, const float *normals, int64_t n_points, int64_t stride_floats);
+int dcreg_pairs_normals_get(dcreg_ctx *, float *out, int64_t capacity_points);
+int dcreg_pairs_normals_kept(const dcreg_ctx *);
+int dcreg_pairs_sources_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *infos);
+int dcreg_pairs_sources_normals_set(dcreg_ctx *, const float *normals, int64_t n_points, int64_t stride_floats);
+int dcreg_pairs_sources_normals_get(dcreg_ctx *, float *out, int64_t capacity_points);
+int dcreg_pairs_normals_reserve_slots(dcreg_ctx *, int64_t n_slots);
+int dcreg_pairs_normals_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                                    const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
+int dcreg_pairs_gicp_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
+                                 const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
+
 /* Checks the whole map's index after updates (dcreg_target_insert*, dcreg_target_crop): rebuilds the current grid (same origin, cell
  * edge, dims and x sub-cells) from scratch in scratch buffers from the raw points and counts the entries that differ, bitwise:
  * mismatches[0] sorted points (kPtsPad tail included), [1] cell table, [2] row words, [3] gap field, [4] owners.  All zero = the index is
