@@ -28,6 +28,9 @@ METHODS = {
 }
 
 OK, E_INVALID, E_NOMEM, E_DEVICE, E_STATE = 0, -1, -2, -3, -4
+# DCREG_ROBUST_* of include/dcreg.h ("robust kernels": the second and third engine's rows)
+ROBUST = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3}
+ROBUST_SCALE_RANGE = (1.0e-6, 1.0e6)
 
 
 class LinParams(C.Structure):
@@ -1337,6 +1340,33 @@ class Context:
 
     def set_option(self, key, value):
         self._check(self._L.dcreg_set_option(self._h, key.encode(), float(value)), "dcreg_set_option")
+
+    def set_robust(self, kernel, scale=None, gicp_scale=None):
+        """The robust kernel of linearize_normals / linearize_gicp and of every form built on them (include/dcreg.h, "robust kernels"):
+        kernel a name of ROBUST or its code; scale: "robust_scale" (second engine, metres), gicp_scale: "gicp_robust_scale" (third engine,
+        whitened units) - None leaves a scale as it is.  Everything is checked before anything reaches the library."""
+        if isinstance(kernel, str):
+            if kernel not in ROBUST:
+                raise ValueError("set_robust: kernel: one of %s is expected, got %r" % (sorted(ROBUST), kernel))
+            code = ROBUST[kernel]
+        else:
+            if isinstance(kernel, bool) or not isinstance(kernel, (int, np.integer)) or int(kernel) not in ROBUST.values():
+                raise ValueError("set_robust: kernel: a name or code of %s is expected, got %r" % (ROBUST, kernel))
+            code = int(kernel)
+        for name, v in (("scale", scale), ("gicp_scale", gicp_scale)):
+            if v is None:
+                continue
+            try:
+                ok = ROBUST_SCALE_RANGE[0] <= float(v) <= ROBUST_SCALE_RANGE[1]
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("set_robust: %s: a finite value in [%g, %g] is expected, got %r" % ((name,) + ROBUST_SCALE_RANGE + (v,)))
+        self.set_option("robust_kernel", code)
+        if scale is not None:
+            self.set_option("robust_scale", float(scale))
+        if gicp_scale is not None:
+            self.set_option("gicp_robust_scale", float(gicp_scale))
 
     def set_target(self, xyz, search_radius):
         a = np.ascontiguousarray(xyz, dtype=np.float32)

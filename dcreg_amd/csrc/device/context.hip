@@ -2364,6 +2364,16 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
         if (!(v >= 1.0e-6 && v <= 1.0)) { c->fail("gicp_epsilon is %g: 1e-6 .. 1 expected", v); return DCREG_E_INVALID; }
         c->opt_gicp_epsilon = v;
     }
+    else if (k == "robust_kernel") {                             // dcreg_linearize_normals / _gicp and every form built on them: read at every launch
+        if (!(v == (double)DCREG_ROBUST_NONE || v == (double)DCREG_ROBUST_HUBER || v == (double)DCREG_ROBUST_CAUCHY || v == (double)DCREG_ROBUST_GEMAN_MCCLURE)) {
+            c->fail("robust_kernel is %g: 0 (none), 1 (Huber), 2 (Cauchy) or 3 (Geman-McClure) expected", v); return DCREG_E_INVALID;
+        }
+        c->opt_robust_kernel = (int)v;
+    }
+    else if (k == "robust_scale" || k == "gicp_robust_scale") {  // the kernel's scale c: metres for the second engine, whitened units for the third
+        if (!(v >= 1.0e-6 && v <= 1.0e6)) { c->fail("%s is %g: 1e-6 .. 1e6 expected", key, v); return DCREG_E_INVALID; }
+        (k == "robust_scale" ? c->opt_robust_scale : c->opt_gicp_robust_scale) = v;
+    }
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;

@@ -496,6 +496,9 @@ struct dcreg_ctx {
     };
     GicpBufs gicp;
     double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
+    int opt_robust_kernel = 0;                                 // "robust_kernel" (DCREG_ROBUST_*): the second and third engine's rows, read at every call
+    double opt_robust_scale = 0.1;                             // "robust_scale": its scale c for the second engine, metres
+    double opt_gicp_robust_scale = 1.0;                        // "gicp_robust_scale": ... for the third engine, whitened units
     double opt_visibility_max_bytes = 268435456.0;             // "visibility_max_bytes": the images of one batch of members
     int opt_visibility_order = 1;                              // the map form votes in index order (0) or in cell order (1)
     int64_t opt_pair_max_table_entries = (int64_t)1 << 24;    // "max_table_entries" of every pair target

@@ -65,14 +65,18 @@ __device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int
 // What a block does with its points once glin_point has run (k_glin and k_glin_batch): the three rows of every flag-1 point through
 // wave_gram3_mfma (the wave's RunList is free now: it stages the rows; a lane past the cloud's end or with another flag than 1 carries
 // zero rows), the wave's Gram matrix and counts in LDS, added in wave order, and the block row at `out`.  note(k, row): the dump's hook.
+// robust: the launch's kernel (GlinArgs::robust); a row is then scaled by the factor glin_point left in o.k before it is noted and staged.
 template <class Note>
-__device__ __forceinline__ void glin_block_rows(const PoseArg &P, uint8_t flag, float sx, float sy, float sz, const GlinPoint &o, RunList &rl,
+__device__ __forceinline__ void glin_block_rows(const PoseArg &P, int robust, uint8_t flag, float sx, float sy, float sz, const GlinPoint &o, RunList &rl,
                                                 double (*gm)[64], double (*cnt)[2], double *__restrict__ out, Note note) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     auto row_of = [&](int k, double (&row)[8]) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) row[j] = 0.0;
-        if (flag == 1) glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+        if (flag == 1) {
+            glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+            if (robust) glin_row_scale(o.k, row);        // (launch-uniform; with no kernel nothing is multiplied)
+        }
         note(k, row);
     };
     double u0, u1;
@@ -123,7 +127,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
             }
         }
     }
-    glin_block_rows(P, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
         if constexpr (DUMP) {
             if (i < n_src) {
                 if (d.r) d.r[3 * oi + k] = row[7];
@@ -177,15 +181,16 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin_batch(const 
         flag = glin_point(g, runs[wave], normals, P, a, s4, src_normals + i, (w && P.fresh == 0u) ? *w : kNoIdx, o);
         if (w) *w = o.pos;
     }
-    glin_block_rows(P, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, runs[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
                     [](int, const double (&)[8]) {});
 }
 
-// the launch's arguments for a search within the bound b ("gicp_epsilon" is read at every call)
+// the launch's arguments for a search within the bound b ("gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at every call)
 GlinArgs glin_args(const dcreg_ctx *c, const OneNnBound &b) {
     GlinArgs a;
     a.radius_sq = b.radius_sq; a.bound_f = b.bound_f; a.max_ring = b.max_ring;
     a.c = 1.0 - c->opt_gicp_epsilon;
+    a.robust = c->opt_robust_kernel; a.robust_c2 = c->opt_gicp_robust_scale * c->opt_gicp_robust_scale;
     return a;
 }
 

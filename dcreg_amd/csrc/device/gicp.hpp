@@ -14,6 +14,8 @@ struct GlinArgs {
     float bound_f;                // the cold search bound: the smallest float >= R^2
     int max_ring;                 // rings that cover it
     double c;                     // 1 - epsilon ("gicp_epsilon"), formed once on the host
+    int robust = 0;               // "robust_kernel" (DCREG_ROBUST_*): 0 multiplies nothing
+    double robust_c2 = 1.0;       // c * c of "gicp_robust_scale", formed once on the host
 };
 
 // what a point leaves for its rows and for the debug dump (flag 0: idx kNoIdx, d2 +inf; the normals as stored for every point that
@@ -24,13 +26,15 @@ struct GlinPoint {
     double n[3], m[3];            // the kept normal of the nearest map point, the kept normal of the source point
     double w[3][3];               // W = L^-1, lower triangular: row k is the pseudo-normal a_k
     double e[3];                  // (double)q - (double)t_j
+    double k;                     // the robust kernel's factor for the point's three rows (1 with no kernel, and unless the flag is 1)
     uint32_t n_eval;              // candidates the search evaluated (host replay)
 };
 
 // One point of dcreg_linearize_gicp up to its whitening matrix.  warm_pos: as nlin_point's - it bounds the search, never decides it.
 // normals: float4 per map point in index order; m4p: where the point's own kept normal lies (read after the two gathers, and only by a
 // point that passed the radius gate: nothing of it is live across the search).  Returns the flag (0 radius gate, 2 the nearest map
-// point has no normal, 3 the source point has none, 5 the covariance is not positive definite, 1 effective).
+// point has no normal, 3 the source point has none, 5 the covariance is not positive definite, 1 effective).  With a robust kernel on
+// (a.robust), a flag-1 point also leaves the kernel's factor at its squared whitened distance in o.k.
 DCREG_DEVFN uint8_t glin_point(const GridDev &g, RunList &rl, const float4 *normals, const PoseArg &P, const GlinArgs &a, const float4 &s4,
                                const float4 *m4p, uint32_t warm_pos, GlinPoint &o) {
 #pragma clang fp contract(off)
@@ -50,6 +54,7 @@ DCREG_DEVFN uint8_t glin_point(const GridDev &g, RunList &rl, const float4 *norm
     }
     knn_search<HeapOne>(g, rl, qx, qy, qz, bound_f, a.max_ring, hp);
     o.idx = kNoIdx; o.pos = kNoIdx; o.d2 = __builtin_inff(); o.n_eval = hp.n_eval;
+    o.k = 1.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         o.n[k] = 0.0; o.m[k] = 0.0; o.e[k] = 0.0;
@@ -98,6 +103,13 @@ DCREG_DEVFN uint8_t glin_point(const GridDev &g, RunList &rl, const float4 *norm
     o.w[1][0] = w10; o.w[1][1] = w11;
     o.w[2][0] = w20; o.w[2][1] = w21; o.w[2][2] = w22;
     o.e[0] = (double)qx - (double)tj.x; o.e[1] = (double)qy - (double)tj.y; o.e[2] = (double)qz - (double)tj.z;
+    if (a.robust) {                                                        // (launch-uniform) one factor per point, from the three residuals as glin_row forms them
+        const double r0 = (o.w[0][0] * o.e[0] + o.w[0][1] * o.e[1]) + o.w[0][2] * o.e[2];
+        const double r1 = (o.w[1][0] * o.e[0] + o.w[1][1] * o.e[1]) + o.w[1][2] * o.e[2];
+        const double r2 = (o.w[2][0] * o.e[0] + o.w[2][1] * o.e[1]) + o.w[2][2] * o.e[2];
+        const double m2 = (r0 * r0 + r1 * r1) + r2 * r2;
+        o.k = robust_factor(a.robust, m2 / a.robust_c2);
+    }
     return 1;
 }
 
@@ -114,6 +126,13 @@ DCREG_DEVFN void glin_row(const PoseArg &P, double px, double py, double pz, dou
     row[3] = m0; row[4] = m1; row[5] = m2;
     row[6] = -r;
     row[7] = r;
+}
+
+// ... with a robust kernel on: slots 0..6 times the point's factor (GlinPoint::k), slot 7 stays r_k
+DCREG_DEVFN void glin_row_scale(double k, double (&row)[8]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 7; ++j) row[j] = k * row[j];
 }
 
 }  // namespace dcreg

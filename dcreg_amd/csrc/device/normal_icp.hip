@@ -131,11 +131,12 @@ bool finite_n(const double *v, int n) {
     return true;
 }
 
-// the launch's arguments for a search within the bound b
-NlinArgs nlin_args(const OneNnBound &b, const dcreg_lin_params *p) {
+// the launch's arguments for a search within the bound b ("robust_kernel" and "robust_scale" are read at every call)
+NlinArgs nlin_args(const dcreg_ctx *c, const OneNnBound &b, const dcreg_lin_params *p) {
     NlinArgs a;
     a.radius_sq = b.radius_sq; a.bound_f = b.bound_f; a.max_ring = b.max_ring;
     a.w_slope = p->weight_slope; a.w_min = p->weight_min; a.use_wd = p->use_weight_derivative;
+    a.robust = c->opt_robust_kernel; a.robust_c2 = c->opt_robust_scale * c->opt_robust_scale;
     return a;
 }
 
@@ -147,13 +148,13 @@ int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     return one_nn_run(c, R, t, p, out, "normal", nullptr, [&](const OneNnLaunch &L) {
         const GridDev &g = c->map.grid;
         hipLaunchKernelGGL(L.dump ? k_nlin<true> : k_nlin<false>, dim3(L.nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)c->n_src, g,
-                           c->nicp.normals.data(), L.P, nlin_args(L.bound, p), L.warm_in, L.warm_out, L.partials, d);
+                           c->nicp.normals.data(), L.P, nlin_args(c, L.bound, p), L.warm_in, L.warm_out, L.partials, d);
     }, dbg != nullptr, fields, 7);
 }
 
 // the second engine's kernel for a batched launch (one_nn_batch_begin below)
 void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
-    const NlinArgs a = nlin_args(L.bound, L.p);
+    const NlinArgs a = nlin_args(c, L.bound, L.p);
     hipLaunchKernelGGL(L.grids ? k_nlin_batch<true> : k_nlin_batch<false>, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src,
                        L.g, L.normals, L.poses, L.slices, a, L.warm, L.warm_stride, L.partials, L.nbx, L.grids, L.grid_ids);
 }

@@ -31,6 +31,8 @@ struct NlinArgs {
     int max_ring;                 // rings that cover it
     double w_slope, w_min;
     int use_wd;
+    int robust = 0;               // "robust_kernel" (DCREG_ROBUST_*): 0 multiplies nothing
+    double robust_c2 = 1.0;       // c * c of "robust_scale", formed once on the host
 };
 
 // what the debug dump shows of a point (flag 0: idx kNoIdx, d2 +inf; no normal: NaN components as stored)
@@ -41,13 +43,26 @@ struct NlinPoint {
     uint32_t n_eval;              // candidates the search evaluated (host replay)
 };
 
+// The robust kernels of the second and third engine (include/dcreg.h, "robust kernels"): k = sqrt(rho'(r) / r) of the kernel `kind` (1 Huber,
+// 2 Cauchy, 3 Geman-McClure) at u2 = (r / c)^2.  Every operation rounds once; division and square root are IEEE double.
+DCREG_DEVFN double robust_factor(int kind, double u2) {
+#pragma clang fp contract(off)
+    if (kind == 1) {
+        const double u = sqrt(u2);
+        return u <= 1.0 ? 1.0 : sqrt(1.0 / u);
+    }
+    if (kind == 2) return 1.0 / sqrt(1.0 + u2);
+    return 1.0 / (1.0 + u2);
+}
+
 DCREG_DEVFN bool nlin_finite(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 
 // One point of dcreg_linearize_normals.  warm_pos: the sorted position of the point's nearest neighbour at its last search (kNoIdx, or
 // anything beyond the map: none) - the search then starts bounded by that point's distance from the new position, inclusive: the point
 // itself is a candidate inside the bound, so the minimum key over the bounded candidates is the minimum over the map - the result does
 // not depend on warm_pos.  normals: float4 {nx, ny, nz, curvature} per map point in index order.  Returns the flag (0 radius gate, 2 no
-// normal, 4 weight gate, 1 effective); the row is zero unless the flag is 1.
+// normal, 4 weight gate, 1 effective); the row is zero unless the flag is 1.  With a robust kernel on, slots 0..6 of a flag-1 row are
+// multiplied by the kernel's factor at r; slot 7 stays r.
 DCREG_DEVFN uint8_t nlin_point(const GridDev &g, RunList &rl, const float4 *normals, const PoseArg &P, const NlinArgs &a, const float4 &s4,
                                uint32_t warm_pos, double (&row)[8], NlinPoint &o) {
 #pragma clang fp contract(off)
@@ -95,6 +110,11 @@ DCREG_DEVFN uint8_t nlin_point(const GridDev &g, RunList &rl, const float4 *norm
     row[3] = w * m0; row[4] = w * m1; row[5] = w * m2;
     row[6] = -(s * r);
     row[7] = r;
+    if (a.robust) {                                                        // (launch-uniform) after the gathers: nothing of it is live across the search
+        const double k = robust_factor(a.robust, (r * r) / a.robust_c2);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) row[j] = k * row[j];
+    }
     return 1;
 }
 

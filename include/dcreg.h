@@ -177,6 +177,15 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   recomputes all of them instead (the results do not depend on it);
  *   "gicp_epsilon"  default 1e-3 (1e-6 .. 1, DCREG_E_INVALID outside): the small eigenvalue of both plane covariances of
  *                   dcreg_linearize_gicp; read at the time of every linearisation;
+ *   "robust_kernel" default 0 = DCREG_ROBUST_NONE; DCREG_ROBUST_HUBER (1), DCREG_ROBUST_CAUCHY (2), DCREG_ROBUST_GEMAN_MCCLURE (3).  The
+ *                   robust kernel of dcreg_linearize_normals and dcreg_linearize_gicp and of every form built on them ("robust
+ *                   kernels" below); any other value - a non-integer, a value that is not finite - is DCREG_E_INVALID and the old
+ *                   value stays.  Read at the time of every linearisation: at the call for a single-pose launch, at *_batch_begin
+ *                   for a batched one;
+ *   "robust_scale"  default 0.1 (1e-6 .. 1e6, DCREG_E_INVALID outside or not finite, the old value stays): the kernel's scale c for
+ *                   dcreg_linearize_normals, in metres; read with "robust_kernel";
+ *   "gicp_robust_scale" default 1.0 (same range, same refusal): the kernel's scale c for dcreg_linearize_gicp, in whitened
+ *                   (Mahalanobis) units; read with "robust_kernel".  Both defaults are starting values: nobody has tuned them;
  *   "visibility_max_bytes" default 2^28 (256 MiB): device bytes the range images of one batch of members may take in the visibility
  *                   calls (a batch always holds at least one image; the results do not depend on it);
  *   "roi_index", "roi_margin": the WINDOW index of a large map.  A map whose table ran into that budget is searched through cells that
@@ -1034,6 +1043,44 @@ int dcreg_source_normals_get_device(dcreg_ctx *, float *d_out, int64_t capacity_
 int dcreg_source_normals_kept(const dcreg_ctx *);
 int dcreg_source_normals_drop(dcreg_ctx *);
 int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
+/* ---------------- robust kernels (second and third engine) ----------------
+ * dcreg_linearize_normals weights a correspondence by the reference's s = 1 - weight_slope*|r| alone, dcreg_linearize_gicp by nothing:
+ * a wrong correspondence inside the radius gate - a parked car that has moved, the part of a loop-closure pair that does not overlap -
+ * enters nearly or entirely in full.  The option "robust_kernel" turns each row of those two linearisations into a row of iteratively
+ * reweighted least squares: it is multiplied by k = sqrt(rho'(r) / r) of the chosen kernel rho at the correspondence's residual, so that
+ * H and g are the kernel's weighted sums.  k is a constant of the iteration: no derivative of k enters the row.
+ *
+ * The rule.  kind = "robust_kernel", c = "robust_scale" (second engine) or "gicp_robust_scale" (third engine) at the time of the
+ * linearisation; c2 = c * c, formed once on the host in double.  Every operation rounds once in double (no contraction); division
+ * and square root are IEEE double.  factor(kind, u2):
+ *   - DCREG_ROBUST_HUBER:          u = sqrt(u2); k = 1 if u <= 1, else k = sqrt(1 / u);
+ *   - DCREG_ROBUST_CAUCHY:         k = 1 / sqrt(1 + u2);
+ *   - DCREG_ROBUST_GEMAN_MCCLURE:  k = 1 / (1 + u2).
+ * dcreg_linearize_normals: flags, r, s, ds and w exactly as without a kernel - the gates do not change, so n_eff and n_pt at a pose
+ * do not change.  For a flag-1 point with the row [A0..A5, b, r]: u2 = (r * r) / c2; k = factor(kind, u2); the row becomes
+ * [k*A0, .., k*A5, k*b, r] - each of the seven products one more rounding on the value of the rule above.  Slot 7 stays r: sum_r2,
+ * and with it the rmse, keeps its geometric meaning; sum_b2 is the sum of the scaled b squared.
+ * dcreg_linearize_gicp: with the three residuals r_0, r_1, r_2 of a flag-1 point (r_k as the rule above forms it):
+ * m2 = (r_0*r_0 + r_1*r_1) + r_2*r_2 (the squared Mahalanobis distance); u2 = m2 / c2; ONE k = factor(kind, u2) per point.  Slots
+ * 0..6 of all three rows are multiplied by k; slot 7 stays r_k.
+ * DCREG_ROBUST_NONE: nothing is multiplied - every call returns the bytes it returned before the option existed.
+ *
+ * Every form of the two engines follows the three options without a new entry point: dcreg_linearize_normals / _gicp,
+ * dcreg_icp_run_normals / _gicp, dcreg_icp_run_trials_normals / _gicp, dcreg_register_frames_normals / _gicp,
+ * dcreg_register_pairs_normals / _gicp and the *_batch_begin calls of dcreg_debug.h.  The engines' host steps, logs, covariance,
+ * aborts and convergence test are untouched; H_upper of a log or a record is the SCALED Hessian (the kernel's weights are in it).
+ * The batched forms stay bitwise their serial sequence - the one run on a context with the same three option values.  The debug
+ * dumps (dcreg_debug.h) keep their layout: `row` is the scaled row, and r (and s) beside it are enough to check k.
+ * The FIRST engine (dcreg_linearize, dcreg_icp_run, dcreg_register_frames, dcreg_register_pairs, ...), the Euler form and the
+ * sharded forms do not read these options: their weight is the reference's.  Not provided: redescending kernels (Tukey), scales
+ * estimated from the data (MAD), graduated non-convexity, a scale per pair in the pairs form.
+ * The default scales (0.1 m, 1.0) are starting values that nobody has tuned: a scale near the noise of a good correspondence leaves
+ * the inliers at k close to 1. */
+#define DCREG_ROBUST_NONE 0
+#define DCREG_ROBUST_HUBER 1
+#define DCREG_ROBUST_CAUCHY 2
+#define DCREG_ROBUST_GEMAN_MCCLURE 3
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */

@@ -212,7 +212,8 @@ int dcreg_normals_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
  * dcreg_normals_reserve_slots (both engines look for the same nearest point; the word bounds the search and decides nothing).  Pose i
  * linearises frame frame_ids[i] with that frame's kept normals or, frame_ids == NULL, the context's own source with its kept source
  * normals; its 31 sums are bitwise what dcreg_set_source(that cloud) + dcreg_source_normals_keep / _set + dcreg_linearize_gicp(pose i)
- * return.  "gicp_epsilon" is read at _begin.  Two more DCREG_E_STATE refusals: no kept frame normals (frame_ids given), no kept source
+ * return.  "gicp_epsilon" is read at _begin, and so are "robust_kernel" and "gicp_robust_scale" ("robust_kernel" and "robust_scale" by
+ * dcreg_normals_batch_begin and dcreg_pairs_normals_batch_begin): dcreg.h, "robust kernels".  Two more DCREG_E_STATE refusals: no kept frame normals (frame_ids given), no kept source
  * normals (frame_ids == NULL).  dcreg_normal_params_check: the parameter refusals of dcreg_normals on their own (DCREG_OK: none). */
 int dcreg_frames_normals_keep(dcreg_ctx *, const dcreg_normal_params *, dcreg_normal_info *infos);
 int dcreg_frames_normals_set(dcreg_ctx *, const float *normals, int64_t n_points, int64_t stride_floats);
