@@ -64,6 +64,20 @@ class GlinDebug(C.Structure):      # dcreg_glin_debug: the per-point dump of dcr
                 ("r", C.POINTER(C.c_double)), ("row", C.POINTER(C.c_double))]
 
 
+class VlinDebug(C.Structure):      # dcreg_vlin_debug: the per-point dump of dcreg_linearize_voxels_debug
+    _fields_ = [("voxel_idx", C.POINTER(C.c_int32)), ("flag", C.POINTER(C.c_uint8)), ("mean", C.POINTER(C.c_double)),
+                ("cov", C.POINTER(C.c_double)), ("normal_src", C.POINTER(C.c_double)), ("w", C.POINTER(C.c_double)),
+                ("r", C.POINTER(C.c_double)), ("row", C.POINTER(C.c_double))]
+
+
+class VoxelMapParams(C.Structure):     # dcreg_voxel_map_params
+    _fields_ = [("leaf", C.c_double), ("epsilon", C.c_double), ("min_points", C.c_int), ("reserved_", C.c_int)]
+
+
+class VoxelMapInfo(C.Structure):       # dcreg_voxel_map_info
+    _fields_ = [("n_points", C.c_int64), ("n_voxels", C.c_int64), ("n_small", C.c_int64), ("n_degenerate", C.c_int64), ("n_kept", C.c_int64)]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("poses", C.c_int64), ("points", C.c_int64), ("points_searched", C.c_int64),
                 ("points_team", C.c_int64)]
@@ -138,7 +152,8 @@ _STRUCTS = {"dcreg_lin_params": LinParams, "dcreg_lin_out": LinOut, "dcreg_lin_d
             "dcreg_index_info": IndexInfo, "dcreg_config": Config, "dcreg_analysis": Analysis,
             "dcreg_iter_log": IterLog, "dcreg_icp_result": IcpResult, "dcreg_trial_result": TrialResult,
             "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats, "dcreg_nlin_debug": NlinDebug,
-            "dcreg_glin_debug": GlinDebug}
+            "dcreg_glin_debug": GlinDebug, "dcreg_vlin_debug": VlinDebug, "dcreg_voxel_map_params": VoxelMapParams,
+            "dcreg_voxel_map_info": VoxelMapInfo}
 # (VoxelParams / VoxelInfo are defined below and join _STRUCTS there)
 
 # every symbol include/dcreg.h and include/dcreg_debug.h declare
@@ -187,6 +202,8 @@ EXPORTS = [
     "dcreg_register_pairs_normals", "dcreg_register_pairs_gicp", "dcreg_pairs_plan_normals", "dcreg_pairs_normals_keep", "dcreg_pairs_normals_set",
     "dcreg_pairs_normals_get", "dcreg_pairs_normals_kept", "dcreg_pairs_sources_normals_keep", "dcreg_pairs_sources_normals_set",
     "dcreg_pairs_sources_normals_get", "dcreg_pairs_normals_reserve_slots", "dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin",
+    "dcreg_default_voxel_map_params", "dcreg_target_voxels_keep", "dcreg_target_voxels_get", "dcreg_target_voxels_kept", "dcreg_target_voxels_drop",
+    "dcreg_linearize_voxels", "dcreg_linearize_voxels_debug", "dcreg_icp_run_voxels",
 ]
 
 _lib = None
@@ -236,10 +253,14 @@ def _method(method, what=None):
 
 
 # the per-point dumps of linearize_normals / linearize_gicp: (key, dtype, shape per point) of every array of the C struct
-_DUMP_FILL = {"nn_idx": -1, "nn_d2": np.inf}
+_DUMP_FILL = {"nn_idx": -1, "nn_d2": np.inf, "voxel_idx": -1}
 _NLIN_DUMP = [("nn_idx", np.int32, ()), ("nn_d2", np.float32, ()), ("flag", np.uint8, ()), ("normal", np.float64, (3,)), ("r", np.float64, ()),
               ("s", np.float64, ()), ("row", np.float64, (8,))]
 _GLIN_DUMP = [("nn_idx", np.int32, ()), ("nn_d2", np.float32, ()), ("flag", np.uint8, ()), ("normal_map", np.float64, (3,)),
+              ("normal_src", np.float64, (3,)), ("w", np.float64, (3, 3)), ("r", np.float64, (3,)), ("row", np.float64, (3, 8))]
+
+
+_VLIN_DUMP = [("voxel_idx", np.int32, ()), ("flag", np.uint8, ()), ("mean", np.float64, (3,)), ("cov", np.float64, (6,)),
               ("normal_src", np.float64, (3,)), ("w", np.float64, (3, 3)), ("r", np.float64, (3,)), ("row", np.float64, (3, 8))]
 
 
@@ -712,6 +733,27 @@ def normal_params(k=5, search_radius=0.0, viewpoint=(0.0, 0.0, 0.0)):
     return p
 
 
+def _check_voxel_map_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_voxel_map_params block"""
+    if not isinstance(p, VoxelMapParams):
+        raise ValueError("%s: voxel_map_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not (np.isfinite(p.leaf) and p.leaf > 0.0):
+        raise ValueError("%s: a finite leaf > 0 is expected, got %r" % (what, p.leaf))
+    if not 1.0e-6 <= p.epsilon <= 1.0:
+        raise ValueError("%s: an epsilon in [1e-6, 1] is expected, got %r" % (what, p.epsilon))
+    if p.min_points < 2:
+        raise ValueError("%s: min_points >= 2 is expected, got %d" % (what, p.min_points))
+
+
+def voxel_map_params(leaf=1.0, epsilon=1.0e-3, min_points=6):
+    """dcreg_voxel_map_params: the voxel edge in metres, the floor of the normalised eigenvalues, and the points a voxel needs to be kept
+    (include/dcreg.h has the rule)"""
+    p = VoxelMapParams()
+    p.leaf, p.epsilon, p.min_points, p.reserved_ = float(leaf), float(epsilon), int(min_points), 0
+    _check_voxel_map_params(p, "voxel_map_params")
+    return p
+
+
 def _normal_info_dict(i):
     return {"n_in": i.n_in, "n_finite": i.n_finite, "n_sparse": i.n_sparse, "n_out": i.n_out}
 
@@ -1122,6 +1164,15 @@ def load():
         L.dcreg_linearize_gicp.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
         L.dcreg_linearize_gicp_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(GlinDebug)]
         L.dcreg_icp_run_gicp.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
+    if hasattr(L, "dcreg_linearize_voxels"):  # (likewise)
+        L.dcreg_default_voxel_map_params.argtypes = [C.POINTER(VoxelMapParams)]
+        L.dcreg_target_voxels_keep.argtypes = [vp, C.POINTER(VoxelMapParams), C.POINTER(VoxelMapInfo)]
+        L.dcreg_target_voxels_get.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
+        L.dcreg_target_voxels_kept.argtypes = [vp]
+        L.dcreg_target_voxels_drop.argtypes = [vp]
+        L.dcreg_linearize_voxels.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
+        L.dcreg_linearize_voxels_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(VlinDebug)]
+        L.dcreg_icp_run_voxels.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
     if hasattr(L, "dcreg_register_frames_gicp"):  # (likewise)
         np_, ni = C.POINTER(NormalParams), C.POINTER(NormalInfo)
         for name in ("dcreg_normals_clouds", "dcreg_normals_clouds_device"):
@@ -2054,6 +2105,70 @@ class Context:
         """dcreg_icp_run_gicp: icp_run_normals's loop around linearize_gicp -> (result, logs); a log's rmse is the RMS Mahalanobis distance
         per effective point"""
         return self._run_logged("dcreg_icp_run_gicp", T0, method, cfg, log_capacity, "icp_run_gicp")
+
+    # ---- the kept voxel map and the fourth engine (include/dcreg.h: dcreg_target_voxels_keep .. dcreg_icp_run_voxels)
+    def keep_target_voxels(self, params=None):
+        """dcreg_target_voxels_keep: one Gaussian per voxel of the map (voxel_map_params(leaf, epsilon, min_points)) stays on the device
+        for linearize_voxels and icp_run_voxels.  -> info dict n_points / n_voxels / n_small / n_degenerate / n_kept"""
+        p = params if params is not None else voxel_map_params()
+        _check_voxel_map_params(p, "keep_target_voxels")
+        info = VoxelMapInfo()
+        self._check(self._L.dcreg_target_voxels_keep(self._h, C.byref(p), C.byref(info)), "dcreg_target_voxels_keep")
+        return {k: int(getattr(info, k)) for k, _ in VoxelMapInfo._fields_}
+
+    def target_voxels_kept(self):
+        """dcreg_target_voxels_kept: the number of kept voxels, 0 without a member"""
+        return int(self._L.dcreg_target_voxels_kept(self._h))
+
+    def drop_target_voxels(self):
+        self._check(self._L.dcreg_target_voxels_drop(self._h), "dcreg_target_voxels_drop")
+
+    def kept_target_voxels(self):
+        """dcreg_target_voxels_get: the kept voxels in ascending (z, y, x) order -> dict coords [V, 3] int64 (absolute voxel coordinates),
+        count [V] int32, mean [V, 3] float32, cov [V, 6] float32 (xx xy xz yy yz zz)"""
+        n = self.target_voxels_kept()
+        m = max(n, 1)
+        coords, count = np.zeros((m, 3), np.int64), np.zeros(m, np.int32)
+        mean, cov = np.zeros((m, 3), np.float32), np.zeros((m, 6), np.float32)
+        self._check(self._L.dcreg_target_voxels_get(self._h, coords.ctypes.data, count.ctypes.data, mean.ctypes.data, cov.ctypes.data, n),
+                    "dcreg_target_voxels_get")
+        return {"coords": coords[:n], "count": count[:n], "mean": mean[:n], "cov": cov[:n]}
+
+    @staticmethod
+    def _vlin_params(params, what):
+        params = params if params is not None else default_lin_params()
+        if not isinstance(params, LinParams):
+            raise ValueError("%s: a default_lin_params(...) block is expected" % what)
+        if params.parameterization != 0:
+            raise ValueError("%s: parameterization must be SO3 (0), got %d" % (what, params.parameterization))
+        return params
+
+    def linearize_voxels(self, T, params=None, debug=False):
+        """dcreg_linearize_voxels at the pose T (4 x 4): three whitened rows per source point that falls into a kept voxel (include/dcreg.h
+        has the rule; of params only the parameterization is read; set_option("voxels_source_cov", 1) adds the source's plane covariance)
+        -> dict as linearize(); debug=True adds the per-point dump in source order: voxel_idx, flag, mean [n, 3], cov [n, 6],
+        normal_src [n, 3], w [n, 3, 3], r [n, 3], row [n, 3, 8]."""
+        what, symbol = "linearize_voxels", "dcreg_linearize_voxels"
+        params = self._vlin_params(params, what)
+        R, t = _pose_arg(T, what)
+        out = LinOut()
+        if not debug:
+            self._check(self._L.dcreg_linearize_voxels(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), symbol)
+            return self._out_dict(out)
+        keep, dbg = _dump_arg(self.index_info().n_source, _VLIN_DUMP, VlinDebug)
+        self._check(self._L.dcreg_linearize_voxels_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)), symbol + "_debug")
+        d = self._out_dict(out)
+        d.update(keep)
+        return d
+
+    def linearize_voxels_debug(self, T, params=None):
+        """linearize_voxels(T, params, debug=True)"""
+        return self.linearize_voxels(T, params, debug=True)
+
+    def icp_run_voxels(self, T0, method, cfg, log_capacity=None):
+        """dcreg_icp_run_voxels: icp_run_gicp's loop around linearize_voxels -> (result, logs); a log's rmse is the RMS Mahalanobis
+        distance per effective point"""
+        return self._run_logged("dcreg_icp_run_voxels", T0, method, cfg, log_capacity, "icp_run_voxels")
 
     # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
     def keyframes_reset(self):

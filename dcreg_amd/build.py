@@ -29,10 +29,11 @@ SOURCES = [
     "device/normals.hip",
     "device/normal_icp.hip",
     "device/gicp.hip",
+    "device/voxel_icp.hip",
     "host/solver.cpp",
     "host/engine.cpp",
 ]
-HEADERS = ["device/kernels.hpp", "device/search.hpp", "device/context.hpp", "device/normal_icp.hpp", "device/gicp.hpp", "host/linalg.hpp", "host/se3.hpp",
+HEADERS = ["device/kernels.hpp", "device/search.hpp", "device/context.hpp", "device/normal_icp.hpp", "device/gicp.hpp", "device/voxel_icp.hpp", "device/jacobi.hpp", "host/linalg.hpp", "host/se3.hpp",
            "../../include/dcreg_debug.h", "../../include/dcreg.h"]
 
 

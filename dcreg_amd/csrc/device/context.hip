@@ -464,6 +464,7 @@ static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double ra
     if (rc) { m.n = 0; return rc; }
     drop_warm(c);            // positions and certificates refer to the old target
     c->nicp.kept = false;    // ... and the kept normals to the old map's points
+    c->vmap.kept = false;    // ... and the kept voxel map
     c->nicp.follow = dcreg_normals_follow_info{};      // (a new map: no update of it yet)
     c->order_valid = false;  // ... and the cost estimate of the query groups to the old map
     c->last_pose_valid = false;
@@ -487,6 +488,7 @@ static void map_changed(dcreg_ctx *c) {
     c->roi_built = false;
     drop_warm(c);
     c->nicp.kept = false;                              // (an update that follows them puts them back: normals.hip normals_follow_update)
+    c->vmap.kept = false;                              // (nothing follows the map: the voxel map goes)
     c->nicp.follow = dcreg_normals_follow_info{c->map.n, 0, 0, 0, 0};
     c->order_valid = false;
     c->last_pose_valid = false;
@@ -2373,6 +2375,10 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "robust_scale" || k == "gicp_robust_scale") {  // the kernel's scale c: metres for the second engine, whitened units for the third
         if (!(v >= 1.0e-6 && v <= 1.0e6)) { c->fail("%s is %g: 1e-6 .. 1e6 expected", key, v); return DCREG_E_INVALID; }
         (k == "robust_scale" ? c->opt_robust_scale : c->opt_gicp_robust_scale) = v;
+    }
+    else if (k == "voxels_source_cov") {                         // dcreg_linearize_voxels: 0 point-to-distribution, 1 distribution-to-distribution, read at every call
+        if (!(v == 0.0 || v == 1.0)) { c->fail("voxels_source_cov is %g: 0 or 1 expected", v); return DCREG_E_INVALID; }
+        c->opt_voxels_source_cov = (int)v;
     }
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }

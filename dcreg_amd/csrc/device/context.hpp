@@ -495,6 +495,26 @@ struct dcreg_ctx {
         DevBuf<float4> tmp;
     };
     GicpBufs gicp;
+    // the kept voxel map and the fourth engine (voxel.hip: dcreg_target_voxels_keep / _get / _kept / _drop; voxel_icp.hip:
+    // dcreg_linearize_voxels).  recs: 3 float4 per kept voxel in _get order (ascending z y x) - {mu, cxx} {cxy cxz cyy cyz} {czz, n as a
+    // word, 0, 0}; vkeys: each one's key, (v - mn) per axis in 21 bits (what _get turns back into coordinates); t_keys / t_vals: the
+    // open-addressing table a lookup probes (voxel_icp.hpp VoxMapDev), mask + 1 slots; mn / mx: the voxel box of all map points.  Dropped
+    // with every change of the map's points (context.hip target_commit, map_changed).  tmp / cls: scratch of a keep - the records of all
+    // voxels before compaction, and the counts [0] small [1] degenerate.  The engine's block rows, result row and dump block are nicp's
+    // (the single-pose launches of the engines never overlap)
+    struct VoxelMapBufs {
+        DevBuf<float4> recs, tmp;
+        DevBuf<uint64_t> vkeys, t_keys;
+        DevBuf<uint32_t> t_vals;
+        DevBuf<unsigned long long> cls;
+        bool kept = false;
+        int64_t n_kept = 0;
+        uint32_t mask = 0;
+        long long mn[3] = {}, mx[3] = {};
+        double leaf = 0.0;
+    };
+    VoxelMapBufs vmap;
+    int opt_voxels_source_cov = 0;                             // "voxels_source_cov": 0 point-to-distribution, 1 distribution-to-distribution, read at every call
     double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
     int opt_robust_kernel = 0;                                 // "robust_kernel" (DCREG_ROBUST_*): the second and third engine's rows, read at every call
     double opt_robust_scale = 0.1;                             // "robust_scale": its scale c for the second engine, metres
@@ -761,6 +781,9 @@ struct VoxelResult {
 };
 int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
                bool packed, VoxelResult &r, DeskewRun *dsk = nullptr, const GatherRun *gat = nullptr);
+// voxel.hip: the kept voxel map of the whole map's points (dcreg_target_voxels_keep): every refusal of include/dcreg.h, then the pass's
+// keying and sort, one lane per voxel for the records, the compaction and the lookup table; info may be null
+int voxel_map_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_map_info *info);
 // voxel.hip: dcreg_voxel_downsample* (and dcreg_deskew* with a voxel block): the pass, then the copy of the output to the caller
 int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off, int64_t stride, bool on_device, const dcreg_voxel_params *p,
                         float *out, int64_t capacity, int64_t *out_off, dcreg_voxel_info *info, DeskewRun *dsk = nullptr);

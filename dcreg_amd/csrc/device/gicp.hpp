@@ -2,8 +2,9 @@
 // normals AND the source's own - transform, exact 1-NN on the cell grid, radius gate (all three nlin_point's), then the plane-to-plane
 // covariance of the pair formed from the two normals in registers, its Cholesky factor, the whitening matrix W = L^-1 and the three
 // point-to-plane rows whose pseudo-normals are W's rows.  The rule is the header's, operation by operation; tests/gicp_ref.py states
-// it in numpy.  Included by gicp.hip (the kernel and the reduction) and, like normal_icp.hpp, compiled for the host under
-// DCREG_HOST_EMUL by the test suite's replay (tests/host_emul/).
+// it in numpy.  Included by gicp.hip (the kernels) and, like normal_icp.hpp, compiled for the host under DCREG_HOST_EMUL by the test
+// suite's replay (tests/host_emul/).  The device-only part at the end is the block tail of the engines with three rows per point
+// (wave_gram3_mfma, glin_block_rows), shared with voxel_icp.hip.
 #pragma once
 #include "normal_icp.hpp"
 
@@ -134,5 +135,75 @@ DCREG_DEVFN void glin_row_scale(double k, double (&row)[8]) {
 #pragma unroll
     for (int j = 0; j < 7; ++j) row[j] = k * row[j];
 }
+
+#if !defined(DCREG_HOST_EMUL)
+// ---- the block tail of the engines with three rows per point (gicp.hip k_glin / k_glin_batch, voxel_icp.hip k_vlin): device only
+}  // namespace dcreg
+#include "kernels.hpp"
+namespace dcreg {
+
+// wave_gram_mfma (kernels.hpp) for three rows per lane: pass k stages row_of(k) of all 64 lanes and runs the 8 MFMA steps on the
+// accumulator the pass before left, then the two DPP adds - the Gram matrix of the wave's 192 rows, summed in the fixed order (pass,
+// step).  The rows of a pass are built just before it.  A pass's operand reads are other lanes' stores: within the wave the LDS
+// executes in program order, and the wavefront fences keep the compiler from moving a pass's stores above the reads of the pass before
+// (or its reads above its own stores).  Returns u0 / u1 as wave_gram_mfma does.
+template <class RowOf>
+__device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int lane, double &u0, double &u1) {
+    const int c16 = lane & 15, k = lane >> 4;
+    const double *op = stage + (2 * k + (c16 >> 3)) * kRowStride + (c16 & 7);
+    mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        double row[8];
+        row_of(pass, row);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // the reads of the pass before are over
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int c = 0; c < 8; ++c) stage[lane * kRowStride + c] = row[c];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // every lane's row is staged
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb) {
+            const double x = op[kb * 8 * kRowStride];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
+        }
+    }
+    const bool even = c16 < 8;
+    u0 = even ? acc[0] : acc[2];
+    u1 = even ? acc[1] : acc[3];
+    u0 = dpp_add<0x128, 0xF>(u0);      // row_ror:8 - the lane holding the other half's block entry
+    u1 = dpp_add<0x128, 0xF>(u1);
+}
+
+// What a block does with its points once glin_point has run (k_glin and k_glin_batch): the three rows of every flag-1 point through
+// wave_gram3_mfma (stage: the wave's staging area of kWave * kRowStride doubles - a RunList that is free now serves; a lane past the cloud's end or with another flag than 1 carries
+// zero rows), the wave's Gram matrix and counts in LDS, added in wave order, and the block row at `out`.  note(k, row): the dump's hook.
+// robust: the launch's kernel (GlinArgs::robust); a row is then scaled by the factor glin_point left in o.k before it is noted and staged.
+template <class Note>
+__device__ __forceinline__ void glin_block_rows(const PoseArg &P, int robust, uint8_t flag, float sx, float sy, float sz, const GlinPoint &o, double *stage,
+                                                double (*gm)[64], double (*cnt)[2], double *__restrict__ out, Note note) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    auto row_of = [&](int k, double (&row)[8]) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) row[j] = 0.0;
+        if (flag == 1) {
+            glin_row(P, (double)sx, (double)sy, (double)sz, o.w[k][0], o.w[k][1], o.w[k][2], o.e[0], o.e[1], o.e[2], row);
+            if (robust) glin_row_scale(o.k, row);        // (launch-uniform; with no kernel nothing is multiplied)
+        }
+        note(k, row);
+    };
+    double u0, u1;
+    wave_gram3_mfma(row_of, stage, lane, u0, u1);
+    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
+    if ((lane & 15) < 8) {
+        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
+        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
+    }
+    const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
+    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
+    __syncthreads();
+    if (threadIdx.x < kSlots) out[threadIdx.x] = block_slot_sum(&gm[0][0], 64, cnt);
+}
+#endif  // !DCREG_HOST_EMUL
 
 }  // namespace dcreg

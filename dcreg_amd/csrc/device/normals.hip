@@ -19,6 +19,7 @@
 
 #include "../../../include/dcreg_debug.h"
 #include "context.hpp"
+#include "jacobi.hpp"
 
 // every multiply and add below rounds once: the rule is stated operation by operation
 #pragma clang fp contract(off)
@@ -69,29 +70,6 @@ struct NrmArgs {
     double vx, vy, vz;
     int orient;
 };
-
-// one Jacobi rotation of the pair (p, q), r the third index: the header's formulas, in its order
-DCREG_DEVFN void jacobi_rot(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p, double &v0q, double &v1p,
-                            double &v1q, double &v2p, double &v2q) {
-    double t = 0.0;
-    if (apq != 0.0) {
-        const double theta = (aqq - app) / (2.0 * apq);
-        t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    }
-    const double c = 1.0 / sqrt(t * t + 1.0);
-    const double s = t * c;
-    const double tp = t * apq;
-    app = app - tp;
-    aqq = aqq + tp;
-    apq = 0.0;
-    const double rp = arp, rq = arq;
-    arp = c * rp - s * rq;
-    arq = s * rp + c * rq;
-    const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
-    v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
-    v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
-    v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
-}
 
 static __global__ void k_nrm_fill(float *__restrict__ a, int64_t n, float v) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -22,6 +22,8 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "context.hpp"
+#include "jacobi.hpp"
+#include "voxel_icp.hpp"
 
 namespace dcreg {
 namespace {
@@ -260,6 +262,102 @@ static __global__ void __launch_bounds__(kVoxBlock) k_vox_write(const float4 *__
     }
 }
 
+// ---- the kept voxel map (dcreg_target_voxels_keep): k_vox_reduce's shape with the second pass, the eigen-solve and the clamp.  ONE lane
+// per voxel: its points are ord[start[v] .. start[v + 1]) in index order, so the sums are left to right; a call pays for its fullest voxel.
+// rec: 3 float4 per voxel (context.hpp VoxelMapBufs), written for the kept ones; keep[v] = 1 for those.  cls[0] += voxels below
+// min_points, cls[1] += degenerate ones (one atomic pair per wave).  The rule is the header's, operation by operation.
+static __global__ void __launch_bounds__(kVoxBlock) k_vmap_reduce(const float4 *__restrict__ pts, const uint32_t *__restrict__ ord, int64_t n_vox,
+                                                                  const uint32_t *__restrict__ start, int min_points, double eps,
+                                                                  float4 *__restrict__ rec, uint32_t *__restrict__ keep,
+                                                                  unsigned long long *__restrict__ cls) {
+#pragma clang fp contract(off)
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool small = false, degenerate = false;
+    if (v < n_vox) {
+        const uint32_t b = start[v], e = start[v + 1];
+        small = (int64_t)(e - b) < (int64_t)min_points;
+        bool k = false;
+        if (!small) {
+            const float4 p0 = pts[ord[b]];
+            double sx = p0.x, sy = p0.y, sz = p0.z;
+            for (uint32_t j = b + 1; j < e; ++j) {
+                const float4 p = pts[ord[j]];
+                sx += (double)p.x; sy += (double)p.y; sz += (double)p.z;
+            }
+            const double m = (double)(e - b);
+            const double mx = sx / m, my = sy / m, mz = sz / m;
+            // (-0.0 is the identity of the IEEE addition: the sums start with their first term)
+            double cxx = -0.0, cxy = -0.0, cxz = -0.0, cyy = -0.0, cyz = -0.0, czz = -0.0;
+            for (uint32_t j = b; j < e; ++j) {
+                const float4 p = pts[ord[j]];
+                const double dx = (double)p.x - mx, dy = (double)p.y - my, dz = (double)p.z - mz;
+                cxx = cxx + dx * dx; cxy = cxy + dx * dy; cxz = cxz + dx * dz;
+                cyy = cyy + dy * dy; cyz = cyz + dy * dz; czz = czz + dz * dz;
+            }
+            double a00 = cxx / m, a01 = cxy / m, a02 = cxz / m, a11 = cyy / m, a12 = cyz / m, a22 = czz / m;
+            double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+            for (int sweep = 0; sweep < 6; ++sweep) {
+                jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);     // (0,1), r = 2
+                jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);     // (0,2), r = 1
+                jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);     // (1,2), r = 0
+            }
+            double lmax = a00;
+            if (a11 > lmax) lmax = a11;
+            if (a22 > lmax) lmax = a22;
+            const double big = 1.7976931348623157e308;
+            k = lmax > 0.0 && fabs(a00) <= big && fabs(a11) <= big && fabs(a22) <= big;
+            degenerate = !k;
+            if (k) {
+                double l0 = a00 / lmax, l1 = a11 / lmax, l2 = a22 / lmax;
+                if (l0 < eps) l0 = eps;
+                if (l1 < eps) l1 = eps;
+                if (l2 < eps) l2 = eps;
+                // C'_ab = ((V_a0 l_0) V_b0 + (V_a1 l_1) V_b1) + (V_a2 l_2) V_b2, a >= b
+                const double c00 = ((v00 * l0) * v00 + (v01 * l1) * v01) + (v02 * l2) * v02;
+                const double c10 = ((v10 * l0) * v00 + (v11 * l1) * v01) + (v12 * l2) * v02;
+                const double c20 = ((v20 * l0) * v00 + (v21 * l1) * v01) + (v22 * l2) * v02;
+                const double c11 = ((v10 * l0) * v10 + (v11 * l1) * v11) + (v12 * l2) * v12;
+                const double c21 = ((v20 * l0) * v10 + (v21 * l1) * v11) + (v22 * l2) * v12;
+                const double c22 = ((v20 * l0) * v20 + (v21 * l1) * v21) + (v22 * l2) * v22;
+                rec[3 * v] = make_float4((float)mx, (float)my, (float)mz, (float)c00);
+                rec[3 * v + 1] = make_float4((float)c10, (float)c20, (float)c11, (float)c21);
+                rec[3 * v + 2] = make_float4((float)c22, __uint_as_float(e - b), 0.f, 0.f);
+            }
+        }
+        keep[v] = k ? 1u : 0u;
+    }
+    const uint64_t S = __ballot(small), D = __ballot(degenerate);
+    if ((threadIdx.x & 63) == 0) {
+        if (S) atomicAdd(cls, (unsigned long long)__popcll(S));
+        if (D) atomicAdd(cls + 1, (unsigned long long)__popcll(D));
+    }
+}
+
+// compaction of the kept voxels (pos = exclusive scan of keep) into the member's arrays, and the fill of the lookup table: the voxel's key
+// (its rel key - widths bx, by - repacked to 21 bits per axis) claims the first free slot of its probe sequence with one 64-bit
+// atomicCAS; keys are unique, so only slots are contended, and the value is written by the lane that won the slot (the kernels that read
+// the table are later launches).  Which slot a key ends in depends on the order of arrival; what a lookup answers does not.
+static __global__ void __launch_bounds__(kVoxBlock) k_vmap_write(const float4 *__restrict__ rec, const uint32_t *__restrict__ keep,
+                                                                 const uint32_t *__restrict__ pos, int64_t n_vox, const uint32_t *__restrict__ ord,
+                                                                 const uint32_t *__restrict__ start, const uint64_t *__restrict__ rel, int bx, int by,
+                                                                 float4 *__restrict__ recs, uint64_t *__restrict__ vkeys,
+                                                                 uint64_t *__restrict__ t_keys, uint32_t *__restrict__ t_vals, uint32_t mask) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vox || !keep[v]) return;
+    const uint32_t j = pos[v];
+    recs[3 * (size_t)j] = rec[3 * v]; recs[3 * (size_t)j + 1] = rec[3 * v + 1]; recs[3 * (size_t)j + 2] = rec[3 * v + 2];
+    const uint64_t r = rel[ord[start[v]]];
+    const uint64_t key = vmap_key(r & ((1ull << bx) - 1ull), (r >> bx) & ((1ull << by) - 1ull), r >> (bx + by));
+    vkeys[j] = key;
+    uint32_t s = vmap_slot(key, mask);
+    for (;;) {                                           // (ends: at most half of the slots are ever claimed)
+        const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(t_keys + s), (unsigned long long)kVmapEmpty, (unsigned long long)key);
+        if (was == (unsigned long long)kVmapEmpty) { t_vals[s] = j; break; }
+        s = (s + 1u) & mask;
+    }
+}
+
 template <typename K>
 int sort_pairs(dcreg_ctx *c, K *keys_in, K *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int bits) {
     size_t tmp = 0;
@@ -280,6 +378,36 @@ int scan(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inclusi
 }
 
 int bits_for(int64_t v) { int b = 0; while (b < 63 && ((int64_t)1 << b) <= v) ++b; return b; }
+
+// Keys, stable sort, voxel heads and starts of the n packed points at pts (k_vox_coords has run: seg and the clouds' minimum voxels in
+// B.cnt; bx / by / bz: the key widths of the largest spans).  ord: the points' indices in (cloud, voxel z y x, input) order; B.incl the
+// voxel numbers + 1 of the sorted positions, B.start where each voxel starts.  The buffers are the caller's to size (n entries each)
+int vox_order(dcreg_ctx *c, const float4 *pts, int64_t n, int n_clouds, double lx, double ly, double lz, int bx, int by, int bz, const uint32_t *&ord) {
+    dcreg_ctx::VoxelBufs &B = c->vox;
+    int rc;
+    const int sbits = bits_for(n_clouds);        // cloud ids 0 .. n_clouds (n_clouds = the non-finite points)
+    const bool one_pass = sbits + bx + by + bz <= 64;
+    hipLaunchKernelGGL(k_vox_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, pts, n, B.seg.data(), n_clouds, lx, ly, lz, B.cnt.data(),
+                       bx, by, bz, one_pass, c->d_mkeys.data(), c->d_vals.data(), B.rel.data());
+    if (one_pass) {
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, sbits + bx + by + bz);
+        if (rc) return rc;
+        ord = c->d_vals2.data();
+    } else {            // voxel key first, then the cloud: both sorts stable, so each cloud's voxels and each voxel's points keep their order
+        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bx + by + bz);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_vox_seg_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, c->d_vals2.data(), n, B.seg.data(), B.head.data());
+        rc = sort_pairs<uint32_t>(c, B.head.data(), B.incl.data(), c->d_vals2.data(), c->d_vals.data(), (size_t)n, sbits);
+        if (rc) return rc;
+        ord = c->d_vals.data();
+    }
+    hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), B.rel.data(), (uint32_t)n_clouds, B.head.data());
+    rc = scan(c, B.head.data(), B.incl.data(), (size_t)n, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), (uint32_t)n_clouds, B.head.data(), B.incl.data(),
+                       B.start.data());
+    return DCREG_OK;
+}
 
 }  // namespace
 
@@ -348,30 +476,11 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
     }
     if (r.n_finite == 0) return DCREG_OK;
     const int bx = bits_for(span[0]), by = bits_for(span[1]), bz = bits_for(span[2]);
-    const int sbits = bits_for(n_clouds);        // cloud ids 0 .. n_clouds (n_clouds = the non-finite points)
-    const bool one_pass = sbits + bx + by + bz <= 64;
 
     // ---- keys, stable sort, voxel heads and starts
-    hipLaunchKernelGGL(k_vox_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), n, B.seg.data(), n_clouds, lx, ly, lz, B.cnt.data(),
-                       bx, by, bz, one_pass, c->d_mkeys.data(), c->d_vals.data(), B.rel.data());
     const uint32_t *ord;
-    if (one_pass) {
-        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, sbits + bx + by + bz);
-        if (rc) return rc;
-        ord = c->d_vals2.data();
-    } else {            // voxel key first, then the cloud: both sorts stable, so each cloud's voxels and each voxel's points keep their order
-        rc = sort_pairs<uint64_t>(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bx + by + bz);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_vox_seg_keys, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, c->d_vals2.data(), n, B.seg.data(), B.head.data());
-        rc = sort_pairs<uint32_t>(c, B.head.data(), B.incl.data(), c->d_vals2.data(), c->d_vals.data(), (size_t)n, sbits);
-        if (rc) return rc;
-        ord = c->d_vals.data();
-    }
-    hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), B.rel.data(), (uint32_t)n_clouds, B.head.data());
-    rc = scan(c, B.head.data(), B.incl.data(), (size_t)n, true);
+    rc = vox_order(c, B.pts.data(), n, n_clouds, lx, ly, lz, bx, by, bz, ord);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), (uint32_t)n_clouds, B.head.data(), B.incl.data(),
-                       B.start.data());
     // ---- one lane per voxel (at most n of them: the grids are sized for n, the lanes beyond the voxel count idle), compaction
     hipLaunchKernelGGL(k_vox_reduce, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), ord, n, B.seg.data(), B.start.data(), B.incl.data(), p->mode,
                        min_points, B.vout.data(), B.keep.data(), B.cnt.data());
@@ -416,6 +525,117 @@ int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int6
     return DCREG_OK;
 }
 
+// dcreg_target_voxels_keep: the whole map's points (index order, all finite) as one cloud through the pass's keying and sort, then the
+// records, their compaction and the table.  Everything is built beside the member; it is replaced once the last launch has run.
+int voxel_map_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_map_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (!p) { c->fail("null voxel map parameters"); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->leaf) && p->leaf > 0.0)) { c->fail("voxel map leaf is %g: finite and > 0 expected", p->leaf); return DCREG_E_INVALID; }
+    if (!(p->epsilon >= 1.0e-6 && p->epsilon <= 1.0)) { c->fail("voxel map epsilon is %g: 1e-6 .. 1 expected", p->epsilon); return DCREG_E_INVALID; }
+    if (p->min_points < 2) { c->fail("voxel map min_points is %d: at least 2 expected", p->min_points); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;
+    const int64_t n = wm.n;
+    if (n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::VoxelBufs &B = c->vox;
+    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    const size_t nc = (size_t)kCnt + kTail;
+    if (B.seg.ensure(c, (size_t)n) || B.rel.ensure(c, (size_t)n) || B.head.ensure(c, (size_t)n) || B.incl.ensure(c, (size_t)n) ||
+        B.start.ensure(c, (size_t)n + 1) || B.keep.ensure(c, (size_t)n) || B.pos.ensure(c, (size_t)n) || B.d_off.ensure(c, 2) ||
+        B.cnt.ensure(c, nc) || c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) || c->d_vals.ensure(c, (size_t)n) ||
+        c->d_vals2.ensure(c, (size_t)n) || M.cls.ensure(c, 2))
+        return DCREG_E_NOMEM;
+    const float4 *pts = wm.raw.data();
+    const int64_t off[2] = {0, n};
+    HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(off), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(M.cls.data(), 0, 2 * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), 1);
+    const double l = p->leaf;
+    hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, pts, n, B.d_off.data(), 1, l, l, l, B.seg.data(),
+                       B.cnt.data());
+    int64_t h[kCnt + kTail];
+    HIP_TRY(c, hipMemcpyAsync(h, B.cnt.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    // ---- the voxel pass's limits
+    uint32_t tail[2 * kTail];
+    std::memcpy(tail, h + kCnt, sizeof(tail));
+    if (tail[6]) { c->fail("a voxel coordinate reaches 2^62 (leaf too small for the coordinates)"); return DCREG_E_INVALID; }
+    int bits[3];
+    for (int a = 0; a < 3; ++a) {
+        const int64_t d = h[3 + a] - h[a];
+        if (d >= ((int64_t)1 << kSpanBits)) { c->fail("the map spans %lld voxels on axis %d (at most 2^21 - 1)", (long long)d + 1, a); return DCREG_E_INVALID; }
+        bits[a] = bits_for(d);
+    }
+    const uint32_t *ord;
+    int rc = vox_order(c, pts, n, 1, l, l, l, bits[0], bits[1], bits[2], ord);
+    if (rc) return rc;
+    uint32_t n_vox32 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_vox32, B.incl.data() + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t n_vox = n_vox32;
+    // ---- one lane per voxel, then the kept ones' count
+    if (M.tmp.ensure(c, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, pts, ord, n_vox, B.start.data(), p->min_points, p->epsilon,
+                       M.tmp.data(), B.keep.data(), M.cls.data());
+    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+    if (rc) return rc;
+    unsigned long long cls[2] = {0, 0};
+    uint32_t last[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(cls, M.cls.data(), sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&last[0], B.keep.data() + (n_vox - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&last[1], B.pos.data() + (n_vox - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t n_kept = (int64_t)last[0] + (int64_t)last[1];
+    if (info) { info->n_points = n; info->n_voxels = n_vox; info->n_small = (int64_t)cls[0]; info->n_degenerate = (int64_t)cls[1]; info->n_kept = n_kept; }
+    M.kept = false; M.n_kept = 0;                      // (the member's arrays are rewritten from here on: a failure leaves none)
+    if (n_kept == 0) return DCREG_OK;                  // (nothing to keep: no member)
+    // ---- the member: records, keys, and a table of the power of two at or above 2 n_kept slots
+    size_t slots = 2;
+    while (slots < 2 * (size_t)n_kept) slots <<= 1;
+    if (M.recs.ensure(c, 3 * (size_t)n_kept) || M.vkeys.ensure(c, (size_t)n_kept) || M.t_keys.ensure(c, slots) || M.t_vals.ensure(c, slots)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(M.t_keys.data(), 0xFF, slots * sizeof(uint64_t), c->stream));
+    hipLaunchKernelGGL(k_vmap_write, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.tmp.data(), B.keep.data(), B.pos.data(), n_vox, ord, B.start.data(),
+                       B.rel.data(), bits[0], bits[1], M.recs.data(), M.vkeys.data(), M.t_keys.data(), M.t_vals.data(), (uint32_t)(slots - 1));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    for (int a = 0; a < 3; ++a) { M.mn[a] = h[a]; M.mx[a] = h[3 + a]; }
+    M.leaf = l; M.mask = (uint32_t)(slots - 1); M.n_kept = n_kept; M.kept = true;
+    return DCREG_OK;
+}
+
+// dcreg_target_voxels_get: the member's records and keys to the host, unpacked there
+static int voxel_map_get(dcreg_ctx *c, int64_t *coords, int32_t *count, float *mean, float *cov, int64_t capacity) {
+    if (!c) return DCREG_E_INVALID;
+    if (!coords || !count || !mean || !cov) { c->fail("null argument"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    const dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    if (!M.kept) { c->fail("no kept voxels: dcreg_target_voxels_keep first"); return DCREG_E_STATE; }
+    if (capacity < M.n_kept) { c->fail("the output holds %lld voxels, the map keeps %lld", (long long)capacity, (long long)M.n_kept); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nk = (size_t)M.n_kept;
+    std::vector<float> rec(12 * nk);
+    std::vector<uint64_t> keys(nk);
+    HIP_TRY(c, hipMemcpyAsync(rec.data(), M.recs.data(), sizeof(float) * 12 * nk, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(keys.data(), M.vkeys.data(), sizeof(uint64_t) * nk, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t am = (1ull << kVmapAxisBits) - 1ull;
+    for (size_t j = 0; j < nk; ++j) {
+        const float *r = rec.data() + 12 * j;
+        coords[3 * j] = M.mn[0] + (int64_t)(keys[j] & am);
+        coords[3 * j + 1] = M.mn[1] + (int64_t)((keys[j] >> kVmapAxisBits) & am);
+        coords[3 * j + 2] = M.mn[2] + (int64_t)(keys[j] >> (2 * kVmapAxisBits));
+        std::memcpy(mean + 3 * j, r, 3 * sizeof(float));
+        std::memcpy(cov + 6 * j, r + 3, 6 * sizeof(float));
+        std::memcpy(count + j, r + 9, sizeof(int32_t));
+    }
+    return DCREG_OK;
+}
+
 }  // namespace dcreg
 
 using namespace dcreg;
@@ -428,5 +648,23 @@ int dcreg_voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const i
 int dcreg_voxel_downsample_device(dcreg_ctx *c, int n_clouds, const float *d_xyz, const int64_t *offsets, int64_t stride_floats,
                                   const dcreg_voxel_params *p, float *d_out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
     return voxel_downsample_to(c, n_clouds, d_xyz, offsets, stride_floats, true, p, d_out_xyz, capacity_points, out_offsets, info);
+}
+int dcreg_default_voxel_map_params(dcreg_voxel_map_params *p) {
+    if (!p) return DCREG_E_INVALID;
+    p->leaf = 1.0; p->epsilon = 1.0e-3; p->min_points = 6; p->reserved_ = 0;
+    return DCREG_OK;
+}
+int dcreg_target_voxels_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_map_info *info) { return voxel_map_keep(c, p, info); }
+int dcreg_target_voxels_get(dcreg_ctx *c, int64_t *coords, int32_t *count, float *mean, float *cov, int64_t capacity_voxels) {
+    return voxel_map_get(c, coords, count, mean, cov, capacity_voxels);
+}
+int dcreg_target_voxels_kept(const dcreg_ctx *c) { return c && c->vmap.kept ? (int)c->vmap.n_kept : 0; }
+int dcreg_target_voxels_drop(dcreg_ctx *c) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    M.kept = false; M.n_kept = 0;
+    M.recs.reset(); M.tmp.reset(); M.vkeys.reset(); M.t_keys.reset(); M.t_vals.reset();
+    return DCREG_OK;
 }
 }

@@ -1,0 +1,151 @@
+// The fourth engine's linearisation on the device (include/dcreg.h: dcreg_linearize_voxels): rows against the map's kept voxel
+// distributions (voxel.hip voxel_map_keep), with the rule of the header, bitwise the numpy reference of tests/voxels_ref.py.
+//   k_vlin<DUMP>   one lane per source point, in the context's curve order: vlin_point (voxel_icp.hpp) - transform, the lookup of the voxel
+//                  the point falls into (no search: nothing is walked, nothing is kept between calls), three 16-byte gathers of its
+//                  record, in mode 1 the coalesced float4 load of the point's own normal, the covariance, its Cholesky factor and W = L^-1;
+//                  then the third engine's block tail (gicp.hpp glin_block_rows): three rows per point over the matrix cores, the block
+//                  row in LDS, added in wave order.  Its LDS is the staging area of the Gram pass and the waves' sums - no RunList
+//   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_glin
+// vlin_run is the launch's own small run function: refusals, buffers, the dump block cut as one_nn_run cuts it, launch, k_finalize, wait.
+// It reads the source, the kept voxel map and - in mode 1 - the kept source normals; it neither reads nor writes warm words, neighbour
+// states, the window index (no roi_ensure) or the map's kept normals.  The block rows, the result row and the dump block are nicp's.
+// No floating-point atomics anywhere: the sums are a function of the rows and their order.
+#include <cmath>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../../include/dcreg_debug.h"
+#include "context.hpp"
+#include "voxel_icp.hpp"
+
+namespace dcreg {
+namespace {
+
+struct VlinDump {
+    int32_t *voxel_idx; uint8_t *flag; double *mean, *cov, *normal_src, *w, *r, *row;
+};
+
+// src_normals: float4 per source point in the order of src (null in mode 0).  Slot 29 counts the effective POINTS (not rows), slot 30
+// the points that fall into a kept voxel.
+template <bool DUMP>
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4 *__restrict__ src, uint32_t n_src, VoxMapDev vm,
+                                                                     const float4 *__restrict__ src_normals, PoseArg P, VlinArgs a,
+                                                                     double *__restrict__ partials, VlinDump d) {
+    __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    uint8_t flag = 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    size_t oi = 0;
+    GlinPoint o;
+    if (i < n_src) {
+        const float4 s4 = src[i];
+        sx = s4.x; sy = s4.y; sz = s4.z;
+        VlinPoint x;
+        flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
+        if constexpr (DUMP) {
+            oi = __float_as_uint(s4.w);
+            if (d.voxel_idx) d.voxel_idx[oi] = x.vidx == kNoIdx ? -1 : (int32_t)x.vidx;
+            if (d.flag) d.flag[oi] = flag;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) if (d.cov) d.cov[6 * oi + k] = x.cov[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (d.mean) d.mean[3 * oi + k] = x.mean[k];
+                if (d.normal_src) d.normal_src[3 * oi + k] = o.m[k];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) if (d.w) d.w[9 * oi + 3 * k + j] = o.w[k][j];
+            }
+        }
+    }
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
+        if constexpr (DUMP) {
+            if (i < n_src) {
+                if (d.r) d.r[3 * oi + k] = row[7];
+                if (d.row) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) d.row[(3 * oi + k) * 8 + j] = row[j];
+                }
+            }
+        }
+    });
+}
+
+bool finite_n(const double *v, int n) {
+    for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
+    return true;
+}
+
+int vlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_vlin_debug *dbg) {
+    // ---- dcreg_linearize_gicp's refusals in its order, with "no kept voxels" in place of "no kept normals"
+    if (!c) return DCREG_E_INVALID;
+    if (!R || !t || !p || !out) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the voxel linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
+    if (!finite_n(R, 9) || !finite_n(t, 3)) { c->fail("the pose is not finite"); return DCREG_E_INVALID; }
+    if ((c->roi_active ? c->roi_store : c->map).n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    if (!M.kept) { c->fail("no kept voxels: dcreg_target_voxels_keep first"); return DCREG_E_STATE; }
+    const int mode = c->opt_voxels_source_cov;
+    if (mode && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    const size_t N = (size_t)c->n_src;
+    const uint32_t nb = (uint32_t)((N + kLinBlock - 1) / kLinBlock);
+    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots)) return DCREG_E_NOMEM;
+    // one block of device memory for the dump, cut into its arrays in the table's order (8-byte ones first)
+    VlinDump d{};
+    const dcreg_vlin_debug none{}, &h = dbg ? *dbg : none;
+    const OneNnDumpField fields[] = {{h.mean, 24, &d.mean}, {h.cov, 48, &d.cov}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
+                                     {h.row, 192, &d.row}, {h.voxel_idx, 4, &d.voxel_idx}, {h.flag, 1, &d.flag}};
+    const int n_fields = dbg ? 8 : 0;
+    size_t total = 0;
+    for (int k = 0; k < n_fields; ++k) total += fields[k].bytes * N;
+    if (dbg && B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
+    unsigned char *b = B.dbg.data();
+    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
+        if (fields[k].host) std::memcpy(fields[k].dev, &b, sizeof(b));
+    VoxMapDev vm;
+    vm.recs = M.recs.data(); vm.keys = M.t_keys.data(); vm.vals = M.t_vals.data(); vm.mask = M.mask; vm.leaf = M.leaf;
+    for (int a = 0; a < 3; ++a) { vm.mn[a] = M.mn[a]; vm.mx[a] = M.mx[a]; }
+    VlinArgs a;
+    a.source_cov = mode; a.c = 1.0 - c->opt_gicp_epsilon;
+    a.robust = c->opt_robust_kernel; a.robust_c2 = c->opt_gicp_robust_scale * c->opt_gicp_robust_scale;
+    PoseArg P;
+    std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
+    P.state = kNoIdx; P.fresh = 1;
+    hipLaunchKernelGGL(dbg ? k_vlin<true> : k_vlin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)N, vm,
+                       mode ? c->gicp.src_normals.data() : (const float4 *)nullptr, P, a, B.partials.data(), d);
+    HIP_TRY(c, hipGetLastError());
+    b = B.dbg.data();
+    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
+        if (fields[k].host) HIP_TRY(c, hipMemcpyAsync(fields[k].host, b, fields[k].bytes * N, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
+    HIP_TRY(c, hipGetLastError());
+    double row[kSlots];
+    HIP_TRY(c, hipMemcpyAsync(row, B.d_out.data(), sizeof(row), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    lin_out_of_row(row, *out);
+    return DCREG_OK;
+}
+
+}  // namespace
+}  // namespace dcreg
+
+using namespace dcreg;
+
+extern "C" {
+int dcreg_linearize_voxels(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out) {
+    return vlin_run(c, R, t, p, out, nullptr);
+}
+int dcreg_linearize_voxels_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
+                                 dcreg_vlin_debug *dbg) {
+    if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }
+    return vlin_run(c, R, t, p, out, dbg);
+}
+}

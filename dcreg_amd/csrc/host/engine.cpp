@@ -293,6 +293,11 @@ int dcreg_icp_run_gicp(dcreg_ctx *ctx, const double R0[9], const double t0[3], i
                        const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
     return icp_run_waited(dcreg_linearize_gicp, ctx, R0, t0, detection, handling, cfg, log, log_capacity, res);
 }
+// (the fourth engine: the same loop around dcreg_linearize_voxels - a lookup per point instead of a search)
+int dcreg_icp_run_voxels(dcreg_ctx *ctx, const double R0[9], const double t0[3], int detection, int handling,
+                         const dcreg_config *cfg, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *res) {
+    return icp_run_waited(dcreg_linearize_voxels, ctx, R0, t0, detection, handling, cfg, log, log_capacity, res);
+}
 
 int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const double *t0, int detection, int handling,
                        const dcreg_config *cfg, dcreg_icp_result *results) {
@@ -947,6 +952,9 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_normals_follow_info")) return sizeof(dcreg_normals_follow_info);
     if (!std::strcmp(name, "dcreg_nlin_debug")) return sizeof(dcreg_nlin_debug);
     if (!std::strcmp(name, "dcreg_glin_debug")) return sizeof(dcreg_glin_debug);
+    if (!std::strcmp(name, "dcreg_vlin_debug")) return sizeof(dcreg_vlin_debug);
+    if (!std::strcmp(name, "dcreg_voxel_map_params")) return sizeof(dcreg_voxel_map_params);
+    if (!std::strcmp(name, "dcreg_voxel_map_info")) return sizeof(dcreg_voxel_map_info);
     return 0;
 }
 

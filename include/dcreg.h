@@ -25,6 +25,9 @@
  *                                                                                   dcreg_source_normals_keep / _set[_device] / _get[_device] /
  *                                                                                   _kept / _drop
  *       one linearisation, the engine                                            -> dcreg_linearize_gicp, dcreg_icp_run_gicp
+ *   registration against per-voxel Gaussians (voxelised GICP / NDT; not in the reference)
+ *       one distribution per voxel kept beside the map                           -> dcreg_target_voxels_keep / _get / _kept / _drop
+ *       one linearisation, the engine                                            -> dcreg_linearize_voxels, dcreg_icp_run_voxels
  *   raw clouds (not in the reference, which reads clouds a pcl::VoxelGrid filtered beforehand)
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
@@ -1082,6 +1085,85 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
 #define DCREG_ROBUST_CAUCHY 2
 #define DCREG_ROBUST_GEMAN_MCCLURE 3
 
+/* ---------------- kept voxel distributions and the voxel-distribution linearisation (fourth engine) ----------------
+ * The second and third engine find every point's match with an exact 1-NN search at every linearisation.  Voxelised GICP and NDT (Koide
+ * et al. 2021; Magnusson 2009) do not search: the map is summarised ONCE as one Gaussian per voxel, and a transformed source point's
+ * correspondence is the voxel it falls into - a constant-time lookup, nothing walked, nothing kept between calls.  The map side needs no
+ * normals, and the correspondence basin is a voxel edge instead of a search radius: the cheap, wide-basin stage that a GICP or 1-NN run
+ * follows.  It is density-hungry and centimetre-grade, not a replacement for those engines.
+ *
+ * The rule of the kept voxel map (dcreg_target_voxels_keep; tests/voxels_ref.py states it in numpy).  The map's points are taken in index
+ * order (the order of dcreg_target_get).  Every operation is in double and rounds once (no contraction).
+ *   - the voxel of a point: v_a = floor((double)p_a / leaf) per axis - the voxel pass's rule with one leaf for all axes.  A voxel's
+ *     members are its points in ascending index; n is their count;
+ *   - a voxel with n < min_points is not kept and counts in n_small;
+ *   - mean: s_a = the left-to-right sum of (double)p_a; mu_a = s_a / n;
+ *   - covariance, a second pass over the same points: d_j = (double)p_j - mu; the six entries C_ab = (sum_j d_ja * d_jb) / n, summed left
+ *     to right, in the order xx, xy, xz, yy, yz, zz;
+ *   - eigen-solve: exactly the cyclic Jacobi of the normals rule (six sweeps; "surface normals and curvature" above).  It leaves
+ *     lambda_0..2 (the diagonal) and V (columns);
+ *   - normalised clamp (fast_gicp's NORMALIZED_MIN_EIG): lmax = the largest lambda.  Unless lmax > 0 and all three lambda are finite the
+ *     voxel is not kept and counts in n_degenerate (coincident points are the usual case).  l_k = lambda_k / lmax, replaced by epsilon
+ *     when l_k < epsilon.  C'_ab = ((V_a0*l_0)*V_b0 + (V_a1*l_1)*V_b1) + (V_a2*l_2)*V_b2 for the lower triangle (a >= b): xx = C'_00,
+ *     xy = C'_10, xz = C'_20, yy = C'_11, yz = C'_21, zz = C'_22;
+ *   - the kept record: (float)mu[3], (float)C'[6] in that order, n.  48 bytes, padded so that a lookup is three 16-byte loads.  The floats
+ *     are widened to double at use: that is part of the rule.
+ * dcreg_target_voxels_get returns the kept voxels in ascending (v_z, v_y, v_x) order: absolute voxel coordinates (3 per voxel), counts,
+ * means (3) and covariances (6).  dcreg_target_voxels_kept: the number of kept voxels, 0 without a member (also for a null context);
+ * _drop frees the member.  A keep that keeps no voxel succeeds, fills info and leaves no member.
+ * A voxel's record depends on its own points and the three parameters only - not on the launch shape, the lookup structure or other
+ * voxels.  One lane reduces one voxel (that fixes the summation order): a call pays for its fullest voxel.  The lookup structure is an
+ * open-addressing table of 64-bit keys (the voxel relative to the map's minimum voxel, 21 bits per axis) with linear probing, at most
+ * half full; a query outside the map's voxel box answers "none" without reading it.  Device memory: 56 B per kept voxel (record and key)
+ * and 12 B per table slot - the power of two at or above twice the kept voxels - 80 to 104 B per kept voxel in all; a keep also uses
+ * 48 B of scratch per occupied voxel and the voxel pass's scratch per map point.
+ * Every call that changes the map's points drops the member: dcreg_set_target* in all its forms, dcreg_target_insert*,
+ * dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic and dcreg_set_target_keyframes.  Nothing follows the map.
+ * DCREG_E_INVALID, before anything is queued: null context, parameters or outputs; a leaf that is not finite and > 0; epsilon outside
+ * [1e-6, 1]; min_points < 2; a capacity_voxels below the kept voxels; and, once the points' voxels are known and before anything is kept,
+ * a map that spans 2^21 or more voxels on an axis or has a voxel coordinate of magnitude 2^62 or more (the voxel pass's limits).
+ * DCREG_E_STATE: no target, a linearisation in flight, _get without a member.  A failed allocation (DCREG_E_NOMEM) leaves no member.
+ *
+ * The rule of one linearisation (dcreg_linearize_voxels).  Of the parameter block only parameterization is read (DCREG_PARAM_SO3, else
+ * DCREG_E_INVALID); there is no radius gate - a point is at most a voxel diagonal from its mean.  Options, read at every call:
+ * "voxels_source_cov" = 0 (default) point-to-distribution, 1 distribution-to-distribution with the source's plane covariance from its
+ * kept normals (dcreg_source_normals_keep / _set) and eps = "gicp_epsilon" as the third engine reads it, c = 1 - eps; "robust_kernel" and
+ * "gicp_robust_scale" exactly as dcreg_linearize_gicp applies them (one k per point from the squared Mahalanobis distance, slots 0..6
+ * of all three rows scaled, slot 7 left; kernel 0 multiplies nothing).  For each source point p (floats, widened to double):
+ *   - q is formed as every engine forms it (stored as float);
+ *   - v_a = floor((double)q_a / leaf) with the member's leaf.  Flag 0 when no kept voxel has these coordinates; otherwise the point
+ *     counts in n_pt;
+ *   - mode 1 only: m = the point's kept source normal, flag 3 when it has none; u = R m, summed as dcreg_linearize_gicp sums it;
+ *   - S_ab = C'_ab (the record's floats, widened) in mode 0; S_ab = C'_ab + (d_ab - c*(u_a*u_b)) in mode 1, d_ab = 1 on the diagonal
+ *     and 0 off it, for the six entries of the lower triangle;
+ *   - the Cholesky factor and W = L^-1 by the third engine's formulas in its order.  Flag 5 unless the three radicands are > 0;
+ *   - e = (double)q - (double)mu per coordinate (mu: the record's floats); the three rows as dcreg_linearize_gicp forms them from W, e
+ *     and p, scaled by the robust kernel's k where one is on.  Flag 1;
+ *   - the sums are the third engine's: three rows per flag-1 point, n_eff counts points, sum_r2 and sum_b2 are both the Mahalanobis sum
+ *     (sum_b2 of the scaled rows with a kernel on), added in a fixed order (no floating-point atomics).
+ * A result depends on the source, the kept records, the pose and the options only.  The call neither reads nor writes warm words,
+ * neighbour states, the window index or the map's kept normals: it may be interleaved with every other engine's calls without moving a
+ * bit on either side.  DCREG_E_INVALID: null arguments, a non-finite pose, a parameterization other than SO3.  DCREG_E_STATE: no target,
+ * no source, no kept voxels, in mode 1 no kept source normals, a linearisation in flight.  Waits for the stream.
+ * Not provided: batched forms (trials, frames, pairs), neighbour-voxel correspondences (7 / 27 voxels per point), a voxel map that
+ * follows map updates, sharded / Euler forms, a caller-supplied voxel map, the runner's YAML. */
+typedef struct dcreg_voxel_map_params {
+    double leaf;      /* voxel edge, metres (default 1.0) */
+    double epsilon;   /* floor of the normalised eigenvalues (default 1e-3) */
+    int min_points;   /* a voxel with fewer points is not kept (default 6) */
+    int reserved_;
+} dcreg_voxel_map_params;
+typedef struct dcreg_voxel_map_info {
+    int64_t n_points, n_voxels, n_small, n_degenerate, n_kept;
+} dcreg_voxel_map_info;
+int dcreg_default_voxel_map_params(dcreg_voxel_map_params *);      /* leaf 1.0, epsilon 1e-3, min_points 6 */
+int dcreg_target_voxels_keep(dcreg_ctx *, const dcreg_voxel_map_params *, dcreg_voxel_map_info *info /* may be NULL */);
+int dcreg_target_voxels_get(dcreg_ctx *, int64_t *coords /*3V*/, int32_t *count /*V*/, float *mean /*3V*/, float *cov /*6V*/,
+                            int64_t capacity_voxels);
+int dcreg_target_voxels_kept(const dcreg_ctx *);   /* number of kept voxels, 0 without a member */
+int dcreg_target_voxels_drop(dcreg_ctx *);
+int dcreg_linearize_voxels(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
 typedef struct dcreg_config {
@@ -1173,6 +1255,14 @@ int dcreg_icp_run_normals(dcreg_ctx *, const double R0[9], const double t0[3], i
  * many pairs, each against a target of its own.  No sharded / RCCL or Euler form of this engine. */
 int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                        const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
+
+/* The same loop with dcreg_linearize_voxels as its linearisation (dcreg_target_voxels_keep first, DCREG_E_STATE without it; with
+ * "voxels_source_cov" = 1 kept source normals too): one waited launch per iteration, the same aborts, fitness, convergence test, log
+ * records, covariance and status codes, the same host step.  rmse is the RMS Mahalanobis distance per effective point, as for
+ * dcreg_icp_run_gicp.  Of the configuration's linearisation parameters none is read.  One pose per call; no batched, sharded / RCCL or
+ * Euler form of this engine. */
+int dcreg_icp_run_voxels(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
+                         const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
 /* n independent scan pairs at once: one host thread per ctx (each ctx owns its clouds, index, stream), every thread runs
  * dcreg_icp_run.  One 100 k-point linearisation fills well under half of an MI355X and the device idles during each host

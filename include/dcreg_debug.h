@@ -69,6 +69,26 @@ typedef struct dcreg_glin_debug {
 int dcreg_linearize_gicp_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *,
                                dcreg_glin_debug *);
 
+/* per-point dump of dcreg_linearize_voxels (original source order; any pointer may be NULL).  flag: 1 effective, 0 no kept voxel holds
+ * the transformed point, 3 the source point has no normal (mode 1), 5 the covariance is not positive definite.  voxel_idx: the voxel's
+ * position in dcreg_target_voxels_get order, -1 for flag 0.  mean / cov: the voxel's record widened to double, for every point with a
+ * voxel.  normal_src: the point's own kept normal as stored (with its non-finite components), in mode 1 for every point with a voxel.
+ * For flag 1: w = the whitening matrix W = L^-1 row-major (its upper triangle 0), r = the three whitened residuals, row = the three rows
+ * [A0..A5, -r_k, r_k] (scaled where a robust kernel is on); everything else is 0. */
+typedef struct dcreg_vlin_debug {
+    int32_t *voxel_idx;  /* [n] */
+    uint8_t *flag;       /* [n] */
+    double *mean;        /* [3*n] */
+    double *cov;         /* [6*n] */
+    double *normal_src;  /* [3*n] */
+    double *w;           /* [9*n] */
+    double *r;           /* [3*n] */
+    double *row;         /* [3*8*n] */
+} dcreg_vlin_debug;
+/* dcreg_linearize_voxels with the dump */
+int dcreg_linearize_voxels_debug(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *,
+                                 dcreg_vlin_debug *);
+
 /* total duration (ms, HIP events on the ctx stream around ALL kernels of a linearisation) of the timed linearisations since the
  * last reset, and their number; option "time_kernels" = N > 0 brackets every N-th linearisation of slot 0 (an event pair costs ~10 us
  * of host time), 0 = off */
