@@ -204,6 +204,7 @@ EXPORTS = [
     "dcreg_pairs_sources_normals_get", "dcreg_pairs_normals_reserve_slots", "dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin",
     "dcreg_default_voxel_map_params", "dcreg_target_voxels_keep", "dcreg_target_voxels_get", "dcreg_target_voxels_kept", "dcreg_target_voxels_drop",
     "dcreg_linearize_voxels", "dcreg_linearize_voxels_debug", "dcreg_icp_run_voxels",
+    "dcreg_voxels_batch_begin", "dcreg_voxels_batch_end", "dcreg_register_frames_voxels", "dcreg_icp_run_trials_voxels",
 ]
 
 _lib = None
@@ -1186,6 +1187,11 @@ def load():
         L.dcreg_register_frames_gicp.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, np_, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.c_int,
                                                  C.POINTER(TrialResult)]
         L.dcreg_icp_run_trials_gicp.argtypes = L.dcreg_icp_run_trials.argtypes
+    if hasattr(L, "dcreg_register_frames_voxels"):  # (likewise)
+        L.dcreg_voxels_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, C.POINTER(LinParams)]
+        L.dcreg_voxels_batch_end.argtypes = L.dcreg_normals_batch_end.argtypes
+        L.dcreg_register_frames_voxels.argtypes = L.dcreg_register_frames_gicp.argtypes
+        L.dcreg_icp_run_trials_voxels.argtypes = L.dcreg_icp_run_trials.argtypes
     if hasattr(L, "dcreg_register_pairs_normals"):  # (likewise)
         np_, ni, cfgp, trp = C.POINTER(NormalParams), C.POINTER(NormalInfo), C.POINTER(Config), C.POINTER(TrialResult)
         L.dcreg_register_pairs_normals.argtypes = [vp, C.c_int, fp, i64p, fp, i64p, C.c_int64, np_, dp, dp, C.c_int, C.c_int, cfgp, C.c_int, trp]
@@ -2169,6 +2175,42 @@ class Context:
         """dcreg_icp_run_voxels: icp_run_gicp's loop around linearize_voxels -> (result, logs); a log's rmse is the RMS Mahalanobis
         distance per effective point"""
         return self._run_logged("dcreg_icp_run_voxels", T0, method, cfg, log_capacity, "icp_run_voxels")
+
+    # ---- the fourth engine's many-frames form (include/dcreg.h: dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels) and its device
+    # seam (include/dcreg_debug.h: dcreg_voxels_batch_begin / _end)
+    def register_frames_voxels(self, frames, T0s, method, cfg, frame_normals=None, slots=0):
+        """dcreg_register_frames_voxels: register_frames with the fourth engine (keep_target_voxels first).  frame_normals =
+        normal_params(...) is the rule every frame's own normals are estimated with when set_option("voxels_source_cov", 1) is on - it is
+        required then - and is not read otherwise (None: a null pointer is passed).  Same arguments and records; each record is bitwise
+        set_source(frame) [+ keep_source_normals(frame_normals)] + icp_run_voxels(T0)."""
+        if frame_normals is not None:
+            _check_normal_params(frame_normals, "register_frames_voxels")
+        return self._register_frames("dcreg_register_frames_voxels", frames, T0s, method, cfg, slots, "register_frames_voxels",
+                                     extra_args=(None if frame_normals is None else C.byref(frame_normals),))
+
+    def icp_run_trials_voxels(self, T0s, method, cfg):
+        """dcreg_icp_run_trials_voxels: icp_run_trials with the fourth engine (kept voxels first, in mode 1 kept source normals too); each
+        record is bitwise icp_run_voxels from its pose"""
+        return self._run_trials("dcreg_icp_run_trials_voxels", T0s, method, cfg, "icp_run_trials_voxels")
+
+    def voxels_batch_begin(self, Ts, frame_ids=None, params=None, slot=0):
+        """dcreg_voxels_batch_begin: one launch over the poses Ts ([n, 4, 4]); pose i linearises frame frame_ids[i] of the loaded frames
+        (None: the own source) against the kept voxels.  Nothing is kept between launches: there are no state_ids.  -> the number of
+        poses, for voxels_batch_end"""
+        params = self._vlin_params(params, "voxels_batch_begin")
+        Rs, ts, n = _poses_arg(Ts)
+        fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
+        self._check(self._L.dcreg_voxels_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts),
+                                                     None if fids is None else fids.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(params)),
+                    "dcreg_voxels_batch_begin")
+        return n
+
+    def voxels_batch_end(self, n_poses, slot=0):
+        """dcreg_voxels_batch_end -> one dict per pose, as linearize_voxels returns"""
+        return self._batch_end("dcreg_voxels_batch_end", n_poses, slot)
+
+    def voxels_batch(self, Ts, frame_ids=None, params=None, slot=0):
+        return self.voxels_batch_end(self.voxels_batch_begin(Ts, frame_ids, params, slot), slot)
 
     # ---- the keyframe store (include/dcreg.h: dcreg_keyframes_*): clouds kept on the device by index, submaps assembled from (id, pose) members
     def keyframes_reset(self):

@@ -712,6 +712,14 @@ struct OneNnBatch {
 int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
                        const int32_t *frame_ids, const int32_t *target_ids, const dcreg_lin_params *p,
                        int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), void (*launch)(dcreg_ctx *, const OneNnBatch &), const char *kernel_name);
+// one_nn_batch_queue: the slot plumbing behind those refusals, which the fourth engine's batched launch (voxel_icp.hip
+// dcreg_voxels_batch_begin) shares as it is - the slot's buffers sized for the largest cloud (n_max: the launch's largest), the pinned pose
+// and slice block and its upload, `launch` (it completes the record - the fields of the engine's own target stay zero until then - and
+// queues the engine's kernel), k_finalize, the result copy, the slot's event and the `failed` path.  state_ids == null: no warm slot is
+// read or written.  The caller has made every refusal, the slot's `pending` included
+int one_nn_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                       const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
+                       const char *kernel_name);
 // the warm slots of the batched form, sized for the own source, the loaded frames or the pairs' sources (dcreg_normals_reserve_slots,
 // dcreg_pairs_normals_reserve_slots)
 int one_nn_reserve_slots(dcreg_ctx *c, int64_t n_slots, dcreg_ctx::NormalIcpBufs::SlotsFor what);

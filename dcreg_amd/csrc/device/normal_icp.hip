@@ -226,9 +226,33 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
             seen[(size_t)sid] = 1;
         }
     }
-    HIP_TRY(c, hipSetDevice(c->device));
     // the whole map's index, wherever it lives (context.hpp roi_store): the window index stays as it is, active or not
     const dcreg_ctx::IndexSet &whole = c->roi_active ? c->roi_store : c->map;
+    return one_nn_batch_queue(c, slot, n_poses, R9, t3, state_ids, fs, frame_ids, target_ids, n_max, [&](OneNnBatch &L) {
+        L.g = pairs ? GridDev{} : whole.grid; L.normals = pairs ? ps.normals.data() : B.normals.data();
+        L.grids = pairs ? ps.d_nn_grids.data() : nullptr;
+        GridDev bound_grid = whole.grid;
+        if (pairs) bound_grid.h = p->search_radius;                 // (the rings come with every pose's target: only the radius' part is used)
+        L.bound = one_nn_bound(bound_grid, p->search_radius);
+        L.warm = B.slots.data(); L.warm_stride = (uint32_t)B.slot_stride;
+        L.p = p;
+        launch(c, L);
+    }, kernel_name);
+}
+
+// The slot plumbing of a batched launch, behind the engine's refusals (context.hpp): the slot's buffers sized for the largest cloud, the
+// pinned pose and slice block and its upload, the engine's kernel (`launch` completes the record and queues it), k_finalize, the result copy
+// and the slot's event.  n_max: the points of the launch's largest cloud.  A failure once something may be queued marks the launch's warm
+// slots empty.
+int one_nn_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                       const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
+                       const char *kernel_name) {
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    BatchSlot &S = B.batch[slot];
+    const bool pairs = target_ids != nullptr;
+    static const std::vector<uint2> no_slices;
+    const std::vector<uint2> &slice = fs ? fs->slice : no_slices;
+    HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t nbx = (uint32_t)((n_max + kLinBlock - 1) / kLinBlock);
     const size_t np = (size_t)n_poses, pose_bytes = np * sizeof(PoseArg), slice_bytes = frame_ids ? np * sizeof(uint2) : 0,
                  bytes = pose_bytes + slice_bytes + (pairs ? np * sizeof(uint32_t) : 0);
@@ -271,18 +295,13 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     };
     hipError_t e = hipMemcpyAsync(S.d_poses.data(), S.h_poses.data(), bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return failed(e, "the pose upload");
-    OneNnBatch L;
+    OneNnBatch L{};
     L.src = fs ? fs->src.data() : c->d_src.data(); L.n_src = (uint32_t)c->n_src;
     L.src_normals = fs ? fs->normals.data() : c->gicp.src_normals.data();
-    L.g = pairs ? GridDev{} : whole.grid; L.normals = pairs ? ps.normals.data() : B.normals.data();
-    L.grids = pairs ? ps.d_nn_grids.data() : nullptr; L.grid_ids = d_grid_ids;
+    L.grid_ids = d_grid_ids;
     L.poses = (const PoseArg *)S.d_poses.data(); L.slices = d_slices;
-    GridDev bound_grid = whole.grid;
-    if (pairs) bound_grid.h = p->search_radius;                 // (the rings come with every pose's target: only the radius' part is used)
-    L.bound = one_nn_bound(bound_grid, p->search_radius);
-    L.warm = B.slots.data(); L.warm_stride = (uint32_t)B.slot_stride;
-    L.partials = S.partials.data(); L.nbx = nbx; L.n_poses = n_poses; L.p = p;
-    launch(c, L);
+    L.partials = S.partials.data(); L.nbx = nbx; L.n_poses = n_poses;
+    launch(L);
     if ((e = hipGetLastError()) != hipSuccess) return failed(e, kernel_name);
     if (frame_ids) hipLaunchKernelGGL(k_finalize<true>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, d_slices);
     else hipLaunchKernelGGL(k_finalize<false>, dim3((unsigned)n_poses), dim3(kLinBlock), 0, c->stream, S.partials.data(), nbx, S.d_out.data(), 0ull, (const uint2 *)nullptr);

@@ -5,10 +5,14 @@
 //                  record, in mode 1 the coalesced float4 load of the point's own normal, the covariance, its Cholesky factor and W = L^-1;
 //                  then the third engine's block tail (gicp.hpp glin_block_rows): three rows per point over the matrix cores, the block
 //                  row in LDS, added in wave order.  Its LDS is the staging area of the Gram pass and the waves' sums - no RunList
+//   k_vlin_batch   the same for many poses in ONE launch (dcreg_voxels_batch_begin: the engine of dcreg_register_frames_voxels): block
+//                  (x, pose), every pose its own cloud - a frame of the loaded frames or the context's source - and nothing else per pose
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_glin
 // vlin_run is the launch's own small run function: refusals, buffers, the dump block cut as one_nn_run cuts it, launch, k_finalize, wait.
 // It reads the source, the kept voxel map and - in mode 1 - the kept source normals; it neither reads nor writes warm words, neighbour
 // states, the window index (no roi_ensure) or the map's kept normals.  The block rows, the result row and the dump block are nicp's.
+// The batched form runs in the second engine's two launch slots (normal_icp.hip one_nn_batch_queue: buffers, pose and slice upload,
+// k_finalize, result copy, event); its refusals are vlin_run's, made here.  It keeps nothing either: no warm slots, no neighbour states.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.
 #include <cmath>
 #include <cstring>
@@ -74,9 +78,60 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4
     });
 }
 
+// Many poses in one launch: k_vlin as k_glin_batch is k_glin (gicp.hip).  Block (x, pose): pose = poses[blockIdx.y], read through a
+// block-uniform index; its cloud is slices[pose] = {first point, points} of src and - in mode 1 - of src_normals (a frame of the loaded
+// frames and that frame's kept normals: the same positions; a block past the end of a short frame's slice exits before it touches
+// anything) or, slices == null, the n_src points at src (the context's own source and its kept source normals).  The body is vlin_point
+// and glin_block_rows, unchanged; the block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the rows and
+// additions of the pose's single launch.  Nothing is kept between launches, so there are no warm words.
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin_batch(const float4 *__restrict__ src, uint32_t n_src, VoxMapDev vm,
+                                                                           const float4 *__restrict__ src_normals,
+                                                                           const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
+                                                                           VlinArgs a, double *__restrict__ partials, uint32_t n_blocks_x) {
+    __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const uint32_t pose_id = blockIdx.y;
+    if (slices) {                                    // (uniform per block: before anything is touched)
+        const uint2 sl = slices[pose_id];
+        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
+        src += sl.x; n_src = sl.y;
+        if (src_normals) src_normals += sl.x;        // (mode 0: null, and never read)
+    }
+    const PoseArg &P = poses[pose_id];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    uint8_t flag = 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    GlinPoint o;
+    if (i < n_src) {
+        const float4 s4 = src[i];
+        sx = s4.x; sy = s4.y; sz = s4.z;
+        VlinPoint x;
+        flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
+    }
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
+                    [](int, const double (&)[8]) {});
+}
+
 bool finite_n(const double *v, int n) {
     for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
     return true;
+}
+
+// the kept voxel map as the kernels read it, and the launch's arguments ("voxels_source_cov", "gicp_epsilon", "robust_kernel" and
+// "gicp_robust_scale" are read at every call)
+VoxMapDev vox_map_dev(const dcreg_ctx::VoxelMapBufs &M) {
+    VoxMapDev vm;
+    vm.recs = M.recs.data(); vm.keys = M.t_keys.data(); vm.vals = M.t_vals.data(); vm.mask = M.mask; vm.leaf = M.leaf;
+    for (int a = 0; a < 3; ++a) { vm.mn[a] = M.mn[a]; vm.mx[a] = M.mx[a]; }
+    return vm;
+}
+VlinArgs vlin_args(const dcreg_ctx *c) {
+    VlinArgs a;
+    a.source_cov = c->opt_voxels_source_cov; a.c = 1.0 - c->opt_gicp_epsilon;
+    a.robust = c->opt_robust_kernel; a.robust_c2 = c->opt_gicp_robust_scale * c->opt_gicp_robust_scale;
+    return a;
 }
 
 int vlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_vlin_debug *dbg) {
@@ -109,12 +164,8 @@ int vlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     unsigned char *b = B.dbg.data();
     for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
         if (fields[k].host) std::memcpy(fields[k].dev, &b, sizeof(b));
-    VoxMapDev vm;
-    vm.recs = M.recs.data(); vm.keys = M.t_keys.data(); vm.vals = M.t_vals.data(); vm.mask = M.mask; vm.leaf = M.leaf;
-    for (int a = 0; a < 3; ++a) { vm.mn[a] = M.mn[a]; vm.mx[a] = M.mx[a]; }
-    VlinArgs a;
-    a.source_cov = mode; a.c = 1.0 - c->opt_gicp_epsilon;
-    a.robust = c->opt_robust_kernel; a.robust_c2 = c->opt_gicp_robust_scale * c->opt_gicp_robust_scale;
+    const VoxMapDev vm = vox_map_dev(M);
+    const VlinArgs a = vlin_args(c);
     PoseArg P;
     std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
     P.state = kNoIdx; P.fresh = 1;
@@ -134,7 +185,48 @@ int vlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     return DCREG_OK;
 }
 
+// The batched launch (include/dcreg_debug.h: dcreg_voxels_batch_begin): every refusal in the header's order - vlin_run's and the launch
+// slots' - before anything is queued, then the shared slot plumbing with k_vlin_batch as its kernel.  The options are read here.
+int vlin_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *frame_ids, const dcreg_lin_params *p) {
+    if (!c) return DCREG_E_INVALID;
+    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
+    if (!R9 || !t3 || !p || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    if (c->nicp.batch[slot].pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the voxel linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
+    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    if ((c->roi_active ? c->roi_store : c->map).n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    const dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    if (!M.kept) { c->fail("no kept voxels: dcreg_target_voxels_keep first"); return DCREG_E_STATE; }
+    dcreg_ctx::FrameSet *fs = frame_ids ? &c->frames : nullptr;
+    int64_t n_max = c->n_src;                         // points of the launch's largest cloud
+    if (fs) {
+        const std::vector<uint2> &slice = fs->slice;
+        if (slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+        n_max = 0;
+        for (int i = 0; i < n_poses; ++i) {
+            const int32_t f = frame_ids[i];
+            if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
+            n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
+        }
+    } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    const VlinArgs a = vlin_args(c);
+    if (a.source_cov && fs && !fs->normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
+    if (a.source_cov && !fs && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    const VoxMapDev vm = vox_map_dev(M);
+    return one_nn_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, frame_ids, nullptr, n_max, [&](OneNnBatch &L) {
+        hipLaunchKernelGGL(k_vlin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, vm,
+                           a.source_cov ? L.src_normals : (const float4 *)nullptr, L.poses, L.slices, a, L.partials, L.nbx);
+    }, "the k_vlin_batch launch");
+}
+
 }  // namespace
+
+// "voxels_source_cov" for the engine's batched calls (engine.cpp reads it once when a call starts)
+int voxels_source_cov(const dcreg_ctx *c) { return c->opt_voxels_source_cov; }
+
 }  // namespace dcreg
 
 using namespace dcreg;
@@ -143,6 +235,11 @@ extern "C" {
 int dcreg_linearize_voxels(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out) {
     return vlin_run(c, R, t, p, out, nullptr);
 }
+int dcreg_voxels_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *frame_ids,
+                             const dcreg_lin_params *p) {
+    return vlin_batch_begin(c, slot, n_poses, R9, t3, frame_ids, p);
+}
+int dcreg_voxels_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
 int dcreg_linearize_voxels_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
                                  dcreg_vlin_debug *dbg) {
     if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }

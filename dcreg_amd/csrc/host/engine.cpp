@@ -25,6 +25,7 @@ namespace dcreg {
 bool invertSpd6(const double H[36], double inv[36]);
 int analyzeStep(const double H[36], int detection, int handling, const dcreg_config &cfg, dcreg_analysis &res);    // solver.cpp
 void analyzeFinish(const double H[36], dcreg_analysis &res, int owed);
+int voxels_source_cov(const dcreg_ctx *);                                                                          // voxel_icp.hip: "voxels_source_cov"
 }
 
 namespace {
@@ -331,8 +332,9 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // the third (dcreg_icp_run_trials_gicp, dcreg_register_frames_gicp, dcreg_register_pairs_gicp) - dcreg_gicp_batch_begin / _end on the same
 // launch and warm slots, the frames' kept normals beside the frames; with pairs the begin calls are dcreg_pairs_normals_batch_begin /
 // dcreg_pairs_gicp_batch_begin (every pose against its own target and that target's kept normals) and the warm slots are sized for the
-// pairs' sources; everything else is shared
-enum class Engine { planes, normals, gicp };
+// pairs' sources; Engine::voxels, the fourth (dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels) - dcreg_voxels_batch_begin / _end
+// on the same launch slots; a voxel launch keeps nothing, so there is nothing to reserve or reset; everything else is shared
+enum class Engine { planes, normals, gicp, voxels };
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
                            int64_t first_pair = -1, Engine engine = Engine::planes) {
@@ -368,7 +370,12 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
                            dcreg_normals_batch_end, label};
     };
     const EngineCalls E =
-        engine == Engine::gicp ? one_nn(dcreg_gicp_batch_begin, dcreg_pairs_gicp_batch_begin, "_gicp")
+        engine == Engine::voxels ? EngineCalls{[](int) { return (int)DCREG_OK; }, [](int) {},
+                                               [&](int gi, int nl, Group &G) {
+                                                   return dcreg_voxels_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), frames ? G.fids.data() : nullptr, &prm);
+                                               },
+                                               dcreg_voxels_batch_end, "_voxels"}
+        : engine == Engine::gicp ? one_nn(dcreg_gicp_batch_begin, dcreg_pairs_gicp_batch_begin, "_gicp")
         : engine == Engine::normals ? one_nn(dcreg_normals_batch_begin, dcreg_pairs_normals_batch_begin, "_normals")
         : pairs ? EngineCalls{[&](int n) { return dcreg_pairs_reserve_states(ctx, n); }, [&](int si) { dcreg_pairs_reset_state(ctx, si); },
                               [&](int gi, int nl, Group &G) {
@@ -603,6 +610,35 @@ int dcreg_register_frames_gicp(dcreg_ctx *ctx, int n_frames, const float *xyz, c
     if (frame_offsets[n_frames] > 0)                                                  // (all frames empty: nothing to estimate, nothing to run)
         if (int rc = dcreg_frames_normals_keep(ctx, frame_normals, nullptr)) return rc;
     return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, frame_points(n_frames, frame_offsets).data(), -1, Engine::gicp);
+}
+
+// The fourth engine's forms (include/dcreg.h): the same checks and the same core with the launches of voxel_icp.hip.  "voxels_source_cov"
+// is read once here: in mode 1 the frames' own normals are estimated in one batched pass behind the load, in mode 0 nothing of the kind
+// runs and frame_normals is not read.  The state refusals carry the single-pose call's text
+static const char *const kNoKeptVoxels = "no kept voxels: dcreg_target_voxels_keep first";
+int dcreg_icp_run_trials_voxels(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
+                                const dcreg_config *cfg, dcreg_trial_result *results) {
+    if (!ctx || !R0 || !t0 || !cfg || !results || n_trials < 0) return DCREG_E_INVALID;
+    if (n_trials == 0) return DCREG_OK;
+    dcreg_index_info info;
+    dcreg_index_info_get(ctx, &info);
+    if (info.n_target <= 0) { dcreg_set_error_message(ctx, kNoTarget); return DCREG_E_STATE; }
+    if (dcreg_target_voxels_kept(ctx) <= 0) { dcreg_set_error_message(ctx, kNoKeptVoxels); return DCREG_E_STATE; }
+    if (dcreg::voxels_source_cov(ctx) && dcreg_source_normals_kept(ctx) != 1) { dcreg_set_error_message(ctx, "no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    return run_trials_core(ctx, n_trials, R0, t0, detection, handling, cfg, results, 0, nullptr, -1, Engine::voxels);
+}
+
+int dcreg_register_frames_voxels(dcreg_ctx *ctx, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                                 const dcreg_normal_params *frame_normals, const double *R0, const double *t0, int detection, int handling,
+                                 const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    const bool mode1 = ctx && dcreg::voxels_source_cov(ctx) != 0;
+    if (int rc = frames_call_check(ctx, n_frames, frame_offsets, stride_floats, R0, t0, cfg, results, false, mode1, frame_normals)) return rc;
+    if (n_frames == 0) return DCREG_OK;
+    if (dcreg_target_voxels_kept(ctx) <= 0) { dcreg_set_error_message(ctx, kNoKeptVoxels); return DCREG_E_STATE; }
+    if (int rc = dcreg_frames_load(ctx, n_frames, xyz, frame_offsets, stride_floats)) return rc;     // (non-finite coordinates: refused here, nothing queued)
+    if (mode1 && frame_offsets[n_frames] > 0)                                         // (all frames empty: nothing to estimate, nothing to run)
+        if (int rc = dcreg_frames_normals_keep(ctx, frame_normals, nullptr)) return rc;
+    return run_trials_core(ctx, n_frames, R0, t0, detection, handling, cfg, results, slots, frame_points(n_frames, frame_offsets).data(), -1, Engine::voxels);
 }
 
 // Scan pairs (include/dcreg.h): everything is checked before anything runs - offsets here, the sources when they are loaded (all of them,

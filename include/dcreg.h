@@ -28,6 +28,7 @@
  *   registration against per-voxel Gaussians (voxelised GICP / NDT; not in the reference)
  *       one distribution per voxel kept beside the map                           -> dcreg_target_voxels_keep / _get / _kept / _drop
  *       one linearisation, the engine                                            -> dcreg_linearize_voxels, dcreg_icp_run_voxels
+ *       many frames / many start poses in one call                               -> dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels
  *   raw clouds (not in the reference, which reads clouds a pcl::VoxelGrid filtered beforehand)
  *       voxel-grid downsampling of many clouds                                   -> dcreg_voxel_downsample[_device]
  *       ... of one cloud, kept as the source / target                            -> dcreg_set_source_voxel[_device],
@@ -234,7 +235,7 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_pairs, dcreg_register_pairs_normals, dcreg_register_pairs_gicp, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
+ * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels, dcreg_register_pairs, dcreg_register_pairs_normals, dcreg_register_pairs_gicp, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
  * the launches, and dcreg_debug.h's dcreg_frames_load, dcreg_normals_reserve_slots (a pending launch slot of dcreg_normals_batch_begin counts as a slot in flight), dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
@@ -1145,8 +1146,11 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  * neighbour states, the window index or the map's kept normals: it may be interleaved with every other engine's calls without moving a
  * bit on either side.  DCREG_E_INVALID: null arguments, a non-finite pose, a parameterization other than SO3.  DCREG_E_STATE: no target,
  * no source, no kept voxels, in mode 1 no kept source normals, a linearisation in flight.  Waits for the stream.
- * Not provided: batched forms (trials, frames, pairs), neighbour-voxel correspondences (7 / 27 voxels per point), a voxel map that
- * follows map updates, sharded / Euler forms, a caller-supplied voxel map, the runner's YAML. */
+ * The batched forms - many trials of the own source, many frames - are dcreg_icp_run_trials_voxels and dcreg_register_frames_voxels below.
+ * Not provided: scan pairs through this engine (each target would need a voxel map of its own, built in batches, and a pairs plan that
+ * skips the index build; the engine is also density-hungry on scan-sized targets: DESIGN.md sections 21 and 22), neighbour-voxel
+ * correspondences (7 / 27 voxels per point), a voxel map that follows map updates, sharded / Euler forms, a caller-supplied voxel map,
+ * the runner's YAML. */
 typedef struct dcreg_voxel_map_params {
     double leaf;      /* voxel edge, metres (default 1.0) */
     double epsilon;   /* floor of the normalised eigenvalues (default 1e-3) */
@@ -1259,8 +1263,8 @@ int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int 
 /* The same loop with dcreg_linearize_voxels as its linearisation (dcreg_target_voxels_keep first, DCREG_E_STATE without it; with
  * "voxels_source_cov" = 1 kept source normals too): one waited launch per iteration, the same aborts, fitness, convergence test, log
  * records, covariance and status codes, the same host step.  rmse is the RMS Mahalanobis distance per effective point, as for
- * dcreg_icp_run_gicp.  Of the configuration's linearisation parameters none is read.  One pose per call; no batched, sharded / RCCL or
- * Euler form of this engine. */
+ * dcreg_icp_run_gicp.  Of the configuration's linearisation parameters none is read.  One pose per call (many at once:
+ * dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels); no sharded / RCCL or Euler form of this engine. */
 int dcreg_icp_run_voxels(dcreg_ctx *, const double R0[9], const double t0[3], int detection, int handling,
                          const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
@@ -1375,6 +1379,34 @@ int dcreg_register_frames_gicp(dcreg_ctx *, int n_frames, const float *xyz, cons
                                int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
 int dcreg_icp_run_trials_gicp(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection, int handling,
                               const dcreg_config *, dcreg_trial_result *results);
+
+/* ... and for the fourth engine (dcreg_icp_run_voxels: rows against the map's kept voxel distributions - the cheap stage with the wide
+ * basin, for many candidates at once: relocalisation hypotheses, loop-closure candidates, a recorded drive on a prior map, Monte-Carlo
+ * starts).  Arguments, argument rules, slots, record fields and amortised time_ms are those of dcreg_register_frames /
+ * dcreg_icp_run_trials: offsets start at 0 and do not decrease, stride_floats >= 3, non-finite coordinates are refused (DCREG_E_INVALID,
+ * nothing runs), an empty frame gets status 3, n_frames == 0 / n_trials == 0 does nothing, errors are taken against cfg->gt_matrix.
+ * Every iteration of a group of registrations is ONE batched launch (dcreg_debug.h: dcreg_voxels_batch_begin), and results[f] is bitwise
+ * what dcreg_set_source(frame f) [+ dcreg_source_normals_keep(frame_normals) in mode 1] + dcreg_icp_run_voxels(R0 f, t0 f) give on a
+ * context with the same map, kept voxels and options - final_transform, iterations, converged, status (1: n_eff < 10, 2: a non-finite
+ * step), final_rmse, final_fitness (of the frame's own point count), corr_num, H_upper and degenerate_mask; for trials,
+ * dcreg_icp_run_voxels of the context's own source from each pose.  A frame with fewer than 10 effective points (points that fall into a kept
+ * voxel) ends with status 1.
+ * "voxels_source_cov" is read once when the call starts.  Mode 0: frame_normals is not read and may be NULL, no normals pass runs, and
+ * the map needs no kept normals.  Mode 1, frames form: frame_normals is checked as dcreg_register_frames_gicp checks it (DCREG_E_INVALID,
+ * before the empty call returns), and all frames' normals are then estimated in one batched pass behind the load
+ * (dcreg_frames_normals_keep); a frame with fewer than k points has no normals and ends with status 1.  Mode 1, trials form: no kept
+ * source normals is DCREG_E_STATE.  "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at every launch, as by the
+ * single-pose call.
+ * DCREG_E_STATE, results untouched: no target, no kept voxels (dcreg_target_voxels_keep first; every change of the map's points drops
+ * them), a linearisation in flight.  The context's own source and its kept normals, every warm and neighbour state of the other engines,
+ * the window index, the map's kept normals and the kept voxels are left as they were (the frames form replaces the frames a previous
+ * dcreg_register_frames* call left on the device, and their kept normals, as between the other engines).  Not provided: scan pairs
+ * through this engine (see the voxel section above), the sharded / RCCL forms, the Euler form. */
+int dcreg_register_frames_voxels(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
+                                 const dcreg_normal_params *frame_normals, const double *R0_9, const double *t0_3, int detection,
+                                 int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
+int dcreg_icp_run_trials_voxels(dcreg_ctx *, int n_trials, const double *R0_9, const double *t0_3, int detection, int handling,
+                                const dcreg_config *, dcreg_trial_result *results);
 
 /* Many scan pairs registered in one call, each against a target of its own (loop-closure candidates against their submaps, scan-to-scan
  * odometry of a recorded drive, multi-session alignment, accuracy evaluation over a dataset of pairs): pair p = source points

@@ -243,6 +243,26 @@ int dcreg_gicp_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9,
 int dcreg_gicp_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
 int dcreg_normal_params_check(dcreg_ctx *, const dcreg_normal_params *);
 
+/* internal: the device seam of dcreg_register_frames_voxels and dcreg_icp_run_trials_voxels (engine.cpp): dcreg_linearize_voxels for
+ * n_poses poses in ONE launch (voxel_icp.hip k_vlin_batch).  Pose i linearises frame frame_ids[i] of the frames dcreg_frames_load left on
+ * the device - in mode 1 with that frame's kept normals (dcreg_frames_normals_keep / _set) - or, frame_ids == NULL, the context's own
+ * source (mode 1: with its kept source normals) against the kept voxel map; its 31 sums are bitwise what dcreg_set_source(that cloud)
+ * [+ dcreg_source_normals_keep / _set] + dcreg_linearize_voxels(pose i) return.  There are no state_ids: a voxel launch keeps nothing.
+ * It runs in the two launch slots of dcreg_normals_batch_begin - they ARE the second engine's: a pending slot of any of the three
+ * engines refuses the others, and every call that dcreg_normals_batch_begin's pending slot refuses (dcreg_set_source*,
+ * dcreg_target_voxels_keep / _drop, dcreg_linearize_voxels, dcreg_frames_load, the map updates, ...) is refused meanwhile; _end waits for
+ * that slot's results only.  "voxels_source_cov", "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at _begin.  Of the
+ * parameter block only parameterization is read (search_radius is not, as in the single-pose call).  The launch neither reads nor writes
+ * warm words, warm slots or neighbour states, the window index (it is neither made active nor deactivated) or the map's kept normals.
+ * Refusals, in this order, nothing queued on any: a null context, a bad slot, null R9 / t3 / parameters or n_poses < 1, n_poses > 65535
+ * (DCREG_E_INVALID); a gated or pending launch of the first engine, the slot already pending (DCREG_E_STATE); a parameterization other
+ * than SO3, a non-finite pose (DCREG_E_INVALID); no target, no kept voxels (DCREG_E_STATE); with frame_ids: no frames loaded
+ * (DCREG_E_STATE), an id outside the load or naming an empty frame (DCREG_E_INVALID); without: no source (DCREG_E_STATE); in mode 1 no
+ * kept frame normals / no kept source normals (DCREG_E_STATE). */
+int dcreg_voxels_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3,
+                             const int32_t *frame_ids /* NULL: the context's own source */, const dcreg_lin_params *);
+int dcreg_voxels_batch_end(dcreg_ctx *, int slot, dcreg_lin_out *outs);
+
 /* internal: the device seam of dcreg_register_pairs (engine.cpp).  dcreg_pairs_plan cuts the pairs into build batches of their targets
  * (batch b = pairs [batch_end[b - 1], batch_end[b]); option "pairs_max_bytes"); dcreg_pairs_sources_load is dcreg_frames_load for the
  * pairs' sources (kept apart from the context's frames); dcreg_pairs_build indexes the targets of one batch (host memory, offsets from 0,
