@@ -1127,7 +1127,7 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  *
  * The rule of one linearisation (dcreg_linearize_voxels).  Of the parameter block only parameterization is read (DCREG_PARAM_SO3, else
  * DCREG_E_INVALID); there is no radius gate - a point is at most a voxel diagonal from its mean.  Options, read at every call:
- * "voxels_source_cov" = 0 (default) point-to-distribution, 1 distribution-to-distribution with the source's plane covariance from its
+ * "voxels_source_cov" = 0 (default) point-to-distribution (any value but 0 or 1: DCREG_E_INVALID, the old value stays), 1 distribution-to-distribution with the source's plane covariance from its
  * kept normals (dcreg_source_normals_keep / _set) and eps = "gicp_epsilon" as the third engine reads it, c = 1 - eps; "robust_kernel" and
  * "gicp_robust_scale" exactly as dcreg_linearize_gicp applies them (one k per point from the squared Mahalanobis distance, slots 0..6
  * of all three rows scaled, slot 7 left; kernel 0 multiplies nothing).  For each source point p (floats, widened to double):

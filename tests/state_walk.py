@@ -2,8 +2,10 @@
 fake context (tests/test_state_walk_model.py runs all of it without a device, tests/test_gpu_state_walk.py on one).
 
 The MODEL holds the map (float32, index order), the radius hint of the last set_target, the source, the options, the kept normals of map,
-source and loaded frames (by `keep` with its parameters or by `set` with the array), the clouds added to the places database and to the
-keyframe store, and whether a gate is pending.  Every transition rule is one sentence of include/dcreg.h (cited as `h:LINE`) or of
+source and loaded frames (by `keep` with its parameters or by `set` with the array), the parameters of the kept voxel map (`vm`: whether
+a keep keeps a voxel at all is tests/voxels_ref.py's answer), the clouds added to the places database and to the keyframe store, and
+whether a gate is pending.  The options hold the robust kernel, its scales, gicp_epsilon and the voxel mode too: they change results, are
+read at every launch, and go into context B with the rest.  Every transition rule is one sentence of include/dcreg.h (cited as `h:LINE`) or of
 include/dcreg_debug.h (`d:LINE`).  Expected clouds come from the bitwise numpy references the suite already has (transform and crop_ref of
 test_gpu_map_update.py, voxel_ref, outliers_ref, visibility_ref, keyframes_ref); the deskew forms, specified to one ulp only, take theirs
 from the cloud form on a helper context (`Model.deskew`: h:417-418 promises that the two are bitwise equal).
@@ -23,6 +25,8 @@ import keyframes_ref as kr
 import normal_icp_scenes as S
 import outliers_ref as orf
 import visibility_ref as vr
+import voxels_ref as vx
+import voxels_scenes as vxs
 from dcreg_amd import api
 from test_gpu_map_update import crop_ref, transform
 from test_gpu_normals import OPTS_WINDOW
@@ -33,9 +37,17 @@ RADIUS = S.RADIUS
 FRAME_SIZES = (1, 63, 257, 1000)
 WINDOW_OFF = [("max_table_entries", 1 << 30), ("roi_index", 1), ("roi_margin", 20.0)]     # the defaults (h:165, h:190, h:185)
 TOGGLES = {"normals_follow": (0, 1), "map_update": (0, 1), "warm_start": (0, 1), "use_certificates": (0, 1), "one_wave": (0, 1, 2),
-           "advance": (0, 1, 2), "team_pass": (0, 1, 2), "dispatch_order": (0, 1), "gap_field": (0, 1)}
+           "advance": (0, 1, 2), "team_pass": (0, 1, 2), "dispatch_order": (0, 1), "gap_field": (0, 1),
+           # the options that DO change results, each read at every launch (h:182-192, h:1129-1133): the model carries them into context B
+           "robust_kernel": (0, 1, 2, 3), "voxels_source_cov": (0, 1), "robust_scale": (0.05, 0.3), "gicp_robust_scale": (0.7, 2.0),
+           "gicp_epsilon": (1e-3, 1e-2)}
 DEFAULTS = dict({"normals_follow": 0, "map_update": 1, "warm_start": 1, "use_certificates": 1, "one_wave": 1, "advance": 1, "team_pass": 1,
-                 "dispatch_order": 1, "gap_field": 1}, **dict(WINDOW_OFF))
+                 "dispatch_order": 1, "gap_field": 1, "robust_kernel": 0, "voxels_source_cov": 0, "robust_scale": 0.1, "gicp_robust_scale": 1.0,
+                 "gicp_epsilon": 1e-3}, **dict(WINDOW_OFF))
+# values that dcreg_set_option refuses with DCREG_E_INVALID, the old value staying (h:186-187, h:189, h:1130, h:182)
+REFUSED_OPTIONS = (("robust_kernel", 4), ("robust_scale", 0), ("voxels_source_cov", 2), ("gicp_epsilon", 2))
+VOXEL_PARAMS = ((1.0, 1e-3, 6), (1.0, 1e-3, 3), (0.5, 1e-2, 3))         # (leaf, epsilon, min_points) of dcreg_target_voxels_keep
+SPAN_LEAF = 1e-7                                                        # a leaf at which every map here spans 2^21 voxels or more (h:1125)
 PLACE = dict(n_rings=8, n_sectors=24, max_range=12.0, min_range=0.0, z_offset=2.0)
 VIS = dict(rows=16, cols=128, elev_min=-0.5, elev_max=0.5, min_range=0.3, max_range=30.0, margin_abs=0.2, margin_rel=0.01, window=1)
 TWIST = (0.002, -0.001, 0.02, 0.3, 0.05, 0.01)
@@ -145,6 +157,22 @@ def thinned(ref_map, q, min_spacing):
     return q[~(d2 < np.float32(min_spacing * min_spacing))]
 
 
+def vmap_of(xyz, p):
+    """the reference voxel map of a cloud for p = (leaf, epsilon, min_points) (tests/voxels_ref.py)"""
+    return memo("vmap", lambda: vx.voxel_map(xyz, *p), xyz, tuple(p))
+
+
+def spans_too_far(xyz, leaf):
+    """h:1124-1125: a map that spans 2^21 or more voxels on an axis"""
+    v = vx.voxel_of(xyz, leaf)
+    return bool(((v.max(axis=0) - v.min(axis=0)) >= 2.0 ** 21).any())
+
+
+def vlin_of(vmap, src, T, mode, normals, eps, kind, scale):
+    return memo("vlin", lambda: vx.linearize(vmap, src, T, mode, normals, eps, kind, scale), vmap["coords"], vmap["mean"], vmap["cov"], vmap["leaf"],
+                src, np.asarray(T, np.float64), mode, None if normals is None else np.asarray(normals), eps, kind, scale)
+
+
 def given_normals(n, seed):
     a = np.array(S.unit_normals(n, seed))
     a[::17, 0] = np.nan                   # h:904: a non-finite component means "this point has no normal"
@@ -162,6 +190,7 @@ class Model:
         self.gate = False
         self.follow_n = 0                         # dcreg_target_normals_follow_info().n_target
         self.reserved = 0
+        self.vm = None                            # (leaf, epsilon, min_points) of the last accepted keep that kept a voxel
 
     # ---- the rules
     def new_target(self, xyz, radius):
@@ -169,14 +198,17 @@ class Model:
         sentence this suite added) the follow record is cleared"""
         self.map, self.radius, self.tn, self.follow_n = np.ascontiguousarray(xyz[:, :3], np.float32), radius, None, 0
         self.reserved = 0                         # h:251 dcreg_set_target / dcreg_set_source drop all states
+        self.vm = None                            # h:1121-1122 every call that changes the map's points drops the kept voxels
 
     def updated_target(self, xyz):
         """h:270-272 the map is the updated cloud; h:957 an update that changes nothing leaves normals and info; h:942-947 the kept
-        normals follow when the option is on and they came from keep, h:906-908 otherwise they are dropped; h:967 n_target"""
+        normals follow when the option is on and they came from keep, h:906-908 otherwise they are dropped; h:967 n_target; h:1121-1122
+        the kept voxels are dropped whatever normals_follow says ("Nothing follows the map")"""
         if len(xyz) == len(self.map) and np.array_equal(xyz.view(np.uint32), self.map.view(np.uint32)):
             return
         self.map, self.follow_n = np.ascontiguousarray(xyz, np.float32), len(xyz)
         self.reserved = 0                         # h:273-274 an update that changes the map drops what dcreg_set_target drops
+        self.vm = None
         if not (self.tn and self.tn[0] == "keep" and self.opts["normals_follow"]):
             self.tn = None
 
@@ -193,6 +225,14 @@ class Model:
 
     def members(self, spec):
         return [(i, poses()[p]) for i, p in spec]
+
+    def vmap(self):
+        """the reference's kept voxels of the map (None: no member)"""
+        return None if self.vm is None else vmap_of(self.map, self.vm)
+
+    def voxels_ready(self):
+        """h:1147-1148 what dcreg_linearize_voxels needs: target, source, kept voxels and in mode 1 kept source normals"""
+        return bool(self.map is not None and self.src is not None and self.vm and (not self.opts["voxels_source_cov"] or self.sn))
 
 
 def rc_of(e):
@@ -464,6 +504,30 @@ def op_drop_source_normals(m, c):
     return OK
 
 
+@op("member")
+def op_keep_target_voxels(m, c, p=(1.0, 1e-3, 3), span=0):
+    """span: the leaf SPAN_LEAF, at which the map spans more voxels than the pass allows: refused, the member as it was (h:1124-1125)"""
+    if span:
+        p = (SPAN_LEAF,) + tuple(p[1:])
+    want = E_STATE if no_target(m) else E_INVALID if spans_too_far(m.map, p[0]) else OK        # h:1126 no target
+    if bool(span) != (want == E_INVALID):
+        return None                                                  # (a map too small, or too wide, for the form asked for)
+    info = call(m, c, want, lambda: c.keep_target_voxels(api.voxel_map_params(*p)))
+    if want == OK:
+        n_kept = vmap_of(m.map, p)["n_kept"]
+        if info is not None and info["n_kept"] != n_kept:
+            raise AssertionError("keep_target_voxels%r kept %d voxels, the reference %d" % (tuple(p), info["n_kept"], n_kept))
+        m.vm = tuple(p) if n_kept else None                          # h:1114 a keep that keeps no voxel succeeds and leaves no member
+    return want
+
+
+@op("member")
+def op_drop_target_voxels(m, c):
+    call(m, c, OK, lambda: c.drop_target_voxels())
+    m.vm = None                                                      # h:1114 _drop frees the member
+    return OK
+
+
 def frame_keys(sizes):
     return tuple(("frame", n) for n in sizes)
 
@@ -580,9 +644,11 @@ def op_reset_warm_state(m, c, state=-1):
 
 @op("option")
 def op_set_option(m, c, key="normals_follow", value=1):
-    call(m, c, OK, lambda: c.set_option(key, value))                 # h:140 results are identical whatever their values
-    m.opts[key] = value
-    return OK
+    want = E_INVALID if (key, value) in REFUSED_OPTIONS else OK      # (REFUSED_OPTIONS has the lines): the old value stays
+    call(m, c, want, lambda: c.set_option(key, value))               # h:144 results are identical whatever their values - but for those of
+    if want == OK:                                                   # TOGGLES' second line, which the model carries into context B
+        m.opts[key] = value
+    return want
 
 
 @op("option")
@@ -779,8 +845,76 @@ def op_icp_run_trials_gicp(m, c, first=0):
     return want
 
 
+# ---- the fourth engine (h:1128-1149, h:1263-1268, h:1383-1404) and the pair forms of the second and third (h:1428-1446)
+@op("history")
+def op_linearize_voxels(m, c, pose=0):
+    want = OK if m.voxels_ready() else E_STATE                       # h:1147-1148 no target, no source, no kept voxels, mode 1: no source normals
+    call(m, c, want, lambda: c.linearize_voxels(poses()[pose], api.default_lin_params(RADIUS)))
+    return want
+
+
+@op("history")
+def op_icp_run_voxels(m, c, pose=0):
+    if not ready(m):
+        return None
+    want = OK if m.voxels_ready() else E_STATE                       # h:1263-1264 dcreg_target_voxels_keep first; mode 1: kept source normals too
+    call(m, c, want, lambda: c.icp_run_voxels(poses()[pose], "Ours", cfg_of()))
+    return want
+
+
+@op("history")
+def op_icp_run_trials_voxels(m, c, first=0, bad=0):
+    if not ready(m):
+        return None
+    T = frame_poses(4, first)
+    if bad:
+        T[2, 0, 3] = np.inf
+    want = E_STATE if not m.voxels_ready() else E_INVALID if bad else OK       # h:1397-1401; h:226-228 a non-finite pose of any of its n_poses
+    call(m, c, want, lambda: c.icp_run_trials_voxels(T, "Ours", cfg_of()))
+    return want
+
+
+@op("history")
+def op_register_frames_voxels(m, c, sizes=(63, 257, 1), first=0, bad=0):
+    """mode 1 ("voxels_source_cov" as the call finds it, h:1394): the frames' normals are estimated behind the load with k = 5"""
+    keys = frame_keys(sizes)
+    if bad:
+        keys = (("nan", keys[0]),) + keys[1:]
+    mode = m.opts["voxels_source_cov"]
+    want = E_STATE if no_target(m) or not m.vm else E_INVALID if bad else OK   # h:1400-1401, before the load; h:1386-1387 non-finite coordinates
+    call(m, c, want, lambda: c.register_frames_voxels(frames_of(keys), frame_poses(len(keys), first), "Ours", cfg_of(),
+                                                      frame_normals=np_params((5, 0.0)) if mode else None, slots=2))
+    if want == OK:
+        m.loaded(keys, ("keep", (5, 0.0)) if mode else None)         # h:1402-1403 replaces the frames and their kept normals; h:1396-1397
+    elif want == E_INVALID:
+        m.fn = None                                                  # d:206
+    return want
+
+
+def _pairs(bad):
+    src = [cloud(("frame", 63)), cloud(("frame", 257)), cloud(("nan", ("src",))) if bad else cloud(("src",))]
+    return src, [cloud(("tgt", 600)), cloud(("tgt", 1500)), cloud(("tgt", 2000))]
+
+
+@op("history")
+def op_register_pairs_normals(m, c, bad=0):
+    src, tgt = _pairs(bad)
+    want = E_INVALID if bad else OK                                  # h:1441-1446 leaves target, normals, source, states, frames and window
+    call(m, c, want, lambda: c.register_pairs_normals(src, tgt, frame_poses(3, 2), "Ours", cfg_of(), np_params((5, 0.0)), slots=2))
+    return want
+
+
+@op("history")
+def op_register_pairs_gicp(m, c, bad=0):
+    src, tgt = _pairs(bad)
+    want = E_INVALID if bad else OK                                  # h:1441-1446
+    call(m, c, want, lambda: c.register_pairs_gicp(src, tgt, frame_poses(3, 2), "Ours", cfg_of(), np_params((5, 0.0)), np_params((5, 0.0)), slots=2))
+    return want
+
+
 # ---- the gate: _gated_begin, one other call (refused with DCREG_E_STATE, h:221-226, changing nothing), then _gate_abort or _gate_open
-GATED_OTHERS = ("set_source", "set_target", "knn", "keep_target_normals", "frames_load", "reset_warm_state", "insert")
+GATED_OTHERS = ("set_source", "set_target", "knn", "keep_target_normals", "frames_load", "reset_warm_state", "insert",
+                "keep_target_voxels", "linearize_voxels")            # h:1126, h:1148 a linearisation in flight
 
 
 @op("gate")
@@ -799,7 +933,9 @@ def op_gated_other(m, c, which="knn"):
     fn = {"set_source": lambda: c.set_source(cloud(("frame", 63))), "set_target": lambda: c.set_target(cloud(("tgt", 600)), RADIUS),
           "knn": lambda: c.knn(cloud(("frame", 63)), k=1), "keep_target_normals": lambda: c.keep_target_normals(np_params((5, 0.0))),
           "frames_load": lambda: c.frames_load([cloud(("frame", 63))]), "reset_warm_state": lambda: c.reset_warm_state(-1),
-          "insert": lambda: c.insert(cloud(("pool", 0, 50)), poses()[5])}[which]
+          "insert": lambda: c.insert(cloud(("pool", 0, 50)), poses()[5]),
+          "keep_target_voxels": lambda: c.keep_target_voxels(api.voxel_map_params(*VOXEL_PARAMS[1])),
+          "linearize_voxels": lambda: c.linearize_voxels(poses()[0], api.default_lin_params(RADIUS))}[which]
     call(m, c, E_STATE, fn)                                          # h:221-226; d:206 a load refused for a launch in flight drops nothing
     return E_STATE
 
@@ -818,7 +954,9 @@ def op_gate_end(m, c, open=0, pose=2):
 
 
 STATE_CLASSES = ("target", "source", "update", "member", "option")
-PROBE_KINDS = ("map", "flags", "lin", "nlin", "glin", "knn", "p2p", "normals", "frames", "frames_n", "frames_g", "batch", "icp", "places", "submaps")
+PROBE_KINDS = ("map", "flags", "lin", "nlin", "glin", "knn", "p2p", "normals", "frames", "frames_n", "frames_g", "batch", "icp", "places", "submaps",
+               "voxels", "vlin", "icp_v", "frames_v", "trials_v", "vbatch", "pairs")
+LAUNCHING = tuple(k for k in PROBE_KINDS if k not in ("map", "flags", "normals", "voxels"))      # the probes that launch an engine's kernels
 
 
 def apply(m, c, step):
@@ -876,7 +1014,16 @@ def _draw_args(rng, name, m):
         "keyframes_add_source": ({}, None),
         "reserve_warm_states": (dict(n=i(1, 4)), None),
         "reset_warm_state": (dict(state=r((-1, 0))), None),
-        "set_option": (dict(key="normals_follow", value=1), None),   # (walk_ops takes key and value off OPTION_DECK)
+        # (walk_ops takes key and value of an accepted set_option off OPTION_DECK)
+        "set_option": (dict(key="normals_follow", value=1), dict(zip(("key", "value"), r(REFUSED_OPTIONS)))),
+        "keep_target_voxels": (dict(p=r(VOXEL_PARAMS)), dict(p=VOXEL_PARAMS[1], span=1)),
+        "drop_target_voxels": ({}, None),
+        "linearize_voxels": (dict(pose=i(0, 5)), None),
+        "icp_run_voxels": (dict(pose=r((0, 2))), None),
+        "icp_run_trials_voxels": (dict(first=i(0, 5)), dict(bad=1)),
+        "register_frames_voxels": (dict(sizes=r(((63, 257, 1), (1000, 63))), first=i(0, 5)), dict(bad=1)),
+        "register_pairs_normals": ({}, dict(bad=1)),
+        "register_pairs_gicp": ({}, dict(bad=1)),
         "set_window": (dict(on=r((1, 1, 0))), None),
         "visibility_filter": (dict(spec=spec), None),
         "keyframe_submaps": (dict(spec=spec, leaf=r((None, 0.3))), None),
@@ -898,13 +1045,17 @@ def _draw_args(rng, name, m):
 
 
 WEIGHTS = {"target": 1, "source": 1, "update": 2, "member": 1, "option": 3, "scratch": 1, "history": 1, "gate": 2}
-# every value of every option but its default, and normals_follow off again: one fixed shuffle, entered where the seed says
-OPTION_DECK = [(k, v) for k in sorted(TOGGLES) for v in TOGGLES[k] if v != DEFAULTS[k]] + [("normals_follow", 0)]
+NAME_WEIGHTS = {"set_option": 8}            # (OPTION_DECK has twice the values it had when "option" got its 3)
+# every value of every option but its default, and normals_follow, the robust kernel and the voxel mode off again (a context warmed under a
+# kernel answers under none): one fixed shuffle, entered where the seed says
+OPTION_DECK = ([(k, v) for k in sorted(TOGGLES) for v in TOGGLES[k] if v != DEFAULTS[k]] +
+               [("normals_follow", 0), ("robust_kernel", 0), ("voxels_source_cov", 0)])
 PROLOGUE = ("keyframes_reset", "places_reset", "set_target", "set_source", "keyframes_add", "places_add_clouds")
 STATE_REFUSALS = ("insert_source", "keep_target_normals", "keep_source_normals", "frames_normals_keep", "places_add_source",
                   "keyframes_add_source", "keyframes_add", "linearize_normals", "linearize_gicp", "icp_run_normals", "icp_run_gicp",
                   "register_frames_normals", "register_frames_gicp", "icp_run_trials_normals", "icp_run_trials_gicp", "set_target_keyframes",
-                  "remove_outliers", "remove_dynamic", "insert", "register_frames")
+                  "remove_outliers", "remove_dynamic", "insert", "register_frames", "keep_target_voxels", "linearize_voxels", "icp_run_voxels",
+                  "icp_run_trials_voxels", "register_frames_voxels")
 
 
 def refusable():
@@ -932,10 +1083,14 @@ def _repairs(m):
         return ["keep_target_normals", "set_target_normals", "set_target_normals"]
     if not m.sn:
         out += ["keep_source_normals", "set_source_normals"]
+    if not m.vm:
+        out.append("keep_target_voxels")
     if m.opts["roi_index"] != 2:
         out.append("set_window")
     if not m.opts["normals_follow"]:
-        out.append("set_option")
+        out.append(("set_option", dict(key="normals_follow", value=1)))
+    if not m.opts["robust_kernel"]:
+        out.append(("set_option", dict(key="robust_kernel", value=1 + len(m.map) % 3)))
     return out
 
 
@@ -946,7 +1101,8 @@ def _deck(rng, names):
 
 
 def walk_ops(seed, n_steps):
-    """a list of (operation, arguments).  Operations come off a deck that holds every operation WEIGHTS[its class] times, shuffled (so map
+    """a list of (operation, arguments).  Operations come off a deck that holds every operation WEIGHTS[its class] times (NAME_WEIGHTS
+    where it names the operation), shuffled (so map
     updates, source changes, member changes, history makers and scratch users alternate, and a walk uses as many different operations as
     it has steps for); one whose precondition does not hold yet waits in the deck.  Between them, with fixed probabilities, a member that
     the last steps dropped is put back (so that probes meet it live) and a call that the header refuses is made - at most a fifth of the
@@ -972,10 +1128,18 @@ def walk_ops(seed, n_steps):
         refused += rc != OK
         return rc
 
+    def take_accepted(name, args):
+        """a keep of the voxels under a window comes right behind a single-pose launch: no probe runs between the two (a launch is not
+        a state-changing step), so the window is the active index when the keep reads the map"""
+        if name == "keep_target_voxels" and m.window_live() and len(ops) + 2 <= n_steps:
+            take("linearize", dict(pose=int(rng.integers(6))))
+        return take(name, args)
+
     def gate_sequence():
         turn = int(seed) * 3 + gates[0]                              # the refused call and the end in turn, from a start the seed moves
+        other = int(seed) * 4 + gates[0]                             # (a step coprime to the number of calls: neighbouring seeds reach them all)
         gates[0] += 1
-        for st in [("gated_begin", {}), ("gated_other", dict(which=GATED_OTHERS[turn % len(GATED_OTHERS)])),
+        for st in [("gated_begin", {}), ("gated_other", dict(which=GATED_OTHERS[other % len(GATED_OTHERS)])),
                    ("gate_end", dict(open=1 - turn % 2, pose=int(rng.integers(6))))]:
             take(*st)
 
@@ -1017,15 +1181,16 @@ def walk_ops(seed, n_steps):
         elif u < 0.46 and _repairs(m):
             fix = _repairs(m)
             name = fix[int(rng.integers(len(fix)))]
-            good, _ = _draw_args(rng, name, m)
-            if name == "set_option":
-                good = dict(key="normals_follow", value=1)
-            elif name == "set_window":
+            if isinstance(name, tuple):
+                name, good = name
+            else:
+                good, _ = _draw_args(rng, name, m)
+            if name == "set_window":
                 good = dict(on=1)
-            take(name, good)
+            take_accepted(name, good)
         else:
             if not deck:                                             # one shuffle for all seeds, entered where the seed says: the committed
-                deck = _deck(np.random.default_rng(2024), [n for n in every for _ in range(WEIGHTS[CLASS[n]])])      # seeds share the work
+                deck = _deck(np.random.default_rng(2024), [n for n in every for _ in range(NAME_WEIGHTS.get(n, WEIGHTS[CLASS[n]]))])      # seeds share the work
                 at = (int(seed) * 17) % len(deck)
                 deck = deck[at:] + deck[:at]
             for j, name in enumerate(deck):                          # the first of the deck that is accepted as things stand
@@ -1041,7 +1206,7 @@ def walk_ops(seed, n_steps):
                     options = options[1:] + options[:1]
                     good = dict(key=key, value=value)
                 if apply(clone(m), None, (name, good)) == OK:
-                    take(name, good)
+                    take_accepted(name, good)
                     del deck[j]
                     if name in ("keyframes_reset", "places_reset"):  # an emptied store is filled again next
                         deck.insert(0, "keyframes_add" if name == "keyframes_reset" else "places_add_clouds")
@@ -1116,7 +1281,8 @@ def probe(kind, c, m, pose, fresh=False):
         mod = [("target_normals_kept", c.target_normals_kept(), int(bool(m.tn))), ("source_normals_kept", c.source_normals_kept(), int(bool(m.sn))),
                ("frames_normals_kept", c.frames_normals_kept(), int(bool(m.fn))),
                ("follow.n_target", c.normals_follow_info()["n_target"], 0 if fresh else m.follow_n),
-               ("places_count", c.places_count(), len(m.places or [])), ("keyframes_count", c.keyframes_count(), len(m.kf or []))]
+               ("places_count", c.places_count(), len(m.places or [])), ("keyframes_count", c.keyframes_count(), len(m.kf or [])),
+               ("target_voxels_kept", c.target_voxels_kept(), m.vmap()["n_kept"] if m.vm else 0)]                 # h:1113
         return [], mod
     if kind == "lin":
         if not ready(m):
@@ -1194,12 +1360,72 @@ def probe(kind, c, m, pose, fresh=False):
             subs, info = c.keyframe_submaps(members, leaf=leaf)
             out += [("submap %r %d" % (leaf, g), bits(s)) for g, s in enumerate(subs)] + [("submaps info %r" % (leaf,), sorted(info.items()))]
         return out, []
+    mode = m.opts["voxels_source_cov"]
+    if kind == "voxels":
+        # the kept records themselves: bitwise the reference's of the model's map (h:1096-1113)
+        if not m.vm:
+            return [], []
+        got, want = c.kept_target_voxels(), m.vmap()
+        return ([("voxels " + k, bits(got[k])) for k in ("coords", "count", "mean", "cov")],
+                [("kept voxels " + k, bits(got[k]), bits(want[k])) for k in ("coords", "count", "mean", "cov")])
+    if kind == "vlin":
+        if not m.voxels_ready():                                     # h:1147-1148 (the plain call: a dump needs a source to size it)
+            out = refusal(lambda: sums(c.linearize_voxels(T, lp)))
+            return out, [("vlin refusal", out[0], ("refused", E_STATE))]
+        got = []
+
+        def run():
+            got.append(c.linearize_voxels(T, lp, debug=True))
+            return dump(got[0], vxs.DUMP_KEYS) + sums(got[0]) + [("plain." + k, v) for k, v in sums(c.linearize_voxels(T, lp))]
+        out = refusal(run)
+        mod = [("vlin refusal", out[0][0] == "refused", False)]
+        if got:                                                      # h:1128-1144: the dump is bitwise the rule's, from what the model knows
+            normals = c.kept_source_normals()[0] if mode else None   # (the normals the context itself returns: the rule starts from them)
+            scale = m.opts["gicp_robust_scale"] if m.opts["robust_kernel"] else 1.0
+            want = vlin_of(m.vmap(), m.src, T, mode, normals, m.opts["gicp_epsilon"], m.opts["robust_kernel"], scale)
+            mod += [("vlin dump " + k, S.same_bits(np.asarray(got[0][k]), np.asarray(want[k])), True) for k in vxs.DUMP_KEYS]
+            mod += [("vlin " + k, int(got[0][k]), int(want[k])) for k in ("n_eff", "n_pt")]
+        return out, mod
+    if kind == "icp_v":
+        if not m.voxels_ready():
+            return [], []
+        res, logs = c.icp_run_voxels(T, "Ours", cfg_of())
+        return fields(res, TIMING) + records(logs), []
+    if kind == "frames_v":
+        if m.map is None or not m.vm:
+            return [], []
+        keys = frame_keys((257, 63, 1000))
+        out = records(c.register_frames_voxels(frames_of(keys), frame_poses(3, pose), "Ours", cfg_of(),
+                                               frame_normals=np_params((5, 0.0)) if mode else None, slots=2))
+        m.loaded(keys, ("keep", (5, 0.0)) if mode else None)         # (the probe's own load: h:1402-1403, h:1396-1397)
+        return out, []
+    if kind == "trials_v":
+        if not m.voxels_ready():
+            return [], []
+        return records(c.icp_run_trials_voxels(frame_poses(4, pose), "Ours", cfg_of())), []
+    if kind == "vbatch":
+        # the loaded frames and their kept normals, and the own source, through the fourth engine's device seam (d:246-261)
+        if not (m.map is not None and m.vm and m.frames and (not mode or m.fn)):
+            return [], []
+        ids = [f for f, k in enumerate(m.frames) if len(cloud(k)) > 0]
+        out = [("vbatch[%d].%s" % (f, k), v) for f, d in enumerate(c.voxels_batch(frame_poses(len(ids), pose), frame_ids=ids, params=lp)) for k, v in sums(d)]
+        if m.src is not None and (not mode or m.sn):
+            out += [("vbatch own[%d].%s" % (f, k), v) for f, d in enumerate(c.voxels_batch(frame_poses(2, pose), frame_ids=None, params=lp)) for k, v in sums(d)]
+        return out, []
+    if kind == "pairs":
+        # two small pairs through the three pair forms: they need nothing of the context and leave it alone (h:1422-1423, h:1443-1446)
+        src, tgt = [cloud(("frame", 63)), cloud(("frame", 257))], [cloud(("tgt", 600)), cloud(("tgt", 1500))]
+        Ts, p5 = frame_poses(2, pose), np_params((5, 0.0))
+        return ([("pairs." + k, v) for k, v in records(c.register_pairs(src, tgt, Ts, "Ours", cfg_of(), slots=2))] +
+                [("pairs_n." + k, v) for k, v in records(c.register_pairs_normals(src, tgt, Ts, "Ours", cfg_of(), p5, slots=2))] +
+                [("pairs_g." + k, v) for k, v in records(c.register_pairs_gicp(src, tgt, Ts, "Ours", cfg_of(), p5, p5, slots=2))]), []
     raise KeyError(kind)
 
 
 def build_fresh(make, m):
     """context B, from the model alone: options, set_target, set_source, the normals by keep with the remembered parameters or by set with
-    the array, frames_load and the frame normals, the places, the keyframes"""
+    the array, the kept voxels (before any launch: the whole map's index is the active one), frames_load and the frame normals, the
+    places, the keyframes"""
     b = make()
     for k in sorted(m.opts):
         b.set_option(k, m.opts[k])
@@ -1210,6 +1436,8 @@ def build_fresh(make, m):
     for what, keep, given in ((m.tn, b.keep_target_normals, b.set_target_normals), (m.sn, b.keep_source_normals, b.set_source_normals)):
         if what:
             keep(np_params(what[1])) if what[0] == "keep" else given(what[1])
+    if m.vm:
+        b.keep_target_voxels(api.voxel_map_params(*m.vm))
     if m.frames:
         b.frames_load(frames_of(m.frames))
         if m.fn:
@@ -1237,11 +1465,12 @@ def check_points(ops, every):
 
 
 def probes_at(seed, step, last):
-    """the map and the flags (host reads and one index check) at every check, two more probes drawn by the seed, all of them at the last step"""
+    """the map and the flags (host reads and one index check) at every check, three more probes drawn by the seed (two of thirteen kinds
+    once, three of twenty now: the same share), all of them at the last step"""
     if last:
         return [(k, (step + j) % 6) for j, k in enumerate(PROBE_KINDS)]
     rng = np.random.default_rng([seed, step])
-    kinds = 2 + rng.choice(len(PROBE_KINDS) - 2, size=2, replace=False)
+    kinds = 2 + rng.choice(len(PROBE_KINDS) - 2, size=3, replace=False)
     return [("map", 0), ("flags", 0)] + [(PROBE_KINDS[int(k)], int(rng.integers(6))) for k in kinds]
 
 
@@ -1267,6 +1496,8 @@ def run_walk(make, seed, ops, every, deskew=host_deskew, on_check=None, make_fre
                 rc = apply(m, a, step)
             except Unexpected as e:                                  # (not an AssertionError: the caller stops its other walks)
                 raise Unexpected(where("%r: %s" % (step, e))) from None
+            except AssertionError as e:                              # (an accepted call whose own answer is not the model's)
+                raise AssertionError(where("%r: %s" % (step, e))) from None
             assert rc is not None, where("precondition")
             if s not in checks or m.gate:
                 continue
@@ -1295,7 +1526,10 @@ def run_walk(make, seed, ops, every, deskew=host_deskew, on_check=None, make_fre
 # FAULTS plants one broken rule at a time (tests/test_state_walk_model.py: the committed seeds must catch each).
 FAULTS = ("set_source_voxel keeps the source normals", "crop without normals_follow keeps the target normals",
           "insert_source leaves the window's answers those of the old map", "a refused set_target forgets the source",
-          "frames_load keeps the frame normals")
+          "frames_load keeps the frame normals", "a crop with normals_follow on keeps the kept voxels",
+          "keep_target_voxels behind a live window summarises the window's points",
+          "register_frames_voxels in mode 0 keeps the previous frames' normals",
+          "robust_kernel is latched by set_source instead of being read at the launch")
 
 
 class FakeError(api.DcregError):
@@ -1313,9 +1547,30 @@ class FakeContext:
         self.opts = dict(DEFAULTS)
         self.map = self.src = self.tn = self.sn = self.frames = self.fn = self.places = self.kf = None
         self.gate, self.follow_n, self.window_map = False, 0, None
+        self.vm = None                          # ((leaf, epsilon, min_points), the points the keep summarised)
+        self.window_active = False              # the window is the active index: the last launch was a single-pose one of the first engine
+        self.latched_kernel = 0                 # (FAULTS[8])
 
     def close(self):
         pass
+
+    # what the second / third and fourth engine's answers may depend on beyond the clouds and the kept members
+    def _robust(self, engine):
+        """the kernel, and the engine's own scale only when a kernel is on (h:1058, h:1071)"""
+        kind = self.latched_kernel if self.fault == FAULTS[8] else self.opts["robust_kernel"]
+        return (kind, self.opts["robust_scale" if engine == 2 else "gicp_robust_scale"]) if kind else (0,)
+
+    def _gicp(self):
+        return self._robust(3) + (self.opts["gicp_epsilon"],)        # h:182-183 read at the time of every linearisation
+
+    def _vox(self, normals):
+        """the fourth engine: the kept voxels, the mode, the kernel and, in mode 1 only, gicp_epsilon and the cloud's kept normals (h:1129-1133)"""
+        mode = self.opts["voxels_source_cov"]
+        return (digest(self.vm[0], self.vm[1]), mode) + self._robust(4) + ((self.opts["gicp_epsilon"], normals) if mode else ())
+
+    def _whole(self):
+        """an entry point that is not a single-pose launch of the first engine makes the whole map's index the active one"""
+        self.window_active = False
 
     def _busy(self):
         if self.gate:
@@ -1333,13 +1588,15 @@ class FakeContext:
         return np.ascontiguousarray(xyz[:, :3], np.float32)
 
     def set_option(self, k, v):
+        if (k, v) in REFUSED_OPTIONS:
+            raise FakeError(E_INVALID)
         self.opts[k] = 1 << 20 if k == "max_table_entries" and v < (1 << 20) else v
         if k.startswith("roi_"):
             self.window_map = None              # (context.hip: the window is rebuilt by the next single-pose launch)
 
     # the map
     def _new_target(self, xyz):
-        self.map, self.tn, self.follow_n, self.window_map = xyz, None, 0, None
+        self.map, self.tn, self.follow_n, self.window_map, self.vm, self.window_active = xyz, None, 0, None, None, False
 
     def set_target(self, xyz, radius):
         self._busy()
@@ -1365,13 +1622,16 @@ class FakeContext:
             raise FakeError(E_INVALID)
         self._new_target(self._finite(kr.submaps_ref(self.kf, [members], leaf)[0][0]))
 
-    def _update(self, xyz, keep_window=False, keep_normals=False):
+    def _update(self, xyz, keep_window=False, keep_normals=False, keep_voxels=False):
         if len(xyz) == 0:
             raise FakeError(E_INVALID)
         if len(xyz) == len(self.map) and np.array_equal(xyz.view(np.uint32), self.map.view(np.uint32)):
             return
         if not keep_window:
             self.window_map = None
+        if not keep_voxels:
+            self.vm = None
+        self.window_active = False
         self.map, self.follow_n = np.ascontiguousarray(xyz), len(xyz)
         follows = self.tn and self.tn[0] == "keep" and self.opts["normals_follow"]
         if not follows and not keep_normals:
@@ -1391,7 +1651,8 @@ class FakeContext:
     def crop(self, lo, hi):
         self._busy()
         self._need(self.map)
-        self._update(crop_ref(self.map, lo, hi), keep_normals=self.fault == FAULTS[1])
+        self._update(crop_ref(self.map, lo, hi), keep_normals=self.fault == FAULTS[1],
+                     keep_voxels=self.fault == FAULTS[5] and bool(self.opts["normals_follow"]))
 
     def remove_outliers(self, p):
         self._busy()
@@ -1406,6 +1667,7 @@ class FakeContext:
     # the source
     def _new_source(self, xyz, keep_normals=False):
         self.src = xyz
+        self.latched_kernel = self.opts["robust_kernel"]
         if not keep_normals:
             self.sn = None
 
@@ -1486,12 +1748,39 @@ class FakeContext:
     def kept_source_normals(self):
         if self.sn[0] == "set":
             return np.ascontiguousarray(self.sn[1][:, :3]), np.full(len(self.src), np.nan, np.float32)
-        return np.frombuffer(self._sn().encode(), np.uint8), np.zeros(1)
+        # kept by the rule: unit vectors named by what they were computed from (the voxel linearisation below starts from them)
+        return np.array(S.unit_normals(len(self.src), int(self._sn(), 16) % (1 << 31))), np.zeros(len(self.src), np.float32)
+
+    # the kept voxels: the reference's records of the points the keep summarised
+    def keep_target_voxels(self, p):
+        self._busy()
+        self._need(self.map)
+        p = (p.leaf, p.epsilon, p.min_points)
+        if spans_too_far(self.map, p[0]):
+            raise FakeError(E_INVALID)
+        pts = self.map
+        if self.fault == FAULTS[6] and self.window_active:
+            pts = np.ascontiguousarray(self.map[:(len(self.map) + 1) // 2])      # (a stand-in for the points inside the window's box)
+        ref = vmap_of(pts, p)
+        self.vm = (p, pts) if ref["n_kept"] else None
+        return {k: ref[k] for k in ("n_points", "n_voxels", "n_small", "n_degenerate", "n_kept")}
+
+    def drop_target_voxels(self):
+        self._busy()
+        self.vm = None
+
+    def target_voxels_kept(self):
+        return vmap_of(self.vm[1], self.vm[0])["n_kept"] if self.vm else 0
+
+    def kept_target_voxels(self):
+        self._busy()
+        self._need(self.vm)
+        return vmap_of(self.vm[1], self.vm[0])
 
     # frames
-    def frames_load(self, frames):
+    def frames_load(self, frames, keep_normals=False):
         self._busy()
-        if self.fault != FAULTS[4]:
+        if self.fault != FAULTS[4] and not keep_normals:
             self.fn = None
         for f in frames:
             if len(f):
@@ -1587,6 +1876,7 @@ class FakeContext:
         """a single-pose launch of the first engine searches through the window when there is one (h:182-188)"""
         if self.opts["roi_index"] == 2 and self.window_map is None:
             self.window_map = self.map
+        self.window_active = self.opts["roi_index"] == 2
         seen = self.window_map if self.opts["roi_index"] == 2 else self.map
         return digest(seen, self.src, pose)
 
@@ -1603,12 +1893,24 @@ class FakeContext:
     def linearize_normals(self, T, lp=None):
         self._busy()
         self._need(self.map, self.src, self.tn or None)
-        return self._sums(self.map, self.src, self._tn(), self._pose(T))
+        return self._sums(self.map, self.src, self._tn(), self._robust(2), self._pose(T))
 
     def linearize_gicp(self, T, lp=None):
         self._busy()
         self._need(self.map, self.src, self.tn or None, self.sn or None)
-        return self._sums(self.map, self.src, self._tn(), self._sn(), self._pose(T))
+        return self._sums(self.map, self.src, self._tn(), self._sn(), self._gicp(), self._pose(T))
+
+    def _need_voxels(self):
+        self._need(self.map, self.src, self.vm, (self.sn or None) if self.opts["voxels_source_cov"] else True)
+
+    def linearize_voxels(self, T, lp=None, debug=False):
+        """the rule itself (tests/voxels_ref.py) from what this context holds: the dump can be compared with the model's"""
+        self._busy()
+        self._pose(T)
+        self._need_voxels()
+        mode, kind = self.opts["voxels_source_cov"], self._robust(4)
+        return vlin_of(vmap_of(self.vm[1], self.vm[0]), self.src, T, mode, self.kept_source_normals()[0] if mode else None,
+                       self.opts["gicp_epsilon"], kind[0], kind[1] if kind[0] else 1.0)
 
     def _rec(self, *parts):
         r = _Rec()
@@ -1623,46 +1925,67 @@ class FakeContext:
     def icp_run_normals(self, T, method, cfg):
         self._busy()
         self._need(self.map, self.src, self.tn or None)
-        return self._rec(self.map, self.src, self._tn(), self._pose(T)), []
+        return self._rec(self.map, self.src, self._tn(), self._robust(2), self._pose(T)), []
 
     def icp_run_gicp(self, T, method, cfg):
         self._busy()
         self._need(self.map, self.src, self.tn or None, self.sn or None)
-        return self._rec(self.map, self.src, self._tn(), self._sn(), self._pose(T)), []
+        return self._rec(self.map, self.src, self._tn(), self._sn(), self._gicp(), self._pose(T)), []
+
+    def icp_run_voxels(self, T, method, cfg):
+        self._busy()
+        self._need_voxels()
+        return self._rec(self.src, self._vox(self._sn()), self._pose(T)), []
 
     def icp_run_trials(self, Ts, method, cfg):
         self._busy()
         self._need(self.map, self.src)
+        self._whole()
         return [self._rec(self.map, self.src, self._pose(T)) for T in Ts]
 
     def icp_run_trials_normals(self, Ts, method, cfg):
         self._busy()
         self._need(self.map, self.src, self.tn or None)
-        return [self._rec(self.map, self.src, self._tn(), self._pose(T)) for T in Ts]
+        return [self._rec(self.map, self.src, self._tn(), self._robust(2), self._pose(T)) for T in Ts]
 
     def icp_run_trials_gicp(self, Ts, method, cfg):
         self._busy()
         self._need(self.map, self.src, self.tn or None, self.sn or None)
-        return [self._rec(self.map, self.src, self._tn(), self._sn(), self._pose(T)) for T in Ts]
+        return [self._rec(self.map, self.src, self._tn(), self._sn(), self._gicp(), self._pose(T)) for T in Ts]
+
+    def icp_run_trials_voxels(self, Ts, method, cfg):
+        self._busy()
+        self._need_voxels()
+        return [self._rec(self.src, self._vox(self._sn()), self._pose(T)) for T in Ts]
 
     def register_frames(self, frames, Ts, method, cfg, slots=0):
         self._busy()
         self._need(self.map)
         self.frames_load(frames)
+        self._whole()
         return [self._rec(self.map, f, self._pose(T)) for f, T in zip(frames, Ts)]
 
     def register_frames_normals(self, frames, Ts, method, cfg, slots=0):
         self._busy()
         self._need(self.map, self.tn or None)
         self.frames_load(frames)
-        return [self._rec(self.map, self._tn(), f, self._pose(T)) for f, T in zip(frames, Ts)]
+        return [self._rec(self.map, self._tn(), f, self._robust(2), self._pose(T)) for f, T in zip(frames, Ts)]
 
     def register_frames_gicp(self, frames, Ts, method, cfg, p=None, slots=0):
         self._busy()
         self._need(self.map, self.tn or None)
         self.frames_load(frames)
         self.frames_normals_keep(p)
-        return [self._rec(self.map, self._tn(), f, p.k, self._pose(T)) for f, T in zip(frames, Ts)]
+        return [self._rec(self.map, self._tn(), f, p.k, self._gicp(), self._pose(T)) for f, T in zip(frames, Ts)]
+
+    def register_frames_voxels(self, frames, Ts, method, cfg, frame_normals=None, slots=0):
+        self._busy()
+        self._need(self.map, self.vm)
+        mode = self.opts["voxels_source_cov"]
+        self.frames_load(frames, keep_normals=self.fault == FAULTS[7] and not mode)
+        if mode:
+            self.frames_normals_keep(frame_normals)
+        return [self._rec(f, self._vox(frame_normals.k if mode else None), self._pose(T)) for f, T in zip(frames, Ts)]
 
     def register_pairs(self, src, tgt, Ts, method, cfg, slots=0):
         self._busy()
@@ -1670,24 +1993,47 @@ class FakeContext:
             self._finite(x)
         return [self._rec(s, t, self._pose(T)) for s, t, T in zip(src, tgt, Ts)]
 
+    def register_pairs_normals(self, src, tgt, Ts, method, cfg, target_normals=None, slots=0):
+        self._busy()
+        for x in list(src) + list(tgt):
+            self._finite(x)
+        return [self._rec(s, t, target_normals.k, self._robust(2), self._pose(T)) for s, t, T in zip(src, tgt, Ts)]
+
+    def register_pairs_gicp(self, src, tgt, Ts, method, cfg, target_normals=None, source_normals=None, slots=0):
+        self._busy()
+        for x in list(src) + list(tgt):
+            self._finite(x)
+        return [self._rec(s, t, target_normals.k, source_normals.k, self._gicp(), self._pose(T)) for s, t, T in zip(src, tgt, Ts)]
+
     def normals_batch(self, Ts, frame_ids=None, params=None):
         self._busy()
-        return [self._sums(self.map, self._tn(), self.frames[f], self._pose(T)) for f, T in zip(frame_ids, Ts)]
+        return [self._sums(self.map, self._tn(), self.frames[f], self._robust(2), self._pose(T)) for f, T in zip(frame_ids, Ts)]
 
     def gicp_batch(self, Ts, frame_ids=None, params=None):
         self._busy()
         fn = digest(*self.fn)
-        return [self._sums(self.map, self._tn(), self.frames[f], fn, f, self._pose(T)) for f, T in zip(frame_ids, Ts)]
+        return [self._sums(self.map, self._tn(), self.frames[f], fn, f, self._gicp(), self._pose(T)) for f, T in zip(frame_ids, Ts)]
+
+    def voxels_batch(self, Ts, frame_ids=None, params=None):
+        self._busy()
+        self._need(self.map, self.vm)
+        if frame_ids is None:
+            self._need_voxels()
+            return [self._sums(self.src, self._vox(self._sn()), self._pose(T)) for T in Ts]
+        fn = digest(*self.fn) if self.opts["voxels_source_cov"] else None
+        return [self._sums(self.frames[f], self._vox((fn, f)), self._pose(T)) for f, T in zip(frame_ids, Ts)]
 
     def knn(self, q, k=5, max_radius=0.0):
         self._busy()
         self._need(self.map)
+        self._whole()
         h = np.frombuffer(digest(self.map, q, k, max_radius).encode(), np.uint8)
         return h, h
 
     def p2p_error(self, T, thr):
         self._busy()
         self._need(self.map, self.src)
+        self._whole()
         return tuple(float(v) for v in np.frombuffer(digest(self.map, self.src, self._pose(T), thr).encode(), np.uint8)[:4])
 
     # the gate
@@ -1717,6 +2063,6 @@ def _vis_dict(p):
 
 
 # ---- the committed walks (tests/test_state_walk_model.py holds the conditions they were chosen to meet)
-SEEDS = (5, 6, 12, 13, 17, 18, 21, 22, 23, 27)
+SEEDS = (5, 6, 12, 13, 17, 18, 21, 22, 23, 27, 2, 7, 9, 33, 42)      # (the first ten are as old as the module: their test ids stay)
 N_STEPS = 72
 EVERY = 1            # A is compared after every EVERY-th state-changing step

@@ -1,8 +1,9 @@
 """Seeded random call sequences against a freshly built context (tests/state_walk.py has the model, the operations and the probes;
 tests/test_state_walk_model.py what the committed walks cover).  Context A takes a walk of calls in an order no feature's own test tried;
-at every check point a fresh context B is built from the model alone - options, set_target of the model's map, set_source, the normals, the
-frames, the places, the keyframes - and both answer the same probes.  A answers warm from its history, B cold; include/dcreg.h promises
-that no bit differs.
+at every check point a fresh context B is built from the model alone - options (the robust kernel, its scales, gicp_epsilon and the voxel
+mode among them), set_target of the model's map, set_source, the normals, the kept voxels, the frames, the places, the keyframes - and both
+answer the same probes, those of the voxel-distribution engine and of the three pair forms included.  A answers warm from its history, B
+cold; include/dcreg.h promises that no bit differs.  The kept voxels and the voxel linearisation's dump are bitwise tests/voxels_ref.py's.
 
 A walk runs once and nothing is retried.  If a walk ends in anything but an AssertionError (a HIP error, a return code the model did not
 expect from the library's side) the remaining walks are skipped: the cause is to be found by reading code, not by running again."""

@@ -293,6 +293,21 @@ def test_a_walk_is_bitwise_fresh_contexts_with_the_other_engines_in_between(lot_
         window.close()
 
 
+def test_a_keep_behind_a_live_window_summarises_the_whole_map():
+    """the window is the ACTIVE index once a single-pose launch of the first engine has run (roi_index = 2): a keep that arrives then must
+    read the whole map's points, not the window's (tests/state_walk.py reaches the same order from many histories)"""
+    L = vs.lot()
+    c = context(L["tgt"], L["src"], keep=False, opts=OPTS_WINDOW)
+    try:
+        c.linearize(np.ascontiguousarray(L["INIT"][:3, :3]).reshape(9), L["INIT"][:3, 3], api.default_lin_params(RADIUS))
+        assert c.roi_info()["active"]
+        assert c.keep_target_voxels(MAP_PARAMS) == {k: L["vmap"][k] for k in INFO_KEYS}
+        vs.assert_map_bitwise(c.kept_target_voxels(), L["vmap"], "behind the window")
+        check(c, vr.linearize(L["vmap"], L["src"], L["INIT"]), L["INIT"], "behind the window")
+    finally:
+        c.close()
+
+
 # ---- 7. invalidation
 def test_every_change_of_the_map_drops_the_voxels_and_the_source_side_calls_leave_them():
     L = vs.lot()

@@ -1,22 +1,29 @@
 """The committed walks of tests/state_walk.py, on the model alone: what they cover, and that the comparison of tests/test_gpu_state_walk.py
 notices a context that breaks a rule.  No device is used: the contexts here are state_walk.FakeContext, whose answers are hashes of exactly
-the state an answer may depend on (the built library is loaded all the same, for the parameter blocks the operations fill in)."""
+the state an answer may depend on (the built library is loaded all the same, for the parameter blocks the operations fill in); its kept
+voxels and its voxel linearisation are tests/voxels_ref.py's own, so that the bitwise items of those probes hold on it too."""
 import collections
 
 import pytest
 
 import state_walk as W
 
-LIVE = ("keep", "set", "source", "window", "follow")
+LIVE = ("keep", "set", "source", "window", "follow", "voxels", "robust")
+# states that must meet under a probe that launches kernels, and orders of calls that must occur, each at least MEET times over all walks
+MEET = 5
+MEETINGS = ("voxels and window live under a launching probe", "mode 1 and kept source normals under a launching probe",
+            "a robust kernel under a frames_n, frames_g or batch probe", "keep_target_voxels accepted right behind a launch under a live window")
 
 
 def walk_facts(seed, ops):
     """one walk on the model and on the unplanted fake (which must pass) -> what it covers"""
     f = dict(acc=collections.Counter(), ref=collections.Counter(), pairs=set(), live=collections.Counter(), points=0, options=set(),
-             crop_nothing=0, gated=collections.Counter(), ends=collections.Counter())
+             crop_nothing=0, gated=collections.Counter(), ends=collections.Counter(), meet=collections.Counter(), keep_nothing=0,
+             follow_update=0, bad_options=set())
     m = W.Model()
+    launched = False                                        # the step before was an accepted single-pose launch of the first engine
     for name, args in ops:
-        live = m.window_live()
+        live, before = m.window_live(), (m.map, m.vm)
         rc = W.apply(m, None, (name, args))
         assert rc is not None, (seed, name, args)
         (f["acc"] if rc == W.OK else f["ref"])[name] += 1
@@ -25,12 +32,25 @@ def walk_facts(seed, ops):
             f["gated"][args["which"]] += 1
         if name == "gate_end":
             f["ends"]["open" if args["open"] and not live else "abort"] += 1
+        if name == "keep_target_voxels" and rc == W.OK:
+            f["keep_nothing"] += m.vm is None
+            f["meet"][MEETINGS[3]] += bool(m.vm and live and launched)
+        if name == "set_option" and rc == W.E_INVALID:
+            f["bad_options"].add((args["key"], args["value"]))
+        # a map update that changed the map with normals_follow on while voxels were kept
+        f["follow_update"] += W.CLASS[name] == "update" and rc == W.OK and m.map is not before[0] and bool(before[1]) and bool(m.opts["normals_follow"])
+        launched = name in ("linearize", "icp_run") and rc == W.OK
     f["refused"] = sum(f["ref"].values())
     seen = []
 
     def on_check(s, kind, m, ran):
         seen.append((s, kind, ran, (bool(m.tn and m.tn[0] == "keep"), bool(m.tn and m.tn[0] == "set"), bool(m.sn), m.window_live(),
-                                    bool(m.opts["normals_follow"])), tuple(k for k in W.TOGGLES if m.opts[k] != W.DEFAULTS[k])))
+                                    bool(m.opts["normals_follow"]), bool(m.vm), m.opts["robust_kernel"] != 0),
+                     tuple(k for k in W.TOGGLES if m.opts[k] != W.DEFAULTS[k])))
+        if ran and kind in W.LAUNCHING:
+            f["meet"][MEETINGS[0]] += bool(m.vm and m.window_live())
+            f["meet"][MEETINGS[1]] += bool(m.opts["voxels_source_cov"] and m.sn)
+            f["meet"][MEETINGS[2]] += bool(m.opts["robust_kernel"] and kind in ("frames_n", "frames_g", "batch"))
     W.run_walk(W.FakeContext, seed, ops, W.EVERY, on_check=on_check)
     checks = W.check_points(ops, W.EVERY)
     changing = [s for s, (n, _) in enumerate(ops) if W.CLASS[n] in W.STATE_CLASSES]
@@ -70,6 +90,12 @@ def conditions(facts, n_steps):
     missed += ["refused behind a gate: " + k for k in W.GATED_OTHERS if gated[k] < 1]
     ends = sum((f["ends"] for f in facts), collections.Counter())
     missed += ["gate ended by %s twice" % k for k in ("open", "abort") if ends[k] < 2]
+    meet = sum((f["meet"] for f in facts), collections.Counter())
+    missed += ["%d times: %s (%d)" % (MEET, k, meet[k]) for k in MEETINGS if meet[k] < MEET]
+    missed += ["a keep that keeps no voxel"] * (sum(f["keep_nothing"] for f in facts) < 1)
+    missed += ["a map update with normals_follow on while voxels were kept"] * (sum(f["follow_update"] for f in facts) < 1)
+    bad_options = set().union(*[f["bad_options"] for f in facts])
+    missed += ["option value refused: %s = %r" % kv for kv in W.REFUSED_OPTIONS if kv not in bad_options]
     return missed
 
 
@@ -111,6 +137,8 @@ def test_the_committed_walks_cover_what_they_must(facts):
     print("operation:accepted/refused " + " ".join("%s:%d/%d" % (n, acc[n], ref[n]) for n in sorted(W.OPS)))
     print("probe points %d, live %r, most state-changing steps between two checks %d" %
           (sum(f["points"] for f in facts), dict(sum((f["live"] for f in facts), collections.Counter())), max(f["gap"] for f in facts)))
+    print("meetings %r, keeps that keep nothing %d, followed updates under kept voxels %d" %
+          (dict(sum((f["meet"] for f in facts), collections.Counter())), sum(f["keep_nothing"] for f in facts), sum(f["follow_update"] for f in facts)))
     assert conditions(facts, W.N_STEPS) == []
 
 
