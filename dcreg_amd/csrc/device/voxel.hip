@@ -31,6 +31,7 @@ namespace {
 constexpr int kVoxBlock = 256;
 constexpr int kVoxPerThread = 8;                        // points per thread of k_vox_coords (a block covers one tile of 2048 points)
 constexpr int kSpanBits = 21;                           // a cloud spans fewer than 2^21 voxels per axis
+constexpr int64_t kSpanMax = ((int64_t)1 << kSpanBits) - 1;     // the most voxels per axis that are accepted: 2^21 or more are refused
 constexpr double kVoxLimit = 4611686018427387904.0;     // 2^62: voxel coordinates beyond it are refused
 // counters of one call, per cloud s: cnt[kCnt s + 0..2] minimum voxel x y z, + 3..5 maximum, + 6 finite points, + 7 voxels, + 8 kept voxels;
 // behind the clouds kTail int64 slots read as uint32: [0..2] minimum, [3..5] maximum of the output (ordered-uint, k_bounds), [6] overflow
@@ -467,8 +468,8 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
         r.n_finite += q[6];
         for (int a = 0; a < 3; ++a) {
             const int64_t d = q[3 + a] - q[a];
-            if (d >= ((int64_t)1 << kSpanBits)) {
-                c->fail("cloud %d spans %lld voxels on axis %d (at most 2^21 - 1)", s, (long long)d + 1, a);
+            if (d + 1 > kSpanMax) {                           // (d = maximum - minimum: d + 1 voxels)
+                c->fail("cloud %d spans %lld voxels on axis %d (at most 2^21 - 1 = %lld)", s, (long long)d + 1, a, (long long)kSpanMax);
                 return DCREG_E_INVALID;
             }
             span[a] = std::max(span[a], d);
@@ -565,7 +566,10 @@ int voxel_map_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_ma
     int bits[3];
     for (int a = 0; a < 3; ++a) {
         const int64_t d = h[3 + a] - h[a];
-        if (d >= ((int64_t)1 << kSpanBits)) { c->fail("the map spans %lld voxels on axis %d (at most 2^21 - 1)", (long long)d + 1, a); return DCREG_E_INVALID; }
+        if (d + 1 > kSpanMax) {                               // (d = maximum - minimum: d + 1 voxels)
+            c->fail("the map spans %lld voxels on axis %d (at most 2^21 - 1 = %lld)", (long long)d + 1, a, (long long)kSpanMax);
+            return DCREG_E_INVALID;
+        }
         bits[a] = bits_for(d);
     }
     const uint32_t *ord;

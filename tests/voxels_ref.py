@@ -35,7 +35,8 @@ def voxel_of(xyz, leaf):
 
 def voxel_map(xyz, leaf=1.0, epsilon=1e-3, min_points=6):
     """-> dict coords [V, 3] int64, count [V] int32, mean [V, 3] float32, cov [V, 6] float32 of the kept voxels in (z, y, x) order; the info
-    counts n_points, n_voxels, n_small, n_degenerate, n_kept; and the doubles behind the records: mean64, cov64 (C'), lam, l (clamped)"""
+    counts n_points, n_voxels, n_small, n_degenerate, n_kept; and the doubles behind the records: mean64, cov64 (C'), cov_raw (C, before
+    the eigen-solve), lam, l (clamped)"""
     xyz = np.ascontiguousarray(np.asarray(xyz, np.float32)[:, :3])
     n = len(xyz)
     v = voxel_of(xyz, leaf)
@@ -79,7 +80,7 @@ def voxel_map(xyz, leaf=1.0, epsilon=1e-3, min_points=6):
         Cp[:, k] = ((V[:, a, 0] * l[:, 0]) * V[:, b, 0] + (V[:, a, 1] * l[:, 1]) * V[:, b, 1]) + (V[:, a, 2] * l[:, 2]) * V[:, b, 2]
     return dict(coords=np.ascontiguousarray(co[ok]), count=ct[ok].astype(np.int32), mean=mu[ok].astype(np.float32), cov=Cp[ok].astype(np.float32),
                 n_points=n, n_voxels=n_vox, n_small=int((~big).sum()), n_degenerate=int((~ok).sum()), n_kept=int(ok.sum()),
-                mean64=mu[ok], cov64=Cp[ok], lam=lam[ok], l=l[ok], V=V[ok], leaf=float(leaf))
+                mean64=mu[ok], cov64=Cp[ok], cov_raw=C[ok], lam=lam[ok], l=l[ok], V=V[ok], leaf=float(leaf))
 
 
 def find(vmap, q):
