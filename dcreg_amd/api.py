@@ -205,6 +205,8 @@ EXPORTS = [
     "dcreg_default_voxel_map_params", "dcreg_target_voxels_keep", "dcreg_target_voxels_get", "dcreg_target_voxels_kept", "dcreg_target_voxels_drop",
     "dcreg_linearize_voxels", "dcreg_linearize_voxels_debug", "dcreg_icp_run_voxels",
     "dcreg_voxels_batch_begin", "dcreg_voxels_batch_end", "dcreg_register_frames_voxels", "dcreg_icp_run_trials_voxels",
+    "dcreg_register_pairs_voxels", "dcreg_pairs_plan_voxels", "dcreg_pairs_voxels_build", "dcreg_pairs_voxels_get", "dcreg_pairs_voxels_kept",
+    "dcreg_voxel_map_params_check", "dcreg_pairs_voxels_box_check", "dcreg_pairs_voxels_batch_begin",
 ]
 
 _lib = None
@@ -1208,6 +1210,17 @@ def load():
         L.dcreg_pairs_normals_reserve_slots.argtypes = [vp, C.c_int64]
         for name in ("dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin"):
             getattr(L, name).argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, ip, C.POINTER(LinParams)]
+    if hasattr(L, "dcreg_register_pairs_voxels"):  # (likewise)
+        vmp, np_ = C.POINTER(VoxelMapParams), C.POINTER(NormalParams)
+        L.dcreg_register_pairs_voxels.argtypes = [vp, C.c_int, fp, i64p, fp, i64p, C.c_int64, vmp, np_, dp, dp, C.c_int, C.c_int, C.POINTER(Config),
+                                                  C.c_int, C.POINTER(TrialResult)]
+        L.dcreg_pairs_plan_voxels.argtypes = [vp, C.c_int, i64p, C.c_int64, ip, C.POINTER(C.c_int)]
+        L.dcreg_pairs_voxels_build.argtypes = [vp, C.c_int, fp, i64p, C.c_int64, vmp, C.POINTER(VoxelMapInfo)]
+        L.dcreg_pairs_voxels_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int64]
+        L.dcreg_pairs_voxels_kept.argtypes = [vp, C.c_int]
+        L.dcreg_voxel_map_params_check.argtypes = [vp, vmp]
+        L.dcreg_pairs_voxels_box_check.argtypes = [vp, fp, fp, C.c_double, C.c_int]
+        L.dcreg_pairs_voxels_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2983,6 +2996,62 @@ class Context:
         """dcreg_pairs_gicp_batch_begin + dcreg_normals_batch_end: the same for linearize_gicp, with the sources' kept normals"""
         n = self._pairs_batch_begin("dcreg_pairs_gicp_batch_begin", Ts, source_ids, target_ids, state_ids, params, slot)
         return self.normals_batch_end(n, slot)
+
+    # ---- the fourth engine's pairs form (include/dcreg.h: dcreg_register_pairs_voxels) and its device seam (include/dcreg_debug.h:
+    # dcreg_pairs_voxels_build / _get / _kept, dcreg_pairs_voxels_batch_begin)
+    def register_pairs_voxels(self, sources, targets, T0s, method, cfg, target_voxels=None, source_normals=None, slots=0):
+        """dcreg_register_pairs_voxels: register_pairs with the fourth engine - a voxel map per target (target_voxels =
+        voxel_map_params(...), None = the defaults) instead of an index.  source_normals = normal_params(...) is the rule every source's
+        own normals are estimated with when set_option("voxels_source_cov", 1) is on - it is required then - and is not read otherwise
+        (None: a null pointer is passed).  Each record is bitwise set_target(target, any radius) + keep_target_voxels(target_voxels) +
+        set_source(source) [+ keep_source_normals(source_normals)] + icp_run_voxels(T0); a target that keeps no voxel gives status 3."""
+        tv = target_voxels if target_voxels is not None else voxel_map_params()
+        _check_voxel_map_params(tv, "register_pairs_voxels")
+        if source_normals is not None:
+            _check_normal_params(source_normals, "register_pairs_voxels")
+        return self._register_pairs("dcreg_register_pairs_voxels", "register_pairs_voxels", sources, targets, T0s, method, cfg, slots,
+                                    extra_args=(C.byref(tv), None if source_normals is None else C.byref(source_normals)))
+
+    def pairs_voxels_build(self, targets, params=None):
+        """dcreg_pairs_voxels_build: the targets of one build batch (a list of [n_i, c] arrays) uploaded, packed and every one's voxel map
+        kept, all at once; no grid is built -> [info dict per target], as keep_target_voxels returns"""
+        p = params if params is not None else voxel_map_params()
+        _check_voxel_map_params(p, "pairs_voxels_build")
+        xyz, off, n = _frames_arg(targets, "pairs_voxels_build")
+        infos = (VoxelMapInfo * max(n, 1))()
+        self._check(self._L.dcreg_pairs_voxels_build(self._h, n, xyz.ctypes.data_as(C.POINTER(C.c_float)), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     xyz.shape[1], C.byref(p), infos), "dcreg_pairs_voxels_build")
+        return [{k: int(getattr(infos[t], k)) for k, _ in VoxelMapInfo._fields_} for t in range(n)]
+
+    def pairs_voxels_kept(self, t):
+        """dcreg_pairs_voxels_kept: the kept voxels of target t of the pairs' voxel batch, 0 without a member"""
+        return int(self._L.dcreg_pairs_voxels_kept(self._h, int(t)))
+
+    def pairs_kept_voxels(self, t):
+        """dcreg_pairs_voxels_get: target t's member of the pairs' voxel batch -> the dict kept_target_voxels returns"""
+        n = self.pairs_voxels_kept(t)
+        m = max(n, 1)
+        coords, count = np.zeros((m, 3), np.int64), np.zeros(m, np.int32)
+        mean, cov = np.zeros((m, 3), np.float32), np.zeros((m, 6), np.float32)
+        self._check(self._L.dcreg_pairs_voxels_get(self._h, int(t), coords.ctypes.data, count.ctypes.data, mean.ctypes.data, cov.ctypes.data, n),
+                    "dcreg_pairs_voxels_get")
+        return {"coords": coords[:n], "count": count[:n], "mean": mean[:n], "cov": cov[:n]}
+
+    def pairs_voxels_batch_begin(self, Ts, source_ids, target_ids, params=None, slot=0):
+        """dcreg_pairs_voxels_batch_begin: one launch over the poses Ts; pose i linearises pair source source_ids[i] against the voxel map
+        of target target_ids[i] of the batch.  -> the number of poses, for voxels_batch_end"""
+        params = self._vlin_params(params, "pairs_voxels_batch_begin")
+        Rs, ts, n = _poses_arg(Ts)
+        i32p = C.POINTER(C.c_int32)
+        sids = np.ascontiguousarray(source_ids, dtype=np.int32).reshape(n)
+        tids = np.ascontiguousarray(target_ids, dtype=np.int32).reshape(n)
+        self._check(self._L.dcreg_pairs_voxels_batch_begin(self._h, int(slot), n, _dp(Rs), _dp(ts), sids.ctypes.data_as(i32p), tids.ctypes.data_as(i32p),
+                                                           C.byref(params)), "dcreg_pairs_voxels_batch_begin")
+        return n
+
+    def pairs_voxels_batch(self, Ts, source_ids, target_ids, params=None, slot=0):
+        """pairs_voxels_batch_begin + voxels_batch_end -> one dict per pose, as linearize_voxels returns"""
+        return self.voxels_batch_end(self.pairs_voxels_batch_begin(Ts, source_ids, target_ids, params, slot), slot)
 
     def insert(self, xyz, T, min_spacing=0.0):
         """dcreg_target_insert: the points xyz (body frame) transformed by the 4x4 pose T appended to the map, except those with a map point

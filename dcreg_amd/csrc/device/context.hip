@@ -1190,6 +1190,18 @@ static double pairs_budget(dcreg_ctx *c) {
 static double pair_target_bytes(const dcreg_ctx *c, int64_t m, int64_t stride, double extra = 0.0) {
     return m > 0 ? (double)m * (4.0 * (double)stride + 16.0 + 16.0 + 16.0 + 8.0 + extra) + 4.0 * (double)c->opt_pair_max_table_entries + 16.0 * kPtsPad : 0.0;
 }
+// ... and what a target of m points is counted at in a build batch of dcreg_register_pairs_voxels (voxel.hip pairs_voxels_build), which
+// allocates no cell table.  Per point: the upload (stride floats), the packed point (16), its cloud and relative key (4 + 8), the head
+// flags, their scan, the voxel starts, the keep flags and their scan (5 x 4), the sort's two key and two value arrays (2 x 8 + 2 x 4)
+// and its own temporary storage, bounded by a further copy of keys and values and its digit counters (16).  Per voxel - a target has at
+// most m of them: the records before compaction (48).  Per kept voxel - each holds at least min_points >= 2 points, so at most m / 2:
+// its record (48), its key (8) and fewer than 4 table slots of 8 + 4 bytes (48), together at most 52 a point.  Per target, points or
+// not: offsets, counters, bounds and its record (256 covers them).  This is the peak of a build; the packed points, the sort's arrays and
+// the per-voxel scratch are scratch of the voxel pass (dcreg_ctx::vox) and are not read while the batch's pairs run, so what a batch
+// holds then is below what it was planned with
+static double pair_voxel_target_bytes(int64_t m, int64_t stride) {
+    return 256.0 + (double)m * (4.0 * (double)stride + 16.0 + 12.0 + 20.0 + 24.0 + 16.0 + 48.0 + 52.0);
+}
 
 // One pass over some targets of the batch (J: batch targets, cells[j]: the geometry of J[j] in this pass): cell keys of all their points
 // in one kernel, ONE sort over (pass target, cell).  occ != null: the occupied cells of every pass target (one readback).  Otherwise the
@@ -2637,7 +2649,8 @@ static int frames_reset_state(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int64_t sta
 }
 int dcreg_frames_reserve_states(dcreg_ctx *c, int64_t n_states) { return c ? frames_reserve_states(c, c->frames, n_states) : DCREG_E_INVALID; }
 int dcreg_frames_reset_state(dcreg_ctx *c, int64_t state_id) { return c ? frames_reset_state(c, c->frames, state_id) : DCREG_E_INVALID; }
-static int pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, double extra, int32_t *batch_end, int *n_batches) {
+static int pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, double extra, int32_t *batch_end, int *n_batches,
+                      bool voxels = false) {
     if (!c || n_pairs < 0 || !tgt_offsets || !batch_end || !n_batches) return DCREG_E_INVALID;
     // build batches of pair targets within the byte budget (pairs_budget): at least one pair each, fewer than 2^31 points each
     const double budget = pairs_budget(c);
@@ -2646,7 +2659,7 @@ static int pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int
     int64_t pts = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const int64_t m = tgt_offsets[p + 1] - tgt_offsets[p];
-        const double b = pair_target_bytes(c, m, stride_floats, extra);
+        const double b = voxels ? pair_voxel_target_bytes(m, stride_floats) : pair_target_bytes(c, m, stride_floats, extra);
         if (p > 0 && (bytes + b > budget || pts + m >= ((int64_t)1 << 31) - 1)) { batch_end[nb++] = p; bytes = 0.0; pts = 0; }
         bytes += b; pts += m;
     }
@@ -2660,6 +2673,10 @@ int dcreg_pairs_plan(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int6
 // ... for the 1-NN engines: a batch also holds its targets' kept normals (16 B a point) and the scratch of their estimation (3 + 1 floats)
 int dcreg_pairs_plan_normals(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
     return pairs_plan(c, n_pairs, tgt_offsets, stride_floats, 32.0, batch_end, n_batches);
+}
+// ... for the fourth engine: a batch is counted with what pairs_voxels_build allocates (pair_voxel_target_bytes), not with a cell table
+int dcreg_pairs_plan_voxels(dcreg_ctx *c, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches) {
+    return pairs_plan(c, n_pairs, tgt_offsets, stride_floats, 0.0, batch_end, n_batches, true);
 }
 int dcreg_pairs_sources_load(dcreg_ctx *c, int n_pairs, const float *xyz, const int64_t *src_offsets, int64_t stride_floats) {
     if (!c) return DCREG_E_INVALID;

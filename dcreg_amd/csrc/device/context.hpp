@@ -148,6 +148,14 @@ struct OneNnGrid {
     int max_ring;
     uint32_t normals_first;
 };
+// the target of one scan pair as the fourth engine's pairs launch reads it (voxel_icp.hip k_vlin_pairs): the build batch's kept records,
+// keys and lookup tables lie target after target (voxel.hip pairs_voxels_build); this target's records start at record `first`, its own
+// table - mask + 1 slots, the values record numbers within the target - at slot `base`; mn / mx: the voxel box of all its points.
+// n_kept == 0: no member, nothing else is read.  The leaf is the batch's
+struct PairVoxMap {
+    uint32_t first, base, mask, n_kept;
+    long long mn[3], mx[3];
+};
 }  // namespace dcreg
 
 // What a linearisation launch is and how it is carried out (context.hip linearize_begin: lin_check settles the kind, lin_plan the rest)
@@ -627,6 +635,25 @@ struct dcreg_ctx {
     struct LaunchRec { double ms; int64_t searched, refitted, points; int advanced, structure; };
     bool opt_record_launches = false;
     std::vector<LaunchRec> launch_series;
+
+    // The pairs' voxel maps (voxel.hip pairs_voxels_build: dcreg_pairs_voxels_build, the build batch of dcreg_register_pairs_voxels): one
+    // kept voxel map per target of the batch, all of them built at once.  recs / vkeys: the kept records and keys of all targets, target
+    // after target, each target's in dcreg_target_voxels_get order; t_keys / t_vals: the targets' lookup tables one behind the other, each
+    // the power of two at or above twice its kept voxels; maps / d_maps: per target where its records and table start, its mask and its
+    // voxel box (host and device copies).  tmp, d_cnt (per target: voxels, small, degenerate, kept) and d_words (the pack's bounds) are
+    // scratch of a build; the packed points and the sort run in the voxel pass's scratch (vox).  Every build replaces the batch; the
+    // pairs' index batch (pairs) is another member and is not touched.  (Last in the struct: no option field above moves.)
+    struct PairVoxBufs {
+        DevBuf<float4> recs, tmp;
+        DevBuf<uint64_t> vkeys, t_keys;
+        DevBuf<uint32_t> t_vals, d_words;
+        DevBuf<unsigned long long> d_cnt;
+        DevBuf<dcreg::PairVoxMap> d_maps;
+        std::vector<dcreg::PairVoxMap> maps;
+        int n = 0;                                             // targets of the batch (0: none built)
+        double leaf = 0.0;
+    };
+    PairVoxBufs pvox;
 
     void fail(const char *fmt, ...);
 };

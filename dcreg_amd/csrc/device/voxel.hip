@@ -12,6 +12,8 @@
 //   (readback)     counts, bounds: the only one at the end of the call
 // The packed points come from upload_cloud: k_pack, the deskew packs (DeskewRun) or the keyframe gather (GatherRun, keyframes.hip).
 // A voxel's result depends on its own points only: where its cloud sits in the call and how the launches are cut never enter it.
+// The kept voxel map of the fourth engine (voxel_map_keep: k_vmap_reduce, k_vmap_write) runs behind the same keying and sort, and so do
+// the voxel maps of a build batch of scan-pair targets, one per target, all at once (pairs_voxels_build: k_pvmap_count, k_pvmap_write).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -359,6 +361,69 @@ static __global__ void __launch_bounds__(kVoxBlock) k_vmap_write(const float4 *_
     }
 }
 
+// ---- the pairs' voxel maps (pairs_voxels_build): many targets' kept maps from ONE k_vmap_reduce over the voxels of all of them.
+// Per-target counters of a build: pc[4 s + 0] voxels, + 1 below min_points, + 2 degenerate, + 3 kept.  One lane per voxel; the voxels
+// are in (target, z, y, x) order, so the targets of a wave's active lanes ascend: one atomic set per run of a target in a wave (integer
+// atomics: the counts do not depend on the order).  A voxel that is neither small nor kept is degenerate (k_vmap_reduce's rule).
+static __global__ void __launch_bounds__(kVoxBlock) k_pvmap_count(const uint32_t *__restrict__ ord, int64_t n_vox, const uint32_t *__restrict__ seg,
+                                                                  const uint32_t *__restrict__ start, const uint32_t *__restrict__ keep, int min_points,
+                                                                  unsigned long long *__restrict__ pc) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool act = v < n_vox;
+    uint32_t s = 0;
+    bool small = false, k = false;
+    if (act) {
+        const uint32_t b = start[v], e = start[v + 1];
+        s = seg[ord[b]];
+        small = (int64_t)(e - b) < (int64_t)min_points;
+        k = keep[v] != 0u;
+    }
+    const int lane = (int)(threadIdx.x & 63);
+    const uint32_t left = __shfl_up(s, 1);
+    const bool leader = act && (lane == 0 || left != s);
+    const uint64_t L = __ballot(leader), A = __ballot(act), S = __ballot(act && small), K = __ballot(act && k);
+    if (leader) {
+        const uint64_t above = lane == 63 ? 0ull : (L & ~((2ull << lane) - 1ull));
+        const int end = above ? __ffsll((unsigned long long)above) - 1 : 64 - __clzll((long long)A);     // next run / past the last active lane
+        const uint64_t run = (end >= 64 ? ~0ull : ((1ull << end) - 1ull)) & ~((1ull << lane) - 1ull);
+        const int n_run = end - lane, n_small = __popcll(S & run), n_kept = __popcll(K & run);
+        unsigned long long *p = pc + 4 * (size_t)s;
+        atomicAdd(p, (unsigned long long)n_run);
+        if (n_small) atomicAdd(p + 1, (unsigned long long)n_small);
+        if (n_run - n_small - n_kept) atomicAdd(p + 2, (unsigned long long)(n_run - n_small - n_kept));
+        if (n_kept) atomicAdd(p + 3, (unsigned long long)n_kept);
+    }
+}
+
+// k_vmap_write for many targets: the compaction of the kept voxels (pos = exclusive scan of keep over the voxels of ALL targets: the
+// (target, z, y, x) order makes every target's records contiguous and in dcreg_target_voxels_get order, target s from record
+// maps[s].first) and the fill of every target's OWN table - maps[s].mask + 1 slots from slot maps[s].base, the key relative to that
+// target's minimum voxel, the value the record's number within the target.  The probing is k_vmap_write's: one 64-bit atomicCAS claims
+// the first free slot; a target's table is at most half full, so the loop ends inside it.
+static __global__ void __launch_bounds__(kVoxBlock) k_pvmap_write(const float4 *__restrict__ rec, const uint32_t *__restrict__ keep,
+                                                                  const uint32_t *__restrict__ pos, int64_t n_vox, const uint32_t *__restrict__ ord,
+                                                                  const uint32_t *__restrict__ seg, const uint32_t *__restrict__ start,
+                                                                  const uint64_t *__restrict__ rel, int bx, int by,
+                                                                  const PairVoxMap *__restrict__ maps, float4 *__restrict__ recs,
+                                                                  uint64_t *__restrict__ vkeys, uint64_t *__restrict__ t_keys,
+                                                                  uint32_t *__restrict__ t_vals) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vox || !keep[v]) return;
+    const uint32_t j = pos[v], o = ord[start[v]];
+    recs[3 * (size_t)j] = rec[3 * v]; recs[3 * (size_t)j + 1] = rec[3 * v + 1]; recs[3 * (size_t)j + 2] = rec[3 * v + 2];
+    const uint64_t r = rel[o];
+    const uint64_t key = vmap_key(r & ((1ull << bx) - 1ull), (r >> bx) & ((1ull << by) - 1ull), r >> (bx + by));
+    vkeys[j] = key;
+    const PairVoxMap m = maps[seg[o]];
+    uint64_t *tk = t_keys + m.base;
+    uint32_t s = vmap_slot(key, m.mask);
+    for (;;) {                                           // (ends: at most half of the target's slots are ever claimed)
+        const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(tk + s), (unsigned long long)kVmapEmpty, (unsigned long long)key);
+        if (was == (unsigned long long)kVmapEmpty) { t_vals[m.base + s] = j - m.first; break; }
+        s = (s + 1u) & m.mask;
+    }
+}
+
 template <typename K>
 int sort_pairs(dcreg_ctx *c, K *keys_in, K *keys_out, uint32_t *vals_in, uint32_t *vals_out, size_t n, int bits) {
     size_t tmp = 0;
@@ -640,11 +705,227 @@ static int voxel_map_get(dcreg_ctx *c, int64_t *coords, int32_t *count, float *m
     return DCREG_OK;
 }
 
+// the parameter refusals of dcreg_target_voxels_keep on their own, in its order (dcreg_register_pairs_voxels makes them before its empty
+// call returns; pairs_voxels_build before it touches anything)
+int voxel_map_params_check(dcreg_ctx *c, const dcreg_voxel_map_params *p) {
+    if (!c) return DCREG_E_INVALID;
+    if (!p) { c->fail("null voxel map parameters"); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->leaf) && p->leaf > 0.0)) { c->fail("voxel map leaf is %g: finite and > 0 expected", p->leaf); return DCREG_E_INVALID; }
+    if (!(p->epsilon >= 1.0e-6 && p->epsilon <= 1.0)) { c->fail("voxel map epsilon is %g: 1e-6 .. 1 expected", p->epsilon); return DCREG_E_INVALID; }
+    if (p->min_points < 2) { c->fail("voxel map min_points is %d: at least 2 expected", p->min_points); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+// What the voxel box of a cloud with these float bounds refuses (floor((double)x / leaf) is monotonic in the float x: the box of a cloud's
+// voxels is exactly the voxels of its coordinate-wise minimum and maximum): a coordinate of magnitude 2^62 or more, 2^21 or more voxels
+// on an axis.  dcreg_register_pairs_voxels checks the targets of its later build batches with it on the host, before anything is queued;
+// the device's own counters (k_vox_coords) refuse the same targets in a build.  `t`: the target's number in the message
+int voxel_box_check(dcreg_ctx *c, const float mn[3], const float mx[3], double leaf, int t) {
+    for (int a = 0; a < 3; ++a) {
+        const double lo = std::floor((double)mn[a] / leaf), hi = std::floor((double)mx[a] / leaf);
+        if (!(std::fabs(lo) < kVoxLimit) || !(std::fabs(hi) < kVoxLimit)) {
+            c->fail("a voxel coordinate of pair target %d reaches 2^62 (leaf too small for the coordinates)", t);
+            return DCREG_E_INVALID;
+        }
+        const int64_t d = (int64_t)hi - (int64_t)lo;
+        if (d + 1 > kSpanMax) {
+            c->fail("pair target %d spans %lld voxels on axis %d (at most 2^21 - 1 = %lld)", t, (long long)d + 1, a, (long long)kSpanMax);
+            return DCREG_E_INVALID;
+        }
+    }
+    return DCREG_OK;
+}
+
+// The kept voxel maps of one build batch of pair targets (xyz: HOST memory, target t = points [off[t], off[t + 1]), off[0] = 0): target
+// t's member is bitwise what dcreg_set_target(target t) + dcreg_target_voxels_keep(p) keep - a voxel map depends on the target's points
+// in upload order only, so no grid, no cell table and no normals are built.  All targets at once: ONE upload, ONE pack with the float
+// bounds (k_pairs_pack), ONE k_vox_coords, the order of vox_order (ONE sort when target and voxel bits fit 64, else TWO; ONE scan), ONE
+// k_vmap_reduce over the voxels of all targets - unchanged: its per-voxel rule and summation order are the contract - ONE scan of the
+// keep flags, ONE k_pvmap_count, ONE k_pvmap_write.  FOUR stream synchronises (bounds and voxel boxes; the voxel count; the per-target
+// counters; the end), whatever the number of targets.  Everything is refused before the batch on the device is replaced: a non-finite
+// coordinate, a voxel coordinate of 2^62, a target of 2^21 voxels on an axis (DCREG_E_INVALID).  infos (may be null): one record per
+// target, as dcreg_target_voxels_keep fills it
+int pairs_voxels_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *off, int64_t stride, const dcreg_voxel_map_params *p,
+                       dcreg_voxel_map_info *infos) {
+    if (int rc = voxel_map_params_check(c, p)) return rc;
+    if (n_t < 0 || !off || stride < 3 || off[0] != 0) { c->fail("invalid pair target arguments"); return DCREG_E_INVALID; }
+    for (int t = 0; t < n_t; ++t)
+        if (off[t + 1] < off[t]) { c->fail("pair target offsets decrease at target %d", t); return DCREG_E_INVALID; }
+    const int64_t n = n_t > 0 ? off[n_t] : 0;
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (n >= ((int64_t)1 << 31) - 1) { c->fail("the pair targets of one build batch hold too many points (%lld)", (long long)n); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::PairVoxBufs &V = c->pvox;
+    dcreg_ctx::VoxelBufs &B = c->vox;
+    std::vector<PairVoxMap> maps((size_t)n_t);
+    std::memset(maps.data(), 0, sizeof(PairVoxMap) * (size_t)n_t);
+    std::vector<unsigned long long> pc((size_t)4 * std::max(n_t, 1), 0ull);
+    const double l = p->leaf;
+    // the targets' records to the device (a target without a member is a record of zeros)
+    auto upload_maps = [&]() -> int {
+        if (V.d_maps.ensure(c, (size_t)std::max(n_t, 1))) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(V.d_maps.data(), maps.data(), sizeof(PairVoxMap) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
+        return DCREG_OK;
+    };
+    // the end of a build: the last wait (maps is the source of the copy above), the infos, the batch
+    auto finish = [&]() -> int {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        for (int t = 0; infos && t < n_t; ++t) {
+            infos[t].n_points = off[t + 1] - off[t]; infos[t].n_voxels = (int64_t)pc[(size_t)4 * t]; infos[t].n_small = (int64_t)pc[(size_t)4 * t + 1];
+            infos[t].n_degenerate = (int64_t)pc[(size_t)4 * t + 2]; infos[t].n_kept = (int64_t)pc[(size_t)4 * t + 3];
+        }
+        V.maps = std::move(maps);
+        V.leaf = l;
+        V.n = n_t;
+        return DCREG_OK;
+    };
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n == 0) {                                          // (no points at all: every target without a member)
+        V.n = 0;
+        if (n_t > 0) if (int rc = upload_maps()) return rc;
+        return finish();
+    }
+    const size_t nc = (size_t)kCnt * n_t + kTail;
+    if (B.pts.ensure(c, (size_t)n) || B.seg.ensure(c, (size_t)n) || B.rel.ensure(c, (size_t)n) || B.head.ensure(c, (size_t)n) ||
+        B.incl.ensure(c, (size_t)n) || B.start.ensure(c, (size_t)n + 1) || B.keep.ensure(c, (size_t)n) || B.pos.ensure(c, (size_t)n) ||
+        B.d_off.ensure(c, (size_t)n_t + 1) || B.cnt.ensure(c, nc) || c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
+        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) || c->d_stage.ensure(c, (size_t)(n * stride)) ||
+        V.d_words.ensure(c, (size_t)6 * n_t) || V.d_cnt.ensure(c, (size_t)4 * n_t + 2))
+        return DCREG_E_NOMEM;
+    // ---- upload, pack and float bounds, voxel boxes: one readback
+    HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * ((size_t)n_t + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(V.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+    HIP_TRY(c, hipMemsetAsync(V.d_words.data() + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
+    HIP_TRY(c, hipMemsetAsync(V.d_cnt.data(), 0, sizeof(unsigned long long) * (4 * (size_t)n_t + 2), c->stream));     // (+ 2: k_vmap_reduce's own two counts)
+    hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, B.d_off.data(), n_t, B.pts.data(), V.d_words.data());
+    hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), n_t);
+    hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), n, B.d_off.data(), n_t, l, l, l,
+                       B.seg.data(), B.cnt.data());
+    std::vector<uint32_t> words((size_t)6 * n_t);
+    std::vector<int64_t> h(nc);
+    HIP_TRY(c, hipMemcpyAsync(words.data(), V.d_words.data(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h.data(), B.cnt.data(), sizeof(int64_t) * nc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    // ---- the refusals of the batch (the batch a previous build left is still whole)
+    for (int t = 0; t < n_t; ++t) {
+        if (off[t + 1] == off[t]) continue;
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(ord2f(words[(size_t)3 * t + a])) || !std::isfinite(ord2f(words[(size_t)3 * n_t + 3 * t + a]))) { c->fail("pair target %d has non-finite coordinates", t); return DCREG_E_INVALID; }
+    }
+    uint32_t tail[2 * kTail];
+    std::memcpy(tail, h.data() + (size_t)kCnt * n_t, sizeof(tail));
+    if (tail[6]) { c->fail("a voxel coordinate of a pair target reaches 2^62 (leaf too small for the coordinates)"); return DCREG_E_INVALID; }
+    int64_t span[3] = {0, 0, 0};
+    for (int t = 0; t < n_t; ++t) {
+        const int64_t *q = h.data() + (size_t)kCnt * t;
+        if (q[6] == 0) continue;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t d = q[3 + a] - q[a];
+            if (d + 1 > kSpanMax) {                           // (d = maximum - minimum: d + 1 voxels)
+                c->fail("pair target %d spans %lld voxels on axis %d (at most 2^21 - 1 = %lld)", t, (long long)d + 1, a, (long long)kSpanMax);
+                return DCREG_E_INVALID;
+            }
+            span[a] = std::max(span[a], d);
+            maps[(size_t)t].mn[a] = q[a]; maps[(size_t)t].mx[a] = q[3 + a];
+        }
+    }
+    V.n = 0;                                               // (the member's arrays are rewritten from here on: a failure leaves no batch)
+    const int bx = bits_for(span[0]), by = bits_for(span[1]), bz = bits_for(span[2]);
+    // ---- keys, stable sort, voxel heads and starts over all targets; the voxel count
+    const uint32_t *ord;
+    int rc = vox_order(c, B.pts.data(), n, n_t, l, l, l, bx, by, bz, ord);
+    if (rc) return rc;
+    uint32_t n_vox32 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_vox32, B.incl.data() + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t n_vox = n_vox32;
+    // ---- one lane per voxel of any target, the scan of the keep flags, the per-target counters
+    if (V.tmp.ensure(c, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), ord, n_vox, B.start.data(), p->min_points,
+                       p->epsilon, V.tmp.data(), B.keep.data(), V.d_cnt.data() + 4 * (size_t)n_t);
+    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pvmap_count, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n_vox, B.seg.data(), B.start.data(), B.keep.data(),
+                       p->min_points, V.d_cnt.data());
+    HIP_TRY(c, hipMemcpyAsync(pc.data(), V.d_cnt.data(), sizeof(unsigned long long) * 4 * (size_t)n_t, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    // ---- the members: every target's first record, and its table of the power of two at or above twice its kept voxels
+    size_t n_kept = 0, n_slots = 0;
+    for (int t = 0; t < n_t; ++t) {
+        PairVoxMap &m = maps[(size_t)t];
+        const size_t k = (size_t)pc[(size_t)4 * t + 3];
+        if (k == 0) continue;
+        size_t slots = 2;
+        while (slots < 2 * k) slots <<= 1;
+        m.first = (uint32_t)n_kept; m.base = (uint32_t)n_slots; m.mask = (uint32_t)(slots - 1); m.n_kept = (uint32_t)k;
+        n_kept += k; n_slots += slots;
+    }
+    if ((rc = upload_maps())) return rc;
+    if (n_kept == 0) return finish();                      // (no target keeps a voxel: no member anywhere)
+    if (n_slots > 0xFFFFFFFFull) { c->fail("the pair targets' lookup tables hold too many slots (%zu)", n_slots); return DCREG_E_INVALID; }
+    if (V.recs.ensure(c, 3 * n_kept) || V.vkeys.ensure(c, n_kept) || V.t_keys.ensure(c, n_slots) || V.t_vals.ensure(c, n_slots)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(V.t_keys.data(), 0xFF, n_slots * sizeof(uint64_t), c->stream));
+    hipLaunchKernelGGL(k_pvmap_write, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, V.tmp.data(), B.keep.data(), B.pos.data(), n_vox, ord, B.seg.data(),
+                       B.start.data(), B.rel.data(), bx, by, V.d_maps.data(), V.recs.data(), V.vkeys.data(), V.t_keys.data(), V.t_vals.data());
+    HIP_TRY(c, hipGetLastError());
+    return finish();                                       // (waits for the stream)
+}
+
+// dcreg_pairs_voxels_get: one target's member of the batch to the host, unpacked as voxel_map_get unpacks the map's
+static int pairs_voxels_get(dcreg_ctx *c, int target, int64_t *coords, int32_t *count, float *mean, float *cov, int64_t capacity) {
+    if (!c) return DCREG_E_INVALID;
+    if (!coords || !count || !mean || !cov) { c->fail("null argument"); return DCREG_E_INVALID; }
+    if (int rc = refuse_in_flight(c)) return rc;
+    const dcreg_ctx::PairVoxBufs &V = c->pvox;
+    if (V.n <= 0) { c->fail("no pair voxel batch built: dcreg_pairs_voxels_build first"); return DCREG_E_STATE; }
+    if (target < 0 || target >= V.n) { c->fail("pair target %d is not in the batch", target); return DCREG_E_INVALID; }
+    const PairVoxMap &m = V.maps[(size_t)target];
+    if (capacity < (int64_t)m.n_kept) { c->fail("the output holds %lld voxels, the target keeps %u", (long long)capacity, m.n_kept); return DCREG_E_INVALID; }
+    if (m.n_kept == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nk = m.n_kept;
+    std::vector<float> rec(12 * nk);
+    std::vector<uint64_t> keys(nk);
+    HIP_TRY(c, hipMemcpyAsync(rec.data(), V.recs.data() + 3 * (size_t)m.first, sizeof(float) * 12 * nk, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(keys.data(), V.vkeys.data() + m.first, sizeof(uint64_t) * nk, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t am = (1ull << kVmapAxisBits) - 1ull;
+    for (size_t j = 0; j < nk; ++j) {
+        const float *r = rec.data() + 12 * j;
+        coords[3 * j] = m.mn[0] + (int64_t)(keys[j] & am);
+        coords[3 * j + 1] = m.mn[1] + (int64_t)((keys[j] >> kVmapAxisBits) & am);
+        coords[3 * j + 2] = m.mn[2] + (int64_t)(keys[j] >> (2 * kVmapAxisBits));
+        std::memcpy(mean + 3 * j, r, 3 * sizeof(float));
+        std::memcpy(cov + 6 * j, r + 3, 6 * sizeof(float));
+        std::memcpy(count + j, r + 9, sizeof(int32_t));
+    }
+    return DCREG_OK;
+}
+
 }  // namespace dcreg
 
 using namespace dcreg;
 
 extern "C" {
+int dcreg_voxel_map_params_check(dcreg_ctx *c, const dcreg_voxel_map_params *p) { return voxel_map_params_check(c, p); }
+int dcreg_pairs_voxels_build(dcreg_ctx *c, int n_targets, const float *xyz, const int64_t *tgt_offsets, int64_t stride_floats,
+                             const dcreg_voxel_map_params *p, dcreg_voxel_map_info *infos) {
+    return c ? pairs_voxels_build(c, n_targets, xyz, tgt_offsets, stride_floats, p, infos) : DCREG_E_INVALID;
+}
+int dcreg_pairs_voxels_get(dcreg_ctx *c, int target, int64_t *coords, int32_t *count, float *mean, float *cov, int64_t capacity_voxels) {
+    return pairs_voxels_get(c, target, coords, count, mean, cov, capacity_voxels);
+}
+int dcreg_pairs_voxels_kept(const dcreg_ctx *c, int target) {
+    return c && target >= 0 && target < c->pvox.n ? (int)c->pvox.maps[(size_t)target].n_kept : 0;
+}
+int dcreg_pairs_voxels_box_check(dcreg_ctx *c, const float mn[3], const float mx[3], double leaf, int target) {
+    return c && mn && mx ? voxel_box_check(c, mn, mx, leaf, target) : DCREG_E_INVALID;
+}
 int dcreg_voxel_downsample(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *offsets, int64_t stride_floats, const dcreg_voxel_params *p,
                            float *out_xyz, int64_t capacity_points, int64_t *out_offsets, dcreg_voxel_info *info) {
     return voxel_downsample_to(c, n_clouds, xyz, offsets, stride_floats, false, p, out_xyz, capacity_points, out_offsets, info);

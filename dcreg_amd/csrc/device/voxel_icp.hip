@@ -7,6 +7,9 @@
 //                  row in LDS, added in wave order.  Its LDS is the staging area of the Gram pass and the waves' sums - no RunList
 //   k_vlin_batch   the same for many poses in ONE launch (dcreg_voxels_batch_begin: the engine of dcreg_register_frames_voxels): block
 //                  (x, pose), every pose its own cloud - a frame of the loaded frames or the context's source - and nothing else per pose
+//   k_vlin_pairs   the same with a voxel map per pose (dcreg_pairs_voxels_batch_begin: the engine of dcreg_register_pairs_voxels): every
+//                  pose its own source of the pairs' sources and its own target's map of the pairs' voxel batch (voxel.hip
+//                  pairs_voxels_build), read through a block-uniform index
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_glin
 // vlin_run is the launch's own small run function: refusals, buffers, the dump block cut as one_nn_run cuts it, launch, k_finalize, wait.
 // It reads the source, the kept voxel map and - in mode 1 - the kept source normals; it neither reads nor writes warm words, neighbour
@@ -109,6 +112,50 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin_batch(const 
         sx = s4.x; sy = s4.y; sz = s4.z;
         VlinPoint x;
         flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
+    }
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
+                    [](int, const double (&)[8]) {});
+}
+
+// Scan pairs in one launch (dcreg_pairs_voxels_batch_begin: the engine of dcreg_register_pairs_voxels): k_vlin_batch with a voxel map per
+// pose.  Block (x, pose): pose = poses[blockIdx.y]; its cloud is slices[pose] of the pairs' sources (and, in mode 1, of their kept
+// normals); its target is maps[target_ids[pose]] of the pairs' voxel batch (voxel.hip pairs_voxels_build), read through a block-uniform
+// index as k_nlin_batch<GRIDS> reads its OneNnGrid - the VoxMapDev that vlin_point takes is formed from that record: the target's own
+// records, its own table, its own box; the leaf is the batch's.  A pose whose target has no member (n_kept 0) reads no table and no
+// record: its points keep flag 0 and the block row is the zero row.  The body is vlin_point and glin_block_rows, unchanged; the block
+// row goes where k_finalize<true> finds it.  A kernel of its own: k_vlin_batch is compiled from the source it had.
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin_pairs(const float4 *__restrict__ src, const float4 *__restrict__ src_normals,
+                                                                           const PairVoxMap *__restrict__ maps, const uint32_t *__restrict__ target_ids,
+                                                                           const float4 *__restrict__ recs, const uint64_t *__restrict__ t_keys,
+                                                                           const uint32_t *__restrict__ t_vals, double leaf,
+                                                                           const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
+                                                                           VlinArgs a, double *__restrict__ partials, uint32_t n_blocks_x) {
+    __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
+    __shared__ double gm[kLinBlock / kWave][64];
+    __shared__ double cnt[kLinBlock / kWave][2];
+    const uint32_t pose_id = blockIdx.y;
+    const uint2 sl = slices[pose_id];                    // (uniform per block: before anything is touched)
+    if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
+    src += sl.x;
+    const uint32_t n_src = sl.y;
+    if (src_normals) src_normals += sl.x;                // (mode 0: null, and never read)
+    const PairVoxMap &m = maps[target_ids[pose_id]];
+    VoxMapDev vm;
+    vm.recs = recs + (size_t)m.first * kVmapRecWords; vm.keys = t_keys + m.base; vm.vals = t_vals + m.base; vm.mask = m.mask; vm.leaf = leaf;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { vm.mn[k] = m.mn[k]; vm.mx[k] = m.mx[k]; }
+    const bool member = m.n_kept != 0u;
+    const PoseArg &P = poses[pose_id];
+    const int wave = threadIdx.x >> 6;
+    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
+    uint8_t flag = 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    GlinPoint o;
+    if (i < n_src) {
+        const float4 s4 = src[i];
+        sx = s4.x; sy = s4.y; sz = s4.z;
+        VlinPoint x;
+        if (member) flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
     }
     glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
                     [](int, const double (&)[8]) {});
@@ -222,6 +269,41 @@ int vlin_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, cons
     }, "the k_vlin_batch launch");
 }
 
+// The pairs launch (include/dcreg_debug.h: dcreg_pairs_voxels_batch_begin): vlin_batch_begin's refusals in its order, with "no pair voxel
+// batch built" and "no pair sources" in place of "no target", "no kept voxels" and "no frames", then the shared slot plumbing with
+// k_vlin_pairs as its kernel; the pose's target rides where the 1-NN pairs launches carry theirs (OneNnBatch::grid_ids)
+int vlin_pairs_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *source_ids, const int32_t *target_ids,
+                           const dcreg_lin_params *p) {
+    if (!c) return DCREG_E_INVALID;
+    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
+    if (!R9 || !t3 || !p || !source_ids || !target_ids || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    if (c->nicp.batch[slot].pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the voxel linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
+    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    const dcreg_ctx::PairVoxBufs &V = c->pvox;
+    if (V.n <= 0) { c->fail("no pair voxel batch built: dcreg_pairs_voxels_build first"); return DCREG_E_STATE; }
+    dcreg_ctx::FrameSet *fs = &c->pair_src;
+    const std::vector<uint2> &slice = fs->slice;
+    if (slice.empty()) { c->fail("no pair sources: dcreg_pairs_sources_load first"); return DCREG_E_STATE; }
+    int64_t n_max = 0;                                // points of the launch's largest cloud
+    for (int i = 0; i < n_poses; ++i) {
+        const int32_t f = source_ids[i], t = target_ids[i];
+        if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("pair source %d is not loaded or empty", f); return DCREG_E_INVALID; }
+        if (t < 0 || t >= V.n) { c->fail("pair target %d is not in the voxel batch", t); return DCREG_E_INVALID; }
+        n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
+    }
+    const VlinArgs a = vlin_args(c);
+    if (a.source_cov && !fs->normals_kept) { c->fail("no kept pair source normals: dcreg_pairs_sources_normals_keep or dcreg_pairs_sources_normals_set first"); return DCREG_E_STATE; }
+    return one_nn_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, source_ids, target_ids, n_max, [&](OneNnBatch &L) {
+        hipLaunchKernelGGL(k_vlin_pairs, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src,
+                           a.source_cov ? L.src_normals : (const float4 *)nullptr, V.d_maps.data(), L.grid_ids, V.recs.data(), V.t_keys.data(),
+                           V.t_vals.data(), V.leaf, L.poses, L.slices, a, L.partials, L.nbx);
+    }, "the k_vlin_pairs launch");
+}
+
 }  // namespace
 
 // "voxels_source_cov" for the engine's batched calls (engine.cpp reads it once when a call starts)
@@ -240,6 +322,10 @@ int dcreg_voxels_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *
     return vlin_batch_begin(c, slot, n_poses, R9, t3, frame_ids, p);
 }
 int dcreg_voxels_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
+int dcreg_pairs_voxels_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *source_ids,
+                                   const int32_t *target_ids, const dcreg_lin_params *p) {
+    return vlin_pairs_batch_begin(c, slot, n_poses, R9, t3, source_ids, target_ids, p);
+}
 int dcreg_linearize_voxels_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
                                  dcreg_vlin_debug *dbg) {
     if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }

@@ -332,8 +332,9 @@ int dcreg_icp_run_many(int n, dcreg_ctx *const *ctxs, const double *R0, const do
 // the third (dcreg_icp_run_trials_gicp, dcreg_register_frames_gicp, dcreg_register_pairs_gicp) - dcreg_gicp_batch_begin / _end on the same
 // launch and warm slots, the frames' kept normals beside the frames; with pairs the begin calls are dcreg_pairs_normals_batch_begin /
 // dcreg_pairs_gicp_batch_begin (every pose against its own target and that target's kept normals) and the warm slots are sized for the
-// pairs' sources; Engine::voxels, the fourth (dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels) - dcreg_voxels_batch_begin / _end
-// on the same launch slots; a voxel launch keeps nothing, so there is nothing to reserve or reset; everything else is shared
+// pairs' sources; Engine::voxels, the fourth (dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels, dcreg_register_pairs_voxels) -
+// dcreg_voxels_batch_begin / _end on the same launch slots, with pairs dcreg_pairs_voxels_batch_begin (every pose against its own target's
+// kept voxel map); a voxel launch keeps nothing, so there is nothing to reserve or reset; everything else is shared
 enum class Engine { planes, normals, gicp, voxels };
 static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, const double *t0, int detection, int handling,
                            const dcreg_config *cfg, dcreg_trial_result *results, int slots_wanted, const int64_t *frame_points = nullptr,
@@ -372,6 +373,7 @@ static int run_trials_core(dcreg_ctx *ctx, int64_t n_trials, const double *R0, c
     const EngineCalls E =
         engine == Engine::voxels ? EngineCalls{[](int) { return (int)DCREG_OK; }, [](int) {},
                                                [&](int gi, int nl, Group &G) {
+                                                   if (pairs) return dcreg_pairs_voxels_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), G.fids.data(), G.gids.data(), &prm);
                                                    return dcreg_voxels_batch_begin(ctx, gi, nl, G.Rb.data(), G.tb.data(), frames ? G.fids.data() : nullptr, &prm);
                                                },
                                                dcreg_voxels_batch_end, "_voxels"}
@@ -646,14 +648,20 @@ int dcreg_register_frames_voxels(dcreg_ctx *ctx, int n_frames, const float *xyz,
 // is indexed (dcreg_pairs_build) and its pairs run as frames do, each against its own target.
 // (engine: the first engine, or one of the 1-NN engines - dcreg_register_pairs_normals / _gicp: their parameter blocks are checked before the
 // empty call returns, a build batch is planned with its kept normals, the sources' own normals are estimated once behind the load (the
-// third engine), and every batch's target normals behind its build)
+// third engine), and every batch's target normals behind its build; or the fourth - dcreg_register_pairs_voxels: target_voxels is checked
+// in their place, a batch is planned with what a voxel build allocates and keeps a voxel map per target instead of an index, the targets
+// of later batches are also checked for the voxel box a build refuses, and a target that keeps no voxel gives its pair status 3)
 static int register_pairs_run(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
                               const int64_t *tgt_offsets, int64_t stride_floats, const double *R0, const double *t0, int detection,
                               int handling, const dcreg_config *cfg, int slots, dcreg_trial_result *results, Engine engine,
-                              const dcreg_normal_params *target_normals, const dcreg_normal_params *source_normals) {
+                              const dcreg_normal_params *target_normals, const dcreg_normal_params *source_normals,
+                              const dcreg_voxel_map_params *target_voxels = nullptr) {
     if (!ctx || !cfg || n_pairs < 0 || stride_floats < 3) return DCREG_E_INVALID;
-    if (engine != Engine::planes) if (int rc = dcreg_normal_params_check(ctx, target_normals)) return rc;
-    if (engine == Engine::gicp) if (int rc = dcreg_normal_params_check(ctx, source_normals)) return rc;
+    const bool voxels = engine == Engine::voxels;
+    const bool own_normals = engine == Engine::gicp || (voxels && dcreg::voxels_source_cov(ctx) != 0);   // ("voxels_source_cov": read once, here)
+    if (voxels) { if (int rc = dcreg_voxel_map_params_check(ctx, target_voxels)) return rc; }
+    else if (engine != Engine::planes) if (int rc = dcreg_normal_params_check(ctx, target_normals)) return rc;
+    if (own_normals) if (int rc = dcreg_normal_params_check(ctx, source_normals)) return rc;
     if (n_pairs == 0) return DCREG_OK;
     if (!src_offsets || !tgt_offsets || !R0 || !t0 || !results) return DCREG_E_INVALID;
     for (const int64_t *off : {src_offsets, tgt_offsets}) {
@@ -664,9 +672,31 @@ static int register_pairs_run(dcreg_ctx *ctx, int n_pairs, const float *src_xyz,
     if (tgt_offsets[n_pairs] > 0 && !tgt_xyz) { dcreg_set_error_message(ctx, "null target buffer"); return DCREG_E_INVALID; }
     std::vector<int32_t> ends((size_t)n_pairs);
     int n_batches = 0;
-    int rc = (engine == Engine::planes ? dcreg_pairs_plan : dcreg_pairs_plan_normals)(ctx, n_pairs, tgt_offsets, stride_floats, ends.data(), &n_batches);
+    int rc = (voxels ? dcreg_pairs_plan_voxels : engine == Engine::planes ? dcreg_pairs_plan : dcreg_pairs_plan_normals)(ctx, n_pairs, tgt_offsets, stride_floats,
+                                                                                                                         ends.data(), &n_batches);
     if (rc != DCREG_OK) return rc;
-    if (n_batches > 1) {         // (the first batch's targets are checked by its bounds pass, before anything runs)
+    if (n_batches > 1 && voxels) {
+        // the fourth engine's targets of the later batches: finiteness and - from the coordinate-wise float bounds the same pass collects -
+        // the voxel box a build would refuse (2^62, 2^21 voxels on an axis), so that no batch runs before every target is known to build
+        std::vector<float> box((size_t)6 * n_pairs);
+        int bad = 0;
+#pragma omp parallel for schedule(dynamic) num_threads(host_team()) reduction(| : bad)
+        for (int p = ends[0]; p < n_pairs; ++p) {
+            float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+            for (int64_t i = tgt_offsets[p]; i < tgt_offsets[p + 1]; ++i) {
+                const float *q = tgt_xyz + i * stride_floats;
+                for (int a = 0; a < 3; ++a) {
+                    if (!(std::fabs(q[a]) <= 3.4e38f)) bad = 1;
+                    mn[a] = std::min(mn[a], q[a]); mx[a] = std::max(mx[a], q[a]);
+                }
+            }
+            for (int a = 0; a < 3; ++a) { box[(size_t)6 * p + a] = mn[a]; box[(size_t)6 * p + 3 + a] = mx[a]; }
+        }
+        if (bad) { dcreg_set_error_message(ctx, "a pair target has non-finite coordinates"); return DCREG_E_INVALID; }
+        for (int p = ends[0]; p < n_pairs; ++p)
+            if (tgt_offsets[p + 1] > tgt_offsets[p])
+                if ((rc = dcreg_pairs_voxels_box_check(ctx, &box[(size_t)6 * p], &box[(size_t)6 * p + 3], target_voxels->leaf, p)) != DCREG_OK) return rc;
+    } else if (n_batches > 1) {  // (the first batch's targets are checked by its bounds pass, before anything runs)
         const int64_t first = tgt_offsets[ends[0]], n = tgt_offsets[n_pairs] - first;
         int bad = 0;
 #pragma omp parallel for schedule(static) num_threads(host_team()) reduction(| : bad)
@@ -678,9 +708,10 @@ static int register_pairs_run(dcreg_ctx *ctx, int n_pairs, const float *src_xyz,
     }
     rc = dcreg_pairs_sources_load(ctx, n_pairs, src_xyz, src_offsets, stride_floats);      // (non-finite coordinates: refused here)
     if (rc != DCREG_OK) return rc;
-    if (engine == Engine::gicp && src_offsets[n_pairs] > 0)                                 // (all sources empty: nothing to estimate, nothing to run)
+    if (own_normals && src_offsets[n_pairs] > 0)                                            // (all sources empty: nothing to estimate, nothing to run)
         if ((rc = dcreg_pairs_sources_normals_keep(ctx, source_normals, nullptr)) != DCREG_OK) return rc;
     std::vector<int64_t> points((size_t)n_pairs), rel;
+    std::vector<dcreg_voxel_map_info> infos;
     for (int p = 0; p < n_pairs; ++p) {
         const bool empty = src_offsets[p + 1] == src_offsets[p] || tgt_offsets[p + 1] == tgt_offsets[p];
         points[(size_t)p] = empty ? 0 : src_offsets[p + 1] - src_offsets[p];
@@ -689,9 +720,16 @@ static int register_pairs_run(dcreg_ctx *ctx, int n_pairs, const float *src_xyz,
         const int p0 = b > 0 ? ends[(size_t)b - 1] : 0, p1 = ends[(size_t)b];
         rel.resize((size_t)(p1 - p0) + 1);
         for (int p = p0; p <= p1; ++p) rel[(size_t)(p - p0)] = tgt_offsets[p] - tgt_offsets[p0];
-        rc = dcreg_pairs_build(ctx, p1 - p0, tgt_xyz ? tgt_xyz + tgt_offsets[p0] * stride_floats : nullptr, rel.data(), stride_floats, cfg->search_radius);
-        if (rc != DCREG_OK) return rc;
-        if (engine != Engine::planes && (rc = dcreg_pairs_normals_keep(ctx, target_normals, nullptr)) != DCREG_OK) return rc;
+        const float *batch_xyz = tgt_xyz ? tgt_xyz + tgt_offsets[p0] * stride_floats : nullptr;
+        if (voxels) {            // no index, no normals: the batch's voxel maps; a target that keeps nothing has nothing to register against
+            infos.resize((size_t)(p1 - p0));
+            if ((rc = dcreg_pairs_voxels_build(ctx, p1 - p0, batch_xyz, rel.data(), stride_floats, target_voxels, infos.data())) != DCREG_OK) return rc;
+            for (int p = p0; p < p1; ++p) if (infos[(size_t)(p - p0)].n_kept <= 0) points[(size_t)p] = 0;
+        } else {
+            rc = dcreg_pairs_build(ctx, p1 - p0, batch_xyz, rel.data(), stride_floats, cfg->search_radius);
+            if (rc != DCREG_OK) return rc;
+            if (engine != Engine::planes && (rc = dcreg_pairs_normals_keep(ctx, target_normals, nullptr)) != DCREG_OK) return rc;
+        }
         rc = run_trials_core(ctx, p1 - p0, R0 + 9 * (size_t)p0, t0 + 3 * (size_t)p0, detection, handling, cfg, results + p0, slots, points.data() + p0, p0, engine);
         if (rc != DCREG_OK) return rc;
     }
@@ -717,6 +755,17 @@ int dcreg_register_pairs_gicp(dcreg_ctx *ctx, int n_pairs, const float *src_xyz,
                               const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
     return register_pairs_run(ctx, n_pairs, src_xyz, src_offsets, tgt_xyz, tgt_offsets, stride_floats, R0, t0, detection, handling, cfg, slots, results,
                               Engine::gicp, target_normals, source_normals);
+}
+
+// The fourth engine's form (include/dcreg.h): the same body with a voxel map per target in place of an index and its normals - a build
+// batch is planned with what the voxel build allocates (dcreg_pairs_plan_voxels) and built by dcreg_pairs_voxels_build; in mode 1 the
+// sources' own normals are estimated once behind the load, in mode 0 source_normals is not read
+int dcreg_register_pairs_voxels(dcreg_ctx *ctx, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                                const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_voxel_map_params *target_voxels,
+                                const dcreg_normal_params *source_normals, const double *R0, const double *t0, int detection, int handling,
+                                const dcreg_config *cfg, int slots, dcreg_trial_result *results) {
+    return register_pairs_run(ctx, n_pairs, src_xyz, src_offsets, tgt_xyz, tgt_offsets, stride_floats, R0, t0, detection, handling, cfg, slots, results,
+                              Engine::voxels, nullptr, source_normals, target_voxels);
 }
 
 int dcreg_icp_run_montecarlo(dcreg_ctx *ctx, const double base_xyzrpy[6], uint64_t seed, int64_t first_trial, int64_t trial_stride,

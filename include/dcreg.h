@@ -235,7 +235,7 @@ int dcreg_linearize_batch(dcreg_ctx *, int n_poses, const double *R9, const doub
  * results of that slot (pinned-memory sequence numbers) and unpacks them.  While any slot is in flight (or a gated launch waits, below)
  * the calls that queue work, wait for the stream or replace buffers return DCREG_E_STATE at once: dcreg_set_target[_device],
  * dcreg_set_source[_device], dcreg_set_stream, dcreg_knn, dcreg_p2p_error, dcreg_reserve_warm_states, dcreg_reset_warm_state(-1),
- * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels, dcreg_register_pairs, dcreg_register_pairs_normals, dcreg_register_pairs_gicp, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
+ * dcreg_register_frames[_normals], dcreg_icp_run_trials[_normals], dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels, dcreg_register_pairs, dcreg_register_pairs_normals, dcreg_register_pairs_gicp, dcreg_register_pairs_voxels, dcreg_linearize_normals, dcreg_linearize_gicp, dcreg_target_normals_keep / _set / _drop, dcreg_source_normals_keep / _set / _get / _drop,
  * the launches, and dcreg_debug.h's dcreg_frames_load, dcreg_normals_reserve_slots (a pending launch slot of dcreg_normals_batch_begin counts as a slot in flight), dcreg_knn_timed, dcreg_kdtree_build, dcreg_team_pass_stamps and
  * dcreg_launch_stats_get with "count_searches" on; readers of host state (dcreg_index_info_get, dcreg_last_error, ...) stay allowed.  Two slots (0, 1) with their own buffers: keep
  * one batch on the device while the host solves the other (dcreg_icp_run_trials does).  R9 / t3 are copied by _begin. */
@@ -1146,11 +1146,11 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  * neighbour states, the window index or the map's kept normals: it may be interleaved with every other engine's calls without moving a
  * bit on either side.  DCREG_E_INVALID: null arguments, a non-finite pose, a parameterization other than SO3.  DCREG_E_STATE: no target,
  * no source, no kept voxels, in mode 1 no kept source normals, a linearisation in flight.  Waits for the stream.
- * The batched forms - many trials of the own source, many frames - are dcreg_icp_run_trials_voxels and dcreg_register_frames_voxels below.
- * Not provided: scan pairs through this engine (each target would need a voxel map of its own, built in batches, and a pairs plan that
- * skips the index build; the engine is also density-hungry on scan-sized targets: DESIGN.md sections 21 and 22), neighbour-voxel
- * correspondences (7 / 27 voxels per point), a voxel map that follows map updates, sharded / Euler forms, a caller-supplied voxel map,
- * the runner's YAML. */
+ * The batched forms - many trials of the own source, many frames, many scan pairs with a voxel map per target - are
+ * dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels and dcreg_register_pairs_voxels below (the engine is density-hungry on
+ * scan-sized targets: DESIGN.md sections 21 to 23).
+ * Not provided: neighbour-voxel correspondences (7 / 27 voxels per point), a voxel map that follows map updates, sharded / Euler forms,
+ * a caller-supplied voxel map, the runner's YAML. */
 typedef struct dcreg_voxel_map_params {
     double leaf;      /* voxel edge, metres (default 1.0) */
     double epsilon;   /* floor of the normalised eigenvalues (default 1e-3) */
@@ -1400,8 +1400,8 @@ int dcreg_icp_run_trials_gicp(dcreg_ctx *, int n_trials, const double *R0_9, con
  * DCREG_E_STATE, results untouched: no target, no kept voxels (dcreg_target_voxels_keep first; every change of the map's points drops
  * them), a linearisation in flight.  The context's own source and its kept normals, every warm and neighbour state of the other engines,
  * the window index, the map's kept normals and the kept voxels are left as they were (the frames form replaces the frames a previous
- * dcreg_register_frames* call left on the device, and their kept normals, as between the other engines).  Not provided: scan pairs
- * through this engine (see the voxel section above), the sharded / RCCL forms, the Euler form. */
+ * dcreg_register_frames* call left on the device, and their kept normals, as between the other engines).  Scan pairs, each against
+ * a voxel map of its own target: dcreg_register_pairs_voxels below.  Not provided: the sharded / RCCL forms, the Euler form. */
 int dcreg_register_frames_voxels(dcreg_ctx *, int n_frames, const float *xyz, const int64_t *frame_offsets, int64_t stride_floats,
                                  const dcreg_normal_params *frame_normals, const double *R0_9, const double *t0_3, int detection,
                                  int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
@@ -1452,6 +1452,40 @@ int dcreg_register_pairs_gicp(dcreg_ctx *, int n_pairs, const float *src_xyz, co
                               const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_normal_params *target_normals,
                               const dcreg_normal_params *source_normals, const double *R0_9, const double *t0_3, int detection,
                               int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
+
+/* dcreg_register_pairs for the fourth engine (dcreg_icp_run_voxels: rows against per-voxel Gaussians): the cheap stage with the wide
+ * basin for many candidates at once, each against its own submap - loop-closure and relocalisation candidates from the place search,
+ * whose starts may lie outside the 1-NN engines' search radius.  Arguments, offset rules, build batches under "pairs_max_bytes", slots,
+ * record fields and amortised time_ms are those of dcreg_register_pairs.  The engine needs no index on the target side: a build batch
+ * uploads and packs its targets and keeps ONE voxel map per target by the rule target_voxels, all maps of the batch in one pass (one
+ * sort - two where target and voxel bits exceed 64 -, a fixed number of launches and synchronises whatever the number of targets); no
+ * cell table, no adaptation pass and no normals pass runs, and a batch is counted with what this build allocates (dcreg_debug.h:
+ * dcreg_pairs_plan_voxels), "pair_max_table_entries" is not read.  Every iteration of a group of pairs is ONE batched launch
+ * (dcreg_debug.h: dcreg_pairs_voxels_batch_begin), each pose reading its own source and its own target's voxel map.
+ * results[p] is bitwise what a context with the same options gives for dcreg_set_target(target p, any radius) +
+ * dcreg_target_voxels_keep(target_voxels) + dcreg_set_source(source p) [+ dcreg_source_normals_keep(source_normals) in mode 1] +
+ * dcreg_icp_run_voxels(R0 p, t0 p): final_transform, iterations, converged, status, final_rmse, final_fitness, corr_num, H_upper and
+ * degenerate_mask; errors against cfg->gt_matrix.  cfg->search_radius is not read by this engine.
+ * "voxels_source_cov" is read once when the call starts; "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" at every launch, as in
+ * the frames form.  Mode 0: source_normals is not read and may be NULL, no normals pass runs.  Mode 1: source_normals is checked as
+ * dcreg_register_pairs_gicp checks it, and all sources' normals are estimated once per call in one batched pass; a source with fewer
+ * than k points has no normals and ends with status 1.
+ * An empty source or target: status 3, the other pairs run.  A target that keeps no voxel (every voxel below min_points or degenerate)
+ * also gives status 3 - the one departure from the serial sequence, where dcreg_icp_run_voxels refuses with DCREG_E_STATE.  n_pairs == 0
+ * does nothing, after the parameter checks.
+ * DCREG_E_INVALID, nothing runs, results untouched: the refusals of dcreg_register_pairs; those of dcreg_target_voxels_keep for
+ * target_voxels (a leaf that is not finite and > 0, epsilon outside [1e-6, 1], min_points < 2, a null block) and, in mode 1, those of
+ * dcreg_normals for source_normals, both checked before the n_pairs == 0 return; any target, in any build batch, that spans 2^21 or more
+ * voxels on an axis or has a voxel coordinate of magnitude 2^62 or more (the targets of later batches are checked on the host from their
+ * coordinate-wise bounds, the first batch's by its own build, before any pair runs).  DCREG_E_STATE: a linearisation or a batched launch
+ * in flight.
+ * The call needs no target on the context and leaves alone its target, kept voxels, kept normals, source, kept source normals, every
+ * warm and neighbour state, the loaded frames with their normals and the window index; it replaces the pairs' sources (and their kept
+ * normals) a previous dcreg_register_pairs* call left on the device and the voxel batch of a previous call of its own. */
+int dcreg_register_pairs_voxels(dcreg_ctx *, int n_pairs, const float *src_xyz, const int64_t *src_offsets, const float *tgt_xyz,
+                                const int64_t *tgt_offsets, int64_t stride_floats, const dcreg_voxel_map_params *target_voxels,
+                                const dcreg_normal_params *source_normals, const double *R0_9, const double *t0_3, int detection,
+                                int handling, const dcreg_config *, int slots, dcreg_trial_result *results);
 
 /* Initial pose of Monte-Carlo trial k (the reference has no RNG: its num_runs loop, icp_test_runner.cpp:339-349, repeats one
  * deterministic run; the seeded perturbation is this build's definition, shared by the runner and dcreg_amd/montecarlo.py):

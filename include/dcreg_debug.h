@@ -313,6 +313,40 @@ int dcreg_pairs_normals_batch_begin(dcreg_ctx *, int slot, int n_poses, const do
 int dcreg_pairs_gicp_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids,
                                  const int32_t *source_ids, const int32_t *target_ids, const dcreg_lin_params *);
 
+/* internal: the device seam of dcreg_register_pairs_voxels (engine.cpp), beside the two above; the pairs' sources are those of
+ * dcreg_pairs_sources_load (mode 1: with dcreg_pairs_sources_normals_keep / _set).
+ * dcreg_pairs_plan_voxels is dcreg_pairs_plan with a batch counted at what this form allocates - no cell table: per target point the
+ * upload, the packed point, the voxel pass's per-point scratch, the sort's key / value arrays and its temporary storage, and a bound for
+ * the per-voxel scratch and the kept members (context.hip pair_voxel_target_bytes has the formula); a batch never exceeds the budget it was
+ * planned with, and never splits a pair.
+ * dcreg_pairs_voxels_build uploads and packs the targets of one batch (host memory, offsets from 0) and keeps a voxel map for every one
+ * of them, all at once (voxel.hip pairs_voxels_build: one upload, one pack, one or two sorts, two scans, one reduction over the voxels of
+ * all targets, four synchronises, whatever the number of targets); it builds no grid.  Target t's member is bitwise what
+ * dcreg_set_target(target t, any radius) + dcreg_target_voxels_keep(params) keep; infos (may be NULL): one record per target, as
+ * dcreg_target_voxels_keep fills it.  A target that keeps no voxel (empty, or every voxel below min_points or degenerate) has no member.
+ * DCREG_E_INVALID, the batch a previous build left untouched: the parameter refusals of dcreg_target_voxels_keep, bad offsets, a
+ * non-finite coordinate, a voxel coordinate of magnitude 2^62 or more, a target that spans 2^21 or more voxels on an axis; DCREG_E_STATE: a
+ * linearisation in flight.  Every build replaces the batch; the index batch of dcreg_pairs_build and the context's own target, kept
+ * voxels, source and frames are not touched.  dcreg_pairs_voxels_kept: the kept voxels of one target of the batch (0: no member, or no
+ * such target); dcreg_pairs_voxels_get: that member in dcreg_target_voxels_get's order and layout.  dcreg_voxel_map_params_check: the
+ * parameter refusals of dcreg_target_voxels_keep on their own; dcreg_pairs_voxels_box_check: what a build refuses of a target with these
+ * coordinate-wise float bounds (floor((double)x / leaf) is monotonic in x: a cloud's voxel box is that of its bounds).
+ * dcreg_pairs_voxels_batch_begin is dcreg_voxels_batch_begin with pose i linearising pair source source_ids[i] against the member of
+ * target target_ids[i] of the batch (voxel_icp.hip k_vlin_pairs); its 31 sums are bitwise what dcreg_linearize_voxels returns on a context
+ * with that target's kept voxels and that source (a target without a member: all zero).  No state_ids; the two launch slots are those of
+ * dcreg_normals_batch_begin; results through dcreg_voxels_batch_end.  The refusals are dcreg_voxels_batch_begin's in its order, the state
+ * refusals being: no pair voxel batch built, no pair sources, in mode 1 no kept pair source normals; DCREG_E_INVALID also for null ids, a
+ * source id outside the load or naming an empty source, and a target id outside the batch. */
+int dcreg_pairs_plan_voxels(dcreg_ctx *, int n_pairs, const int64_t *tgt_offsets, int64_t stride_floats, int32_t *batch_end, int *n_batches);
+int dcreg_pairs_voxels_build(dcreg_ctx *, int n_targets, const float *xyz, const int64_t *tgt_offsets, int64_t stride_floats,
+                             const dcreg_voxel_map_params *, dcreg_voxel_map_info *infos /* per target, may be NULL */);
+int dcreg_pairs_voxels_get(dcreg_ctx *, int target, int64_t *coords, int32_t *count, float *mean, float *cov, int64_t capacity_voxels);
+int dcreg_pairs_voxels_kept(const dcreg_ctx *, int target);
+int dcreg_voxel_map_params_check(dcreg_ctx *, const dcreg_voxel_map_params *);
+int dcreg_pairs_voxels_box_check(dcreg_ctx *, const float mn[3], const float mx[3], double leaf, int target);
+int dcreg_pairs_voxels_batch_begin(dcreg_ctx *, int slot, int n_poses, const double *R9, const double *t3, const int32_t *source_ids,
+                                   const int32_t *target_ids, const dcreg_lin_params *);
+
 /* Checks the whole map's index after updates (dcreg_target_insert*, dcreg_target_crop): rebuilds the current grid (same origin, cell
  * edge, dims and x sub-cells) from scratch in scratch buffers from the raw points and counts the entries that differ, bitwise:
  * mismatches[0] sorted points (kPtsPad tail included), [1] cell table, [2] row words, [3] gap field, [4] owners.  All zero = the index is
