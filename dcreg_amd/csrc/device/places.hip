@@ -51,7 +51,9 @@ __device__ __forceinline__ bool finite3f(float x, float y, float z) {
     return fabsf(x) <= 3.4028235e38f && fabsf(y) <= 3.4028235e38f && fabsf(z) <= 3.4028235e38f;
 }
 
-// the bin of a finite point by the rules of include/dcreg.h (-1: outside the range gate) and the value it offers to it
+// the bin of a finite point by the rules of include/dcreg.h (-1: outside the range gate) and the value it offers to it.  Every operation
+// and its order are the header's: a folded constant (n_sectors / 2 pi, n_rings / max_range) or a gate on the root moves points that lie on
+// an edge into another bin (tests/places_edge_scenes.py)
 __device__ __forceinline__ int place_bin(const PlaceDev &P, float x, float y, float z, float &val) {
     const double dx = (double)x, dy = (double)y;
     const double r2 = dx * dx + dy * dy;

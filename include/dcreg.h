@@ -499,8 +499,17 @@ int dcreg_set_source_deskew_path_device(dcreg_ctx *, const float *d_xyz, int64_t
  *   - ring coordinate a = sqrt(rho2) * n_rings / max_range, ring = min(floor(a), n_rings - 1);
  *   - theta = atan2(y, x), plus 2 pi when negative; sector coordinate b = theta * n_sectors / (2 pi), sector = min(floor(b), n_sectors - 1);
  *   - a bin's value is the maximum over its points of (float)((double)z + z_offset); an empty bin holds 0;
- *   - a point whose a or b lies within 1e-9 of an integer may fall in either neighbouring bin (sqrt and atan2 differ between libraries in
- *     their last bits); every other point falls in the bin the formulas give.
+ *   - the formulas are evaluated in double as they are written, one rounding per operation, left to right: (sqrt(rho2) * n_rings) /
+ *     max_range and (theta * n_sectors) / 6.283185307179586, with that same double for the 2 pi of the sum.  A point on an edge falls in
+ *     the bin this evaluation gives, which need not be the mathematical one: with 60 sectors (0, 4) has b = 14.999999999999998 and
+ *     lies in sector 14, not 15; (4, -1e-30) has theta + 2 pi == 2 pi and the last sector only through the clamp.  rho2 == min_range^2
+ *     is used, rho2 == max_range^2 is not; -0.0 is not negative, so theta = -0.0 (y = -0.0, x > 0) lies in sector 0;
+ *   - this fixes the bin wherever theta is fixed: on the axes, where atan2 is +-0, +-pi/2 or +-pi rounded to double (C Annex F, the
+ *     origin included: theta = 0 for x = +0, pi for x = -0); on the diagonals |x| == |y|, where it is +-pi/4 or +-3 pi/4 rounded to
+ *     double; and beside the +x axis, where |theta| is so small that 2 pi absorbs it.  sqrt is correctly rounded, so the ring of
+ *     every point is fixed (rho2 a perfect square reaches a ring edge exactly);
+ *   - elsewhere a point whose b lies within 1e-9 of an integer may fall in either neighbouring sector (atan2 differs between libraries
+ *     in its last bits); every other point falls in the bin the formulas give.
  * The maximum is taken with integer atomics on order-preserving keys, so a descriptor does not depend on the order of the points, on the
  * launch configuration, or on the other clouds of the call.
  * Distance of a query descriptor q and an entry c at shift n in [0, n_sectors), everything in double: over the columns j for which both

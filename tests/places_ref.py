@@ -108,6 +108,37 @@ def distance_table(qs, db, block=256):
     return out
 
 
+def small_table(qs, db):
+    """D[query, entry, n] of distance_table for grids of a few bins and databases of 10^5 entries and more: the rule written out per
+    (query, n, j) and evaluated over all entries at once (test_places_edge_scenes.py holds it to `distances`).  The terms of a shift are
+    added in the order of the query's columns, as `distances` adds them"""
+    qs = np.asarray(qs, np.float32).astype(np.float64)
+    db = np.asarray(db, np.float32).astype(np.float64)
+    nq, R, S = qs.shape
+    ne = db.shape[0]
+    out = np.ones((nq, ne, S))
+    if nq == 0 or ne == 0:
+        return out
+    qn = np.sqrt((qs * qs).sum(1))
+    cn = np.sqrt((db * db).sum(1))
+    for qi in range(nq):
+        for n in range(S):
+            total, m = np.zeros(ne), np.zeros(ne, np.int64)
+            for j in range(S):
+                if not qn[qi, j] > 0.0:
+                    continue
+                l = (j + n) % S
+                ok = cn[:, l] > 0.0
+                dot = np.zeros(ne)
+                for r in range(R):
+                    dot += qs[qi, r, j] * db[:, r, l]
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    total += np.where(ok, 1.0 - dot / (qn[qi, j] * cn[:, l]), 0.0)
+                m += ok
+            out[qi, :, n] = np.where(m > 0, total / np.maximum(m, 1), 1.0)
+    return out
+
+
 def search_table(D, first, last, k):
     """the search on a distance table D[query, entry, n] -> (idx [nq, k] int32, shift [nq, k] int32, dist [nq, k] float64)"""
     nq = D.shape[0]
