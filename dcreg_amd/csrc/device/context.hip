@@ -276,11 +276,7 @@ static double roi_pad_for(const dcreg_ctx *c, double search_radius) {
     return std::max(search_radius, c->radius_hint) * (1.0 + c->opt_cert_margin) * 1.001 + 1e-3;
 }
 // R (9) and t (3) of n poses are all finite numbers
-static bool poses_finite(int n, const double *R9, const double *t3) {
-    for (int64_t k = 0; k < 9 * (int64_t)n; ++k) if (!std::isfinite(R9[k])) return false;
-    for (int64_t k = 0; k < 3 * (int64_t)n; ++k) if (!std::isfinite(t3[k])) return false;
-    return true;
-}
+static bool poses_finite(int n, const double *R9, const double *t3) { return finite_n(R9, 9 * (int64_t)n) && finite_n(t3, 3 * (int64_t)n); }
 
 // A single-pose linearisation at (R, t) with this search radius is about to be queued: make the index it should search the active one -
 // the window if the map wants one (building it around the pose when there is none that covers it), the whole map otherwise.

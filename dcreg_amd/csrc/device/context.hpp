@@ -494,8 +494,8 @@ struct dcreg_ctx {
     // the third engine (gicp.hip: dcreg_linearize_gicp; normals.hip: dcreg_source_normals_keep / _set / _get / _drop).  src_normals: float4
     // {nx, ny, nz, curvature} per SOURCE point in the context's curve order - lane i of k_glin reads it beside d_src[i]; dropped by every
     // call that replaces the source's points (context.hip source_commit), left alone by the batched calls.  The warm words are nicp.warm:
-    // both 1-NN engines look for the same nearest point, and so are nicp's block rows, result row and dump block (normal_icp.hip one_nn_run: the
-    // two engines' launches never overlap).  tmp: the original-order form of a get.
+    // both 1-NN engines look for the same nearest point, and so are nicp's block rows, result row and dump block (normal_icp.hip rows_run: the
+    // engines' single-pose launches never overlap).  tmp: the original-order form of a get.
     // The batched form (k_glin_batch: dcreg_gicp_batch_begin / _end) has no buffers of its own: it runs in nicp's launch slots and warm
     // slots (normal_icp.hip one_nn_batch_begin) and reads a frame's normals from FrameSet::normals
     struct GicpBufs {
@@ -694,7 +694,22 @@ int launch_linearize(dcreg_ctx *c, int n_poses, const double *R9, const double *
                      dcreg_lin_out *outs, dcreg_lin_debug *dbg_host);
 void kdtree_free(void *kd);      // kdtree.hip (the comparator index of dcreg_debug.h)
 int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_radius);   // context.hip: the index a single-pose linearisation at this pose searches becomes the active one
-// normal_icp.hip: what the single-pose 1-NN linearisations (dcreg_linearize_normals, dcreg_linearize_gicp) share.  one_nn_check: every refusal
+// ---- normal_icp.hip: the host seam of the engines that leave block rows for k_finalize (the second, third and fourth: dcreg_linearize_normals,
+// _gicp and _voxels and their batched forms).  The rows_* functions serve all three; the one_nn_* functions are about the 1-NN search and
+// serve the second and third only - the fourth searches nothing.
+// n finite numbers (a pose's R and t, many poses' R9 and t3, ...)
+inline bool finite_n(const double *v, int64_t n) {
+    for (int64_t k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
+    return true;
+}
+// rows_run: the back half of a single-pose call, plain or debug, behind the engine's refusals (all three engines) - nicp's block rows and
+// result row sized for the context's source, the dump block cut into its arrays, `launch` (it queues the engine's kernel: nb blocks that
+// leave their rows at partials), the copies of the dump arrays that were asked for, k_finalize, the row copy, the wait and the result.
+// fields: the debug form's arrays in the order they are cut from the dump block (8-byte ones first): the caller's array (null: not asked
+// for), its bytes per point, and the kernel argument's pointer that receives the device array; n_fields == 0: the plain form
+struct DumpField { void *host; size_t bytes; void *dev; };
+int rows_run(dcreg_ctx *c, dcreg_lin_out *out, const DumpField *fields, int n_fields, const std::function<void(double *partials, uint32_t nb)> &launch);
+// What the single-pose 1-NN linearisations (dcreg_linearize_normals, dcreg_linearize_gicp) share in front of it.  one_nn_check: every refusal
 // of both, in the header's order, up to "no kept normals" (`what` names the linearisation in the messages).  one_nn_bound: the gate R^2, the
 // cold search bound (the smallest float >= R^2) and the rings that cover it.  The warm words (NormalIcpBufs::warm): _reserve sizes them for
 // the source (a new array holds nothing), _take returns what a plain launch starts from (null: cold) and marks them invalid until _done
@@ -703,30 +718,40 @@ struct OneNnBound { double radius_sq; float bound_f; int max_ring; };
 int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, const dcreg_lin_out *out, const char *what);
 OneNnBound one_nn_bound(const GridDev &g, double search_radius);
 int one_nn_warm_reserve(dcreg_ctx *c);
-// one_nn_run: the single-pose call of either engine, plain or debug - one_nn_check, the engine's own refusal (`extra`, with fs == null),
-// roi_ensure, the buffers, then `launch` queues the engine's kernel for the filled record, the requested dump arrays come back, k_finalize,
-// the wait, the warm bookkeeping and the result.  fields: the debug form's arrays in the order they are cut from the dump block (8-byte ones
-// first): the caller's array (null: not asked for), its bytes per point, and the kernel argument's pointer that receives the device array
+// one_nn_run: the single-pose call of either 1-NN engine, plain or debug - what belongs to a search against the index: one_nn_check, the
+// engine's own refusal (`extra`, with fs == null), roi_ensure, the warm words and the search bound; then rows_run, with `launch` queueing
+// the engine's kernel for the filled record, and the warm bookkeeping.  fields / n_fields: rows_run's (read with dump only)
 struct OneNnLaunch {
     PoseArg P; OneNnBound bound;                // the pose, the search bound on the active index
     bool dump;                                  // the debug form: the kernel's dump instantiation, no warm words
     const uint32_t *warm_in; uint32_t *warm_out;
     double *partials; uint32_t nb;
 };
-struct OneNnDumpField { void *host; size_t bytes; void *dev; };
 int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
                int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), const std::function<void(const OneNnLaunch &)> &launch, bool dump,
-               const OneNnDumpField *fields, int n_fields);
-// ... and what their batched forms share (dcreg_normals_batch_begin / _end, dcreg_gicp_batch_begin / _end): the two launch slots and the warm
-// slots of NormalIcpBufs.  one_nn_batch_begin makes every refusal of include/dcreg_debug.h before anything is queued (`extra`: the engine's
-// own state refusals, after "no kept normals"; fs = the set the frame_ids name, null without them), uploads the poses and slices, has
-// `launch` queue the engine's kernel for the filled record, then queues k_finalize, the result copy and the slot's event; one_nn_batch_end
-// waits for that event.  fs: the source set frame_ids index (c->frames, or c->pair_src; null with frame_ids == null: the own source).
+               const DumpField *fields, int n_fields);
+// ... and the batched forms: the two launch slots of NormalIcpBufs, which all three engines share (a pending slot of one refuses the others).
+// rows_batch_check: the front of every batched begin's refusal ladder (include/dcreg_debug.h), in this order - null context, bad slot, null
+// arguments (ids_given: the ids a launch cannot do without are there) or n_poses < 1, more than 65535 poses, a waiting gate, a pending
+// slot of the first engine, this slot pending, the parameterization (`what` names the linearisation in the message), with `search` the
+// search radius, a non-finite pose.  The engine's state refusals follow it.
+int rows_batch_check(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *p, bool ids_given, const char *what,
+                     bool search);
+// rows_batch_clouds: the clouds of a launch and n_max, the points of the largest.  fs == null: the context's own source ("no source").
+// Else pose i's cloud is ids[i] of fs (c->frames or c->pair_src): "no frames" / "no pair sources" for an empty set, then pose by pose an
+// id outside the set or naming an empty cloud ("<noun> %d is not loaded or empty") and whatever pose_check(i) refuses (may be empty: the
+// voxel pairs launch checks pose i's target there, after its source and before pose i + 1's)
+int rows_batch_clouds(dcreg_ctx *c, const dcreg_ctx::FrameSet *fs, int n_poses, const int32_t *ids, const char *noun,
+                      const std::function<int(int)> &pose_check, int64_t &n_max);
+// one_nn_batch_begin (dcreg_normals_batch_begin, dcreg_gicp_batch_begin and their pairs forms) makes every refusal of the header before
+// anything is queued - rows_batch_check, the state refusals, rows_batch_clouds, `extra` (the engine's own state refusals, after "no kept
+// normals"), the warm slots - and queues through rows_batch_queue with the index, the kept normals, the bound and the warm slots filled in.
+// fs: the source set frame_ids index (c->frames, or c->pair_src; null with frame_ids == null: the own source).
 // target_ids (with fs == &c->pair_src only): pose i searches target target_ids[i] of the pairs' build batch and reads that target's kept
 // normals (OneNnGrid) instead of the map and its kept normals; the state refusals are then "no pair batch built" and "no kept pair normals"
 struct OneNnBatch {
     const float4 *src; uint32_t n_src;          // the set's points (slices != null) or the own source
-    const float4 *src_normals;                  // ... and its kept normals at the same positions (the third engine)
+    const float4 *src_normals;                  // ... and its kept normals at the same positions (the third and fourth engine)
     GridDev g;                                  // the whole map's index (grids == null)
     const float4 *normals;                      // the map's kept normals, or the pair batch's
     const OneNnGrid *grids; const uint32_t *grid_ids;   // device; pairs: the batch's target records and every pose's target
@@ -739,18 +764,19 @@ struct OneNnBatch {
 int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
                        const int32_t *frame_ids, const int32_t *target_ids, const dcreg_lin_params *p,
                        int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), void (*launch)(dcreg_ctx *, const OneNnBatch &), const char *kernel_name);
-// one_nn_batch_queue: the slot plumbing behind those refusals, which the fourth engine's batched launch (voxel_icp.hip
-// dcreg_voxels_batch_begin) shares as it is - the slot's buffers sized for the largest cloud (n_max: the launch's largest), the pinned pose
+// rows_batch_queue: the slot plumbing behind the refusals, for all three engines (the fourth: voxel_icp.hip vlin_batch_begin,
+// vlin_pairs_batch_begin) - the slot's buffers sized for the largest cloud (n_max: the launch's largest), the pinned pose
 // and slice block and its upload, `launch` (it completes the record - the fields of the engine's own target stay zero until then - and
 // queues the engine's kernel), k_finalize, the result copy, the slot's event and the `failed` path.  state_ids == null: no warm slot is
-// read or written.  The caller has made every refusal, the slot's `pending` included
-int one_nn_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
-                       const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
-                       const char *kernel_name);
-// the warm slots of the batched form, sized for the own source, the loaded frames or the pairs' sources (dcreg_normals_reserve_slots,
+// read or written.  The caller has made every refusal, the slot's `pending` included.  rows_batch_end waits for the slot's event and
+// turns its rows into results (dcreg_normals_batch_end, dcreg_gicp_batch_end, dcreg_voxels_batch_end)
+int rows_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                     const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
+                     const char *kernel_name);
+int rows_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs);
+// the warm slots of the batched 1-NN forms, sized for the own source, the loaded frames or the pairs' sources (dcreg_normals_reserve_slots,
 // dcreg_pairs_normals_reserve_slots)
 int one_nn_reserve_slots(dcreg_ctx *c, int64_t n_slots, dcreg_ctx::NormalIcpBufs::SlotsFor what);
-int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs);
 const uint32_t *one_nn_warm_take(dcreg_ctx *c);
 void one_nn_warm_done(dcreg_ctx *c);
 // a result row of kSlots doubles (block_slot_sum's slots, summed) as the C-ABI's record

@@ -323,11 +323,6 @@ int deskew_prepare(dcreg_ctx *c, int n_clouds, const int64_t *off, int64_t strid
     return DCREG_OK;
 }
 
-static bool finite_n(const double *v, int n) {
-    bool ok = true;
-    for (int k = 0; k < n; ++k) ok &= std::isfinite(v[k]);
-    return ok;
-}
 // C = A^T B of two rotations; o = A^T v
 static void mat3tmul(const double *A, const double *B, double *C) {
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C[i * 3 + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];

@@ -1,5 +1,6 @@
 // The third engine's linearisation on the device (include/dcreg.h: dcreg_linearize_gicp): plane-to-plane (Generalized-ICP) rows from the
 // map's kept normals and the source's own, with the rule of the header, bitwise the numpy reference of tests/gicp_ref.py.
+//   glin_block<DUMP>  what every block of this engine does, in one place; k_glin and k_glin_batch are block-uniform prologues in front of it
 //   k_glin<DUMP>   one lane per source point, in the context's curve order: glin_point (gicp.hpp) - transform, k_nlin's 1-NN search from
 //                  the warm bound, one gather of the nearest point and one of its float4 normal, the coalesced float4 load of the point's
 //                  own normal, the covariance of the pair from the two normals, its Cholesky factor and W = L^-1; then THREE rows per
@@ -8,9 +9,10 @@
 //   k_glin_batch   the same for many poses in ONE launch (dcreg_gicp_batch_begin: the engine of dcreg_register_frames_gicp): block (x, pose)
 //                  runs glin_point on block x of the pose's own source slice and its kept normals, and leaves its row at partials[pose][x]
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_nlin
-// The host side is the second engine's (normal_icp.hip): one_nn_run for the single pose and one_nn_batch_begin / _end for many, with this
-// engine's refusal (gicp_refuse), its launch arguments (glin_args), its kernels and the fields of its dump; the block rows, the result
-// row and the dump block are nicp's.
+// The host side is the seam of normal_icp.hip (context.hpp): one_nn_run for the single pose and one_nn_batch_begin / rows_batch_end for
+// many - the 1-NN layer, shared with the second engine, on top of the rows_* layer all three row engines share - with this engine's
+// refusal (gicp_refuse), its launch arguments (glin_args), its kernels and the fields of its dump; the block rows, the result row and
+// the dump block are nicp's.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  The search reads and writes the warm words of
 // k_nlin (context.hpp NormalIcpBufs::warm): both engines look for the same nearest point, and the word decides how fast, never which.
 #include <cmath>
@@ -29,13 +31,13 @@ struct GlinDump {
     int32_t *nn_idx; float *nn_d2; uint8_t *flag; double *normal_map, *normal_src, *w, *r, *row;
 };
 
-// warm_in / warm_out / partials: as k_nlin's.  src_normals: float4 per source point in the order of src.  Slot 29 counts the effective
+// The body of both kernels: block blockIdx.x of the n_src points at src against the index g and its kept normals at pose P; the block row
+// goes to `out`.  warm_in / warm_out: as k_nlin's.  src_normals: float4 per source point in the order of src.  Slot 29 counts the effective
 // POINTS (not rows), slot 30 the points inside the radius.
 template <bool DUMP>
-static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
-                                                                     const float4 *__restrict__ normals, const float4 *__restrict__ src_normals,
-                                                                     PoseArg P, GlinArgs a, const uint32_t *warm_in, uint32_t *warm_out,
-                                                                     double *__restrict__ partials, GlinDump d) {
+__device__ __forceinline__ void glin_block(const float4 *__restrict__ src, uint32_t n_src, const GridDev &g, const float4 *__restrict__ normals,
+                                           const float4 *__restrict__ src_normals, const PoseArg &P, const GlinArgs &a, const uint32_t *warm_in,
+                                           uint32_t *warm_out, double *__restrict__ out, const GlinDump &d) {
     __shared__ RunList runs[kLinBlock / kWave];
     __shared__ double gm[kLinBlock / kWave][64];
     __shared__ double cnt[kLinBlock / kWave][2];
@@ -64,7 +66,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
             }
         }
     }
-    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, runs[wave].stage, gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, runs[wave].stage, gm, cnt, out, [&](int k, const double (&row)[8]) {
         if constexpr (DUMP) {
             if (i < n_src) {
                 if (d.r) d.r[3 * oi + k] = row[7];
@@ -77,12 +79,19 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4
     });
 }
 
+template <bool DUMP>
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
+                                                                     const float4 *__restrict__ normals, const float4 *__restrict__ src_normals,
+                                                                     PoseArg P, GlinArgs a, const uint32_t *warm_in, uint32_t *warm_out,
+                                                                     double *__restrict__ partials, GlinDump d) {
+    glin_block<DUMP>(src, n_src, g, normals, src_normals, P, a, warm_in, warm_out, partials + (size_t)blockIdx.x * kSlots, d);
+}
+
 // Many poses in one launch: k_glin as k_nlin_batch is k_nlin (normal_icp.hip).  Block (x, pose): pose = poses[blockIdx.y], read through a
-// block-uniform index; its cloud is slices[pose] = {first point, points} of src AND of src_normals (a frame of the loaded frames and that
-// frame's kept normals: the same positions; a block past the end of a short frame's slice exits before it touches anything) or, slices ==
-// null, the n_src points at src (the context's own source and its kept source normals).  The warm words are k_nlin_batch's slots.  The body
-// is glin_point and glin_block_rows, unchanged; the block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the
-// rows and additions of the pose's single launch.
+// block-uniform index; its cloud is slices[pose] of src AND of src_normals (a frame of the loaded frames and that frame's kept normals:
+// the same positions; normal_icp.hpp batch_slice) or, slices == null, the n_src points at src (the context's own source and its kept
+// source normals).  The warm words are k_nlin_batch's slots: the pose's own array, read unless it is fresh.  The block row goes to
+// partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the rows and additions of the pose's single launch.
 // GRIDS (scan pairs: dcreg_pairs_gicp_batch_begin): as k_nlin_batch<GRIDS> - grids[grid_ids[pose]], read through a block-uniform index, holds
 // the pose's own target: its grid, its rings and where its kept normals start in `normals`; src and src_normals are the pairs' sources.
 template <bool GRIDS>
@@ -92,34 +101,20 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_glin_batch(const 
                                                                            GlinArgs a, uint32_t *warm, uint32_t warm_stride,
                                                                            double *__restrict__ partials, uint32_t n_blocks_x,
                                                                            const OneNnGrid *__restrict__ grids, const uint32_t *__restrict__ grid_ids) {
-    __shared__ RunList runs[kLinBlock / kWave];
-    __shared__ double gm[kLinBlock / kWave][64];
-    __shared__ double cnt[kLinBlock / kWave][2];
     const uint32_t pose_id = blockIdx.y;
     if constexpr (GRIDS) {                           // (uniform per block)
         const OneNnGrid &og = grids[grid_ids[pose_id]];
         g = og.g; a.max_ring = og.max_ring; normals += og.normals_first;
     }
-    if (slices) {                                    // (uniform per block: before anything is touched)
-        const uint2 sl = slices[pose_id];
-        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
-        src += sl.x; src_normals += sl.x; n_src = sl.y;
+    if (slices) {
+        uint32_t first;
+        if (!batch_slice(slices, first, n_src)) return;
+        src += first; src_normals += first;
     }
     const PoseArg &P = poses[pose_id];
-    const int wave = threadIdx.x >> 6;
-    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
-    uint8_t flag = 0;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    GlinPoint o;
-    if (i < n_src) {
-        uint32_t *w = P.state != kNoIdx ? warm + (size_t)P.state * warm_stride + i : nullptr;
-        const float4 s4 = src[i];
-        sx = s4.x; sy = s4.y; sz = s4.z;
-        flag = glin_point(g, runs[wave], normals, P, a, s4, src_normals + i, (w && P.fresh == 0u) ? *w : kNoIdx, o);
-        if (w) *w = o.pos;
-    }
-    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, runs[wave].stage, gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
-                    [](int, const double (&)[8]) {});
+    uint32_t *w = P.state != kNoIdx ? warm + (size_t)P.state * warm_stride : nullptr;
+    glin_block<false>(src, n_src, g, normals, src_normals, P, a, P.fresh == 0u ? w : nullptr, w,
+                      partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots, GlinDump{});
 }
 
 // the launch's arguments for a search within the bound b ("gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at every call)
@@ -143,7 +138,7 @@ int gicp_refuse(dcreg_ctx *c, const dcreg_ctx::FrameSet *fs) {
 int glin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_glin_debug *dbg) {
     GlinDump d{};
     const dcreg_glin_debug none{}, &h = dbg ? *dbg : none;
-    const OneNnDumpField fields[] = {{h.normal_map, 24, &d.normal_map}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
+    const DumpField fields[] = {{h.normal_map, 24, &d.normal_map}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
                                      {h.row, 192, &d.row}, {h.nn_idx, 4, &d.nn_idx}, {h.nn_d2, 4, &d.nn_d2}, {h.flag, 1, &d.flag}};
     return one_nn_run(c, R, t, p, out, "GICP", gicp_refuse, [&](const OneNnLaunch &L) {
         hipLaunchKernelGGL(L.dump ? k_glin<true> : k_glin<false>, dim3(L.nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)c->n_src,
@@ -178,7 +173,7 @@ int dcreg_pairs_gicp_batch_begin(dcreg_ctx *c, int slot, int n_poses, const doub
     return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->pair_src : nullptr, source_ids, target_ids, p, gicp_refuse, glin_batch_launch,
                               "the k_glin_batch launch");
 }
-int dcreg_gicp_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
+int dcreg_gicp_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return rows_batch_end(c, slot, outs); }
 int dcreg_linearize_gicp_debug(dcreg_ctx *c, const double R[9], const double t[3], const dcreg_lin_params *p, dcreg_lin_out *out,
                                dcreg_glin_debug *dbg) {
     if (c && !dbg) { c->fail("null dump"); return DCREG_E_INVALID; }

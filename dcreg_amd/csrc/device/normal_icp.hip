@@ -9,10 +9,16 @@
 //                  source - with the pose read from a device array, and leaves its row at partials[pose][x]; <GRIDS>: against the pose's
 //                  own target and that target's kept normals (dcreg_pairs_normals_batch_begin: dcreg_register_pairs_normals)
 //   k_finalize     (kernels.hpp) the block rows in chunk order, the additions of the first engine's batched launches
-// Both kernels end in nlin_block_rows (the wave's rows to LDS, block_slot_sum of kernels.hpp, the block row).  On the host, one_nn_run is
-// the single-pose call of this engine AND of gicp.hip's (refusals, buffers, the dump block cut from a table of fields, launch, k_finalize,
-// warm bookkeeping): an engine brings its extra refusal, its kernel launch and its dump fields.  one_nn_batch_begin / _end are the same
-// seam for the batched form.
+// Both kernels end in nlin_block_rows (the wave's rows to LDS, block_slot_sum of kernels.hpp, the block row); the batched kernels of all
+// three engines find their block's cloud with batch_slice (normal_icp.hpp).
+// This file also holds the host seam of the three engines that leave block rows (declared in context.hpp), in two layers:
+//   rows_*     for every such engine, the fourth (voxel_icp.hip) included: rows_run - the back half of a single-pose call: buffers, the dump
+//              block cut from a table of fields, launch, k_finalize, wait; rows_batch_check - the front of every batched begin's refusal
+//              ladder; rows_batch_clouds - the frame / pair-source ids resolved to the launch's largest cloud; rows_batch_queue / _end -
+//              the launch slots' plumbing
+//   one_nn_*   what belongs to the 1-NN search, for this engine AND gicp.hip's: one_nn_run - one_nn_check, roi_ensure, the warm words and
+//              the search bound in front of rows_run; one_nn_batch_begin - the state refusals, the targets and the warm slots between
+//              rows_batch_check and rows_batch_queue.  An engine brings its extra refusal, its kernel launch and its dump fields.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.  A point's row depends on the clouds, the
 // normals and the pose only; the warm position decides how fast the neighbour is found, never which.
 #include <cmath>
@@ -104,10 +110,10 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin_batch(const 
         const OneNnGrid &og = grids[grid_ids[pose_id]];
         g = og.g; a.max_ring = og.max_ring; normals += og.normals_first;
     }
-    if (slices) {                                    // (uniform per block: before anything is touched)
-        const uint2 sl = slices[pose_id];
-        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
-        src += sl.x; n_src = sl.y;
+    if (slices) {
+        uint32_t first;
+        if (!batch_slice(slices, first, n_src)) return;
+        src += first;
     }
     const PoseArg &P = poses[pose_id];
     const int wave = threadIdx.x >> 6;
@@ -126,11 +132,6 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_nlin_batch(const 
     nlin_block_rows(row, flag, runs[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots);
 }
 
-bool finite_n(const double *v, int n) {
-    for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
 // the launch's arguments for a search within the bound b ("robust_kernel" and "robust_scale" are read at every call)
 NlinArgs nlin_args(const dcreg_ctx *c, const OneNnBound &b, const dcreg_lin_params *p) {
     NlinArgs a;
@@ -143,7 +144,7 @@ NlinArgs nlin_args(const dcreg_ctx *c, const OneNnBound &b, const dcreg_lin_para
 int nlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, dcreg_nlin_debug *dbg) {
     NlinDump d{};
     const dcreg_nlin_debug none{}, &h = dbg ? *dbg : none;
-    const OneNnDumpField fields[] = {{h.normal, 24, &d.normal}, {h.r, 8, &d.r}, {h.s, 8, &d.s}, {h.row, 64, &d.row},
+    const DumpField fields[] = {{h.normal, 24, &d.normal}, {h.r, 8, &d.r}, {h.s, 8, &d.s}, {h.row, 64, &d.row},
                                      {h.nn_idx, 4, &d.nn_idx}, {h.nn_d2, 4, &d.nn_d2}, {h.flag, 1, &d.flag}};
     return one_nn_run(c, R, t, p, out, "normal", nullptr, [&](const OneNnLaunch &L) {
         const GridDev &g = c->map.grid;
@@ -164,8 +165,44 @@ void nlin_batch_launch(dcreg_ctx *c, const OneNnBatch &L) {
 // ---- the batched form (context.hpp NormalIcpBufs::BatchSlot), shared with gicp.hip.  begin: every refusal before anything is queued or
 // changed, then the pose upload, the engine's batched kernel (`launch`: k_nlin_batch, k_glin_batch), k_finalize and the copy of the result
 // rows to pinned memory on the context's stream, and the slot's event behind them; end waits for that event - never for what the other
-// slot queued behind it.  The two launch slots serve both 1-NN engines: a pending slot of either refuses the other.
+// slot queued behind it.  The two launch slots serve the second, third and fourth engine: a pending slot of one refuses the others.
 using BatchSlot = dcreg_ctx::NormalIcpBufs::BatchSlot;
+
+// the front of every batched begin's refusals, in the order of include/dcreg_debug.h (context.hpp)
+int rows_batch_check(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const dcreg_lin_params *p, bool ids_given, const char *what,
+                     bool search) {
+    if (!c) return DCREG_E_INVALID;
+    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
+    if (!R9 || !t3 || !p || !ids_given || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
+    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
+    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
+    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
+    if (c->nicp.batch[slot].pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
+    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the %s linearisation has the SO(3) row only (parameterization %d)", what, p->parameterization); return DCREG_E_INVALID; }
+    if (search && !(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
+    if (!finite_n(R9, 9 * (int64_t)n_poses) || !finite_n(t3, 3 * (int64_t)n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+// the clouds of a batched launch and the points of the largest (context.hpp)
+int rows_batch_clouds(dcreg_ctx *c, const dcreg_ctx::FrameSet *fs, int n_poses, const int32_t *ids, const char *noun,
+                      const std::function<int(int)> &pose_check, int64_t &n_max) {
+    n_max = c->n_src;
+    if (!fs) {
+        if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+        return DCREG_OK;
+    }
+    const std::vector<uint2> &slice = fs->slice;
+    if (slice.empty()) { c->fail(fs == &c->pair_src ? "no pair sources: dcreg_pairs_sources_load first" : "no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
+    n_max = 0;
+    for (int i = 0; i < n_poses; ++i) {
+        const int32_t f = ids[i];
+        if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("%s %d is not loaded or empty", noun, f); return DCREG_E_INVALID; }
+        if (pose_check) if (int rc = pose_check(i)) return rc;
+        n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
+    }
+    return DCREG_OK;
+}
 
 int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
                        const int32_t *frame_ids, const int32_t *target_ids, const dcreg_lin_params *p,
@@ -177,16 +214,7 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     const bool pairs = fs == &c->pair_src;
     if (pairs != (target_ids != nullptr)) { c->fail("pair launches name a source and a target for every pose"); return DCREG_E_INVALID; }
     const SlotsFor slots_for = pairs ? SlotsFor::pairs : fs ? SlotsFor::frames : SlotsFor::source;
-    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
-    if (!R9 || !t3 || !p || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
-    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
-    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
-    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
-    BatchSlot &S = B.batch[slot];
-    if (S.pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
-    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the normal linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
-    if (!(std::isfinite(p->search_radius) && p->search_radius > 0.0)) { c->fail("search_radius is %g: finite and > 0 expected", p->search_radius); return DCREG_E_INVALID; }
-    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    if (int rc = rows_batch_check(c, slot, n_poses, R9, t3, p, true, "normal", true)) return rc;   // ("normal" for the third engine too)
     const dcreg_ctx::PairSet &ps = c->pairs;
     if (pairs) {
         if (ps.n <= 0) { c->fail("no pair batch built: dcreg_pairs_build first"); return DCREG_E_STATE; }
@@ -200,18 +228,8 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
         if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
         if (!B.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
     }
-    static const std::vector<uint2> no_slices;
-    const std::vector<uint2> &slice = fs ? fs->slice : no_slices;
-    int64_t n_max = c->n_src;                         // points of the launch's largest cloud
-    if (frame_ids) {
-        if (slice.empty()) { c->fail(pairs ? "no pair sources: dcreg_pairs_sources_load first" : "no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
-        n_max = 0;
-        for (int i = 0; i < n_poses; ++i) {
-            const int32_t f = frame_ids[i];
-            if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
-            n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
-        }
-    } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    int64_t n_max;                                    // (every target above before any source: "frame %d" names a pair source too)
+    if (int rc = rows_batch_clouds(c, fs, n_poses, frame_ids, "frame", nullptr, n_max)) return rc;
     if (extra) if (int rc = extra(c, fs)) return rc;
     if (state_ids) {
         std::vector<uint8_t> seen((size_t)std::max<int64_t>(B.n_slots, 1), 0);
@@ -228,7 +246,7 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     }
     // the whole map's index, wherever it lives (context.hpp roi_store): the window index stays as it is, active or not
     const dcreg_ctx::IndexSet &whole = c->roi_active ? c->roi_store : c->map;
-    return one_nn_batch_queue(c, slot, n_poses, R9, t3, state_ids, fs, frame_ids, target_ids, n_max, [&](OneNnBatch &L) {
+    return rows_batch_queue(c, slot, n_poses, R9, t3, state_ids, fs, frame_ids, target_ids, n_max, [&](OneNnBatch &L) {
         L.g = pairs ? GridDev{} : whole.grid; L.normals = pairs ? ps.normals.data() : B.normals.data();
         L.grids = pairs ? ps.d_nn_grids.data() : nullptr;
         GridDev bound_grid = whole.grid;
@@ -244,9 +262,9 @@ int one_nn_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
 // pinned pose and slice block and its upload, the engine's kernel (`launch` completes the record and queues it), k_finalize, the result copy
 // and the slot's event.  n_max: the points of the launch's largest cloud.  A failure once something may be queued marks the launch's warm
 // slots empty.
-int one_nn_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
-                       const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
-                       const char *kernel_name) {
+int rows_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *state_ids, dcreg_ctx::FrameSet *fs,
+                     const int32_t *frame_ids, const int32_t *target_ids, int64_t n_max, const std::function<void(OneNnBatch &)> &launch,
+                     const char *kernel_name) {
     dcreg_ctx::NormalIcpBufs &B = c->nicp;
     BatchSlot &S = B.batch[slot];
     const bool pairs = target_ids != nullptr;
@@ -316,7 +334,7 @@ int one_nn_batch_queue(dcreg_ctx *c, int slot, int n_poses, const double *R9, co
     return DCREG_OK;
 }
 
-int one_nn_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
+int rows_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) {
     if (!c) return DCREG_E_INVALID;
     if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
     BatchSlot &S = c->nicp.batch[slot];
@@ -346,49 +364,57 @@ int one_nn_check(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin
     if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
     return DCREG_OK;
 }
-// The single-pose runner of both 1-NN engines (context.hpp).  The engine's kernel searches the index roi_ensure made the active one; a debug
-// launch searches cold and keeps no positions, a plain one starts from the warm words and leaves its own there.
+// The single-pose runner of both 1-NN engines (context.hpp): what belongs to the search, in front of rows_run.  The engine's kernel searches
+// the index roi_ensure made the active one; a debug launch searches cold and keeps no positions, a plain one starts from the warm words
+// and leaves its own there.
 int one_nn_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_params *p, dcreg_lin_out *out, const char *what,
                int (*extra)(dcreg_ctx *, const dcreg_ctx::FrameSet *fs), const std::function<void(const OneNnLaunch &)> &launch, bool dump,
-               const OneNnDumpField *fields, int n_fields) {
+               const DumpField *fields, int n_fields) {
     if (int rc = one_nn_check(c, R, t, p, out, what)) return rc;
     if (extra) if (int rc = extra(c, nullptr)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the index a single-pose linearisation searches: the window of a capped map, as dcreg_linearize (a swap drops the warm positions)
     if (int rc = roi_ensure(c, R, t, p->search_radius)) return rc;
-    dcreg_ctx::NormalIcpBufs &B = c->nicp;
-    const size_t N = (size_t)c->n_src;
+    if (one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
     OneNnLaunch L;
-    L.nb = (uint32_t)((N + kLinBlock - 1) / kLinBlock);
-    if (B.partials.ensure(c, (size_t)L.nb * kSlots) || B.d_out.ensure(c, kSlots) || one_nn_warm_reserve(c)) return DCREG_E_NOMEM;
     L.bound = one_nn_bound(c->map.grid, p->search_radius);
     std::memcpy(L.P.R, R, sizeof(L.P.R)); std::memcpy(L.P.t, t, sizeof(L.P.t));
     L.P.state = kNoIdx; L.P.fresh = 1;
     L.dump = dump;
-    if (!dump) n_fields = 0;
+    const int rc = rows_run(c, out, fields, dump ? n_fields : 0, [&](double *partials, uint32_t nb) {
+        L.warm_in = dump ? nullptr : one_nn_warm_take(c);
+        L.warm_out = dump ? nullptr : c->nicp.warm.data();
+        L.partials = partials; L.nb = nb;
+        launch(L);
+    });
+    if (rc == DCREG_OK && !dump) one_nn_warm_done(c);
+    return rc;
+}
+// The back half of every single-pose call that leaves block rows (context.hpp): all three engines end here
+int rows_run(dcreg_ctx *c, dcreg_lin_out *out, const DumpField *fields, int n_fields, const std::function<void(double *partials, uint32_t nb)> &launch) {
+    dcreg_ctx::NormalIcpBufs &B = c->nicp;
+    const size_t N = (size_t)c->n_src;
+    const uint32_t nb = (uint32_t)((N + kLinBlock - 1) / kLinBlock);
+    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots)) return DCREG_E_NOMEM;
     // one block of device memory for the dump, cut into its arrays in the table's order (8-byte ones first)
     size_t total = 0;
     for (int k = 0; k < n_fields; ++k) total += fields[k].bytes * N;
-    if (dump && B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
+    if (n_fields && B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
     unsigned char *b = B.dbg.data();
     for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
         if (fields[k].host) std::memcpy(fields[k].dev, &b, sizeof(b));
-    L.warm_in = dump ? nullptr : one_nn_warm_take(c);
-    L.warm_out = dump ? nullptr : B.warm.data();
-    L.partials = B.partials.data();
-    launch(L);
+    launch(B.partials.data(), nb);
     HIP_TRY(c, hipGetLastError());
     b = B.dbg.data();
     for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
         if (fields[k].host) HIP_TRY(c, hipMemcpyAsync(fields[k].host, b, fields[k].bytes * N, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), L.nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
+    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
     HIP_TRY(c, hipGetLastError());
-    double h[kSlots];
-    HIP_TRY(c, hipMemcpyAsync(h, B.d_out.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    double row[kSlots];
+    HIP_TRY(c, hipMemcpyAsync(row, B.d_out.data(), sizeof(row), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (!dump) one_nn_warm_done(c);
-    lin_out_of_row(h, *out);
+    lin_out_of_row(row, *out);
     return DCREG_OK;
 }
 OneNnBound one_nn_bound(const GridDev &g, double search_radius) {
@@ -470,5 +496,5 @@ int dcreg_normals_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double 
     return one_nn_batch_begin(c, slot, n_poses, R9, t3, state_ids, c ? &c->frames : nullptr, frame_ids, nullptr, p, nullptr, nlin_batch_launch,
                               "the k_nlin_batch launch");
 }
-int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
+int dcreg_normals_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return rows_batch_end(c, slot, outs); }
 }

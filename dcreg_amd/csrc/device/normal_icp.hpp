@@ -118,4 +118,16 @@ DCREG_DEVFN uint8_t nlin_point(const GridDev &g, RunList &rl, const float4 *norm
     return 1;
 }
 
+#if !defined(DCREG_HOST_EMUL)
+// The cloud of block (x, pose) in a batched launch of any engine (k_nlin_batch, k_glin_batch, k_vlin_batch, k_vlin_pairs): slices[pose] =
+// {first point, points} of the set the launch reads.  false: the block lies past the end of its pose's slice and exits before it touches
+// anything (uniform per block); else the slice's points become n_src and `first` is where they start in the set's arrays
+__device__ __forceinline__ bool batch_slice(const uint2 *__restrict__ slices, uint32_t &first, uint32_t &n_src) {
+    const uint2 sl = slices[blockIdx.y];
+    if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return false;
+    first = sl.x; n_src = sl.y;
+    return true;
+}
+#endif
+
 }  // namespace dcreg

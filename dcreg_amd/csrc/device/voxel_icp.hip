@@ -1,21 +1,24 @@
 // The fourth engine's linearisation on the device (include/dcreg.h: dcreg_linearize_voxels): rows against the map's kept voxel
 // distributions (voxel.hip voxel_map_keep), with the rule of the header, bitwise the numpy reference of tests/voxels_ref.py.
-//   k_vlin<DUMP>   one lane per source point, in the context's curve order: vlin_point (voxel_icp.hpp) - transform, the lookup of the voxel
-//                  the point falls into (no search: nothing is walked, nothing is kept between calls), three 16-byte gathers of its
-//                  record, in mode 1 the coalesced float4 load of the point's own normal, the covariance, its Cholesky factor and W = L^-1;
-//                  then the third engine's block tail (gicp.hpp glin_block_rows): three rows per point over the matrix cores, the block
-//                  row in LDS, added in wave order.  Its LDS is the staging area of the Gram pass and the waves' sums - no RunList
-//   k_vlin_batch   the same for many poses in ONE launch (dcreg_voxels_batch_begin: the engine of dcreg_register_frames_voxels): block
-//                  (x, pose), every pose its own cloud - a frame of the loaded frames or the context's source - and nothing else per pose
-//   k_vlin_pairs   the same with a voxel map per pose (dcreg_pairs_voxels_batch_begin: the engine of dcreg_register_pairs_voxels): every
-//                  pose its own source of the pairs' sources and its own target's map of the pairs' voxel batch (voxel.hip
+//   vlin_block<DUMP>  what every block of this engine does, in one place: one lane per source point, in the cloud's curve order: vlin_point
+//                  (voxel_icp.hpp) - transform, the lookup of the voxel the point falls into (no search: nothing is walked, nothing is
+//                  kept between calls), three 16-byte gathers of its record, in mode 1 the coalesced float4 load of the point's own
+//                  normal, the covariance, its Cholesky factor and W = L^-1; then the third engine's block tail (gicp.hpp
+//                  glin_block_rows): three rows per point over the matrix cores, the block row in LDS, added in wave order.  Its LDS is
+//                  the staging area of the Gram pass and the waves' sums - no RunList
+// The three kernels are block-uniform prologues in front of it - they pick the cloud, the pose, the voxel map and the output row:
+//   k_vlin<DUMP>   the context's source, pose and kept voxel map: block x leaves partials[x]
+//   k_vlin_batch   many poses in ONE launch (dcreg_voxels_batch_begin: the engine of dcreg_register_frames_voxels): block (x, pose), every
+//                  pose its own cloud - a frame of the loaded frames or the context's source
+//   k_vlin_pairs   ... with a voxel map per pose (dcreg_pairs_voxels_batch_begin: the engine of dcreg_register_pairs_voxels): every pose
+//                  its own source of the pairs' sources and its own target's map of the pairs' voxel batch (voxel.hip
 //                  pairs_voxels_build), read through a block-uniform index
 //   k_finalize     (kernels.hpp) the block rows in chunk order, as for k_glin
-// vlin_run is the launch's own small run function: refusals, buffers, the dump block cut as one_nn_run cuts it, launch, k_finalize, wait.
-// It reads the source, the kept voxel map and - in mode 1 - the kept source normals; it neither reads nor writes warm words, neighbour
-// states, the window index (no roi_ensure) or the map's kept normals.  The block rows, the result row and the dump block are nicp's.
-// The batched form runs in the second engine's two launch slots (normal_icp.hip one_nn_batch_queue: buffers, pose and slice upload,
-// k_finalize, result copy, event); its refusals are vlin_run's, made here.  It keeps nothing either: no warm slots, no neighbour states.
+// On the host the engine brings its refusals, its launch and the fields of its dump to the seam all engines that leave block rows share
+// (normal_icp.hip, declared in context.hpp): vlin_run ends in rows_run (buffers, dump block, launch, k_finalize, wait); the batched forms
+// make the common refusals with rows_batch_check, resolve their clouds with rows_batch_clouds and queue through rows_batch_queue.
+// The engine reads the source, the kept voxel map and - in mode 1 - the kept source normals; it neither reads nor writes warm words,
+// warm slots, neighbour states, the window index (no roi_ensure) or the map's kept normals.
 // No floating-point atomics anywhere: the sums are a function of the rows and their order.
 #include <cmath>
 #include <cstring>
@@ -33,12 +36,14 @@ struct VlinDump {
     int32_t *voxel_idx; uint8_t *flag; double *mean, *cov, *normal_src, *w, *r, *row;
 };
 
-// src_normals: float4 per source point in the order of src (null in mode 0).  Slot 29 counts the effective POINTS (not rows), slot 30
-// the points that fall into a kept voxel.
+// The body of the three kernels: block blockIdx.x of the n_src points at src against the voxel map vm at pose P; the block row goes to
+// `out`.  src_normals: float4 per source point in the order of src (null in mode 0, and never read).  member == false (a pair target
+// that kept no voxel): no table and no record is read, the points keep flag 0 and the block row is the zero row.  Slot 29 counts the
+// effective POINTS (not rows), slot 30 the points that fall into a kept voxel.
 template <bool DUMP>
-static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4 *__restrict__ src, uint32_t n_src, VoxMapDev vm,
-                                                                     const float4 *__restrict__ src_normals, PoseArg P, VlinArgs a,
-                                                                     double *__restrict__ partials, VlinDump d) {
+__device__ __forceinline__ void vlin_block(const float4 *__restrict__ src, uint32_t n_src, const VoxMapDev &vm, bool member,
+                                           const float4 *__restrict__ src_normals, const PoseArg &P, const VlinArgs &a,
+                                           double *__restrict__ out, const VlinDump &d) {
     __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
     __shared__ double gm[kLinBlock / kWave][64];
     __shared__ double cnt[kLinBlock / kWave][2];
@@ -52,7 +57,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4
         const float4 s4 = src[i];
         sx = s4.x; sy = s4.y; sz = s4.z;
         VlinPoint x;
-        flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
+        if (member) flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
         if constexpr (DUMP) {
             oi = __float_as_uint(s4.w);
             if (d.voxel_idx) d.voxel_idx[oi] = x.vidx == kNoIdx ? -1 : (int32_t)x.vidx;
@@ -68,7 +73,7 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4
             }
         }
     }
-    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + (size_t)blockIdx.x * kSlots, [&](int k, const double (&row)[8]) {
+    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, out, [&](int k, const double (&row)[8]) {
         if constexpr (DUMP) {
             if (i < n_src) {
                 if (d.r) d.r[3 * oi + k] = row[7];
@@ -81,99 +86,55 @@ static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4
     });
 }
 
+template <bool DUMP>
+static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin(const float4 *__restrict__ src, uint32_t n_src, VoxMapDev vm,
+                                                                     const float4 *__restrict__ src_normals, PoseArg P, VlinArgs a,
+                                                                     double *__restrict__ partials, VlinDump d) {
+    vlin_block<DUMP>(src, n_src, vm, true, src_normals, P, a, partials + (size_t)blockIdx.x * kSlots, d);
+}
+
 // Many poses in one launch: k_vlin as k_glin_batch is k_glin (gicp.hip).  Block (x, pose): pose = poses[blockIdx.y], read through a
-// block-uniform index; its cloud is slices[pose] = {first point, points} of src and - in mode 1 - of src_normals (a frame of the loaded
-// frames and that frame's kept normals: the same positions; a block past the end of a short frame's slice exits before it touches
-// anything) or, slices == null, the n_src points at src (the context's own source and its kept source normals).  The body is vlin_point
-// and glin_block_rows, unchanged; the block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the rows and
+// block-uniform index; its cloud is slices[pose] of src and - in mode 1 - of src_normals (a frame of the loaded frames and that frame's
+// kept normals: the same positions; normal_icp.hpp batch_slice) or, slices == null, the n_src points at src (the context's own source
+// and its kept source normals).  The block row goes to partials[pose * n_blocks_x + x], where k_finalize<SLICE> finds it: the rows and
 // additions of the pose's single launch.  Nothing is kept between launches, so there are no warm words.
 static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin_batch(const float4 *__restrict__ src, uint32_t n_src, VoxMapDev vm,
                                                                            const float4 *__restrict__ src_normals,
                                                                            const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
                                                                            VlinArgs a, double *__restrict__ partials, uint32_t n_blocks_x) {
-    __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
-    __shared__ double gm[kLinBlock / kWave][64];
-    __shared__ double cnt[kLinBlock / kWave][2];
     const uint32_t pose_id = blockIdx.y;
-    if (slices) {                                    // (uniform per block: before anything is touched)
-        const uint2 sl = slices[pose_id];
-        if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
-        src += sl.x; n_src = sl.y;
-        if (src_normals) src_normals += sl.x;        // (mode 0: null, and never read)
+    if (slices) {
+        uint32_t first;
+        if (!batch_slice(slices, first, n_src)) return;
+        src += first;
+        if (src_normals) src_normals += first;       // (mode 0: null, and never read)
     }
-    const PoseArg &P = poses[pose_id];
-    const int wave = threadIdx.x >> 6;
-    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
-    uint8_t flag = 0;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    GlinPoint o;
-    if (i < n_src) {
-        const float4 s4 = src[i];
-        sx = s4.x; sy = s4.y; sz = s4.z;
-        VlinPoint x;
-        flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
-    }
-    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
-                    [](int, const double (&)[8]) {});
+    vlin_block<false>(src, n_src, vm, true, src_normals, poses[pose_id], a, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
+                      VlinDump{});
 }
 
 // Scan pairs in one launch (dcreg_pairs_voxels_batch_begin: the engine of dcreg_register_pairs_voxels): k_vlin_batch with a voxel map per
-// pose.  Block (x, pose): pose = poses[blockIdx.y]; its cloud is slices[pose] of the pairs' sources (and, in mode 1, of their kept
-// normals); its target is maps[target_ids[pose]] of the pairs' voxel batch (voxel.hip pairs_voxels_build), read through a block-uniform
-// index as k_nlin_batch<GRIDS> reads its OneNnGrid - the VoxMapDev that vlin_point takes is formed from that record: the target's own
-// records, its own table, its own box; the leaf is the batch's.  A pose whose target has no member (n_kept 0) reads no table and no
-// record: its points keep flag 0 and the block row is the zero row.  The body is vlin_point and glin_block_rows, unchanged; the block
-// row goes where k_finalize<true> finds it.  A kernel of its own: k_vlin_batch is compiled from the source it had.
+// pose.  Block (x, pose): its cloud is slices[pose] of the pairs' sources (and, in mode 1, of their kept normals); its target is
+// maps[target_ids[pose]] of the pairs' voxel batch (voxel.hip pairs_voxels_build), read through a block-uniform index as
+// k_nlin_batch<GRIDS> reads its OneNnGrid - the VoxMapDev that vlin_point takes is formed from that record: the target's own records, its
+// own table, its own box; the leaf is the batch's.  A pose whose target has no member (n_kept 0) leaves the zero row.
 static __global__ __launch_bounds__(kLinBlock, kLinOcc) void k_vlin_pairs(const float4 *__restrict__ src, const float4 *__restrict__ src_normals,
                                                                            const PairVoxMap *__restrict__ maps, const uint32_t *__restrict__ target_ids,
                                                                            const float4 *__restrict__ recs, const uint64_t *__restrict__ t_keys,
                                                                            const uint32_t *__restrict__ t_vals, double leaf,
                                                                            const PoseArg *__restrict__ poses, const uint2 *__restrict__ slices,
                                                                            VlinArgs a, double *__restrict__ partials, uint32_t n_blocks_x) {
-    __shared__ double stage[kLinBlock / kWave][kWave * kRowStride];
-    __shared__ double gm[kLinBlock / kWave][64];
-    __shared__ double cnt[kLinBlock / kWave][2];
     const uint32_t pose_id = blockIdx.y;
-    const uint2 sl = slices[pose_id];                    // (uniform per block: before anything is touched)
-    if (blockIdx.x >= (sl.y + kLinBlock - 1) / kLinBlock) return;
-    src += sl.x;
-    const uint32_t n_src = sl.y;
-    if (src_normals) src_normals += sl.x;                // (mode 0: null, and never read)
+    uint32_t first, n_src;
+    if (!batch_slice(slices, first, n_src)) return;
+    src += first;
+    if (src_normals) src_normals += first;           // (mode 0: null, and never read)
     const PairVoxMap &m = maps[target_ids[pose_id]];
-    VoxMapDev vm;
-    vm.recs = recs + (size_t)m.first * kVmapRecWords; vm.keys = t_keys + m.base; vm.vals = t_vals + m.base; vm.mask = m.mask; vm.leaf = leaf;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { vm.mn[k] = m.mn[k]; vm.mx[k] = m.mx[k]; }
-    const bool member = m.n_kept != 0u;
-    const PoseArg &P = poses[pose_id];
-    const int wave = threadIdx.x >> 6;
-    const uint32_t i = blockIdx.x * kLinBlock + threadIdx.x;
-    uint8_t flag = 0;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    GlinPoint o;
-    if (i < n_src) {
-        const float4 s4 = src[i];
-        sx = s4.x; sy = s4.y; sz = s4.z;
-        VlinPoint x;
-        if (member) flag = vlin_point(vm, P, a, s4, src_normals + i, o, x);
-    }
-    glin_block_rows(P, a.robust, flag, sx, sy, sz, o, stage[wave], gm, cnt, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots,
-                    [](int, const double (&)[8]) {});
+    vlin_block<false>(src, n_src, vox_map_dev(recs + (size_t)m.first * kVmapRecWords, t_keys + m.base, t_vals + m.base, m.mask, m.mn, m.mx, leaf),
+                      m.n_kept != 0u, src_normals, poses[pose_id], a, partials + ((size_t)pose_id * n_blocks_x + blockIdx.x) * kSlots, VlinDump{});
 }
 
-bool finite_n(const double *v, int n) {
-    for (int k = 0; k < n; ++k) if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
-// the kept voxel map as the kernels read it, and the launch's arguments ("voxels_source_cov", "gicp_epsilon", "robust_kernel" and
-// "gicp_robust_scale" are read at every call)
-VoxMapDev vox_map_dev(const dcreg_ctx::VoxelMapBufs &M) {
-    VoxMapDev vm;
-    vm.recs = M.recs.data(); vm.keys = M.t_keys.data(); vm.vals = M.t_vals.data(); vm.mask = M.mask; vm.leaf = M.leaf;
-    for (int a = 0; a < 3; ++a) { vm.mn[a] = M.mn[a]; vm.mx[a] = M.mx[a]; }
-    return vm;
-}
+// the launch's arguments ("voxels_source_cov", "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at every call)
 VlinArgs vlin_args(const dcreg_ctx *c) {
     VlinArgs a;
     a.source_cov = c->opt_voxels_source_cov; a.c = 1.0 - c->opt_gicp_epsilon;
@@ -190,114 +151,64 @@ int vlin_run(dcreg_ctx *c, const double *R, const double *t, const dcreg_lin_par
     if (!finite_n(R, 9) || !finite_n(t, 3)) { c->fail("the pose is not finite"); return DCREG_E_INVALID; }
     if ((c->roi_active ? c->roi_store : c->map).n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
-    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    const dcreg_ctx::VoxelMapBufs &M = c->vmap;
     if (!M.kept) { c->fail("no kept voxels: dcreg_target_voxels_keep first"); return DCREG_E_STATE; }
-    const int mode = c->opt_voxels_source_cov;
-    if (mode && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
+    const VlinArgs a = vlin_args(c);
+    if (a.source_cov && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
     HIP_TRY(c, hipSetDevice(c->device));
-    dcreg_ctx::NormalIcpBufs &B = c->nicp;
-    const size_t N = (size_t)c->n_src;
-    const uint32_t nb = (uint32_t)((N + kLinBlock - 1) / kLinBlock);
-    if (B.partials.ensure(c, (size_t)nb * kSlots) || B.d_out.ensure(c, kSlots)) return DCREG_E_NOMEM;
-    // one block of device memory for the dump, cut into its arrays in the table's order (8-byte ones first)
     VlinDump d{};
     const dcreg_vlin_debug none{}, &h = dbg ? *dbg : none;
-    const OneNnDumpField fields[] = {{h.mean, 24, &d.mean}, {h.cov, 48, &d.cov}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
-                                     {h.row, 192, &d.row}, {h.voxel_idx, 4, &d.voxel_idx}, {h.flag, 1, &d.flag}};
-    const int n_fields = dbg ? 8 : 0;
-    size_t total = 0;
-    for (int k = 0; k < n_fields; ++k) total += fields[k].bytes * N;
-    if (dbg && B.dbg.ensure(c, total)) return DCREG_E_NOMEM;
-    unsigned char *b = B.dbg.data();
-    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
-        if (fields[k].host) std::memcpy(fields[k].dev, &b, sizeof(b));
-    const VoxMapDev vm = vox_map_dev(M);
-    const VlinArgs a = vlin_args(c);
+    const DumpField fields[] = {{h.mean, 24, &d.mean}, {h.cov, 48, &d.cov}, {h.normal_src, 24, &d.normal_src}, {h.w, 72, &d.w}, {h.r, 24, &d.r},
+                                {h.row, 192, &d.row}, {h.voxel_idx, 4, &d.voxel_idx}, {h.flag, 1, &d.flag}};
+    const VoxMapDev vm = vox_map_dev(M.recs.data(), M.t_keys.data(), M.t_vals.data(), M.mask, M.mn, M.mx, M.leaf);
     PoseArg P;
     std::memcpy(P.R, R, sizeof(P.R)); std::memcpy(P.t, t, sizeof(P.t));
     P.state = kNoIdx; P.fresh = 1;
-    hipLaunchKernelGGL(dbg ? k_vlin<true> : k_vlin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)N, vm,
-                       mode ? c->gicp.src_normals.data() : (const float4 *)nullptr, P, a, B.partials.data(), d);
-    HIP_TRY(c, hipGetLastError());
-    b = B.dbg.data();
-    for (int k = 0; k < n_fields; b += fields[k++].bytes * N)
-        if (fields[k].host) HIP_TRY(c, hipMemcpyAsync(fields[k].host, b, fields[k].bytes * N, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(k_finalize<false>, dim3(1), dim3(kLinBlock), 0, c->stream, B.partials.data(), nb, B.d_out.data(), 0ull, (const uint2 *)nullptr);
-    HIP_TRY(c, hipGetLastError());
-    double row[kSlots];
-    HIP_TRY(c, hipMemcpyAsync(row, B.d_out.data(), sizeof(row), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    lin_out_of_row(row, *out);
-    return DCREG_OK;
+    return rows_run(c, out, fields, dbg ? 8 : 0, [&](double *partials, uint32_t nb) {
+        hipLaunchKernelGGL(dbg ? k_vlin<true> : k_vlin<false>, dim3(nb), dim3(kLinBlock), 0, c->stream, c->d_src.data(), (uint32_t)c->n_src, vm,
+                           a.source_cov ? c->gicp.src_normals.data() : (const float4 *)nullptr, P, a, partials, d);
+    });
 }
 
-// The batched launch (include/dcreg_debug.h: dcreg_voxels_batch_begin): every refusal in the header's order - vlin_run's and the launch
-// slots' - before anything is queued, then the shared slot plumbing with k_vlin_batch as its kernel.  The options are read here.
+// The batched launch (include/dcreg_debug.h: dcreg_voxels_batch_begin): every refusal in the header's order - the launch slots' and
+// vlin_run's - before anything is queued, then the shared slot plumbing with k_vlin_batch as its kernel.  The options are read here.
 int vlin_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *frame_ids, const dcreg_lin_params *p) {
-    if (!c) return DCREG_E_INVALID;
-    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
-    if (!R9 || !t3 || !p || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
-    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
-    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
-    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
-    if (c->nicp.batch[slot].pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
-    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the voxel linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
-    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    if (int rc = rows_batch_check(c, slot, n_poses, R9, t3, p, true, "voxel", false)) return rc;
     if ((c->roi_active ? c->roi_store : c->map).n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     const dcreg_ctx::VoxelMapBufs &M = c->vmap;
     if (!M.kept) { c->fail("no kept voxels: dcreg_target_voxels_keep first"); return DCREG_E_STATE; }
     dcreg_ctx::FrameSet *fs = frame_ids ? &c->frames : nullptr;
-    int64_t n_max = c->n_src;                         // points of the launch's largest cloud
-    if (fs) {
-        const std::vector<uint2> &slice = fs->slice;
-        if (slice.empty()) { c->fail("no frames: dcreg_frames_load first"); return DCREG_E_STATE; }
-        n_max = 0;
-        for (int i = 0; i < n_poses; ++i) {
-            const int32_t f = frame_ids[i];
-            if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("frame %d is not loaded or empty", f); return DCREG_E_INVALID; }
-            n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
-        }
-    } else if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
+    int64_t n_max;
+    if (int rc = rows_batch_clouds(c, fs, n_poses, frame_ids, "frame", nullptr, n_max)) return rc;
     const VlinArgs a = vlin_args(c);
     if (a.source_cov && fs && !fs->normals_kept) { c->fail("no kept frame normals: dcreg_frames_normals_keep or dcreg_frames_normals_set first"); return DCREG_E_STATE; }
     if (a.source_cov && !fs && !c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
-    const VoxMapDev vm = vox_map_dev(M);
-    return one_nn_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, frame_ids, nullptr, n_max, [&](OneNnBatch &L) {
+    const VoxMapDev vm = vox_map_dev(M.recs.data(), M.t_keys.data(), M.t_vals.data(), M.mask, M.mn, M.mx, M.leaf);
+    return rows_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, frame_ids, nullptr, n_max, [&](OneNnBatch &L) {
         hipLaunchKernelGGL(k_vlin_batch, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src, L.n_src, vm,
                            a.source_cov ? L.src_normals : (const float4 *)nullptr, L.poses, L.slices, a, L.partials, L.nbx);
     }, "the k_vlin_batch launch");
 }
 
-// The pairs launch (include/dcreg_debug.h: dcreg_pairs_voxels_batch_begin): vlin_batch_begin's refusals in its order, with "no pair voxel
-// batch built" and "no pair sources" in place of "no target", "no kept voxels" and "no frames", then the shared slot plumbing with
-// k_vlin_pairs as its kernel; the pose's target rides where the 1-NN pairs launches carry theirs (OneNnBatch::grid_ids)
+// The pairs launch (include/dcreg_debug.h: dcreg_pairs_voxels_batch_begin): vlin_batch_begin's refusals in its order - null ids are null
+// arguments; "no pair voxel batch built" and "no pair sources" in place of "no target", "no kept voxels" and "no frames"; pose i's source
+// is checked before its target - then the shared slot plumbing with k_vlin_pairs as its kernel; the pose's target rides where the 1-NN
+// pairs launches carry theirs (OneNnBatch::grid_ids)
 int vlin_pairs_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *source_ids, const int32_t *target_ids,
                            const dcreg_lin_params *p) {
-    if (!c) return DCREG_E_INVALID;
-    if (slot < 0 || slot >= 2) { c->fail("invalid slot %d", slot); return DCREG_E_INVALID; }
-    if (!R9 || !t3 || !p || !source_ids || !target_ids || n_poses < 1) { c->fail("null linearisation arguments"); return DCREG_E_INVALID; }
-    if (n_poses > 65535) { c->fail("at most 65535 poses per batched launch (grid.y limit), got %d", n_poses); return DCREG_E_INVALID; }
-    if (c->gate_slot >= 0) { c->fail("a gated linearisation still waits for its pose (dcreg_linearize_gate_open / _gate_abort first)"); return DCREG_E_STATE; }
-    for (const LinSlot &S : c->slots) if (S.pending) { c->fail("a linearisation is still in flight"); return DCREG_E_STATE; }
-    if (c->nicp.batch[slot].pending) { c->fail("slot %d still has a batched normal linearisation in flight", slot); return DCREG_E_STATE; }
-    if (p->parameterization != DCREG_PARAM_SO3) { c->fail("the voxel linearisation has the SO(3) row only (parameterization %d)", p->parameterization); return DCREG_E_INVALID; }
-    if (!finite_n(R9, 9 * n_poses) || !finite_n(t3, 3 * n_poses)) { c->fail("a pose is not finite"); return DCREG_E_INVALID; }
+    if (int rc = rows_batch_check(c, slot, n_poses, R9, t3, p, source_ids && target_ids, "voxel", false)) return rc;
     const dcreg_ctx::PairVoxBufs &V = c->pvox;
     if (V.n <= 0) { c->fail("no pair voxel batch built: dcreg_pairs_voxels_build first"); return DCREG_E_STATE; }
     dcreg_ctx::FrameSet *fs = &c->pair_src;
-    const std::vector<uint2> &slice = fs->slice;
-    if (slice.empty()) { c->fail("no pair sources: dcreg_pairs_sources_load first"); return DCREG_E_STATE; }
-    int64_t n_max = 0;                                // points of the launch's largest cloud
-    for (int i = 0; i < n_poses; ++i) {
-        const int32_t f = source_ids[i], t = target_ids[i];
-        if (f < 0 || (size_t)f >= slice.size() || slice[(size_t)f].y == 0u) { c->fail("pair source %d is not loaded or empty", f); return DCREG_E_INVALID; }
-        if (t < 0 || t >= V.n) { c->fail("pair target %d is not in the voxel batch", t); return DCREG_E_INVALID; }
-        n_max = std::max<int64_t>(n_max, slice[(size_t)f].y);
-    }
+    int64_t n_max;
+    if (int rc = rows_batch_clouds(c, fs, n_poses, source_ids, "pair source", [&](int i) {
+            const int32_t t = target_ids[i];
+            if (t < 0 || t >= V.n) { c->fail("pair target %d is not in the voxel batch", t); return DCREG_E_INVALID; }
+            return DCREG_OK;
+        }, n_max)) return rc;
     const VlinArgs a = vlin_args(c);
     if (a.source_cov && !fs->normals_kept) { c->fail("no kept pair source normals: dcreg_pairs_sources_normals_keep or dcreg_pairs_sources_normals_set first"); return DCREG_E_STATE; }
-    return one_nn_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, source_ids, target_ids, n_max, [&](OneNnBatch &L) {
+    return rows_batch_queue(c, slot, n_poses, R9, t3, nullptr, fs, source_ids, target_ids, n_max, [&](OneNnBatch &L) {
         hipLaunchKernelGGL(k_vlin_pairs, dim3(L.nbx, (unsigned)L.n_poses), dim3(kLinBlock), 0, c->stream, L.src,
                            a.source_cov ? L.src_normals : (const float4 *)nullptr, V.d_maps.data(), L.grid_ids, V.recs.data(), V.t_keys.data(),
                            V.t_vals.data(), V.leaf, L.poses, L.slices, a, L.partials, L.nbx);
@@ -321,7 +232,7 @@ int dcreg_voxels_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *
                              const dcreg_lin_params *p) {
     return vlin_batch_begin(c, slot, n_poses, R9, t3, frame_ids, p);
 }
-int dcreg_voxels_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return one_nn_batch_end(c, slot, outs); }
+int dcreg_voxels_batch_end(dcreg_ctx *c, int slot, dcreg_lin_out *outs) { return rows_batch_end(c, slot, outs); }
 int dcreg_pairs_voxels_batch_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9, const double *t3, const int32_t *source_ids,
                                    const int32_t *target_ids, const dcreg_lin_params *p) {
     return vlin_pairs_batch_begin(c, slot, n_poses, R9, t3, source_ids, target_ids, p);

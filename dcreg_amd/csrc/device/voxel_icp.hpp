@@ -24,6 +24,17 @@ struct VoxMapDev {
     long long mn[3], mx[3];
     double leaf;
 };
+// ... formed on the host from the context's kept map and in k_vlin_pairs from a pair target's record (voxel_icp.hip)
+#if !defined(DCREG_HOST_EMUL)
+__host__ __device__ __forceinline__ VoxMapDev vox_map_dev(const float4 *recs, const uint64_t *keys, const uint32_t *vals, uint32_t mask,
+                                                          const long long (&mn)[3], const long long (&mx)[3], double leaf) {
+    VoxMapDev vm;
+    vm.recs = recs; vm.keys = keys; vm.vals = vals; vm.mask = mask; vm.leaf = leaf;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { vm.mn[k] = mn[k]; vm.mx[k] = mx[k]; }
+    return vm;
+}
+#endif
 
 DCREG_DEVFN uint64_t vmap_key(uint64_t rx, uint64_t ry, uint64_t rz) { return (rz << (2 * kVmapAxisBits)) | (ry << kVmapAxisBits) | rx; }
 // where a key's probe sequence starts (the finaliser of MurmurHash3: neighbouring voxels land far apart)
