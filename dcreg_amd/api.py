@@ -1384,6 +1384,7 @@ class Context:
         self._L = load()
         self._h = C.c_void_p()
         self._n_frames = 0            # frames the last successful load put on the device
+        self._voxels_neighbors = 1    # "voxels_neighbors" as set_option last set it: the size of linearize_voxels' dump
         rc = self._L.dcreg_backend_create(C.byref(self._h), int(device))
         if rc != OK:
             self._h = None
@@ -1410,6 +1411,8 @@ class Context:
 
     def set_option(self, key, value):
         self._check(self._L.dcreg_set_option(self._h, key.encode(), float(value)), "dcreg_set_option")
+        if key == "voxels_neighbors":
+            self._voxels_neighbors = int(value)
 
     def set_robust(self, kernel, scale=None, gicp_scale=None):
         """The robust kernel of linearize_normals / linearize_gicp and of every form built on them (include/dcreg.h, "robust kernels"):
@@ -2164,9 +2167,12 @@ class Context:
 
     def linearize_voxels(self, T, params=None, debug=False):
         """dcreg_linearize_voxels at the pose T (4 x 4): three whitened rows per source point that falls into a kept voxel (include/dcreg.h
-        has the rule; of params only the parameterization is read; set_option("voxels_source_cov", 1) adds the source's plane covariance)
+        has the rule; of params only the parameterization is read; set_option("voxels_source_cov", 1) adds the source's plane covariance;
+        set_option("voxels_neighbors", S), S = 7 or 27, matches a point to the kept voxels of the stencil around its own, three rows each)
         -> dict as linearize(); debug=True adds the per-point dump in source order: voxel_idx, flag, mean [n, 3], cov [n, 6],
-        normal_src [n, 3], w [n, 3, 3], r [n, 3], row [n, 3, 8]."""
+        normal_src [n, 3], w [n, 3, 3], r [n, 3], row [n, 3, 8].  With S > 1 every array but normal_src has an axis of length S - the
+        correspondences in stencil order - behind the point axis: voxel_idx [n, S], ..., row [n, S, 3, 8].  S is the value this wrapper's
+        set_option set last."""
         what, symbol = "linearize_voxels", "dcreg_linearize_voxels"
         params = self._vlin_params(params, what)
         R, t = _pose_arg(T, what)
@@ -2174,7 +2180,9 @@ class Context:
         if not debug:
             self._check(self._L.dcreg_linearize_voxels(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out)), symbol)
             return self._out_dict(out)
-        keep, dbg = _dump_arg(self.index_info().n_source, _VLIN_DUMP, VlinDebug)
+        S = self._voxels_neighbors
+        entries = [(k, dt, shape if S == 1 or k == "normal_src" else (S,) + shape) for k, dt, shape in _VLIN_DUMP]
+        keep, dbg = _dump_arg(self.index_info().n_source, entries, VlinDebug)
         self._check(self._L.dcreg_linearize_voxels_debug(self._h, _dp(R), _dp(t), C.byref(params), C.byref(out), C.byref(dbg)), symbol + "_debug")
         d = self._out_dict(out)
         d.update(keep)
@@ -2186,7 +2194,7 @@ class Context:
 
     def icp_run_voxels(self, T0, method, cfg, log_capacity=None):
         """dcreg_icp_run_voxels: icp_run_gicp's loop around linearize_voxels -> (result, logs); a log's rmse is the RMS Mahalanobis
-        distance per effective point"""
+        distance per effective point.  "voxels_neighbors" is read when the call starts, like "voxels_source_cov"."""
         return self._run_logged("dcreg_icp_run_voxels", T0, method, cfg, log_capacity, "icp_run_voxels")
 
     # ---- the fourth engine's many-frames form (include/dcreg.h: dcreg_register_frames_voxels, dcreg_icp_run_trials_voxels) and its device
@@ -2195,7 +2203,7 @@ class Context:
         """dcreg_register_frames_voxels: register_frames with the fourth engine (keep_target_voxels first).  frame_normals =
         normal_params(...) is the rule every frame's own normals are estimated with when set_option("voxels_source_cov", 1) is on - it is
         required then - and is not read otherwise (None: a null pointer is passed).  Same arguments and records; each record is bitwise
-        set_source(frame) [+ keep_source_normals(frame_normals)] + icp_run_voxels(T0)."""
+        set_source(frame) [+ keep_source_normals(frame_normals)] + icp_run_voxels(T0), at the "voxels_neighbors" in force when the call starts."""
         if frame_normals is not None:
             _check_normal_params(frame_normals, "register_frames_voxels")
         return self._register_frames("dcreg_register_frames_voxels", frames, T0s, method, cfg, slots, "register_frames_voxels",
@@ -2203,13 +2211,13 @@ class Context:
 
     def icp_run_trials_voxels(self, T0s, method, cfg):
         """dcreg_icp_run_trials_voxels: icp_run_trials with the fourth engine (kept voxels first, in mode 1 kept source normals too); each
-        record is bitwise icp_run_voxels from its pose"""
+        record is bitwise icp_run_voxels from its pose, at the "voxels_neighbors" in force when the call starts"""
         return self._run_trials("dcreg_icp_run_trials_voxels", T0s, method, cfg, "icp_run_trials_voxels")
 
     def voxels_batch_begin(self, Ts, frame_ids=None, params=None, slot=0):
         """dcreg_voxels_batch_begin: one launch over the poses Ts ([n, 4, 4]); pose i linearises frame frame_ids[i] of the loaded frames
-        (None: the own source) against the kept voxels.  Nothing is kept between launches: there are no state_ids.  -> the number of
-        poses, for voxels_batch_end"""
+        (None: the own source) against the kept voxels.  Nothing is kept between launches: there are no state_ids.  "voxels_neighbors" is
+        read here, with the other options.  -> the number of poses, for voxels_batch_end"""
         params = self._vlin_params(params, "voxels_batch_begin")
         Rs, ts, n = _poses_arg(Ts)
         fids = None if frame_ids is None else np.ascontiguousarray(frame_ids, dtype=np.int32).reshape(n)
@@ -3004,7 +3012,7 @@ class Context:
         voxel_map_params(...), None = the defaults) instead of an index.  source_normals = normal_params(...) is the rule every source's
         own normals are estimated with when set_option("voxels_source_cov", 1) is on - it is required then - and is not read otherwise
         (None: a null pointer is passed).  Each record is bitwise set_target(target, any radius) + keep_target_voxels(target_voxels) +
-        set_source(source) [+ keep_source_normals(source_normals)] + icp_run_voxels(T0); a target that keeps no voxel gives status 3."""
+        set_source(source) [+ keep_source_normals(source_normals)] + icp_run_voxels(T0), at the "voxels_neighbors" in force when the call starts; a target that keeps no voxel gives status 3."""
         tv = target_voxels if target_voxels is not None else voxel_map_params()
         _check_voxel_map_params(tv, "register_pairs_voxels")
         if source_normals is not None:
@@ -3039,7 +3047,8 @@ class Context:
 
     def pairs_voxels_batch_begin(self, Ts, source_ids, target_ids, params=None, slot=0):
         """dcreg_pairs_voxels_batch_begin: one launch over the poses Ts; pose i linearises pair source source_ids[i] against the voxel map
-        of target target_ids[i] of the batch.  -> the number of poses, for voxels_batch_end"""
+        of target target_ids[i] of the batch; "voxels_neighbors" is read here, with the other options.  -> the number of poses, for
+        voxels_batch_end"""
         params = self._vlin_params(params, "pairs_voxels_batch_begin")
         Rs, ts, n = _poses_arg(Ts)
         i32p = C.POINTER(C.c_int32)

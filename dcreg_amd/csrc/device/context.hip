@@ -2388,6 +2388,10 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
         if (!(v == 0.0 || v == 1.0)) { c->fail("voxels_source_cov is %g: 0 or 1 expected", v); return DCREG_E_INVALID; }
         c->opt_voxels_source_cov = (int)v;
     }
+    else if (k == "voxels_neighbors") {                          // dcreg_linearize_voxels: the stencil of voxels a point is matched to (1, 7 or 27), read at every call
+        if (!(v == 1.0 || v == 7.0 || v == 27.0)) { c->fail("voxels_neighbors is %g: 1, 7 or 27 expected", v); return DCREG_E_INVALID; }
+        c->opt_voxels_neighbors = (int)v;
+    }
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;

@@ -523,6 +523,7 @@ struct dcreg_ctx {
     };
     VoxelMapBufs vmap;
     int opt_voxels_source_cov = 0;                             // "voxels_source_cov": 0 point-to-distribution, 1 distribution-to-distribution, read at every call
+    int opt_voxels_neighbors = 1;                              // "voxels_neighbors": the voxels a point is matched to - its own (1), with the face neighbours (7), the whole 3^3 block (27), read at every call
     double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
     int opt_robust_kernel = 0;                                 // "robust_kernel" (DCREG_ROBUST_*): the second and third engine's rows, read at every call
     double opt_robust_scale = 0.1;                             // "robust_scale": its scale c for the second engine, metres

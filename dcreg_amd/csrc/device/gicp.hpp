@@ -4,7 +4,7 @@
 // point-to-plane rows whose pseudo-normals are W's rows.  The rule is the header's, operation by operation; tests/gicp_ref.py states
 // it in numpy.  Included by gicp.hip (the kernels) and, like normal_icp.hpp, compiled for the host under DCREG_HOST_EMUL by the test
 // suite's replay (tests/host_emul/).  The device-only part at the end is the block tail of the engines with three rows per point
-// (wave_gram3_mfma, glin_block_rows), shared with voxel_icp.hip.
+// (WaveGram, wave_gram3_mfma, glin_block_rows, glin_block_tail), shared with voxel_icp.hip.
 #pragma once
 #include "normal_icp.hpp"
 
@@ -142,20 +142,21 @@ DCREG_DEVFN void glin_row_scale(double k, double (&row)[8]) {
 #include "kernels.hpp"
 namespace dcreg {
 
-// wave_gram_mfma (kernels.hpp) for three rows per lane: pass k stages row_of(k) of all 64 lanes and runs the 8 MFMA steps on the
-// accumulator the pass before left, then the two DPP adds - the Gram matrix of the wave's 192 rows, summed in the fixed order (pass,
-// step).  The rows of a pass are built just before it.  A pass's operand reads are other lanes' stores: within the wave the LDS
-// executes in program order, and the wavefront fences keep the compiler from moving a pass's stores above the reads of the pass before
-// (or its reads above its own stores).  Returns u0 / u1 as wave_gram_mfma does.
-template <class RowOf>
-__device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int lane, double &u0, double &u1) {
-    const int c16 = lane & 15, k = lane >> 4;
-    const double *op = stage + (2 * k + (c16 >> 3)) * kRowStride + (c16 & 7);
-    mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int pass = 0; pass < 3; ++pass) {
-        double row[8];
-        row_of(pass, row);
+// wave_gram_mfma (kernels.hpp) for several rows per lane, one pass each: pass() stages one row of all 64 lanes and runs the 8 MFMA steps on
+// the accumulator the pass before left; end() makes the two DPP adds - the Gram matrix of all the rows the wave passed, summed in the fixed
+// order (pass, step).  A pass's operand reads are other lanes' stores: within the wave the LDS executes in program order, and the wavefront
+// fences keep the compiler from moving a pass's stores above the reads of the pass before (or its reads above its own stores).  Every lane
+// of the wave makes every pass (a lane without a row passes zeros); a pass whose rows are all zero adds +0.0 products to an accumulator
+// that started at +0.0, so leaving it out moves no bit.
+struct WaveGram {
+    const double *op;
+    mfma_d4 acc;
+    __device__ __forceinline__ void begin(const double *stage, int lane) {
+        const int c16 = lane & 15, k = lane >> 4;
+        op = stage + (2 * k + (c16 >> 3)) * kRowStride + (c16 & 7);
+        acc = mfma_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    __device__ __forceinline__ void pass(const double (&row)[8], double *stage, int lane) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // the reads of the pass before are over
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -168,11 +169,44 @@ __device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, acc, 0, 0, 0);
         }
     }
-    const bool even = c16 < 8;
-    u0 = even ? acc[0] : acc[2];
-    u1 = even ? acc[1] : acc[3];
-    u0 = dpp_add<0x128, 0xF>(u0);      // row_ror:8 - the lane holding the other half's block entry
-    u1 = dpp_add<0x128, 0xF>(u1);
+    // u0 / u1 as wave_gram_mfma returns them
+    __device__ __forceinline__ void end(int lane, double &u0, double &u1) const {
+        const bool even = (lane & 15) < 8;
+        u0 = even ? acc[0] : acc[2];
+        u1 = even ? acc[1] : acc[3];
+        u0 = dpp_add<0x128, 0xF>(u0);      // row_ror:8 - the lane holding the other half's block entry
+        u1 = dpp_add<0x128, 0xF>(u1);
+    }
+};
+
+// ... for three rows per lane: the rows of a pass are built just before it (row_of(pass, row)); the Gram matrix of the wave's 192 rows
+template <class RowOf>
+__device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int lane, double &u0, double &u1) {
+    WaveGram G;
+    G.begin(stage, lane);
+#pragma unroll
+    for (int pass = 0; pass < 3; ++pass) {
+        double row[8];
+        row_of(pass, row);
+        G.pass(row, stage, lane);
+    }
+    G.end(lane, u0, u1);
+}
+
+// What a block does with its waves' Gram matrices (u0 / u1 of WaveGram::end) and its points' two counts - eff: the lane's point is
+// effective, inr: it has a correspondence at all: the wave's matrix and counts in LDS, added in wave order, and the block row at `out`
+__device__ __forceinline__ void glin_block_tail(double u0, double u1, bool eff_pt, bool inr_pt, double (*gm)[64], double (*cnt)[2],
+                                                double *__restrict__ out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
+    if ((lane & 15) < 8) {
+        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
+        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
+    }
+    const unsigned long long eff = __builtin_amdgcn_ballot_w64(eff_pt), inr = __builtin_amdgcn_ballot_w64(inr_pt);
+    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
+    __syncthreads();
+    if (threadIdx.x < kSlots) out[threadIdx.x] = block_slot_sum(&gm[0][0], 64, cnt);
 }
 
 // What a block does with its points once glin_point has run (k_glin and k_glin_batch): the three rows of every flag-1 point through
@@ -182,7 +216,7 @@ __device__ __forceinline__ void wave_gram3_mfma(RowOf row_of, double *stage, int
 template <class Note>
 __device__ __forceinline__ void glin_block_rows(const PoseArg &P, int robust, uint8_t flag, float sx, float sy, float sz, const GlinPoint &o, double *stage,
                                                 double (*gm)[64], double (*cnt)[2], double *__restrict__ out, Note note) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63;
     auto row_of = [&](int k, double (&row)[8]) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) row[j] = 0.0;
@@ -194,15 +228,7 @@ __device__ __forceinline__ void glin_block_rows(const PoseArg &P, int robust, ui
     };
     double u0, u1;
     wave_gram3_mfma(row_of, stage, lane, u0, u1);
-    // (the wave's Gram matrix, M[a][b] at a * 8 + b, and its counts: what wave_rows_to_lds leaves)
-    if ((lane & 15) < 8) {
-        gm[wave][(lane >> 4) * 8 + (lane & 7)] = u0;
-        gm[wave][32 + (lane >> 4) * 8 + (lane & 7)] = u1;
-    }
-    const unsigned long long eff = __builtin_amdgcn_ballot_w64(flag == 1), inr = __builtin_amdgcn_ballot_w64(flag != 0);
-    if (lane == 0) { cnt[wave][0] = (double)__builtin_popcountll(eff); cnt[wave][1] = (double)__builtin_popcountll(inr); }
-    __syncthreads();
-    if (threadIdx.x < kSlots) out[threadIdx.x] = block_slot_sum(&gm[0][0], 64, cnt);
+    glin_block_tail(u0, u1, flag == 1, flag != 0, gm, cnt, out);
 }
 #endif  // !DCREG_HOST_EMUL
 

@@ -616,7 +616,8 @@ int dcreg_register_frames_gicp(dcreg_ctx *ctx, int n_frames, const float *xyz, c
 
 // The fourth engine's forms (include/dcreg.h): the same checks and the same core with the launches of voxel_icp.hip.  "voxels_source_cov"
 // is read once here: in mode 1 the frames' own normals are estimated in one batched pass behind the load, in mode 0 nothing of the kind
-// runs and frame_normals is not read.  The state refusals carry the single-pose call's text
+// runs and frame_normals is not read.  "voxels_neighbors" needs nothing here: the launches read it (voxel_icp.hip vlin_stencil), and no
+// option can change while a call runs, so it too holds from the call's start.  The state refusals carry the single-pose call's text
 static const char *const kNoKeptVoxels = "no kept voxels: dcreg_target_voxels_keep first";
 int dcreg_icp_run_trials_voxels(dcreg_ctx *ctx, int n_trials, const double *R0, const double *t0, int detection, int handling,
                                 const dcreg_config *cfg, dcreg_trial_result *results) {

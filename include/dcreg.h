@@ -1155,10 +1155,31 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  * neighbour states, the window index or the map's kept normals: it may be interleaved with every other engine's calls without moving a
  * bit on either side.  DCREG_E_INVALID: null arguments, a non-finite pose, a parameterization other than SO3.  DCREG_E_STATE: no target,
  * no source, no kept voxels, in mode 1 no kept source normals, a linearisation in flight.  Waits for the stream.
+ *
+ * Neighbour-voxel correspondences.  Option "voxels_neighbors" = S, S = 1 (default), 7 or 27 (any other value: DCREG_E_INVALID, the old
+ * value stays), read at every call with the options above: a point is matched to the kept voxels of a stencil around its own, S
+ * correspondences per point with three rows each.  With S = 1 every byte is the rule above.  Everything not named here is the rule above:
+ *   - q and v are formed as above.  The stencil is a fixed list of integer offsets o_j, j = 0..S-1.  S = 7: (0,0,0), (+1,0,0), (-1,0,0),
+ *     (0,+1,0), (0,-1,0), (0,0,+1), (0,0,-1).  S = 27: (0,0,0) first, then the other 26 offsets of the 3 x 3 x 3 block in ascending
+ *     (dz, dy, dx);
+ *   - correspondence j is the kept voxel at u = v + o_j, the sum formed in double before the box test: a u outside the map's voxel box
+ *     answers "none" without reading the table (so the key is never formed from a negative difference), and a v that is not finite
+ *     gives no correspondence at all;
+ *   - every correspondence has its own flag: 0 no kept voxel at u, 3 (mode 1) the point has no source normal - every found voxel of that
+ *     point gets flag 3 - 5 not positive definite, 1 effective.  S_ab, its Cholesky factor, W, e = (double)q - (double)mu_j and the
+ *     three rows are formed per correspondence, exactly as above, from that voxel's record;
+ *   - mode 1: the source normal m and u = R m are the point's own, read and formed once, not per neighbour;
+ *   - with a robust kernel on there is one factor k_j per correspondence, from that correspondence's own squared Mahalanobis distance,
+ *     applied to slots 0..6 of its three rows;
+ *   - the sums are over all rows of all flag-1 correspondences, in the fixed order (point, j, row k) within a lane - pass 3 j + k of the
+ *     wave's accumulation - and without floating-point atomics.  n_pt counts the points with at least one flag != 0, n_eff the points
+ *     with at least one flag 1: both count points, not rows or correspondences.
+ * The correspondences are not weighted: every effective one adds its full Mahalanobis distance.  A neighbour voxel's thin Gaussian then
+ * pulls as hard as the point's own, so S > 1 is meant to run in mode 1 or under a robust kernel (DESIGN.md section 24 has the figures).
  * The batched forms - many trials of the own source, many frames, many scan pairs with a voxel map per target - are
  * dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels and dcreg_register_pairs_voxels below (the engine is density-hungry on
  * scan-sized targets: DESIGN.md sections 21 to 23).
- * Not provided: neighbour-voxel correspondences (7 / 27 voxels per point), a voxel map that follows map updates, sharded / Euler forms,
+ * Not provided: correspondences weighted by the voxel's point count, a voxel map that follows map updates, sharded / Euler forms,
  * a caller-supplied voxel map, the runner's YAML. */
 typedef struct dcreg_voxel_map_params {
     double leaf;      /* voxel edge, metres (default 1.0) */
@@ -1270,7 +1291,7 @@ int dcreg_icp_run_gicp(dcreg_ctx *, const double R0[9], const double t0[3], int 
                        const dcreg_config *, dcreg_iter_log *log, int log_capacity, dcreg_icp_result *);
 
 /* The same loop with dcreg_linearize_voxels as its linearisation (dcreg_target_voxels_keep first, DCREG_E_STATE without it; with
- * "voxels_source_cov" = 1 kept source normals too): one waited launch per iteration, the same aborts, fitness, convergence test, log
+ * "voxels_source_cov" = 1 kept source normals too; "voxels_neighbors" is read once when the call starts): one waited launch per iteration, the same aborts, fitness, convergence test, log
  * records, covariance and status codes, the same host step.  rmse is the RMS Mahalanobis distance per effective point, as for
  * dcreg_icp_run_gicp.  Of the configuration's linearisation parameters none is read.  One pose per call (many at once:
  * dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels); no sharded / RCCL or Euler form of this engine. */
@@ -1400,7 +1421,7 @@ int dcreg_icp_run_trials_gicp(dcreg_ctx *, int n_trials, const double *R0_9, con
  * step), final_rmse, final_fitness (of the frame's own point count), corr_num, H_upper and degenerate_mask; for trials,
  * dcreg_icp_run_voxels of the context's own source from each pose.  A frame with fewer than 10 effective points (points that fall into a kept
  * voxel) ends with status 1.
- * "voxels_source_cov" is read once when the call starts.  Mode 0: frame_normals is not read and may be NULL, no normals pass runs, and
+ * "voxels_source_cov" and "voxels_neighbors" are read once when the call starts.  Mode 0: frame_normals is not read and may be NULL, no normals pass runs, and
  * the map needs no kept normals.  Mode 1, frames form: frame_normals is checked as dcreg_register_frames_gicp checks it (DCREG_E_INVALID,
  * before the empty call returns), and all frames' normals are then estimated in one batched pass behind the load
  * (dcreg_frames_normals_keep); a frame with fewer than k points has no normals and ends with status 1.  Mode 1, trials form: no kept
@@ -1475,7 +1496,7 @@ int dcreg_register_pairs_gicp(dcreg_ctx *, int n_pairs, const float *src_xyz, co
  * dcreg_target_voxels_keep(target_voxels) + dcreg_set_source(source p) [+ dcreg_source_normals_keep(source_normals) in mode 1] +
  * dcreg_icp_run_voxels(R0 p, t0 p): final_transform, iterations, converged, status, final_rmse, final_fitness, corr_num, H_upper and
  * degenerate_mask; errors against cfg->gt_matrix.  cfg->search_radius is not read by this engine.
- * "voxels_source_cov" is read once when the call starts; "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" at every launch, as in
+ * "voxels_source_cov" and "voxels_neighbors" are read once when the call starts; "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" at every launch, as in
  * the frames form.  Mode 0: source_normals is not read and may be NULL, no normals pass runs.  Mode 1: source_normals is checked as
  * dcreg_register_pairs_gicp checks it, and all sources' normals are estimated once per call in one batched pass; a source with fewer
  * than k points has no normals and ends with status 1.

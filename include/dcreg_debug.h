@@ -74,7 +74,12 @@ int dcreg_linearize_gicp_debug(dcreg_ctx *, const double R[9], const double t[3]
  * position in dcreg_target_voxels_get order, -1 for flag 0.  mean / cov: the voxel's record widened to double, for every point with a
  * voxel.  normal_src: the point's own kept normal as stored (with its non-finite components), in mode 1 for every point with a voxel.
  * For flag 1: w = the whitening matrix W = L^-1 row-major (its upper triangle 0), r = the three whitened residuals, row = the three rows
- * [A0..A5, -r_k, r_k] (scaled where a robust kernel is on); everything else is 0. */
+ * [A0..A5, -r_k, r_k] (scaled where a robust kernel is on); everything else is 0.
+ * With "voxels_neighbors" = S > 1 every array but normal_src holds S entries per point, one per correspondence in stencil order:
+ * correspondence j of point i is entry i*S + j - voxel_idx[n*S], flag[n*S], mean[3*n*S], cov[6*n*S], w[9*n*S], r[3*n*S], row[3*8*n*S] -
+ * each with the correspondence's own flag and the meaning above (voxel_idx -1 where the stencil's voxel is not kept or lies outside the
+ * map's box).  normal_src stays per point, [3*n]: in mode 1 the normal of every point with at least one correspondence.  The sizes
+ * below are those of S = 1; the caller sizes the arrays for the value of the option in force at the call. */
 typedef struct dcreg_vlin_debug {
     int32_t *voxel_idx;  /* [n] */
     uint8_t *flag;       /* [n] */
@@ -251,7 +256,7 @@ int dcreg_normal_params_check(dcreg_ctx *, const dcreg_normal_params *);
  * It runs in the two launch slots of dcreg_normals_batch_begin - they ARE the second engine's: a pending slot of any of the three
  * engines refuses the others, and every call that dcreg_normals_batch_begin's pending slot refuses (dcreg_set_source*,
  * dcreg_target_voxels_keep / _drop, dcreg_linearize_voxels, dcreg_frames_load, the map updates, ...) is refused meanwhile; _end waits for
- * that slot's results only.  "voxels_source_cov", "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at _begin.  Of the
+ * that slot's results only.  "voxels_source_cov", "voxels_neighbors", "gicp_epsilon", "robust_kernel" and "gicp_robust_scale" are read at _begin.  Of the
  * parameter block only parameterization is read (search_radius is not, as in the single-pose call).  The launch neither reads nor writes
  * warm words, warm slots or neighbour states, the window index (it is neither made active nor deactivated) or the map's kept normals.
  * Refusals, in this order, nothing queued on any: a null context, a bad slot, null R9 / t3 / parameters or n_poses < 1, n_poses > 65535
