@@ -2580,7 +2580,8 @@ class Context:
         """dcreg_launch_series (dcreg_debug.h; option "record_launches"): per completed launch its HIP-event time (ms, -1 = untimed),
         points searched, points refitted and points linearised, which pass ran in front (dcreg_launch_series_passes: 0 / 1 / 2),
         whether the linearisation kernel ran in one-wave blocks and which kernels carried the launch out (dcreg_launch_series_structure:
-        0 the linearisation kernel alone, 1 a pass and the kernel behind it, 2 the advance pass alone) -> dict of arrays"""
+        0 the linearisation kernel alone, 1 a pass and the kernel behind it, 2 the advance pass alone; its bit 2 comes back as "five":
+        1 where the launch was a five-neighbour launch, option "search_five") -> dict of arrays"""
         lp = C.POINTER(C.c_int64)
         n = self._L.dcreg_launch_series(self._h, None, None, None, None, 0, 0)
         if n < 0:
@@ -2595,7 +2596,7 @@ class Context:
         if hasattr(self._L, "dcreg_launch_series_structure"):
             self._L.dcreg_launch_series_structure(self._h, st.ctypes.data_as(C.POINTER(C.c_uint8)), n)
         self._L.dcreg_launch_series(self._h, _dp(ms), se.ctypes.data_as(lp), rf.ctypes.data_as(lp), pt.ctypes.data_as(lp), n, int(reset))
-        return {"ms": ms, "searched": se, "refitted": rf, "points": pt, "advanced": adv & 3, "one_wave": (adv >> 2) & 1, "structure": st}
+        return {"ms": ms, "searched": se, "refitted": rf, "points": pt, "advanced": adv & 3, "one_wave": (adv >> 2) & 1, "structure": st & 3, "five": (st >> 2) & 1}
 
     def team_pass_stamps(self):
         """dcreg_team_pass_stamps (option "team_stamps"): [n_blocks, 8] shader-clock words of the last launch that ran the small-frame pass"""

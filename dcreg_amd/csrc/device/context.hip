@@ -1592,6 +1592,7 @@ struct LinLaunch {
     const uint2 *d_slices;              // frames: {first point, points} of every pose's frame (kernels.hpp k_lin SLICE)
     const uint32_t *d_grid_ids;         // pairs: every pose's target grid (kernels.hpp k_lin GRIDS)
     bool state_was_valid;               // the ctx's own state held a search before this launch (restored if a gated launch is called off)
+    bool state_was_five;                // ... left by a five-neighbour launch (dcreg_ctx::state_five)
     bool own() const { return kind >= LinKind::single; }
     bool uses_state(const dcreg_ctx *c) const { return own() && c->opt_warm; }
 };
@@ -1700,7 +1701,11 @@ static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
     // the rows itself beats k_lin alone by 6 us and more).  Scheduling only: the sums are the same with and without the pass.
     if ((L.kind == LinKind::single || L.kind == LinKind::gated) && c->opt_warm && !fresh && P.use_cert && L.a.count_scale != 0.0) {
         constexpr double kAdvanceLo = 0.005, kAdvanceHi = 0.70;
-        const bool adv = c->opt_advance >= 2 || (c->opt_advance == 1 && P.nbx >= (uint32_t)c->opt_advance_min_blocks && known && f >= kAdvanceLo && f <= kAdvanceHi);
+        // (the two launches behind the end of a series of five-neighbour launches: what the last completed launch searched - everything,
+        //  by construction - says nothing about them; the series ended because the pose has nearly settled, the first six-neighbour
+        //  launch has left fresh certificates, and a fifth to a half of the points is what such a launch searches: inside the window)
+        const bool in_window = (known && f >= kAdvanceLo && f <= kAdvanceHi) || c->five_tail > 0;
+        const bool adv = c->opt_advance >= 2 || (c->opt_advance == 1 && P.nbx >= (uint32_t)c->opt_advance_min_blocks && in_window);
         // ... its small-frame form (k_advance_team: sixteen lanes per query, one wave per kTeamTile points): a frame of a few thousand
         // points, whose query blocks leave most of the device idle, in a launch expected to search most of its points (the pass costs
         // ~12 us whatever it finds to do; k_lin alone gets cheaper as its searching waves thin out, so below half it wins again)
@@ -1712,6 +1717,7 @@ static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
         const bool team = c->opt_team_pass >= 2 || (c->opt_team_pass == 1 && L.n <= (int64_t)kTeamPassMaxPoints && known && f >= kTeamPassMinFrac &&
                                                     per_cell >= kTeamPassMinCellPts);
         P.pass = team ? LinPass::team : adv ? LinPass::advance : LinPass::none;
+        if (c->opt_search_five >= 2 && c->opt_advance < 2 && c->opt_team_pass < 2) P.pass = LinPass::none;    // (tests: five-neighbour launches wherever possible)
     }
     // the one-wave instantiation of k_lin (kernels.hpp): fused single-pose launches of many blocks in which most waves search
     bool one_wave = false;
@@ -1739,6 +1745,20 @@ static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
     // the pass carries the launch out alone (kernels.hpp k_advance ROWS: the rows of a tile by the block that worked its list off, no k_lin
     // behind it) wherever k_lin would run as the plain fused kernel behind it; direct launches keep the two kernels (option "advance_fused")
     P.pass_rows = P.pass == LinPass::advance && c->opt_advance_fused != 0 && !P.direct && P.body == LinBody::fused;
+    // A five-neighbour launch (kernels.hpp k_lin FIVE)?  What a six-neighbour search leaves for the NEXT launch - the sixth neighbour, the
+    // bound of the seventh, the certificate, the plane - is used only if the pose then moves by less than a certificate's radius: a few
+    // per cent of the point spacing.  While a trajectory still moves by more than that per launch, every launch searches every point and
+    // that part of its work is wasted.  Where it can run: a single pose on the ctx's own state, carried out by the fused or the one-wave
+    // k_lin alone (no pass in front, not gated in the kernel, no dump).  By the rule (option "search_five" = 1) on an engine's trajectory
+    // only - the first launch of a run the engine announced (dcreg_hint_misalignment(-1)) and the launches queued behind a gate -, when
+    // the last completed launch searched at least 95 % of its points (in the engines' pipeline: the launch two back) and the last step
+    // known exceeds "search_five_step" cell edges (profiles/five_mode_ab.md has the table both numbers come from).  A five-neighbour launch
+    // reports every point as searched, so it is the step that ends the series.  Scheduling only: the sums are bitwise the same.
+    const bool can_five = (L.kind == LinKind::single || L.kind == LinKind::gated) && L.uses_state(c) && !dbg && P.pass == LinPass::none &&
+                          (P.body == LinBody::fused || P.body == LinBody::one_wave);
+    P.five = can_five && (c->opt_search_five >= 2 ||
+                          (c->opt_search_five == 1 && P.use_cert && (fresh || (known && f >= c->opt_search_five_frac)) &&
+                           c->last_step > c->opt_search_five_step * c->map.grid.h));
     return P;
 }
 
@@ -1865,7 +1885,8 @@ static int lin_reserve(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P)
         if (dbg->stamps) dd.stamps = (unsigned long long *)alloc(sizeof(unsigned long long) * 8 * (kLinBlock / 64) * (size_t)P.nbx, 0);
         if (oom) { free_tmp(S); drop_warm(c); c->fail("hipMalloc of the debug dump buffers failed"); return DCREG_E_NOMEM; }
     }
-    L.a.use_cert = P.use_cert ? 1 : 0;
+    // (a five-neighbour launch on a state whose last launch was one too: every certificate has radius zero - nothing to load or test)
+    L.a.use_cert = (P.use_cert && !(P.five && c->state_five && L.state_was_valid)) ? 1 : 0;
     L.a.search_count = c->opt_count_searches ? c->d_search_count.data() : nullptr;
     L.a.group_blocks = std::max<uint32_t>(c->group_blocks, 1u); L.a.n_groups = P.ordered ? c->n_groups : 0u;
     std::memcpy(L.a.group_order, c->group_order, sizeof(L.a.group_order));
@@ -1882,6 +1903,9 @@ static LinKernel lin_kernel(const LinPlan &P) {
         if (P.body == LinBody::gated) return k_lin<0, true, FAST, true>;         // (MODE 0: a gated launch is never a dump)
         if (P.body == LinBody::stamps) return k_lin<2, true, FAST>;      // (the probe writes the shared state: same fit as the plain launches)
         if (P.body == LinBody::dump) return k_lin<1, true, FAST>;
+    }
+    if constexpr (!SLICE) {
+        if (P.five) return P.one_wave() ? k_lin<0, true, FAST, false, true, false, false, true> : k_lin<0, true, FAST, false, false, false, false, true>;
     }
     if (P.one_wave()) return k_lin<0, true, FAST, false, true, SLICE, GRIDS>;
     return P.fused() ? k_lin<0, true, FAST, false, false, SLICE, GRIDS> : k_lin<0, false, FAST, false, false, SLICE, GRIDS>;
@@ -1969,12 +1993,18 @@ static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
         if (ce != hipSuccess) { (void)hipStreamSynchronize(c->stream); return bail("copying the debug dump back", ce); }
     }
     c->n_launches += 1; c->n_poses_launched += P.n_poses; c->n_points_launched += (int64_t)P.n_poses * L.n;
-    if (L.uses_state(c)) c->state_valid = true;          // once this launch has run, the state holds a search of the current clouds
+    if (L.uses_state(c)) {
+        // (lin_plan's advance rule: the first six-neighbour launch the rule puts behind five-neighbour launches, and the two after it)
+        if (P.five) c->five_tail = 0;
+        else if (c->opt_search_five == 1 && L.state_was_valid && L.state_was_five) c->five_tail = 2;
+        else if (c->five_tail > 0) c->five_tail -= 1;
+        c->state_valid = true; c->state_five = P.five;       // once this launch has run, the state holds a search of the current clouds
+    }
     S.pending = true; S.plan = P; S.timed = timed; S.seq = seq; S.sync = L.dbg != nullptr;
     S.coded = L.a.count_scale != 0.0;        // how THIS launch's count slots are to be read (the source may be replaced while it is pending)
     if (gated) {
         c->gate_slot = L.slot;
-        c->gate_uses_state = L.uses_state(c); c->gate_state_was_valid = L.state_was_valid;
+        c->gate_uses_state = L.uses_state(c); c->gate_state_was_valid = L.state_was_valid; c->gate_state_was_five = L.state_was_five;
     }
     return DCREG_OK;
 }
@@ -2009,6 +2039,9 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     L.key.radius_sq_f = a.radius_sq_f; L.key.cert_r_out = a.cert_r_out; L.key.cert_r_in = a.cert_r_in; L.key.fast_plane = c->opt_fast_plane ? 1 : 0;
     if (L.own() && !gated) {
         const double jump = c->last_pose_valid ? pose_jump(c, L.R9, L.t3, c->last_R, c->last_t) : 1e300;
+        // (five-neighbour launches, lin_plan: a launch the engine announced as the start of a run is a step of a trajectory, as long as
+        //  its pose; anything else is a call nobody said anything about)
+        c->last_step = c->hint_unknown ? jump : 0.0;
         if (c->hint_unknown && jump <= 0.5 * c->map.grid.h) c->hint_misalign = c->hint_last;      // the same trajectory, continued
         // ... and what the last completed launch searched says nothing about a launch half a cell or more away from it (the first
         // launch of a new run): expect a search of everything - for this launch and for the one that may be queued behind it before
@@ -2031,7 +2064,7 @@ static int linearize_begin(dcreg_ctx *c, int slot, int n_poses, const double *R9
     }
     // the ctx's own state (single-pose kinds)
     if (L.uses_state(c) && !(L.key == c->state_key)) { c->state_valid = false; c->state_key = L.key; }
-    L.state_was_valid = c->state_valid;
+    L.state_was_valid = c->state_valid; L.state_was_five = c->state_five;
     L.one.state = kNoIdx; L.one.fresh = 1;
     if (L.own()) {
         std::memcpy(L.one.R, L.R9, sizeof(L.one.R)); std::memcpy(L.one.t, L.t3, sizeof(L.one.t));
@@ -2361,6 +2394,9 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "team_stamps") c->opt_team_stamps = v != 0.0;   // timing probe of the small-frame pass (dcreg_team_pass_stamps)
     else if (k == "team_pass") c->opt_team_pass = (int)v;        // the small-frame advance pass: 0 never, 1 (default) by the host's rule, 2 whenever possible
     else if (k == "advance_min_blocks") c->opt_advance_min_blocks = (int)v;   // ... and the cloud has at least this many query blocks
+    else if (k == "search_five") c->opt_search_five = (int)std::min(std::max(v, 0.0), 2.0);     // five-neighbour launches: 0 never, 1 (default) by the rule of lin_plan, 2 wherever possible
+    else if (k == "search_five_step") c->opt_search_five_step = std::max(v, 0.0);             // ... the rule's step, in cell edges
+    else if (k == "search_five_frac") c->opt_search_five_frac = std::min(std::max(v, 0.0), 1.0);   // ... and its searched share
     else if (k == "team_search") c->opt_team_max = (int)v;        // lanes a sparse wave serves cooperatively (0 = off, default 7)
     else if (k == "spin") c->opt_spin = v != 0.0;
     else if (k == "far_bound") c->opt_far_bound = v != 0.0;       // next dcreg_set_target: start bound of far queries from the nearest occupied cell
@@ -2718,6 +2754,7 @@ int dcreg_linearize_gate_open(dcreg_ctx *c, const double R[9], const double t[3]
         return DCREG_E_STATE;
     }
     gate_publish(c, c->gate_seq << 1, R, t);
+    c->last_step = c->last_pose_valid ? pose_jump(c, R, t, c->last_R, c->last_t) : 1e300;
     std::memcpy(c->last_R, R, sizeof(c->last_R)); std::memcpy(c->last_t, t, sizeof(c->last_t));
     c->last_pose_valid = true;
     c->gate_slot = -1;
@@ -2731,7 +2768,7 @@ int dcreg_linearize_gate_abort(dcreg_ctx *c) {
     S.pending = false;                 // no result will come; tickets_dirty stays set, so the next launch of the slot clears them
     free_tmp(S);
     // the kernels behind the gate return without touching anything: the state, its pose and the list counters are as before
-    if (c->gate_uses_state) c->state_valid = c->gate_state_was_valid;
+    if (c->gate_uses_state) { c->state_valid = c->gate_state_was_valid; c->state_five = c->gate_state_was_five; }
     c->gate_slot = -1;
     return DCREG_OK;
 }

@@ -170,10 +170,11 @@ struct LinPlan {
     bool gate_inside = false;          // the gated launch waits for its pose in its first kernel (kernels.hpp gate_wait)
     bool pass_rows = false;            // the advance pass builds the rows and finishes the launch itself: no k_lin behind it (k_advance ROWS)
     bool ordered = false, use_cert = true;   // heavy query-block groups first (LinArgs::n_groups); certificates in use (LinArgs::use_cert)
+    bool five = false;                 // a five-neighbour launch (kernels.hpp k_lin FIVE; context.hip lin_plan has the rule)
     bool fused() const { return body != LinBody::chunked; }     // the kernels sum and publish per pose (no k_finalize)
     bool one_wave() const { return body == LinBody::one_wave; }
     int passes() const { return (int)pass | (one_wave() ? 4 : 0); }   // dcreg_launch_series_passes: + 4 = k_lin ran in one-wave blocks
-    int structure() const { return pass_rows ? 2 : pass != LinPass::none ? 1 : 0; }   // dcreg_launch_series_structure
+    int structure() const { return (pass_rows ? 2 : pass != LinPass::none ? 1 : 0) | (five ? 4 : 0); }   // dcreg_launch_series_structure
 };
 
 // buffers and in-flight state of one linearisation slot
@@ -564,6 +565,7 @@ struct dcreg_ctx {
     int gate_slot = -1;                    // slot of the gated launch that still waits for its pose (-1: none)
     bool gate_uses_state = false;          // what the queued launch was built with: it reads / writes the ctx's own state,
     bool gate_state_was_valid = false;     //   and what state_valid was before it was queued (restored if it is called off)
+    bool gate_state_was_five = false;      //   ... and state_five
     static constexpr int kLinSlots = 2;
     LinSlot slots[kLinSlots];
 
@@ -625,6 +627,16 @@ struct dcreg_ctx {
     DevBuf<unsigned long long> d_team_stamps; uint32_t team_stamps_n = 0;
     DevBuf<uint32_t> d_adv_counts; bool adv_counts_dirty = true;
     int64_t n_advance_launches = 0;
+    // Five-neighbour launches (kernels.hpp k_lin FIVE): 0 never, 1 by the rule of context.hip lin_plan, 2 wherever a launch can be one
+    // (tests).  state_five: the last launch queued on the ctx's own state was one - every certificate in it has radius zero, the next
+    // five-neighbour launch does not load them.  last_step: how far the pose of the last launch of an engine's trajectory lies from the
+    // pose before it (pose_jump; 1e300 = a run starts, nothing known; 0 = no trajectory: launches nobody announced)
+    int opt_search_five = 1;
+    double opt_search_five_step = 0.04;  // the rule: the last known step exceeds this many cell edges
+    double opt_search_five_frac = 0.95;  // ... and the last completed launch searched at least this share of its points
+    bool state_five = false;
+    int five_tail = 0;                   // launches still to come whose searched share the last completed launch does not predict (lin_plan)
+    double last_step = 0.0;
     int opt_team_max = 7;          // search.hpp team_search6: waves with at most this many lanes to search serve them cooperatively
     bool opt_warm = true;          // bound each search by the previous neighbour set (same exact result, fewer cells)
     int64_t n_launches = 0, n_poses_launched = 0, n_points_launched = 0;    // dcreg_launch_stats

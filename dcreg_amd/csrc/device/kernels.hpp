@@ -504,7 +504,15 @@ static_assert(kAdvTile % kLinBlock == 0 && kAdvTile <= 65536, "a tile is a whole
 // GRIDS: every pose also searches a target index of its own (dcreg_register_pairs: many scan pairs, each against its own target) -
 // grids[grid_ids[pose]] holds its grid, the rings that cover the search bound in that grid's cells and the pruning cap sized for them; the
 // block takes them before anything else and runs as a SLICE block against that grid.  Group dispatch order is never used (n_groups = 0).
-template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false, bool SLICE = false, bool GRIDS = false>
+// FIVE: a five-neighbour launch (the host's rule: context.hip lin_plan, option "search_five") - for launches in which nearly every point is
+// searched and the pose still moves by far more than a certificate's radius, so that what a six-neighbour search leaves behind for the next
+// launch would not be used.  Level 1 keeps five neighbours (search.hpp lin_search5: no sixth, no bound for the seventh, no inflation, no
+// certificate), level 2 fits those five, and the state receives the five positions (the sixth: kNoIdx) and V0 with a certificate of radius
+// zero - "valid now, search again next time" - and no fit word; V1, V2 and W3 are not written.  A point is at level 3 (its stored plane)
+// where certificate AND fit word hold, and is searched otherwise.  The rows depend on the set of the five nearest alone, so the 31 sums are
+// bitwise those of the six-neighbour launch.  (With a.use_cert = 0 - the launch before this one on the state was a FIVE launch too, there is
+// nothing to test - the 56 B of certificate and plane per point are not loaded either.)
+template <int MODE, bool FUSED, bool FAST, bool GATE = false, bool ONE = false, bool SLICE = false, bool GRIDS = false, bool FIVE = false>
 static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin(const float4 *__restrict__ src, uint32_t n_src, GridDev g,
                                                           PoseArg pose1, const PoseArg *__restrict__ poses, LinArgs a,
                                                           double *__restrict__ partials, uint32_t n_blocks_x, FinArgs fin,
@@ -515,6 +523,7 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
     static_assert(!ONE || (MODE == 0 && FUSED && !GATE), "the one-wave instantiation is the fused product launch behind k_gate");
     static_assert(!SLICE || (MODE == 0 && !GATE), "per-pose source slices are batched product launches");
     static_assert(!GRIDS || SLICE, "per-pose target grids come with per-pose source slices");
+    static_assert(!FIVE || (MODE == 0 && FUSED && !GATE && !SLICE), "five-neighbour launches are fused single-pose product launches");
     if constexpr (GRIDS) {                           // (uniform per block)
         const PairGrid &pg = grids[grid_ids[blockIdx.y]];
         g = pg.g; a.max_ring = pg.max_ring; a.infl_max_d2 = pg.infl_max_d2;
@@ -591,8 +600,10 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
     const float q0x = __uint_as_float(q0[0]), q0y = __uint_as_float(q0[1]), q0z = __uint_as_float(q0[2]);
     // three levels: (1) the set certificate fails -> search; (2) it holds but the fit certificate does not -> gather the known
     // neighbours, order, fit; (3) both hold -> the stored plane.  OUT certificates: nothing to do at all.
-    const bool need = have_q && !(CERT && cert_holds(cert, q0x, q0y, q0z, qx, qy, qz));
-    bool refit = have_q && !need && !cert_is_out(cert) && !fit_holds(fitw, q0x, q0y, q0z, qx, qy, qz);
+    // (FIVE: no level 2 of its own - a point whose certificate holds and whose fit word does not is searched like the rest)
+    const bool need = have_q && !(CERT && cert_holds(cert, q0x, q0y, q0z, qx, qy, qz) &&
+                                  (!FIVE || cert_is_out(cert) || fit_holds(fitw, q0x, q0y, q0z, qx, qy, qz)));
+    bool refit = !FIVE && have_q && !need && !cert_is_out(cert) && !fit_holds(fitw, q0x, q0y, q0z, qx, qy, qz);
     uint32_t stats = 0;
     uint32_t w_search = 0, w_refit = 0;             // lanes of this wave that were searched / only refitted (uniform)
     uint32_t adv_s = 0, adv_r = 0;                  // ... and what the advance pass in front of this launch did for this block's points
@@ -635,7 +646,7 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
             }
             bool by_team = false;                   // uniform: the team served every lane that had to be searched
             // a wave with a few lanes to search, each of them near its old neighbours: the 64 lanes serve one query at a time
-            if (warm && w_search <= (uint32_t)a.team_max) {
+            if (!FIVE && warm && w_search <= (uint32_t)a.team_max) {
                 float tb = 0.f;
                 bool tight = false;
                 if (need && pos6[5] != kNoIdx) tb = team_bound(g, a, pos6, qx, qy, qz, tight);
@@ -652,7 +663,20 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
                 }
             }
             // (all or nothing: a team result kept alive across the lock-step search would cost that search registers)
-            if (!by_team) {
+            if constexpr (FIVE) {
+                Set5 s5;
+                lin_search5<kLinSweep, kLinDepth>(g, runs[wave], a, need, warm, pos6, qx, qy, qz, s5);
+                if (need) {
+                    // the radius gate of the fit (search.hpp fit_from_points, :1726) on the search's own fifth distance - the float the fit
+                    // would compute again: beyond it (or fewer than five inside the bound) the point is OUT, as a six-neighbour launch finds
+                    const bool in5 = s5.pos[4] != kNoIdx && (double)s5.d2[4] < a.radius_sq;
+                    cert = in5 ? 0u : 0x80000000u;              // radius zero either way: searched again by the next launch
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) pos6[j] = s5.pos[j];
+                    pos6[5] = kNoIdx;
+                    stats = (s5.n_eval & 0xFFFFu) | ((s5.n_shell & 0x7FFFu) << 16);
+                }
+            } else if (!by_team) {
                 Set6 s6;
                 uint32_t c2;
                 lin_search6<kLinSweep, kLinDepth>(g, runs[wave], a, need, warm, pos6, qx, qy, qz, s6, c2);
@@ -676,9 +700,9 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
         if (wave_any(fitnow)) {
             // a SET6 certificate says nothing about which five of the six are nearest: the fit certificate must then cover the gap
             // between the 5th and the 6th itself, i.e. the fit works on all six
-            const bool use6 = fitnow && cert_is_set6(cert);
+            const bool use6 = !FIVE && fitnow && cert_is_set6(cert);
             const bool six = wave_any(use6);
-            const bool presorted = !wave_any(fitnow && !need);     // every lane that fits was searched just now: its six are in order
+            const bool presorted = FIVE || !wave_any(fitnow && !need);     // every lane that fits was searched just now: its six are in order
             if (fitnow && !need) {
                 const uint4 x = SX[iw];
                 const uint2 y = SY[iw];
@@ -694,10 +718,14 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
                         const uint32_t o1 = SW3[iw];
                         cert = cert_rebased(cert, __uint_as_float(o0.z), __uint_as_float(o0.w), __uint_as_float(o1), qx, qy, qz);
                     }
+                    if constexpr (FIVE) {
+                        SV0[iw] = make_uint4(cert, kFitNone, __float_as_uint(qx), __float_as_uint(qy));
+                    } else {
                     SV0[iw] = make_uint4(cert, fit.word, __float_as_uint(qx), __float_as_uint(qy));
                     SV1[iw] = dbl2{fit.plane[0], fit.plane[1]};
                     SV2[iw] = dbl2{fit.plane[2], fit.plane[3]};
                     SW3[iw] = __float_as_uint(qz);
+                    }
                 }
             }
         }
@@ -709,7 +737,7 @@ static __global__ __launch_bounds__(ONE ? kWave : kLinBlock, kLinOcc) void k_lin
         }
         if (!set && need && keep) {                 // searched and found OUT: certificate and reference position, no fit
             SV0[iw] = make_uint4(cert, kFitNone, __float_as_uint(qx), __float_as_uint(qy));
-            SW3[iw] = __float_as_uint(qz);
+            if constexpr (!FIVE) SW3[iw] = __float_as_uint(qz);
         }
     }
     double nrm[3] = {0.0, 0.0, 0.0}, r_pt = 0.0, s_pt = 0.0;

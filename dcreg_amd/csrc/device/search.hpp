@@ -16,6 +16,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 #if defined(DCREG_HOST_EMUL)
 #define DCREG_DEVFN inline
 #define DCREG_ON_DEVICE 0
@@ -329,6 +330,22 @@ struct Top6 {
     }
 };
 
+// ... and the five smallest (lin_search5's probe)
+struct Top5 {
+    static constexpr int K = 5;
+    float d[5];
+    uint32_t n_eval, n_shell;
+    DCREG_DEVFN void init(float bound_f) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) d[i] = bound_f;
+        n_eval = 0; n_shell = 1;
+    }
+    DCREG_DEVFN void push(float x, uint32_t /*idx*/, uint32_t /*p*/, bool /*valid*/ = true) {
+        d[4] = med3f(d[3], d[4], x); d[3] = med3f(d[2], d[3], x);
+        d[2] = med3f(d[1], d[2], x); d[1] = med3f(d[0], d[1], x); d[0] = fminf(d[0], x);
+    }
+};
+
 // float32, NOT contracted to FMA: must round exactly like the oracle's / FLANN's plain mul+add chain
 DCREG_DEVFN float dist2_nofma(float qx, float qy, float qz, const float4 &c) {
 #pragma clang fp contract(off)
@@ -366,7 +383,7 @@ DCREG_DEVFN float sqrt_approx(float x) {
 }
 
 struct RunList;
-template <class H, bool SWEEP, bool NOTE>
+template <class H, bool SWEEP, bool NOTE, bool INCL = false>
 DCREG_DEVFN void knn_shells(const GridDev &g, RunList &rl, float qx, float qy, float qz, int cx, int cy, int cz,
                                            double fx, double fy, double fz, float bound_f, int max_ring, H &hp);
 
@@ -443,7 +460,7 @@ DCREG_DEVFN void scan_run(const GridDev &g, uint32_t s, uint32_t e, float qx, fl
 // - one compare instead of the sorted insertion - and, if it passes, parked in the lane's pending list; the list
 // is pushed into the heap when some lane runs out of room and at the end of the run.  Pushes happen in scan order and everything
 // that was filtered out is noted as "seen and not kept", so heap, tie flag and 7th-neighbour bound come out as with scan_run.
-template <class H, bool NOTE>
+template <class H, bool NOTE, bool INCL = false>
 DCREG_DEVFN void scan_run_deferred(const GridDev &g, RunList &rl, uint32_t s, uint32_t e, float qx, float qy, float qz, H &hp) {
     DCREG_STAT(runs);
     const int tid = threadIdx.x & (kWave - 1);
@@ -468,7 +485,7 @@ DCREG_DEVFN void scan_run_deferred(const GridDev &g, RunList &rl, uint32_t s, ui
         for (int u = 0; u < 4; ++u) {
             const float d2 = dist2_nofma(qx, qy, qz, c[u]);
             const bool valid = p + u < e;
-            const bool pass = valid && d2 < lim;
+            const bool pass = valid && (INCL ? d2 <= lim : d2 < lim);
             hp.n_eval += valid ? 1u : 0u;
             if (pass) { rl.pend[cnt][tid] = PendEntry{__float_as_uint(d2), p + u}; ++cnt; }
             if (NOTE) om = fminf(om, (valid && !pass) ? d2 : __builtin_inff());
@@ -504,7 +521,11 @@ DCREG_DEVFN void scan_run_deferred(const GridDev &g, RunList &rl, uint32_t s, ui
 // DEPTH: register sets of the candidate loop's software pipeline, i.e. trips whose loads are in flight while one is consumed (2: what a
 // kernel at four waves per SIMD can afford; 4: the instantiations whose launches leave the SIMDs nearly empty and last as long as one
 // wave's chain of round trips - the advance pass).  The scan order - and with it every result - does not depend on it.
-template <class H, bool SWEEP = false, bool NOTE = true, int DEPTH = 2>
+// INCL (with NOTE = false; search5): the deferred insertion lets a candidate AT the pruning distance through to the heap instead of
+// noting what it filters out.  What it still filters out lies strictly beyond the pruning distance of its moment, hence strictly beyond
+// the final K-th best: it cannot tie with it; what it lets through and the heap turns away is noted there (HeapFast::push), so the
+// boundary-tie test stays exact - one compare per candidate instead of three instructions, and no register for the minimum.
+template <class H, bool SWEEP = false, bool NOTE = true, int DEPTH = 2, bool INCL = false>
 DCREG_DEVFN void knn_search(const GridDev &g, RunList &rl, float qx, float qy, float qz, float bound_f,
                                            int max_ring, H &hp, float infl = 1.f, float cap = __builtin_inff(), bool empty_block = false) {   // max_ring < 0: unbounded
     hp.init(bound_f, infl, cap);
@@ -634,7 +655,7 @@ DCREG_DEVFN void knn_search(const GridDev &g, RunList &rl, float qx, float qy, f
                 for (int u = 0; u < W; ++u) {
                     const float d2 = dist2_nofma(qx, qy, qz, sl.c[u]);
                     const bool valid = sl.cp + u < sl.ce;
-                    const bool pass = valid && d2 < lim;
+                    const bool pass = valid && (INCL ? d2 <= lim : d2 < lim);
                     hp.n_eval += valid ? 1u : 0u;
                     if (pass) { rl.pend[cnt][tid] = PendEntry{__float_as_uint(d2), sl.cp + u}; ++cnt; }
                     if (NOTE) om = fminf(om, (valid && !pass) ? d2 : __builtin_inff());
@@ -661,7 +682,7 @@ DCREG_DEVFN void knn_search(const GridDev &g, RunList &rl, float qx, float qy, f
             hp.note_outside(om);
         }
     }
-    knn_shells<H, SWEEP, NOTE>(g, rl, qx, qy, qz, cx, cy, cz, fx, fy, fz, bound_f, max_ring, hp);
+    knn_shells<H, SWEEP, NOTE, INCL>(g, rl, qx, qy, qz, cx, cy, cz, fx, fy, fz, bound_f, max_ring, hp);
 }
 
 // Rings k >= 2 around cell (cx,cy,cz) (sparse neighbourhoods, cloud borders, large misalignment), global loads.
@@ -678,7 +699,7 @@ DCREG_DEVFN void knn_search(const GridDev &g, RunList &rl, float qx, float qy, f
 //     per-lane iteration order, empty-space culling per face and centre-out rows visited fewer rows
 //     and was 25 % slower; batching the table loads of four rows, a flattened collect-then-scan walk and a 2x2x2 block occupancy
 //     bitmap that spares 88 % of the table lookups were all slower too: profiles/r02_ablation.md).
-template <class H, bool SWEEP, bool NOTE>
+template <class H, bool SWEEP, bool NOTE, bool INCL>
 DCREG_DEVFN void knn_shells(const GridDev &g, RunList &rl, float qx, float qy, float qz, int cx, int cy, int cz,
                                            double fx, double fy, double fz, float bound_f, int max_ring, H &hp) {
     const int nx = g.nx, ny = g.ny, nz = g.nz;
@@ -700,7 +721,7 @@ DCREG_DEVFN void knn_shells(const GridDev &g, RunList &rl, float qx, float qy, f
     auto lookup_scan = [&](int64_t c0, int64_t c1) {
         DCREG_STAT(table_loads); DCREG_STAT(table_loads); DCREG_STAT(faces);
         const uint32_t s_ = g.cell_start[c0], e_ = g.cell_start[c1];
-        if constexpr (SWEEP && H::kDeferred) scan_run_deferred<H, NOTE>(g, rl, s_, e_, qx, qy, qz, hp);
+        if constexpr (SWEEP && H::kDeferred) scan_run_deferred<H, NOTE, INCL>(g, rl, s_, e_, qx, qy, qz, hp);
         else scan_run<H>(g, s_, e_, qx, qy, qz, hp);
     };
     // slab distance (metres, float) from the query to cell index c along an axis (cq = the query's cell, fr = the query's position
@@ -1293,6 +1314,32 @@ DCREG_DEVFN void search6(const GridDev &g, RunList &rl, float qx, float qy, floa
     }
 }
 
+// Exact 5 nearest neighbours under `bound_f` (strict), nothing beyond them: the search of a five-neighbour launch.  The walk prunes at the
+// 5th best distance itself, so whether the SET is the canonical one cannot be read off a sixth entry: it is unless some point that was
+// not kept lies at exactly the 5th best distance - a candidate the heap turned away or evicted; the deferred insertion hands it every
+// candidate at or inside the pruning distance (knn_search INCL) -, which HeapFast::boundary_tie() says exactly; then the 64-bit-key
+// search decides for this lane.
+struct Set5 {
+    uint32_t pos[5];      // positions in the sorted target, ascending distance (kNoIdx = not found inside the bound)
+    float d2[5];          // squared distances (the bound where not found)
+    uint32_t n_eval, n_shell;
+};
+template <bool SWEEP, int DEPTH = 2>
+DCREG_DEVFN void search5(const GridDev &g, RunList &rl, float qx, float qy, float qz, float bound_f, int max_ring, Set5 &out, bool empty_block = false) {
+    HeapFast<5> hf;
+    knn_search<HeapFast<5>, SWEEP, false, DEPTH, true>(g, rl, qx, qy, qz, bound_f, max_ring, hf, 1.f, __builtin_inff(), empty_block);
+    out.n_eval = hf.n_eval; out.n_shell = hf.n_shell;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { out.pos[j] = hf.pos[j]; out.d2[j] = hf.d[j]; }
+    if (hf.boundary_tie()) {
+        HeapExact<5> he;
+        knn_search<HeapExact<5>, SWEEP>(g, rl, qx, qy, qz, bound_f, max_ring, he, 1.f, __builtin_inff(), empty_block);
+        out.n_eval += he.n_eval;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) { out.pos[j] = he.pos[j]; out.d2[j] = he.dist(j); }
+    }
+}
+
 // The certificate of a search (kStateRows comment above).  a4 / a5 = distances of the 5th / 6th neighbour, a6 = the lower bound of
 // the 7th's, or - where the search found fewer inside its bound - the bound, which every point it did not return lies beyond.  All
 // distances are floats of dist2_nofma (within 3e-7 relative of the real squared distance) and of a 1-ulp square root, i.e. within
@@ -1326,32 +1373,51 @@ DCREG_DEVFN bool cert_holds(uint32_t cert, float q0x, float q0y, float q0z, floa
 }
 
 // Bound of a search from what the last one found: the 6th-neighbour distance is at most the largest distance to ANY six distinct
-// target points.  oldpos = the state's six positions (all valid).  Inclusive bound for a strict '<' heap: the next float up.
+// target points.  oldpos = the state's six positions, the first five valid.  Inclusive bound for a strict '<' heap: the next float up.
+// A state that holds five positions only (its last search was a five-neighbour launch's, or found five inside the radius) gives the
+// largest of FIVE real distances: the five nearest lie inside it, exactly what the search must return; the sixth is then found inside
+// the bound or reported as "beyond it", which is what make_cert takes for a lower bound anyway.
+constexpr float kFiveBoundGrow = 1.3f;
 DCREG_DEVFN float warm_bound6(const GridDev &g, const uint32_t (&oldpos)[6], float qx, float qy, float qz, float bound) {
     float4 pv[6];
 #pragma unroll
-    for (int j = 0; j < 6; ++j) pv[j] = g.pts[oldpos[j]];
+    for (int j = 0; j < 5; ++j) pv[j] = g.pts[oldpos[j]];
+    pv[5] = g.pts[oldpos[5] != kNoIdx ? oldpos[5] : oldpos[4]];
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < 6; ++j) m = fmaxf(m, dist2_nofma(qx, qy, qz, pv[j]));
+    // (five positions: the ball of the five would hold the sixth neighbour by chance only, and a sixth "somewhere beyond the bound" right
+    //  behind the fifth certifies next to nothing - the first six-neighbour launch after a series of five-neighbour launches would leave
+    //  certificates that fail at the next step, and the launches after it would search everything again.  The ball is widened by
+    //  kFiveBoundGrow in squared distance, 14 % in radius: the sixth neighbour on a surface lies ~10 % beyond the fifth, and where it is
+    //  not inside, "beyond 1.14 x the fifth" is a certificate as good as the average real gap)
+    if (oldpos[5] == kNoIdx) m *= kFiveBoundGrow;
+    const float incl = fmaxf(__uint_as_float(__float_as_uint(m) + 1u), 1.17549435e-38f);
+    return fminf(bound, incl);
+}
+// ... of a five-neighbour search: the largest of the distances to the five old neighbours (all valid), inclusive alike
+DCREG_DEVFN float warm_bound5(const GridDev &g, const uint32_t (&oldpos)[6], float qx, float qy, float qz, float bound) {
+    float4 pv[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) pv[j] = g.pts[oldpos[j]];
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) m = fmaxf(m, dist2_nofma(qx, qy, qz, pv[j]));
     const float incl = fmaxf(__uint_as_float(__float_as_uint(m) + 1u), 1.17549435e-38f);
     return fminf(bound, incl);
 }
 
-// search of one query inside a linearisation: bound (warm or cold), reach test, 6-NN, certificate
-template <bool SWEEP, int DEPTH = 2>
-DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, bool have_q, bool warm, const uint32_t (&oldpos)[6],
-                             float qx, float qy, float qz, Set6 &st, uint32_t &cert) {
-    float bound = a.radius_sq_f;
-    if (warm && oldpos[5] != kNoIdx) bound = warm_bound6(g, oldpos, qx, qy, qz, bound);
-    // a search whose ball is small (the query sits among its neighbours: the regime in which certificates get used) looks a little
-    // further than it must - bound and pruning distance inflated alike (HeapFast::worst_d2), so that what lies beyond is a useful
-    // lower bound for the 7th neighbour; a search over many cells (a query far from the surface it belongs to) is expensive enough
+// The start bound of a linearisation's search beyond what the old neighbours give (K = 6: lin_search6, K = 5: lin_search5): the reach
+// test and, for a query whose bound is loose, the probe of the points around the nearest occupied cell - the K-th smallest of their
+// distances is a distance K REAL points lie within.
+template <int K>
+DCREG_DEVFN void lin_start_bound(const GridDev &g, const LinArgs &a, bool have_q, float qx, float qy, float qz, float &bound, bool &reach,
+                                 bool &all_in_space) {
     const double fx = ((double)qx - g.ox) * g.inv_h, fy = ((double)qy - g.oy) * g.inv_h, fz = ((double)qz - g.oz) * g.inv_h;
     const double lim = (double)a.max_ring + 1.0;
     // a query farther than max_ring cells from the grid has no neighbour inside the search bound
-    const bool reach = have_q && !(fx < -lim || fy < -lim || fz < -lim || fx > g.nx + lim || fy > g.ny + lim || fz > g.nz + lim);
-    bool all_in_space = false;        // ... and that holds for every searching query of the wave (knn_search skips the block then)
+    reach = have_q && !(fx < -lim || fy < -lim || fz < -lim || fx > g.nx + lim || fy > g.ny + lim || fz > g.nz + lim);
+    all_in_space = false;             // ... and that holds for every searching query of the wave (knn_search skips the block then)
     if (g.owner) {
         // A query whose bound is loose (nothing known, or neighbours of a pose far from this one): the ball of that bound cuts a wide
         // cap out of the surface it faces - candidates ~ bound - d^2, hundreds where six are wanted.  The field names an occupied
@@ -1391,7 +1457,7 @@ DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, 
         if (wave_any(far)) {
             // (only the sixth smallest DISTANCE of the probed points is wanted - no positions, no tie bookkeeping: a sorted six of floats
             //  kept by the median trick of HeapFast::push, six instructions per point instead of the 25 of the full insertion network)
-            Top6 hb;
+            typename std::conditional<K == 6, Top6, Top5>::type hb;
             hb.init(bound);
             uint32_t s_ = 0, e_ = 0;
             if (far) {
@@ -1409,7 +1475,7 @@ DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, 
             // (only where the run itself was short: a run of six and more points none of which is inside the bound says the query has no
             //  six neighbours within reach here - an OUT point of a sparse map -, and four more scans per launch were a fifth of a small
             //  frame's registration)
-            bool more = far && e_ - s_ < 6u && !(hb.d[5] < bound);
+            bool more = far && e_ - s_ < (uint32_t)K && !(hb.d[K - 1] < bound);
             if (wave_any(more)) {
                 uint32_t ox = 0, oy = 0, oz = 0;
                 if (more) { ox = oc % (uint32_t)g.nx; const uint32_t r_ = oc / (uint32_t)g.nx; oy = r_ % (uint32_t)g.ny; oz = r_ / (uint32_t)g.ny; }
@@ -1426,13 +1492,26 @@ DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, 
                         }
                     }
                     scan_run<decltype(hb), kProbeBatch>(g, s2, e2, qx, qy, qz, hb);
-                    more = far && !(hb.d[5] < bound);
+                    more = far && !(hb.d[K - 1] < bound);
                 }
             }
             // (six points closer than the bound: d[5] < bound, and only then does the new bound differ from the old one)
-            if (far) bound = fminf(bound, fmaxf(__uint_as_float(__float_as_uint(hb.d[5]) + 1u), 1.17549435e-38f));   // inclusive, as warm_bound6
+            if (far) bound = fminf(bound, fmaxf(__uint_as_float(__float_as_uint(hb.d[K - 1]) + 1u), 1.17549435e-38f));   // inclusive, as warm_bound6
         }
     }
+}
+
+// search of one query inside a linearisation: bound (warm or cold), reach test, 6-NN, certificate
+template <bool SWEEP, int DEPTH = 2>
+DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, bool have_q, bool warm, const uint32_t (&oldpos)[6],
+                             float qx, float qy, float qz, Set6 &st, uint32_t &cert) {
+    float bound = a.radius_sq_f;
+    if (warm && oldpos[4] != kNoIdx) bound = warm_bound6(g, oldpos, qx, qy, qz, bound);
+    // a search whose ball is small (the query sits among its neighbours: the regime in which certificates get used) looks a little
+    // further than it must - bound and pruning distance inflated alike (HeapFast::worst_d2), so that what lies beyond is a useful
+    // lower bound for the 7th neighbour; a search over many cells (a query far from the surface it belongs to) is expensive enough
+    bool reach, all_in_space;
+    lin_start_bound<6>(g, a, have_q, qx, qy, qz, bound, reach, all_in_space);
     const float infl = a.prune_infl, cap = a.infl_max_d2 * a.prune_infl;
     bound = fminf(fmaxf(bound, fminf(bound * infl, cap)), a.radius_sq_f);
 #pragma unroll
@@ -1440,6 +1519,21 @@ DCREG_DEVFN void lin_search6(const GridDev &g, RunList &runs, const LinArgs &a, 
     st.lb7 = bound; st.n_eval = 0; st.n_shell = 1;
     if (reach) search6<SWEEP, DEPTH>(g, runs, qx, qy, qz, bound, a.max_ring, infl, cap, st, SWEEP && all_in_space);
     cert = make_cert(st, a);
+}
+
+// ... in a five-neighbour launch (kernels.hpp k_lin FIVE): the five nearest and nothing else - no sixth, no bound for the seventh, no
+// inflation, no certificate.  The warm bound is the largest of five real distances, the probe takes the fifth smallest.
+template <bool SWEEP, int DEPTH = 2>
+DCREG_DEVFN void lin_search5(const GridDev &g, RunList &runs, const LinArgs &a, bool have_q, bool warm, const uint32_t (&oldpos)[6],
+                             float qx, float qy, float qz, Set5 &st) {
+    float bound = a.radius_sq_f;
+    if (warm && oldpos[4] != kNoIdx) bound = warm_bound5(g, oldpos, qx, qy, qz, bound);
+    bool reach, all_in_space;
+    lin_start_bound<5>(g, a, have_q, qx, qy, qz, bound, reach, all_in_space);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { st.pos[j] = kNoIdx; st.d2[j] = bound; }
+    st.n_eval = 0; st.n_shell = 1;
+    if (reach) search5<SWEEP, DEPTH>(g, runs, qx, qy, qz, bound, a.max_ring, st, SWEEP && all_in_space);
 }
 
 // ---------------------------------------------------------------- wave-cooperative search of a few queries (sparse waves)

@@ -126,7 +126,8 @@ int dcreg_launch_series(dcreg_ctx *, double *ms, int64_t *searched, int64_t *ref
 int dcreg_launch_series_passes(dcreg_ctx *, uint8_t *advanced, int64_t cap);
 /* ... and which kernels carried each launch of that log out: 0 = the linearisation kernel alone, 1 = a pass and the linearisation kernel
  * behind it, 2 = the advance pass alone (kernels.hpp k_advance ROWS: it builds the rows of its tiles and finishes the launch itself;
- * option "advance_fused").  Call it before the resetting dcreg_launch_series too.  Returns the number of entries logged. */
+ * option "advance_fused").  Bit 2 (+ 4): a five-neighbour launch (option "search_five").  Call it before the resetting
+ * dcreg_launch_series too.  Returns the number of entries logged. */
 int dcreg_launch_series_structure(dcreg_ctx *, uint8_t *structure, int64_t cap);
 
 /* Timing probe of the small-frame advance pass (option "team_stamps" = 1): of the LAST launch that ran the pass, per block (one wave,
@@ -173,6 +174,13 @@ int dcreg_knn_timed(dcreg_ctx *, const float *q_xyz, int64_t n, int64_t stride_f
  *   "team_pass"          the small-frame advance pass (sixteen lanes per query) in front of single-pose launches: 0 = never, 1 (default) =
  *                        for clouds of at most 16384 points when the last completed launch searched at least half of them and the map holds
  *                        at least 3 points per occupied cell, 2 = whenever the launch can take it; "team_stamps": see dcreg_team_pass_stamps;
+ *   "search_five"        five-neighbour launches (kernels.hpp k_lin FIVE: the searches keep the five nearest and nothing for the next launch -
+ *                        no sixth neighbour, no certificate, no stored plane; the next launch on the state searches every point again):
+ *                        0 = never, 1 (default) = by the rule - on an engine's trajectory (the first launch of a run announced by
+ *                        dcreg_hint_misalignment(-1) and the launches queued behind a gate) while the last completed launch searched at
+ *                        least "search_five_frac" (0.95) of its points and the last known step of the pose exceeds "search_five_step"
+ *                        (0.04) cell edges -, 2 = every single-pose launch on the context's own state that the fused or the one-wave
+ *                        kernel carries out alone (the passes chosen by a rule give way): tests.  Scheduling only: no sum changes;
  *   "one_wave"           the linearisation kernel in one-wave blocks (a tile row per wave, k_sum_tiles behind it): 0 = never, 1 (default) =
  *                        single-pose launches of at least "one_wave_min_blocks" (1024) query blocks most of whose points are expected to
  *                        search ("one_wave_min_frac", 0.5) while the misalignment hint is above "one_wave_min_cells" (1.5) cells - the
