@@ -78,6 +78,11 @@ class VoxelMapInfo(C.Structure):       # dcreg_voxel_map_info
     _fields_ = [("n_points", C.c_int64), ("n_voxels", C.c_int64), ("n_small", C.c_int64), ("n_degenerate", C.c_int64), ("n_kept", C.c_int64)]
 
 
+class VoxelsFollowInfo(C.Structure):   # dcreg_voxels_follow_info
+    _fields_ = [("n_target", C.c_int64), ("n_touched", C.c_int64), ("n_refit", C.c_int64), ("n_carried", C.c_int64), ("n_kept", C.c_int64),
+                ("followed", C.c_int), ("reserved_", C.c_int)]
+
+
 class LaunchStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("poses", C.c_int64), ("points", C.c_int64), ("points_searched", C.c_int64),
                 ("points_team", C.c_int64)]
@@ -153,7 +158,7 @@ _STRUCTS = {"dcreg_lin_params": LinParams, "dcreg_lin_out": LinOut, "dcreg_lin_d
             "dcreg_iter_log": IterLog, "dcreg_icp_result": IcpResult, "dcreg_trial_result": TrialResult,
             "dcreg_launch_stats": LaunchStats, "dcreg_method_stats": MethodStats, "dcreg_nlin_debug": NlinDebug,
             "dcreg_glin_debug": GlinDebug, "dcreg_vlin_debug": VlinDebug, "dcreg_voxel_map_params": VoxelMapParams,
-            "dcreg_voxel_map_info": VoxelMapInfo}
+            "dcreg_voxel_map_info": VoxelMapInfo, "dcreg_voxels_follow_info": VoxelsFollowInfo}
 # (VoxelParams / VoxelInfo are defined below and join _STRUCTS there)
 
 # every symbol include/dcreg.h and include/dcreg_debug.h declare
@@ -203,6 +208,7 @@ EXPORTS = [
     "dcreg_pairs_normals_get", "dcreg_pairs_normals_kept", "dcreg_pairs_sources_normals_keep", "dcreg_pairs_sources_normals_set",
     "dcreg_pairs_sources_normals_get", "dcreg_pairs_normals_reserve_slots", "dcreg_pairs_normals_batch_begin", "dcreg_pairs_gicp_batch_begin",
     "dcreg_default_voxel_map_params", "dcreg_target_voxels_keep", "dcreg_target_voxels_get", "dcreg_target_voxels_kept", "dcreg_target_voxels_drop",
+    "dcreg_target_voxels_follow_info",
     "dcreg_linearize_voxels", "dcreg_linearize_voxels_debug", "dcreg_icp_run_voxels",
     "dcreg_voxels_batch_begin", "dcreg_voxels_batch_end", "dcreg_register_frames_voxels", "dcreg_icp_run_trials_voxels",
     "dcreg_register_pairs_voxels", "dcreg_pairs_plan_voxels", "dcreg_pairs_voxels_build", "dcreg_pairs_voxels_get", "dcreg_pairs_voxels_kept",
@@ -1173,6 +1179,8 @@ def load():
         L.dcreg_target_voxels_get.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
         L.dcreg_target_voxels_kept.argtypes = [vp]
         L.dcreg_target_voxels_drop.argtypes = [vp]
+    if hasattr(L, "dcreg_target_voxels_follow_info"):  # (likewise)
+        L.dcreg_target_voxels_follow_info.argtypes = [vp, C.POINTER(VoxelsFollowInfo)]
         L.dcreg_linearize_voxels.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut)]
         L.dcreg_linearize_voxels_debug.argtypes = [vp, dp, dp, C.POINTER(LinParams), C.POINTER(LinOut), C.POINTER(VlinDebug)]
         L.dcreg_icp_run_voxels.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.POINTER(Config), C.POINTER(IterLog), C.c_int, C.POINTER(IcpResult)]
@@ -2141,6 +2149,14 @@ class Context:
     def target_voxels_kept(self):
         """dcreg_target_voxels_kept: the number of kept voxels, 0 without a member"""
         return int(self._L.dcreg_target_voxels_kept(self._h))
+
+    def voxels_follow_info(self):
+        """dcreg_target_voxels_follow_info: what the last update that changed the map did to the kept voxel map (set_option("voxels_follow",
+        1) makes inserts and removals refit it instead of dropping it) -> dict n_target / n_touched / n_refit / n_carried / n_kept /
+        followed (0 not followed, 1 incremental, 2 the full keep)"""
+        info = VoxelsFollowInfo()
+        self._check(self._L.dcreg_target_voxels_follow_info(self._h, C.byref(info)), "dcreg_target_voxels_follow_info")
+        return {k: int(getattr(info, k)) for k, _ in VoxelsFollowInfo._fields_ if k != "reserved_"}
 
     def drop_target_voxels(self):
         self._check(self._L.dcreg_target_voxels_drop(self._h), "dcreg_target_voxels_drop")

@@ -461,6 +461,7 @@ static int target_commit(dcreg_ctx *c, int64_t n, const double box[6], double ra
     drop_warm(c);            // positions and certificates refer to the old target
     c->nicp.kept = false;    // ... and the kept normals to the old map's points
     c->vmap.kept = false;    // ... and the kept voxel map
+    c->vmap.follow = dcreg_voxels_follow_info{};
     c->nicp.follow = dcreg_normals_follow_info{};      // (a new map: no update of it yet)
     c->order_valid = false;  // ... and the cost estimate of the query groups to the old map
     c->last_pose_valid = false;
@@ -484,7 +485,7 @@ static void map_changed(dcreg_ctx *c) {
     c->roi_built = false;
     drop_warm(c);
     c->nicp.kept = false;                              // (an update that follows them puts them back: normals.hip normals_follow_update)
-    c->vmap.kept = false;                              // (nothing follows the map: the voxel map goes)
+    c->vmap.kept = false;                              // (an update that follows it puts it back: voxel.hip voxels_follow_update)
     c->nicp.follow = dcreg_normals_follow_info{c->map.n, 0, 0, 0, 0};
     c->order_valid = false;
     c->last_pose_valid = false;
@@ -710,7 +711,7 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     if (n_old + (int64_t)n_add > (int64_t)INT32_MAX) { c->fail("the map would hold more than 2^31 - 1 points"); return DCREG_E_INVALID; }
     if (n_add == 0) { update_info(info, m, 0, 0, n_old, 0); return DCREG_OK; }     // everything thinned: nothing changes
     // ---- the map changes
-    const bool follow = normals_follow_wanted(c);      // (asked before map_changed drops them)
+    const bool follow = normals_follow_wanted(c), vfollow = voxels_follow_wanted(c);      // (asked before map_changed drops them)
     (void)roi_deactivate(c);
     double box[6];
     for (int a = 0; a < 3; ++a) {
@@ -751,12 +752,11 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
         }
         map_changed(c);
     }
-    if (rc) { c->map.n = 0; return rc; }         // (a failure after a rebuild swapped its grid in: the map is gone, as after a failed dcreg_set_target)
-    if (follow) {
-        FollowChange ch;
-        ch.added = c->d_map_new.data(); ch.n_added = (int64_t)n_add;
-        normals_follow_update(c, ch);
-    }
+    if (rc) { c->map.n = 0; c->vmap.follow = dcreg_voxels_follow_info{}; return rc; }         // (a failure after a rebuild swapped its grid in: the map is gone, as after a failed dcreg_set_target)
+    FollowChange ch;
+    ch.added = c->d_map_new.data(); ch.n_added = (int64_t)n_add;
+    if (follow) normals_follow_update(c, ch);
+    voxels_follow_update(c, ch, vfollow);
     update_info(info, m, n_add, 0, c->map.n, rebuilt);
     return DCREG_OK;
 }
@@ -823,6 +823,7 @@ static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_updat
     hipLaunchKernelGGL(k_crop_raw, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, m.raw.data(), n, flag_r, pos_r, alt.raw.data());
     // the survivors' kept normals go the same way, beside the current ones (short of memory they will not follow: dropped as without the option)
     const bool follow = normals_follow_wanted(c) && normals_follow_carry(c, n, flag_r, pos_r, (int64_t)kept);
+    const bool vfollow = voxels_follow_wanted(c);
     int rebuilt = 0, rc = DCREG_OK;
     bool swapped = false;
     if (rederive) {
@@ -853,12 +854,11 @@ static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_updat
         if (rc == DCREG_OK) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { c->fail("crop: %s", hipGetErrorString(e)); rc = DCREG_E_DEVICE; } }
     }
     map_changed(c);
-    if (rc) { m.n = 0; return rc; }
-    if (follow) {
-        FollowChange ch;                               // (the map as it was is in alt.raw since the swap, its keep flags still in c->d_upd)
-        ch.old_raw = alt.raw.data(); ch.flag_r = flag_r; ch.n_old = n; ch.carried = true;
-        normals_follow_update(c, ch);
-    }
+    if (rc) { m.n = 0; c->vmap.follow = dcreg_voxels_follow_info{}; return rc; }
+    FollowChange ch;                                   // (the map as it was is in alt.raw since the swap, its keep flags still in c->d_upd)
+    ch.old_raw = alt.raw.data(); ch.flag_r = flag_r; ch.n_old = n; ch.carried = true;
+    if (follow) normals_follow_update(c, ch);
+    voxels_follow_update(c, ch, vfollow);
     update_info(info, n, 0, n - kept, m.n, rebuilt);
     return DCREG_OK;
 }
@@ -2406,6 +2406,8 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     else if (k == "map_update") c->opt_map_update = v != 0.0 ? 1 : 0;    // dcreg_target_insert / _crop: 1 merge into the current grid where possible, 0 always re-derive it
     else if (k == "normals_follow") c->opt_normals_follow = v != 0.0 ? 1 : 0;   // map updates refit the kept normals of dcreg_target_normals_keep instead of dropping them
     else if (k == "normals_follow_full_share") c->opt_normals_follow_full_share = std::min(std::max(v, 0.0), 1.0);   // dirty share past which a followed update recomputes everything (no result depends on it)
+    else if (k == "voxels_follow") c->opt_voxels_follow = v != 0.0 ? 1 : 0;     // map updates refit the kept voxel map of dcreg_target_voxels_keep instead of dropping it
+    else if (k == "voxels_follow_full_share") c->opt_voxels_follow_full_share = std::min(std::max(v, 0.0), 1.0);   // share of points in touched voxels past which a followed update runs the full keep (no result depends on it)
     else if (k == "gicp_epsilon") {                              // dcreg_linearize_gicp: the small eigenvalue of both plane covariances, read at every call
         if (!(v >= 1.0e-6 && v <= 1.0)) { c->fail("gicp_epsilon is %g: 1e-6 .. 1 expected", v); return DCREG_E_INVALID; }
         c->opt_gicp_epsilon = v;

@@ -508,9 +508,13 @@ struct dcreg_ctx {
     // dcreg_linearize_voxels).  recs: 3 float4 per kept voxel in _get order (ascending z y x) - {mu, cxx} {cxy cxz cyy cyz} {czz, n as a
     // word, 0, 0}; vkeys: each one's key, (v - mn) per axis in 21 bits (what _get turns back into coordinates); t_keys / t_vals: the
     // open-addressing table a lookup probes (voxel_icp.hpp VoxMapDev), mask + 1 slots; mn / mx: the voxel box of all map points.  Dropped
-    // with every change of the map's points (context.hip target_commit, map_changed).  tmp / cls: scratch of a keep - the records of all
+    // with every change of the map's points (context.hip target_commit, map_changed) unless an update follows it ("voxels_follow").  tmp / cls: scratch of a keep - the records of all
     // voxels before compaction, and the counts [0] small [1] degenerate.  The engine's block rows, result row and dump block are nicp's
-    // (the single-pose launches of the engines never overlap)
+    // (the single-pose launches of the engines never overlap).
+    // Following the map ("voxels_follow", voxel.hip voxels_follow_*): params = the block of the keep that made the member; *_alt: the
+    // arrays a followed update builds the next member in (swapped in after its last launch); f_set: the touched voxels' keys, an
+    // open-addressing set; f_cnt: its counters; f_sub: the points of the touched voxels, gathered in index order; f_flag: carry flags of
+    // the old records and their scan; f_akeys / f_asrc, f_bkeys / f_bsrc: key and source record of the two sorted runs of the merge
     struct VoxelMapBufs {
         DevBuf<float4> recs, tmp;
         DevBuf<uint64_t> vkeys, t_keys;
@@ -521,10 +525,18 @@ struct dcreg_ctx {
         uint32_t mask = 0;
         long long mn[3] = {}, mx[3] = {};
         double leaf = 0.0;
+        dcreg_voxel_map_params params{};
+        dcreg_voxels_follow_info follow{};
+        DevBuf<float4> recs_alt, f_sub;
+        DevBuf<uint64_t> vkeys_alt, t_keys_alt, f_set, f_akeys, f_bkeys;
+        DevBuf<uint32_t> t_vals_alt, f_flag, f_asrc, f_bsrc;
+        DevBuf<long long> f_cnt;
     };
     VoxelMapBufs vmap;
     int opt_voxels_source_cov = 0;                             // "voxels_source_cov": 0 point-to-distribution, 1 distribution-to-distribution, read at every call
-    int opt_voxels_neighbors = 1;                              // "voxels_neighbors": the voxels a point is matched to - its own (1), with the face neighbours (7), the whole 3^3 block (27), read at every call
+    int opt_voxels_follow = 0;                                 // "voxels_follow": 1 = an update refits the kept voxel map of dcreg_target_voxels_keep instead of dropping it
+    double opt_voxels_follow_full_share = 0.25;                // "voxels_follow_full_share": past this share of the map's points in touched voxels a followed update runs the full keep
+    int opt_voxels_neighbors = 1;                            // "voxels_neighbors": the voxels a point is matched to - its own (1), with the face neighbours (7), the whole 3^3 block (27), read at every call
     double opt_gicp_epsilon = 1.0e-3;                          // "gicp_epsilon": the small eigenvalue of both plane covariances, read at every call
     int opt_robust_kernel = 0;                                 // "robust_kernel" (DCREG_ROBUST_*): the second and third engine's rows, read at every call
     double opt_robust_scale = 0.1;                             // "robust_scale": its scale c for the second engine, metres
@@ -916,6 +928,14 @@ struct FollowChange {
 bool normals_follow_wanted(const dcreg_ctx *c);
 bool normals_follow_carry(dcreg_ctx *c, int64_t n_old, const uint32_t *flag_r, const uint32_t *pos_r, int64_t kept);
 void normals_follow_update(dcreg_ctx *c, const FollowChange &ch);
+// voxel.hip: the kept voxel map follows an update of the map ("voxels_follow", include/dcreg.h).  voxels_follow_wanted: asked BEFORE the
+// update drops the member (option on, a member kept).  voxels_follow_update (after the update stands and the whole map's index is the
+// active one; wanted = what voxels_follow_wanted answered): the voxels of the points that came or went are marked, the updated map's
+// points in them gathered and reduced again, the other records carried and both runs merged into the alternate arrays - or, past the
+// threshold, the full keep; the member is restored on success.  On any failure it stays dropped, as map_changed left it; !wanted: the
+// info says so and nothing else happens
+bool voxels_follow_wanted(const dcreg_ctx *c);
+void voxels_follow_update(dcreg_ctx *c, const FollowChange &ch, bool wanted);
 // visibility.hip: one call's votes.  visibility_prepare checks parameters and members on the host (every refusal of include/dcreg.h before
 // anything is queued; poses == null: range images only) and cuts the members into batches; visibility_votes leaves through / observed of
 // the n packed points at `pts` in c->vis (by_w: point i counts at index w_i - a map in cell order); visibility_flags writes the keep flags

@@ -14,6 +14,7 @@
 // A voxel's result depends on its own points only: where its cloud sits in the call and how the launches are cut never enter it.
 // The kept voxel map of the fourth engine (voxel_map_keep: k_vmap_reduce, k_vmap_write) runs behind the same keying and sort, and so do
 // the voxel maps of a build batch of scan-pair targets, one per target, all at once (pairs_voxels_build: k_pvmap_count, k_pvmap_write).
+// Under "voxels_follow" an update of the map refits the kept voxel map's touched voxels and carries the rest (follow_run: k_vfollow_*).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -674,6 +675,7 @@ int voxel_map_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_ma
     HIP_TRY(c, hipGetLastError());
     for (int a = 0; a < 3; ++a) { M.mn[a] = h[a]; M.mx[a] = h[3 + a]; }
     M.leaf = l; M.mask = (uint32_t)(slots - 1); M.n_kept = n_kept; M.kept = true;
+    M.params = *p;                                     // (the rule a followed update refits with: "voxels_follow")
     return DCREG_OK;
 }
 
@@ -703,6 +705,392 @@ static int voxel_map_get(dcreg_ctx *c, int64_t *coords, int32_t *count, float *m
         std::memcpy(count + j, r + 9, sizeof(int32_t));
     }
     return DCREG_OK;
+}
+
+// ------------------------------------------------------------------------------------------ the kept voxel map follows the map ("voxels_follow")
+// A voxel's record is a function of its points in index order (k_vmap_reduce), and an update appends points or removes some and renumbers
+// the survivors in their old order: the records of the voxels that hold no added and no removed point are what a fresh keep computes,
+// bit for bit.  The others - the "touched" voxels - are reduced again from ALL of their points in the updated map:
+//   k_vfollow_box    one lane per changed point: the voxel box of the changed points (= the touched voxels' box), per wave before the atomics
+//   k_vfollow_mark   one lane per changed point: its voxel, relative to the union of that box and the member's, claims a slot of the touched set
+//   k_vfollow_flags  the ONLY pass over the updated map (16 B read per point): the points in touched voxels, and the map's new voxel box
+//   scan, k_vfollow_gather   those points, compacted in index order: a cloud that vox_order + k_vmap_reduce take as they take a map
+//   k_vfollow_carry  one lane per old record: touched = it goes, else it is carried
+//   k_vfollow_runs   the two sorted runs of the merge - carried records and the subset's kept voxels - with keys relative to the NEW minimum
+//   k_vfollow_write  one lane per record of either run: its place = its rank in its run + the keys below it in the other run (keys are
+//                    unique across the runs: a touched voxel is never carried); the record, its key and its slot of a fresh table
+// Keys order as voxels do (z y x) whatever minimum they are relative to, so both runs ascend and the merged records are in _get order.
+namespace {
+
+constexpr int kVfOvf = 6, kVfDistinct = 7, kVfNew = 8, kVfWords = 16;   // f_cnt: [0..5] the changed points' voxel box, [8..13] the updated map's
+struct VfBox { long long lo[3], hi[3]; };
+
+// k_vox_coords' voxel of a finite point as integers; false: a coordinate reaches 2^62 (the pass's refusal)
+__device__ __forceinline__ bool voxel_int(const float4 p, const double l, long long vi[3]) {
+    double v[3];
+    voxel_of(p, l, l, l, v);
+    const bool ok = fabs(v[0]) < kVoxLimit && fabs(v[1]) < kVoxLimit && fabs(v[2]) < kVoxLimit;
+    for (int a = 0; a < 3; ++a) vi[a] = ok ? (long long)v[a] : 0;
+    return ok;
+}
+__device__ __forceinline__ bool vf_inside(const long long vi[3], const VfBox &b) {
+    return vi[0] >= b.lo[0] && vi[0] <= b.hi[0] && vi[1] >= b.lo[1] && vi[1] <= b.hi[1] && vi[2] >= b.lo[2] && vi[2] <= b.hi[2];
+}
+__device__ __forceinline__ uint64_t vf_key(const long long vi[3], const long long mn[3]) {
+    return vmap_key((uint64_t)(vi[0] - mn[0]), (uint64_t)(vi[1] - mn[1]), (uint64_t)(vi[2] - mn[2]));
+}
+// is the key in the touched set (the probing of vmap_find_voxel: the set is at most half full)
+__device__ __forceinline__ bool vf_touched(const uint64_t *__restrict__ set, uint32_t mask, uint64_t key) {
+    uint32_t s = vmap_slot(key, mask);
+    for (;;) {
+        const uint64_t k = set[s];
+        if (k == key) return true;
+        if (k == kVmapEmpty) return false;
+        s = (s + 1u) & mask;
+    }
+}
+__device__ __forceinline__ void vf_wave_box(long long mn[3], long long mx[3]) {
+    for (int o = 32; o > 0; o >>= 1)
+        for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], (long long)__shfl_xor(mn[a], o)); mx[a] = std::max(mx[a], (long long)__shfl_xor(mx[a], o)); }
+}
+
+// keep != null: the points whose flag is set stay - only the others changed
+static __global__ void __launch_bounds__(kVoxBlock) k_vfollow_box(const float4 *__restrict__ pts, int64_t n, const uint32_t *__restrict__ keep, double leaf,
+                                                                  long long *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = i < n && !(keep && keep[i] != 0u);
+    long long mn[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, mx[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    bool big = false;
+    if (on) {
+        long long vi[3];
+        big = !voxel_int(pts[i], leaf, vi);
+        if (!big)
+            for (int a = 0; a < 3; ++a) { mn[a] = vi[a]; mx[a] = vi[a]; }
+    }
+    const uint64_t any = __ballot(on && !big), B = __ballot(big);
+    if (!any && !B) return;                // (wave-uniform)
+    vf_wave_box(mn, mx);
+    if ((threadIdx.x & 63) == 0) {
+        if (B) atomicOr(reinterpret_cast<unsigned long long *>(cnt + kVfOvf), 1ull);
+        // (a removal brings millions of points and every wave's six atomics meet at the same words: a plain look first - the words only
+        // ever move outwards, so a stale value can cost an atomic and never skips one that is needed)
+        if (any)
+            for (int a = 0; a < 3; ++a) {
+                if (mn[a] < *reinterpret_cast<volatile long long *>(cnt + a)) atomicMin(cnt + a, mn[a]);
+                if (mx[a] > *reinterpret_cast<volatile long long *>(cnt + 3 + a)) atomicMax(cnt + 3 + a, mx[a]);
+            }
+    }
+}
+
+// The touched set: a changed point's voxel, relative to the union of the member's box `old` and the changed points' box (the old box for
+// a removal, the new one for an insert: one contains the other), claims the first free slot of its probe sequence with k_vmap_write's
+// 64-bit atomicCAS; a lane that meets its own key stops.  The claims are the distinct touched voxels: counted per wave.  A union of
+// 2^21 voxels on an axis or a coordinate of 2^62 marks nothing (grid-uniform; the host refuses from the same words)
+static __global__ void __launch_bounds__(kVoxBlock) k_vfollow_mark(const float4 *__restrict__ pts, int64_t n, const uint32_t *__restrict__ keep, double leaf,
+                                                                   VfBox old, long long *cnt, uint64_t *__restrict__ set, uint32_t mask) {
+    long long u[3];
+    bool bad = cnt[kVfOvf] != 0;
+    for (int a = 0; a < 3; ++a) {
+        u[a] = std::min(old.lo[a], cnt[a]);
+        bad |= std::max(old.hi[a], cnt[3 + a]) - u[a] + 1 > kSpanMax;
+    }
+    if (bad) return;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool won = false;
+    if (i < n && !(keep && keep[i] != 0u)) {
+        long long vi[3];
+        (void)voxel_int(pts[i], leaf, vi);
+        const uint64_t key = vf_key(vi, u);
+        uint32_t s = vmap_slot(key, mask);
+        for (;;) {                                       // (ends: at most half of the slots are ever claimed)
+            // a plain look first: a removal sends thousands of lanes to one voxel's slot, and all but the first find its key there
+            // without an atomic (a slot never changes once claimed; a stale "empty" only costs the CAS)
+            unsigned long long was = *reinterpret_cast<volatile unsigned long long *>(set + s);
+            if (was == (unsigned long long)kVmapEmpty)
+                was = atomicCAS(reinterpret_cast<unsigned long long *>(set + s), (unsigned long long)kVmapEmpty, (unsigned long long)key);
+            if (was == (unsigned long long)kVmapEmpty) { won = true; break; }
+            if (was == (unsigned long long)key) break;
+            s = (s + 1u) & mask;
+        }
+    }
+    const uint64_t W = __ballot(won);
+    if (W && (threadIdx.x & 63) == 0) atomicAdd(reinterpret_cast<unsigned long long *>(cnt + kVfDistinct), (unsigned long long)__popcll(W));
+}
+
+// The pass over the updated map, k_vox_coords' tile shape: flag[i] = point i lies in a touched voxel (n + 1 entries, the last 0) - its
+// voxel, the early-out against the touched voxels' box `tb`, then the probe - and the voxel box of all points (the member's new box)
+static __global__ void __launch_bounds__(kVoxBlock) k_vfollow_flags(const float4 *__restrict__ pts, int64_t n, double leaf, VfBox uni, VfBox tb,
+                                                                    const uint64_t *__restrict__ set, uint32_t mask, uint32_t *__restrict__ flag,
+                                                                    long long *__restrict__ cnt) {
+    const int64_t base = (int64_t)blockIdx.x * (kVoxBlock * kVoxPerThread);
+    long long mn[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, mx[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    for (int k = 0; k < kVoxPerThread; ++k) {
+        const int64_t i = base + threadIdx.x + (int64_t)k * kVoxBlock;
+        if (i > n) break;
+        if (i == n) { flag[i] = 0u; break; }
+        const float4 p = pts[i];
+        long long vi[3];
+        bool hit = false;
+        if (voxel_int(p, leaf, vi)) {
+            for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], vi[a]); mx[a] = std::max(mx[a], vi[a]); }
+            hit = vf_inside(vi, tb) && vf_touched(set, mask, vf_key(vi, uni.lo));
+        }
+        flag[i] = hit ? 1u : 0u;
+    }
+    vf_wave_box(mn, mx);
+    __shared__ long long smn[kVoxBlock / 64][3], smx[kVoxBlock / 64][3];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int a = 0; a < 3; ++a) { smn[wave][a] = mn[a]; smx[wave][a] = mx[a]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        long long l = smn[0][a], h = smx[0][a];
+        for (int w = 1; w < kVoxBlock / 64; ++w) { l = std::min(l, smn[w][a]); h = std::max(h, smx[w][a]); }
+        if (l <= h) { atomicMin(cnt + kVfNew + a, l); atomicMax(cnt + kVfNew + 3 + a, h); }
+    }
+}
+
+// the points of the touched voxels, compacted in index order (pos = exclusive scan of flag)
+static __global__ void k_vfollow_gather(const float4 *__restrict__ pts, int64_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                        float4 *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    out[pos[i]] = pts[i];
+}
+
+__device__ __forceinline__ void vf_unpack(uint64_t key, const long long mn[3], long long vi[3]) {
+    const uint64_t am = (1ull << kVmapAxisBits) - 1ull;
+    vi[0] = mn[0] + (long long)(key & am);
+    vi[1] = mn[1] + (long long)((key >> kVmapAxisBits) & am);
+    vi[2] = mn[2] + (long long)(key >> (2 * kVmapAxisBits));
+}
+
+// cflag[j] = 1: old record j is carried - its voxel (the member's minimum + its key) holds no changed point (nk + 1 entries, the last 0)
+static __global__ void k_vfollow_carry(const uint64_t *__restrict__ vkeys, int64_t nk, VfBox old, VfBox uni, VfBox tb, const uint64_t *__restrict__ set,
+                                       uint32_t mask, uint32_t *__restrict__ cflag) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > nk) return;
+    if (j == nk) { cflag[j] = 0u; return; }
+    long long vi[3];
+    vf_unpack(vkeys[j], old.lo, vi);
+    const bool touched = vf_inside(vi, tb) && vf_touched(set, mask, vf_key(vi, uni.lo));
+    cflag[j] = touched ? 0u : 1u;
+}
+
+// The runs of the merge.  Lanes [0, nk): a carried record's key, rewritten relative to the new minimum `nw`, and its number, at its rank
+// cpos.  Lanes [nk, nk + n_vox): a kept voxel of the subset - its rel key (widths bx, by, relative to tb's minimum, as vox_order was
+// given it) rewritten the same way - and its number in the uncompacted records, at its rank pos
+static __global__ void k_vfollow_runs(const uint64_t *__restrict__ vkeys, int64_t nk, const uint32_t *__restrict__ cflag, const uint32_t *__restrict__ cpos,
+                                      VfBox old, VfBox nw, int64_t n_vox, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ pos,
+                                      const uint32_t *__restrict__ ord, const uint32_t *__restrict__ start, const uint64_t *__restrict__ rel, int bx, int by,
+                                      VfBox tb, uint64_t *__restrict__ akeys, uint32_t *__restrict__ asrc, uint64_t *__restrict__ bkeys,
+                                      uint32_t *__restrict__ bsrc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    long long vi[3];
+    if (i < nk) {
+        if (!cflag[i]) return;
+        vf_unpack(vkeys[i], old.lo, vi);
+        const uint32_t r = cpos[i];
+        akeys[r] = vf_key(vi, nw.lo); asrc[r] = (uint32_t)i;
+    } else {
+        const int64_t v = i - nk;
+        if (v >= n_vox || !keep[v]) return;
+        const uint64_t q = rel[ord[start[v]]];
+        vi[0] = tb.lo[0] + (long long)(q & ((1ull << bx) - 1ull));
+        vi[1] = tb.lo[1] + (long long)((q >> bx) & ((1ull << by) - 1ull));
+        vi[2] = tb.lo[2] + (long long)(q >> (bx + by));
+        const uint32_t r = pos[v];
+        bkeys[r] = vf_key(vi, nw.lo); bsrc[r] = (uint32_t)v;
+    }
+}
+
+// Merge and write: lane i < n_a is carried record i of run a (from the member's records), the others the kept voxels of run b (from the
+// subset's uncompacted records).  Place = rank in the own run + the other run's keys below the own key (binary search); then the record,
+// its key, and its slot of the fresh table by k_vmap_write's probing
+static __global__ void __launch_bounds__(kVoxBlock) k_vfollow_write(int64_t n_a, int64_t n_b, const uint64_t *__restrict__ akeys, const uint32_t *__restrict__ asrc,
+                                                                    const uint64_t *__restrict__ bkeys, const uint32_t *__restrict__ bsrc,
+                                                                    const float4 *__restrict__ recs_old, const float4 *__restrict__ tmp,
+                                                                    float4 *__restrict__ recs, uint64_t *__restrict__ vkeys, uint64_t *__restrict__ t_keys,
+                                                                    uint32_t *__restrict__ t_vals, uint32_t mask) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_a + n_b) return;
+    const bool own_a = i < n_a;
+    const int64_t r = own_a ? i : i - n_a;
+    const uint64_t key = own_a ? akeys[r] : bkeys[r];
+    const uint64_t *other = own_a ? bkeys : akeys;
+    int64_t lo = 0, hi = own_a ? n_b : n_a;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (other[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    const uint32_t j = (uint32_t)(r + lo);
+    const float4 *src = own_a ? recs_old + 3 * (size_t)asrc[r] : tmp + 3 * (size_t)bsrc[r];
+    recs[3 * (size_t)j] = src[0]; recs[3 * (size_t)j + 1] = src[1]; recs[3 * (size_t)j + 2] = src[2];
+    vkeys[j] = key;
+    uint32_t s = vmap_slot(key, mask);
+    for (;;) {                                           // (ends: at most half of the slots are ever claimed)
+        const unsigned long long was = atomicCAS(reinterpret_cast<unsigned long long *>(t_keys + s), (unsigned long long)kVmapEmpty, (unsigned long long)key);
+        if (was == (unsigned long long)kVmapEmpty) { t_vals[s] = j; break; }
+        s = (s + 1u) & mask;
+    }
+}
+
+// scratch that grows with the map from keyframe to keyframe: an eighth of headroom, so that not every update allocates again
+template <typename T>
+int vf_ensure(dcreg_ctx *c, DevBuf<T> &b, size_t need) { return b.holds(need) ? DCREG_OK : b.ensure(c, need + need / 8 + 4096); }
+
+// A followed update.  FIVE stream synchronises on the incremental path (the touched box and count; the hits and the new box; the subset's
+// voxels; the two runs' lengths; the end).  Every array of the next member is written beside the current one and swapped in last
+int follow_run(dcreg_ctx *c, const FollowChange &ch) {
+    dcreg_ctx::VoxelBufs &B = c->vox;
+    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    const int64_t n = c->map.n, nk = M.n_kept;
+    if (n <= 0 || nk <= 0 || c->roi_active) { c->fail("the kept voxel map cannot follow: the whole map's index is not the active one"); return DCREG_E_STATE; }
+    const bool removal = ch.n_old > 0;
+    const float4 *cpts = removal ? ch.old_raw : ch.added;
+    const uint32_t *ckeep = removal ? ch.flag_r : nullptr;
+    const int64_t n_c = removal ? ch.n_old : ch.n_added, n_changed = removal ? ch.n_old - n : ch.n_added;
+    if (!cpts || n_changed <= 0 || (removal && !ckeep)) { c->fail("the kept voxel map cannot follow: no change given"); return DCREG_E_STATE; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const dcreg_voxel_map_params prm = M.params;
+    const double l = prm.leaf;
+    dcreg_voxels_follow_info &F = M.follow;
+    // ---- the touched voxels
+    size_t fslots = 2;
+    while (fslots < 2 * (size_t)n_changed) fslots <<= 1;
+    if (M.f_set.ensure(c, fslots) || M.f_cnt.ensure(c, kVfWords)) return DCREG_E_NOMEM;
+    long long h[kVfWords] = {};
+    for (int a = 0; a < 3; ++a) { h[a] = INT64_MAX; h[3 + a] = INT64_MIN; h[kVfNew + a] = INT64_MAX; h[kVfNew + 3 + a] = INT64_MIN; }
+    HIP_TRY(c, hipMemcpyAsync(M.f_cnt.data(), h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(M.f_set.data(), 0xFF, fslots * sizeof(uint64_t), c->stream));
+    VfBox old, tb, uni, nw;
+    for (int a = 0; a < 3; ++a) { old.lo[a] = M.mn[a]; old.hi[a] = M.mx[a]; }
+    const uint32_t fmask = (uint32_t)(fslots - 1);
+    hipLaunchKernelGGL(k_vfollow_box, dim3(blocks(n_c, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, cpts, n_c, ckeep, l, M.f_cnt.data());
+    hipLaunchKernelGGL(k_vfollow_mark, dim3(blocks(n_c, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, cpts, n_c, ckeep, l, old, M.f_cnt.data(), M.f_set.data(), fmask);
+    HIP_TRY(c, hipMemcpyAsync(h, M.f_cnt.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    // ---- the keep's limits, on the union box (an insert's union is the updated map's box; a removal's is the member's, which passed)
+    if (h[kVfOvf]) { c->fail("a voxel coordinate reaches 2^62 (leaf too small for the coordinates): the kept voxel map is dropped"); return DCREG_E_INVALID; }
+    for (int a = 0; a < 3; ++a) {
+        tb.lo[a] = h[a]; tb.hi[a] = h[3 + a];
+        uni.lo[a] = std::min(old.lo[a], tb.lo[a]); uni.hi[a] = std::max(old.hi[a], tb.hi[a]);
+        if (uni.hi[a] - uni.lo[a] + 1 > kSpanMax) {
+            c->fail("the map spans %lld voxels on axis %d (at most 2^21 - 1 = %lld): the kept voxel map is dropped", (long long)(uni.hi[a] - uni.lo[a] + 1), a,
+                    (long long)kSpanMax);
+            return DCREG_E_INVALID;
+        }
+    }
+    F.n_touched = h[kVfDistinct];
+    // ---- the one pass over the updated map: the points in touched voxels (flag and its scan in the voxel pass's head / incl), the new box
+    const float4 *pts = c->map.raw.data();
+    const size_t n1 = (size_t)n + 1;
+    if (vf_ensure(c, B.head, n1) || vf_ensure(c, B.incl, n1)) return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_vfollow_flags, dim3(blocks((int64_t)n1, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, pts, n, l, uni, tb, M.f_set.data(), fmask,
+                       B.head.data(), M.f_cnt.data());
+    int rc = scan(c, B.head.data(), B.incl.data(), n1, false);
+    if (rc) return rc;
+    uint32_t n_hit32 = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_hit32, B.incl.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h, M.f_cnt.data(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t n_hit = n_hit32;
+    for (int a = 0; a < 3; ++a) { nw.lo[a] = h[kVfNew + a]; nw.hi[a] = h[kVfNew + 3 + a]; }
+    if ((double)n_hit > c->opt_voxels_follow_full_share * (double)n) {      // past the share: the keep itself, with the same bits
+        dcreg_voxel_map_info info{};
+        rc = voxel_map_keep(c, &prm, &info);
+        if (rc) return rc;
+        F.n_refit = info.n_voxels; F.n_carried = 0; F.n_kept = info.n_kept; F.followed = 2;
+        return DCREG_OK;
+    }
+    // ---- the subset through the keep's order and reduction, unchanged: one cloud, keys relative to the touched box's minimum
+    int64_t n_vox = 0;
+    int bits[3] = {0, 0, 0};
+    const uint32_t *ord = nullptr;
+    if (n_hit > 0) {
+        const size_t nc = (size_t)kCnt + kTail;
+        if (vf_ensure(c, M.f_sub, (size_t)n_hit) || vf_ensure(c, B.seg, (size_t)n_hit) || vf_ensure(c, B.rel, (size_t)n_hit) ||
+            vf_ensure(c, B.start, (size_t)n_hit + 1) || vf_ensure(c, B.keep, (size_t)n_hit) || vf_ensure(c, B.pos, (size_t)n_hit) || B.cnt.ensure(c, nc) ||
+            vf_ensure(c, c->d_mkeys, (size_t)n_hit) || vf_ensure(c, c->d_mkeys2, (size_t)n_hit) || vf_ensure(c, c->d_vals, (size_t)n_hit) ||
+            vf_ensure(c, c->d_vals2, (size_t)n_hit) || M.cls.ensure(c, 2))
+            return DCREG_E_NOMEM;
+        hipLaunchKernelGGL(k_vfollow_gather, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, pts, n, B.head.data(), B.incl.data(), M.f_sub.data());
+        int64_t hc[kCnt + kTail] = {};
+        for (int a = 0; a < 3; ++a) { hc[a] = tb.lo[a]; hc[3 + a] = tb.hi[a]; bits[a] = bits_for(tb.hi[a] - tb.lo[a]); }
+        HIP_TRY(c, hipMemcpyAsync(B.cnt.data(), hc, sizeof(hc), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(B.seg.data(), 0, (size_t)n_hit * sizeof(uint32_t), c->stream));       // (all of cloud 0)
+        HIP_TRY(c, hipMemsetAsync(M.cls.data(), 0, 2 * sizeof(unsigned long long), c->stream));
+        rc = vox_order(c, M.f_sub.data(), n_hit, 1, l, l, l, bits[0], bits[1], bits[2], ord);
+        if (rc) return rc;
+        uint32_t n_vox32 = 0;
+        HIP_TRY(c, hipMemcpyAsync(&n_vox32, B.incl.data() + (n_hit - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        n_vox = n_vox32;
+        if (vf_ensure(c, M.tmp, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
+        hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.f_sub.data(), ord, n_vox, B.start.data(), prm.min_points,
+                           prm.epsilon, M.tmp.data(), B.keep.data(), M.cls.data());
+        rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+        if (rc) return rc;
+    }
+    // ---- the old records: carried or gone
+    const size_t nk1 = (size_t)nk + 1;
+    if (vf_ensure(c, M.f_flag, 2 * nk1)) return DCREG_E_NOMEM;
+    uint32_t *cflag = M.f_flag.data(), *cpos = cflag + nk1;
+    hipLaunchKernelGGL(k_vfollow_carry, dim3(blocks((int64_t)nk1, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.vkeys.data(), nk, old, uni, tb, M.f_set.data(), fmask, cflag);
+    rc = scan(c, cflag, cpos, nk1, false);
+    if (rc) return rc;
+    uint32_t n_a32 = 0, last[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(&n_a32, cpos + nk, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (n_vox > 0) {
+        HIP_TRY(c, hipMemcpyAsync(&last[0], B.keep.data() + (n_vox - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&last[1], B.pos.data() + (n_vox - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t n_a = n_a32, n_b = (int64_t)last[0] + (int64_t)last[1], n_kept = n_a + n_b;
+    F.n_refit = n_vox; F.n_carried = n_a; F.n_kept = n_kept; F.followed = 1;
+    M.n_kept = 0;
+    if (n_kept == 0) return DCREG_OK;                  // (nothing kept: no member, as after a keep that keeps nothing)
+    // ---- the next member beside the current one: merge, records, keys, table
+    size_t slots = 2;
+    while (slots < 2 * (size_t)n_kept) slots <<= 1;
+    if (vf_ensure(c, M.f_akeys, (size_t)nk) || vf_ensure(c, M.f_asrc, (size_t)nk) || vf_ensure(c, M.f_bkeys, (size_t)n_vox) || vf_ensure(c, M.f_bsrc, (size_t)n_vox) ||
+        vf_ensure(c, M.recs_alt, 3 * (size_t)n_kept) || vf_ensure(c, M.vkeys_alt, (size_t)n_kept) || M.t_keys_alt.ensure(c, slots) || M.t_vals_alt.ensure(c, slots))
+        return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(M.t_keys_alt.data(), 0xFF, slots * sizeof(uint64_t), c->stream));
+    hipLaunchKernelGGL(k_vfollow_runs, dim3(blocks(nk + n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.vkeys.data(), nk, cflag, cpos, old, nw, n_vox, B.keep.data(),
+                       B.pos.data(), ord, B.start.data(), B.rel.data(), bits[0], bits[1], tb, M.f_akeys.data(), M.f_asrc.data(), M.f_bkeys.data(), M.f_bsrc.data());
+    hipLaunchKernelGGL(k_vfollow_write, dim3(blocks(n_kept, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, n_a, n_b, M.f_akeys.data(), M.f_asrc.data(), M.f_bkeys.data(),
+                       M.f_bsrc.data(), M.recs.data(), M.tmp.data(), M.recs_alt.data(), M.vkeys_alt.data(), M.t_keys_alt.data(), M.t_vals_alt.data(),
+                       (uint32_t)(slots - 1));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    M.recs.swap(M.recs_alt); M.vkeys.swap(M.vkeys_alt); M.t_keys.swap(M.t_keys_alt); M.t_vals.swap(M.t_vals_alt);
+    for (int a = 0; a < 3; ++a) { M.mn[a] = nw.lo[a]; M.mx[a] = nw.hi[a]; }
+    M.mask = (uint32_t)(slots - 1); M.n_kept = n_kept; M.kept = true;
+    return DCREG_OK;
+}
+
+}  // namespace
+
+bool voxels_follow_wanted(const dcreg_ctx *c) { return c->opt_voxels_follow && c->vmap.kept && c->vmap.n_kept > 0; }
+
+// (the update stands whatever happens here: a failure leaves the member dropped, as map_changed left it, and says so in the info)
+void voxels_follow_update(dcreg_ctx *c, const FollowChange &ch, bool wanted) {
+    dcreg_ctx::VoxelMapBufs &M = c->vmap;
+    M.follow = dcreg_voxels_follow_info{};
+    M.follow.n_target = c->map.n;
+    if (!wanted) return;
+    if (follow_run(c, ch) == DCREG_OK) return;
+    (void)hipGetLastError();
+    M.kept = false; M.n_kept = 0;
+    M.follow = dcreg_voxels_follow_info{};
+    M.follow.n_target = c->map.n;
 }
 
 // the parameter refusals of dcreg_target_voxels_keep on their own, in its order (dcreg_register_pairs_voxels makes them before its empty
@@ -950,6 +1338,13 @@ int dcreg_target_voxels_drop(dcreg_ctx *c) {
     dcreg_ctx::VoxelMapBufs &M = c->vmap;
     M.kept = false; M.n_kept = 0;
     M.recs.reset(); M.tmp.reset(); M.vkeys.reset(); M.t_keys.reset(); M.t_vals.reset();
+    M.recs_alt.reset(); M.vkeys_alt.reset(); M.t_keys_alt.reset(); M.t_vals_alt.reset(); M.f_sub.reset(); M.f_set.reset(); M.f_flag.reset();
+    M.f_akeys.reset(); M.f_asrc.reset(); M.f_bkeys.reset(); M.f_bsrc.reset();
+    return DCREG_OK;
+}
+int dcreg_target_voxels_follow_info(const dcreg_ctx *c, dcreg_voxels_follow_info *info) {
+    if (!c || !info) return DCREG_E_INVALID;
+    *info = c->vmap.follow;
     return DCREG_OK;
 }
 }

@@ -1036,6 +1036,7 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_normal_params")) return sizeof(dcreg_normal_params);
     if (!std::strcmp(name, "dcreg_normal_info")) return sizeof(dcreg_normal_info);
     if (!std::strcmp(name, "dcreg_normals_follow_info")) return sizeof(dcreg_normals_follow_info);
+    if (!std::strcmp(name, "dcreg_voxels_follow_info")) return sizeof(dcreg_voxels_follow_info);
     if (!std::strcmp(name, "dcreg_nlin_debug")) return sizeof(dcreg_nlin_debug);
     if (!std::strcmp(name, "dcreg_glin_debug")) return sizeof(dcreg_glin_debug);
     if (!std::strcmp(name, "dcreg_vlin_debug")) return sizeof(dcreg_vlin_debug);

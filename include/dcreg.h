@@ -179,6 +179,12 @@ int dcreg_set_stream(dcreg_ctx *, void *hip_stream);
  *                   at the time of the update;
  *   "normals_follow_full_share" default 0.25 (0 .. 1): the share of the map's points a followed update may have to refit before it
  *                   recomputes all of them instead (the results do not depend on it);
+ *   "voxels_follow" 0 (default) = every update of the map drops the kept voxel map; 1 = dcreg_target_insert*, dcreg_target_crop,
+ *                   dcreg_target_remove_outliers and dcreg_target_remove_dynamic refit the voxels of dcreg_target_voxels_keep that an added
+ *                   or removed point lies in and carry the rest ("kept voxel map that follows the map" below); read at the time of
+ *                   the update;
+ *   "voxels_follow_full_share" default 0.25 (0 .. 1): the share of the updated map's points lying in touched voxels beyond which a
+ *                   followed update runs the full keep instead (the results do not depend on it);
  *   "gicp_epsilon"  default 1e-3 (1e-6 .. 1, DCREG_E_INVALID outside): the small eigenvalue of both plane covariances of
  *                   dcreg_linearize_gicp; read at the time of every linearisation;
  *   "robust_kernel" default 0 = DCREG_ROBUST_NONE; DCREG_ROBUST_HUBER (1), DCREG_ROBUST_CAUCHY (2), DCREG_ROBUST_GEMAN_MCCLURE (3).  The
@@ -1128,7 +1134,8 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  * and 12 B per table slot - the power of two at or above twice the kept voxels - 80 to 104 B per kept voxel in all; a keep also uses
  * 48 B of scratch per occupied voxel and the voxel pass's scratch per map point.
  * Every call that changes the map's points drops the member: dcreg_set_target* in all its forms, dcreg_target_insert*,
- * dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic and dcreg_set_target_keyframes.  Nothing follows the map.
+ * dcreg_target_crop, dcreg_target_remove_outliers, dcreg_target_remove_dynamic and dcreg_set_target_keyframes - unless the option
+ * "voxels_follow" makes the updates refit it ("kept voxel map that follows the map" below).
  * DCREG_E_INVALID, before anything is queued: null context, parameters or outputs; a leaf that is not finite and > 0; epsilon outside
  * [1e-6, 1]; min_points < 2; a capacity_voxels below the kept voxels; and, once the points' voxels are known and before anything is kept,
  * a map that spans 2^21 or more voxels on an axis or has a voxel coordinate of magnitude 2^62 or more (the voxel pass's limits).
@@ -1179,8 +1186,8 @@ int dcreg_linearize_gicp(dcreg_ctx *, const double R[9], const double t[3], cons
  * The batched forms - many trials of the own source, many frames, many scan pairs with a voxel map per target - are
  * dcreg_icp_run_trials_voxels, dcreg_register_frames_voxels and dcreg_register_pairs_voxels below (the engine is density-hungry on
  * scan-sized targets: DESIGN.md sections 21 to 23).
- * Not provided: correspondences weighted by the voxel's point count, a voxel map that follows map updates, sharded / Euler forms,
- * a caller-supplied voxel map, the runner's YAML. */
+ * Not provided: correspondences weighted by the voxel's point count, sharded / Euler forms, a caller-supplied voxel map, the runner's
+ * YAML. */
 typedef struct dcreg_voxel_map_params {
     double leaf;      /* voxel edge, metres (default 1.0) */
     double epsilon;   /* floor of the normalised eigenvalues (default 1e-3) */
@@ -1197,6 +1204,47 @@ int dcreg_target_voxels_get(dcreg_ctx *, int64_t *coords /*3V*/, int32_t *count 
 int dcreg_target_voxels_kept(const dcreg_ctx *);   /* number of kept voxels, 0 without a member */
 int dcreg_target_voxels_drop(dcreg_ctx *);
 int dcreg_linearize_voxels(dcreg_ctx *, const double R[9], const double t[3], const dcreg_lin_params *, dcreg_lin_out *);
+
+/* ---------------- kept voxel map that follows the map ----------------
+ * dcreg_set_option("voxels_follow", 1) makes the map updates - dcreg_target_insert, _insert_device, _insert_source, dcreg_target_crop,
+ * dcreg_target_remove_outliers, dcreg_target_remove_dynamic - UPDATE the kept voxel map instead of dropping it, so that a keyframe loop
+ * (dcreg_set_source + dcreg_icp_run_voxels + dcreg_target_insert_source, a crop every few keyframes) never sorts the whole map again.
+ * Default 0: every update drops the member, as stated above.  The option is read at the time of the update.  It applies only while a
+ * member exists (dcreg_target_voxels_kept() > 0): the context remembers the parameter block (leaf, epsilon, min_points) of the
+ * dcreg_target_voxels_keep that made it and refits with it.  dcreg_set_target* in all its forms and dcreg_set_target_keyframes always
+ * drop (the map is a new one).
+ *   Contract.  After a followed update dcreg_target_voxels_get returns, bit for bit, what a fresh context returns after
+ *   dcreg_set_target(M') + dcreg_target_voxels_keep(params), M' = dcreg_target_get of the updated map: coordinates, counts, means and
+ *   covariances in ascending (v_z, v_y, v_x) order, and dcreg_target_voxels_kept agrees.  Every dcreg_linearize_voxels dump and sum
+ *   agrees too, at "voxels_neighbors" 1, 7 and 27 and in both "voxels_source_cov" modes; dcreg_icp_run_voxels,
+ *   dcreg_icp_run_trials_voxels and dcreg_register_frames_voxels are therefore bitwise the fresh context's.  The result does not depend
+ *   on the sequence of updates, on "map_update", on whether an update merged into the grid or re-derived it
+ *   (dcreg_map_update::rebuilt), on whether the window index was active, or on whether the update ran incrementally or as a full keep.
+ *   A voxel's record is a function of its points in index order, so a voxel that holds an added or a removed point ("touched") is
+ *   reduced again from ALL of its points; the records of every other voxel are moved over unchanged.
+ *   An update that changes nothing (an insert whose points were all thinned away, a crop that keeps everything) leaves the member and
+ *   the info as they were; a refused update leaves the member bitwise as it was.  If the follow leaves no kept voxel the member goes,
+ *   exactly as a keep that keeps nothing leaves none.  The follow may fail after the map has changed - out of memory, an updated map
+ *   that spans 2^21 or more voxels on an axis, a voxel coordinate of magnitude 2^62 or more: the keep's own refusals.  The update then
+ *   stands with its return code unchanged, and the voxel map is dropped (dcreg_target_voxels_kept 0, followed 0).
+ *   Memory while a followed update runs: a second copy of the records, keys and table (56 B per kept voxel, 12 B per slot; it stays
+ *   until the next update reuses it), 20 B per kept voxel of merge scratch, the touched set (8 B per slot, the power of two at or above
+ *   twice the changed points), 8 B per point of the updated map (the voxel pass's own scratch, as a keep sizes it), and for the
+ *   gathered subset - the points of the touched voxels - 16 B per point plus the voxel pass's scratch per point and 48 B per voxel.
+ *   dcreg_target_voxels_follow_info     what the last update that changed the map did (all zero after dcreg_set_target* in any of its
+ *                                       forms: a new map has had no update yet): n_target = the map's size after it; n_touched = the
+ *                                       distinct voxels that hold an added or removed point; n_refit = voxels reduced again (the
+ *                                       touched voxels still occupied after the update; every occupied voxel when followed is 2);
+ *                                       n_carried = kept records moved over unchanged; n_kept = kept voxels after the update
+ *                                       (n_kept - n_carried = the refitted voxels that ended up kept); followed = 0 not followed
+ *                                       (the member was dropped, or no update yet), 1 incremental, 2 followed by the full keep.
+ *                                       DCREG_E_INVALID: null context or info. */
+typedef struct dcreg_voxels_follow_info {
+    int64_t n_target, n_touched, n_refit, n_carried, n_kept;
+    int followed;
+    int reserved_;
+} dcreg_voxels_follow_info;
+int dcreg_target_voxels_follow_info(const dcreg_ctx *, dcreg_voxels_follow_info *info);
 
 /* ---------------- solver seam (host only, no device needed) ---------------- */
 /* Config + ICPParameters subset (utils.hpp:82-171) */
