@@ -213,6 +213,8 @@ EXPORTS = [
     "dcreg_voxels_batch_begin", "dcreg_voxels_batch_end", "dcreg_register_frames_voxels", "dcreg_icp_run_trials_voxels",
     "dcreg_register_pairs_voxels", "dcreg_pairs_plan_voxels", "dcreg_pairs_voxels_build", "dcreg_pairs_voxels_get", "dcreg_pairs_voxels_kept",
     "dcreg_voxel_map_params_check", "dcreg_pairs_voxels_box_check", "dcreg_pairs_voxels_batch_begin",
+    "dcreg_default_fpfh_params", "dcreg_fpfh", "dcreg_fpfh_device", "dcreg_target_fpfh", "dcreg_target_fpfh_device", "dcreg_fpfh_debug_counts",
+    "dcreg_feature_match", "dcreg_feature_match_device",
 ]
 
 _lib = None
@@ -742,6 +744,65 @@ def normal_params(k=5, search_radius=0.0, viewpoint=(0.0, 0.0, 0.0)):
     return p
 
 
+class FpfhParams(C.Structure):
+    _fields_ = [("k", C.c_int), ("reserved0_", C.c_int), ("search_radius", C.c_double), ("reserved_", C.c_double * 2)]
+
+
+class FpfhInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_used", C.c_int64), ("n_empty", C.c_int64), ("n_out", C.c_int64)]
+
+
+class MatchInfo(C.Structure):
+    _fields_ = [("n_a_valid", C.c_int64), ("n_b_valid", C.c_int64), ("n_mutual", C.c_int64), ("reserved_", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_fpfh_params": FpfhParams, "dcreg_fpfh_info": FpfhInfo, "dcreg_match_info": MatchInfo})
+FPFH_DIM = 33                            # DCREG_FPFH_DIM
+FPFH_MIN_K, FPFH_MAX_K = 3, 32
+_normal_params = normal_params            # (Context.fpfh has an argument of that name)
+
+
+def _check_fpfh_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_fpfh_params block"""
+    if not isinstance(p, FpfhParams):
+        raise ValueError("%s: fpfh_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not FPFH_MIN_K <= p.k <= FPFH_MAX_K:
+        raise ValueError("%s: k in [%d, %d] is expected, got %d" % (what, FPFH_MIN_K, FPFH_MAX_K, p.k))
+    if not (np.isfinite(p.search_radius) and p.search_radius >= 0.0):
+        raise ValueError("%s: a finite search_radius >= 0 is expected, got %r" % (what, p.search_radius))
+
+
+def fpfh_params(k=16, search_radius=0.0):
+    """dcreg_fpfh_params: k neighbours per point, the point itself among them (PCL FPFHEstimation setKSearch); search_radius > 0 bounds
+    the search (a point keeps the neighbours it has inside it); include/dcreg.h has the rule"""
+    p = FpfhParams()
+    p.k = int(k)
+    p.search_radius = float(search_radius)
+    _check_fpfh_params(p, "fpfh_params")
+    return p
+
+
+def _fpfh_info_dict(i):
+    return {"n_in": i.n_in, "n_used": i.n_used, "n_empty": i.n_empty, "n_out": i.n_out}
+
+
+def _feature_rows(a, what):
+    """descriptor rows as the C-ABI takes them: 2-D float32, the 33 values in the first columns, further columns skipped through the stride"""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype != np.float32 or a.shape[1] < FPFH_DIM:
+        raise ValueError("%s: a 2-D float32 array with at least %d columns is expected, got %s %s" % (what, FPFH_DIM, a.dtype, a.shape))
+    if a.shape[0] > OUTLIER_MAX_POINTS:
+        raise ValueError("%s: at most 2^31 - 1 rows are expected, got %d" % (what, a.shape[0]))
+    return np.ascontiguousarray(a)
+
+
+def _check_device_rows(n, stride, what):
+    if int(n) < 0 or int(n) > OUTLIER_MAX_POINTS:
+        raise ValueError("%s: 0 .. 2^31 - 1 rows are expected, got %d" % (what, int(n)))
+    if int(stride) < FPFH_DIM:
+        raise ValueError("%s: a stride of at least %d floats is expected, got %d" % (what, FPFH_DIM, int(stride)))
+
+
 def _check_voxel_map_params(p, what):
     """the refusals of include/dcreg.h for a dcreg_voxel_map_params block"""
     if not isinstance(p, VoxelMapParams):
@@ -1229,6 +1290,16 @@ def load():
         L.dcreg_voxel_map_params_check.argtypes = [vp, vmp]
         L.dcreg_pairs_voxels_box_check.argtypes = [vp, fp, fp, C.c_double, C.c_int]
         L.dcreg_pairs_voxels_batch_begin.argtypes = [vp, C.c_int, C.c_int, dp, dp, ip, ip, C.POINTER(LinParams)]
+    if hasattr(L, "dcreg_fpfh"):  # (likewise)
+        np_, fpp, fpi = C.POINTER(NormalParams), C.POINTER(FpfhParams), C.POINTER(FpfhInfo)
+        L.dcreg_default_fpfh_params.argtypes = [fpp]
+        for name in ("dcreg_fpfh", "dcreg_fpfh_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, np_, fpp, vp, vp, fpi]
+        for name in ("dcreg_target_fpfh", "dcreg_target_fpfh_device"):
+            getattr(L, name).argtypes = [vp, fpp, vp, C.c_int64, fpi]
+        L.dcreg_fpfh_debug_counts.argtypes = [vp, vp, C.c_int64]
+        for name in ("dcreg_feature_match", "dcreg_feature_match_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(MatchInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -1981,6 +2052,115 @@ class Context:
                                                  n, C.byref(info)), "dcreg_target_normals")
         return (nrm[:n] if want_normals else None, cur[:n] if want_curvature else None, eig[:n] if want_eigenvalues else None,
                 _normal_info_dict(info))
+
+    # ---- FPFH descriptors and feature-space matching (include/dcreg.h: dcreg_fpfh .. dcreg_feature_match)
+    def fpfh(self, cloud, normals=None, normal_params=None, params=None, want_normals=False):
+        """dcreg_fpfh: per point of one cloud ([n, c] float32, x y z first) its FPFH descriptor, 33 floats - three histograms of 11 bins,
+        each summing to 100 (PCL FPFHEstimation with setKSearch; include/dcreg.h has the rule).  normals: [n, c] float32, the normal in
+        the first three columns; None = they are estimated first with normal_params (normal_params(...), None = its defaults) on the same
+        index, and returned with want_normals.  A point without finite coordinates and a finite normal, and an EMPTY point, get NaN.
+        params: fpfh_params(...), None = the defaults.  -> (fpfh [n, 33] float32, normals [n, 3] float32 or None, dict n_in / n_used /
+        n_empty / n_out)"""
+        p = params if params is not None else fpfh_params()
+        _check_fpfh_params(p, "fpfh")
+        a = _points(cloud, "fpfh")
+        n = a.shape[0]
+        nrm_in = npb = None
+        if normals is not None:
+            nrm_in = _points(normals, "fpfh")
+            if nrm_in.shape[0] != n:
+                raise ValueError("fpfh: one normal per point is expected, got %d normals for %d points" % (nrm_in.shape[0], n))
+            if want_normals:
+                raise ValueError("fpfh: want_normals returns the normals the call estimates; these were given")
+        else:
+            npb = normal_params if normal_params is not None else _normal_params()
+            _check_normal_params(npb, "fpfh")
+        out = np.full((max(n, 1), FPFH_DIM), np.nan, np.float32)
+        nrm_out = np.full((max(n, 1), 3), np.nan, np.float32) if want_normals else None
+        info = FpfhInfo()
+        self._check(self._L.dcreg_fpfh(self._h, a.ctypes.data, n, a.shape[1], nrm_in.ctypes.data if nrm_in is not None else None,
+                                       nrm_in.shape[1] if nrm_in is not None else 3, C.byref(npb) if npb is not None else None, C.byref(p),
+                                       out.ctypes.data, nrm_out.ctypes.data if want_normals else None, C.byref(info)), "dcreg_fpfh")
+        return out[:n], (nrm_out[:n] if want_normals else None), _fpfh_info_dict(info)
+
+    def fpfh_device(self, dev_ptr, n, stride, dev_fpfh_ptr, dev_normals_ptr=0, normals_stride=3, normal_params=None, params=None,
+                    dev_normals_out_ptr=0):
+        """dcreg_fpfh_device: the cloud, the normals (0: estimated with normal_params) and the outputs (33 n floats; 3 n floats of
+        estimated normals, 0: not wanted) in device memory.  -> info dict"""
+        p = params if params is not None else fpfh_params()
+        _check_fpfh_params(p, "fpfh_device")
+        _check_device_cloud(n, stride, "fpfh_device")
+        if not dev_fpfh_ptr:
+            raise ValueError("fpfh_device: an output buffer is expected")
+        npb = None
+        if dev_normals_ptr:
+            if int(normals_stride) < 3:
+                raise ValueError("fpfh_device: a normals stride of at least 3 floats is expected, got %d" % int(normals_stride))
+        else:
+            npb = normal_params if normal_params is not None else _normal_params()
+            _check_normal_params(npb, "fpfh_device")
+        info = FpfhInfo()
+        self._check(self._L.dcreg_fpfh_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.c_void_p(dev_normals_ptr or None), int(normals_stride),
+                                              C.byref(npb) if npb is not None else None, C.byref(p), C.c_void_p(dev_fpfh_ptr),
+                                              C.c_void_p(dev_normals_out_ptr or None), C.byref(info)), "dcreg_fpfh_device")
+        return _fpfh_info_dict(info)
+
+    def target_fpfh(self, params=None):
+        """dcreg_target_fpfh: the descriptors of the resident map's points in index order (target_points()), from the kept normals
+        (keep_target_normals / set_target_normals) through the map's own index.  -> (fpfh [n, 33] float32, info dict)"""
+        p = params if params is not None else fpfh_params()
+        _check_fpfh_params(p, "target_fpfh")
+        n = max(int(self.index_info().n_target), 0)
+        out = np.full((max(n, 1), FPFH_DIM), np.nan, np.float32)
+        info = FpfhInfo()
+        self._check(self._L.dcreg_target_fpfh(self._h, C.byref(p), out.ctypes.data, n, C.byref(info)), "dcreg_target_fpfh")
+        return out[:n], _fpfh_info_dict(info)
+
+    def fpfh_debug_counts(self, n):
+        """dcreg_fpfh_debug_counts: the SPFH records behind the descriptor call just made, for its n input points
+        -> (counts [n, 33] uint8, m [n] uint8, has_spfh [n] bool)"""
+        raw = np.zeros((max(int(n), 1), 36), np.uint8)
+        self._check(self._L.dcreg_fpfh_debug_counts(self._h, raw.ctypes.data, int(n)), "dcreg_fpfh_debug_counts")
+        raw = raw[:n]
+        return raw[:, :FPFH_DIM].copy(), raw[:, FPFH_DIM].copy(), raw[:, FPFH_DIM + 1] != 0
+
+    def feature_match(self, a, b, want_second=True, want_mutual=True):
+        """dcreg_feature_match: for every row of a ([n_a, c] float32, 33 values first) its nearest and second-nearest row of b in feature
+        space, ranked by (squared distance in double, index); rows with a non-finite value are neither queries nor candidates.
+        -> dict idx [n_a] int32 (-1: none), d [n_a] float64, idx2 / d2 (want_second), mutual [n_a] uint8 (want_mutual: b's best row of a
+        is the query), n_a_valid, n_b_valid, n_mutual"""
+        a = _feature_rows(a, "feature_match")
+        b = _feature_rows(b, "feature_match")
+        na = a.shape[0]
+        idx = np.full(max(na, 1), -1, np.int32)
+        d = np.full(max(na, 1), np.nan, np.float64)
+        idx2 = np.full(max(na, 1), -1, np.int32) if want_second else None
+        d2 = np.full(max(na, 1), np.nan, np.float64) if want_second else None
+        mutual = np.zeros(max(na, 1), np.uint8) if want_mutual else None
+        info = MatchInfo()
+        self._check(self._L.dcreg_feature_match(self._h, a.ctypes.data, na, a.shape[1], b.ctypes.data, b.shape[0], b.shape[1], idx.ctypes.data,
+                                                d.ctypes.data, idx2.ctypes.data if want_second else None, d2.ctypes.data if want_second else None,
+                                                mutual.ctypes.data if want_mutual else None, C.byref(info)), "dcreg_feature_match")
+        out = {"idx": idx[:na], "d": d[:na], "n_a_valid": info.n_a_valid, "n_b_valid": info.n_b_valid, "n_mutual": info.n_mutual}
+        if want_second:
+            out.update(idx2=idx2[:na], d2=d2[:na])
+        if want_mutual:
+            out["mutual"] = mutual[:na]
+        return out
+
+    def feature_match_device(self, dev_a, n_a, stride_a, dev_b, n_b, stride_b, dev_idx, dev_d, dev_idx2=0, dev_d2=0, dev_mutual=0):
+        """dcreg_feature_match_device: both descriptor sets and the outputs (n_a int32 / float64 / bytes; 0: not wanted) in device memory
+        -> dict n_a_valid / n_b_valid / n_mutual"""
+        _check_device_rows(n_a, stride_a, "feature_match_device")
+        _check_device_rows(n_b, stride_b, "feature_match_device")
+        if not dev_idx or not dev_d:
+            raise ValueError("feature_match_device: the index and distance outputs are expected")
+        info = MatchInfo()
+        self._check(self._L.dcreg_feature_match_device(self._h, C.c_void_p(dev_a or None), int(n_a), int(stride_a), C.c_void_p(dev_b or None), int(n_b),
+                                                       int(stride_b), C.c_void_p(dev_idx), C.c_void_p(dev_d), C.c_void_p(dev_idx2 or None),
+                                                       C.c_void_p(dev_d2 or None), C.c_void_p(dev_mutual or None), C.byref(info)),
+                    "dcreg_feature_match_device")
+        return {"n_a_valid": info.n_a_valid, "n_b_valid": info.n_b_valid, "n_mutual": info.n_mutual}
 
     # ---- kept normals and the second engine (include/dcreg.h: dcreg_target_normals_keep .. dcreg_icp_run_normals)
     def keep_target_normals(self, params=None):

@@ -2430,6 +2430,7 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
         if (!(v == 1.0 || v == 7.0 || v == 27.0)) { c->fail("voxels_neighbors is %g: 1, 7 or 27 expected", v); return DCREG_E_INVALID; }
         c->opt_voxels_neighbors = (int)v;
     }
+    else if (k == "feature_match_split") c->opt_feature_match_split = (int64_t)std::min(std::max(v, 0.0), 2147483647.0);   // dcreg_feature_match: rows of b per block column (0: from the sizes; no result depends on it)
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;

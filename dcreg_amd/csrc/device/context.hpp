@@ -680,6 +680,32 @@ struct dcreg_ctx {
     };
     PairVoxBufs pvox;
 
+    // FPFH descriptors and feature-space matching (features.hip: dcreg_fpfh*, dcreg_target_fpfh*, dcreg_feature_match*).  Scratch of one
+    // call, kept for the next.  Descriptors: the caller's normals as uploaded (the host form), per used point in cell order the neighbour
+    // list ([slot][point]: position in the sorted array and d2, k slots) and the SPFH record (12 words: 33 byte counts, then m and the
+    // "has an SPFH" flag), the 33 floats per input point, the call's counts ([0] descriptors, [1] empty points, [2] non-finite kept
+    // normals of the map form).  Matching: both descriptor sets (the host form), per row of either set its valid flag, per (split, query)
+    // the partial winners {D1, D2, {j1, j2}}, the results of both directions and the counts ([0] valid a, [1] valid b, [2] mutual).
+    // The cloud form packs, compacts and indexes its cloud in the outlier scratch, as the normals do.
+    struct FeatureBufs {
+        DevBuf<float> nrm_in, out;
+        DevBuf<uint32_t> nb_pos;
+        DevBuf<float> nb_d2;
+        DevBuf<uint4> spfh;
+        DevBuf<unsigned long long> cnt;
+        DevBuf<float> a, b;
+        DevBuf<uint8_t> va, vb, mutual;
+        DevBuf<double> part_d;
+        DevBuf<int32_t> part_i;
+        DevBuf<int32_t> idx, idx2, idx_b;
+        DevBuf<double> d1, d2;
+        // dcreg_fpfh_debug_counts: the sorted points, their number and the input's size of the last descriptor call, and the export
+        const float4 *last_q = nullptr; int64_t last_nq = 0, last_n = 0;
+        DevBuf<uint32_t> dbg;
+    };
+    FeatureBufs feat;
+    int64_t opt_feature_match_split = 0;                      // "feature_match_split": rows of b per block column of k_match (0: from the sizes; tests)
+
     void fail(const char *fmt, ...);
 };
 
@@ -913,6 +939,11 @@ int outlier_rings(const GridDev &g, float bound);
 int outlier_used_compact(dcreg_ctx *c, const float4 *in, int64_t n);
 // normals.hip: the parameter refusals of dcreg_normals (engine.cpp reaches it through dcreg_normal_params_check)
 int normals_check(dcreg_ctx *c, const dcreg_normal_params *p);
+// normals.hip, for features.hip: dcreg_normals of a cloud that is already indexed (q: its nq used points in cell order behind the grid g,
+// w = the input index; nq = 0: no index, every used point sparse) - normals and curvature of the n input points into c->nrm.normal /
+// curv, NaN where a point has none; waits for the stream
+int normals_to_scratch(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int64_t n, int64_t n_used, const dcreg_normal_params *p,
+                       dcreg_normal_info *info);
 // normals.hip: the kept normals follow an update of the map ("normals_follow", include/dcreg.h).  normals_follow_wanted: asked BEFORE the
 // update drops them (option on, normals kept, and kept by dcreg_target_normals_keep).  normals_follow_carry (a removal, beside k_crop_raw,
 // before anything is swapped): the survivors' normals and reaches compacted by flag_r / pos_r into the alt arrays; false: out of memory,

@@ -1,0 +1,597 @@
+// FPFH descriptors and feature-space matching on the device (include/dcreg.h: dcreg_fpfh*, dcreg_target_fpfh*, dcreg_feature_match*): the
+// first two stages of a correspondence-based global alignment, with the rules of the header, bitwise the numpy reference of
+// tests/fpfh_ref.py up to the header's one freedom (atan2 at an interior bin edge of theta).
+//   (cloud form)    the cloud packed, the points without a finite normal made non-finite (k_fpfh_unuse), the used points compacted and
+//                   indexed: the first step of the outlier pass (outliers.hip outlier_index_used); normals == NULL: dcreg_normals first,
+//                   on the same index (normals.hip normals_to_scratch).  The map form searches the map's own index
+//   k_fpfh_spfh<K>  one lane per used point, in the index's cell order: the ring walk of k_nrm with its heap (heap_nrm.hpp); the lane
+//                   writes its neighbour list - position and d2, rank order, k slots - and walks it once more for the pair features.
+//                   The 33 counters are indexed by a computed bin: they live as bytes in the lane's column of the wave's RunList, which
+//                   is free once the search is over (9 words of s[][lane]), never in a register array
+//   k_fpfh_sum      behind it (every point needs its neighbours' counts): one lane per used point gathers them through the list and
+//                   accumulates 33 doubles in rank order (statically indexed: registers), normalises and writes at the input index
+//   k_match         one query row per lane, its 33 values as doubles in registers; the candidates go through LDS in tiles of kMatchTile
+//                   rows widened to double once, every lane reading the same row (a broadcast); the lane keeps its best two (D, j).
+//                   blockIdx.y takes a range of candidates ("split"): many blocks for few queries against many candidates
+//   k_match_merge   the partial winners of the splits merged in ascending split order - candidates arrive in ascending j everywhere, so
+//                   a strict < keeps the lowest index among equal distances and the result does not depend on the split
+//   (mutual)        k_match + k_match_merge with the roles swapped, then k_match_mutual
+// A result depends on the inputs and the parameters only: the index decides how fast the neighbours are found, never which.
+#include <cmath>
+#include <cstring>
+
+#include <hip/hip_runtime.h>
+
+#include "../../../include/dcreg_debug.h"
+#include "context.hpp"
+#include "heap_nrm.hpp"
+
+// every multiply and add below rounds once: the rules are stated operation by operation
+#pragma clang fp contract(off)
+
+namespace dcreg {
+namespace {
+
+constexpr int kMinK = 3, kMaxK = 32;
+constexpr int kDim = 33;                                 // DCREG_FPFH_DIM
+constexpr int kCountWords = 9;                           // 33 byte counters
+constexpr int kMatchBlock = 256, kMatchTile = 128;       // queries per block, candidate rows per LDS tile (33 KiB of doubles)
+constexpr double kPi = 3.14159265358979323846;
+
+inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
+DCREG_DEVFN bool finitef(float x) { return fabsf(x) <= 3.4028235e38f; }
+
+static __global__ void k_fpfh_fill(float *__restrict__ a, int64_t n, float v) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
+// a point without a finite normal is not used: its x becomes NaN before the used points are compacted
+static __global__ void k_fpfh_unuse(float4 *__restrict__ pts, int64_t n, const float *__restrict__ nrm, int64_t nstride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *q = nrm + (size_t)i * (size_t)nstride;
+    if (!(finitef(q[0]) && finitef(q[1]) && finitef(q[2]))) pts[i].x = __builtin_nanf("");
+}
+
+// the map form: cnt[2] += kept normals that are not finite (one atomic per wave)
+static __global__ void k_fpfh_bad(const float4 *__restrict__ nrm, int64_t n, unsigned long long *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (i < n) { const float4 v = nrm[i]; bad = !(finitef(v.x) && finitef(v.y) && finitef(v.z)); }
+    const unsigned long long B = __ballot(bad);
+    if (B != 0ull && (int)(threadIdx.x & 63) == __ffsll(B) - 1) atomicAdd(cnt + 2, (unsigned long long)__popcll(B));
+}
+
+DCREG_DEVFN int fpfh_bin(double x) { return (int)fmin(fmax(floor(x), 0.0), 10.0); }
+
+// The body of one lane of k_fpfh_spfh: the point at position i of the index's cell order (its input index in w).  nrm: the normals by
+// input index, nstride floats apart.  nb_pos / nb_d2: [slot][point] lists of nq points; a slot that was never filled keeps position
+// kNoIdx.  spfh: 3 uint4 per point - nine words of byte counts (bin b in byte b & 3 of word b >> 2), then m | has << 8
+// (one body for the cloud form and the map form: they differ in where the index and the normals come from)
+template <int K>
+DCREG_DEVFN void spfh_point(uint32_t i, uint32_t nq, const float4 s4, const GridDev &g, RunList &rl, float bound_f, int max_ring, int k,
+                            const float *__restrict__ nrm, int64_t nstride, uint32_t *nb_pos, float *nb_d2, uint4 *__restrict__ spfh) {
+    HeapNrm<K> hp;
+    hp.k = k;
+    knn_search<HeapNrm<K>>(g, rl, s4.x, s4.y, s4.z, bound_f, max_ring, hp);
+    int m = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j >= K - k) {
+            const size_t at = (size_t)(j - (K - k)) * nq + i;
+            nb_pos[at] = hp.pos[j];
+            nb_d2[at] = __uint_as_float((uint32_t)(hp.key[j] >> 32));
+            m += hp.pos[j] != kNoIdx ? 1 : 0;         // (sorted: the filled slots come first)
+        }
+    // the search is over: the lane's column of the run list holds its 33 counters now
+    const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+    for (int w = 0; w < kCountWords; ++w) rl.s[w][lane] = 0u;
+    const uint32_t self = __float_as_uint(s4.w);
+    const float *np_ = nrm + (size_t)self * (size_t)nstride;
+    const double px = (double)s4.x, py = (double)s4.y, pz = (double)s4.z;
+    const double npx = (double)np_[0], npy = (double)np_[1], npz = (double)np_[2];
+#pragma unroll 1
+    for (int j = 0; j < m; ++j) {
+        const size_t at = (size_t)j * nq + i;
+        const float d2 = nb_d2[at];
+        if (!(d2 > 0.f)) continue;
+        const float4 c = g.pts[nb_pos[at]];
+        const float *nq_ = nrm + (size_t)__float_as_uint(c.w) * (size_t)nstride;
+        const double nqx = (double)nq_[0], nqy = (double)nq_[1], nqz = (double)nq_[2];
+        double dx = (double)c.x - px, dy = (double)c.y - py, dz = (double)c.z - pz;
+        const double f4 = sqrt((dx * dx + dy * dy) + dz * dz);
+        if (f4 == 0.0) continue;
+        const double a1 = ((npx * dx + npy * dy) + npz * dz) / f4;
+        const double a2 = ((nqx * dx + nqy * dy) + nqz * dz) / f4;
+        const bool sw = fabs(a1) < fabs(a2);
+        const double n1x = sw ? nqx : npx, n1y = sw ? nqy : npy, n1z = sw ? nqz : npz;
+        const double n2x = sw ? npx : nqx, n2y = sw ? npy : nqy, n2z = sw ? npz : nqz;
+        const double phi = sw ? -a2 : a1;
+        if (sw) { dx = -dx; dy = -dy; dz = -dz; }
+        double vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
+        const double vn = sqrt((vx * vx + vy * vy) + vz * vz);
+        if (vn == 0.0) continue;
+        vx = vx / vn; vy = vy / vn; vz = vz / vn;
+        const double wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
+        const double alpha = (vx * n2x + vy * n2y) + vz * n2z;
+        const double theta = atan2((wx * n2x + wy * n2y) + wz * n2z, (n1x * n2x + n1y * n2y) + n1z * n2z);
+        const int b0 = fpfh_bin(11.0 * ((theta + kPi) / (2.0 * kPi)));
+        const int b1 = 11 + fpfh_bin(11.0 * ((alpha + 1.0) * 0.5));
+        const int b2 = 22 + fpfh_bin(11.0 * ((phi + 1.0) * 0.5));
+        rl.s[b0 >> 2][lane] += 1u << ((b0 & 3) * 8);
+        rl.s[b1 >> 2][lane] += 1u << ((b1 & 3) * 8);
+        rl.s[b2 >> 2][lane] += 1u << ((b2 & 3) * 8);
+    }
+    uint32_t w[kCountWords], any = 0u;
+#pragma unroll
+    for (int u = 0; u < kCountWords; ++u) { w[u] = rl.s[u][lane]; any |= w[u]; }
+    const uint32_t has = (m >= 2 && any != 0u) ? 1u : 0u;
+    spfh[3 * (size_t)i] = make_uint4(w[0], w[1], w[2], w[3]);
+    spfh[3 * (size_t)i + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+    spfh[3 * (size_t)i + 2] = make_uint4(w[8], (uint32_t)m | (has << 8), 0u, 0u);
+}
+
+template <int K>
+static __global__ __launch_bounds__(kBlock) void k_fpfh_spfh(const float4 *__restrict__ q, uint32_t n, GridDev g, float bound_f, int max_ring, int k,
+                                                             const float *__restrict__ nrm, int64_t nstride, uint32_t *nb_pos, float *nb_d2,
+                                                             uint4 *__restrict__ spfh) {
+    __shared__ RunList runs[kBlock / kWave];
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    spfh_point<K>(i, n, q[i], g, runs[threadIdx.x / kWave], bound_f, max_ring, k, nrm, nstride, nb_pos, nb_d2, spfh);
+}
+
+// One lane per used point, in cell order: F_b over the list in rank order, the three blocks normalised, 33 floats at the point's input
+// index.  cnt[0] += points with a descriptor, cnt[1] += empty points (one atomic pair per wave)
+static __global__ __launch_bounds__(kBlock) void k_fpfh_sum(const float4 *__restrict__ q, uint32_t n, int k, const uint32_t *__restrict__ nb_pos,
+                                                            const float *__restrict__ nb_d2, const uint4 *__restrict__ spfh, float *__restrict__ out,
+                                                            unsigned long long *__restrict__ cnt) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    // (-0.0 is the identity of the IEEE addition: the sums start with their first term)
+    double acc[kDim];
+#pragma unroll
+    for (int b = 0; b < kDim; ++b) acc[b] = -0.0;
+#pragma unroll 1
+    for (int j = 0; j < k; ++j) {
+        const size_t at = (size_t)j * n + i;
+        const uint32_t pos = nb_pos[at];
+        if (pos == kNoIdx) break;
+        const float d2 = nb_d2[at];
+        if (!(d2 > 0.f)) continue;
+        const uint4 r2 = spfh[3 * (size_t)pos + 2];
+        if ((r2.y >> 8) == 0u) continue;
+        const uint4 r0 = spfh[3 * (size_t)pos], r1 = spfh[3 * (size_t)pos + 1];
+        const uint32_t w[kCountWords] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x};
+        const double wt = 1.0 / (double)d2;
+        const double sc = 100.0 / (double)((int)(r2.y & 0xffu) - 1);
+#pragma unroll
+        for (int b = 0; b < kDim; ++b) {
+            const double s = (double)((w[b >> 2] >> ((b & 3) * 8)) & 0xffu) * sc;
+            acc[b] = acc[b] + wt * s;
+        }
+    }
+    double S[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        double s = acc[11 * t];
+#pragma unroll
+        for (int b = 1; b < 11; ++b) s = s + acc[11 * t + b];
+        S[t] = s;
+    }
+    const bool full = S[0] > 0.0 && S[1] > 0.0 && S[2] > 0.0;
+    if (full) {
+        float *o = out + (size_t)kDim * (size_t)__float_as_uint(q[i].w);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const double f = 100.0 / S[t];
+#pragma unroll
+            for (int b = 0; b < 11; ++b) o[11 * t + b] = (float)(acc[11 * t + b] * f);
+        }
+    }
+    const unsigned long long A = __ballot(true), F = __ballot(full);
+    if ((int)(threadIdx.x & 63) == __ffsll(A) - 1) {
+        const unsigned long long nf = (unsigned long long)__popcll(F), ne = (unsigned long long)__popcll(A) - nf;
+        if (nf) atomicAdd(cnt, nf);
+        if (ne) atomicAdd(cnt + 1, ne);
+    }
+}
+
+// dcreg_fpfh_debug_counts: the SPFH record of the point at sorted position i, 36 bytes at its input index (33 counts, m, has, 0)
+static __global__ void k_fpfh_counts(const float4 *__restrict__ q, uint32_t n, const uint4 *__restrict__ spfh, uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 r0 = spfh[3 * (size_t)i], r1 = spfh[3 * (size_t)i + 1], r2 = spfh[3 * (size_t)i + 2];
+    uint32_t *o = out + (size_t)kCountWords * (size_t)__float_as_uint(q[i].w);
+    o[0] = r0.x; o[1] = r0.y; o[2] = r0.z; o[3] = r0.w; o[4] = r1.x; o[5] = r1.y; o[6] = r1.z; o[7] = r1.w;
+    o[8] = (r2.x & 0xffu) | ((r2.y & 0xffu) << 8) | ((r2.y >> 8) << 16);
+}
+
+// ------------------------------------------------------------------------------------------ matching
+// flag[i] = row i holds 33 finite values; *cnt += their number (one atomic per wave)
+static __global__ void k_match_valid(const float *__restrict__ rows, int64_t n, int64_t stride, uint8_t *__restrict__ flag,
+                                     unsigned long long *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool ok = false;
+    if (i < n) {
+        const float *r = rows + (size_t)i * (size_t)stride;
+        ok = true;
+        for (int c = 0; c < kDim; ++c) ok = ok && finitef(r[c]);
+        flag[i] = ok ? 1 : 0;
+    }
+    const unsigned long long V = __ballot(ok);
+    if (V != 0ull && (int)(threadIdx.x & 63) == __ffsll(V) - 1) atomicAdd(cnt, (unsigned long long)__popcll(V));
+}
+
+// the running best two of a lane: candidates arrive in ascending j, so strict comparisons rank by (D, j)
+DCREG_DEVFN void best_two(double D, int32_t j, double &d1, int32_t &j1, double &d2, int32_t &j2) {
+    // (selects, not branches: behind branches the compiler addresses the four values through memory)
+    const bool first = D < d1, second = D < d2;
+    d2 = first ? d1 : (second ? D : d2); j2 = first ? j1 : (second ? j : j2);
+    d1 = first ? D : d1; j1 = first ? j : j1;
+}
+
+// Block (x, y): queries [256 x, 256 x + 256) of a against the candidates [chunk y, chunk y + chunk) of b; ok_b: b's valid flags.  The
+// partial winners of split y and query i go to part_d[2 (y n_a + i) ..] (D1, D2) and part_i[2 (y n_a + i) ..] (j1, j2; -1: none).  A
+// query with a non-finite value computes NaN distances, which win nothing
+static __global__ __launch_bounds__(kMatchBlock) void k_match(const float *__restrict__ a, uint32_t n_a, int64_t stride_a, const float *__restrict__ b,
+                                                              uint32_t n_b, int64_t stride_b, const uint8_t *__restrict__ ok_b, uint32_t chunk,
+                                                              double *__restrict__ part_d, int32_t *__restrict__ part_i) {
+    __shared__ double tile[kMatchTile * kDim];
+    __shared__ uint8_t ok[kMatchTile];
+    const uint32_t tid = threadIdx.x, i = blockIdx.x * kMatchBlock + tid;
+    const bool live = i < n_a;
+    double q[kDim];
+    {
+        const float *r = a + (size_t)(live ? i : 0u) * (size_t)stride_a;
+#pragma unroll
+        for (int c = 0; c < kDim; ++c) q[c] = (double)r[c];
+    }
+    const uint32_t j_begin = blockIdx.y * chunk, j_end = n_b - j_begin > chunk ? j_begin + chunk : n_b;      // (j_begin < n_b: the grid's y)
+    double d1 = __builtin_inf(), d2 = __builtin_inf();
+    int32_t j1 = -1, j2 = -1;
+    for (uint32_t t0 = j_begin; t0 < j_end; t0 += kMatchTile) {
+        const uint32_t rows = min((uint32_t)kMatchTile, j_end - t0);
+        __syncthreads();                                  // (the tile of the trip before is read no more)
+        for (uint32_t e = tid; e < rows * kDim; e += kMatchBlock) {
+            const uint32_t r = e / kDim, c = e - r * kDim;
+            tile[e] = (double)b[(size_t)(t0 + r) * (size_t)stride_b + c];
+        }
+        if (tid < rows) ok[tid] = ok_b[t0 + tid];
+        __syncthreads();
+        for (uint32_t r = 0; r < rows; ++r) {
+            if (!ok[r]) continue;                         // (uniform: every lane reads the same flag)
+            const double *row = tile + r * kDim;
+            double x = q[0] - row[0];
+            double D = x * x;
+#pragma unroll
+            for (int c = 1; c < kDim; ++c) { x = q[c] - row[c]; D = D + x * x; }
+            best_two(D, (int32_t)(t0 + r), d1, j1, d2, j2);
+        }
+    }
+    if (live) {
+        const size_t at = 2 * ((size_t)blockIdx.y * n_a + i);
+        part_d[at] = d1; part_d[at + 1] = d2;
+        part_i[at] = j1; part_i[at + 1] = j2;
+    }
+}
+
+// the splits' winners of query i merged in ascending split order; an invalid query gets -1 and NaN.  Any output may be null
+static __global__ void k_match_merge(uint32_t n_a, uint32_t n_split, const double *__restrict__ part_d, const int32_t *__restrict__ part_i,
+                                     const uint8_t *__restrict__ ok_a, int32_t *__restrict__ idx, double *__restrict__ dist, int32_t *__restrict__ idx2,
+                                     double *__restrict__ dist2) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_a) return;
+    double d1 = __builtin_inf(), d2 = __builtin_inf();
+    int32_t j1 = -1, j2 = -1;
+    for (uint32_t s = 0; s < n_split; ++s) {
+        const size_t at = 2 * ((size_t)s * n_a + i);
+        if (part_i[at] >= 0) best_two(part_d[at], part_i[at], d1, j1, d2, j2);
+        if (part_i[at + 1] >= 0) best_two(part_d[at + 1], part_i[at + 1], d1, j1, d2, j2);
+    }
+    if (!ok_a[i]) { d1 = d2 = __builtin_nan(""); j1 = j2 = -1; }
+    if (idx) idx[i] = j1;
+    if (dist) dist[i] = d1;
+    if (idx2) idx2[i] = j2;
+    if (dist2) dist2[i] = d2;
+}
+
+// mutual[i] = the best row of a for b[idx[i]] is i; cnt[2] += their number
+static __global__ void k_match_mutual(uint32_t n_a, const int32_t *__restrict__ idx, const int32_t *__restrict__ idx_b, uint8_t *__restrict__ mutual,
+                                      unsigned long long *__restrict__ cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool mu = false;
+    if (i < n_a) {
+        const int32_t j = idx[i];
+        mu = j >= 0 && idx_b[j] == (int32_t)i;
+        mutual[i] = mu ? 1 : 0;
+    }
+    const unsigned long long M = __ballot(mu);
+    if (M != 0ull && (int)(threadIdx.x & 63) == __ffsll(M) - 1) atomicAdd(cnt + 2, (unsigned long long)__popcll(M));
+}
+
+// ------------------------------------------------------------------------------------------ descriptors: the host side
+int fpfh_check(dcreg_ctx *c, const dcreg_fpfh_params *p) {
+    if (!p) { c->fail("null fpfh parameters"); return DCREG_E_INVALID; }
+    if (p->k < kMinK || p->k > kMaxK) { c->fail("fpfh k is %d: %d .. %d expected", p->k, kMinK, kMaxK); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->search_radius) && p->search_radius >= 0.0)) { c->fail("fpfh search_radius is %g: finite and >= 0 expected", p->search_radius); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+
+// memory another stream may have written (a device-pointer argument): the context's own stream waits for the legacy default stream, as
+// upload_cloud orders a device cloud
+int order_after_null_stream(dcreg_ctx *c) {
+    if (c->stream != c->own_stream) return DCREG_OK;
+    if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    return DCREG_OK;
+}
+
+template <int K>
+void launch_spfh(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const float *nrm, int64_t nstride) {
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    hipLaunchKernelGGL(k_fpfh_spfh<K>, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, bound, max_ring, k, nrm, nstride,
+                       F.nb_pos.data(), F.nb_d2.data(), F.spfh.data());
+}
+
+// The outputs of n points start as NaN; the nq used points at q (cell order, w = the output index) behind the grid g get theirs from the
+// normals at nrm (by input index); then the copy to the caller and the counts.  nq = 0: no used point.  The queries ARE the grid's points:
+// a neighbour's position in the sorted array is also its lane in both kernels, which is how k_fpfh_sum finds its counts
+int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float *nrm, int64_t nstride, const dcreg_fpfh_params *p,
+             float *out, bool on_device, dcreg_fpfh_info *info) {
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    const size_t k = (size_t)p->k, nqs = (size_t)std::max<int64_t>(nq, 1);
+    if (F.out.ensure(c, (size_t)kDim * (size_t)n) || F.cnt.ensure(c, 3) || F.nb_pos.ensure(c, k * nqs) || F.nb_d2.ensure(c, k * nqs) ||
+        F.spfh.ensure(c, 3 * nqs))
+        return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_fpfh_fill, dim3(blocks((int64_t)kDim * n, 256)), dim3(256), 0, c->stream, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
+    HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
+    unsigned long long cnt[2] = {0, 0};
+    F.last_q = nq > 0 ? g.pts : nullptr; F.last_nq = nq; F.last_n = n;      // (dcreg_fpfh_debug_counts)
+    if (nq > 0) {
+        const float4 *q = g.pts;
+        float bound = 3.0e38f;
+        int max_ring = -1;
+        if (p->search_radius > 0.0) {
+            bound = (float)(p->search_radius * p->search_radius);
+            if (!(bound <= 3.0e38f)) bound = 3.0e38f;
+            max_ring = outlier_rings(g, bound);
+        }
+        if (p->k <= 8) launch_spfh<8>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
+        else if (p->k <= 16) launch_spfh<16>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
+        else launch_spfh<32>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
+        hipLaunchKernelGGL(k_fpfh_sum, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, p->k, F.nb_pos.data(), F.nb_d2.data(),
+                           F.spfh.data(), F.out.data(), F.cnt.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (info) { info->n_in = n; info->n_used = nq; info->n_empty = (int64_t)cnt[1]; info->n_out = (int64_t)cnt[0]; }
+    return DCREG_OK;
+}
+
+// the n packed points at pts lose those without a finite normal, the rest is compacted and indexed in the outlier scratch
+int fpfh_index(dcreg_ctx *c, float4 *pts, int64_t n, const float *nrm, int64_t nstride, double hint, int64_t *n_used) {
+    hipLaunchKernelGGL(k_fpfh_unuse, dim3(blocks(n, 256)), dim3(256), 0, c->stream, pts, n, nrm, nstride);
+    HIP_TRY(c, hipGetLastError());
+    return outlier_index_used(c, pts, n, hint, 1, n_used);
+}
+
+// dcreg_fpfh*: the cloud packed, the normals given or estimated, the used points indexed, the two kernels, the copies
+int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const float *normals, int64_t nstride, bool on_device,
+               const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *out, float *normals_out, dcreg_fpfh_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = fpfh_check(c, p)) return rc;
+    if (!normals && !np) { c->fail("no normals and no normal parameters: one of them is expected"); return DCREG_E_INVALID; }
+    if (!normals) if (int rc = normals_check(c, np)) return rc;
+    if (n < 0 || stride < 3 || (normals && nstride < 3)) { c->fail("invalid fpfh arguments"); return DCREG_E_INVALID; }
+    if (n > (int64_t)INT32_MAX) { c->fail("too many points for one descriptor call (%lld)", (long long)n); return DCREG_E_INVALID; }
+    if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (n == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::OutlierBufs &B = c->outl;
+    if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
+    const double hint = p->search_radius;
+    int64_t n_used = 0;
+    const float *nrm = normals;
+    if (normals) {
+        if (!on_device) {
+            const size_t words = (size_t)(n - 1) * (size_t)nstride + 3;            // (the last point's padding is not the caller's to give)
+            if (c->feat.nrm_in.ensure(c, words)) return DCREG_E_NOMEM;
+            HIP_TRY(c, hipMemcpyAsync(c->feat.nrm_in.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
+            nrm = c->feat.nrm_in.data();
+        }
+        if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
+    } else {
+        int64_t n_finite = 0;
+        if (int rc = outlier_index_used(c, B.pts.data(), n, hint, 1, &n_finite)) return rc;
+        dcreg_normal_info ni{};
+        const bool indexed = n_finite >= np->k;            // (fewer: every point is sparse, as dcreg_normals says it)
+        if (int rc = normals_to_scratch(c, indexed ? B.idx.sorted.data() : nullptr, indexed ? n_finite : 0, indexed ? B.idx.grid : GridDev{}, n, n_finite, np, &ni))
+            return rc;
+        nrm = c->nrm.normal.data();
+        nstride = 3;
+        if (normals_out)
+            HIP_TRY(c, hipMemcpyAsync(normals_out, nrm, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        n_used = n_finite;
+        // (a finite point without a normal is not used: the index over the finite points serves only when every one of them has one)
+        if (ni.n_out != n_finite) if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
+    }
+    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, nstride, p, out, on_device, info);
+}
+
+// dcreg_target_fpfh*: the whole map's points through the map's own index and its kept normals
+int fpfh_map(dcreg_ctx *c, bool on_device, const dcreg_fpfh_params *p, float *out, int64_t capacity, dcreg_fpfh_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (int rc = fpfh_check(c, p)) return rc;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
+    if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
+    const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;      // the whole map's index, whichever is active
+    const int64_t n = wm.n;
+    if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (info) std::memset(info, 0, sizeof(*info));
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    if (F.cnt.ensure(c, 3)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(F.cnt.data() + 2, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_fpfh_bad, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->nicp.normals.data(), n, F.cnt.data());
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, F.cnt.data() + 2, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const float *nrm = (const float *)c->nicp.normals.data();
+    if (bad == 0) return fpfh_run(c, n, wm.grid, n, nrm, 4, p, out, on_device, info);
+    // some map points have no normal: they are no candidates, so the others are indexed on their own, as a cloud's
+    dcreg_ctx::OutlierBufs &B = c->outl;
+    if (B.pts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemcpyAsync(B.pts.data(), wm.raw.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    int64_t n_used = 0;
+    if (int rc = fpfh_index(c, B.pts.data(), n, nrm, 4, p->search_radius, &n_used)) return rc;
+    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, 4, p, out, on_device, info);
+}
+
+// dcreg_fpfh_debug_counts (include/dcreg_debug.h)
+int fpfh_debug_counts(dcreg_ctx *c, uint8_t *out, int64_t capacity) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (F.last_n <= 0) { c->fail("no descriptor call to report"); return DCREG_E_STATE; }
+    if (capacity < F.last_n) { c->fail("the call had %lld points, the capacity is %lld", (long long)F.last_n, (long long)capacity); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t words = (size_t)kCountWords * (size_t)F.last_n;
+    if (F.dbg.ensure(c, words)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(F.dbg.data(), 0, sizeof(uint32_t) * words, c->stream));
+    if (F.last_nq > 0)
+        hipLaunchKernelGGL(k_fpfh_counts, dim3(blocks(F.last_nq, 256)), dim3(256), 0, c->stream, F.last_q, (uint32_t)F.last_nq, F.spfh.data(), F.dbg.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, F.dbg.data(), sizeof(uint32_t) * words, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
+// ------------------------------------------------------------------------------------------ matching: the host side
+// one direction: the best two rows of y for every row of x, through the partial winners; the outputs (device, may be null) are queued
+int match_pass(dcreg_ctx *c, const float *x, int64_t n_x, int64_t stride_x, const uint8_t *ok_x, const float *y, int64_t n_y, int64_t stride_y,
+               const uint8_t *ok_y, int32_t *idx, double *dist, int32_t *idx2, double *dist2) {
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    const int64_t blocks_x = (n_x + kMatchBlock - 1) / kMatchBlock;
+    int64_t chunk = c->opt_feature_match_split, n_split = 0;
+    if (n_y > 0) {
+        if (chunk <= 0) {                                   // about a thousand blocks, a split no shorter than a tile
+            const int64_t want = std::max<int64_t>(1, 1024 / blocks_x), tiles = (n_y + kMatchTile - 1) / kMatchTile;
+            chunk = (tiles + std::min(want, tiles) - 1) / std::min(want, tiles) * kMatchTile;
+        }
+        chunk = std::max<int64_t>(chunk, (n_y + 65534) / 65535);          // (blockIdx.y)
+        n_split = (n_y + chunk - 1) / chunk;
+    }
+    const size_t parts = 2 * (size_t)std::max<int64_t>(n_split, 1) * (size_t)n_x;
+    if (F.part_d.ensure(c, parts) || F.part_i.ensure(c, parts)) return DCREG_E_NOMEM;
+    if (n_split > 0)
+        hipLaunchKernelGGL(k_match, dim3((unsigned)blocks_x, (unsigned)n_split), dim3(kMatchBlock), 0, c->stream, x, (uint32_t)n_x, stride_x, y, (uint32_t)n_y,
+                           stride_y, ok_y, (uint32_t)chunk, F.part_d.data(), F.part_i.data());
+    hipLaunchKernelGGL(k_match_merge, dim3(blocks(n_x, 256)), dim3(256), 0, c->stream, (uint32_t)n_x, (uint32_t)n_split, F.part_d.data(), F.part_i.data(), ok_x,
+                       idx, dist, idx2, dist2);
+    HIP_TRY(c, hipGetLastError());
+    return DCREG_OK;
+}
+
+int feature_match(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, bool on_device,
+                  int32_t *idx_out, double *d_out, int32_t *idx2_out, double *d2nd_out, uint8_t *mutual_out, dcreg_match_info *info) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    if (n_a < 0 || n_b < 0 || stride_a < kDim || stride_b < kDim) { c->fail("invalid feature matching arguments"); return DCREG_E_INVALID; }
+    if (n_a > (int64_t)INT32_MAX || n_b > (int64_t)INT32_MAX) { c->fail("too many rows for one feature matching call"); return DCREG_E_INVALID; }
+    if ((n_a > 0 && !a) || (n_b > 0 && !b)) { c->fail("null descriptor buffer"); return DCREG_E_INVALID; }
+    if (!idx_out || !d_out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (n_a == 0) return DCREG_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    const size_t na = (size_t)n_a, nb = (size_t)std::max<int64_t>(n_b, 1);
+    if (F.va.ensure(c, na) || F.vb.ensure(c, nb) || F.cnt.ensure(c, 3) || F.idx.ensure(c, na) || F.d1.ensure(c, na) || F.idx2.ensure(c, na) ||
+        F.d2.ensure(c, na) || (mutual_out && (F.mutual.ensure(c, na) || F.idx_b.ensure(c, nb))))
+        return DCREG_E_NOMEM;
+    const float *da = a, *db = b;
+    if (on_device) {
+        if (int rc = order_after_null_stream(c)) return rc;
+    } else {
+        const size_t wa = (na - 1) * (size_t)stride_a + kDim, wb = n_b > 0 ? (size_t)(n_b - 1) * (size_t)stride_b + kDim : 0;
+        if (F.a.ensure(c, wa) || F.b.ensure(c, wb)) return DCREG_E_NOMEM;
+        HIP_TRY(c, hipMemcpyAsync(F.a.data(), a, sizeof(float) * wa, hipMemcpyHostToDevice, c->stream));
+        if (wb) HIP_TRY(c, hipMemcpyAsync(F.b.data(), b, sizeof(float) * wb, hipMemcpyHostToDevice, c->stream));
+        da = F.a.data(); db = F.b.data();
+    }
+    HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 3 * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_match_valid, dim3(blocks(n_a, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, F.va.data(), F.cnt.data());
+    if (n_b > 0) hipLaunchKernelGGL(k_match_valid, dim3(blocks(n_b, 256)), dim3(256), 0, c->stream, db, n_b, stride_b, F.vb.data(), F.cnt.data() + 1);
+    if (int rc = match_pass(c, da, n_a, stride_a, F.va.data(), db, n_b, stride_b, F.vb.data(), F.idx.data(), F.d1.data(), F.idx2.data(), F.d2.data())) return rc;
+    if (mutual_out) {
+        if (n_b > 0)
+            if (int rc = match_pass(c, db, n_b, stride_b, F.vb.data(), da, n_a, stride_a, F.va.data(), F.idx_b.data(), nullptr, nullptr, nullptr)) return rc;
+        hipLaunchKernelGGL(k_match_mutual, dim3(blocks(n_a, 256)), dim3(256), 0, c->stream, (uint32_t)n_a, F.idx.data(), F.idx_b.data(), F.mutual.data(), F.cnt.data());
+        HIP_TRY(c, hipGetLastError());
+    }
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    unsigned long long cnt[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(idx_out, F.idx.data(), sizeof(int32_t) * na, kind, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_out, F.d1.data(), sizeof(double) * na, kind, c->stream));
+    if (idx2_out) HIP_TRY(c, hipMemcpyAsync(idx2_out, F.idx2.data(), sizeof(int32_t) * na, kind, c->stream));
+    if (d2nd_out) HIP_TRY(c, hipMemcpyAsync(d2nd_out, F.d2.data(), sizeof(double) * na, kind, c->stream));
+    if (mutual_out) HIP_TRY(c, hipMemcpyAsync(mutual_out, F.mutual.data(), na, kind, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (info) { info->n_a_valid = (int64_t)cnt[0]; info->n_b_valid = (int64_t)cnt[1]; info->n_mutual = (int64_t)cnt[2]; }
+    return DCREG_OK;
+}
+
+}  // namespace
+}  // namespace dcreg
+
+using namespace dcreg;
+
+extern "C" {
+int dcreg_default_fpfh_params(dcreg_fpfh_params *p) {
+    if (!p) return DCREG_E_INVALID;
+    std::memset(p, 0, sizeof(*p));
+    p->k = 16; p->search_radius = 0.0;
+    return DCREG_OK;
+}
+int dcreg_fpfh(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride_floats, const float *normals, int64_t normals_stride_floats,
+               const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *fpfh_out, float *normals_out, dcreg_fpfh_info *info) {
+    return fpfh_cloud(c, xyz, n, stride_floats, normals, normals_stride_floats, false, np, p, fpfh_out, normals_out, info);
+}
+int dcreg_fpfh_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride_floats, const float *d_normals, int64_t normals_stride_floats,
+                      const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *d_fpfh_out, float *d_normals_out, dcreg_fpfh_info *info) {
+    return fpfh_cloud(c, d_xyz, n, stride_floats, d_normals, normals_stride_floats, true, np, p, d_fpfh_out, d_normals_out, info);
+}
+int dcreg_target_fpfh(dcreg_ctx *c, const dcreg_fpfh_params *p, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info) {
+    return fpfh_map(c, false, p, fpfh_out, capacity_points, info);
+}
+int dcreg_target_fpfh_device(dcreg_ctx *c, const dcreg_fpfh_params *p, float *d_fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info) {
+    return fpfh_map(c, true, p, d_fpfh_out, capacity_points, info);
+}
+int dcreg_fpfh_debug_counts(dcreg_ctx *c, uint8_t *counts_out, int64_t capacity_points) { return fpfh_debug_counts(c, counts_out, capacity_points); }
+int dcreg_feature_match(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, int32_t *idx_out,
+                        double *d_out, int32_t *idx2_out, double *d2nd_out, uint8_t *mutual_out, dcreg_match_info *info) {
+    return feature_match(c, a, n_a, stride_a, b, n_b, stride_b, false, idx_out, d_out, idx2_out, d2nd_out, mutual_out, info);
+}
+int dcreg_feature_match_device(dcreg_ctx *c, const float *d_a, int64_t n_a, int64_t stride_a, const float *d_b, int64_t n_b, int64_t stride_b,
+                               int32_t *d_idx_out, double *d_d_out, int32_t *d_idx2_out, double *d_d2nd_out, uint8_t *d_mutual_out,
+                               dcreg_match_info *info) {
+    return feature_match(c, d_a, n_a, stride_a, d_b, n_b, stride_b, true, d_idx_out, d_d_out, d_idx2_out, d_d2nd_out, d_mutual_out, info);
+}
+}

@@ -1042,6 +1042,9 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_vlin_debug")) return sizeof(dcreg_vlin_debug);
     if (!std::strcmp(name, "dcreg_voxel_map_params")) return sizeof(dcreg_voxel_map_params);
     if (!std::strcmp(name, "dcreg_voxel_map_info")) return sizeof(dcreg_voxel_map_info);
+    if (!std::strcmp(name, "dcreg_fpfh_params")) return sizeof(dcreg_fpfh_params);
+    if (!std::strcmp(name, "dcreg_fpfh_info")) return sizeof(dcreg_fpfh_info);
+    if (!std::strcmp(name, "dcreg_match_info")) return sizeof(dcreg_match_info);
     return 0;
 }
 

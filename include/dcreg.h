@@ -46,6 +46,9 @@
  *                                                                                   dcreg_keyframes_add_clouds[_device], _add_source
  *       submaps assembled from (keyframe id, pose) members                       -> dcreg_keyframes_submaps[_device]
  *       ... as the map: a rebuild after a pose-graph update, a local map         -> dcreg_set_target_keyframes
+ *   correspondences for a global alignment (not in the reference: a start pose outside the ICP's basin)
+ *       FPFH descriptors of a cloud / of the resident map                        -> dcreg_fpfh[_device], dcreg_target_fpfh[_device]
+ *       nearest and second-nearest rows in feature space, mutual flags           -> dcreg_feature_match[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -1635,6 +1638,100 @@ int dcreg_get_host_threads(void);
  *   Results are deterministic: the same clouds and T give the same bits. */
 int dcreg_p2p_error(dcreg_ctx *, const double T[16], double error_threshold, double *rmse, double *fitness,
                     double *chamfer, int64_t *valid_correspondences);
+
+/* ---------------- FPFH descriptors and feature-space matching ----------------
+ * The first two stages of a correspondence-based global alignment (PCL FPFHEstimation with setKSearch + a nearest-neighbour search in
+ * feature space; Open3D compute_fpfh_feature + correspondences): 33 floats per point, and for every row of one descriptor set its best
+ * and second-best row of another.  The pose from the correspondences (RANSAC, a graph method) is the caller's.  Both rules are fixed
+ * tightly enough that the output is bitwise the numpy reference of tests/fpfh_ref.py, with ONE freedom, stated below (atan2).
+ *
+ * The descriptor rule.  For a cloud of n points, one normal per point (3 floats, normals_stride floats apart) and the parameters k
+ * (3 .. 32, the point itself among the neighbours) and search_radius (>= 0, 0 = unbounded):
+ *   - used points: a point is used when its three coordinates AND its three normal components are all finite.  Unused points are neither
+ *     queries nor candidates and get NaN in all 33 outputs;
+ *   - neighbours: candidates are ranked by (d2, input index) with dcreg_knn's float d2; the neighbours of a point are the first k used
+ *     points with d2 < bound, bound = min((float)(search_radius^2), 3.0e38f) for search_radius > 0 and 3.0e38f for search_radius = 0 (the
+ *     normals' bound).  A point with fewer than k candidates inside the bound keeps the m it has, 1 <= m <= k (unlike the normals this is
+ *     not sparse-or-nothing);
+ *   - pair features: for the point p and each neighbour q with d2 > 0, in rank order, everything in double, every operation rounded
+ *     once, a dot product evaluated as (x + y) + z:
+ *       d = q - p; f4 = sqrt(d.d); a pair with f4 == 0 is skipped;
+ *       a1 = (n_p.d) / f4; a2 = (n_q.d) / f4;
+ *       if |a1| < |a2|: n1 = n_q, n2 = n_p, d = -d, phi = -a2; otherwise n1 = n_p, n2 = n_q, phi = a1;
+ *       v = d x n1; vn = sqrt(v.v); a pair with vn == 0 is skipped; v = v / vn per coordinate;
+ *       w = n1 x v; alpha = v.n2; theta = atan2(w.n2, n1.n2);
+ *   - bins, each min(max(floor(.), 0), 10): of t = 11 * ((theta + pi) / (2 * pi)), of 11 * ((alpha + 1) * 0.5), of 11 * ((phi + 1) * 0.5);
+ *   - SPFH: c[33] integer counts, theta in 0 .. 10, alpha in 11 .. 21, phi in 22 .. 32; as a double s_b = (double)c_b * (100.0 /
+ *     (double)(m - 1)).  A point with m < 2 or with no counted pair has no SPFH;
+ *   - FPFH: F_b = sum_j (1.0 / (double)d2_j) * s_b(q_j) over the neighbours in rank order, skipping every j with d2_j == 0 and every j
+ *     whose q_j has no SPFH; summed left to right, starting from the first term;
+ *   - normalisation, each block of 11 on its own: S = the block's sum, left to right; out_b = (float)(F_b * (100.0 / S)).  A point whose
+ *     three S are not all > 0 is EMPTY: NaN in all 33 outputs, counted in n_empty;
+ *   - info: n_in, n_used, n_empty and n_out = n_used - n_empty.
+ * A point's result depends on the cloud, the normals and the parameters only - never on the index, the launch or the context's other
+ * state.  The ONE operation that is not bit-reproducible between numpy and the device is atan2: it matters only where t falls within
+ * rounding of an interior bin edge of theta (t = 1 .. 10; the clamped outer edges are harmless), and there the device's bin may be
+ * either neighbour's.  Everything else is bitwise; the reference flags the points with such a pair ("edge-near": |t - round(t)| < 1e-9).
+ * The descriptor changes when a normal flips its sign: orient the normals of clouds that are to be matched consistently.
+ *
+ * dcreg_fpfh reads one cloud as dcreg_normals reads it.  normals == NULL: the call estimates them first with normal_params (the rule
+ * of dcreg_normals, bitwise) on the same per-cloud index - a sparse point has no normal and is then unused - and returns them in
+ * normals_out (3 n floats) when that is not NULL; the cloud is indexed a second time only when some finite point got no normal.  With
+ * normals given, normal_params and normals_out are ignored and may be NULL.  dcreg_target_fpfh computes the resident map's descriptors
+ * in index order (dcreg_target_get) from the kept normals of dcreg_target_normals_keep / _set through the map's own index (a map whose
+ * kept normals are not all finite is indexed once more without those points).  fpfh_out holds 33 n floats (33 capacity_points).
+ * Neither call changes the target, the source, warm states, kept normals, places or keyframes; both wait for the stream; repeated
+ * calls and calls on another context are bitwise equal.
+ * DCREG_E_INVALID, before anything is queued: null context or parameters, k outside 3 .. 32, a search_radius that is not finite or is
+ * negative, stride < 3, normals_stride < 3, n < 0, more than 2^31 - 1 points, a null cloud with n > 0, a null output, both normals and
+ * normal_params NULL, the refusals of dcreg_normals for normal_params when it is read, a capacity below the map's size.  DCREG_E_STATE:
+ * a linearisation in flight; no target or no kept normals (the map form).  Device memory: the outlier filter's scratch for the cloud
+ * and its index (the cloud form), 8 k bytes per point for the neighbour lists (position and d2), 48 bytes per point for the counts and
+ * 132 for the output - kept as scratch of the context, as the outlier pass's, and reused by the next call. */
+typedef struct dcreg_fpfh_params {
+    int k;                 /* neighbours per point, the point itself among them (PCL setKSearch), 3 .. 32 */
+    int reserved0_;
+    double search_radius;  /* 0 = unbounded, > 0 = neighbours beyond it do not count (m) */
+    double reserved_[2];
+} dcreg_fpfh_params;
+typedef struct dcreg_fpfh_info {
+    int64_t n_in;        /* points passed in / points of the map */
+    int64_t n_used;      /* ... with finite coordinates and a finite normal */
+    int64_t n_empty;     /* ... of those, without a descriptor (a block's sum is not > 0) */
+    int64_t n_out;       /* points that received a descriptor */
+} dcreg_fpfh_info;
+#define DCREG_FPFH_DIM 33
+/* k = 16, search_radius = 0 */
+int dcreg_default_fpfh_params(dcreg_fpfh_params *);
+int dcreg_fpfh(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const float *normals, int64_t normals_stride_floats,
+               const dcreg_normal_params *, const dcreg_fpfh_params *, float *fpfh_out, float *normals_out, dcreg_fpfh_info *info);
+int dcreg_fpfh_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const float *d_normals, int64_t normals_stride_floats,
+                      const dcreg_normal_params *, const dcreg_fpfh_params *, float *d_fpfh_out, float *d_normals_out, dcreg_fpfh_info *info);
+int dcreg_target_fpfh(dcreg_ctx *, const dcreg_fpfh_params *, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info);
+int dcreg_target_fpfh_device(dcreg_ctx *, const dcreg_fpfh_params *, float *d_fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info);
+
+/* The matching rule.  a: n_a rows, b: n_b rows, 33 floats each, stride_a / stride_b floats apart (>= 33):
+ *   - a row with any non-finite value is neither a query nor a candidate; as a query it returns index -1 and NaN distances;
+ *   - D(i, j) = sum_{c = 0 .. 32} ((double)a_ic - (double)b_jc)^2, left to right, the multiply and the add rounded separately;
+ *   - candidates are ranked by (D, j); idx_out / d_out (n_a int32 / n_a doubles) receive the best, idx2_out / d2nd_out the second-best
+ *     (either pair may be NULL); with fewer than two valid candidates the missing places get -1 and +inf;
+ *   - mutual_out (n_a bytes, may be NULL): 1 when the best row of a for b[idx_i], under the same rule with the roles swapped, is i;
+ *   - info: n_a_valid, n_b_valid, n_mutual (0 when mutual_out is NULL).
+ * Every distance is computed in the order above whatever the launch: the result does not depend on how the candidates are split over
+ * blocks ("feature_match_split": rows of b per block column, 0 = chosen from the sizes; a test option).  No ratio test and no distance
+ * filter: the caller has both distances.  n_a == 0 does nothing; n_b == 0 returns -1 / +inf for every valid query.
+ * DCREG_E_INVALID, before anything is queued: null context, null a with n_a > 0, null b with n_b > 0, null idx_out or d_out, a stride
+ * below 33, a negative count or more than 2^31 - 1 rows; DCREG_E_STATE: a linearisation in flight.  Touches nothing else in the context.
+ * Device memory: both descriptor sets (the host form), 24 bytes per query and candidate split, and the results. */
+typedef struct dcreg_match_info {
+    int64_t n_a_valid, n_b_valid, n_mutual;
+    int64_t reserved_;
+} dcreg_match_info;
+int dcreg_feature_match(dcreg_ctx *, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b,
+                        int32_t *idx_out, double *d_out, int32_t *idx2_out, double *d2nd_out, uint8_t *mutual_out, dcreg_match_info *info);
+int dcreg_feature_match_device(dcreg_ctx *, const float *d_a, int64_t n_a, int64_t stride_a, const float *d_b, int64_t n_b, int64_t stride_b,
+                               int32_t *d_idx_out, double *d_d_out, int32_t *d_idx2_out, double *d_d2nd_out, uint8_t *d_mutual_out,
+                               dcreg_match_info *info);
 
 size_t dcreg_sizeof(const char *struct_name);
 const char *dcreg_version(void);

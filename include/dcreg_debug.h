@@ -366,6 +366,13 @@ int dcreg_pairs_voxels_batch_begin(dcreg_ctx *, int slot, int n_poses, const dou
  * exactly what a full build of that grid gives. */
 int dcreg_debug_index_check(dcreg_ctx *, int64_t mismatches[5]);
 
+/* The SPFH records behind the last dcreg_fpfh* / dcreg_target_fpfh* call of this context (tests: where the device's atan2 puts a pair
+ * at a bin edge of theta, the counts say which pair moved).  36 bytes per input point: the 33 counts, m, 1 when the point has an SPFH,
+ * and a zero; all zero for an unused point.  Only directly behind that call: the records lie in scratch that the next call of the
+ * descriptor, normal and outlier families reuses.  DCREG_E_STATE without such a call, DCREG_E_INVALID for a null buffer or a capacity
+ * below the call's points. */
+int dcreg_fpfh_debug_counts(dcreg_ctx *, uint8_t *counts_out, int64_t capacity_points);
+
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */
 void dcreg_set_error_message(dcreg_ctx *, const char *msg);
 
