@@ -215,6 +215,7 @@ EXPORTS = [
     "dcreg_voxel_map_params_check", "dcreg_pairs_voxels_box_check", "dcreg_pairs_voxels_batch_begin",
     "dcreg_default_fpfh_params", "dcreg_fpfh", "dcreg_fpfh_device", "dcreg_target_fpfh", "dcreg_target_fpfh_device", "dcreg_fpfh_debug_counts",
     "dcreg_feature_match", "dcreg_feature_match_device",
+    "dcreg_default_align_params", "dcreg_align_correspondences", "dcreg_align_correspondences_device",
 ]
 
 _lib = None
@@ -803,6 +804,94 @@ def _check_device_rows(n, stride, what):
         raise ValueError("%s: a stride of at least %d floats is expected, got %d" % (what, FPFH_DIM, int(stride)))
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_int64), ("seed", C.c_uint64), ("inlier_distance", C.c_double), ("edge_similarity", C.c_double),
+                ("n_best", C.c_int), ("refine_iterations", C.c_int), ("reserved_", C.c_double * 2)]
+
+
+class AlignRecord(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("hypothesis", C.c_int64), ("pairs", C.c_int32 * 3), ("count", C.c_int32), ("cost", C.c_uint64),
+                ("n_inliers", C.c_int32), ("refined", C.c_int32), ("rmse", C.c_double)]
+
+
+class AlignInfo(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_used", C.c_int64), ("n_drawn", C.c_int64), ("n_degenerate", C.c_int64), ("n_rejected", C.c_int64),
+                ("n_scored", C.c_int64), ("n_returned", C.c_int64), ("reserved_", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_align_params": AlignParams, "dcreg_align_record": AlignRecord, "dcreg_align_info": AlignInfo})
+ALIGN_MAX_HYPOTHESES, ALIGN_MAX_BEST, ALIGN_MAX_REFINE = 1 << 24, 32, 8
+
+
+def _check_align_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_align_params block"""
+    if not isinstance(p, AlignParams):
+        raise ValueError("%s: align_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not 1 <= p.n_hypotheses <= ALIGN_MAX_HYPOTHESES:
+        raise ValueError("%s: n_hypotheses in [1, 2^24] is expected, got %d" % (what, p.n_hypotheses))
+    if not (np.isfinite(p.inlier_distance) and p.inlier_distance > 0.0):
+        raise ValueError("%s: a finite inlier_distance > 0 is expected, got %r" % (what, p.inlier_distance))
+    if not 0.0 <= p.edge_similarity < 1.0:
+        raise ValueError("%s: an edge_similarity in [0, 1) is expected, got %r" % (what, p.edge_similarity))
+    if not 1 <= p.n_best <= ALIGN_MAX_BEST:
+        raise ValueError("%s: n_best in [1, %d] is expected, got %d" % (what, ALIGN_MAX_BEST, p.n_best))
+    if not 0 <= p.refine_iterations <= ALIGN_MAX_REFINE:
+        raise ValueError("%s: refine_iterations in [0, %d] is expected, got %d" % (what, ALIGN_MAX_REFINE, p.refine_iterations))
+
+
+def align_params(n_hypotheses=100000, seed=0, inlier_distance=0.5, edge_similarity=0.9, n_best=1, refine_iterations=3):
+    """dcreg_align_params: H seeded three-pair hypotheses, the inlier distance d in metres, the edge-length pre-rejection s (0 = none;
+    a hypothesis is kept when the three edges of its triangles agree within the factor s), the number of records returned and the
+    least-squares refinement steps of each; include/dcreg.h has the rule"""
+    p = AlignParams()
+    p.n_hypotheses = int(n_hypotheses)
+    p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    p.inlier_distance = float(inlier_distance)
+    p.edge_similarity = float(edge_similarity)
+    p.n_best = int(n_best)
+    p.refine_iterations = int(refine_iterations)
+    _check_align_params(p, "align_params")
+    return p
+
+
+def _align_info_dict(i):
+    return {k: getattr(i, k) for k in ("n_pairs", "n_used", "n_drawn", "n_degenerate", "n_rejected", "n_scored", "n_returned")}
+
+
+def _align_records(recs, n):
+    return [{"T": np.array(r.T, np.float64).reshape(4, 4), "hypothesis": r.hypothesis, "pairs": tuple(r.pairs), "count": r.count, "cost": r.cost,
+             "n_inliers": r.n_inliers, "refined": r.refined, "rmse": r.rmse} for r in recs[:n]]
+
+
+def _corr_index(a, what):
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("%s: a 1-D integer index array is expected, got %s %s" % (what, a.dtype, a.shape))
+    if a.size and (a.min() < -(2 ** 31) or a.max() > 2 ** 31 - 1):
+        raise ValueError("%s: index values that fit an int32 are expected" % what)
+    return np.ascontiguousarray(a, np.int32)
+
+
+def correspondences_from_match(match, mutual_only=True, max_ratio=None):
+    """The dict of Context.feature_match(a, b) as index pairs for align_correspondences: rows of a without a match (-1) are dropped, with
+    mutual_only the rows whose match is not mutual, with max_ratio the rows whose ratio sqrt(d / d2) of the best to the second-best
+    distance is above it (a row without a second-best passes).  Pure numpy.  -> (corr_a [m] int32, corr_b [m] int32)"""
+    idx = np.asarray(match["idx"])
+    keep = idx >= 0
+    if mutual_only:
+        if "mutual" not in match:
+            raise ValueError("correspondences_from_match: mutual_only needs feature_match(..., want_mutual=True)")
+        keep &= np.asarray(match["mutual"]) != 0
+    if max_ratio is not None:
+        if "d2" not in match:
+            raise ValueError("correspondences_from_match: max_ratio needs feature_match(..., want_second=True)")
+        d, d2 = np.asarray(match["d"], np.float64), np.asarray(match["d2"], np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            keep &= ~(np.sqrt(d / d2) > float(max_ratio))
+    rows = np.flatnonzero(keep)
+    return rows.astype(np.int32), idx[rows].astype(np.int32)
+
+
 def _check_voxel_map_params(p, what):
     """the refusals of include/dcreg.h for a dcreg_voxel_map_params block"""
     if not isinstance(p, VoxelMapParams):
@@ -1300,6 +1389,11 @@ def load():
         L.dcreg_fpfh_debug_counts.argtypes = [vp, vp, C.c_int64]
         for name in ("dcreg_feature_match", "dcreg_feature_match_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(MatchInfo)]
+    if hasattr(L, "dcreg_align_correspondences"):  # (likewise)
+        L.dcreg_default_align_params.argtypes = [C.POINTER(AlignParams)]
+        for name in ("dcreg_align_correspondences", "dcreg_align_correspondences_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.POINTER(AlignParams),
+                                         C.POINTER(AlignRecord), vp, C.POINTER(AlignInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2161,6 +2255,51 @@ class Context:
                                                        C.c_void_p(dev_d2 or None), C.c_void_p(dev_mutual or None), C.byref(info)),
                     "dcreg_feature_match_device")
         return {"n_a_valid": info.n_a_valid, "n_b_valid": info.n_b_valid, "n_mutual": info.n_mutual}
+
+    # ---- a pose from correspondences (include/dcreg.h: dcreg_align_correspondences)
+    def align_correspondences(self, a, b, corr_a, corr_b, params=None, want_mask=True):
+        """dcreg_align_correspondences: the rigid pose q ~ R p + t that most of the point pairs (a[corr_a[m]], b[corr_b[m]]) agree on,
+        by seeded RANSAC over three-pair hypotheses (include/dcreg.h has the rule).  a, b: [n, c] float32 clouds, x y z first; corr_a,
+        corr_b: integer arrays of one length - a pair with an index out of range (feature_match's -1) or a non-finite point is skipped.
+        params: align_params(...), None = the defaults.  -> dict records (best first, at most n_best dicts: T [4, 4] float64 - a start
+        pose as icp_run* and icp_run_trials* take it -, hypothesis, pairs, count, cost, n_inliers, refined, rmse), mask ([m] uint8:
+        the inliers of records[0]; None without want_mask) and info (n_pairs, n_used, n_drawn, n_degenerate, n_rejected, n_scored,
+        n_returned)"""
+        p = params if params is not None else align_params()
+        _check_align_params(p, "align_correspondences")
+        a = _points(a, "align_correspondences")
+        b = _points(b, "align_correspondences")
+        ca = _corr_index(corr_a, "align_correspondences")
+        cb = _corr_index(corr_b, "align_correspondences")
+        if ca.shape[0] != cb.shape[0]:
+            raise ValueError("align_correspondences: index arrays of one length are expected, got %d and %d" % (ca.shape[0], cb.shape[0]))
+        m = ca.shape[0]
+        recs = (AlignRecord * p.n_best)()
+        mask = np.zeros(max(m, 1), np.uint8) if want_mask else None
+        info = AlignInfo()
+        self._check(self._L.dcreg_align_correspondences(self._h, a.ctypes.data, a.shape[0], a.shape[1], b.ctypes.data, b.shape[0], b.shape[1],
+                                                        ca.ctypes.data, cb.ctypes.data, m, C.byref(p), recs, mask.ctypes.data if want_mask else None,
+                                                        C.byref(info)), "dcreg_align_correspondences")
+        return {"records": _align_records(recs, info.n_returned), "mask": mask[:m] if want_mask else None, "info": _align_info_dict(info)}
+
+    def align_correspondences_device(self, dev_a, n_a, stride_a, dev_b, n_b, stride_b, dev_corr_a, dev_corr_b, n_pairs, params=None, dev_mask=0):
+        """dcreg_align_correspondences_device: both clouds, both int32 index arrays and the mask (n_pairs bytes; 0: not wanted) in device
+        memory.  -> dict records / info, as align_correspondences"""
+        p = params if params is not None else align_params()
+        _check_align_params(p, "align_correspondences_device")
+        _check_device_cloud(n_a, stride_a, "align_correspondences_device")
+        _check_device_cloud(n_b, stride_b, "align_correspondences_device")
+        if int(n_pairs) < 0 or int(n_pairs) > OUTLIER_MAX_POINTS:
+            raise ValueError("align_correspondences_device: 0 .. 2^31 - 1 pairs are expected, got %d" % int(n_pairs))
+        if int(n_pairs) > 0 and (not dev_corr_a or not dev_corr_b):
+            raise ValueError("align_correspondences_device: both index arrays are expected")
+        recs = (AlignRecord * p.n_best)()
+        info = AlignInfo()
+        self._check(self._L.dcreg_align_correspondences_device(self._h, C.c_void_p(dev_a or None), int(n_a), int(stride_a), C.c_void_p(dev_b or None),
+                                                               int(n_b), int(stride_b), C.c_void_p(dev_corr_a or None), C.c_void_p(dev_corr_b or None),
+                                                               int(n_pairs), C.byref(p), recs, C.c_void_p(dev_mask or None), C.byref(info)),
+                    "dcreg_align_correspondences_device")
+        return {"records": _align_records(recs, info.n_returned), "info": _align_info_dict(info)}
 
     # ---- kept normals and the second engine (include/dcreg.h: dcreg_target_normals_keep .. dcreg_icp_run_normals)
     def keep_target_normals(self, params=None):

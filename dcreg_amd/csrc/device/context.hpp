@@ -15,6 +15,7 @@
 
 #include "../../../include/dcreg.h"
 #include "kernels.hpp"
+#include "align.hpp"
 
 struct dcreg_lin_params;
 struct dcreg_lin_out;
@@ -705,6 +706,21 @@ struct dcreg_ctx {
     };
     FeatureBufs feat;
     int64_t opt_feature_match_split = 0;                      // "feature_match_split": rows of b per block column of k_match (0: from the sizes; tests)
+
+    // A pose from correspondences (align.hip: dcreg_align_correspondences*).  Scratch of one call, kept for the next: both clouds and both
+    // index arrays as uploaded (the host form), per correspondence its used flag and the flags' exclusive scan (n_pairs + 1 entries: the
+    // last one is the number of used pairs), the used pairs compacted ([u] -> p, q: six floats) with their correspondence numbers, the
+    // survivors' keys {count, h, cost} as k_align_hypotheses appends them and in rank order, the counts ([0] survivors, [1] degenerate,
+    // [2] rejected hypotheses).
+    struct AlignBufs {
+        DevBuf<float> a, b, P;
+        DevBuf<int32_t> ca, cb, m_of_u;
+        DevBuf<uint32_t> flag, pos;
+        DevBuf<dcreg::AlignKey> keys, sorted;
+        DevBuf<unsigned long long> cnt;
+    };
+    AlignBufs algn;
+    int64_t opt_align_score_split = 0;                        // "align_score_split": used pairs per block column of k_align_score (0: from the sizes; tests)
 
     void fail(const char *fmt, ...);
 };

@@ -49,6 +49,7 @@
  *   correspondences for a global alignment (not in the reference: a start pose outside the ICP's basin)
  *       FPFH descriptors of a cloud / of the resident map                        -> dcreg_fpfh[_device], dcreg_target_fpfh[_device]
  *       nearest and second-nearest rows in feature space, mutual flags           -> dcreg_feature_match[_device]
+ *       the pose most point pairs agree on (seeded RANSAC), the best T as start poses -> dcreg_align_correspondences[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -1732,6 +1733,92 @@ int dcreg_feature_match(dcreg_ctx *, const float *a, int64_t n_a, int64_t stride
 int dcreg_feature_match_device(dcreg_ctx *, const float *d_a, int64_t n_a, int64_t stride_a, const float *d_b, int64_t n_b, int64_t stride_b,
                                int32_t *d_idx_out, double *d_d_out, int32_t *d_idx2_out, double *d_d2nd_out, uint8_t *d_mutual_out,
                                dcreg_match_info *info);
+
+/* ---------------- Pose from correspondences ----------------
+ * The stage behind dcreg_feature_match: from point pairs (a[corr_a[m]], b[corr_b[m]]), most of them wrong, the rigid pose q ~ R p + t
+ * that most of them agree on, by seeded RANSAC over three-pair hypotheses (Open3D registration_ransac_based_on_correspondence, PCL
+ * SampleConsensusPrerejective without its verification against the cloud).  The call knows nothing of descriptors: two clouds and two
+ * index arrays.  The best n_best hypotheses come back as 4x4 poses that every T0 / T0s argument of the engines takes as they are.
+ * Everything is in double, every operation is rounded once, a dot product is (x + y) + z, and no operation of the rule is a library
+ * function whose last bit is free: the output is BITWISE the numpy reference of tests/align_ref.py, with no stated freedom.
+ *
+ * 1. Used pairs.  Pair m is used when 0 <= corr_a[m] < n_a, 0 <= corr_b[m] < n_b and the six coordinates are finite; the others are
+ *    skipped (n_pairs - n_used), which makes dcreg_feature_match's -1 entries harmless.  The used pairs are numbered u = 0 .. M_u - 1
+ *    in ascending m; p_u, q_u are their points widened to double.  With M_u < 3 the call returns DCREG_OK with n_returned = 0.
+ * 2. Draws (splitmix64, integers mod 2^64).  x(k) = mix(seed + k * 0x9E3779B97F4A7C15) with mix(z): z = (z ^ z >> 30) *
+ *    0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  Hypothesis h = 0 .. H - 1 takes the used pairs
+ *    u_j = ((x(3 h + j + 1) >> 32) * M_u) >> 32, j = 0, 1, 2.  Two equal u_j: the hypothesis is DEGENERATE (counted, not drawn again).
+ * 3. Pre-rejection (edge_similarity s > 0).  For the edges (i, j) = (0, 1), (1, 2), (2, 0): g = p_i - p_j, la = sqrt((g_x g_x + g_y g_y)
+ *    + g_z g_z), lb likewise from q.  The hypothesis is REJECTED unless la >= s * lb and lb >= s * la on all three edges.
+ * 4. Pose (a triad; the least-squares fit is step 7).  u = p_1 - p_0, v = p_2 - p_0, w = u x v (w_x = u_y v_z - u_z v_y, cyclic: two
+ *    products, one subtraction).  DEGENERATE if w.w <= 1e-4 * ((u.u) * (v.v)); the same test on the q side (both sides are computed).
+ *    e1 = u / sqrt(u.u), e3 = w / sqrt(w.w) (per coordinate), e2 = e3 x e1; f1, f2, f3 the same from q.  R_rc = (f1_r e1_c + f2_r e2_c)
+ *    + f3_r e3_c.  c_p = ((p_0 + p_1) + p_2) / 3.0 per coordinate, c_q likewise; t_r = c_q_r - ((R_r0 c_p_x + R_r1 c_p_y) + R_r2 c_p_z).
+ * 5. Score, over ALL used pairs: r_r = (((R_r0 p_x + R_r1 p_y) + R_r2 p_z) + t_r) - q_r; e2 = (r_x r_x + r_y r_y) + r_z r_z; the pair
+ *    is an inlier when e2 <= dd, dd = d * d (d = inlier_distance).  count = the number of inliers; cost = the sum over the inliers of
+ *    (uint64) floor((e2 / dd) * 1048576.0).  Both are integers: no order of summation is part of the rule.
+ * 6. Rank: (count descending, cost ascending, h ascending) over the n_scored = H - n_degenerate - n_rejected hypotheses; the first
+ *    n_returned = min(n_best, n_scored) are returned, best first.  The records behind them are zero.
+ * 7. Refinement, for every returned record on its own, refine_iterations times: the inliers of the current pose (step 5's test) in
+ *    ascending u; fewer than three: stop (`refined` counts the steps taken).  With n of them: c_p = (sum p) / n per coordinate, the sum
+ *    from 0.0 left to right, c_q likewise; S_ab = sum (p_a - c_p_a) * (q_b - c_q_b) from 0.0 left to right, the product rounded, then
+ *    added.  Horn's matrix: N00 = (Sxx + Syy) + Szz, N11 = (Sxx - Syy) - Szz, N22 = (Syy - Sxx) - Szz, N33 = (Szz - Sxx) - Syy,
+ *    N01 = Syz - Szy, N02 = Szx - Sxz, N03 = Sxy - Syx, N12 = Sxy + Syx, N13 = Szx + Sxz, N23 = Syz + Szy, symmetric.  V = I.  Eight
+ *    cyclic Jacobi sweeps over (0,1), (0,2), (0,3), (1,2), (1,3), (2,3); one rotation of (p, q), as for the normals' 3x3: t = 0 if
+ *    N_pq == 0, otherwise theta = (N_qq - N_pp) / (2.0 * N_pq), t = (theta >= 0 ? 1.0 : -1.0) / (|theta| + sqrt(theta * theta + 1.0));
+ *    c = 1.0 / sqrt(t * t + 1.0); s = t * c; N_pp -= t * N_pq; N_qq += t * N_pq; N_pq = 0; for the two other rows r (ascending):
+ *    N_rp' = c * N_rp - s * N_rq, N_rq' = s * N_rp + c * N_rq (and their mirror images); for the four rows k of V: V_kp' = c * V_kp -
+ *    s * V_kq, V_kq' = s * V_kp + c * V_kq.  The column of V under the largest diagonal entry (the lowest index among equals) is
+ *    (w, x, y, z); negated if w < 0; divided by sqrt(((w w + x x) + y y) + z z).  With the nine products xx .. wz:
+ *      R00 = 1.0 - 2.0 * (yy + zz)   R01 = 2.0 * (xy - wz)         R02 = 2.0 * (xz + wy)
+ *      R10 = 2.0 * (xy + wz)         R11 = 1.0 - 2.0 * (xx + zz)   R12 = 2.0 * (yz - wx)
+ *      R20 = 2.0 * (xz - wy)         R21 = 2.0 * (yz + wx)         R22 = 1.0 - 2.0 * (xx + yy)
+ *    and t from c_p, c_q as in step 4.  After the iterations: n_inliers and rmse = sqrt((sum e2) / n_inliers) over the inliers of the
+ *    final pose in ascending u, the sum from 0.0 (0.0 without an inlier), and for record 0 the mask: inlier_mask_out[m] = 1 for the
+ *    correspondences m of those inliers, 0 for every other one of the n_pairs (all 0 when nothing is returned).
+ * `count` and `cost` are the unrefined hypothesis's (the ranking key); T, n_inliers and rmse the refined pose's.  `pairs` are the
+ * correspondence numbers m of u_0, u_1, u_2.
+ *
+ * Steps 1 to 6 run on the device, step 7 on the host from the used pairs (28 bytes each, downloaded once).  The call touches nothing
+ * else in the context and waits for the stream; repeated calls and calls on another context are bitwise equal; no result depends on
+ * how the scorer splits the pairs over blocks ("align_score_split": used pairs per block column, 0 = chosen from the sizes; a test option).
+ * DCREG_E_INVALID, before anything is queued: null context, parameters or records; n_hypotheses outside 1 .. 2^24; n_best outside
+ * 1 .. 32; refine_iterations outside 0 .. 8; an inlier_distance that is not finite or not > 0; an edge_similarity outside [0, 1) or not
+ * finite; a stride below 3; a negative count; more than 2^31 - 1 points or pairs; a null cloud with a positive point count; a null index
+ * array with n_pairs > 0.  DCREG_E_STATE: a linearisation in flight.  Device memory: the clouds and index arrays (the host form),
+ * 36 bytes per correspondence, 32 bytes per hypothesis (the survivors' keys, unsorted and sorted) - kept as scratch of the context. */
+typedef struct dcreg_align_params {
+    int64_t n_hypotheses;      /* H, 1 .. 2^24 */
+    uint64_t seed;
+    double inlier_distance;    /* d > 0, metres */
+    double edge_similarity;    /* s in [0, 1): 0 = no pre-rejection; Open3D's edge-length checker uses 0.9 */
+    int n_best;                /* T, 1 .. 32 records returned */
+    int refine_iterations;     /* 0 .. 8 */
+    double reserved_[2];
+} dcreg_align_params;
+typedef struct dcreg_align_record {   /* one per returned hypothesis, best first */
+    double T[16];              /* row-major 4x4, bottom row 0 0 0 1: q ~ R p + t; feeds every T0 argument as it is */
+    int64_t hypothesis;        /* h */
+    int32_t pairs[3];          /* the three correspondence numbers m it was drawn from */
+    int32_t count;             /* inliers of the unrefined hypothesis (the ranking key) */
+    uint64_t cost;             /* its integer cost (ranking key) */
+    int32_t n_inliers;         /* inliers of T, after refinement */
+    int32_t refined;           /* refinement steps actually taken */
+    double rmse;               /* over the inliers of T */
+} dcreg_align_record;
+typedef struct dcreg_align_info {
+    int64_t n_pairs, n_used, n_drawn, n_degenerate, n_rejected, n_scored, n_returned;
+    int64_t reserved_;
+} dcreg_align_info;
+/* H = 100000, seed = 0, d = 0.5, s = 0.9, T = 1, refine = 3 */
+int dcreg_default_align_params(dcreg_align_params *);
+int dcreg_align_correspondences(dcreg_ctx *, const float *a_xyz, int64_t n_a, int64_t stride_a, const float *b_xyz, int64_t n_b,
+                                int64_t stride_b, const int32_t *corr_a, const int32_t *corr_b, int64_t n_pairs, const dcreg_align_params *,
+                                dcreg_align_record *records_out, uint8_t *inlier_mask_out, dcreg_align_info *info);
+int dcreg_align_correspondences_device(dcreg_ctx *, const float *d_a_xyz, int64_t n_a, int64_t stride_a, const float *d_b_xyz, int64_t n_b,
+                                       int64_t stride_b, const int32_t *d_corr_a, const int32_t *d_corr_b, int64_t n_pairs,
+                                       const dcreg_align_params *, dcreg_align_record *records_out, uint8_t *d_inlier_mask_out,
+                                       dcreg_align_info *info);
 
 size_t dcreg_sizeof(const char *struct_name);
 const char *dcreg_version(void);
