@@ -215,6 +215,8 @@ EXPORTS = [
     "dcreg_voxel_map_params_check", "dcreg_pairs_voxels_box_check", "dcreg_pairs_voxels_batch_begin",
     "dcreg_default_fpfh_params", "dcreg_fpfh", "dcreg_fpfh_device", "dcreg_target_fpfh", "dcreg_target_fpfh_device", "dcreg_fpfh_debug_counts",
     "dcreg_feature_match", "dcreg_feature_match_device",
+    "dcreg_default_fpfh_radius_params", "dcreg_fpfh_radius", "dcreg_fpfh_radius_device", "dcreg_target_fpfh_radius", "dcreg_target_fpfh_radius_device",
+    "dcreg_fpfh_radius_debug_counts",
     "dcreg_default_align_params", "dcreg_align_correspondences", "dcreg_align_correspondences_device",
 ]
 
@@ -785,6 +787,46 @@ def fpfh_params(k=16, search_radius=0.0):
 
 def _fpfh_info_dict(i):
     return {"n_in": i.n_in, "n_used": i.n_used, "n_empty": i.n_empty, "n_out": i.n_out}
+
+
+class FpfhRadiusParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("max_neighbors", C.c_int), ("reserved0_", C.c_int), ("reserved_", C.c_double * 2)]
+
+
+class FpfhRadiusInfo(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_used", C.c_int64), ("n_empty", C.c_int64), ("n_crowded", C.c_int64), ("n_out", C.c_int64),
+                ("m_max", C.c_int64), ("m_sum", C.c_int64), ("reserved_", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_fpfh_radius_params": FpfhRadiusParams, "dcreg_fpfh_radius_info": FpfhRadiusInfo})
+FPFH_MIN_CAP, FPFH_MAX_CAP = 2, 65535
+
+
+def _check_fpfh_radius_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_fpfh_radius_params block"""
+    if not isinstance(p, FpfhRadiusParams):
+        raise ValueError("%s: fpfh_radius_params(...) is expected, got %s" % (what, type(p).__name__))
+    with np.errstate(all="ignore"):
+        r2 = np.float32(np.float64(p.radius) * np.float64(p.radius))
+    if not (np.isfinite(p.radius) and p.radius > 0.0 and np.float32(0.0) < r2 < np.float32(3.0e38)):
+        raise ValueError("%s: a finite radius > 0 whose square is a float in (0, 3.0e38) is expected, got %r" % (what, p.radius))
+    if not FPFH_MIN_CAP <= p.max_neighbors <= FPFH_MAX_CAP:
+        raise ValueError("%s: max_neighbors in [%d, %d] is expected, got %d" % (what, FPFH_MIN_CAP, FPFH_MAX_CAP, p.max_neighbors))
+
+
+def fpfh_radius_params(radius=1.0, max_neighbors=65535):
+    """dcreg_fpfh_radius_params: every used point within radius is a neighbour (PCL FPFHEstimation setRadiusSearch); a point with more
+    than max_neighbors of them is crowded and gets no descriptor; include/dcreg.h has the rule"""
+    p = FpfhRadiusParams()
+    p.radius = float(radius)
+    p.max_neighbors = int(max_neighbors)
+    _check_fpfh_radius_params(p, "fpfh_radius_params")
+    return p
+
+
+def _fpfh_radius_info_dict(i):
+    return {"n_in": i.n_in, "n_used": i.n_used, "n_empty": i.n_empty, "n_crowded": i.n_crowded, "n_out": i.n_out, "m_max": i.m_max,
+            "m_sum": i.m_sum}
 
 
 def _feature_rows(a, what):
@@ -1389,6 +1431,14 @@ def load():
         L.dcreg_fpfh_debug_counts.argtypes = [vp, vp, C.c_int64]
         for name in ("dcreg_feature_match", "dcreg_feature_match_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.POINTER(MatchInfo)]
+    if hasattr(L, "dcreg_fpfh_radius"):  # (likewise)
+        np_, frp, fri = C.POINTER(NormalParams), C.POINTER(FpfhRadiusParams), C.POINTER(FpfhRadiusInfo)
+        L.dcreg_default_fpfh_radius_params.argtypes = [frp]
+        for name in ("dcreg_fpfh_radius", "dcreg_fpfh_radius_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, np_, frp, vp, vp, fri]
+        for name in ("dcreg_target_fpfh_radius", "dcreg_target_fpfh_radius_device"):
+            getattr(L, name).argtypes = [vp, frp, vp, C.c_int64, fri]
+        L.dcreg_fpfh_radius_debug_counts.argtypes = [vp, vp, C.c_int64]
     if hasattr(L, "dcreg_align_correspondences"):  # (likewise)
         L.dcreg_default_align_params.argtypes = [C.POINTER(AlignParams)]
         for name in ("dcreg_align_correspondences", "dcreg_align_correspondences_device"):
@@ -2215,6 +2265,74 @@ class Context:
         -> (counts [n, 33] uint8, m [n] uint8, has_spfh [n] bool)"""
         raw = np.zeros((max(int(n), 1), 36), np.uint8)
         self._check(self._L.dcreg_fpfh_debug_counts(self._h, raw.ctypes.data, int(n)), "dcreg_fpfh_debug_counts")
+        raw = raw[:n]
+        return raw[:, :FPFH_DIM].copy(), raw[:, FPFH_DIM].copy(), raw[:, FPFH_DIM + 1] != 0
+
+    # ---- FPFH over a radius support (include/dcreg.h: dcreg_fpfh_radius ..)
+    def fpfh_radius(self, cloud, normals=None, normal_params=None, params=None, want_normals=False):
+        """dcreg_fpfh_radius: fpfh() with every used point within params.radius as the support (PCL setRadiusSearch; include/dcreg.h has
+        the rule).  params: fpfh_radius_params(...), None = the defaults.  -> (fpfh [n, 33] float32, normals [n, 3] float32 or None, dict
+        n_in / n_used / n_empty / n_crowded / n_out / m_max / m_sum)"""
+        p = params if params is not None else fpfh_radius_params()
+        _check_fpfh_radius_params(p, "fpfh_radius")
+        a = _points(cloud, "fpfh_radius")
+        n = a.shape[0]
+        nrm_in = npb = None
+        if normals is not None:
+            nrm_in = _points(normals, "fpfh_radius")
+            if nrm_in.shape[0] != n:
+                raise ValueError("fpfh_radius: one normal per point is expected, got %d normals for %d points" % (nrm_in.shape[0], n))
+            if want_normals:
+                raise ValueError("fpfh_radius: want_normals returns the normals the call estimates; these were given")
+        else:
+            npb = normal_params if normal_params is not None else _normal_params()
+            _check_normal_params(npb, "fpfh_radius")
+        out = np.full((max(n, 1), FPFH_DIM), np.nan, np.float32)
+        nrm_out = np.full((max(n, 1), 3), np.nan, np.float32) if want_normals else None
+        info = FpfhRadiusInfo()
+        self._check(self._L.dcreg_fpfh_radius(self._h, a.ctypes.data, n, a.shape[1], nrm_in.ctypes.data if nrm_in is not None else None,
+                                              nrm_in.shape[1] if nrm_in is not None else 3, C.byref(npb) if npb is not None else None,
+                                              C.byref(p), out.ctypes.data, nrm_out.ctypes.data if want_normals else None, C.byref(info)),
+                    "dcreg_fpfh_radius")
+        return out[:n], (nrm_out[:n] if want_normals else None), _fpfh_radius_info_dict(info)
+
+    def fpfh_radius_device(self, dev_ptr, n, stride, dev_fpfh_ptr, dev_normals_ptr=0, normals_stride=3, normal_params=None, params=None,
+                           dev_normals_out_ptr=0):
+        """dcreg_fpfh_radius_device: the arguments of fpfh_device with fpfh_radius_params(...).  -> info dict"""
+        p = params if params is not None else fpfh_radius_params()
+        _check_fpfh_radius_params(p, "fpfh_radius_device")
+        _check_device_cloud(n, stride, "fpfh_radius_device")
+        if not dev_fpfh_ptr:
+            raise ValueError("fpfh_radius_device: an output buffer is expected")
+        npb = None
+        if dev_normals_ptr:
+            if int(normals_stride) < 3:
+                raise ValueError("fpfh_radius_device: a normals stride of at least 3 floats is expected, got %d" % int(normals_stride))
+        else:
+            npb = normal_params if normal_params is not None else _normal_params()
+            _check_normal_params(npb, "fpfh_radius_device")
+        info = FpfhRadiusInfo()
+        self._check(self._L.dcreg_fpfh_radius_device(self._h, C.c_void_p(dev_ptr), int(n), int(stride), C.c_void_p(dev_normals_ptr or None),
+                                                     int(normals_stride), C.byref(npb) if npb is not None else None, C.byref(p),
+                                                     C.c_void_p(dev_fpfh_ptr), C.c_void_p(dev_normals_out_ptr or None), C.byref(info)),
+                    "dcreg_fpfh_radius_device")
+        return _fpfh_radius_info_dict(info)
+
+    def target_fpfh_radius(self, params=None):
+        """dcreg_target_fpfh_radius: target_fpfh() under the radius rule.  -> (fpfh [n, 33] float32, info dict)"""
+        p = params if params is not None else fpfh_radius_params()
+        _check_fpfh_radius_params(p, "target_fpfh_radius")
+        n = max(int(self.index_info().n_target), 0)
+        out = np.full((max(n, 1), FPFH_DIM), np.nan, np.float32)
+        info = FpfhRadiusInfo()
+        self._check(self._L.dcreg_target_fpfh_radius(self._h, C.byref(p), out.ctypes.data, n, C.byref(info)), "dcreg_target_fpfh_radius")
+        return out[:n], _fpfh_radius_info_dict(info)
+
+    def fpfh_radius_debug_counts(self, n):
+        """dcreg_fpfh_radius_debug_counts: the SPFH records behind the radius descriptor call just made, for its n input points
+        -> (counts [n, 33] uint32, m [n] uint32, has_spfh [n] bool)"""
+        raw = np.zeros((max(int(n), 1), FPFH_DIM + 2), np.uint32)
+        self._check(self._L.dcreg_fpfh_radius_debug_counts(self._h, raw.ctypes.data, int(n)), "dcreg_fpfh_radius_debug_counts")
         raw = raw[:n]
         return raw[:, :FPFH_DIM].copy(), raw[:, FPFH_DIM].copy(), raw[:, FPFH_DIM + 1] != 0
 

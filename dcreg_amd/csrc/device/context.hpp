@@ -703,6 +703,11 @@ struct dcreg_ctx {
         // dcreg_fpfh_debug_counts: the sorted points, their number and the input's size of the last descriptor call, and the export
         const float4 *last_q = nullptr; int64_t last_nq = 0, last_n = 0;
         DevBuf<uint32_t> dbg;
+        // the radius rule (dcreg_fpfh_radius*): per used point its record (q[33], m, has, 0) and its 33 counts, in the index's cell order;
+        // what dcreg_fpfh_radius_debug_counts reports.  A call of either rule ends the other's report
+        DevBuf<uint4> rrec;
+        DevBuf<uint32_t> rcounts;
+        const float4 *rlast_q = nullptr; int64_t rlast_nq = 0, rlast_n = 0;
     };
     FeatureBufs feat;
     int64_t opt_feature_match_split = 0;                      // "feature_match_split": rows of b per block column of k_match (0: from the sizes; tests)

@@ -16,6 +16,8 @@
 //   k_match_merge   the partial winners of the splits merged in ascending split order - candidates arrive in ascending j everywhere, so
 //                   a strict < keeps the lowest index among equal distances and the result does not depend on the split
 //   (mutual)        k_match + k_match_merge with the roles swapped, then k_match_mutual
+//   (radius rule)   dcreg_fpfh_radius*: the same cloud and map forms with every point within the radius as the support, through kernels of
+//                   their own - one wave per point, integer sums (k_fpfh_rspfh, k_fpfh_rsum; described where they stand)
 // A result depends on the inputs and the parameters only: the index decides how fast the neighbours are found, never which.
 #include <cmath>
 #include <cstring>
@@ -210,6 +212,244 @@ static __global__ void k_fpfh_counts(const float4 *__restrict__ q, uint32_t n, c
     o[8] = (r2.x & 0xffu) | ((r2.y & 0xffu) << 8) | ((r2.y >> 8) << 16);
 }
 
+// ------------------------------------------------------------------------------------------ descriptors over a radius support
+// dcreg_fpfh_radius*: every used point within the radius is a neighbour - hundreds per point, so ONE WAVE serves one point and its lanes
+// take the candidates of the ball side by side.  Both sums of the rule are integers: no order is part of it, and the lanes' shares meet in
+// LDS counters (pass 1) and in a butterfly of 64-bit adds (pass 2).
+//   ball_walk      the (y, z) rows of the grid that the ball reaches, 64 per batch, one per lane: the row's x-run trimmed to the ball in
+//                  sub-cells (conservative; the float d2 < R2 of the rule decides).  The runs of a batch are laid end to end - their
+//                  starts and an exclusive scan of their lengths in LDS - and the lanes walk that one sequence 64 candidates a trip,
+//                  each finding its run by six halving steps: dense lanes whether a row holds two points or two hundred
+//   k_fpfh_rspfh   pass 1: m by ballot, the pair features in the lanes whose candidate is inside, 33 LDS counters per wave bumped by
+//                  ds_add; then lane b writes q_b, and the counts for dcreg_fpfh_radius_debug_counts.  Past the cap the walk stops
+//   k_fpfh_rsum    pass 2, a kernel boundary behind: the same walk; a lane whose candidate counts gathers its record (nine 16-byte loads,
+//                  consecutive positions in consecutive lanes) and adds w q_b to 33 statically indexed uint64 registers; the wave's
+//                  totals by xor shuffles, lane b normalises and writes value b at the input index
+//   k_fpfh_rstats  one lane per used point: n_out, n_crowded, m_max, m_sum (one atomic each per wave)
+// Per used point 144 + 132 bytes, whatever the radius.
+constexpr int kRecWords = 36;                            // q[33], m, has, 0: nine uint4
+constexpr int kTeams = kBlock / kWave;                   // points per block
+constexpr double kWeightOne = 16384.0, kWeightCap = 1073741824.0;      // 2^14, 2^30
+
+struct BallLds { uint32_t start[kWave], base[kWave], bins[kDim]; };
+
+DCREG_DEVFN void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// floor(x) as a cell index of an axis of n cells, clamped as k_cell_keys clamps a point's
+DCREG_DEVFN int ball_cell(double x, int n) { return (int)fmin(fmax(floor(x), 0.0), (double)(n - 1)); }
+
+// Every point of the grid that can have d2 < R2 from (qx, qy, qz), a point of the grid itself, goes through visit(position, valid) once:
+// all 64 lanes call it together, valid says whether the lane holds a candidate (position 0 otherwise).  visit returns whether to stop,
+// the same in every lane.  Margins: 1e-5 relative and 1e-4 of a (sub-)cell, against 1e-7 of float rounding in d2
+template <class Visit>
+DCREG_DEVFN void ball_walk(const GridDev &g, float qx, float qy, float qz, float R2, BallLds &L, Visit &&visit) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int nxf = g.nx * g.sx;
+    const double fxs = ((double)qx - g.ox) * g.inv_h * (double)g.sx, fy = ((double)qy - g.oy) * g.inv_h, fz = ((double)qz - g.oz) * g.inv_h;
+    const double reach = sqrt((double)R2) * g.inv_h * 1.00001 + 1e-4;                  // cells
+    const int cy = ball_cell(fy, g.ny), cz = ball_cell(fz, g.nz);
+    const int y0 = ball_cell(fy - reach, g.ny), y1 = ball_cell(fy + reach, g.ny), z0 = ball_cell(fz - reach, g.nz), z1 = ball_cell(fz + reach, g.nz);
+    const int nyr = y1 - y0 + 1, nrows = nyr * (z1 - z0 + 1);
+    for (int r0 = 0; r0 < nrows; r0 += kWave) {
+        const int r = r0 + lane;
+        uint32_t s = 0u, len = 0u;
+        if (r < nrows) {
+            const int z = z0 + r / nyr, y = y0 + r % nyr;
+            // the row's slab: its distance from the query in y and z (cells), then what is left of the ball along x
+            const double gy = y < cy ? fy - (double)(y + 1) : (y > cy ? (double)y - fy : 0.0);
+            const double gz = z < cz ? fz - (double)(z + 1) : (z > cz ? (double)z - fz : 0.0);
+            const double left = (double)R2 - ((gy * gy + gz * gz) * (g.h * g.h)) * 0.99999;
+            if (left >= 0.0) {
+                const double rx = sqrt(left) * g.inv_h * (double)g.sx * 1.00001 + 1e-4;      // sub-cells
+                const int x0 = ball_cell(fxs - rx, nxf), x1 = ball_cell(fxs + rx, nxf);
+                const size_t row = ((size_t)z * (size_t)g.ny + (size_t)y) * (size_t)nxf;
+                s = g.cell_start[row + (size_t)x0];
+                len = g.cell_start[row + (size_t)x1 + 1] - s;
+            }
+        }
+        uint32_t incl = len;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const uint32_t v = __shfl_up(incl, o);
+            incl += lane >= o ? v : 0u;
+        }
+        const uint32_t total = __builtin_amdgcn_readlane(incl, kWave - 1);
+        wave_sync();                                      // (the lists of the batch before are read no more)
+        L.start[lane] = s; L.base[lane] = incl - len;
+        wave_sync();
+        for (uint32_t t0 = 0; t0 < total; t0 += kWave) {
+            const uint32_t t = t0 + lane;
+            const bool valid = t < total;
+            // the last run that starts at or before t: it is not empty, because the next one starts beyond t
+            int rr = 0;
+#pragma unroll
+            for (int step = kWave / 2; step > 0; step >>= 1) rr += L.base[rr + step] <= t ? step : 0;
+            const uint32_t pos = valid ? L.start[rr] + (t - L.base[rr]) : 0u;
+            if (visit(pos, valid)) return;
+        }
+    }
+}
+
+// the three bins of the pair (p, q), the pair features of the header's FPFH rule; false: the pair is skipped (f4 == 0 or vn == 0)
+DCREG_DEVFN bool pair_bins(double px, double py, double pz, double npx, double npy, double npz, const float4 c, const float *__restrict__ nq_, int &b0,
+                           int &b1, int &b2) {
+    const double nqx = (double)nq_[0], nqy = (double)nq_[1], nqz = (double)nq_[2];
+    double dx = (double)c.x - px, dy = (double)c.y - py, dz = (double)c.z - pz;
+    const double f4 = sqrt((dx * dx + dy * dy) + dz * dz);
+    if (f4 == 0.0) return false;
+    const double a1 = ((npx * dx + npy * dy) + npz * dz) / f4;
+    const double a2 = ((nqx * dx + nqy * dy) + nqz * dz) / f4;
+    const bool sw = fabs(a1) < fabs(a2);
+    const double n1x = sw ? nqx : npx, n1y = sw ? nqy : npy, n1z = sw ? nqz : npz;
+    const double n2x = sw ? npx : nqx, n2y = sw ? npy : nqy, n2z = sw ? npz : nqz;
+    const double phi = sw ? -a2 : a1;
+    if (sw) { dx = -dx; dy = -dy; dz = -dz; }
+    double vx = dy * n1z - dz * n1y, vy = dz * n1x - dx * n1z, vz = dx * n1y - dy * n1x;
+    const double vn = sqrt((vx * vx + vy * vy) + vz * vz);
+    if (vn == 0.0) return false;
+    vx = vx / vn; vy = vy / vn; vz = vz / vn;
+    const double wx = n1y * vz - n1z * vy, wy = n1z * vx - n1x * vz, wz = n1x * vy - n1y * vx;
+    const double alpha = (vx * n2x + vy * n2y) + vz * n2z;
+    const double theta = atan2((wx * n2x + wy * n2y) + wz * n2z, (n1x * n2x + n1y * n2y) + n1z * n2z);
+    b0 = fpfh_bin(11.0 * ((theta + kPi) / (2.0 * kPi)));
+    b1 = 11 + fpfh_bin(11.0 * ((alpha + 1.0) * 0.5));
+    b2 = 22 + fpfh_bin(11.0 * ((phi + 1.0) * 0.5));
+    return true;
+}
+
+// Pass 1.  Wave w of block b: the point at position 4 b + w of the index's cell order.  rec: kRecWords words per point (q_b, then the m
+// that is reported - min(m, cap + 1) -, then has); counts: 33 words per point
+static __global__ __launch_bounds__(kBlock) void k_fpfh_rspfh(const float4 *__restrict__ q, uint32_t n, GridDev g, float R2, uint32_t cap,
+                                                              const float *__restrict__ nrm, int64_t nstride, uint32_t *__restrict__ rec,
+                                                              uint32_t *__restrict__ counts) {
+    __shared__ BallLds lds[kTeams];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
+    const uint32_t i = blockIdx.x * kTeams + wave;
+    if (i >= n) return;
+    BallLds &L = lds[wave];
+    if (lane < (uint32_t)kDim) L.bins[lane] = 0u;
+    wave_sync();
+    const float4 s4 = q[i];
+    const float *np_ = nrm + (size_t)__float_as_uint(s4.w) * (size_t)nstride;
+    const double px = (double)s4.x, py = (double)s4.y, pz = (double)s4.z;
+    const double npx = (double)np_[0], npy = (double)np_[1], npz = (double)np_[2];
+    uint32_t m = 0u;
+    ball_walk(g, s4.x, s4.y, s4.z, R2, L, [&](uint32_t pos, bool valid) {
+        const float4 c = g.pts[pos];
+        const float d2 = dist2_nofma(s4.x, s4.y, s4.z, c);
+        const bool in = valid && d2 < R2;
+        m += (uint32_t)__popcll(__ballot(in));
+        if (in && d2 > 0.f) {
+            int b0, b1, b2;
+            if (pair_bins(px, py, pz, npx, npy, npz, c, nrm + (size_t)__float_as_uint(c.w) * (size_t)nstride, b0, b1, b2)) {
+                atomicAdd(&L.bins[b0], 1u); atomicAdd(&L.bins[b1], 1u); atomicAdd(&L.bins[b2], 1u);
+            }
+        }
+        return m > cap;
+    });
+    wave_sync();
+    const bool crowded = m > cap;
+    const uint32_t cb = (lane < (uint32_t)kDim && !crowded) ? L.bins[lane] : 0u;
+    const bool has = m >= 2u && __ballot(cb != 0u) != 0ull;
+    // c_b <= m - 1 <= 65534: c_b << 16 fits 32 bits
+    uint32_t word = has ? (cb << 16) / (m - 1u) : 0u;
+    if (lane == (uint32_t)kDim) word = crowded ? cap + 1u : m;
+    if (lane == (uint32_t)kDim + 1u) word = has ? 1u : 0u;
+    if (lane < (uint32_t)kRecWords) rec[(size_t)kRecWords * i + lane] = word;
+    if (lane < (uint32_t)kDim) counts[(size_t)kDim * i + lane] = cb;
+}
+
+// Pass 2.  The same wave for the same point; rec as uint4, nine per point.  A crowded point walks nothing and stays NaN
+static __global__ __launch_bounds__(kBlock) void k_fpfh_rsum(const float4 *__restrict__ q, uint32_t n, GridDev g, float R2, uint32_t cap,
+                                                             const uint4 *__restrict__ rec, float *__restrict__ out) {
+    __shared__ BallLds lds[kTeams];
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
+    const uint32_t i = blockIdx.x * kTeams + wave;
+    if (i >= n) return;
+    const float4 s4 = q[i];
+    if (rec[9 * (size_t)i + 8].y > cap) return;
+    unsigned long long acc[kDim];
+#pragma unroll
+    for (int b = 0; b < kDim; ++b) acc[b] = 0ull;
+    const double R2d = (double)R2;
+    ball_walk(g, s4.x, s4.y, s4.z, R2, lds[wave], [&](uint32_t pos, bool valid) {
+        const float4 c = g.pts[pos];
+        const float d2 = dist2_nofma(s4.x, s4.y, s4.z, c);
+        if (valid && d2 < R2 && d2 > 0.f) {
+            const uint4 *r = rec + 9 * (size_t)pos;
+            const uint4 r8 = r[8];
+            if (r8.z != 0u) {
+                // one IEEE division; the multiply is by a power of two; the clamp before the conversion (the quotient may pass 2^64)
+                const uint32_t w = (uint32_t)fmin(floor((R2d / (double)d2) * kWeightOne), kWeightCap);
+                uint4 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = r[u];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    acc[4 * u] += (unsigned long long)w * v[u].x; acc[4 * u + 1] += (unsigned long long)w * v[u].y;
+                    acc[4 * u + 2] += (unsigned long long)w * v[u].z; acc[4 * u + 3] += (unsigned long long)w * v[u].w;
+                }
+                acc[32] += (unsigned long long)w * r8.x;
+            }
+        }
+        return false;
+    });
+#pragma unroll
+    for (int b = 0; b < kDim; ++b) {
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) acc[b] += __shfl_xor(acc[b], o);
+    }
+    unsigned long long S[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        S[t] = 0ull;
+#pragma unroll
+        for (int b = 0; b < 11; ++b) S[t] += acc[11 * t + b];
+    }
+    if (S[0] == 0ull || S[1] == 0ull || S[2] == 0ull) return;
+    unsigned long long F = 0ull, St = 1ull;
+#pragma unroll
+    for (int b = 0; b < kDim; ++b)
+        if (lane == (uint32_t)b) { F = acc[b]; St = S[b / 11]; }
+    if (lane < (uint32_t)kDim) out[(size_t)kDim * (size_t)__float_as_uint(s4.w) + lane] = (float)((double)F * (100.0 / (double)St));
+}
+
+// cnt[0] += points with a descriptor, cnt[1] += crowded points, cnt[2] = max(cnt[2], m), cnt[3] += m (one atomic each per wave)
+static __global__ void k_fpfh_rstats(const float4 *__restrict__ q, uint32_t n, uint32_t cap, const uint32_t *__restrict__ rec, const float *__restrict__ out,
+                                     unsigned long long *__restrict__ cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long m = 0ull;
+    bool full = false;
+    if (i < n) {
+        m = rec[(size_t)kRecWords * i + kDim];
+        const float f = out[(size_t)kDim * (size_t)__float_as_uint(q[i].w)];
+        full = f == f;
+    }
+    const unsigned long long Fm = __ballot(full), Cm = __ballot(m > (unsigned long long)cap);
+    unsigned long long mx = m, sum = m;
+    for (int o = 32; o > 0; o >>= 1) { mx = max(mx, __shfl_xor(mx, o)); sum += __shfl_xor(sum, o); }
+    if ((threadIdx.x & 63) == 0) {
+        if (Fm) atomicAdd(cnt, (unsigned long long)__popcll(Fm));
+        if (Cm) atomicAdd(cnt + 1, (unsigned long long)__popcll(Cm));
+        atomicMax(cnt + 2, mx);
+        atomicAdd(cnt + 3, sum);
+    }
+}
+
+// dcreg_fpfh_radius_debug_counts: 35 words at the input index of the point at sorted position i (33 counts, m, has)
+static __global__ void k_fpfh_rcounts(const float4 *__restrict__ q, uint32_t n, const uint32_t *__restrict__ rec, const uint32_t *__restrict__ counts,
+                                      uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t *o = out + (size_t)(kDim + 2) * (size_t)__float_as_uint(q[i].w);
+    for (int b = 0; b < kDim; ++b) o[b] = counts[(size_t)kDim * i + b];
+    o[kDim] = rec[(size_t)kRecWords * i + kDim];
+    o[kDim + 1] = rec[(size_t)kRecWords * i + kDim + 1];
+}
+
 // ------------------------------------------------------------------------------------------ matching
 // flag[i] = row i holds 33 finite values; *cnt += their number (one atomic per wave)
 static __global__ void k_match_valid(const float *__restrict__ rows, int64_t n, int64_t stride, uint8_t *__restrict__ flag,
@@ -314,12 +554,37 @@ static __global__ void k_match_mutual(uint32_t n_a, const int32_t *__restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------ descriptors: the host side
+// which rule a descriptor call follows: the k nearest (p) or the radius support (rp), with the info block of that rule
+struct FpfhRule {
+    const dcreg_fpfh_params *p = nullptr;
+    dcreg_fpfh_info *info = nullptr;
+    const dcreg_fpfh_radius_params *rp = nullptr;
+    dcreg_fpfh_radius_info *rinfo = nullptr;
+    bool radius = false;
+    double hint() const { return radius ? rp->radius : p->search_radius; }            // the index's cell edge is capped by it
+    void clear_info() const {
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (rinfo) std::memset(rinfo, 0, sizeof(*rinfo));
+    }
+};
+
 int fpfh_check(dcreg_ctx *c, const dcreg_fpfh_params *p) {
     if (!p) { c->fail("null fpfh parameters"); return DCREG_E_INVALID; }
     if (p->k < kMinK || p->k > kMaxK) { c->fail("fpfh k is %d: %d .. %d expected", p->k, kMinK, kMaxK); return DCREG_E_INVALID; }
     if (!(std::isfinite(p->search_radius) && p->search_radius >= 0.0)) { c->fail("fpfh search_radius is %g: finite and >= 0 expected", p->search_radius); return DCREG_E_INVALID; }
     return DCREG_OK;
 }
+
+constexpr int kMinCap = 2, kMaxCap = 65535;
+int fpfh_radius_check(dcreg_ctx *c, const dcreg_fpfh_radius_params *p) {
+    if (!p) { c->fail("null fpfh radius parameters"); return DCREG_E_INVALID; }
+    if (!(std::isfinite(p->radius) && p->radius > 0.0)) { c->fail("fpfh radius is %g: finite and > 0 expected", p->radius); return DCREG_E_INVALID; }
+    const float R2 = (float)(p->radius * p->radius);
+    if (!(R2 > 0.f && R2 < 3.0e38f)) { c->fail("fpfh radius is %g: its square is not a float in (0, 3.0e38)", p->radius); return DCREG_E_INVALID; }
+    if (p->max_neighbors < kMinCap || p->max_neighbors > kMaxCap) { c->fail("fpfh max_neighbors is %d: %d .. %d expected", p->max_neighbors, kMinCap, kMaxCap); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+int fpfh_check(dcreg_ctx *c, const FpfhRule &r) { return r.radius ? fpfh_radius_check(c, r.rp) : fpfh_check(c, r.p); }
 
 // memory another stream may have written (a device-pointer argument): the context's own stream waits for the legacy default stream, as
 // upload_cloud orders a device cloud
@@ -352,6 +617,7 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[2] = {0, 0};
     F.last_q = nq > 0 ? g.pts : nullptr; F.last_nq = nq; F.last_n = n;      // (dcreg_fpfh_debug_counts)
+    F.rlast_n = 0;
     if (nq > 0) {
         const float4 *q = g.pts;
         float bound = 3.0e38f;
@@ -377,6 +643,46 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     return DCREG_OK;
 }
 
+// fpfh_run under the radius rule: pass 1, pass 2, the statistics
+int fpfh_radius_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float *nrm, int64_t nstride, const dcreg_fpfh_radius_params *p,
+                    float *out, bool on_device, dcreg_fpfh_radius_info *info) {
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    const size_t nqs = (size_t)std::max<int64_t>(nq, 1);
+    if (F.out.ensure(c, (size_t)kDim * (size_t)n) || F.cnt.ensure(c, 4) || F.rrec.ensure(c, 9 * nqs) || F.rcounts.ensure(c, (size_t)kDim * nqs))
+        return DCREG_E_NOMEM;
+    hipLaunchKernelGGL(k_fpfh_fill, dim3(blocks((int64_t)kDim * n, 256)), dim3(256), 0, c->stream, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
+    HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 4 * sizeof(unsigned long long), c->stream));
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    F.rlast_q = nq > 0 ? g.pts : nullptr; F.rlast_nq = nq; F.rlast_n = n;      // (dcreg_fpfh_radius_debug_counts)
+    F.last_n = 0;
+    if (nq > 0) {
+        const float4 *q = g.pts;
+        const float R2 = (float)(p->radius * p->radius);
+        const uint32_t cap = (uint32_t)p->max_neighbors;
+        hipLaunchKernelGGL(k_fpfh_rspfh, dim3(blocks(nq, kTeams)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, R2, cap, nrm, nstride,
+                           (uint32_t *)F.rrec.data(), F.rcounts.data());
+        hipLaunchKernelGGL(k_fpfh_rsum, dim3(blocks(nq, kTeams)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, R2, cap, (const uint4 *)F.rrec.data(),
+                           F.out.data());
+        hipLaunchKernelGGL(k_fpfh_rstats, dim3(blocks(nq, 256)), dim3(256), 0, c->stream, q, (uint32_t)nq, cap, (const uint32_t *)F.rrec.data(),
+                           (const float *)F.out.data(), F.cnt.data());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                              c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (info) {
+        info->n_in = n; info->n_used = nq; info->n_out = (int64_t)cnt[0]; info->n_empty = nq - (int64_t)cnt[0]; info->n_crowded = (int64_t)cnt[1];
+        info->m_max = (int64_t)cnt[2]; info->m_sum = (int64_t)cnt[3];
+    }
+    return DCREG_OK;
+}
+
+int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float *nrm, int64_t nstride, const FpfhRule &r, float *out, bool on_device) {
+    return r.radius ? fpfh_radius_run(c, nq, g, n, nrm, nstride, r.rp, out, on_device, r.rinfo) : fpfh_run(c, nq, g, n, nrm, nstride, r.p, out, on_device, r.info);
+}
+
 // the n packed points at pts lose those without a finite normal, the rest is compacted and indexed in the outlier scratch
 int fpfh_index(dcreg_ctx *c, float4 *pts, int64_t n, const float *nrm, int64_t nstride, double hint, int64_t *n_used) {
     hipLaunchKernelGGL(k_fpfh_unuse, dim3(blocks(n, 256)), dim3(256), 0, c->stream, pts, n, nrm, nstride);
@@ -386,22 +692,22 @@ int fpfh_index(dcreg_ctx *c, float4 *pts, int64_t n, const float *nrm, int64_t n
 
 // dcreg_fpfh*: the cloud packed, the normals given or estimated, the used points indexed, the two kernels, the copies
 int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const float *normals, int64_t nstride, bool on_device,
-               const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *out, float *normals_out, dcreg_fpfh_info *info) {
+               const dcreg_normal_params *np, const FpfhRule &rule, float *out, float *normals_out) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
-    if (int rc = fpfh_check(c, p)) return rc;
+    if (int rc = fpfh_check(c, rule)) return rc;
     if (!normals && !np) { c->fail("no normals and no normal parameters: one of them is expected"); return DCREG_E_INVALID; }
     if (!normals) if (int rc = normals_check(c, np)) return rc;
     if (n < 0 || stride < 3 || (normals && nstride < 3)) { c->fail("invalid fpfh arguments"); return DCREG_E_INVALID; }
     if (n > (int64_t)INT32_MAX) { c->fail("too many points for one descriptor call (%lld)", (long long)n); return DCREG_E_INVALID; }
     if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
-    if (info) std::memset(info, 0, sizeof(*info));
+    rule.clear_info();
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::OutlierBufs &B = c->outl;
     if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
-    const double hint = p->search_radius;
+    const double hint = rule.hint();
     int64_t n_used = 0;
     const float *nrm = normals;
     if (normals) {
@@ -427,21 +733,21 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
         // (a finite point without a normal is not used: the index over the finite points serves only when every one of them has one)
         if (ni.n_out != n_finite) if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
     }
-    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, nstride, p, out, on_device, info);
+    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, nstride, rule, out, on_device);
 }
 
 // dcreg_target_fpfh*: the whole map's points through the map's own index and its kept normals
-int fpfh_map(dcreg_ctx *c, bool on_device, const dcreg_fpfh_params *p, float *out, int64_t capacity, dcreg_fpfh_info *info) {
+int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int64_t capacity) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
-    if (int rc = fpfh_check(c, p)) return rc;
+    if (int rc = fpfh_check(c, rule)) return rc;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
     if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
     const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;      // the whole map's index, whichever is active
     const int64_t n = wm.n;
     if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
-    if (info) std::memset(info, 0, sizeof(*info));
+    rule.clear_info();
     HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::FeatureBufs &F = c->feat;
     if (F.cnt.ensure(c, 3)) return DCREG_E_NOMEM;
@@ -452,14 +758,14 @@ int fpfh_map(dcreg_ctx *c, bool on_device, const dcreg_fpfh_params *p, float *ou
     HIP_TRY(c, hipMemcpyAsync(&bad, F.cnt.data() + 2, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const float *nrm = (const float *)c->nicp.normals.data();
-    if (bad == 0) return fpfh_run(c, n, wm.grid, n, nrm, 4, p, out, on_device, info);
+    if (bad == 0) return fpfh_run(c, n, wm.grid, n, nrm, 4, rule, out, on_device);
     // some map points have no normal: they are no candidates, so the others are indexed on their own, as a cloud's
     dcreg_ctx::OutlierBufs &B = c->outl;
     if (B.pts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     HIP_TRY(c, hipMemcpyAsync(B.pts.data(), wm.raw.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     int64_t n_used = 0;
-    if (int rc = fpfh_index(c, B.pts.data(), n, nrm, 4, p->search_radius, &n_used)) return rc;
-    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, 4, p, out, on_device, info);
+    if (int rc = fpfh_index(c, B.pts.data(), n, nrm, 4, rule.hint(), &n_used)) return rc;
+    return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, 4, rule, out, on_device);
 }
 
 // dcreg_fpfh_debug_counts (include/dcreg_debug.h)
@@ -476,6 +782,27 @@ int fpfh_debug_counts(dcreg_ctx *c, uint8_t *out, int64_t capacity) {
     HIP_TRY(c, hipMemsetAsync(F.dbg.data(), 0, sizeof(uint32_t) * words, c->stream));
     if (F.last_nq > 0)
         hipLaunchKernelGGL(k_fpfh_counts, dim3(blocks(F.last_nq, 256)), dim3(256), 0, c->stream, F.last_q, (uint32_t)F.last_nq, F.spfh.data(), F.dbg.data());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, F.dbg.data(), sizeof(uint32_t) * words, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
+// dcreg_fpfh_radius_debug_counts (include/dcreg_debug.h)
+int fpfh_radius_debug_counts(dcreg_ctx *c, uint32_t *out, int64_t capacity) {
+    if (!c) return DCREG_E_INVALID;
+    if (int rc = refuse_in_flight(c)) return rc;
+    dcreg_ctx::FeatureBufs &F = c->feat;
+    if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
+    if (F.rlast_n <= 0) { c->fail("no radius descriptor call to report"); return DCREG_E_STATE; }
+    if (capacity < F.rlast_n) { c->fail("the call had %lld points, the capacity is %lld", (long long)F.rlast_n, (long long)capacity); return DCREG_E_INVALID; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t words = (size_t)(kDim + 2) * (size_t)F.rlast_n;
+    if (F.dbg.ensure(c, words)) return DCREG_E_NOMEM;
+    HIP_TRY(c, hipMemsetAsync(F.dbg.data(), 0, sizeof(uint32_t) * words, c->stream));
+    if (F.rlast_nq > 0)
+        hipLaunchKernelGGL(k_fpfh_rcounts, dim3(blocks(F.rlast_nq, 256)), dim3(256), 0, c->stream, F.rlast_q, (uint32_t)F.rlast_nq,
+                           (const uint32_t *)F.rrec.data(), (const uint32_t *)F.rcounts.data(), F.dbg.data());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(out, F.dbg.data(), sizeof(uint32_t) * words, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -572,19 +899,50 @@ int dcreg_default_fpfh_params(dcreg_fpfh_params *p) {
 }
 int dcreg_fpfh(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride_floats, const float *normals, int64_t normals_stride_floats,
                const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *fpfh_out, float *normals_out, dcreg_fpfh_info *info) {
-    return fpfh_cloud(c, xyz, n, stride_floats, normals, normals_stride_floats, false, np, p, fpfh_out, normals_out, info);
+    FpfhRule r; r.p = p; r.info = info;
+    return fpfh_cloud(c, xyz, n, stride_floats, normals, normals_stride_floats, false, np, r, fpfh_out, normals_out);
 }
 int dcreg_fpfh_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride_floats, const float *d_normals, int64_t normals_stride_floats,
                       const dcreg_normal_params *np, const dcreg_fpfh_params *p, float *d_fpfh_out, float *d_normals_out, dcreg_fpfh_info *info) {
-    return fpfh_cloud(c, d_xyz, n, stride_floats, d_normals, normals_stride_floats, true, np, p, d_fpfh_out, d_normals_out, info);
+    FpfhRule r; r.p = p; r.info = info;
+    return fpfh_cloud(c, d_xyz, n, stride_floats, d_normals, normals_stride_floats, true, np, r, d_fpfh_out, d_normals_out);
 }
 int dcreg_target_fpfh(dcreg_ctx *c, const dcreg_fpfh_params *p, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info) {
-    return fpfh_map(c, false, p, fpfh_out, capacity_points, info);
+    FpfhRule r; r.p = p; r.info = info;
+    return fpfh_map(c, false, r, fpfh_out, capacity_points);
 }
 int dcreg_target_fpfh_device(dcreg_ctx *c, const dcreg_fpfh_params *p, float *d_fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info) {
-    return fpfh_map(c, true, p, d_fpfh_out, capacity_points, info);
+    FpfhRule r; r.p = p; r.info = info;
+    return fpfh_map(c, true, r, d_fpfh_out, capacity_points);
 }
 int dcreg_fpfh_debug_counts(dcreg_ctx *c, uint8_t *counts_out, int64_t capacity_points) { return fpfh_debug_counts(c, counts_out, capacity_points); }
+int dcreg_default_fpfh_radius_params(dcreg_fpfh_radius_params *p) {
+    if (!p) return DCREG_E_INVALID;
+    std::memset(p, 0, sizeof(*p));
+    p->radius = 1.0; p->max_neighbors = 65535;
+    return DCREG_OK;
+}
+static FpfhRule radius_rule(const dcreg_fpfh_radius_params *p, dcreg_fpfh_radius_info *info) {
+    FpfhRule r; r.rp = p; r.rinfo = info; r.radius = true;
+    return r;
+}
+int dcreg_fpfh_radius(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride_floats, const float *normals, int64_t normals_stride_floats,
+                      const dcreg_normal_params *np, const dcreg_fpfh_radius_params *p, float *fpfh_out, float *normals_out, dcreg_fpfh_radius_info *info) {
+    return fpfh_cloud(c, xyz, n, stride_floats, normals, normals_stride_floats, false, np, radius_rule(p, info), fpfh_out, normals_out);
+}
+int dcreg_fpfh_radius_device(dcreg_ctx *c, const float *d_xyz, int64_t n, int64_t stride_floats, const float *d_normals, int64_t normals_stride_floats,
+                             const dcreg_normal_params *np, const dcreg_fpfh_radius_params *p, float *d_fpfh_out, float *d_normals_out,
+                             dcreg_fpfh_radius_info *info) {
+    return fpfh_cloud(c, d_xyz, n, stride_floats, d_normals, normals_stride_floats, true, np, radius_rule(p, info), d_fpfh_out, d_normals_out);
+}
+int dcreg_target_fpfh_radius(dcreg_ctx *c, const dcreg_fpfh_radius_params *p, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_radius_info *info) {
+    return fpfh_map(c, false, radius_rule(p, info), fpfh_out, capacity_points);
+}
+int dcreg_target_fpfh_radius_device(dcreg_ctx *c, const dcreg_fpfh_radius_params *p, float *d_fpfh_out, int64_t capacity_points,
+                                    dcreg_fpfh_radius_info *info) {
+    return fpfh_map(c, true, radius_rule(p, info), d_fpfh_out, capacity_points);
+}
+int dcreg_fpfh_radius_debug_counts(dcreg_ctx *c, uint32_t *counts_out, int64_t capacity_points) { return fpfh_radius_debug_counts(c, counts_out, capacity_points); }
 int dcreg_feature_match(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, int32_t *idx_out,
                         double *d_out, int32_t *idx2_out, double *d2nd_out, uint8_t *mutual_out, dcreg_match_info *info) {
     return feature_match(c, a, n_a, stride_a, b, n_b, stride_b, false, idx_out, d_out, idx2_out, d2nd_out, mutual_out, info);

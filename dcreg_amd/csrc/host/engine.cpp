@@ -1044,6 +1044,8 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_voxel_map_info")) return sizeof(dcreg_voxel_map_info);
     if (!std::strcmp(name, "dcreg_fpfh_params")) return sizeof(dcreg_fpfh_params);
     if (!std::strcmp(name, "dcreg_fpfh_info")) return sizeof(dcreg_fpfh_info);
+    if (!std::strcmp(name, "dcreg_fpfh_radius_params")) return sizeof(dcreg_fpfh_radius_params);
+    if (!std::strcmp(name, "dcreg_fpfh_radius_info")) return sizeof(dcreg_fpfh_radius_info);
     if (!std::strcmp(name, "dcreg_match_info")) return sizeof(dcreg_match_info);
     if (!std::strcmp(name, "dcreg_align_params")) return sizeof(dcreg_align_params);
     if (!std::strcmp(name, "dcreg_align_record")) return sizeof(dcreg_align_record);

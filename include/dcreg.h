@@ -48,6 +48,7 @@
  *       ... as the map: a rebuild after a pose-graph update, a local map         -> dcreg_set_target_keyframes
  *   correspondences for a global alignment (not in the reference: a start pose outside the ICP's basin)
  *       FPFH descriptors of a cloud / of the resident map                        -> dcreg_fpfh[_device], dcreg_target_fpfh[_device]
+ *       ... over every point within a radius (PCL setRadiusSearch)               -> dcreg_fpfh_radius[_device], dcreg_target_fpfh_radius[_device]
  *       nearest and second-nearest rows in feature space, mutual flags           -> dcreg_feature_match[_device]
  *       the pose most point pairs agree on (seeded RANSAC), the best T as start poses -> dcreg_align_correspondences[_device]
  *
@@ -1710,6 +1711,69 @@ int dcreg_fpfh_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride
                       const dcreg_normal_params *, const dcreg_fpfh_params *, float *d_fpfh_out, float *d_normals_out, dcreg_fpfh_info *info);
 int dcreg_target_fpfh(dcreg_ctx *, const dcreg_fpfh_params *, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info);
 int dcreg_target_fpfh_device(dcreg_ctx *, const dcreg_fpfh_params *, float *d_fpfh_out, int64_t capacity_points, dcreg_fpfh_info *info);
+
+/* ---------------- FPFH over a radius support ----------------
+ * The same descriptor with PCL's other neighbourhood (FPFHEstimation with setRadiusSearch): EVERY used point within `radius` is a
+ * neighbour, a few hundred per point at the usual five leaves.  With m unbounded there is no rank-ordered list to sum over, so both
+ * sums of this rule are INTEGERS: no order of summation is part of it, and the output is bitwise the numpy reference of
+ * tests/fpfh_radius_ref.py with the one freedom of the rule above (atan2 at an interior bin edge of theta, the same "edge-near" flags).
+ * Unchanged from the rule above: the used points, dcreg_knn's float d2 = (dx*dx + dy*dy) + dz*dz with every operation rounded to float,
+ * the pair features in double and the three bins.  Parameters: radius, finite and > 0, with R2 = (float)(radius * radius) > 0 and
+ * < 3.0e38f; max_neighbors in 2 .. 65535.
+ *   1. neighbours of a used point i: every used point j with d2_ij < R2 (strict), the point itself and exact duplicates included;
+ *      m_i is their number;
+ *   2. a point with m_i > max_neighbors is CROWDED: it has no SPFH and it is EMPTY, counted in n_crowded as well as in n_empty (its
+ *      walk stops where the count passes the cap: it is reported with m = max_neighbors + 1);
+ *   3. counts: for every neighbour with d2 > 0 the pair features and bins of the rule above; pairs with f4 == 0 or vn == 0 are skipped;
+ *      c_b(i), b = 0 .. 32, are integer counts;
+ *   4. a point has an SPFH when 2 <= m_i <= max_neighbors and at least one pair was counted;
+ *   5. quantised SPFH: q_b(i) = (c_b(i) << 16) / (m_i - 1), integer floor.  c_b <= m - 1, so q_b <= 65536 and each block of 11 sums to
+ *      at most 65536;
+ *   6. weight: w_ij = min((uint64) floor(((double)R2 / (double)d2_ij) * 16384.0), 2^30) - one IEEE double division, a multiply by a
+ *      power of two; 16384 <= w <= 2^30, and pairs closer than radius / 256 share the clamped weight;
+ *   7. FPFH: F_b(i) = sum of w_ij * q_b(j) over the neighbours j with d2_ij > 0 and an SPFH, in uint64.  F_b <= m * 2^30 * 2^16 <=
+ *      65535 * 2^46 < 2^62, and a block's sum S_t has the same bound because a block of q sums to at most 65536: nothing wraps.
+ *      That bound is why max_neighbors ends at 65535;
+ *   8. normalisation: out_b = (float)((double)F_b * (100.0 / (double)S_t)), uint64 to double rounding to nearest even.  A point with
+ *      any S_t == 0 is EMPTY: NaN in all 33 outputs;
+ *   9. info: n_in, n_used, n_empty, n_crowded, n_out = n_used - n_empty, m_max and m_sum = the maximum and the sum of m over the used
+ *      points (a crowded point with max_neighbors + 1).  m_sum / n_used is what a caller tunes the radius by.
+ * The calls take the arguments of dcreg_fpfh / dcreg_target_fpfh with this parameter block and follow their text above: normals == NULL
+ * estimates them with normal_params under the k-rule of dcreg_normals, the map form reads the kept normals through the map's own index
+ * (whole or window), nothing else in the context changes, both wait for the stream, repeated calls and other contexts give the same bits.
+ * DCREG_E_INVALID, before anything is queued: null context or parameters, a radius that is not finite or not > 0 or whose R2 leaves
+ * (0, 3.0e38), max_neighbors outside 2 .. 65535, stride < 3, normals_stride < 3, n < 0, more than 2^31 - 1 points, a null cloud with
+ * n > 0, a null output, both normals and normal_params NULL, the refusals of dcreg_normals for normal_params when it is read, a capacity
+ * below the map's size.  DCREG_E_STATE: a linearisation in flight; no target or no kept normals (the map form).  Device memory does not
+ * depend on the radius: the outlier filter's scratch for the cloud and its index (the cloud form), 276 bytes per used point for the
+ * quantised SPFH and the counts, 132 per point for the output - kept as scratch of the context and reused by the next call. */
+typedef struct dcreg_fpfh_radius_params {
+    double radius;         /* the support: neighbours are the used points with d2 < (float)(radius * radius) (PCL setRadiusSearch) */
+    int max_neighbors;     /* a point with more neighbours is crowded and gets no descriptor, 2 .. 65535 */
+    int reserved0_;
+    double reserved_[2];
+} dcreg_fpfh_radius_params;
+typedef struct dcreg_fpfh_radius_info {
+    int64_t n_in;        /* points passed in / points of the map */
+    int64_t n_used;      /* ... with finite coordinates and a finite normal */
+    int64_t n_empty;     /* ... of those, without a descriptor (crowded, or a block's sum is 0) */
+    int64_t n_crowded;   /* ... of those, with more than max_neighbors neighbours */
+    int64_t n_out;       /* points that received a descriptor */
+    int64_t m_max;       /* the largest m of a used point */
+    int64_t m_sum;       /* the sum of m over the used points */
+    int64_t reserved_;
+} dcreg_fpfh_radius_info;
+/* radius = 1.0, max_neighbors = 65535 */
+int dcreg_default_fpfh_radius_params(dcreg_fpfh_radius_params *);
+int dcreg_fpfh_radius(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const float *normals, int64_t normals_stride_floats,
+                      const dcreg_normal_params *, const dcreg_fpfh_radius_params *, float *fpfh_out, float *normals_out,
+                      dcreg_fpfh_radius_info *info);
+int dcreg_fpfh_radius_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const float *d_normals,
+                             int64_t normals_stride_floats, const dcreg_normal_params *, const dcreg_fpfh_radius_params *, float *d_fpfh_out,
+                             float *d_normals_out, dcreg_fpfh_radius_info *info);
+int dcreg_target_fpfh_radius(dcreg_ctx *, const dcreg_fpfh_radius_params *, float *fpfh_out, int64_t capacity_points, dcreg_fpfh_radius_info *info);
+int dcreg_target_fpfh_radius_device(dcreg_ctx *, const dcreg_fpfh_radius_params *, float *d_fpfh_out, int64_t capacity_points,
+                                    dcreg_fpfh_radius_info *info);
 
 /* The matching rule.  a: n_a rows, b: n_b rows, 33 floats each, stride_a / stride_b floats apart (>= 33):
  *   - a row with any non-finite value is neither a query nor a candidate; as a query it returns index -1 and NaN distances;

@@ -373,6 +373,11 @@ int dcreg_debug_index_check(dcreg_ctx *, int64_t mismatches[5]);
  * below the call's points. */
 int dcreg_fpfh_debug_counts(dcreg_ctx *, uint8_t *counts_out, int64_t capacity_points);
 
+/* The same behind the last dcreg_fpfh_radius* / dcreg_target_fpfh_radius* call: 35 uint32 per input point - the 33 counts c_b, the m
+ * that the info sums (max_neighbors + 1 for a crowded point, whose counts are 0), 1 when the point has an SPFH; all zero for an unused
+ * point.  A call of either rule ends the other's report: DCREG_E_STATE then, and without any such call; DCREG_E_INVALID as above. */
+int dcreg_fpfh_radius_debug_counts(dcreg_ctx *, uint32_t *counts_out, int64_t capacity_points);
+
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */
 void dcreg_set_error_message(dcreg_ctx *, const char *msg);
 
