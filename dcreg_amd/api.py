@@ -218,6 +218,7 @@ EXPORTS = [
     "dcreg_default_fpfh_radius_params", "dcreg_fpfh_radius", "dcreg_fpfh_radius_device", "dcreg_target_fpfh_radius", "dcreg_target_fpfh_radius_device",
     "dcreg_fpfh_radius_debug_counts",
     "dcreg_default_align_params", "dcreg_align_correspondences", "dcreg_align_correspondences_device",
+    "dcreg_default_consensus_params", "dcreg_consensus_correspondences", "dcreg_consensus_correspondences_device",
 ]
 
 _lib = None
@@ -934,6 +935,70 @@ def correspondences_from_match(match, mutual_only=True, max_ratio=None):
     return rows.astype(np.int32), idx[rows].astype(np.int32)
 
 
+class ConsensusParams(C.Structure):
+    _fields_ = [("compat_distance", C.c_double), ("min_length", C.c_double), ("inlier_distance", C.c_double), ("n_seeds", C.c_int),
+                ("consensus_size", C.c_int), ("n_best", C.c_int), ("refine_iterations", C.c_int), ("reserved_", C.c_double * 2)]
+
+
+class ConsensusRecord(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("seed", C.c_int32), ("seed_rank", C.c_int32), ("weight", C.c_int32), ("n_members", C.c_int32),
+                ("count", C.c_int32), ("cost", C.c_uint64), ("n_inliers", C.c_int32), ("refined", C.c_int32), ("rmse", C.c_double)]
+
+
+class ConsensusInfo(C.Structure):
+    _fields_ = [("n_pairs", C.c_int64), ("n_used", C.c_int64), ("n_edges", C.c_int64), ("max_degree", C.c_int64), ("n_seeds", C.c_int64),
+                ("n_skipped", C.c_int64), ("n_scored", C.c_int64), ("n_returned", C.c_int64), ("reserved_", C.c_int64)]
+
+
+_STRUCTS.update({"dcreg_consensus_params": ConsensusParams, "dcreg_consensus_record": ConsensusRecord, "dcreg_consensus_info": ConsensusInfo})
+CONSENSUS_MAX_PAIRS, CONSENSUS_MAX_SEEDS, CONSENSUS_MAX_SET = 32768, 1024, 64
+
+
+def _check_consensus_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_consensus_params block"""
+    if not isinstance(p, ConsensusParams):
+        raise ValueError("%s: consensus_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not (np.isfinite(p.compat_distance) and p.compat_distance > 0.0):
+        raise ValueError("%s: a finite compat_distance > 0 is expected, got %r" % (what, p.compat_distance))
+    if not (np.isfinite(p.min_length) and p.min_length >= 0.0):
+        raise ValueError("%s: a finite min_length >= 0 is expected, got %r" % (what, p.min_length))
+    if not (np.isfinite(p.inlier_distance) and p.inlier_distance > 0.0):
+        raise ValueError("%s: a finite inlier_distance > 0 is expected, got %r" % (what, p.inlier_distance))
+    if not 1 <= p.n_seeds <= CONSENSUS_MAX_SEEDS:
+        raise ValueError("%s: n_seeds in [1, %d] is expected, got %d" % (what, CONSENSUS_MAX_SEEDS, p.n_seeds))
+    if not 3 <= p.consensus_size <= CONSENSUS_MAX_SET:
+        raise ValueError("%s: consensus_size in [3, %d] is expected, got %d" % (what, CONSENSUS_MAX_SET, p.consensus_size))
+    if not 1 <= p.n_best <= ALIGN_MAX_BEST:
+        raise ValueError("%s: n_best in [1, %d] is expected, got %d" % (what, ALIGN_MAX_BEST, p.n_best))
+    if not 0 <= p.refine_iterations <= ALIGN_MAX_REFINE:
+        raise ValueError("%s: refine_iterations in [0, %d] is expected, got %d" % (what, ALIGN_MAX_REFINE, p.refine_iterations))
+
+
+def consensus_params(compat_distance=0.5, min_length=1.0, inlier_distance=0.5, n_seeds=64, consensus_size=16, n_best=1, refine_iterations=3):
+    """dcreg_consensus_params: two pairs are compatible when their lengths on both sides are at least min_length and differ by at most
+    compat_distance (metres); the n_seeds pairs of the largest second-order weight each gather a set of at most consensus_size members;
+    the sets' poses are scored with the inlier distance d, the n_best best returned and refined; include/dcreg.h has the rule"""
+    p = ConsensusParams()
+    p.compat_distance = float(compat_distance)
+    p.min_length = float(min_length)
+    p.inlier_distance = float(inlier_distance)
+    p.n_seeds = int(n_seeds)
+    p.consensus_size = int(consensus_size)
+    p.n_best = int(n_best)
+    p.refine_iterations = int(refine_iterations)
+    _check_consensus_params(p, "consensus_params")
+    return p
+
+
+def _consensus_info_dict(i):
+    return {k: getattr(i, k) for k in ("n_pairs", "n_used", "n_edges", "max_degree", "n_seeds", "n_skipped", "n_scored", "n_returned")}
+
+
+def _consensus_records(recs, n):
+    return [{"T": np.array(r.T, np.float64).reshape(4, 4), "seed": r.seed, "seed_rank": r.seed_rank, "weight": r.weight, "n_members": r.n_members,
+             "count": r.count, "cost": r.cost, "n_inliers": r.n_inliers, "refined": r.refined, "rmse": r.rmse} for r in recs[:n]]
+
+
 def _check_voxel_map_params(p, what):
     """the refusals of include/dcreg.h for a dcreg_voxel_map_params block"""
     if not isinstance(p, VoxelMapParams):
@@ -1444,6 +1509,11 @@ def load():
         for name in ("dcreg_align_correspondences", "dcreg_align_correspondences_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.POINTER(AlignParams),
                                          C.POINTER(AlignRecord), vp, C.POINTER(AlignInfo)]
+    if hasattr(L, "dcreg_consensus_correspondences"):  # (likewise)
+        L.dcreg_default_consensus_params.argtypes = [C.POINTER(ConsensusParams)]
+        for name in ("dcreg_consensus_correspondences", "dcreg_consensus_correspondences_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.POINTER(ConsensusParams),
+                                         C.POINTER(ConsensusRecord), vp, vp, vp, vp, C.POINTER(ConsensusInfo)]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2418,6 +2488,67 @@ class Context:
                                                                int(n_pairs), C.byref(p), recs, C.c_void_p(dev_mask or None), C.byref(info)),
                     "dcreg_align_correspondences_device")
         return {"records": _align_records(recs, info.n_returned), "info": _align_info_dict(info)}
+
+    # ---- a consensus pose from the correspondences' compatibility graph (include/dcreg.h: dcreg_consensus_correspondences)
+    def consensus_correspondences(self, a, b, corr_a, corr_b, params=None, want_mask=True, want_members=False, want_weights=False):
+        """dcreg_consensus_correspondences: the rigid pose q ~ R p + t of the largest length-preserving set among the point pairs
+        (a[corr_a[m]], b[corr_b[m]]), for inlier shares of a per cent and below (include/dcreg.h has the rule).  Arguments as
+        align_correspondences takes them, at most 32768 pairs; params: consensus_params(...), None = the defaults.  -> dict records (best
+        first, at most n_best dicts: T [4, 4] float64, seed, seed_rank, weight, n_members, count, cost, n_inliers, refined, rmse), mask
+        ([m] uint8: the inliers of records[0]; None without want_mask), info (n_pairs, n_used, n_edges, max_degree, n_seeds, n_skipped,
+        n_scored, n_returned); with want_members: members [n_best, consensus_size] int32 (the correspondence numbers of each record's
+        set, -1 padded); with want_weights: degree and weight [m] uint32 (0 at unused pairs) - the pairs with weight > 0 are a far
+        cleaner input for align_correspondences"""
+        p = params if params is not None else consensus_params()
+        _check_consensus_params(p, "consensus_correspondences")
+        a = _points(a, "consensus_correspondences")
+        b = _points(b, "consensus_correspondences")
+        ca = _corr_index(corr_a, "consensus_correspondences")
+        cb = _corr_index(corr_b, "consensus_correspondences")
+        if ca.shape[0] != cb.shape[0]:
+            raise ValueError("consensus_correspondences: index arrays of one length are expected, got %d and %d" % (ca.shape[0], cb.shape[0]))
+        m = ca.shape[0]
+        if m > CONSENSUS_MAX_PAIRS:
+            raise ValueError("consensus_correspondences: at most %d pairs are expected, got %d" % (CONSENSUS_MAX_PAIRS, m))
+        recs = (ConsensusRecord * p.n_best)()
+        mask = np.zeros(max(m, 1), np.uint8) if want_mask else None
+        members = np.full((p.n_best, p.consensus_size), -1, np.int32) if want_members else None
+        degree = np.zeros(max(m, 1), np.uint32) if want_weights else None
+        weight = np.zeros(max(m, 1), np.uint32) if want_weights else None
+        info = ConsensusInfo()
+        ptr = lambda x: x.ctypes.data if x is not None else None
+        self._check(self._L.dcreg_consensus_correspondences(self._h, a.ctypes.data, a.shape[0], a.shape[1], b.ctypes.data, b.shape[0], b.shape[1],
+                                                            ca.ctypes.data, cb.ctypes.data, m, C.byref(p), recs, ptr(mask), ptr(members), ptr(degree),
+                                                            ptr(weight), C.byref(info)), "dcreg_consensus_correspondences")
+        out = {"records": _consensus_records(recs, info.n_returned), "mask": mask[:m] if want_mask else None, "info": _consensus_info_dict(info)}
+        if want_members:
+            out["members"] = members
+        if want_weights:
+            out["degree"], out["weight"] = degree[:m], weight[:m]
+        return out
+
+    def consensus_correspondences_device(self, dev_a, n_a, stride_a, dev_b, n_b, stride_b, dev_corr_a, dev_corr_b, n_pairs, params=None, dev_mask=0,
+                                         dev_members=0, dev_degree=0, dev_weight=0):
+        """dcreg_consensus_correspondences_device: both clouds, both int32 index arrays and the outputs wanted (0: not wanted) - the mask
+        (n_pairs bytes), the members (n_best x consensus_size int32), degree and weight (n_pairs uint32 each) - in device memory.
+        -> dict records / info, as consensus_correspondences"""
+        p = params if params is not None else consensus_params()
+        _check_consensus_params(p, "consensus_correspondences_device")
+        _check_device_cloud(n_a, stride_a, "consensus_correspondences_device")
+        _check_device_cloud(n_b, stride_b, "consensus_correspondences_device")
+        if int(n_pairs) < 0 or int(n_pairs) > CONSENSUS_MAX_PAIRS:
+            raise ValueError("consensus_correspondences_device: 0 .. %d pairs are expected, got %d" % (CONSENSUS_MAX_PAIRS, int(n_pairs)))
+        if int(n_pairs) > 0 and (not dev_corr_a or not dev_corr_b):
+            raise ValueError("consensus_correspondences_device: both index arrays are expected")
+        recs = (ConsensusRecord * p.n_best)()
+        info = ConsensusInfo()
+        self._check(self._L.dcreg_consensus_correspondences_device(self._h, C.c_void_p(dev_a or None), int(n_a), int(stride_a), C.c_void_p(dev_b or None),
+                                                                   int(n_b), int(stride_b), C.c_void_p(dev_corr_a or None),
+                                                                   C.c_void_p(dev_corr_b or None), int(n_pairs), C.byref(p), recs,
+                                                                   C.c_void_p(dev_mask or None), C.c_void_p(dev_members or None),
+                                                                   C.c_void_p(dev_degree or None), C.c_void_p(dev_weight or None), C.byref(info)),
+                    "dcreg_consensus_correspondences_device")
+        return {"records": _consensus_records(recs, info.n_returned), "info": _consensus_info_dict(info)}
 
     # ---- kept normals and the second engine (include/dcreg.h: dcreg_target_normals_keep .. dcreg_icp_run_normals)
     def keep_target_normals(self, params=None):

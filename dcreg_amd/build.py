@@ -32,6 +32,7 @@ SOURCES = [
     "device/voxel_icp.hip",
     "device/features.hip",
     "device/align.hip",
+    "device/consensus.hip",
     "host/solver.cpp",
     "host/align_host.cpp",
     "host/engine.cpp",

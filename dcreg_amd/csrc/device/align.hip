@@ -194,39 +194,11 @@ int align_run(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const
     I.n_pairs = n_pairs;
     if (info) *info = I;
     if (n_pairs == 0) return DCREG_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::AlignBufs &A = c->algn;
     const size_t np = (size_t)n_pairs;
-    if (A.flag.ensure(c, np + 1) || A.pos.ensure(c, np + 1) || A.P.ensure(c, kAlignPairFloats * np) || A.m_of_u.ensure(c, np) || A.cnt.ensure(c, 3))
-        return DCREG_E_NOMEM;
-    const float *da = a, *db = b;
-    const int32_t *dca = ca, *dcb = cb;
-    if (on_device) {
-        if (int rc = after_null_stream(c)) return rc;
-    } else {
-        const size_t wa = n_a > 0 ? (size_t)(n_a - 1) * (size_t)stride_a + 3 : 0, wb = n_b > 0 ? (size_t)(n_b - 1) * (size_t)stride_b + 3 : 0;
-        if (A.a.ensure(c, wa) || A.b.ensure(c, wb) || A.ca.ensure(c, np) || A.cb.ensure(c, np)) return DCREG_E_NOMEM;
-        if (wa) HIP_TRY(c, hipMemcpyAsync(A.a.data(), a, sizeof(float) * wa, hipMemcpyHostToDevice, c->stream));
-        if (wb) HIP_TRY(c, hipMemcpyAsync(A.b.data(), b, sizeof(float) * wb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(A.ca.data(), ca, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(A.cb.data(), cb, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
-        da = A.a.data(); db = A.b.data(); dca = A.ca.data(); dcb = A.cb.data();
-    }
     // ---- the used pairs
-    hipLaunchKernelGGL(k_align_valid, dim3(blocks(n_pairs + 1, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, db, n_b, stride_b, dca, dcb, n_pairs,
-                       A.flag.data());
-    {
-        size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
-        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
-    }
-    hipLaunchKernelGGL(k_align_gather, dim3(blocks(n_pairs, 256)), dim3(256), 0, c->stream, da, stride_a, db, stride_b, dca, dcb, n_pairs, A.flag.data(),
-                       A.pos.data(), A.P.data(), A.m_of_u.data());
-    HIP_TRY(c, hipGetLastError());
     uint32_t m_u = 0;
-    HIP_TRY(c, hipMemcpyAsync(&m_u, A.pos.data() + np, sizeof(m_u), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = align_used_pairs(c, a, n_a, stride_a, b, n_b, stride_b, ca, cb, n_pairs, on_device, &m_u)) return rc;
     I.n_used = (int64_t)m_u;
     if (info) *info = I;
     if (m_u < 3u) return align_no_record(c, mask, n_pairs, on_device);
@@ -286,6 +258,46 @@ int align_run(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const
 }
 
 }  // namespace
+
+int align_used_pairs(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, const int32_t *ca,
+                     const int32_t *cb, int64_t n_pairs, bool on_device, uint32_t *m_u_out) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    dcreg_ctx::AlignBufs &A = c->algn;
+    const size_t np = (size_t)n_pairs;
+    if (A.flag.ensure(c, np + 1) || A.pos.ensure(c, np + 1) || A.P.ensure(c, kAlignPairFloats * np) || A.m_of_u.ensure(c, np) || A.cnt.ensure(c, 3))
+        return DCREG_E_NOMEM;
+    const float *da = a, *db = b;
+    const int32_t *dca = ca, *dcb = cb;
+    if (on_device) {
+        if (int rc = after_null_stream(c)) return rc;
+    } else {
+        const size_t wa = n_a > 0 ? (size_t)(n_a - 1) * (size_t)stride_a + 3 : 0, wb = n_b > 0 ? (size_t)(n_b - 1) * (size_t)stride_b + 3 : 0;
+        if (A.a.ensure(c, wa) || A.b.ensure(c, wb) || A.ca.ensure(c, np) || A.cb.ensure(c, np)) return DCREG_E_NOMEM;
+        if (wa) HIP_TRY(c, hipMemcpyAsync(A.a.data(), a, sizeof(float) * wa, hipMemcpyHostToDevice, c->stream));
+        if (wb) HIP_TRY(c, hipMemcpyAsync(A.b.data(), b, sizeof(float) * wb, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(A.ca.data(), ca, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(A.cb.data(), cb, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
+        da = A.a.data(); db = A.b.data(); dca = A.ca.data(); dcb = A.cb.data();
+    }
+    // ---- the used pairs
+    hipLaunchKernelGGL(k_align_valid, dim3(blocks(n_pairs + 1, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, db, n_b, stride_b, dca, dcb, n_pairs,
+                       A.flag.data());
+    {
+        size_t tmp = 0;
+        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
+        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
+        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
+    }
+    hipLaunchKernelGGL(k_align_gather, dim3(blocks(n_pairs, 256)), dim3(256), 0, c->stream, da, stride_a, db, stride_b, dca, dcb, n_pairs, A.flag.data(),
+                       A.pos.data(), A.P.data(), A.m_of_u.data());
+    HIP_TRY(c, hipGetLastError());
+    uint32_t m_u = 0;
+    HIP_TRY(c, hipMemcpyAsync(&m_u, A.pos.data() + np, sizeof(m_u), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *m_u_out = m_u;
+    return DCREG_OK;
+}
+
 }  // namespace dcreg
 
 using namespace dcreg;

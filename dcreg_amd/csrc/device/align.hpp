@@ -109,4 +109,18 @@ struct AlignKey {
 void align_host_records(const float *P, const int32_t *m_of_u, int64_t m_u, int64_t n_pairs, const dcreg_align_params *prm, const AlignKey *keys,
                         int n_rec, dcreg_align_record *rec, uint8_t *mask);
 
+// host/align_host.cpp: the least-squares fit of step 7 over the n used pairs idx (in the order given: ascending u) - centroids, S_ab,
+// Horn's N, eight Jacobi sweeps, the quaternion, R and t.  The refinement calls it with the inliers, the consensus call with a set's members
+void align_host_fit(const float *P, const uint32_t *idx, size_t n, double R[9], double t[3]);
+
+// host/align_host.cpp, for the consensus call (device/consensus.hip).  One seed's set: its members as used-pair numbers in ascending u
+constexpr int kConsMaxSet = 64, kConsMaxSeeds = 1024;
+// the poses (R row-major, then t: 12 doubles) of the n sets whose member lists are mem[kConsMaxSet * set[i]] with n_mem[set[i]] entries
+void consensus_host_fit(const float *P, const uint32_t *mem, const uint32_t *n_mem, const uint32_t *set, int n, double *pose);
+// the records of the n_rec best sets: keys[k].h is the place i of the set among the scored ones (pose 12 i, rank set[i]); seed_u,
+// seed_w: the seeds' used pair and weight by rank.  mask as align_host_records'; members (may be null): [n_best x consensus_size], -1 padded
+void consensus_host_records(const float *P, const int32_t *m_of_u, int64_t m_u, int64_t n_pairs, const dcreg_consensus_params *prm, const AlignKey *keys,
+                            int n_rec, const double *pose, const uint32_t *set, const uint32_t *seed_u, const uint32_t *seed_w, const uint32_t *mem,
+                            const uint32_t *n_mem, dcreg_consensus_record *rec, uint8_t *mask, int32_t *members);
+
 }  // namespace dcreg

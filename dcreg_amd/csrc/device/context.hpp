@@ -727,6 +727,19 @@ struct dcreg_ctx {
     AlignBufs algn;
     int64_t opt_align_score_split = 0;                        // "align_score_split": used pairs per block column of k_align_score (0: from the sizes; tests)
 
+    // The consensus pose (consensus.hip: dcreg_consensus_correspondences*), behind the used pairs of AlignBufs.  The compatibility graph as
+    // a bit matrix, word-major (adj[word * M_u + u]: bits 64 word .. 64 word + 63 of row u), deg and w per used pair, the seeds' sort keys
+    // ((~w) << 32 | u) unsorted and sorted, per seed its row of second-order counts (uint16, M_u each), its members (64 used-pair numbers)
+    // and their number, the scored sets' poses (12 doubles) and keys {count, place, cost}, and the host form's degree / weight outputs.
+    struct ConsensusBufs {
+        DevBuf<unsigned long long> adj, key, key_sorted;
+        DevBuf<uint32_t> deg, w, mem, n_mem, out_deg, out_w;
+        DevBuf<uint16_t> s_row;
+        DevBuf<double> pose;
+        DevBuf<dcreg::AlignKey> score;
+    };
+    ConsensusBufs cons;
+
     void fail(const char *fmt, ...);
 };
 
@@ -859,6 +872,11 @@ inline void lin_out_of_row(const double *row, dcreg_lin_out &o) {
     o.n_eff = (int64_t)std::llround(row[29]); o.n_pt = (int64_t)std::llround(row[30]);
 }
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
+// align.hip: step 1 of the alignment rule for both correspondence calls - the host form's uploads (on_device: the stream waits for the
+// legacy default stream instead), k_align_valid, the scan and k_align_gather into c->algn.P / m_of_u (and, for the host form, the index
+// arrays in c->algn.ca / cb) - and the number of used pairs, read back behind a stream synchronisation.  n_pairs > 0
+int align_used_pairs(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, const int32_t *ca,
+                     const int32_t *cb, int64_t n_pairs, bool on_device, uint32_t *m_u);
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
 // deskew.hip: one call's motion compensation, checked and prepared on the host by deskew_prepare (every refusal of include/dcreg.h before
 // anything is queued).  upload_cloud given one packs the records with k_pack_deskew instead of k_pack (into its float4 buffer, or 3 floats

@@ -1050,6 +1050,9 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_align_params")) return sizeof(dcreg_align_params);
     if (!std::strcmp(name, "dcreg_align_record")) return sizeof(dcreg_align_record);
     if (!std::strcmp(name, "dcreg_align_info")) return sizeof(dcreg_align_info);
+    if (!std::strcmp(name, "dcreg_consensus_params")) return sizeof(dcreg_consensus_params);
+    if (!std::strcmp(name, "dcreg_consensus_record")) return sizeof(dcreg_consensus_record);
+    if (!std::strcmp(name, "dcreg_consensus_info")) return sizeof(dcreg_consensus_info);
     return 0;
 }
 

@@ -51,6 +51,7 @@
  *       ... over every point within a radius (PCL setRadiusSearch)               -> dcreg_fpfh_radius[_device], dcreg_target_fpfh_radius[_device]
  *       nearest and second-nearest rows in feature space, mutual flags           -> dcreg_feature_match[_device]
  *       the pose most point pairs agree on (seeded RANSAC), the best T as start poses -> dcreg_align_correspondences[_device]
+ *       ... at inlier shares of a per cent: a compatibility graph's consensus sets -> dcreg_consensus_correspondences[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -1883,6 +1884,87 @@ int dcreg_align_correspondences_device(dcreg_ctx *, const float *d_a_xyz, int64_
                                        int64_t stride_b, const int32_t *d_corr_a, const int32_t *d_corr_b, int64_t n_pairs,
                                        const dcreg_align_params *, dcreg_align_record *records_out, uint8_t *d_inlier_mask_out,
                                        dcreg_align_info *info);
+
+/* ---------------- Consensus pose from a compatibility graph ----------------
+ * The same stage as the call above, for inlier shares a three-pair sampler does not survive (an all-inlier draw has the probability of
+ * the share cubed): a rigid motion keeps lengths, so two right pairs (p_i, q_i), (p_j, q_j) have |p_i - p_j| ~ |q_i - q_j|, the right
+ * pairs form a clique in that compatibility graph, and second-order counts - the compatible neighbours two compatible pairs share -
+ * make the clique stand out (SC2-PCR, the graph stage of TEASER).  The same clouds and index arrays go in, records with 4x4 poses come
+ * out.  Arithmetic as above: double, every operation rounded once, a dot product is (x + y) + z, nothing contracted; every quantity of
+ * the graph is a bit or an integer.  The output is BITWISE the numpy reference of tests/consensus_ref.py, with no stated freedom.
+ *
+ * 1. Used pairs: step 1 of the rule above, unchanged - the same test, u = 0 .. M_u - 1 in ascending m, p_u and q_u widened to double.
+ *    With M_u < 3 the call returns DCREG_OK with nothing returned and an all-zero mask.
+ * 2. Compatibility.  For u != v: g = p_u - p_v, la = sqrt((g_x g_x + g_y g_y) + g_z g_z), lb likewise from q (the squares make both
+ *    symmetric bitwise).  C(u, v) = 1 when corr_a[m_u] != corr_a[m_v] and corr_b[m_u] != corr_b[m_v] and la >= min_length and
+ *    lb >= min_length and fabs(la - lb) <= compat_distance; C(u, u) = 0.  deg(u) = the number of ones in row u.
+ * 3. Second-order counts and weights.  S(u, v) = C(u, v) * |{x : C(u, x) and C(v, x)}|; w(u) = sum over v of S(u, v).  With
+ *    M_u <= 32768, w < 2^31.  Integers: no order is part of the rule.
+ * 4. Seeds and their sets.  The seeds are the first min(n_seeds, M_u) used pairs in the order (w descending, u ascending); a seed's
+ *    rank r is its place there.  For seed s: S_max = max over v of S(s, v); the candidates are the v with C(s, v) = 1, S(s, v) >= 1
+ *    and 2 * S(s, v) >= S_max; the members are s and the first min(consensus_size - 1, candidates) candidates in the order (S(s, v)
+ *    descending, v ascending).  A seed with fewer than three members is SKIPPED: counted, and no further seed is taken in its place.
+ * 5. Pose of a set: the fit of step 7 above - centroids, S_ab, Horn's N, eight Jacobi sweeps, quaternion, R, t - over the members in
+ *    ascending u, once.
+ * 6. Score, over ALL used pairs: step 5 above with d = inlier_distance - the integer count and the integer cost.
+ * 7. Rank: (count descending, cost ascending, r ascending) over the n_scored seeds not skipped; the first n_returned = min(n_best,
+ *    n_scored) are returned, best first, each refined refine_iterations times exactly as step 7 above refines a record; n_inliers,
+ *    rmse and record 0's inlier_mask_out as there.  The records behind them are zero.
+ * `count` and `cost` are the set's unrefined pose's (the ranking key); T, n_inliers and rmse the refined pose's.
+ *
+ * Optional outputs, each may be null (host pointers in the host form, device pointers in the device form):
+ *   members_out [n_best x consensus_size] int32: the correspondence numbers m of the members of each returned record in ascending u,
+ *               padded with -1 (rows behind the returned ones are all -1)
+ *   degree_out  [n_pairs] uint32: deg of every used pair, 0 at unused pairs
+ *   weight_out  [n_pairs] uint32: w likewise.  The weights are a product in their own right: a pair without a compatible neighbour
+ *               that shares one has w = 0, so a caller can keep the pairs with w > 0 and give those to dcreg_align_correspondences,
+ *               whose sampler then draws from a far higher inlier share.
+ * Steps 1 to 4 and 6 run on the device; the host fits the seeds' poses from their member lists (at most 1024 x 64 indices, OpenMP over
+ * the seeds), uploads 12 doubles per seed, ranks the at most 1024 scores and refines the returned records.  The graph is a bit matrix
+ * of M_u^2 / 8 bytes (128 MiB at the cap) and one uint16 row of counts per seed, kept as scratch of the context.  The call touches
+ * nothing else in the context and waits for the stream; repeated calls and calls on another context are bitwise equal.
+ * DCREG_E_INVALID, before anything is queued: what dcreg_align_correspondences lists for its context, records, clouds, index arrays,
+ * strides and counts; n_pairs > 32768; a compat_distance or inlier_distance that is not finite or not > 0; a min_length that is not
+ * finite or < 0; n_seeds outside 1 .. 1024; consensus_size outside 3 .. 64; n_best outside 1 .. 32; refine_iterations outside 0 .. 8.
+ * DCREG_E_STATE: a linearisation in flight. */
+typedef struct dcreg_consensus_params {
+    double compat_distance;    /* > 0, metres: two pairs are compatible when their lengths differ by no more */
+    double min_length;         /* >= 0, metres: pairs closer than this on either side say nothing about each other */
+    double inlier_distance;    /* d > 0, metres */
+    int n_seeds;               /* 1 .. 1024 */
+    int consensus_size;        /* 3 .. 64 members of a set, the seed among them */
+    int n_best;                /* 1 .. 32 records returned */
+    int refine_iterations;     /* 0 .. 8 */
+    double reserved_[2];
+} dcreg_consensus_params;
+typedef struct dcreg_consensus_record {   /* one per returned seed, best first */
+    double T[16];              /* row-major 4x4, bottom row 0 0 0 1: q ~ R p + t; feeds every T0 argument as it is */
+    int32_t seed;              /* the correspondence number m of the seed s */
+    int32_t seed_rank;         /* r */
+    int32_t weight;            /* w(s) */
+    int32_t n_members;
+    int32_t count;             /* inliers of the set's pose (the ranking key) */
+    uint64_t cost;             /* the set's pose's integer cost (ranking key) */
+    int32_t n_inliers;         /* inliers of T, after refinement */
+    int32_t refined;           /* refinement steps actually taken */
+    double rmse;              /* over the inliers of T */
+} dcreg_consensus_record;
+typedef struct dcreg_consensus_info {
+    int64_t n_pairs, n_used, n_edges, max_degree, n_seeds, n_skipped, n_scored, n_returned;
+    int64_t reserved_;
+} dcreg_consensus_info;
+#define DCREG_CONSENSUS_MAX_PAIRS 32768
+/* compat_distance = 0.5, min_length = 1.0, d = 0.5, n_seeds = 64, consensus_size = 16, n_best = 1, refine = 3 */
+int dcreg_default_consensus_params(dcreg_consensus_params *);
+int dcreg_consensus_correspondences(dcreg_ctx *, const float *a_xyz, int64_t n_a, int64_t stride_a, const float *b_xyz, int64_t n_b,
+                                    int64_t stride_b, const int32_t *corr_a, const int32_t *corr_b, int64_t n_pairs,
+                                    const dcreg_consensus_params *, dcreg_consensus_record *records_out, uint8_t *inlier_mask_out,
+                                    int32_t *members_out, uint32_t *degree_out, uint32_t *weight_out, dcreg_consensus_info *info);
+int dcreg_consensus_correspondences_device(dcreg_ctx *, const float *d_a_xyz, int64_t n_a, int64_t stride_a, const float *d_b_xyz,
+                                           int64_t n_b, int64_t stride_b, const int32_t *d_corr_a, const int32_t *d_corr_b, int64_t n_pairs,
+                                           const dcreg_consensus_params *, dcreg_consensus_record *records_out, uint8_t *d_inlier_mask_out,
+                                           int32_t *d_members_out, uint32_t *d_degree_out, uint32_t *d_weight_out,
+                                           dcreg_consensus_info *info);
 
 size_t dcreg_sizeof(const char *struct_name);
 const char *dcreg_version(void);
