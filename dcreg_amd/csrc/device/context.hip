@@ -86,6 +86,7 @@ static int build_grid_at(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d
     g.sx = sx;
     const int64_t n_cells = (int64_t)g.nx * sx * g.ny * g.nz;       // table entries
     g.n_pts = (uint32_t)n;
+    c->index_epoch += 1;           // d.sorted is about to be reallocated or rewritten
     if (c->d_keys.ensure(c, (size_t)n) || c->d_keys2.ensure(c, (size_t)n) || c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) ||
         d.cell_start.ensure(c, (size_t)n_cells + 1) || d.sorted.ensure(c, (size_t)n + kPtsPad))
         return DCREG_E_NOMEM;
@@ -240,6 +241,7 @@ static int build_row_words(dcreg_ctx *c, IndexSet &d) {
 static void swap_index(dcreg_ctx *c) {
     std::swap(c->map, c->roi_store);
     c->roi_active = !c->roi_active;
+    c->index_epoch += 1;
     drop_warm(c);                 // the states' positions are positions in the other index's order
     c->order_valid = false;
     c->last_pose_valid = false;
@@ -482,6 +484,7 @@ static void update_info(dcreg_map_update *info, int64_t offered, int64_t added, 
 
 // everything derived from the map as it was goes, as dcreg_set_target drops it
 static void map_changed(dcreg_ctx *c) {
+    c->index_epoch += 1;
     c->roi_built = false;
     drop_warm(c);
     c->nicp.kept = false;                              // (an update that follows them puts them back: normals.hip normals_follow_update)
@@ -628,6 +631,7 @@ static int map_merge(dcreg_ctx *c, uint32_t n_add, uint32_t *keys, uint32_t *val
     int rc = sort_pairs_u32(c, keys, keys2, vals, vals2, (size_t)n_add, bits);
     if (rc) return rc;
     // ---- from here on the map is rewritten
+    c->index_epoch += 1;
     uint32_t *scratch = c->d_scratch.data();
     HIP_TRY(c, hipMemcpyAsync(m.raw.data() + n_old, c->d_map_new.data(), sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(scratch + kMwOccupied, 0, sizeof(uint32_t), c->stream));

@@ -217,6 +217,10 @@ struct dcreg_ctx {
     };
     // target: the ACTIVE index, the one every kernel launch uses (the whole map, or its window: see roi_store below)
     IndexSet map;
+    // counts every event after which a pointer into some index's sorted points may show other points: a build of any index (context.hip
+    // build_grid_at: the map, its window, the outlier scratch index, the source's grid), a change of the map (map_merge, map_changed) and a
+    // change of the active index (swap_index).  The descriptor reports remember it beside their pointer (FeatureBufs::last_epoch)
+    uint64_t index_epoch = 0;
     double radius_hint = 0.0;
     int last_max_ring = 0;
     // ---- updates of the map in place (context.hip map_insert / map_crop: dcreg_target_insert*, dcreg_target_crop).  The new sorted points
@@ -702,6 +706,7 @@ struct dcreg_ctx {
         DevBuf<double> d1, d2;
         // dcreg_fpfh_debug_counts: the sorted points, their number and the input's size of the last descriptor call, and the export
         const float4 *last_q = nullptr; int64_t last_nq = 0, last_n = 0;
+        uint64_t last_epoch = 0;       // dcreg_ctx::index_epoch when last_q / rlast_q was taken: a report behind a later epoch is refused
         DevBuf<uint32_t> dbg;
         // the radius rule (dcreg_fpfh_radius*): per used point its record (q[33], m, has, 0) and its 33 counts, in the index's cell order;
         // what dcreg_fpfh_radius_debug_counts reports.  A call of either rule ends the other's report

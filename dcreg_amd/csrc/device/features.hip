@@ -617,7 +617,7 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[2] = {0, 0};
     F.last_q = nq > 0 ? g.pts : nullptr; F.last_nq = nq; F.last_n = n;      // (dcreg_fpfh_debug_counts)
-    F.rlast_n = 0;
+    F.rlast_n = 0; F.last_epoch = c->index_epoch;
     if (nq > 0) {
         const float4 *q = g.pts;
         float bound = 3.0e38f;
@@ -654,7 +654,7 @@ int fpfh_radius_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 4 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[4] = {0, 0, 0, 0};
     F.rlast_q = nq > 0 ? g.pts : nullptr; F.rlast_nq = nq; F.rlast_n = n;      // (dcreg_fpfh_radius_debug_counts)
-    F.last_n = 0;
+    F.last_n = 0; F.last_epoch = c->index_epoch;
     if (nq > 0) {
         const float4 *q = g.pts;
         const float R2 = (float)(p->radius * p->radius);
@@ -694,6 +694,7 @@ int fpfh_index(dcreg_ctx *c, float4 *pts, int64_t n, const float *nrm, int64_t n
 int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const float *normals, int64_t nstride, bool on_device,
                const dcreg_normal_params *np, const FpfhRule &rule, float *out, float *normals_out) {
     if (!c) return DCREG_E_INVALID;
+    rule.clear_info();                  // (a refused call leaves the info zero, whatever it held)
     if (int rc = refuse_in_flight(c)) return rc;
     if (int rc = fpfh_check(c, rule)) return rc;
     if (!normals && !np) { c->fail("no normals and no normal parameters: one of them is expected"); return DCREG_E_INVALID; }
@@ -702,7 +703,6 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
     if (n > (int64_t)INT32_MAX) { c->fail("too many points for one descriptor call (%lld)", (long long)n); return DCREG_E_INVALID; }
     if (n > 0 && !xyz) { c->fail("null point buffer"); return DCREG_E_INVALID; }
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
-    rule.clear_info();
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::OutlierBufs &B = c->outl;
@@ -739,6 +739,7 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
 // dcreg_target_fpfh*: the whole map's points through the map's own index and its kept normals
 int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int64_t capacity) {
     if (!c) return DCREG_E_INVALID;
+    rule.clear_info();                  // (as the cloud form: zero behind every refusal)
     if (int rc = refuse_in_flight(c)) return rc;
     if (int rc = fpfh_check(c, rule)) return rc;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
@@ -747,7 +748,6 @@ int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int
     const dcreg_ctx::IndexSet &wm = c->roi_active ? c->roi_store : c->map;      // the whole map's index, whichever is active
     const int64_t n = wm.n;
     if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
-    rule.clear_info();
     HIP_TRY(c, hipSetDevice(c->device));
     dcreg_ctx::FeatureBufs &F = c->feat;
     if (F.cnt.ensure(c, 3)) return DCREG_E_NOMEM;
@@ -768,6 +768,15 @@ int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int
     return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, 4, rule, out, on_device);
 }
 
+// The reports read the sorted points of the index their call searched (last_q / rlast_q: the outlier scratch index or the map's own).  An
+// index built since, an update of the map or a change of its active index (dcreg_ctx::index_epoch) leaves other points there, with input
+// indices the export was not sized for: refused on the host, before anything is queued
+int fpfh_report_stale(dcreg_ctx *c) {
+    if (c->feat.last_epoch == c->index_epoch) return DCREG_OK;
+    c->fail("the descriptor call's index has been rebuilt or its map changed since: the report is only valid directly behind that call");
+    return DCREG_E_STATE;
+}
+
 // dcreg_fpfh_debug_counts (include/dcreg_debug.h)
 int fpfh_debug_counts(dcreg_ctx *c, uint8_t *out, int64_t capacity) {
     if (!c) return DCREG_E_INVALID;
@@ -775,6 +784,7 @@ int fpfh_debug_counts(dcreg_ctx *c, uint8_t *out, int64_t capacity) {
     dcreg_ctx::FeatureBufs &F = c->feat;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (F.last_n <= 0) { c->fail("no descriptor call to report"); return DCREG_E_STATE; }
+    if (int rc = fpfh_report_stale(c)) return rc;
     if (capacity < F.last_n) { c->fail("the call had %lld points, the capacity is %lld", (long long)F.last_n, (long long)capacity); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t words = (size_t)kCountWords * (size_t)F.last_n;
@@ -795,6 +805,7 @@ int fpfh_radius_debug_counts(dcreg_ctx *c, uint32_t *out, int64_t capacity) {
     dcreg_ctx::FeatureBufs &F = c->feat;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (F.rlast_n <= 0) { c->fail("no radius descriptor call to report"); return DCREG_E_STATE; }
+    if (int rc = fpfh_report_stale(c)) return rc;
     if (capacity < F.rlast_n) { c->fail("the call had %lld points, the capacity is %lld", (long long)F.rlast_n, (long long)capacity); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t words = (size_t)(kDim + 2) * (size_t)F.rlast_n;

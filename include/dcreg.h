@@ -1690,7 +1690,7 @@ int dcreg_p2p_error(dcreg_ctx *, const double T[16], double error_threshold, dou
  * normal_params NULL, the refusals of dcreg_normals for normal_params when it is read, a capacity below the map's size.  DCREG_E_STATE:
  * a linearisation in flight; no target or no kept normals (the map form).  Device memory: the outlier filter's scratch for the cloud
  * and its index (the cloud form), 8 k bytes per point for the neighbour lists (position and d2), 48 bytes per point for the counts and
- * 132 for the output - kept as scratch of the context, as the outlier pass's, and reused by the next call. */
+ * 132 for the output - kept as scratch of the context, as the outlier pass's, and reused by the next call.  A refused call zeroes *info. */
 typedef struct dcreg_fpfh_params {
     int k;                 /* neighbours per point, the point itself among them (PCL setKSearch), 3 .. 32 */
     int reserved0_;

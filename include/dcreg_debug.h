@@ -368,14 +368,18 @@ int dcreg_debug_index_check(dcreg_ctx *, int64_t mismatches[5]);
 
 /* The SPFH records behind the last dcreg_fpfh* / dcreg_target_fpfh* call of this context (tests: where the device's atan2 puts a pair
  * at a bin edge of theta, the counts say which pair moved).  36 bytes per input point: the 33 counts, m, 1 when the point has an SPFH,
- * and a zero; all zero for an unused point.  Only directly behind that call: the records lie in scratch that the next call of the
- * descriptor, normal and outlier families reuses.  DCREG_E_STATE without such a call, DCREG_E_INVALID for a null buffer or a capacity
- * below the call's points. */
+ * and a zero; all zero for an unused point.  Only directly behind that call: the report reads the points of the index the call searched,
+ * which lie in scratch that the next call of the descriptor, normal and outlier families reuses, or in the map.  Once any index of the
+ * context has been built since (such a call on a cloud, a dcreg_set_target* / dcreg_set_source* form, a window built by a
+ * linearisation), the map has been updated (dcreg_target_insert*, _crop, _remove_*) or its active index has changed, the report is
+ * refused with DCREG_E_STATE before anything is queued.  DCREG_E_STATE also without such a call, DCREG_E_INVALID for a null buffer or a
+ * capacity below the call's points. */
 int dcreg_fpfh_debug_counts(dcreg_ctx *, uint8_t *counts_out, int64_t capacity_points);
 
 /* The same behind the last dcreg_fpfh_radius* / dcreg_target_fpfh_radius* call: 35 uint32 per input point - the 33 counts c_b, the m
  * that the info sums (max_neighbors + 1 for a crowded point, whose counts are 0), 1 when the point has an SPFH; all zero for an unused
- * point.  A call of either rule ends the other's report: DCREG_E_STATE then, and without any such call; DCREG_E_INVALID as above. */
+ * point.  A call of either rule ends the other's report: DCREG_E_STATE then, without any such call, and for a report whose index has
+ * been rebuilt or whose map has changed since, as above; DCREG_E_INVALID as above. */
 int dcreg_fpfh_radius_debug_counts(dcreg_ctx *, uint32_t *counts_out, int64_t capacity_points);
 
 /* internal: the host-only translation units above the device seam (engine.cpp) store their error text where dcreg_last_error finds it */

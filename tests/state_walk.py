@@ -8,7 +8,9 @@ whether a gate is pending.  The options hold the robust kernel, its scales, gicp
 read at every launch, and go into context B with the rest.  Every transition rule is one sentence of include/dcreg.h (cited as `h:LINE`) or of
 include/dcreg_debug.h (`d:LINE`).  Expected clouds come from the bitwise numpy references the suite already has (transform and crop_ref of
 test_gpu_map_update.py, voxel_ref, outliers_ref, visibility_ref, keyframes_ref); the deskew forms, specified to one ulp only, take theirs
-from the cloud form on a helper context (`Model.deskew`: h:417-418 promises that the two are bitwise equal).
+from the cloud form on a helper context (`Model.deskew`: h:417-418 promises that the two are bitwise equal).  The calls of the
+global-alignment chain (descriptors, matching, the sampler, the consensus graph) change no state: their whole ANSWER is compared, bitwise,
+with that of a context that has done nothing else (`alone`, `Model.fresh`), and the probe "desc" reads the map form of the descriptors.
 
 An OPERATION is a function op_NAME(m, c, **args): it reads its precondition from the model, derives the call's concrete arguments from
 the scene and the model, predicts the return code (0, or the refusal the header names), makes the call on the context c (None: the model
@@ -21,6 +23,8 @@ import re
 
 import numpy as np
 
+import align_scenes as als
+import consensus_scenes as cs
 import keyframes_ref as kr
 import normal_icp_scenes as S
 import outliers_ref as orf
@@ -191,6 +195,7 @@ class Model:
         self.follow_n = 0                         # dcreg_target_normals_follow_info().n_target
         self.reserved = 0
         self.vm = None                            # (leaf, epsilon, min_points) of the last accepted keep that kept a voxel
+        self.fresh, self.fresh_tag = None, ""     # makes a context that has done nothing yet (run_walk: the chain's answers are compared with its)
 
     # ---- the rules
     def new_target(self, xyz, radius):
@@ -706,6 +711,79 @@ def op_keyframe_submaps(m, c, spec=((0, 5),), leaf=0.3):
     return OK
 
 
+# ---- the global-alignment chain: descriptors, matching, the sampler and the consensus graph.  Scratch users too - they share the outlier
+# scratch and its index, the normal scratch, the sort's and each other's (c->feat, c->algn) - and each promises an answer that depends on
+# its inputs only and is bitwise the same on another context (h:1674-1675 + h:1686-1687, h:1742, h:1786-1790, h:1847-1848, h:1924-1925).
+# So the WHOLE answer is compared with that of a context that has done nothing else, obtained once per argument set.
+def frozen(x):
+    """an answer - nested dicts, lists, arrays and numbers - as comparable items, arrays and floats by their bits"""
+    if isinstance(x, dict):
+        return [(k, frozen(x[k])) for k in sorted(x)]
+    if isinstance(x, (list, tuple)):
+        return [frozen(v) for v in x]
+    return None if x is None else bits(np.asarray(x))
+
+
+def alone(m, c, tag, parts, fn):
+    got = call(m, c, OK, lambda: fn(c))
+    if c is None or m.fresh is None:
+        return OK
+
+    def first():
+        b = m.fresh()
+        try:
+            return frozen(fn(b))
+        finally:
+            b.close()
+    if frozen(got) != memo("alone %s %s" % (tag, m.fresh_tag), first, *parts):
+        raise AssertionError("%s%r does not answer as a context that has done nothing else" % (tag, tuple(parts)))
+    return OK
+
+
+CHAIN_NORMALS = (8, 0.0)
+
+
+@op("scratch")
+def op_fpfh(m, c, n=1000, k=16, radius=0.0):
+    """the normals are estimated in the call (h:1680-1682) and returned with the descriptors"""
+    return alone(m, c, "fpfh", (n, k, radius), lambda x: x.fpfh(cloud(("frame", n)), None, np_params(CHAIN_NORMALS),
+                                                                 api.fpfh_params(k=k, search_radius=radius), want_normals=True))
+
+
+@op("scratch")
+def op_fpfh_radius(m, c, n=1000, radius=0.9, cap=65535):
+    return alone(m, c, "fpfh_radius", (n, radius, cap), lambda x: x.fpfh_radius(cloud(("frame", n)), None, np_params(CHAIN_NORMALS),
+                                                                                  api.fpfh_radius_params(radius, cap), want_normals=True))
+
+
+@functools.lru_cache(maxsize=None)
+def feature_rows(n, seed):
+    """n seeded rows of 33 floats in 0 .. 100, every 29th with a NaN (h:1780: neither a query nor a candidate)"""
+    a = np.random.default_rng(5200 + seed + n).uniform(0.0, 100.0, (n, 33)).astype(np.float32)
+    a[::29, n % 33] = np.nan
+    a.setflags(write=False)
+    return a
+
+
+@op("scratch")
+def op_feature_match(m, c, n_a=257, n_b=1000):
+    return alone(m, c, "feature_match", (n_a, n_b), lambda x: x.feature_match(feature_rows(n_a, 1), feature_rows(n_b, 2)))
+
+
+@op("scratch")
+def op_align_correspondences(m, c, pairs=400, seed=1):
+    a, b, ca, cb = als.synthetic(pairs, 0.3, 0.02, 60 + pairs)[:4]
+    p = dict(n_hypotheses=2000, seed=seed, inlier_distance=0.1, edge_similarity=0.9, n_best=2, refine_iterations=3)
+    return alone(m, c, "align_correspondences", (pairs, seed), lambda x: x.align_correspondences(a, b, ca, cb, api.align_params(**p)))
+
+
+@op("scratch")
+def op_consensus_correspondences(m, c, pairs=400):
+    a, b, ca, cb = cs.scene(pairs, 0.1, 70 + pairs)[:4]
+    return alone(m, c, "consensus_correspondences", (pairs,),
+                 lambda x: x.consensus_correspondences(a, b, ca, cb, api.consensus_params(**cs.SETTINGS), want_members=True, want_weights=True))
+
+
 # ---- history makers: the engines and the batched calls.  They leave warm states, window and scratch behind, and no result depends on it.
 def bad_pose():
     T = np.array(poses()[0])
@@ -955,8 +1033,8 @@ def op_gate_end(m, c, open=0, pose=2):
 
 STATE_CLASSES = ("target", "source", "update", "member", "option")
 PROBE_KINDS = ("map", "flags", "lin", "nlin", "glin", "knn", "p2p", "normals", "frames", "frames_n", "frames_g", "batch", "icp", "places", "submaps",
-               "voxels", "vlin", "icp_v", "frames_v", "trials_v", "vbatch", "pairs")
-LAUNCHING = tuple(k for k in PROBE_KINDS if k not in ("map", "flags", "normals", "voxels"))      # the probes that launch an engine's kernels
+               "voxels", "vlin", "icp_v", "frames_v", "trials_v", "vbatch", "pairs", "desc")
+LAUNCHING = tuple(k for k in PROBE_KINDS if k not in ("map", "flags", "normals", "voxels", "desc"))      # the probes that launch an engine's kernels
 
 
 def apply(m, c, step):
@@ -1025,6 +1103,12 @@ def _draw_args(rng, name, m):
         "register_pairs_normals": ({}, dict(bad=1)),
         "register_pairs_gicp": ({}, dict(bad=1)),
         "set_window": (dict(on=r((1, 1, 0))), None),
+        # the chain: two sizes each, so that a large call is followed by a small one and the other way round on the same scratch
+        "fpfh": (r((dict(n=1000, k=16), dict(n=257, k=9, radius=0.7), dict(n=63, k=32))), None),
+        "fpfh_radius": (r((dict(n=1000, radius=0.9), dict(n=257, radius=1.2, cap=30))), None),
+        "feature_match": (r((dict(n_a=257, n_b=1000), dict(n_a=1000, n_b=63))), None),
+        "align_correspondences": (dict(pairs=r((400, 150)), seed=i(1, 2)), None),
+        "consensus_correspondences": (dict(pairs=r((400, 150))), None),
         "visibility_filter": (dict(spec=spec), None),
         "keyframe_submaps": (dict(spec=spec, leaf=r((None, 0.3))), None),
         "linearize": (dict(pose=i(0, 5)), dict(bad=1)),
@@ -1045,7 +1129,9 @@ def _draw_args(rng, name, m):
 
 
 WEIGHTS = {"target": 1, "source": 1, "update": 2, "member": 1, "option": 3, "scratch": 1, "history": 1, "gate": 2}
-NAME_WEIGHTS = {"set_option": 8}            # (OPTION_DECK has twice the values it had when "option" got its 3)
+# (OPTION_DECK has twice the values it had when "option" got its 3; the sampler and the consensus stage share c->algn, and only a walk that
+# holds both, the sampler first, can tell whether the second reads what the first left: twice each, so that either order occurs)
+NAME_WEIGHTS = {"set_option": 8, "align_correspondences": 2, "consensus_correspondences": 2}
 # every value of every option but its default, and normals_follow, the robust kernel and the voxel mode off again (a context warmed under a
 # kernel answers under none): one fixed shuffle, entered where the seed says
 OPTION_DECK = ([(k, v) for k in sorted(TOGGLES) for v in TOGGLES[k] if v != DEFAULTS[k]] +
@@ -1419,6 +1505,23 @@ def probe(kind, c, m, pose, fresh=False):
         return ([("pairs." + k, v) for k, v in records(c.register_pairs(src, tgt, Ts, "Ours", cfg_of(), slots=2))] +
                 [("pairs_n." + k, v) for k, v in records(c.register_pairs_normals(src, tgt, Ts, "Ours", cfg_of(), p5, slots=2))] +
                 [("pairs_g." + k, v) for k, v in records(c.register_pairs_gicp(src, tgt, Ts, "Ours", cfg_of(), p5, p5, slots=2))]), []
+    if kind == "desc":
+        # the map form of the descriptors (h:1683-1687): from the map's own index and the kept normals, whatever updates made of either
+        kp, rp = api.fpfh_params(k=9, search_radius=0.7), api.fpfh_radius_params(0.9, 30)
+        got = []
+
+        def run():
+            got.extend([c.target_fpfh(kp), c.target_fpfh_radius(rp)])
+            return [("target_fpfh", frozen(got[0])), ("target_fpfh_radius", frozen(got[1]))]
+        out = refusal(run)
+        mod = [("desc refusal", out[0] == ("refused", E_STATE), m.map is None or not m.tn)]       # h:1690-1691 no target or no kept normals
+        if got and m.tn[0] == "set":                                 # given normals: the cloud form of (map, normals) is the same call (h:1683-1685)
+            given = np.ascontiguousarray(m.tn[1][:, :3])
+            f, _, info = c.fpfh(m.map, given, params=kp)
+            mod.append(("cloud form fpfh", frozen((f, info)), frozen(got[0])))
+            f, _, info = c.fpfh_radius(m.map, given, params=rp)
+            mod.append(("cloud form fpfh_radius", frozen((f, info)), frozen(got[1])))
+        return out, mod
     raise KeyError(kind)
 
 
@@ -1466,7 +1569,7 @@ def check_points(ops, every):
 
 def probes_at(seed, step, last):
     """the map and the flags (host reads and one index check) at every check, three more probes drawn by the seed (two of thirteen kinds
-    once, three of twenty now: the same share), all of them at the last step"""
+    once, three of twenty-one now: the same share), all of them at the last step"""
     if last:
         return [(k, (step + j) % 6) for j, k in enumerate(PROBE_KINDS)]
     rng = np.random.default_rng([seed, step])
@@ -1487,6 +1590,8 @@ def first_difference(a, b):
 def run_walk(make, seed, ops, every, deskew=host_deskew, on_check=None, make_fresh=None):
     """A takes the walk; at every check point a fresh B is built from the model and both answer the probes"""
     a, m = make(), Model(deskew)
+    m.fresh = make_fresh or make
+    m.fresh_tag = getattr(m.fresh, "__name__", "context")
     checks = set(check_points(ops, every))
     try:
         for s, step in enumerate(ops):
@@ -1529,7 +1634,9 @@ FAULTS = ("set_source_voxel keeps the source normals", "crop without normals_fol
           "frames_load keeps the frame normals", "a crop with normals_follow on keeps the kept voxels",
           "keep_target_voxels behind a live window summarises the window's points",
           "register_frames_voxels in mode 0 keeps the previous frames' normals",
-          "robust_kernel is latched by set_source instead of being read at the launch")
+          "robust_kernel is latched by set_source instead of being read at the launch",
+          "an insert with normals_follow on leaves the map's descriptors those of the old map",
+          "consensus_correspondences reads the used pairs the sampler left behind")
 
 
 class FakeError(api.DcregError):
@@ -1550,6 +1657,8 @@ class FakeContext:
         self.vm = None                          # ((leaf, epsilon, min_points), the points the keep summarised)
         self.window_active = False              # the window is the active index: the last launch was a single-pose one of the first engine
         self.latched_kernel = 0                 # (FAULTS[8])
+        self.desc_map = None                    # (FAULTS[9]) the map the descriptors still see
+        self.left_used = None                   # (FAULTS[10]) the used pairs of the last align_correspondences
 
     def close(self):
         pass
@@ -1597,6 +1706,7 @@ class FakeContext:
     # the map
     def _new_target(self, xyz):
         self.map, self.tn, self.follow_n, self.window_map, self.vm, self.window_active = xyz, None, 0, None, None, False
+        self.desc_map = None
 
     def set_target(self, xyz, radius):
         self._busy()
@@ -1622,11 +1732,13 @@ class FakeContext:
             raise FakeError(E_INVALID)
         self._new_target(self._finite(kr.submaps_ref(self.kf, [members], leaf)[0][0]))
 
-    def _update(self, xyz, keep_window=False, keep_normals=False, keep_voxels=False):
+    def _update(self, xyz, keep_window=False, keep_normals=False, keep_voxels=False, stale_desc=False):
         if len(xyz) == 0:
             raise FakeError(E_INVALID)
         if len(xyz) == len(self.map) and np.array_equal(xyz.view(np.uint32), self.map.view(np.uint32)):
             return
+        follows = self.tn and self.tn[0] == "keep" and self.opts["normals_follow"]
+        self.desc_map = (self.map if self.desc_map is None else self.desc_map) if stale_desc and follows else None
         if not keep_window:
             self.window_map = None
         if not keep_voxels:
@@ -1641,12 +1753,13 @@ class FakeContext:
         self._busy()
         self._need(self.map)
         q = transform(self._finite(xyz), T)
-        self._update(np.concatenate([self.map, thinned(self.map, q, min_spacing)]))
+        self._update(np.concatenate([self.map, thinned(self.map, q, min_spacing)]), stale_desc=self.fault == FAULTS[9])
 
     def insert_source(self, T, min_spacing=0.0):
         self._busy()
         self._need(self.map, self.src)
-        self._update(np.concatenate([self.map, thinned(self.map, transform(self.src, T), min_spacing)]), keep_window=self.fault == FAULTS[2])
+        self._update(np.concatenate([self.map, thinned(self.map, transform(self.src, T), min_spacing)]), keep_window=self.fault == FAULTS[2],
+                     stale_desc=self.fault == FAULTS[9])
 
     def crop(self, lo, hi):
         self._busy()
@@ -1853,6 +1966,58 @@ class FakeContext:
         self._busy()
 
     normals = normals_clouds = outlier_filter = visibility_filter = place_descriptors = voxel_downsample
+
+    # the chain: an answer is named by its inputs (h:1674-1675, h:1786-1790, h:1847-1848, h:1924-1925)
+    @staticmethod
+    def _normals_id(xyz, normals, np_):
+        return digest("keep", (np_.k, np_.search_radius), xyz) if normals is None else digest("set", np.ascontiguousarray(np.asarray(normals)[:, :3]))
+
+    @staticmethod
+    def _desc(rule, xyz, normals_id, p):
+        p = (p.k, p.search_radius) if rule == "k" else (p.radius, p.max_neighbors)
+        return np.frombuffer(digest(rule, np.ascontiguousarray(xyz), normals_id, p).encode(), np.uint8)
+
+    def fpfh(self, xyz, normals=None, normal_params=None, params=None, want_normals=False):
+        self._busy()
+        nid = self._normals_id(xyz, normals, normal_params)
+        return self._desc("k", xyz, nid, params), (np.frombuffer(nid.encode(), np.uint8) if want_normals else None), {}
+
+    def fpfh_radius(self, xyz, normals=None, normal_params=None, params=None, want_normals=False):
+        self._busy()
+        nid = self._normals_id(xyz, normals, normal_params)
+        return self._desc("radius", xyz, nid, params), (np.frombuffer(nid.encode(), np.uint8) if want_normals else None), {}
+
+    def _target_desc(self, rule, p):
+        """the map form: the map and its kept normals - a kept set is named by the map it was computed from, a given one by itself"""
+        self._busy()
+        self._need(self.map, self.tn or None)
+        seen = self.map if self.desc_map is None else self.desc_map
+        nid = digest("keep", self.tn[1], seen) if self.tn[0] == "keep" else digest("set", np.ascontiguousarray(self.tn[1][:, :3]))
+        return self._desc(rule, seen, nid, p), {}
+
+    def target_fpfh(self, p):
+        return self._target_desc("k", p)
+
+    def target_fpfh_radius(self, p):
+        return self._target_desc("radius", p)
+
+    def feature_match(self, a, b, want_second=True, want_mutual=True):
+        self._busy()
+        return {"idx": np.frombuffer(digest(a, b).encode(), np.uint8)}
+
+    @staticmethod
+    def _block(p):
+        return [(f[0], getattr(p, f[0])) for f in p._fields_ if not f[0].startswith("reserved")]
+
+    def align_correspondences(self, a, b, corr_a, corr_b, params=None, want_mask=True):
+        self._busy()
+        self.left_used = digest(a, b, corr_a, corr_b)
+        return {"records": np.frombuffer(digest(a, b, corr_a, corr_b, self._block(params)).encode(), np.uint8)}
+
+    def consensus_correspondences(self, a, b, corr_a, corr_b, params=None, want_mask=True, want_members=False, want_weights=False):
+        self._busy()
+        left = self.left_used if self.fault == FAULTS[10] else None
+        return {"records": np.frombuffer(digest(a, b, corr_a, corr_b, self._block(params), left).encode(), np.uint8)}
 
     # answers
     def target_points(self):
@@ -2063,6 +2228,7 @@ def _vis_dict(p):
 
 
 # ---- the committed walks (tests/test_state_walk_model.py holds the conditions they were chosen to meet)
-SEEDS = (5, 6, 12, 13, 17, 18, 21, 22, 23, 27, 2, 7, 9, 33, 42)      # (the first ten are as old as the module: their test ids stay)
+# (the first ten are as old as the module, the next five came with the fourth engine, the last four with the alignment chain: the ids stay)
+SEEDS = (5, 6, 12, 13, 17, 18, 21, 22, 23, 27, 2, 7, 9, 33, 42, 173, 80, 59, 83)
 N_STEPS = 72
 EVERY = 1            # A is compared after every EVERY-th state-changing step

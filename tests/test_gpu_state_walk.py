@@ -4,6 +4,10 @@ at every check point a fresh context B is built from the model alone - options (
 mode among them), set_target of the model's map, set_source, the normals, the kept voxels, the frames, the places, the keyframes - and both
 answer the same probes, those of the voxel-distribution engine and of the three pair forms included.  A answers warm from its history, B
 cold; include/dcreg.h promises that no bit differs.  The kept voxels and the voxel linearisation's dump are bitwise tests/voxels_ref.py's.
+The walks also call the global-alignment chain - FPFH over k neighbours and over a radius, feature matching, the three-pair sampler and the
+consensus graph - between the other families whose scratch these calls share; each answer is compared bitwise with the answer of a context
+that has done nothing else, and the probe "desc" compares the map form of the descriptors of A and B (and, under given normals, with the
+cloud form of the model's map).
 
 A walk runs once and nothing is retried.  If a walk ends in anything but an AssertionError (a HIP error, a return code the model did not
 expect from the library's side) the remaining walks are skipped: the cause is to be found by reading code, not by running again."""
