@@ -313,6 +313,16 @@ void analyzeFinish(const double H[36], dcreg_analysis &res, int owed) {
 void solveDegenerateSystem(const double H[36], const double g[6], int handling, const dcreg_config &cfg,
                            dcreg_analysis &an, double x[6]) {
     Vec<6> gv; std::memcpy(gv.data(), g, sizeof(double) * 6);
+    // a non-finite entry of H or g gives a non-finite step with every handling (the loop's abort, icp_test_runner.cpp:1942-1950, reads
+    // it): left to themselves PCG stops at once on !(pAp > 0) and the truncated SVD retains no direction, and both return a finite 0 -
+    // which the loop would take for convergence
+    bool finite = true;
+    for (int i = 0; i < 36; ++i) finite &= std::isfinite(H[i]);
+    for (int i = 0; i < 6; ++i) finite &= std::isfinite(g[i]);
+    if (!finite) {
+        for (int i = 0; i < 6; ++i) x[i] = std::numeric_limits<double>::quiet_NaN();
+        return;
+    }
     const Vec<6> xv = solve(toMat6(H), gv, handling, cfg, an);
     std::memcpy(x, xv.data(), sizeof(double) * 6);
 }

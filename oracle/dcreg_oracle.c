@@ -736,6 +736,12 @@ void orc_pcg(const double A[36], const double b[6], const double P[36], int max_
 
 void orc_solve(const double H[36], const double g[6], int handling, const orc_config *cfg,
                orc_analysis *an, double x[6]) {
+    /* a non-finite entry of H or g: a non-finite step with every handling, so that the loop's abort (:1942-1950) sees it
+     * (PCG and the truncated SVD would return a finite 0 otherwise) */
+    int fin = 1;
+    for (int i = 0; i < 36; ++i) if (!isfinite(H[i])) fin = 0;
+    for (int i = 0; i < 6; ++i) if (!isfinite(g[i])) fin = 0;
+    if (!fin) { for (int i = 0; i < 6; ++i) x[i] = NAN; return; }
     switch (handling) {
     case ORC_HAND_STANDARD_REGULARIZATION: { /* dcreg.hpp:177-184 */
         double Hr[36];
