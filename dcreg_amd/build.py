@@ -17,6 +17,7 @@ RUNNER = os.path.join(BINDIR, "icp_test_runner")
 
 SOURCES = [
     "device/context.hip",
+    "device/scratch.hip",
     "device/metrics.hip",
     "device/kdtree.hip",
     "device/exchange.hip",

@@ -19,7 +19,7 @@
 #include <vector>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/rocprim.hpp>
+#include <rocprim/device/device_merge_sort.hpp>
 
 #include "align.hpp"
 #include "context.hpp"
@@ -34,8 +34,6 @@ constexpr int64_t kMaxHypotheses = (int64_t)1 << 24;
 constexpr int kMaxBest = 32, kMaxRefine = 8;
 constexpr int kHypBlock = 256, kHypGrid = 4096;          // k_align_hypotheses: 2^20 hypotheses per stride of the grid
 constexpr int kScoreBlock = 256, kScoreTile = 256;       // survivors per block, pairs per LDS tile (12 KiB of doubles)
-
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 DCREG_DEVFN bool finitef(float x) { return fabsf(x) <= 3.4028235e38f; }
 
@@ -282,12 +280,7 @@ int align_used_pairs(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a
     // ---- the used pairs
     hipLaunchKernelGGL(k_align_valid, dim3(blocks(n_pairs + 1, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, db, n_b, stride_b, dca, dcb, n_pairs,
                        A.flag.data());
-    {
-        size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
-        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, A.flag.data(), A.pos.data(), 0u, np + 1, rocprim::plus<uint32_t>(), c->stream));
-    }
+    if (int rc = scan_u32(c, A.flag.data(), A.pos.data(), np + 1, false)) return rc;
     hipLaunchKernelGGL(k_align_gather, dim3(blocks(n_pairs, 256)), dim3(256), 0, c->stream, da, stride_a, db, stride_b, dca, dcb, n_pairs, A.flag.data(),
                        A.pos.data(), A.P.data(), A.m_of_u.data());
     HIP_TRY(c, hipGetLastError());

@@ -42,8 +42,6 @@ constexpr int kRowsPerBlock = kBlock / kWave;            // k_cons_weights: a wa
 constexpr int kMaxWords = (int)(kMaxPairs / 64);         // 512 words in a row at the cap
 constexpr int kScoreTile = 256;                          // k_cons_score: pairs per LDS tile (12 KiB of doubles), as k_align_score
 
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 // Block (x, y): rows [256 x, 256 x + 256) against the columns of words [4 y, 4 y + 4)
 static __global__ __launch_bounds__(kBlock) void k_cons_adjacency(const float *__restrict__ P, const int32_t *__restrict__ m_of_u,
                                                                   const int32_t *__restrict__ ca, const int32_t *__restrict__ cb, uint32_t m_u,

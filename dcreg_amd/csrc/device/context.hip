@@ -13,7 +13,6 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "../../../include/dcreg_debug.h"
 #include "context.hpp"
@@ -23,7 +22,6 @@ namespace dcreg {
 
 constexpr double kCountScale = 67108864.0;      // 2^26 (search.hpp LinArgs::count_scale)
 constexpr size_t kSearchCountBytes = 64 * kCounterStride * sizeof(uint32_t);     // 64 counters, one per 128-byte line
-static inline unsigned blocks_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 static void drop_warm(dcreg_ctx *c);
 
 // ------------------------------------------------------------------------------------------ index build
@@ -61,7 +59,7 @@ static void host_bounds(const float *xyz, int64_t n, int64_t stride, double mn[3
 static int device_bounds(dcreg_ctx *c, const float4 *pts, int64_t n, double mn[3], double mx[3], DeskewRun *dsk = nullptr) {
     uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), init, sizeof(init), hipMemcpyHostToDevice, c->stream));
-    const unsigned nb = std::min<unsigned>(blocks_for(n, 256), 256);      // grid-stride: one block per CU is plenty
+    const unsigned nb = std::min<unsigned>(blocks(n, 256), 256);      // grid-stride: one block per CU is plenty
     hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(256), 0, c->stream, pts, n, c->d_scratch.data());
     uint32_t out[6];
     HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch.data(), sizeof(out), hipMemcpyDeviceToHost, c->stream));
@@ -90,15 +88,15 @@ static int build_grid_at(dcreg_ctx *c, const float4 *raw, int64_t n, IndexSet &d
     if (c->d_keys.ensure(c, (size_t)n) || c->d_keys2.ensure(c, (size_t)n) || c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) ||
         d.cell_start.ensure(c, (size_t)n_cells + 1) || d.sorted.ensure(c, (size_t)n + kPtsPad))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, n, g, c->d_keys.data(), c->d_vals.data());
+    hipLaunchKernelGGL(k_cell_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, raw, n, g, c->d_keys.data(), c->d_vals.data());
     int bits = 1;
     while (((int64_t)1 << bits) < n_cells && bits < 32) ++bits;
     int rc = sort_pairs_u32(c, c->d_keys.data(), c->d_keys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bits);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d.sorted.data());
+    hipLaunchKernelGGL(k_gather4, dim3(blocks(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d.sorted.data());
     HIP_TRY(c, hipMemsetAsync(d.sorted.data() + n, 0, kPtsPad * sizeof(float4), c->stream));   // tail padding
     HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_cells + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_cells, d.cell_start.data(),
+    hipLaunchKernelGGL(k_cell_start, dim3(blocks(n_cells + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_cells, d.cell_start.data(),
                        c->d_scratch.data());
     HIP_TRY(c, hipMemcpyAsync(occupied, c->d_scratch.data(), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -198,18 +196,18 @@ int build_gap_field(dcreg_ctx *c, IndexSet &d, double radius_hint) {
     while (rings < 12 && (double)rings * g.h < (radius_hint > 0.0 ? radius_hint : 4.0 * g.h)) ++rings;
     if (rings < 2) return DCREG_OK;                           // one ring covers the radius: nothing to skip
     if (d.gap.ensure(c, (size_t)n_cells) || d.owner.ensure(c, (size_t)n_cells)) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_gap_init, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), n_cells, g.sx, d.gap.data(), d.owner.data());
+    hipLaunchKernelGGL(k_gap_init, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), n_cells, g.sx, d.gap.data(), d.owner.data());
     for (int r = 1; r <= rings; ++r)
-        hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.gap.data(), d.owner.data(), g.nx, g.ny, g.nz, r);
+        hipLaunchKernelGGL(k_gap_dilate, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, d.gap.data(), d.owner.data(), g.nx, g.ny, g.nz, r);
     if (c->opt_far_bound) {      // the probe's owners: nearest DENSE cell (kernels.hpp k_gap_init_dense); scratch of this block only
         DevBuf<uint8_t> gap2;
         DevBuf<uint32_t> own2;
         if (gap2.alloc((size_t)n_cells) == hipSuccess && own2.alloc((size_t)n_cells) == hipSuccess) {
-            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, n_cells, g.sx, 6u,
+            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, n_cells, g.sx, 6u,
                                gap2.data(), own2.data());
             for (int r = 1; r <= rings; ++r)
-                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap2.data(), own2.data(), g.nx, g.ny, g.nz, r);
-            hipLaunchKernelGGL(k_owner_merge, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, d.owner.data(), own2.data(), n_cells);
+                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, gap2.data(), own2.data(), g.nx, g.ny, g.nz, r);
+            hipLaunchKernelGGL(k_owner_merge, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, d.owner.data(), own2.data(), n_cells);
         } else {
             (void)hipGetLastError();     // (no memory for the scratch: the plain owners serve)
         }
@@ -229,7 +227,7 @@ static int build_row_words(dcreg_ctx *c, IndexSet &d) {
     g.nxb = (g.nx + 15) >> 4; g.nyw = (g.ny + 31) >> 5;
     const int64_t n_words = (int64_t)g.nz * g.nxb * g.nyw;
     if (d.ymask.ensure(c, (size_t)n_words)) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_ymask, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw,
+    hipLaunchKernelGGL(k_ymask, dim3(blocks(n_words, 256)), dim3(256), 0, c->stream, d.cell_start.data(), g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw,
                        d.ymask.data());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -324,11 +322,8 @@ int roi_ensure(dcreg_ctx *c, const double *R, const double *t, double search_rad
         const int n_rows = (int)n_rows64, nxs = g.nx * g.sx, x0s = c0[0] * g.sx, x1s = c1[0] * g.sx;
         if (c->d_vals.ensure(c, (size_t)n_rows) || c->d_vals2.ensure(c, (size_t)n_rows)) return DCREG_E_NOMEM;
         uint32_t *vals = c->d_vals.data(), *vals2 = c->d_vals2.data();
-        hipLaunchKernelGGL(k_roi_rows, dim3(blocks_for(n_rows, 256)), dim3(256), 0, c->stream, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], n_rows, vals);
-        size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, vals, vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
-        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, vals, vals2, 0u, (size_t)n_rows, rocprim::plus<uint32_t>(), c->stream));
+        hipLaunchKernelGGL(k_roi_rows, dim3(blocks(n_rows, 256)), dim3(256), 0, c->stream, g.cell_start, nxs, g.ny, x0s, x1s, c0[1], ny_box, c0[2], n_rows, vals);
+        if (int rc = scan_u32(c, vals, vals2, (size_t)n_rows, false)) return rc;
         uint32_t last[2] = {0u, 0u};
         HIP_TRY(c, hipMemcpyAsync(&last[0], vals + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(&last[1], vals2 + (n_rows - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -420,7 +415,7 @@ int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
     }
     if (dsk) return deskew_queue(c, src, n, stride, *dsk, dsk->out3 ? nullptr : raw.data());     // (deskew.hip: k_pack_deskew packs)
-    hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw.data());
+    hipLaunchKernelGGL(k_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw.data());
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
 }
@@ -528,7 +523,7 @@ static void fields_local(dcreg_ctx *c, const MapBox &S) {
     if (g.ymask) {
         const int xb0 = S.x0 >> 4, xb1 = (S.x1 + 15) >> 4, yw0 = S.y0 >> 5, yw1 = (S.y1 + 31) >> 5;
         const int64_t nw = (int64_t)(xb1 - xb0) * (yw1 - yw0) * (S.z1 - S.z0);
-        hipLaunchKernelGGL(k_ymask_box, dim3(blocks_for(nw, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, g.nxb, g.nyw,
+        hipLaunchKernelGGL(k_ymask_box, dim3(blocks(nw, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, g.nxb, g.nyw,
                            xb0, xb1 - xb0, yw0, yw1 - yw0, S.z0, S.z1 - S.z0, c->map.ymask.data());
     }
     if (!g.gap) return;
@@ -537,21 +532,21 @@ static void fields_local(dcreg_ctx *c, const MapBox &S) {
     const int64_t ne = box_cells(E), nb = box_cells(B);
     uint8_t *gap_p = c->d_fgap.data(), *gap_d = gap_p + ne;
     uint32_t *own_p = c->d_fown.data(), *own_d = own_p + ne;
-    hipLaunchKernelGGL(k_gap_init_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 0, 0u, gap_p, own_p);
+    hipLaunchKernelGGL(k_gap_init_box, dim3(blocks(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 0, 0u, gap_p, own_p);
     for (int r = 1; r <= rings; ++r)
-        hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.nx, g.ny, E, r);
+        hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks(ne, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.nx, g.ny, E, r);
     if (g.owner) {
-        hipLaunchKernelGGL(k_gap_init_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 1, 6u, gap_d, own_d);
+        hipLaunchKernelGGL(k_gap_init_box, dim3(blocks(ne, 256)), dim3(256), 0, c->stream, g.cell_start, g.nx, g.ny, g.sx, E, 1, 6u, gap_d, own_d);
         for (int r = 1; r <= rings; ++r)
-            hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks_for(ne, 256)), dim3(256), 0, c->stream, gap_d, own_d, g.nx, g.ny, E, r);
+            hipLaunchKernelGGL(k_gap_dilate_box, dim3(blocks(ne, 256)), dim3(256), 0, c->stream, gap_d, own_d, g.nx, g.ny, E, r);
     }
-    hipLaunchKernelGGL(k_gap_store_box, dim3(blocks_for(nb, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.owner ? own_d : (const uint32_t *)nullptr,
+    hipLaunchKernelGGL(k_gap_store_box, dim3(blocks(nb, 256)), dim3(256), 0, c->stream, gap_p, own_p, g.owner ? own_d : (const uint32_t *)nullptr,
                        g.nx, g.ny, E, B, c->map.gap.data(), c->map.owner.data());
 }
 
 static int count_occupied(dcreg_ctx *c, const GridDev &g, int64_t n_cells, uint32_t *out) {
     HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_count_occupied, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.cell_start, n_cells, g.sx, c->d_scratch.data());
+    hipLaunchKernelGGL(k_count_occupied, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, g.cell_start, n_cells, g.sx, c->d_scratch.data());
     HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch.data(), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
@@ -635,13 +630,13 @@ static int map_merge(dcreg_ctx *c, uint32_t n_add, uint32_t *keys, uint32_t *val
     uint32_t *scratch = c->d_scratch.data();
     HIP_TRY(c, hipMemcpyAsync(m.raw.data() + n_old, c->d_map_new.data(), sizeof(float4) * n_add, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(scratch + kMwOccupied, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_map_bpos, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, keys2, n_add, g.cell_start, g.sx, b, scratch);
-    hipLaunchKernelGGL(k_map_merge_old, dim3(blocks_for(n_old, 256)), dim3(256), 0, c->stream, m.sorted.data(), (uint32_t)n_old, b, n_add, alt.data());
-    hipLaunchKernelGGL(k_map_merge_new, dim3(blocks_for(n_add, 256)), dim3(256), 0, c->stream, c->d_map_new.data(), vals2, b, n_add, alt.data());
+    hipLaunchKernelGGL(k_map_bpos, dim3(blocks(n_add, 256)), dim3(256), 0, c->stream, keys2, n_add, g.cell_start, g.sx, b, scratch);
+    hipLaunchKernelGGL(k_map_merge_old, dim3(blocks(n_old, 256)), dim3(256), 0, c->stream, m.sorted.data(), (uint32_t)n_old, b, n_add, alt.data());
+    hipLaunchKernelGGL(k_map_merge_new, dim3(blocks(n_add, 256)), dim3(256), 0, c->stream, c->d_map_new.data(), vals2, b, n_add, alt.data());
     HIP_TRY(c, hipMemsetAsync(alt.data() + n_new, 0, kPtsPad * sizeof(float4), c->stream));
     const int64_t first = (int64_t)w[kMwKeyMin] + 1;       // entries up to the smallest new key keep their value
     if (first <= n_entries)
-        hipLaunchKernelGGL(k_map_table_insert, dim3(blocks_for(n_entries - first + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), first, n_entries,
+        hipLaunchKernelGGL(k_map_table_insert, dim3(blocks(n_entries - first + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), first, n_entries,
                            keys2, n_add);
     m.sorted.swap(alt);
     m.n = n_new;
@@ -686,7 +681,7 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
     PoseArg P{};
     for (int k = 0; k < 9; ++k) P.R[k] = R[k];
     for (int k = 0; k < 3; ++k) P.t[k] = t[k];
-    hipLaunchKernelGGL(k_map_transform, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, in, m, P, c->d_map_q.data(), c->d_scratch.data());
+    hipLaunchKernelGGL(k_map_transform, dim3(blocks(m, 256)), dim3(256), 0, c->stream, in, m, P, c->d_map_q.data(), c->d_scratch.data());
     const GridDev wg = whole_map(c).grid;
     const float *d2 = nullptr;
     float spacing_sq = 0.f;
@@ -697,14 +692,9 @@ static int map_insert(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride,
         d2 = c->d_nn_d2.data();
         spacing_sq = (float)(min_spacing * min_spacing);
     }
-    hipLaunchKernelGGL(k_map_keep, dim3(blocks_for((int64_t)m1, 256)), dim3(256), 0, c->stream, m, d2, spacing_sq, flag);
-    {
-        size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
-        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag, pos, 0u, m1, rocprim::plus<uint32_t>(), c->stream));
-    }
-    hipLaunchKernelGGL(k_map_append, dim3(blocks_for(m, 256)), dim3(256), 0, c->stream, c->d_map_q.data(), m, flag, pos, (uint32_t)n_old, wg, c->d_map_new.data(),
+    hipLaunchKernelGGL(k_map_keep, dim3(blocks((int64_t)m1, 256)), dim3(256), 0, c->stream, m, d2, spacing_sq, flag);
+    if (int rc = scan_u32(c, flag, pos, m1, false)) return rc;
+    hipLaunchKernelGGL(k_map_append, dim3(blocks(m, 256)), dim3(256), 0, c->stream, c->d_map_q.data(), m, flag, pos, (uint32_t)n_old, wg, c->d_map_new.data(),
                        keys, vals, c->d_scratch.data());
     uint32_t n_add = 0;
     HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch.data(), sizeof(w), hipMemcpyDeviceToHost, c->stream));
@@ -780,8 +770,8 @@ static int map_crop(dcreg_ctx *c, const double *lo, const double *hi, dcreg_map_
     uint32_t *flag_r = c->d_upd.data(), *flag_s = flag_r + 2 * n1;
     CropBox bx;
     for (int a = 0; a < 3; ++a) { bx.lo[a] = lo[a]; bx.hi[a] = hi[a]; }
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, bx, flag_r);
-    hipLaunchKernelGGL(k_crop_flags, dim3(blocks_for((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, bx, flag_s);
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, bx, flag_r);
+    hipLaunchKernelGGL(k_crop_flags, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, bx, flag_s);
     return map_keep_flagged(c, "the crop box keeps no point of the map", info);
 }
 
@@ -796,14 +786,9 @@ static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_updat
     uint32_t w[kMwWords];
     words_init(w);
     HIP_TRY(c, hipMemcpyAsync(c->d_scratch.data(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-    {
-        size_t tmp = 0;
-        HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
-        if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag_r, pos_r, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
-        HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, flag_s, pos_s, 0u, n1, rocprim::plus<uint32_t>(), c->stream));
-    }
-    hipLaunchKernelGGL(k_crop_scan_box, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, flag_s, wm.grid, c->d_scratch.data());
+    if (int rc = scan_u32(c, flag_r, pos_r, n1, false)) return rc;
+    if (int rc = scan_u32(c, flag_s, pos_s, n1, false)) return rc;
+    hipLaunchKernelGGL(k_crop_scan_box, dim3(blocks(n, 256)), dim3(256), 0, c->stream, wm.sorted.data(), n, flag_s, wm.grid, c->d_scratch.data());
     uint32_t kept = 0;
     HIP_TRY(c, hipMemcpyAsync(w, c->d_scratch.data(), sizeof(w), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&kept, pos_r + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -824,7 +809,7 @@ static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_updat
     const MapBox S = change_box(w, g);
     if (alt.raw.ensure(c, (size_t)kept) || (!rederive && (alt.sorted.ensure(c, (size_t)kept + kPtsPad) || fields_reserve(c, S))))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_crop_raw, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, m.raw.data(), n, flag_r, pos_r, alt.raw.data());
+    hipLaunchKernelGGL(k_crop_raw, dim3(blocks(n, 256)), dim3(256), 0, c->stream, m.raw.data(), n, flag_r, pos_r, alt.raw.data());
     // the survivors' kept normals go the same way, beside the current ones (short of memory they will not follow: dropped as without the option)
     const bool follow = normals_follow_wanted(c) && normals_follow_carry(c, n, flag_r, pos_r, (int64_t)kept);
     const bool vfollow = voxels_follow_wanted(c);
@@ -845,9 +830,9 @@ static int map_keep_flagged(dcreg_ctx *c, const char *none_kept, dcreg_map_updat
             return rc;
         }
     } else {
-        hipLaunchKernelGGL(k_crop_sorted, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, m.sorted.data(), n, flag_s, pos_s, pos_r, alt.sorted.data());
+        hipLaunchKernelGGL(k_crop_sorted, dim3(blocks(n, 256)), dim3(256), 0, c->stream, m.sorted.data(), n, flag_s, pos_s, pos_r, alt.sorted.data());
         HIP_TRY(c, hipMemsetAsync(alt.sorted.data() + kept, 0, kPtsPad * sizeof(float4), c->stream));
-        hipLaunchKernelGGL(k_crop_table, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), n_entries, pos_s);
+        hipLaunchKernelGGL(k_crop_table, dim3(blocks(n_entries + 1, 256)), dim3(256), 0, c->stream, m.cell_start.data(), n_entries, pos_s);
         m.raw.swap(alt.raw);
         m.sorted.swap(alt.sorted);
         m.n = kept;
@@ -887,7 +872,7 @@ static int map_remove_outliers(dcreg_ctx *c, const dcreg_outlier_params *p, dcre
     if (c->d_upd.ensure(c, 4 * n1)) return DCREG_E_NOMEM;
     uint32_t *flag_r = c->d_upd.data(), *flag_s = flag_r + 2 * n1;
     HIP_TRY(c, hipMemcpyAsync(flag_r, c->outl.keep.data(), sizeof(uint32_t) * n1, hipMemcpyDeviceToDevice, c->stream));
-    rc = outlier_sorted_flags(c, wm.sorted.data(), n, flag_r, flag_s);
+    rc = flags_to_sorted(c, wm.sorted.data(), n, flag_r, flag_s);
     if (rc) return rc;
     return map_keep_flagged(c, "the filter would remove every point of the map", nullptr);
 }
@@ -917,7 +902,7 @@ static int map_remove_dynamic(dcreg_ctx *c, int64_t n_members, const int64_t *id
     if (r.n_out == 0) { c->fail("the votes would remove every point of the map"); return DCREG_E_INVALID; }
     visibility_info(info, r);
     if (r.n_out == n) return DCREG_OK;               // nothing to remove: nothing changes
-    rc = outlier_sorted_flags(c, wm.sorted.data(), n, flag_r, flag_s);
+    rc = flags_to_sorted(c, wm.sorted.data(), n, flag_r, flag_s);
     if (rc) return rc;
     return map_keep_flagged(c, "the votes would remove every point of the map", nullptr);
 }
@@ -946,33 +931,33 @@ static int index_check(dcreg_ctx *c, int64_t mm[5]) {
     uint8_t *gap = gap_b.data(), *gap2 = gap2_b.data();
     unsigned long long *cnt = cnt_b.data();
     HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 5, c->stream));
-    hipLaunchKernelGGL(k_cell_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, g, c->d_keys.data(), c->d_vals.data());
+    hipLaunchKernelGGL(k_cell_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), n, g, c->d_keys.data(), c->d_vals.data());
     int bits = 1;
     while (((int64_t)1 << bits) < n_entries && bits < 32) ++bits;
     int rc = sort_pairs_u32(c, c->d_keys.data(), c->d_keys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, bits);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), c->d_vals2.data(), n, pts);
+    hipLaunchKernelGGL(k_gather4, dim3(blocks(n, 256)), dim3(256), 0, c->stream, wm.raw.data(), c->d_vals2.data(), n, pts);
     HIP_TRY(c, hipMemsetAsync(pts + n, 0, kPtsPad * sizeof(float4), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_scratch.data(), 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_cell_start, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_entries, tab, c->d_scratch.data());
-    hipLaunchKernelGGL(k_count_diff<float4>, dim3(blocks_for(n + kPtsPad, 256)), dim3(256), 0, c->stream, (const float4 *)g.pts, (const float4 *)pts, n + kPtsPad, cnt);
-    hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_entries + 1, 256)), dim3(256), 0, c->stream, g.cell_start, (const uint32_t *)tab, n_entries + 1, cnt + 1);
+    hipLaunchKernelGGL(k_cell_start, dim3(blocks(n_entries + 1, 256)), dim3(256), 0, c->stream, c->d_keys2.data(), n, n_entries, tab, c->d_scratch.data());
+    hipLaunchKernelGGL(k_count_diff<float4>, dim3(blocks(n + kPtsPad, 256)), dim3(256), 0, c->stream, (const float4 *)g.pts, (const float4 *)pts, n + kPtsPad, cnt);
+    hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks(n_entries + 1, 256)), dim3(256), 0, c->stream, g.cell_start, (const uint32_t *)tab, n_entries + 1, cnt + 1);
     if (g.ymask) {
-        hipLaunchKernelGGL(k_ymask, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, tab, g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw, ym);
-        hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_words, 256)), dim3(256), 0, c->stream, g.ymask, (const uint32_t *)ym, n_words, cnt + 2);
+        hipLaunchKernelGGL(k_ymask, dim3(blocks(n_words, 256)), dim3(256), 0, c->stream, tab, g.nx, g.ny, g.nz, g.sx, g.nxb, g.nyw, ym);
+        hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks(n_words, 256)), dim3(256), 0, c->stream, g.ymask, (const uint32_t *)ym, n_words, cnt + 2);
     }
     if (g.gap) {
-        hipLaunchKernelGGL(k_gap_init, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, tab, n_cells, g.sx, gap, own);
+        hipLaunchKernelGGL(k_gap_init, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, tab, n_cells, g.sx, gap, own);
         for (int r = 1; r <= g.gap_cap; ++r)
-            hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap, own, g.nx, g.ny, g.nz, r);
+            hipLaunchKernelGGL(k_gap_dilate, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, gap, own, g.nx, g.ny, g.nz, r);
         if (g.owner) {
-            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, tab, g.nx, n_cells, g.sx, 6u, gap2, own2);
+            hipLaunchKernelGGL(k_gap_init_dense, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, tab, g.nx, n_cells, g.sx, 6u, gap2, own2);
             for (int r = 1; r <= g.gap_cap; ++r)
-                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, gap2, own2, g.nx, g.ny, g.nz, r);
-            hipLaunchKernelGGL(k_owner_merge, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, own, own2, n_cells);
-            hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.owner, (const uint32_t *)own, n_cells, cnt + 4);
+                hipLaunchKernelGGL(k_gap_dilate, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, gap2, own2, g.nx, g.ny, g.nz, r);
+            hipLaunchKernelGGL(k_owner_merge, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, own, own2, n_cells);
+            hipLaunchKernelGGL(k_count_diff<uint32_t>, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, g.owner, (const uint32_t *)own, n_cells, cnt + 4);
         }
-        hipLaunchKernelGGL(k_count_diff<uint8_t>, dim3(blocks_for(n_cells, 256)), dim3(256), 0, c->stream, g.gap, (const uint8_t *)gap, n_cells, cnt + 3);
+        hipLaunchKernelGGL(k_count_diff<uint8_t>, dim3(blocks(n_cells, 256)), dim3(256), 0, c->stream, g.gap, (const uint8_t *)gap, n_cells, cnt + 3);
     }
     unsigned long long h[5] = {0, 0, 0, 0, 0};
     const hipError_t e0 = hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream);
@@ -992,7 +977,7 @@ static int target_get(const dcreg_ctx *cc, float *out, int64_t capacity) {
     if (!out || capacity < wm.n) { c->fail("the output holds %lld points, the map %lld", (long long)capacity, (long long)wm.n); return DCREG_E_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->d_stage.ensure(c, (size_t)(3 * wm.n))) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_unpack3, dim3(blocks_for(wm.n, 256)), dim3(256), 0, c->stream, wm.raw.data(), wm.n, c->d_stage.data());
+    hipLaunchKernelGGL(k_unpack3, dim3(blocks(wm.n, 256)), dim3(256), 0, c->stream, wm.raw.data(), wm.n, c->d_stage.data());
     HIP_TRY(c, hipMemcpyAsync(out, c->d_stage.data(), sizeof(float) * (size_t)(3 * wm.n), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -1055,10 +1040,10 @@ static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const doub
         // the curve is resolved as far as the cloud can tell cells apart (curve_frame)
         // (round 6: ONE workgroup ordering a frame of <= 8192 points in LDS - keys, bitonic sort, gather, a single launch - was built and
         //  measured: 35 us of host time instead of 39, and 120 us of DEVICE time in front of the first linearisation instead of 15; removed)
-        hipLaunchKernelGGL(k_curve_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), n, mn[0], mn[1], mn[2], inv_q, c->opt_curve_x_scale, c->d_mkeys.data(), c->d_vals.data());
+        hipLaunchKernelGGL(k_curve_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), n, mn[0], mn[1], mn[2], inv_q, c->opt_curve_x_scale, c->d_mkeys.data(), c->d_vals.data());
         rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 63 - 3 * levels);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gather4, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), c->d_vals2.data(), n, c->d_src.data());
+        hipLaunchKernelGGL(k_gather4, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src_raw.data(), c->d_vals2.data(), n, c->d_src.data());
     }
     // A small frame from a host buffer went through the context's pinned block (upload_cloud): the caller's buffer is consumed, whatever
     // kind of memory it is, and nothing has to be waited for - the first linearisation queues behind the sort, and a device fault surfaces
@@ -1067,7 +1052,7 @@ static int source_commit(dcreg_ctx *c, int64_t n, const double mn[3], const doub
     HIP_TRY(c, hipGetLastError());
     c->n_src = n;
     {   // dispatch groups of the single-pose launches (kernels.hpp k_group_cost): multiples of 16 query blocks, at most kMaxGroups of them
-        const uint32_t nb = blocks_for(n, kLinBlock);
+        const uint32_t nb = blocks(n, kLinBlock);
         const uint32_t gq = 16u;                  // one XCD's run of query blocks (kXcdChunk)
         c->group_blocks = gq * std::max<uint32_t>(1u, (nb + gq * kMaxGroups - 1) / (gq * kMaxGroups));
         c->n_groups = std::min<uint32_t>(nb / c->group_blocks, (uint32_t)kMaxGroups);
@@ -1139,16 +1124,16 @@ static int frames_load(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int n_frames, cons
         HIP_TRY(c, hipMemcpyAsync(fs.d_off.data(), off, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(fs.d_dst.data(), dst.data(), sizeof(uint32_t) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(fs.d_box.data(), box.data(), sizeof(FrameBox) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, fs.raw.data());
+        hipLaunchKernelGGL(k_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, fs.raw.data());
         const uint32_t *order = nullptr;
         if (fbits + max_bits > 0) {
-            hipLaunchKernelGGL(k_frame_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), n, fs.d_off.data(), n_frames, fs.d_box.data(), fbits,
+            hipLaunchKernelGGL(k_frame_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), n, fs.d_off.data(), n_frames, fs.d_box.data(), fbits,
                                c->opt_curve_x_scale, c->d_mkeys.data(), c->d_vals.data());
             const int rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 63 - fbits - max_bits);
             if (rc) return rc;
             order = c->d_vals2.data();
         }
-        hipLaunchKernelGGL(k_frame_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), order, n, fs.d_off.data(), n_frames, fs.d_dst.data(), fs.src.data());
+        hipLaunchKernelGGL(k_frame_gather, dim3(blocks(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), order, n, fs.d_off.data(), n_frames, fs.d_dst.data(), fs.src.data());
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -1237,20 +1222,20 @@ static int pairs_pass(dcreg_ctx *c, dcreg_ctx::PairSet &ps, const float4 *raw, c
     int64_t *d_po = ps.d_off.data(), *d_to = d_po + (n_j + 1), *d_yo = d_to + (n_j + 1);
     HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), offs.data(), sizeof(int64_t) * offs.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(ps.d_cells.data(), cells.data(), sizeof(PairCells) * (size_t)n_j, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, n, d_po, n_j, ps.d_cells.data(), cbits, c->d_mkeys.data(), c->d_vals.data());
+    hipLaunchKernelGGL(k_pairs_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, raw, n, d_po, n_j, ps.d_cells.data(), cbits, c->d_mkeys.data(), c->d_vals.data());
     int rc = sort_pairs_u64(c, c->d_mkeys.data(), c->d_mkeys2.data(), c->d_vals.data(), c->d_vals2.data(), (size_t)n, 0, cbits + jbits);
     if (rc) return rc;
     if (occ) {
         HIP_TRY(c, hipMemsetAsync(ps.d_words.data(), 0, sizeof(uint32_t) * (size_t)n_j, c->stream));
-        hipLaunchKernelGGL(k_pairs_occupancy, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), n, cbits, ps.d_words.data());
+        hipLaunchKernelGGL(k_pairs_occupancy, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), n, cbits, ps.d_words.data());
         occ->assign((size_t)n_j, 0u);
         HIP_TRY(c, hipMemcpyAsync(occ->data(), ps.d_words.data(), sizeof(uint32_t) * (size_t)n_j, hipMemcpyDeviceToHost, c->stream));
     } else {
-        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d_po, n_j, ps.d_cells.data(), ps.sorted.data());
+        hipLaunchKernelGGL(k_pairs_gather, dim3(blocks(n, 256)), dim3(256), 0, c->stream, raw, c->d_vals2.data(), n, d_po, n_j, ps.d_cells.data(), ps.sorted.data());
         hipLaunchKernelGGL(k_pairs_pad, dim3((unsigned)n_j), dim3(64), 0, c->stream, d_po, ps.d_cells.data(), ps.sorted.data());
-        hipLaunchKernelGGL(k_pairs_table, dim3(blocks_for(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), d_po, d_to, n_j, cbits, ps.table.data());
+        hipLaunchKernelGGL(k_pairs_table, dim3(blocks(to[n_j], 256)), dim3(256), 0, c->stream, c->d_mkeys2.data(), d_po, d_to, n_j, cbits, ps.table.data());
         if (yo[n_j] > 0)
-            hipLaunchKernelGGL(k_pairs_ymask, dim3(blocks_for(yo[n_j], 256)), dim3(256), 0, c->stream, ps.table.data(), d_to, d_yo, n_j, ps.d_cells.data(), ps.ymask.data());
+            hipLaunchKernelGGL(k_pairs_ymask, dim3(blocks(yo[n_j], 256)), dim3(256), 0, c->stream, ps.table.data(), d_to, d_yo, n_j, ps.d_cells.data(), ps.ymask.data());
         tab_first->assign(to, to + n_j);
         yw_first->assign(yo, yo + n_j);
     }
@@ -1398,7 +1383,7 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
         HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), off, sizeof(int64_t) * (size_t)(n_t + 1), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemsetAsync(ps.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
         HIP_TRY(c, hipMemsetAsync(ps.d_words.data() + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
-        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, ps.d_off.data(), n_t, ps.raw.data(), ps.d_words.data());
+        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, ps.d_off.data(), n_t, ps.raw.data(), ps.d_words.data());
         HIP_TRY(c, hipMemcpyAsync(words.data(), ps.d_words.data(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
@@ -1566,7 +1551,7 @@ static int estimate_dispatch_order(dcreg_ctx *c, const double *R9, const double 
     for (int k = 0; k < 9; ++k) P.R[k] = R9[k];
     for (int k = 0; k < 3; ++k) P.t[k] = t3[k];
     const uint32_t ng = c->n_groups;
-    const uint32_t lead = (blocks_for(c->n_src, kLinBlock) - ng * c->group_blocks) * (uint32_t)kLinBlock;      // points in front of the first group
+    const uint32_t lead = (blocks(c->n_src, kLinBlock) - ng * c->group_blocks) * (uint32_t)kLinBlock;      // points in front of the first group
     hipLaunchKernelGGL(k_group_cost, dim3(ng), dim3(256), 0, c->stream, c->d_src.data() + lead, (uint32_t)c->n_src - lead, c->map.grid, P, c->group_blocks * (uint32_t)kLinBlock,
                        max_ring, c->d_group_est.data());
     float est[kMaxGroups];
@@ -1676,14 +1661,14 @@ static int lin_check(dcreg_ctx *c, LinLaunch &L) {
 // heavy groups first: single-pose launches of at least two groups, once the order has been estimated (a gated launch does not know its
 // pose yet: it uses the order there is).  (A launch whose blocks are all resident at once - 4 per CU - has no order to speak of.)
 static bool order_wanted(const dcreg_ctx *c, const LinLaunch &L) {
-    return c->opt_dispatch_order && L.own() && c->n_groups >= 2 && blocks_for(L.n, kLinBlock) > 4u * (uint32_t)c->n_cus &&
+    return c->opt_dispatch_order && L.own() && c->n_groups >= 2 && blocks(L.n, kLinBlock) > 4u * (uint32_t)c->n_cus &&
            c->hint_misalign > 0.5 * c->map.grid.h;
 }
 
 // Plan: how a checked launch is carried out.  fresh: the ctx's own state holds nothing yet (single-pose kinds)
 static LinPlan lin_plan(const dcreg_ctx *c, const LinLaunch &L, bool fresh) {
     LinPlan P;
-    P.kind = L.kind; P.n_poses = L.n_poses; P.nbx = blocks_for(L.n, kLinBlock);
+    P.kind = L.kind; P.n_poses = L.n_poses; P.nbx = blocks(L.n, kLinBlock);
     // one pose: the kernels finish the reduction themselves (chunk rows -> pinned memory); many poses: k_finalize
     P.n_chunks = (P.nbx + kChunk - 1) / kChunk;
     // ... and so do batches whose poses are one chunk each (the Monte-Carlo batches: 30 blocks per pose): the last block of a pose sums
@@ -1863,7 +1848,7 @@ static int lin_reserve(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P)
         L.a.adv_counts = c->d_adv_counts.data();
     }
     if (P.pass == LinPass::team && c->opt_team_stamps) {   // timing probe (dcreg_debug.h dcreg_team_pass_stamps): eight clock words per block of the pass
-        const uint32_t n_tiles = blocks_for(L.n, kTeamTile);
+        const uint32_t n_tiles = blocks(L.n, kTeamTile);
         if (c->d_team_stamps.ensure(c, (size_t)8 * (n_tiles + 1))) return DCREG_E_NOMEM;
         HIP_TRY(c, hipMemsetAsync(c->d_team_stamps.data(), 0, sizeof(unsigned long long) * 8 * (n_tiles + 1), c->stream));
         c->team_stamps_n = n_tiles;
@@ -1954,12 +1939,12 @@ static int lin_queue(dcreg_ctx *c, LinSlot &S, LinLaunch &L, const LinPlan &P) {
     if (int rc = record(S.ev0)) return rc;         // after the gate: the events bracket the linearisation, not the wait for the pose
     if (P.pass == LinPass::advance) {          // (pass_rows: the launch's only linearisation kernel - rows, tickets and chunk rows are its own)
         const auto pass = P.pass_rows ? k_advance<FAST, true> : k_advance<FAST, false>;
-        hipLaunchKernelGGL(pass, dim3(blocks_for(L.n, kAdvTile)), dim3(kLinBlock), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, L.d_poses, L.a,
+        hipLaunchKernelGGL(pass, dim3(blocks(L.n, kAdvTile)), dim3(kLinBlock), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, L.d_poses, L.a,
                            P.pass_rows ? nullptr : c->d_adv_counts.data(), abort_flag, S.d_partials.data(), P.nbx, fin);
     }
     if (team) {      // with the gate inside, the teams are the gated kernel
         const auto pass = P.gate_inside ? k_advance_team<FAST, true> : k_advance_team<FAST>;
-        hipLaunchKernelGGL(pass, dim3(blocks_for(L.n, kTeamTile)), dim3(kWave), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, P.gate_inside ? nullptr : L.d_poses,
+        hipLaunchKernelGGL(pass, dim3(blocks(L.n, kTeamTile)), dim3(kWave), 0, c->stream, c->d_src.data(), n, c->map.grid, L.one, P.gate_inside ? nullptr : L.d_poses,
                            L.a, c->d_adv_counts.data(), P.gate_inside ? nullptr : abort_flag, c->opt_team_stamps ? c->d_team_stamps.data() : nullptr, gt);
     }
     if (P.pass != LinPass::none) {
@@ -2253,9 +2238,8 @@ int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, 
         const double r2 = max_radius * max_radius;
         float rf = (float)r2; if ((double)rf < r2) rf = std::nextafterf(rf, INFINITY);
         bound = std::nextafterf(rf, INFINITY);
-        int kk = 1;
-        while (kk < 100000) { const double s = (double)kk * grid.h * (1.0 - 1e-9); if (s * s * (1.0 - 1e-6) >= (double)bound) break; ++kk; }
-        max_ring = kk;
+        max_ring = rings_for_bound(grid, bound);
+        if (max_ring < 0) max_ring = 100000;      // (the rule ran out: the walk still stops there, it does not sweep)
     } else {
         bound = 3.0e38f;
         max_ring = -1;   // unbounded: the kernel sweeps as many rings as the grid needs
@@ -2264,14 +2248,14 @@ int launch_knn(dcreg_ctx *c, const GridDev &grid, const float4 *d_q, int64_t n, 
     if (pose) P = *pose;
     if (sweep) {       // the linearisation's way of covering what lies beyond the 27-cell block, in the plain kernel (k = 5, bounded)
         if (k != 5 || max_ring < 0 || !grid.ymask) { c->fail("the row sweep needs k = 5, a radius and the target grid"); return DCREG_E_INVALID; }
-        hipLaunchKernelGGL((k_knn<5, true>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
+        hipLaunchKernelGGL((k_knn<5, true>), dim3(blocks(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
         HIP_TRY(c, hipGetLastError());
         return DCREG_OK;
     }
     if (k == 1)
-        hipLaunchKernelGGL(k_knn<1>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
+        hipLaunchKernelGGL(k_knn<1>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
     else
-        hipLaunchKernelGGL(k_knn<5>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
+        hipLaunchKernelGGL(k_knn<5>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, c->stream, d_q, (uint32_t)n, grid, bound, max_ring, P, pose ? 1 : 0, d_idx, d_d2);
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
 }

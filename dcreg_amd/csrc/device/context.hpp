@@ -139,6 +139,16 @@ __device__ __forceinline__ uint32_t seg_of(const int64_t *__restrict__ off, int 
     }
     return (uint32_t)lo;
 }
+// blocks of bs threads that cover n items
+inline unsigned blocks(int64_t n, int64_t bs) { return (unsigned)((n + bs - 1) / bs); }
+// a packed point / three coordinates are finite: the rule of every pass over a caller's cloud (at most FLT_MAX in magnitude).  NOT
+// kernels.hpp's finite3 of the map-insert path, whose bound is 3.4e38f: the two differ for values in (3.4e38, FLT_MAX]
+__device__ __forceinline__ bool finite_xyz(float x, float y, float z) {
+    return fabsf(x) <= 3.4028235e38f && fabsf(y) <= 3.4028235e38f && fabsf(z) <= 3.4028235e38f;
+}
+__device__ __forceinline__ bool finite_point(const float4 p) {
+    return fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
+}
 }  // namespace dcreg
 
 namespace dcreg {
@@ -218,7 +228,7 @@ struct dcreg_ctx {
     // target: the ACTIVE index, the one every kernel launch uses (the whole map, or its window: see roi_store below)
     IndexSet map;
     // counts every event after which a pointer into some index's sorted points may show other points: a build of any index (context.hip
-    // build_grid_at: the map, its window, the outlier scratch index, the source's grid), a change of the map (map_merge, map_changed) and a
+    // build_grid_at: the map, its window, the cloud scratch index, the source's grid), a change of the map (map_merge, map_changed) and a
     // change of the active index (swap_index).  The descriptor reports remember it beside their pointer (FeatureBufs::last_epoch)
     uint64_t index_epoch = 0;
     double radius_hint = 0.0;
@@ -389,19 +399,29 @@ struct dcreg_ctx {
         DevBuf<int32_t> sel_shift;
     };
     PlaceBufs places;
-    // outlier removal (outliers.hip: dcreg_outlier_filter*, dcreg_set_*_outliers*, dcreg_target_remove_outliers).  Scratch of one call: the
-    // packed cloud, the used flags and their scan, the used points compacted (w = input index) and their index; per input point the score,
-    // the keep flag and its scan (n + 1 entries each, the last flag 0); the partial sums of the tree reductions (two sides, used in turn);
-    // the call's counts ([0] points in the statistics, [1] sparse points); the outputs (3 floats per point, or packed as k_pack packs a
-    // cloud) and the byte mask
+    // the packed-cloud scratch of every call over a caller's cloud (scratch.hip cloud_used_compact / cloud_index_used): the packed cloud,
+    // the used (finite) flags and their scan (n + 1 entries each, the last flag 0), the used points compacted (w = input index) and their
+    // index.  Scratch of one call, kept for the next.  The outlier filter packs, compacts and indexes its cloud here, and so do the cloud
+    // forms of the normals (one cloud and many) and of both FPFH rules; the map form of the descriptors re-indexes the points with a
+    // normal here.  One index for all of them: a descriptor call lets the normals search it and then rebuilds it for itself, and a
+    // descriptor report behind any later build is refused (index_epoch)
+    struct CloudScratch {
+        DevBuf<float4> pts, cpts;
+        DevBuf<uint32_t> used, upos;
+        IndexSet idx;
+    };
+    CloudScratch cloud;
+    // outlier removal (outliers.hip: dcreg_outlier_filter*, dcreg_set_*_outliers*, dcreg_target_remove_outliers).  Scratch of one call, beside
+    // the packed-cloud scratch above: per input point the score, the keep flag and its scan (n + 1 entries each, the last flag 0); the
+    // partial sums of the tree reductions (two sides, used in turn); the call's counts ([0] points in the statistics, [1] sparse points);
+    // the outputs (3 floats per point, or packed as k_pack packs a cloud) and the byte mask
     struct OutlierBufs {
-        DevBuf<float4> pts, cpts, out4;
-        DevBuf<uint32_t> used, upos, keep, pos;
+        DevBuf<float4> out4;
+        DevBuf<uint32_t> keep, pos;
         DevBuf<float> score, out;
         DevBuf<uint8_t> mask;
         DevBuf<double> part[2];
         DevBuf<unsigned long long> cnt;
-        IndexSet idx;
     };
     OutlierBufs outl;
     // keyframe store (keyframes.hip: dcreg_keyframes_*, dcreg_set_target_keyframes).  The store: the points of all keyframes back to back,
@@ -434,7 +454,7 @@ struct dcreg_ctx {
     VisibilityBufs vis;
     // surface normals (normals.hip: dcreg_normals*, dcreg_target_normals*).  Scratch of one call: the outputs per input point (3 + 1 + 3
     // floats, those that are wanted) and the call's counts ([0] points with a normal, [1] sparse points); the cloud form packs, compacts and
-    // indexes its cloud in the outlier scratch (outl.pts, cpts, used, upos, idx)
+    // indexes its cloud in the cloud scratch (CloudScratch: cloud.pts, cpts, used, upos, idx)
     // The many-clouds form (dcreg_normals_clouds*, dcreg_frames_normals_keep): every cloud's used points indexed on its own, all at once
     // (context.hip clouds_index_build into `clouds`: sorted points, tables, row words), cnt two words per cloud; d_off the cloud offsets,
     // d_words the clouds' bounds (6 n ordered floats) and the first compacted point of each (n + 1), d_launch the launch's records
@@ -691,7 +711,7 @@ struct dcreg_ctx {
     // "has an SPFH" flag), the 33 floats per input point, the call's counts ([0] descriptors, [1] empty points, [2] non-finite kept
     // normals of the map form).  Matching: both descriptor sets (the host form), per row of either set its valid flag, per (split, query)
     // the partial winners {D1, D2, {j1, j2}}, the results of both directions and the counts ([0] valid a, [1] valid b, [2] mutual).
-    // The cloud form packs, compacts and indexes its cloud in the outlier scratch, as the normals do.
+    // The cloud form packs, compacts and indexes its cloud in the cloud scratch (CloudScratch), as the normals do.
     struct FeatureBufs {
         DevBuf<float> nrm_in, out;
         DevBuf<uint32_t> nb_pos;
@@ -955,9 +975,34 @@ int build_gap_field(dcreg_ctx *c, dcreg_ctx::IndexSet &d, double radius_hint);
 int clouds_index_build(dcreg_ctx *c, dcreg_ctx::PairSet &ps, const float4 *raw, int n_t, const std::vector<int64_t> &count,
                        const std::vector<int64_t> &first, const std::vector<uint32_t> &words, double radius_hint, double max_cells,
                        std::vector<GridDev> &grids, std::vector<uint8_t> &built);
-// outliers.hip: one call's filter over the n packed points at `in` (input order, w = the index).  map == null: the used points are compacted
-// and indexed (c->outl.idx); otherwise the points ARE the map behind that index (all finite) and its grid is searched.  Leaves the scores in
-// c->outl.score, the keep flags and their exclusive scan in c->outl.keep / pos (n + 1 entries) and the counts in r; waits for the stream.
+// ---- scratch.hip: what the passes over a cloud share (the outlier filter, the normals, the descriptors, the visibility filter, the 1-NN
+// engines, the map updates).
+// cloud_used_compact: used flags of the n packed points at `in` and their scan (n + 1 entries in c->cloud.used / upos) and ALL used points
+// compacted into c->cloud.cpts (w = the input index); nothing is waited for.  cloud_index_used: that, then - when there are at least
+// min_used used points - their index in c->cloud.idx (hint: the cell size follows it, 0 = from the density); waits for the stream for
+// *n_used.  The build's last_build_capped word belongs to the target's builds: saved and restored here
+int cloud_used_compact(dcreg_ctx *c, const float4 *in, int64_t n);
+int cloud_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used);
+// the compaction of the n packed points at `in` by keep flags and their exclusive scan: 3 floats per kept point to out3 and / or a packed
+// point (w = the new index, as k_pack packs a cloud) to out4, the byte mask where wanted
+int cloud_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, float4 *out4, uint8_t *mask);
+// the tail of a filter call (dcreg_outlier_filter*, dcreg_visibility_filter*) behind its keep flags: the capacity refusal, the output and
+// mask buffers sized, the flags' scan where the caller has not made it (scan), cloud_write_kept and the copies of points and mask to the
+// caller, queued.  The caller adds its own copies and waits for the stream; n == 0: nothing but the refusal
+int cloud_filter_finish(dcreg_ctx *c, const float4 *pts, int64_t n, const uint32_t *keep, uint32_t *pos, bool scan, int64_t n_out, int64_t capacity,
+                        DevBuf<float> &out_buf, DevBuf<uint8_t> &mask_buf, float *out, uint8_t *mask, bool on_device);
+// flag_s[p] = the flag of the point at sorted position p of an index, flag_r by original index (n + 1 entries, the last 0)
+int flags_to_sorted(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s);
+// the plus-scan of n uint32 on c->stream, exclusive (from 0) or inclusive; its temporary storage is c->sort_tmp
+int scan_u32(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inclusive);
+// the rings a walk of g needs to cover the ball of squared radius `bound`; -1: sweep the grid
+int rings_for_bound(const GridDev &g, float bound);
+// a[0 .. n) = v, queued
+void fill_f32(dcreg_ctx *c, float *a, int64_t n, float v);
+// ---- outliers.hip: one call's filter over the n packed points at `in` (input order, w = the index).  map == null: the used points are
+// compacted and indexed (cloud_index_used); otherwise the points ARE the map behind that index (all finite) and its grid is searched.  Leaves
+// the scores in c->outl.score, the keep flags and their exclusive scan in c->outl.keep / pos (n + 1 entries) and the counts in r; waits for
+// the stream.
 struct OutlierResult {
     int64_t n_in = 0, n_finite = 0, n_sparse = 0, n_out = 0;
     double mean = 0.0, stddev = 0.0, threshold = 0.0;
@@ -967,20 +1012,6 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
 void outlier_info(dcreg_outlier_info *info, const OutlierResult &r);
 // the kept points of the pass packed into c->outl.out4 as k_pack packs a cloud (w = the new index)
 int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_out);
-// flag_s[p] = the keep flag of the map point at sorted position p (n + 1 entries, the last 0)
-int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s);
-// the helpers the other passes share: the exclusive scan of n flags, and the compaction of the n packed points at `in` by keep flags and
-// their scan - 3 floats per kept point to out3, the byte mask where wanted
-int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n);
-int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask);
-// ... and for normals.hip: the first step of outlier_pass on its own - the used points of the n packed points at `in` compacted into
-// c->outl.cpts (w = the input index) and, when there are at least min_used of them, indexed in c->outl.idx (hint: the cell size follows
-// it, 0 = from the density); waits for the stream for *n_used.  outlier_rings: the rings a walk needs to cover a squared radius
-int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used);
-int outlier_rings(const GridDev &g, float bound);
-// ... and its first two kernels alone, for many clouds at once: used flags and their scan (n + 1 entries in c->outl.used / upos) and ALL used
-// points compacted into c->outl.cpts (w = the input index); nothing is waited for
-int outlier_used_compact(dcreg_ctx *c, const float4 *in, int64_t n);
 // normals.hip: the parameter refusals of dcreg_normals (engine.cpp reaches it through dcreg_normal_params_check)
 int normals_check(dcreg_ctx *c, const dcreg_normal_params *p);
 // normals.hip, for features.hip: dcreg_normals of a cloud that is already indexed (q: its nq used points in cell order behind the grid g,

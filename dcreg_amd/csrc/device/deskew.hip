@@ -26,8 +26,6 @@ constexpr int kDskBlock = 256;
 constexpr int kSpanPerThread = 8;                        // points per thread of k_deskew_span (a block covers one tile of 2048 points)
 constexpr int kHead = 4;                                 // keys[0..3]: finite points, outside their span, minimum key, ~maximum key
 
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 // order-preserving key of a double (ascending keys = ascending values; -0.0 below +0.0) and its inverse
 __device__ __forceinline__ unsigned long long key_of(double s) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(s);
@@ -53,10 +51,6 @@ __device__ __forceinline__ double stamp_of(const float *__restrict__ rec, int co
         v = type == DCREG_TIME_F64 ? __hiloint2double((int)hi, (int)lo) : (double)(((unsigned long long)hi << 32) | lo);
     }
     return scale * v;
-}
-
-__device__ __forceinline__ bool finite3f(float x, float y, float z) {
-    return fabsf(x) <= 3.4028235e38f && fabsf(y) <= 3.4028235e38f && fabsf(z) <= 3.4028235e38f;
 }
 
 __device__ __forceinline__ void cross(const double a[3], const double b[3], double o[3]) {
@@ -104,7 +98,7 @@ static __global__ void __launch_bounds__(kDskBlock) k_deskew_span(const float *_
         if (!cl[s].from_data) continue;
         const float *r = xyz + i * stride;
         const double t = stamp_of(r, column, type, scale);
-        if (!finite3f(r[0], r[1], r[2]) || !isfinite(t)) continue;
+        if (!finite_xyz(r[0], r[1], r[2]) || !isfinite(t)) continue;
         const unsigned long long kk = key_of(t);
         if (uniform) {
             kmin = std::min(kmin, kk); kmaxn = std::min(kmaxn, ~kk);
@@ -177,7 +171,7 @@ static __global__ void __launch_bounds__(kDskBlock) k_pack_deskew(const float *_
         const float x = r[0], y = r[1], z = r[2];
         const double t = stamp_of(r, column, type, scale);
         float ox = __builtin_nanf(""), oy = ox, oz = ox;
-        if (finite3f(x, y, z) && isfinite(t)) {
+        if (finite_xyz(x, y, z) && isfinite(t)) {
             const uint32_t s = n_clouds == 1 ? 0u : seg_of(off, n_clouds, i);
             const DeskewCloud &q = cl[s];
             double tb = q.t_begin, te = q.t_end;
@@ -227,7 +221,7 @@ static __global__ void __launch_bounds__(kDskBlock) k_pack_deskew_path(const flo
         const float x = r[0], y = r[1], z = r[2];
         const double t = stamp_of(r, column, type, scale);
         float ox = __builtin_nanf(""), oy = ox, oz = ox;
-        if (finite3f(x, y, z) && isfinite(t)) {
+        if (finite_xyz(x, y, z) && isfinite(t)) {
             const uint32_t s = n_clouds == 1 ? 0u : seg_of(off, n_clouds, i);
             const PathCloud &q = cl[s];
             const PathSeg *S = sg + q.first_seg;

@@ -2,7 +2,7 @@
 // first two stages of a correspondence-based global alignment, with the rules of the header, bitwise the numpy reference of
 // tests/fpfh_ref.py up to the header's one freedom (atan2 at an interior bin edge of theta).
 //   (cloud form)    the cloud packed, the points without a finite normal made non-finite (k_fpfh_unuse), the used points compacted and
-//                   indexed: the first step of the outlier pass (outliers.hip outlier_index_used); normals == NULL: dcreg_normals first,
+//                   indexed: the shared first step of scratch.hip (cloud_index_used); normals == NULL: dcreg_normals first,
 //                   on the same index (normals.hip normals_to_scratch).  The map form searches the map's own index
 //   k_fpfh_spfh<K>  one lane per used point, in the index's cell order: the ring walk of k_nrm with its heap (heap_nrm.hpp); the lane
 //                   writes its neighbour list - position and d2, rank order, k slots - and walks it once more for the pair features.
@@ -40,14 +40,7 @@ constexpr int kCountWords = 9;                           // 33 byte counters
 constexpr int kMatchBlock = 256, kMatchTile = 128;       // queries per block, candidate rows per LDS tile (33 KiB of doubles)
 constexpr double kPi = 3.14159265358979323846;
 
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 DCREG_DEVFN bool finitef(float x) { return fabsf(x) <= 3.4028235e38f; }
-
-static __global__ void k_fpfh_fill(float *__restrict__ a, int64_t n, float v) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = v;
-}
 
 // a point without a finite normal is not used: its x becomes NaN before the used points are compacted
 static __global__ void k_fpfh_unuse(float4 *__restrict__ pts, int64_t n, const float *__restrict__ nrm, int64_t nstride) {
@@ -613,7 +606,7 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     if (F.out.ensure(c, (size_t)kDim * (size_t)n) || F.cnt.ensure(c, 3) || F.nb_pos.ensure(c, k * nqs) || F.nb_d2.ensure(c, k * nqs) ||
         F.spfh.ensure(c, 3 * nqs))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_fpfh_fill, dim3(blocks((int64_t)kDim * n, 256)), dim3(256), 0, c->stream, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
+    fill_f32(c, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[2] = {0, 0};
     F.last_q = nq > 0 ? g.pts : nullptr; F.last_nq = nq; F.last_n = n;      // (dcreg_fpfh_debug_counts)
@@ -625,7 +618,7 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
         if (p->search_radius > 0.0) {
             bound = (float)(p->search_radius * p->search_radius);
             if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-            max_ring = outlier_rings(g, bound);
+            max_ring = rings_for_bound(g, bound);
         }
         if (p->k <= 8) launch_spfh<8>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
         else if (p->k <= 16) launch_spfh<16>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
@@ -650,7 +643,7 @@ int fpfh_radius_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const
     const size_t nqs = (size_t)std::max<int64_t>(nq, 1);
     if (F.out.ensure(c, (size_t)kDim * (size_t)n) || F.cnt.ensure(c, 4) || F.rrec.ensure(c, 9 * nqs) || F.rcounts.ensure(c, (size_t)kDim * nqs))
         return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_fpfh_fill, dim3(blocks((int64_t)kDim * n, 256)), dim3(256), 0, c->stream, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
+    fill_f32(c, F.out.data(), (int64_t)kDim * n, __builtin_nanf(""));
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 4 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[4] = {0, 0, 0, 0};
     F.rlast_q = nq > 0 ? g.pts : nullptr; F.rlast_nq = nq; F.rlast_n = n;      // (dcreg_fpfh_radius_debug_counts)
@@ -683,11 +676,11 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     return r.radius ? fpfh_radius_run(c, nq, g, n, nrm, nstride, r.rp, out, on_device, r.rinfo) : fpfh_run(c, nq, g, n, nrm, nstride, r.p, out, on_device, r.info);
 }
 
-// the n packed points at pts lose those without a finite normal, the rest is compacted and indexed in the outlier scratch
+// the n packed points at pts lose those without a finite normal, the rest is compacted and indexed in the cloud scratch
 int fpfh_index(dcreg_ctx *c, float4 *pts, int64_t n, const float *nrm, int64_t nstride, double hint, int64_t *n_used) {
     hipLaunchKernelGGL(k_fpfh_unuse, dim3(blocks(n, 256)), dim3(256), 0, c->stream, pts, n, nrm, nstride);
     HIP_TRY(c, hipGetLastError());
-    return outlier_index_used(c, pts, n, hint, 1, n_used);
+    return cloud_index_used(c, pts, n, hint, 1, n_used);
 }
 
 // dcreg_fpfh*: the cloud packed, the normals given or estimated, the used points indexed, the two kernels, the copies
@@ -705,7 +698,7 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    dcreg_ctx::OutlierBufs &B = c->outl;
+    dcreg_ctx::CloudScratch &B = c->cloud;
     if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
     const double hint = rule.hint();
     int64_t n_used = 0;
@@ -720,7 +713,7 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
         if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
     } else {
         int64_t n_finite = 0;
-        if (int rc = outlier_index_used(c, B.pts.data(), n, hint, 1, &n_finite)) return rc;
+        if (int rc = cloud_index_used(c, B.pts.data(), n, hint, 1, &n_finite)) return rc;
         dcreg_normal_info ni{};
         const bool indexed = n_finite >= np->k;            // (fewer: every point is sparse, as dcreg_normals says it)
         if (int rc = normals_to_scratch(c, indexed ? B.idx.sorted.data() : nullptr, indexed ? n_finite : 0, indexed ? B.idx.grid : GridDev{}, n, n_finite, np, &ni))
@@ -760,7 +753,7 @@ int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int
     const float *nrm = (const float *)c->nicp.normals.data();
     if (bad == 0) return fpfh_run(c, n, wm.grid, n, nrm, 4, rule, out, on_device);
     // some map points have no normal: they are no candidates, so the others are indexed on their own, as a cloud's
-    dcreg_ctx::OutlierBufs &B = c->outl;
+    dcreg_ctx::CloudScratch &B = c->cloud;
     if (B.pts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     HIP_TRY(c, hipMemcpyAsync(B.pts.data(), wm.raw.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     int64_t n_used = 0;
@@ -768,7 +761,7 @@ int fpfh_map(dcreg_ctx *c, bool on_device, const FpfhRule &rule, float *out, int
     return fpfh_run(c, n_used, n_used > 0 ? B.idx.grid : GridDev{}, n, nrm, 4, rule, out, on_device);
 }
 
-// The reports read the sorted points of the index their call searched (last_q / rlast_q: the outlier scratch index or the map's own).  An
+// The reports read the sorted points of the index their call searched (last_q / rlast_q: the cloud scratch index or the map's own).  An
 // index built since, an update of the map or a change of its active index (dcreg_ctx::index_epoch) leaves other points there, with input
 // indices the export was not sized for: refused on the host, before anything is queued
 int fpfh_report_stale(dcreg_ctx *c) {

@@ -27,8 +27,6 @@ using namespace dcreg;
 
 namespace dcreg {
 
-static inline unsigned blocks_for(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 struct KdDev {
     const float *split;          // [n_internal]
     const uint8_t *axis;         // [n_internal]
@@ -203,8 +201,8 @@ int dcreg_knn_timed(dcreg_ctx *c, const float *q, int64_t n, int64_t stride, int
     }
     auto launch = [&]() -> int {
         if (index != 1) return launch_knn(c, c->map.grid, T.d_q.data(), n, k, max_radius, nullptr, T.d_idx.data(), T.d_d2.data(), index == 2);
-        if (k == 1) hipLaunchKernelGGL(k_kdtree_knn<1>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
-        else hipLaunchKernelGGL(k_kdtree_knn<5>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
+        if (k == 1) hipLaunchKernelGGL(k_kdtree_knn<1>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
+        else hipLaunchKernelGGL(k_kdtree_knn<5>, dim3(blocks(n, kBlock)), dim3(kBlock), 0, c->stream, T.d_q.data(), (uint32_t)n, T.dev(), bound, T.d_idx.data(), T.d_d2.data());
         HIP_TRY(c, hipGetLastError());
         return DCREG_OK;
     };

@@ -27,8 +27,6 @@ constexpr int kKfTile = kKfBlock * kKfPerThread;
 constexpr int64_t kKfMaxStored = ((int64_t)1 << 32) - 1;  // points the store may hold (KfMember::src is 32 bits wide: 51.5 GB of points)
 constexpr int64_t kKfMaxCall = ((int64_t)1 << 31) - 1;    // a call gathers fewer member points than this (the voxel pass's limit)
 
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 // the member of output point i: the largest m with mem[m].start <= i (the starts ascend strictly: empty members are not in the list)
 __device__ __forceinline__ int member_of(const KfMember *__restrict__ mem, int n_members, uint32_t i) {
     int lo = 0, hi = n_members - 1;
@@ -118,7 +116,7 @@ static __global__ void k_kf_store(const float4 *__restrict__ in, int64_t n, floa
     if (i >= n) return;
     const float4 p = in[i];
     out[3 * i] = p.x; out[3 * i + 1] = p.y; out[3 * i + 2] = p.z;
-    if (!(fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f)) atomicOr(flag, 1u);
+    if (!finite_point(p)) atomicOr(flag, 1u);
 }
 
 // what every entry point does first

@@ -424,7 +424,7 @@ OneNnBound one_nn_bound(const GridDev &g, double search_radius) {
     if ((double)bound < b.radius_sq) bound = std::nextafterf(bound, __builtin_inff());     // the smallest float >= R^2
     if (!(bound <= 3.0e38f)) bound = 3.0e38f;
     b.bound_f = bound;
-    b.max_ring = outlier_rings(g, bound);
+    b.max_ring = rings_for_bound(g, bound);
     return b;
 }
 int one_nn_warm_reserve(dcreg_ctx *c) {

@@ -1,7 +1,7 @@
 // Surface normals and curvature on the device (include/dcreg.h: dcreg_normals*, dcreg_target_normals*): pcl::NormalEstimation with a k
 // search, with the rule of the header, bitwise the numpy reference of tests/normals_ref.py.
-//   (cloud form)  the used (finite) points compacted with their input index in w and indexed: the first step of the outlier pass
-//                 (outliers.hip outlier_index_used); the map form skips this - the map is its own index
+//   (cloud form)  the used (finite) points compacted with their input index in w and indexed: the shared first step of every pass over a
+//                 cloud (scratch.hip cloud_index_used); the map form skips this - the map is its own index
 //   k_nrm<K>      one lane per used point, in the index's cell order: the ring walk of k_knn with a heap of (d2, index) keys and positions in
 //                 the last k of K slots; then the lane gathers its k neighbours in rank order (twice: the mean, the covariance - they are
 //                 hot in L2), solves the 3x3 problem with six Jacobi sweeps in registers, orients the normal and writes 12 + 4 (+ 12) bytes
@@ -30,17 +30,10 @@ namespace {
 
 constexpr int kMinK = 3, kMaxK = 32;
 
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 struct NrmArgs {
     double vx, vy, vz;
     int orient;
 };
-
-static __global__ void k_nrm_fill(float *__restrict__ a, int64_t n, float v) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = v;
-}
 
 // One lane per used point, in the index's cell order (the lanes of a wave search neighbouring cells); the point's input index is in w, and
 // the outputs go there (a null output is not wanted).  cnt[0] += points with a normal, cnt[1] += sparse points (one atomic pair per wave)
@@ -274,7 +267,7 @@ NrmSearch nrm_search_bound(const dcreg_normal_params *p) {       // (the bound a
 }
 NrmSearch nrm_search(const GridDev &g, const dcreg_normal_params *p) {
     NrmSearch s = nrm_search_bound(p);
-    if (p->search_radius > 0.0) s.max_ring = outlier_rings(g, s.bound);
+    if (p->search_radius > 0.0) s.max_ring = rings_for_bound(g, s.bound);
     return s;
 }
 void launch_nrm_k(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, const dcreg_normal_params *p, float *normal, float *curv, float *eig,
@@ -319,9 +312,9 @@ int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int
         return DCREG_E_NOMEM;
     float *d_normal = want_n ? B.normal.data() : nullptr, *d_curv = want_c ? B.curv.data() : nullptr, *d_eig = o.eig ? B.eig.data() : nullptr;
     const float nanf_ = __builtin_nanf("");
-    if (d_normal) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, d_normal, 3 * n, nanf_);
-    if (d_curv) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, d_curv, n, nanf_);
-    if (d_eig) hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, d_eig, 3 * n, nanf_);
+    if (d_normal) fill_f32(c, d_normal, 3 * n, nanf_);
+    if (d_curv) fill_f32(c, d_curv, n, nanf_);
+    if (d_eig) fill_f32(c, d_eig, 3 * n, nanf_);
     HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     unsigned long long cnt[2] = {0, (unsigned long long)n_used};
     if (nq > 0) {
@@ -352,10 +345,10 @@ int normals_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, boo
     if (info) std::memset(info, 0, sizeof(*info));
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    dcreg_ctx::OutlierBufs &B = c->outl;
+    dcreg_ctx::CloudScratch &B = c->cloud;
     if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
     int64_t n_used = 0;
-    if (int rc = outlier_index_used(c, B.pts.data(), n, p->search_radius, p->k, &n_used)) return rc;
+    if (int rc = cloud_index_used(c, B.pts.data(), n, p->search_radius, p->k, &n_used)) return rc;
     const bool indexed = n_used >= p->k;
     const NormalOut o{normal, curv, eig, on_device};
     return normals_run(c, indexed ? B.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? B.idx.grid : GridDev{}, n, n_used, p, o, info);
@@ -376,15 +369,15 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
         B.d_words.ensure(c, 7 * nc + 1))
         return DCREG_E_NOMEM;
     const float nanf_ = __builtin_nanf("");
-    hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, B.normal.data(), 3 * n, nanf_);
-    hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.curv.data(), n, nanf_);
+    fill_f32(c, B.normal.data(), 3 * n, nanf_);
+    fill_f32(c, B.curv.data(), n, nanf_);
     HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * nc * sizeof(unsigned long long), c->stream));
     HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * (nc + 1), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(B.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * nc, c->stream));
     HIP_TRY(c, hipMemsetAsync(B.d_words.data() + 3 * nc, 0, sizeof(uint32_t) * 3 * nc, c->stream));
-    if (int rc = outlier_used_compact(c, in, n)) return rc;
-    hipLaunchKernelGGL(k_ncl_bounds, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, c->outl.used.data(), B.d_off.data(), n_clouds, B.d_words.data());
-    hipLaunchKernelGGL(k_ncl_starts, dim3(blocks((int64_t)nc + 1, 256)), dim3(256), 0, c->stream, c->outl.upos.data(), B.d_off.data(), n_clouds,
+    if (int rc = cloud_used_compact(c, in, n)) return rc;
+    hipLaunchKernelGGL(k_ncl_bounds, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, c->cloud.used.data(), B.d_off.data(), n_clouds, B.d_words.data());
+    hipLaunchKernelGGL(k_ncl_starts, dim3(blocks((int64_t)nc + 1, 256)), dim3(256), 0, c->stream, c->cloud.upos.data(), B.d_off.data(), n_clouds,
                        B.d_words.data() + 6 * nc);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> words(7 * nc + 1);
@@ -407,7 +400,7 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
         words.resize(6 * nc);
         // (the table budget of a pair target, and at most 2^22 entries a cloud: the clouds of a call share the device)
         const double max_cells = (double)std::min<int64_t>(c->opt_pair_max_table_entries, (int64_t)1 << 22);
-        if (int rc = clouds_index_build(c, B.clouds, c->outl.cpts.data(), n_clouds, count, first, words, p->search_radius, max_cells, grids, built)) return rc;
+        if (int rc = clouds_index_build(c, B.clouds, c->cloud.cpts.data(), n_clouds, count, first, words, p->search_radius, max_cells, grids, built)) return rc;
         const NrmSearch sr = nrm_search_bound(p);                // (the rings are counted per grid below)
         std::vector<NrmCloud> recs;
         std::vector<uint2> blk;
@@ -415,7 +408,7 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
             if (!built[s]) continue;
             NrmCloud r;
             r.g = grids[s];
-            r.max_ring = p->search_radius > 0.0 ? outlier_rings(grids[s], sr.bound) : -1;
+            r.max_ring = p->search_radius > 0.0 ? rings_for_bound(grids[s], sr.bound) : -1;
             r.cloud = (uint32_t)s;
             r.base = 0u;
             const uint32_t nb = blocks(count[s], kBlock);
@@ -476,8 +469,8 @@ int normals_clouds(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *
     if (infos) std::memset(infos, 0, sizeof(*infos) * (size_t)n_clouds);
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = upload_cloud(c, xyz, n, stride, on_device, c->outl.pts)) return rc;
-    if (int rc = normals_clouds_run(c, c->outl.pts.data(), n, n_clouds, off, p, infos)) return rc;
+    if (int rc = upload_cloud(c, xyz, n, stride, on_device, c->cloud.pts)) return rc;
+    if (int rc = normals_clouds_run(c, c->cloud.pts.data(), n, n_clouds, off, p, infos)) return rc;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (normal) HIP_TRY(c, hipMemcpyAsync(normal, c->nrm.normal.data(), sizeof(float) * 3 * (size_t)n, kind, c->stream));
     if (curv) HIP_TRY(c, hipMemcpyAsync(curv, c->nrm.curv.data(), sizeof(float) * (size_t)n, kind, c->stream));
@@ -613,8 +606,8 @@ int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_
     if (n > 0) {
         if (B.normal.ensure(c, 3 * (size_t)n) || B.curv.ensure(c, (size_t)n) || B.cnt.ensure(c, 2 * nt) || ps.normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
         const float nanf_ = __builtin_nanf("");
-        hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(3 * n, 256)), dim3(256), 0, c->stream, B.normal.data(), 3 * n, nanf_);
-        hipLaunchKernelGGL(k_nrm_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.curv.data(), n, nanf_);
+        fill_f32(c, B.normal.data(), 3 * n, nanf_);
+        fill_f32(c, B.curv.data(), n, nanf_);
         HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * nt * sizeof(unsigned long long), c->stream));
         const NrmSearch sr = nrm_search_bound(p);
         std::vector<NrmCloud> recs;
@@ -624,7 +617,7 @@ int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_
             if (!ps.built[t] || m < p->k) continue;
             NrmCloud r;
             r.g = ps.grids[t];
-            r.max_ring = p->search_radius > 0.0 ? outlier_rings(ps.grids[t], sr.bound) : -1;
+            r.max_ring = p->search_radius > 0.0 ? rings_for_bound(ps.grids[t], sr.bound) : -1;
             r.cloud = (uint32_t)t;
             r.base = (uint32_t)ps.off[t];
             const uint32_t nb = blocks(m, kBlock);
@@ -771,11 +764,11 @@ int normals_source_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal
     c->gicp.src_kept = false;                                   // (a failed call leaves none)
     if (c->gicp.src_normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     int64_t n_used = 0;
-    if (int rc = outlier_index_used(c, c->d_src_raw.data(), n, p->search_radius, p->k, &n_used)) return rc;
+    if (int rc = cloud_index_used(c, c->d_src_raw.data(), n, p->search_radius, p->k, &n_used)) return rc;
     const bool indexed = n_used >= p->k;
     NormalOut o{nullptr, nullptr, nullptr, true};
     o.scratch = true;
-    if (int rc = normals_run(c, indexed ? c->outl.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? c->outl.idx.grid : GridDev{}, n, n_used, p, o, info))
+    if (int rc = normals_run(c, indexed ? c->cloud.idx.sorted.data() : nullptr, indexed ? n_used : 0, indexed ? c->cloud.idx.grid : GridDev{}, n, n_used, p, o, info))
         return rc;
     hipLaunchKernelGGL(k_nrm_pack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, c->nrm.normal.data(), (int64_t)3,
                        c->nrm.curv.data(), c->gicp.src_normals.data());
@@ -936,7 +929,7 @@ int follow_refit(dcreg_ctx *c, int64_t n, int64_t n_old) {
     uint32_t *flag = N.f_flag.data(), *pos = flag + n1;
     hipLaunchKernelGGL(k_follow_dirty, dim3(blocks((int64_t)n1, kBlock)), dim3(kBlock), 0, c->stream, m.sorted.data(), (uint32_t)n, (uint32_t)n_old,
                        N.reach.data(), m.grid, N.f_bits.data(), flag);
-    if (int rc = outlier_scan_flags(c, flag, pos, n1)) return rc;
+    if (int rc = scan_u32(c, flag, pos, n1, false)) return rc;
     uint32_t n_dirty = 0;
     HIP_TRY(c, hipMemcpyAsync(&n_dirty, pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,8 +1,8 @@
 // Outlier removal on the device (include/dcreg.h: dcreg_outlier_filter*, dcreg_set_source_outliers*, dcreg_set_target_outliers*,
 // dcreg_target_remove_outliers): PCL's StatisticalOutlierRemoval and RadiusOutlierRemoval with the rules of the header, bitwise the numpy
 // reference of tests/outliers_ref.py.  One pass serves every entry point:
-//   k_out_used + scan + k_out_compact   the used (finite) points, compacted with their input index in w; build_index over them
-//                                       (the in-place map call skips this: the map is its own index)
+//   (cloud_index_used)   the used (finite) points, compacted with their input index in w, and the index over them: the shared first step
+//                     of scratch.hip (the in-place map call skips this: the map is its own index)
 //   k_out_score<K>    statistical: a lane searches the grid for the k nearest OTHER points of its own point (the ring walk of k_knn, the
 //                     lane's own index never enters the heap), sums the k square roots in ascending order and writes ONE float
 //   k_out_count       radius mode: the same walk with a counter in place of the heap; it stops at min_neighbors
@@ -16,7 +16,6 @@
 #include <limits>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
 #include "context.hpp"
 
@@ -25,12 +24,6 @@ namespace {
 
 constexpr int kTreeBlock = 256;                          // threads of k_out_tree: a block reduces 2 x kTreeBlock aligned values
 constexpr int kMaxK = 32;
-
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
-__device__ __forceinline__ bool finite3(const float4 p) {
-    return fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
-}
 
 // The k smallest d2 to points other than `self`, ascending, in the last k of K slots (the first K - k hold -1 and never move: one
 // instantiation serves every k <= K, and the pruning distance is the k-th best, not the K-th).  Distances only: among equal d2 the rank by
@@ -68,25 +61,6 @@ struct HeapCount {
     DCREG_DEVFN void push(float d2, uint32_t idx, uint32_t, bool valid = true) { cnt += (valid && idx != self && d2 < bound) ? 1u : 0u; }
     DCREG_DEVFN float worst_d2() const { return cnt >= need ? 0.f : walk; }
 };
-
-// flag[i] = point i is used (n + 1 entries, the last 0)
-static __global__ void k_out_used(const float4 *__restrict__ p, int64_t n, uint32_t *__restrict__ flag) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    flag[i] = (i < n && finite3(p[i])) ? 1u : 0u;
-}
-// the used points, in input order (w keeps the input index)
-static __global__ void k_out_compact(const float4 *__restrict__ p, int64_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
-                                     float4 *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const float4 v = p[i];
-    out[pos[i]] = make_float4(v.x, v.y, v.z, __uint_as_float((uint32_t)i));
-}
-static __global__ void k_out_fill(float *__restrict__ score, int64_t n, float v) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) score[i] = v;
-}
 
 // Statistical mode: one lane per used point, in the index's cell order (the lanes of a wave search neighbouring cells); the point's input
 // index is in w, and the score goes there.  cnt[0] += points that enter the statistics, cnt[1] += sparse points (one atomic pair per wave)
@@ -173,33 +147,6 @@ static __global__ void k_out_keep(const float *__restrict__ score, int64_t n, do
     keep[i] = k ? 1u : 0u;
 }
 
-static __global__ void k_out_write(const float4 *__restrict__ in, int64_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ pos,
-                                   float *__restrict__ out3, float4 *__restrict__ out4, uint8_t *__restrict__ mask) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const bool k = keep[i] != 0u;
-    if (mask) mask[i] = k ? 1 : 0;
-    if (!k) return;
-    const float4 v = in[i];
-    const uint32_t j = pos[i];
-    if (out4) out4[j] = make_float4(v.x, v.y, v.z, __uint_as_float(j));
-    if (out3) { out3[3 * (int64_t)j] = v.x; out3[3 * (int64_t)j + 1] = v.y; out3[3 * (int64_t)j + 2] = v.z; }
-}
-
-static __global__ void k_out_sorted_flags(const float4 *__restrict__ sorted, int64_t n, const uint32_t *__restrict__ flag_r, uint32_t *__restrict__ flag_s) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    flag_s[i] = i < n ? flag_r[__float_as_uint(sorted[i].w)] : 0u;
-}
-
-int scan_excl(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n) {
-    size_t tmp = 0;
-    HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    return DCREG_OK;
-}
-
 // T over the n scores (MODE 0 / 1): queued; the sum lands in *d_sum (device)
 int tree_sum(dcreg_ctx *c, int mode, const float *score, int64_t n, double mean, const double **d_sum) {
     dcreg_ctx::OutlierBufs &B = c->outl;
@@ -216,13 +163,6 @@ int tree_sum(dcreg_ctx *c, int mode, const float *score, int64_t n, double mean,
     HIP_TRY(c, hipGetLastError());
     *d_sum = B.part[side].data();
     return DCREG_OK;
-}
-
-// the rings a walk needs to cover the ball of squared radius `bound` (launch_knn's rule); -1: sweep the grid
-int rings_for_bound(const GridDev &g, float bound) {
-    int kk = 1;
-    while (kk < 100000) { const double s = (double)kk * g.h * (1.0 - 1e-9); if (s * s * (1.0 - 1e-6) >= (double)bound) return kk; ++kk; }
-    return -1;
 }
 
 template <int K>
@@ -268,12 +208,12 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
     dcreg_ctx::OutlierBufs &B = c->outl;
     const size_t n1 = (size_t)n + 1;
     const size_t parts = (size_t)((n + 2 * kTreeBlock - 1) / (2 * kTreeBlock));
-    if (B.used.ensure(c, n1) || B.upos.ensure(c, n1) || B.keep.ensure(c, n1) || B.pos.ensure(c, n1) || B.score.ensure(c, (size_t)n) ||
-        B.part[0].ensure(c, parts) || B.part[1].ensure(c, parts) || B.cnt.ensure(c, 2) || (!map && B.cpts.ensure(c, (size_t)n)))
+    if (B.keep.ensure(c, n1) || B.pos.ensure(c, n1) || B.score.ensure(c, (size_t)n) || B.part[0].ensure(c, parts) || B.part[1].ensure(c, parts) ||
+        B.cnt.ensure(c, 2))
         return DCREG_E_NOMEM;
     const bool stat = p->mode == DCREG_OUTLIER_STATISTICAL;
     const double hint = stat ? p->search_radius : p->radius;
-    hipLaunchKernelGGL(k_out_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, B.score.data(), n, __builtin_nanf(""));
+    fill_f32(c, B.score.data(), n, __builtin_nanf(""));
     HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * sizeof(unsigned long long), c->stream));
     HIP_TRY(c, hipMemsetAsync(B.keep.data(), 0, n1 * sizeof(uint32_t), c->stream));
     // ---- the used points and their index
@@ -285,29 +225,17 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
         q = map->sorted.data(); nq = n; g = map->grid;
         r.n_finite = n;
     } else {
-        hipLaunchKernelGGL(k_out_used, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, in, n, B.used.data());
-        if (int rc = scan_excl(c, B.used.data(), B.upos.data(), n1)) return rc;
-        uint32_t n_used = 0;
-        HIP_TRY(c, hipMemcpyAsync(&n_used, B.upos.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
+        // (unbounded statistics over at most k used points keep every one of them: no search, no index)
+        int64_t n_used = 0;
+        if (int rc = cloud_index_used(c, in, n, hint, (stat && p->search_radius == 0.0) ? (int64_t)p->k + 1 : 1, &n_used)) return rc;
         r.n_finite = n_used;
-        used = B.used.data();
+        used = c->cloud.used.data();
         if (n_used == 0) {                    // nothing to search: every score NaN, every flag 0
             HIP_TRY(c, hipMemsetAsync(B.pos.data(), 0, n1 * sizeof(uint32_t), c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             return DCREG_OK;
         }
-        if (!(stat && p->search_radius == 0.0 && (int64_t)n_used <= p->k)) {
-            hipLaunchKernelGGL(k_out_compact, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.used.data(), B.upos.data(), B.cpts.data());
-            // (the build reports whether the table budget capped its cells: that word belongs to the target's builds)
-            const bool capped = c->last_build_capped;
-            int rc = build_index(c, B.cpts.data(), n_used, B.idx, hint, nullptr);
-            if (rc == DCREG_OK) rc = build_gap_field(c, B.idx, hint);
-            c->last_build_capped = capped;
-            if (rc) return rc;
-        }
-        q = B.idx.sorted.data(); nq = n_used; g = B.idx.grid;
+        q = c->cloud.idx.sorted.data(); nq = n_used; g = c->cloud.idx.grid;
     }
     // ---- scores, statistics, keep flags
     if (stat) {
@@ -363,7 +291,7 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
         hipLaunchKernelGGL(k_out_count, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, g, bound, walk, max_ring, (uint32_t)p->min_neighbors,
                            B.score.data(), B.keep.data());
     }
-    if (int rc = scan_excl(c, B.keep.data(), B.pos.data(), n1)) return rc;
+    if (int rc = scan_u32(c, B.keep.data(), B.pos.data(), n1, false)) return rc;
     uint32_t n_out = 0;
     HIP_TRY(c, hipMemcpyAsync(&n_out, B.pos.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -375,55 +303,7 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
 int outlier_write_packed(dcreg_ctx *c, const float4 *in, int64_t n, int64_t n_out) {
     dcreg_ctx::OutlierBufs &B = c->outl;
     if (B.out4.ensure(c, (size_t)std::max<int64_t>(n_out, 1))) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_out_write, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.keep.data(), B.pos.data(), (float *)nullptr, B.out4.data(),
-                       (uint8_t *)nullptr);
-    HIP_TRY(c, hipGetLastError());
-    return DCREG_OK;
-}
-
-int outlier_scan_flags(dcreg_ctx *c, const uint32_t *flag, uint32_t *pos, size_t n) { return scan_excl(c, flag, pos, n); }
-
-int outlier_rings(const GridDev &g, float bound) { return rings_for_bound(g, bound); }
-
-int outlier_used_compact(dcreg_ctx *c, const float4 *in, int64_t n) {
-    dcreg_ctx::OutlierBufs &B = c->outl;
-    const size_t n1 = (size_t)n + 1;
-    if (B.used.ensure(c, n1) || B.upos.ensure(c, n1) || B.cpts.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_out_used, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, in, n, B.used.data());
-    if (int rc = scan_excl(c, B.used.data(), B.upos.data(), n1)) return rc;
-    hipLaunchKernelGGL(k_out_compact, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, B.used.data(), B.upos.data(), B.cpts.data());
-    HIP_TRY(c, hipGetLastError());
-    return DCREG_OK;
-}
-
-int outlier_index_used(dcreg_ctx *c, const float4 *in, int64_t n, double hint, int64_t min_used, int64_t *n_used_out) {
-    dcreg_ctx::OutlierBufs &B = c->outl;
-    if (int rc = outlier_used_compact(c, in, n)) return rc;
-    uint32_t n_used = 0;
-    HIP_TRY(c, hipMemcpyAsync(&n_used, B.upos.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    *n_used_out = n_used;
-    if (n_used == 0 || (int64_t)n_used < min_used) return DCREG_OK;
-    // (the build reports whether the table budget capped its cells: that word belongs to the target's builds)
-    const bool capped = c->last_build_capped;
-    int rc = build_index(c, B.cpts.data(), n_used, B.idx, hint, nullptr);
-    if (rc == DCREG_OK) rc = build_gap_field(c, B.idx, hint);
-    c->last_build_capped = capped;
-    return rc;
-}
-
-int outlier_write_kept(dcreg_ctx *c, const float4 *in, int64_t n, const uint32_t *keep, const uint32_t *pos, float *out3, uint8_t *mask) {
-    if (n <= 0) return DCREG_OK;
-    hipLaunchKernelGGL(k_out_write, dim3(blocks(n, 256)), dim3(256), 0, c->stream, in, n, keep, pos, out3, (float4 *)nullptr, mask);
-    HIP_TRY(c, hipGetLastError());
-    return DCREG_OK;
-}
-
-int outlier_sorted_flags(dcreg_ctx *c, const float4 *sorted, int64_t n, const uint32_t *flag_r, uint32_t *flag_s) {
-    hipLaunchKernelGGL(k_out_sorted_flags, dim3(blocks(n + 1, 256)), dim3(256), 0, c->stream, sorted, n, flag_r, flag_s);
-    HIP_TRY(c, hipGetLastError());
-    return DCREG_OK;
+    return cloud_write_kept(c, in, n, B.keep.data(), B.pos.data(), nullptr, B.out4.data(), nullptr);
 }
 
 // dcreg_outlier_filter*: the pass, then - when the caller's capacity holds the output - the copies to the caller
@@ -437,22 +317,17 @@ static int outlier_filter_to(dcreg_ctx *c, const float *xyz, int64_t n, int64_t 
     if ((n > 0 && !xyz) || (capacity > 0 && !out)) { c->fail("null point buffer"); return DCREG_E_INVALID; }
     OutlierResult r;
     dcreg_ctx::OutlierBufs &B = c->outl;
+    DevBuf<float4> &pts = c->cloud.pts;
     if (n > 0) {
         HIP_TRY(c, hipSetDevice(c->device));
-        if (int rc = upload_cloud(c, xyz, n, stride, on_device, B.pts)) return rc;
+        if (int rc = upload_cloud(c, xyz, n, stride, on_device, pts)) return rc;
     }
-    if (int rc = outlier_pass(c, B.pts.data(), n, p, nullptr, r)) return rc;
+    if (int rc = outlier_pass(c, pts.data(), n, p, nullptr, r)) return rc;
     *n_out = r.n_out;
     outlier_info(info, r);
-    if (r.n_out > capacity) { c->fail("the output holds %lld points, the capacity is %lld", (long long)r.n_out, (long long)capacity); return DCREG_E_INVALID; }
+    if (int rc = cloud_filter_finish(c, pts.data(), n, B.keep.data(), B.pos.data(), false, r.n_out, capacity, B.out, B.mask, out, mask, on_device)) return rc;
     if (n == 0) return DCREG_OK;
-    if (B.out.ensure(c, (size_t)(3 * std::max<int64_t>(r.n_out, 1))) || (mask && B.mask.ensure(c, (size_t)n))) return DCREG_E_NOMEM;
-    hipLaunchKernelGGL(k_out_write, dim3(blocks(n, 256)), dim3(256), 0, c->stream, (const float4 *)B.pts.data(), n, (const uint32_t *)B.keep.data(),
-                       (const uint32_t *)B.pos.data(), B.out.data(), (float4 *)nullptr, mask ? B.mask.data() : (uint8_t *)nullptr);
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (r.n_out > 0) HIP_TRY(c, hipMemcpyAsync(out, B.out.data(), sizeof(float) * 3 * (size_t)r.n_out, kind, c->stream));
-    if (mask) HIP_TRY(c, hipMemcpyAsync(mask, B.mask.data(), (size_t)n, kind, c->stream));
-    if (scores) HIP_TRY(c, hipMemcpyAsync(scores, B.score.data(), sizeof(float) * (size_t)n, kind, c->stream));
+    if (scores) HIP_TRY(c, hipMemcpyAsync(scores, B.score.data(), sizeof(float) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;

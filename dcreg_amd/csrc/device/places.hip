@@ -32,8 +32,6 @@ constexpr int kDistEntries = 4, kDistQueries = 16;       // entries x queries of
 constexpr int64_t kDistBatchPairs = (int64_t)1 << 24;    // (query, entry) pairs whose distances are kept at once (12 B each)
 constexpr int kNoIndex = 0x7FFFFFFF;                     // k_place_select: a candidate that is used up or never was one
 
-inline unsigned blocks(int64_t n, int64_t bs) { return (unsigned)((n + bs - 1) / bs); }
-
 // what the kernels need of dcreg_place_params
 struct PlaceDev {
     int n_rings, n_sectors;
@@ -46,10 +44,6 @@ __device__ __forceinline__ uint32_t fkey_of(float v) {
     return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float fkey_value(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7FFFFFFFu) : ~k); }
-
-__device__ __forceinline__ bool finite3f(float x, float y, float z) {
-    return fabsf(x) <= 3.4028235e38f && fabsf(y) <= 3.4028235e38f && fabsf(z) <= 3.4028235e38f;
-}
 
 // the bin of a finite point by the rules of include/dcreg.h (-1: outside the range gate) and the value it offers to it.  Every operation
 // and its order are the header's: a folded constant (n_sectors / 2 pi, n_rings / max_range) or a gate on the root moves points that lie on
@@ -87,7 +81,7 @@ static __global__ void __launch_bounds__(kPlBlock) k_place_bins(const float4 *__
         const int64_t i = base + threadIdx.x + (int64_t)k * kPlBlock;
         if (i > last) break;
         const float4 p = pts[i];
-        if (!finite3f(p.x, p.y, p.z)) continue;
+        if (!finite_xyz(p.x, p.y, p.z)) continue;
         ++fin;
         float v;
         const int bin = place_bin(P, p.x, p.y, p.z, v);

@@ -8,7 +8,7 @@
 //   k_vis_vote     one thread per point, a loop over the batch's members with pose and parameters in scalar registers; the range gate comes
 //                  before any trigonometry; the two counts stay in registers and are added to the point's counters once per batch by the
 //                  thread that owns the point (plain loads and stores, no atomics)
-//   k_vis_keep     the decision per point, the call's counts (one atomic triple per wave); the callers scan and compact (outliers.hip)
+//   k_vis_keep     the decision per point, the call's counts (one atomic triple per wave); the callers scan and compact (scratch.hip)
 // The counts are integers summed over the members, so neither the member order nor the batching ("visibility_max_bytes") can change a bit.
 #include <algorithm>
 #include <cmath>
@@ -29,8 +29,6 @@ constexpr int kVisTile = kVisBlock * kVisPerThread;
 constexpr int64_t kVisMaxBatchPoints = ((int64_t)1 << 31) - 1;   // stored points of one batch (VisMember::start is 32 bits wide)
 constexpr uint32_t kInfBits = 0x7f800000u;
 constexpr double kTwoPi = 6.283185307179586;
-
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 // the parameters as the kernels take them (by value: scalar registers)
 struct VisDev {
@@ -150,7 +148,7 @@ static __global__ void __launch_bounds__(kVisBlock) k_vis_keep(const float4 *__r
     bool fin = false, obs = false, gone = false;
     if (i < n) {
         const float4 p = pts[i];
-        fin = fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
+        fin = fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;   // (finite_point, written out: the call compiles to other code here)
         const int th = through[i], ob = observed[i];
         obs = fin && ob >= 1;
         gone = fin && th >= min_votes && (double)th >= min_ratio * (double)ob;
@@ -269,14 +267,10 @@ int filter_to(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on
     }
     *n_out = r.n_out;
     visibility_info(info, r);
-    if (r.n_out > capacity) { c->fail("the output holds %lld points, the capacity is %lld", (long long)r.n_out, (long long)capacity); return DCREG_E_INVALID; }
+    // (the flags' scan is queued just before the write)
+    if (int rc = cloud_filter_finish(c, B.pts.data(), n, B.keep.data(), B.pos.data(), true, r.n_out, capacity, B.out, B.mask, out, mask, on_device)) return rc;
     if (n == 0) return DCREG_OK;
-    if (B.out.ensure(c, (size_t)(3 * std::max<int64_t>(r.n_out, 1))) || (mask && B.mask.ensure(c, (size_t)n))) return DCREG_E_NOMEM;
-    if (int rc = outlier_scan_flags(c, B.keep.data(), B.pos.data(), (size_t)n + 1)) return rc;
-    if (int rc = outlier_write_kept(c, B.pts.data(), n, B.keep.data(), B.pos.data(), B.out.data(), mask ? B.mask.data() : nullptr)) return rc;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (r.n_out > 0) HIP_TRY(c, hipMemcpyAsync(out, B.out.data(), sizeof(float) * 3 * (size_t)r.n_out, kind, c->stream));
-    if (mask) HIP_TRY(c, hipMemcpyAsync(mask, B.mask.data(), (size_t)n, kind, c->stream));
     if (through) HIP_TRY(c, hipMemcpyAsync(through, B.through.data(), sizeof(int32_t) * (size_t)n, kind, c->stream));
     if (observed) HIP_TRY(c, hipMemcpyAsync(observed, B.observed.data(), sizeof(int32_t) * (size_t)n, kind, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -22,7 +22,6 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "context.hpp"
 #include "jacobi.hpp"
@@ -40,12 +39,6 @@ constexpr double kVoxLimit = 4611686018427387904.0;     // 2^62: voxel coordinat
 // behind the clouds kTail int64 slots read as uint32: [0..2] minimum, [3..5] maximum of the output (ordered-uint, k_bounds), [6] overflow
 constexpr int kCnt = 9;
 constexpr int kTail = 4;
-
-inline unsigned blocks(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
-__device__ __forceinline__ bool finite3(const float4 p) {
-    return fabsf(p.x) <= 3.4028235e38f && fabsf(p.y) <= 3.4028235e38f && fabsf(p.z) <= 3.4028235e38f;
-}
 
 // floor((double)p / leaf) per axis, as the header defines it (an IEEE double division: the build has no fast-math)
 __device__ __forceinline__ void voxel_of(const float4 p, const double lx, const double ly, const double lz, double v[3]) {
@@ -84,7 +77,7 @@ static __global__ void __launch_bounds__(kVoxBlock) k_vox_coords(const float4 *_
         const uint32_t s = uniform ? s0 : seg_of(off, n_clouds, i);
         seg[i] = s;
         const float4 p = pts[i];
-        if (!finite3(p)) continue;
+        if (!finite_point(p)) continue;
         double v[3];
         voxel_of(p, lx, ly, lz, v);
         long long vi[3];
@@ -138,7 +131,7 @@ static __global__ void k_vox_keys(const float4 *__restrict__ pts, int64_t n, uin
     const float4 p = pts[i];
     uint32_t s = seg[i];
     uint64_t r = 0;
-    if (finite3(p)) {
+    if (finite_point(p)) {
         double v[3];
         voxel_of(p, lx, ly, lz, v);
         const int64_t *c = cnt + (int64_t)kCnt * s;
@@ -434,16 +427,6 @@ int sort_pairs(dcreg_ctx *c, K *keys_in, K *keys_out, uint32_t *vals_in, uint32_
     return DCREG_OK;
 }
 
-int scan(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inclusive) {
-    size_t tmp = 0;
-    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
-    else HIP_TRY(c, rocprim::exclusive_scan(nullptr, tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    if (c->sort_tmp.ensure(c, tmp) != DCREG_OK) return DCREG_E_NOMEM;
-    if (inclusive) HIP_TRY(c, rocprim::inclusive_scan(c->sort_tmp.data(), tmp, in, out, n, rocprim::plus<uint32_t>(), c->stream));
-    else HIP_TRY(c, rocprim::exclusive_scan(c->sort_tmp.data(), tmp, in, out, 0u, n, rocprim::plus<uint32_t>(), c->stream));
-    return DCREG_OK;
-}
-
 int bits_for(int64_t v) { int b = 0; while (b < 63 && ((int64_t)1 << b) <= v) ++b; return b; }
 
 // Keys, stable sort, voxel heads and starts of the n packed points at pts (k_vox_coords has run: seg and the clouds' minimum voxels in
@@ -469,7 +452,7 @@ int vox_order(dcreg_ctx *c, const float4 *pts, int64_t n, int n_clouds, double l
         ord = c->d_vals.data();
     }
     hipLaunchKernelGGL(k_vox_heads, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), B.rel.data(), (uint32_t)n_clouds, B.head.data());
-    rc = scan(c, B.head.data(), B.incl.data(), (size_t)n, true);
+    rc = scan_u32(c, B.head.data(), B.incl.data(), (size_t)n, true);
     if (rc) return rc;
     hipLaunchKernelGGL(k_vox_starts, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n, B.seg.data(), (uint32_t)n_clouds, B.head.data(), B.incl.data(),
                        B.start.data());
@@ -551,7 +534,7 @@ int voxel_pass(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *off,
     // ---- one lane per voxel (at most n of them: the grids are sized for n, the lanes beyond the voxel count idle), compaction
     hipLaunchKernelGGL(k_vox_reduce, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), ord, n, B.seg.data(), B.start.data(), B.incl.data(), p->mode,
                        min_points, B.vout.data(), B.keep.data(), B.cnt.data());
-    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n, false);
+    rc = scan_u32(c, B.keep.data(), B.pos.data(), (size_t)n, false);
     if (rc) return rc;
     hipLaunchKernelGGL(k_vox_write, dim3(blocks(n, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.vout.data(), B.keep.data(), B.pos.data(), B.incl.data(), n,
                        packed ? nullptr : B.out.data(), packed ? c->d_aligned.data() : nullptr,
@@ -650,7 +633,7 @@ int voxel_map_keep(dcreg_ctx *c, const dcreg_voxel_map_params *p, dcreg_voxel_ma
     if (M.tmp.ensure(c, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, pts, ord, n_vox, B.start.data(), p->min_points, p->epsilon,
                        M.tmp.data(), B.keep.data(), M.cls.data());
-    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+    rc = scan_u32(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
     if (rc) return rc;
     unsigned long long cls[2] = {0, 0};
     uint32_t last[2] = {0, 0};
@@ -990,7 +973,7 @@ int follow_run(dcreg_ctx *c, const FollowChange &ch) {
     if (vf_ensure(c, B.head, n1) || vf_ensure(c, B.incl, n1)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_vfollow_flags, dim3(blocks((int64_t)n1, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, pts, n, l, uni, tb, M.f_set.data(), fmask,
                        B.head.data(), M.f_cnt.data());
-    int rc = scan(c, B.head.data(), B.incl.data(), n1, false);
+    int rc = scan_u32(c, B.head.data(), B.incl.data(), n1, false);
     if (rc) return rc;
     uint32_t n_hit32 = 0;
     HIP_TRY(c, hipMemcpyAsync(&n_hit32, B.incl.data() + n, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1033,7 +1016,7 @@ int follow_run(dcreg_ctx *c, const FollowChange &ch) {
         if (vf_ensure(c, M.tmp, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
         hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.f_sub.data(), ord, n_vox, B.start.data(), prm.min_points,
                            prm.epsilon, M.tmp.data(), B.keep.data(), M.cls.data());
-        rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+        rc = scan_u32(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
         if (rc) return rc;
     }
     // ---- the old records: carried or gone
@@ -1041,7 +1024,7 @@ int follow_run(dcreg_ctx *c, const FollowChange &ch) {
     if (vf_ensure(c, M.f_flag, 2 * nk1)) return DCREG_E_NOMEM;
     uint32_t *cflag = M.f_flag.data(), *cpos = cflag + nk1;
     hipLaunchKernelGGL(k_vfollow_carry, dim3(blocks((int64_t)nk1, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, M.vkeys.data(), nk, old, uni, tb, M.f_set.data(), fmask, cflag);
-    rc = scan(c, cflag, cpos, nk1, false);
+    rc = scan_u32(c, cflag, cpos, nk1, false);
     if (rc) return rc;
     uint32_t n_a32 = 0, last[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(&n_a32, cpos + nk, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1235,7 +1218,7 @@ int pairs_voxels_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     if (V.tmp.ensure(c, 3 * (size_t)n_vox)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_vmap_reduce, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), ord, n_vox, B.start.data(), p->min_points,
                        p->epsilon, V.tmp.data(), B.keep.data(), V.d_cnt.data() + 4 * (size_t)n_t);
-    rc = scan(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
+    rc = scan_u32(c, B.keep.data(), B.pos.data(), (size_t)n_vox, false);
     if (rc) return rc;
     hipLaunchKernelGGL(k_pvmap_count, dim3(blocks(n_vox, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, ord, n_vox, B.seg.data(), B.start.data(), B.keep.data(),
                        p->min_points, V.d_cnt.data());

@@ -199,6 +199,32 @@ def test_at_size_against_the_oracle_tree(ctx):
     assert_bitwise(ctx.outlier_filter(cloud, p), ref)
 
 
+@pytest.mark.parametrize("mode", ["statistical", "radius"])
+def test_a_cloud_without_a_finite_point(ctx, mode):
+    """65 points, every one NaN or inf in some coordinate: nothing is used, nothing is searched"""
+    cloud = np.full((65, 3), np.nan, np.float32)
+    cloud[1::3] = [1.0, np.inf, 2.0]
+    cloud[2::3] = [0.5, 0.25, -np.inf]
+    p = api.outlier_params(k=8, std_mul=1.0) if mode == "statistical" else api.outlier_params("radius", radius=0.5, min_neighbors=1)
+    got = ctx.outlier_filter(cloud, p)
+    kept, mask, scores, info = got
+    assert np.all(np.isnan(scores)) and not mask.any() and len(kept) == 0 and info["n_out"] == 0 and info["n_finite"] == 0
+    assert_bitwise(got, ref_of(cloud, p), mode)
+
+
+def test_fewer_points_than_k_bounded_and_unbounded(ctx):
+    """5 finite points, k = 8.  Bounded, the index is built and searched although no point can have k neighbours; unbounded, neither
+    happens and every point is kept"""
+    cloud = uniform(5)
+    bounded, unbounded = api.outlier_params(k=8, std_mul=1.0, search_radius=10.0), api.outlier_params(k=8, std_mul=1.0)
+    ref_b, ref_u = ref_of(cloud, bounded), ref_of(cloud, unbounded)
+    assert ref_b["n_finite"] == ref_u["n_finite"] == 5 and ref_u["n_out"] == 5 and ref_u["mask"].all()
+    got_b, got_u = ctx.outlier_filter(cloud, bounded), ctx.outlier_filter(cloud, unbounded)
+    assert_bitwise(got_b, ref_b, "bounded")
+    assert_bitwise(got_u, ref_u, "unbounded")
+    assert got_u[3]["n_out"] == 5 and got_u[1].all() and np.array_equal(bits(got_u[0]), bits(cloud))
+
+
 # ---- 2. determinism, device form, capacity
 def test_repeated_calls_and_other_contexts_give_the_same_bits(ctx, park):        # noqa: F811
     cloud = CLOUDS["planted"]()
