@@ -146,16 +146,6 @@ struct AlignKeyLess {
     }
 };
 
-// memory another stream may have written (a device-pointer argument): the context's own stream waits for the legacy default stream, as
-// upload_cloud orders a device cloud
-int after_null_stream(dcreg_ctx *c) {
-    if (c->stream != c->own_stream) return DCREG_OK;
-    if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    return DCREG_OK;
-}
-
 int align_check(dcreg_ctx *c, const dcreg_align_params *p) {
     if (!p) { c->fail("null alignment parameters"); return DCREG_E_INVALID; }
     if (p->n_hypotheses < 1 || p->n_hypotheses > kMaxHypotheses) { c->fail("n_hypotheses is %lld: 1 .. 2^24 expected", (long long)p->n_hypotheses); return DCREG_E_INVALID; }
@@ -264,19 +254,12 @@ int align_used_pairs(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a
     const size_t np = (size_t)n_pairs;
     if (A.flag.ensure(c, np + 1) || A.pos.ensure(c, np + 1) || A.P.ensure(c, kAlignPairFloats * np) || A.m_of_u.ensure(c, np) || A.cnt.ensure(c, 3))
         return DCREG_E_NOMEM;
-    const float *da = a, *db = b;
-    const int32_t *dca = ca, *dcb = cb;
-    if (on_device) {
-        if (int rc = after_null_stream(c)) return rc;
-    } else {
-        const size_t wa = n_a > 0 ? (size_t)(n_a - 1) * (size_t)stride_a + 3 : 0, wb = n_b > 0 ? (size_t)(n_b - 1) * (size_t)stride_b + 3 : 0;
-        if (A.a.ensure(c, wa) || A.b.ensure(c, wb) || A.ca.ensure(c, np) || A.cb.ensure(c, np)) return DCREG_E_NOMEM;
-        if (wa) HIP_TRY(c, hipMemcpyAsync(A.a.data(), a, sizeof(float) * wa, hipMemcpyHostToDevice, c->stream));
-        if (wb) HIP_TRY(c, hipMemcpyAsync(A.b.data(), b, sizeof(float) * wb, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(A.ca.data(), ca, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(A.cb.data(), cb, sizeof(int32_t) * np, hipMemcpyHostToDevice, c->stream));
-        da = A.a.data(); db = A.b.data(); dca = A.ca.data(); dcb = A.cb.data();
-    }
+    const float *da = nullptr, *db = nullptr;
+    const int32_t *dca = nullptr, *dcb = nullptr;
+    if (int rc = caller_rows(c, a, n_a, stride_a, 3, on_device, A.a, &da)) return rc;
+    if (int rc = caller_rows(c, b, n_b, stride_b, 3, on_device, A.b, &db, true)) return rc;
+    if (int rc = caller_rows(c, ca, n_pairs, 1, 1, on_device, A.ca, &dca, true)) return rc;
+    if (int rc = caller_rows(c, cb, n_pairs, 1, 1, on_device, A.cb, &dcb, true)) return rc;
     // ---- the used pairs
     hipLaunchKernelGGL(k_align_valid, dim3(blocks(n_pairs + 1, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, db, n_b, stride_b, dca, dcb, n_pairs,
                        A.flag.data());

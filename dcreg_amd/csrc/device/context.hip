@@ -406,14 +406,7 @@ int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool
         HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), from, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
         if (from == c->h_stage.data()) { HIP_TRY(c, hipEventRecord(c->h_stage_ev, c->stream)); c->h_stage_busy = true; }
         src = c->d_stage.data();
-    } else if (c->stream == c->own_stream) {
-        // The caller most likely wrote the cloud on the legacy default stream (torch's default stream is that stream: cuda_stream == 0), and
-        // the context's own stream is non-blocking, so nothing orders it after that stream: make it wait for the work queued there so far.
-        // A context given the caller's stream (dcreg_set_stream) is ordered on that stream instead.
-        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    }
+    } else if (int rc = caller_order(c)) return rc;
     if (dsk) return deskew_queue(c, src, n, stride, *dsk, dsk->out3 ? nullptr : raw.data());     // (deskew.hip: k_pack_deskew packs)
     hipLaunchKernelGGL(k_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, n, stride, raw.data());
     HIP_TRY(c, hipGetLastError());
@@ -1116,15 +1109,15 @@ static int frames_load(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, int n_frames, cons
     if (n > 0) {
         if (fs.raw.ensure(c, (size_t)n) || fs.src.ensure(c, (size_t)padded) || fs.d_off.ensure(c, (size_t)n_frames + 1) ||
             fs.d_dst.ensure(c, (size_t)n_frames) || fs.d_box.ensure(c, (size_t)n_frames) ||
-            c->d_stage.ensure(c, (size_t)(n * stride)) ||
             c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
             c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n))
             return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        const float *staged = nullptr;                 // (whole records: the deskew fields live in them)
+        if (int rc = caller_rows(c, xyz, n, stride, stride, false, c->d_stage, &staged)) return rc;
         HIP_TRY(c, hipMemcpyAsync(fs.d_off.data(), off, sizeof(int64_t) * ((size_t)n_frames + 1), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(fs.d_dst.data(), dst.data(), sizeof(uint32_t) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(fs.d_box.data(), box.data(), sizeof(FrameBox) * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, fs.raw.data());
+        hipLaunchKernelGGL(k_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, staged, n, stride, fs.raw.data());
         const uint32_t *order = nullptr;
         if (fbits + max_bits > 0) {
             hipLaunchKernelGGL(k_frame_keys, dim3(blocks(n, 256)), dim3(256), 0, c->stream, fs.raw.data(), n, fs.d_off.data(), n_frames, fs.d_box.data(), fbits,
@@ -1378,12 +1371,13 @@ static int pairs_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     for (int t = 0; t < n_t; ++t) count[(size_t)t] = off[t + 1] - off[t];
     std::vector<uint32_t> words((size_t)6 * n_t);
     if (n > 0) {
-        if (ps.raw.ensure(c, (size_t)n) || c->d_stage.ensure(c, (size_t)(n * stride))) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+        const float *staged = nullptr;
+        if (ps.raw.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
+        if (int rc = caller_rows(c, xyz, n, stride, stride, false, c->d_stage, &staged)) return rc;
         HIP_TRY(c, hipMemcpyAsync(ps.d_off.data(), off, sizeof(int64_t) * (size_t)(n_t + 1), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemsetAsync(ps.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
         HIP_TRY(c, hipMemsetAsync(ps.d_words.data() + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
-        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, ps.d_off.data(), n_t, ps.raw.data(), ps.d_words.data());
+        hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, staged, n, stride, ps.d_off.data(), n_t, ps.raw.data(), ps.d_words.data());
         HIP_TRY(c, hipMemcpyAsync(words.data(), ps.d_words.data(), sizeof(uint32_t) * words.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());

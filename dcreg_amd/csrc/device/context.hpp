@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -580,7 +581,7 @@ struct dcreg_ctx {
     // uploaded from there - the caller's buffer is consumed when dcreg_set_source returns whatever kind of memory it is, without a
     // stream synchronise; h_stage_ev = the upload behind the last use of the block
     PinnedBuf<float> h_stage; hipEvent_t h_stage_ev = nullptr; bool h_stage_busy = false;
-    hipEvent_t null_ev = nullptr;          // a cloud in device memory: marks the work queued on the legacy default stream before it is read
+    hipEvent_t null_ev = nullptr;          // caller_order: marks the work queued on the legacy default stream before a device input is read
     DevBuf<uint32_t> d_keys, d_keys2, d_vals, d_vals2;
     DevBuf<uint64_t> d_mkeys, d_mkeys2;
     DevBuf<uint32_t> d_scratch;
@@ -897,9 +898,9 @@ inline void lin_out_of_row(const double *row, dcreg_lin_out &o) {
     o.n_eff = (int64_t)std::llround(row[29]); o.n_pt = (int64_t)std::llround(row[30]);
 }
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
-// align.hip: step 1 of the alignment rule for both correspondence calls - the host form's uploads (on_device: the stream waits for the
-// legacy default stream instead), k_align_valid, the scan and k_align_gather into c->algn.P / m_of_u (and, for the host form, the index
-// arrays in c->algn.ca / cb) - and the number of used pairs, read back behind a stream synchronisation.  n_pairs > 0
+// align.hip: step 1 of the alignment rule for both correspondence calls - both clouds and both index arrays through caller_rows (the host
+// form's staged in c->algn.a / b / ca / cb, the device form's ordered once), k_align_valid, the scan and k_align_gather into c->algn.P /
+// m_of_u - and the number of used pairs, read back behind a stream synchronisation.  n_pairs > 0
 int align_used_pairs(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, const float *b, int64_t n_b, int64_t stride_b, const int32_t *ca,
                      const int32_t *cb, int64_t n_pairs, bool on_device, uint32_t *m_u);
 int refuse_in_flight(dcreg_ctx *c);    // context.hip: DCREG_E_STATE while a linearisation is queued or in flight (entry points that queue work)
@@ -944,8 +945,10 @@ struct GatherRun {
     int64_t n = 0;                         // points of the call
 };
 int gather_queue(dcreg_ctx *c, const GatherRun &g, float4 *out4, float *out3);
+// context.hip: a caller's cloud packed into `raw` - host records staged in c->d_stage (a small frame through the pinned block first), a
+// device cloud ordered by caller_order: the seam call of every entry point that takes a cloud
 int upload_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &raw,
-                 DeskewRun *dsk = nullptr, const GatherRun *gat = nullptr);   // context.hip
+                 DeskewRun *dsk = nullptr, const GatherRun *gat = nullptr);
 // voxel.hip: the voxel-grid pass of n_clouds clouds (offsets off[n_clouds + 1], host memory) - checks everything before it writes; the output
 // points go to c->vox.out (3 floats each) or, packed, to c->d_aligned as k_pack packs a cloud (one cloud only).  Ends with ONE readback of
 // the per-cloud counts and the bounds of the output.  dsk: the clouds are deskewed while they are packed (its counts come back with the
@@ -999,6 +1002,34 @@ int scan_u32(dcreg_ctx *c, const uint32_t *in, uint32_t *out, size_t n, bool inc
 int rings_for_bound(const GridDev &g, float bound);
 // a[0 .. n) = v, queued
 void fill_f32(dcreg_ctx *c, float *a, int64_t n, float v);
+// the squared bound of a search radius as a float (0: unbounded, 3.0e38) and, given the grid, the rings its walk needs (-1: sweep)
+struct SearchBound { float bound = 3.0e38f; int max_ring = -1; };
+SearchBound search_bound(double search_radius, const GridDev *g);
+// f(std::integral_constant<int, K>) for the neighbour-heap size K the kernels are instantiated for: the smallest of 8, 16, 32 that holds k
+template <class F>
+void with_heap_k(int k, F &&f) {
+    if (k <= 8) f(std::integral_constant<int, 8>{});
+    else if (k <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 32>{});
+}
+// ---- scratch.hip: the seam for caller memory.  Every input that arrives as host memory or as a device pointer
+// and every output that goes back to either passes through these three.
+// caller_order: a device-pointer input is read behind the legacy default stream (the rule and its reason stand at the definition).
+// caller_rows: n rows of `width` used elements at `stride` become readable on c->stream at *dev - host rows are copied into `stage`
+// ((n - 1) * stride + width elements; width == stride: whole records), device rows are ordered by caller_order and read in place.
+// ordered: an earlier input of the same call has already made the stream wait (a call orders itself once).  n == 0 copies nothing.
+// caller_out: `bytes` of a result to the caller's host or device buffer, queued on c->stream; the caller waits
+int caller_order(dcreg_ctx *c);
+int caller_in(dcreg_ctx *c, void *stage, const void *src, size_t bytes, bool on_device, bool ordered);
+int caller_out(dcreg_ctx *c, void *dst, const void *src, size_t bytes, bool on_device);
+template <typename T>
+int caller_rows(dcreg_ctx *c, const T *rows, int64_t n, int64_t stride, int64_t width, bool on_device, DevBuf<T> &stage, const T **dev,
+                bool ordered = false) {
+    const size_t len = n > 0 ? (size_t)(n - 1) * (size_t)stride + (size_t)width : 0;     // (the last row's padding is not the caller's to give)
+    if (!on_device && stage.ensure(c, len)) return DCREG_E_NOMEM;
+    *dev = on_device ? rows : stage.data();
+    return caller_in(c, stage.data(), rows, sizeof(T) * len, on_device, ordered);
+}
 // ---- outliers.hip: one call's filter over the n packed points at `in` (input order, w = the index).  map == null: the used points are
 // compacted and indexed (cloud_index_used); otherwise the points ARE the map behind that index (all finite) and its grid is searched.  Leaves
 // the scores in c->outl.score, the keep flags and their exclusive scan in c->outl.keep / pos (n + 1 entries) and the counts in r; waits for

@@ -579,16 +579,6 @@ int fpfh_radius_check(dcreg_ctx *c, const dcreg_fpfh_radius_params *p) {
 }
 int fpfh_check(dcreg_ctx *c, const FpfhRule &r) { return r.radius ? fpfh_radius_check(c, r.rp) : fpfh_check(c, r.p); }
 
-// memory another stream may have written (a device-pointer argument): the context's own stream waits for the legacy default stream, as
-// upload_cloud orders a device cloud
-int order_after_null_stream(dcreg_ctx *c) {
-    if (c->stream != c->own_stream) return DCREG_OK;
-    if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    return DCREG_OK;
-}
-
 template <int K>
 void launch_spfh(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, float bound, int max_ring, int k, const float *nrm, int64_t nstride) {
     dcreg_ctx::FeatureBufs &F = c->feat;
@@ -613,23 +603,14 @@ int fpfh_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const float 
     F.rlast_n = 0; F.last_epoch = c->index_epoch;
     if (nq > 0) {
         const float4 *q = g.pts;
-        float bound = 3.0e38f;
-        int max_ring = -1;
-        if (p->search_radius > 0.0) {
-            bound = (float)(p->search_radius * p->search_radius);
-            if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-            max_ring = rings_for_bound(g, bound);
-        }
-        if (p->k <= 8) launch_spfh<8>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
-        else if (p->k <= 16) launch_spfh<16>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
-        else launch_spfh<32>(c, q, nq, g, bound, max_ring, p->k, nrm, nstride);
+        const SearchBound s = search_bound(p->search_radius, &g);
+        with_heap_k(p->k, [&](auto K) { launch_spfh<decltype(K)::value>(c, q, nq, g, s.bound, s.max_ring, p->k, nrm, nstride); });
         hipLaunchKernelGGL(k_fpfh_sum, dim3(blocks(nq, kBlock)), dim3(kBlock), 0, c->stream, q, (uint32_t)nq, p->k, F.nb_pos.data(), F.nb_d2.data(),
                            F.spfh.data(), F.out.data(), F.cnt.data());
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(c, hipMemcpyAsync(out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                              c->stream));
+    if (int rc = caller_out(c, out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     if (info) { info->n_in = n; info->n_used = nq; info->n_empty = (int64_t)cnt[1]; info->n_out = (int64_t)cnt[0]; }
@@ -661,8 +642,7 @@ int fpfh_radius_run(dcreg_ctx *c, int64_t nq, const GridDev &g, int64_t n, const
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(c, hipMemcpyAsync(out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                              c->stream));
+    if (int rc = caller_out(c, out, F.out.data(), sizeof(float) * (size_t)kDim * (size_t)n, on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     if (info) {
@@ -704,12 +684,8 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
     int64_t n_used = 0;
     const float *nrm = normals;
     if (normals) {
-        if (!on_device) {
-            const size_t words = (size_t)(n - 1) * (size_t)nstride + 3;            // (the last point's padding is not the caller's to give)
-            if (c->feat.nrm_in.ensure(c, words)) return DCREG_E_NOMEM;
-            HIP_TRY(c, hipMemcpyAsync(c->feat.nrm_in.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-            nrm = c->feat.nrm_in.data();
-        }
+        // (staged beside the cloud, which upload_cloud has just left in c->d_stage; device normals: upload_cloud has ordered the call)
+        if (int rc = caller_rows(c, normals, n, nstride, 3, on_device, c->feat.nrm_in, &nrm, true)) return rc;
         if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
     } else {
         int64_t n_finite = 0;
@@ -721,7 +697,7 @@ int fpfh_cloud(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, const 
         nrm = c->nrm.normal.data();
         nstride = 3;
         if (normals_out)
-            HIP_TRY(c, hipMemcpyAsync(normals_out, nrm, sizeof(float) * 3 * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+            if (int rc = caller_out(c, normals_out, nrm, sizeof(float) * 3 * (size_t)n, on_device)) return rc;
         n_used = n_finite;
         // (a finite point without a normal is not used: the index over the finite points serves only when every one of them has one)
         if (ni.n_out != n_finite) if (int rc = fpfh_index(c, B.pts.data(), n, nrm, nstride, hint, &n_used)) return rc;
@@ -855,16 +831,9 @@ int feature_match(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, c
     if (F.va.ensure(c, na) || F.vb.ensure(c, nb) || F.cnt.ensure(c, 3) || F.idx.ensure(c, na) || F.d1.ensure(c, na) || F.idx2.ensure(c, na) ||
         F.d2.ensure(c, na) || (mutual_out && (F.mutual.ensure(c, na) || F.idx_b.ensure(c, nb))))
         return DCREG_E_NOMEM;
-    const float *da = a, *db = b;
-    if (on_device) {
-        if (int rc = order_after_null_stream(c)) return rc;
-    } else {
-        const size_t wa = (na - 1) * (size_t)stride_a + kDim, wb = n_b > 0 ? (size_t)(n_b - 1) * (size_t)stride_b + kDim : 0;
-        if (F.a.ensure(c, wa) || F.b.ensure(c, wb)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(F.a.data(), a, sizeof(float) * wa, hipMemcpyHostToDevice, c->stream));
-        if (wb) HIP_TRY(c, hipMemcpyAsync(F.b.data(), b, sizeof(float) * wb, hipMemcpyHostToDevice, c->stream));
-        da = F.a.data(); db = F.b.data();
-    }
+    const float *da = nullptr, *db = nullptr;
+    if (int rc = caller_rows(c, a, n_a, stride_a, kDim, on_device, F.a, &da)) return rc;
+    if (int rc = caller_rows(c, b, n_b, stride_b, kDim, on_device, F.b, &db, true)) return rc;
     HIP_TRY(c, hipMemsetAsync(F.cnt.data(), 0, 3 * sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_match_valid, dim3(blocks(n_a, 256)), dim3(256), 0, c->stream, da, n_a, stride_a, F.va.data(), F.cnt.data());
     if (n_b > 0) hipLaunchKernelGGL(k_match_valid, dim3(blocks(n_b, 256)), dim3(256), 0, c->stream, db, n_b, stride_b, F.vb.data(), F.cnt.data() + 1);
@@ -875,13 +844,12 @@ int feature_match(dcreg_ctx *c, const float *a, int64_t n_a, int64_t stride_a, c
         hipLaunchKernelGGL(k_match_mutual, dim3(blocks(n_a, 256)), dim3(256), 0, c->stream, (uint32_t)n_a, F.idx.data(), F.idx_b.data(), F.mutual.data(), F.cnt.data());
         HIP_TRY(c, hipGetLastError());
     }
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     unsigned long long cnt[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(idx_out, F.idx.data(), sizeof(int32_t) * na, kind, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_out, F.d1.data(), sizeof(double) * na, kind, c->stream));
-    if (idx2_out) HIP_TRY(c, hipMemcpyAsync(idx2_out, F.idx2.data(), sizeof(int32_t) * na, kind, c->stream));
-    if (d2nd_out) HIP_TRY(c, hipMemcpyAsync(d2nd_out, F.d2.data(), sizeof(double) * na, kind, c->stream));
-    if (mutual_out) HIP_TRY(c, hipMemcpyAsync(mutual_out, F.mutual.data(), na, kind, c->stream));
+    if (int rc = caller_out(c, idx_out, F.idx.data(), sizeof(int32_t) * na, on_device)) return rc;
+    if (int rc = caller_out(c, d_out, F.d1.data(), sizeof(double) * na, on_device)) return rc;
+    if (idx2_out) if (int rc = caller_out(c, idx2_out, F.idx2.data(), sizeof(int32_t) * na, on_device)) return rc;
+    if (d2nd_out) if (int rc = caller_out(c, d2nd_out, F.d2.data(), sizeof(double) * na, on_device)) return rc;
+    if (mutual_out) if (int rc = caller_out(c, mutual_out, F.mutual.data(), na, on_device)) return rc;
     HIP_TRY(c, hipMemcpyAsync(cnt, F.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());

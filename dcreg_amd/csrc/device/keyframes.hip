@@ -282,7 +282,7 @@ int submaps(dcreg_ctx *c, int n_submaps, const int64_t *moff, const int64_t *ids
             from = c->kf.out.data();
         }
     }
-    if (n_out > 0 && from) HIP_TRY(c, hipMemcpyAsync(out, from, bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (n_out > 0 && from) if (int rc = caller_out(c, out, from, bytes, out_on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;

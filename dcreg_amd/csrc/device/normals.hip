@@ -256,27 +256,16 @@ void launch_nrm(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, flo
 }
 // the search of a parameter set in a grid, and the launch of the instantiation its k takes
 struct NrmSearch { float bound; int max_ring; NrmArgs a; };
-NrmSearch nrm_search_bound(const dcreg_normal_params *p) {       // (the bound and the arguments: no grid yet, max_ring -1)
-    NrmSearch s{3.0e38f, -1, {}};
-    if (p->search_radius > 0.0) {
-        s.bound = (float)(p->search_radius * p->search_radius);
-        if (!(s.bound <= 3.0e38f)) s.bound = 3.0e38f;
-    }
+NrmSearch nrm_search(const dcreg_normal_params *p, const GridDev *g) {       // (g null: the bound and the arguments, no grid yet, max_ring -1)
+    const SearchBound b = search_bound(p->search_radius, g);
+    NrmSearch s{b.bound, b.max_ring, {}};
     s.a.vx = p->viewpoint[0]; s.a.vy = p->viewpoint[1]; s.a.vz = p->viewpoint[2]; s.a.orient = p->orient;
-    return s;
-}
-NrmSearch nrm_search(const GridDev &g, const dcreg_normal_params *p) {
-    NrmSearch s = nrm_search_bound(p);
-    if (p->search_radius > 0.0) s.max_ring = rings_for_bound(g, s.bound);
     return s;
 }
 void launch_nrm_k(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, const dcreg_normal_params *p, float *normal, float *curv, float *eig,
                   float4 *kept, float *reach) {
-    const NrmSearch s = nrm_search(g, p);
-    const int k = p->k;
-    if (k <= 8) launch_nrm<8>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
-    else if (k <= 16) launch_nrm<16>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
-    else launch_nrm<32>(c, q, nq, g, s.bound, s.max_ring, k, s.a, normal, curv, eig, kept, reach);
+    const NrmSearch s = nrm_search(p, &g);
+    with_heap_k(p->k, [&](auto K) { launch_nrm<decltype(K)::value>(c, q, nq, g, s.bound, s.max_ring, p->k, s.a, normal, curv, eig, kept, reach); });
 }
 
 }  // namespace
@@ -322,10 +311,9 @@ int normals_run(dcreg_ctx *c, const float4 *q, int64_t nq, const GridDev &g, int
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt, B.cnt.data(), sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     }
-    const hipMemcpyKind kind = o.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (o.normal) HIP_TRY(c, hipMemcpyAsync(o.normal, d_normal, sizeof(float) * 3 * (size_t)n, kind, c->stream));
-    if (o.curv) HIP_TRY(c, hipMemcpyAsync(o.curv, d_curv, sizeof(float) * (size_t)n, kind, c->stream));
-    if (o.eig) HIP_TRY(c, hipMemcpyAsync(o.eig, d_eig, sizeof(float) * 3 * (size_t)n, kind, c->stream));
+    if (o.normal) if (int rc = caller_out(c, o.normal, d_normal, sizeof(float) * 3 * (size_t)n, o.on_device)) return rc;
+    if (o.curv) if (int rc = caller_out(c, o.curv, d_curv, sizeof(float) * (size_t)n, o.on_device)) return rc;
+    if (o.eig) if (int rc = caller_out(c, o.eig, d_eig, sizeof(float) * 3 * (size_t)n, o.on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     if (info) { info->n_in = n; info->n_finite = n_used; info->n_sparse = (int64_t)cnt[1]; info->n_out = (int64_t)cnt[0]; }
@@ -401,7 +389,7 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
         // (the table budget of a pair target, and at most 2^22 entries a cloud: the clouds of a call share the device)
         const double max_cells = (double)std::min<int64_t>(c->opt_pair_max_table_entries, (int64_t)1 << 22);
         if (int rc = clouds_index_build(c, B.clouds, c->cloud.cpts.data(), n_clouds, count, first, words, p->search_radius, max_cells, grids, built)) return rc;
-        const NrmSearch sr = nrm_search_bound(p);                // (the rings are counted per grid below)
+        const NrmSearch sr = nrm_search(p, nullptr);             // (the rings are counted per grid below)
         std::vector<NrmCloud> recs;
         std::vector<uint2> blk;
         for (size_t s = 0; s < nc; ++s) {
@@ -425,9 +413,7 @@ int normals_clouds_run(dcreg_ctx *c, const float4 *in, int64_t n, int n_clouds, 
         const uint2 *d_blk = (const uint2 *)(B.d_launch.data() + rec_bytes);
         const dim3 grid((unsigned)blk.size()), block(kBlock);
         const int k = p->k;
-        if (k <= 8) hipLaunchKernelGGL(k_nrm_batch<8>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
-        else if (k <= 16) hipLaunchKernelGGL(k_nrm_batch<16>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
-        else hipLaunchKernelGGL(k_nrm_batch<32>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+        with_heap_k(k, [&](auto K) { hipLaunchKernelGGL(k_nrm_batch<decltype(K)::value>, grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data()); });
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(cnt.data(), B.cnt.data(), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));          // (h, recs and blk are the sources of the upload)
@@ -471,9 +457,8 @@ int normals_clouds(dcreg_ctx *c, int n_clouds, const float *xyz, const int64_t *
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = upload_cloud(c, xyz, n, stride, on_device, c->cloud.pts)) return rc;
     if (int rc = normals_clouds_run(c, c->cloud.pts.data(), n, n_clouds, off, p, infos)) return rc;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (normal) HIP_TRY(c, hipMemcpyAsync(normal, c->nrm.normal.data(), sizeof(float) * 3 * (size_t)n, kind, c->stream));
-    if (curv) HIP_TRY(c, hipMemcpyAsync(curv, c->nrm.curv.data(), sizeof(float) * (size_t)n, kind, c->stream));
+    if (normal) if (int rc = caller_out(c, normal, c->nrm.normal.data(), sizeof(float) * 3 * (size_t)n, on_device)) return rc;
+    if (curv) if (int rc = caller_out(c, curv, c->nrm.curv.data(), sizeof(float) * (size_t)n, on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;
@@ -518,25 +503,55 @@ int frames_normals_keep(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, const dcreg_norma
     return DCREG_OK;
 }
 
+// ------------------------------------------------------------------------------------------ kept normals given and read back
+// The four holders of kept normals (the map, the source, a frame set, the pair targets) share what their set and get forms do behind the
+// holder's own refusals, whose order each entry point keeps.  kept_args / kept_count / kept_capacity: the refusals with a common text
+// (`holds`: "the map holds", ...).  kept_take: the holder's array sized, the caller's n rows staged in c->d_stage or ordered
+// (caller_rows), `pack` queues the holder's kernel over them, the wait.  kept_give: n records from `from` to the caller, the wait.
+int kept_args(dcreg_ctx *c, const float *normals, int64_t stride) {
+    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+int kept_count(dcreg_ctx *c, const char *holds, int64_t n, int64_t n_given) {
+    if (n_given != n) { c->fail("%s %lld points, %lld normals were given", holds, (long long)n, (long long)n_given); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+int kept_capacity(dcreg_ctx *c, const char *holds, int64_t n, int64_t capacity) {
+    if (capacity < n) { c->fail("%s %lld points, the capacity is %lld", holds, (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    return DCREG_OK;
+}
+template <class Pack>
+int kept_take(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, bool on_device, DevBuf<float4> &kept, int64_t kept_len, Pack pack) {
+    const float *src = nullptr;
+    if (kept.ensure(c, (size_t)kept_len)) return DCREG_E_NOMEM;
+    if (int rc = caller_rows(c, normals, n, stride, 3, on_device, c->d_stage, &src)) return rc;
+    pack(src);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+int kept_give(dcreg_ctx *c, float *out, const float4 *from, int64_t n, bool on_device) {
+    if (int rc = caller_out(c, out, from, sizeof(float4) * (size_t)n, on_device)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCREG_OK;
+}
+
 // dcreg_frames_normals_set: the caller's normals in the upload order of the load become the frames' kept normals, as given
 int frames_normals_set(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, const float *normals, int64_t n_given, int64_t stride) {
-    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = kept_args(c, normals, stride)) return rc;
     if (int rc = refuse_in_flight(c)) return rc;
     if (fs.slice.empty()) { c->fail("%s", no_frames_msg(c, fs)); return DCREG_E_STATE; }
     std::vector<int64_t> off;
     const int64_t padded = frames_offsets(fs, off), n = off.back();
-    if (n_given != n) { c->fail("the frames hold %lld points, %lld normals were given", (long long)n, (long long)n_given); return DCREG_E_INVALID; }
+    if (int rc = kept_count(c, "the frames hold", n, n_given)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     fs.normals_kept = false;
-    if (n > 0) {
-        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
-        if (fs.normals.ensure(c, (size_t)padded) || c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_nrm_pack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(), fs.d_off.data(),
-                           (int)fs.slice.size(), c->d_stage.data(), stride, (const float *)nullptr, fs.normals.data());
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if (n > 0)
+        if (int rc = kept_take(c, normals, n, stride, false, fs.normals, padded, [&](const float *src) {
+                hipLaunchKernelGGL(k_nrm_pack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(),
+                                   fs.d_off.data(), (int)fs.slice.size(), src, stride, (const float *)nullptr, fs.normals.data());
+            }))
+            return rc;
     fs.normals_kept = true;
     return DCREG_OK;
 }
@@ -548,16 +563,14 @@ int frames_normals_get(dcreg_ctx *c, dcreg_ctx::FrameSet &fs, float *out, int64_
     if (fs.slice.empty() || !fs.normals_kept) { c->fail("no kept normals of these clouds"); return DCREG_E_STATE; }
     std::vector<int64_t> off;
     const int64_t padded = frames_offsets(fs, off), n = off.back();
-    if (capacity < n) { c->fail("the clouds hold %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (int rc = kept_capacity(c, "the clouds hold", n, capacity)) return rc;
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->gicp.tmp.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_nrm_unpack_frames, dim3(blocks(padded, 256)), dim3(256), 0, c->stream, fs.src.data(), padded, fs.d_dst.data(), fs.d_off.data(),
                        (int)fs.slice.size(), fs.normals.data(), c->gicp.tmp.data());
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->gicp.tmp.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DCREG_OK;
+    return kept_give(c, out, c->gicp.tmp.data(), n, false);
 }
 
 // ------------------------------------------------------------------------------------------ the targets of a pairs' build batch
@@ -609,7 +622,7 @@ int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_
         fill_f32(c, B.normal.data(), 3 * n, nanf_);
         fill_f32(c, B.curv.data(), n, nanf_);
         HIP_TRY(c, hipMemsetAsync(B.cnt.data(), 0, 2 * nt * sizeof(unsigned long long), c->stream));
-        const NrmSearch sr = nrm_search_bound(p);
+        const NrmSearch sr = nrm_search(p, nullptr);
         std::vector<NrmCloud> recs;
         std::vector<uint2> blk;
         for (size_t t = 0; t < nt; ++t) {
@@ -636,9 +649,7 @@ int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_
             const uint2 *d_blk = (const uint2 *)(B.d_launch.data() + rec_bytes);
             const dim3 grid((unsigned)blk.size()), block(kBlock);
             const int k = p->k;
-            if (k <= 8) hipLaunchKernelGGL((k_nrm_batch<8, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
-            else if (k <= 16) hipLaunchKernelGGL((k_nrm_batch<16, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
-            else hipLaunchKernelGGL((k_nrm_batch<32, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data());
+            with_heap_k(k, [&](auto K) { hipLaunchKernelGGL((k_nrm_batch<decltype(K)::value, true>), grid, block, 0, c->stream, d_recs, d_blk, sr.bound, k, sr.a, B.normal.data(), B.curv.data(), B.cnt.data()); });
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipMemcpyAsync(cnt.data(), B.cnt.data(), sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
         }
@@ -662,21 +673,18 @@ int pairs_normals_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal_
 // dcreg_pairs_normals_set: the caller's normals for all points of the batch in its upload order become the kept normals, as given
 int pairs_normals_set(dcreg_ctx *c, const float *normals, int64_t n_given, int64_t stride) {
     if (!c) return DCREG_E_INVALID;
-    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = kept_args(c, normals, stride)) return rc;
     if (int rc = pairs_batch_check(c)) return rc;
     dcreg_ctx::PairSet &ps = c->pairs;
     const int64_t n = ps.off.back();
-    if (n_given != n) { c->fail("the pair targets hold %lld points, %lld normals were given", (long long)n, (long long)n_given); return DCREG_E_INVALID; }
+    if (int rc = kept_count(c, "the pair targets hold", n, n_given)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     ps.normals_kept = false;
-    if (n > 0) {
-        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
-        if (ps.normals.ensure(c, (size_t)n) || c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), stride, (const float *)nullptr, n, ps.normals.data());
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if (n > 0)
+        if (int rc = kept_take(c, normals, n, stride, false, ps.normals, n, [&](const float *src) {
+                hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, stride, (const float *)nullptr, n, ps.normals.data());
+            }))
+            return rc;
     if (int rc = pairs_nn_grids(c)) return rc;
     ps.normals_kept = true;
     return DCREG_OK;
@@ -690,12 +698,10 @@ int pairs_normals_get(dcreg_ctx *c, float *out, int64_t capacity) {
     dcreg_ctx::PairSet &ps = c->pairs;
     if (!ps.normals_kept) { c->fail("no kept pair normals: dcreg_pairs_normals_keep or dcreg_pairs_normals_set first"); return DCREG_E_STATE; }
     const int64_t n = ps.off.back();
-    if (capacity < n) { c->fail("the pair targets hold %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (int rc = kept_capacity(c, "the pair targets hold", n, capacity)) return rc;
     if (n == 0) return DCREG_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, ps.normals.data(), sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DCREG_OK;
+    return kept_give(c, out, ps.normals.data(), n, false);
 }
 
 // dcreg_target_normals*: the whole map's points through the map's own index
@@ -724,28 +730,16 @@ int normals_map(dcreg_ctx *c, bool on_device, const dcreg_normal_params *p, floa
 int normals_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, bool on_device) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
-    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = kept_args(c, normals, stride)) return rc;
     if (c->map.n <= 0) { c->fail("no target: dcreg_set_target first"); return DCREG_E_STATE; }
-    const int64_t n_map = c->roi_active ? c->roi_store.n : c->map.n;
-    if (n != n_map) { c->fail("the map holds %lld points, %lld normals were given", (long long)n_map, (long long)n); return DCREG_E_INVALID; }
+    if (int rc = kept_count(c, "the map holds", c->roi_active ? c->roi_store.n : c->map.n, n)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->nicp.kept = false; c->nicp.warm_valid = false;
     c->nicp.from_keep = false;                                 // (given normals have no rule to refit with: updates drop them)
-    if (c->nicp.normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
-    const float *src = normals;
-    if (!on_device) {
-        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
-        if (c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-        src = c->d_stage.data();
-    } else if (c->stream == c->own_stream) {       // written on the legacy default stream, most likely: as upload_cloud orders a device cloud
-        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    }
-    hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, stride, (const float *)nullptr, n, c->nicp.normals.data());
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = kept_take(c, normals, n, stride, on_device, c->nicp.normals, n, [&](const float *src) {
+            hipLaunchKernelGGL(k_nrm_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, src, stride, (const float *)nullptr, n, c->nicp.normals.data());
+        }))
+        return rc;
     c->nicp.kept = true;
     return DCREG_OK;
 }
@@ -782,27 +776,16 @@ int normals_source_keep(dcreg_ctx *c, const dcreg_normal_params *p, dcreg_normal
 int normals_source_set(dcreg_ctx *c, const float *normals, int64_t n, int64_t stride, bool on_device) {
     if (!c) return DCREG_E_INVALID;
     if (int rc = refuse_in_flight(c)) return rc;
-    if (!normals || stride < 3) { c->fail("invalid kept-normal arguments"); return DCREG_E_INVALID; }
+    if (int rc = kept_args(c, normals, stride)) return rc;
     if (c->n_src <= 0) { c->fail("no source: dcreg_set_source first"); return DCREG_E_STATE; }
-    if (n != c->n_src) { c->fail("the source holds %lld points, %lld normals were given", (long long)c->n_src, (long long)n); return DCREG_E_INVALID; }
+    if (int rc = kept_count(c, "the source holds", c->n_src, n)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     c->gicp.src_kept = false;
-    if (c->gicp.src_normals.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
-    const float *src = normals;
-    if (!on_device) {
-        const size_t words = (size_t)(n - 1) * (size_t)stride + 3;            // (the last point's padding is not the caller's to give)
-        if (c->d_stage.ensure(c, words)) return DCREG_E_NOMEM;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), normals, sizeof(float) * words, hipMemcpyHostToDevice, c->stream));
-        src = c->d_stage.data();
-    } else if (c->stream == c->own_stream) {       // written on the legacy default stream, most likely: as upload_cloud orders a device cloud
-        if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    }
-    hipLaunchKernelGGL(k_nrm_pack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, src, stride, (const float *)nullptr,
-                       c->gicp.src_normals.data());
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = kept_take(c, normals, n, stride, on_device, c->gicp.src_normals, n, [&](const float *src) {
+            hipLaunchKernelGGL(k_nrm_pack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, src, stride, (const float *)nullptr,
+                               c->gicp.src_normals.data());
+        }))
+        return rc;
     c->gicp.src_kept = true;
     return DCREG_OK;
 }
@@ -814,14 +797,12 @@ int normals_source_get(dcreg_ctx *c, float *out, int64_t capacity, bool on_devic
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (!c->gicp.src_kept) { c->fail("no kept source normals: dcreg_source_normals_keep or dcreg_source_normals_set first"); return DCREG_E_STATE; }
     const int64_t n = c->n_src;
-    if (capacity < n) { c->fail("the source holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (int rc = kept_capacity(c, "the source holds", n, capacity)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->gicp.tmp.ensure(c, (size_t)n)) return DCREG_E_NOMEM;
     hipLaunchKernelGGL(k_nrm_unpack_src, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_src.data(), n, c->gicp.src_normals.data(), c->gicp.tmp.data());
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->gicp.tmp.data(), sizeof(float4) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DCREG_OK;
+    return kept_give(c, out, c->gicp.tmp.data(), n, on_device);
 }
 
 // ------------------------------------------------------------------------------------------ kept normals that follow the map ("normals_follow")
@@ -987,11 +968,9 @@ int normals_get(dcreg_ctx *c, float *out, int64_t capacity, bool on_device) {
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
     if (!c->nicp.kept) { c->fail("no kept normals: dcreg_target_normals_keep or dcreg_target_normals_set first"); return DCREG_E_STATE; }
     const int64_t n = c->roi_active ? c->roi_store.n : c->map.n;
-    if (capacity < n) { c->fail("the map holds %lld points, the capacity is %lld", (long long)n, (long long)capacity); return DCREG_E_INVALID; }
+    if (int rc = kept_capacity(c, "the map holds", n, capacity)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, c->nicp.normals.data(), sizeof(float4) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DCREG_OK;
+    return kept_give(c, out, c->nicp.normals.data(), n, on_device);
 }
 
 }  // namespace

@@ -244,17 +244,9 @@ int outlier_pass(dcreg_ctx *c, const float4 *in, int64_t n, const dcreg_outlier_
         if (!bounded && r.n_finite <= k) {    // no statistics: every used point is kept
             hipLaunchKernelGGL(k_out_keep, dim3(blocks((int64_t)n1, 256)), dim3(256), 0, c->stream, B.score.data(), n, 0.0, 1, used, B.keep.data());
         } else {
-            float bound = 3.0e38f;
-            int max_ring = -1;
-            if (bounded) {
-                bound = (float)(p->search_radius * p->search_radius);
-                if (!(bound <= 3.0e38f)) bound = 3.0e38f;
-                max_ring = rings_for_bound(g, bound);
-            }
-            if (k <= 4) launch_score<4>(c, q, nq, g, bound, max_ring, k, bounded);
-            else if (k <= 8) launch_score<8>(c, q, nq, g, bound, max_ring, k, bounded);
-            else if (k <= 16) launch_score<16>(c, q, nq, g, bound, max_ring, k, bounded);
-            else launch_score<32>(c, q, nq, g, bound, max_ring, k, bounded);
+            const SearchBound s = search_bound(p->search_radius, &g);
+            if (k <= 4) launch_score<4>(c, q, nq, g, s.bound, s.max_ring, k, bounded);
+            else with_heap_k(k, [&](auto K) { launch_score<decltype(K)::value>(c, q, nq, g, s.bound, s.max_ring, k, bounded); });
             HIP_TRY(c, hipGetLastError());
             const double *d_sum = nullptr;
             if (int rc = tree_sum(c, 0, B.score.data(), n, 0.0, &d_sum)) return rc;
@@ -327,7 +319,7 @@ static int outlier_filter_to(dcreg_ctx *c, const float *xyz, int64_t n, int64_t 
     outlier_info(info, r);
     if (int rc = cloud_filter_finish(c, pts.data(), n, B.keep.data(), B.pos.data(), false, r.n_out, capacity, B.out, B.mask, out, mask, on_device)) return rc;
     if (n == 0) return DCREG_OK;
-    if (scores) HIP_TRY(c, hipMemcpyAsync(scores, B.score.data(), sizeof(float) * (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (scores) if (int rc = caller_out(c, scores, B.score.data(), sizeof(float) * (size_t)n, on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;

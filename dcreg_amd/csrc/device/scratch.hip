@@ -10,6 +10,7 @@
 //   scan_u32                                the one rocprim scan of the library: uint32 plus-scan on the context's stream
 //   rings_for_bound                         the rings a grid walk needs to cover a ball
 //   k_fill                                  a float array set to one value
+// and the seam for caller memory: caller_order, caller_rows / caller_in, caller_out
 #include <algorithm>
 
 #include <hip/hip_runtime.h>
@@ -76,6 +77,38 @@ int rings_for_bound(const GridDev &g, float bound) {
     return -1;
 }
 
+SearchBound search_bound(double search_radius, const GridDev *g) {
+    SearchBound s;
+    if (search_radius > 0.0) {
+        s.bound = (float)(search_radius * search_radius);
+        if (!(s.bound <= 3.0e38f)) s.bound = 3.0e38f;
+        if (g) s.max_ring = rings_for_bound(*g, s.bound);
+    }
+    return s;
+}
+
+// The caller most likely wrote its device memory on the legacy default stream (torch's default stream is that stream: cuda_stream == 0), and
+// the context's own stream is non-blocking, so nothing orders it after that stream: make it wait for the work queued there so far.
+// A context given the caller's stream (dcreg_set_stream) is ordered on that stream instead.
+int caller_order(dcreg_ctx *c) {
+    if (c->stream != c->own_stream) return DCREG_OK;
+    if (!c->null_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->null_ev, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->null_ev, nullptr));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    return DCREG_OK;
+}
+
+int caller_in(dcreg_ctx *c, void *stage, const void *src, size_t bytes, bool on_device, bool ordered) {
+    if (on_device) return ordered ? DCREG_OK : caller_order(c);
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(stage, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return DCREG_OK;
+}
+
+int caller_out(dcreg_ctx *c, void *dst, const void *src, size_t bytes, bool on_device) {
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    return DCREG_OK;
+}
+
 void fill_f32(dcreg_ctx *c, float *a, int64_t n, float v) {
     hipLaunchKernelGGL(k_fill, dim3(blocks(n, 256)), dim3(256), 0, c->stream, a, n, v);
 }
@@ -128,9 +161,8 @@ int cloud_filter_finish(dcreg_ctx *c, const float4 *pts, int64_t n, const uint32
     if (out_buf.ensure(c, (size_t)(3 * std::max<int64_t>(n_out, 1))) || (mask && mask_buf.ensure(c, (size_t)n))) return DCREG_E_NOMEM;
     if (scan) if (int rc = scan_u32(c, keep, pos, (size_t)n + 1, false)) return rc;
     if (int rc = cloud_write_kept(c, pts, n, keep, pos, out_buf.data(), nullptr, mask ? mask_buf.data() : nullptr)) return rc;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (n_out > 0) HIP_TRY(c, hipMemcpyAsync(out, out_buf.data(), sizeof(float) * 3 * (size_t)n_out, kind, c->stream));
-    if (mask) HIP_TRY(c, hipMemcpyAsync(mask, mask_buf.data(), (size_t)n, kind, c->stream));
+    if (n_out > 0) if (int rc = caller_out(c, out, out_buf.data(), sizeof(float) * 3 * (size_t)n_out, on_device)) return rc;
+    if (mask) if (int rc = caller_out(c, mask, mask_buf.data(), (size_t)n, on_device)) return rc;
     return DCREG_OK;
 }
 

@@ -237,8 +237,7 @@ int range_images(dcreg_ctx *c, int64_t n, const int64_t *ids, const dcreg_visibi
     size_t done = 0;
     for (size_t b = 0; b + 1 < v.batch.size(); ++b) {
         if (int rc = batch_images(c, v, b)) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out + px * done, c->vis.images.data(), sizeof(float) * px * (size_t)v.n_img[b],
-                                  on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        if (int rc = caller_out(c, out + px * done, c->vis.images.data(), sizeof(float) * px * (size_t)v.n_img[b], on_device)) return rc;
         done += (size_t)v.n_img[b];
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -270,9 +269,8 @@ int filter_to(dcreg_ctx *c, const float *xyz, int64_t n, int64_t stride, bool on
     // (the flags' scan is queued just before the write)
     if (int rc = cloud_filter_finish(c, B.pts.data(), n, B.keep.data(), B.pos.data(), true, r.n_out, capacity, B.out, B.mask, out, mask, on_device)) return rc;
     if (n == 0) return DCREG_OK;
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (through) HIP_TRY(c, hipMemcpyAsync(through, B.through.data(), sizeof(int32_t) * (size_t)n, kind, c->stream));
-    if (observed) HIP_TRY(c, hipMemcpyAsync(observed, B.observed.data(), sizeof(int32_t) * (size_t)n, kind, c->stream));
+    if (through) if (int rc = caller_out(c, through, B.through.data(), sizeof(int32_t) * (size_t)n, on_device)) return rc;
+    if (observed) if (int rc = caller_out(c, observed, B.observed.data(), sizeof(int32_t) * (size_t)n, on_device)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     return DCREG_OK;

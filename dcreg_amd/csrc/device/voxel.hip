@@ -569,8 +569,7 @@ int voxel_downsample_to(dcreg_ctx *c, int n_clouds, const float *xyz, const int6
     if (r.n_out > capacity) { c->fail("the output holds %lld points, the capacity is %lld", (long long)r.n_out, (long long)capacity); return DCREG_E_INVALID; }
     if (r.n_out == 0) return DCREG_OK;
     if (!out) { c->fail("null output buffer"); return DCREG_E_INVALID; }
-    const size_t bytes = sizeof(float) * 3 * (size_t)r.n_out;
-    HIP_TRY(c, hipMemcpyAsync(out, c->vox.out.data(), bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if ((rc = caller_out(c, out, c->vox.out.data(), sizeof(float) * 3 * (size_t)r.n_out, on_device))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCREG_OK;
 }
@@ -1161,16 +1160,17 @@ int pairs_voxels_build(dcreg_ctx *c, int n_t, const float *xyz, const int64_t *o
     if (B.pts.ensure(c, (size_t)n) || B.seg.ensure(c, (size_t)n) || B.rel.ensure(c, (size_t)n) || B.head.ensure(c, (size_t)n) ||
         B.incl.ensure(c, (size_t)n) || B.start.ensure(c, (size_t)n + 1) || B.keep.ensure(c, (size_t)n) || B.pos.ensure(c, (size_t)n) ||
         B.d_off.ensure(c, (size_t)n_t + 1) || B.cnt.ensure(c, nc) || c->d_mkeys.ensure(c, (size_t)n) || c->d_mkeys2.ensure(c, (size_t)n) ||
-        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) || c->d_stage.ensure(c, (size_t)(n * stride)) ||
+        c->d_vals.ensure(c, (size_t)n) || c->d_vals2.ensure(c, (size_t)n) ||
         V.d_words.ensure(c, (size_t)6 * n_t) || V.d_cnt.ensure(c, (size_t)4 * n_t + 2))
         return DCREG_E_NOMEM;
     // ---- upload, pack and float bounds, voxel boxes: one readback
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage.data(), xyz, sizeof(float) * (size_t)(n * stride), hipMemcpyHostToDevice, c->stream));
+    const float *staged = nullptr;
+    if (int rc = caller_rows(c, xyz, n, stride, stride, false, c->d_stage, &staged)) return rc;
     HIP_TRY(c, hipMemcpyAsync(B.d_off.data(), off, sizeof(int64_t) * ((size_t)n_t + 1), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(V.d_words.data(), 0xFF, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
     HIP_TRY(c, hipMemsetAsync(V.d_words.data() + 3 * (size_t)n_t, 0, sizeof(uint32_t) * 3 * (size_t)n_t, c->stream));
     HIP_TRY(c, hipMemsetAsync(V.d_cnt.data(), 0, sizeof(unsigned long long) * (4 * (size_t)n_t + 2), c->stream));     // (+ 2: k_vmap_reduce's own two counts)
-    hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, c->d_stage.data(), n, stride, B.d_off.data(), n_t, B.pts.data(), V.d_words.data());
+    hipLaunchKernelGGL(k_pairs_pack, dim3(blocks(n, 256)), dim3(256), 0, c->stream, staged, n, stride, B.d_off.data(), n_t, B.pts.data(), V.d_words.data());
     hipLaunchKernelGGL(k_vox_init, dim3(blocks((int64_t)nc * 2, kVoxBlock)), dim3(kVoxBlock), 0, c->stream, B.cnt.data(), n_t);
     hipLaunchKernelGGL(k_vox_coords, dim3(blocks(n, kVoxBlock * kVoxPerThread)), dim3(kVoxBlock), 0, c->stream, B.pts.data(), n, B.d_off.data(), n_t, l, l, l,
                        B.seg.data(), B.cnt.data());

@@ -6,7 +6,9 @@ one runtime, and checks that only one is mapped.
   side_stream    a context on a torch side stream (dcreg_set_stream), then back on its own stream: bitwise its own stream's records;
   order_side     a cloud written on the caller's stream behind a long device sleep is read after the write;
   order_default  the same on torch's default stream (the legacy null stream) with the context on its own non-blocking stream - with
-                 and without dcreg_set_stream(0).
+                 and without dcreg_set_stream(0);
+  order_rows     the same for the device inputs that are not clouds - kept normals given from device memory, descriptor rows,
+                 correspondence arrays - on the default stream (both contexts) and on a side stream.
 
 After a child ends abnormally (a signal, or the time limit) no further child is started."""
 import os
@@ -22,7 +24,7 @@ CHILD = os.path.join(HERE, "torch_seam_child.py")
 _abnormal = []
 
 
-@pytest.mark.parametrize("case", ["views", "side_stream", "order_side", "order_default"])
+@pytest.mark.parametrize("case", ["views", "side_stream", "order_side", "order_default", "order_rows"])
 def test_torch_case_in_child(case):
     pytest.importorskip("torch")
     if _abnormal:

@@ -1,6 +1,6 @@
 """Child process of tests/test_gpu_torch_seam.py: torch tensors and torch streams handed to the C-ABI.  One case per process:
 
-    python tests/torch_seam_child.py views | side_stream | order_side | order_default
+    python tests/torch_seam_child.py views | side_stream | order_side | order_default | order_rows
 
 torch is imported and device 0 initialised BEFORE the library is loaded, so that both bind the one HIP runtime already mapped (torch
 bundles its own libamdhip64.so.7); a process that has two of them mapped stops (EXIT_TWO_RUNTIMES) before any pointer or stream reaches
@@ -167,7 +167,128 @@ def ordering(on_side_stream):
         c.close()
 
 
-CASES = {"views": case_views, "side_stream": case_side_stream, "order_side": lambda: ordering(True), "order_default": lambda: ordering(False)}
+def frozen(x):
+    """a result as something == compares bitwise: arrays and floats by their bytes, containers element by element"""
+    if isinstance(x, dict):
+        return tuple((k, frozen(x[k])) for k in sorted(x))
+    if isinstance(x, (list, tuple)):
+        return tuple(frozen(v) for v in x)
+    if isinstance(x, np.ndarray):
+        return (str(x.dtype), x.shape, x.tobytes())
+    if isinstance(x, (float, np.floating)):
+        return np.float64(x).tobytes()
+    return x
+
+
+def case_order_rows():
+    """ordering() for the device inputs that do not pass through upload_cloud - kept normals given from device memory, descriptor rows,
+    correspondence arrays: the tensor holds A, B is copied into it behind ~75 ms of device sleep on the caller's stream with no host
+    synchronise, and the call must answer bitwise what the host form answers for B.  On torch's default stream with a context never
+    given a stream and one after set_stream(0), and on a side stream handed over with set_stream."""
+    rng = np.random.default_rng(11)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    # kept normals: 257 points (two blocks of the pack kernel), stride 4 with a NaN fourth column
+    n = 257
+    tgt = rng.uniform(-5, 5, (n, 3)).astype(np.float32)
+    src = rng.uniform(-5, 5, (n, 3)).astype(np.float32)
+
+    def unit(m):
+        v = rng.normal(size=(m, 3))
+        return (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32)
+    nrm_a, nrm_b = unit(n), unit(n)
+    nrm_b[5] = np.nan                                               # (a point without a normal is kept as given)
+    # descriptor rows: a 65 x 33 at stride 36 (NaN padding), b 64 x 33 at stride 33; one invalid row on either side
+    def rows(m, stride):
+        f = np.full((m, stride), np.nan, np.float32)
+        f[:, :33] = rng.uniform(0, 100, (m, 33)).astype(np.float32)
+        f[m // 2, 7] = np.nan
+        return f
+    fa_a, fa_b, fb_a, fb_b = rows(65, 36), rows(65, 36), rows(64, 33), rows(64, 33)
+    # a rigid scene of 40 points and 40 pairs, 10 of them wrong (B); A: every pair wrong
+    m = 40
+    pa = rng.uniform(-5, 5, (m, 3)).astype(np.float32)
+    T = h.pose6d_matrix(1.0, -2.0, 0.5, 0.1, -0.2, 0.7)
+    pb = (pa.astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+    ca_b = np.arange(m, dtype=np.int32)
+    cb_b = ca_b.copy()
+    cb_b[:10] = np.roll(cb_b[:10], 3)
+    ca_a, cb_a = ca_b[::-1].copy(), np.roll(ca_b, 7)
+    ap, cp = api.align_params(n_hypotheses=4096), api.consensus_params(n_seeds=8)
+
+    # ---- the host forms' answers for B (and for A: the case must be able to tell them apart)
+    hc = api.Context(0)
+    hc.set_target(tgt, 1.0); hc.set_source(src)
+
+    def host(na, fa, fb, ca, cb):
+        hc.set_target_normals(na); hc.set_source_normals(na)
+        al, co = hc.align_correspondences(pa, pb, ca, cb, ap), hc.consensus_correspondences(pa, pb, ca, cb, cp)
+        return dict(target_normals=frozen(hc.kept_target_normals()), source_normals=frozen(hc.kept_source_normals()),
+                    match=frozen(hc.feature_match(fa, fb)), align=frozen(al), consensus=frozen(co))
+    want, other = host(nrm_b, fa_b, fb_b, ca_b, cb_b), host(nrm_a, fa_a, fb_a, ca_a, cb_a)
+    hc.close()
+    for k in want:
+        assert want[k] != other[k], "%s: A and B give one answer: the case proves nothing" % k
+
+    # ---- the device buffers and their late values
+    x = torch.full((n, 4), float("nan"), device="cuda")
+    nv = x[:, :3]
+    assert nv.stride() == (4, 1)
+    f_a, f_b = torch.empty((65, 36), device="cuda"), torch.empty((64, 33), device="cuda")
+    d_ca, d_cb = torch.empty(m, dtype=torch.int32, device="cuda"), torch.empty(m, dtype=torch.int32, device="cuda")
+    d_pa, d_pb = dev(pa), dev(pb)
+    late = dict(nrm=[(nv, dev(nrm_b))], rows=[(f_a, dev(fa_b)), (f_b, dev(fb_b))], corr=[(d_ca, dev(ca_b)), (d_cb, dev(cb_b))])
+    early = dict(nrm=[(nv, dev(nrm_a))], rows=[(f_a, dev(fa_a)), (f_b, dev(fb_a))], corr=[(d_ca, dev(ca_a)), (d_cb, dev(cb_a))])
+    o_idx, o_idx2 = torch.empty(65, dtype=torch.int32, device="cuda"), torch.empty(65, dtype=torch.int32, device="cuda")
+    o_d, o_d2 = torch.empty(65, dtype=torch.float64, device="cuda"), torch.empty(65, dtype=torch.float64, device="cuda")
+    o_mut, o_mask = torch.empty(65, dtype=torch.uint8, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda")
+    host_of = lambda t: t.cpu().numpy()
+    cycles = sleep_cycles(75.0)
+
+    def call_normals(c, which):
+        getattr(c, "set_%s_normals" % which)(dev_ptr=nv.data_ptr(), n=n, stride=4)
+        return frozen(getattr(c, "kept_%s_normals" % which)())
+
+    def call_match(c):
+        info = c.feature_match_device(f_a.data_ptr(), 65, 36, f_b.data_ptr(), 64, 33, o_idx.data_ptr(), o_d.data_ptr(), o_idx2.data_ptr(), o_d2.data_ptr(),
+                                      o_mut.data_ptr())
+        return frozen(dict(info, idx=host_of(o_idx), d=host_of(o_d), idx2=host_of(o_idx2), d2=host_of(o_d2), mutual=host_of(o_mut)))
+
+    def call_corr(c, which, params):
+        r = getattr(c, which + "_correspondences_device")(d_pa.data_ptr(), m, 3, d_pb.data_ptr(), m, 3, d_ca.data_ptr(), d_cb.data_ptr(), m, params,
+                                                          dev_mask=o_mask.data_ptr())
+        return frozen(dict(r, mask=host_of(o_mask)))
+    calls = [("target_normals", "nrm", lambda c: call_normals(c, "target")), ("source_normals", "nrm", lambda c: call_normals(c, "source")),
+             ("match", "rows", call_match), ("align", "corr", lambda c: call_corr(c, "align", ap)),
+             ("consensus", "corr", lambda c: call_corr(c, "consensus", cp))]
+
+    assert torch.cuda.current_stream().cuda_stream == 0
+    side = torch.cuda.Stream()
+    assert side.cuda_stream != 0
+    for name, S, stream_arg in (("never given a stream", torch.cuda.current_stream(), None), ("after set_stream(0)", torch.cuda.current_stream(), 0),
+                                ("on a side stream", side, side.cuda_stream)):
+        c = api.Context(0)
+        if stream_arg is not None:
+            c.set_stream(stream_arg)
+        c.set_target(tgt, 1.0); c.set_source(src)
+        for key, inputs, call in calls:
+            for buf, val in early[inputs]:
+                buf.copy_(val)
+            torch.cuda.synchronize()
+            ev = torch.cuda.Event()
+            with torch.cuda.stream(S):
+                torch.cuda._sleep(cycles)
+                for buf, val in late[inputs]:
+                    buf.copy_(val)
+                ev.record(S)
+            assert not ev.query(), "the copy finished before the call: the case proves nothing"
+            got = call(c)
+            assert got == want[key], "%s, context %s: the call did not read what was written before it" % (key, name)
+            torch.cuda.synchronize()
+        c.close()
+
+
+CASES = {"views": case_views, "side_stream": case_side_stream, "order_side": lambda: ordering(True), "order_default": lambda: ordering(False),
+         "order_rows": case_order_rows}
 
 if __name__ == "__main__":
     CASES[sys.argv[1]]()
