@@ -219,6 +219,7 @@ EXPORTS = [
     "dcreg_fpfh_radius_debug_counts",
     "dcreg_default_align_params", "dcreg_align_correspondences", "dcreg_align_correspondences_device",
     "dcreg_default_consensus_params", "dcreg_consensus_correspondences", "dcreg_consensus_correspondences_device",
+    "dcreg_default_verify_params", "dcreg_verify_poses", "dcreg_verify_poses_cloud", "dcreg_verify_poses_cloud_device",
 ]
 
 _lib = None
@@ -999,6 +1000,85 @@ def _consensus_records(recs, n):
              "count": r.count, "cost": r.cost, "n_inliers": r.n_inliers, "refined": r.refined, "rmse": r.rmse} for r in recs[:n]]
 
 
+class VerifyParams(C.Structure):
+    _fields_ = [("inlier_distance", C.c_double), ("point_stride", C.c_int64), ("rank_by", C.c_int32), ("detail_pose", C.c_int32),
+                ("reserved_", C.c_double * 2)]
+
+
+class VerifyRecord(C.Structure):
+    _fields_ = [("pose", C.c_int32), ("count", C.c_int32), ("cost", C.c_uint64), ("score", C.c_uint64), ("fitness", C.c_double),
+                ("rmse", C.c_double)]
+
+
+class VerifyInfo(C.Structure):
+    _fields_ = [("n_poses", C.c_int64), ("n_points", C.c_int64), ("n_scored", C.c_int64), ("best_pose", C.c_int64), ("reserved_", C.c_int64 * 2)]
+
+
+_STRUCTS.update({"dcreg_verify_params": VerifyParams, "dcreg_verify_record": VerifyRecord, "dcreg_verify_info": VerifyInfo})
+VERIFY_MAX_POSES, VERIFY_RECORD_STRIDE = 65535, 22      # (22 doubles: the size of an align or consensus record, whose T leads it)
+
+
+def _check_verify_params(p, what):
+    """the refusals of include/dcreg.h for a dcreg_verify_params block (detail_pose against the poses: _verify_poses)"""
+    if not isinstance(p, VerifyParams):
+        raise ValueError("%s: verify_params(...) is expected, got %s" % (what, type(p).__name__))
+    if not (np.isfinite(p.inlier_distance) and p.inlier_distance > 0.0):
+        raise ValueError("%s: a finite inlier_distance > 0 is expected, got %r" % (what, p.inlier_distance))
+    if p.point_stride < 1:
+        raise ValueError("%s: point_stride >= 1 is expected, got %d" % (what, p.point_stride))
+    if p.rank_by not in (0, 1):
+        raise ValueError("%s: rank_by 0 (count, cost) or 1 (score) is expected, got %d" % (what, p.rank_by))
+    if p.detail_pose < -1:
+        raise ValueError("%s: detail_pose -1 (none) or an input index is expected, got %d" % (what, p.detail_pose))
+
+
+def verify_params(inlier_distance=0.5, point_stride=1, rank_by=0, detail_pose=-1):
+    """dcreg_verify_params: the inlier distance d in metres (a point counts when a map point lies strictly inside it), every
+    point_stride-th point of the cloud by original index, the ranking key - 0: (count descending, cost ascending), the align records'
+    key; 1: the MSAC score ascending - and the input index of the pose whose inlier mask and neighbours are wanted (-1: none);
+    include/dcreg.h has the rule"""
+    p = VerifyParams()
+    p.inlier_distance = float(inlier_distance)
+    p.point_stride = int(point_stride)
+    p.rank_by = int(rank_by)
+    p.detail_pose = int(detail_pose)
+    _check_verify_params(p, "verify_params")
+    return p
+
+
+def _verify_poses(Ts, p, what):
+    """the poses of a verify call - [P, 4, 4], or a list of record dicts with a T - as a contiguous [P, 16] block, checked as the C-ABI
+    checks them"""
+    if isinstance(Ts, (list, tuple)) and len(Ts) and isinstance(Ts[0], dict):
+        Ts = [r["T"] for r in Ts]
+    Ts = np.ascontiguousarray(Ts, dtype=np.float64)
+    if Ts.size == 0:
+        Ts = Ts.reshape(0, 4, 4)
+    if Ts.ndim != 3 or Ts.shape[1:] != (4, 4):
+        raise ValueError("%s: poses of shape [P, 4, 4] are expected, got %s" % (what, (Ts.shape,)))
+    n = Ts.shape[0]
+    if n > VERIFY_MAX_POSES:
+        raise ValueError("%s: at most %d poses are expected, got %d" % (what, VERIFY_MAX_POSES, n))
+    if p.detail_pose >= n:
+        raise ValueError("%s: detail_pose in [-1, %d] is expected, got %d" % (what, n - 1, p.detail_pose))
+    top = Ts[:, :3, :]
+    bad = np.flatnonzero(~np.isfinite(top).all(axis=(1, 2)))
+    if len(bad):
+        raise ValueError("%s: pose %d has a non-finite entry" % (what, bad[0]))
+    bad = np.flatnonzero(~_rotations_ok(top[:, :, :3]))
+    if len(bad):
+        raise ValueError("%s: the rotation block of pose %d is not a rotation (|R^T R - I| > 1e-6 or det <= 0)" % (what, bad[0]))
+    return Ts.reshape(n, 16), n
+
+
+def _verify_info_dict(i):
+    return {k: getattr(i, k) for k in ("n_poses", "n_points", "n_scored", "best_pose")}
+
+
+def _verify_records(recs, n):
+    return [{"pose": r.pose, "count": r.count, "cost": r.cost, "score": r.score, "fitness": r.fitness, "rmse": r.rmse} for r in recs[:n]]
+
+
 def _check_voxel_map_params(p, what):
     """the refusals of include/dcreg.h for a dcreg_voxel_map_params block"""
     if not isinstance(p, VoxelMapParams):
@@ -1514,6 +1594,12 @@ def load():
         for name in ("dcreg_consensus_correspondences", "dcreg_consensus_correspondences_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.POINTER(ConsensusParams),
                                          C.POINTER(ConsensusRecord), vp, vp, vp, vp, C.POINTER(ConsensusInfo)]
+    if hasattr(L, "dcreg_verify_poses"):  # (likewise)
+        vpp, vrp, vip = C.POINTER(VerifyParams), C.POINTER(VerifyRecord), C.POINTER(VerifyInfo)
+        L.dcreg_default_verify_params.argtypes = [vpp]
+        L.dcreg_verify_poses.argtypes = [vp, vp, C.c_int64, C.c_int64, vpp, vrp, vp, vp, vip]
+        for name in ("dcreg_verify_poses_cloud", "dcreg_verify_poses_cloud_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vpp, vrp, vp, vp, vip]
     L.dcreg_p2p_error.argtypes = [vp, dp, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
     L.dcreg_trial_pose.argtypes = [dp, C.c_uint64, C.c_int64, C.c_double, C.c_double, dp, dp]
     L.dcreg_set_host_threads.argtypes = [C.c_int]
@@ -2549,6 +2635,57 @@ class Context:
                                                                    C.c_void_p(dev_degree or None), C.c_void_p(dev_weight or None), C.byref(info)),
                     "dcreg_consensus_correspondences_device")
         return {"records": _consensus_records(recs, info.n_returned), "info": _consensus_info_dict(info)}
+
+    # ---- candidate poses scored against the map (include/dcreg.h: dcreg_verify_poses)
+    def verify_poses(self, Ts, params=None, cloud=None, want_detail=False):
+        """dcreg_verify_poses / dcreg_verify_poses_cloud: P candidate poses of one cloud scored against the resident map in one launch -
+        per pose the points with a map point strictly inside the inlier distance and an integer cost of their distances (include/dcreg.h
+        has the rule).  Ts: [P, 4, 4] poses, or the record dicts of align_correspondences / consensus_correspondences (their T is
+        taken); cloud: None = the resident source, else an [n, c] float32 cloud (x y z first, non-finite rows skipped) - the resident
+        source is then neither read nor changed; params: verify_params(...), None = the defaults.  -> dict records (ALL poses, best
+        first: pose - the input index -, count, cost, score, fitness, rmse), order (the ranked input indices: Ts[order[0]] is a start
+        pose as icp_run* and icp_run_trials* take it), info (n_poses, n_points, n_scored, best_pose); with want_detail (params.detail_pose
+        names the pose): mask [n] uint8 and nn [n] int32 in the cloud's original order"""
+        p = params if params is not None else verify_params()
+        _check_verify_params(p, "verify_poses")
+        T16, n_poses = _verify_poses(Ts, p, "verify_poses")
+        if want_detail and p.detail_pose < 0:
+            raise ValueError("verify_poses: want_detail needs a detail_pose in the parameters, got %d" % p.detail_pose)
+        pts = _points(cloud, "verify_poses") if cloud is not None else None
+        recs = (VerifyRecord * max(n_poses, 1))()
+        info = VerifyInfo()
+        n = pts.shape[0] if pts is not None else (int(self.index_info().n_source) if want_detail else 0)
+        mask = np.zeros(max(n, 1), np.uint8) if want_detail else None
+        nn = np.full(max(n, 1), -1, np.int32) if want_detail else None
+        ptr = lambda x: x.ctypes.data if x is not None else None
+        tail = (T16.ctypes.data, n_poses, 16, C.byref(p), recs, ptr(mask), ptr(nn), C.byref(info))
+        if pts is None:
+            self._check(self._L.dcreg_verify_poses(self._h, *tail), "dcreg_verify_poses")
+        else:
+            self._check(self._L.dcreg_verify_poses_cloud(self._h, pts.ctypes.data, pts.shape[0], pts.shape[1], *tail), "dcreg_verify_poses_cloud")
+        out = {"records": _verify_records(recs, info.n_poses), "info": _verify_info_dict(info)}
+        out["order"] = [r["pose"] for r in out["records"]]
+        if want_detail:
+            out["mask"], out["nn"] = mask[:n], nn[:n]
+        return out
+
+    def verify_poses_device(self, dev_ptr, n, stride, Ts, params=None, dev_mask=0, dev_nn=0):
+        """dcreg_verify_poses_cloud_device: the cloud (n rows of `stride` floats) and the detail outputs wanted (0: not wanted; n bytes
+        / n int32, written for params.detail_pose) in device memory.  -> dict records / order / info, as verify_poses"""
+        p = params if params is not None else verify_params()
+        _check_verify_params(p, "verify_poses_device")
+        _check_device_cloud(n, stride, "verify_poses_device")
+        if int(n) > 0 and not dev_ptr:
+            raise ValueError("verify_poses_device: a cloud pointer is expected")
+        T16, n_poses = _verify_poses(Ts, p, "verify_poses_device")
+        recs = (VerifyRecord * max(n_poses, 1))()
+        info = VerifyInfo()
+        self._check(self._L.dcreg_verify_poses_cloud_device(self._h, C.c_void_p(dev_ptr or None), int(n), int(stride), T16.ctypes.data, n_poses, 16,
+                                                            C.byref(p), recs, C.c_void_p(dev_mask or None), C.c_void_p(dev_nn or None), C.byref(info)),
+                    "dcreg_verify_poses_cloud_device")
+        out = {"records": _verify_records(recs, info.n_poses), "info": _verify_info_dict(info)}
+        out["order"] = [r["pose"] for r in out["records"]]
+        return out
 
     # ---- kept normals and the second engine (include/dcreg.h: dcreg_target_normals_keep .. dcreg_icp_run_normals)
     def keep_target_normals(self, params=None):

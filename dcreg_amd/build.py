@@ -34,11 +34,12 @@ SOURCES = [
     "device/features.hip",
     "device/align.hip",
     "device/consensus.hip",
+    "device/verify.hip",
     "host/solver.cpp",
     "host/align_host.cpp",
     "host/engine.cpp",
 ]
-HEADERS = ["device/kernels.hpp", "device/search.hpp", "device/context.hpp", "device/normal_icp.hpp", "device/gicp.hpp", "device/voxel_icp.hpp", "device/jacobi.hpp", "device/heap_nrm.hpp", "device/align.hpp", "host/linalg.hpp", "host/se3.hpp",
+HEADERS = ["device/kernels.hpp", "device/search.hpp", "device/context.hpp", "device/normal_icp.hpp", "device/gicp.hpp", "device/voxel_icp.hpp", "device/jacobi.hpp", "device/heap_nrm.hpp", "device/align.hpp", "device/verify.hpp", "host/linalg.hpp", "host/se3.hpp",
            "../../include/dcreg_debug.h", "../../include/dcreg.h"]
 
 

@@ -2414,6 +2414,7 @@ int dcreg_set_option(dcreg_ctx *c, const char *key, double v) {
     }
     else if (k == "feature_match_split") c->opt_feature_match_split = (int64_t)std::min(std::max(v, 0.0), 2147483647.0);   // dcreg_feature_match: rows of b per block column (0: from the sizes; no result depends on it)
     else if (k == "align_score_split") c->opt_align_score_split = (int64_t)std::min(std::max(v, 0.0), 2147483647.0);   // dcreg_align_correspondences: used pairs per block column of k_align_score (0: from the sizes; no result depends on it)
+    else if (k == "verify_poses_per_launch") c->opt_verify_poses_per_launch = (int64_t)std::min(std::max(v, 0.0), 65535.0);   // dcreg_verify_poses*: poses per launch of k_verify (0: all; no result depends on it)
     else if (k == "map_grow_margin") c->opt_map_grow_margin = std::min(std::max(v, 0.0), 1.0e4);   // metres around the map when an update re-derives the grid
     else { c->fail("unknown option '%s'", key); return DCREG_E_INVALID; }
     return DCREG_OK;

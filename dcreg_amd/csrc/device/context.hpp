@@ -766,6 +766,22 @@ struct dcreg_ctx {
     };
     ConsensusBufs cons;
 
+    // Verification of candidate poses (verify.hip: dcreg_verify_poses*).  Scratch of one call, kept for the next, and nothing any other
+    // call reads: the cloud form's rows as uploaded, the selection flags and their exclusive scan (n + 1 entries, the last flag 0), the
+    // selected points compacted (w = the original index), the pose table (12 doubles per pose), the sums {count, cost} per pose, and the
+    // detail pose's mask and nn by original index.
+    struct VerifyBufs {
+        DevBuf<float> rows;
+        DevBuf<uint32_t> flag, pos;
+        DevBuf<float4> sel;
+        DevBuf<double> poses;
+        DevBuf<unsigned long long> acc;
+        DevBuf<uint8_t> mask;
+        DevBuf<int32_t> nn;
+    };
+    VerifyBufs verify;
+    int64_t opt_verify_poses_per_launch = 0;                  // "verify_poses_per_launch": poses per launch of k_verify (0: all of them; tests)
+
     void fail(const char *fmt, ...);
 };
 
@@ -898,6 +914,17 @@ inline void lin_out_of_row(const double *row, dcreg_lin_out &o) {
     o.n_eff = (int64_t)std::llround(row[29]); o.n_pt = (int64_t)std::llround(row[30]);
 }
 int roi_deactivate(dcreg_ctx *c);      // context.hip: make the whole map's index the active one (entry points that are not single-pose linearisations)
+// the rule of the deskew calls (deskew.hip is_rotation) on the rotation block of a row-major 4x4: what dcreg_p2p_error and
+// dcreg_verify_poses* refuse a pose by
+inline bool rigid_rotation(const double T[16]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double g = T[i] * T[j] + T[4 + i] * T[4 + j] + T[8 + i] * T[8 + j] - (i == j ? 1.0 : 0.0);   // (R^T R - I)_ij
+            if (!(std::fabs(g) <= 1e-6)) return false;
+        }
+    const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
+    return det > 0.0;
+}
 // align.hip: step 1 of the alignment rule for both correspondence calls - both clouds and both index arrays through caller_rows (the host
 // form's staged in c->algn.a / b / ca / cb, the device form's ordered once), k_align_valid, the scan and k_align_gather into c->algn.P /
 // m_of_u - and the number of used pairs, read back behind a stream synchronisation.  n_pairs > 0

@@ -24,17 +24,6 @@ namespace dcreg {
 int build_aux_index(dcreg_ctx *c);   // context.hip
 }
 
-// the rule of the deskew calls (deskew.hip is_rotation) on the rotation block of a row-major 4x4
-static bool rigid_rotation(const double T[16]) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double g = T[i] * T[j] + T[4 + i] * T[4 + j] + T[8 + i] * T[8 + j] - (i == j ? 1.0 : 0.0);   // (R^T R - I)_ij
-            if (!(std::fabs(g) <= 1e-6)) return false;
-        }
-    const double det = T[0] * (T[5] * T[10] - T[6] * T[9]) - T[1] * (T[4] * T[10] - T[6] * T[8]) + T[2] * (T[4] * T[9] - T[5] * T[8]);
-    return det > 0.0;
-}
-
 static int reduce_p2p(dcreg_ctx *c, const float *d_d2, int64_t n, double thr, double out[3]) {
     const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
     if (c->d_p2p_part.ensure(c, (size_t)nb * 4)) return DCREG_E_NOMEM;

@@ -1053,6 +1053,9 @@ size_t dcreg_sizeof(const char *name) {
     if (!std::strcmp(name, "dcreg_consensus_params")) return sizeof(dcreg_consensus_params);
     if (!std::strcmp(name, "dcreg_consensus_record")) return sizeof(dcreg_consensus_record);
     if (!std::strcmp(name, "dcreg_consensus_info")) return sizeof(dcreg_consensus_info);
+    if (!std::strcmp(name, "dcreg_verify_params")) return sizeof(dcreg_verify_params);
+    if (!std::strcmp(name, "dcreg_verify_record")) return sizeof(dcreg_verify_record);
+    if (!std::strcmp(name, "dcreg_verify_info")) return sizeof(dcreg_verify_info);
     return 0;
 }
 

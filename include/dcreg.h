@@ -52,6 +52,7 @@
  *       nearest and second-nearest rows in feature space, mutual flags           -> dcreg_feature_match[_device]
  *       the pose most point pairs agree on (seeded RANSAC), the best T as start poses -> dcreg_align_correspondences[_device]
  *       ... at inlier shares of a per cent: a compatibility graph's consensus sets -> dcreg_consensus_correspondences[_device]
+ *       candidate poses scored against the map: inlier count and integer cost, ranked -> dcreg_verify_poses, dcreg_verify_poses_cloud[_device]
  *
  * Conventions: plain pointers and sizes only; the caller owns host buffers (borrowed for the call);
  * a ctx owns its device memory, stream and events; return 0 = ok, <0 = error; a ctx is
@@ -1965,6 +1966,82 @@ int dcreg_consensus_correspondences_device(dcreg_ctx *, const float *d_a_xyz, in
                                            const dcreg_consensus_params *, dcreg_consensus_record *records_out, uint8_t *d_inlier_mask_out,
                                            int32_t *d_members_out, uint32_t *d_degree_out, uint32_t *d_weight_out,
                                            dcreg_consensus_info *info);
+
+/* ---------------- Verification of candidate poses against the map ----------------
+ * The stage behind the two calls above (PCL SampleConsensusPrerejective's scoring against the cloud, Open3D evaluate_registration): P
+ * candidate poses of ONE cloud are scored against the resident map in one launch - per pose the number of cloud points with a map point
+ * strictly inside the inlier distance, and an integer cost of their distances.  The poses of dcreg_align_correspondences,
+ * dcreg_consensus_correspondences, a register_frames result or a place-recognition guess go in as they are; the best of the ranked
+ * records feed every T0 / T0s argument of the engines.  Counts and costs are integers: the records are BITWISE the numpy reference of
+ * tests/verify_ref.py and do not depend on how the work is split over blocks or launches.
+ *
+ * Inputs: the poses T_k, k = 0 .. P - 1 (row-major 4x4 at T + k * pose_stride_doubles; the bottom row is ignored), a cloud, and
+ * d = inlier_distance, s = point_stride, rank_by, detail_pose.
+ * 1. Points.  The resident form takes the source as dcreg_set_source* holds it, original indices i = 0 .. n - 1 (all finite).  The
+ *    cloud forms take n rows of a caller's cloud; row i is USED when its three coordinates are finite.  Row i is SELECTED when
+ *    i % s == 0 - the stride is taken on the original index, before the finiteness test.  n_scored = the selected used points.
+ * 2. Transform (the engines' body_to_global): per coordinate a, ((R_a0 * px + R_a1 * py) + R_a2 * pz) + t_a in double, every operation
+ *    rounded once, nothing contracted; the result is stored as float32.  A transformed point with a non-finite coordinate is not an
+ *    inlier of that pose.
+ * 3. Nearest map point: d2 = (dx * dx + dy * dy) + dz * dz in float32, as dcreg_knn computes it; j = the map point of the smallest
+ *    (d2, original index) over the WHOLE resident map (the call makes the whole map's index the active one, as the metrics do).
+ * 4. Inlier iff (double)d2 < dd, dd = d * d in double - STRICT, the search's convention, not the `<=` of the align rule.  Its term:
+ *    e = (uint64) floor(((double)d2 / dd) * 1048576.0), at most 2^20 - 1.
+ * 5. Sums: count_k = the inliers, cost_k = the sum of their e, score_k = cost_k + (n_scored - count_k) * 1048576 - an MSAC score:
+ *    every outlier pays the full 2^20.  Integers all three: no order of summation is part of the rule.
+ * 6. Derived: fitness_k = (double)count_k / (double)n_scored (0.0 when n_scored is 0); rmse_k = sqrt((((double)cost_k / 1048576.0) * dd)
+ *    / (double)count_k) (0.0 when count_k is 0).  rmse_k is the FLOOR-QUANTISED value: its square lies at most dd * 2^-20 below the mean
+ *    of the inliers' float d2 (each term loses less than one unit of 2^-20 dd), and never above it but for the rounding of these four
+ *    double operations.
+ * 7. Rank.  rank_by = 0: (count descending, cost ascending, k ascending) - the key of the align and consensus records.  rank_by = 1:
+ *    (score ascending, count descending, k ascending).  All P records come back, best first, each with its input index k in `pose`.
+ * 8. Detail of one pose: detail_pose = an input index k, or -1 for none.  mask_out[i] = 1 where point i is an inlier of that pose, 0
+ *    elsewhere (rows that are not selected or not used included); nn_out[i] = j for an inlier, -1 elsewhere - n entries each, in the
+ *    cloud's original order.  Either may be null; both are left alone when detail_pose is -1.
+ *
+ * dcreg_verify_poses scores the resident source.  dcreg_verify_poses_cloud / _cloud_device score a caller's cloud (xyz, n,
+ * stride_floats) in host / device memory - the device form also takes device pointers for mask_out and nn_out - and neither read nor
+ * change the resident source.  With pose_stride_doubles = 22 the T of an array of dcreg_align_record or dcreg_consensus_record - 176
+ * bytes each - is read in place.  The calls wait for the stream, keep nothing from one call to the next but scratch memory, touch no
+ * warm state, no kept normals or voxels and no source ordering; the whole map's index becomes the active one.  One launch scores all
+ * poses: block (x, k) takes 256 selected points at pose k; with s > 1 the selected points are compacted first.  "verify_poses_per_launch"
+ * (0 = all; a test option) splits the poses over several launches; no result depends on it.
+ * DCREG_E_INVALID, before anything is queued and with records, detail outputs and info untouched: a null context, parameters or records;
+ * n_poses outside 0 .. 65535 (0 returns DCREG_OK with a zero info); a null T with n_poses > 0; pose_stride_doubles < 16; an
+ * inlier_distance that is not finite or not > 0; point_stride < 1; rank_by outside 0 and 1; detail_pose outside -1 .. n_poses - 1; a
+ * cloud stride below 3, a negative n, more than 2^31 - 1 points, a null cloud with n > 0; a pose with a non-finite entry in its top
+ * three rows or whose rotation block is no rotation (|R^T R - I| > 1e-6 in an entry, or det <= 0: the rule of dcreg_p2p_error) - the
+ * message names the pose's index.  DCREG_E_STATE: a linearisation in flight; no map; the resident form without a source. */
+typedef struct dcreg_verify_params {
+    double inlier_distance;    /* d > 0, metres */
+    int64_t point_stride;      /* s >= 1: every s-th point of the cloud, by original index */
+    int32_t rank_by;           /* 0: (count desc, cost asc, k asc); 1: (score asc, count desc, k asc) */
+    int32_t detail_pose;       /* the input index whose mask / nn are written, -1: none */
+    double reserved_[2];
+} dcreg_verify_params;
+typedef struct dcreg_verify_record {   /* one per pose, best first */
+    int32_t pose;              /* k: the input index */
+    int32_t count;             /* inliers */
+    uint64_t cost;             /* sum of the inliers' terms */
+    uint64_t score;            /* cost + (n_scored - count) * 2^20 */
+    double fitness;            /* count / n_scored */
+    double rmse;               /* floor-quantised, see step 6 */
+} dcreg_verify_record;
+typedef struct dcreg_verify_info {
+    int64_t n_poses, n_points, n_scored, best_pose;   /* best_pose: records_out[0].pose (0 in the zero info of a call without poses) */
+    int64_t reserved_[2];
+} dcreg_verify_info;
+#define DCREG_VERIFY_MAX_POSES 65535
+/* d = 0.5, stride 1, rank_by 0, detail_pose -1 */
+int dcreg_default_verify_params(dcreg_verify_params *);
+int dcreg_verify_poses(dcreg_ctx *, const double *T, int64_t n_poses, int64_t pose_stride_doubles, const dcreg_verify_params *,
+                       dcreg_verify_record *records_out, uint8_t *mask_out, int32_t *nn_out, dcreg_verify_info *info);
+int dcreg_verify_poses_cloud(dcreg_ctx *, const float *xyz, int64_t n, int64_t stride_floats, const double *T, int64_t n_poses,
+                             int64_t pose_stride_doubles, const dcreg_verify_params *, dcreg_verify_record *records_out, uint8_t *mask_out,
+                             int32_t *nn_out, dcreg_verify_info *info);
+int dcreg_verify_poses_cloud_device(dcreg_ctx *, const float *d_xyz, int64_t n, int64_t stride_floats, const double *T, int64_t n_poses,
+                                    int64_t pose_stride_doubles, const dcreg_verify_params *, dcreg_verify_record *records_out,
+                                    uint8_t *d_mask_out, int32_t *d_nn_out, dcreg_verify_info *info);
 
 size_t dcreg_sizeof(const char *struct_name);
 const char *dcreg_version(void);
